@@ -13,11 +13,16 @@ no data-path collective other than that final gather (weak scaling: per-GPU work
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W        # or under an external launcher
   python bench.py --gpus 8 --config c4              # BASELINE configs[3]: 8192 pages sharded over the ranks + RCCL gather
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full                   # + every leg behind the headline (see below)
+  python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR       # + the last timed step's results as DIR/*.npy
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the MFMA prefilter launch with the
-most work), timed live with HIP events on the stream it runs on; `cpu_baseline` times the reference's
-own AVX2 kernel (oracle/_ref, kind "reference") or, if that artefact is absent, the CPU restatement
-(kind "port") on a bounded sample of the same pages on the host cores.
+most work), timed live with HIP events on the stream it runs on.  A plain run sets up, warms up, times
+--steps steps and prints the line; `--full` adds the legs that take runs of their own: the PCIe-inclusive
+pipelined rate, the dominant kernel alone on the chip (`frac_isolated`), `cpu_baseline` (the reference's
+own AVX2 kernel, oracle/_ref, kind "reference", or, if that artefact is absent, the CPU restatement, kind
+"port", on a bounded sample of the same pages on the host cores), the parity check of page 0 against the
+committed golden lists, and the configs[2] / stream workloads (`c3_value`, `c4_stream_value`).
 """
 import argparse
 import json
@@ -73,6 +78,50 @@ def effective_cpus():
     except (OSError, ValueError):
         pass
     return n
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_SEED = 20251015
+
+
+def dump_outputs(sc, out_dir):
+    """--dump-outputs: what a caller of the timed path receives for one batch, read back from the context that ran the last timed
+    step — the raw match lists (Scanner.counts / matches) and the post-processed lines (Scanner.lines) — as float arrays:
+      counts          (pages, templates) float64   raw matches per page and template (the segments of `matches`, in order)
+      matches         (n, 3) float32               x, y, similarity of every raw match in (page, template, y, x) order
+      lines_per_page  (pages,) float64             lines of each page
+      chars_per_line  (lines,) float64             characters of each line, pages in order
+      chars           (n_chars, 7) float32         x, y, w, h, similarity, letter, template_index of every character, line by line
+    (every integer field is below 2^24, so float32 holds it exactly).  Arrays above their share of DUMP_BUDGET_BYTES keep a sample of
+    their rows drawn with DUMP_SEED, in order; the sample depends only on the array's length.  Returns {name: [rows written, rows]}."""
+    from font_ocr_amd.bank import HIT_DTYPE
+
+    counts = sc.counts()
+    _, m = sc.matches()
+    pages_ = sc.lines()
+    lines_ = [ln for p_ in pages_ for ln in p_]
+    chars = np.concatenate(lines_) if lines_ else np.zeros(0, HIT_DTYPE)
+    arrays = {
+        "counts": counts.astype(np.float64),
+        "matches": np.stack([m["x"], m["y"], m["similarity"]], axis=1).astype(np.float32),
+        "lines_per_page": np.array([len(p_) for p_ in pages_], np.float64),
+        "chars_per_line": np.array([len(ln) for ln in lines_], np.float64),
+        "chars": np.stack([chars[f] for f in HIT_DTYPE.names], axis=1).astype(np.float32),
+    }
+    rows = {k: len(a) for k, a in arrays.items()}
+    left = DUMP_BUDGET_BYTES - 4096 * len(arrays)  # room for the .npy headers
+    names = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, k in enumerate(names):  # smallest first: each array gets at most an equal share of what the smaller ones left
+        a = arrays[k]
+        share = left // (len(names) - i)
+        if a.nbytes > share:
+            keep = share // (a.nbytes // len(a))
+            arrays[k] = a[np.sort(np.random.default_rng(DUMP_SEED).choice(len(a), keep, replace=False))]
+        left -= arrays[k].nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: [len(arrays[k]), rows[k]] for k in arrays}
 
 
 def self_launch(args):
@@ -304,6 +353,13 @@ def main():
     ap.add_argument("--inject-stall-ms", type=float, default=0.0,
                     help="self-test of the executor's tolerance: the submitting thread sleeps this long every --inject-stall-every timed steps")
     ap.add_argument("--inject-stall-every", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg behind the headline figure: the PCIe-inclusive pipelined rate, the dominant kernel alone, the CPU "
+                         "baseline, the parity check against the golden lists and the configs[2] / stream workloads (each still subject to its "
+                         "--no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the results of the last timed step (rank 0's last batch) as DIR/<name>.npy in float32 / "
+                         "float64, at most 64 MB in all (larger arrays: a fixed, seeded sample of their rows)")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -530,13 +586,15 @@ def main():
     n_chars = 0
     timed = False
     ticket_log = []  # focr_pipe_ticket_times of every batch retired inside the timed region
+    last_ctx = None  # the context of the newest retired batch: after the timed region, the last timed step's (--dump-outputs)
 
     def retire():
         """Consume the oldest step in flight: its results stay on the device; with several ranks they are gathered."""
-        nonlocal n_chars
+        nonlocal n_chars, last_ctx
         t = jobs.popleft()
         t_w = time.perf_counter()
         c_ = pipe.wait(t)
+        last_ctx = c_
         main_dbg[0] += time.perf_counter() - t_w
         stamp("main", f"wait ticket {t}", t_w, time.perf_counter())
         t_r = time.perf_counter()
@@ -689,6 +747,9 @@ def main():
     # what the size estimates did during the timed region: the bench rescans the same resident batches every step, so the
     # estimates are at their best case (smallest margin, nothing redone); --config c4 streams different batches
     est = [c_.size_estimate_stats() for c_ in scs]
+    if args.dump_outputs and rank == 0:  # before any later leg reuses the context
+        dumped = dump_outputs(last_ctx, args.dump_outputs)
+        print(f"[bench] --dump-outputs: {', '.join(f'{k} {w} of {n} rows' for k, (w, n) in dumped.items())} -> {args.dump_outputs}", file=sys.stderr)
     e2e = e2e_pipe = None
     e2e_steps = 0
     if args.with_upload and shard is None:  # PCIe-inclusive, pageable host memory, upload and scan back to back on one context
@@ -745,7 +806,7 @@ def main():
             pin.close()
         return rate, n_steps
 
-    if not args.no_e2e and shard is None and not use_dist:
+    if args.full and not args.no_e2e and shard is None and not use_dist:
         try:
             e2e_pipe, e2e_steps = measure_e2e()
         except Exception as e:  # noqa: BLE001 - reported in the line; the device-resident measurement stands
@@ -756,7 +817,7 @@ def main():
     # the dominant kernel alone on the chip (no other batch in flight, all CUs): a short extra leg outside the timed
     # region, reported beside the in-flight figure so that both ways of reading "kernel duration" are on the table
     iso = {}
-    if rank == 0 and n_lanes > 1 and not leg_errors:  # (a failed PCIe leg leaves the lanes in an unknown state)
+    if args.full and rank == 0 and n_lanes > 1 and not leg_errors:  # (a failed PCIe leg leaves the lanes in an unknown state)
         try:
             sc.set_scan_cus(0)
             for i in range(14):  # 4 to settle (the leg starts from an idle GPU), 10 measured
@@ -916,8 +977,8 @@ def main():
                 out["roofline"]["frac_isolated"] = round(2.0 * k["alg"] / (iso_ms / 1e3) / 1e12 / PEAK_I8_MFMA_TOPS, 4)
             out["roofline"]["note"] += (f"; {n_lanes} batches in flight: 'achieved'/'frac' use the per-launch duration inside the timed region "
                                         "(launches of different contexts overlap, so it is longer than the kernel alone), "
-                                        "'frac_isolated' = same kernel alone on all CUs (extra untimed leg), "
-                                        "'frac_whole_step' = algorithmic ops of one step / wall time of one step")
+                                        + ("'frac_isolated' = same kernel alone on all CUs (extra untimed leg), " if key in iso else "")
+                                        + "'frac_whole_step' = algorithmic ops of one step / wall time of one step")
         out["phases_ms_per_step"] = {k_: round(v / args.steps, 4) for k_, v in phase.items()}
         per_name = {}
         for (n_, _alg), v in kern.items():
@@ -925,7 +986,7 @@ def main():
         out["kernels_ms_per_step"] = {n_: round(v, 4) for n_, v in per_name.items()}
         out["work"] = {"candidates": counters["candidates"], "raw_hits": counters["raw_hits"], "chars_out": int(n_chars)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             from oracle import oracle as O  # test infrastructure: the CPU baseline leg is allowed to use it
 
@@ -953,7 +1014,7 @@ def main():
         except Exception as e:  # noqa: BLE001 - the reference's CPU rate is a reported baseline, not the measurement
             leg_errors["cpu_baseline"] = repr(e)
 
-    if rank == 0 and args.config in ("c2", "c4") and not args.noise and first_page_is_seed0:
+    if args.full and rank == 0 and args.config in ("c2", "c4") and not args.noise and first_page_is_seed0:
         # parity in the same run: page 0 of this very batch against the committed reference golden (tests/golden/c2_page0.npz)
         try:
             g = np.load(os.path.join(ROOT, "tests", "golden", "c2_page0.npz"))
@@ -1019,7 +1080,7 @@ def main():
         return {"kernel": name_, "avg_kernel_ms": round(ms_ / n_, 4), "frac": round(2.0 * alg_ / (ms_ / n_ / 1e3) / 1e12 / PEAK_I8_MFMA_TOPS, 4),
                 "frac_whole_step": round(2.0 * step_alg / (ms_step / 1e3) / 1e12 / PEAK_I8_MFMA_TOPS, 4)}
 
-    if rank == 0 and world == 1 and args.config == "c2" and not args.noise and not args.no_extra_legs and not use_dist and mode == SCAN_MFMA:
+    if args.full and rank == 0 and world == 1 and args.config == "c2" and not args.noise and not args.no_extra_legs and not use_dist and mode == SCAN_MFMA:
         try:  # c4_stream: 2048 different pages, HBM-resident as luma8, ingested device -> device batch by batch (one DMA-free pass per 16 steps)
             n_stream = 2048
             stream_dev = torch.from_numpy(synth_pages(bank, n_stream, R_W, R_H, first=100000)).to(dev)

@@ -12,8 +12,9 @@ source text is stored.  Fonts: DejaVu Sans Mono (Courier New is not available of
   kernel_cases.npz                 per-call vectors for ncc_8_u8 / ncc_16_u8
   c1_page.npz                      one 608x720 page, 74 templates: raw lists + post-processed lines
   c2_page0.npz                     page 0 of configs[1]: counts + lists for the 380-template bank
+  ref_random_cases.npz             40 seeded random (page, needle, threshold, cap) calls + the reference kernel's output
 
-Usage: python oracle/gen_golden.py
+Usage: python oracle/gen_golden.py [ref_random_cases]     (the argument: that fixture alone)
 """
 import os
 import sys
@@ -27,8 +28,8 @@ from font_ocr_amd import ASCII95, DEFAULT_ALPHABET, Bank, synth_page  # noqa: E4
 from font_ocr_amd.bank import SYNTH_SEED_BASE  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
-FONT = "/usr/share/fonts/truetype/dejavu/DejaVuSansMono.ttf"
 GOLD = os.path.join(ROOT, "tests", "golden")
+FONT = os.path.join(GOLD, "DejaVuSansMono.ttf")
 
 
 def kernel_case(name, page_inv, needle, thr, cap=1024):
@@ -139,7 +140,38 @@ def main():
         page_crc=np.uint32(__import__("zlib").crc32(page.tobytes())),
     )
     print(f"c2_page0.npz: {int(counts.sum())} raw hits")
+    ref_random_cases()
+
+
+def ref_random_cases():
+    """Seeded random pages (dense or sparse: start/end pruning) and needles (cut from the page or random), thresholds and caps; the
+    page's window statistics come from the restated prepare_for_size, the output from the REFERENCE kernel."""
+    assert O.have_ref(), "oracle/_ref/libncc_ref.so missing: run make -C oracle where the reference sources are present"
+    rng = np.random.default_rng(7)
+    cases = {}
+    for it in range(40):
+        r_w, r_h = int(rng.integers(20, 90)), int(rng.integers(20, 70))
+        n_w, n_h = int(rng.integers(1, 17)), int(rng.integers(1, 19))
+        if rng.random() < 0.5:
+            page = rng.integers(0, 256, (r_h, r_w), dtype=np.uint8)
+        else:  # sparse page: exercises start/end pruning
+            page = np.zeros((r_h, r_w), np.uint8)
+            k = int(rng.integers(0, 40))
+            page[rng.integers(0, r_h, k), rng.integers(0, r_w, k)] = rng.integers(1, 256, k)
+        y0, x0 = int(rng.integers(0, r_h - n_h + 1)), int(rng.integers(0, r_w - n_w + 1))
+        nd = page[y0:y0 + n_h, x0:x0 + n_w].copy() if rng.random() < 0.5 else rng.integers(0, 256, (n_h, n_w), dtype=np.uint8)
+        thr = float(rng.choice([-1.0, 0.0, 0.3, 0.8, 0.99]))
+        cap = int(rng.choice([1, 7, 1024]))
+        stats = O.prepare_for_size(page, n_w, n_h)
+        out = O.ncc_u8(O.padded(page), r_w, r_h, nd, stats, thr, cap, use_ref=True)
+        cases.update({f"{it:02d}/page": page, f"{it:02d}/needle": np.ascontiguousarray(nd), f"{it:02d}/thr": np.float64(thr),
+                      f"{it:02d}/cap": np.int64(cap), f"{it:02d}/expect": out})
+    np.savez_compressed(os.path.join(GOLD, "ref_random_cases.npz"), **cases)
+    print(f"ref_random_cases.npz: 40 cases, {sum(len(v) for k, v in cases.items() if k.endswith('/expect'))} matches")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref_random_cases"]:
+        ref_random_cases()
+    else:
+        main()

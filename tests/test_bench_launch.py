@@ -60,6 +60,11 @@ def test_ranks_stderr_is_prefixed():
     assert "[rank 0] dry-launch rank 0 of 2" in r.stderr and "[rank 1] dry-launch rank 1 of 2" in r.stderr
 
 
+def test_full_and_dump_outputs_are_options():
+    r = _run("--help")
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
 def test_world_size_mismatch_is_refused():
     r = _run("--gpus", "2", "--dry-launch", "--steps", "1", "--warmup", "0", env={"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr

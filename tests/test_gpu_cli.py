@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NCC = os.path.join(ROOT, "font_ocr_amd", "bin", "ncc")
-FONT = "/usr/share/fonts/truetype/dejavu/DejaVuSansMono.ttf"
+FONT = os.path.join(ROOT, "tests", "golden", "DejaVuSansMono.ttf")  # DejaVu Sans Mono, with its licence beside it
 
 
 @pytest.mark.skipif(not os.path.exists(FONT), reason="DejaVu Sans Mono not installed")

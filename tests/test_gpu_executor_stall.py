@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(*extra):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "150", "--warmup", "6", "--no-cpu-baseline", "--no-e2e", "--no-extra-legs", "--settle-s", "0.4", *extra],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "150", "--warmup", "6", "--full", "--no-cpu-baseline", "--no-e2e", "--no-extra-legs", "--settle-s", "0.4", *extra],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads(r.stdout.strip().splitlines()[-1])

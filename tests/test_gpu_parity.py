@@ -732,7 +732,7 @@ def test_box_size_char_and_font_banks(scanner, mode, box_size):
 
     from font_ocr_amd import Bank
 
-    font = "/usr/share/fonts/truetype/dejavu/DejaVuSansMono.ttf"
+    font = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "DejaVuSansMono.ttf")
     if not os.path.exists(font):
         pytest.skip("DejaVu Sans Mono not installed")
     alphabet = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789.,;:-_"

@@ -1,6 +1,7 @@
 """The oracle (CPU restatement, oracle/ncc_oracle.c) against the golden vectors produced by the
 reference's own compiled kernels (oracle/gen_golden.py), and — when oracle/_ref is present —
 against those kernels live.  No GPU."""
+import os
 import zlib
 
 import numpy as np
@@ -76,28 +77,23 @@ def test_sim_formula_against_float64_bruteforce(kernel_cases):
         assert abs(ncc - float(m["similarity"])) < 1e-6
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref/libncc_ref.so not present")
 def test_oracle_vs_live_reference_random():
-    """Seeded random pages/needles: restatement == compiled reference, bit for bit."""
-    rng = np.random.default_rng(7)
-    for it in range(40):
-        r_w, r_h = int(rng.integers(20, 90)), int(rng.integers(20, 70))
-        n_w, n_h = int(rng.integers(1, 17)), int(rng.integers(1, 19))
-        if rng.random() < 0.5:
-            page = rng.integers(0, 256, (r_h, r_w), dtype=np.uint8)
-        else:  # sparse page: exercises start/end pruning
-            page = np.zeros((r_h, r_w), np.uint8)
-            k = int(rng.integers(0, 40))
-            page[rng.integers(0, r_h, k), rng.integers(0, r_w, k)] = rng.integers(1, 256, k)
-        y0, x0 = int(rng.integers(0, r_h - n_h + 1)), int(rng.integers(0, r_w - n_w + 1))
-        nd = page[y0:y0 + n_h, x0:x0 + n_w].copy() if rng.random() < 0.5 else rng.integers(0, 256, (n_h, n_w), dtype=np.uint8)
-        thr = float(rng.choice([-1.0, 0.0, 0.3, 0.8, 0.99]))
-        cap = int(rng.choice([1, 7, 1024]))
+    """Seeded random pages/needles (tests/golden/ref_random_cases.npz, oracle/gen_golden.py): restatement == the compiled
+    reference's output stored with them, bit for bit — and == the compiled reference live where oracle/_ref is present."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_random_cases.npz"))
+    names = sorted({k.split("/")[0] for k in z.files})
+    assert len(names) == 40
+    for it in names:
+        page, nd = z[it + "/page"], z[it + "/needle"]
+        (r_h, r_w), (n_h, n_w) = page.shape, nd.shape
+        thr, cap = float(z[it + "/thr"]), int(z[it + "/cap"])
         stats = O.prepare_for_size(page, n_w, n_h)
         flat = O.padded(page)
-        a = O.ncc_u8(flat, r_w, r_h, nd, stats, thr, cap, use_ref=True)
         b = O.ncc_u8(flat, r_w, r_h, nd, stats, thr, cap, use_ref=False)
-        assert a.tobytes() == b.tobytes(), (it, r_w, r_h, n_w, n_h, thr, cap)
+        assert b.tobytes() == z[it + "/expect"].tobytes(), (it, r_w, r_h, n_w, n_h, thr, cap)
+        if O.have_ref():
+            a = O.ncc_u8(flat, r_w, r_h, nd, stats, thr, cap, use_ref=True)
+            assert a.tobytes() == b.tobytes(), (it, r_w, r_h, n_w, n_h, thr, cap)
 
 
 def test_c1_page_raw_hits(bank_default, c1_golden):
