@@ -247,3 +247,90 @@ def raster():
 def rccl():
     """libfocr_rccl.so — the match-list gather over RCCL for one process driving several GPUs (loads librccl)."""
     return _load("libfocr_rccl.so", RCCL_SYMBOLS)
+
+
+# ---- the `focr` line decoder (include/focr_decode.h): its own tables, so the ones above stay equal to their headers ----
+
+class DecodeGlyph(C.Structure):
+    """focr_decode_glyph_t (include/focr_decode.h)."""
+
+    _fields_ = [
+        ("codepoint", C.c_uint32),
+        ("increment", C.c_float),
+        ("box_w", C.c_uint32),
+        ("box_h", C.c_uint32),
+        ("stride", C.c_uint32),
+        ("offset", C.c_uint64),
+        ("off_x", C.c_int32 * 64),
+        ("off_y", C.c_int32 * 64),
+    ]
+
+
+class DecodeFontStruct(C.Structure):
+    """focr_decode_font_t (include/focr_decode.h)."""
+
+    _fields_ = [
+        ("glyphs", C.POINTER(DecodeGlyph)),
+        ("n_glyphs", C.c_size_t),
+        ("bitmaps", C.POINTER(C.c_uint8)),
+        ("bitmaps_len", C.c_size_t),
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("text_size", C.c_float),
+        ("kerning", C.c_float),
+        ("hinting", C.c_int),
+        ("min_increment", C.c_float),
+    ]
+
+
+class DecodedLine(C.Structure):
+    """focr_decoded_line_t (include/focr_decode.h)."""
+
+    _fields_ = [("page", C.c_uint32), ("y", C.c_uint32), ("first", C.c_uint64), ("n_chars", C.c_uint32), ("pad", C.c_uint32)]
+
+
+# the declarations of include/focr_decode.h in libfocr_raster.so
+DECODE_RASTER_SYMBOLS = {
+    "focr_raster_glyph": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_size_t,
+                                    C.c_size_t, C.c_char_p, C.c_size_t]),
+    "focr_glyph_metrics": (C.c_int, [C.c_char_p, C.c_float, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    "focr_render_text": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
+    "focr_decode_font_build": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_size_t,
+                                         C.POINTER(DecodeFontStruct), C.c_char_p, C.c_size_t]),
+    "focr_decode_font_free": (None, [C.POINTER(DecodeFontStruct)]),
+}
+
+# the declarations of include/focr_decode.h in libfocr_hip.so
+DECODE_HIP_SYMBOLS = {
+    "focr_decoder_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "focr_decoder_destroy": (None, [C.c_void_p]),
+    "focr_decoder_last_error": (C.c_char_p, [C.c_void_p]),
+    "focr_decoder_set_font": (C.c_int, [C.c_void_p, C.POINTER(DecodeFontStruct)]),
+    "focr_decoder_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32,
+                                   C.c_uint32, C.c_uint32, C.c_uint32]),
+    "focr_decoder_n_lines": (C.c_size_t, [C.c_void_p]),
+    "focr_decoder_n_chars": (C.c_size_t, [C.c_void_p]),
+    "focr_decoder_get": (C.c_int, [C.c_void_p, C.POINTER(DecodedLine), C.c_void_p]),
+    "focr_decoder_last_ms": (C.c_float, [C.c_void_p]),
+    "focr_decoder_last_launches": (C.c_uint32, [C.c_void_p]),
+}
+
+
+def _bind(lib, symbols):
+    for sym, (restype, argtypes) in symbols.items():
+        fn = getattr(lib, sym)  # AttributeError if the library does not export it
+        fn.restype = restype
+        fn.argtypes = argtypes
+    return lib
+
+
+def decode_raster():
+    """libfocr_raster.so with the line decoder's host entries bound."""
+    return _bind(raster(), DECODE_RASTER_SYMBOLS)
+
+
+def decode_hip():
+    """libfocr_hip.so with the line decoder bound.  Raises if it is not built."""
+    return _bind(hip(), DECODE_HIP_SYMBOLS)

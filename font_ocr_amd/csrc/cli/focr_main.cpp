@@ -1,0 +1,332 @@
+// focr — the reference's default binary (src/main.rs: Args at 343-385, main at 387-470) on top of the MI355X line decoder.
+//
+// Same flags, defaults and stdout as the reference.  Differences, all deliberate:
+//   * glyphs are rasterised once per run into 64 sub-pixel phases (focr_decode_font_build), not once per candidate;
+//   * pages of equal size are decoded as one device batch on one GPU; stdout is still in the order of -i;
+//   * kerning <= 0 or a glyph that does not advance the pen is an error (the reference never finishes a line);
+//   * --verify clips rendered text that falls outside the page (the reference panics there);
+//   * --test is refused: its RGBA blend cannot be pinned here.
+// There is no CPU fallback: without a device it exits non-zero with the error.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include <sys/stat.h>
+#include <unistd.h>
+#include <zlib.h>
+
+#include "focr_decode.h"
+#include "focr_host.h"
+
+namespace {
+
+const char *DEFAULT_ALPHABET = "> =ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";  // src/main.rs:13-14
+const size_t BATCH_PAGES = 256;
+
+struct Args {
+    std::vector<std::string> img;
+    std::string font, alphabet = DEFAULT_ALPHABET, verify, test;
+    bool hinting = false, have_verify = false, have_test = false;
+    float text_size = 0.f, kerning = 1.f;
+    uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0;
+    bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
+};
+
+const char *USAGE =
+    "Usage: focr [OPTIONS] --font <FONT> --text-size <TEXT_SIZE> --width <WIDTH> --line-height <LINE_HEIGHT> --line-advance <LINE_ADVANCE>";
+
+[[noreturn]] void usage_error(const std::string &msg) {
+    fprintf(stderr, "error: %s\n\n%s\n\nFor more information, try '--help'.\n", msg.c_str(), USAGE);
+    exit(2);  // clap's usage-error exit code
+}
+
+[[noreturn]] void die(const std::string &msg, int code = 101) {  // 101: a Rust panic's exit status
+    fprintf(stderr, "focr: %s\n", msg.c_str());
+    fflush(stdout);
+    fflush(stderr);
+    _exit(code);
+}
+
+void print_help() {
+    printf("%s\n\nOptions:\n"
+           "  -i, --img <IMG>...                   \n"
+           "  -f, --font <FONT>                    \n"
+           "  -a, --alphabet <ALPHABET>            [default: %s]\n"
+           "      --hinting                        \n"
+           "  -t, --text-size <TEXT_SIZE>          \n"
+           "  -k, --kerning <KERNING>              [default: 1]\n"
+           "  -x, --x <X>                          [default: 0]\n"
+           "  -y, --y <Y>                          [default: 0]\n"
+           "  -w, --width <WIDTH>                  \n"
+           "      --line-height <LINE_HEIGHT>      \n"
+           "      --line-advance <LINE_ADVANCE>    \n"
+           "      --test <TEST>                    Prefix for output test images (not supported here)\n"
+           "      --verify <VERIFY>                Dir for verify images. Red is reference, Blue is rendered\n"
+           "  -h, --help                           Print help\n"
+           "  -V, --version                        Print version\n",
+           USAGE, DEFAULT_ALPHABET);
+}
+
+Args parse_args(int argc, char **argv) {
+    Args a;
+    std::vector<std::string> v(argv + 1, argv + argc);
+    auto is_opt = [](const std::string &s) { return s.size() > 1 && s[0] == '-' && !(isdigit((unsigned char)s[1]) || s[1] == '.'); };
+    for (size_t i = 0; i < v.size(); i++) {
+        std::string k = v[i], val;
+        bool has_val = false;
+        if (k.rfind("--", 0) == 0) {
+            size_t eq = k.find('=');
+            if (eq != std::string::npos) {
+                val = k.substr(eq + 1);
+                k = k.substr(0, eq);
+                has_val = true;
+            }
+        } else if (k.size() > 2 && k[0] == '-' && k[1] != '-') {  // -t13, -ipage.pgm
+            val = k.substr(k[2] == '=' ? 3 : 2);
+            k = k.substr(0, 2);
+            has_val = true;
+        }
+        auto need = [&]() -> std::string {
+            if (has_val) return val;
+            if (i + 1 >= v.size()) usage_error("a value is required for '" + k + "' but none was supplied");
+            return v[++i];
+        };
+        auto num_u = [&](const std::string &s) -> uint32_t {
+            char *e = nullptr;
+            unsigned long long r = strtoull(s.c_str(), &e, 10);
+            if (!e || *e || s.empty() || s[0] == '-' || s[0] == '+' || r > 0xffffffffull) usage_error("invalid value '" + s + "' for '" + k + "'");
+            return (uint32_t)r;
+        };
+        auto num_f = [&](const std::string &s) -> float {
+            char *e = nullptr;
+            float r = strtof(s.c_str(), &e);
+            if (!e || *e || s.empty()) usage_error("invalid value '" + s + "' for '" + k + "'");
+            return r;
+        };
+        if (k == "-i" || k == "--img") {
+            a.img.push_back(need());
+            while (i + 1 < v.size() && !is_opt(v[i + 1])) a.img.push_back(v[++i]);  // num_args = 1..
+        } else if (k == "-f" || k == "--font") a.font = need();
+        else if (k == "-a" || k == "--alphabet") a.alphabet = need();
+        else if (k == "--hinting") a.hinting = true;
+        else if (k == "-t" || k == "--text-size") a.text_size = num_f(need()), a.have_text_size = true;
+        else if (k == "-k" || k == "--kerning") a.kerning = num_f(need());
+        else if (k == "-x" || k == "--x") a.x = num_u(need());
+        else if (k == "-y" || k == "--y") a.y = num_u(need());
+        else if (k == "-w" || k == "--width") a.width = num_u(need()), a.have_width = true;
+        else if (k == "--line-height") a.line_height = num_u(need()), a.have_line_height = true;
+        else if (k == "--line-advance") a.line_advance = num_u(need()), a.have_line_advance = true;
+        else if (k == "--test") a.test = need(), a.have_test = true;
+        else if (k == "--verify") a.verify = need(), a.have_verify = true;
+        else if (k == "-h" || k == "--help") {
+            print_help();
+            exit(0);
+        } else if (k == "-V" || k == "--version") {
+            puts("font-ocr 0.1.0");
+            exit(0);
+        } else usage_error("unexpected argument '" + v[i] + "' found");
+    }
+    std::string missing;
+    if (a.font.empty()) missing += "\n  --font <FONT>";
+    if (!a.have_text_size) missing += "\n  --text-size <TEXT_SIZE>";
+    if (!a.have_width) missing += "\n  --width <WIDTH>";
+    if (!a.have_line_height) missing += "\n  --line-height <LINE_HEIGHT>";
+    if (!a.have_line_advance) missing += "\n  --line-advance <LINE_ADVANCE>";
+    if (!missing.empty()) usage_error("the following required arguments were not provided:" + missing);
+    return a;
+}
+
+std::vector<uint32_t> utf8_decode(const std::string &s) {
+    std::vector<uint32_t> out;
+    for (size_t i = 0; i < s.size();) {
+        unsigned char c = (unsigned char)s[i];
+        uint32_t cp;
+        int n;
+        if (c < 0x80) cp = c, n = 1;
+        else if ((c >> 5) == 6) cp = c & 0x1f, n = 2;
+        else if ((c >> 4) == 14) cp = c & 0x0f, n = 3;
+        else cp = c & 0x07, n = 4;
+        for (int k = 1; k < n && i + k < s.size(); k++) cp = (cp << 6) | ((unsigned char)s[i + k] & 0x3f);
+        out.push_back(cp);
+        i += n;
+    }
+    return out;
+}
+
+std::string utf8_encode(uint32_t cp) {
+    std::string s;
+    if (cp < 0x80) s += (char)cp;
+    else if (cp < 0x800) s += (char)(0xc0 | (cp >> 6)), s += (char)(0x80 | (cp & 0x3f));
+    else if (cp < 0x10000) s += (char)(0xe0 | (cp >> 12)), s += (char)(0x80 | ((cp >> 6) & 0x3f)), s += (char)(0x80 | (cp & 0x3f));
+    else s += (char)(0xf0 | (cp >> 18)), s += (char)(0x80 | ((cp >> 12) & 0x3f)), s += (char)(0x80 | ((cp >> 6) & 0x3f)), s += (char)(0x80 | (cp & 0x3f));
+    return s;
+}
+
+// 8-bit RGB PNG, filter 0 on every row (what DynamicImage::save writes for an RgbImage, byte for byte in the pixels)
+bool write_png_rgb(const std::string &path, const uint8_t *px, uint32_t w, uint32_t h) {
+    const size_t row = (size_t)w * 3;
+    std::vector<uint8_t> raw((row + 1) * h);
+    for (uint32_t y = 0; y < h; y++) {
+        raw[(size_t)y * (row + 1)] = 0;
+        if (row) memcpy(&raw[(size_t)y * (row + 1) + 1], px + (size_t)y * row, row);
+    }
+    uLongf zl = compressBound((uLong)raw.size());
+    std::vector<uint8_t> z(zl);
+    if (compress2(z.data(), &zl, raw.data(), (uLong)raw.size(), 6) != Z_OK) return false;
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    auto be32 = [](uint8_t *p, uint32_t v) { p[0] = v >> 24, p[1] = v >> 16, p[2] = v >> 8, p[3] = v; };
+    auto chunk = [&](const char *type, const uint8_t *data, uint32_t len) {
+        uint8_t hdr[8];
+        be32(hdr, len);
+        memcpy(hdr + 4, type, 4);
+        fwrite(hdr, 1, 8, f);
+        if (len) fwrite(data, 1, len, f);
+        uLong crc = crc32(0, (const Bytef *)type, 4);
+        if (len) crc = crc32(crc, data, len);
+        uint8_t c[4];
+        be32(c, (uint32_t)crc);
+        fwrite(c, 1, 4, f);
+    };
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    fwrite(sig, 1, 8, f);
+    uint8_t ihdr[13] = {0};
+    be32(ihdr, w);
+    be32(ihdr + 4, h);
+    ihdr[8] = 8;  // bit depth
+    ihdr[9] = 2;  // colour type: RGB
+    chunk("IHDR", ihdr, 13);
+    chunk("IDAT", z.data(), (uint32_t)zl);
+    chunk("IEND", nullptr, 0);
+    bool ok = ferror(f) == 0;
+    return fclose(f) == 0 && ok;
+}
+
+struct Line {
+    uint32_t y;
+    std::vector<uint32_t> text;  // code points
+};
+
+// draw_verify + red_blue_mse (src/main.rs:300-329, 518-524): red = reference ink, blue = the decoded text rendered at
+// (x_start, line.y); rendered pixels outside the page are clipped (the reference panics on them)
+float verify_page(const Args &a, const uint8_t *luma, size_t W, size_t H, const std::vector<Line> &lines, const std::string &out_path) {
+    std::vector<uint8_t> rgb(W * H * 3, 0);
+    for (size_t i = 0; i < W * H; i++)
+        if (luma[i] != 255) rgb[i * 3] = luma[i];
+    char err[256] = {0};
+    for (const Line &l : lines) {
+        uint8_t *c = nullptr;
+        size_t cw = 0, ch = 0;
+        if (focr_render_text(a.font.c_str(), a.text_size, a.hinting, a.kerning, l.text.data(), l.text.size(), &c, &cw, &ch, err, sizeof err) != 0)
+            die(std::string("render: ") + err);
+        for (size_t y = 0; y < ch; y++)
+            for (size_t x = 0; x < cw; x++) {
+                const uint8_t v = c[y * cw + x];
+                const uint64_t ox = (uint64_t)a.x + x, oy = (uint64_t)l.y + y;
+                if (v == 0 || ox >= W || oy >= H) continue;  // canvas_to_lum8: 255 - v != 255
+                rgb[(oy * W + ox) * 3 + 2] = (uint8_t)(255 - v);
+            }
+        free(c);
+    }
+    if (!write_png_rgb(out_path, rgb.data(), (uint32_t)W, (uint32_t)H)) die("cannot write " + out_path);
+    int64_t sum = 0;
+    for (size_t i = 0; i < W * H; i++) {
+        const int d = (int)rgb[i * 3] - (int)rgb[i * 3 + 2];
+        sum += (int64_t)d * d;
+    }
+    return (float)sum / (float)(uint32_t)(W * H);
+}
+
+std::string verify_path(const std::string &dir, const std::string &img) {  // Path::new(img).with_extension("png").file_name()
+    std::string name = img.substr(img.find_last_of('/') == std::string::npos ? 0 : img.find_last_of('/') + 1);
+    const size_t dot = name.find_last_of('.');
+    if (dot != std::string::npos && dot != 0) name = name.substr(0, dot);
+    return dir + (dir.empty() || dir.back() == '/' ? "" : "/") + name + ".png";
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    Args args = parse_args(argc, argv);
+    if (args.have_test)
+        die("--test is not supported by this port (its RGBA blend of the test images is not pinned); decode without it", 1);
+    if (args.have_verify) {
+        struct stat st;
+        if (stat(args.verify.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) die("--verify should be a dir");  // src/main.rs:389-391
+    }
+    if (args.img.empty()) return 0;
+
+    std::vector<uint32_t> alphabet = utf8_decode(args.alphabet);
+    char err[256] = {0};
+    focr_decode_font_t font{};
+    if (focr_decode_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), &font, err,
+                               sizeof err) != 0)
+        die(std::string("decode font: ") + err);
+
+    // sizes first, so that pages of one size form one batch
+    const size_t n_img = args.img.size();
+    std::vector<std::pair<size_t, size_t>> dims(n_img);
+    std::map<std::pair<size_t, size_t>, std::vector<size_t>> groups;
+    for (size_t i = 0; i < n_img; i++) {
+        if (focr_image_probe(args.img[i].c_str(), &dims[i].first, &dims[i].second, err, sizeof err) != 0)
+            die("called `Result::unwrap()` on an `Err` value: " + std::string(err) + " (" + args.img[i] + ")");
+        groups[dims[i]].push_back(i);
+    }
+
+    focr_decoder_t *dec = nullptr;
+    if (focr_decoder_create(0, &dec) != 0) die(std::string("no usable GPU: ") + focr_decoder_last_error(nullptr), 1);
+    if (focr_decoder_set_font(dec, &font) != 0) die(std::string("focr_decoder_set_font: ") + focr_decoder_last_error(dec), 1);
+
+    std::vector<std::vector<Line>> lines(n_img);
+    std::vector<uint8_t> batch;
+    for (const auto &grp : groups) {
+        const size_t W = grp.first.first, H = grp.first.second;
+        for (size_t b0 = 0; b0 < grp.second.size(); b0 += BATCH_PAGES) {
+            const size_t nb = std::min(BATCH_PAGES, grp.second.size() - b0);
+            batch.assign(nb * W * H, 255);
+            for (size_t j = 0; j < nb; j++) {
+                const size_t i = grp.second[b0 + j];
+                uint8_t *px = nullptr;
+                size_t w = 0, h = 0;
+                if (focr_image_load_luma8(args.img[i].c_str(), &px, &w, &h, err, sizeof err) != 0)
+                    die("called `Result::unwrap()` on an `Err` value: " + std::string(err) + " (" + args.img[i] + ")");
+                if (w != W || h != H) die("image size changed while reading " + args.img[i]);
+                memcpy(batch.data() + j * W * H, px, W * H);
+                free(px);
+            }
+            if (focr_decoder_run(dec, batch.data(), 0, nb, W, H, args.x, args.y, args.width, args.line_height, args.line_advance) != 0)
+                die(std::string("focr_decoder_run: ") + focr_decoder_last_error(dec), 1);
+            std::vector<focr_decoded_line_t> dl(focr_decoder_n_lines(dec));
+            std::vector<uint16_t> dc(focr_decoder_n_chars(dec));
+            focr_decoder_get(dec, dl.data(), dc.data());
+            for (const focr_decoded_line_t &l : dl) {
+                Line out{l.y, {}};
+                for (uint32_t c = 0; c < l.n_chars; c++) out.text.push_back(alphabet[dc[l.first + c]]);
+                lines[grp.second[b0 + l.page]].push_back(std::move(out));
+            }
+            if (args.have_verify)
+                for (size_t j = 0; j < nb; j++) {
+                    const size_t i = grp.second[b0 + j];
+                    const std::string path = verify_path(args.verify, args.img[i]);
+                    const float mse = verify_page(args, batch.data() + j * W * H, W, H, lines[i], path);
+                    fprintf(stderr, "%s %.6f\n", args.img[i].c_str(), (double)mse);
+                }
+        }
+    }
+    focr_decoder_destroy(dec);
+    focr_decode_font_free(&font);
+
+    std::string out;
+    for (size_t i = 0; i < n_img; i++)
+        for (const Line &l : lines[i]) {
+            for (uint32_t cp : l.text) out += utf8_encode(cp);
+            out += '\n';
+        }
+    fwrite(out.data(), 1, out.size(), stdout);
+    return 0;
+}

@@ -1,0 +1,424 @@
+// decode.hip — the `focr` line decoder on the device (include/focr_decode.h; decode_image / decode_line, src/main.rs:112-218).
+//
+// A batch of equal-size pages runs in three launches, whatever its line count:
+//   1. line_prepass_kernel: one workgroup per (page, line) slot crops the line as the image crate does, inverts it
+//      (r = 255 - luma) into a zero-padded strip and flags it non-blank (an empty crop counts as all-white);
+//   2. line_compact_kernel: one workgroup turns the flags into the work list of non-blank slots, in (page, line) order;
+//   3. line_decode_kernel: one wave per work-list line runs the reference's pen loop.  The pen and the step count are
+//      uniform across the wave; each lane scores its glyphs (lane, lane + 64, ...) against the strip (LDS when it fits)
+//      from the glyph's phase tile, then a wave argmin takes the lowest (score, glyph index).
+// The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
+// c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
+// included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
+// order of the sums nor the device changes a choice.  The pen update is one f32 add of the host-computed increment.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "focr_decode.h"
+
+namespace focr_dec {
+
+constexpr uint32_t PAD = 4;                 // zero bytes left of a strip row (reads up to 3 bytes left of column 0)
+constexpr uint32_t LDS_STRIP_MAX = 65536;   // the strip is staged in LDS up to this many bytes, else read from global
+constexpr uint32_t PREPASS_THREADS = 256;
+constexpr uint32_t COMPACT_THREADS = 1024;
+
+struct DevGlyph {
+    uint32_t off_dw;  // dword offset of phase 0 in the bitmap table
+    uint32_t ndw;     // dwords per bitmap row
+    uint32_t box_h;
+    float inc;
+};
+
+struct Geometry {
+    uint32_t page_w, page_h;
+    uint32_t x, w;               // clamped crop x and width (equal for every line of the batch)
+    uint32_t y_start, line_height, line_advance;
+    uint32_t n_slots;            // line slots per page: y_start + i * line_advance < page_h
+    uint32_t total;              // n_pages * n_slots
+    uint32_t stride;             // bytes per strip row: PAD + w rounded up to dwords, plus two dwords of reach
+    uint32_t cap;                // characters per line at most
+};
+
+__device__ __forceinline__ void slot_rows(const Geometry &g, uint32_t i, uint32_t *yc, uint32_t *h) {
+    const uint64_t y = (uint64_t)g.y_start + (uint64_t)i * g.line_advance;
+    *yc = (uint32_t)std::min<uint64_t>(y, g.page_h);
+    *h = std::min(g.line_height, g.page_h - *yc);
+}
+
+// 1. crop + invert + blank flag, one workgroup per slot
+__global__ __launch_bounds__(PREPASS_THREADS) void line_prepass_kernel(const uint8_t *__restrict__ pages, Geometry g,
+                                                                       uint8_t *__restrict__ strips, uint32_t *__restrict__ flags) {
+    const uint32_t slot = blockIdx.x;
+    const uint32_t page = slot / g.n_slots, i = slot % g.n_slots;
+    uint32_t yc, h;
+    slot_rows(g, i, &yc, &h);
+    const uint8_t *src = pages + (size_t)page * g.page_w * g.page_h + (size_t)yc * g.page_w + g.x;
+    uint8_t *dst = strips + (size_t)slot * g.stride * g.line_height;
+    int ink = 0;
+    const uint32_t n = g.stride * h;
+    for (uint32_t k = threadIdx.x; k < n; k += PREPASS_THREADS) {
+        const uint32_t row = k / g.stride;
+        const int col = (int)(k % g.stride) - (int)PAD;
+        uint8_t v = 0;
+        if (col >= 0 && (uint32_t)col < g.w) {
+            const uint8_t l = src[(size_t)row * g.page_w + col];
+            v = 255 - l;
+            ink |= l != 255;
+        }
+        dst[k] = v;
+    }
+    ink = __syncthreads_or(ink);
+    if (threadIdx.x == 0) flags[slot] = ink ? 1u : 0u;
+}
+
+// 2. order-preserving compaction of the non-blank slots, one workgroup
+__global__ __launch_bounds__(COMPACT_THREADS) void line_compact_kernel(const uint32_t *__restrict__ flags, uint32_t total,
+                                                                       uint32_t *__restrict__ work, uint32_t *__restrict__ count) {
+    __shared__ uint32_t wave_sum[COMPACT_THREADS / 64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t base = 0;
+    for (uint32_t start = 0; start < total; start += COMPACT_THREADS) {
+        const uint32_t s = start + threadIdx.x;
+        const bool live = s < total && flags[s] != 0;
+        const uint64_t m = __ballot(live);
+        if (lane == 0) wave_sum[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t w = 0; w < COMPACT_THREADS / 64; w++) {
+            before += w < wave ? wave_sum[w] : 0;
+            all += wave_sum[w];
+        }
+        if (live) work[base + before + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = s;
+        base += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *count = base;
+}
+
+__device__ __forceinline__ uint32_t edge_mask(int base, int w) {
+    uint32_t m = 0;
+    for (int b = 0; b < 4; b++)
+        if (base + b >= 0 && base + b < w) m |= 0xffu << (8 * b);
+    return m;
+}
+
+// 3. the pen loop, one wave per work-list line
+template <bool LDS>
+__global__ __launch_bounds__(64) void line_decode_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
+                                                         const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
+                                                         const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps,
+                                                         uint32_t n_glyphs, float origin_x, uint32_t *__restrict__ n_chars,
+                                                         uint16_t *__restrict__ chars) {
+    extern __shared__ uint32_t lds_strip[];
+    const uint32_t k = blockIdx.x;
+    if (k >= *count) return;
+    const uint32_t slot = work[k];
+    uint32_t yc, h;
+    slot_rows(g, slot % g.n_slots, &yc, &h);
+    const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
+    const uint32_t sdw = g.stride / 4;
+    if (LDS) {
+        for (uint32_t q = threadIdx.x; q < sdw * h; q += 64) lds_strip[q] = strip[q];
+        __syncthreads();
+        strip = lds_strip;
+    }
+    const uint32_t lane = threadIdx.x;
+    const int w = (int)g.w;
+    const float fw = (float)g.w;
+    uint16_t *out = chars + (size_t)k * g.cap;
+    float pos = 0.f;
+    uint32_t n = 0;
+    while (pos < fw && n < g.cap) {
+        const int d = (int)((origin_x + pos) * 64.0f);  // FreeType's delta: trunc(t * 64)
+        const int phase = d & 63, shift = d >> 6;
+        uint64_t best = ~0ull;
+        for (uint32_t gi = lane; gi < n_glyphs; gi += 64) {
+            const DevGlyph gl = glyphs[gi];
+            const int2 o = offs[gi * 64 + phase];
+            const int x0 = shift + o.x, y0 = o.y;
+            const uint32_t *tile = bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h;
+            const int r_lo = std::max(0, -y0), r_hi = std::min((int)gl.box_h, (int)h - y0);
+            uint32_t cc = 0, cr = 0;
+            for (int r = r_lo; r < r_hi; r++) {
+                const uint32_t *srow = strip + (size_t)(y0 + r) * sdw;
+                const uint32_t *trow = tile + (size_t)r * gl.ndw;
+                for (uint32_t q = 0; q < gl.ndw; q++) {
+                    const int base = x0 + 4 * (int)q;
+                    if (base <= -4 || base >= w) continue;
+                    uint32_t c = trow[q];
+                    if (base < 0 || base + 4 > w) c &= edge_mask(base, w);
+                    const uint32_t a = (uint32_t)(base + (int)PAD);
+                    const uint32_t rv = __builtin_amdgcn_alignbyte(srow[(a >> 2) + 1], srow[a >> 2], a & 3);
+                    cr = __builtin_amdgcn_udot4(c, rv, cr, false);
+                    cc = __builtin_amdgcn_udot4(c, c, cc, false);
+                }
+            }
+            const int score = (int)cc - 2 * (int)cr;
+            const uint64_t key = ((uint64_t)((uint32_t)score ^ 0x80000000u) << 32) | gi;  // (score, index), lowest first
+            best = std::min(best, key);
+        }
+        for (int m = 32; m >= 1; m >>= 1) {
+            const uint32_t lo = __shfl_xor((uint32_t)best, m, 64), hi = __shfl_xor((uint32_t)(best >> 32), m, 64);
+            best = std::min(best, ((uint64_t)hi << 32) | lo);
+        }
+        const uint32_t gbest = (uint32_t)best;
+        if (lane == 0) out[n] = (uint16_t)gbest;
+        n++;
+        pos = __fadd_rn(pos, glyphs[gbest].inc);
+    }
+    if (lane == 0) n_chars[k] = n;
+}
+
+}  // namespace focr_dec
+
+using namespace focr_dec;
+
+struct focr_decoder {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::string err;
+    // font
+    uint32_t n_glyphs = 0;
+    float origin_x = 0.f, min_inc = 0.f;
+    std::vector<float> inc;
+    DevGlyph *d_glyphs = nullptr;
+    int2 *d_offs = nullptr;
+    uint32_t *d_bitmaps = nullptr;
+    // batch buffers (grown on demand)
+    uint8_t *d_pages = nullptr;
+    size_t pages_cap = 0;
+    uint8_t *d_strips = nullptr;
+    size_t strips_cap = 0;
+    uint32_t *d_flags = nullptr, *d_work = nullptr, *d_nchars = nullptr, *d_count = nullptr;
+    size_t slots_cap = 0;
+    uint16_t *d_chars = nullptr;
+    size_t chars_cap = 0;
+    // results of the last run
+    std::vector<focr_decoded_line_t> lines;
+    std::vector<uint16_t> chars;
+    float last_ms = 0.f;
+    uint32_t last_launches = 0;
+};
+
+namespace {
+
+thread_local std::string g_dec_err;
+
+int dfail(focr_decoder *dec, const std::string &msg) {
+    if (dec) dec->err = msg;
+    g_dec_err = msg;
+    return 1;
+}
+
+#define DEC_CHECK(call)                                                                              \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) return dfail(dec, std::string(#call ": ") + hipGetErrorString(e_));    \
+    } while (0)
+
+template <class T>
+int grow(focr_decoder *dec, T **p, size_t *cap, size_t want) {
+    if (want <= *cap) return 0;
+    if (*p) DEC_CHECK(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    DEC_CHECK(hipMalloc((void **)p, want * sizeof(T)));
+    *cap = want;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int focr_decoder_create(int device, focr_decoder_t **out) {
+    focr_decoder *dec = nullptr;
+    if (!out) return dfail(nullptr, "focr_decoder_create: null out");
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return dfail(nullptr, "no HIP device available (the focr decoder has no CPU fallback)");
+    if (device < 0 || device >= n) return dfail(nullptr, "focr_decoder_create: device index out of range");
+    DEC_CHECK(hipSetDevice(device));
+    dec = new focr_decoder;
+    dec->device = device;
+    if (hipStreamCreateWithFlags(&dec->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&dec->ev0) != hipSuccess ||
+        hipEventCreate(&dec->ev1) != hipSuccess) {
+        focr_decoder_destroy(dec);
+        return dfail(nullptr, "focr_decoder_create: stream / event creation failed");
+    }
+    *out = dec;
+    return 0;
+}
+
+extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
+    if (!dec) return;
+    (void)hipSetDevice(dec->device);
+    if (dec->stream) (void)hipStreamSynchronize(dec->stream);
+    for (void *p : {(void *)dec->d_glyphs, (void *)dec->d_offs, (void *)dec->d_bitmaps, (void *)dec->d_pages, (void *)dec->d_strips,
+                    (void *)dec->d_flags, (void *)dec->d_work, (void *)dec->d_nchars, (void *)dec->d_count, (void *)dec->d_chars})
+        if (p) (void)hipFree(p);
+    if (dec->ev0) (void)hipEventDestroy(dec->ev0);
+    if (dec->ev1) (void)hipEventDestroy(dec->ev1);
+    if (dec->stream) (void)hipStreamDestroy(dec->stream);
+    delete dec;
+}
+
+extern "C" const char *focr_decoder_last_error(const focr_decoder_t *dec) { return dec ? dec->err.c_str() : g_dec_err.c_str(); }
+
+extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font_t *font) {
+    if (!dec || !font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_font: bad arguments");
+    if (font->n_glyphs > 65535) return dfail(dec, "focr_decoder_set_font: more than 65535 glyphs");
+    if (font->bitmaps_len % 4 || font->bitmaps_len / 4 > 0xffffffffull) return dfail(dec, "focr_decoder_set_font: bad bitmap table");
+    DEC_CHECK(hipSetDevice(dec->device));
+    const size_t G = font->n_glyphs;
+    std::vector<DevGlyph> gl(G);
+    std::vector<int2> offs(G * FOCR_DECODE_PHASES);
+    dec->inc.assign(G, 0.f);
+    float min_inc = font->glyphs[0].increment;
+    for (size_t i = 0; i < G; i++) {
+        const focr_decode_glyph_t &s = font->glyphs[i];
+        if (!(s.increment > 0.f)) return dfail(dec, "focr_decoder_set_font: a glyph does not advance the pen");
+        if (s.stride % 4 || s.stride < s.box_w || s.offset % 4 ||
+            s.offset + (uint64_t)FOCR_DECODE_PHASES * s.stride * s.box_h > font->bitmaps_len ||
+            (uint64_t)s.stride * s.box_h * 2 * 255 * 255 >= (1ull << 31))
+            return dfail(dec, "focr_decoder_set_font: inconsistent glyph table");
+        gl[i] = DevGlyph{(uint32_t)(s.offset / 4), s.stride / 4, s.box_h, s.increment};
+        for (int p = 0; p < FOCR_DECODE_PHASES; p++) offs[i * FOCR_DECODE_PHASES + p] = make_int2(s.off_x[p], s.off_y[p]);
+        dec->inc[i] = s.increment;
+        min_inc = std::min(min_inc, s.increment);
+    }
+    for (void *p : {(void *)dec->d_glyphs, (void *)dec->d_offs, (void *)dec->d_bitmaps})
+        if (p) DEC_CHECK(hipFree(p));
+    dec->d_glyphs = nullptr, dec->d_offs = nullptr, dec->d_bitmaps = nullptr, dec->n_glyphs = 0;
+    DEC_CHECK(hipMalloc((void **)&dec->d_glyphs, sizeof(DevGlyph) * G));
+    DEC_CHECK(hipMalloc((void **)&dec->d_offs, sizeof(int2) * offs.size()));
+    DEC_CHECK(hipMalloc((void **)&dec->d_bitmaps, std::max<size_t>(font->bitmaps_len, 4)));
+    DEC_CHECK(hipMemcpy(dec->d_glyphs, gl.data(), sizeof(DevGlyph) * G, hipMemcpyHostToDevice));
+    DEC_CHECK(hipMemcpy(dec->d_offs, offs.data(), sizeof(int2) * offs.size(), hipMemcpyHostToDevice));
+    if (font->bitmaps_len) DEC_CHECK(hipMemcpy(dec->d_bitmaps, font->bitmaps, font->bitmaps_len, hipMemcpyHostToDevice));
+    dec->n_glyphs = (uint32_t)G;
+    dec->origin_x = font->origin_x;
+    dec->min_inc = min_inc;
+    return 0;
+}
+
+extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int on_device, size_t n_pages, size_t page_w, size_t page_h,
+                                uint32_t x_start, uint32_t y_start, uint32_t width, uint32_t line_height, uint32_t line_advance) {
+    if (!dec) return dfail(nullptr, "focr_decoder_run: null decoder");
+    dec->lines.clear();
+    dec->chars.clear();
+    dec->last_ms = 0.f;
+    dec->last_launches = 0;
+    if (!dec->n_glyphs) return dfail(dec, "focr_decoder_run: no font (focr_decoder_set_font)");
+    if (n_pages && !pages) return dfail(dec, "focr_decoder_run: null pages");
+    if (page_w > 0xffffu * 16 || page_h > 0xffffu * 16) return dfail(dec, "focr_decoder_run: page too large");
+    Geometry g{};
+    g.page_w = (uint32_t)page_w;
+    g.page_h = (uint32_t)page_h;
+    g.x = std::min<uint32_t>(x_start, g.page_w);  // image::crop_imm's clamping
+    g.w = std::min<uint32_t>(width, g.page_w - g.x);
+    g.y_start = y_start;
+    g.line_height = line_height;
+    g.line_advance = line_advance;
+    if (line_height == 0 || y_start >= g.page_h) g.n_slots = 0;  // the first crop is empty: the loop ends at once
+    else if (line_advance == 0) return dfail(dec, "focr_decoder_run: line_advance 0 (the reference never ends)");
+    else g.n_slots = (uint32_t)(((uint64_t)g.page_h - y_start + line_advance - 1) / line_advance);
+    const uint64_t total = (uint64_t)n_pages * g.n_slots;
+    if (total == 0) return 0;
+    if (total > (1u << 30)) return dfail(dec, "focr_decoder_run: too many lines in one batch");
+    g.total = (uint32_t)total;
+    g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;
+    // characters per line at most: the pen moves at least min_inc per step, and f32 rounding is monotone, so the
+    // sequence 0, min_inc, ... reaches w no earlier than any pen does
+    {
+        float p = 0.f;
+        uint32_t steps = 0;
+        while (p < (float)g.w) {
+            p = p + dec->min_inc;
+            if (++steps > (1u << 20)) return dfail(dec, "focr_decoder_run: the pen advance is too small for the line width");
+        }
+        g.cap = std::max<uint32_t>(steps, 1);
+    }
+    DEC_CHECK(hipSetDevice(dec->device));
+    const size_t page_bytes = page_w * page_h * n_pages;
+    const uint8_t *d_src = pages;
+    if (!on_device) {
+        if (grow(dec, &dec->d_pages, &dec->pages_cap, std::max<size_t>(page_bytes, 1))) return 1;
+        DEC_CHECK(hipMemcpyAsync(dec->d_pages, pages, page_bytes, hipMemcpyHostToDevice, dec->stream));
+        d_src = dec->d_pages;
+    }
+    const size_t strip_bytes = (size_t)g.stride * g.line_height;
+    if (grow(dec, &dec->d_strips, &dec->strips_cap, strip_bytes * total)) return 1;
+    if (dec->slots_cap < total) {
+        for (uint32_t **p : {&dec->d_flags, &dec->d_work, &dec->d_nchars}) {
+            if (*p) DEC_CHECK(hipFree(*p));
+            *p = nullptr;
+        }
+        dec->slots_cap = 0;
+        DEC_CHECK(hipMalloc((void **)&dec->d_flags, total * 4));
+        DEC_CHECK(hipMalloc((void **)&dec->d_work, total * 4));
+        DEC_CHECK(hipMalloc((void **)&dec->d_nchars, total * 4));
+        dec->slots_cap = total;
+    }
+    if (!dec->d_count) DEC_CHECK(hipMalloc((void **)&dec->d_count, 4));
+    if (grow(dec, &dec->d_chars, &dec->chars_cap, (size_t)g.cap * total)) return 1;
+
+    DEC_CHECK(hipEventRecord(dec->ev0, dec->stream));
+    line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
+    DEC_CHECK(hipGetLastError());
+    line_compact_kernel<<<1, COMPACT_THREADS, 0, dec->stream>>>(dec->d_flags, g.total, dec->d_work, dec->d_count);
+    DEC_CHECK(hipGetLastError());
+    if (strip_bytes <= LDS_STRIP_MAX)
+        line_decode_kernel<true><<<g.total, 64, strip_bytes, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs,
+                                                                         dec->d_bitmaps, dec->n_glyphs, dec->origin_x, dec->d_nchars, dec->d_chars);
+    else
+        line_decode_kernel<false><<<g.total, 64, 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs,
+                                                                dec->d_bitmaps, dec->n_glyphs, dec->origin_x, dec->d_nchars, dec->d_chars);
+    DEC_CHECK(hipGetLastError());
+    DEC_CHECK(hipEventRecord(dec->ev1, dec->stream));
+
+    uint32_t count = 0;
+    std::vector<uint32_t> work(total), nch(total);
+    std::vector<uint16_t> all((size_t)g.cap * total);
+    DEC_CHECK(hipMemcpyAsync(&count, dec->d_count, 4, hipMemcpyDeviceToHost, dec->stream));
+    DEC_CHECK(hipMemcpyAsync(work.data(), dec->d_work, total * 4, hipMemcpyDeviceToHost, dec->stream));
+    DEC_CHECK(hipMemcpyAsync(nch.data(), dec->d_nchars, total * 4, hipMemcpyDeviceToHost, dec->stream));
+    DEC_CHECK(hipMemcpyAsync(all.data(), dec->d_chars, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
+    DEC_CHECK(hipStreamSynchronize(dec->stream));
+    DEC_CHECK(hipEventElapsedTime(&dec->last_ms, dec->ev0, dec->ev1));
+    dec->last_launches = 3;
+    if (count > total) return dfail(dec, "focr_decoder_run: inconsistent line count from the device");
+    dec->lines.resize(count);
+    for (uint32_t k = 0; k < count; k++) {
+        const uint32_t slot = work[k], n = nch[k];
+        if (slot >= total || n > g.cap) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
+        focr_decoded_line_t &l = dec->lines[k];
+        l.page = slot / g.n_slots;
+        l.y = y_start + (slot % g.n_slots) * line_advance;
+        l.first = dec->chars.size();
+        l.n_chars = n;
+        l.pad = 0;
+        dec->chars.insert(dec->chars.end(), all.begin() + (size_t)k * g.cap, all.begin() + (size_t)k * g.cap + n);
+    }
+    return 0;
+}
+
+extern "C" size_t focr_decoder_n_lines(const focr_decoder_t *dec) { return dec ? dec->lines.size() : 0; }
+extern "C" size_t focr_decoder_n_chars(const focr_decoder_t *dec) { return dec ? dec->chars.size() : 0; }
+
+extern "C" int focr_decoder_get(const focr_decoder_t *dec, focr_decoded_line_t *lines, uint16_t *chars) {
+    if (!dec) return dfail(nullptr, "focr_decoder_get: null decoder");
+    if (lines && !dec->lines.empty()) memcpy(lines, dec->lines.data(), dec->lines.size() * sizeof(focr_decoded_line_t));
+    if (chars && !dec->chars.empty()) memcpy(chars, dec->chars.data(), dec->chars.size() * sizeof(uint16_t));
+    return 0;
+}
+
+extern "C" float focr_decoder_last_ms(const focr_decoder_t *dec) { return dec ? dec->last_ms : 0.f; }
+extern "C" uint32_t focr_decoder_last_launches(const focr_decoder_t *dec) { return dec ? dec->last_launches : 0; }

@@ -19,12 +19,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include <ft2build.h>
 #include FT_FREETYPE_H
 #include FT_TRUETYPE_TABLES_H
 
+#include "focr_decode.h"
 #include "focr_host.h"
 
 namespace {
@@ -258,4 +260,263 @@ extern "C" int focr_font_metrics(const char *font_path, focr_font_metrics_t *out
     out->bbox[2] = (float)fc->bbox.xMax;
     out->bbox[3] = (float)fc->bbox.yMax;
     return 0;
+}
+
+// ---- the `focr` line decoder's host side (include/focr_decode.h; src/main.rs) ---------------------------------------
+
+namespace {
+
+struct Bitmap {  // one FreeType rendering: bitmap_left, -bitmap_top, rows of `w` bytes
+    int left = 0, top = 0, w = 0, h = 0;
+    std::vector<uint8_t> px;
+};
+
+// rasterize_glyph for a pure translation given as FreeType's 26.6 delta (y already negated)
+bool render_delta(Face &f, FT_UInt gid, float size, int hinting, FT_Pos dx, FT_Pos dy, Bitmap *out) {
+    FT_Vector delta{dx, dy};
+    FT_Matrix shape{65536, 0, 0, 65536};
+    FT_Set_Transform(f.face, &shape, &delta);
+    bool ok = FT_Set_Char_Size(f.face, (FT_F26Dot6)(int32_t)(size * 64.0f), 0, 0, 0) == 0;
+    FT_Int32 flags = FT_LOAD_DEFAULT | FT_LOAD_RENDER;
+    flags |= hinting ? FT_LOAD_TARGET_NORMAL : (FT_LOAD_TARGET_NORMAL | FT_LOAD_NO_HINTING);
+    ok = ok && FT_Load_Glyph(f.face, gid, flags) == 0;
+    if (ok) {
+        const FT_GlyphSlot slot = f.face->glyph;
+        const FT_Bitmap &bm = slot->bitmap;
+        out->left = slot->bitmap_left;
+        out->top = -slot->bitmap_top;
+        out->w = out->h = 0;
+        out->px.clear();
+        if (bm.buffer && bm.width && bm.rows) {
+            ok = bm.pixel_mode == FT_PIXEL_MODE_GRAY;
+            out->w = (int)bm.width;
+            out->h = (int)bm.rows;
+            out->px.resize((size_t)out->w * out->h);
+            for (int y = 0; ok && y < out->h; y++)
+                memcpy(&out->px[(size_t)y * out->w], bm.buffer + (ptrdiff_t)y * bm.pitch, out->w);
+        }
+    }
+    f.reset_size();
+    return ok;
+}
+
+FT_Pos delta_of(float t) { return (FT_Pos)(int32_t)(t * 64.0f); }  // trunc(t * 64), as raster.cpp does for the bank
+
+// Canvas::blit_from: copy (not blend), clipped
+void blit(const Bitmap &b, int x0, int y0, uint8_t *canvas, size_t w, size_t h) {
+    for (int y = 0; y < b.h; y++) {
+        long cy = (long)y0 + y;
+        if (cy < 0 || cy >= (long)h) continue;
+        for (int x = 0; x < b.w; x++) {
+            long cx = (long)x0 + x;
+            if (cx < 0 || cx >= (long)w) continue;
+            canvas[(size_t)cy * w + cx] = b.px[(size_t)y * b.w + x];
+        }
+    }
+}
+
+// font.advance(gid).x in font units (loaded unhinted at char size = units_per_em, as font-kit keeps the face)
+bool advance_units(Face &f, FT_UInt gid, float *out) {
+    f.reset_size();
+    if (FT_Load_Glyph(f.face, gid, FT_LOAD_DEFAULT | FT_LOAD_NO_HINTING) != 0) return false;
+    *out = (float)f.face->glyph->advance.x / 64.0f;
+    return true;
+}
+
+// font.advance(gid) / units_per_em * size * kern_x, f32, left to right (src/main.rs:52-54, 177-179)
+float increment_of(float advance, float upem, float size, float kerning) { return advance / upem * size * kerning; }
+
+// One open face per thread and font path, for callers that rasterise glyph by glyph (the test model).
+struct CachedFace {
+    std::string path;
+    Face f;
+};
+thread_local CachedFace *g_cached = nullptr;
+
+Face *cached_face(const char *path) {
+    if (g_cached && g_cached->path == path) return &g_cached->f;
+    delete g_cached;
+    g_cached = new CachedFace;
+    g_cached->path = path;
+    if (FT_Init_FreeType(&g_cached->f.lib) != 0 || FT_New_Face(g_cached->f.lib, path, 0, &g_cached->f.face) != 0) {
+        delete g_cached;
+        g_cached = nullptr;
+        return nullptr;
+    }
+    return &g_cached->f;
+}
+
+bool open_face(Face &f, const char *path) {
+    return FT_Init_FreeType(&f.lib) == 0 && FT_New_Face(f.lib, path, 0, &f.face) == 0;
+}
+
+}  // namespace
+
+extern "C" int focr_raster_glyph(const char *font_path, float text_size, int hinting, uint32_t codepoint, float tx,
+                                 float ty, uint8_t *canvas, size_t w, size_t h, char *err, size_t errlen) {
+    if (!font_path || (!canvas && w && h)) return fail(err, errlen, "focr_raster_glyph: bad arguments");
+    Face *f = cached_face(font_path);
+    if (!f) return fail(err, errlen, "cannot open font");
+    FT_UInt gid = FT_Get_Char_Index(f->face, codepoint);
+    if (gid == 0) return fail(err, errlen, "character missing from font");
+    Bitmap b;
+    if (!render_delta(*f, gid, text_size, hinting, delta_of(tx), -delta_of(ty), &b))
+        return fail(err, errlen, "FT_Load_Glyph failed");
+    blit(b, b.left, b.top, canvas, w, h);
+    return 0;
+}
+
+extern "C" int focr_glyph_metrics(const char *font_path, float text_size, uint32_t codepoint, float *advance,
+                                  uint32_t *units_per_em, int32_t bounds[4], char *err, size_t errlen) {
+    if (!font_path || !advance || !units_per_em || !bounds) return fail(err, errlen, "focr_glyph_metrics: bad arguments");
+    Face *f = cached_face(font_path);
+    if (!f) return fail(err, errlen, "cannot open font");
+    FT_UInt gid = FT_Get_Char_Index(f->face, codepoint);
+    if (gid == 0) return fail(err, errlen, "character missing from font");
+    RectI r;
+    if (!advance_units(*f, gid, advance) || !f->raster_bounds(gid, text_size, 0.f, 0.f, &r))
+        return fail(err, errlen, "glyph load failed");
+    *units_per_em = f->face->units_per_EM;
+    bounds[0] = r.ox, bounds[1] = r.oy, bounds[2] = r.lx, bounds[3] = r.ly;
+    return 0;
+}
+
+extern "C" int focr_render_text(const char *font_path, float text_size, int hinting, float kerning, const uint32_t *text,
+                                size_t n, uint8_t **canvas, size_t *w, size_t *h, char *err, size_t errlen) {
+    if (!font_path || (!text && n) || !canvas || !w || !h) return fail(err, errlen, "focr_render_text: bad arguments");
+    *canvas = nullptr;
+    Face f;
+    if (!open_face(f, font_path)) return fail(err, errlen, "cannot open font");
+    const float upem = (float)f.face->units_per_EM;
+    std::vector<FT_UInt> gids(n);
+    std::vector<float> pos(n);
+    float pen = 0.f;
+    for (size_t i = 0; i < n; i++) {  // src/main.rs:48-55
+        gids[i] = FT_Get_Char_Index(f.face, text[i]);
+        if (gids[i] == 0) return fail(err, errlen, "character missing from font");  // glyph_for_char(..).unwrap()
+        pos[i] = pen;
+        float adv;
+        if (!advance_units(f, gids[i], &adv)) return fail(err, errlen, "glyph load failed");
+        pen = pen + increment_of(adv, upem, text_size, kerning);
+    }
+    RectF bounds;  // src/main.rs:57-70: the fold starts from the empty rect at (0, 0)
+    for (size_t i = 0; i < n; i++) {
+        RectI r;
+        if (!f.raster_bounds(gids[i], text_size, pos[i], 0.f, &r)) return fail(err, errlen, "glyph load failed");
+        bounds = union_rect(bounds, RectF{(float)r.ox, (float)r.oy, (float)r.lx, (float)r.ly});
+    }
+    // bounds.round().to_i32().size()
+    const long cw = std::lround(bounds.lx) - std::lround(bounds.ox), ch = std::lround(bounds.ly) - std::lround(bounds.oy);
+    if (cw < 0 || ch < 0 || cw > 1 << 20 || ch > 1 << 16) return fail(err, errlen, "canvas too large");
+    *w = (size_t)cw;
+    *h = (size_t)ch;
+    *canvas = (uint8_t *)calloc((size_t)cw * ch + 1, 1);
+    if (!*canvas) return fail(err, errlen, "out of memory");
+    for (size_t i = 0; i < n; i++) {  // src/main.rs:74-83: translation -bounds.origin + pos
+        Bitmap b;
+        if (!render_delta(f, gids[i], text_size, hinting, delta_of(-bounds.ox + pos[i]), -delta_of(-bounds.oy + 0.f), &b)) {
+            free(*canvas);
+            *canvas = nullptr;
+            return fail(err, errlen, "FT_Load_Glyph failed");
+        }
+        blit(b, b.left, b.top, *canvas, *w, *h);
+    }
+    return 0;
+}
+
+extern "C" int focr_decode_font_build(const char *font_path, float text_size, int hinting, float kerning,
+                                      const uint32_t *alphabet, size_t n_alphabet, focr_decode_font_t *out, char *err,
+                                      size_t errlen) {
+    if (!font_path || !alphabet || !n_alphabet || !out) return fail(err, errlen, "focr_decode_font_build: bad arguments");
+    memset(out, 0, sizeof *out);
+    // DIVERGENCE: the reference's pen loop never ends for kerning <= 0 or a glyph that does not advance
+    if (!(kerning > 0.f)) return fail(err, errlen, "kerning must be > 0 (the reference never finishes a line otherwise)");
+    Face f;
+    if (!open_face(f, font_path)) return fail(err, errlen, "cannot open font");
+    const float upem = (float)f.face->units_per_EM;
+    std::vector<FT_UInt> gids(n_alphabet);
+    RectF bbox;  // src/main.rs:136-147: union of raster_bounds(identity), folded from the empty rect at (0, 0)
+    for (size_t i = 0; i < n_alphabet; i++) {
+        gids[i] = FT_Get_Char_Index(f.face, alphabet[i]);
+        if (gids[i] == 0) {
+            char m[96];
+            snprintf(m, sizeof m, "alphabet character U+%04X missing from font", (unsigned)alphabet[i]);
+            return fail(err, errlen, m);
+        }
+        RectI r;
+        if (!f.raster_bounds(gids[i], text_size, 0.f, 0.f, &r)) return fail(err, errlen, "glyph load failed");
+        bbox = union_rect(bbox, RectF{(float)r.ox, (float)r.oy, (float)r.lx, (float)r.ly});
+    }
+    const float origin_x = -bbox.ox, origin_y = -bbox.oy;
+    const FT_Pos dy = -delta_of(origin_y + 0.f);  // origin + pos, pos.y = 0
+
+    std::vector<focr_decode_glyph_t> glyphs(n_alphabet);
+    std::vector<uint8_t> bitmaps;
+    float min_inc = 0.f;
+    for (size_t i = 0; i < n_alphabet; i++) {
+        focr_decode_glyph_t &g = glyphs[i];
+        memset(&g, 0, sizeof g);
+        g.codepoint = alphabet[i];
+        float adv;
+        if (!advance_units(f, gids[i], &adv)) return fail(err, errlen, "glyph load failed");
+        g.increment = increment_of(adv, upem, text_size, kerning);
+        if (!(g.increment > 0.f)) {
+            char m[128];
+            snprintf(m, sizeof m, "glyph of U+%04X does not advance the pen (the reference never finishes a line)", (unsigned)alphabet[i]);
+            return fail(err, errlen, m);
+        }
+        min_inc = i == 0 ? g.increment : std::fmin(min_inc, g.increment);
+        std::vector<Bitmap> ph(FOCR_DECODE_PHASES);
+        int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+        bool any = false;
+        for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
+            if (!render_delta(f, gids[i], text_size, hinting, p, dy, &ph[p])) return fail(err, errlen, "FT_Load_Glyph failed");
+            const Bitmap &b = ph[p];
+            if (!b.w || !b.h) continue;
+            x0 = any ? std::min(x0, b.left) : b.left;
+            y0 = any ? std::min(y0, b.top) : b.top;
+            x1 = any ? std::max(x1, b.left + b.w) : b.left + b.w;
+            y1 = any ? std::max(y1, b.top + b.h) : b.top + b.h;
+            any = true;
+        }
+        g.box_w = (uint32_t)(x1 - x0);
+        g.box_h = (uint32_t)(y1 - y0);
+        g.stride = (g.box_w + 3) & ~3u;
+        // the device keeps sum c^2 and sum c*r of a glyph in 32 bits: score = sum c^2 - 2 sum c*r, |score| <= 2 * 255^2 * area
+        if ((uint64_t)g.stride * g.box_h * 2 * 255 * 255 >= (1ull << 31)) return fail(err, errlen, "glyph box too large for the decoder");
+        g.offset = bitmaps.size();
+        bitmaps.resize(bitmaps.size() + (size_t)FOCR_DECODE_PHASES * g.stride * g.box_h, 0);
+        for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
+            g.off_x[p] = x0;
+            g.off_y[p] = y0;
+            const Bitmap &b = ph[p];
+            uint8_t *dst = bitmaps.data() + g.offset + (size_t)p * g.stride * g.box_h;
+            for (int y = 0; y < b.h; y++)
+                memcpy(dst + (size_t)(b.top - y0 + y) * g.stride + (b.left - x0), &b.px[(size_t)y * b.w], b.w);
+        }
+    }
+    out->glyphs = (focr_decode_glyph_t *)malloc(sizeof(focr_decode_glyph_t) * n_alphabet);
+    out->bitmaps = (uint8_t *)malloc(bitmaps.size() ? bitmaps.size() : 1);
+    if (!out->glyphs || !out->bitmaps) {
+        focr_decode_font_free(out);
+        return fail(err, errlen, "out of memory");
+    }
+    memcpy(out->glyphs, glyphs.data(), sizeof(focr_decode_glyph_t) * n_alphabet);
+    if (!bitmaps.empty()) memcpy(out->bitmaps, bitmaps.data(), bitmaps.size());
+    out->n_glyphs = n_alphabet;
+    out->bitmaps_len = bitmaps.size();
+    out->origin_x = origin_x;
+    out->origin_y = origin_y;
+    out->text_size = text_size;
+    out->kerning = kerning;
+    out->hinting = hinting;
+    out->min_increment = min_inc;
+    return 0;
+}
+
+extern "C" void focr_decode_font_free(focr_decode_font_t *font) {
+    if (!font) return;
+    free(font->glyphs);
+    free(font->bitmaps);
+    memset(font, 0, sizeof *font);
 }

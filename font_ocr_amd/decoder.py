@@ -1,0 +1,188 @@
+"""The `focr` line decoder (src/main.rs of the reference): host side and the device decoder, over include/focr_decode.h.
+
+    with LineDecoder(0) as dec:
+        dec.set_font("DejaVuSansMono.ttf", 13.0)
+        pages = dec.decode(luma_pages, x=45, y=39, width=608, line_height=12, line_advance=15)
+        # [[(y, text), ...] per page]
+
+There is no CPU path: the decoder needs a device, and says so when it has none.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+
+FOCR_DEFAULT_ALPHABET = "> =ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/"  # src/main.rs:13-14
+
+
+class DecoderError(RuntimeError):
+    pass
+
+
+def _err():
+    return C.create_string_buffer(512)
+
+
+def _codepoints(text):
+    cps = [ord(c) for c in text]
+    return (C.c_uint32 * max(1, len(cps)))(*cps), len(cps)
+
+
+def raster_glyph(font_path, text_size, char, tx, ty, canvas, hinting=False):
+    """focr_raster_glyph: copy the glyph rendered at float translation (tx, ty) into `canvas` (uint8 h x w, in place)."""
+    assert canvas.dtype == np.uint8 and canvas.flags.c_contiguous and canvas.ndim == 2
+    e = _err()
+    h, w = canvas.shape
+    if N.decode_raster().focr_raster_glyph(font_path.encode(), float(text_size), int(hinting), ord(char), float(tx), float(ty),
+                                           canvas.ctypes.data, w, h, e, len(e)) != 0:
+        raise DecoderError(e.value.decode())
+    return canvas
+
+
+def glyph_metrics(font_path, text_size, char):
+    """(advance in font units as f32, units_per_em, raster_bounds at the identity as (ox, oy, lx, ly))."""
+    adv, upem, b, e = C.c_float(), C.c_uint32(), (C.c_int32 * 4)(), _err()
+    if N.decode_raster().focr_glyph_metrics(font_path.encode(), float(text_size), ord(char), C.byref(adv), C.byref(upem), b, e,
+                                            len(e)) != 0:
+        raise DecoderError(e.value.decode())
+    return np.float32(adv.value), int(upem.value), tuple(int(v) for v in b)
+
+
+def render_text(font_path, text_size, text, kerning=1.0, hinting=False):
+    """focr_render_text: render() of the reference (src/main.rs:40-85) -> uint8 coverage canvas (h x w, 255 = ink)."""
+    cps, n = _codepoints(text)
+    p, w, h, e = C.c_void_p(), C.c_size_t(), C.c_size_t(), _err()
+    lib = N.decode_raster()
+    if lib.focr_render_text(font_path.encode(), float(text_size), int(hinting), float(kerning), cps, n, C.byref(p), C.byref(w),
+                            C.byref(h), e, len(e)) != 0:
+        raise DecoderError(e.value.decode())
+    try:
+        out = np.ctypeslib.as_array((C.c_uint8 * max(1, w.value * h.value)).from_address(p.value)).copy()
+    finally:
+        C.CDLL(None).free(p)
+    return out[: w.value * h.value].reshape(h.value, w.value)
+
+
+class DecodeFont:
+    """The 64-phase table of an alphabet (focr_decode_font_build).  Owns the native struct; free with close()."""
+
+    def __init__(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0):
+        self.font_path, self.text_size, self.alphabet = font_path, float(text_size), alphabet
+        self.hinting, self.kerning = bool(hinting), float(kerning)
+        self.s = N.DecodeFontStruct()
+        cps, n = _codepoints(alphabet)
+        e = _err()
+        if N.decode_raster().focr_decode_font_build(font_path.encode(), self.text_size, int(hinting), self.kerning, cps, n,
+                                                    C.byref(self.s), e, len(e)) != 0:
+            raise DecoderError(e.value.decode())
+
+    @property
+    def origin(self):
+        return np.float32(self.s.origin_x), np.float32(self.s.origin_y)
+
+    def increments(self):
+        return np.array([self.s.glyphs[i].increment for i in range(self.s.n_glyphs)], dtype=np.float32)
+
+    def phase(self, i, p):
+        """(bitmap h x w, off_x, off_y) of glyph i's phase p."""
+        g = self.s.glyphs[i]
+        n = g.stride * g.box_h
+        raw = np.ctypeslib.as_array(self.s.bitmaps, shape=(self.s.bitmaps_len,))
+        bm = raw[g.offset + p * n: g.offset + (p + 1) * n].reshape(g.box_h, g.stride)[:, : g.box_w]
+        return bm.copy(), int(g.off_x[p]), int(g.off_y[p])
+
+    def close(self):
+        if self.s is not None:
+            N.decode_raster().focr_decode_font_free(C.byref(self.s))
+            self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LineDecoder:
+    """focr's decode_image on one device: set_font(), then decode() batches of luma pages."""
+
+    def __init__(self, device=0):
+        self._lib = N.decode_hip()
+        h = C.c_void_p()
+        if self._lib.focr_decoder_create(int(device), C.byref(h)) != 0:
+            raise DecoderError(self._lib.focr_decoder_last_error(None).decode())
+        self._h = h
+        self.font = None
+        self.last_ms = 0.0
+
+    def _check(self, rc):
+        if rc != 0:
+            raise DecoderError(self._lib.focr_decoder_last_error(self._h).decode())
+
+    def set_font(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0):
+        font = font_path if isinstance(font_path, DecodeFont) else DecodeFont(font_path, text_size, alphabet, hinting, kerning)
+        self._check(self._lib.focr_decoder_set_font(self._h, C.byref(font.s)))
+        self.font = font
+        return font
+
+    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance):
+        self._check(self._lib.focr_decoder_run(self._h, ptr, int(on_device), n, w, h, x, y, width, line_height, line_advance))
+        self.last_ms = float(self._lib.focr_decoder_last_ms(self._h))
+        nl, nc = self._lib.focr_decoder_n_lines(self._h), self._lib.focr_decoder_n_chars(self._h)
+        lines = (N.DecodedLine * max(1, nl))()
+        chars = np.zeros(max(1, nc), dtype=np.uint16)
+        self._check(self._lib.focr_decoder_get(self._h, lines, chars.ctypes.data))
+        alpha = self.font.alphabet
+        out = [[] for _ in range(n)]
+        for k in range(nl):
+            ln = lines[k]
+            text = "".join(alpha[c] for c in chars[ln.first: ln.first + ln.n_chars])
+            out[ln.page].append((int(ln.y), text))
+        return out
+
+    def decode(self, luma_pages, x, y, width, line_height, line_advance):
+        """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
+        Returns [[(y, text), ...] per page] in page order."""
+        if self.font is None:
+            raise DecoderError("set_font() first")
+        geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
+        if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
+            pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
+        else:
+            pages = list(luma_pages)
+        out = [None] * len(pages)
+        by_size = {}
+        for i, p in enumerate(pages):
+            by_size.setdefault(np.asarray(p).shape, []).append(i)
+        for (h, w), idx in by_size.items():
+            batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
+            res = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo)
+            for i, r in zip(idx, res):
+                out[i] = r
+        return out
+
+    def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance):
+        """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
+        this library uses, on the decoder's device, written before the call)."""
+        if self.font is None:
+            raise DecoderError("set_font() first")
+        return self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
+                         int(line_height), int(line_advance))
+
+    def close(self):
+        if self._h is not None:
+            self._lib.focr_decoder_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,117 @@
+/*
+ * focr_decode.h — C ABI of the `focr` line decoder (the upstream package's default binary, src/main.rs).
+ *
+ * The reference decodes a text line by rasterising every alphabet glyph at the current pen position with FreeType,
+ * scoring it by the sum of squared differences against the whole line canvas, taking the first minimum and moving the
+ * pen by that glyph's advance (decode_line, src/main.rs:112-181).  The 26.6 translation FreeType receives is
+ * trunc(t * 64), so a glyph has at most 64 distinct sub-pixel renderings and a whole-pixel shift only moves the bitmap:
+ * the decode font below holds those 64 phases per glyph, built once on the host, and the device does an exact integer
+ * argmin with them.
+ *
+ * libfocr_raster.so : focr_raster_glyph, focr_glyph_metrics, focr_render_text, focr_decode_font_build/free (FreeType)
+ * libfocr_hip.so    : focr_decoder_* (gfx950)
+ */
+#ifndef FOCR_DECODE_H
+#define FOCR_DECODE_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- host: rasterisation (libfocr_raster.so) --------------------------------------------------------------------- */
+
+/* font-kit's rasterize_glyph for a pure translation (tx, ty) onto a zero-or-not caller canvas of w x h bytes (A8,
+ * row-major): FreeType delta = (trunc(tx * 64), -trunc(ty * 64)), the bitmap copied (not blended) at
+ * (bitmap_left, -bitmap_top), clipped to the canvas.  The face is cached per thread and font path.  Returns 0, or
+ * non-zero with a message in err (no glyph for the code point, unreadable font). */
+int focr_raster_glyph(const char *font_path, float text_size, int hinting, uint32_t codepoint, float tx, float ty,
+                      uint8_t *canvas, size_t w, size_t h, char *err, size_t errlen);
+
+/* The glyph queries decode_line makes: font.advance(gid).x in font units, units_per_em, and
+ * raster_bounds(gid, size, identity) as (origin x, origin y, lower-right x, lower-right y) in px. */
+int focr_glyph_metrics(const char *font_path, float text_size, uint32_t codepoint, float *advance, uint32_t *units_per_em,
+                       int32_t bounds[4], char *err, size_t errlen);
+
+/* render() (src/main.rs:40-85) of a whole string: pen positions advance by font.advance / upem * size * kerning (f32),
+ * the canvas is the rounded union of every glyph's raster bounds at its pen position, each glyph is copied in turn at
+ * -bounds.origin + pos.  *canvas is malloc'ed (w x h A8 bytes, 255 = ink; free with free()). */
+int focr_render_text(const char *font_path, float text_size, int hinting, float kerning, const uint32_t *text, size_t n,
+                     uint8_t **canvas, size_t *w, size_t *h, char *err, size_t errlen);
+
+/* ---- host: the decode font (libfocr_raster.so) ------------------------------------------------------------------- */
+
+enum { FOCR_DECODE_PHASES = 64 };
+
+/* One alphabet glyph.  Phase p is the rendering at 26.6 delta x = p (and the font's fixed delta y): a box_h x stride
+ * byte bitmap at bitmaps + offset + p * box_h * stride, whose top-left pixel lands on the canvas at
+ * (shift + off_x[p], off_y[p]) for a delta x of 64 * shift + p.  All 64 phases share the box size. */
+typedef struct focr_decode_glyph {
+    uint32_t codepoint;
+    float increment;                         /* pen increment in px: advance / upem * size * kerning, f32, left to right */
+    uint32_t box_w, box_h, stride;           /* box in px; stride = box_w rounded up to 4 bytes */
+    uint64_t offset;                         /* byte offset of phase 0 in bitmaps */
+    int32_t off_x[FOCR_DECODE_PHASES];
+    int32_t off_y[FOCR_DECODE_PHASES];
+} focr_decode_glyph_t;
+
+typedef struct focr_decode_font {
+    focr_decode_glyph_t *glyphs;             /* alphabet order */
+    size_t n_glyphs;
+    uint8_t *bitmaps;
+    size_t bitmaps_len;
+    float origin_x, origin_y;                /* -bbox.origin, bbox = union of raster_bounds(identity) with the empty rect at 0 */
+    float text_size, kerning;
+    int hinting;
+    float min_increment;
+} focr_decode_font_t;
+
+/* Build the decode font for an alphabet (code points, in order).  Fails with a message if a code point has no glyph,
+ * if kerning <= 0 or if any increment is <= 0 (the reference loops forever there), or if a glyph's box is too large for
+ * the device's 32-bit scores.  Free with focr_decode_font_free. */
+int focr_decode_font_build(const char *font_path, float text_size, int hinting, float kerning, const uint32_t *alphabet,
+                           size_t n_alphabet, focr_decode_font_t *out, char *err, size_t errlen);
+void focr_decode_font_free(focr_decode_font_t *font);
+
+/* ---- device: the decoder (libfocr_hip.so) ------------------------------------------------------------------------ */
+
+typedef struct focr_decoder focr_decoder_t;
+
+/* One decoded, non-blank line: page index in the batch, crop y, and n_chars alphabet indices at chars + first. */
+typedef struct focr_decoded_line {
+    uint32_t page, y;
+    uint64_t first;
+    uint32_t n_chars;
+    uint32_t pad;
+} focr_decoded_line_t;
+
+/* A decoder on one device.  Non-zero (message in focr_decoder_last_error(NULL)) if there is no usable device: there is
+ * no CPU fallback. */
+int focr_decoder_create(int device, focr_decoder_t **out);
+void focr_decoder_destroy(focr_decoder_t *dec);
+/* The last error of dec, or of the calling thread's last failed create when dec is NULL. */
+const char *focr_decoder_last_error(const focr_decoder_t *dec);
+/* Upload a decode font (the decoder keeps its own copy). */
+int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font_t *font);
+/* Decode a batch of n_pages equal-size luma pages (page_h rows of page_w bytes, 255 = paper, pages back to back) from
+ * host memory, or from device memory of the decoder's device when on_device != 0 (the caller orders its writes before
+ * the call).  Line geometry as the reference's DecodeOptions.  Runs a fixed number of launches and returns when the
+ * results are on the host.  line_advance == 0 with a non-empty first crop is refused (the reference never ends). */
+int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int on_device, size_t n_pages, size_t page_w, size_t page_h,
+                     uint32_t x_start, uint32_t y_start, uint32_t width, uint32_t line_height, uint32_t line_advance);
+/* Results of the last run: number of lines, total characters, and a copy into caller arrays (lines[n_lines],
+ * chars[n_chars], in (page, line) order). */
+size_t focr_decoder_n_lines(const focr_decoder_t *dec);
+size_t focr_decoder_n_chars(const focr_decoder_t *dec);
+int focr_decoder_get(const focr_decoder_t *dec, focr_decoded_line_t *lines, uint16_t *chars);
+/* Device time of the last run's kernels (prepass, compaction, decode) in ms, from events. */
+float focr_decoder_last_ms(const focr_decoder_t *dec);
+/* Kernel launches of the last run (constant per batch). */
+uint32_t focr_decoder_last_launches(const focr_decoder_t *dec);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* FOCR_DECODE_H */

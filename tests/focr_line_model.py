@@ -1,0 +1,108 @@
+"""Brute-force restatement of the reference's focr decoder (src/main.rs:112-218, 300-329, 518-524), for the tests.
+
+Every candidate is rasterised directly with focr_raster_glyph at its float translation, scored over the whole canvas
+in int64, and the first minimum wins.  It shares FreeType (through focr_raster_glyph / focr_glyph_metrics) with the
+product and nothing else: no phase table, no increments or origin from the decode font.  Slow on purpose: keep pages small.
+"""
+import numpy as np
+
+from font_ocr_amd.decoder import glyph_metrics, raster_glyph, render_text
+
+F32 = np.float32
+
+
+def increment(font, size, ch, kerning):
+    adv, upem, _ = glyph_metrics(font, size, ch)
+    return F32(F32(F32(adv) / F32(upem)) * F32(size)) * F32(kerning)
+
+
+def origin(font, size, alphabet):
+    """-bbox.origin, bbox folded over raster_bounds(identity) from the empty rect at (0, 0) (src/main.rs:136-148)."""
+    ox, oy = F32(0), F32(0)
+    for ch in alphabet:
+        b = glyph_metrics(font, size, ch)[2]
+        ox, oy = min(ox, F32(b[0])), min(oy, F32(b[1]))
+    return -ox, -oy
+
+
+def decode_line(ref, font, size, alphabet, kerning=1.0, hinting=False):
+    """decode_line on one cropped luma line (h x w uint8)."""
+    h, w = ref.shape
+    r = 255 - ref.astype(np.int64)
+    ox, oy = origin(font, size, alphabet)
+    incs = [increment(font, size, ch, kerning) for ch in alphabet]
+    pos, text = F32(0), []
+    canvas = np.zeros((h, w), dtype=np.uint8)
+    while pos < F32(w):
+        best = None
+        for i, ch in enumerate(alphabet):
+            canvas[:] = 0
+            raster_glyph(font, size, ch, F32(ox + pos), oy, canvas, hinting)
+            s = int(((r - canvas.astype(np.int64)) ** 2).sum())
+            if best is None or s < best[0]:
+                best = (s, i)
+        text.append(alphabet[best[1]])
+        pos = F32(pos + incs[best[1]])
+    return "".join(text)
+
+
+def crop(page, x, y, width, height):
+    """image::DynamicImage::crop_imm's clamping."""
+    H, W = page.shape
+    x, y = min(x, W), min(y, H)
+    return page[y: y + min(height, H - y), x: x + min(width, W - x)]
+
+
+def decode_image(page, font, size, alphabet, x, y, width, line_height, line_advance, kerning=1.0, hinting=False):
+    """decode_image: [(y, text)] of every non-blank line."""
+    out = []
+    i = 0
+    while True:
+        ly = y + i * line_advance
+        i += 1
+        line = crop(page, x, ly, width, line_height)
+        if line.shape[0] == 0:
+            return out
+        if np.all(line == 255):
+            continue
+        out.append((ly, decode_line(line, font, size, alphabet, kerning, hinting)))
+
+
+def verify_image(page, lines, font, size, x, kerning=1.0, hinting=False):
+    """draw_verify (text outside the page clipped) and red_blue_mse as an f32."""
+    H, W = page.shape
+    out = np.zeros((H, W, 3), dtype=np.uint8)
+    out[..., 0] = np.where(page != 255, page, 0)
+    for ly, text in lines:
+        c = render_text(font, size, text, kerning, hinting)
+        for yy, xx in zip(*np.nonzero(c)):
+            if x + xx < W and ly + yy < H:
+                out[ly + yy, x + xx, 2] = 255 - c[yy, xx]
+    d = out[..., 0].astype(np.int64) - out[..., 2].astype(np.int64)
+    mse = F32(F32(int((d * d).sum())) / F32(W * H))
+    return out, mse
+
+
+def synth_page(rng, font, size, alphabet, W, H, x, y, line_advance, n_lines, kerning=1.0, hinting=False, blank_every=0,
+               noise=0):
+    """White page with n_lines random lines of `alphabet` rendered by focr_render_text at (x, y + i * line_advance);
+    every blank_every-th line left empty; optional uniform noise of +-noise.  Returns (page, texts)."""
+    page = np.full((H, W), 255, dtype=np.uint8)
+    texts = []
+    for i in range(n_lines):
+        ly = y + i * line_advance
+        if blank_every and i % blank_every == blank_every - 1:
+            texts.append(None)
+            continue
+        n = int(rng.integers(3, 40))
+        t = "".join(alphabet[j] for j in rng.integers(0, len(alphabet), n))
+        texts.append(t)
+        c = render_text(font, size, t, kerning, hinting)
+        hh, ww = min(c.shape[0], H - ly), min(c.shape[1], W - x)
+        if hh > 0 and ww > 0:
+            region = page[ly: ly + hh, x: x + ww]
+            region[:] = np.minimum(region, 255 - c[:hh, :ww])
+    if noise:
+        n = rng.integers(-noise, noise + 1, page.shape)
+        page = np.clip(page.astype(np.int32) + n, 0, 255).astype(np.uint8)
+    return page, texts

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Throughput of the focr line decoder: one JSON line for a batch of synthetic 608x720 pages (DejaVu Sans Mono 13 px,
+focr's default alphabet, 40 text lines at line_advance 15, decoded at x 45, y 39, width 608, line height 12).
+
+  host_table_ms        building the 64-phase decode font on the host (FreeType)
+  device_ms_per_batch  median over --steps runs after --warmup, device events around the batch's kernels
+  wall_ms_per_batch    median host time of one decode() call (upload, launches, read-back)
+  pages/s, lines/s and page Mpx/s from the device time
+
+No reference number: the reference's Rust / font-kit build is not available to run beside it.  Kernel times per
+launch come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from font_ocr_amd import FOCR_DEFAULT_ALPHABET, DecodeFont, LineDecoder  # noqa: E402
+from font_ocr_amd.decoder import render_text  # noqa: E402
+
+FONT = os.path.join(ROOT, "tests", "golden", "DejaVuSansMono.ttf")
+
+
+def synth(n_pages, seed, W=608, H=720, x=45, y=39, n_lines=40, advance=15, size=13.0):
+    rng = np.random.default_rng(seed)
+    ink = FOCR_DEFAULT_ALPHABET.replace(" ", "")
+    pages = np.full((n_pages, H, W), 255, dtype=np.uint8)
+    for p in range(n_pages):
+        for i in range(n_lines):
+            words = [''.join(rng.choice(list(ink), int(rng.integers(2, 10)))) for _ in range(12)]
+            c = render_text(FONT, size, " ".join(words)[:68])
+            ly = y + i * advance
+            hh, ww = min(c.shape[0], H - ly), min(c.shape[1], W - x)
+            pages[p, ly: ly + hh, x: x + ww] = np.minimum(pages[p, ly: ly + hh, x: x + ww], 255 - c[:hh, :ww])
+    return pages
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pages", type=int, default=128)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    pages = synth(a.pages, a.seed)
+    geo = (45, 39, 608, 12, 15)
+    t0 = time.perf_counter()
+    font = DecodeFont(FONT, 13.0, FOCR_DEFAULT_ALPHABET)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    with LineDecoder(0) as dec:
+        dec.set_font(font, 13.0)
+        for _ in range(a.warmup):
+            out = dec.decode(pages, *geo)
+        dev, wall = [], []
+        for _ in range(a.steps):
+            t = time.perf_counter()
+            out = dec.decode(pages, *geo)
+            wall.append((time.perf_counter() - t) * 1e3)
+            dev.append(dec.last_ms)
+        launches = int(dec._lib.focr_decoder_last_launches(dec._h))
+    n_lines = sum(len(p) for p in out)
+    n_chars = sum(len(t) for p in out for _, t in p)
+    ms = float(np.median(dev))
+    print(json.dumps({
+        "bench": "focr_decode", "pages": a.pages, "page_w": 608, "page_h": 720, "lines": n_lines, "chars": n_chars,
+        "font": "DejaVuSansMono 13px", "alphabet_len": len(FOCR_DEFAULT_ALPHABET), "launches_per_batch": launches,
+        "host_table_ms": round(host_ms, 2), "device_ms_per_batch": round(ms, 4), "device_ms_min": round(float(min(dev)), 4),
+        "wall_ms_per_batch": round(float(np.median(wall)), 3), "steps": a.steps, "warmup": a.warmup,
+        "pages_per_s": round(a.pages / ms * 1e3, 1), "lines_per_s": round(n_lines / ms * 1e3, 1),
+        "page_mpx_per_s": round(a.pages * 608 * 720 / ms / 1e3, 1),
+    }))
+
+
+if __name__ == "__main__":
+    main()
