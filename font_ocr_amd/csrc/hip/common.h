@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
@@ -43,9 +44,10 @@ struct SuperClass {
     std::vector<uint32_t> tile_first;  // first N-tile of each class inside the super-class
     uint32_t n_tiles;
     size_t q_offset, tg_offset;
-    // per scan: window enumeration of the pass (smallest searchable template) and its live-tile list
+    // per scan (plan_scan): window enumeration of the pass (smallest searchable template), its live-tile list, its threshold planes
     uint32_t min_w, min_h, mtx, n_rows;
-    size_t live_offset;
+    size_t live_offset, plane_off;  // plane_off: first value in d_planes, if `planes` (else the legacy path: int32 tables in d_L)
+    bool planes;
 };
 
 // Per-template constants, computed once on the host in IEEE double exactly as
@@ -109,6 +111,23 @@ __host__ __device__ inline uint32_t row_of_key(uint64_t key, const RowHist &h) {
     return (((line >> h.by) - h.page_base) * h.r_h + (line & ((1u << h.by) - 1u))) * h.n_seg + (x >> h.seg_shift);
 }
 
+// Size estimates of one setup (focr_ctx::est_sig: bank, device, geometry, threshold, cap, mode) for its next scan (ctx.hip: focr_scan,
+// finish_results).  Bounds only: a count above its bound redoes the batch with exact sizes.
+struct SizeEstimate {
+    size_t cand = 0, hits = 0;  // bounds of the next scan: the last counts + margin() (0: none, exact sizes)
+    double var = 0.0667;        // how much the counts of consecutive scans have differed lately (relative; decays by a quarter per scan)
+    uint64_t last_cand = 0, last_hits = 0;
+    uint32_t row_max = 0;    // largest row of the last scan (estimated mode picks the row capacity from it; 0: it took the legacy tail)
+    uint32_t seg_shift = 0;  // log2 of the x-segment width of the row buckets (0: not chosen yet; rows.hip, row_segments)
+    void reset() { *this = SizeEstimate{}; }
+    double margin() const { return std::min(0.2, std::max(0.04, 3.0 * var)); }  // 4 .. 20 %
+    uint64_t row_bound() const { return (uint64_t)row_max + row_max / 4 + 16; }   // the next scan's largest row: the last + 25 %
+    void update(const focr_ctx *c, uint64_t n_cand, uint64_t n_hits);  // a finished batch's counts (and its largest row bucket)
+    void adopt(uint64_t sig);  // shared with the other contexts of the process that scan the same setup (ctx.hip: g_est)
+    void publish(uint64_t sig) const;
+    static void forget(uint64_t sig);
+};
+
 }  // namespace focr
 
 // Item queues of the persistent scan kernels (scan_mfma2.hip): one per launch, QUEUE_XCDS counters QUEUE_STRIDE dwords
@@ -154,11 +173,8 @@ struct focr_ctx {
     size_t ub_hits = 0;                  // the bound its buffers were sized for
     uint64_t n_hits_raw_u64 = 0;
     bool sizes_pending = false, post_pending = false, estimated = false, estimates_enabled = true;
-    size_t est_cand = 0, est_hits = 0, ub_cand = 0;
-    // how much the counts of consecutive scans of one setup have differed lately (relative; decays by a quarter per scan):
-    // the next scan's bounds are the last counts + 3 x this, between 4 % and 20 % (finish_results)
-    double est_var = 0.0667;
-    uint64_t est_last_cand = 0, est_last_hits = 0;
+    focr::SizeEstimate est;
+    size_t ub_cand = 0;
     uint64_t est_sig = 0, bank_gen = 0, bank_hash = 0, counters_redone = 0;
     float scan_thr = 0.f, post_anchor = 0.f;
     int scan_mode = 0;
@@ -168,7 +184,7 @@ struct focr_ctx {
     uint32_t dbg_grid_num = 0, dbg_grid_den = 0;  // tests: the tail's persistent kernels on num / den times their workgroups (focr_debug_set_tail_grid; 0: as designed)
     int prefilter = 0;                          // FOCR_PREFILTER_*: auto / plane kernel / legacy kernel (focr_ctx_set_prefilter)
     uint16_t *d_planes = nullptr;               // threshold planes, int16: [super-class][value][page][Lrows][Lpitch] (mfma_common.h)
-    size_t planes_bytes = 0;
+    size_t plane_values = 0;
     uint32_t *d_tglobal = nullptr;              // class-ordered -> global template index, 0xffffffff = never emits
     uint32_t *d_order_of = nullptr;             // global template index -> class-ordered index
     std::vector<double> mfma_c_scale, mfma_e_max, mfma_rho_max;  // per class: quantisation scale, max rounding-error norm, max norm of a unit template's dropped column
@@ -212,13 +228,12 @@ struct focr_ctx {
     uint64_t *d_hit_keys = nullptr, *d_hit_keys_alt = nullptr;
     float *d_hit_sims = nullptr, *d_hit_sims_alt = nullptr;
     uint32_t *d_counter = nullptr;  // u64 [0] hits, u64 [1] candidates, u32 [8..47] live M-tile counts, then the scan kernels' item queues
-    unsigned stats_turn = 0;        // this batch's place in the device's chain of statistics launches (launch_scan_mfma)
     uint32_t scan_queues_used = 0;  // item queues handed out since the last reset (launch_scan_mfma)
-    size_t cand_capacity = 0, cand_alt_capacity = 0;
+    size_t cand_capacity = 0, cand_alt_capacity = 0;  // entries in d_cand / d_cand_alt
     uint64_t *d_cand = nullptr, *d_cand_alt = nullptr;
     bool ordered = false;  // the scan path already produced d_matches (MFMA path); order_hits is skipped
     int32_t *d_L = nullptr;  // prefilter thresholds [class][page][r_h][pitchL]
-    size_t L_bytes = 0;
+    size_t L_values = 0;
     void *d_sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
     size_t n_hits_raw = 0;    // hits before the cap
@@ -248,9 +263,6 @@ struct focr_ctx {
     focr::RowHist row_hist{};   // what the scan kernels' flush path counts into (cnt == nullptr: legacy tail)
     DevBuf rows_hits, rows_hbase, rows_big;
     uint32_t row_cap = 0;       // per-row candidate capacity the row kernel was instantiated for in the last scan
-    uint32_t est_row_max = 0;   // largest row of the previous scan of this setup (estimated mode picks the capacity from it)
-    uint32_t row_seg_shift = 0; // log2 of the x-segment width of the buckets (0: not chosen yet for this setup; rows.hip, row_segments)
-    bool chunked_verify = true; // hits-first tail, banks above the LDS: verify in chunk passes (false: template rows gathered from global memory; FOCR_VERIFY_GLOBAL, A/B)
     int tail_mode = 1;          // focr_ctx_set_row_tail(): 0 = the legacy tail (radix sort + verify + compaction), 1 = hits-first row tail
                                 // (verify in flush order, hits bucketed + sorted: the default)
     DevBuf ord_k2, ord_k2_alt, ord_v, ord_v_alt, ord_keep;

@@ -12,15 +12,51 @@ namespace focr {
 static std::mutex g_err_mu;
 static std::string g_err;
 
-// Size estimates shared between the contexts of a process (ctx.hip: focr_scan, finish_results), keyed by the setup's signature
-// (bank content, device, geometry, threshold, cap, mode): bounds only — a count above its bound redoes the batch exactly.
-struct SharedEstimate {
-    size_t cand, hits;
-    uint32_t row_max, seg_shift;
-};
+// Size estimates shared between the contexts of a process, keyed by the setup's signature (SizeEstimate::publish / adopt)
 static std::mutex g_est_mu;
-static std::unordered_map<uint64_t, SharedEstimate> g_est;
+static std::unordered_map<uint64_t, SizeEstimate> g_est;
 static hipEvent_t g_base_event[64] = {};  // per device: the origin of focr_debug_phase_stamps (guarded by g_est_mu)
+
+void row_segments(const focr_ctx *c, uint32_t *seg_shift, uint32_t *n_seg);  // rows.hip
+
+// bounds for the next scan of the same setup: this scan's counts + a margin that follows how much the counts have been moving (20 %
+// after the first scan of a setup; 4 % once consecutive batches agree to ~1 %): every element of margin is sorted, scanned and stepped
+// over by all the later phases
+void SizeEstimate::update(const focr_ctx *c, uint64_t n_cand, uint64_t n_hits) {
+    if (last_cand) {
+        const auto rel = [](uint64_t a, uint64_t b) { return (double)(a > b ? a - b : b - a) / (double)std::max<uint64_t>(std::min(a, b), 1); };
+        var = std::max(var * 0.75, std::max(rel(n_cand, last_cand), rel(n_hits, last_hits)));
+    }
+    last_cand = n_cand;
+    last_hits = n_hits;
+    const double m = margin();
+    cand = (size_t)n_cand + (size_t)((double)n_cand * m) + 8192;
+    hits = (size_t)n_hits + (size_t)((double)n_hits * m) + 8192;
+    const uint64_t largest_row = c->h_res[5];
+    row_max = c->row_cap ? (uint32_t)std::max<uint64_t>(largest_row, 1) : 0;  // 0: the scan took the legacy tail
+    uint32_t sh, ns;
+    row_segments(c, &sh, &ns);
+    // buckets still well above what a wave sorts in registers: halve the x-segments for the next scan of this setup
+    seg_shift = largest_row > 2048 && sh > 5 ? sh - 1 : sh;
+}
+
+// the last counts + the widest margin, for the executor's other contexts: only a stream's first batch pays the exact-size scan's waits
+void SizeEstimate::publish(uint64_t sig) const {
+    std::lock_guard<std::mutex> lk(g_est_mu);
+    if (g_est.size() > 256) g_est.clear();
+    g_est[sig] = SizeEstimate{(size_t)last_cand + (size_t)last_cand / 5 + 8192, (size_t)last_hits + (size_t)last_hits / 5 + 8192, 0.0667, 0, 0, row_max, seg_shift};
+}
+
+void SizeEstimate::adopt(uint64_t sig) {
+    std::lock_guard<std::mutex> lk(g_est_mu);
+    auto it = g_est.find(sig);
+    if (it != g_est.end()) *this = it->second;
+}
+
+void SizeEstimate::forget(uint64_t sig) {
+    std::lock_guard<std::mutex> lk(g_est_mu);
+    g_est.erase(sig);
+}
 
 void set_global_error(const std::string &s) {
     std::lock_guard<std::mutex> lk(g_err_mu);
@@ -125,7 +161,6 @@ static void free_results(focr_ctx *c) {
     free_dev(c->d_hit_sims_alt);
     free_dev(c->d_cand);
     free_dev(c->d_cand_alt);
-    c->cand_alt_capacity = 0;
     c->scan_flags.release();
     c->scan_pos.release();
     c->scan_live.release();
@@ -135,7 +170,6 @@ static void free_results(focr_ctx *c) {
         b->release();
     free_dev(c->d_L);
     free_dev(c->d_planes);
-    c->planes_bytes = 0;
     free_dev(c->d_sort_tmp);
     free_dev(c->d_seg_count);
     free_dev(c->d_seg_start);
@@ -145,7 +179,7 @@ static void free_results(focr_ctx *c) {
     for (auto *b : {&c->post_keep, &c->post_choice, &c->post_owner, &c->post_packed, &c->post_scanned, &c->post_page_off,
                     &c->post_line_off, &c->post_chars})
         b->release();
-    c->hit_capacity = c->cand_capacity = c->L_bytes = c->sort_tmp_bytes = c->seg_alloc = c->matches_alloc = 0;
+    c->hit_capacity = c->cand_capacity = c->cand_alt_capacity = c->L_values = c->plane_values = c->sort_tmp_bytes = c->seg_alloc = c->matches_alloc = 0;
     c->scanned = c->processed = false;
 }
 
@@ -250,7 +284,6 @@ int focr_ctx_create(int device, focr_ctx_t **out) {
         int cus = 0;
         FOCR_HIP(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
         c->n_cus = (unsigned)std::max(cus, 1);
-        c->chunked_verify = getenv("FOCR_VERIFY_GLOBAL") == nullptr;
         FOCR_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         c->io_stream = c->stream;
         {
@@ -318,8 +351,7 @@ int focr_ctx_set_row_tail(focr_ctx_t *c, int on) {
     if (!c) return fail(c, FOCR_ERR_INVALID, "focr_ctx_set_row_tail: null context");
     if (on < 0 || on > 1) return fail(c, FOCR_ERR_INVALID, "focr_ctx_set_row_tail: 0 (legacy tail) or 1 (hits-first row tail, the default)");
     c->tail_mode = on;
-    c->est_row_max = 0;
-    c->est_cand = c->est_hits = 0;  // the next scan runs with exact sizes
+    c->est.reset();  // the next scan runs with exact sizes
     return FOCR_OK;
 }
 
@@ -384,7 +416,7 @@ int focr_debug_planes(focr_ctx_t *c, uint16_t *out, size_t capacity, size_t *n_v
     if (!c || !n_values) return FOCR_ERR_INVALID;
     FOCR_HIP(c, hipSetDevice(c->device));
     if (int rc = focr_sync(c)) return rc;
-    *n_values = c->planes_bytes / 2;
+    *n_values = c->plane_values;
     if (!out) return FOCR_OK;
     if (capacity < *n_values) return fail(c, FOCR_ERR_INVALID, "focr_debug_planes: buffer too small");
     if (*n_values) FOCR_HIP(c, hipMemcpy(out, c->d_planes, *n_values * 2, hipMemcpyDeviceToHost));
@@ -830,19 +862,16 @@ static int scan_now(focr_ctx *c) {
         c->sizes_pending = false;
         rc = scan_split(c, run);
         if (rc) return rc;
-        // the sub-runs left the size estimates at the counts of the LAST page sub-range: a following scan of this setup must
-        // not run "estimated" on them (it would overflow, redo exact, overflow again and only then split)
-        c->est_cand = c->est_hits = 0;
-        c->est_last_cand = c->est_last_hits = 0;
-        c->est_row_max = 0;
+        // the sub-runs left the size estimates at the counts of the LAST page sub-range: a following scan of this setup, here or on
+        // another context, must not run "estimated" on them (it would overflow, redo exact, overflow again and only then split)
+        c->est.reset();
+        SizeEstimate::forget(c->est_sig);
     } else if (rc) {
         return rc;
     }
     c->scanned = true;
     return FOCR_OK;
 }
-
-void row_segments(const focr_ctx *c, uint32_t *seg_shift, uint32_t *n_seg);  // rows.hip
 
 // The context joins a lane of an executor (pipe.hip): it works on the lane's stream from now on (its own, idle, is destroyed) and reads
 // results back on the lane's side stream.
@@ -885,10 +914,7 @@ int finish_results(focr_ctx *c) {
             const bool redo_post = c->post_pending;
             c->post_pending = false;
             c->estimated = false;
-            c->est_cand = c->est_hits = 0;
-            c->est_var = 0.0667;  // back to the 20 % margin
-            c->est_last_cand = c->est_last_hits = 0;
-            c->est_row_max = 0;
+            c->est.reset();  // back to the 20 % margin
             c->counters_redone++;
             int rc = scan_now(c);
             if (rc) return rc;
@@ -909,30 +935,9 @@ int finish_results(focr_ctx *c) {
                 c->counters[3] += li.issued_macs;
             }
             c->launches_collect();
-            // bounds for the next scan of the same setup: this scan's counts + a margin that follows how much the counts have
-            // been moving (20 % after the first scan of a setup; 4 % once consecutive batches agree to ~1 %): every element of
-            // margin is sorted, scanned and stepped over by all the later phases
-            if (c->est_last_cand) {
-                const auto rel = [](uint64_t a, uint64_t b) { return (double)(a > b ? a - b : b - a) / (double)std::max<uint64_t>(std::min(a, b), 1); };
-                c->est_var = std::max(c->est_var * 0.75, std::max(rel(n_cand, c->est_last_cand), rel(n_hits, c->est_last_hits)));
-            }
-            c->est_last_cand = n_cand;
-            c->est_last_hits = n_hits;
-            const double margin = std::min(0.2, std::max(0.04, 3.0 * c->est_var));
-            c->est_cand = (size_t)n_cand + (size_t)((double)n_cand * margin) + 8192;
-            c->est_hits = (size_t)n_hits + (size_t)((double)n_hits * margin) + 8192;
-            c->est_row_max = c->row_cap ? (uint32_t)std::max<uint64_t>(c->h_res[5], 1) : 0;  // 0: the last scan took the legacy tail
-            {  // buckets still well above what a wave sorts in registers: halve the x-segments for the next scan of this setup
-                uint32_t sh, ns;
-                row_segments(c, &sh, &ns);
-                c->row_seg_shift = sh;
-                if (c->h_res[5] > 2048 && sh > 5) c->row_seg_shift = sh - 1;
-            }
-            if (c->est_sig) {  // for the other contexts that scan this setup (focr_scan): this batch's counts + the widest margin
-                std::lock_guard<std::mutex> lk(g_est_mu);
-                if (g_est.size() > 256) g_est.clear();
-                g_est[c->est_sig] = SharedEstimate{(size_t)n_cand + (size_t)n_cand / 5 + 8192, (size_t)n_hits + (size_t)n_hits / 5 + 8192, c->est_row_max, c->row_seg_shift};
-            }
+            c->est.update(c, n_cand, n_hits);
+            // for the other contexts that scan this setup — counts of a page sub-range of a split batch are no bound for a whole batch
+            if (c->est_sig && c->sub_np == c->n_pages) c->est.publish(c->est_sig);
         }
         c->counters[1] = n_hits;
         c->n_hits = c->n_hits_raw = (size_t)n_hits;
@@ -986,28 +991,10 @@ int focr_scan(focr_ctx_t *c, float threshold, uint32_t cap, int mode) {
     for (uint64_t v : {(uint64_t)c->bank_hash, (uint64_t)c->device, (uint64_t)c->tail_mode, (uint64_t)c->n_pages, (uint64_t)c->r_w, (uint64_t)c->r_h, (uint64_t)tb, (uint64_t)cap, (uint64_t)mode,
                        (uint64_t)c->prefilter})
         sig = (sig ^ v) * 1099511628211ull;
-    if (sig != c->est_sig) {
-        c->est_row_max = 0;
-        c->row_seg_shift = 0;
-        c->est_cand = c->est_hits = 0;
-        c->est_var = 0.0667;
-        c->est_last_cand = c->est_last_hits = 0;
-    }
+    if (sig != c->est_sig) c->est.reset();
     c->est_sig = sig;
-    if (c->est_cand == 0 && c->estimates_enabled && mode == FOCR_SCAN_MFMA) {
-        // no estimate of its own yet: another context of this process may have scanned the same setup (an executor's contexts take
-        // consecutive batches of one stream: only the stream's very first batch pays the exact-size scan with its host waits)
-        std::lock_guard<std::mutex> lk(g_est_mu);
-        auto it = g_est.find(sig);
-        if (it != g_est.end()) {
-            c->est_cand = it->second.cand;
-            c->est_hits = it->second.hits;
-            c->est_row_max = it->second.row_max;
-            c->row_seg_shift = it->second.seg_shift;
-            c->est_var = 0.0667;  // a neighbour's batch, not this context's: the widest margin was applied when it was published
-        }
-    }
-    c->estimated = c->estimates_enabled && mode == FOCR_SCAN_MFMA && !c->force_split && c->est_cand != 0;
+    if (c->est.cand == 0 && c->estimates_enabled && mode == FOCR_SCAN_MFMA) c->est.adopt(sig);  // none of its own yet: a neighbour's, if any
+    c->estimated = c->estimates_enabled && mode == FOCR_SCAN_MFMA && !c->force_split && c->est.cand != 0;
     return scan_now(c);
 }
 
@@ -1015,8 +1002,8 @@ int focr_size_estimate_stats(focr_ctx_t *c, uint64_t *redone, double *margin, ui
     if (!c) return FOCR_ERR_INVALID;
     if (int rc = finish_results(c)) return rc;
     if (redone) *redone = c->counters_redone;
-    if (margin) *margin = std::min(0.2, std::max(0.04, 3.0 * c->est_var));
-    if (row_max) *row_max = c->est_row_max;
+    if (margin) *margin = c->est.margin();
+    if (row_max) *row_max = c->est.row_max;
     return FOCR_OK;
 }
 

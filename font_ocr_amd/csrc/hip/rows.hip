@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void hit_scatter_kernel(const uint64_t *__rest
 // configs[2]: 1200 x 1520 -> 5 segments of 256 px), later scans halve the segments while the largest bucket stays above 2048
 // (ctx.hip, finish_results: configs[2] settles at 128 px).  The segmentation never changes a result.
 void row_segments(const focr_ctx *c, uint32_t *seg_shift, uint32_t *n_seg) {
-    uint32_t sh = c->row_seg_shift;
+    uint32_t sh = c->est.seg_shift;
     if (!sh) {
         while (((size_t)1 << sh) < c->r_w) sh++;  // one segment
         while (sh > 5 && ((size_t)1 << sh) * c->n_templates > ((size_t)1 << 19)) sh--;
@@ -572,7 +572,7 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
         size_t lds;
         uint32_t all_rows;
         const int mode = verify_mode(c, &lds, &all_rows);
-        if (mode == 0 && c->vrow_bytes && c->chunked_verify) {
+        if (mode == 0 && c->vrow_bytes) {
             // the operand does not fit the LDS whole: chunks of consecutive templates that do (verify_chunks_kernel)
             const bool narrow = c->vrow_bytes == 12;
             const size_t queue_bytes = (size_t)(VERIFY_THREADS / 64) * CHUNK_QUEUE * 12 + 64;

@@ -815,12 +815,15 @@ PlaneParams plane_params(const focr_ctx *c, size_t k, double thr_d) {
     return p;
 }
 
-// whether a size class's statistics take the register form (stats8_kernel): threshold planes, a kept width of 8 px
+// whether a size class's statistics take the register form (stats8_kernel): threshold planes, a kept width of 4, 8, 12 or 16 px
+// (focr_debug_set_stats_form(1): the LDS-tiled kernel for every class)
 static bool stats_register_form(const focr_ctx *c, const SizeClass &sc) {
-    static const bool no_s8 = getenv("FOCR_NO_STATS8") != nullptr;  // A/B: the LDS-tiled kernel for every class
-    // kept widths 4, 8, 12, 16 (a dropped column only exists for 9 -> 8 and 13 -> 12: layout_supers)
-    return sc.keep_w % 4 == 0 && sc.keep_w >= 4 && sc.keep_w <= 16 && !no_s8 && c->dbg_stats_form == 0;
+    // (a dropped column only exists for 9 -> 8 and 13 -> 12: layout_supers)
+    return sc.keep_w % 4 == 0 && sc.keep_w >= 4 && sc.keep_w <= 16 && c->dbg_stats_form == 0;
 }
+
+// bands per workgroup of stats8_kernel, at most: 1 .. 5 measured 34.15 / 34.60 / 33.89 / 34.23 / 33.70 Gpx/s
+constexpr uint32_t S8_BANDS_MAX = 2;
 
 // one statistics launch: class k (full box), optionally together with its kept box as class `pair` (< 0: none);
 // append_list / append_count: the launch is the pass's only one and appends its live M-tiles to the work list itself (stats8_kernel, APPEND)
@@ -839,8 +842,7 @@ static int launch_stats(focr_ctx *c, size_t k, int pair, double thr_d, void *out
         const uint32_t cols = std::min<uint32_t>(Lpitch, 16 * mtx), rows_n = std::min<uint32_t>(Lrows, n_rows + 1);
         const uint32_t strips_x = (cols + S8_COLS - 1) / S8_COLS, bands_y = (rows_n + S8_ROWS - 1) / S8_ROWS;
         // a workgroup: GS neighbouring strips x GB bands, at most 16 waves (stats8_kernel)
-        static const uint32_t gb_max = getenv("FOCR_S8_GB") ? (uint32_t)atoi(getenv("FOCR_S8_GB")) : 2u;  // 1 .. 5 measured: 34.15 / 34.60 / 33.89 / 34.23 / 33.70 Gpx/s (tools/r5_gb.sh)
-        const uint32_t GS = std::min<uint32_t>(strips_x, 16), GB = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(16 / GS, gb_max), bands_y));
+        const uint32_t GS = std::min<uint32_t>(strips_x, 16), GB = std::max<uint32_t>(1, std::min<uint32_t>(std::min<uint32_t>(16 / GS, S8_BANDS_MAX), bands_y));
         const uint32_t sgroups = (strips_x + GS - 1) / GS, bgroups = (bands_y + GB - 1) / GB;
         const uint64_t n_wgs = (uint64_t)sgroups * bgroups * c->sub_np;
         if (n_wgs >= 0x7fffffffull) return fail(c, FOCR_ERR_INVALID, "scan_mfma: batch too large for 32-bit tile ids; scan fewer pages per call");
@@ -898,222 +900,187 @@ VerifyArgs verify_args(const focr_ctx *c, double thr_d) {
                       (uint32_t)c->r_w, (uint32_t)c->r_h, (unsigned long long *)(c->d_res + 4)};
 }
 
-// Process-wide hand-over of the scan kernel between contexts of one device (events are never destroyed).
-struct ScanTurns {
+// The buffers the scan sizes itself: exactly `want` entries of T, unless the buffer already holds `have` >= want (plan_scan, legacy_tail).
+template <typename T>
+static int ensure_exact(focr_ctx *c, T *&p, size_t &have, size_t want, const char *what) {
+    if (have >= want) return FOCR_OK;
+    FOCR_HIP(c, hipStreamSynchronize(c->stream));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    have = 0;
+    if (hipMalloc((void **)&p, want * sizeof(T)) != hipSuccess) return fail(c, FOCR_ERR_NOMEM, std::string("scan_mfma: hipMalloc(") + what + ") failed");
+    have = want;
+    return FOCR_OK;
+}
+
+// Process-wide hand-over between the contexts of one device (events are never destroyed).  A Turn holds the chain's lock from its wait
+// on the previous turn (begin) to the record of its own when it goes out of scope, error returns included; nothing in it waits on the host.
+struct TurnChain {
     std::mutex mu;
-    hipEvent_t ev[8];
+    hipEvent_t ev[8] = {};
     unsigned n = 0;
-    bool init = false;
 };
-static ScanTurns scan_turns[64];
-static ScanTurns stats_turns[64];  // the same for the statistics in front of the scans
+static TurnChain scan_turns[64], stats_turns[64];  // per device: the scan kernels', and the statistics' in front of them
 
-int launch_scan_mfma(focr_ctx *c, float threshold) {
-    const double thr_d = (double)threshold;  // src/ncc.cpp:83, 288
-    const uint32_t Lpitch = (uint32_t)((c->r_w + 63) / 64 * 64 + 64), Lrows = (uint32_t)((c->r_h + 7) / 8 * 8 + 8);
-    const size_t L_per_class = c->n_pages * (size_t)Lrows * Lpitch;
-    // the per-class int32 threshold tables are only needed by super-classes on the legacy path
-    bool need_L = false;
-    for (const SuperClass &su : c->supers) need_L |= su.ksteps > 4 || su.classes.size() > (size_t)MAX_PLANE_VALUES || c->prefilter == FOCR_PREFILTER_LEGACY;
-    const size_t L_bytes = need_L ? L_per_class * c->classes.size() * sizeof(int32_t) : 0;
-    if (c->L_bytes < L_bytes) {
-        FOCR_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_L) (void)hipFree(c->d_L);
-        c->d_L = nullptr;
-        c->L_bytes = 0;
-        if (hipMalloc(&c->d_L, L_bytes) != hipSuccess) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc(negL) failed");
-        c->L_bytes = L_bytes;
+struct Turn {
+    focr_ctx *c;
+    TurnChain &chain;
+    std::lock_guard<std::mutex> lock;
+    bool entered = false;
+    Turn(focr_ctx *c, TurnChain &chain) : c(c), chain(chain), lock(chain.mu) {}
+    int begin() {
+        for (hipEvent_t &e : chain.ev)
+            if (!e) FOCR_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (chain.n) FOCR_HIP(c, hipStreamWaitEvent(c->stream, chain.ev[(chain.n - 1) % 8], 0));
+        entered = true;
+        return FOCR_OK;
     }
-    int rc = ensure_hit_capacity(c, std::max<size_t>(c->hit_capacity, std::max<size_t>(1u << 20, c->sub_np * 65536)));
-    if (rc) return rc;
-    size_t want_cand = std::max<size_t>(c->cand_capacity, std::max<size_t>(1u << 21, c->sub_np * 131072));
-    if (c->estimated) want_cand = std::max(want_cand, c->est_cand);
+    ~Turn() { if (entered) (void)hipEventRecord(chain.ev[chain.n++ % 8], c->stream); }
+};
 
-    for (int attempt = 0; attempt < 4; attempt++) {
-        if (c->cand_capacity < want_cand) {
-            FOCR_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->d_cand) (void)hipFree(c->d_cand);
-            c->d_cand = nullptr;
-            c->cand_capacity = 0;
-            if (hipMalloc(&c->d_cand, want_cand * 8) != hipSuccess) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc(cand) failed");
-            c->cand_capacity = want_cand;
+// What a scan of the batch launches, decided before anything is enqueued (plan_scan: also every buffer sized)
+struct ScanPlan {
+    uint32_t Lpitch = 0, Lrows = 0;
+    size_t L_per_class = 0;      // int32 values of one class's table in d_L ([class][page][Lrows][Lpitch]; legacy passes)
+    size_t plane = 0;            // int16 values of one threshold plane ([page][Lrows][Lpitch] of the pages scanned)
+    size_t tiles_total = 0;      // M-tiles of all passes (SuperClass::live_offset)
+    uint8_t *live = nullptr;     // per M-tile mark bytes
+    uint64_t *live_list = nullptr;
+};
+
+// THE decision whether a pass takes the threshold planes: the planes it takes (the kernel is instantiated for 1 / 2 / 4 values), or
+// 0 for the legacy path — more than 4 K-steps or 4 size classes, the legacy prefilter asked for, or planes beyond 32-bit offsets
+static size_t pass_planes(const focr_ctx *c, const SuperClass &su, size_t plane) {
+    const size_t nv = su.classes.size(), n = nv <= 1 ? 1 : nv <= 2 ? 2 : 4;
+    const bool ok = su.ksteps <= 4 && nv <= (size_t)MAX_PLANE_VALUES && c->prefilter != FOCR_PREFILTER_LEGACY && n * plane * 2 < ((size_t)1 << 32);
+    return ok ? n : 0;
+}
+
+static int plan_scan(focr_ctx *c, bool nothing, size_t want_cand, ScanPlan &P) {
+    if (int rc = ensure_exact(c, c->d_cand, c->cand_capacity, want_cand, "cand")) return rc;
+    if (nothing) return FOCR_OK;  // no statistics, no scan
+    if (c->supers.size() > 40) return fail(c, FOCR_ERR_INVALID, "scan_mfma: too many super-classes");
+    P.Lpitch = (uint32_t)((c->r_w + 63) / 64 * 64 + 64);
+    P.Lrows = (uint32_t)((c->r_h + 7) / 8 * 8 + 8);
+    P.L_per_class = c->n_pages * (size_t)P.Lrows * P.Lpitch;
+    P.plane = c->sub_np * (size_t)P.Lrows * P.Lpitch;
+    size_t plane_vals = 0;
+    bool need_L = false;
+    for (SuperClass &su : c->supers) {
+        // windows of the pass: those of its smallest searchable class
+        su.min_w = su.min_h = 0xffffffffu;
+        for (uint32_t k : su.classes) {
+            const SizeClass &sc = c->classes[k];
+            if (sc.n_w >= c->r_w || sc.n_h >= c->r_h) continue;
+            su.min_w = std::min(su.min_w, sc.n_w);
+            su.min_h = std::min(su.min_h, sc.n_h);
         }
-        c->counters[3] = 0;
-        c->launches_reset();
-        ClearList clear{};  // everything the scan needs zeroed: one launch (launch_clear), in front of the first kernel
-        if (!clear.add(c->d_counter, COUNTER_BYTES)) return fail(c, FOCR_ERR_INVALID, "scan_mfma: clear list full or region too large");  // counters + the scan kernels' item queues
-        c->scan_queues_used = 0;
-        if (!clear.add(c->d_res, 7 * sizeof(uint64_t))) return fail(c, FOCR_ERR_INVALID, "scan_mfma: clear list full or region too large");
-        // Sizes.  Exact mode: the host reads the candidate count after the scan kernels and the hit count after the
-        // verify (two waits), so every later phase runs on exact sizes.  Estimated mode (ctx.hip: same setup as the
-        // previous scan): the counts stay on the device, grids and buffers take the previous counts + a margin (4 .. 20 %, ctx.hip) as bounds,
-        // unused candidate slots hold the largest key so that the sort leaves them at the end; nothing waits.
-        c->ub_cand = c->estimated ? std::min(c->est_cand, c->cand_capacity) : c->cand_capacity;
-        // Tail: the row path (rows.hip) unless a row could exceed its capacity — exact mode finds out after the scan kernels,
-        // estimated mode goes by the previous scan's largest row + 25 % (a larger one sets the overflow bit: batch redone).
-        bool use_rows = rows_applicable(c);
-        uint32_t row_cap = 0;
-        if (use_rows && c->estimated) {
-            row_cap = rows_capacity_for((uint64_t)c->est_row_max + c->est_row_max / 4 + 16);
-            use_rows = c->est_row_max != 0 && row_cap != 0;
-        }
-        c->row_hist = RowHist{};
-        if (use_rows && (rc = rows2_begin(c, clear))) return rc;  // hits-first row tail: verify in flush order, only hits are bucketed and sorted (rows.hip)
-        // legacy tail, estimated sizes: unused candidate slots hold the largest key so that the radix sort leaves them at the end
-        if (c->estimated && !use_rows) FOCR_HIP(c, hipMemsetAsync(c->d_cand, 0xff, c->ub_cand * 8, c->stream));
-        FOCR_HIP(c, hipEventRecord(c->ev[0], c->stream));
-        // `sim > +inf` is never true (NaN thresholds arrive here as +inf, focr_scan): no statistics, no scan, zero candidates
-        // (kappa would be inf - inf = NaN and every window of every live tile a candidate for verify to reject)
-        const bool nothing = !(thr_d < (double)INFINITY);
-        if (nothing) {
-            if ((rc = launch_clear(c, clear))) return rc;
-            FOCR_HIP(c, hipEventRecord(c->ev[1], c->stream));
-        }
-        if (!nothing) {
-        // 1. statistics + live-tile work lists, per super-class (classes that share one scan pass)
-        size_t tiles_total = 0;
-        for (SuperClass &su : c->supers) {
-            su.min_w = su.min_h = 0xffffffffu;
-            for (uint32_t k : su.classes) {
-                const SizeClass &sc = c->classes[k];
-                if (sc.n_w >= c->r_w || sc.n_h >= c->r_h) continue;
-                su.min_w = std::min(su.min_w, sc.n_w);
-                su.min_h = std::min(su.min_h, sc.n_h);
-            }
-            su.mtx = su.n_rows = 0;
-            su.live_offset = tiles_total;
-            if (su.min_w == 0xffffffffu) continue;  // nothing searchable
-            su.mtx = (uint32_t)((c->r_w - su.min_w + 1 + 15) / 16);  // windows x in [0, r_w - min n_w]
-            su.n_rows = (uint32_t)(c->r_h - su.min_h);               // y in [1, r_h - min n_h]
-            const uint64_t nt = (uint64_t)su.mtx * su.n_rows * c->sub_np;
-            if (nt >= 0x7fffffffull) return fail(c, FOCR_ERR_INVALID, "scan_mfma: batch too large for 32-bit tile ids; scan fewer pages per call");
-            tiles_total += (size_t)nt;
-        }
-        uint8_t *live = (uint8_t *)c->scan_live.ensure(c, tiles_total + 24);
-        uint64_t *live_list = (uint64_t *)c->scan_live_list.ensure(c, (tiles_total + 16) * 8);
-        if (!live || !live_list) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc failed");
-        if (!clear.add(live, tiles_total + 16)) return fail(c, FOCR_ERR_INVALID, "scan_mfma: clear list full or region too large");
-        // The statistics of the batches of one device take turns too (an event chain like the scan kernels' below): two lanes that
-        // start their statistics at the same moment — a pipeline filling up from a drained state does that — share the free CUs,
-        // finish together, then wait for their scan turns one behind the other, and their tails overlap again: a second steady state
-        // with the same work and 7 % less throughput (two batches completing together, then 2.5 and 3.0 ms: DESIGN.md section 5,
-        // "two rhythms").  In the staggered state a batch's statistics never meet another's, and the chain costs nothing.
-        static const bool stats_chain = getenv("FOCR_NO_STATS_CHAIN") == nullptr;
-        ScanTurns &st = stats_turns[(unsigned)c->device % 64];
-        if (stats_chain) {
-            std::lock_guard<std::mutex> turn(st.mu);
-            if (!st.init) {
-                for (hipEvent_t &e : st.ev) FOCR_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                st.init = true;
-            }
-            if (st.n) FOCR_HIP(c, hipStreamWaitEvent(c->stream, st.ev[(st.n - 1) % 8], 0));
-            // (the event of THIS batch's statistics is recorded below, under the same lock order: reserve its place now)
-            c->stats_turn = st.n++;
-        }
-        if ((rc = launch_clear(c, clear))) return rc;
-        // which super-classes take the plane path (scan_mfma2s_kernel), and their threshold planes
-        const size_t plane = c->sub_np * (size_t)Lrows * Lpitch;  // int16 values per plane
-        std::vector<int> two(c->supers.size(), 0);
-        std::vector<size_t> plane_off(c->supers.size(), 0);
-        size_t plane_vals = 0;
-        // two[si]: 0 = legacy path (per-class int32 negL tables, scan_mfma2_kernel: > 4 K-steps or > 4 size classes),
-        //          1 = int16 threshold planes + scan_mfma2s_kernel (A = templates, B = windows)
-        for (size_t si = 0; si < c->supers.size(); si++) {
-            const SuperClass &su = c->supers[si];
-            if (!su.mtx || su.ksteps > 4 || su.classes.size() > (size_t)MAX_PLANE_VALUES || c->prefilter == FOCR_PREFILTER_LEGACY) continue;
-            const uint32_t nv = (uint32_t)su.classes.size();
-            if ((size_t)(nv <= 1 ? 1 : nv <= 2 ? 2 : 4) * plane * 2 >= ((size_t)1 << 32)) continue;  // the plane kernel addresses a pass's planes with 32-bit offsets
-            two[si] = 1;
-            plane_off[si] = plane_vals;
-            plane_vals += (size_t)(nv <= 1 ? 1 : nv <= 2 ? 2 : 4) * plane;  // the kernel is instantiated for 1 / 2 / 4 values
-        }
-        if (c->planes_bytes < plane_vals * 2) {
-            FOCR_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->d_planes) (void)hipFree(c->d_planes);
-            c->d_planes = nullptr;
-            c->planes_bytes = 0;
-            if (hipMalloc((void **)&c->d_planes, plane_vals * 2) != hipSuccess) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc(planes) failed");
-            c->planes_bytes = plane_vals * 2;
-        }
-        for (size_t si = 0; si < c->supers.size(); si++) {
-            const SuperClass &su = c->supers[si];
-            if (!su.mtx) continue;
-            uint8_t *lv = live + su.live_offset;
-            std::vector<char> done(su.classes.size(), 0);
-            std::vector<size_t> order;  // classes whose last column is dropped first: they can take their kept box along
-            for (int pass = 0; pass < 2; pass++)
-                for (size_t v = 0; v < su.classes.size(); v++)
-                    if ((c->classes[su.classes[v]].keep_w != c->classes[su.classes[v]].n_w) == (pass == 0)) order.push_back(v);
-            struct StatsLaunch {
-                size_t v, k, pv;
-                int pair;
-            };
-            std::vector<StatsLaunch> todo;  // the pass's statistics launches
-            for (size_t v : order) {
-                if (done[v]) continue;
-                const size_t k = su.classes[v];
-                const SizeClass &sc = c->classes[k];
-                if (!two[si] && (sc.n_w >= c->r_w || sc.n_h >= c->r_h)) continue;  // nothing searchable: its tiles are skipped below
-                // a class whose last column is dropped computes its kept box's statistics anyway: if that box is a size class
-                // of this pass too, both come out of one launch
-                int pair = -1;
-                size_t pv = 0;
-                if (sc.keep_w != sc.n_w)
-                    for (size_t u = 0; u < su.classes.size(); u++) {
-                        const SizeClass &o = c->classes[su.classes[u]];
-                        if (u != v && !done[u] && o.n_w == sc.keep_w && o.n_h == sc.n_h && o.keep_w == o.n_w) pair = (int)su.classes[u], pv = u;
-                    }
-                todo.push_back(StatsLaunch{v, k, pv, pair});
-                done[v] = 1;
-                if (pair >= 0) done[pv] = 1;
-            }
-            // ONE launch for the whole pass, in the register form: its marks are final and it appends the live M-tiles to the work
-            // list itself (stats8_kernel, APPEND) — no mark bytes, no compaction launch in front of the scan kernel
-            static const bool no_append = getenv("FOCR_NO_STATS_APPEND") != nullptr;  // A/B
-            // (several launches: one in the register form goes LAST and merges the marks the others left in `live`)
-            for (size_t i = 0; i + 1 < todo.size(); i++)
-                if (stats_register_form(c, c->classes[todo[i].k]) && !stats_register_form(c, c->classes[todo.back().k])) std::swap(todo[i], todo.back());
-            const bool direct = two[si] && !todo.empty() && stats_register_form(c, c->classes[todo.back().k]) && !no_append;
-            for (const StatsLaunch &L : todo) {
-                if (two[si]) {
-                    uint16_t *base = c->d_planes + plane_off[si];
-                    const bool last = direct && &L == &todo.back();
-                    rc = launch_stats<1>(c, L.k, L.pair, thr_d, base + L.v * plane, L.pair >= 0 ? base + L.pv * plane : nullptr, Lpitch, Lrows,
-                                         last && todo.size() == 1 ? nullptr : lv, su.mtx, su.n_rows, last ? live_list + su.live_offset : nullptr,
-                                         last ? c->d_counter + 8 + si : nullptr);
-                } else {
-                    rc = launch_stats<0>(c, L.k, L.pair, thr_d, c->d_L + L.k * L_per_class, L.pair >= 0 ? c->d_L + (size_t)L.pair * L_per_class : nullptr, Lpitch, Lrows, lv,
-                                         su.mtx, su.n_rows);
+        su.mtx = su.n_rows = 0;
+        su.live_offset = P.tiles_total;
+        su.planes = false;
+        if (su.min_w == 0xffffffffu) continue;  // nothing searchable
+        su.mtx = (uint32_t)((c->r_w - su.min_w + 1 + 15) / 16);  // windows x in [0, r_w - min n_w]
+        su.n_rows = (uint32_t)(c->r_h - su.min_h);               // y in [1, r_h - min n_h]
+        const uint64_t nt = (uint64_t)su.mtx * su.n_rows * c->sub_np;
+        if (nt >= 0x7fffffffull) return fail(c, FOCR_ERR_INVALID, "scan_mfma: batch too large for 32-bit tile ids; scan fewer pages per call");
+        P.tiles_total += (size_t)nt;
+        const size_t n_planes = pass_planes(c, su, P.plane);
+        su.planes = n_planes != 0;
+        su.plane_off = plane_vals;
+        plane_vals += n_planes * P.plane;
+        need_L |= !su.planes;
+    }
+    if (int rc = ensure_exact(c, c->d_L, c->L_values, need_L ? P.L_per_class * c->classes.size() : 0, "negL")) return rc;
+    if (int rc = ensure_exact(c, c->d_planes, c->plane_values, plane_vals, "planes")) return rc;
+    P.live = (uint8_t *)c->scan_live.ensure(c, P.tiles_total + 24);
+    P.live_list = (uint64_t *)c->scan_live_list.ensure(c, (P.tiles_total + 16) * 8);
+    if (!P.live || !P.live_list) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc failed");
+    return FOCR_OK;
+}
+
+// 1. the clear launch, then statistics + live-tile work lists per super-class (classes that share one scan pass).
+// The statistics of the batches of one device take turns (an event chain like the scan kernels'): two lanes that start their
+// statistics at the same moment — a pipeline filling up from a drained state does that — share the free CUs, finish together, then
+// wait for their scan turns one behind the other, and their tails overlap again: a second steady state with the same work and 7 % less
+// throughput (two batches completing together, then 2.5 and 3.0 ms: DESIGN.md section 5, "two rhythms").  In the staggered state a
+// batch's statistics never meet another's, and the chain costs nothing.
+static int stats_phase(focr_ctx *c, const ScanPlan &P, ClearList &clear, double thr_d) {
+    if (!clear.add(P.live, P.tiles_total + 16)) return fail(c, FOCR_ERR_INVALID, "scan_mfma: clear list full or region too large");
+    Turn turn(c, stats_turns[(unsigned)c->device % 64]);
+    int rc = turn.begin();
+    if (rc || (rc = launch_clear(c, clear))) return rc;
+    for (size_t si = 0; si < c->supers.size(); si++) {
+        const SuperClass &su = c->supers[si];
+        if (!su.mtx) continue;
+        uint8_t *lv = P.live + su.live_offset;
+        std::vector<char> done(su.classes.size(), 0);
+        std::vector<size_t> order;  // classes whose last column is dropped first: they can take their kept box along
+        for (int pass = 0; pass < 2; pass++)
+            for (size_t v = 0; v < su.classes.size(); v++)
+                if ((c->classes[su.classes[v]].keep_w != c->classes[su.classes[v]].n_w) == (pass == 0)) order.push_back(v);
+        struct StatsLaunch {
+            size_t v, k, pv;
+            int pair;
+        };
+        std::vector<StatsLaunch> todo;  // the pass's statistics launches
+        for (size_t v : order) {
+            if (done[v]) continue;
+            const size_t k = su.classes[v];
+            const SizeClass &sc = c->classes[k];
+            if (!su.planes && (sc.n_w >= c->r_w || sc.n_h >= c->r_h)) continue;  // nothing searchable: its tiles are skipped by the scan
+            // a class whose last column is dropped computes its kept box's statistics anyway: if that box is a size class
+            // of this pass too, both come out of one launch
+            int pair = -1;
+            size_t pv = 0;
+            if (sc.keep_w != sc.n_w)
+                for (size_t u = 0; u < su.classes.size(); u++) {
+                    const SizeClass &o = c->classes[su.classes[u]];
+                    if (u != v && !done[u] && o.n_w == sc.keep_w && o.n_h == sc.n_h && o.keep_w == o.n_w) pair = (int)su.classes[u], pv = u;
                 }
-                if (rc) return rc;
+            todo.push_back(StatsLaunch{v, k, pv, pair});
+            done[v] = 1;
+            if (pair >= 0) done[pv] = 1;
+        }
+        // ONE launch for the whole pass, in the register form: its marks are final and it appends the live M-tiles to the work
+        // list itself (stats8_kernel, APPEND) — no mark bytes, no compaction launch in front of the scan kernel
+        // (several launches: one in the register form goes LAST and merges the marks the others left in `live`)
+        for (size_t i = 0; i + 1 < todo.size(); i++)
+            if (stats_register_form(c, c->classes[todo[i].k]) && !stats_register_form(c, c->classes[todo.back().k])) std::swap(todo[i], todo.back());
+        const bool direct = su.planes && !todo.empty() && stats_register_form(c, c->classes[todo.back().k]);
+        for (const StatsLaunch &L : todo) {
+            if (su.planes) {
+                uint16_t *base = c->d_planes + su.plane_off;
+                const bool last = direct && &L == &todo.back();
+                rc = launch_stats<1>(c, L.k, L.pair, thr_d, base + L.v * P.plane, L.pair >= 0 ? base + L.pv * P.plane : nullptr, P.Lpitch, P.Lrows,
+                                     last && todo.size() == 1 ? nullptr : lv, su.mtx, su.n_rows, last ? P.live_list + su.live_offset : nullptr,
+                                     last ? c->d_counter + 8 + si : nullptr);
+            } else {
+                rc = launch_stats<0>(c, L.k, L.pair, thr_d, c->d_L + L.k * P.L_per_class, L.pair >= 0 ? c->d_L + (size_t)L.pair * P.L_per_class : nullptr,
+                                     P.Lpitch, P.Lrows, lv, su.mtx, su.n_rows);
             }
-            if (direct) continue;
-            const uint32_t nt = (uint32_t)((uint64_t)su.mtx * su.n_rows * c->sub_np);
-            hipLaunchKernelGGL(compact_live_tiles, dim3((nt + 256 * CLT_PER_THREAD - 1) / (256 * CLT_PER_THREAD)), dim3(256), 0, c->stream, live + su.live_offset, nt, su.mtx,
-                               su.n_rows, 1u, live_list + su.live_offset, c->d_counter + 8 + si);
-            FOCR_HIP(c, hipGetLastError());
+            if (rc) return rc;
         }
-        FOCR_HIP(c, hipEventRecord(c->ev[1], c->stream));
-        if (stats_chain) {
-            std::lock_guard<std::mutex> turn(st.mu);
-            FOCR_HIP(c, hipEventRecord(st.ev[c->stats_turn % 8], c->stream));
-        }
-        // 2. MFMA prefilter: one launch per (super-class, bank chunk that fits the LDS budget).
-        // With several contexts in flight on one GPU the persistent scan kernels take turns: each context's launches
-        // wait (on the device, hipStreamWaitEvent) for the previous context's to finish.  Two of them sharing the
-        // MFMA pipes finish no sooner than one after the other; in turn each runs at its full rate while the other
-        // contexts' small kernels use the CUs left free by focr_ctx_set_scan_cus.
-        if (c->supers.size() > 40) return fail(c, FOCR_ERR_INVALID, "scan_mfma: too many super-classes");
-        {
-        // (an executor queues its batches from ONE thread in ticket order, pipe.hip: its scans enter this chain in that order
-        // with no host-side gate; contexts driven by threads of their own take their turn in the order they get here)
-        ScanTurns &tn = scan_turns[(unsigned)c->device % 64];
-        std::lock_guard<std::mutex> turn(tn.mu);  // held only while enqueueing
-        if (!tn.init) {
-            for (hipEvent_t &e : tn.ev) FOCR_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            tn.init = true;
-        }
-        if (tn.n) FOCR_HIP(c, hipStreamWaitEvent(c->stream, tn.ev[(tn.n - 1) % 8], 0));
+        if (direct) continue;
+        const uint32_t nt = (uint32_t)((uint64_t)su.mtx * su.n_rows * c->sub_np);
+        hipLaunchKernelGGL(compact_live_tiles, dim3((nt + 256 * CLT_PER_THREAD - 1) / (256 * CLT_PER_THREAD)), dim3(256), 0, c->stream, lv, nt, su.mtx,
+                           su.n_rows, 1u, P.live_list + su.live_offset, c->d_counter + 8 + si);
+        FOCR_HIP(c, hipGetLastError());
+    }
+    FOCR_HIP(c, hipEventRecord(c->ev[1], c->stream));
+    return FOCR_OK;
+}
+
+// 2. MFMA prefilter: one launch per (super-class, bank chunk that fits the LDS budget), then the tall classes.
+// With several contexts in flight on one GPU the persistent scan kernels take turns: each context's launches wait (on the device,
+// hipStreamWaitEvent) for the previous context's to finish.  Two of them sharing the MFMA pipes finish no sooner than one after the
+// other; in turn each runs at its full rate while the other contexts' small kernels use the CUs left free by focr_ctx_set_scan_cus.
+// (An executor queues its batches from ONE thread in ticket order, pipe.hip: its scans enter this chain in that order with no
+// host-side gate; contexts driven by threads of their own take their turn in the order they get here.)
+static int scan_phase(focr_ctx *c, const ScanPlan &P, double thr_d) {
+    int rc = FOCR_OK;
+    {
+        Turn turn(c, scan_turns[(unsigned)c->device % 64]);
+        if ((rc = turn.begin())) return rc;
         for (size_t si = 0; si < c->supers.size(); si++) {
             const SuperClass &su = c->supers[si];
             if (!su.mtx) continue;
@@ -1123,11 +1090,11 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
                 MfmaLaunch L{};
                 L.layout = su.layout;
                 L.ksteps = su.ksteps;
-                L.Lpitch = Lpitch;
-                L.Lrows = Lrows;
+                L.Lpitch = P.Lpitch;
+                L.Lrows = P.Lrows;
                 L.mtx = su.mtx;
                 L.n_rows = su.n_rows;
-                L.live_list = live_list + su.live_offset;
+                L.live_list = P.live_list + su.live_offset;
                 L.live_count = c->d_counter + 8 + si;
                 L.super_index = (uint32_t)si;
                 const uint32_t t_limit = std::min(su.n_tiles, t0 + chunk_tiles);
@@ -1138,7 +1105,7 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
                     const uint32_t cb = su.tile_first[i], ce = cb + sc.n_tiles16;
                     const uint32_t b = std::max(cb, t1), e = std::min(ce, t_limit);
                     if (b >= e || b != t1) continue;  // segments must tile [t0, t1) contiguously
-                    if (!two[si] && (sc.n_w >= c->r_w || sc.n_h >= c->r_h)) {  // no searchable window: skip the class's tiles
+                    if (!su.planes && (sc.n_w >= c->r_w || sc.n_h >= c->r_h)) {  // no searchable window: skip the class's tiles
                         if (L.segs.n == 0) {
                             t0 = t1 = e;
                             continue;
@@ -1148,12 +1115,10 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
                     A3.shift[L.segs.n] = plane_params(c, su.classes[i], thr_d).shift;  // the unit of the class's plane
                     A3.seg_value[L.segs.n] = (uint32_t)i;
                     A3.seg_full[L.segs.n] = (su.layout == LAYOUT_W12 && sc.keep_w <= 8) ? 0u : 1u;  // mfma_common.h: K layouts
-                    {  // tiles of the class from n_live / 16 on hold dead / padding slots; chunk-local numbering
-                        const uint32_t dead = cb + sc.n_live / 16;
-                        A3.seg_dead_from[L.segs.n] = dead > t0 ? dead - t0 : 0u;
-                    }
+                    const uint32_t dead = cb + sc.n_live / 16;  // tiles of the class from n_live / 16 on hold dead / padding slots
+                    A3.seg_dead_from[L.segs.n] = dead > t0 ? dead - t0 : 0u;  // chunk-local numbering
                     MfmaSeg &sg = L.segs.s[L.segs.n++];
-                    sg.negL = c->d_L + su.classes[i] * L_per_class;
+                    sg.negL = c->d_L + su.classes[i] * P.L_per_class;
                     sg.tile_end = e - t0;
                     const uint32_t real = std::min(sc.n_templates, (e - cb) * 16) - (b - cb) * 16;
                     L.n_templates += real;
@@ -1171,36 +1136,118 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
                 const unsigned cus = c->scan_cus ? std::min(c->scan_cus, c->n_cus) : c->n_cus;
                 if (c->scan_queues_used >= MAX_SCAN_QUEUES) return fail(c, FOCR_ERR_INVALID, "scan_mfma: too many scan passes for one call (bank too large)");
                 L.queue = c->d_counter + COUNTER_WORDS + (size_t)(c->scan_queues_used++) * QUEUE_XCDS * QUEUE_STRIDE;
-                if (two[si]) {
-                    A3.planes = c->d_planes + plane_off[si];
-                    A3.stride = plane;
+                if (su.planes) {
+                    A3.planes = c->d_planes + su.plane_off;
+                    A3.stride = P.plane;
                     A3.nv = (uint32_t)su.classes.size();
-                    if ((rc = dispatch_mfma_v2s(c, L, A3, cus))) return rc;
-                } else if ((rc = dispatch_mfma_v2(c, L, cus))) {
-                    return rc;
+                    rc = dispatch_mfma_v2s(c, L, A3, cus);
+                } else {
+                    rc = dispatch_mfma_v2(c, L, cus);
                 }
+                if (rc) return rc;
                 t0 = t1;
             }
         }
-        FOCR_HIP(c, hipEventRecord(tn.ev[tn.n % 8], c->stream));
-        tn.n++;
+    }
+    // tall classes: exact scan straight into the candidate list
+    for (size_t k = 0; k < c->classes.size(); k++) {
+        const SizeClass &sc = c->classes[k];
+        if (!sc.tall || sc.n_w >= c->r_w || sc.n_h >= c->r_h) continue;
+        if ((rc = launch_scan_tall(c, k, thr_d, c->d_cand, nullptr, (unsigned long long *)c->d_counter + 1, (unsigned long long)c->ub_cand, 0))) return rc;
+    }
+    return FOCR_OK;
+}
+
+// 3a. hits-first row tail: verify the candidates where they lie, then bucket + sort the hits only (rows.hip)
+static int row_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c) {
+    int rc = rows2_verify(c, thr_d, n_cand_p, ub_c);
+    if (rc) return rc;
+    size_t ub_h = std::min(ub_c, c->est.hits);
+    uint64_t row_max = c->est.row_bound();
+    if (!c->estimated) {  // exact number of hits and the largest bucket
+        uint64_t hits = 0;
+        FOCR_HIP(c, hipMemcpyAsync(&hits, c->d_res + 6, 8, hipMemcpyDeviceToHost, c->stream));
+        FOCR_HIP(c, hipMemcpyAsync(&row_max, c->d_res + 5, 8, hipMemcpyDeviceToHost, c->stream));
+        FOCR_HIP(c, hipStreamSynchronize(c->stream));
+        ub_h = (size_t)hits;
+    }
+    // buckets above the row sort's first capacity class get a second launch (rows.hip); a bucket beyond the sort's largest capacity
+    // (exact sizes only: launch_scan_mfma): library sort of the placed hits
+    c->row_cap = rows_capacity_for(row_max);
+    const bool big_expected = row_max > 1024, sort_rows = c->row_cap != 0;
+    if ((rc = rows2_place(c, n_cand_p, ub_c, ub_h, big_expected, sort_rows))) return rc;
+    if (!sort_rows && (rc = sort_pairs_u64_f32(c, c->d_hit_keys, c->d_hit_keys_alt, c->d_hit_sims_alt, c->d_hit_sims, ub_h, c->fmt.bits()))) return rc;
+    return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims_alt, c->d_res + 6, ub_h, n_cand_p, ub_c);
+}
+
+// 3b. legacy tail: sort the candidates into emission order, verify them exactly in place, compact + cap (order.hip)
+static int legacy_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c) {
+    c->row_cap = 0;
+    int rc = ensure_hit_capacity(c, std::max<size_t>(c->hit_capacity, ub_c + 1));
+    if (rc) return rc;
+    uint64_t *flags = (uint64_t *)c->scan_flags.ensure(c, (ub_c + 1) * 8);
+    uint64_t *pos = (uint64_t *)c->scan_pos.ensure(c, (ub_c + 1) * 8);
+    if (!flags || !pos) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc failed");
+    if ((rc = ensure_exact(c, c->d_cand_alt, c->cand_alt_capacity, c->cand_capacity, "cand_alt"))) return rc;
+    if ((rc = sort_keys_u64(c, c->d_cand, c->d_cand_alt, ub_c, c->fmt.bits()))) return rc;
+    hipLaunchKernelGGL(verify_kernel, dim3((unsigned)((ub_c + 1 + 255) / 256)), dim3(256), 0, c->stream, c->d_cand, n_cand_p, (unsigned long long)ub_c,
+                       verify_args(c, thr_d), c->d_hit_sims, flags);
+    FOCR_HIP(c, hipGetLastError());
+    FOCR_HIP(c, hipEventRecord(c->ev[3], c->stream));
+    if ((rc = compact_candidates(c, c->d_cand, c->d_hit_sims, flags, pos, n_cand_p, ub_c))) return rc;
+    size_t ub_h = std::min(ub_c, c->est.hits);
+    if (!c->estimated) {  // exact number of hits for the ordering pass
+        uint64_t hits = 0;
+        FOCR_HIP(c, hipMemcpyAsync(&hits, pos + ub_c, 8, hipMemcpyDeviceToHost, c->stream));
+        FOCR_HIP(c, hipStreamSynchronize(c->stream));
+        ub_h = (size_t)hits;
+    }
+    return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims_alt, pos + ub_c, ub_h, n_cand_p, ub_c);
+}
+
+int launch_scan_mfma(focr_ctx *c, float threshold) {
+    const double thr_d = (double)threshold;  // src/ncc.cpp:83, 288
+    // `sim > +inf` is never true (NaN thresholds arrive here as +inf, focr_scan): no statistics, no scan, zero candidates
+    // (kappa would be inf - inf = NaN and every window of every live tile a candidate for verify to reject)
+    const bool nothing = !(thr_d < (double)INFINITY);
+    int rc = ensure_hit_capacity(c, std::max<size_t>(c->hit_capacity, std::max<size_t>(1u << 20, c->sub_np * 65536)));
+    if (rc) return rc;
+    size_t want_cand = std::max<size_t>(c->cand_capacity, std::max<size_t>(1u << 21, c->sub_np * 131072));
+    if (c->estimated) want_cand = std::max(want_cand, c->est.cand);
+    for (int attempt = 0; attempt < 4; attempt++) {
+        ScanPlan P;
+        if ((rc = plan_scan(c, nothing, want_cand, P))) return rc;
+        c->counters[3] = 0;
+        c->launches_reset();
+        ClearList clear{};  // everything the scan needs zeroed: one launch (launch_clear), in front of the first kernel
+        if (!clear.add(c->d_counter, COUNTER_BYTES) || !clear.add(c->d_res, 7 * sizeof(uint64_t)))  // counters + the scan kernels' item queues, result sizes
+            return fail(c, FOCR_ERR_INVALID, "scan_mfma: clear list full or region too large");
+        c->scan_queues_used = 0;
+        // Sizes.  Exact mode: the host reads the candidate count after the scan kernels and the hit count after the
+        // verify (two waits), so every later phase runs on exact sizes.  Estimated mode (ctx.hip: same setup as the
+        // previous scan): the counts stay on the device, grids and buffers take the previous counts + a margin (4 .. 20 %, ctx.hip) as bounds,
+        // unused candidate slots hold the largest key so that the sort leaves them at the end; nothing waits.
+        c->ub_cand = c->estimated ? std::min(c->est.cand, c->cand_capacity) : c->cand_capacity;
+        // Tail: the row path (rows.hip) unless a row could exceed its capacity — exact mode finds out after the scan kernels,
+        // estimated mode goes by the previous scan's largest row + 25 % (a larger one sets the overflow bit: batch redone).
+        bool use_rows = rows_applicable(c);
+        if (use_rows && c->estimated) use_rows = c->est.row_max != 0 && rows_capacity_for(c->est.row_bound()) != 0;
+        c->row_hist = RowHist{};
+        if (use_rows && (rc = rows2_begin(c, clear))) return rc;  // hits-first row tail: verify in flush order, only hits are bucketed and sorted (rows.hip)
+        // legacy tail, estimated sizes: unused candidate slots hold the largest key so that the radix sort leaves them at the end
+        if (c->estimated && !use_rows) FOCR_HIP(c, hipMemsetAsync(c->d_cand, 0xff, c->ub_cand * 8, c->stream));
+        FOCR_HIP(c, hipEventRecord(c->ev[0], c->stream));
+        if (nothing) {
+            if ((rc = launch_clear(c, clear))) return rc;
+            FOCR_HIP(c, hipEventRecord(c->ev[1], c->stream));
+            use_rows = false;
+        } else if ((rc = stats_phase(c, P, clear, thr_d)) || (rc = scan_phase(c, P, thr_d))) {
+            return rc;
         }
-        // tall classes: exact scan straight into the candidate list
-        for (size_t k = 0; k < c->classes.size(); k++) {
-            const SizeClass &sc = c->classes[k];
-            if (!sc.tall || sc.n_w >= c->r_w || sc.n_h >= c->r_h) continue;
-            if ((rc = launch_scan_tall(c, k, thr_d, c->d_cand, nullptr, (unsigned long long *)c->d_counter + 1,
-                                       (unsigned long long)c->ub_cand, 0)))
-                return rc;
-        }
-        }  // !nothing
         FOCR_HIP(c, hipEventRecord(c->ev[2], c->stream));
         FOCR_HIP(c, hipMemcpyAsync(c->h_live, c->d_counter + 8, 40 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         const unsigned long long *n_cand_p = (const unsigned long long *)c->d_counter + 1;
         size_t ub_c = c->ub_cand;
-        if (nothing) use_rows = false;
-        // buckets above the row sort's first capacity class get a second launch (rows.hip): estimated sizes go by the previous scan's largest + 25 %
-        bool big_expected = (uint64_t)c->est_row_max + c->est_row_max / 4 + 16 > 1024;
         if (!c->estimated) {
             unsigned long long n_cand = 0;
             FOCR_HIP(c, hipMemcpyAsync(&n_cand, n_cand_p, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1212,54 +1259,7 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
             }
             ub_c = (size_t)n_cand;
         }
-        if (use_rows) {
-            // 3a'. hits-first row path: verify the candidates where they lie, then bucket + sort the hits only (rows.hip)
-            if ((rc = rows2_verify(c, thr_d, n_cand_p, ub_c))) return rc;
-            size_t ub_h = std::min(ub_c, c->est_hits);
-            bool sort_rows = true;
-            if (!c->estimated) {  // exact number of hits and the largest bucket
-                uint64_t hits = 0, row_max = 0;
-                FOCR_HIP(c, hipMemcpyAsync(&hits, c->d_res + 6, 8, hipMemcpyDeviceToHost, c->stream));
-                FOCR_HIP(c, hipMemcpyAsync(&row_max, c->d_res + 5, 8, hipMemcpyDeviceToHost, c->stream));
-                FOCR_HIP(c, hipStreamSynchronize(c->stream));
-                ub_h = (size_t)hits;
-                big_expected = row_max > 1024;
-                sort_rows = rows_capacity_for(row_max) != 0;  // a bucket beyond the sort's largest capacity: library sort of the placed hits
-                row_cap = sort_rows ? rows_capacity_for(row_max) : 0;
-            }
-            c->row_cap = row_cap;
-            if ((rc = rows2_place(c, n_cand_p, ub_c, ub_h, big_expected, sort_rows))) return rc;
-            if (!sort_rows && (rc = sort_pairs_u64_f32(c, c->d_hit_keys, c->d_hit_keys_alt, c->d_hit_sims_alt, c->d_hit_sims, ub_h, c->fmt.bits()))) return rc;
-            return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims_alt, c->d_res + 6, ub_h, n_cand_p, ub_c);
-        }
-        c->row_cap = 0;
-        // 3b. legacy tail: sort the candidates into emission order, verify them exactly in place, compact + cap (order.hip)
-        if ((rc = ensure_hit_capacity(c, std::max<size_t>(c->hit_capacity, ub_c + 1)))) return rc;
-        uint64_t *flags = (uint64_t *)c->scan_flags.ensure(c, (ub_c + 1) * 8);
-        uint64_t *pos = (uint64_t *)c->scan_pos.ensure(c, (ub_c + 1) * 8);
-        if (!flags || !pos) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc failed");
-        if (c->cand_alt_capacity < c->cand_capacity) {
-            FOCR_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->d_cand_alt) (void)hipFree(c->d_cand_alt);
-            c->d_cand_alt = nullptr;
-            c->cand_alt_capacity = 0;
-            if (hipMalloc(&c->d_cand_alt, c->cand_capacity * 8) != hipSuccess) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc failed");
-            c->cand_alt_capacity = c->cand_capacity;
-        }
-        if ((rc = sort_keys_u64(c, c->d_cand, c->d_cand_alt, ub_c, c->fmt.bits()))) return rc;
-        hipLaunchKernelGGL(verify_kernel, dim3((unsigned)((ub_c + 1 + 255) / 256)), dim3(256), 0, c->stream, c->d_cand, n_cand_p, (unsigned long long)ub_c,
-                           verify_args(c, thr_d), c->d_hit_sims, flags);
-        FOCR_HIP(c, hipGetLastError());
-        FOCR_HIP(c, hipEventRecord(c->ev[3], c->stream));
-        if ((rc = compact_candidates(c, c->d_cand, c->d_hit_sims, flags, pos, n_cand_p, ub_c))) return rc;
-        size_t ub_h = std::min(ub_c, c->est_hits);
-        if (!c->estimated) {  // exact number of hits for the ordering pass
-            uint64_t hits = 0;
-            FOCR_HIP(c, hipMemcpyAsync(&hits, pos + ub_c, 8, hipMemcpyDeviceToHost, c->stream));
-            FOCR_HIP(c, hipStreamSynchronize(c->stream));
-            ub_h = (size_t)hits;
-        }
-        return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims_alt, pos + ub_c, ub_h, n_cand_p, ub_c);
+        return use_rows ? row_tail(c, thr_d, n_cand_p, ub_c) : legacy_tail(c, thr_d, n_cand_p, ub_c);
     }
     return fail(c, FOCR_ERR_OVERFLOW, "scan_mfma: candidate buffer kept overflowing");
 }

@@ -1282,6 +1282,59 @@ def test_unexpected_large_bucket_under_estimated_sizes_redoes_the_batch():
         assert sc.size_estimate_stats()["redone"] == redone0 + 1
 
 
+def test_split_batch_does_not_publish_its_size_estimates(bank_x2):
+    """A batch scanned in page sub-ranges (the overflow fallback, forced here) leaves no size estimates behind, on its own context or
+    for the other contexts of the setup: the counts of a half batch would be bounds far below the whole batch's, so the next scan of
+    the setup would overflow them and be redone."""
+    bank = bank_x2.subset(list(range(33, 70)) + list(range(95 + 33, 95 + 70)))
+    pages = np.stack([synth_page(bank_x2, SYNTH_SEED_BASE + 640, 608, 720)] * 4)  # identical pages: each half batch has half the counts
+    thr, cap = 0.3, 999
+    with Scanner(0) as a, Scanner(0) as b:
+        for s in (a, b):
+            s.set_bank(bank)
+            s.set_pages(pages)
+        a.force_split(True)
+        a.scan(thr, cap, MFMA1)
+        want = a.matches()
+        a.force_split(False)
+        redone_a, redone_b = a.size_estimate_stats()["redone"], b.size_estimate_stats()["redone"]
+        b.scan(thr, cap, MFMA1)  # a context of the same setup, right behind the split batch: exact sizes
+        n_cand = b.counters()["candidates"]
+        assert n_cand > 1.2 * (n_cand // 2) + 8192 + 10_000, n_cand  # the whole batch would overflow bounds taken from a half
+        a.scan(thr, cap, MFMA1)
+        for s in (a, b):
+            offsets, m = s.matches()
+            assert np.array_equal(offsets, want[0]) and m.tobytes() == want[1].tobytes()
+        assert a.size_estimate_stats()["redone"] == redone_a
+        assert b.size_estimate_stats()["redone"] == redone_b
+
+
+def test_pass_with_planes_above_4_gib_takes_the_legacy_path():
+    """The plane kernel addresses a pass's threshold planes with 32-bit offsets: a pass whose planes would exceed 4 GiB (3 size classes
+    -> 4 planes over 1 100 pages of 608x720: 4.5 GB) takes the legacy path with int32 tables, which must then be allocated for it.
+    The lists equal the direct scan's."""
+    rng = np.random.default_rng(4096)
+    bank = _random_bank(rng, [(6, 12), (7, 14), (8, 16)], 4)  # one K layout, 2 K-steps: one pass
+    n_pages, r_w, r_h = 1100, 608, 720
+    pages = np.full((n_pages, r_h, r_w), 255, np.uint8)  # paper, but for a few pages
+    for p in (0, 1, 517, n_pages - 1):
+        pages[p, 100:160, 40:560] = rng.integers(0, 256, (60, 520), dtype=np.uint8)
+    thr, cap = 0.3, 1024
+    with Scanner(0) as sc:
+        sc.set_bank(bank)
+        sc.set_pages(pages)
+        sc.scan(thr, cap, MFMA1)
+        names = {li["name"].split("<")[0] for li in sc.launches()}
+        assert names == {"scan_mfma2_kernel"}, names  # the legacy kernel only
+        assert len(sc.planes()) == 0
+        got = (sc.counts().copy(), *(x.copy() for x in sc.matches()))
+        sc.scan(thr, cap, SCAN_DIRECT)
+        want = (sc.counts(), *sc.matches())
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    assert got[2].tobytes() == want[2].tobytes()
+    assert got[0].sum() > 0
+
+
 def test_compat_symbols_in_the_reference_call_pattern(bank_x2):
     """The unmodified reference host calls ncc_8_u8 / ncc_16_u8 once per template with the same page and, per size class,
     the same window tables (src/ncc.rs:332-404, 587-701).  All 380 calls of one 608x720 page through the drop-in symbols:
