@@ -283,6 +283,33 @@ class DecodeFontStruct(C.Structure):
     ]
 
 
+class VerifyGlyph(C.Structure):
+    """focr_verify_glyph_t (include/focr_decode.h)."""
+
+    _fields_ = [
+        ("codepoint", C.c_uint32),
+        ("increment", C.c_float),
+        ("box", C.c_float * 4),
+        ("rect_x", C.c_uint32 * 64),
+        ("rect_y", C.c_uint32 * 64),
+        ("rect_w", C.c_uint32 * 64),
+        ("rect_h", C.c_uint32 * 64),
+    ]
+
+
+class VerifyFontStruct(C.Structure):
+    """focr_verify_font_t (include/focr_decode.h)."""
+
+    _fields_ = [
+        ("glyphs", C.POINTER(VerifyGlyph)),
+        ("n_glyphs", C.c_size_t),
+        ("origin_y", C.c_float),
+        ("text_size", C.c_float),
+        ("kerning", C.c_float),
+        ("hinting", C.c_int),
+    ]
+
+
 class DecodedLine(C.Structure):
     """focr_decoded_line_t (include/focr_decode.h)."""
 
@@ -300,6 +327,9 @@ DECODE_RASTER_SYMBOLS = {
     "focr_decode_font_build": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_size_t,
                                          C.POINTER(DecodeFontStruct), C.c_char_p, C.c_size_t]),
     "focr_decode_font_free": (None, [C.POINTER(DecodeFontStruct)]),
+    "focr_verify_font_build": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_size_t,
+                                         C.POINTER(VerifyFontStruct), C.c_char_p, C.c_size_t]),
+    "focr_verify_font_free": (None, [C.POINTER(VerifyFontStruct)]),
 }
 
 # the declarations of include/focr_decode.h in libfocr_hip.so
@@ -315,6 +345,10 @@ DECODE_HIP_SYMBOLS = {
     "focr_decoder_get": (C.c_int, [C.c_void_p, C.POINTER(DecodedLine), C.c_void_p]),
     "focr_decoder_last_ms": (C.c_float, [C.c_void_p]),
     "focr_decoder_last_launches": (C.c_uint32, [C.c_void_p]),
+    "focr_decoder_set_verify_font": (C.c_int, [C.c_void_p, C.POINTER(VerifyFontStruct)]),
+    "focr_decoder_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "focr_decoder_last_verify_ms": (C.c_float, [C.c_void_p]),
+    "focr_decoder_last_verify_launches": (C.c_uint32, [C.c_void_p]),
 }
 
 

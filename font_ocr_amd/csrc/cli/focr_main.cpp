@@ -4,15 +4,19 @@
 //   * glyphs are rasterised once per run into 64 sub-pixel phases (focr_decode_font_build), not once per candidate;
 //   * pages of equal size are decoded as one device batch on one GPU; stdout is still in the order of -i;
 //   * kerning <= 0 or a glyph that does not advance the pen is an error (the reference never finishes a line);
-//   * --verify clips rendered text that falls outside the page (the reference panics there);
+//   * --verify clips rendered text that falls outside the page (the reference panics there); its images are drawn on the
+//     device (focr_decoder_verify) and written on up to 16 threads;
 //   * --test is refused: its RGBA blend cannot be pinned here.
 // There is no CPU fallback: without a device it exits non-zero with the error.
+#include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -212,34 +216,20 @@ struct Line {
     std::vector<uint32_t> text;  // code points
 };
 
-// draw_verify + red_blue_mse (src/main.rs:300-329, 518-524): red = reference ink, blue = the decoded text rendered at
-// (x_start, line.y); rendered pixels outside the page are clipped (the reference panics on them)
-float verify_page(const Args &a, const uint8_t *luma, size_t W, size_t H, const std::vector<Line> &lines, const std::string &out_path) {
-    std::vector<uint8_t> rgb(W * H * 3, 0);
-    for (size_t i = 0; i < W * H; i++)
-        if (luma[i] != 255) rgb[i * 3] = luma[i];
-    char err[256] = {0};
-    for (const Line &l : lines) {
-        uint8_t *c = nullptr;
-        size_t cw = 0, ch = 0;
-        if (focr_render_text(a.font.c_str(), a.text_size, a.hinting, a.kerning, l.text.data(), l.text.size(), &c, &cw, &ch, err, sizeof err) != 0)
-            die(std::string("render: ") + err);
-        for (size_t y = 0; y < ch; y++)
-            for (size_t x = 0; x < cw; x++) {
-                const uint8_t v = c[y * cw + x];
-                const uint64_t ox = (uint64_t)a.x + x, oy = (uint64_t)l.y + y;
-                if (v == 0 || ox >= W || oy >= H) continue;  // canvas_to_lum8: 255 - v != 255
-                rgb[(oy * W + ox) * 3 + 2] = (uint8_t)(255 - v);
-            }
-        free(c);
-    }
-    if (!write_png_rgb(out_path, rgb.data(), (uint32_t)W, (uint32_t)H)) die("cannot write " + out_path);
-    int64_t sum = 0;
-    for (size_t i = 0; i < W * H; i++) {
-        const int d = (int)rgb[i * 3] - (int)rgb[i * 3 + 2];
-        sum += (int64_t)d * d;
-    }
-    return (float)sum / (float)(uint32_t)(W * H);
+// Writes the batch's verify images (the device's draw_verify, n x H x W x 3 bytes) as PNGs on at most 16 threads, and
+// no more than the batch's pages; ok[j] says whether page j's file was written.
+std::vector<char> write_verify_pngs(const std::vector<std::string> &paths, const uint8_t *rgb, uint32_t W, uint32_t H) {
+    const size_t n = paths.size(), page = (size_t)W * H * 3;
+    std::vector<char> ok(n, 0);
+    std::atomic<size_t> next{0};
+    auto work = [&]() {
+        for (size_t j; (j = next.fetch_add(1)) < n;) ok[j] = write_png_rgb(paths[j], rgb + j * page, W, H);
+    };
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < std::min<size_t>(16, n); t++) pool.emplace_back(work);
+    work();
+    for (std::thread &t : pool) t.join();
+    return ok;
 }
 
 std::string verify_path(const std::string &dir, const std::string &img) {  // Path::new(img).with_extension("png").file_name()
@@ -281,9 +271,18 @@ int main(int argc, char **argv) {
     focr_decoder_t *dec = nullptr;
     if (focr_decoder_create(0, &dec) != 0) die(std::string("no usable GPU: ") + focr_decoder_last_error(nullptr), 1);
     if (focr_decoder_set_font(dec, &font) != 0) die(std::string("focr_decoder_set_font: ") + focr_decoder_last_error(dec), 1);
+    if (args.have_verify) {
+        focr_verify_font_t vfont{};
+        if (focr_verify_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), &vfont, err,
+                                   sizeof err) != 0)
+            die(std::string("verify font: ") + err);
+        if (focr_decoder_set_verify_font(dec, &vfont) != 0) die(std::string("focr_decoder_set_verify_font: ") + focr_decoder_last_error(dec), 1);
+        focr_verify_font_free(&vfont);
+    }
 
     std::vector<std::vector<Line>> lines(n_img);
-    std::vector<uint8_t> batch;
+    std::vector<uint8_t> batch, rgb;
+    std::vector<uint64_t> sums;
     for (const auto &grp : groups) {
         const size_t W = grp.first.first, H = grp.first.second;
         for (size_t b0 = 0; b0 < grp.second.size(); b0 += BATCH_PAGES) {
@@ -309,13 +308,20 @@ int main(int argc, char **argv) {
                 for (uint32_t c = 0; c < l.n_chars; c++) out.text.push_back(alphabet[dc[l.first + c]]);
                 lines[grp.second[b0 + l.page]].push_back(std::move(out));
             }
-            if (args.have_verify)
+            if (args.have_verify) {  // draw_verify + red_blue_mse (src/main.rs:300-329, 518-524) on the device
+                rgb.resize(nb * W * H * 3);
+                sums.assign(nb, 0);
+                if (focr_decoder_verify(dec, rgb.data(), 0, sums.data()) != 0)
+                    die(std::string("focr_decoder_verify: ") + focr_decoder_last_error(dec), 1);
+                std::vector<std::string> paths(nb);
+                for (size_t j = 0; j < nb; j++) paths[j] = verify_path(args.verify, args.img[grp.second[b0 + j]]);
+                const std::vector<char> ok = write_verify_pngs(paths, rgb.data(), (uint32_t)W, (uint32_t)H);
                 for (size_t j = 0; j < nb; j++) {
-                    const size_t i = grp.second[b0 + j];
-                    const std::string path = verify_path(args.verify, args.img[i]);
-                    const float mse = verify_page(args, batch.data() + j * W * H, W, H, lines[i], path);
-                    fprintf(stderr, "%s %.6f\n", args.img[i].c_str(), (double)mse);
+                    if (!ok[j]) die("cannot write " + paths[j]);
+                    const float mse = (float)sums[j] / (float)(uint32_t)(W * H);
+                    fprintf(stderr, "%s %.6f\n", args.img[grp.second[b0 + j]].c_str(), (double)mse);
                 }
+            }
         }
     }
     focr_decoder_destroy(dec);

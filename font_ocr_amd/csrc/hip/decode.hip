@@ -11,6 +11,14 @@
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
 // order of the sums nor the device changes a choice.  The pen update is one f32 add of the host-computed increment.
+//
+// focr_decoder_verify draws focr --verify's image of the last run in two more launches, from the run's own buffers:
+//   4. verify_layout_kernel: one wave per work-list line repeats render()'s f32 arithmetic (pen, round_out bounds, the
+//      26.6 delta of every glyph) and writes each glyph's true bitmap rectangle, clipped to the canvas and the page;
+//   5. verify_compose_kernel: one workgroup per (page, 16 rows, 256 columns) tile takes, line by line in order, the
+//      last glyph covering each pixel (an LDS atomic max of the glyph index, so placement and order do not matter),
+//      lets a non-zero value replace the blue of earlier lines, writes RGB and adds the exact sum of (R - B)^2 to the
+//      page's total with one 64-bit atomic.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -176,6 +184,182 @@ __global__ __launch_bounds__(64) void line_decode_kernel(const uint8_t *__restri
     if (lane == 0) n_chars[k] = n;
 }
 
+// ---- verify ------------------------------------------------------------------------------------------------------
+
+constexpr uint32_t VERIFY_TILE_W = 256;     // compose tile: one column per thread
+constexpr uint32_t VERIFY_TILE_H = 16;
+constexpr uint32_t VERIFY_MAX_GRID = 1u << 20;
+
+struct VerifyGlyph {
+    float box[4];      // raster_bounds at the identity before round_out (focr_verify_glyph_t::box)
+};
+
+struct VerifyPhase {
+    int32_t x, y;      // top-left of the true bitmap on a line canvas at whole-pixel shift 0 and vertical translation 0
+    uint32_t w, h;
+    uint32_t src;      // byte offset of that top-left pixel in the bitmap table
+    uint32_t stride;
+};
+
+struct VerifyLine {    // one line slot: its canvas on the page, clipped (empty for a blank slot), and its glyph records
+    int32_t x0, y0, x1, y1;
+    uint32_t k, n;
+};
+
+struct VerifyRec {     // one glyph: its bitmap rectangle on the page, clipped to the canvas and the page
+    int32_t x0, y0, x1, y1;
+    uint32_t src, stride;  // byte offset in the bitmap table of the pixel at (x0, y0)
+};
+
+// 4. render()'s layout of every decoded line, one wave per work-list line; blocks below n_pages also zero the sums
+__global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t n_pages, uint32_t x_start, const uint32_t *__restrict__ flags,
+                                                           const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
+                                                           const uint32_t *__restrict__ n_chars, const uint16_t *__restrict__ chars,
+                                                           const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
+                                                           const VerifyPhase *__restrict__ vphases, VerifyLine *__restrict__ lines,
+                                                           VerifyRec *__restrict__ recs, unsigned long long *__restrict__ sums) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (b < n_pages && lane == 0) sums[b] = 0;
+    if (b >= g.total) return;
+    if (lane == 0 && flags[b] == 0) lines[b] = VerifyLine{0, 0, 0, 0, 0, 0};  // blank slots are in no work-list entry
+    if (b >= *count) return;
+    const uint32_t k = b, slot = work[k], n = n_chars[k];
+    const uint16_t *cs = chars + (size_t)k * g.cap;
+    VerifyRec *out = recs + (size_t)k * g.cap;
+    // the pen (f32 adds in text order) and the union of round_out boxes, folded from the empty rect at (0, 0)
+    float pen = 0.f;
+    int ox = 0, oy = 0, lx = 0, ly = 0;
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t j = base + lane, m = std::min(64u, n - base);
+        const bool live = j < n;
+        const uint32_t c = live ? cs[j] : 0;
+        const float inc = live ? glyphs[c].inc : 0.f;
+        float pos = 0.f;
+        for (uint32_t q = 0; q < m; q++) {
+            if (lane == q) pos = pen;
+            pen = __fadd_rn(pen, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), q)));
+        }
+        if (live) {
+            const VerifyGlyph v = vglyphs[c];
+            ox = std::min(ox, (int)floorf(__fadd_rn(v.box[0], pos)));
+            oy = std::min(oy, (int)floorf(__fadd_rn(v.box[1], 0.f)));
+            lx = std::max(lx, (int)ceilf(__fadd_rn(v.box[2], pos)));
+            ly = std::max(ly, (int)ceilf(__fadd_rn(v.box[3], 0.f)));
+            out[j].x0 = __float_as_int(pos);  // kept for the second pass of this same lane
+        }
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        ox = std::min(ox, __shfl_xor(ox, s, 64));
+        oy = std::min(oy, __shfl_xor(oy, s, 64));
+        lx = std::max(lx, __shfl_xor(lx, s, 64));
+        ly = std::max(ly, __shfl_xor(ly, s, 64));
+    }
+    const int cw = lx - ox, ch = ly - oy;
+    const int64_t W = g.page_w, H = g.page_h;
+    const int64_t line_y = (int64_t)g.y_start + (int64_t)(slot % g.n_slots) * g.line_advance;
+    const float neg_ox = (float)(-ox);
+    for (uint32_t j = lane; j < n; j += 64) {
+        const float pos = __int_as_float(out[j].x0);
+        const int d = (int)__fmul_rn(__fadd_rn(neg_ox, pos), 64.0f);  // FreeType's delta: trunc((-bounds.ox + pos) * 64) >= 0
+        const VerifyPhase ph = vphases[(size_t)cs[j] * FOCR_DECODE_PHASES + (d & 63)];
+        const int gx0 = (d >> 6) + ph.x, gy0 = ph.y - oy;  // on the canvas: whole-pixel shift, vertical delta -bounds.oy
+        const int ax0 = std::max(gx0, 0), ay0 = std::max(gy0, 0);
+        const int ax1 = std::min(gx0 + (int)ph.w, cw), ay1 = std::min(gy0 + (int)ph.h, ch);
+        const int64_t X0 = x_start + (int64_t)ax0, Y0 = line_y + ay0;
+        const int64_t X1 = std::min<int64_t>(x_start + (int64_t)ax1, W), Y1 = std::min<int64_t>(line_y + ay1, H);
+        VerifyRec r{0, 0, 0, 0, 0, 0};
+        if (ax0 < ax1 && ay0 < ay1 && X0 < X1 && Y0 < Y1)
+            r = VerifyRec{(int32_t)X0, (int32_t)Y0, (int32_t)X1, (int32_t)Y1, ph.src + (uint32_t)(ay0 - gy0) * ph.stride + (uint32_t)(ax0 - gx0),
+                          ph.stride};
+        out[j] = r;
+    }
+    if (lane == 0) {
+        const int64_t X1 = std::min<int64_t>(x_start + (int64_t)cw, W), Y1 = std::min<int64_t>(line_y + ch, H);
+        VerifyLine l{0, 0, 0, 0, k, n};
+        if ((int64_t)x_start < X1 && line_y < Y1) l = VerifyLine{(int32_t)x_start, (int32_t)line_y, (int32_t)X1, (int32_t)Y1, k, n};
+        lines[slot] = l;
+    }
+}
+
+// 5. compose the verify image tile by tile; every thread owns one column of a 16-row, 256-column tile
+__global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_kernel(const uint8_t *__restrict__ pages, Geometry g, uint32_t n_pages,
+                                                                       uint32_t hmax, uint32_t tiles_x, uint32_t tiles_y,
+                                                                       const VerifyLine *__restrict__ lines, const VerifyRec *__restrict__ recs,
+                                                                       const uint8_t *__restrict__ bitmaps, uint8_t *__restrict__ rgb,
+                                                                       unsigned long long *__restrict__ sums) {
+    __shared__ uint32_t win[VERIFY_TILE_H * VERIFY_TILE_W];  // 1 + index of the last glyph of the current line over the pixel
+    __shared__ uint8_t blue[VERIFY_TILE_H * VERIFY_TILE_W];
+    __shared__ uint32_t part[VERIFY_TILE_W / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint64_t per_page = (uint64_t)tiles_x * tiles_y, n_tiles = per_page * n_pages;
+    const size_t W = g.page_w, H = g.page_h;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t page = (uint32_t)(tile / per_page), rem = (uint32_t)(tile % per_page);
+        const int r0 = (int)((rem / tiles_x) * VERIFY_TILE_H), c0 = (int)((rem % tiles_x) * VERIFY_TILE_W);
+        const int r1 = std::min<int>(r0 + VERIFY_TILE_H, (int)H), c1 = std::min<int>(c0 + VERIFY_TILE_W, (int)W);
+        for (uint32_t r = 0; r < VERIFY_TILE_H; r++) {
+            win[r * VERIFY_TILE_W + t] = 0;
+            blue[r * VERIFY_TILE_W + t] = 0;
+        }
+        __syncthreads();
+        // the slots whose canvas (at most hmax rows, from the slot's y) can reach rows r0 .. r1 - 1, in line order
+        int64_t i_lo = 0, i_hi = -1;
+        if (g.n_slots) {
+            const int64_t lo = (int64_t)r0 - hmax + 1 - g.y_start, hi = (int64_t)r1 - 1 - g.y_start;
+            i_lo = lo <= 0 ? 0 : (lo + g.line_advance - 1) / g.line_advance;
+            i_hi = hi < 0 ? -1 : std::min<int64_t>(g.n_slots - 1, hi / g.line_advance);
+        }
+        for (int64_t i = i_lo; i <= i_hi; i++) {
+            const VerifyLine l = lines[(size_t)page * g.n_slots + i];
+            if (l.n == 0 || l.x0 >= c1 || l.x1 <= c0 || l.y0 >= r1 || l.y1 <= r0) continue;  // uniform across the workgroup
+            const VerifyRec *lr = recs + (size_t)l.k * g.cap;
+            for (uint32_t j = wave; j < l.n; j += VERIFY_TILE_W / 64) {
+                const VerifyRec r = lr[j];
+                const int x0 = std::max(r.x0, c0), x1 = std::min(r.x1, c1), y0 = std::max(r.y0, r0), y1 = std::min(r.y1, r1);
+                if (x0 >= x1 || y0 >= y1) continue;
+                const int w = x1 - x0, npx = w * (y1 - y0);
+                for (int q = (int)lane; q < npx; q += 64)
+                    atomicMax(&win[(y0 + q / w - r0) * VERIFY_TILE_W + (x0 + q % w - c0)], j + 1);
+            }
+            __syncthreads();
+            const int x = c0 + (int)t;
+            for (int y = r0; y < r1 && x < c1; y++) {
+                const uint32_t idx = (uint32_t)(y - r0) * VERIFY_TILE_W + t, w = win[idx];
+                if (!w) continue;
+                win[idx] = 0;
+                const VerifyRec r = lr[w - 1];
+                const uint8_t v = bitmaps[r.src + (uint32_t)(y - r.y0) * r.stride + (uint32_t)(x - r.x0)];
+                if (v) blue[idx] = (uint8_t)(255 - v);  // canvas_to_lum8 then draw_verify: only v != 0 reaches the page
+            }
+            __syncthreads();
+        }
+        uint32_t acc = 0;
+        const int x = c0 + (int)t;
+        if (x < c1)
+            for (int y = r0; y < r1; y++) {
+                const size_t at = ((size_t)page * H + y) * W + x;
+                const uint8_t l = pages[at];
+                const uint8_t red = l != 255 ? l : 0, b = blue[(uint32_t)(y - r0) * VERIFY_TILE_W + t];
+                if (rgb) {
+                    rgb[at * 3] = red;
+                    rgb[at * 3 + 1] = 0;
+                    rgb[at * 3 + 2] = b;
+                }
+                const int dd = (int)red - (int)b;
+                acc += (uint32_t)(dd * dd);  // at most 16 * 255^2 per thread, 2^28 per workgroup
+            }
+        for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 64);
+        if (lane == 0) part[wave] = acc;
+        __syncthreads();
+        if (t == 0) {
+            unsigned long long sum = 0;
+            for (uint32_t w = 0; w < VERIFY_TILE_W / 64; w++) sum += part[w];
+            if (sum) atomicAdd(&sums[page], sum);
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace focr_dec
 
 using namespace focr_dec;
@@ -189,6 +373,10 @@ struct focr_decoder {
     uint32_t n_glyphs = 0;
     float origin_x = 0.f, min_inc = 0.f;
     std::vector<float> inc;
+    std::vector<focr_decode_glyph_t> font_glyphs;  // what set_verify_font checks and places the verify table against
+    float origin_y = 0.f, text_size = 0.f, kerning = 0.f;
+    int hinting = 0;
+    size_t bitmaps_len = 0;
     DevGlyph *d_glyphs = nullptr;
     int2 *d_offs = nullptr;
     uint32_t *d_bitmaps = nullptr;
@@ -206,6 +394,26 @@ struct focr_decoder {
     std::vector<uint16_t> chars;
     float last_ms = 0.f;
     uint32_t last_launches = 0;
+    // verify: the table, what the last successful run left for it, buffers, timing
+    hipEvent_t ev2 = nullptr, ev3 = nullptr;
+    uint32_t n_vglyphs = 0, hmax = 0;
+    VerifyGlyph *d_vglyphs = nullptr;
+    VerifyPhase *d_vphases = nullptr;
+    bool run_ok = false;
+    Geometry run_g{};
+    size_t run_pages = 0;
+    uint32_t run_x_start = 0;
+    const uint8_t *run_src = nullptr;
+    VerifyLine *d_vlines = nullptr;
+    size_t vlines_cap = 0;
+    VerifyRec *d_vrecs = nullptr;
+    size_t vrecs_cap = 0;
+    unsigned long long *d_sums = nullptr;
+    size_t sums_cap = 0;
+    uint8_t *d_rgb = nullptr;
+    size_t rgb_cap = 0;
+    float last_verify_ms = 0.f;
+    uint32_t last_verify_launches = 0;
 };
 
 namespace {
@@ -235,6 +443,30 @@ int grow(focr_decoder *dec, T **p, size_t *cap, size_t want) {
     return 0;
 }
 
+// What focr_decoder_verify draws from: the successful run's geometry and its pages on the device.
+int remember_run(focr_decoder *dec, const Geometry &g, const uint8_t *d_src, size_t n_pages, uint32_t x_start) {
+    dec->run_g = g;
+    dec->run_pages = n_pages;
+    dec->run_x_start = x_start;
+    dec->run_src = d_src;
+    dec->run_ok = true;
+    return 0;
+}
+
+// A run with no line slot launches nothing, but a verify of it still draws the pages: they go to the device here.
+int keep_run(focr_decoder *dec, const Geometry &g, const uint8_t *pages, int on_device, size_t n_pages, uint32_t x_start) {
+    const uint8_t *d_src = pages;
+    const size_t page_bytes = (size_t)g.page_w * g.page_h * n_pages;
+    if (!on_device && page_bytes) {
+        DEC_CHECK(hipSetDevice(dec->device));
+        if (grow(dec, &dec->d_pages, &dec->pages_cap, page_bytes)) return 1;
+        DEC_CHECK(hipMemcpyAsync(dec->d_pages, pages, page_bytes, hipMemcpyHostToDevice, dec->stream));
+        DEC_CHECK(hipStreamSynchronize(dec->stream));
+        d_src = dec->d_pages;
+    }
+    return remember_run(dec, g, d_src, n_pages, x_start);
+}
+
 }  // namespace
 
 extern "C" int focr_decoder_create(int device, focr_decoder_t **out) {
@@ -249,7 +481,7 @@ extern "C" int focr_decoder_create(int device, focr_decoder_t **out) {
     dec = new focr_decoder;
     dec->device = device;
     if (hipStreamCreateWithFlags(&dec->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&dec->ev0) != hipSuccess ||
-        hipEventCreate(&dec->ev1) != hipSuccess) {
+        hipEventCreate(&dec->ev1) != hipSuccess || hipEventCreate(&dec->ev2) != hipSuccess || hipEventCreate(&dec->ev3) != hipSuccess) {
         focr_decoder_destroy(dec);
         return dfail(nullptr, "focr_decoder_create: stream / event creation failed");
     }
@@ -262,10 +494,12 @@ extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
     (void)hipSetDevice(dec->device);
     if (dec->stream) (void)hipStreamSynchronize(dec->stream);
     for (void *p : {(void *)dec->d_glyphs, (void *)dec->d_offs, (void *)dec->d_bitmaps, (void *)dec->d_pages, (void *)dec->d_strips,
-                    (void *)dec->d_flags, (void *)dec->d_work, (void *)dec->d_nchars, (void *)dec->d_count, (void *)dec->d_chars})
+                    (void *)dec->d_flags, (void *)dec->d_work, (void *)dec->d_nchars, (void *)dec->d_count, (void *)dec->d_chars,
+                    (void *)dec->d_vglyphs, (void *)dec->d_vphases, (void *)dec->d_vlines, (void *)dec->d_vrecs, (void *)dec->d_sums,
+                    (void *)dec->d_rgb})
         if (p) (void)hipFree(p);
-    if (dec->ev0) (void)hipEventDestroy(dec->ev0);
-    if (dec->ev1) (void)hipEventDestroy(dec->ev1);
+    for (hipEvent_t e : {dec->ev0, dec->ev1, dec->ev2, dec->ev3})
+        if (e) (void)hipEventDestroy(e);
     if (dec->stream) (void)hipStreamDestroy(dec->stream);
     delete dec;
 }
@@ -273,6 +507,7 @@ extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
 extern "C" const char *focr_decoder_last_error(const focr_decoder_t *dec) { return dec ? dec->err.c_str() : g_dec_err.c_str(); }
 
 extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font_t *font) {
+    if (dec) dec->run_ok = false, dec->n_vglyphs = 0;  // the last run and the verify table belong to the previous font
     if (!dec || !font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_font: bad arguments");
     if (font->n_glyphs > 65535) return dfail(dec, "focr_decoder_set_font: more than 65535 glyphs");
     if (font->bitmaps_len % 4 || font->bitmaps_len / 4 > 0xffffffffull) return dfail(dec, "focr_decoder_set_font: bad bitmap table");
@@ -306,12 +541,19 @@ extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font
     dec->n_glyphs = (uint32_t)G;
     dec->origin_x = font->origin_x;
     dec->min_inc = min_inc;
+    dec->font_glyphs.assign(font->glyphs, font->glyphs + G);
+    dec->origin_y = font->origin_y;
+    dec->text_size = font->text_size;
+    dec->kerning = font->kerning;
+    dec->hinting = font->hinting;
+    dec->bitmaps_len = font->bitmaps_len;
     return 0;
 }
 
 extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int on_device, size_t n_pages, size_t page_w, size_t page_h,
                                 uint32_t x_start, uint32_t y_start, uint32_t width, uint32_t line_height, uint32_t line_advance) {
     if (!dec) return dfail(nullptr, "focr_decoder_run: null decoder");
+    dec->run_ok = false;
     dec->lines.clear();
     dec->chars.clear();
     dec->last_ms = 0.f;
@@ -331,7 +573,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     else if (line_advance == 0) return dfail(dec, "focr_decoder_run: line_advance 0 (the reference never ends)");
     else g.n_slots = (uint32_t)(((uint64_t)g.page_h - y_start + line_advance - 1) / line_advance);
     const uint64_t total = (uint64_t)n_pages * g.n_slots;
-    if (total == 0) return 0;
+    if (total == 0) return keep_run(dec, g, pages, on_device, n_pages, x_start);  // nothing to decode; a verify still draws the pages
     if (total > (1u << 30)) return dfail(dec, "focr_decoder_run: too many lines in one batch");
     g.total = (uint32_t)total;
     g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;
@@ -407,7 +649,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         l.pad = 0;
         dec->chars.insert(dec->chars.end(), all.begin() + (size_t)k * g.cap, all.begin() + (size_t)k * g.cap + n);
     }
-    return 0;
+    return remember_run(dec, g, d_src, n_pages, x_start);
 }
 
 extern "C" size_t focr_decoder_n_lines(const focr_decoder_t *dec) { return dec ? dec->lines.size() : 0; }
@@ -422,3 +664,93 @@ extern "C" int focr_decoder_get(const focr_decoder_t *dec, focr_decoded_line_t *
 
 extern "C" float focr_decoder_last_ms(const focr_decoder_t *dec) { return dec ? dec->last_ms : 0.f; }
 extern "C" uint32_t focr_decoder_last_launches(const focr_decoder_t *dec) { return dec ? dec->last_launches : 0; }
+
+extern "C" int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_verify_font_t *font) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_verify_font: null decoder");
+    dec->n_vglyphs = 0;
+    if (!font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_verify_font: bad arguments");
+    if (!dec->n_glyphs) return dfail(dec, "focr_decoder_set_verify_font: no decode font (focr_decoder_set_font)");
+    const size_t G = font->n_glyphs;
+    if (G != dec->n_glyphs || font->text_size != dec->text_size || font->kerning != dec->kerning ||
+        (font->hinting != 0) != (dec->hinting != 0) || font->origin_y != dec->origin_y)
+        return dfail(dec, "focr_decoder_set_verify_font: the table does not match the decode font (glyph count, size, kerning, hinting or origin)");
+    if (dec->bitmaps_len > 0xffffffffull) return dfail(dec, "focr_decoder_set_verify_font: decode font bitmaps over 4 GiB");
+    std::vector<VerifyGlyph> vg(G);
+    std::vector<VerifyPhase> vp(G * FOCR_DECODE_PHASES);
+    int y_lo = 0, y_hi = 0;
+    for (size_t i = 0; i < G; i++) {
+        const focr_verify_glyph_t &v = font->glyphs[i];
+        const focr_decode_glyph_t &d = dec->font_glyphs[i];
+        if (v.codepoint != d.codepoint || memcmp(&v.increment, &d.increment, sizeof(float)) != 0)
+            return dfail(dec, "focr_decoder_set_verify_font: the table does not match the decode font (code points or increments)");
+        for (float b : v.box)
+            if (!std::isfinite(b) || std::fabs(b) > (float)(1 << 20)) return dfail(dec, "focr_decoder_set_verify_font: bad glyph box");
+        memcpy(vg[i].box, v.box, sizeof v.box);
+        y_lo = std::min(y_lo, (int)std::floor(v.box[1] + 0.f));  // the rows render() gives any line: at most hmax
+        y_hi = std::max(y_hi, (int)std::ceil(v.box[3] + 0.f));
+        for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
+            if ((uint64_t)v.rect_x[p] + v.rect_w[p] > d.box_w || (uint64_t)v.rect_y[p] + v.rect_h[p] > d.box_h)
+                return dfail(dec, "focr_decoder_set_verify_font: a phase rectangle leaves the decode font's box");
+            vp[i * FOCR_DECODE_PHASES + p] = VerifyPhase{
+                d.off_x[p] + (int32_t)v.rect_x[p], d.off_y[p] + (int32_t)v.rect_y[p] - (int32_t)font->origin_y, v.rect_w[p], v.rect_h[p],
+                (uint32_t)(d.offset + (uint64_t)p * d.stride * d.box_h + (uint64_t)v.rect_y[p] * d.stride + v.rect_x[p]), d.stride};
+        }
+    }
+    DEC_CHECK(hipSetDevice(dec->device));
+    for (void *p : {(void *)dec->d_vglyphs, (void *)dec->d_vphases})
+        if (p) DEC_CHECK(hipFree(p));
+    dec->d_vglyphs = nullptr, dec->d_vphases = nullptr;
+    DEC_CHECK(hipMalloc((void **)&dec->d_vglyphs, sizeof(VerifyGlyph) * G));
+    DEC_CHECK(hipMalloc((void **)&dec->d_vphases, sizeof(VerifyPhase) * vp.size()));
+    DEC_CHECK(hipMemcpy(dec->d_vglyphs, vg.data(), sizeof(VerifyGlyph) * G, hipMemcpyHostToDevice));
+    DEC_CHECK(hipMemcpy(dec->d_vphases, vp.data(), sizeof(VerifyPhase) * vp.size(), hipMemcpyHostToDevice));
+    dec->hmax = (uint32_t)(y_hi - y_lo);
+    dec->n_vglyphs = (uint32_t)G;
+    return 0;
+}
+
+extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums) {
+    if (!dec) return dfail(nullptr, "focr_decoder_verify: null decoder");
+    dec->last_verify_ms = 0.f;
+    dec->last_verify_launches = 0;
+    if (!dec->run_ok) return dfail(dec, "focr_decoder_verify: no successful focr_decoder_run since the font was set");
+    if (!dec->n_vglyphs) return dfail(dec, "focr_decoder_verify: no verify table (focr_decoder_set_verify_font)");
+    if (!sq_sums) return dfail(dec, "focr_decoder_verify: null sq_sums");
+    const Geometry &g = dec->run_g;
+    const size_t n_pages = dec->run_pages;
+    if (n_pages == 0) return 0;
+    const size_t W = g.page_w, H = g.page_h, px = n_pages * W * H;
+    const size_t tiles_x = (W + VERIFY_TILE_W - 1) / VERIFY_TILE_W, tiles_y = (H + VERIFY_TILE_H - 1) / VERIFY_TILE_H;
+    const size_t n_tiles = n_pages * tiles_x * tiles_y;
+    const size_t layout_blocks = std::max<size_t>(g.total, n_pages);
+    if (layout_blocks > 0x7fffffffu) return dfail(dec, "focr_decoder_verify: too many pages in one batch");
+    DEC_CHECK(hipSetDevice(dec->device));
+    if (grow(dec, &dec->d_vlines, &dec->vlines_cap, std::max<size_t>(g.total, 1))) return 1;
+    if (grow(dec, &dec->d_vrecs, &dec->vrecs_cap, std::max<size_t>((size_t)g.total * g.cap, 1))) return 1;
+    if (grow(dec, &dec->d_sums, &dec->sums_cap, n_pages)) return 1;
+    uint8_t *d_rgb = rgb_on_device ? rgb : nullptr;
+    if (rgb && !rgb_on_device) {
+        if (grow(dec, &dec->d_rgb, &dec->rgb_cap, std::max<size_t>(px * 3, 1))) return 1;
+        d_rgb = dec->d_rgb;
+    }
+    DEC_CHECK(hipEventRecord(dec->ev2, dec->stream));
+    verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, dec->run_x_start, dec->d_flags, dec->d_work,
+                                                                         dec->d_count, dec->d_nchars, dec->d_chars, dec->d_glyphs,
+                                                                         dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
+    DEC_CHECK(hipGetLastError());
+    verify_compose_kernel<<<(uint32_t)std::min<size_t>(std::max<size_t>(n_tiles, 1), VERIFY_MAX_GRID), VERIFY_TILE_W, 0, dec->stream>>>(
+        dec->run_src, g, (uint32_t)n_pages, dec->hmax, (uint32_t)tiles_x, (uint32_t)tiles_y, dec->d_vlines, dec->d_vrecs,
+        (const uint8_t *)dec->d_bitmaps, d_rgb, dec->d_sums);
+    DEC_CHECK(hipGetLastError());
+    DEC_CHECK(hipEventRecord(dec->ev3, dec->stream));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit sums");
+    DEC_CHECK(hipMemcpyAsync(sq_sums, dec->d_sums, n_pages * sizeof(uint64_t), hipMemcpyDeviceToHost, dec->stream));
+    if (rgb && !rgb_on_device) DEC_CHECK(hipMemcpyAsync(rgb, dec->d_rgb, px * 3, hipMemcpyDeviceToHost, dec->stream));
+    DEC_CHECK(hipStreamSynchronize(dec->stream));
+    DEC_CHECK(hipEventElapsedTime(&dec->last_verify_ms, dec->ev2, dec->ev3));
+    dec->last_verify_launches = 2;
+    return 0;
+}
+
+extern "C" float focr_decoder_last_verify_ms(const focr_decoder_t *dec) { return dec ? dec->last_verify_ms : 0.f; }
+extern "C" uint32_t focr_decoder_last_verify_launches(const focr_decoder_t *dec) { return dec ? dec->last_verify_launches : 0; }

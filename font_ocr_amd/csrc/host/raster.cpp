@@ -73,14 +73,20 @@ struct Face {
         out->ly = (oy + h) / 64.0f;
         return true;
     }
-    // Loader::raster_bounds default implementation for a pure translation.
-    bool raster_bounds(FT_UInt gid, float size, float tx, float ty, RectI *out) {
+    // Loader::raster_bounds before the translation: (nox, noy, nox + width, noy + height), each rounded to f32.
+    bool raster_box(FT_UInt gid, float size, RectF *out) {
         RectF tb;
         if (!typographic_bounds(gid, &tb)) return false;
         RectF trb = scale(tb, size / (float)face->units_per_EM);
         float nox = trb.ox, noy = -trb.oy - trb.height();
-        RectF r{nox + tx, noy + ty, nox + trb.width() + tx, noy + trb.height() + ty};
-        *out = round_out(r);
+        *out = RectF{nox, noy, nox + trb.width(), noy + trb.height()};
+        return true;
+    }
+    // Loader::raster_bounds default implementation for a pure translation.
+    bool raster_bounds(FT_UInt gid, float size, float tx, float ty, RectI *out) {
+        RectF b;
+        if (!raster_box(gid, size, &b)) return false;
+        *out = round_out(RectF{b.ox + tx, b.oy + ty, b.lx + tx, b.ly + ty});
         return true;
     }
 };
@@ -424,31 +430,83 @@ extern "C" int focr_render_text(const char *font_path, float text_size, int hint
     return 0;
 }
 
-extern "C" int focr_decode_font_build(const char *font_path, float text_size, int hinting, float kerning,
-                                      const uint32_t *alphabet, size_t n_alphabet, focr_decode_font_t *out, char *err,
-                                      size_t errlen) {
-    if (!font_path || !alphabet || !n_alphabet || !out) return fail(err, errlen, "focr_decode_font_build: bad arguments");
-    memset(out, 0, sizeof *out);
+namespace {
+
+// What both tables of an alphabet start from: the open face, the glyph ids and the line origin of decode_line
+struct Alphabet {
+    Face f;
+    std::vector<FT_UInt> gids;
+    float upem = 0.f, origin_x = 0.f, origin_y = 0.f;
+};
+
+int open_alphabet(const char *font_path, float text_size, float kerning, const uint32_t *alphabet, size_t n_alphabet, Alphabet *a,
+                  char *err, size_t errlen) {
     // DIVERGENCE: the reference's pen loop never ends for kerning <= 0 or a glyph that does not advance
     if (!(kerning > 0.f)) return fail(err, errlen, "kerning must be > 0 (the reference never finishes a line otherwise)");
-    Face f;
-    if (!open_face(f, font_path)) return fail(err, errlen, "cannot open font");
-    const float upem = (float)f.face->units_per_EM;
-    std::vector<FT_UInt> gids(n_alphabet);
+    if (!open_face(a->f, font_path)) return fail(err, errlen, "cannot open font");
+    a->upem = (float)a->f.face->units_per_EM;
+    a->gids.resize(n_alphabet);
     RectF bbox;  // src/main.rs:136-147: union of raster_bounds(identity), folded from the empty rect at (0, 0)
     for (size_t i = 0; i < n_alphabet; i++) {
-        gids[i] = FT_Get_Char_Index(f.face, alphabet[i]);
-        if (gids[i] == 0) {
+        a->gids[i] = FT_Get_Char_Index(a->f.face, alphabet[i]);
+        if (a->gids[i] == 0) {
             char m[96];
             snprintf(m, sizeof m, "alphabet character U+%04X missing from font", (unsigned)alphabet[i]);
             return fail(err, errlen, m);
         }
         RectI r;
-        if (!f.raster_bounds(gids[i], text_size, 0.f, 0.f, &r)) return fail(err, errlen, "glyph load failed");
+        if (!a->f.raster_bounds(a->gids[i], text_size, 0.f, 0.f, &r)) return fail(err, errlen, "glyph load failed");
         bbox = union_rect(bbox, RectF{(float)r.ox, (float)r.oy, (float)r.lx, (float)r.ly});
     }
-    const float origin_x = -bbox.ox, origin_y = -bbox.oy;
-    const FT_Pos dy = -delta_of(origin_y + 0.f);  // origin + pos, pos.y = 0
+    a->origin_x = -bbox.ox;
+    a->origin_y = -bbox.oy;
+    return 0;
+}
+
+// glyph i's pen increment, refused if it does not advance the pen
+int glyph_increment(Alphabet &a, size_t i, uint32_t codepoint, float text_size, float kerning, float *inc, char *err, size_t errlen) {
+    float adv;
+    if (!advance_units(a.f, a.gids[i], &adv)) return fail(err, errlen, "glyph load failed");
+    *inc = increment_of(adv, a.upem, text_size, kerning);
+    if (!(*inc > 0.f)) {
+        char m[128];
+        snprintf(m, sizeof m, "glyph of U+%04X does not advance the pen (the reference never finishes a line)", (unsigned)codepoint);
+        return fail(err, errlen, m);
+    }
+    return 0;
+}
+
+// The 64 phases of glyph i (26.6 delta x = p, delta y of the line origin) and the box they share
+struct Phases {
+    std::vector<Bitmap> ph = std::vector<Bitmap>(FOCR_DECODE_PHASES);
+    int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+};
+
+int render_phases(Alphabet &a, size_t i, float text_size, int hinting, Phases *out, char *err, size_t errlen) {
+    const FT_Pos dy = -delta_of(a.origin_y + 0.f);  // origin + pos, pos.y = 0
+    bool any = false;
+    for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
+        if (!render_delta(a.f, a.gids[i], text_size, hinting, p, dy, &out->ph[p])) return fail(err, errlen, "FT_Load_Glyph failed");
+        const Bitmap &b = out->ph[p];
+        if (!b.w || !b.h) continue;
+        out->x0 = any ? std::min(out->x0, b.left) : b.left;
+        out->y0 = any ? std::min(out->y0, b.top) : b.top;
+        out->x1 = any ? std::max(out->x1, b.left + b.w) : b.left + b.w;
+        out->y1 = any ? std::max(out->y1, b.top + b.h) : b.top + b.h;
+        any = true;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int focr_decode_font_build(const char *font_path, float text_size, int hinting, float kerning,
+                                      const uint32_t *alphabet, size_t n_alphabet, focr_decode_font_t *out, char *err,
+                                      size_t errlen) {
+    if (!font_path || !alphabet || !n_alphabet || !out) return fail(err, errlen, "focr_decode_font_build: bad arguments");
+    memset(out, 0, sizeof *out);
+    Alphabet a;
+    if (open_alphabet(font_path, text_size, kerning, alphabet, n_alphabet, &a, err, errlen)) return 1;
 
     std::vector<focr_decode_glyph_t> glyphs(n_alphabet);
     std::vector<uint8_t> bitmaps;
@@ -457,42 +515,24 @@ extern "C" int focr_decode_font_build(const char *font_path, float text_size, in
         focr_decode_glyph_t &g = glyphs[i];
         memset(&g, 0, sizeof g);
         g.codepoint = alphabet[i];
-        float adv;
-        if (!advance_units(f, gids[i], &adv)) return fail(err, errlen, "glyph load failed");
-        g.increment = increment_of(adv, upem, text_size, kerning);
-        if (!(g.increment > 0.f)) {
-            char m[128];
-            snprintf(m, sizeof m, "glyph of U+%04X does not advance the pen (the reference never finishes a line)", (unsigned)alphabet[i]);
-            return fail(err, errlen, m);
-        }
+        if (glyph_increment(a, i, alphabet[i], text_size, kerning, &g.increment, err, errlen)) return 1;
         min_inc = i == 0 ? g.increment : std::fmin(min_inc, g.increment);
-        std::vector<Bitmap> ph(FOCR_DECODE_PHASES);
-        int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
-        bool any = false;
-        for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
-            if (!render_delta(f, gids[i], text_size, hinting, p, dy, &ph[p])) return fail(err, errlen, "FT_Load_Glyph failed");
-            const Bitmap &b = ph[p];
-            if (!b.w || !b.h) continue;
-            x0 = any ? std::min(x0, b.left) : b.left;
-            y0 = any ? std::min(y0, b.top) : b.top;
-            x1 = any ? std::max(x1, b.left + b.w) : b.left + b.w;
-            y1 = any ? std::max(y1, b.top + b.h) : b.top + b.h;
-            any = true;
-        }
-        g.box_w = (uint32_t)(x1 - x0);
-        g.box_h = (uint32_t)(y1 - y0);
+        Phases ph;
+        if (render_phases(a, i, text_size, hinting, &ph, err, errlen)) return 1;
+        g.box_w = (uint32_t)(ph.x1 - ph.x0);
+        g.box_h = (uint32_t)(ph.y1 - ph.y0);
         g.stride = (g.box_w + 3) & ~3u;
         // the device keeps sum c^2 and sum c*r of a glyph in 32 bits: score = sum c^2 - 2 sum c*r, |score| <= 2 * 255^2 * area
         if ((uint64_t)g.stride * g.box_h * 2 * 255 * 255 >= (1ull << 31)) return fail(err, errlen, "glyph box too large for the decoder");
         g.offset = bitmaps.size();
         bitmaps.resize(bitmaps.size() + (size_t)FOCR_DECODE_PHASES * g.stride * g.box_h, 0);
         for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
-            g.off_x[p] = x0;
-            g.off_y[p] = y0;
-            const Bitmap &b = ph[p];
+            g.off_x[p] = ph.x0;
+            g.off_y[p] = ph.y0;
+            const Bitmap &b = ph.ph[p];
             uint8_t *dst = bitmaps.data() + g.offset + (size_t)p * g.stride * g.box_h;
             for (int y = 0; y < b.h; y++)
-                memcpy(dst + (size_t)(b.top - y0 + y) * g.stride + (b.left - x0), &b.px[(size_t)y * b.w], b.w);
+                memcpy(dst + (size_t)(b.top - ph.y0 + y) * g.stride + (b.left - ph.x0), &b.px[(size_t)y * b.w], b.w);
         }
     }
     out->glyphs = (focr_decode_glyph_t *)malloc(sizeof(focr_decode_glyph_t) * n_alphabet);
@@ -505,8 +545,8 @@ extern "C" int focr_decode_font_build(const char *font_path, float text_size, in
     if (!bitmaps.empty()) memcpy(out->bitmaps, bitmaps.data(), bitmaps.size());
     out->n_glyphs = n_alphabet;
     out->bitmaps_len = bitmaps.size();
-    out->origin_x = origin_x;
-    out->origin_y = origin_y;
+    out->origin_x = a.origin_x;
+    out->origin_y = a.origin_y;
     out->text_size = text_size;
     out->kerning = kerning;
     out->hinting = hinting;
@@ -518,5 +558,49 @@ extern "C" void focr_decode_font_free(focr_decode_font_t *font) {
     if (!font) return;
     free(font->glyphs);
     free(font->bitmaps);
+    memset(font, 0, sizeof *font);
+}
+
+extern "C" int focr_verify_font_build(const char *font_path, float text_size, int hinting, float kerning,
+                                      const uint32_t *alphabet, size_t n_alphabet, focr_verify_font_t *out, char *err,
+                                      size_t errlen) {
+    if (!font_path || !alphabet || !n_alphabet || !out) return fail(err, errlen, "focr_verify_font_build: bad arguments");
+    memset(out, 0, sizeof *out);
+    Alphabet a;
+    if (open_alphabet(font_path, text_size, kerning, alphabet, n_alphabet, &a, err, errlen)) return 1;
+    std::vector<focr_verify_glyph_t> glyphs(n_alphabet);
+    for (size_t i = 0; i < n_alphabet; i++) {
+        focr_verify_glyph_t &g = glyphs[i];
+        memset(&g, 0, sizeof g);
+        g.codepoint = alphabet[i];
+        if (glyph_increment(a, i, alphabet[i], text_size, kerning, &g.increment, err, errlen)) return 1;
+        RectF box;
+        if (!a.f.raster_box(a.gids[i], text_size, &box)) return fail(err, errlen, "glyph load failed");
+        g.box[0] = box.ox, g.box[1] = box.oy, g.box[2] = box.lx, g.box[3] = box.ly;
+        Phases ph;
+        if (render_phases(a, i, text_size, hinting, &ph, err, errlen)) return 1;
+        for (int p = 0; p < FOCR_DECODE_PHASES; p++) {  // an empty bitmap is the empty rectangle at the box's corner
+            const Bitmap &b = ph.ph[p];
+            const bool ink = b.w && b.h;
+            g.rect_x[p] = ink ? (uint32_t)(b.left - ph.x0) : 0;
+            g.rect_y[p] = ink ? (uint32_t)(b.top - ph.y0) : 0;
+            g.rect_w[p] = ink ? (uint32_t)b.w : 0;
+            g.rect_h[p] = ink ? (uint32_t)b.h : 0;
+        }
+    }
+    out->glyphs = (focr_verify_glyph_t *)malloc(sizeof(focr_verify_glyph_t) * n_alphabet);
+    if (!out->glyphs) return fail(err, errlen, "out of memory");
+    memcpy(out->glyphs, glyphs.data(), sizeof(focr_verify_glyph_t) * n_alphabet);
+    out->n_glyphs = n_alphabet;
+    out->origin_y = a.origin_y;
+    out->text_size = text_size;
+    out->kerning = kerning;
+    out->hinting = hinting;
+    return 0;
+}
+
+extern "C" void focr_verify_font_free(focr_verify_font_t *font) {
+    if (!font) return;
+    free(font->glyphs);
     memset(font, 0, sizeof *font);
 }

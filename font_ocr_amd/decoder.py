@@ -4,6 +4,8 @@
         dec.set_font("DejaVuSansMono.ttf", 13.0)
         pages = dec.decode(luma_pages, x=45, y=39, width=608, line_height=12, line_advance=15)
         # [[(y, text), ...] per page]
+        pages, mse, images = dec.decode(luma_pages, 45, 39, 608, 12, 15, verify="image")
+        # focr --verify on the device: red = the page's ink, blue = the decoded text re-rendered; MSE per page
 
 There is no CPU path: the decoder needs a device, and says so when it has none.
 """
@@ -64,6 +66,11 @@ def render_text(font_path, text_size, text, kerning=1.0, hinting=False):
     return out[: w.value * h.value].reshape(h.value, w.value)
 
 
+def _check_verify(verify):
+    if verify not in (None, "mse", "image"):
+        raise ValueError(f"verify must be None, 'mse' or 'image', not {verify!r}")
+
+
 class DecodeFont:
     """The 64-phase table of an alphabet (focr_decode_font_build).  Owns the native struct; free with close()."""
 
@@ -104,6 +111,41 @@ class DecodeFont:
             pass
 
 
+class VerifyFont:
+    """The verify table of an alphabet (focr_verify_font_build): each glyph's f32 raster box and each phase's true
+    bitmap rectangle inside the decode font's box.  Owns the native struct; free with close()."""
+
+    def __init__(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0):
+        self.font_path, self.text_size, self.alphabet = font_path, float(text_size), alphabet
+        self.hinting, self.kerning = bool(hinting), float(kerning)
+        self.s = N.VerifyFontStruct()
+        cps, n = _codepoints(alphabet)
+        e = _err()
+        if N.decode_raster().focr_verify_font_build(font_path.encode(), self.text_size, int(hinting), self.kerning, cps, n,
+                                                    C.byref(self.s), e, len(e)) != 0:
+            raise DecoderError(e.value.decode())
+
+    def box(self, i):
+        """raster_bounds of glyph i at the identity before round_out: (ox, oy, lx, ly) as f32."""
+        return np.array(self.s.glyphs[i].box[:], dtype=np.float32)
+
+    def rect(self, i, p):
+        """(x, y, w, h) of glyph i's phase p bitmap inside the decode font's box."""
+        g = self.s.glyphs[i]
+        return int(g.rect_x[p]), int(g.rect_y[p]), int(g.rect_w[p]), int(g.rect_h[p])
+
+    def close(self):
+        if self.s is not None:
+            N.decode_raster().focr_verify_font_free(C.byref(self.s))
+            self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LineDecoder:
     """focr's decode_image on one device: set_font(), then decode() batches of luma pages."""
 
@@ -115,6 +157,9 @@ class LineDecoder:
         self._h = h
         self.font = None
         self.last_ms = 0.0
+        self.last_verify_ms = 0.0
+        self._vfont = None
+        self._batch = None  # (n_pages, page_h, page_w) of the last run
 
     def _check(self, rc):
         if rc != 0:
@@ -122,12 +167,44 @@ class LineDecoder:
 
     def set_font(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0):
         font = font_path if isinstance(font_path, DecodeFont) else DecodeFont(font_path, text_size, alphabet, hinting, kerning)
+        self._vfont, self._batch = None, None  # the library drops its verify table and its last run here too
         self._check(self._lib.focr_decoder_set_font(self._h, C.byref(font.s)))
         self.font = font
         return font
 
+    def verify(self, images=True, rgb_device=None):
+        """focr --verify of the last decode on the device: (sums, images).  sums[p] is page p's exact sum of
+        (R - B)^2 (uint64); images is an (N, H, W, 3) uint8 array (red = the page's ink, blue = the decoded text
+        re-rendered), or None when images is false or when they go to rgb_device, a device address of the HIP runtime
+        this library uses with room for N * H * W * 3 bytes.  The verify table is built on first use."""
+        if self._batch is None:
+            raise DecoderError("verify: no decode since the font was set")
+        if self._vfont is None:
+            f = self.font
+            vf = VerifyFont(f.font_path, f.text_size, f.alphabet, f.hinting, f.kerning)
+            self._check(self._lib.focr_decoder_set_verify_font(self._h, C.byref(vf.s)))
+            self._vfont = vf
+        n, h, w = self._batch
+        sums = np.zeros(max(1, n), dtype=np.uint64)
+        out = np.empty((n, h, w, 3), dtype=np.uint8) if images and rgb_device is None else None
+        if rgb_device is not None:
+            rgb, on_device = C.c_void_p(int(rgb_device)), 1
+        else:
+            rgb, on_device = (C.c_void_p(out.ctypes.data) if out is not None and out.size else None), 0
+        self._check(self._lib.focr_decoder_verify(self._h, rgb, on_device, sums.ctypes.data))
+        self.last_verify_ms = float(self._lib.focr_decoder_last_verify_ms(self._h))
+        return sums[:n], out
+
+    def _verified(self, verify, h, w):
+        """(mse per page as f32, images or None) of the last run, for decode(verify=...)."""
+        sums, imgs = self.verify(images=verify == "image")
+        mse = sums.astype(np.float32) / np.float32((h * w) & 0xFFFFFFFF)  # red_blue_mse: (sum as f32) / (w * h as u32)
+        return mse, imgs
+
     def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance):
+        self._batch = None
         self._check(self._lib.focr_decoder_run(self._h, ptr, int(on_device), n, w, h, x, y, width, line_height, line_advance))
+        self._batch = (n, h, w)
         self.last_ms = float(self._lib.focr_decoder_last_ms(self._h))
         nl, nc = self._lib.focr_decoder_n_lines(self._h), self._lib.focr_decoder_n_chars(self._h)
         lines = (N.DecodedLine * max(1, nl))()
@@ -141,17 +218,22 @@ class LineDecoder:
             out[ln.page].append((int(ln.y), text))
         return out
 
-    def decode(self, luma_pages, x, y, width, line_height, line_advance):
+    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
-        Returns [[(y, text), ...] per page] in page order."""
+        Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
+        mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
+        "image" and None for "mse"; each size group is verified on the device right after its own decode."""
         if self.font is None:
             raise DecoderError("set_font() first")
+        _check_verify(verify)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
         else:
             pages = list(luma_pages)
         out = [None] * len(pages)
+        mse = np.zeros(len(pages), dtype=np.float32)
+        images = [None] * len(pages) if verify == "image" else None
         by_size = {}
         for i, p in enumerate(pages):
             by_size.setdefault(np.asarray(p).shape, []).append(i)
@@ -160,15 +242,26 @@ class LineDecoder:
             res = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo)
             for i, r in zip(idx, res):
                 out[i] = r
-        return out
+            if verify:
+                m, imgs = self._verified(verify, h, w)
+                mse[idx] = m
+                for j, i in enumerate(idx):
+                    if images is not None:
+                        images[i] = imgs[j]
+        return (out, mse, images) if verify else out
 
-    def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance):
+    def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
-        this library uses, on the decoder's device, written before the call)."""
+        this library uses, on the decoder's device, written before the call and still valid for the verify)."""
         if self.font is None:
             raise DecoderError("set_font() first")
-        return self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
-                         int(line_height), int(line_advance))
+        _check_verify(verify)
+        out = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
+                        int(line_height), int(line_advance))
+        if not verify:
+            return out
+        mse, imgs = self._verified(verify, int(page_h), int(page_w))
+        return out, mse, (list(imgs) if imgs is not None else None)
 
     def close(self):
         if self._h is not None:

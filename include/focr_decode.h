@@ -8,8 +8,9 @@
  * the decode font below holds those 64 phases per glyph, built once on the host, and the device does an exact integer
  * argmin with them.
  *
- * libfocr_raster.so : focr_raster_glyph, focr_glyph_metrics, focr_render_text, focr_decode_font_build/free (FreeType)
- * libfocr_hip.so    : focr_decoder_* (gfx950)
+ * libfocr_raster.so : focr_raster_glyph, focr_glyph_metrics, focr_render_text, focr_decode_font_build/free,
+ *                     focr_verify_font_build/free (FreeType)
+ * libfocr_hip.so    : focr_decoder_* (gfx950), including the device verify of a run (--verify)
  */
 #ifndef FOCR_DECODE_H
 #define FOCR_DECODE_H
@@ -75,6 +76,34 @@ int focr_decode_font_build(const char *font_path, float text_size, int hinting, 
                            size_t n_alphabet, focr_decode_font_t *out, char *err, size_t errlen);
 void focr_decode_font_free(focr_decode_font_t *font);
 
+/* ---- host: the verify table (libfocr_raster.so) ------------------------------------------------------------------ */
+
+/* What render() needs beyond the decode font, for one alphabet glyph.  box is raster_bounds at the identity before
+ * round_out: (nox, noy, nox + width, noy + height) in px, each an f32 as the host computes it, so that raster_bounds at
+ * a translation (tx, ty) is round_out(box + (tx, ty)) in f32.  rect_* is phase p's true FreeType bitmap inside the
+ * decode font's box (box-relative, zeros included); render() copies exactly that rectangle and nothing of the padding. */
+typedef struct focr_verify_glyph {
+    uint32_t codepoint;
+    float increment;                         /* equal to the decode font's, bitwise */
+    float box[4];
+    uint32_t rect_x[FOCR_DECODE_PHASES], rect_y[FOCR_DECODE_PHASES];
+    uint32_t rect_w[FOCR_DECODE_PHASES], rect_h[FOCR_DECODE_PHASES];
+} focr_verify_glyph_t;
+
+typedef struct focr_verify_font {
+    focr_verify_glyph_t *glyphs;             /* alphabet order */
+    size_t n_glyphs;
+    float origin_y;                          /* the vertical translation the decode font's phases are rendered at */
+    float text_size, kerning;
+    int hinting;
+} focr_verify_font_t;
+
+/* Build the verify table for the same arguments as focr_decode_font_build (and with the same refusals).  Free with
+ * focr_verify_font_free. */
+int focr_verify_font_build(const char *font_path, float text_size, int hinting, float kerning, const uint32_t *alphabet,
+                           size_t n_alphabet, focr_verify_font_t *out, char *err, size_t errlen);
+void focr_verify_font_free(focr_verify_font_t *font);
+
 /* ---- device: the decoder (libfocr_hip.so) ------------------------------------------------------------------------ */
 
 typedef struct focr_decoder focr_decoder_t;
@@ -110,6 +139,26 @@ int focr_decoder_get(const focr_decoder_t *dec, focr_decoded_line_t *lines, uint
 float focr_decoder_last_ms(const focr_decoder_t *dec);
 /* Kernel launches of the last run (constant per batch). */
 uint32_t focr_decoder_last_launches(const focr_decoder_t *dec);
+
+/* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
+
+/* Upload the verify table of the current decode font (the decoder keeps its own copy).  Refused unless it matches the
+ * decode font: glyph count, code points, increments (bitwise), origin, size, kerning and hinting.  focr_decoder_set_font
+ * drops the verify table, and so does a failed upload. */
+int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_verify_font_t *font);
+/* The verify image and squared error of every page of the last successful focr_decoder_run, on the decoder's stream:
+ * red = the page's luma where it is not 255, blue = 255 - v where the decoded line rendered at (x_start, line y) as
+ * render() does has v != 0 (later lines over earlier ones, clipped to the page), green = 0.  rgb receives
+ * n_pages x page_h x page_w x 3 bytes, in host memory, or in device memory of the decoder's device when
+ * rgb_on_device != 0, or nothing when NULL; sq_sums[n_pages] receives the exact sum over the page of (R - B)^2 (the
+ * reference's MSE is (float)sum / (float)(uint32_t)(page_w * page_h)).  For a run from device-memory pages, the
+ * caller's page buffer must still hold those pages.  Runs a fixed number of launches and returns when the results are
+ * in rgb and sq_sums.  Fails with a message without a successful run since the last set_font, or without a verify
+ * table. */
+int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums);
+/* Device time of the last verify's kernels in ms (events), and their launch count (constant per batch). */
+float focr_decoder_last_verify_ms(const focr_decoder_t *dec);
+uint32_t focr_decoder_last_verify_launches(const focr_decoder_t *dec);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,10 @@ focr's default alphabet, 40 text lines at line_advance 15, decoded at x 45, y 39
   device_ms_per_batch  median over --steps runs after --warmup, device events around the batch's kernels
   wall_ms_per_batch    median host time of one decode() call (upload, launches, read-back)
   pages/s, lines/s and page Mpx/s from the device time
+With --verify, also focr --verify's images of the batch on the device (focr_decoder_verify):
+  verify_device_ms_per_batch  median device time of the verify's kernels
+  verify_launches             their launch count
+  verify_wall_ms              median host time of one verify call with the images read back to the host
 
 No reference number: the reference's Rust / font-kit build is not available to run beside it.  Kernel times per
 launch come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
@@ -47,6 +51,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--verify", action="store_true", help="also time the device verify of the batch")
     a = ap.parse_args()
     pages = synth(a.pages, a.seed)
     geo = (45, 39, 608, 12, 15)
@@ -64,17 +69,31 @@ def main():
             wall.append((time.perf_counter() - t) * 1e3)
             dev.append(dec.last_ms)
         launches = int(dec._lib.focr_decoder_last_launches(dec._h))
+        if a.verify:
+            for _ in range(a.warmup):
+                dec.verify()
+            vdev, vwall = [], []
+            for _ in range(a.steps):
+                t = time.perf_counter()
+                dec.verify()
+                vwall.append((time.perf_counter() - t) * 1e3)
+                vdev.append(dec.last_verify_ms)
+            vlaunches = int(dec._lib.focr_decoder_last_verify_launches(dec._h))
     n_lines = sum(len(p) for p in out)
     n_chars = sum(len(t) for p in out for _, t in p)
     ms = float(np.median(dev))
-    print(json.dumps({
+    res = {
         "bench": "focr_decode", "pages": a.pages, "page_w": 608, "page_h": 720, "lines": n_lines, "chars": n_chars,
         "font": "DejaVuSansMono 13px", "alphabet_len": len(FOCR_DEFAULT_ALPHABET), "launches_per_batch": launches,
         "host_table_ms": round(host_ms, 2), "device_ms_per_batch": round(ms, 4), "device_ms_min": round(float(min(dev)), 4),
         "wall_ms_per_batch": round(float(np.median(wall)), 3), "steps": a.steps, "warmup": a.warmup,
         "pages_per_s": round(a.pages / ms * 1e3, 1), "lines_per_s": round(n_lines / ms * 1e3, 1),
         "page_mpx_per_s": round(a.pages * 608 * 720 / ms / 1e3, 1),
-    }))
+    }
+    if a.verify:
+        res.update({"verify_device_ms_per_batch": round(float(np.median(vdev)), 4), "verify_launches": vlaunches,
+                    "verify_wall_ms": round(float(np.median(vwall)), 3)})
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
