@@ -73,11 +73,12 @@ def verify_image(page, lines, font, size, x, kerning=1.0, hinting=False):
     H, W = page.shape
     out = np.zeros((H, W, 3), dtype=np.uint8)
     out[..., 0] = np.where(page != 255, page, 0)
-    for ly, text in lines:
+    for ly, text in lines:  # in line order: a later line's ink replaces an earlier one's
         c = render_text(font, size, text, kerning, hinting)
-        for yy, xx in zip(*np.nonzero(c)):
-            if x + xx < W and ly + yy < H:
-                out[ly + yy, x + xx, 2] = 255 - c[yy, xx]
+        hh, ww = min(c.shape[0], H - ly), min(c.shape[1], W - x)
+        if hh > 0 and ww > 0:
+            c = c[:hh, :ww]
+            np.copyto(out[ly: ly + hh, x: x + ww, 2], 255 - c, where=c != 0)
     d = out[..., 0].astype(np.int64) - out[..., 2].astype(np.int64)
     mse = F32(F32(int((d * d).sum())) / F32(W * H))
     return out, mse
