@@ -3,5 +3,5 @@
 HIP kernels + C ABI live in csrc/ (built in-tree into lib/); this package is the thin host-side
 mirror used by tests and bench.py.  See DESIGN.md.
 """
-from .bank import ASCII95, DEFAULT_ALPHABET, Bank, load_image, save_pgm, synth_page, synth_pages  # noqa: F401
+from .bank import ASCII95, DEFAULT_ALPHABET, Bank, load_image, load_image_rgba, save_pgm, synth_page, synth_pages  # noqa: F401
 from .decoder import FOCR_DEFAULT_ALPHABET, DecodeFont, LineDecoder, VerifyFont  # noqa: F401,E402

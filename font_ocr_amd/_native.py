@@ -176,6 +176,8 @@ HOST_SYMBOLS = {
     "focr_bank_load": (C.c_int, [C.c_char_p, C.POINTER(BankStruct)]),
     "focr_image_load_luma8": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
+    "focr_image_load_rgba8": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
     "focr_image_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
     "focr_image_load_luma8_into": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                              C.c_char_p, C.c_size_t]),
@@ -349,6 +351,12 @@ DECODE_HIP_SYMBOLS = {
     "focr_decoder_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "focr_decoder_last_verify_ms": (C.c_float, [C.c_void_p]),
     "focr_decoder_last_verify_launches": (C.c_uint32, [C.c_void_p]),
+    "focr_decoder_test_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
+                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_int]),
+    "focr_decoder_last_test_ms": (C.c_float, [C.c_void_p]),
+    "focr_decoder_last_test_launches": (C.c_uint32, [C.c_void_p]),
+    "focr_decoder_debug_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 

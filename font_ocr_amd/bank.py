@@ -155,6 +155,19 @@ def load_image(path):
         C.CDLL(None).free(px)
 
 
+def load_image_rgba(path):
+    """image::open(path).into_rgba8() (focr --test): PNM or PNG -> (h, w, 4) uint8, tRNS applied."""
+    px = C.POINTER(C.c_uint8)()
+    w, h = C.c_size_t(), C.c_size_t()
+    err = C.create_string_buffer(256)
+    if N.host().focr_image_load_rgba8(str(path).encode(), C.byref(px), C.byref(w), C.byref(h), err, 256) != 0:
+        raise OSError(err.value.decode())
+    try:
+        return np.frombuffer(C.string_at(px, w.value * h.value * 4), np.uint8).reshape(h.value, w.value, 4).copy()
+    finally:
+        C.CDLL(None).free(px)
+
+
 def save_pgm(path, img):
     img = np.ascontiguousarray(img, np.uint8)
     if N.host().focr_image_save_pgm(str(path).encode(), img.ctypes.data, img.shape[1], img.shape[0]) != 0:

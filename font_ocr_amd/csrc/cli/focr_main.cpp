@@ -6,7 +6,10 @@
 //   * kerning <= 0 or a glyph that does not advance the pen is an error (the reference never finishes a line);
 //   * --verify clips rendered text that falls outside the page (the reference panics there); its images are drawn on the
 //     device (focr_decoder_verify) and written on up to 16 threads;
-//   * --test is refused: its RGBA blend cannot be pinned here.
+//   * --test draws its two images on the device (focr_decoder_test_images) from the first -i image only, as the reference
+//     does; boxes that fall outside the page are clipped (the reference panics in get_pixel_mut), the decode font's
+//     refusals apply (kerning <= 0, a glyph that does not advance; the reference's --test decodes nothing), line_advance 0
+//     is refused, and its blend is image's Blend for Rgba<u8> restated in f32 (parity unpinned).
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -69,7 +72,7 @@ void print_help() {
            "  -w, --width <WIDTH>                  \n"
            "      --line-height <LINE_HEIGHT>      \n"
            "      --line-advance <LINE_ADVANCE>    \n"
-           "      --test <TEST>                    Prefix for output test images (not supported here)\n"
+           "      --test <TEST>                    Prefix for output test images\n"
            "      --verify <VERIFY>                Dir for verify images. Red is reference, Blue is rendered\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
@@ -171,9 +174,10 @@ std::string utf8_encode(uint32_t cp) {
     return s;
 }
 
-// 8-bit RGB PNG, filter 0 on every row (what DynamicImage::save writes for an RgbImage, byte for byte in the pixels)
-bool write_png_rgb(const std::string &path, const uint8_t *px, uint32_t w, uint32_t h) {
-    const size_t row = (size_t)w * 3;
+// 8-bit RGB (colour type 2) or RGBA (colour type 6) PNG, filter 0 on every row (what DynamicImage::save writes for an
+// RgbImage / RgbaImage, byte for byte in the pixels)
+bool write_png(const std::string &path, const uint8_t *px, uint32_t w, uint32_t h, bool alpha) {
+    const size_t row = (size_t)w * (alpha ? 4 : 3);
     std::vector<uint8_t> raw((row + 1) * h);
     for (uint32_t y = 0; y < h; y++) {
         raw[(size_t)y * (row + 1)] = 0;
@@ -203,7 +207,7 @@ bool write_png_rgb(const std::string &path, const uint8_t *px, uint32_t w, uint3
     be32(ihdr, w);
     be32(ihdr + 4, h);
     ihdr[8] = 8;  // bit depth
-    ihdr[9] = 2;  // colour type: RGB
+    ihdr[9] = alpha ? 6 : 2;  // colour type: RGBA or RGB
     chunk("IHDR", ihdr, 13);
     chunk("IDAT", z.data(), (uint32_t)zl);
     chunk("IEND", nullptr, 0);
@@ -223,7 +227,7 @@ std::vector<char> write_verify_pngs(const std::vector<std::string> &paths, const
     std::vector<char> ok(n, 0);
     std::atomic<size_t> next{0};
     auto work = [&]() {
-        for (size_t j; (j = next.fetch_add(1)) < n;) ok[j] = write_png_rgb(paths[j], rgb + j * page, W, H);
+        for (size_t j; (j = next.fetch_add(1)) < n;) ok[j] = write_png(paths[j], rgb + j * page, W, H, false);
     };
     std::vector<std::thread> pool;
     for (size_t t = 1; t < std::min<size_t>(16, n); t++) pool.emplace_back(work);
@@ -239,19 +243,56 @@ std::string verify_path(const std::string &dir, const std::string &img) {  // Pa
     return dir + (dir.empty() || dir.back() == '/' ? "" : "/") + name + ".png";
 }
 
+// --test PREFIX (src/main.rs:416-425): PREFIX-rect.png (the box of every non-blank line slot) and PREFIX-text.png (the
+// alphabet rendered at the top-left corner), both over the first -i image as RGBA, drawn on the device; nothing on stdout.
+int run_test(const Args &args, const std::vector<uint32_t> &alphabet) {
+    if (args.img.empty()) die("--test: no -i image to draw on");
+    const std::string &img = args.img[0];
+    char err[256] = {0};
+    uint8_t *luma = nullptr, *rgba = nullptr;
+    size_t W = 0, H = 0, w2 = 0, h2 = 0;
+    if (focr_image_load_luma8(img.c_str(), &luma, &W, &H, err, sizeof err) != 0 ||
+        focr_image_load_rgba8(img.c_str(), &rgba, &w2, &h2, err, sizeof err) != 0)
+        die("--test: called `Result::unwrap()` on an `Err` value: " + std::string(err) + " (" + img + ")");
+    if (w2 != W || h2 != H) die("--test: image size changed while reading " + img);
+    focr_decode_font_t font{};
+    if (focr_decode_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), &font, err,
+                               sizeof err) != 0)
+        die(std::string("--test: decode font: ") + err);
+    focr_verify_font_t vfont{};
+    if (focr_verify_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), &vfont, err,
+                               sizeof err) != 0)
+        die(std::string("--test: verify font: ") + err);
+    focr_decoder_t *dec = nullptr;
+    if (focr_decoder_create(0, &dec) != 0) die(std::string("--test: no usable GPU: ") + focr_decoder_last_error(nullptr), 1);
+    if (focr_decoder_set_font(dec, &font) != 0 || focr_decoder_set_verify_font(dec, &vfont) != 0)
+        die(std::string("--test: ") + focr_decoder_last_error(dec), 1);
+    std::vector<uint8_t> rect(W * H * 4), text(W * H * 4);
+    if (focr_decoder_test_images(dec, luma, rgba, 0, 1, W, H, args.x, args.y, args.width, args.line_height, args.line_advance, rect.data(),
+                                 text.data(), 0) != 0)
+        die(std::string("--test: focr_decoder_test_images: ") + focr_decoder_last_error(dec), 1);
+    focr_decoder_destroy(dec);
+    focr_verify_font_free(&vfont);
+    focr_decode_font_free(&font);
+    free(luma);
+    free(rgba);
+    for (const auto &out : {std::make_pair(args.test + "-rect.png", rect.data()), std::make_pair(args.test + "-text.png", text.data())})
+        if (!write_png(out.first, out.second, (uint32_t)W, (uint32_t)H, true)) die("--test: cannot write " + out.first);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     Args args = parse_args(argc, argv);
-    if (args.have_test)
-        die("--test is not supported by this port (its RGBA blend of the test images is not pinned); decode without it", 1);
     if (args.have_verify) {
         struct stat st;
         if (stat(args.verify.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) die("--verify should be a dir");  // src/main.rs:389-391
     }
+    std::vector<uint32_t> alphabet = utf8_decode(args.alphabet);
+    if (args.have_test) return run_test(args, alphabet);
     if (args.img.empty()) return 0;
 
-    std::vector<uint32_t> alphabet = utf8_decode(args.alphabet);
     char err[256] = {0};
     focr_decode_font_t font{};
     if (focr_decode_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), &font, err,

@@ -19,6 +19,13 @@
 //      last glyph covering each pixel (an LDS atomic max of the glyph index, so placement and order do not matter),
 //      lets a non-zero value replace the blue of earlier lines, writes RGB and adds the exact sum of (R - B)^2 to the
 //      page's total with one 64-bit atomic.
+//
+// focr_decoder_test_images draws focr --test's two images of a batch in three more launches, in buffers of its own:
+//   6. test_flags_kernel: the blank test of every slot, as the prepass makes it;
+//   7. test_layout_kernel: one wave lays out render() of the whole alphabet at (0, 0), as verify_layout_kernel does a line;
+//   8. test_compose_kernel: one workgroup per tile counts, per row, the non-blank boxes with an edge on it and blends each
+//      pixel once per edge through it (the rect image), and blends the last alphabet glyph over each pixel (the text
+//      image), both from the base RGBA pixel with image's Blend for Rgba<u8> restated in f32 (blend_rgba).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -211,28 +218,22 @@ struct VerifyRec {     // one glyph: its bitmap rectangle on the page, clipped t
     uint32_t src, stride;  // byte offset in the bitmap table of the pixel at (x0, y0)
 };
 
-// 4. render()'s layout of every decoded line, one wave per work-list line; blocks below n_pages also zero the sums
-__global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t n_pages, uint32_t x_start, const uint32_t *__restrict__ flags,
-                                                           const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
-                                                           const uint32_t *__restrict__ n_chars, const uint16_t *__restrict__ chars,
-                                                           const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
-                                                           const VerifyPhase *__restrict__ vphases, VerifyLine *__restrict__ lines,
-                                                           VerifyRec *__restrict__ recs, unsigned long long *__restrict__ sums) {
-    const uint32_t b = blockIdx.x, lane = threadIdx.x;
-    if (b < n_pages && lane == 0) sums[b] = 0;
-    if (b >= g.total) return;
-    if (lane == 0 && flags[b] == 0) lines[b] = VerifyLine{0, 0, 0, 0, 0, 0};  // blank slots are in no work-list entry
-    if (b >= *count) return;
-    const uint32_t k = b, slot = work[k], n = n_chars[k];
-    const uint16_t *cs = chars + (size_t)k * g.cap;
-    VerifyRec *out = recs + (size_t)k * g.cap;
-    // the pen (f32 adds in text order) and the union of round_out boxes, folded from the empty rect at (0, 0)
+// render()'s layout of one line of n glyphs on a page of g, by one wave: the pen (f32 adds in text order), the union
+// of round_out boxes folded from the empty rect at (0, 0), and each glyph's true bitmap rectangle clipped to the canvas
+// and the page, written to out[0 .. n).  The line is cs[0 .. n) at (x_start, y of g's slot), or for IOTA the alphabet
+// indices 0 .. n - 1 at (x_start, 0).  Lane 0 writes the line's canvas on the page to *line, clipped (empty when none
+// of it is on the page), with k and n.
+template <bool IOTA>
+__device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, const uint16_t *__restrict__ cs, uint32_t n, uint32_t k,
+                                            uint32_t x_start, const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
+                                            const VerifyPhase *__restrict__ vphases, VerifyRec *__restrict__ out, VerifyLine *__restrict__ line) {
+    const uint32_t lane = threadIdx.x;
     float pen = 0.f;
     int ox = 0, oy = 0, lx = 0, ly = 0;
     for (uint32_t base = 0; base < n; base += 64) {
         const uint32_t j = base + lane, m = std::min(64u, n - base);
         const bool live = j < n;
-        const uint32_t c = live ? cs[j] : 0;
+        const uint32_t c = live ? (IOTA ? j : cs[j]) : 0;
         const float inc = live ? glyphs[c].inc : 0.f;
         float pos = 0.f;
         for (uint32_t q = 0; q < m; q++) {
@@ -256,12 +257,12 @@ __global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t 
     }
     const int cw = lx - ox, ch = ly - oy;
     const int64_t W = g.page_w, H = g.page_h;
-    const int64_t line_y = (int64_t)g.y_start + (int64_t)(slot % g.n_slots) * g.line_advance;
+    const int64_t line_y = IOTA ? 0 : (int64_t)g.y_start + (int64_t)(slot % g.n_slots) * g.line_advance;
     const float neg_ox = (float)(-ox);
     for (uint32_t j = lane; j < n; j += 64) {
         const float pos = __int_as_float(out[j].x0);
         const int d = (int)__fmul_rn(__fadd_rn(neg_ox, pos), 64.0f);  // FreeType's delta: trunc((-bounds.ox + pos) * 64) >= 0
-        const VerifyPhase ph = vphases[(size_t)cs[j] * FOCR_DECODE_PHASES + (d & 63)];
+        const VerifyPhase ph = vphases[(size_t)(IOTA ? j : cs[j]) * FOCR_DECODE_PHASES + (d & 63)];
         const int gx0 = (d >> 6) + ph.x, gy0 = ph.y - oy;  // on the canvas: whole-pixel shift, vertical delta -bounds.oy
         const int ax0 = std::max(gx0, 0), ay0 = std::max(gy0, 0);
         const int ax1 = std::min(gx0 + (int)ph.w, cw), ay1 = std::min(gy0 + (int)ph.h, ch);
@@ -277,8 +278,24 @@ __global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t 
         const int64_t X1 = std::min<int64_t>(x_start + (int64_t)cw, W), Y1 = std::min<int64_t>(line_y + ch, H);
         VerifyLine l{0, 0, 0, 0, k, n};
         if ((int64_t)x_start < X1 && line_y < Y1) l = VerifyLine{(int32_t)x_start, (int32_t)line_y, (int32_t)X1, (int32_t)Y1, k, n};
-        lines[slot] = l;
+        *line = l;
     }
+}
+
+// 4. render()'s layout of every decoded line, one wave per work-list line; blocks below n_pages also zero the sums
+__global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t n_pages, uint32_t x_start, const uint32_t *__restrict__ flags,
+                                                           const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
+                                                           const uint32_t *__restrict__ n_chars, const uint16_t *__restrict__ chars,
+                                                           const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
+                                                           const VerifyPhase *__restrict__ vphases, VerifyLine *__restrict__ lines,
+                                                           VerifyRec *__restrict__ recs, unsigned long long *__restrict__ sums) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (b < n_pages && lane == 0) sums[b] = 0;
+    if (b >= g.total) return;
+    if (lane == 0 && flags[b] == 0) lines[b] = VerifyLine{0, 0, 0, 0, 0, 0};  // blank slots are in no work-list entry
+    if (b >= *count) return;
+    const uint32_t k = b, slot = work[k], n = n_chars[k];
+    layout_line<false>(g, slot, chars + (size_t)k * g.cap, n, k, x_start, glyphs, vglyphs, vphases, recs + (size_t)k * g.cap, lines + slot);
 }
 
 // 5. compose the verify image tile by tile; every thread owns one column of a 16-row, 256-column tile
@@ -360,6 +377,144 @@ __global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_kernel(const uin
     }
 }
 
+// ---- test images (focr --test: draw_test_rectangles, draw_test_text) ------------------------------------------------
+
+constexpr uint32_t TEST_THREADS = 256;
+
+// image 0.25's Blend for Rgba<u8> (restated from the published crate, parity unpinned): every step one f32 operation,
+// rounded on its own, and the result cast back with NumCast (truncation toward zero; every value lies in [0, 256)).
+__device__ __forceinline__ uint32_t blend_rgba(uint32_t bg, uint32_t fg) {
+    const uint32_t fa8 = fg >> 24;
+    if (fa8 == 0) return bg;     // the crate's shortcuts: a transparent foreground changes nothing,
+    if (fa8 == 255) return fg;   // an opaque one replaces the pixel
+    const float m = 255.0f;
+    const float bg_a = __fdiv_rn((float)(bg >> 24), m), fg_a = __fdiv_rn((float)fa8, m);
+    const float a = __fsub_rn(__fadd_rn(bg_a, fg_a), __fmul_rn(bg_a, fg_a));
+    if (a == 0.f) return bg;
+    const float keep = __fsub_rn(1.0f, fg_a);
+    uint32_t out = (uint32_t)__fmul_rn(m, a) << 24;
+    for (int c = 0; c < 3; c++) {
+        const float b = __fdiv_rn((float)((bg >> (8 * c)) & 255), m), f = __fdiv_rn((float)((fg >> (8 * c)) & 255), m);
+        const float v = __fdiv_rn(__fadd_rn(__fmul_rn(f, fg_a), __fmul_rn(__fmul_rn(b, bg_a), keep)), a);
+        out |= ((uint32_t)__fmul_rn(m, v) & 255) << (8 * c);
+    }
+    return out;
+}
+
+// focr_decoder_debug_blend: pixel i of out = blend_rgba(bg[i], fg[i]), RGBA bytes packed little-endian
+__global__ __launch_bounds__(TEST_THREADS) void debug_blend_kernel(const uint32_t *__restrict__ bg, const uint32_t *__restrict__ fg, size_t n,
+                                                                   uint32_t *__restrict__ out) {
+    for (size_t i = (size_t)blockIdx.x * TEST_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * TEST_THREADS) out[i] = blend_rgba(bg[i], fg[i]);
+}
+
+// 6. the blank test of every (page, slot), as line_prepass_kernel makes it but without the strip: one workgroup per slot
+__global__ __launch_bounds__(TEST_THREADS) void test_flags_kernel(const uint8_t *__restrict__ pages, Geometry g, uint32_t *__restrict__ flags) {
+    const uint32_t slot = blockIdx.x;
+    if (slot >= g.total) return;
+    const uint32_t page = slot / g.n_slots, i = slot % g.n_slots;
+    uint32_t yc, h;
+    slot_rows(g, i, &yc, &h);
+    const uint8_t *src = pages + (size_t)page * g.page_w * g.page_h + (size_t)yc * g.page_w + g.x;
+    int ink = 0;
+    const uint64_t n = (uint64_t)g.w * h;
+    for (uint64_t k = threadIdx.x; k < n; k += TEST_THREADS) ink |= src[(k / g.w) * g.page_w + k % g.w] != 255;
+    ink = __syncthreads_or(ink);
+    if (threadIdx.x == 0) flags[slot] = ink ? 1u : 0u;
+}
+
+// 7. render() of the whole alphabet at (0, 0) on a page of g, one wave
+__global__ __launch_bounds__(64) void test_layout_kernel(Geometry g, uint32_t n_glyphs, const DevGlyph *__restrict__ glyphs,
+                                                         const VerifyGlyph *__restrict__ vglyphs, const VerifyPhase *__restrict__ vphases,
+                                                         VerifyRec *__restrict__ recs, VerifyLine *__restrict__ line) {
+    layout_line<true>(g, 0, nullptr, n_glyphs, 0, 0, glyphs, vglyphs, vphases, recs, line);
+}
+
+// 8. both test images, tile by tile; every thread owns one column of a 16-row, 256-column tile.  The base pixel is
+// base's, or (l, l, l, 255) from the luma without one.  rect: the pixel takes the red blend once per box edge through
+// it (a corner is on two edges), counted per tile row from the flags of the slots whose box reaches the row; k blends in
+// sequence stop early once one leaves the pixel as it was.  text: the last alphabet glyph over the pixel, as in
+// verify_compose_kernel, blends (255 - v, 0, 0, 128) where its value v is not zero.  A null output is not drawn.
+__global__ __launch_bounds__(VERIFY_TILE_W) void test_compose_kernel(const uint8_t *__restrict__ pages, const uint32_t *__restrict__ base,
+                                                                     Geometry g, uint32_t n_pages, uint32_t x_start, uint32_t width,
+                                                                     uint32_t tiles_x, uint32_t tiles_y, const uint32_t *__restrict__ flags,
+                                                                     const VerifyLine *__restrict__ line, const VerifyRec *__restrict__ recs,
+                                                                     const uint8_t *__restrict__ bitmaps, uint32_t *__restrict__ rect,
+                                                                     uint32_t *__restrict__ text) {
+    __shared__ uint32_t win[VERIFY_TILE_H * VERIFY_TILE_W];  // 1 + index of the last glyph over the pixel
+    __shared__ uint32_t n_h[VERIFY_TILE_H], n_v[VERIFY_TILE_H];  // per tile row: boxes with a horizontal edge on it, boxes spanning it
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint64_t per_page = (uint64_t)tiles_x * tiles_y, n_tiles = per_page * n_pages;
+    const size_t W = g.page_w, H = g.page_h;
+    const int64_t X0 = x_start, X1 = (int64_t)x_start + width;
+    const VerifyLine l = text ? *line : VerifyLine{0, 0, 0, 0, 0, 0};
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t page = (uint32_t)(tile / per_page), rem = (uint32_t)(tile % per_page);
+        const int r0 = (int)((rem / tiles_x) * VERIFY_TILE_H), c0 = (int)((rem % tiles_x) * VERIFY_TILE_W);
+        const int r1 = std::min<int>(r0 + VERIFY_TILE_H, (int)H), c1 = std::min<int>(c0 + VERIFY_TILE_W, (int)W);
+        for (uint32_t r = 0; r < VERIFY_TILE_H; r++) win[r * VERIFY_TILE_W + t] = 0;
+        if (t < VERIFY_TILE_H) n_h[t] = 0, n_v[t] = 0;
+        __syncthreads();
+        if (rect && g.n_slots) {  // slots i with y_i <= r1 - 1 and y_i + line_height >= r0
+            const int64_t lo = (int64_t)r0 - g.line_height - g.y_start, hi = (int64_t)r1 - 1 - g.y_start;
+            const int64_t i_lo = lo <= 0 ? 0 : (lo + g.line_advance - 1) / g.line_advance;
+            const int64_t i_hi = hi < 0 ? -1 : std::min<int64_t>(g.n_slots - 1, hi / g.line_advance);
+            const int64_t n_pairs = (i_hi - i_lo + 1) * VERIFY_TILE_H;
+            for (int64_t q = t; q < n_pairs; q += VERIFY_TILE_W) {
+                const int64_t i = i_lo + q / VERIFY_TILE_H, y = r0 + q % VERIFY_TILE_H;
+                if (y >= r1 || !flags[(size_t)page * g.n_slots + i]) continue;
+                const int64_t Y0 = (int64_t)g.y_start + i * g.line_advance, Y1 = Y0 + g.line_height;
+                const uint32_t e = (y == Y0) + (y == Y1);
+                if (e) atomicAdd(&n_h[y - r0], e);
+                if (Y0 <= y && y <= Y1) atomicAdd(&n_v[y - r0], 1u);
+            }
+        }
+        const bool glyphs_here = l.n && l.x0 < c1 && l.x1 > c0 && l.y0 < r1 && l.y1 > r0;  // uniform across the workgroup
+        if (glyphs_here)
+            for (uint32_t j = wave; j < l.n; j += VERIFY_TILE_W / 64) {
+                const VerifyRec r = recs[j];
+                const int x0 = std::max(r.x0, c0), x1 = std::min(r.x1, c1), y0 = std::max(r.y0, r0), y1 = std::min(r.y1, r1);
+                if (x0 >= x1 || y0 >= y1) continue;
+                const int w = x1 - x0, npx = w * (y1 - y0);
+                for (int q = (int)lane; q < npx; q += 64)
+                    atomicMax(&win[(y0 + q / w - r0) * VERIFY_TILE_W + (x0 + q % w - c0)], j + 1);
+            }
+        __syncthreads();
+        const int x = c0 + (int)t;
+        if (x < c1)
+            for (int y = r0; y < r1; y++) {
+                const size_t at = ((size_t)page * H + y) * W + x;
+                uint32_t px;
+                if (base) px = base[at];
+                else {
+                    const uint32_t v = pages[at];
+                    px = v * 0x010101u | 0xff000000u;
+                }
+                const uint32_t row = (uint32_t)(y - r0);
+                if (rect) {
+                    const uint32_t k = (X0 <= x && x <= X1 ? n_h[row] : 0) + (x == X0 ? n_v[row] : 0) + (x == X1 ? n_v[row] : 0);
+                    uint32_t p = px;
+                    for (uint32_t q = 0; q < k; q++) {
+                        const uint32_t nx = blend_rgba(p, 0x800000ffu);  // Rgba(255, 0, 0, 128)
+                        if (nx == p) break;
+                        p = nx;
+                    }
+                    rect[at] = p;
+                }
+                if (text) {
+                    uint32_t p = px;
+                    if (glyphs_here)
+                        if (const uint32_t w = win[row * VERIFY_TILE_W + t]) {
+                            const VerifyRec r = recs[w - 1];
+                            const uint32_t v = bitmaps[r.src + (uint32_t)(y - r.y0) * r.stride + (uint32_t)(x - r.x0)];
+                            if (v) p = blend_rgba(p, 0x80000000u | (255 - v));  // canvas_to_lum8: l = 255 - v, blended where l != 255
+                        }
+                    text[at] = p;
+                }
+            }
+        __syncthreads();
+    }
+}
+
 }  // namespace focr_dec
 
 using namespace focr_dec;
@@ -414,6 +569,18 @@ struct focr_decoder {
     size_t rgb_cap = 0;
     float last_verify_ms = 0.f;
     uint32_t last_verify_launches = 0;
+    // test images: buffers of their own, so that a test call leaves the last run and its verify as they were
+    hipEvent_t ev4 = nullptr, ev5 = nullptr;
+    uint8_t *d_tpages = nullptr;
+    size_t tpages_cap = 0;
+    uint32_t *d_tbase = nullptr, *d_trect = nullptr, *d_ttext = nullptr, *d_tflags = nullptr;
+    size_t tbase_cap = 0, trect_cap = 0, ttext_cap = 0, tflags_cap = 0;
+    VerifyRec *d_trecs = nullptr;
+    size_t trecs_cap = 0;
+    VerifyLine *d_tline = nullptr;
+    size_t tline_cap = 0;
+    float last_test_ms = 0.f;
+    uint32_t last_test_launches = 0;
 };
 
 namespace {
@@ -441,6 +608,25 @@ int grow(focr_decoder *dec, T **p, size_t *cap, size_t want) {
     DEC_CHECK(hipMalloc((void **)p, want * sizeof(T)));
     *cap = want;
     return 0;
+}
+
+// The line slots of a batch as the reference's loop visits them, with image::crop_imm's clamping of every crop.  False
+// for line_advance 0 with a non-empty first crop (the reference never ends).
+bool slot_geometry(size_t page_w, size_t page_h, uint32_t x_start, uint32_t y_start, uint32_t width, uint32_t line_height,
+                   uint32_t line_advance, Geometry *out) {
+    Geometry g{};
+    g.page_w = (uint32_t)page_w;
+    g.page_h = (uint32_t)page_h;
+    g.x = std::min<uint32_t>(x_start, g.page_w);  // image::crop_imm's clamping
+    g.w = std::min<uint32_t>(width, g.page_w - g.x);
+    g.y_start = y_start;
+    g.line_height = line_height;
+    g.line_advance = line_advance;
+    if (line_height == 0 || y_start >= g.page_h) g.n_slots = 0;  // the first crop is empty: the loop ends at once
+    else if (line_advance == 0) return false;
+    else g.n_slots = (uint32_t)(((uint64_t)g.page_h - y_start + line_advance - 1) / line_advance);
+    *out = g;
+    return true;
 }
 
 // What focr_decoder_verify draws from: the successful run's geometry and its pages on the device.
@@ -481,7 +667,8 @@ extern "C" int focr_decoder_create(int device, focr_decoder_t **out) {
     dec = new focr_decoder;
     dec->device = device;
     if (hipStreamCreateWithFlags(&dec->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&dec->ev0) != hipSuccess ||
-        hipEventCreate(&dec->ev1) != hipSuccess || hipEventCreate(&dec->ev2) != hipSuccess || hipEventCreate(&dec->ev3) != hipSuccess) {
+        hipEventCreate(&dec->ev1) != hipSuccess || hipEventCreate(&dec->ev2) != hipSuccess || hipEventCreate(&dec->ev3) != hipSuccess ||
+        hipEventCreate(&dec->ev4) != hipSuccess || hipEventCreate(&dec->ev5) != hipSuccess) {
         focr_decoder_destroy(dec);
         return dfail(nullptr, "focr_decoder_create: stream / event creation failed");
     }
@@ -496,9 +683,10 @@ extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
     for (void *p : {(void *)dec->d_glyphs, (void *)dec->d_offs, (void *)dec->d_bitmaps, (void *)dec->d_pages, (void *)dec->d_strips,
                     (void *)dec->d_flags, (void *)dec->d_work, (void *)dec->d_nchars, (void *)dec->d_count, (void *)dec->d_chars,
                     (void *)dec->d_vglyphs, (void *)dec->d_vphases, (void *)dec->d_vlines, (void *)dec->d_vrecs, (void *)dec->d_sums,
-                    (void *)dec->d_rgb})
+                    (void *)dec->d_rgb, (void *)dec->d_tpages, (void *)dec->d_tbase, (void *)dec->d_trect, (void *)dec->d_ttext,
+                    (void *)dec->d_tflags, (void *)dec->d_trecs, (void *)dec->d_tline})
         if (p) (void)hipFree(p);
-    for (hipEvent_t e : {dec->ev0, dec->ev1, dec->ev2, dec->ev3})
+    for (hipEvent_t e : {dec->ev0, dec->ev1, dec->ev2, dec->ev3, dec->ev4, dec->ev5})
         if (e) (void)hipEventDestroy(e);
     if (dec->stream) (void)hipStreamDestroy(dec->stream);
     delete dec;
@@ -562,16 +750,8 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     if (n_pages && !pages) return dfail(dec, "focr_decoder_run: null pages");
     if (page_w > 0xffffu * 16 || page_h > 0xffffu * 16) return dfail(dec, "focr_decoder_run: page too large");
     Geometry g{};
-    g.page_w = (uint32_t)page_w;
-    g.page_h = (uint32_t)page_h;
-    g.x = std::min<uint32_t>(x_start, g.page_w);  // image::crop_imm's clamping
-    g.w = std::min<uint32_t>(width, g.page_w - g.x);
-    g.y_start = y_start;
-    g.line_height = line_height;
-    g.line_advance = line_advance;
-    if (line_height == 0 || y_start >= g.page_h) g.n_slots = 0;  // the first crop is empty: the loop ends at once
-    else if (line_advance == 0) return dfail(dec, "focr_decoder_run: line_advance 0 (the reference never ends)");
-    else g.n_slots = (uint32_t)(((uint64_t)g.page_h - y_start + line_advance - 1) / line_advance);
+    if (!slot_geometry(page_w, page_h, x_start, y_start, width, line_height, line_advance, &g))
+        return dfail(dec, "focr_decoder_run: line_advance 0 (the reference never ends)");
     const uint64_t total = (uint64_t)n_pages * g.n_slots;
     if (total == 0) return keep_run(dec, g, pages, on_device, n_pages, x_start);  // nothing to decode; a verify still draws the pages
     if (total > (1u << 30)) return dfail(dec, "focr_decoder_run: too many lines in one batch");
@@ -754,3 +934,106 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
 
 extern "C" float focr_decoder_last_verify_ms(const focr_decoder_t *dec) { return dec ? dec->last_verify_ms : 0.f; }
 extern "C" uint32_t focr_decoder_last_verify_launches(const focr_decoder_t *dec) { return dec ? dec->last_verify_launches : 0; }
+
+extern "C" int focr_decoder_test_images(focr_decoder_t *dec, const uint8_t *pages, const uint8_t *base_rgba, int in_on_device, size_t n_pages,
+                                        size_t page_w, size_t page_h, uint32_t x_start, uint32_t y_start, uint32_t width,
+                                        uint32_t line_height, uint32_t line_advance, uint8_t *rect_rgba, uint8_t *text_rgba,
+                                        int out_on_device) {
+    if (!dec) return dfail(nullptr, "focr_decoder_test_images: null decoder");
+    dec->last_test_ms = 0.f;
+    dec->last_test_launches = 0;
+    if (n_pages && !pages) return dfail(dec, "focr_decoder_test_images: null pages");
+    if (text_rgba && !dec->n_glyphs) return dfail(dec, "focr_decoder_test_images: the text image needs a decode font (focr_decoder_set_font)");
+    if (text_rgba && !dec->n_vglyphs)
+        return dfail(dec, "focr_decoder_test_images: the text image needs a verify table (focr_decoder_set_verify_font)");
+    if (page_w > 0xffffu * 16 || page_h > 0xffffu * 16) return dfail(dec, "focr_decoder_test_images: page too large");
+    Geometry g{};
+    if (!slot_geometry(page_w, page_h, x_start, y_start, width, line_height, line_advance, &g))
+        return dfail(dec, "focr_decoder_test_images: line_advance 0 (the reference never ends)");
+    const uint64_t total = (uint64_t)n_pages * g.n_slots;
+    if (total > (1u << 30)) return dfail(dec, "focr_decoder_test_images: too many lines in one batch");
+    g.total = (uint32_t)total;
+    for (const void *p : {in_on_device ? (const void *)base_rgba : nullptr, out_on_device ? (const void *)rect_rgba : nullptr,
+                          out_on_device ? (const void *)text_rgba : nullptr})
+        if ((uintptr_t)p % 4) return dfail(dec, "focr_decoder_test_images: device RGBA buffers must be 4-byte aligned");
+    const size_t W = page_w, H = page_h, px = n_pages * W * H;
+    if (px == 0 || (!rect_rgba && !text_rgba)) return 0;
+    const size_t tiles_x = (W + VERIFY_TILE_W - 1) / VERIFY_TILE_W, tiles_y = (H + VERIFY_TILE_H - 1) / VERIFY_TILE_H;
+    const size_t n_tiles = n_pages * tiles_x * tiles_y;
+    DEC_CHECK(hipSetDevice(dec->device));
+    const uint8_t *d_src = pages;
+    const uint32_t *d_base = (const uint32_t *)base_rgba;
+    if (!in_on_device) {
+        if (grow(dec, &dec->d_tpages, &dec->tpages_cap, px)) return 1;
+        DEC_CHECK(hipMemcpyAsync(dec->d_tpages, pages, px, hipMemcpyHostToDevice, dec->stream));
+        d_src = dec->d_tpages;
+        if (base_rgba) {
+            if (grow(dec, &dec->d_tbase, &dec->tbase_cap, px)) return 1;
+            DEC_CHECK(hipMemcpyAsync(dec->d_tbase, base_rgba, px * 4, hipMemcpyHostToDevice, dec->stream));
+            d_base = dec->d_tbase;
+        }
+    }
+    uint32_t *d_rect = (uint32_t *)rect_rgba, *d_text = (uint32_t *)text_rgba;
+    if (!out_on_device) {
+        if (rect_rgba && grow(dec, &dec->d_trect, &dec->trect_cap, px)) return 1;
+        if (text_rgba && grow(dec, &dec->d_ttext, &dec->ttext_cap, px)) return 1;
+        d_rect = rect_rgba ? dec->d_trect : nullptr;
+        d_text = text_rgba ? dec->d_ttext : nullptr;
+    }
+    if (rect_rgba && grow(dec, &dec->d_tflags, &dec->tflags_cap, std::max<size_t>(total, 1))) return 1;
+    if (text_rgba) {
+        if (grow(dec, &dec->d_trecs, &dec->trecs_cap, dec->n_glyphs)) return 1;
+        if (grow(dec, &dec->d_tline, &dec->tline_cap, 1)) return 1;
+    }
+    uint32_t launches = 0;
+    DEC_CHECK(hipEventRecord(dec->ev4, dec->stream));
+    if (rect_rgba) {
+        test_flags_kernel<<<std::max<uint32_t>(g.total, 1), TEST_THREADS, 0, dec->stream>>>(d_src, g, dec->d_tflags);
+        DEC_CHECK(hipGetLastError());
+        launches++;
+    }
+    if (text_rgba) {
+        test_layout_kernel<<<1, 64, 0, dec->stream>>>(g, dec->n_glyphs, dec->d_glyphs, dec->d_vglyphs, dec->d_vphases, dec->d_trecs, dec->d_tline);
+        DEC_CHECK(hipGetLastError());
+        launches++;
+    }
+    test_compose_kernel<<<(uint32_t)std::min<size_t>(n_tiles, VERIFY_MAX_GRID), VERIFY_TILE_W, 0, dec->stream>>>(
+        d_src, d_base, g, (uint32_t)n_pages, x_start, width, (uint32_t)tiles_x, (uint32_t)tiles_y, dec->d_tflags, dec->d_tline, dec->d_trecs,
+        (const uint8_t *)dec->d_bitmaps, d_rect, d_text);
+    DEC_CHECK(hipGetLastError());
+    launches++;
+    DEC_CHECK(hipEventRecord(dec->ev5, dec->stream));
+    if (!out_on_device) {
+        if (rect_rgba) DEC_CHECK(hipMemcpyAsync(rect_rgba, d_rect, px * 4, hipMemcpyDeviceToHost, dec->stream));
+        if (text_rgba) DEC_CHECK(hipMemcpyAsync(text_rgba, d_text, px * 4, hipMemcpyDeviceToHost, dec->stream));
+    }
+    DEC_CHECK(hipStreamSynchronize(dec->stream));
+    DEC_CHECK(hipEventElapsedTime(&dec->last_test_ms, dec->ev4, dec->ev5));
+    dec->last_test_launches = launches;
+    return 0;
+}
+
+extern "C" float focr_decoder_last_test_ms(const focr_decoder_t *dec) { return dec ? dec->last_test_ms : 0.f; }
+extern "C" uint32_t focr_decoder_last_test_launches(const focr_decoder_t *dec) { return dec ? dec->last_test_launches : 0; }
+
+extern "C" int focr_decoder_debug_blend(focr_decoder_t *dec, const uint8_t *bg_rgba, const uint8_t *fg_rgba, size_t n, uint8_t *out_rgba) {
+    if (!dec) return dfail(nullptr, "focr_decoder_debug_blend: null decoder");
+    if (n && (!bg_rgba || !fg_rgba || !out_rgba)) return dfail(dec, "focr_decoder_debug_blend: null buffer");
+    if (!n) return 0;
+    DEC_CHECK(hipSetDevice(dec->device));
+    uint32_t *d = nullptr;
+    DEC_CHECK(hipMalloc((void **)&d, n * 12));
+    hipError_t e = hipMemcpyAsync(d, bg_rgba, n * 4, hipMemcpyHostToDevice, dec->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + n, fg_rgba, n * 4, hipMemcpyHostToDevice, dec->stream);
+    if (e == hipSuccess) {
+        debug_blend_kernel<<<(uint32_t)std::min<size_t>((n + TEST_THREADS - 1) / TEST_THREADS, 1u << 16), TEST_THREADS, 0, dec->stream>>>(d, d + n, n,
+                                                                                                                                       d + 2 * n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, d + 2 * n, n * 4, hipMemcpyDeviceToHost, dec->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dec->stream);
+    (void)hipStreamSynchronize(dec->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) return dfail(dec, std::string("focr_decoder_debug_blend: ") + hipGetErrorString(e));
+    return 0;
+}

@@ -1,5 +1,5 @@
 // host.cpp — CPU-side host utilities of the ncc path (libfocr_host.so):
-// bank files, image decode (image::open(..).into_luma8(), src/ncc.rs:575),
+// bank files, image decode (image::open(..).into_luma8(), src/ncc.rs:575, and into_rgba8 for focr --test),
 // synthetic pages and Rust-compatible float printing
 // for the --csv / --raw formats (src/ncc.rs:685-697, 855-864).
 #include <algorithm>
@@ -44,6 +44,26 @@ bool read_file(const char *path, std::vector<uint8_t> &buf) {
     return got == (size_t)n;
 }
 
+// What an image decodes into: start(W, H) once (false when out of memory), then one put_gray or put_rgb per pixel with
+// the 8-bit samples and alpha.  into_luma8 takes grey as it is and rgb_to_luma of colour; into_rgba8 spreads grey.
+struct LumaSink {
+    uint8_t *px = nullptr;
+    bool start(size_t w, size_t h) { return (px = (uint8_t *)malloc(w * h)) != nullptr; }
+    void put_gray(size_t i, uint32_t v, uint32_t a) { px[i] = (uint8_t)v; }
+    void put_rgb(size_t i, uint32_t r, uint32_t g, uint32_t b, uint32_t a) { px[i] = rgb_to_luma(r, g, b); }
+    void drop() { free(px), px = nullptr; }
+};
+
+struct RgbaSink {
+    uint8_t *px = nullptr;
+    bool start(size_t w, size_t h) { return (px = (uint8_t *)malloc(w * h * 4)) != nullptr; }
+    void put_gray(size_t i, uint32_t v, uint32_t a) { put_rgb(i, v, v, v, a); }
+    void put_rgb(size_t i, uint32_t r, uint32_t g, uint32_t b, uint32_t a) {
+        px[i * 4] = (uint8_t)r, px[i * 4 + 1] = (uint8_t)g, px[i * 4 + 2] = (uint8_t)b, px[i * 4 + 3] = (uint8_t)a;
+    }
+    void drop() { free(px), px = nullptr; }
+};
+
 // ---- PNM ---------------------------------------------------------------
 struct PnmTok {
     const uint8_t *p, *e;
@@ -68,7 +88,8 @@ struct PnmTok {
     }
 };
 
-int load_pnm(const std::vector<uint8_t> &d, uint8_t **px, size_t *w, size_t *h, char *err, size_t errlen) {
+template <class Sink>
+int load_pnm(const std::vector<uint8_t> &d, Sink &out, size_t *w, size_t *h, char *err, size_t errlen) {
     int kind = d[1] - '0';
     PnmTok t{d.data() + 2, d.data() + d.size()};
     uint32_t W, H, maxv = 1;
@@ -76,9 +97,9 @@ int load_pnm(const std::vector<uint8_t> &d, uint8_t **px, size_t *w, size_t *h, 
     if (kind != 1 && kind != 4 && !t.next_uint(&maxv)) return fail(err, errlen, "pnm: bad maxval");
     if (W == 0 || H == 0 || maxv == 0 || maxv > 65535) return fail(err, errlen, "pnm: bad dimensions");
     size_t npx = (size_t)W * H;
-    uint8_t *out = (uint8_t *)malloc(npx);
-    if (!out) return fail(err, errlen, "out of memory");
+    if (!out.start(W, H)) return fail(err, errlen, "out of memory");
     const int ch = (kind == 3 || kind == 6) ? 3 : 1;
+    auto put = [&](size_t i, const uint32_t *c) { ch == 3 ? out.put_rgb(i, c[0], c[1], c[2], 255) : out.put_gray(i, c[0], 255); };
     auto conv = [&](uint32_t v) -> uint32_t { return maxv > 255 ? u16_to_u8((uint32_t)((uint64_t)v * 65535 / maxv)) : v; };
     if (kind == 1 || kind == 2 || kind == 3) {  // ASCII
         for (size_t i = 0; i < npx; i++) {
@@ -86,46 +107,44 @@ int load_pnm(const std::vector<uint8_t> &d, uint8_t **px, size_t *w, size_t *h, 
             for (int k = 0; k < ch; k++) {
                 if (kind == 1) {  // bits may be unseparated
                     while (t.p < t.e && (isspace(*t.p))) t.p++;
-                    if (t.p >= t.e) { free(out); return fail(err, errlen, "pnm: truncated"); }
+                    if (t.p >= t.e) { out.drop(); return fail(err, errlen, "pnm: truncated"); }
                     c[k] = (*t.p++ == '1') ? 0 : 255;
                 } else {
-                    if (!t.next_uint(&c[k])) { free(out); return fail(err, errlen, "pnm: truncated"); }
+                    if (!t.next_uint(&c[k])) { out.drop(); return fail(err, errlen, "pnm: truncated"); }
                     c[k] = conv(c[k]);
                 }
             }
-            out[i] = ch == 3 ? rgb_to_luma(c[0], c[1], c[2]) : (uint8_t)c[0];
+            put(i, c);
         }
     } else {
-        if (t.p >= t.e) { free(out); return fail(err, errlen, "pnm: truncated"); }
+        if (t.p >= t.e) { out.drop(); return fail(err, errlen, "pnm: truncated"); }
         t.p++;  // single whitespace after the header
         const uint8_t *s = t.p;
         size_t avail = (size_t)(t.e - t.p);
         if (kind == 4) {
             size_t stride = (W + 7) / 8;
-            if (avail < stride * H) { free(out); return fail(err, errlen, "pnm: truncated"); }
+            if (avail < stride * H) { out.drop(); return fail(err, errlen, "pnm: truncated"); }
             for (size_t y = 0; y < H; y++)
-                for (size_t x = 0; x < W; x++)
-                    out[y * W + x] = ((s[y * stride + x / 8] >> (7 - x % 8)) & 1) ? 0 : 255;
+                for (size_t x = 0; x < W; x++) out.put_gray(y * W + x, ((s[y * stride + x / 8] >> (7 - x % 8)) & 1) ? 0 : 255, 255);
         } else {
             size_t bps = maxv > 255 ? 2 : 1;
-            if (avail < npx * ch * bps) { free(out); return fail(err, errlen, "pnm: truncated"); }
+            if (avail < npx * ch * bps) { out.drop(); return fail(err, errlen, "pnm: truncated"); }
             for (size_t i = 0; i < npx; i++) {
                 uint32_t c[3] = {0, 0, 0};
                 for (int k = 0; k < ch; k++) {
                     const uint8_t *q = s + (i * ch + k) * bps;
                     c[k] = conv(bps == 2 ? ((uint32_t)q[0] << 8 | q[1]) : q[0]);
                 }
-                out[i] = ch == 3 ? rgb_to_luma(c[0], c[1], c[2]) : (uint8_t)c[0];
+                put(i, c);
             }
         }
     }
-    *px = out;
     *w = W;
     *h = H;
     return 0;
 }
 
-// ---- PNG (non-interlaced and Adam7; gray/rgb/palette, 1-16 bit) ----------
+// ---- PNG (non-interlaced and Adam7; gray/rgb/palette, 1-16 bit; tRNS as the png crate's EXPAND) -------------
 inline uint32_t be32(const uint8_t *p) { return (uint32_t)p[0] << 24 | p[1] << 16 | p[2] << 8 | p[3]; }
 
 inline int paeth(int a, int b, int c) {
@@ -159,11 +178,12 @@ bool unfilter(uint8_t *data, size_t rows, size_t rowbytes, size_t bpp) {
     return true;
 }
 
-int load_png(const std::vector<uint8_t> &d, uint8_t **px, size_t *w, size_t *h, char *err, size_t errlen) {
+template <class Sink>
+int load_png(const std::vector<uint8_t> &d, Sink &out, size_t *w, size_t *h, char *err, size_t errlen) {
     size_t pos = 8;
     uint32_t W = 0, H = 0;
     int depth = 0, ctype = 0, interlace = 0;
-    std::vector<uint8_t> idat, plte;
+    std::vector<uint8_t> idat, plte, trns;
     bool have_ihdr = false;
     while (pos + 12 <= d.size()) {
         uint32_t len = be32(&d[pos]);
@@ -179,6 +199,8 @@ int load_png(const std::vector<uint8_t> &d, uint8_t **px, size_t *w, size_t *h, 
             have_ihdr = true;
         } else if (!memcmp(type, "PLTE", 4)) {
             plte.assign(body, body + len);
+        } else if (!memcmp(type, "tRNS", 4)) {
+            trns.assign(body, body + len);
         } else if (!memcmp(type, "IDAT", 4)) {
             idat.insert(idat.end(), body, body + len);
         } else if (!memcmp(type, "IEND", 4)) {
@@ -224,41 +246,50 @@ int load_png(const std::vector<uint8_t> &d, uint8_t **px, size_t *w, size_t *h, 
     inflateEnd(&zs);
     if ((zr != Z_STREAM_END && zr != Z_OK && zr != Z_BUF_ERROR) || produced < total) return fail(err, errlen, "png: inflate failed");
 
-    size_t npx = (size_t)W * H;
-    uint8_t *out = (uint8_t *)malloc(npx);
-    if (!out) return fail(err, errlen, "out of memory");
+    // tRNS: alpha per palette entry (255 past the list), or the grey / RGB key whose pixels are transparent, compared in
+    // the file's samples (the key's low byte below 16 bits); ignored for colour types with an alpha channel
+    int n_key = 0;
+    uint32_t key[3] = {0, 0, 0};
+    if ((ctype == 0 && trns.size() >= 2) || (ctype == 2 && trns.size() >= 6)) {
+        n_key = ctype == 0 ? 1 : 3;
+        for (int k = 0; k < n_key; k++) key[k] = depth == 16 ? (uint32_t)trns[2 * k] << 8 | trns[2 * k + 1] : trns[2 * k + 1];
+    }
+    if (!out.start(W, H)) return fail(err, errlen, "out of memory");
     size_t off = 0;
     for (auto &p : passes) {
         size_t pw = W > p.x0 ? (W - p.x0 + p.dx - 1) / p.dx : 0, ph = H > p.y0 ? (H - p.y0 + p.dy - 1) / p.dy : 0;
         if (!pw || !ph) continue;
         size_t rowbytes = (pw * bits_pp + 7) / 8;
-        if (!unfilter(raw.data() + off, ph, rowbytes, bpp)) { free(out); return fail(err, errlen, "png: bad filter"); }
+        if (!unfilter(raw.data() + off, ph, rowbytes, bpp)) { out.drop(); return fail(err, errlen, "png: bad filter"); }
         for (size_t y = 0; y < ph; y++) {
             const uint8_t *line = raw.data() + off + y * (rowbytes + 1) + 1;
             for (size_t x = 0; x < pw; x++) {
-                uint32_t c[4] = {0, 0, 0, 0};
+                uint32_t c[4] = {0, 0, 0, 0}, raw_c[4] = {0, 0, 0, 0};
                 for (int k = 0; k < channels; k++) {
-                    if (depth == 8) c[k] = line[x * channels + k];
-                    else if (depth == 16) c[k] = u16_to_u8((uint32_t)line[(x * channels + k) * 2] << 8 | line[(x * channels + k) * 2 + 1]);
-                    else {
+                    if (depth == 8) c[k] = raw_c[k] = line[x * channels + k];
+                    else if (depth == 16) {
+                        raw_c[k] = (uint32_t)line[(x * channels + k) * 2] << 8 | line[(x * channels + k) * 2 + 1];
+                        c[k] = u16_to_u8(raw_c[k]);
+                    } else {
                         size_t bit = x * depth;
-                        uint32_t v = (line[bit / 8] >> (8 - depth - bit % 8)) & ((1u << depth) - 1);
+                        uint32_t v = raw_c[k] = (line[bit / 8] >> (8 - depth - bit % 8)) & ((1u << depth) - 1);
                         c[k] = ctype == 3 ? v : v * 255 / ((1u << depth) - 1);
                     }
                 }
-                uint8_t l;
+                const size_t i = (p.y0 + y * p.dy) * W + (p.x0 + x * p.dx);
+                uint32_t a = ctype == 4 ? c[1] : ctype == 6 ? c[3] : 255;
+                if (n_key && raw_c[0] == key[0] && (n_key == 1 || (raw_c[1] == key[1] && raw_c[2] == key[2]))) a = 0;
                 if (ctype == 3) {
                     size_t idx = c[0];
-                    if (idx * 3 + 2 < plte.size()) l = rgb_to_luma(plte[idx * 3], plte[idx * 3 + 1], plte[idx * 3 + 2]);
-                    else l = 0;
-                } else if (ctype == 2 || ctype == 6) l = rgb_to_luma(c[0], c[1], c[2]);
-                else l = (uint8_t)c[0];
-                out[(p.y0 + y * p.dy) * W + (p.x0 + x * p.dx)] = l;
+                    a = idx < trns.size() ? trns[idx] : 255;
+                    if (idx * 3 + 2 < plte.size()) out.put_rgb(i, plte[idx * 3], plte[idx * 3 + 1], plte[idx * 3 + 2], a);
+                    else out.put_rgb(i, 0, 0, 0, a);
+                } else if (ctype == 2 || ctype == 6) out.put_rgb(i, c[0], c[1], c[2], a);
+                else out.put_gray(i, c[0], a);
             }
         }
         off += ph * (rowbytes + 1);
     }
-    *px = out;
     *w = W;
     *h = H;
     return 0;
@@ -335,13 +366,36 @@ int focr_bank_load(const char *path, focr_bank_t *out) {
     return ok ? 0 : 1;
 }
 
-int focr_image_load_luma8(const char *path, uint8_t **px, size_t *w, size_t *h, char *err, size_t errlen) {
+}  // extern "C"
+
+namespace {
+
+template <class Sink>
+int load_image(const char *path, Sink &out, size_t *w, size_t *h, char *err, size_t errlen) {
     std::vector<uint8_t> d;
     if (!read_file(path, d)) return fail(err, errlen, std::string("cannot read ") + path);
     static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
-    if (d.size() >= 8 && !memcmp(d.data(), png_sig, 8)) return load_png(d, px, w, h, err, errlen);
-    if (d.size() >= 3 && d[0] == 'P' && d[1] >= '1' && d[1] <= '6') return load_pnm(d, px, w, h, err, errlen);
+    if (d.size() >= 8 && !memcmp(d.data(), png_sig, 8)) return load_png(d, out, w, h, err, errlen);
+    if (d.size() >= 3 && d[0] == 'P' && d[1] >= '1' && d[1] <= '6') return load_pnm(d, out, w, h, err, errlen);
     return fail(err, errlen, "unsupported image format (pnm and png only, Cargo.toml:10)");
+}
+
+}  // namespace
+
+extern "C" {
+
+int focr_image_load_luma8(const char *path, uint8_t **px, size_t *w, size_t *h, char *err, size_t errlen) {
+    LumaSink out;
+    if (int rc = load_image(path, out, w, h, err, errlen)) return rc;
+    *px = out.px;
+    return 0;
+}
+
+int focr_image_load_rgba8(const char *path, uint8_t **px, size_t *w, size_t *h, char *err, size_t errlen) {
+    RgbaSink out;
+    if (int rc = load_image(path, out, w, h, err, errlen)) return rc;
+    *px = out.px;
+    return 0;
 }
 
 // Size of an image from the first bytes of its file (PNM header / PNG IHDR); 0 on success.

@@ -6,6 +6,8 @@
         # [[(y, text), ...] per page]
         pages, mse, images = dec.decode(luma_pages, 45, 39, 608, 12, 15, verify="image")
         # focr --verify on the device: red = the page's ink, blue = the decoded text re-rendered; MSE per page
+        rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
+        # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
 There is no CPU path: the decoder needs a device, and says so when it has none.
 """
@@ -158,6 +160,7 @@ class LineDecoder:
         self.font = None
         self.last_ms = 0.0
         self.last_verify_ms = 0.0
+        self.last_test_ms = 0.0
         self._vfont = None
         self._batch = None  # (n_pages, page_h, page_w) of the last run
 
@@ -179,11 +182,7 @@ class LineDecoder:
         this library uses with room for N * H * W * 3 bytes.  The verify table is built on first use."""
         if self._batch is None:
             raise DecoderError("verify: no decode since the font was set")
-        if self._vfont is None:
-            f = self.font
-            vf = VerifyFont(f.font_path, f.text_size, f.alphabet, f.hinting, f.kerning)
-            self._check(self._lib.focr_decoder_set_verify_font(self._h, C.byref(vf.s)))
-            self._vfont = vf
+        self._ensure_verify_font()
         n, h, w = self._batch
         sums = np.zeros(max(1, n), dtype=np.uint64)
         out = np.empty((n, h, w, 3), dtype=np.uint8) if images and rgb_device is None else None
@@ -194,6 +193,81 @@ class LineDecoder:
         self._check(self._lib.focr_decoder_verify(self._h, rgb, on_device, sums.ctypes.data))
         self.last_verify_ms = float(self._lib.focr_decoder_last_verify_ms(self._h))
         return sums[:n], out
+
+    def _ensure_verify_font(self):
+        if self._vfont is None:
+            f = self.font
+            vf = VerifyFont(f.font_path, f.text_size, f.alphabet, f.hinting, f.kerning)
+            self._check(self._lib.focr_decoder_set_verify_font(self._h, C.byref(vf.s)))
+            self._vfont = vf
+
+    def test_images(self, luma_pages, x, y, width, line_height, line_advance, rgba=None, rect=True, text=True):
+        """focr --test on the device: (rect_images, text_images), each a per-page list of (H, W, 4) uint8 RGBA images,
+        or None where that image was not asked for.  rect draws the box of every non-blank line slot, text the whole
+        alphabet rendered at the top-left corner, both blended in red over the page: over rgba (per page (H, W, 4)
+        uint8, in the layout of luma_pages) when given, else over the grey page.  luma_pages as for decode(); pages are
+        grouped by size.  The text image needs set_font(); its verify table is built on first use.  The last decode
+        and its verify are left as they were."""
+        if text and self.font is None:
+            raise DecoderError("set_font() first")
+        geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
+        if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
+            pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
+        else:
+            pages = list(luma_pages)
+        if rgba is not None:
+            if isinstance(rgba, np.ndarray) and rgba.ndim == 3:
+                rgba = [rgba]
+            rgba = list(rgba)
+            if len(rgba) != len(pages) or any(np.asarray(c).shape != np.asarray(p).shape + (4,) for c, p in zip(rgba, pages)):
+                raise ValueError("rgba must hold one (H, W, 4) image per page, of its page's size")
+        if text:
+            self._ensure_verify_font()
+        rects = [None] * len(pages) if rect else None
+        texts = [None] * len(pages) if text else None
+        by_size = {}
+        for i, p in enumerate(pages):
+            by_size.setdefault(np.asarray(p).shape, []).append(i)
+        for (h, w), idx in by_size.items():
+            batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
+            base = None if rgba is None else np.ascontiguousarray(np.stack([np.asarray(rgba[i], dtype=np.uint8) for i in idx]))
+            r_out = np.empty((len(idx), h, w, 4), dtype=np.uint8) if rect else None
+            t_out = np.empty((len(idx), h, w, 4), dtype=np.uint8) if text else None
+            ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
+            self._check(self._lib.focr_decoder_test_images(self._h, ptr(batch), ptr(base), 0, len(idx), w, h, *geo, ptr(r_out),
+                                                           ptr(t_out), 0))
+            self.last_test_ms = float(self._lib.focr_decoder_last_test_ms(self._h))
+            for j, i in enumerate(idx):
+                if rect:
+                    rects[i] = r_out[j]
+                if text:
+                    texts[i] = t_out[j]
+        return rects, texts
+
+    def test_images_device(self, pages_ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, rgba_ptr=None,
+                           rect_ptr=None, text_ptr=None):
+        """As test_images(), all in device memory of the decoder's device (addresses of the HIP runtime this library
+        uses): n_pages luma pages at pages_ptr, their RGBA base at rgba_ptr (or None for grey), and the images written
+        to rect_ptr / text_ptr (n_pages * page_h * page_w * 4 bytes each, 4-byte aligned; None: not drawn)."""
+        if text_ptr is not None:
+            if self.font is None:
+                raise DecoderError("set_font() first")
+            self._ensure_verify_font()
+        p = lambda a: C.c_void_p(int(a)) if a is not None else None  # noqa: E731
+        self._check(self._lib.focr_decoder_test_images(self._h, p(pages_ptr), p(rgba_ptr), 1, int(n_pages), int(page_w),
+                                                       int(page_h), int(x), int(y), int(width), int(line_height),
+                                                       int(line_advance), p(rect_ptr), p(text_ptr), 1))
+        self.last_test_ms = float(self._lib.focr_decoder_last_test_ms(self._h))
+
+    def debug_blend(self, bg, fg):
+        """The device's blend (image's Blend for Rgba<u8>, as test_images draws with) of fg onto bg: (N, 4) uint8 each."""
+        bg = np.ascontiguousarray(bg, dtype=np.uint8).reshape(-1, 4)
+        fg = np.ascontiguousarray(fg, dtype=np.uint8).reshape(-1, 4)
+        if bg.shape != fg.shape:
+            raise ValueError("bg and fg must have the same shape")
+        out = np.empty_like(bg)
+        self._check(self._lib.focr_decoder_debug_blend(self._h, bg.ctypes.data, fg.ctypes.data, len(bg), out.ctypes.data))
+        return out
 
     def _verified(self, verify, h, w):
         """(mse per page as f32, images or None) of the last run, for decode(verify=...)."""

@@ -10,7 +10,8 @@
  *
  * libfocr_raster.so : focr_raster_glyph, focr_glyph_metrics, focr_render_text, focr_decode_font_build/free,
  *                     focr_verify_font_build/free (FreeType)
- * libfocr_hip.so    : focr_decoder_* (gfx950), including the device verify of a run (--verify)
+ * libfocr_hip.so    : focr_decoder_* (gfx950), including the device verify of a run (--verify) and the test images
+ *                     (--test)
  */
 #ifndef FOCR_DECODE_H
 #define FOCR_DECODE_H
@@ -159,6 +160,35 @@ int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, ui
 /* Device time of the last verify's kernels in ms (events), and their launch count (constant per batch). */
 float focr_decoder_last_verify_ms(const focr_decoder_t *dec);
 uint32_t focr_decoder_last_verify_launches(const focr_decoder_t *dec);
+
+/* ---- device: test images (focr --test: draw_test_rectangles, draw_test_text, src/main.rs:241-298) ---------------- */
+
+/* focr --test's two images of each page of a batch of n_pages equal-size pages, drawn on the decoder's stream.  Both
+ * start from base_rgba (n_pages x page_h x page_w x 4 bytes, RGBA), or from (l, l, l, 255) of the luma pages when
+ * base_rgba is NULL (into_rgba8 of a grey image):
+ *   rect_rgba: for every line slot whose crop is not blank (the decoder's crop and blank test on the luma pages), the
+ *              box x_start ..= x_start + width by y ..= y + line_height, each edge pixel blended once with
+ *              Rgba(255, 0, 0, 128) per edge through it (corners twice, shared rows of overlapping boxes more); pixels
+ *              outside the page are skipped (the reference panics there);
+ *   text_rgba: render() of the whole alphabet of the decode font at (0, 0), clipped to the page: where the canvas has
+ *              v != 0, the pixel is blended once with Rgba(255 - v, 0, 0, 128).
+ * The blend is image 0.25's Blend for Rgba<u8>, restated in f32 (parity unpinned).  A NULL output is not drawn.
+ * Inputs are in host memory, or in device memory of the decoder's device when in_on_device != 0; outputs likewise with
+ * out_on_device (n_pages x page_h x page_w x 4 bytes each); device RGBA buffers must be 4-byte aligned.  text_rgba
+ * needs a decode font and a verify table (focr_decoder_set_verify_font); rect_rgba needs neither.  line_advance == 0
+ * with a non-empty first crop is refused, as in focr_decoder_run.  Runs a fixed number of launches, in buffers of its
+ * own: the last run's results, timing and verify stay as they were.  Returns when the images are written. */
+int focr_decoder_test_images(focr_decoder_t *dec, const uint8_t *pages, const uint8_t *base_rgba, int in_on_device,
+                             size_t n_pages, size_t page_w, size_t page_h, uint32_t x_start, uint32_t y_start,
+                             uint32_t width, uint32_t line_height, uint32_t line_advance,
+                             uint8_t *rect_rgba, uint8_t *text_rgba, int out_on_device);
+/* Device time of the last test_images' kernels in ms (events), and their launch count (constant per batch: 3 with
+ * both images, one less without either). */
+float focr_decoder_last_test_ms(const focr_decoder_t *dec);
+uint32_t focr_decoder_last_test_launches(const focr_decoder_t *dec);
+/* Debug: out[i] = the device's blend of fg[i] onto bg[i], for n RGBA pixels in host memory (the function
+ * focr_decoder_test_images blends with). */
+int focr_decoder_debug_blend(focr_decoder_t *dec, const uint8_t *bg_rgba, const uint8_t *fg_rgba, size_t n, uint8_t *out_rgba);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,12 @@ int focr_bank_load(const char *path, focr_bank_t *out);
  * non-interlaced/interlaced 8/16-bit PNG.  *px is malloc'ed. */
 int focr_image_load_luma8(const char *path, uint8_t **px, size_t *w, size_t *h, char *err,
                           size_t errlen);
+/* The same files as image::open(..).into_rgba8() (focr --test): w x h x 4 bytes, RGBA.  Grey g is (g, g, g, 255), grey
+ * with alpha (g, g, g, a), RGB gets alpha 255, palette entries their colour; samples of 1/2/4/16 bits and PNM maxvals
+ * are scaled as for luma8.  tRNS as the png crate's EXPAND: palette entries take their alpha from the list (255 past its
+ * end); a grey or RGB pixel equal to the key in the file's samples gets alpha 0.  *px is malloc'ed. */
+int focr_image_load_rgba8(const char *path, uint8_t **px, size_t *w, size_t *h, char *err,
+                          size_t errlen);
 /* Width and height from the file's header alone (no decode). */
 int focr_image_probe(const char *path, size_t *w, size_t *h, char *err, size_t errlen);
 /* Decode into caller memory of `cap` bytes (e.g. one slot of a page-locked batch slab, focr_host_register): binary

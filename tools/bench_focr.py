@@ -10,6 +10,12 @@ With --verify, also focr --verify's images of the batch on the device (focr_deco
   verify_device_ms_per_batch  median device time of the verify's kernels
   verify_launches             their launch count
   verify_wall_ms              median host time of one verify call with the images read back to the host
+With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
+grey pages):
+  test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
+  test_launches               their launch count
+  test_wall_ms                median host time of one test_images call (upload, launches, both images read back)
+  test_write_gb_per_s         the RGBA bytes written per second of device time
 
 No reference number: the reference's Rust / font-kit build is not available to run beside it.  Kernel times per
 launch come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
@@ -52,6 +58,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--verify", action="store_true", help="also time the device verify of the batch")
+    ap.add_argument("--test-images", action="store_true", help="also time focr --test's images of the batch")
     a = ap.parse_args()
     pages = synth(a.pages, a.seed)
     geo = (45, 39, 608, 12, 15)
@@ -79,6 +86,16 @@ def main():
                 vwall.append((time.perf_counter() - t) * 1e3)
                 vdev.append(dec.last_verify_ms)
             vlaunches = int(dec._lib.focr_decoder_last_verify_launches(dec._h))
+        if a.test_images:
+            for _ in range(a.warmup):
+                dec.test_images(pages, *geo)
+            tdev, twall = [], []
+            for _ in range(a.steps):
+                t = time.perf_counter()
+                dec.test_images(pages, *geo)
+                twall.append((time.perf_counter() - t) * 1e3)
+                tdev.append(dec.last_test_ms)
+            tlaunches = int(dec._lib.focr_decoder_last_test_launches(dec._h))
     n_lines = sum(len(p) for p in out)
     n_chars = sum(len(t) for p in out for _, t in p)
     ms = float(np.median(dev))
@@ -93,6 +110,10 @@ def main():
     if a.verify:
         res.update({"verify_device_ms_per_batch": round(float(np.median(vdev)), 4), "verify_launches": vlaunches,
                     "verify_wall_ms": round(float(np.median(vwall)), 3)})
+    if a.test_images:
+        tms = float(np.median(tdev))
+        res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
+                    "test_write_gb_per_s": round(2 * a.pages * 608 * 720 * 4 / tms / 1e6, 1)})
     print(json.dumps(res))
 
 
