@@ -13,6 +13,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -128,11 +129,13 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--hinting") a.hinting = true;
         else if (k == "--threshold") a.threshold = num_f(need());
         else if (k == "--anchor-threshold") a.anchor_threshold = num_f(need());
-        else if (k == "--overlap") {
+        else if (k == "--overlap") {  // an i32 (src/ncc.rs:514): clap refuses what does not fit, negative values included
             std::string s = need();
             char *e = nullptr;
-            long r = strtol(s.c_str(), &e, 10);
+            long long r = strtoll(s.c_str(), &e, 10);  // saturates beyond 64 bits, which is outside the i32 range too
             if (!e || *e || s.empty()) usage_error("invalid value '" + s + "' for '--overlap <OVERLAP>'");
+            if (r > INT32_MAX) usage_error("invalid value '" + s + "' for '--overlap <OVERLAP>': number too large to fit in target type");
+            if (r < INT32_MIN) usage_error("invalid value '" + s + "' for '--overlap <OVERLAP>': number too small to fit in target type");
             a.overlap = (int)r;
         } else if (k == "-a" || k == "--alphabet") a.alphabet = need();
         else if (k == "--box-size") a.box_size = need();

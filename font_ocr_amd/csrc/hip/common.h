@@ -77,6 +77,16 @@ struct KeyFmt {
     __host__ __device__ uint64_t line(uint64_t k) const { return k >> (bt + bx); }  // (page << by) | y
 };
 
+// The batch's key format: the fewest bits that hold every template index, x, y and page of the batch.
+inline KeyFmt key_format(size_t n_templates, size_t r_w, size_t r_h, size_t n_pages) {
+    auto nbits = [](size_t n) {
+        uint32_t b = 1;
+        while (((size_t)1 << b) < n) b++;
+        return b;
+    };
+    return KeyFmt{nbits(n_templates), nbits(r_w), nbits(r_h), nbits(n_pages)};
+}
+
 // The BUCKETS of the row path of the tail (rows.hip).  A bucket is a page row cut into n_seg segments of
 // 2^seg_shift pixels (x >> seg_shift): one segment for narrow pages and small banks, more where a whole row would hold
 // more candidates than one wave sorts in LDS (BASELINE configs[2]: 1200-px rows x 1520 templates).  Buckets ascend with the
@@ -180,6 +190,7 @@ struct focr_ctx {
     int scan_mode = 0;
     int32_t post_overlap = 0;
     bool force_split = false;                   // tests: take scan_split without waiting for an overflow (focr_debug_force_split)
+    bool debug_hits = false;                    // tests: the hits came from focr_debug_process_hits, no per-call lists stand behind them
     int dbg_stats_form = 0;  // tests / A-B: 1 = the LDS-tiled statistics kernel for every class (focr_debug_set_stats_form; 0: the register form where it applies)
     uint32_t dbg_grid_num = 0, dbg_grid_den = 0;  // tests: the tail's persistent kernels on num / den times their workgroups (focr_debug_set_tail_grid; 0: as designed)
     int prefilter = 0;                          // FOCR_PREFILTER_*: auto / plane kernel / legacy kernel (focr_ctx_set_prefilter)

@@ -839,7 +839,7 @@ namespace focr {
 static int scan_now(focr_ctx *c) {
     const float threshold = c->scan_thr;
     const int mode = c->scan_mode;
-    c->scanned = c->processed = false;
+    c->scanned = c->processed = c->debug_hits = false;
     c->sizes_pending = c->post_pending = false;
     for (auto &m : c->ms) m = 0.f;
     c->counters[3] = 0;
@@ -978,12 +978,7 @@ int focr_scan(focr_ctx_t *c, float threshold, uint32_t cap, int mode) {
         macs += wx * wy * (uint64_t)sc.n_w * sc.n_h * sc.n_templates;
     }
     c->counters[2] = macs * c->n_pages;
-    auto nbits = [](size_t n) {
-        uint32_t b = 1;
-        while (((size_t)1 << b) < n) b++;
-        return b;
-    };
-    c->fmt = KeyFmt{nbits(c->n_templates), nbits(c->r_w), nbits(c->r_h), nbits(c->n_pages)};
+    c->fmt = key_format(c->n_templates, c->r_w, c->r_h, c->n_pages);
     // Size estimates are reused only for the very same setup (bank, batch geometry, threshold, cap, prefilter)
     uint32_t tb;
     memcpy(&tb, &threshold, 4);
@@ -1016,6 +1011,7 @@ int focr_ctx_set_size_estimates(focr_ctx_t *c, int on) {
 int focr_get_counts(focr_ctx_t *c, uint32_t *counts) {
     if (!c || !counts) return fail(c, FOCR_ERR_INVALID, "focr_get_counts: bad arguments");
     if (!c->scanned) return fail(c, FOCR_ERR_STATE, "focr_get_counts: no scan results");
+    if (c->debug_hits) return fail(c, FOCR_ERR_STATE, "focr_get_counts: the hits came from focr_debug_process_hits, not from a scan");
     if (int rc = finish_results(c)) return rc;
     FOCR_HIP(c, hipSetDevice(c->device));
     // (finished results are read back on io_stream: inside an executor the context's own stream already holds the lane's next batch)
@@ -1029,6 +1025,7 @@ size_t focr_total_matches(focr_ctx_t *c) { return (c && c->scanned && finish_res
 int focr_get_matches(focr_ctx_t *c, uint64_t *offsets, focr_match_t *matches) {
     if (!c) return FOCR_ERR_INVALID;
     if (!c->scanned) return fail(c, FOCR_ERR_STATE, "focr_get_matches: no scan results");
+    if (c->debug_hits) return fail(c, FOCR_ERR_STATE, "focr_get_matches: the hits came from focr_debug_process_hits, not from a scan");
     if (int rc = finish_results(c)) return rc;
     FOCR_HIP(c, hipSetDevice(c->device));
     if (offsets)

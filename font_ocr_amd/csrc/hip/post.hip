@@ -87,18 +87,25 @@ __global__ __launch_bounds__(256) void walk_lines(const uint64_t *__restrict__ k
         const uint32_t ord = valid ? ((uint32_t)total_key(sims[i]) ^ 0x80000000u) : 0u;  // unsigned order of total_cmp
         const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
         uint32_t pos = 0;  // wave-uniform cursor inside the chunk
+        int32_t opened_at = -1;  // lane of the element that opened the open group in this chunk; -1: the group was carried in
+        // Termination, for every overlap (INT32_MIN included): the opener of a group is always a member (partition_by puts the
+        // first element of a slice in it whatever the predicate says, src/ncc.rs:1040-1048), so a trip that opens a group at pos
+        // ends with stop > pos.  A trip that opens nothing is the chunk's first, with a carried group: it closes that group at
+        // stop >= pos or leaves the chunk.  So every trip but the first consumes an element or leaves: at most 65 trips a chunk.
         while (pos < 64) {
             if (!open) {
                 const uint64_t cand = vmask & (~0ull << pos);  // the next kept element opens a group
                 if (!cand) break;
                 pos = (uint32_t)__builtin_ctzll(cand);
                 anchor = __builtin_amdgcn_readlane(x, (int)pos);
+                opened_at = (int32_t)pos;
                 best_ord = 0;
                 best_idx = 0;
                 open = true;
             }
-            // kept members of the open group at/after pos; the first kept non-member closes it
-            const bool in = valid && lane >= pos && (x - anchor <= overlap) && (anchor - x <= overlap);
+            // kept members of the open group at/after pos; the first kept non-member closes it.  With overlap < 0 nothing but
+            // the opener is a member: every kept hit of an anchored row is a character of its own.
+            const bool in = valid && lane >= pos && ((int32_t)lane == opened_at || ((x - anchor <= overlap) && (anchor - x <= overlap)));
             const uint64_t inmask = __builtin_amdgcn_ballot_w64(in);
             const uint64_t brk = vmask & ~inmask & (~0ull << pos);
             const uint32_t stop = brk ? (uint32_t)__builtin_ctzll(brk) : 64u;
@@ -307,6 +314,56 @@ int focr_get_lines_into(focr_ctx_t *c, uint64_t *page_line_offsets, uint64_t *li
 
 const focr_hit_t *focr_lines_device_chars(focr_ctx_t *c) {
     return (c && c->processed && finish_results(c) == FOCR_OK && c->n_chars) ? (const focr_hit_t *)c->post_chars.p : nullptr;
+}
+
+// Test hook: the caller's hits where a scan leaves them for focr_process_hits — keys packed with the batch's KeyFmt, similarities
+// and keep flags in the buffers a split scan installs (scan_split, ctx.hip), the count on the device in d_res[7].
+int focr_debug_process_hits(focr_ctx_t *c, const uint32_t *page, const uint32_t *y, const uint32_t *x, const uint32_t *t,
+                            const float *similarity, const uint8_t *keep, size_t n) {
+    if (!c) return FOCR_ERR_INVALID;
+    if (n && (!page || !y || !x || !t || !similarity || !keep)) return fail(c, FOCR_ERR_INVALID, "focr_debug_process_hits: bad arguments");
+    if (!c->n_templates || !c->d_pages) return fail(c, FOCR_ERR_STATE, "focr_debug_process_hits: upload a bank and allocate pages first");
+    if (n >= 0xffffffffull) return fail(c, FOCR_ERR_OVERFLOW, "focr_debug_process_hits: more than 2^32 hits in one batch");
+    const KeyFmt fmt = key_format(c->n_templates, c->r_w, c->r_h, c->n_pages);
+    std::vector<uint64_t> keys(n);
+    std::vector<uint8_t> kept(n);
+    size_t n_kept = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (page[i] >= c->n_pages || y[i] >= c->r_h || x[i] >= c->r_w || t[i] >= c->n_templates)
+            return fail(c, FOCR_ERR_INVALID, "focr_debug_process_hits: hit " + std::to_string(i) + " lies outside the pages or the bank");
+        keys[i] = fmt.pack(page[i], y[i], x[i], t[i]);
+        if (i && keys[i] <= keys[i - 1])
+            return fail(c, FOCR_ERR_INVALID, "focr_debug_process_hits: hit " + std::to_string(i) + " does not follow its predecessor in (page, y, x, t)");
+        kept[i] = keep[i] != 0;
+        n_kept += kept[i];
+    }
+    if (int rc = finish_results(c)) return rc;  // whatever an earlier call queued is done before its buffers are overwritten
+    FOCR_HIP(c, hipSetDevice(c->device));
+    uint64_t *d_keys = (uint64_t *)c->acc_hkeys.ensure(c, (n + 1) * 8);
+    float *d_sims = (float *)c->acc_hsims.ensure(c, (n + 1) * 4);
+    uint8_t *d_keep = (uint8_t *)c->ord_keep.ensure(c, n + 1);
+    if (!d_keys || !d_sims || !d_keep) return fail(c, FOCR_ERR_NOMEM, "focr_debug_process_hits: hipMalloc failed");
+    c->n_hits_raw_u64 = n;
+    if (n) {
+        FOCR_HIP(c, hipMemcpyAsync(d_keys, keys.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+        FOCR_HIP(c, hipMemcpyAsync(d_sims, similarity, n * 4, hipMemcpyHostToDevice, c->stream));
+        FOCR_HIP(c, hipMemcpyAsync(d_keep, kept.data(), n, hipMemcpyHostToDevice, c->stream));
+    }
+    FOCR_HIP(c, hipMemcpyAsync(c->d_res + 7, &c->n_hits_raw_u64, 8, hipMemcpyHostToDevice, c->stream));
+    FOCR_HIP(c, hipStreamSynchronize(c->stream));
+    c->fmt = fmt;
+    c->d_hkeys = d_keys;
+    c->d_hsims = d_sims;
+    c->d_n_hits = c->d_res + 7;
+    c->ub_hits = n;
+    c->n_hits = c->n_hits_raw = n;
+    c->n_matches = n_kept;
+    c->sub_p0 = 0;
+    c->sub_np = c->n_pages;
+    c->sizes_pending = c->post_pending = c->estimated = false;
+    c->processed = c->lines_on_host = false;
+    c->scanned = c->debug_hits = true;
+    return FOCR_OK;
 }
 
 }  // extern "C"

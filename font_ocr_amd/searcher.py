@@ -30,6 +30,14 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _overlap_i32(overlap):
+    """overlap is the reference's i32 (src/ncc.rs:514); ctypes would wrap a wider value into the int32_t argument silently."""
+    o = int(overlap)
+    if not -(1 << 31) <= o < (1 << 31):
+        raise ValueError(f"overlap {o} is outside the i32 range")
+    return o
+
+
 class PinnedPages:
     """(n, r_h, r_w) uint8 array in page-locked host memory (focr_host_alloc): `.array` is a numpy view.
     Scanner.upload_pages from it is an asynchronous DMA (see include/focr_ncc.h)."""
@@ -245,7 +253,19 @@ class Scanner:
         return offsets, m
 
     def process_hits(self, anchor_threshold=0.95, overlap=5):
-        self._ck(self._lib.focr_process_hits(self._h, float(anchor_threshold), int(overlap)))
+        overlap = _overlap_i32(overlap)
+        self._ck(self._lib.focr_process_hits(self._h, float(anchor_threshold), overlap))
+
+    def debug_process_hits(self, page, y, x, t, similarity, keep):
+        """Test hook (focr_debug_process_hits): these hits, strictly increasing in (page, y, x, t), become the context's hits as if
+        a scan had found them (keep = 0: cut off by the cap); process_hits() and lines() then run as usual."""
+        cols = [np.ascontiguousarray(a, np.uint32) for a in (page, y, x, t)]
+        sims = np.ascontiguousarray(similarity, np.float32)
+        kp = np.ascontiguousarray(keep, np.uint8)
+        n = len(sims)
+        if any(len(a) != n for a in cols + [kp]):
+            raise ValueError("debug_process_hits: fields of different lengths")
+        self._ck(self._lib.focr_debug_process_hits(self._h, *[_ptr(a) for a in cols], _ptr(sims), _ptr(kp), n))
 
     def lines(self):
         """-> list over pages of list over lines of HIT_DTYPE arrays."""
@@ -346,6 +366,7 @@ class Pipeline:
                overlap=5, invert=True, device_ptr=None, shape=None, chars_out=None):
         """luma: (n, r_h, r_w) uint8 host pages; or device_ptr + shape=(n, r_h, r_w); or neither = rescan the lane's
         resident pages.  chars_out=(device pointer, bytes): also copy the batch's characters there.  Returns the ticket."""
+        overlap = _overlap_i32(overlap)
         t = C.c_uint64()
         if luma is not None:
             luma = np.ascontiguousarray(luma, np.uint8)
@@ -360,7 +381,7 @@ class Pipeline:
             n = r_h = r_w = 0
             ptr, on_dev = None, 0
         rc = self._lib.focr_pipe_submit(self._h, ptr, on_dev, n, r_w, r_h, int(bool(invert)), float(threshold), int(cap), int(mode),
-                                        int(bool(process_hits)), float(anchor_threshold), int(overlap),
+                                        int(bool(process_hits)), float(anchor_threshold), overlap,
                                         C.c_void_p(int(chars_out[0])) if chars_out else None, int(chars_out[1]) if chars_out else 0,
                                         C.byref(t))
         if rc != 0:
@@ -480,13 +501,14 @@ class Fleet:
         return int(self._lib.focr_fleet_device_of(self._h, int(ticket)))
 
     def submit(self, luma, threshold=0.8, cap=MAX_MATCHES, mode=SCAN_MFMA, process_hits=True, anchor_threshold=0.95, overlap=5, invert=True):
+        overlap = _overlap_i32(overlap)
         luma = np.ascontiguousarray(luma, np.uint8)
         if luma.ndim == 2:
             luma = luma[None]
         n, r_h, r_w = luma.shape
         t = C.c_uint64()
         rc = self._lib.focr_fleet_submit(self._h, _ptr(luma), 0, n, r_w, r_h, int(bool(invert)), float(threshold), int(cap), int(mode),
-                                         int(bool(process_hits)), float(anchor_threshold), int(overlap), C.byref(t))
+                                         int(bool(process_hits)), float(anchor_threshold), overlap, C.byref(t))
         if rc != 0:
             raise FocrError(f"[{rc}] {self._lib.focr_last_error_global().decode()}")
         self._keep[t.value] = luma

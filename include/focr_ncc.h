@@ -186,7 +186,11 @@ int focr_get_matches(focr_ctx_t *ctx, uint64_t *offsets, focr_match_t *matches);
 
 /* process_hits on the device (src/ncc.rs:723-786 + partition_by 1036-1052)
  * over the last scan's hits, for every page.  A page without hits yields zero
- * lines (the reference panics there, src/ncc.rs:1040). */
+ * lines (the reference panics there, src/ncc.rs:1040).  overlap is the
+ * reference's i32 (src/ncc.rs:514): a group holds the hits within
+ * |x - x_first| <= overlap of its first hit, and the first hit always belongs
+ * to its group (partition_by, src/ncc.rs:1040-1048).  So with overlap < 0
+ * every kept hit of an anchored row is a character of its own. */
 int focr_process_hits(focr_ctx_t *ctx, float anchor_threshold, int32_t overlap);
 size_t focr_total_chars(focr_ctx_t *ctx);
 size_t focr_total_lines(focr_ctx_t *ctx);
@@ -455,6 +459,15 @@ int focr_debug_prefilter(const focr_template_t *templates, size_t n_templates, c
 void focr_debug_plane_value(const float *L, size_t n, uint32_t shift, int16_t *out);
 /* The same as the device computes them (the GPU tests compare the two bit for bit). */
 int focr_debug_plane_value_device(focr_ctx_t *ctx, const float *L, size_t n, uint32_t shift, int16_t *out);
+
+/* Test hook: n caller-chosen hits become the context's hits, as if a scan had found them, so that the tests can put ties,
+ * group boundaries and capped hits where focr_process_hits' line walk cuts a row into chunks of 64.  Hit i is (page[i], y[i],
+ * x[i], template t[i], similarity[i]); keep[i] == 0 marks a hit cut off by its call's cap, which process_hits does not see.
+ * The hits must be strictly increasing in (page, y, x, t) and lie inside the context's pages and bank (focr_pages_alloc,
+ * focr_bank_upload; their contents are not read).  focr_process_hits and focr_get_lines then run unchanged;
+ * focr_get_counts and focr_get_matches refuse, as no per-call lists stand behind such hits.  The next focr_scan replaces them. */
+int focr_debug_process_hits(focr_ctx_t *ctx, const uint32_t *page, const uint32_t *y, const uint32_t *x, const uint32_t *t,
+                            const float *similarity, const uint8_t *keep, size_t n);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,22 @@ def test_cli_flags_and_errors(ncc_bin):
     assert r.returncode == 101  # Font::from_path(..).unwrap() panics, src/ncc.rs:561
 
 
+def test_cli_overlap_is_an_i32(ncc_bin):
+    """--overlap is the reference's i32 (src/ncc.rs:514): a value outside it is refused as clap refuses it (exit 2), in either
+    spelling; negative values inside it are accepted (parsing passes and the run stops at the missing font, exit 101)."""
+    base = [ncc_bin, "-f", "/nonexistent.ttf", "-t", "13"]
+    for v in ("2147483648", "4294967295", "-2147483649", "99999999999999999999999"):
+        for form in (["--overlap", v], ["--overlap=" + v]):
+            r = subprocess.run(base + form, capture_output=True, text=True)
+            assert r.returncode == 2, (v, r.stderr)
+            assert f"invalid value '{v}' for '--overlap <OVERLAP>'" in r.stderr, r.stderr
+    r = subprocess.run(base + ["--overlap", "5x"], capture_output=True, text=True)
+    assert r.returncode == 2 and "invalid value '5x' for '--overlap <OVERLAP>'" in r.stderr
+    for form in (["--overlap", "-1"], ["--overlap=-1"], ["--overlap", "-2147483648"], ["--overlap=2147483647"], ["--overlap", "0"]):
+        r = subprocess.run(base + form, capture_output=True, text=True)
+        assert r.returncode == 101, (form, r.stderr)
+
+
 def test_pnm_and_png_decode(tmp_path):
     rng = np.random.default_rng(3)
     img = rng.integers(0, 256, (17, 23), dtype=np.uint8)

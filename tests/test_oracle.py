@@ -255,6 +255,21 @@ def test_rust_witness_process_hits_fuzz_with_ties():
         overlap = int(rng.integers(0, 9))
         anchor = float(rng.choice([0.95, 0.5, 0.97, 1.5]))
         assert _witness_lines(hits, anchor, overlap) == _oracle_line_indices(hits, anchor, overlap), it
+    # the edges of the i32 overlap (below zero every kept hit of an anchored row is its own character; a row's width and more)
+    # and of the f32 anchor (NaN, +-inf, -1, exactly a hit's similarity and the next f32 above it), on rows of several hundred hits
+    edge_sims = np.array([0.5, 0.95, 0.97, 0.97, 1.0, -0.0, 0.0, 1e-45, -0.25, 0.9731], np.float32)
+    for it in range(8):
+        n = int(rng.integers(300, 700)) if it % 2 else int(rng.integers(20, 120))
+        hits = np.zeros(n, O.HIT_DTYPE)
+        hits["x"] = rng.integers(1, 90 if it % 4 < 2 else 3000, n)
+        hits["y"] = rng.integers(1, 3 if it % 2 else 8, n)
+        hits["w"], hits["h"] = 8, 15
+        hits["similarity"] = edge_sims[rng.integers(0, len(edge_sims), n)]
+        hits["letter"] = rng.integers(33, 127, n)
+        s = np.float32(hits["similarity"][int(rng.integers(0, n))])
+        for anchor in (float("nan"), float("inf"), float("-inf"), -1.0, float(s), float(np.nextafter(s, np.float32(np.inf)))):
+            for overlap in (-2**31, -5, -1, 0, 1, 64, 65535, 2**31 - 1):
+                assert _witness_lines(hits, anchor, overlap) == _oracle_line_indices(hits, anchor, overlap), (it, anchor, overlap)
     with pytest.raises(IndexError):  # the reference panics on an empty hit list (src/ncc.rs:1040)
         W.partition_by([], lambda a, b: True)
     assert W.partition_by([1, 2, 3, 9, 10, 14], lambda a, b: abs(a - b) <= 2) == [(0, 3), (3, 5), (5, 6)]
