@@ -132,6 +132,10 @@ HIP_SYMBOLS = {
     "focr_debug_process_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "focr_debug_prefilter": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "focr_debug_prefilter_page": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32,
+                                            C.c_float, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "focr_debug_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "focr_pipe_create": (C.c_int, [C.c_int, C.c_uint, C.POINTER(C.c_void_p)]),
     "focr_pipe_create2": (C.c_int, [C.c_int, C.c_uint, C.c_uint, C.POINTER(C.c_void_p)]),
     "focr_pipe_destroy": (None, [C.c_void_p]),

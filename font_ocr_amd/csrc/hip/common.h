@@ -191,6 +191,7 @@ struct focr_ctx {
     int32_t post_overlap = 0;
     bool force_split = false;                   // tests: take scan_split without waiting for an overflow (focr_debug_force_split)
     bool debug_hits = false;                    // tests: the hits came from focr_debug_process_hits, no per-call lists stand behind them
+    bool cand_intact = false;                   // tests: d_cand still holds the last MFMA scan's candidates as the scan kernels left them (focr_debug_candidates)
     int dbg_stats_form = 0;  // tests / A-B: 1 = the LDS-tiled statistics kernel for every class (focr_debug_set_stats_form; 0: the register form where it applies)
     uint32_t dbg_grid_num = 0, dbg_grid_den = 0;  // tests: the tail's persistent kernels on num / den times their workgroups (focr_debug_set_tail_grid; 0: as designed)
     int prefilter = 0;                          // FOCR_PREFILTER_*: auto / plane kernel / legacy kernel (focr_ctx_set_prefilter)

@@ -423,6 +423,34 @@ int focr_debug_planes(focr_ctx_t *c, uint16_t *out, size_t capacity, size_t *n_v
     return FOCR_OK;
 }
 
+// Test hook: the candidate keys of the last MFMA scan, unpacked.  Nothing is kept for it during a scan: the hits-first tail only reads
+// d_cand, so the keys are still where the scan kernels' flushes left them; the legacy tail sorts and compacts them in place, and a
+// split batch leaves only its last page sub-range there — both are refused.
+int focr_debug_candidates(focr_ctx_t *c, uint32_t *out, size_t capacity, size_t *n) {
+    if (!c || !n) return fail(c, FOCR_ERR_INVALID, "focr_debug_candidates: bad arguments");
+    if (!c->scanned) return fail(c, FOCR_ERR_STATE, "focr_debug_candidates: no scan results");
+    if (c->debug_hits) return fail(c, FOCR_ERR_STATE, "focr_debug_candidates: the hits came from focr_debug_process_hits, not from a scan");
+    if (c->scan_mode != FOCR_SCAN_MFMA) return fail(c, FOCR_ERR_STATE, "focr_debug_candidates: the last scan was not an MFMA scan (no candidate list)");
+    if (int rc = finish_results(c)) return rc;  // (an estimated scan whose counts exceeded their bounds is redone here, with exact sizes)
+    if (!c->cand_intact)
+        return fail(c, FOCR_ERR_STATE, "focr_debug_candidates: the last scan's candidates are gone (legacy tail: sorted and compacted in place; split batch: only the last page sub-range is left)");
+    *n = c->n_cand;
+    if (!out) return FOCR_OK;
+    if (capacity < c->n_cand) return fail(c, FOCR_ERR_INVALID, "focr_debug_candidates: buffer too small");
+    if (c->n_cand > c->cand_capacity) return fail(c, FOCR_ERR_STATE, "focr_debug_candidates: internal: more candidates than the list holds");
+    FOCR_HIP(c, hipSetDevice(c->device));
+    std::vector<uint64_t> keys(c->n_cand);
+    if (c->n_cand) {
+        FOCR_HIP(c, hipMemcpyAsync(keys.data(), c->d_cand, c->n_cand * 8, hipMemcpyDeviceToHost, c->io_stream));
+        FOCR_HIP(c, hipStreamSynchronize(c->io_stream));
+    }
+    for (size_t i = 0; i < keys.size(); i++) {
+        out[4 * i] = c->fmt.page(keys[i]), out[4 * i + 1] = c->fmt.y(keys[i]);
+        out[4 * i + 2] = c->fmt.x(keys[i]), out[4 * i + 3] = c->fmt.t(keys[i]);
+    }
+    return FOCR_OK;
+}
+
 int focr_sync(focr_ctx_t *c) {
     if (!c) return FOCR_ERR_INVALID;
     FOCR_HIP(c, hipSetDevice(c->device));
@@ -839,7 +867,7 @@ namespace focr {
 static int scan_now(focr_ctx *c) {
     const float threshold = c->scan_thr;
     const int mode = c->scan_mode;
-    c->scanned = c->processed = c->debug_hits = false;
+    c->scanned = c->processed = c->debug_hits = c->cand_intact = false;
     c->sizes_pending = c->post_pending = false;
     for (auto &m : c->ms) m = 0.f;
     c->counters[3] = 0;
@@ -862,6 +890,7 @@ static int scan_now(focr_ctx *c) {
         c->sizes_pending = false;
         rc = scan_split(c, run);
         if (rc) return rc;
+        c->cand_intact = false;  // d_cand holds the last page sub-range's candidates only
         // the sub-runs left the size estimates at the counts of the LAST page sub-range: a following scan of this setup, here or on
         // another context, must not run "estimated" on them (it would overflow, redo exact, overflow again and only then split)
         c->est.reset();

@@ -69,7 +69,11 @@ struct PlaneParams {
 };
 constexpr int16_t PLANE_NEVER = -32768;  // the reference never emits at this window: an unreachable threshold
 
-// f32 square root: the raw 1-ulp instruction on the device, the correctly rounded one in the host model
+// f32 square root: the raw 1-ulp instruction on the device, the correctly rounded one in the host model — so the model's L and the
+// device's differ by up to 2^-22 of |kq|*sqrt(V) + crk*sqrt(W) (2^-23 of each term from the root, at most 2^-24 more from the
+// multiply / fma behind it) and a plane value by one unit where (L - 2) / S lies that close to an integer.  Either L stays within
+// the "- 2" of the real number (below), so both planes are conservative; tests/test_gpu_prefilter_model.py checks the device's
+// against float64 and against the model with exactly this allowance.
 __host__ __device__ inline float sqrt_fast(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_sqrtf(x);
@@ -110,7 +114,8 @@ __host__ __device__ inline int16_t plane_value(const PlaneParams &p, float Lf) {
     // of L - 2 scaled — bit-identical to (Lf - 2.0f) * inv_S, one instruction less
     // ... and the sign goes into the same step: -floor(t) = ceil(-t), and fma(L, -1/S, 2/S) = -fma(L, 1/S, -2/S) bit for bit (rounding to
     // nearest is symmetric), so the value is ceil of one fma; the clamp is one integer median (the conversion saturates at
-    // +-2^31 by itself, on the device as in the host's std::clamp below): four instructions per window and class, not six
+    // +-2^31 by itself; the host model clamps the float before it converts — two flavours of one function, which is why the test
+    // named above compares them bit for bit instead of taking it on trust): four instructions per window and class, not six
     const float t = __builtin_ceilf(__builtin_fmaf(Lf, -p.inv_S, 2.0f * p.inv_S));
 #if defined(__HIP_DEVICE_COMPILE__)
     const int q = (int)t;  // (v_cvt_i32_f32 saturates)
@@ -425,6 +430,7 @@ struct PlaneArgs {
 
 // scan_mfma.hip (host)
 PlaneParams plane_params(const focr_ctx *c, size_t k, double thr_d);
+int plan_passes(focr_ctx *c, size_t plane, size_t &tiles_total, size_t &plane_vals, bool &need_L);
 // scan_mfma2.hip
 uint32_t mfma2_chunk_tiles(uint32_t ksteps);
 int dispatch_mfma_v2s(focr_ctx *c, const MfmaLaunch &L, const PlaneArgs &A, unsigned n_cus);  // A = templates, B = windows, threshold planes

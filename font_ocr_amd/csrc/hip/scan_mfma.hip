@@ -21,7 +21,8 @@
 //     hence sim > thr  ==>  G > (c*thr - max_t ||e_t||) * norm_p =: kappa * norm_p; kappa carries an extra relative margin for
 //     the f64 roundings of the exact formula.  Classes 9 or 13 px wide leave their last column to a second Cauchy-Schwarz term,
 //     L(w) = kappa * norm_p(w) - c * rho_max * dnorm(w), and take the next narrower K layout (column drop, mfma_common.h).  The
-//     filter has no false negatives (host model of the device arithmetic: prefilter_model.hip, tests/test_prefilter_host.py).
+//     filter has no false negatives (host model: prefilter_model.hip, tests/test_prefilter_host.py; the device's planes and candidate
+//     sets against that model: tests/test_gpu_prefilter_model.py).
 //     Survivors go to a candidate list.
 //  3. the hits-first row tail (rows.hip): candidates verified exactly where they lie — the reference formula, operation for
 //     operation (verify_candidate, mfma_common.h / common.h) — hits bucketed by page row and sorted per bucket; order.hip derives
@@ -956,16 +957,12 @@ static size_t pass_planes(const focr_ctx *c, const SuperClass &su, size_t plane)
     return ok ? n : 0;
 }
 
-static int plan_scan(focr_ctx *c, bool nothing, size_t want_cand, ScanPlan &P) {
-    if (int rc = ensure_exact(c, c->d_cand, c->cand_capacity, want_cand, "cand")) return rc;
-    if (nothing) return FOCR_OK;  // no statistics, no scan
-    if (c->supers.size() > 40) return fail(c, FOCR_ERR_INVALID, "scan_mfma: too many super-classes");
-    P.Lpitch = (uint32_t)((c->r_w + 63) / 64 * 64 + 64);
-    P.Lrows = (uint32_t)((c->r_h + 7) / 8 * 8 + 8);
-    P.L_per_class = c->n_pages * (size_t)P.Lrows * P.Lpitch;
-    P.plane = c->sub_np * (size_t)P.Lrows * P.Lpitch;
-    size_t plane_vals = 0;
-    bool need_L = false;
+// The passes of a scan of c->sub_np pages of c->r_w x c->r_h (host only; also what the host model reports, prefilter_model.hip): per
+// super-class the window enumeration, the offset of its M-tiles in the work list and of its planes in d_planes (`plane`: int16 values
+// of one plane).  Totals: M-tiles of all passes, plane values, and whether a pass takes the int32 tables.
+int plan_passes(focr_ctx *c, size_t plane, size_t &tiles_total, size_t &plane_vals, bool &need_L) {
+    tiles_total = plane_vals = 0;
+    need_L = false;
     for (SuperClass &su : c->supers) {
         // windows of the pass: those of its smallest searchable class
         su.min_w = su.min_h = 0xffffffffu;
@@ -976,20 +973,34 @@ static int plan_scan(focr_ctx *c, bool nothing, size_t want_cand, ScanPlan &P) {
             su.min_h = std::min(su.min_h, sc.n_h);
         }
         su.mtx = su.n_rows = 0;
-        su.live_offset = P.tiles_total;
+        su.live_offset = tiles_total;
         su.planes = false;
         if (su.min_w == 0xffffffffu) continue;  // nothing searchable
         su.mtx = (uint32_t)((c->r_w - su.min_w + 1 + 15) / 16);  // windows x in [0, r_w - min n_w]
         su.n_rows = (uint32_t)(c->r_h - su.min_h);               // y in [1, r_h - min n_h]
         const uint64_t nt = (uint64_t)su.mtx * su.n_rows * c->sub_np;
         if (nt >= 0x7fffffffull) return fail(c, FOCR_ERR_INVALID, "scan_mfma: batch too large for 32-bit tile ids; scan fewer pages per call");
-        P.tiles_total += (size_t)nt;
-        const size_t n_planes = pass_planes(c, su, P.plane);
+        tiles_total += (size_t)nt;
+        const size_t n_planes = pass_planes(c, su, plane);
         su.planes = n_planes != 0;
         su.plane_off = plane_vals;
-        plane_vals += n_planes * P.plane;
+        plane_vals += n_planes * plane;
         need_L |= !su.planes;
     }
+    return FOCR_OK;
+}
+
+static int plan_scan(focr_ctx *c, bool nothing, size_t want_cand, ScanPlan &P) {
+    if (int rc = ensure_exact(c, c->d_cand, c->cand_capacity, want_cand, "cand")) return rc;
+    if (nothing) return FOCR_OK;  // no statistics, no scan
+    if (c->supers.size() > 40) return fail(c, FOCR_ERR_INVALID, "scan_mfma: too many super-classes");
+    P.Lpitch = (uint32_t)((c->r_w + 63) / 64 * 64 + 64);
+    P.Lrows = (uint32_t)((c->r_h + 7) / 8 * 8 + 8);
+    P.L_per_class = c->n_pages * (size_t)P.Lrows * P.Lpitch;
+    P.plane = c->sub_np * (size_t)P.Lrows * P.Lpitch;
+    size_t plane_vals = 0;
+    bool need_L = false;
+    if (int rc = plan_passes(c, P.plane, P.tiles_total, plane_vals, need_L)) return rc;
     if (int rc = ensure_exact(c, c->d_L, c->L_values, need_L ? P.L_per_class * c->classes.size() : 0, "negL")) return rc;
     if (int rc = ensure_exact(c, c->d_planes, c->plane_values, plane_vals, "planes")) return rc;
     P.live = (uint8_t *)c->scan_live.ensure(c, P.tiles_total + 24);
@@ -1259,6 +1270,7 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
             }
             ub_c = (size_t)n_cand;
         }
+        c->cand_intact = use_rows;  // the row tail only reads d_cand; the legacy tail sorts and compacts it in place (focr_debug_candidates)
         return use_rows ? row_tail(c, thr_d, n_cand_p, ub_c) : legacy_tail(c, thr_d, n_cand_p, ub_c);
     }
     return fail(c, FOCR_ERR_OVERFLOW, "scan_mfma: candidate buffer kept overflowing");

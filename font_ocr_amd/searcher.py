@@ -38,6 +38,45 @@ def _overlap_i32(overlap):
     return o
 
 
+CLASS_INFO_FIELDS = ("n_w", "n_h", "keep_w", "layout", "ksteps", "super", "value", "plane_slot", "mtx", "n_rows", "kq", "crk", "shift",
+                     "n_templates", "n_live", "tile_first")
+
+
+def prefilter_page_model(bank, page_ink, threshold, column_drop=True, prefilter=PREFILTER_AUTO, want=("V", "W_upper", "L", "plane", "G", "sim")):
+    """Host model of the MFMA prefilter over every window of one ink-high page (focr_debug_prefilter_page; no device).  Returns a dict:
+    'classes' (list of dicts, CLASS_INFO_FIELDS), 'templates' ((T, 4) int32: class, slot, live, N-tile), 'q' ((T, 32, 16) int8) and,
+    if page_ink is given, the arrays named in `want`: V / W_upper / L / plane as (classes, r_h, r_w), G / sim as (T, r_h, r_w)."""
+    lib = N.hip()
+    T = len(bank.templates)
+    info = np.zeros(16 * T, np.float64)
+    n_cls = C.c_size_t(0)
+    tinfo = np.zeros((T, 4), np.int32)
+    q = np.zeros((T, 32, 16), np.int8)
+    page = None if page_ink is None else np.ascontiguousarray(page_ink, np.uint8)
+    r_h, r_w = (1, 1) if page is None else page.shape
+
+    def call(pg, outs):
+        rc = lib.focr_debug_prefilter_page(_ptr(bank.templates), T, _ptr(bank.needles), bank.needles.size, int(bool(column_drop)), int(prefilter),
+                                           None if pg is None else _ptr(pg), r_w, r_h, float(threshold), _ptr(info), info.size, C.byref(n_cls),
+                                           _ptr(tinfo), _ptr(q), *[None if a is None else _ptr(a) for a in outs])
+        if rc != 0:
+            raise FocrError(f"[{rc}] focr_debug_prefilter_page")
+
+    if page is None:
+        call(None, [None] * 6)
+        out = {}
+    else:
+        call(None, [None] * 6)  # the number of classes first
+        k = n_cls.value
+        shapes = {"V": ((k, r_h, r_w), np.uint64), "W_upper": ((k, r_h, r_w), np.float32), "L": ((k, r_h, r_w), np.float32),
+                  "plane": ((k, r_h, r_w), np.int16), "G": ((T, r_h, r_w), np.int32), "sim": ((T, r_h, r_w), np.float64)}
+        out = {name: np.zeros(*shapes[name]) for name in want}
+        call(page, [out.get(name) for name in ("V", "W_upper", "L", "plane", "G", "sim")])
+    out["classes"] = [dict(zip(CLASS_INFO_FIELDS, info[16 * k: 16 * k + 16])) for k in range(n_cls.value)]
+    out["templates"], out["q"] = tinfo, q
+    return out
+
+
 class PinnedPages:
     """(n, r_h, r_w) uint8 array in page-locked host memory (focr_host_alloc): `.array` is a numpy view.
     Scanner.upload_pages from it is an asynchronous DMA (see include/focr_ncc.h)."""
@@ -227,6 +266,16 @@ class Scanner:
         out = np.empty(n.value, dtype=np.int16)
         if n.value:
             self._ck(self._lib.focr_debug_planes(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def candidates(self):
+        """Test hook (focr_debug_candidates): the last MFMA scan's candidates as an (n, 4) uint32 array of (page, y, x, global
+        template index), in no particular order.  Raises after a scan that took the legacy tail, a split batch, a direct scan."""
+        n = C.c_size_t(0)
+        self._ck(self._lib.focr_debug_candidates(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 4), np.uint32)
+        if n.value:
+            self._ck(self._lib.focr_debug_candidates(self._h, _ptr(out), n.value, C.byref(n)))
         return out
 
     def set_scan_cus(self, max_cus):

@@ -445,7 +445,8 @@ int focr_debug_planes(focr_ctx_t *ctx, uint16_t *out, size_t capacity, size_t *n
  * frame_w x frame_h bytes (row-major; every template must fit the frame, its window is the frame's top-left n_w x n_h
  * box), per (window, template):
  *   sim[w * n_templates + t]   the exact similarity (double; NaN where the reference cannot emit: zero variance)
- *   d[w * n_templates + t]     G + C-in as the device forms them: the int8 MFMA sum over the kept columns plus
+ *   d[w * n_templates + t]     G + C-in as the kernels form them (up to the device's 1-ulp square root: see
+ *                              focr_debug_prefilter_page below): the int8 MFMA sum over the kept columns plus
  *                              the window's plane value (the statistics kernel's arithmetic: f32, then -floor((L - 2) / S)
  *                              as int16) times S; the pair is a candidate iff d > 0
  * column_drop: as focr_ctx_set_column_drop.  info[4 * k ..] = {c_scale, e_max, rho_max, kept width} of size class k (in
@@ -453,6 +454,42 @@ int focr_debug_planes(focr_ctx_t *ctx, uint16_t *out, size_t capacity, size_t *n
 int focr_debug_prefilter(const focr_template_t *templates, size_t n_templates, const uint8_t *needles, size_t needles_len,
                          int column_drop, const uint8_t *windows, size_t n_windows, uint32_t frame_w, uint32_t frame_h,
                          float threshold, double *sim, int64_t *d, double *info, size_t n_info);
+
+/* The same host model over EVERY window of one ink-high page of r_w x r_h, with its pieces laid open (no device needed), so that
+ * a test can hold each phase of the device's prefilter against it (tests/test_gpu_prefilter_model.py).  Window (x, y) of a class
+ * is the n_w x n_h box at that corner; prefilter: as focr_ctx_set_prefilter.  Every output may be NULL; page == NULL fills only
+ * the first three.
+ *   class_info[16 * k ..]   size class k (order of first appearance; *n_classes of them): n_w, n_h, kept width, K layout (1 = 16-byte
+ *                           rows, 2 = 8, 3 = 12), K-steps, super-class, value index inside it, index of the class's plane in
+ *                           focr_debug_planes' output counted in planes ([n_pages][Lrows][Lpitch] values each; -1: the pass takes
+ *                           the int32 tables of the legacy kernel — more than 4 K-steps or classes, FOCR_PREFILTER_LEGACY — or
+ *                           nothing of it fits the page), M-tiles per row and searched rows of its pass (the scan kernel reads
+ *                           the planes at x < 16 * mtx, y <= n_rows), then the threshold's parameters for `threshold`: kq, crk
+ *                           (f32 values), log2 of the plane's unit S; templates, live templates, first N-tile in the super-class
+ *   template_info[4 * t ..] class, slot inside the class's N-tiles, 1 if the template can emit (0: constant needle), N-tile
+ *                           inside the super-class
+ *   qtemplates[t][32][16]   the int8 template the MFMA multiplies (rows x kept columns, zero elsewhere)
+ *   V, W_upper, L, plane    [class][r_h][r_w]: the exact integer V = n*s2 - s^2, the f32 upper bound of W (0: nothing dropped), the
+ *                           f32 threshold L and the model's int16 plane value: -32768 at x = 0, y = 0, V = 0 and where the box
+ *                           leaves the page (there V = W = L = 0)
+ *   G                       [template][r_h][r_w]: the int8 sum over the kept columns; INT32_MIN for a template that cannot emit
+ *                           and where the box leaves the page.  The pair is a candidate iff G + (plane << log2 S) > 0.
+ *   sim                     [template][r_h][r_w]: the exact similarity; NaN where the reference cannot emit
+ * The model is not the device's arithmetic to the bit: its square roots are correctly rounded, the device's are the 1-ulp
+ * instruction, so a plane value may differ by one unit where (L - 2) / S lies next to an integer. */
+int focr_debug_prefilter_page(const focr_template_t *templates, size_t n_templates, const uint8_t *needles, size_t needles_len,
+                              int column_drop, int prefilter, const uint8_t *page, uint32_t r_w, uint32_t r_h, float threshold,
+                              double *class_info, size_t class_info_len, size_t *n_classes, int32_t *template_info,
+                              int8_t *qtemplates, uint64_t *V, float *W_upper, float *L, int16_t *plane, int32_t *G, double *sim);
+
+/* Test hook: the candidates of the context's last MFMA scan — what the prefilter flagged (and what the exact scan of classes
+ * taller than 32 px or wider than 16 emitted), before the verify — as (page, y, x, global template index) quadruples in no
+ * particular order; *n = their number = focr_last_counters()[0]; out = NULL: only the number.  Costs a normal scan nothing:
+ * the hits-first tail only reads the candidate list, so it is copied from where the scan kernels left it.  FOCR_ERR_STATE
+ * where that list is gone or was never there: after a scan that took the legacy tail (focr_ctx_set_row_tail(0), or a bank
+ * the row tail does not cover: it sorts and compacts the list in place), a batch scanned in page sub-ranges, a direct / rust
+ * scan, focr_debug_process_hits. */
+int focr_debug_candidates(focr_ctx_t *ctx, uint32_t *out, size_t capacity, size_t *n);
 
 /* The threshold planes' values (mfma_common.h: -floor((L - 2) / 2^shift) as int16, clamped to +-32767), host flavour, for the
  * CPU tests. */

@@ -1,6 +1,11 @@
 """Host model of the MFMA prefilter's bound (font_ocr_amd/csrc/hip/prefilter_model.hip, focr_debug_prefilter): the quantised
 bank focr_bank_upload builds and the threshold arithmetic the statistics / scan kernels perform (shared inline functions of
-mfma_common.h), evaluated on the CPU.  The property the fast path rests on: "the reference emits (sim > thr)  =>  the
+mfma_common.h), evaluated on the CPU.  The model is not the device's arithmetic to the bit: its f32 square roots are correctly
+rounded where the device's are the 1-ulp instruction, the plane value's clamp is written differently (the two flavours are compared
+bit for bit by tests/test_gpu_parity.py::test_threshold_plane_values_device_equals_host), and its sums come from plain loops where the
+kernels use sliding sums, 24-bit multiplies and byte-unaligned fragment loads.  What the device itself computes is held against this
+model, plane by plane and candidate set by candidate set, by tests/test_gpu_prefilter_model.py; the tests at the end of this file
+check the model's own pieces against numpy.  The property the fast path rests on: "the reference emits (sim > thr)  =>  the
 prefilter flags the pair (G + C-in > 0)" — no false negatives — on text, noise, degenerate and adversarial windows, for
 positive AND negative thresholds (round 2's f16 window norms raised the threshold for negative ones: VERDICT r02 weak #1),
 with and without the column drop.  No GPU."""
@@ -9,6 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import prefilter_cases as PC
 from font_ocr_amd import _native as N
 from font_ocr_amd import synth_page
 from font_ocr_amd.bank import SYNTH_SEED_BASE, TEMPLATE_DTYPE, Bank
@@ -114,7 +120,8 @@ def _two_level(w, h, lo=100, hi=101, seed=0):
 def test_adversarial_exact_bank_near_threshold_windows(thr):
     """a bank whose quantisation is exact (e_max = 0) and uniform-noise windows whose similarity lies
     within 1e-4 of the threshold — picked out of millions in numpy — are where a threshold formed from a LOWER bound of the
-    window norm misses true hits when kappa < 0.  The model (= the device arithmetic) must flag every emitting one."""
+    window norm misses true hits when kappa < 0.  The model must flag every emitting one (the device's planes are tied to the model's
+    by tests/test_gpu_prefilter_model.py: at most one unit apart, and conservative against float64 on their own)."""
     nd = _two_level(8, 15)
     bank = _bank_of([nd])
     _, _, info = _model(bank, np.zeros((0, 120)), 8, 15, thr)
@@ -206,3 +213,98 @@ def test_plane_value_helper_matches_numpy():
             t = np.floor((x - np.float32(2.0)).astype(np.float32) * np.float32(2.0 ** -shift))
         want = (-np.clip(t, -32767.0, 32767.0)).astype(np.int16)
         assert np.array_equal(out, want), (shift, x[out != want][:5], out[out != want][:5], want[out != want][:5])
+
+
+# ---- the model's pieces (focr_debug_prefilter_page), against plain numpy ----
+
+def _pieces_pages(rng):
+    """Random, sparse and saturated content: what tests/prefilter_cases.py builds its pages from, on one small page each."""
+    a = rng.integers(0, 256, (40, 56), dtype=np.uint8)
+    b = a.copy()
+    b[rng.random(b.shape) < 0.6] = 0
+    return [a, b] + list(PC._saturated_pages(4, 56, 40, rng))
+
+
+@pytest.mark.parametrize("drop", [True, False], ids=["column-drop", "full-width"])
+@pytest.mark.parametrize("thr", [0.8, 0.0, -0.9])
+def test_page_model_pieces_match_numpy(thr, drop):
+    """V and G in int64 numpy (G from the int8 templates the model reports), d of focr_debug_prefilter == G + (plane << shift), the f32
+    bound of W >= the exact W, and the model's own planes conservative against float64: -plane * S <= kq*sqrt(V) - crk*sqrt(W) — check B of
+    tests/test_gpu_prefilter_model.py on the model, so that a failure there can be told from a failure of the bound itself."""
+    rng = np.random.default_rng(17)
+    shapes = [(9, 15), (8, 15), (13, 16), (16, 16), (16, 17), (5, 9), (12, 7)]
+    bank = _bank_of([rng.integers(0, 256, (h, w), dtype=np.uint8) for w, h in shapes for _ in range(3)] + [np.full((15, 9), 7, np.uint8)])
+    T = len(bank)
+    for page in _pieces_pages(rng):
+        r_h, r_w = page.shape
+        m = PC.prefilter_page_model(bank, page, thr, drop)
+        assert len(m["classes"]) == len(shapes)
+        yy, xx = np.mgrid[0:r_h, 0:r_w]
+        for k, c in enumerate(m["classes"]):
+            n_w, n_h, kw, shift = int(c["n_w"]), int(c["n_h"]), int(c["keep_w"]), int(c["shift"])
+            assert (n_w, n_h) == shapes[k] and kw == (n_w - 1 if drop and n_w in (9, 13) else n_w)
+            V, W = PC.window_sums(page, n_w, n_h, kw, r_h, r_w)
+            fits = (xx + n_w <= r_w) & (yy + n_h <= r_h)
+            assert np.array_equal(m["V"][k][fits].astype(np.int64), V[fits]) and not m["V"][k][~fits].any()
+            assert (m["W_upper"][k][fits].astype(np.float64) >= W[fits]).all() and (W >= 0).all()
+            can = fits & (xx >= 1) & (yy >= 1) & (V != 0)
+            assert np.array_equal(m["plane"][k] != PC.NEVER, can)
+            S, q = float(1 << shift), m["plane"][k].astype(np.float64)
+            L64 = float(c["kq"]) * np.sqrt(V.astype(np.float64)) - float(c["crk"]) * np.sqrt(W.astype(np.float64))
+            free = can & (np.abs(m["plane"][k].astype(np.int64)) != 32767)
+            assert (-q[free] * S <= L64[free]).all(), (thr, drop, n_w, n_h, float((-q * S - L64)[free].max()))
+            # the plane value itself, from the model's own f32 L: -floor((L - 2) / S), clamped — the "- 2" and the unit, in plain numpy
+            with np.errstate(over="ignore", invalid="ignore"):
+                ref = -np.clip(np.floor((m["L"][k] - np.float32(2.0)).astype(np.float32) * np.float32(1.0 / S)), -32767.0, 32767.0)
+            assert np.array_equal(m["plane"][k][can].astype(np.int64), ref[can].astype(np.int64)), (thr, drop, n_w, n_h)
+        for t in range(T):
+            k, live = int(m["templates"][t, 0]), bool(m["templates"][t, 2])
+            n_w, n_h, kw = (int(m["classes"][k][f]) for f in ("n_w", "n_h", "keep_w"))
+            fits = (xx + n_w <= r_w) & (yy + n_h <= r_h)
+            q = m["q"][t].astype(np.int64)
+            assert not q[n_h:].any() and not q[:, kw:].any() and (not live or q.sum() == 0)
+            assert live == (t != T - 1)
+            if not live:
+                assert (m["G"][t] == np.iinfo(np.int32).min).all()
+                continue
+            win = np.lib.stride_tricks.sliding_window_view(page.astype(np.int64) - 128, (n_h, kw))
+            G = np.einsum("yxjk,jk->yx", win, q[:n_h, :kw])
+            sub = fits[: G.shape[0], : G.shape[1]]
+            assert np.array_equal(m["G"][t][: G.shape[0], : G.shape[1]][sub], G[sub]) and (m["G"][t][~fits] == np.iinfo(np.int32).min).all()
+        # the window form of the model (focr_debug_prefilter) on a few of the page's windows: the same d, the same sim
+        for k, c in enumerate(m["classes"]):
+            n_w, n_h = int(c["n_w"]), int(c["n_h"])
+            pts = [(int(rng.integers(1, r_h - n_h)), int(rng.integers(1, r_w - n_w))) for _ in range(12)]
+            sub = bank.subset([t for t in range(T) if int(m["templates"][t, 0]) == k])
+            ts = [t for t in range(T) if int(m["templates"][t, 0]) == k]
+            wins = np.stack([page[y:y + n_h, x:x + n_w].reshape(-1) for y, x in pts])
+            if len({(int(o["n_w"]), int(o["n_h"])) for o in m["classes"] if int(o["super"]) == int(c["super"])}) > 1 or (not drop and n_w <= 8):
+                continue  # the class's K layout (hence nothing else) depends on its neighbours in the bank: compare whole-bank runs only
+            sim, d, _ = _model(sub, wins, n_w, n_h, thr, drop)
+            for i, (y, x) in enumerate(pts):
+                for j, t in enumerate(ts):
+                    if not m["templates"][t, 2]:
+                        continue
+                    assert d[i, j] == int(m["G"][t, y, x]) + (int(m["plane"][k, y, x]) << int(c["shift"]))
+                    assert (np.isnan(sim[i, j]) and np.isnan(m["sim"][t, y, x])) or sim[i, j] == m["sim"][t, y, x]
+
+
+@pytest.mark.parametrize("case_id", list(PC.CASES))
+def test_gpu_prefilter_cases_are_not_vacuous(case_id):
+    """Check E of tests/test_gpu_prefilter_model.py from the model alone, before any GPU time is spent: every case has emitting pairs,
+    candidates that do not emit, pairs just under the threshold (-S < d <= 0) and blank as well as live statistics tiles — and the
+    model flags every emitting pair.  (Thresholds beyond the planes' clamp pass nothing or everything: no pair is near them.)"""
+    case, bank, pages = PC.build(case_id)
+    models = [PC.model(case, bank, pg, ("plane", "G", "sim")) for pg in pages]
+    v = PC.vacuity(case, bank, pages, models)
+    print(case_id, v)
+    assert v["missed"] == 0, v
+    assert v["blank_tiles"] > 0 and v["live_tiles"] > 0, v
+    if not case.get("vacuous_ok"):
+        assert v["emit"] > 0 and v["cand_no_emit"] > 0 and v["near"] > 0, v
+    if case_id in PC.ODD_MTILES:  # (from the model's planes here; from the device's in tests/test_gpu_prefilter_model.py)
+        assert any(n % 4 for n in v["live_mtiles"]), v
+    got = {(int(c["n_w"]), int(c["n_h"])): (int(c["keep_w"]), int(c["layout"]), int(c["ksteps"]), int(c["super"]), int(c["plane_slot"]) >= 0) for c in models[0]["classes"]}
+    assert got == PC.EXPECT[case_id], (case_id, got)  # the kernel paths the case is there for
+    slots = sorted(int(c["plane_slot"]) for c in models[0]["classes"] if c["plane_slot"] >= 0)
+    assert slots == sorted(set(slots))  # every class that has a plane has its own
