@@ -119,6 +119,7 @@ HIP_SYMBOLS = {
     "focr_ctx_set_scan_cus": (C.c_int, [C.c_void_p, C.c_uint]),
     "focr_ctx_set_prefilter": (C.c_int, [C.c_void_p, C.c_int]),
     "focr_debug_force_split": (C.c_int, [C.c_void_p, C.c_int]),
+    "focr_debug_device_bytes": (C.c_size_t, []),
     "focr_debug_set_tail_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "focr_debug_phase_stamps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "focr_debug_set_stats_form": (C.c_int, [C.c_void_p, C.c_int]),

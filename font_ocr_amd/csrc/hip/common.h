@@ -10,9 +10,12 @@
 #include <string>
 #include <vector>
 
+#include "devmem.h"
 #include "focr_ncc.h"
 
 namespace focr {
+
+struct VerifyMeta;  // mfma_common.h
 
 // ---- geometry of one size class -------------------------------------------
 // A size class is the set of templates that share (n_w, n_h); window statistics
@@ -40,7 +43,7 @@ struct SizeClass {
 // pass: their N-tiles are concatenated; only the C-in table (negL) changes from class to class.
 struct SuperClass {
     uint32_t layout, ksteps;
-    std::vector<uint32_t> classes;     // indices into focr_ctx::classes
+    std::vector<uint32_t> classes;     // indices into focr_ctx::bank.classes
     std::vector<uint32_t> tile_first;  // first N-tile of each class inside the super-class
     uint32_t n_tiles;
     size_t q_offset, tg_offset;
@@ -159,16 +162,34 @@ struct focr_ctx {
     bool tail_full_chip = false;        // the executor says nothing scans behind this batch (focr_pipe_end_of_stream / _announce_last): its tail may take every CU (rows2_verify)
     std::string err;
 
-    // bank
+    // bank: everything focr_bank_upload builds.  Replaced as a whole (ctx.hip: c->bank = {}), so an array added here cannot leak.
+    struct Bank {
+        std::vector<focr_template_t> h_templates;
+        std::vector<focr::SizeClass> classes;
+        std::vector<focr::TemplateConst> h_tconst;         // class-ordered
+        focr::DevArray<focr::TemplateConst> d_tconst;      // class-ordered
+        focr::DevArray<uint32_t> d_direct_bank;            // class-ordered, [maxh][ndw] dwords each
+        std::vector<size_t> direct_bank_off;               // dword offset per class
+        focr::DevArray<int8_t> d_qbank;                    // quantised i8 templates for the MFMA prefilter (per-lane B layout)
+        focr::DevArray<uint32_t> d_tglobal;                // class-ordered -> global template index, 0xffffffff = never emits
+        focr::DevArray<uint32_t> d_order_of;               // global template index -> class-ordered index
+        std::vector<double> mfma_c_scale, mfma_e_max, mfma_rho_max;  // per class: quantisation scale, max rounding-error norm, max norm of a unit template's dropped column
+        focr::DevArray<uint8_t> d_needles;                 // dense needles (class-ordered, for verify)
+        std::vector<uint32_t> h_needle_off;                // class-ordered byte offsets into d_needles
+        focr::DevArray<uint32_t> d_needle_off;
+        focr::DevArray<uint8_t> d_needles16;               // class-ordered, n_h rows of 16 bytes each (verify operand)
+        focr::DevArray<uint32_t> d_needle16_row;           // class-ordered first row index into d_needles16
+        focr::DevArray<focr::VerifyMeta> d_vmeta;          // by GLOBAL template index (mfma_common.h): what the verify needs about a template, 32 B
+        // the verify operand once more, ordered by GLOBAL template index, for banks that do not fit the LDS whole: a chunk of
+        // consecutive templates is then one contiguous piece (verify_chunks_kernel, rows.hip)
+        focr::DevArray<uint8_t> d_vrows_t;                 // rows of vrow_bytes each (12 when every template is at most 12 px wide, else 16), by global index
+        focr::DevArray<focr::VerifyMeta> d_vmeta_t;        // VerifyMeta by global index whose row0 counts rows of d_vrows_t
+        std::vector<uint32_t> h_vrow0_t;                   // [n_templates + 1] first row of every template in d_vrows_t
+        uint32_t vrow_bytes = 0;                           // 0: no such copy (a template wider than 16 px)
+        focr::DevArray<uint32_t> d_t_w, d_t_h, d_t_letter;  // by global template index
+    } bank;
     size_t n_templates = 0;
-    std::vector<focr_template_t> h_templates;
-    std::vector<focr::SizeClass> classes;
     std::vector<focr::SuperClass> supers;
-    std::vector<focr::TemplateConst> h_tconst;  // class-ordered
-    focr::TemplateConst *d_tconst = nullptr;    // class-ordered
-    uint32_t *d_direct_bank = nullptr;          // class-ordered, [maxh][ndw] dwords each
-    std::vector<size_t> direct_bank_off;        // dword offset per class
-    int8_t *d_qbank = nullptr;                  // quantised i8 templates for the MFMA prefilter (per-lane B layout)
     bool column_drop = true;                    // bound the last column of 9- / 13-wide classes instead of multiplying it (takes effect at the next bank upload)
     std::vector<uint32_t> mfma_slot;            // per class-ordered template: its slot inside its class's N-tiles (tile = slot / 16)
     // ---- result sizes (ctx.hip: finish_results) ----
@@ -176,10 +197,10 @@ struct focr_ctx {
     // grids and buffers.  Exact mode reads the counts between the phases (as round 1 did); estimated mode (same bank,
     // geometry, threshold, cap as the previous scan) bounds them by the previous scan's counts + a margin (4 .. 20 %), launches everything
     // without waiting, and reads all sizes once at the end; a count above its bound redoes the batch in exact mode.
-    uint64_t *d_res = nullptr;   // [0] candidates [1] hits [2] matches [3] lines << 32 | chars [4] overflow flag [7] scratch count
+    focr::DevArray<uint64_t> d_res;  // 8 values: [0] candidates [1] hits [2] matches [3] lines << 32 | chars [4] overflow flag [7] scratch count
     uint64_t *h_res = nullptr;   // pinned copy
     uint32_t *h_live = nullptr;  // pinned copy of the live M-tile counts (d_counter + 8 ..), 40 entries
-    const uint64_t *d_n_hits = nullptr;  // device-side number of hits of the last scan
+    const uint64_t *d_n_hits = nullptr;  // view, not an owner: the device-side number of hits of the last scan (in d_res, or in scan_pos)
     size_t ub_hits = 0;                  // the bound its buffers were sized for
     uint64_t n_hits_raw_u64 = 0;
     bool sizes_pending = false, post_pending = false, estimated = false, estimates_enabled = true;
@@ -195,97 +216,84 @@ struct focr_ctx {
     int dbg_stats_form = 0;  // tests / A-B: 1 = the LDS-tiled statistics kernel for every class (focr_debug_set_stats_form; 0: the register form where it applies)
     uint32_t dbg_grid_num = 0, dbg_grid_den = 0;  // tests: the tail's persistent kernels on num / den times their workgroups (focr_debug_set_tail_grid; 0: as designed)
     int prefilter = 0;                          // FOCR_PREFILTER_*: auto / plane kernel / legacy kernel (focr_ctx_set_prefilter)
-    uint16_t *d_planes = nullptr;               // threshold planes, int16: [super-class][value][page][Lrows][Lpitch] (mfma_common.h)
-    size_t plane_values = 0;
-    uint32_t *d_tglobal = nullptr;              // class-ordered -> global template index, 0xffffffff = never emits
-    uint32_t *d_order_of = nullptr;             // global template index -> class-ordered index
-    std::vector<double> mfma_c_scale, mfma_e_max, mfma_rho_max;  // per class: quantisation scale, max rounding-error norm, max norm of a unit template's dropped column
-    uint8_t *d_needles = nullptr;               // dense needles (class-ordered, for verify)
-    std::vector<uint32_t> h_needle_off;         // class-ordered byte offsets into d_needles
-    uint32_t *d_needle_off = nullptr;
-    uint8_t *d_needles16 = nullptr;             // class-ordered, n_h rows of 16 bytes each (verify operand)
-    uint32_t *d_needle16_row = nullptr;         // class-ordered first row index into d_needles16
-    void *d_vmeta = nullptr;                    // VerifyMeta by GLOBAL template index (mfma_common.h): what the verify needs about a template, 32 B
-    // the verify operand once more, ordered by GLOBAL template index, for banks that do not fit the LDS whole: a chunk of
-    // consecutive templates is then one contiguous piece (verify_chunks_kernel, rows.hip)
-    uint32_t *d_vrows_t = nullptr;              // rows of vrow_bytes each (12 when every template is at most 12 px wide, else 16), by global index
-    void *d_vmeta_t = nullptr;                  // VerifyMeta by global index whose row0 counts rows of d_vrows_t
-    std::vector<uint32_t> h_vrow0_t;            // [n_templates + 1] first row of every template in d_vrows_t
-    uint32_t vrow_bytes = 0;                    // 0: no such copy (a template wider than 16 px)
-    uint32_t *d_t_w = nullptr, *d_t_h = nullptr, *d_t_letter = nullptr;  // by global template index
+    focr::DevArray<uint16_t> d_planes;          // threshold planes, int16: [super-class][value][page][Lrows][Lpitch] (mfma_common.h); exact, grow-only
 
-    // pages: [n_pages][rows_alloc][pitch] ink-high u8, zero padded
-    size_t n_pages = 0, r_w = 0, r_h = 0, pitch = 0, rows_alloc = 0;
-    size_t pages_capacity = 0;  // pages d_pages was allocated for (>= n_pages)
+    // pages: the resident set the scans read, and the executor's second set (pipe.hip, focr_pipe_prefetch): the NEXT batch of a
+    // lane is ingested into `alt`, on the lane's copy stream, while the lane still scans `pages`; the two change places when that
+    // batch starts (pages_alt_swap, ctx.hip)
+    struct PageSet {  // [capacity][rows_alloc][pitch] ink-high u8, zero padded (ctx.hip: page_set_alloc)
+        focr::DevArray<uint8_t> u8;
+        focr::DevArray<uint8_t> i8;  // the same pages as int8 (ink - 128, i.e. byte ^ 0x80; padding = 0x80): the MFMA prefilter's window operand,
+                                     // written at ingest so that the scan kernels need no v_xor per fragment dword
+        size_t capacity = 0, r_w = 0, r_h = 0, pitch = 0, rows_alloc = 0;  // capacity: pages the arrays were allocated for
+        bool holds(size_t n, size_t w, size_t h) const { return u8 && r_w == w && r_h == h && n <= capacity; }
+    } pages, alt;
+    size_t n_pages = 0;         // pages of the batch (<= pages.capacity)
     unsigned n_cus = 0;         // compute units of the device (read once, focr_ctx_create)
     unsigned scan_cus = 0;      // CUs the persistent scan kernel may occupy, 0 = all (focr_ctx_set_scan_cus)
-    uint8_t *d_pages = nullptr;
-    uint8_t *d_pages_i8 = nullptr;  // the same pages as int8 (ink - 128, i.e. byte ^ 0x80; padding = 0x80): the MFMA prefilter's window operand,
-                                    // written at ingest so that the scan kernels need no v_xor per fragment dword
-    uint8_t *d_stage = nullptr;  // device staging for uploads
-    size_t stage_bytes = 0;
-    // the executor's second page set (pipe.hip, focr_pipe_prefetch): the NEXT batch of a lane is ingested here, on the lane's copy
-    // stream, while the lane still scans d_pages; the two sets change places when that batch starts (pages_alt_swap, ctx.hip)
-    struct PageSet {
-        uint8_t *u8 = nullptr, *i8 = nullptr;
-        size_t capacity = 0, r_w = 0, r_h = 0, pitch = 0, rows_alloc = 0;
-    } alt;
+    focr::DevArray<uint8_t> d_stage;  // device staging for uploads (exact)
 
-    // scan results
+    // scan results (every reserve waits for the context's stream first)
     size_t sub_p0 = 0, sub_np = 0;  // page range the scan pipeline is currently working on (normally the whole batch)
     focr::KeyFmt fmt{};
     bool scanned = false;
     uint32_t cap = FOCR_MAX_MATCHES;
-    size_t hit_capacity = 0;     // entries in d_hit_keys / d_hit_sims
-    uint64_t *d_hit_keys = nullptr, *d_hit_keys_alt = nullptr;
-    float *d_hit_sims = nullptr, *d_hit_sims_alt = nullptr;
-    uint32_t *d_counter = nullptr;  // u64 [0] hits, u64 [1] candidates, u32 [8..47] live M-tile counts, then the scan kernels' item queues
+    focr::DevArray<uint64_t> d_hit_keys, d_hit_keys_alt;  // the four hit arrays have one length (reserve_hits, scan_direct.hip)
+    focr::DevArray<float> d_hit_sims, d_hit_sims_alt;
+    focr::DevArray<uint32_t> d_counter;  // COUNTER_BYTES: u64 [0] hits, u64 [1] candidates, u32 [8..47] live M-tile counts, then the scan kernels' item queues
     uint32_t scan_queues_used = 0;  // item queues handed out since the last reset (launch_scan_mfma)
-    size_t cand_capacity = 0, cand_alt_capacity = 0;  // entries in d_cand / d_cand_alt
-    uint64_t *d_cand = nullptr, *d_cand_alt = nullptr;
+    focr::DevArray<uint64_t> d_cand, d_cand_alt;
     bool ordered = false;  // the scan path already produced d_matches (MFMA path); order_hits is skipped
-    int32_t *d_L = nullptr;  // prefilter thresholds [class][page][r_h][pitchL]
-    size_t L_values = 0;
-    void *d_sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
+    focr::DevArray<int32_t> d_L;  // prefilter thresholds [class][page][r_h][pitchL]
+    focr::DevArray<uint8_t> d_sort_tmp;  // rocPRIM's temporary storage
     size_t n_hits_raw = 0;    // hits before the cap
     size_t n_cand = 0;
-    uint32_t *d_seg_count = nullptr;   // [n_pages*T] capped counts
-    uint64_t *d_seg_start = nullptr;   // [n_pages*T] start in the sorted arrays
-    uint64_t *d_seg_offset = nullptr;  // [n_pages*T + 1] CSR offsets of the capped lists
-    size_t seg_alloc = 0;
-    focr_match_t *d_matches = nullptr;  // capped, ordered by (page, template, y, x)
-    // all hits (before the cap) in process_hits order (page, y, x, t); d_keep[i] = survives its (page, template) cap
+    focr::DevArray<uint32_t> d_seg_count;   // [n_pages*T] capped counts
+    focr::DevArray<uint64_t> d_seg_start;   // [n_pages*T] start in the sorted arrays
+    focr::DevArray<uint64_t> d_seg_offset;  // [n_pages*T + 1] CSR offsets of the capped lists
+    focr::DevArray<focr_match_t> d_matches;  // capped, ordered by (page, template, y, x); Grow::eighth
+    // views, not owners: all hits (before the cap) in process_hits order (page, y, x, t), in the hit arrays or in acc_hkeys / acc_hsims
     uint64_t *d_hkeys = nullptr;
     float *d_hsims = nullptr;
     size_t n_hits = 0;
-    size_t matches_alloc = 0;
     size_t n_matches = 0;
 
-    // process_hits results (device-resident; copied to the host on focr_get_lines)
-    struct DevBuf {  // grow-only device scratch
-        void *p = nullptr;
-        size_t bytes = 0;
-        void *ensure(focr_ctx *c, size_t want);
-        void *ensure_keep(focr_ctx *c, size_t want, size_t keep_bytes);
-        void release();
-    };
-    DevBuf scan_flags, scan_pos, scan_live, scan_live_list;
+    // grow-only scratch (Grow::quarter at every reserve).  scan_flags / scan_pos and ord_k2 / ord_v are bytes: their readers disagree
+    // about the type (u64 flags and positions in scan_split and the legacy tail, u32 slots / f32 similarities in rows.hip; u64 keys /
+    // f32 values in order.hip's sorting form, u32 tables in its counting form)
+    focr::DevArray<uint8_t> scan_flags, scan_pos, scan_live;
+    focr::DevArray<uint64_t> scan_live_list;
     // row path of the tail (rows.hip): candidates bucketed by page row, sorted + verified per row
     focr::RowHist row_hist{};   // what the scan kernels' flush path counts into (cnt == nullptr: legacy tail)
-    DevBuf rows_hits, rows_hbase, rows_big;
+    focr::DevArray<uint32_t> rows_hits, rows_hbase, rows_big;
     uint32_t row_cap = 0;       // per-row candidate capacity the row kernel was instantiated for in the last scan
     int tail_mode = 1;          // focr_ctx_set_row_tail(): 0 = the legacy tail (radix sort + verify + compaction), 1 = hits-first row tail
                                 // (verify in flush order, hits bucketed + sorted: the default)
-    DevBuf ord_k2, ord_k2_alt, ord_v, ord_v_alt, ord_keep;
-    DevBuf acc_matches, acc_seg_count, acc_hkeys, acc_hsims;  // split-batch mode: results appended sub-batch by sub-batch
-    DevBuf post_line_be;
-    DevBuf post_keep, post_choice, post_owner, post_packed, post_scanned, post_page_off, post_line_off, post_chars;
+    focr::DevArray<uint8_t> ord_k2, ord_k2_alt, ord_v, ord_v_alt, ord_keep;
+    // split-batch mode: results appended sub-batch by sub-batch (scan_split: Grow::half, what is there kept)
+    focr::DevArray<focr_match_t> acc_matches;
+    focr::DevArray<uint64_t> acc_hkeys;
+    focr::DevArray<float> acc_hsims;
+    focr::DevArray<uint32_t> acc_seg_count;
+
+    // process_hits results (device-resident; copied to the host on focr_get_lines)
+    focr::DevArray<uint32_t> post_line_be, post_choice;
+    focr::DevArray<uint8_t> post_keep;
+    focr::DevArray<uint64_t> post_packed, post_scanned, post_page_off, post_line_off;
+    focr::DevArray<focr_hit_t> post_chars;
     bool lines_on_host = false;
     bool processed = false;
     size_t n_chars = 0, n_lines = 0;
     std::vector<uint64_t> h_page_line_off, h_line_char_off;
     std::vector<focr_hit_t> h_chars;
+
+    template <typename T>
+    bool scratch(focr::DevArray<T> &a, size_t want) {  // grow-only scratch: Grow::quarter, behind the context's stream
+        return a.reserve(want, focr::Grow::quarter, &stream) == hipSuccess;
+    }
+
+    template <typename T>
+    int upload(focr::DevArray<T> &a, const T *src, size_t n, size_t at_least = 0);  // a bank array from host memory (ctx.hip: fail() on error)
 
     hipEvent_t ev[8] = {};
     float ms[6] = {};
@@ -304,6 +312,14 @@ namespace focr {
 
 void set_global_error(const std::string &s);
 int fail(focr_ctx *ctx, int code, const std::string &msg);
+
+}  // namespace focr
+template <typename T>
+int focr_ctx::upload(focr::DevArray<T> &a, const T *src, size_t n, size_t at_least) {
+    const hipError_t e = a.upload(src, n, at_least);
+    return e == hipSuccess ? FOCR_OK : focr::fail(this, FOCR_ERR_NO_DEVICE, std::string("bank upload: hipMalloc / hipMemcpy: ") + hipGetErrorString(e));
+}
+namespace focr {
 
 #define FOCR_HIP(ctx, expr)                                                                       \
     do {                                                                                          \

@@ -19,9 +19,9 @@
 
 namespace focr {
 
-int sort_pairs_u64_f32(focr_ctx *c, uint64_t *&keys, uint64_t *&keys_alt, float *&vals, float *&vals_alt, size_t n,
+int sort_pairs_u64_f32(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, DevArray<float> &vals, DevArray<float> &vals_alt, size_t n,
                        unsigned end_bit);
-int ensure_hit_capacity(focr_ctx *c, size_t want);
+int reserve_hits(focr_ctx *c, size_t want);
 
 typedef int v4i_c __attribute__((ext_vector_type(4), aligned(1)));
 typedef int v2i_c __attribute__((ext_vector_type(2), aligned(1)));
@@ -112,12 +112,11 @@ struct CompatState {
     // uploaded again only when its content (or geometry) changed
     uint64_t h_ref = 0, h_ps = 0, h_pr = 0, h_se = 0;
     size_t res_w = 0, res_h = 0;
-    uint8_t *d_ref = nullptr, *d_needle = nullptr;
-    uint32_t *d_ps = nullptr;
-    double *d_pr = nullptr;
-    uint16_t *d_se = nullptr;
-    focr_match_t *d_out = nullptr;
-    size_t px_alloc = 0, rows_alloc = 0, out_alloc = 0;
+    DevArray<uint8_t> d_ref, d_needle;  // (all exact growth, behind the context's stream)
+    DevArray<uint32_t> d_ps;
+    DevArray<double> d_pr;
+    DevArray<uint16_t> d_se;
+    DevArray<focr_match_t> d_out;
     // the call's hits land in page-locked host memory as the kernel finds them (a call emits tens to a few thousand): ONE wait per
     // call, then a host sort of those few — instead of a count read-back, a device radix sort (a dozen launches), a pack kernel and
     // a second read-back.  A call with more hits than the block holds takes the device path.
@@ -125,11 +124,11 @@ struct CompatState {
     uint64_t *h_keys = nullptr;
     float *h_sims = nullptr;
     static constexpr size_t PIN_HITS = 1u << 16;
-    // deliberately no destructor: thread-exit / process-exit order against the HIP runtime's own
-    // teardown is unspecified, and the driver reclaims everything anyway.
 };
 
-static thread_local CompatState tl;
+// One per thread, deliberately never destroyed (its arrays stay live, and counted, past the thread's end): thread-exit / process-exit
+// order against the HIP runtime's own teardown is unspecified, and the driver reclaims everything anyway.
+static thread_local CompatState &tl = *new CompatState;
 
 template <int N>
 static size_t compat_call(uint8_t *reference, size_t r_w, size_t r_h, uint8_t *needle_u8, size_t n_w, size_t n_h,
@@ -166,30 +165,18 @@ static size_t compat_call(uint8_t *reference, size_t r_w, size_t r_h, uint8_t *n
     } while (0)
     CK(hipSetDevice(c->device));
     const size_t npx = r_w * r_h;
-    if (tl.px_alloc < npx) {
-        CK(hipStreamSynchronize(c->stream));
-        for (void *p : {(void *)tl.d_ref, (void *)tl.d_ps, (void *)tl.d_pr})
-            if (p) (void)hipFree(p);
-        tl.d_ref = nullptr;
-        tl.d_ps = nullptr;
-        tl.d_pr = nullptr;
-        tl.px_alloc = 0;
-        CK(hipMalloc(&tl.d_ref, npx + 64));
+    if (tl.d_ref.cap < npx + 64 || tl.d_ps.cap < npx || tl.d_pr.cap < npx) {  // any of the three (a grow that failed half-way leaves them unequal)
+        tl.res_w = tl.res_h = 0;  // nothing is resident from here on, whether the grow succeeds or not
+        CK(tl.d_ref.reserve(npx + 64, Grow::exact, &c->stream));
         CK(hipMemsetAsync(tl.d_ref, 0, npx + 64, c->stream));
-        CK(hipMalloc(&tl.d_ps, npx * 4));
-        CK(hipMalloc(&tl.d_pr, npx * 8));
-        tl.px_alloc = npx;
-        tl.res_w = tl.res_h = 0;  // nothing resident in the new buffers
+        CK(tl.d_ps.reserve(npx, Grow::exact, &c->stream));
+        CK(tl.d_pr.reserve(npx, Grow::exact, &c->stream));
     }
-    if (tl.rows_alloc < r_h) {
-        CK(hipStreamSynchronize(c->stream));
-        if (tl.d_se) (void)hipFree(tl.d_se);
-        tl.d_se = nullptr;
-        CK(hipMalloc(&tl.d_se, r_h * 2 * sizeof(uint16_t)));
-        tl.rows_alloc = r_h;
+    if (tl.d_se.cap < r_h * 2) {
         tl.res_w = tl.res_h = 0;
+        CK(tl.d_se.reserve(r_h * 2, Grow::exact, &c->stream));
     }
-    if (!tl.d_needle) CK(hipMalloc(&tl.d_needle, 16 * 65536));
+    CK(tl.d_needle.reserve(16 * 65536, Grow::exact, nullptr));
     if (n_h * N > 16 * 65536) {
         set_global_error("ncc_N_u8: needle too tall");
         return 0;
@@ -239,8 +226,8 @@ static size_t compat_call(uint8_t *reference, size_t r_w, size_t r_h, uint8_t *n
         CK(hipMemsetAsync(c->d_counter, 0, 64 * sizeof(uint32_t), c->stream));
         dim3 grid((unsigned)((r_w + 255) / 256), (unsigned)(y_searches - 1));
         hipLaunchKernelGGL((compat_kernel<N>), grid, dim3(256), 0, c->stream, tl.d_ref, (uint32_t)r_w, (uint32_t)r_h,
-                           reinterpret_cast<const uint32_t *>(tl.d_needle), (uint32_t)n_w, (uint32_t)n_h, tl.d_ps, tl.d_pr, tl.d_se, (double)s_n, n_recip,
-                           rnorm_n, (double)threshold, tl.h_keys, tl.h_sims, (unsigned long long *)c->d_counter, (unsigned long long)CompatState::PIN_HITS);
+                           tl.d_needle.as<const uint32_t>(), (uint32_t)n_w, (uint32_t)n_h, tl.d_ps, tl.d_pr, tl.d_se, (double)s_n, n_recip,
+                           rnorm_n, (double)threshold, tl.h_keys, tl.h_sims, c->d_counter.as<unsigned long long>(), (unsigned long long)CompatState::PIN_HITS);
         CK(hipGetLastError());
         CK(hipMemcpyAsync(tl.h_count, c->d_counter, 8, hipMemcpyDeviceToHost, c->stream));
         CK(hipStreamSynchronize(c->stream));
@@ -261,20 +248,20 @@ static size_t compat_call(uint8_t *reference, size_t r_w, size_t r_h, uint8_t *n
         }
         // more hits than the block holds (very low thresholds): the device path below counts and sorts them all
     }
-    size_t want = std::max<size_t>(c->hit_capacity, std::max<size_t>(1u << 16, n_out * 4));
+    size_t want = std::max<size_t>(c->d_hit_keys.cap, std::max<size_t>(1u << 16, n_out * 4));
     for (int attempt = 0; attempt < 3; attempt++) {
-        if (ensure_hit_capacity(c, want) != FOCR_OK) return 0;
+        if (reserve_hits(c, want) != FOCR_OK) return 0;
         CK(hipMemsetAsync(c->d_counter, 0, 64 * sizeof(uint32_t), c->stream));
         dim3 grid((unsigned)((r_w + 255) / 256), (unsigned)(y_searches - 1));
         hipLaunchKernelGGL((compat_kernel<N>), grid, dim3(256), 0, c->stream, tl.d_ref, (uint32_t)r_w, (uint32_t)r_h,
-                           reinterpret_cast<const uint32_t *>(tl.d_needle), (uint32_t)n_w, (uint32_t)n_h, tl.d_ps, tl.d_pr, tl.d_se, (double)s_n, n_recip,
-                           rnorm_n, (double)threshold, c->d_hit_keys, c->d_hit_sims, (unsigned long long *)c->d_counter,
-                           (unsigned long long)c->hit_capacity);
+                           tl.d_needle.as<const uint32_t>(), (uint32_t)n_w, (uint32_t)n_h, tl.d_ps, tl.d_pr, tl.d_se, (double)s_n, n_recip,
+                           rnorm_n, (double)threshold, c->d_hit_keys, c->d_hit_sims, c->d_counter.as<unsigned long long>(),
+                           (unsigned long long)c->d_hit_keys.cap);
         CK(hipGetLastError());
         unsigned long long cnt = 0;
         CK(hipMemcpyAsync(&cnt, c->d_counter, 8, hipMemcpyDeviceToHost, c->stream));
         CK(hipStreamSynchronize(c->stream));
-        if (cnt > c->hit_capacity) {
+        if (cnt > c->d_hit_keys.cap) {
             want = (size_t)cnt + 1024;
             continue;
         }
@@ -282,13 +269,7 @@ static size_t compat_call(uint8_t *reference, size_t r_w, size_t r_h, uint8_t *n
         if (sort_pairs_u64_f32(c, c->d_hit_keys, c->d_hit_keys_alt, c->d_hit_sims, c->d_hit_sims_alt, (size_t)cnt, 32) != FOCR_OK)
             return 0;
         const size_t keep = std::min<size_t>((size_t)cnt, n_out);  // src/ncc.cpp:225-227, 371-373
-        if (tl.out_alloc < keep) {
-            CK(hipStreamSynchronize(c->stream));
-            if (tl.d_out) (void)hipFree(tl.d_out);
-            tl.d_out = nullptr;
-            CK(hipMalloc(&tl.d_out, keep * sizeof(focr_match_t)));
-            tl.out_alloc = keep;
-        }
+        CK(tl.d_out.reserve(keep, Grow::exact, &c->stream));
         hipLaunchKernelGGL(compat_pack, dim3((unsigned)((keep + 255) / 256)), dim3(256), 0, c->stream, c->d_hit_keys,
                            c->d_hit_sims, keep, tl.d_out);
         CK(hipGetLastError());

@@ -1,4 +1,5 @@
 // ctx.hip — context, bank upload, resident pages, result read-back (include/focr_ncc.h layer 2).
+// The context's device memory is DevArray members (devmem.h, common.h): nothing here frees a buffer by name.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -119,108 +120,14 @@ __global__ void widen_u32_to_u64(const uint32_t *__restrict__ in, size_t n, uint
     if (i <= n) out[i] = i < n ? in[i] : 0;
 }
 
-template <typename T>
-static void free_dev(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 static void free_bank(focr_ctx *c) {
-    free_dev(c->d_tconst);
-    free_dev(c->d_direct_bank);
-    free_dev(c->d_qbank);
-    free_dev(c->d_tglobal);
-    free_dev(c->d_order_of);
-    c->mfma_c_scale.clear();
-    c->mfma_e_max.clear();
-    c->mfma_rho_max.clear();
-    free_dev(c->d_needles);
-    free_dev(c->d_needle_off);
-    free_dev(c->d_needles16);
-    free_dev(c->d_needle16_row);
-    free_dev(c->d_vmeta);
-    free_dev(c->d_vrows_t);
-    free_dev(c->d_vmeta_t);
-    c->h_vrow0_t.clear();
-    c->vrow_bytes = 0;
-    free_dev(c->d_t_w);
-    free_dev(c->d_t_h);
-    free_dev(c->d_t_letter);
-    c->classes.clear();
-    c->h_tconst.clear();
-    c->h_templates.clear();
-    c->direct_bank_off.clear();
-    c->h_needle_off.clear();
+    c->bank = {};
     c->n_templates = 0;
-}
-
-static void free_results(focr_ctx *c) {
-    free_dev(c->d_hit_keys);
-    free_dev(c->d_hit_keys_alt);
-    free_dev(c->d_hit_sims);
-    free_dev(c->d_hit_sims_alt);
-    free_dev(c->d_cand);
-    free_dev(c->d_cand_alt);
-    c->scan_flags.release();
-    c->scan_pos.release();
-    c->scan_live.release();
-    c->scan_live_list.release();
-    for (auto *b : {&c->ord_k2, &c->ord_k2_alt, &c->ord_v, &c->ord_v_alt, &c->ord_keep, &c->acc_matches, &c->acc_seg_count,
-                    &c->acc_hkeys, &c->acc_hsims, &c->rows_hits, &c->rows_hbase, &c->rows_big})
-        b->release();
-    free_dev(c->d_L);
-    free_dev(c->d_planes);
-    free_dev(c->d_sort_tmp);
-    free_dev(c->d_seg_count);
-    free_dev(c->d_seg_start);
-    free_dev(c->d_seg_offset);
-    free_dev(c->d_matches);
-    c->post_line_be.release();
-    for (auto *b : {&c->post_keep, &c->post_choice, &c->post_owner, &c->post_packed, &c->post_scanned, &c->post_page_off,
-                    &c->post_line_off, &c->post_chars})
-        b->release();
-    c->hit_capacity = c->cand_capacity = c->cand_alt_capacity = c->L_values = c->plane_values = c->sort_tmp_bytes = c->seg_alloc = c->matches_alloc = 0;
-    c->scanned = c->processed = false;
 }
 
 }  // namespace focr
 
 using namespace focr;
-
-void *focr_ctx::DevBuf::ensure(focr_ctx *c, size_t want) {
-    if (want <= bytes && p) return p;
-    (void)hipStreamSynchronize(c->stream);
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    size_t grow = want + want / 4 + 256;
-    if (hipMalloc(&p, grow) != hipSuccess) {
-        p = nullptr;
-        return nullptr;
-    }
-    bytes = grow;
-    return p;
-}
-
-// grow while preserving the first `keep_bytes` bytes
-void *focr_ctx::DevBuf::ensure_keep(focr_ctx *c, size_t want, size_t keep_bytes) {
-    if (want <= bytes && p) return p;
-    (void)hipStreamSynchronize(c->stream);
-    void *q = nullptr;
-    size_t grow = want + want / 2 + 256;
-    if (hipMalloc(&q, grow) != hipSuccess) return nullptr;
-    if (p && keep_bytes) (void)hipMemcpy(q, p, keep_bytes, hipMemcpyDeviceToDevice);
-    if (p) (void)hipFree(p);
-    p = q;
-    bytes = grow;
-    return p;
-}
-
-void focr_ctx::DevBuf::release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-}
 
 void focr_ctx::launch_begin(const char *name, uint32_t n_t, uint64_t alg, uint64_t issued) {
     focr_launch_info_t li{};
@@ -292,9 +199,9 @@ int focr_ctx_create(int device, focr_ctx_t **out) {
             if (!b && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(b, c->stream);
         }
         for (auto &ev : c->ev) FOCR_HIP(c, hipEventCreate(&ev));
-        FOCR_HIP(c, hipMalloc(&c->d_counter, COUNTER_BYTES));
+        FOCR_HIP(c, c->d_counter.reserve(COUNTER_BYTES / sizeof(uint32_t), Grow::exact, nullptr));
         FOCR_HIP(c, hipMemsetAsync(c->d_counter, 0, COUNTER_BYTES, c->stream));
-        FOCR_HIP(c, hipMalloc((void **)&c->d_res, 8 * sizeof(uint64_t)));
+        FOCR_HIP(c, c->d_res.reserve(8, Grow::exact, nullptr));
         FOCR_HIP(c, hipMemsetAsync(c->d_res, 0, 8 * sizeof(uint64_t), c->stream));
         FOCR_HIP(c, hipHostMalloc((void **)&c->h_res, 8 * sizeof(uint64_t), hipHostMallocDefault));
         FOCR_HIP(c, hipHostMalloc((void **)&c->h_live, 40 * sizeof(uint32_t), hipHostMallocDefault));
@@ -315,15 +222,6 @@ void focr_ctx_destroy(focr_ctx_t *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_bank(c);
-    free_results(c);
-    free_dev(c->d_pages);
-    free_dev(c->d_pages_i8);
-    free_dev(c->alt.u8);
-    free_dev(c->alt.i8);
-    free_dev(c->d_stage);
-    free_dev(c->d_counter);
-    free_dev(c->d_res);
     if (c->h_res) (void)hipHostFree(c->h_res);
     if (c->h_live) (void)hipHostFree(c->h_live);
     for (auto &ev : c->ev)
@@ -331,8 +229,10 @@ void focr_ctx_destroy(focr_ctx_t *c) {
     for (auto &ev : c->launch_events)
         if (ev) (void)hipEventDestroy(ev);
     if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // every device array of the context dies here, behind the wait above
 }
+
+size_t focr_debug_device_bytes(void) { return g_device_bytes.load(); }
 
 int focr_ctx_set_scan_cus(focr_ctx_t *c, unsigned max_cus) {
     if (!c) return fail(c, FOCR_ERR_INVALID, "focr_ctx_set_scan_cus: null context");
@@ -416,7 +316,7 @@ int focr_debug_planes(focr_ctx_t *c, uint16_t *out, size_t capacity, size_t *n_v
     if (!c || !n_values) return FOCR_ERR_INVALID;
     FOCR_HIP(c, hipSetDevice(c->device));
     if (int rc = focr_sync(c)) return rc;
-    *n_values = c->plane_values;
+    *n_values = c->d_planes.cap;
     if (!out) return FOCR_OK;
     if (capacity < *n_values) return fail(c, FOCR_ERR_INVALID, "focr_debug_planes: buffer too small");
     if (*n_values) FOCR_HIP(c, hipMemcpy(out, c->d_planes, *n_values * 2, hipMemcpyDeviceToHost));
@@ -437,7 +337,7 @@ int focr_debug_candidates(focr_ctx_t *c, uint32_t *out, size_t capacity, size_t 
     *n = c->n_cand;
     if (!out) return FOCR_OK;
     if (capacity < c->n_cand) return fail(c, FOCR_ERR_INVALID, "focr_debug_candidates: buffer too small");
-    if (c->n_cand > c->cand_capacity) return fail(c, FOCR_ERR_STATE, "focr_debug_candidates: internal: more candidates than the list holds");
+    if (c->n_cand > c->d_cand.cap) return fail(c, FOCR_ERR_STATE, "focr_debug_candidates: internal: more candidates than the list holds");
     FOCR_HIP(c, hipSetDevice(c->device));
     std::vector<uint64_t> keys(c->n_cand);
     if (c->n_cand) {
@@ -500,19 +400,14 @@ int focr_bank_upload(focr_ctx_t *c, const focr_template_t *templates, size_t n_t
         th[t] = templates[t].n_h;
         tl[t] = templates[t].letter;
     }
-    auto up = [&](auto *&dptr, const void *src, size_t bytes) -> int {
-        FOCR_HIP(c, hipMalloc((void **)&dptr, bytes ? bytes : 16));
-        FOCR_HIP(c, hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice));
-        return FOCR_OK;
-    };
-    int rc;
-    if ((rc = up(c->d_tconst, c->h_tconst.data(), c->h_tconst.size() * sizeof(TemplateConst)))) return rc;
-    if ((rc = up(c->d_direct_bank, direct.data(), direct.size() * 4))) return rc;
-    if ((rc = up(c->d_needles, dense.data(), dense.size()))) return rc;
-    if ((rc = up(c->d_needle_off, c->h_needle_off.data(), c->h_needle_off.size() * 4))) return rc;
-    if ((rc = up(c->d_t_w, tw.data(), tw.size() * 4))) return rc;
-    if ((rc = up(c->d_t_h, th.data(), th.size() * 4))) return rc;
-    if ((rc = up(c->d_t_letter, tl.data(), tl.size() * 4))) return rc;
+    focr_ctx::Bank &b = c->bank;
+    if (int rc = c->upload(b.d_tconst, b.h_tconst.data(), b.h_tconst.size())) return rc;
+    if (int rc = c->upload(b.d_direct_bank, direct.data(), direct.size())) return rc;
+    if (int rc = c->upload(b.d_needles, dense.data(), dense.size())) return rc;
+    if (int rc = c->upload(b.d_needle_off, b.h_needle_off.data(), b.h_needle_off.size())) return rc;
+    if (int rc = c->upload(b.d_t_w, tw.data(), tw.size())) return rc;
+    if (int rc = c->upload(b.d_t_h, th.data(), th.size())) return rc;
+    if (int rc = c->upload(b.d_t_letter, tl.data(), tl.size())) return rc;
     return build_mfma_bank(c, dense.data());
 }
 
@@ -523,22 +418,22 @@ namespace focr {
 void bank_host_prepare(focr_ctx *c, const focr_template_t *templates, size_t n_templates, const uint8_t *needles,
                        std::vector<uint32_t> &direct, std::vector<uint8_t> &dense) {
     c->n_templates = n_templates;
-    c->h_templates.assign(templates, templates + n_templates);
+    c->bank.h_templates.assign(templates, templates + n_templates);
 
     // size classes in order of first appearance
     std::vector<std::vector<uint32_t>> members;
     for (size_t t = 0; t < n_templates; t++) {
         size_t k = 0;
-        for (; k < c->classes.size(); k++)
-            if (c->classes[k].n_w == templates[t].n_w && c->classes[k].n_h == templates[t].n_h) break;
-        if (k == c->classes.size()) {
+        for (; k < c->bank.classes.size(); k++)
+            if (c->bank.classes[k].n_w == templates[t].n_w && c->bank.classes[k].n_h == templates[t].n_h) break;
+        if (k == c->bank.classes.size()) {
             SizeClass sc{};
             sc.n_w = templates[t].n_w;
             sc.n_h = templates[t].n_h;
             sc.ndw = (sc.n_w + 3) / 4;
             sc.tall = sc.n_h > 32 || sc.n_w > 16;
             sc.maxh = sc.tall ? sc.n_h : (sc.n_h <= 16 ? 16 : 32);
-            c->classes.push_back(sc);
+            c->bank.classes.push_back(sc);
             members.emplace_back();
         }
         members[k].push_back((uint32_t)t);
@@ -555,12 +450,12 @@ void bank_host_prepare(focr_ctx *c, const focr_template_t *templates, size_t n_t
         });
 
     uint32_t first = 0;
-    for (size_t k = 0; k < c->classes.size(); k++) {
-        SizeClass &sc = c->classes[k];
+    for (size_t k = 0; k < c->bank.classes.size(); k++) {
+        SizeClass &sc = c->bank.classes[k];
         sc.first = first;
         sc.n_templates = (uint32_t)members[k].size();
         first += sc.n_templates;
-        c->direct_bank_off.push_back(direct.size());
+        c->bank.direct_bank_off.push_back(direct.size());
         const uint32_t n = sc.n_w * sc.n_h;
         for (uint32_t t : members[k]) {
             const uint8_t *nd = needles + templates[t].offset;
@@ -579,7 +474,7 @@ void bank_host_prepare(focr_ctx *c, const focr_template_t *templates, size_t n_t
             tc.index = t;
             tc.n_w = sc.n_w;
             tc.n_h = sc.n_h;
-            c->h_tconst.push_back(tc);
+            c->bank.h_tconst.push_back(tc);
             // direct-kernel layout: maxh rows of ndw dwords, zero padded
             for (uint32_t j = 0; j < sc.maxh; j++)
                 for (uint32_t k4 = 0; k4 < sc.ndw; k4++) {
@@ -590,11 +485,44 @@ void bank_host_prepare(focr_ctx *c, const focr_template_t *templates, size_t n_t
                     }
                     direct.push_back(w);
                 }
-            c->h_needle_off.push_back((uint32_t)dense.size());
+            c->bank.h_needle_off.push_back((uint32_t)dense.size());
             dense.insert(dense.end(), nd, nd + n);
         }
     }
 }
+}  // namespace focr
+
+namespace focr {
+
+// A fresh set of n pages of r_w x r_h, all paper: every row is followed by >= 64 zero bytes, every page by 48 zero rows (0x80 in
+// the int8 copy), written on stream s.  The caller has made sure nothing reads the set's previous arrays.  On failure the set is empty.
+static hipError_t page_set_alloc(focr_ctx::PageSet &ps, size_t n, size_t r_w, size_t r_h, hipStream_t s) {
+    ps = {};
+    const size_t pitch = (r_w + 64 + 63) / 64 * 64, rows_alloc = r_h + 48, bytes = n * rows_alloc * pitch;
+    if (ps.u8.reserve(bytes, Grow::exact, nullptr) || ps.i8.reserve(bytes, Grow::exact, nullptr)) {
+        ps = {};
+        return hipErrorOutOfMemory;  // (whatever the allocator said: the callers report "hipMalloc failed", as they always did)
+    }
+    hipError_t e = hipMemsetAsync(ps.u8, 0, bytes, s);
+    if (e == hipSuccess) e = hipMemsetAsync(ps.i8, 0x80, bytes, s);  // paper (0) as int8
+    if (e != hipSuccess) {
+        ps = {};
+        return e;
+    }
+    ps.capacity = n, ps.r_w = r_w, ps.r_h = r_h, ps.pitch = pitch, ps.rows_alloc = rows_alloc;
+    return hipSuccess;
+}
+
+// `count` tight luma8 pages at d_src (device memory) -> pages [first, first + count) of the set, on stream s
+static hipError_t page_set_ingest(const focr_ctx::PageSet &ps, const uint8_t *d_src, size_t first, size_t count, int invert, hipStream_t s) {
+    const size_t n_rows = count * ps.r_h;
+    const unsigned blocks = (unsigned)std::min<size_t>(n_rows, (size_t)1 << 20);
+    const int dwords = ps.r_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_src) & 3) == 0;
+    hipLaunchKernelGGL(ingest_pages, dim3(blocks), dim3(64), 0, s, d_src, ps.u8.p, ps.i8.p, (uint32_t)ps.r_w, (uint32_t)ps.r_h, ps.pitch, ps.rows_alloc, first,
+                       n_rows, invert, dwords);
+    return hipGetLastError();
+}
+
 }  // namespace focr
 
 extern "C" {
@@ -605,42 +533,19 @@ int focr_pages_alloc(focr_ctx_t *c, size_t n_pages, size_t r_w, size_t r_h) {
         return fail(c, FOCR_ERR_INVALID, "focr_pages_alloc: page side above 65535 px");
     if (n_pages > 65535) return fail(c, FOCR_ERR_INVALID, "focr_pages_alloc: more than 65535 pages per batch");
     FOCR_HIP(c, hipSetDevice(c->device));
-    if (c->d_pages && c->r_w == r_w && c->r_h == r_h && n_pages <= c->pages_capacity) {
-        // same geometry, no more pages than before: keep the buffer (its zero padding is never written)
-        c->scanned = c->processed = false;
-        c->n_pages = n_pages;
-        return FOCR_OK;
-    }
-    FOCR_HIP(c, hipStreamSynchronize(c->stream));
-    free_dev(c->d_pages);
-    free_dev(c->d_pages_i8);
-    c->pages_capacity = 0;
     c->scanned = c->processed = false;
     c->n_pages = n_pages;
-    c->r_w = r_w;
-    c->r_h = r_h;
-    c->pitch = (r_w + 64 + 63) / 64 * 64;  // >= 64 zero bytes right of every row
-    c->rows_alloc = r_h + 48;              // >= 48 zero rows below every page
-    size_t bytes = c->n_pages * c->rows_alloc * c->pitch;
-    if (hipMalloc(&c->d_pages, bytes) != hipSuccess || hipMalloc(&c->d_pages_i8, bytes) != hipSuccess) {
-        free_dev(c->d_pages);
-        free_dev(c->d_pages_i8);
-        c->n_pages = 0;
-        return fail(c, FOCR_ERR_NOMEM, "focr_pages_alloc: hipMalloc failed");
-    }
-    c->pages_capacity = n_pages;
-    FOCR_HIP(c, hipMemsetAsync(c->d_pages, 0, bytes, c->stream));
-    FOCR_HIP(c, hipMemsetAsync(c->d_pages_i8, 0x80, bytes, c->stream));  // paper (0) as int8
+    if (c->pages.holds(n_pages, r_w, r_h)) return FOCR_OK;  // same geometry, no more pages than before: keep the buffer (its zero padding is never written)
+    FOCR_HIP(c, hipStreamSynchronize(c->stream));
+    const hipError_t e = page_set_alloc(c->pages, n_pages, r_w, r_h, c->stream);
+    if (e != hipSuccess) c->n_pages = 0;
+    if (e == hipErrorOutOfMemory) return fail(c, FOCR_ERR_NOMEM, "focr_pages_alloc: hipMalloc failed");
+    FOCR_HIP(c, e);
     return FOCR_OK;
 }
 
 static int ingest(focr_ctx *c, const uint8_t *d_src, size_t first, size_t count, int invert) {
-    const size_t n_rows = count * c->r_h;
-    const unsigned blocks = (unsigned)std::min<size_t>(n_rows, (size_t)1 << 20);
-    const int dwords = c->r_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_src) & 3) == 0;
-    hipLaunchKernelGGL(ingest_pages, dim3(blocks), dim3(64), 0, c->stream, d_src, c->d_pages, c->d_pages_i8, (uint32_t)c->r_w, (uint32_t)c->r_h, c->pitch,
-                       c->rows_alloc, first, n_rows, invert, dwords);
-    FOCR_HIP(c, hipGetLastError());
+    FOCR_HIP(c, page_set_ingest(c->pages, d_src, first, count, invert, c->stream));
     c->scanned = c->processed = false;
     c->sizes_pending = c->post_pending = false;  // results of the previous batch are gone with its pages
     return FOCR_OK;
@@ -651,64 +556,28 @@ static int ingest(focr_ctx *c, const uint8_t *d_src, size_t first, size_t count,
 namespace focr {
 
 // The executor's early ingest (pipe.hip): n_pages tight luma8 pages at d_luma (device memory) become the ALTERNATE page set of the
-// context, on stream s — not the context's own: the context may be scanning d_pages meanwhile.  The caller orders s behind the
-// arrival of d_luma and the context's stream behind s (an event) before pages_alt_swap makes the set current.  The alternate set
+// context, on stream s — not the context's own: the context may be scanning its current pages meanwhile.  The caller orders s behind
+// the arrival of d_luma and the context's stream behind s (an event) before pages_alt_swap makes the set current.  The alternate set
 // is free whenever this is called: it was current two batches ago, and every batch of a lane ends with focr_sync.
 int pages_alt_ingest(focr_ctx *c, const void *d_luma, size_t n_pages, size_t r_w, size_t r_h, int invert, hipStream_t s) {
     if (!c || !d_luma || !n_pages || !r_w || !r_h || r_w > 65535 || r_h > 65535 || n_pages > 65535)
         return fail(nullptr, FOCR_ERR_INVALID, "pages_alt_ingest: bad arguments");
     // (errors go to the process-wide message only: the context's own belongs to the lane's thread, which may be running a batch)
-    focr_ctx::PageSet &a = c->alt;
-    if (!a.u8 || a.r_w != r_w || a.r_h != r_h || a.capacity < n_pages) {
-        free_dev(a.u8);  // (hipFree waits for the device: a change of geometry, not the steady state)
-        free_dev(a.i8);
-        a = focr_ctx::PageSet{};
-        const size_t pitch = (r_w + 64 + 63) / 64 * 64, rows_alloc = r_h + 48;  // as focr_pages_alloc
-        const size_t bytes = n_pages * rows_alloc * pitch;
-        if (hipMalloc(&a.u8, bytes) != hipSuccess || hipMalloc(&a.i8, bytes) != hipSuccess) {
-            free_dev(a.u8);
-            free_dev(a.i8);
-            return fail(nullptr, FOCR_ERR_NOMEM, "pages_alt_ingest: hipMalloc failed");
-        }
-        a.capacity = n_pages;
-        a.r_w = r_w;
-        a.r_h = r_h;
-        a.pitch = pitch;
-        a.rows_alloc = rows_alloc;
-        FOCR_HIP((focr_ctx *)nullptr, hipMemsetAsync(a.u8, 0, bytes, s));
-        FOCR_HIP((focr_ctx *)nullptr, hipMemsetAsync(a.i8, 0x80, bytes, s));  // paper (0) as int8
+    if (!c->alt.holds(n_pages, r_w, r_h)) {  // (freeing the old set waits for the device: a change of geometry, not the steady state)
+        const hipError_t e = page_set_alloc(c->alt, n_pages, r_w, r_h, s);
+        if (e == hipErrorOutOfMemory) return fail(nullptr, FOCR_ERR_NOMEM, "pages_alt_ingest: hipMalloc failed");
+        FOCR_HIP((focr_ctx *)nullptr, e);
     }
-    const size_t n_rows = n_pages * r_h;
-    const unsigned blocks = (unsigned)std::min<size_t>(n_rows, (size_t)1 << 20);
-    const int dwords = r_w % 4 == 0 && (reinterpret_cast<uintptr_t>(d_luma) & 3) == 0;
-    hipLaunchKernelGGL(ingest_pages, dim3(blocks), dim3(64), 0, s, (const uint8_t *)d_luma, a.u8, a.i8, (uint32_t)r_w, (uint32_t)r_h, a.pitch, a.rows_alloc, (size_t)0,
-                       n_rows, invert, dwords);
-    FOCR_HIP((focr_ctx *)nullptr, hipGetLastError());
+    FOCR_HIP((focr_ctx *)nullptr, page_set_ingest(c->alt, (const uint8_t *)d_luma, 0, n_pages, invert, s));
     return FOCR_OK;
 }
 
 // The alternate set becomes the context's pages (n_pages of r_w x r_h, as ingested by pages_alt_ingest), the previous pages the
 // alternate set.  Host state only: the caller has ordered the context's stream behind the ingest.
 int pages_alt_swap(focr_ctx *c, size_t n_pages, size_t r_w, size_t r_h) {
-    focr_ctx::PageSet &a = c->alt;
-    if (!a.u8 || a.r_w != r_w || a.r_h != r_h || a.capacity < n_pages) return fail(c, FOCR_ERR_STATE, "pages_alt_swap: no such alternate page set");
-    focr_ctx::PageSet cur;
-    cur.u8 = c->d_pages;
-    cur.i8 = c->d_pages_i8;
-    cur.capacity = c->pages_capacity;
-    cur.r_w = c->r_w;
-    cur.r_h = c->r_h;
-    cur.pitch = c->pitch;
-    cur.rows_alloc = c->rows_alloc;
-    c->d_pages = a.u8;
-    c->d_pages_i8 = a.i8;
-    c->pages_capacity = a.capacity;
-    c->r_w = a.r_w;
-    c->r_h = a.r_h;
-    c->pitch = a.pitch;
-    c->rows_alloc = a.rows_alloc;
+    if (!c->alt.holds(n_pages, r_w, r_h)) return fail(c, FOCR_ERR_STATE, "pages_alt_swap: no such alternate page set");
+    std::swap(c->pages, c->alt);
     c->n_pages = n_pages;
-    a = cur;
     c->scanned = c->processed = false;
     c->sizes_pending = c->post_pending = false;  // results of the previous batch are gone with its pages
     return FOCR_OK;
@@ -720,18 +589,13 @@ extern "C" {
 
 int focr_pages_upload(focr_ctx_t *c, size_t first, size_t count, const uint8_t *luma, int invert) {
     if (!c || !luma) return fail(c, FOCR_ERR_INVALID, "focr_pages_upload: bad arguments");
-    if (!c->d_pages) return fail(c, FOCR_ERR_STATE, "focr_pages_upload: call focr_pages_alloc first");
+    if (!c->pages.u8) return fail(c, FOCR_ERR_STATE, "focr_pages_upload: call focr_pages_alloc first");
     if (first + count > c->n_pages) return fail(c, FOCR_ERR_INVALID, "focr_pages_upload: page range out of bounds");
     FOCR_HIP(c, hipSetDevice(c->device));
-    const size_t page_bytes = c->r_w * c->r_h;
+    const size_t page_bytes = c->pages.r_w * c->pages.r_h;
     const size_t chunk_pages = std::max<size_t>(1, (256u << 20) / page_bytes);
     size_t need = std::min(count, chunk_pages) * page_bytes;
-    if (c->stage_bytes < need) {
-        FOCR_HIP(c, hipStreamSynchronize(c->stream));
-        free_dev(c->d_stage);
-        FOCR_HIP(c, hipMalloc(&c->d_stage, need));
-        c->stage_bytes = need;
-    }
+    FOCR_HIP(c, c->d_stage.reserve(need, Grow::exact, &c->stream));
     for (size_t done = 0; done < count; done += chunk_pages) {
         size_t n = std::min(chunk_pages, count - done);
         FOCR_HIP(c, hipMemcpyAsync(c->d_stage, luma + done * page_bytes, n * page_bytes, hipMemcpyHostToDevice, c->stream));
@@ -771,7 +635,7 @@ void focr_host_unregister(void *p) {
 
 int focr_pages_upload_device(focr_ctx_t *c, size_t first, size_t count, const void *d_luma, int invert) {
     if (!c || !d_luma) return fail(c, FOCR_ERR_INVALID, "focr_pages_upload_device: bad arguments");
-    if (!c->d_pages) return fail(c, FOCR_ERR_STATE, "focr_pages_upload_device: call focr_pages_alloc first");
+    if (!c->pages.u8) return fail(c, FOCR_ERR_STATE, "focr_pages_upload_device: call focr_pages_alloc first");
     if (first + count > c->n_pages) return fail(c, FOCR_ERR_INVALID, "focr_pages_upload_device: page range out of bounds");
     FOCR_HIP(c, hipSetDevice(c->device));
     return ingest(c, (const uint8_t *)d_luma, first, count, invert);
@@ -785,8 +649,8 @@ static int scan_split(focr_ctx *c, Run &run) {
     size_t match_total = 0, hit_total = 0, raw_total = 0, cand_total = 0;
     float ms_acc[6] = {0, 0, 0, 0, 0, 0};
     uint64_t issued = 0;
-    uint32_t *acc_cnt = (uint32_t *)c->acc_seg_count.ensure(c, (n_seg_all + 1) * 4);
-    if (!acc_cnt) return fail(c, FOCR_ERR_NOMEM, "focr_scan: hipMalloc failed");
+    if (!c->scratch(c->acc_seg_count, n_seg_all + 1)) return fail(c, FOCR_ERR_NOMEM, "focr_scan: hipMalloc failed");
+    uint32_t *acc_cnt = c->acc_seg_count;
     size_t np = std::max<size_t>(1, c->n_pages / 2);
     for (size_t p0 = 0; p0 < c->n_pages;) {
         np = std::min(np, c->n_pages - p0);
@@ -798,19 +662,22 @@ static int scan_split(focr_ctx *c, Run &run) {
         if (rc) return rc;
         // append: matches, per-call counts, kept hits
         const size_t nm = c->n_matches, nh = c->n_hits;
-        focr_match_t *am = (focr_match_t *)c->acc_matches.ensure_keep(c, (match_total + nm + 1) * sizeof(focr_match_t), match_total * sizeof(focr_match_t));
-        uint64_t *ak = (uint64_t *)c->acc_hkeys.ensure_keep(c, (hit_total + nm + 1) * 8, hit_total * 8);
-        float *as = (float *)c->acc_hsims.ensure_keep(c, (hit_total + nm + 1) * 4, hit_total * 4);
-        if (!am || !ak || !as) return fail(c, FOCR_ERR_NOMEM, "focr_scan: hipMalloc failed");
+        if (c->acc_matches.reserve(match_total + nm + 1, Grow::half, &c->stream, match_total) ||
+            c->acc_hkeys.reserve(hit_total + nm + 1, Grow::half, &c->stream, hit_total) ||
+            c->acc_hsims.reserve(hit_total + nm + 1, Grow::half, &c->stream, hit_total))
+            return fail(c, FOCR_ERR_NOMEM, "focr_scan: hipMalloc failed");
+        focr_match_t *am = c->acc_matches;
+        uint64_t *ak = c->acc_hkeys;
+        float *as = c->acc_hsims;
         if (nm) FOCR_HIP(c, hipMemcpyAsync(am + match_total, c->d_matches, nm * sizeof(focr_match_t), hipMemcpyDeviceToDevice, c->stream));
         FOCR_HIP(c, hipMemcpyAsync(acc_cnt + p0 * T, c->d_seg_count, np * T * 4, hipMemcpyDeviceToDevice, c->stream));
         if (nh) {
-            uint64_t *f64 = (uint64_t *)c->scan_flags.ensure(c, (nh + 1) * 8), *pos = (uint64_t *)c->scan_pos.ensure(c, (nh + 1) * 8);
-            if (!f64 || !pos) return fail(c, FOCR_ERR_NOMEM, "focr_scan: hipMalloc failed");
+            if (!c->scratch(c->scan_flags, (nh + 1) * 8) || !c->scratch(c->scan_pos, (nh + 1) * 8)) return fail(c, FOCR_ERR_NOMEM, "focr_scan: hipMalloc failed");
+            uint64_t *f64 = c->scan_flags.as<uint64_t>(), *pos = c->scan_pos.as<uint64_t>();
             const unsigned nb = (unsigned)((nh + 255) / 256);
-            hipLaunchKernelGGL(widen_u8_to_u64, dim3(nb), dim3(256), 0, c->stream, (const uint8_t *)c->ord_keep.p, nh, f64);
+            hipLaunchKernelGGL(widen_u8_to_u64, dim3(nb), dim3(256), 0, c->stream, c->ord_keep.p, nh, f64);
             if ((rc = exclusive_scan_u64(c, f64, pos, nh))) return rc;
-            hipLaunchKernelGGL(append_kept_hits, dim3(nb), dim3(256), 0, c->stream, c->d_hkeys, c->d_hsims, (const uint8_t *)c->ord_keep.p,
+            hipLaunchKernelGGL(append_kept_hits, dim3(nb), dim3(256), 0, c->stream, c->d_hkeys, c->d_hsims, c->ord_keep.p,
                                pos, nh, ak + hit_total, as + hit_total);
             FOCR_HIP(c, hipGetLastError());
         }
@@ -830,16 +697,12 @@ static int scan_split(focr_ctx *c, Run &run) {
         int rc = exclusive_scan_u64(c, count64, c->d_seg_offset, n_seg_all + 1);
         if (rc) return rc;
         FOCR_HIP(c, hipMemcpyAsync(c->d_seg_count, acc_cnt, n_seg_all * 4, hipMemcpyDeviceToDevice, c->stream));
-        uint8_t *keep = (uint8_t *)c->ord_keep.ensure(c, hit_total + 1);
-        if (!keep) return fail(c, FOCR_ERR_NOMEM, "focr_scan: hipMalloc failed");
-        FOCR_HIP(c, hipMemsetAsync(keep, 1, hit_total + 1, c->stream));
+        if (!c->scratch(c->ord_keep, hit_total + 1)) return fail(c, FOCR_ERR_NOMEM, "focr_scan: hipMalloc failed");
+        FOCR_HIP(c, hipMemsetAsync(c->ord_keep, 1, hit_total + 1, c->stream));
         FOCR_HIP(c, hipStreamSynchronize(c->stream));
-        std::swap(c->d_matches, *(focr_match_t **)&c->acc_matches.p);  // hand the accumulated list over (capacities swap too)
-        size_t acc_cap = c->acc_matches.bytes / sizeof(focr_match_t);
-        c->acc_matches.bytes = c->matches_alloc * sizeof(focr_match_t);
-        c->matches_alloc = acc_cap;
-        c->d_hkeys = (uint64_t *)c->acc_hkeys.p;
-        c->d_hsims = (float *)c->acc_hsims.p;
+        std::swap(c->d_matches, c->acc_matches);  // hand the accumulated list over
+        c->d_hkeys = c->acc_hkeys;
+        c->d_hsims = c->acc_hsims;
         // the accumulated hit count as the device-side value process_hits reads
         c->n_hits_raw_u64 = hit_total;
         FOCR_HIP(c, hipMemcpyAsync(c->d_res + 7, &c->n_hits_raw_u64, 8, hipMemcpyHostToDevice, c->stream));
@@ -991,7 +854,7 @@ extern "C" {
 int focr_scan(focr_ctx_t *c, float threshold, uint32_t cap, int mode) {
     if (!c) return FOCR_ERR_INVALID;
     if (!c->n_templates) return fail(c, FOCR_ERR_STATE, "focr_scan: no bank uploaded");
-    if (!c->d_pages) return fail(c, FOCR_ERR_STATE, "focr_scan: no pages resident");
+    if (!c->pages.u8) return fail(c, FOCR_ERR_STATE, "focr_scan: no pages resident");
     if (cap == 0) return fail(c, FOCR_ERR_INVALID, "focr_scan: cap must be >= 1 (src/ncc.cpp:43-46)");
     if (mode != FOCR_SCAN_MFMA && mode != FOCR_SCAN_DIRECT && mode != FOCR_SCAN_RUST) return fail(c, FOCR_ERR_INVALID, "focr_scan: bad mode");
     if (std::isnan(threshold)) threshold = INFINITY;  // `sim > NaN` is never true in the reference (src/ncc.cpp:362-366): no hits
@@ -1001,18 +864,18 @@ int focr_scan(focr_ctx_t *c, float threshold, uint32_t cap, int mode) {
     c->scan_mode = mode;
     // algorithmic MACs, SURVEY.md section 8(d): true template area x searched windows
     uint64_t macs = 0;
-    for (const SizeClass &sc : c->classes) {
-        if (sc.n_w > c->r_w || sc.n_h > c->r_h) continue;
-        uint64_t wx = c->r_w - sc.n_w, wy = c->r_h - sc.n_h;  // x in [1, r_w-n_w], y in [1, r_h-n_h]
+    for (const SizeClass &sc : c->bank.classes) {
+        if (sc.n_w > c->pages.r_w || sc.n_h > c->pages.r_h) continue;
+        uint64_t wx = c->pages.r_w - sc.n_w, wy = c->pages.r_h - sc.n_h;  // x in [1, r_w-n_w], y in [1, r_h-n_h]
         macs += wx * wy * (uint64_t)sc.n_w * sc.n_h * sc.n_templates;
     }
     c->counters[2] = macs * c->n_pages;
-    c->fmt = key_format(c->n_templates, c->r_w, c->r_h, c->n_pages);
+    c->fmt = key_format(c->n_templates, c->pages.r_w, c->pages.r_h, c->n_pages);
     // Size estimates are reused only for the very same setup (bank, batch geometry, threshold, cap, prefilter)
     uint32_t tb;
     memcpy(&tb, &threshold, 4);
     uint64_t sig = 1469598103934665603ull;
-    for (uint64_t v : {(uint64_t)c->bank_hash, (uint64_t)c->device, (uint64_t)c->tail_mode, (uint64_t)c->n_pages, (uint64_t)c->r_w, (uint64_t)c->r_h, (uint64_t)tb, (uint64_t)cap, (uint64_t)mode,
+    for (uint64_t v : {(uint64_t)c->bank_hash, (uint64_t)c->device, (uint64_t)c->tail_mode, (uint64_t)c->n_pages, (uint64_t)c->pages.r_w, (uint64_t)c->pages.r_h, (uint64_t)tb, (uint64_t)cap, (uint64_t)mode,
                        (uint64_t)c->prefilter})
         sig = (sig ^ v) * 1099511628211ull;
     if (sig != c->est_sig) c->est.reset();
@@ -1084,28 +947,21 @@ int focr_last_counters(focr_ctx_t *c, uint64_t out[4]) {
 int focr_debug_rnorm(focr_ctx_t *c, const uint32_t *s, const uint64_t *s2, const uint32_t *n, size_t n_items, double *out) {
     if (!c || !s || !s2 || !n || !out) return fail(c, FOCR_ERR_INVALID, "focr_debug_rnorm: bad arguments");
     FOCR_HIP(c, hipSetDevice(c->device));
-    uint32_t *ds = nullptr, *dn = nullptr;
-    uint64_t *ds2 = nullptr;
-    double *dout = nullptr;
-    auto run = [&]() -> int {
-        FOCR_HIP(c, hipMalloc(&ds, n_items * 4));
-        FOCR_HIP(c, hipMalloc(&dn, n_items * 4));
-        FOCR_HIP(c, hipMalloc(&ds2, n_items * 8));
-        FOCR_HIP(c, hipMalloc(&dout, n_items * 8));
-        FOCR_HIP(c, hipMemcpyAsync(ds, s, n_items * 4, hipMemcpyHostToDevice, c->stream));
-        FOCR_HIP(c, hipMemcpyAsync(dn, n, n_items * 4, hipMemcpyHostToDevice, c->stream));
-        FOCR_HIP(c, hipMemcpyAsync(ds2, s2, n_items * 8, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(debug_rnorm_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, c->stream, ds, ds2, dn, n_items,
-                           dout);
-        FOCR_HIP(c, hipGetLastError());
-        FOCR_HIP(c, hipMemcpyAsync(out, dout, n_items * 8, hipMemcpyDeviceToHost, c->stream));
-        FOCR_HIP(c, hipStreamSynchronize(c->stream));
-        return FOCR_OK;
-    };
-    const int rc = run();
-    for (void *p : {(void *)ds, (void *)dn, (void *)ds2, (void *)dout})
-        if (p) (void)hipFree(p);
-    return rc;
+    DevArray<uint32_t> ds, dn;
+    DevArray<uint64_t> ds2;
+    DevArray<double> dout;
+    FOCR_HIP(c, ds.reserve(n_items, Grow::exact, nullptr));
+    FOCR_HIP(c, dn.reserve(n_items, Grow::exact, nullptr));
+    FOCR_HIP(c, ds2.reserve(n_items, Grow::exact, nullptr));
+    FOCR_HIP(c, dout.reserve(n_items, Grow::exact, nullptr));
+    FOCR_HIP(c, hipMemcpyAsync(ds, s, n_items * 4, hipMemcpyHostToDevice, c->stream));
+    FOCR_HIP(c, hipMemcpyAsync(dn, n, n_items * 4, hipMemcpyHostToDevice, c->stream));
+    FOCR_HIP(c, hipMemcpyAsync(ds2, s2, n_items * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(debug_rnorm_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, c->stream, ds.p, ds2.p, dn.p, n_items, dout.p);
+    FOCR_HIP(c, hipGetLastError());
+    FOCR_HIP(c, hipMemcpyAsync(out, dout, n_items * 8, hipMemcpyDeviceToHost, c->stream));
+    FOCR_HIP(c, hipStreamSynchronize(c->stream));
+    return FOCR_OK;
 }
 
 }  // extern "C"

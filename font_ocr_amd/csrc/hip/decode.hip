@@ -35,6 +35,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "devmem.h"
 #include "focr_decode.h"
 
 namespace focr_dec {
@@ -532,18 +533,14 @@ struct focr_decoder {
     float origin_y = 0.f, text_size = 0.f, kerning = 0.f;
     int hinting = 0;
     size_t bitmaps_len = 0;
-    DevGlyph *d_glyphs = nullptr;
-    int2 *d_offs = nullptr;
-    uint32_t *d_bitmaps = nullptr;
+    // every device array: exact growth, no stream wait (each call ends with one, so the buffers are idle when the next call grows them)
+    focr::DevArray<DevGlyph> d_glyphs;
+    focr::DevArray<int2> d_offs;
+    focr::DevArray<uint8_t> d_bitmaps;  // dwords (read as uint32_t by the decode kernel, as bytes by the compose kernels)
     // batch buffers (grown on demand)
-    uint8_t *d_pages = nullptr;
-    size_t pages_cap = 0;
-    uint8_t *d_strips = nullptr;
-    size_t strips_cap = 0;
-    uint32_t *d_flags = nullptr, *d_work = nullptr, *d_nchars = nullptr, *d_count = nullptr;
-    size_t slots_cap = 0;
-    uint16_t *d_chars = nullptr;
-    size_t chars_cap = 0;
+    focr::DevArray<uint8_t> d_pages, d_strips;
+    focr::DevArray<uint32_t> d_flags, d_work, d_nchars, d_count;
+    focr::DevArray<uint16_t> d_chars;
     // results of the last run
     std::vector<focr_decoded_line_t> lines;
     std::vector<uint16_t> chars;
@@ -552,33 +549,25 @@ struct focr_decoder {
     // verify: the table, what the last successful run left for it, buffers, timing
     hipEvent_t ev2 = nullptr, ev3 = nullptr;
     uint32_t n_vglyphs = 0, hmax = 0;
-    VerifyGlyph *d_vglyphs = nullptr;
-    VerifyPhase *d_vphases = nullptr;
+    focr::DevArray<VerifyGlyph> d_vglyphs;
+    focr::DevArray<VerifyPhase> d_vphases;
     bool run_ok = false;
     Geometry run_g{};
     size_t run_pages = 0;
     uint32_t run_x_start = 0;
     const uint8_t *run_src = nullptr;
-    VerifyLine *d_vlines = nullptr;
-    size_t vlines_cap = 0;
-    VerifyRec *d_vrecs = nullptr;
-    size_t vrecs_cap = 0;
-    unsigned long long *d_sums = nullptr;
-    size_t sums_cap = 0;
-    uint8_t *d_rgb = nullptr;
-    size_t rgb_cap = 0;
+    focr::DevArray<VerifyLine> d_vlines;
+    focr::DevArray<VerifyRec> d_vrecs;
+    focr::DevArray<unsigned long long> d_sums;
+    focr::DevArray<uint8_t> d_rgb;
     float last_verify_ms = 0.f;
     uint32_t last_verify_launches = 0;
     // test images: buffers of their own, so that a test call leaves the last run and its verify as they were
     hipEvent_t ev4 = nullptr, ev5 = nullptr;
-    uint8_t *d_tpages = nullptr;
-    size_t tpages_cap = 0;
-    uint32_t *d_tbase = nullptr, *d_trect = nullptr, *d_ttext = nullptr, *d_tflags = nullptr;
-    size_t tbase_cap = 0, trect_cap = 0, ttext_cap = 0, tflags_cap = 0;
-    VerifyRec *d_trecs = nullptr;
-    size_t trecs_cap = 0;
-    VerifyLine *d_tline = nullptr;
-    size_t tline_cap = 0;
+    focr::DevArray<uint8_t> d_tpages;
+    focr::DevArray<uint32_t> d_tbase, d_trect, d_ttext, d_tflags;
+    focr::DevArray<VerifyRec> d_trecs;
+    focr::DevArray<VerifyLine> d_tline;
     float last_test_ms = 0.f;
     uint32_t last_test_launches = 0;
 };
@@ -599,16 +588,17 @@ int dfail(focr_decoder *dec, const std::string &msg) {
         if (e_ != hipSuccess) return dfail(dec, std::string(#call ": ") + hipGetErrorString(e_));    \
     } while (0)
 
-template <class T>
-int grow(focr_decoder *dec, T **p, size_t *cap, size_t want) {
-    if (want <= *cap) return 0;
-    if (*p) DEC_CHECK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    DEC_CHECK(hipMalloc((void **)p, want * sizeof(T)));
-    *cap = want;
-    return 0;
-}
+// exact growth of a batch buffer / a fresh table from host memory, reported as the allocation they are
+#define DEC_GROW(a, want)                                                                                                          \
+    do {                                                                                                                           \
+        hipError_t e_ = (a).reserve((want), focr::Grow::exact, nullptr);                                                           \
+        if (e_ != hipSuccess) return dfail(dec, std::string("hipMalloc((void **)p, want * sizeof(T)): ") + hipGetErrorString(e_)); \
+    } while (0)
+#define DEC_UPLOAD(a, ...)                                                                                          \
+    do {                                                                                                            \
+        hipError_t e_ = (a).upload(__VA_ARGS__);                                                                    \
+        if (e_ != hipSuccess) return dfail(dec, std::string("hipMalloc / hipMemcpy(" #a "): ") + hipGetErrorString(e_)); \
+    } while (0)
 
 // The line slots of a batch as the reference's loop visits them, with image::crop_imm's clamping of every crop.  False
 // for line_advance 0 with a non-empty first crop (the reference never ends).
@@ -645,7 +635,7 @@ int keep_run(focr_decoder *dec, const Geometry &g, const uint8_t *pages, int on_
     const size_t page_bytes = (size_t)g.page_w * g.page_h * n_pages;
     if (!on_device && page_bytes) {
         DEC_CHECK(hipSetDevice(dec->device));
-        if (grow(dec, &dec->d_pages, &dec->pages_cap, page_bytes)) return 1;
+        DEC_GROW(dec->d_pages, page_bytes);
         DEC_CHECK(hipMemcpyAsync(dec->d_pages, pages, page_bytes, hipMemcpyHostToDevice, dec->stream));
         DEC_CHECK(hipStreamSynchronize(dec->stream));
         d_src = dec->d_pages;
@@ -680,16 +670,10 @@ extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
     if (!dec) return;
     (void)hipSetDevice(dec->device);
     if (dec->stream) (void)hipStreamSynchronize(dec->stream);
-    for (void *p : {(void *)dec->d_glyphs, (void *)dec->d_offs, (void *)dec->d_bitmaps, (void *)dec->d_pages, (void *)dec->d_strips,
-                    (void *)dec->d_flags, (void *)dec->d_work, (void *)dec->d_nchars, (void *)dec->d_count, (void *)dec->d_chars,
-                    (void *)dec->d_vglyphs, (void *)dec->d_vphases, (void *)dec->d_vlines, (void *)dec->d_vrecs, (void *)dec->d_sums,
-                    (void *)dec->d_rgb, (void *)dec->d_tpages, (void *)dec->d_tbase, (void *)dec->d_trect, (void *)dec->d_ttext,
-                    (void *)dec->d_tflags, (void *)dec->d_trecs, (void *)dec->d_tline})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : {dec->ev0, dec->ev1, dec->ev2, dec->ev3, dec->ev4, dec->ev5})
         if (e) (void)hipEventDestroy(e);
     if (dec->stream) (void)hipStreamDestroy(dec->stream);
-    delete dec;
+    delete dec;  // every device array of the decoder dies here, behind the wait above
 }
 
 extern "C" const char *focr_decoder_last_error(const focr_decoder_t *dec) { return dec ? dec->err.c_str() : g_dec_err.c_str(); }
@@ -717,15 +701,10 @@ extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font
         dec->inc[i] = s.increment;
         min_inc = std::min(min_inc, s.increment);
     }
-    for (void *p : {(void *)dec->d_glyphs, (void *)dec->d_offs, (void *)dec->d_bitmaps})
-        if (p) DEC_CHECK(hipFree(p));
-    dec->d_glyphs = nullptr, dec->d_offs = nullptr, dec->d_bitmaps = nullptr, dec->n_glyphs = 0;
-    DEC_CHECK(hipMalloc((void **)&dec->d_glyphs, sizeof(DevGlyph) * G));
-    DEC_CHECK(hipMalloc((void **)&dec->d_offs, sizeof(int2) * offs.size()));
-    DEC_CHECK(hipMalloc((void **)&dec->d_bitmaps, std::max<size_t>(font->bitmaps_len, 4)));
-    DEC_CHECK(hipMemcpy(dec->d_glyphs, gl.data(), sizeof(DevGlyph) * G, hipMemcpyHostToDevice));
-    DEC_CHECK(hipMemcpy(dec->d_offs, offs.data(), sizeof(int2) * offs.size(), hipMemcpyHostToDevice));
-    if (font->bitmaps_len) DEC_CHECK(hipMemcpy(dec->d_bitmaps, font->bitmaps, font->bitmaps_len, hipMemcpyHostToDevice));
+    dec->n_glyphs = 0;
+    DEC_UPLOAD(dec->d_glyphs, gl.data(), G);
+    DEC_UPLOAD(dec->d_offs, offs.data(), offs.size());
+    DEC_UPLOAD(dec->d_bitmaps, (const uint8_t *)font->bitmaps, font->bitmaps_len, 4);
     dec->n_glyphs = (uint32_t)G;
     dec->origin_x = font->origin_x;
     dec->min_inc = min_inc;
@@ -772,25 +751,17 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     const size_t page_bytes = page_w * page_h * n_pages;
     const uint8_t *d_src = pages;
     if (!on_device) {
-        if (grow(dec, &dec->d_pages, &dec->pages_cap, std::max<size_t>(page_bytes, 1))) return 1;
+        DEC_GROW(dec->d_pages, std::max<size_t>(page_bytes, 1));
         DEC_CHECK(hipMemcpyAsync(dec->d_pages, pages, page_bytes, hipMemcpyHostToDevice, dec->stream));
         d_src = dec->d_pages;
     }
     const size_t strip_bytes = (size_t)g.stride * g.line_height;
-    if (grow(dec, &dec->d_strips, &dec->strips_cap, strip_bytes * total)) return 1;
-    if (dec->slots_cap < total) {
-        for (uint32_t **p : {&dec->d_flags, &dec->d_work, &dec->d_nchars}) {
-            if (*p) DEC_CHECK(hipFree(*p));
-            *p = nullptr;
-        }
-        dec->slots_cap = 0;
-        DEC_CHECK(hipMalloc((void **)&dec->d_flags, total * 4));
-        DEC_CHECK(hipMalloc((void **)&dec->d_work, total * 4));
-        DEC_CHECK(hipMalloc((void **)&dec->d_nchars, total * 4));
-        dec->slots_cap = total;
-    }
-    if (!dec->d_count) DEC_CHECK(hipMalloc((void **)&dec->d_count, 4));
-    if (grow(dec, &dec->d_chars, &dec->chars_cap, (size_t)g.cap * total)) return 1;
+    DEC_GROW(dec->d_strips, strip_bytes * total);
+    DEC_GROW(dec->d_flags, total);
+    DEC_GROW(dec->d_work, total);
+    DEC_GROW(dec->d_nchars, total);
+    DEC_GROW(dec->d_count, 1);
+    DEC_GROW(dec->d_chars, (size_t)g.cap * total);
 
     DEC_CHECK(hipEventRecord(dec->ev0, dec->stream));
     line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
@@ -799,10 +770,10 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     DEC_CHECK(hipGetLastError());
     if (strip_bytes <= LDS_STRIP_MAX)
         line_decode_kernel<true><<<g.total, 64, strip_bytes, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs,
-                                                                         dec->d_bitmaps, dec->n_glyphs, dec->origin_x, dec->d_nchars, dec->d_chars);
+                                                                         dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs, dec->origin_x, dec->d_nchars, dec->d_chars);
     else
         line_decode_kernel<false><<<g.total, 64, 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs,
-                                                                dec->d_bitmaps, dec->n_glyphs, dec->origin_x, dec->d_nchars, dec->d_chars);
+                                                                dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs, dec->origin_x, dec->d_nchars, dec->d_chars);
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->ev1, dec->stream));
 
@@ -877,13 +848,8 @@ extern "C" int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_veri
         }
     }
     DEC_CHECK(hipSetDevice(dec->device));
-    for (void *p : {(void *)dec->d_vglyphs, (void *)dec->d_vphases})
-        if (p) DEC_CHECK(hipFree(p));
-    dec->d_vglyphs = nullptr, dec->d_vphases = nullptr;
-    DEC_CHECK(hipMalloc((void **)&dec->d_vglyphs, sizeof(VerifyGlyph) * G));
-    DEC_CHECK(hipMalloc((void **)&dec->d_vphases, sizeof(VerifyPhase) * vp.size()));
-    DEC_CHECK(hipMemcpy(dec->d_vglyphs, vg.data(), sizeof(VerifyGlyph) * G, hipMemcpyHostToDevice));
-    DEC_CHECK(hipMemcpy(dec->d_vphases, vp.data(), sizeof(VerifyPhase) * vp.size(), hipMemcpyHostToDevice));
+    DEC_UPLOAD(dec->d_vglyphs, vg.data(), G);
+    DEC_UPLOAD(dec->d_vphases, vp.data(), vp.size());
     dec->hmax = (uint32_t)(y_hi - y_lo);
     dec->n_vglyphs = (uint32_t)G;
     return 0;
@@ -905,12 +871,12 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     const size_t layout_blocks = std::max<size_t>(g.total, n_pages);
     if (layout_blocks > 0x7fffffffu) return dfail(dec, "focr_decoder_verify: too many pages in one batch");
     DEC_CHECK(hipSetDevice(dec->device));
-    if (grow(dec, &dec->d_vlines, &dec->vlines_cap, std::max<size_t>(g.total, 1))) return 1;
-    if (grow(dec, &dec->d_vrecs, &dec->vrecs_cap, std::max<size_t>((size_t)g.total * g.cap, 1))) return 1;
-    if (grow(dec, &dec->d_sums, &dec->sums_cap, n_pages)) return 1;
+    DEC_GROW(dec->d_vlines, std::max<size_t>(g.total, 1));
+    DEC_GROW(dec->d_vrecs, std::max<size_t>((size_t)g.total * g.cap, 1));
+    DEC_GROW(dec->d_sums, n_pages);
     uint8_t *d_rgb = rgb_on_device ? rgb : nullptr;
     if (rgb && !rgb_on_device) {
-        if (grow(dec, &dec->d_rgb, &dec->rgb_cap, std::max<size_t>(px * 3, 1))) return 1;
+        DEC_GROW(dec->d_rgb, std::max<size_t>(px * 3, 1));
         d_rgb = dec->d_rgb;
     }
     DEC_CHECK(hipEventRecord(dec->ev2, dec->stream));
@@ -964,26 +930,26 @@ extern "C" int focr_decoder_test_images(focr_decoder_t *dec, const uint8_t *page
     const uint8_t *d_src = pages;
     const uint32_t *d_base = (const uint32_t *)base_rgba;
     if (!in_on_device) {
-        if (grow(dec, &dec->d_tpages, &dec->tpages_cap, px)) return 1;
+        DEC_GROW(dec->d_tpages, px);
         DEC_CHECK(hipMemcpyAsync(dec->d_tpages, pages, px, hipMemcpyHostToDevice, dec->stream));
         d_src = dec->d_tpages;
         if (base_rgba) {
-            if (grow(dec, &dec->d_tbase, &dec->tbase_cap, px)) return 1;
+            DEC_GROW(dec->d_tbase, px);
             DEC_CHECK(hipMemcpyAsync(dec->d_tbase, base_rgba, px * 4, hipMemcpyHostToDevice, dec->stream));
             d_base = dec->d_tbase;
         }
     }
     uint32_t *d_rect = (uint32_t *)rect_rgba, *d_text = (uint32_t *)text_rgba;
     if (!out_on_device) {
-        if (rect_rgba && grow(dec, &dec->d_trect, &dec->trect_cap, px)) return 1;
-        if (text_rgba && grow(dec, &dec->d_ttext, &dec->ttext_cap, px)) return 1;
+        if (rect_rgba) DEC_GROW(dec->d_trect, px);
+        if (text_rgba) DEC_GROW(dec->d_ttext, px);
         d_rect = rect_rgba ? dec->d_trect : nullptr;
         d_text = text_rgba ? dec->d_ttext : nullptr;
     }
-    if (rect_rgba && grow(dec, &dec->d_tflags, &dec->tflags_cap, std::max<size_t>(total, 1))) return 1;
+    if (rect_rgba) DEC_GROW(dec->d_tflags, std::max<size_t>(total, 1));
     if (text_rgba) {
-        if (grow(dec, &dec->d_trecs, &dec->trecs_cap, dec->n_glyphs)) return 1;
-        if (grow(dec, &dec->d_tline, &dec->tline_cap, 1)) return 1;
+        DEC_GROW(dec->d_trecs, dec->n_glyphs);
+        DEC_GROW(dec->d_tline, 1);
     }
     uint32_t launches = 0;
     DEC_CHECK(hipEventRecord(dec->ev4, dec->stream));
@@ -1021,8 +987,9 @@ extern "C" int focr_decoder_debug_blend(focr_decoder_t *dec, const uint8_t *bg_r
     if (n && (!bg_rgba || !fg_rgba || !out_rgba)) return dfail(dec, "focr_decoder_debug_blend: null buffer");
     if (!n) return 0;
     DEC_CHECK(hipSetDevice(dec->device));
-    uint32_t *d = nullptr;
-    DEC_CHECK(hipMalloc((void **)&d, n * 12));
+    focr::DevArray<uint32_t> buf;  // background, foreground, result
+    DEC_GROW(buf, 3 * n);
+    uint32_t *d = buf;
     hipError_t e = hipMemcpyAsync(d, bg_rgba, n * 4, hipMemcpyHostToDevice, dec->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + n, fg_rgba, n * 4, hipMemcpyHostToDevice, dec->stream);
     if (e == hipSuccess) {
@@ -1033,7 +1000,6 @@ extern "C" int focr_decoder_debug_blend(focr_decoder_t *dec, const uint8_t *bg_r
     if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, d + 2 * n, n * 4, hipMemcpyDeviceToHost, dec->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(dec->stream);
     (void)hipStreamSynchronize(dec->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return dfail(dec, std::string("focr_decoder_debug_blend: ") + hipGetErrorString(e));
     return 0;
 }

@@ -32,39 +32,42 @@ __device__ __forceinline__ uint64_t lower_bound_u64(const uint64_t *__restrict__
     return lo;
 }
 
-static int ensure_sort_tmp(focr_ctx *c, size_t tmp) {
-    if (c->sort_tmp_bytes >= tmp && c->d_sort_tmp) return FOCR_OK;
-    FOCR_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->d_sort_tmp) (void)hipFree(c->d_sort_tmp);
-    c->d_sort_tmp = nullptr;
-    if (hipMalloc(&c->d_sort_tmp, tmp ? tmp : 16) != hipSuccess) return fail(c, FOCR_ERR_NOMEM, "order: hipMalloc failed");
-    c->sort_tmp_bytes = tmp ? tmp : 16;
+// rocPRIM's temporary storage: exact growth; never null, which would make the call a size query
+static int reserve_sort_tmp(focr_ctx *c, size_t tmp) {
+    if (c->d_sort_tmp.reserve(tmp ? tmp : 16, Grow::exact, &c->stream)) return fail(c, FOCR_ERR_NOMEM, "order: hipMalloc failed");
     return FOCR_OK;
 }
 
-int sort_pairs_u64_f32(focr_ctx *c, uint64_t *&keys, uint64_t *&keys_alt, float *&vals, float *&vals_alt, size_t n,
-                       unsigned end_bit) {
-    if (n < 2) return FOCR_OK;
+// The radix sorts go from a buffer into its alternate (n >= 2); the caller then swaps the two
+static int radix_pairs(focr_ctx *c, uint64_t *keys, uint64_t *keys_alt, float *vals, float *vals_alt, size_t n, unsigned end_bit) {
     size_t tmp = 0;
     if (rocprim::radix_sort_pairs(nullptr, tmp, keys, keys_alt, vals, vals_alt, n, 0u, end_bit, c->stream) != hipSuccess)
         return fail(c, FOCR_ERR_NO_DEVICE, "radix_sort_pairs (size query) failed");
-    int rc = ensure_sort_tmp(c, tmp);
+    int rc = reserve_sort_tmp(c, tmp);
     if (rc) return rc;
-    if (rocprim::radix_sort_pairs(c->d_sort_tmp, tmp, keys, keys_alt, vals, vals_alt, n, 0u, end_bit, c->stream) != hipSuccess)
+    if (rocprim::radix_sort_pairs(c->d_sort_tmp.p, tmp, keys, keys_alt, vals, vals_alt, n, 0u, end_bit, c->stream) != hipSuccess)
         return fail(c, FOCR_ERR_NO_DEVICE, "radix_sort_pairs failed");
+    return FOCR_OK;
+}
+
+// Ping-pong sorts of owned buffers: afterwards `keys` / `vals` own the sorted data, the alternates the input's memory
+int sort_pairs_u64_f32(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, DevArray<float> &vals, DevArray<float> &vals_alt, size_t n,
+                       unsigned end_bit) {
+    if (n < 2) return FOCR_OK;
+    if (int rc = radix_pairs(c, keys, keys_alt, vals, vals_alt, n, end_bit)) return rc;
     std::swap(keys, keys_alt);
     std::swap(vals, vals_alt);
     return FOCR_OK;
 }
 
-int sort_keys_u64(focr_ctx *c, uint64_t *&keys, uint64_t *&keys_alt, size_t n, unsigned end_bit) {
+int sort_keys_u64(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, size_t n, unsigned end_bit) {
     if (n < 2) return FOCR_OK;
     size_t tmp = 0;
-    if (rocprim::radix_sort_keys(nullptr, tmp, keys, keys_alt, n, 0u, end_bit, c->stream) != hipSuccess)
+    if (rocprim::radix_sort_keys(nullptr, tmp, keys.p, keys_alt.p, n, 0u, end_bit, c->stream) != hipSuccess)
         return fail(c, FOCR_ERR_NO_DEVICE, "radix_sort_keys (size query) failed");
-    int rc = ensure_sort_tmp(c, tmp);
+    int rc = reserve_sort_tmp(c, tmp);
     if (rc) return rc;
-    if (rocprim::radix_sort_keys(c->d_sort_tmp, tmp, keys, keys_alt, n, 0u, end_bit, c->stream) != hipSuccess)
+    if (rocprim::radix_sort_keys(c->d_sort_tmp.p, tmp, keys.p, keys_alt.p, n, 0u, end_bit, c->stream) != hipSuccess)
         return fail(c, FOCR_ERR_NO_DEVICE, "radix_sort_keys failed");
     std::swap(keys, keys_alt);
     return FOCR_OK;
@@ -76,9 +79,9 @@ int exclusive_scan_u64(focr_ctx *c, const uint64_t *in, uint64_t *out, size_t n)
     size_t tmp = 0;
     if (rocprim::exclusive_scan(nullptr, tmp, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->stream) != hipSuccess)
         return fail(c, FOCR_ERR_NO_DEVICE, "exclusive_scan (size query) failed");
-    int rc = ensure_sort_tmp(c, tmp);
+    int rc = reserve_sort_tmp(c, tmp);
     if (rc) return rc;
-    if (rocprim::exclusive_scan(c->d_sort_tmp, tmp, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->stream) != hipSuccess)
+    if (rocprim::exclusive_scan(c->d_sort_tmp.p, tmp, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), c->stream) != hipSuccess)
         return fail(c, FOCR_ERR_NO_DEVICE, "exclusive_scan failed");
     return FOCR_OK;
 }
@@ -163,31 +166,12 @@ __global__ void record_scan_sizes(const unsigned long long *__restrict__ n_cand_
     if ((n_cand_p && *n_cand_p > ub_c) || *n_hits_p > ub_h) res[4] |= 1;
 }
 
-static int ensure_seg_arrays(focr_ctx *c, size_t n_seg) {
-    if (c->seg_alloc >= n_seg + 1) return FOCR_OK;
-    FOCR_HIP(c, hipStreamSynchronize(c->stream));
-    for (void *p : {(void *)c->d_seg_count, (void *)c->d_seg_start, (void *)c->d_seg_offset})
-        if (p) (void)hipFree(p);
-    c->d_seg_count = nullptr;
-    c->d_seg_start = c->d_seg_offset = nullptr;
-    c->seg_alloc = 0;
+// The per-call arrays for n_seg (page, template) calls and the match list for `ub` hits (matches <= hits)
+static int reserve_calls(focr_ctx *c, size_t n_seg, size_t ub) {
     // d_seg_start doubles as the u64 copy of the counts during the scan: 2*(n_seg+1) entries
-    if (hipMalloc(&c->d_seg_count, (n_seg + 1) * 4) != hipSuccess || hipMalloc(&c->d_seg_start, 2 * (n_seg + 1) * 8) != hipSuccess ||
-        hipMalloc(&c->d_seg_offset, (n_seg + 1) * 8) != hipSuccess)
+    if (c->d_seg_count.reserve(n_seg + 1, Grow::exact, &c->stream) || c->d_seg_start.reserve(2 * (n_seg + 1), Grow::exact, &c->stream) ||
+        c->d_seg_offset.reserve(n_seg + 1, Grow::exact, &c->stream) || c->d_matches.reserve(ub, Grow::eighth, &c->stream))
         return fail(c, FOCR_ERR_NOMEM, "order: hipMalloc failed");
-    c->seg_alloc = n_seg + 1;
-    return FOCR_OK;
-}
-
-static int ensure_matches(focr_ctx *c, size_t want) {
-    if (c->matches_alloc >= want && c->d_matches) return FOCR_OK;
-    FOCR_HIP(c, hipStreamSynchronize(c->stream));
-    want = std::max<size_t>(want + want / 8, 1024);
-    if (c->d_matches) (void)hipFree(c->d_matches);
-    c->d_matches = nullptr;
-    c->matches_alloc = 0;
-    if (hipMalloc(&c->d_matches, want * sizeof(focr_match_t)) != hipSuccess) return fail(c, FOCR_ERR_NOMEM, "order: hipMalloc failed");
-    c->matches_alloc = want;
     return FOCR_OK;
 }
 
@@ -197,12 +181,13 @@ static int ensure_matches(focr_ctx *c, size_t want) {
 static int order_sorted_hits_sort(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t *n_p, size_t ub, const unsigned long long *n_cand_p, size_t ub_c) {
     const size_t n_seg = c->sub_np * c->n_templates;  // (page, template) calls of the pages being processed
     int rc;
-    if ((rc = ensure_seg_arrays(c, c->n_pages * c->n_templates))) return rc;
-    if ((rc = ensure_matches(c, ub))) return rc;  // matches <= hits
-    uint64_t *k2 = (uint64_t *)c->ord_k2.ensure(c, (ub + 1) * 8), *k2_alt = (uint64_t *)c->ord_k2_alt.ensure(c, (ub + 1) * 8);
-    float *v = (float *)c->ord_v.ensure(c, (ub + 1) * 4), *v_alt = (float *)c->ord_v_alt.ensure(c, (ub + 1) * 4);
-    uint8_t *keep = (uint8_t *)c->ord_keep.ensure(c, ub + 1);
-    if (!k2 || !k2_alt || !v || !v_alt || !keep) return fail(c, FOCR_ERR_NOMEM, "order: hipMalloc failed");
+    if ((rc = reserve_calls(c, c->n_pages * c->n_templates, ub))) return rc;
+    if (!c->scratch(c->ord_k2, (ub + 1) * 8) || !c->scratch(c->ord_k2_alt, (ub + 1) * 8) || !c->scratch(c->ord_v, (ub + 1) * 4) || !c->scratch(c->ord_v_alt, (ub + 1) * 4) ||
+        !c->scratch(c->ord_keep, ub + 1))
+        return fail(c, FOCR_ERR_NOMEM, "order: hipMalloc failed");
+    uint64_t *k2 = c->ord_k2.as<uint64_t>(), *k2_alt = c->ord_k2_alt.as<uint64_t>();
+    float *v = c->ord_v.as<float>(), *v_alt = c->ord_v_alt.as<float>();
+    uint8_t *keep = c->ord_keep;
     c->d_hkeys = hkeys;
     c->d_hsims = hsims;
     uint64_t *count64 = c->d_seg_start + (n_seg + 1);
@@ -211,8 +196,11 @@ static int order_sorted_hits_sort(focr_ctx *c, uint64_t *hkeys, float *hsims, co
         hipLaunchKernelGGL(build_segment_keys, dim3(nb), dim3(256), 0, c->stream, hkeys, n_p, (uint64_t)ub, c->fmt, (uint32_t)c->n_templates,
                            (uint32_t)c->sub_p0, k2, v);
         FOCR_HIP(c, hipGetLastError());
-        if ((rc = sort_pairs_u64_f32(c, k2, k2_alt, v, v_alt, ub, c->fmt.bp + c->fmt.bt))) return rc;  // LSD radix sort: stable
-        // (the sort may have swapped k2/v with their alternates; they are local pointers, the DevBufs keep ownership)
+        if (ub >= 2) {
+            if ((rc = radix_pairs(c, k2, k2_alt, v, v_alt, ub, c->fmt.bp + c->fmt.bt))) return rc;  // LSD radix sort: stable
+            std::swap(k2, k2_alt);  // (local pointers: the owners stay as they are)
+            std::swap(v, v_alt);
+        }
     }
     hipLaunchKernelGGL(segment_bounds, dim3((unsigned)((n_seg + 1 + 255) / 256)), dim3(256), 0, c->stream, k2, n_p, (uint64_t)ub,
                        (uint32_t)n_seg, c->cap, c->d_seg_start, c->d_seg_count, count64);
@@ -454,14 +442,13 @@ int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t
     const size_t n_seg = (size_t)n_pages * T;
     if (T > ORDER_T_MAX || ub >= ((size_t)1 << 31) || n_seg >= ((size_t)1 << 31)) return order_sorted_hits_sort(c, hkeys, hsims, n_p, ub, n_cand_p, ub_c);
     int rc;
-    if ((rc = ensure_seg_arrays(c, c->n_pages * c->n_templates + 8))) return rc;
-    if ((rc = ensure_matches(c, ub))) return rc;  // matches <= hits
+    if ((rc = reserve_calls(c, c->n_pages * c->n_templates + 8, ub))) return rc;
     const size_t max_units = ub / ORDER_UNIT + n_pages + 1;
-    uint8_t *keep = (uint8_t *)c->ord_keep.ensure(c, ub + 1);
     // unit tables: page_start, page_unit0 (n_pages + 1 each), unit_page / begin / end (max_units each)
-    uint32_t *tab = (uint32_t *)c->ord_v.ensure(c, (2 * ((size_t)n_pages + 1) + 3 * max_units) * 4);
-    uint32_t *uhist = (uint32_t *)c->ord_k2.ensure(c, max_units * T * 4);
-    if (!keep || !tab || !uhist) return fail(c, FOCR_ERR_NOMEM, "order: hipMalloc failed");
+    if (!c->scratch(c->ord_keep, ub + 1) || !c->scratch(c->ord_v, (2 * ((size_t)n_pages + 1) + 3 * max_units) * 4) || !c->scratch(c->ord_k2, max_units * T * 4))
+        return fail(c, FOCR_ERR_NOMEM, "order: hipMalloc failed");
+    uint8_t *keep = c->ord_keep;
+    uint32_t *tab = c->ord_v.as<uint32_t>(), *uhist = c->ord_k2.as<uint32_t>();
     uint32_t *page_start = tab, *page_unit0 = tab + n_pages + 1, *unit_page = page_unit0 + n_pages + 1, *unit_begin = unit_page + max_units,
              *unit_end = unit_begin + max_units;
     c->d_hkeys = hkeys;

@@ -94,8 +94,7 @@ struct PipeLane {
     hipStream_t stream = nullptr;       // owned by the lane's first context
     hipStream_t copy_stream = nullptr;  // announced batches: host -> staging buffer -> alternate page set
     hipStream_t io_stream = nullptr;    // results of finished batches: device -> host, device -> chars_out
-    void *pf_stage = nullptr;
-    size_t pf_stage_bytes = 0;
+    DevArray<uint8_t> pf_stage;         // announced batches on their way to an alternate page set (exact growth)
     std::mutex stage_mu;                // the staging buffer's owner while a copy + ingest is being queued
 };
 
@@ -136,14 +135,8 @@ static int issue_prefetch(focr_pipe *P, PipeSlot *S, const void *pages, size_t n
     const size_t bytes = n_pages * r_w * r_h;
     FOCR_HIP((focr_ctx *)nullptr, hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(L->stage_mu);  // one staging buffer per lane; its users are in order on the copy stream
-    if (L->pf_stage_bytes < bytes) {
-        FOCR_HIP((focr_ctx *)nullptr, hipStreamSynchronize(L->copy_stream));  // the previous announcement's ingest has read the old buffer
-        if (L->pf_stage) (void)hipFree(L->pf_stage);
-        L->pf_stage = nullptr;
-        L->pf_stage_bytes = 0;
-        if (hipMalloc(&L->pf_stage, bytes) != hipSuccess) return fail(nullptr, FOCR_ERR_NOMEM, "focr_pipe: staging buffer: hipMalloc failed");
-        L->pf_stage_bytes = bytes;
-    }
+    // (a larger buffer waits for the copy stream first: the previous announcement's ingest has read the old one)
+    if (L->pf_stage.reserve(bytes, Grow::exact, &L->copy_stream)) return fail(nullptr, FOCR_ERR_NOMEM, "focr_pipe: staging buffer: hipMalloc failed");
     // copy, then ingest, in stream order (the lane's previous ingest, which read the staging buffer, is ahead of this copy)
     FOCR_HIP((focr_ctx *)nullptr, hipMemcpyAsync(L->pf_stage, pages, bytes, hipMemcpyHostToDevice, L->copy_stream));
     if (int rc = pages_alt_ingest(c, L->pf_stage, n_pages, r_w, r_h, invert, L->copy_stream)) return rc;
@@ -425,7 +418,6 @@ void focr_pipe_destroy(focr_pipe_t *p) {
     for (PipeLane *L : p->lanes) {
         if (L->copy_stream) (void)hipStreamDestroy(L->copy_stream);
         if (L->io_stream) (void)hipStreamDestroy(L->io_stream);
-        if (L->pf_stage) (void)hipFree(L->pf_stage);
         delete L;
     }
     delete p;

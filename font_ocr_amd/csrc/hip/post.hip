@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void copy_chars_kernel(const uint32_t *__restr
 bool post_queue_chars_copy(focr_ctx *c, void *dst, size_t dst_bytes) {
     static_assert(sizeof(focr_hit_t) % 4 == 0, "focr_hit_t is copied as dwords");
     if (!c->post_pending || !c->post_scanned.p || !c->post_chars.p || !dst) return false;
-    const size_t n_rows_total = c->n_pages * c->r_h;
+    const size_t n_rows_total = c->n_pages * c->pages.r_h;
     hipLaunchKernelGGL(copy_chars_kernel, dim3(64), dim3(256), 0, c->stream, (const uint32_t *)c->post_chars.p, (const uint64_t *)c->post_scanned.p + n_rows_total,
                        (uint32_t *)dst, (uint64_t)(dst_bytes / 4));
     return hipGetLastError() == hipSuccess;
@@ -216,18 +216,17 @@ int focr_process_hits(focr_ctx_t *c, float anchor_threshold, int32_t overlap) {
     FOCR_HIP(c, hipEventRecord(c->ev[5], c->stream));
     // grow-only device scratch (no allocation in the steady state); outputs are sized by their bounds: characters <= hits,
     // lines <= page rows
-    const size_t n_rows_total = n_pages * c->r_h;
-    uint8_t *keep_row = (uint8_t *)c->post_keep.ensure(c, n_rows_total + 8);
-    uint32_t *choice = (uint32_t *)c->post_choice.ensure(c, (ub + 1) * 4);
-    uint64_t *packed = (uint64_t *)c->post_packed.ensure(c, (n_rows_total + 1) * 8);    // per row: 1<<32 | groups
-    uint64_t *scanned = (uint64_t *)c->post_scanned.ensure(c, (n_rows_total + 1) * 8);
-    uint64_t *d_page_off = (uint64_t *)c->post_page_off.ensure(c, (n_pages + 1) * 8);
-    uint32_t *line_b = (uint32_t *)c->post_line_be.ensure(c, n_rows_total * 8), *line_e = line_b ? line_b + n_rows_total : nullptr;
-    uint64_t *d_line_off = (uint64_t *)c->post_line_off.ensure(c, (n_rows_total + 1) * 8);
-    focr_hit_t *d_chars = (focr_hit_t *)c->post_chars.ensure(c, (ub + 1) * sizeof(focr_hit_t));
-    if (!line_b || !keep_row || !choice || !packed || !scanned || !d_page_off || !d_line_off || !d_chars)
+    const size_t n_rows_total = n_pages * c->pages.r_h;
+    if (!c->scratch(c->post_keep, n_rows_total + 8) || !c->scratch(c->post_choice, ub + 1) || !c->scratch(c->post_packed, n_rows_total + 1) ||
+        !c->scratch(c->post_scanned, n_rows_total + 1) || !c->scratch(c->post_page_off, n_pages + 1) || !c->scratch(c->post_line_be, 2 * n_rows_total) ||
+        !c->scratch(c->post_line_off, n_rows_total + 1) || !c->scratch(c->post_chars, ub + 1))
         return fail(c, FOCR_ERR_NOMEM, "focr_process_hits: hipMalloc failed");
-    const uint8_t *keep = (const uint8_t *)c->ord_keep.p;
+    uint8_t *keep_row = c->post_keep;
+    uint32_t *choice = c->post_choice, *line_b = c->post_line_be, *line_e = line_b + n_rows_total;
+    uint64_t *packed = c->post_packed, *scanned = c->post_scanned;  // packed: per row, 1<<32 | groups
+    uint64_t *d_page_off = c->post_page_off, *d_line_off = c->post_line_off;
+    focr_hit_t *d_chars = c->post_chars;
+    const uint8_t *keep = c->ord_keep;
     {
         ClearList clear{};  // one launch instead of two memsets (common.h)
         if (!clear.add(keep_row, n_rows_total)) return fail(c, FOCR_ERR_INVALID, "focr_process_hits: clear list full or region too large");
@@ -237,7 +236,7 @@ int focr_process_hits(focr_ctx_t *c, float anchor_threshold, int32_t overlap) {
     const unsigned nb = (unsigned)((ub + 255) / 256);
     if (ub)
         hipLaunchKernelGGL(mark_anchor_rows, dim3(nb), dim3(256), 0, c->stream, c->d_hkeys, c->d_hsims, keep, c->d_n_hits, (uint64_t)ub, c->fmt,
-                           anchor_threshold, (uint32_t)c->r_h, keep_row, line_b, line_e);
+                           anchor_threshold, (uint32_t)c->pages.r_h, keep_row, line_b, line_e);
     hipLaunchKernelGGL(walk_lines, dim3((unsigned)(((n_rows_total + WALK_ROWS - 1) / WALK_ROWS * 64 + 255) / 256)), dim3(256), 0, c->stream, c->d_hkeys, c->d_hsims,
                        keep, c->fmt, (uint32_t)n_rows_total, overlap, keep_row, line_b, line_e, choice, packed);
     int rc;
@@ -245,9 +244,9 @@ int focr_process_hits(focr_ctx_t *c, float anchor_threshold, int32_t overlap) {
     // packed[n_rows_total] = 0, so the scan's last entry is the grand total (lines << 32 | characters): into the result block
     FOCR_HIP(c, hipMemcpyAsync(c->h_res + 3, scanned + n_rows_total, 8, hipMemcpyDeviceToHost, c->stream));
     if (ub)
-        hipLaunchKernelGGL(emit_chars, dim3(nb), dim3(256), 0, c->stream, c->d_hkeys, c->d_hsims, c->d_n_hits, (uint64_t)ub, c->fmt, (uint32_t)c->r_h,
-                           keep_row, line_b, choice, packed, scanned, c->d_t_w, c->d_t_h, c->d_t_letter, d_line_off, d_chars);
-    hipLaunchKernelGGL(page_offsets, dim3((unsigned)((n_pages + 1 + 255) / 256)), dim3(256), 0, c->stream, scanned, (uint32_t)c->r_h,
+        hipLaunchKernelGGL(emit_chars, dim3(nb), dim3(256), 0, c->stream, c->d_hkeys, c->d_hsims, c->d_n_hits, (uint64_t)ub, c->fmt, (uint32_t)c->pages.r_h,
+                           keep_row, line_b, choice, packed, scanned, c->bank.d_t_w, c->bank.d_t_h, c->bank.d_t_letter, d_line_off, d_chars);
+    hipLaunchKernelGGL(page_offsets, dim3((unsigned)((n_pages + 1 + 255) / 256)), dim3(256), 0, c->stream, scanned, (uint32_t)c->pages.r_h,
                        (uint32_t)n_pages, d_page_off);
     FOCR_HIP(c, hipGetLastError());
     FOCR_HIP(c, hipEventRecord(c->ev[6], c->stream));
@@ -322,14 +321,14 @@ int focr_debug_process_hits(focr_ctx_t *c, const uint32_t *page, const uint32_t 
                             const float *similarity, const uint8_t *keep, size_t n) {
     if (!c) return FOCR_ERR_INVALID;
     if (n && (!page || !y || !x || !t || !similarity || !keep)) return fail(c, FOCR_ERR_INVALID, "focr_debug_process_hits: bad arguments");
-    if (!c->n_templates || !c->d_pages) return fail(c, FOCR_ERR_STATE, "focr_debug_process_hits: upload a bank and allocate pages first");
+    if (!c->n_templates || !c->pages.u8) return fail(c, FOCR_ERR_STATE, "focr_debug_process_hits: upload a bank and allocate pages first");
     if (n >= 0xffffffffull) return fail(c, FOCR_ERR_OVERFLOW, "focr_debug_process_hits: more than 2^32 hits in one batch");
-    const KeyFmt fmt = key_format(c->n_templates, c->r_w, c->r_h, c->n_pages);
+    const KeyFmt fmt = key_format(c->n_templates, c->pages.r_w, c->pages.r_h, c->n_pages);
     std::vector<uint64_t> keys(n);
     std::vector<uint8_t> kept(n);
     size_t n_kept = 0;
     for (size_t i = 0; i < n; i++) {
-        if (page[i] >= c->n_pages || y[i] >= c->r_h || x[i] >= c->r_w || t[i] >= c->n_templates)
+        if (page[i] >= c->n_pages || y[i] >= c->pages.r_h || x[i] >= c->pages.r_w || t[i] >= c->n_templates)
             return fail(c, FOCR_ERR_INVALID, "focr_debug_process_hits: hit " + std::to_string(i) + " lies outside the pages or the bank");
         keys[i] = fmt.pack(page[i], y[i], x[i], t[i]);
         if (i && keys[i] <= keys[i - 1])
@@ -339,10 +338,11 @@ int focr_debug_process_hits(focr_ctx_t *c, const uint32_t *page, const uint32_t 
     }
     if (int rc = finish_results(c)) return rc;  // whatever an earlier call queued is done before its buffers are overwritten
     FOCR_HIP(c, hipSetDevice(c->device));
-    uint64_t *d_keys = (uint64_t *)c->acc_hkeys.ensure(c, (n + 1) * 8);
-    float *d_sims = (float *)c->acc_hsims.ensure(c, (n + 1) * 4);
-    uint8_t *d_keep = (uint8_t *)c->ord_keep.ensure(c, n + 1);
-    if (!d_keys || !d_sims || !d_keep) return fail(c, FOCR_ERR_NOMEM, "focr_debug_process_hits: hipMalloc failed");
+    if (!c->scratch(c->acc_hkeys, n + 1) || !c->scratch(c->acc_hsims, n + 1) || !c->scratch(c->ord_keep, n + 1))
+        return fail(c, FOCR_ERR_NOMEM, "focr_debug_process_hits: hipMalloc failed");
+    uint64_t *d_keys = c->acc_hkeys;
+    float *d_sims = c->acc_hsims;
+    uint8_t *d_keep = c->ord_keep;
     c->n_hits_raw_u64 = n;
     if (n) {
         FOCR_HIP(c, hipMemcpyAsync(d_keys, keys.data(), n * 8, hipMemcpyHostToDevice, c->stream));

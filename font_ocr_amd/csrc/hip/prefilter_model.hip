@@ -36,18 +36,18 @@ extern "C" int focr_debug_prefilter(const focr_template_t *templates, size_t n_t
     std::vector<int8_t> qbank;
     bank_host_prepare(c, templates, n_templates, needles, direct, dense);
     if (int rc = quantise_bank(c, dense.data(), qbank, tglobal, order_of)) return rc;
-    for (size_t k = 0; k < c->classes.size() && info && 4 * k + 3 < n_info; k++) {
-        info[4 * k] = c->mfma_c_scale[k];
-        info[4 * k + 1] = c->mfma_e_max[k];
-        info[4 * k + 2] = c->mfma_rho_max[k];
-        info[4 * k + 3] = c->classes[k].keep_w;
+    for (size_t k = 0; k < c->bank.classes.size() && info && 4 * k + 3 < n_info; k++) {
+        info[4 * k] = c->bank.mfma_c_scale[k];
+        info[4 * k + 1] = c->bank.mfma_e_max[k];
+        info[4 * k + 2] = c->bank.mfma_rho_max[k];
+        info[4 * k + 3] = c->bank.classes[k].keep_w;
     }
     if (!windows || !n_windows || !sim || !d) return FOCR_OK;
     const double thr_d = (double)threshold;
     // int8 templates back out of the per-lane operand image
-    std::vector<std::vector<int>> bq(c->h_tconst.size());
-    for (size_t k = 0; k < c->classes.size(); k++) {
-        const SizeClass &sc = c->classes[k];
+    std::vector<std::vector<int>> bq(c->bank.h_tconst.size());
+    for (size_t k = 0; k < c->bank.classes.size(); k++) {
+        const SizeClass &sc = c->bank.classes[k];
         const uint32_t ksteps = sc.k_groups / 4;
         for (uint32_t i = 0; i < sc.n_templates; i++) {
             std::vector<int> &q = bq[sc.first + i];
@@ -63,8 +63,8 @@ extern "C" int focr_debug_prefilter(const focr_template_t *templates, size_t n_t
     }
     for (size_t wi = 0; wi < n_windows; wi++) {
         const uint8_t *a = windows + wi * (size_t)frame_w * frame_h;
-        for (size_t k = 0; k < c->classes.size(); k++) {
-            const SizeClass &sc = c->classes[k];
+        for (size_t k = 0; k < c->bank.classes.size(); k++) {
+            const SizeClass &sc = c->bank.classes[k];
             const PlaneParams p = plane_params(c, k, thr_d);
             const uint32_t n = sc.n_w * sc.n_h, kw = sc.keep_w, n_k = kw * sc.n_h;
             uint32_t s = 0, s2 = 0, q1 = 0, q2 = 0;
@@ -81,7 +81,7 @@ extern "C" int focr_debug_prefilter(const focr_template_t *templates, size_t n_t
             const int cin = prefilter_cin(p.shift, plane);
             const double norm_p = std::sqrt((double)V / (double)n);
             for (uint32_t i = 0; i < sc.n_templates; i++) {
-                const TemplateConst &tc = c->h_tconst[sc.first + i];
+                const TemplateConst &tc = c->bank.h_tconst[sc.first + i];
                 const size_t o = wi * n_templates + tc.index;
                 sim[o] = NAN;
                 d[o] = INT64_MIN;  // dead templates (constant needles) never reach the candidate list
@@ -91,7 +91,7 @@ extern "C" int focr_debug_prefilter(const focr_template_t *templates, size_t n_t
                     for (uint32_t x = 0; x < kw; x++) G += (long)((int)a[j * frame_w + x] - 128) * bq[sc.first + i][j * kw + x];
                 d[o] = (int64_t)G + cin;
                 if (V != 0 && std::isfinite(tc.rnorm_n)) {
-                    const uint8_t *nd = dense.data() + c->h_needle_off[sc.first + i];
+                    const uint8_t *nd = dense.data() + c->bank.h_needle_off[sc.first + i];
                     double num = 0;
                     for (uint32_t j = 0; j < sc.n_h; j++)
                         for (uint32_t x = 0; x < sc.n_w; x++) num += (double)a[j * frame_w + x] * nd[j * sc.n_w + x];
@@ -128,12 +128,12 @@ extern "C" int focr_debug_prefilter_page(const focr_template_t *templates, size_
     bank_host_prepare(c, templates, n_templates, needles, direct, dense);
     if (int rc = quantise_bank(c, dense.data(), qbank, tglobal, order_of)) return rc;
     // the passes of a scan of one page of this size, as launch_scan_mfma plans them
-    c->r_w = r_w, c->r_h = r_h, c->n_pages = c->sub_np = 1;
+    c->pages.r_w = r_w, c->pages.r_h = r_h, c->n_pages = c->sub_np = 1;
     const size_t one_plane = (size_t)((r_w + 63) / 64 * 64 + 64) * ((r_h + 7) / 8 * 8 + 8);
     size_t tiles_total = 0, plane_vals = 0;
     bool need_L = false;
     if (int rc = plan_passes(c, one_plane, tiles_total, plane_vals, need_L)) return rc;
-    const size_t n_cls = c->classes.size(), wins = (size_t)r_w * r_h;
+    const size_t n_cls = c->bank.classes.size(), wins = (size_t)r_w * r_h;
     if (n_classes) *n_classes = n_cls;
     const double thr_d = (double)threshold;
     std::vector<PlaneParams> pp(n_cls);
@@ -142,7 +142,7 @@ extern "C" int focr_debug_prefilter_page(const focr_template_t *templates, size_
         const SuperClass &su = c->supers[si];
         for (size_t v = 0; v < su.classes.size(); v++) {
             const size_t k = su.classes[v];
-            const SizeClass &sc = c->classes[k];
+            const SizeClass &sc = c->bank.classes[k];
             if (!class_info || 16 * k + 15 >= class_info_len) continue;
             double *o = class_info + 16 * k;
             o[0] = sc.n_w, o[1] = sc.n_h, o[2] = sc.keep_w, o[3] = sc.layout, o[4] = su.ksteps, o[5] = (double)si, o[6] = (double)v;
@@ -152,14 +152,14 @@ extern "C" int focr_debug_prefilter_page(const focr_template_t *templates, size_
         }
     }
     for (size_t k = 0; k < n_cls; k++) {  // per template: class, slot, live, N-tile inside the super-class; the int8 template itself
-        const SizeClass &sc = c->classes[k];
+        const SizeClass &sc = c->bank.classes[k];
         size_t si = 0, v = 0;
         for (size_t s = 0; s < c->supers.size(); s++)
             for (size_t u = 0; u < c->supers[s].classes.size(); u++)
                 if (c->supers[s].classes[u] == k) si = s, v = u;
         const uint32_t ksteps = sc.k_groups / 4;
         for (uint32_t i = 0; i < sc.n_templates; i++) {
-            const uint32_t t = c->h_tconst[sc.first + i].index, slot = c->mfma_slot[sc.first + i];
+            const uint32_t t = c->bank.h_tconst[sc.first + i].index, slot = c->mfma_slot[sc.first + i];
             if (template_info) {
                 int32_t *o = template_info + 4 * (size_t)t;
                 o[0] = (int32_t)k, o[1] = (int32_t)slot, o[2] = tglobal[sc.tg_offset + slot] != 0xffffffffu, o[3] = (int32_t)(c->supers[si].tile_first[v] + slot / 16);
@@ -182,7 +182,7 @@ extern "C" int focr_debug_prefilter_page(const focr_template_t *templates, size_
     for (size_t i = 0; i < wins; i++) a8[i] = (int16_t)((int)page[i] - 128);
     std::vector<uint32_t> S1, S2;  // window sums of the class at hand (for sim)
     for (size_t k = 0; k < n_cls; k++) {
-        const SizeClass &sc = c->classes[k];
+        const SizeClass &sc = c->bank.classes[k];
         const PlaneParams &p = pp[k];
         const uint32_t n = sc.n_w * sc.n_h, kw = sc.keep_w, n_k = kw * sc.n_h, ksteps = sc.k_groups / 4;
         S1.assign(wins, 0), S2.assign(wins, 0);
@@ -215,7 +215,7 @@ extern "C" int focr_debug_prefilter_page(const focr_template_t *templates, size_
         if (!G && !sim) continue;
         std::vector<int16_t> bq((size_t)sc.n_h * kw);
         for (uint32_t i = 0; i < sc.n_templates; i++) {
-            const TemplateConst &tc = c->h_tconst[sc.first + i];
+            const TemplateConst &tc = c->bank.h_tconst[sc.first + i];
             const uint32_t slot = c->mfma_slot[sc.first + i];
             const bool live = tglobal[sc.tg_offset + slot] != 0xffffffffu;
             int32_t *Gt = G ? G + (size_t)tc.index * wins : nullptr;
@@ -226,7 +226,7 @@ extern "C" int focr_debug_prefilter_page(const focr_template_t *templates, size_
                     kgroup_of(sc.layout, j, x, &ks, &g, &byte);
                     bq[(size_t)j * kw + x] = qbank[sc.q_offset + ((size_t)((slot / 16) * ksteps + ks) * 64 + g * 16 + slot % 16) * 16 + byte];
                 }
-            const uint8_t *nd = dense.data() + c->h_needle_off[sc.first + i];
+            const uint8_t *nd = dense.data() + c->bank.h_needle_off[sc.first + i];
             for (uint32_t y = 0; y < r_h; y++)
                 for (uint32_t x = 0; x < r_w; x++) {
                     const size_t w = (size_t)y * r_w + x;
@@ -284,20 +284,14 @@ extern "C" int focr_debug_plane_value_device(focr_ctx_t *c, const float *x, size
     p.shift = shift;
     p.S = std::ldexp(1.0f, (int)shift);
     p.inv_S = std::ldexp(1.0f, -(int)shift);
-    float *dx = nullptr;
-    int16_t *dout = nullptr;
-    auto run = [&]() -> int {
-        FOCR_HIP(c, hipMalloc((void **)&dx, n * 4));
-        FOCR_HIP(c, hipMalloc((void **)&dout, n * 2));
-        FOCR_HIP(c, hipMemcpyAsync(dx, x, n * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(plane_value_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dx, n, p, dout);
-        FOCR_HIP(c, hipGetLastError());
-        FOCR_HIP(c, hipMemcpyAsync(out, dout, n * 2, hipMemcpyDeviceToHost, c->stream));
-        FOCR_HIP(c, hipStreamSynchronize(c->stream));
-        return FOCR_OK;
-    };
-    const int rc = run();
-    if (dx) (void)hipFree(dx);
-    if (dout) (void)hipFree(dout);
-    return rc;
+    DevArray<float> dx;
+    DevArray<int16_t> dout;
+    FOCR_HIP(c, dx.reserve(n, Grow::exact, nullptr));
+    FOCR_HIP(c, dout.reserve(n, Grow::exact, nullptr));
+    FOCR_HIP(c, hipMemcpyAsync(dx, x, n * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(plane_value_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, dx.p, n, p, dout.p);
+    FOCR_HIP(c, hipGetLastError());
+    FOCR_HIP(c, hipMemcpyAsync(out, dout, n * 2, hipMemcpyDeviceToHost, c->stream));
+    FOCR_HIP(c, hipStreamSynchronize(c->stream));
+    return FOCR_OK;
 }

@@ -31,7 +31,7 @@
 namespace focr {
 
 int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t *n_p, size_t ub, const unsigned long long *n_cand_p, size_t ub_c);
-int ensure_hit_capacity(focr_ctx *c, size_t want);
+int reserve_hits(focr_ctx *c, size_t want);
 
 // exclusive prefix of n u32 counts by ONE workgroup: base[0..n] (base[n] = total); *total_out = total, *max_out = max
 // (u64 each; either may be null); zero[0..n) is cleared on the way if given (the scatter's per-row cursors).  Each of the 16
@@ -486,22 +486,22 @@ __global__ __launch_bounds__(256) void hit_scatter_kernel(const uint64_t *__rest
 void row_segments(const focr_ctx *c, uint32_t *seg_shift, uint32_t *n_seg) {
     uint32_t sh = c->est.seg_shift;
     if (!sh) {
-        while (((size_t)1 << sh) < c->r_w) sh++;  // one segment
+        while (((size_t)1 << sh) < c->pages.r_w) sh++;  // one segment
         while (sh > 5 && ((size_t)1 << sh) * c->n_templates > ((size_t)1 << 19)) sh--;
     }
     *seg_shift = sh;
-    *n_seg = (uint32_t)((c->r_w + ((size_t)1 << sh) - 1) >> sh);
+    *n_seg = (uint32_t)((c->pages.r_w + ((size_t)1 << sh) - 1) >> sh);
 }
 
 static size_t row_buckets(const focr_ctx *c) {
     uint32_t sh, ns;
     row_segments(c, &sh, &ns);
-    return c->sub_np * c->r_h * ns;
+    return c->sub_np * c->pages.r_h * ns;
 }
 
 bool rows_applicable(const focr_ctx *c) {
     if (c->tail_mode == 0) return false;  // focr_ctx_set_row_tail(0): the legacy tail, for A/B
-    for (const SizeClass &sc : c->classes)
+    for (const SizeClass &sc : c->bank.classes)
         if (sc.tall) return false;  // scan_tall_kernel appends its candidates without counting them per bucket
     static_assert(sizeof(VerifyMeta) == 32, "VerifyMeta is staged in LDS as two 16-byte words per template");
     return row_buckets(c) <= ((size_t)1 << 22) && c->fmt.bp + c->fmt.by <= 32 && c->n_templates <= 4096;  // 4096 x 32 B of template records in the verify's LDS
@@ -511,15 +511,14 @@ bool rows_applicable(const focr_ctx *c) {
 int rows2_begin(focr_ctx *c, ClearList &clear) {
     const size_t n_rows = row_buckets(c);
     const size_t padded = (n_rows + 1 + 3) / 4 * 4 + 4;  // row_prefix_kernel moves 16 bytes at a time
-    uint32_t *hits = (uint32_t *)c->rows_hits.ensure(c, padded * 4);
-    if (!hits || !c->rows_hbase.ensure(c, padded * 4)) return fail(c, FOCR_ERR_NOMEM, "rows: hipMalloc failed");
-    uint32_t *big = (uint32_t *)c->rows_big.ensure(c, ((size_t)n_rows + 1) * 4 + 8);  // [0]: length of the list of large buckets
-    if (!big) return fail(c, FOCR_ERR_NOMEM, "rows: hipMalloc failed");
+    if (!c->scratch(c->rows_hits, padded) || !c->scratch(c->rows_hbase, padded) || !c->scratch(c->rows_big, n_rows + 1 + 2))  // big[0]: length of the list of large buckets
+        return fail(c, FOCR_ERR_NOMEM, "rows: hipMalloc failed");
+    uint32_t *hits = c->rows_hits, *big = c->rows_big;
     if (!clear.add(hits, padded * 4)) return fail(c, FOCR_ERR_INVALID, "rows: clear list full or region too large");
     if (!clear.add(big, 8)) return fail(c, FOCR_ERR_INVALID, "rows: clear list full or region too large");
     uint32_t seg_shift, n_seg;
     row_segments(c, &seg_shift, &n_seg);
-    c->row_hist = RowHist{nullptr, (uint32_t)c->r_h, c->fmt.bt + c->fmt.bx, c->fmt.by, (uint32_t)c->sub_p0, c->fmt.bt, c->fmt.bx, seg_shift, n_seg};
+    c->row_hist = RowHist{nullptr, (uint32_t)c->pages.r_h, c->fmt.bt + c->fmt.bx, c->fmt.by, (uint32_t)c->sub_p0, c->fmt.bt, c->fmt.bx, seg_shift, n_seg};
     return FOCR_OK;
 }
 
@@ -535,7 +534,7 @@ static unsigned tail_grid(const focr_ctx *c, unsigned blocks) {
 static int verify_mode(const focr_ctx *c, size_t *lds, uint32_t *rows_out) {
     size_t all_rows = 0;
     uint32_t max_w = 0;
-    for (const TemplateConst &tc : c->h_tconst) {
+    for (const TemplateConst &tc : c->bank.h_tconst) {
         all_rows += (size_t)tc.n_h * (tc.n_w > 16 ? 2u : 1u);
         max_w = std::max<uint32_t>(max_w, tc.n_w);
     }
@@ -551,11 +550,11 @@ static int verify_mode(const focr_ctx *c, size_t *lds, uint32_t *rows_out) {
 // slots per bucket, prefix -> d_res[6] = hits, d_res[5] = the largest bucket.  Records ev[3] behind the verify.
 int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c) {
     const uint32_t n_rows = (uint32_t)row_buckets(c);
-    float *csims = (float *)c->scan_pos.ensure(c, (ub_c + 1) * 4);
-    uint32_t *cslots = (uint32_t *)c->scan_flags.ensure(c, (ub_c + 1) * 4);
-    if (!csims || !cslots) return fail(c, FOCR_ERR_NOMEM, "rows: hipMalloc failed");
+    if (!c->scratch(c->scan_pos, (ub_c + 1) * 4) || !c->scratch(c->scan_flags, (ub_c + 1) * 4)) return fail(c, FOCR_ERR_NOMEM, "rows: hipMalloc failed");
+    float *csims = c->scan_pos.as<float>();
+    uint32_t *cslots = c->scan_flags.as<uint32_t>();
     const unsigned cus = c->n_cus;
-    uint32_t *hits = (uint32_t *)c->rows_hits.p, *hbase = (uint32_t *)c->rows_hbase.p;
+    uint32_t *hits = c->rows_hits, *hbase = c->rows_hbase;
     const TailWork tw{c->d_counter + TAIL_DONE_WORD, n_rows, hbase, c->d_res + 6, c->d_res + 5};  // the verify's last workgroup does the prefix
     // The verify's workgroups are persistent (they walk the list with the grid's stride), so where the scan kernel is confined to
     // scan_cus CUs — several batches in flight — the verify asks for no more workgroups than fit the CUs the scan leaves free: a
@@ -572,9 +571,9 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
         size_t lds;
         uint32_t all_rows;
         const int mode = verify_mode(c, &lds, &all_rows);
-        if (mode == 0 && c->vrow_bytes) {
+        if (mode == 0 && c->bank.vrow_bytes) {
             // the operand does not fit the LDS whole: chunks of consecutive templates that do (verify_chunks_kernel)
-            const bool narrow = c->vrow_bytes == 12;
+            const bool narrow = c->bank.vrow_bytes == 12;
             const size_t queue_bytes = (size_t)(VERIFY_THREADS / 64) * CHUNK_QUEUE * 12 + 64;
             const size_t budget = ((size_t)150 << 10) - queue_bytes;  // one workgroup per CU: fewer, larger chunks beat more waves per CU (above)
             ChunkTable ct{};
@@ -582,14 +581,14 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
             uint32_t t0 = 0;
             bool ok = true;
             for (uint32_t t = 0; t <= c->n_templates && ok; t++) {
-                const size_t add = t < c->n_templates ? sizeof(VerifyMeta) + (size_t)(c->h_vrow0_t[t + 1] - c->h_vrow0_t[t]) * c->vrow_bytes : 0;
+                const size_t add = t < c->n_templates ? sizeof(VerifyMeta) + (size_t)(c->bank.h_vrow0_t[t + 1] - c->bank.h_vrow0_t[t]) * c->bank.vrow_bytes : 0;
                 if (t == c->n_templates || bytes + add > budget) {
                     if (t == t0 || ct.n == MAX_VERIFY_CHUNKS) {
                         ok = false;  // a single template above the budget, or too many chunks: global loads after all
                         break;
                     }
                     ct.t_lo[ct.n] = t0;
-                    ct.row_lo[ct.n] = c->h_vrow0_t[t0];
+                    ct.row_lo[ct.n] = c->bank.h_vrow0_t[t0];
                     ct.data_bytes = std::max(ct.data_bytes, (uint32_t)((bytes + 15) & ~(size_t)15));  // this chunk's records + rows (bytes <= budget)
                     ct.n++;
                     t0 = t;
@@ -599,7 +598,7 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
             }
             if (ok) {
                 ct.t_lo[ct.n] = (uint32_t)c->n_templates;
-                ct.row_lo[ct.n] = c->h_vrow0_t[c->n_templates];
+                ct.row_lo[ct.n] = c->bank.h_vrow0_t[c->n_templates];
                 const size_t lds_c = (size_t)ct.data_bytes + queue_bytes;  // <= 150 KiB by construction: every chunk's data is within the budget
                 // one workgroup per CU of the whole chip: at configs[2] the chunk passes are a fifth of a lane's chain, and the lane
                 // waits for them (half / a third / a quarter of the CUs: 7.25 / 7.21 / 7.12 Gpx/s against 7.28)
@@ -609,7 +608,7 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
     attr = hipFuncSetAttribute(reinterpret_cast<const void *>(verify_chunks_kernel<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);                \
     if (attr == hipSuccess)                                                                                                                                    \
     hipLaunchKernelGGL(verify_chunks_kernel<R>, dim3(nbc), dim3(VERIFY_THREADS), lds_c, c->stream, (const uint64_t *)c->d_cand, n_cand_p, (unsigned long long)ub_c, va, \
-                       ct, (const uint32_t *)c->d_vrows_t, (const VerifyMeta *)c->d_vmeta_t, c->row_hist, csims, cslots, hits, tw)
+                       ct, c->bank.d_vrows_t.as<const uint32_t>(), c->bank.d_vmeta_t.p, c->row_hist, csims, cslots, hits, tw)
                 if (narrow) {
                     FOCR_VERIFY_CHUNKS(12);
                 } else {
@@ -653,13 +652,13 @@ verified:
 int rows2_place(focr_ctx *c, const unsigned long long *n_cand_p, size_t ub_c, size_t ub_h, bool big_expected, bool sort) {
     const uint32_t n_rows = (uint32_t)row_buckets(c);
     int rc;
-    if ((rc = ensure_hit_capacity(c, std::max<size_t>(c->hit_capacity, ub_h + 1)))) return rc;
+    if ((rc = reserve_hits(c, ub_h + 1))) return rc;
     const unsigned cus = c->n_cus;
     const uint32_t *hits = (const uint32_t *)c->rows_hits.p, *hbase = (const uint32_t *)c->rows_hbase.p;
     if (ub_c) {
         const unsigned nb = tail_grid(c, (unsigned)std::max<size_t>(1, std::min<size_t>((ub_c + 255) / 256, (size_t)cus * 16)));
         hipLaunchKernelGGL(hit_scatter_kernel, dim3(nb), dim3(256), 0, c->stream, (const uint64_t *)c->d_cand, n_cand_p, (unsigned long long)ub_c, c->row_hist, hbase,
-                           (const float *)c->scan_pos.p, (const uint32_t *)c->scan_flags.p, c->d_hit_keys, c->d_hit_sims_alt, (unsigned long long)c->hit_capacity);
+                           (const float *)c->scan_pos.p, (const uint32_t *)c->scan_flags.p, c->d_hit_keys, c->d_hit_sims_alt, (unsigned long long)c->d_hit_keys.cap);
         FOCR_HIP(c, hipGetLastError());
     }
     if (!sort) return FOCR_OK;  // a bucket beyond the row sort's capacity (exact sizes know): the caller sorts the placed hits with the library sort
@@ -674,7 +673,7 @@ int rows2_place(focr_ctx *c, const unsigned long long *n_cand_p, size_t ub_c, si
     auto k2 = row_sort_kernel<4096, 1, true, true>;
     const size_t lds1 = (size_t)4 * (XBINS + 1 + 1024) * 4, lds2 = (size_t)(XBINS + 1 + 4096) * 4;
     hipLaunchKernelGGL(k1, dim3(row_blocks), dim3(256), lds1, c->stream, n_rows, hbase, hits, c->d_hit_keys, c->fmt.bt + c->fmt.bx, c->fmt.bt, seg_w - 1, xs, n_bins,
-                       big_expected ? big : (uint32_t *)nullptr, flags_word, c->d_hit_sims_alt, (unsigned long long)c->hit_capacity);
+                       big_expected ? big : (uint32_t *)nullptr, flags_word, c->d_hit_sims_alt, (unsigned long long)c->d_hit_keys.cap);
     FOCR_HIP(c, hipGetLastError());
     // Buckets above 1 024 hits (the list `big`) get a second launch only where one is expected: exact sizes know the largest bucket,
     // estimated sizes go by the previous scan's (+ 25 %).  Without the launch a bucket that lands on the list after all is an
@@ -683,7 +682,7 @@ int rows2_place(focr_ctx *c, const unsigned long long *n_cand_p, size_t ub_c, si
     // batches' kernels keep full: profiles/r04_timeline_bench_c2.log), for a list that BASELINE configs[1] and [2] never fill.
     if (big_expected) {
         hipLaunchKernelGGL(k2, dim3(cus), dim3(64), lds2, c->stream, n_rows, hbase, hits, c->d_hit_keys, c->fmt.bt + c->fmt.bx, c->fmt.bt, seg_w - 1, xs, n_bins, big, flags_word,
-                           c->d_hit_sims_alt, (unsigned long long)c->hit_capacity);
+                           c->d_hit_sims_alt, (unsigned long long)c->d_hit_keys.cap);
         FOCR_HIP(c, hipGetLastError());
     }
     return FOCR_OK;

@@ -187,15 +187,15 @@ __global__ __launch_bounds__(256) void scan_tall_kernel(const uint8_t *__restric
 template <int NDW>
 static void launch_tall_one(focr_ctx *c, const SizeClass &sc, size_t k, double thr_d, uint64_t *keys, float *sims,
                             unsigned long long *counter, unsigned long long capacity, int rust) {
-    dim3 grid((unsigned)((c->r_w - sc.n_w + DTX - 1) / DTX), (unsigned)((c->r_h - sc.n_h + DTY - 1) / DTY), (unsigned)c->sub_np);
-    const uint64_t win = (uint64_t)(c->r_w - sc.n_w) * (c->r_h - sc.n_h) * c->sub_np;
+    dim3 grid((unsigned)((c->pages.r_w - sc.n_w + DTX - 1) / DTX), (unsigned)((c->pages.r_h - sc.n_h + DTY - 1) / DTY), (unsigned)c->sub_np);
+    const uint64_t win = (uint64_t)(c->pages.r_w - sc.n_w) * (c->pages.r_h - sc.n_h) * c->sub_np;
     char name[64];
     snprintf(name, sizeof name, "scan_tall_kernel<%d>", NDW);
     c->launch_begin(name, sc.n_templates, win * sc.n_w * sc.n_h * sc.n_templates, win * NDW * 4 * sc.n_h * sc.n_templates);
     const size_t lds = (size_t)(DTY + sc.n_h - 1) * DLDW * 4;
-    hipLaunchKernelGGL((scan_tall_kernel<NDW>), grid, dim3(256), lds, c->stream, c->d_pages, (uint32_t)c->pitch,
-                       (uint32_t)c->rows_alloc, (uint32_t)c->r_w, (uint32_t)c->r_h, sc.n_w, sc.n_h,
-                       c->d_direct_bank + c->direct_bank_off[k], c->d_tconst + sc.first, sc.n_templates, c->fmt, thr_d, keys, sims,
+    hipLaunchKernelGGL((scan_tall_kernel<NDW>), grid, dim3(256), lds, c->stream, c->pages.u8, (uint32_t)c->pages.pitch,
+                       (uint32_t)c->pages.rows_alloc, (uint32_t)c->pages.r_w, (uint32_t)c->pages.r_h, sc.n_w, sc.n_h,
+                       c->bank.d_direct_bank + c->bank.direct_bank_off[k], c->bank.d_tconst + sc.first, sc.n_templates, c->fmt, thr_d, keys, sims,
                        counter, capacity, (uint32_t)c->sub_p0, rust);
     c->launch_end();
 }
@@ -203,7 +203,7 @@ static void launch_tall_one(focr_ctx *c, const SizeClass &sc, size_t k, double t
 // Scan one tall class (both modes call this).  sims == nullptr: keys only.
 int launch_scan_tall(focr_ctx *c, size_t k, double thr_d, uint64_t *keys, float *sims, unsigned long long *counter,
                      unsigned long long capacity, int rust) {
-    const SizeClass &sc = c->classes[k];
+    const SizeClass &sc = c->bank.classes[k];
     switch (sc.ndw) {
         case 1: launch_tall_one<1>(c, sc, k, thr_d, keys, sims, counter, capacity, rust); break;
         case 2: launch_tall_one<2>(c, sc, k, thr_d, keys, sims, counter, capacity, rust); break;
@@ -216,57 +216,52 @@ int launch_scan_tall(focr_ctx *c, size_t k, double thr_d, uint64_t *keys, float 
         default: return fail(c, FOCR_ERR_INVALID, "scan_tall: unsupported size class");
     }
     FOCR_HIP(c, hipGetLastError());
-    c->counters[3] += (uint64_t)(c->r_w - sc.n_w) * (c->r_h - sc.n_h) * sc.ndw * 4 * sc.n_h * sc.n_templates * c->sub_np;
+    c->counters[3] += (uint64_t)(c->pages.r_w - sc.n_w) * (c->pages.r_h - sc.n_h) * sc.ndw * 4 * sc.n_h * sc.n_templates * c->sub_np;
     return FOCR_OK;
 }
 
 template <int NDW, int MAXH>
 static void launch_one(focr_ctx *c, const SizeClass &sc, size_t k, double thr_d, int rust) {
-    dim3 grid((unsigned)((c->r_w - sc.n_w + DTX - 1) / DTX), (unsigned)((c->r_h - sc.n_h + DTY - 1) / DTY),
+    dim3 grid((unsigned)((c->pages.r_w - sc.n_w + DTX - 1) / DTX), (unsigned)((c->pages.r_h - sc.n_h + DTY - 1) / DTY),
               (unsigned)c->sub_np);
-    const uint64_t win = (uint64_t)(c->r_w - sc.n_w) * (c->r_h - sc.n_h) * c->sub_np;
+    const uint64_t win = (uint64_t)(c->pages.r_w - sc.n_w) * (c->pages.r_h - sc.n_h) * c->sub_np;
     char name[64];
     snprintf(name, sizeof name, "scan_direct_kernel<%d,%d>", NDW, MAXH);
     c->launch_begin(name, sc.n_templates, win * sc.n_w * sc.n_h * sc.n_templates, win * NDW * 4 * MAXH * sc.n_templates);
-    hipLaunchKernelGGL((scan_direct_kernel<NDW, MAXH>), grid, dim3(256), 0, c->stream, c->d_pages, (uint32_t)c->pitch,
-                       (uint32_t)c->rows_alloc, (uint32_t)c->r_w, (uint32_t)c->r_h, sc.n_w, sc.n_h,
-                       c->d_direct_bank + c->direct_bank_off[k], c->d_tconst + sc.first, sc.n_templates,
-                       c->fmt, thr_d, c->d_hit_keys, c->d_hit_sims, (unsigned long long *)c->d_counter,
-                       (unsigned long long)c->hit_capacity, (uint32_t)c->sub_p0, rust);
+    hipLaunchKernelGGL((scan_direct_kernel<NDW, MAXH>), grid, dim3(256), 0, c->stream, c->pages.u8, (uint32_t)c->pages.pitch,
+                       (uint32_t)c->pages.rows_alloc, (uint32_t)c->pages.r_w, (uint32_t)c->pages.r_h, sc.n_w, sc.n_h,
+                       c->bank.d_direct_bank + c->bank.direct_bank_off[k], c->bank.d_tconst + sc.first, sc.n_templates,
+                       c->fmt, thr_d, c->d_hit_keys, c->d_hit_sims, c->d_counter.as<unsigned long long>(),
+                       (unsigned long long)c->d_hit_keys.cap, (uint32_t)c->sub_p0, rust);
     c->launch_end();
 }
 
-int ensure_hit_capacity(focr_ctx *c, size_t want) {
-    if (c->hit_capacity >= want) return FOCR_OK;
+// The four hit arrays, one length (exact growth)
+int reserve_hits(focr_ctx *c, size_t want) {
     if (want > ((size_t)1 << 33)) return fail(c, FOCR_ERR_OVERFLOW, "more than 2^33 raw hits in one batch; scan fewer pages per call");
-    FOCR_HIP(c, hipStreamSynchronize(c->stream));
-    for (void *p : {(void *)c->d_hit_keys, (void *)c->d_hit_keys_alt, (void *)c->d_hit_sims, (void *)c->d_hit_sims_alt})
-        if (p) (void)hipFree(p);
-    c->d_hit_keys = c->d_hit_keys_alt = nullptr;
-    c->d_hit_sims = c->d_hit_sims_alt = nullptr;
-    c->hit_capacity = 0;
-    if (hipMalloc(&c->d_hit_keys, want * 8) != hipSuccess || hipMalloc(&c->d_hit_keys_alt, want * 8) != hipSuccess ||
-        hipMalloc(&c->d_hit_sims, want * 4) != hipSuccess || hipMalloc(&c->d_hit_sims_alt, want * 4) != hipSuccess)
+    if (c->d_hit_keys.reserve(want, Grow::exact, &c->stream) || c->d_hit_keys_alt.reserve(want, Grow::exact, &c->stream) ||
+        c->d_hit_sims.reserve(want, Grow::exact, &c->stream) || c->d_hit_sims_alt.reserve(want, Grow::exact, &c->stream)) {
+        c->d_hit_keys.release(), c->d_hit_keys_alt.release(), c->d_hit_sims.release(), c->d_hit_sims_alt.release();
         return fail(c, FOCR_ERR_NOMEM, "hit buffers: hipMalloc failed");
-    c->hit_capacity = want;
+    }
     return FOCR_OK;
 }
 
 int launch_scan_direct(focr_ctx *c, float threshold, int rust) {
     const double thr_d = (double)threshold;  // src/ncc.cpp:83, 288
-    int rc = ensure_hit_capacity(c, std::max<size_t>(c->hit_capacity, std::max<size_t>(1u << 20, c->sub_np * 65536)));
+    int rc = reserve_hits(c, std::max<size_t>(1u << 20, c->sub_np * 65536));
     if (rc) return rc;
     for (int attempt = 0; attempt < 3; attempt++) {
         c->launches_reset();
         FOCR_HIP(c, hipMemsetAsync(c->d_counter, 0, 64 * sizeof(uint32_t), c->stream));
         FOCR_HIP(c, hipEventRecord(c->ev[0], c->stream));
         FOCR_HIP(c, hipEventRecord(c->ev[1], c->stream));
-        for (size_t k = 0; k < c->classes.size(); k++) {
-            const SizeClass &sc = c->classes[k];
-            if (sc.n_w >= c->r_w || sc.n_h >= c->r_h) continue;  // no window with x,y >= 1 fits
+        for (size_t k = 0; k < c->bank.classes.size(); k++) {
+            const SizeClass &sc = c->bank.classes[k];
+            if (sc.n_w >= c->pages.r_w || sc.n_h >= c->pages.r_h) continue;  // no window with x,y >= 1 fits
             if (sc.tall) {
-                if ((rc = launch_scan_tall(c, k, thr_d, c->d_hit_keys, c->d_hit_sims, (unsigned long long *)c->d_counter,
-                                           (unsigned long long)c->hit_capacity, rust)))
+                if ((rc = launch_scan_tall(c, k, thr_d, c->d_hit_keys, c->d_hit_sims, c->d_counter.as<unsigned long long>(),
+                                           (unsigned long long)c->d_hit_keys.cap, rust)))
                     return rc;
                 continue;
             }
@@ -282,7 +277,7 @@ int launch_scan_direct(focr_ctx *c, float threshold, int rust) {
                 default: return fail(c, FOCR_ERR_INVALID, "scan_direct: unsupported size class");
             }
             FOCR_HIP(c, hipGetLastError());
-            c->counters[3] += (uint64_t)(c->r_w - sc.n_w) * (c->r_h - sc.n_h) * sc.ndw * 4 * sc.maxh * sc.n_templates * c->sub_np;
+            c->counters[3] += (uint64_t)(c->pages.r_w - sc.n_w) * (c->pages.r_h - sc.n_h) * sc.ndw * 4 * sc.maxh * sc.n_templates * c->sub_np;
         }
         FOCR_HIP(c, hipEventRecord(c->ev[2], c->stream));
         FOCR_HIP(c, hipEventRecord(c->ev[3], c->stream));
@@ -291,7 +286,7 @@ int launch_scan_direct(focr_ctx *c, float threshold, int rust) {
         FOCR_HIP(c, hipStreamSynchronize(c->stream));
         c->n_hits_raw = n;
         c->n_cand = n;
-        if (n <= c->hit_capacity) {
+        if (n <= c->d_hit_keys.cap) {
             FOCR_HIP(c, hipEventElapsedTime(&c->ms[1], c->ev[1], c->ev[2]));
             c->counters[0] = n;
             c->counters[1] = n;
@@ -299,7 +294,7 @@ int launch_scan_direct(focr_ctx *c, float threshold, int rust) {
             return FOCR_OK;
         }
         c->counters[3] = 0;
-        rc = ensure_hit_capacity(c, (size_t)n + (size_t)n / 8 + 1024);  // grow and rescan
+        rc = reserve_hits(c, (size_t)n + (size_t)n / 8 + 1024);  // grow and rescan
         if (rc) return rc;
     }
     return fail(c, FOCR_ERR_OVERFLOW, "scan_direct: hit buffer kept overflowing");

@@ -44,8 +44,8 @@
 
 namespace focr {
 
-int ensure_hit_capacity(focr_ctx *c, size_t want);
-int sort_keys_u64(focr_ctx *c, uint64_t *&keys, uint64_t *&keys_alt, size_t n, unsigned end_bit);
+int reserve_hits(focr_ctx *c, size_t want);
+int sort_keys_u64(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, size_t n, unsigned end_bit);
 int launch_scan_tall(focr_ctx *c, size_t k, double thr_d, uint64_t *keys, float *sims, unsigned long long *counter,
                      unsigned long long capacity, int rust);
 int compact_candidates(focr_ctx *c, const uint64_t *keys, const float *sims, const uint64_t *flags, uint64_t *pos,
@@ -57,7 +57,7 @@ uint32_t rows_capacity_for(uint64_t row_max);
 int rows2_begin(focr_ctx *c, ClearList &clear);  // the hits-first tail (rows.hip): verify in flush order, then only hits are placed and sorted
 int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c);
 int rows2_place(focr_ctx *c, const unsigned long long *n_cand_p, size_t ub_c, size_t ub_h, bool big_expected, bool sort);
-int sort_pairs_u64_f32(focr_ctx *c, uint64_t *&keys, uint64_t *&keys_alt, float *&vals, float *&vals_alt, size_t n, unsigned end_bit);
+int sort_pairs_u64_f32(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, DevArray<float> &vals, DevArray<float> &vals_alt, size_t n, unsigned end_bit);
 
 
 // ---------------------------------------------------------------------------------------------
@@ -547,14 +547,14 @@ __global__ __launch_bounds__(256) void verify_kernel(const uint64_t *__restrict_
 void layout_supers(focr_ctx *c) {
     // Column drop (mfma_common.h, "threshold planes"): a class of width 4k + 1 (9, 13) gives its last column to the bound
     // and takes the next narrower K layout — BASELINE configs[1]'s 9x15 templates: 2 K-steps instead of 3.
-    for (SizeClass &sc : c->classes) sc.keep_w = (c->column_drop && !sc.tall && (sc.n_w == 9 || sc.n_w == 13)) ? sc.n_w - 1 : sc.n_w;
+    for (SizeClass &sc : c->bank.classes) sc.keep_w = (c->column_drop && !sc.tall && (sc.n_w == 9 || sc.n_w == 13)) ? sc.n_w - 1 : sc.n_w;
     // K layout per class (mfma_common.h).  Narrow classes ride the 12-byte-row layout whenever a 9..12-wide
     // class exists, so that all of them share one set of A fragments (one "super-class", one kernel pass).
     bool any_mid = false;
-    for (const SizeClass &sc : c->classes) any_mid |= (!sc.tall && sc.keep_w >= 9 && sc.keep_w <= 12);
+    for (const SizeClass &sc : c->bank.classes) any_mid |= (!sc.tall && sc.keep_w >= 9 && sc.keep_w <= 12);
     c->supers.clear();
-    for (size_t k = 0; k < c->classes.size(); k++) {
-        SizeClass &sc = c->classes[k];
+    for (size_t k = 0; k < c->bank.classes.size(); k++) {
+        SizeClass &sc = c->bank.classes[k];
         if (sc.tall) {  // scanned exactly by scan_tall_kernel; no quantised copy
             sc.layout = LAYOUT_W16;
             sc.k_groups = sc.n_tiles16 = 0;
@@ -586,7 +586,7 @@ void layout_supers(focr_ctx *c) {
         q_bytes += (size_t)su.n_tiles * su.ksteps * 1024;
         tg_entries += (size_t)su.n_tiles * 16;
         for (size_t i = 0; i < su.classes.size(); i++) {
-            SizeClass &sc = c->classes[su.classes[i]];
+            SizeClass &sc = c->bank.classes[su.classes[i]];
             sc.q_offset = (uint32_t)(su.q_offset + (size_t)su.tile_first[i] * su.ksteps * 1024);
             sc.tg_offset = (uint32_t)(su.tg_offset + (size_t)su.tile_first[i] * 16);
         }
@@ -611,7 +611,7 @@ static std::vector<uint32_t> live_first_slots(const std::vector<std::vector<doub
 
 // Quantise the bank (header comment; column drop: mfma_common.h).  `dense` holds the class-ordered dense needles.  Host only:
 // fills the per-lane MFMA operand image of every class, the class-ordered template ids (~0 = dead / padding) and
-// c->mfma_c_scale / mfma_e_max / mfma_rho_max.
+// c->bank.mfma_c_scale / mfma_e_max / mfma_rho_max.
 int quantise_bank(focr_ctx *c, const uint8_t *dense, std::vector<int8_t> &qbank, std::vector<uint32_t> &tglobal, std::vector<uint32_t> &order_of) {
     layout_supers(c);
     size_t q_bytes = 0, tg_entries = 0;
@@ -622,28 +622,28 @@ int quantise_bank(focr_ctx *c, const uint8_t *dense, std::vector<int8_t> &qbank,
     qbank.assign(q_bytes, 0);
     tglobal.assign(tg_entries, 0xffffffffu);
     order_of.assign(c->n_templates, 0);
-    c->mfma_slot.assign(c->h_tconst.size(), 0);
-    c->mfma_c_scale.clear();
-    c->mfma_e_max.clear();
-    c->mfma_rho_max.clear();
-    for (size_t k = 0; k < c->classes.size(); k++) {
-        SizeClass &sc = c->classes[k];
+    c->mfma_slot.assign(c->bank.h_tconst.size(), 0);
+    c->bank.mfma_c_scale.clear();
+    c->bank.mfma_e_max.clear();
+    c->bank.mfma_rho_max.clear();
+    for (size_t k = 0; k < c->bank.classes.size(); k++) {
+        SizeClass &sc = c->bank.classes[k];
         const uint32_t n = sc.n_w * sc.n_h, ksteps = sc.k_groups / 4, kw = sc.keep_w, n_k = kw * sc.n_h;
         sc.n_live = 0;
         if (sc.tall) {
-            for (uint32_t i = 0; i < sc.n_templates; i++) order_of[c->h_tconst[sc.first + i].index] = sc.first + i;
-            c->mfma_c_scale.push_back(1.0);
-            c->mfma_e_max.push_back(0.0);
-            c->mfma_rho_max.push_back(0.0);
+            for (uint32_t i = 0; i < sc.n_templates; i++) order_of[c->bank.h_tconst[sc.first + i].index] = sc.first + i;
+            c->bank.mfma_c_scale.push_back(1.0);
+            c->bank.mfma_e_max.push_back(0.0);
+            c->bank.mfma_rho_max.push_back(0.0);
             continue;
         }
         // unit mean-centred templates beta; on the kept columns beta' = beta + sigma / n_k (sigma = the dropped column's sum)
         std::vector<std::vector<double>> bp(sc.n_templates);
         double max_ratio = 0.0, rho_max = 0.0;
         for (uint32_t i = 0; i < sc.n_templates; i++) {
-            const TemplateConst &tc = c->h_tconst[sc.first + i];
+            const TemplateConst &tc = c->bank.h_tconst[sc.first + i];
             order_of[tc.index] = sc.first + i;
-            const uint8_t *nd = dense + c->h_needle_off[sc.first + i];
+            const uint8_t *nd = dense + c->bank.h_needle_off[sc.first + i];
             double s = 0, s2 = 0;
             for (uint32_t p = 0; p < n; p++) {
                 s += nd[p];
@@ -672,7 +672,7 @@ int quantise_bank(focr_ctx *c, const uint8_t *dense, std::vector<int8_t> &qbank,
         for (uint32_t i = 0; i < sc.n_templates; i++) {
             c->mfma_slot[sc.first + i] = slot[i];
             if (bp[i].empty()) continue;
-            tglobal[sc.tg_offset + slot[i]] = c->h_tconst[sc.first + i].index;
+            tglobal[sc.tg_offset + slot[i]] = c->bank.h_tconst[sc.first + i].index;
             sc.n_live++;
         }
         const double c_scale = max_ratio > 0 ? 126.0 / max_ratio : 1.0;
@@ -713,9 +713,9 @@ int quantise_bank(focr_ctx *c, const uint8_t *dense, std::vector<int8_t> &qbank,
                     qbank[sc.q_offset + ((size_t)(nt * ksteps + ks) * 64 + g * 16 + nn) * 16 + byte] = (int8_t)bq[j * kw + x];
                 }
         }
-        c->mfma_c_scale.push_back(c_scale);
-        c->mfma_e_max.push_back(e_max);
-        c->mfma_rho_max.push_back(rho_max);
+        c->bank.mfma_c_scale.push_back(c_scale);
+        c->bank.mfma_e_max.push_back(e_max);
+        c->bank.mfma_rho_max.push_back(rho_max);
     }
     return FOCR_OK;
 }
@@ -724,67 +724,59 @@ int build_mfma_bank(focr_ctx *c, const uint8_t *dense) {
     std::vector<int8_t> qbank;
     std::vector<uint32_t> tglobal, order_of;
     if (int rc = quantise_bank(c, dense, qbank, tglobal, order_of)) return rc;
-    FOCR_HIP(c, hipMalloc((void **)&c->d_qbank, qbank.size() ? qbank.size() : 16));
-    FOCR_HIP(c, hipMemcpy(c->d_qbank, qbank.data(), qbank.size(), hipMemcpyHostToDevice));
-    FOCR_HIP(c, hipMalloc((void **)&c->d_tglobal, tglobal.size() ? tglobal.size() * 4 : 16));
-    FOCR_HIP(c, hipMemcpy(c->d_tglobal, tglobal.data(), tglobal.size() * 4, hipMemcpyHostToDevice));
+    if (int rc = c->upload(c->bank.d_qbank, qbank.data(), qbank.size(), 16)) return rc;  // (at least 16 bytes: never a null operand)
+    if (int rc = c->upload(c->bank.d_tglobal, tglobal.data(), tglobal.size(), 4)) return rc;
     // verify operand: every template as n_h rows of 16 bytes (zero padded), class-ordered
     std::vector<uint8_t> n16;
-    std::vector<uint32_t> n16_row(c->h_tconst.size(), 0);
-    for (size_t ci = 0; ci < c->h_tconst.size(); ci++) {
-        const TemplateConst &tc = c->h_tconst[ci];
+    std::vector<uint32_t> n16_row(c->bank.h_tconst.size(), 0);
+    for (size_t ci = 0; ci < c->bank.h_tconst.size(); ci++) {
+        const TemplateConst &tc = c->bank.h_tconst[ci];
         n16_row[ci] = (uint32_t)(n16.size() / 16);
-        const uint8_t *nd = dense + c->h_needle_off[ci];
+        const uint8_t *nd = dense + c->bank.h_needle_off[ci];
         const uint32_t row_bytes = tc.n_w > 16 ? 32 : 16;
         for (uint32_t j = 0; j < tc.n_h; j++)
             for (uint32_t x = 0; x < row_bytes; x++) n16.push_back(x < tc.n_w ? nd[j * tc.n_w + x] : 0);
     }
-    FOCR_HIP(c, hipMalloc((void **)&c->d_needles16, n16.size() ? n16.size() : 16));
-    FOCR_HIP(c, hipMemcpy(c->d_needles16, n16.data(), n16.size(), hipMemcpyHostToDevice));
+    if (int rc = c->upload(c->bank.d_needles16, n16.data(), n16.size(), 16)) return rc;
     {  // the verify's per-template record, by global template index
         std::vector<VerifyMeta> vm(c->n_templates);
-        for (size_t ci = 0; ci < c->h_tconst.size(); ci++) {
-            const TemplateConst &tc = c->h_tconst[ci];
+        for (size_t ci = 0; ci < c->bank.h_tconst.size(); ci++) {
+            const TemplateConst &tc = c->bank.h_tconst[ci];
             vm[tc.index] = VerifyMeta{tc.s_n, tc.n_recip, tc.rnorm_n, (uint16_t)tc.n_w, (uint16_t)tc.n_h, n16_row[ci]};
         }
-        FOCR_HIP(c, hipMalloc(&c->d_vmeta, vm.size() * sizeof(VerifyMeta)));
-        FOCR_HIP(c, hipMemcpy(c->d_vmeta, vm.data(), vm.size() * sizeof(VerifyMeta), hipMemcpyHostToDevice));
+        if (int rc = c->upload(c->bank.d_vmeta, vm.data(), vm.size())) return rc;
     }
     {  // the same operand by GLOBAL template index, as rows of 12 bytes (every template at most 12 px wide) or 16: chunks of consecutive
        // templates are contiguous there (verify_chunks_kernel, rows.hip: banks whose operand does not fit the LDS whole)
         uint32_t max_w = 0;
-        for (const TemplateConst &tc : c->h_tconst) max_w = std::max<uint32_t>(max_w, tc.n_w);
-        c->vrow_bytes = max_w <= 12 ? 12u : max_w <= 16 ? 16u : 0u;
-        c->h_vrow0_t.assign(c->n_templates + 1, 0);
-        if (c->vrow_bytes) {
+        for (const TemplateConst &tc : c->bank.h_tconst) max_w = std::max<uint32_t>(max_w, tc.n_w);
+        c->bank.vrow_bytes = max_w <= 12 ? 12u : max_w <= 16 ? 16u : 0u;
+        c->bank.h_vrow0_t.assign(c->n_templates + 1, 0);
+        if (c->bank.vrow_bytes) {
             std::vector<size_t> ci_of(c->n_templates, 0);
-            for (size_t ci = 0; ci < c->h_tconst.size(); ci++) ci_of[c->h_tconst[ci].index] = ci;
-            for (size_t t = 0; t < c->n_templates; t++) c->h_vrow0_t[t + 1] = c->h_vrow0_t[t] + c->h_tconst[ci_of[t]].n_h;
-            std::vector<uint8_t> rows((size_t)c->h_vrow0_t[c->n_templates] * c->vrow_bytes + 16, 0);
+            for (size_t ci = 0; ci < c->bank.h_tconst.size(); ci++) ci_of[c->bank.h_tconst[ci].index] = ci;
+            for (size_t t = 0; t < c->n_templates; t++) c->bank.h_vrow0_t[t + 1] = c->bank.h_vrow0_t[t] + c->bank.h_tconst[ci_of[t]].n_h;
+            std::vector<uint8_t> rows((size_t)c->bank.h_vrow0_t[c->n_templates] * c->bank.vrow_bytes + 16, 0);
             std::vector<VerifyMeta> vm(c->n_templates);
             for (size_t t = 0; t < c->n_templates; t++) {
-                const TemplateConst &tc = c->h_tconst[ci_of[t]];
-                const uint8_t *nd = dense + c->h_needle_off[ci_of[t]];
-                for (uint32_t j = 0; j < tc.n_h; j++) memcpy(&rows[((size_t)c->h_vrow0_t[t] + j) * c->vrow_bytes], nd + (size_t)j * tc.n_w, tc.n_w);
-                vm[t] = VerifyMeta{tc.s_n, tc.n_recip, tc.rnorm_n, (uint16_t)tc.n_w, (uint16_t)tc.n_h, c->h_vrow0_t[t]};
+                const TemplateConst &tc = c->bank.h_tconst[ci_of[t]];
+                const uint8_t *nd = dense + c->bank.h_needle_off[ci_of[t]];
+                for (uint32_t j = 0; j < tc.n_h; j++) memcpy(&rows[((size_t)c->bank.h_vrow0_t[t] + j) * c->bank.vrow_bytes], nd + (size_t)j * tc.n_w, tc.n_w);
+                vm[t] = VerifyMeta{tc.s_n, tc.n_recip, tc.rnorm_n, (uint16_t)tc.n_w, (uint16_t)tc.n_h, c->bank.h_vrow0_t[t]};
             }
-            FOCR_HIP(c, hipMalloc((void **)&c->d_vrows_t, rows.size()));
-            FOCR_HIP(c, hipMemcpy(c->d_vrows_t, rows.data(), rows.size(), hipMemcpyHostToDevice));
-            FOCR_HIP(c, hipMalloc(&c->d_vmeta_t, vm.size() * sizeof(VerifyMeta)));
-            FOCR_HIP(c, hipMemcpy(c->d_vmeta_t, vm.data(), vm.size() * sizeof(VerifyMeta), hipMemcpyHostToDevice));
+            if (int rc = c->upload(c->bank.d_vrows_t, rows.data(), rows.size())) return rc;
+            if (int rc = c->upload(c->bank.d_vmeta_t, vm.data(), vm.size())) return rc;
         }
     }
-    FOCR_HIP(c, hipMalloc((void **)&c->d_needle16_row, n16_row.size() * 4));
-    FOCR_HIP(c, hipMemcpy(c->d_needle16_row, n16_row.data(), n16_row.size() * 4, hipMemcpyHostToDevice));
-    FOCR_HIP(c, hipMalloc((void **)&c->d_order_of, order_of.size() * 4));
-    FOCR_HIP(c, hipMemcpy(c->d_order_of, order_of.data(), order_of.size() * 4, hipMemcpyHostToDevice));
+    if (int rc = c->upload(c->bank.d_needle16_row, n16_row.data(), n16_row.size())) return rc;
+    if (int rc = c->upload(c->bank.d_order_of, order_of.data(), order_of.size())) return rc;
     return FOCR_OK;
 }
 
 // Threshold parameters of one size class for one scan (mfma_common.h, "threshold planes"): kq towards -inf, crk upwards.
 PlaneParams plane_params(const focr_ctx *c, size_t k, double thr_d) {
-    const SizeClass &sc = c->classes[k];
-    const double cs = c->mfma_c_scale[k], em = c->mfma_e_max[k], rho = c->mfma_rho_max[k];
+    const SizeClass &sc = c->bank.classes[k];
+    const double cs = c->bank.mfma_c_scale[k], em = c->bank.mfma_e_max[k], rho = c->bank.mfma_rho_max[k];
     const double n = (double)sc.n_w * sc.n_h, n_k = (double)sc.keep_w * sc.n_h, D = n - n_k;
     // kappa carries a relative 1e-4 for the f64 roundings of the reference's formula (its similarity differs from the real
     // number by far less)
@@ -831,7 +823,7 @@ constexpr uint32_t S8_BANDS_MAX = 2;
 template <int OUT>
 static int launch_stats(focr_ctx *c, size_t k, int pair, double thr_d, void *out, void *out_pair, uint32_t Lpitch, uint32_t Lrows, uint8_t *live,
                         uint32_t mtx, uint32_t n_rows, uint64_t *append_list = nullptr, uint32_t *append_count = nullptr) {
-    const SizeClass &sc = c->classes[k];
+    const SizeClass &sc = c->bank.classes[k];
     // only what the scan kernels read: the windows of the pass's M-tiles (x < 16 * mtx) in the searched rows (y <= n_rows)
     dim3 grid(std::min<unsigned>(Lpitch / STX, (16 * mtx + STX - 1) / STX), std::min<unsigned>((Lrows + STY - 1) / STY, (n_rows + 1 + STY - 1) / STY),
               (unsigned)c->sub_np);
@@ -848,8 +840,8 @@ static int launch_stats(focr_ctx *c, size_t k, int pair, double thr_d, void *out
         const uint64_t n_wgs = (uint64_t)sgroups * bgroups * c->sub_np;
         if (n_wgs >= 0x7fffffffull) return fail(c, FOCR_ERR_INVALID, "scan_mfma: batch too large for 32-bit tile ids; scan fewer pages per call");
         auto launch8 = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)n_wgs), dim3(GS * GB * 64), 0, c->stream, c->d_pages + c->sub_p0 * c->rows_alloc * c->pitch, (uint32_t)c->pitch,
-                               (uint32_t)c->rows_alloc, (uint32_t)c->r_w, (uint32_t)c->r_h, sc.n_w, sc.n_h, A, B, Lpitch, Lrows, live, mtx, n_rows, strips_x, bands_y,
+            hipLaunchKernelGGL(kern, dim3((unsigned)n_wgs), dim3(GS * GB * 64), 0, c->stream, c->pages.u8 + c->sub_p0 * c->pages.rows_alloc * c->pages.pitch, (uint32_t)c->pages.pitch,
+                               (uint32_t)c->pages.rows_alloc, (uint32_t)c->pages.r_w, (uint32_t)c->pages.r_h, sc.n_w, sc.n_h, A, B, Lpitch, Lrows, live, mtx, n_rows, strips_x, bands_y,
                                GS, GB, sgroups, bgroups, append_list, append_count);
         };
 #define S8_DROPS(KQ, AP)                                                                                                                         \
@@ -876,8 +868,8 @@ static int launch_stats(focr_ctx *c, size_t k, int pair, double thr_d, void *out
         return FOCR_OK;
     }
     auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, dim3(256), stats_lds_bytes(sc.n_h), c->stream, c->d_pages + c->sub_p0 * c->rows_alloc * c->pitch, (uint32_t)c->pitch,
-                           (uint32_t)c->rows_alloc, (uint32_t)c->r_w, (uint32_t)c->r_h, sc.n_w, sc.n_h, A, B, Lpitch, Lrows, live, mtx, n_rows);
+        hipLaunchKernelGGL(kern, grid, dim3(256), stats_lds_bytes(sc.n_h), c->stream, c->pages.u8 + c->sub_p0 * c->pages.rows_alloc * c->pages.pitch, (uint32_t)c->pages.pitch,
+                           (uint32_t)c->pages.rows_alloc, (uint32_t)c->pages.r_w, (uint32_t)c->pages.r_h, sc.n_w, sc.n_h, A, B, Lpitch, Lrows, live, mtx, n_rows);
     };
 #define STATS_CASE(NDW)                                                                          \
     case NDW:                                                                                    \
@@ -895,23 +887,10 @@ static int launch_stats(focr_ctx *c, size_t k, int pair, double thr_d, void *out
 }
 
 VerifyArgs verify_args(const focr_ctx *c, double thr_d) {
-    return VerifyArgs{c->d_pages, (uint32_t)c->pitch, (uint32_t)c->rows_alloc, c->fmt, c->d_order_of, c->d_tconst,
-                      reinterpret_cast<const v4i *>(c->d_needles16), c->d_needle16_row, thr_d, reinterpret_cast<const VerifyMeta *>(c->d_vmeta),
+    return VerifyArgs{c->pages.u8, (uint32_t)c->pages.pitch, (uint32_t)c->pages.rows_alloc, c->fmt, c->bank.d_order_of, c->bank.d_tconst,
+                      c->bank.d_needles16.as<const v4i>(), c->bank.d_needle16_row, thr_d, c->bank.d_vmeta.p,
                       (uint32_t)c->n_templates, (uint32_t)c->n_pages,
-                      (uint32_t)c->r_w, (uint32_t)c->r_h, (unsigned long long *)(c->d_res + 4)};
-}
-
-// The buffers the scan sizes itself: exactly `want` entries of T, unless the buffer already holds `have` >= want (plan_scan, legacy_tail).
-template <typename T>
-static int ensure_exact(focr_ctx *c, T *&p, size_t &have, size_t want, const char *what) {
-    if (have >= want) return FOCR_OK;
-    FOCR_HIP(c, hipStreamSynchronize(c->stream));
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    have = 0;
-    if (hipMalloc((void **)&p, want * sizeof(T)) != hipSuccess) return fail(c, FOCR_ERR_NOMEM, std::string("scan_mfma: hipMalloc(") + what + ") failed");
-    have = want;
-    return FOCR_OK;
+                      (uint32_t)c->pages.r_w, (uint32_t)c->pages.r_h, (unsigned long long *)(c->d_res + 4)};
 }
 
 // Process-wide hand-over between the contexts of one device (events are never destroyed).  A Turn holds the chain's lock from its wait
@@ -957,7 +936,7 @@ static size_t pass_planes(const focr_ctx *c, const SuperClass &su, size_t plane)
     return ok ? n : 0;
 }
 
-// The passes of a scan of c->sub_np pages of c->r_w x c->r_h (host only; also what the host model reports, prefilter_model.hip): per
+// The passes of a scan of c->sub_np pages of c->pages.r_w x c->pages.r_h (host only; also what the host model reports, prefilter_model.hip): per
 // super-class the window enumeration, the offset of its M-tiles in the work list and of its planes in d_planes (`plane`: int16 values
 // of one plane).  Totals: M-tiles of all passes, plane values, and whether a pass takes the int32 tables.
 int plan_passes(focr_ctx *c, size_t plane, size_t &tiles_total, size_t &plane_vals, bool &need_L) {
@@ -967,8 +946,8 @@ int plan_passes(focr_ctx *c, size_t plane, size_t &tiles_total, size_t &plane_va
         // windows of the pass: those of its smallest searchable class
         su.min_w = su.min_h = 0xffffffffu;
         for (uint32_t k : su.classes) {
-            const SizeClass &sc = c->classes[k];
-            if (sc.n_w >= c->r_w || sc.n_h >= c->r_h) continue;
+            const SizeClass &sc = c->bank.classes[k];
+            if (sc.n_w >= c->pages.r_w || sc.n_h >= c->pages.r_h) continue;
             su.min_w = std::min(su.min_w, sc.n_w);
             su.min_h = std::min(su.min_h, sc.n_h);
         }
@@ -976,8 +955,8 @@ int plan_passes(focr_ctx *c, size_t plane, size_t &tiles_total, size_t &plane_va
         su.live_offset = tiles_total;
         su.planes = false;
         if (su.min_w == 0xffffffffu) continue;  // nothing searchable
-        su.mtx = (uint32_t)((c->r_w - su.min_w + 1 + 15) / 16);  // windows x in [0, r_w - min n_w]
-        su.n_rows = (uint32_t)(c->r_h - su.min_h);               // y in [1, r_h - min n_h]
+        su.mtx = (uint32_t)((c->pages.r_w - su.min_w + 1 + 15) / 16);  // windows x in [0, r_w - min n_w]
+        su.n_rows = (uint32_t)(c->pages.r_h - su.min_h);               // y in [1, r_h - min n_h]
         const uint64_t nt = (uint64_t)su.mtx * su.n_rows * c->sub_np;
         if (nt >= 0x7fffffffull) return fail(c, FOCR_ERR_INVALID, "scan_mfma: batch too large for 32-bit tile ids; scan fewer pages per call");
         tiles_total += (size_t)nt;
@@ -991,21 +970,25 @@ int plan_passes(focr_ctx *c, size_t plane, size_t &tiles_total, size_t &plane_va
 }
 
 static int plan_scan(focr_ctx *c, bool nothing, size_t want_cand, ScanPlan &P) {
-    if (int rc = ensure_exact(c, c->d_cand, c->cand_capacity, want_cand, "cand")) return rc;
+    // the buffers the scan sizes itself: exactly what is wanted, unless they already hold that much
+    const auto exact = [c](auto &a, size_t want, const char *what) {
+        return a.reserve(want, Grow::exact, &c->stream) ? fail(c, FOCR_ERR_NOMEM, std::string("scan_mfma: hipMalloc(") + what + ") failed") : FOCR_OK;
+    };
+    if (int rc = exact(c->d_cand, want_cand, "cand")) return rc;
     if (nothing) return FOCR_OK;  // no statistics, no scan
     if (c->supers.size() > 40) return fail(c, FOCR_ERR_INVALID, "scan_mfma: too many super-classes");
-    P.Lpitch = (uint32_t)((c->r_w + 63) / 64 * 64 + 64);
-    P.Lrows = (uint32_t)((c->r_h + 7) / 8 * 8 + 8);
+    P.Lpitch = (uint32_t)((c->pages.r_w + 63) / 64 * 64 + 64);
+    P.Lrows = (uint32_t)((c->pages.r_h + 7) / 8 * 8 + 8);
     P.L_per_class = c->n_pages * (size_t)P.Lrows * P.Lpitch;
     P.plane = c->sub_np * (size_t)P.Lrows * P.Lpitch;
     size_t plane_vals = 0;
     bool need_L = false;
     if (int rc = plan_passes(c, P.plane, P.tiles_total, plane_vals, need_L)) return rc;
-    if (int rc = ensure_exact(c, c->d_L, c->L_values, need_L ? P.L_per_class * c->classes.size() : 0, "negL")) return rc;
-    if (int rc = ensure_exact(c, c->d_planes, c->plane_values, plane_vals, "planes")) return rc;
-    P.live = (uint8_t *)c->scan_live.ensure(c, P.tiles_total + 24);
-    P.live_list = (uint64_t *)c->scan_live_list.ensure(c, (P.tiles_total + 16) * 8);
-    if (!P.live || !P.live_list) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc failed");
+    if (int rc = exact(c->d_L, need_L ? P.L_per_class * c->bank.classes.size() : 0, "negL")) return rc;
+    if (int rc = exact(c->d_planes, plane_vals, "planes")) return rc;
+    if (!c->scratch(c->scan_live, P.tiles_total + 24) || !c->scratch(c->scan_live_list, P.tiles_total + 16)) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc failed");
+    P.live = c->scan_live;
+    P.live_list = c->scan_live_list;
     return FOCR_OK;
 }
 
@@ -1028,7 +1011,7 @@ static int stats_phase(focr_ctx *c, const ScanPlan &P, ClearList &clear, double 
         std::vector<size_t> order;  // classes whose last column is dropped first: they can take their kept box along
         for (int pass = 0; pass < 2; pass++)
             for (size_t v = 0; v < su.classes.size(); v++)
-                if ((c->classes[su.classes[v]].keep_w != c->classes[su.classes[v]].n_w) == (pass == 0)) order.push_back(v);
+                if ((c->bank.classes[su.classes[v]].keep_w != c->bank.classes[su.classes[v]].n_w) == (pass == 0)) order.push_back(v);
         struct StatsLaunch {
             size_t v, k, pv;
             int pair;
@@ -1037,15 +1020,15 @@ static int stats_phase(focr_ctx *c, const ScanPlan &P, ClearList &clear, double 
         for (size_t v : order) {
             if (done[v]) continue;
             const size_t k = su.classes[v];
-            const SizeClass &sc = c->classes[k];
-            if (!su.planes && (sc.n_w >= c->r_w || sc.n_h >= c->r_h)) continue;  // nothing searchable: its tiles are skipped by the scan
+            const SizeClass &sc = c->bank.classes[k];
+            if (!su.planes && (sc.n_w >= c->pages.r_w || sc.n_h >= c->pages.r_h)) continue;  // nothing searchable: its tiles are skipped by the scan
             // a class whose last column is dropped computes its kept box's statistics anyway: if that box is a size class
             // of this pass too, both come out of one launch
             int pair = -1;
             size_t pv = 0;
             if (sc.keep_w != sc.n_w)
                 for (size_t u = 0; u < su.classes.size(); u++) {
-                    const SizeClass &o = c->classes[su.classes[u]];
+                    const SizeClass &o = c->bank.classes[su.classes[u]];
                     if (u != v && !done[u] && o.n_w == sc.keep_w && o.n_h == sc.n_h && o.keep_w == o.n_w) pair = (int)su.classes[u], pv = u;
                 }
             todo.push_back(StatsLaunch{v, k, pv, pair});
@@ -1056,8 +1039,8 @@ static int stats_phase(focr_ctx *c, const ScanPlan &P, ClearList &clear, double 
         // list itself (stats8_kernel, APPEND) — no mark bytes, no compaction launch in front of the scan kernel
         // (several launches: one in the register form goes LAST and merges the marks the others left in `live`)
         for (size_t i = 0; i + 1 < todo.size(); i++)
-            if (stats_register_form(c, c->classes[todo[i].k]) && !stats_register_form(c, c->classes[todo.back().k])) std::swap(todo[i], todo.back());
-        const bool direct = su.planes && !todo.empty() && stats_register_form(c, c->classes[todo.back().k]);
+            if (stats_register_form(c, c->bank.classes[todo[i].k]) && !stats_register_form(c, c->bank.classes[todo.back().k])) std::swap(todo[i], todo.back());
+        const bool direct = su.planes && !todo.empty() && stats_register_form(c, c->bank.classes[todo.back().k]);
         for (const StatsLaunch &L : todo) {
             if (su.planes) {
                 uint16_t *base = c->d_planes + su.plane_off;
@@ -1112,11 +1095,11 @@ static int scan_phase(focr_ctx *c, const ScanPlan &P, double thr_d) {
                 uint32_t t1 = t0;
                 PlaneArgs A3{};
                 for (size_t i = 0; i < su.classes.size() && L.segs.n < (uint32_t)MAX_SEGS; i++) {
-                    const SizeClass &sc = c->classes[su.classes[i]];
+                    const SizeClass &sc = c->bank.classes[su.classes[i]];
                     const uint32_t cb = su.tile_first[i], ce = cb + sc.n_tiles16;
                     const uint32_t b = std::max(cb, t1), e = std::min(ce, t_limit);
                     if (b >= e || b != t1) continue;  // segments must tile [t0, t1) contiguously
-                    if (!su.planes && (sc.n_w >= c->r_w || sc.n_h >= c->r_h)) {  // no searchable window: skip the class's tiles
+                    if (!su.planes && (sc.n_w >= c->pages.r_w || sc.n_h >= c->pages.r_h)) {  // no searchable window: skip the class's tiles
                         if (L.segs.n == 0) {
                             t0 = t1 = e;
                             continue;
@@ -1133,8 +1116,8 @@ static int scan_phase(focr_ctx *c, const ScanPlan &P, double thr_d) {
                     sg.tile_end = e - t0;
                     const uint32_t real = std::min(sc.n_templates, (e - cb) * 16) - (b - cb) * 16;
                     L.n_templates += real;
-                    if (sc.n_w < c->r_w && sc.n_h < c->r_h)
-                        L.alg_macs += (uint64_t)(c->r_w - sc.n_w) * (c->r_h - sc.n_h) * sc.n_w * sc.n_h * real * c->sub_np;
+                    if (sc.n_w < c->pages.r_w && sc.n_h < c->pages.r_h)
+                        L.alg_macs += (uint64_t)(c->pages.r_w - sc.n_w) * (c->pages.r_h - sc.n_h) * sc.n_w * sc.n_h * real * c->sub_np;
                     t1 = e;
                 }
                 if (L.segs.n == 0) {
@@ -1161,10 +1144,10 @@ static int scan_phase(focr_ctx *c, const ScanPlan &P, double thr_d) {
         }
     }
     // tall classes: exact scan straight into the candidate list
-    for (size_t k = 0; k < c->classes.size(); k++) {
-        const SizeClass &sc = c->classes[k];
-        if (!sc.tall || sc.n_w >= c->r_w || sc.n_h >= c->r_h) continue;
-        if ((rc = launch_scan_tall(c, k, thr_d, c->d_cand, nullptr, (unsigned long long *)c->d_counter + 1, (unsigned long long)c->ub_cand, 0))) return rc;
+    for (size_t k = 0; k < c->bank.classes.size(); k++) {
+        const SizeClass &sc = c->bank.classes[k];
+        if (!sc.tall || sc.n_w >= c->pages.r_w || sc.n_h >= c->pages.r_h) continue;
+        if ((rc = launch_scan_tall(c, k, thr_d, c->d_cand, nullptr, c->d_counter.as<unsigned long long>() + 1, (unsigned long long)c->ub_cand, 0))) return rc;
     }
     return FOCR_OK;
 }
@@ -1194,12 +1177,11 @@ static int row_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_
 // 3b. legacy tail: sort the candidates into emission order, verify them exactly in place, compact + cap (order.hip)
 static int legacy_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c) {
     c->row_cap = 0;
-    int rc = ensure_hit_capacity(c, std::max<size_t>(c->hit_capacity, ub_c + 1));
+    int rc = reserve_hits(c, ub_c + 1);
     if (rc) return rc;
-    uint64_t *flags = (uint64_t *)c->scan_flags.ensure(c, (ub_c + 1) * 8);
-    uint64_t *pos = (uint64_t *)c->scan_pos.ensure(c, (ub_c + 1) * 8);
-    if (!flags || !pos) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc failed");
-    if ((rc = ensure_exact(c, c->d_cand_alt, c->cand_alt_capacity, c->cand_capacity, "cand_alt"))) return rc;
+    if (!c->scratch(c->scan_flags, (ub_c + 1) * 8) || !c->scratch(c->scan_pos, (ub_c + 1) * 8)) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc failed");
+    uint64_t *flags = c->scan_flags.as<uint64_t>(), *pos = c->scan_pos.as<uint64_t>();
+    if (c->d_cand_alt.reserve(c->d_cand.cap, Grow::exact, &c->stream)) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc(cand_alt) failed");
     if ((rc = sort_keys_u64(c, c->d_cand, c->d_cand_alt, ub_c, c->fmt.bits()))) return rc;
     hipLaunchKernelGGL(verify_kernel, dim3((unsigned)((ub_c + 1 + 255) / 256)), dim3(256), 0, c->stream, c->d_cand, n_cand_p, (unsigned long long)ub_c,
                        verify_args(c, thr_d), c->d_hit_sims, flags);
@@ -1221,9 +1203,9 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
     // `sim > +inf` is never true (NaN thresholds arrive here as +inf, focr_scan): no statistics, no scan, zero candidates
     // (kappa would be inf - inf = NaN and every window of every live tile a candidate for verify to reject)
     const bool nothing = !(thr_d < (double)INFINITY);
-    int rc = ensure_hit_capacity(c, std::max<size_t>(c->hit_capacity, std::max<size_t>(1u << 20, c->sub_np * 65536)));
+    int rc = reserve_hits(c, std::max<size_t>(1u << 20, c->sub_np * 65536));
     if (rc) return rc;
-    size_t want_cand = std::max<size_t>(c->cand_capacity, std::max<size_t>(1u << 21, c->sub_np * 131072));
+    size_t want_cand = std::max<size_t>(c->d_cand.cap, std::max<size_t>(1u << 21, c->sub_np * 131072));
     if (c->estimated) want_cand = std::max(want_cand, c->est.cand);
     for (int attempt = 0; attempt < 4; attempt++) {
         ScanPlan P;
@@ -1238,7 +1220,7 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
         // verify (two waits), so every later phase runs on exact sizes.  Estimated mode (ctx.hip: same setup as the
         // previous scan): the counts stay on the device, grids and buffers take the previous counts + a margin (4 .. 20 %, ctx.hip) as bounds,
         // unused candidate slots hold the largest key so that the sort leaves them at the end; nothing waits.
-        c->ub_cand = c->estimated ? std::min(c->est.cand, c->cand_capacity) : c->cand_capacity;
+        c->ub_cand = c->estimated ? std::min(c->est.cand, c->d_cand.cap) : c->d_cand.cap;
         // Tail: the row path (rows.hip) unless a row could exceed its capacity — exact mode finds out after the scan kernels,
         // estimated mode goes by the previous scan's largest row + 25 % (a larger one sets the overflow bit: batch redone).
         bool use_rows = rows_applicable(c);
@@ -1257,13 +1239,13 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
         }
         FOCR_HIP(c, hipEventRecord(c->ev[2], c->stream));
         FOCR_HIP(c, hipMemcpyAsync(c->h_live, c->d_counter + 8, 40 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        const unsigned long long *n_cand_p = (const unsigned long long *)c->d_counter + 1;
+        const unsigned long long *n_cand_p = c->d_counter.as<const unsigned long long>() + 1;
         size_t ub_c = c->ub_cand;
         if (!c->estimated) {
             unsigned long long n_cand = 0;
             FOCR_HIP(c, hipMemcpyAsync(&n_cand, n_cand_p, 8, hipMemcpyDeviceToHost, c->stream));
             FOCR_HIP(c, hipStreamSynchronize(c->stream));
-            if (n_cand > c->cand_capacity) {
+            if (n_cand > c->d_cand.cap) {
                 if (n_cand > ((unsigned long long)1 << 31)) return fail(c, FOCR_ERR_OVERFLOW, "scan_mfma: more than 2^31 candidates in one pass");
                 want_cand = (size_t)n_cand + (size_t)n_cand / 8 + 1024;
                 continue;

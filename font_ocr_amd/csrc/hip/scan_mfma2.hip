@@ -401,9 +401,9 @@ static void launch_v2s(focr_ctx *c, const MfmaLaunch &L, const PlaneArgs &A3, un
     char name[64];
     snprintf(name, sizeof name, "scan_mfma2s_kernel<%d,%d,%d,%d>", KSTEPS, RPG, MT, NW);
     c->launch_begin(name, L.n_templates | (L.super_index << 24), L.alg_macs, issued);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, c->stream, c->d_pages_i8 + c->sub_p0 * c->rows_alloc * c->pitch, (uint32_t)c->pitch, (uint32_t)c->rows_alloc,
-                       L.live_list, L.live_count, (uint32_t)c->sub_p0, reinterpret_cast<const v4i *>(c->d_qbank + L.q_offset), n_tiles16, L.segs, L.Lpitch, L.Lrows, A3,
-                       c->d_tglobal + L.tg_offset, c->fmt, c->d_cand, (unsigned long long *)c->d_counter + 1, (unsigned long long)c->ub_cand, L.queue, c->row_hist);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, c->stream, c->pages.i8 + c->sub_p0 * c->pages.rows_alloc * c->pages.pitch, (uint32_t)c->pages.pitch, (uint32_t)c->pages.rows_alloc,
+                       L.live_list, L.live_count, (uint32_t)c->sub_p0, reinterpret_cast<const v4i *>(c->bank.d_qbank + L.q_offset), n_tiles16, L.segs, L.Lpitch, L.Lrows, A3,
+                       c->bank.d_tglobal + L.tg_offset, c->fmt, c->d_cand, c->d_counter.as<unsigned long long>() + 1, (unsigned long long)c->ub_cand, L.queue, c->row_hist);
     c->launch_end();
 }
 
@@ -438,14 +438,14 @@ static void launch_v2(focr_ctx *c, const MfmaLaunch &L, unsigned n_cus) {
     unsigned grid = (unsigned)std::min<uint64_t>(n_cus, (n_items + NW - 1) / NW);
     auto kern = scan_mfma2_kernel<KSTEPS, RPG, MT, NW>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const v4i *qb = reinterpret_cast<const v4i *>(c->d_qbank + L.q_offset);
+    const v4i *qb = reinterpret_cast<const v4i *>(c->bank.d_qbank + L.q_offset);
     const uint64_t issued = 16 * (uint64_t)n_tiles16 * 16 * KSTEPS * 64;  // per live M-tile; scaled by the live count after the scan
     char name[64];
     snprintf(name, sizeof name, "scan_mfma2_kernel<%d,%d,%d,%d>", KSTEPS, RPG, MT, NW);
     c->launch_begin(name, L.n_templates | (L.super_index << 24), L.alg_macs, issued);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, c->stream, c->d_pages_i8 + c->sub_p0 * c->rows_alloc * c->pitch, (uint32_t)c->pitch, (uint32_t)c->rows_alloc,
-                       L.live_list, L.live_count, (uint32_t)c->sub_p0, qb, n_tiles16, L.segs, L.Lpitch, L.Lrows, c->d_tglobal + L.tg_offset,
-                       c->fmt, c->d_cand, (unsigned long long *)c->d_counter + 1,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, c->stream, c->pages.i8 + c->sub_p0 * c->pages.rows_alloc * c->pages.pitch, (uint32_t)c->pages.pitch, (uint32_t)c->pages.rows_alloc,
+                       L.live_list, L.live_count, (uint32_t)c->sub_p0, qb, n_tiles16, L.segs, L.Lpitch, L.Lrows, c->bank.d_tglobal + L.tg_offset,
+                       c->fmt, c->d_cand, c->d_counter.as<unsigned long long>() + 1,
                        (unsigned long long)c->ub_cand, L.queue, c->row_hist);
     c->launch_end();
 }

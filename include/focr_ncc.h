@@ -423,6 +423,10 @@ int focr_debug_rnorm(focr_ctx_t *ctx, const uint32_t *s, const uint64_t *s2, con
  * without waiting for an overflow. */
 int focr_debug_force_split(focr_ctx_t *ctx, int on);
 
+/* Diagnostic: bytes of device memory the library holds in this process right now (contexts, decoders, executors and the compat
+ * symbols' per-thread state).  Everything a destroyed object owned is gone from the count. */
+size_t focr_debug_device_bytes(void);
+
 /* Diagnostic: the phases of the context's last batch on the device's clock, in milliseconds since a per-device origin (the creation of
  * the device's first context): [0] statistics start, [1] statistics end, [2] scan kernels end, [3] verify end, [4] ordering end,
  * [5] process_hits start, [6] process_hits end, [7] start and [8] end of the scan launch with the most work; -1 where not available.
