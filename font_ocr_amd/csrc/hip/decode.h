@@ -1,0 +1,275 @@
+// decode.h — what the two halves of the `focr` decoder share (decode.hip: font and line decoder; decode_images.hip: the
+// verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels, the blank
+// test's crop, the decoder itself, and the host plumbing every entry point repeats (errors, stages, staging, refusals).
+#pragma once
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "devmem.h"
+#include "focr_decode.h"
+
+namespace focr_dec {
+
+struct DevGlyph {
+    uint32_t off_dw;  // dword offset of phase 0 in the bitmap table
+    uint32_t ndw;     // dwords per bitmap row
+    uint32_t box_h;
+    float inc;
+};
+
+struct Geometry {
+    uint32_t page_w, page_h;
+    uint32_t x, w;               // clamped crop x and width (equal for every line of the batch)
+    uint32_t y_start, line_height, line_advance;
+    uint32_t n_slots;            // line slots per page: y_start + i * line_advance < page_h
+    uint32_t total;              // n_pages * n_slots
+    uint32_t stride;             // bytes per strip row: PAD + w rounded up to dwords, plus two dwords of reach
+    uint32_t cap;                // characters per line at most
+};
+
+__device__ __forceinline__ void slot_rows(const Geometry &g, uint32_t i, uint32_t *yc, uint32_t *h) {
+    const uint64_t y = (uint64_t)g.y_start + (uint64_t)i * g.line_advance;
+    *yc = (uint32_t)std::min<uint64_t>(y, g.page_h);
+    *h = std::min(g.line_height, g.page_h - *yc);
+}
+
+// The crop of (page, line) slot `slot` < g.total as image::crop_imm clamps it: its first pixel; g.w columns by *h rows.
+__device__ __forceinline__ const uint8_t *slot_crop(const uint8_t *__restrict__ pages, const Geometry &g, uint32_t slot, uint32_t *h) {
+    uint32_t yc;
+    slot_rows(g, slot % g.n_slots, &yc, h);
+    return pages + (size_t)(slot / g.n_slots) * g.page_w * g.page_h + (size_t)yc * g.page_w + g.x;
+}
+
+constexpr uint32_t TEST_THREADS = 256;
+
+// The blank test of a slot by a workgroup of TEST_THREADS: this thread's share of "some pixel of the crop is not 255"
+// (an empty crop counts as all-white), for the caller's __syncthreads_or.
+__device__ __forceinline__ int slot_has_ink(const uint8_t *__restrict__ pages, const Geometry &g, uint32_t slot) {
+    uint32_t h;
+    const uint8_t *src = slot_crop(pages, g, slot, &h);
+    int ink = 0;
+    const uint64_t n = (uint64_t)g.w * h;
+    for (uint64_t k = threadIdx.x; k < n; k += TEST_THREADS) ink |= src[(k / g.w) * g.page_w + k % g.w] != 255;
+    return ink;
+}
+
+struct VerifyGlyph {
+    float box[4];      // raster_bounds at the identity before round_out (focr_verify_glyph_t::box)
+};
+
+struct VerifyPhase {
+    int32_t x, y;      // top-left of the true bitmap on a line canvas at whole-pixel shift 0 and vertical translation 0
+    uint32_t w, h;
+    uint32_t src;      // byte offset of that top-left pixel in the bitmap table
+    uint32_t stride;
+};
+
+struct VerifyLine {    // one line slot: its canvas on the page, clipped (empty for a blank slot), and its glyph records
+    int32_t x0, y0, x1, y1;
+    uint32_t k, n;
+};
+
+struct VerifyRec {     // one glyph: its bitmap rectangle on the page, clipped to the canvas and the page
+    int32_t x0, y0, x1, y1;
+    uint32_t src, stride;  // byte offset in the bitmap table of the pixel at (x0, y0)
+};
+
+// ---- the tile frame of the compose kernels: a workgroup of VERIFY_TILE_W threads walks (page, tile row, tile column)
+// tiles grid-stride; every thread owns one column of the tile, and `win` (one word per tile pixel) takes the glyphs ----
+
+constexpr uint32_t VERIFY_TILE_W = 256;
+constexpr uint32_t VERIFY_TILE_H = 16;
+constexpr uint32_t VERIFY_MAX_GRID = 1u << 20;
+
+struct TileGrid {
+    uint32_t tiles_x, tiles_y;
+    uint64_t n_tiles;  // n_pages * tiles_x * tiles_y
+    uint32_t grid;     // workgroups to launch: one per tile up to VERIFY_MAX_GRID, and at least one
+};
+
+inline TileGrid tile_grid(size_t n_pages, size_t W, size_t H) {
+    const size_t tiles_x = (W + VERIFY_TILE_W - 1) / VERIFY_TILE_W, tiles_y = (H + VERIFY_TILE_H - 1) / VERIFY_TILE_H;
+    const size_t n_tiles = n_pages * tiles_x * tiles_y;
+    return TileGrid{(uint32_t)tiles_x, (uint32_t)tiles_y, n_tiles, (uint32_t)std::min<size_t>(std::max<size_t>(n_tiles, 1), VERIFY_MAX_GRID)};
+}
+
+struct Tile {
+    uint32_t page;
+    int r0, c0, r1, c1;  // rows r0 .. r1 - 1 and columns c0 .. c1 - 1 of the page
+};
+
+__device__ __forceinline__ Tile tile_at(uint64_t tile, uint32_t tiles_x, uint32_t tiles_y, uint32_t page_w, uint32_t page_h) {
+    const uint64_t per_page = (uint64_t)tiles_x * tiles_y;
+    const uint32_t page = (uint32_t)(tile / per_page), rem = (uint32_t)(tile % per_page);
+    const int r0 = (int)((rem / tiles_x) * VERIFY_TILE_H), c0 = (int)((rem % tiles_x) * VERIFY_TILE_W);
+    return Tile{page, r0, c0, std::min<int>(r0 + VERIFY_TILE_H, (int)page_h), std::min<int>(c0 + VERIFY_TILE_W, (int)page_w)};
+}
+
+// The line slots i of g, in order, with y_i <= r1 - 1 and y_i + reach >= r0, where y_i = y_start + i * line_advance:
+// *i_lo .. *i_hi, empty when *i_hi < *i_lo.
+__device__ __forceinline__ void slot_range(const Geometry &g, int r0, int r1, int64_t reach, int64_t *i_lo, int64_t *i_hi) {
+    *i_lo = 0, *i_hi = -1;
+    if (!g.n_slots) return;
+    const int64_t lo = (int64_t)r0 - reach - g.y_start, hi = (int64_t)r1 - 1 - g.y_start;
+    *i_lo = lo <= 0 ? 0 : (lo + g.line_advance - 1) / g.line_advance;
+    *i_hi = hi < 0 ? -1 : std::min<int64_t>(g.n_slots - 1, hi / g.line_advance);
+}
+
+// Every wave takes glyph records of recs[0 .. n), clips them to the tile and leaves 1 + index of the last glyph over each
+// pixel in win: an LDS atomic max, so neither placement nor arrival order matters.
+__device__ __forceinline__ void mark_glyphs(uint32_t *win, const VerifyRec *__restrict__ recs, uint32_t n, const Tile &T, uint32_t lane,
+                                            uint32_t wave) {
+    for (uint32_t j = wave; j < n; j += VERIFY_TILE_W / 64) {
+        const VerifyRec r = recs[j];
+        const int x0 = std::max(r.x0, T.c0), x1 = std::min(r.x1, T.c1), y0 = std::max(r.y0, T.r0), y1 = std::min(r.y1, T.r1);
+        if (x0 >= x1 || y0 >= y1) continue;
+        const int w = x1 - x0, npx = w * (y1 - y0);
+        for (int q = (int)lane; q < npx; q += 64) atomicMax(&win[(y0 + q / w - T.r0) * VERIFY_TILE_W + (x0 + q % w - T.c0)], j + 1);
+    }
+}
+
+// The bitmap byte at page pixel (x, y) of the glyph a non-zero win word w names.
+__device__ __forceinline__ uint8_t glyph_value(uint32_t w, const VerifyRec *__restrict__ recs, const uint8_t *__restrict__ bitmaps, int x, int y) {
+    const VerifyRec r = recs[w - 1];
+    return bitmaps[r.src + (uint32_t)(y - r.y0) * r.stride + (uint32_t)(x - r.x0)];
+}
+
+struct Stage {  // the kernels of one entry point's last call: device events around them, their time and their number
+    hipEvent_t begin = nullptr, end = nullptr;
+    float ms = 0.f;
+    uint32_t launches = 0;
+};
+
+}  // namespace focr_dec
+
+struct focr_decoder {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    focr_dec::Stage run, verify, test;
+    std::string err;
+    // font
+    uint32_t n_glyphs = 0;
+    float origin_x = 0.f, min_inc = 0.f;
+    std::vector<float> inc;
+    std::vector<focr_decode_glyph_t> font_glyphs;  // what set_verify_font checks and places the verify table against
+    float origin_y = 0.f, text_size = 0.f, kerning = 0.f;
+    int hinting = 0;
+    size_t bitmaps_len = 0;
+    // every device array: exact growth, no stream wait (each call ends with one, so the buffers are idle when the next call grows them)
+    focr::DevArray<focr_dec::DevGlyph> d_glyphs;
+    focr::DevArray<int2> d_offs;
+    focr::DevArray<uint8_t> d_bitmaps;  // dwords (read as uint32_t by the decode kernel, as bytes by the compose kernels)
+    // batch buffers (grown on demand)
+    focr::DevArray<uint8_t> d_pages, d_strips;
+    focr::DevArray<uint32_t> d_flags, d_work, d_nchars, d_count;
+    focr::DevArray<uint16_t> d_chars;
+    // results of the last run
+    std::vector<focr_decoded_line_t> lines;
+    std::vector<uint16_t> chars;
+    // verify: the table, what the last successful run left for it, buffers
+    uint32_t n_vglyphs = 0, hmax = 0;
+    focr::DevArray<focr_dec::VerifyGlyph> d_vglyphs;
+    focr::DevArray<focr_dec::VerifyPhase> d_vphases;
+    bool run_ok = false;
+    focr_dec::Geometry run_g{};
+    size_t run_pages = 0;
+    uint32_t run_x_start = 0;
+    const uint8_t *run_src = nullptr;
+    focr::DevArray<focr_dec::VerifyLine> d_vlines;
+    focr::DevArray<focr_dec::VerifyRec> d_vrecs;
+    focr::DevArray<unsigned long long> d_sums;
+    focr::DevArray<uint8_t> d_rgb;
+    // test images: buffers of their own, so that a test call leaves the last run and its verify as they were
+    focr::DevArray<uint8_t> d_tpages;
+    focr::DevArray<uint32_t> d_tbase, d_trect, d_ttext, d_tflags;
+    focr::DevArray<focr_dec::VerifyRec> d_trecs;
+    focr::DevArray<focr_dec::VerifyLine> d_tline;
+};
+
+namespace focr_dec {
+
+inline thread_local std::string g_dec_err;
+
+inline int dfail(focr_decoder *dec, const std::string &msg) {
+    if (dec) dec->err = msg;
+    g_dec_err = msg;
+    return 1;
+}
+
+#define DEC_CHECK(call)                                                                              \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) return dfail(dec, std::string(#call ": ") + hipGetErrorString(e_));    \
+    } while (0)
+
+// exact growth of a batch buffer / a fresh table from host memory, reported as the allocation they are
+#define DEC_GROW(a, want)                                                                                                          \
+    do {                                                                                                                           \
+        hipError_t e_ = (a).reserve((want), focr::Grow::exact, nullptr);                                                           \
+        if (e_ != hipSuccess) return dfail(dec, std::string("hipMalloc((void **)p, want * sizeof(T)): ") + hipGetErrorString(e_)); \
+    } while (0)
+#define DEC_UPLOAD(a, ...)                                                                                          \
+    do {                                                                                                            \
+        hipError_t e_ = (a).upload(__VA_ARGS__);                                                                    \
+        if (e_ != hipSuccess) return dfail(dec, std::string("hipMalloc / hipMemcpy(" #a "): ") + hipGetErrorString(e_)); \
+    } while (0)
+
+// A caller's n elements where the kernels read them: a device pointer (or none) is used as it is; host memory is copied
+// into `a` on the decoder's stream.
+template <typename T>
+int stage_in(focr_decoder *dec, focr::DevArray<T> &a, const void *src, int on_device, size_t n, const T **d) {
+    *d = (const T *)src;
+    if (on_device || !src) return 0;
+    DEC_GROW(a, std::max<size_t>(n, 1));
+    DEC_CHECK(hipMemcpyAsync(a, src, n * sizeof(T), hipMemcpyHostToDevice, dec->stream));
+    *d = a;
+    return 0;
+}
+
+// Where the kernels write n elements for the caller: its device buffer (or none), or `a` for fetch_out to copy to its
+// host memory on the decoder's stream once the kernels are queued.
+template <typename T>
+int stage_out(focr_decoder *dec, focr::DevArray<T> &a, void *dst, int on_device, size_t n, T **d) {
+    *d = (T *)dst;
+    if (on_device || !dst) return 0;
+    DEC_GROW(a, std::max<size_t>(n, 1));
+    *d = a;
+    return 0;
+}
+
+template <typename T>
+int fetch_out(focr_decoder *dec, void *dst, int on_device, const T *d, size_t n) {
+    if (dst && !on_device) DEC_CHECK(hipMemcpyAsync(dst, d, n * sizeof(T), hipMemcpyDeviceToHost, dec->stream));
+    return 0;
+}
+
+// The geometry of a batch for the entry point `who`, or its refusal: the page-size limit; the line slots as the
+// reference's loop visits them, with image::crop_imm's clamping of every crop (line_advance 0 with a non-empty first
+// crop never ends there); the limit on the slots of one batch.  stride and cap are the line decoder's to fill.
+inline int batch_geometry(focr_decoder *dec, const char *who, size_t n_pages, size_t page_w, size_t page_h, uint32_t x_start, uint32_t y_start,
+                          uint32_t width, uint32_t line_height, uint32_t line_advance, Geometry *out) {
+    const std::string pre = std::string(who) + ": ";
+    if (page_w > 0xffffu * 16 || page_h > 0xffffu * 16) return dfail(dec, pre + "page too large");
+    Geometry g{};
+    g.page_w = (uint32_t)page_w;
+    g.page_h = (uint32_t)page_h;
+    g.x = std::min<uint32_t>(x_start, g.page_w);  // image::crop_imm's clamping
+    g.w = std::min<uint32_t>(width, g.page_w - g.x);
+    g.y_start = y_start;
+    g.line_height = line_height;
+    g.line_advance = line_advance;
+    if (line_height == 0 || y_start >= g.page_h) g.n_slots = 0;  // the first crop is empty: the loop ends at once
+    else if (line_advance == 0) return dfail(dec, pre + "line_advance 0 (the reference never ends)");
+    else g.n_slots = (uint32_t)(((uint64_t)g.page_h - y_start + line_advance - 1) / line_advance);
+    const uint64_t total = (uint64_t)n_pages * g.n_slots;
+    if (total > (1u << 30)) return dfail(dec, pre + "too many lines in one batch");
+    g.total = (uint32_t)total;
+    *out = g;
+    return 0;
+}
+
+}  // namespace focr_dec

@@ -1,4 +1,4 @@
-"""The focr decoder and verify kernels (csrc/hip/decode.hip) at the shapes they branch on, against the fast model
+"""The focr decoder and verify kernels (csrc/hip/decode.hip, decode_images.hip) at the shapes they branch on, against the fast model
 (tests/focr_fast_model.py, proven equal to the brute-force model by tests/test_focr_fast_model.py) and the model's
 draw_verify (tests/focr_line_model.py): lists exactly, images byte for byte, MSE as f32.  Each test asserts from the
 geometry that it reaches the branch it names."""
@@ -19,7 +19,7 @@ MONO = os.path.join(GOLD, "DejaVuSansMono.ttf")
 SANS = os.path.join(GOLD, "DejaVuSans.ttf")
 LDS_STRIP_MAX = 65536     # decode.hip: a strip up to this many bytes is staged in LDS, a larger one is read from global
 COMPACT_THREADS = 1024    # decode.hip: line_compact_kernel's slots per iteration
-VERIFY_TILE = (16, 256)   # decode.hip: verify_compose_kernel's tile, rows x columns
+VERIFY_TILE = (16, 256)   # decode.h: the compose kernels' tile, rows x columns
 
 pytestmark = pytest.mark.gpu
 

@@ -115,6 +115,38 @@ def test_clipping_and_thin_geometry(dec, geo):
         assert all(np.array_equal(r, T.grey_rgba(p)) for r, p in zip(rects, pages))
 
 
+@pytest.mark.parametrize("W", [256, 257, 513])
+def test_tile_boundaries(dec, W):
+    """The compose tile is 16 rows by 256 columns: 17 rows make a second tile row one row high, 257 and 513 columns a
+    last tile column one column wide.  Boxes of height 5 every 5 rows from y = 1 put a bottom edge and a top edge on
+    row 16 and vertical edges across rows 15 / 16; the right edge is the page's last column; the 24 px alphabet canvas
+    crosses every seam.  Both images at once, then each alone."""
+    H, size, geo = 17, 24.0, (2, 1, W - 3, 5, 5)
+    rng = np.random.default_rng(27)
+    pages = [rng.integers(0, 255, (H, W), dtype=np.uint8) for _ in range(2)]
+    pages[1][6:11] = 255  # the second slot of the second page is blank
+    canvas = render_text(MONO, size, FOCR_DEFAULT_ALPHABET)
+    want_r = [T.draw_test_rectangles(p, *geo) for p in pages]
+    want_t = [T.draw_test_text(canvas, T.grey_rgba(p)) for p in pages]
+    last = (W - 1) // 256 * 256  # first column of the last tile column
+    for p, r, t in zip(pages, want_r, want_t):  # the expectation itself reaches the second tile row and the last tile column
+        for img in (r, t):
+            changed = np.any(img != T.grey_rgba(p), axis=-1)
+            assert changed[16].any() and changed[:16].any() and changed[:, last:].any()
+    assert T.rect_counts(pages[0], *geo)[8, 2] == 1 and T.rect_counts(pages[1], *geo)[8, 2] == 0  # row 8 is the second box's alone
+    dec.set_font(MONO, size)
+    lib, h = dec._lib, dec._h
+    for rect, text, launches in ((True, True, 3), (True, False, 2), (False, True, 2)):
+        rects, texts = dec.test_images(pages, *geo, rect=rect, text=text)
+        assert lib.focr_decoder_last_test_launches(h) == launches
+        assert (rects is None) == (not rect) and (texts is None) == (not text)
+        for i in range(2):
+            if rect:
+                assert np.array_equal(rects[i], want_r[i]), (i, np.argwhere(np.any(rects[i] != want_r[i], axis=-1))[:5])
+            if text:
+                assert np.array_equal(texts[i], want_t[i]), (i, np.argwhere(np.any(texts[i] != want_t[i], axis=-1))[:5])
+
+
 @pytest.mark.parametrize("alphabet,font,size", [(FOCR_DEFAULT_ALPHABET, MONO, 24.0), (ALPHABET_319, SANS, 13.0),
                                                 (ALPHABET_319, MONO, 20.0)], ids=["default24", "319sans", "319mono"])
 def test_alphabet_larger_than_the_page(dec, alphabet, font, size):
