@@ -53,6 +53,16 @@ struct SuperClass {
     bool planes;
 };
 
+// What a scan of the batch launches, decided before anything is enqueued (plan_scan, scan_mfma.hip: also every buffer sized)
+struct ScanPlan {
+    uint32_t Lpitch = 0, Lrows = 0;
+    size_t L_per_class = 0;      // int32 values of one class's table in d_L ([class][page][Lrows][Lpitch]; legacy passes)
+    size_t plane = 0;            // int16 values of one threshold plane ([page][Lrows][Lpitch] of the pages scanned)
+    size_t tiles_total = 0;      // M-tiles of all passes (SuperClass::live_offset)
+    uint8_t *live = nullptr;     // per M-tile mark bytes
+    uint64_t *live_list = nullptr;
+};
+
 // Per-template constants, computed once on the host in IEEE double exactly as
 // the reference's kernel prologue does (src/ncc.cpp:73-86, 278-291).
 struct TemplateConst {
@@ -104,7 +114,7 @@ struct RowHist {
     uint32_t bt, bx;     // x = (key >> bt) & (2^bx - 1)
     uint32_t seg_shift, n_seg;
 };
-// Everything a scan needs zeroed, in ONE launch (clear_kernel, scan_mfma.hip).  A hipMemsetAsync costs the submitting thread several
+// Everything a scan needs zeroed, in ONE launch (clear_kernel, stats.hip).  A hipMemsetAsync costs the submitting thread several
 // times a kernel launch (six of them stood between a batch's hand-over and its first kernel: ~0.3 ms of a 1.9 ms step).
 struct ClearList {
     void *p[8];       // 8-byte aligned
@@ -329,23 +339,47 @@ namespace focr {
                               std::string(#expr) + ": " + hipGetErrorString(e_));                 \
     } while (0)
 
-// launchers implemented in the .hip files
+// Every function one .hip file defines and another calls (the decoder's: decode.h; those that need mfma_common.h's types: there).
+// The defining file includes this header too, so a signature that drifts is a compile error, not a link error at the call site.
+// scan_direct.hip
 int launch_scan_direct(focr_ctx *ctx, float threshold, int rust_formula);
+int launch_scan_tall(focr_ctx *c, size_t k, double thr_d, uint64_t *keys, float *sims, unsigned long long *counter,
+                     unsigned long long capacity, int rust);
+int reserve_hits(focr_ctx *c, size_t want);
+// scan_mfma.hip
 int launch_scan_mfma(focr_ctx *ctx, float threshold);
-int launch_clear(focr_ctx *c, const focr::ClearList &l);  // zero every region of the list in one launch (scan_mfma.hip)
-int exclusive_scan_u64(focr_ctx *c, const uint64_t *in, uint64_t *out, size_t n);
-int order_hits(focr_ctx *ctx);  // direct path: unordered hits in d_hit_keys / d_hit_sims -> everything below
-int finish_results(focr_ctx *c);  // wait for the stream once and read the result sizes of the last scan / process_hits
+// stats.hip
+int launch_clear(focr_ctx *c, const focr::ClearList &l);  // zero every region of the list in one launch
+int pass_stats(focr_ctx *c, const ScanPlan &P, size_t si, double thr_d);  // one scan pass's statistics launches and its work list, queued on the context's stream
+// bank_mfma.hip (host only)
 int build_mfma_bank(focr_ctx *ctx, const uint8_t *needles);
+void layout_supers(focr_ctx *c);  // size classes -> super-classes, MFMA K layouts, bank offsets
+int quantise_bank(focr_ctx *c, const uint8_t *dense, std::vector<int8_t> &qbank, std::vector<uint32_t> &tglobal, std::vector<uint32_t> &order_of);
+// rows.hip: the row path of the tail
+bool rows_applicable(const focr_ctx *c);
+uint32_t rows_capacity_for(uint64_t row_max);
+void row_segments(const focr_ctx *c, uint32_t *seg_shift, uint32_t *n_seg);
+int rows2_begin(focr_ctx *c, ClearList &clear);  // the hits-first tail: verify in flush order, then only hits are placed and sorted
+int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c);
+int rows2_place(focr_ctx *c, const unsigned long long *n_cand_p, size_t ub_c, size_t ub_h, bool big_expected, bool sort);
+// order.hip
+int sort_keys_u64(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, size_t n, unsigned end_bit);
+int sort_pairs_u64_f32(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, DevArray<float> &vals, DevArray<float> &vals_alt, size_t n, unsigned end_bit);
+int exclusive_scan_u64(focr_ctx *c, const uint64_t *in, uint64_t *out, size_t n);
+int compact_candidates(focr_ctx *c, const uint64_t *keys, const float *sims, const uint64_t *flags, uint64_t *pos,
+                       const unsigned long long *n_cand_p, size_t ub_c);
+int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t *n_p, size_t ub, const unsigned long long *n_cand_p, size_t ub_c);
+int order_hits(focr_ctx *ctx);  // direct path: unordered hits in d_hit_keys / d_hit_sims -> everything below
+// ctx.hip
+int finish_results(focr_ctx *c);  // wait for the stream once and read the result sizes of the last scan / process_hits
 void bank_host_prepare(focr_ctx *c, const focr_template_t *templates, size_t n_templates, const uint8_t *needles,
                        std::vector<uint32_t> &direct, std::vector<uint8_t> &dense);
-void layout_supers(focr_ctx *c);  // size classes -> super-classes, MFMA K layouts, bank offsets (host only)
-int pages_alt_ingest(focr_ctx *c, const void *d_luma, size_t n_pages, size_t r_w, size_t r_h, int invert, hipStream_t s);  // ctx.hip
+int pages_alt_ingest(focr_ctx *c, const void *d_luma, size_t n_pages, size_t r_w, size_t r_h, int invert, hipStream_t s);
 int pages_alt_swap(focr_ctx *c, size_t n_pages, size_t r_w, size_t r_h);
-void ctx_share_stream(focr_ctx *c, hipStream_t lane_stream, hipStream_t io_stream);  // ctx.hip: the context joins an executor's lane
-bool post_queue_chars_copy(focr_ctx *c, void *dst, size_t dst_bytes);  // post.hip: the batch's characters to a device buffer, queued on the context's stream
-int wait_batch(focr_ctx *c);  // ctx.hip: until the context's queued work is done (its batch's event inside an executor, else its stream)
-int quantise_bank(focr_ctx *c, const uint8_t *dense, std::vector<int8_t> &qbank, std::vector<uint32_t> &tglobal, std::vector<uint32_t> &order_of);  // host only
+void ctx_share_stream(focr_ctx *c, hipStream_t lane_stream, hipStream_t io_stream);  // the context joins an executor's lane
+int wait_batch(focr_ctx *c);  // until the context's queued work is done (its batch's event inside an executor, else its stream)
+// post.hip
+bool post_queue_chars_copy(focr_ctx *c, void *dst, size_t dst_bytes);  // the batch's characters to a device buffer, queued on the context's stream
 
 // ---- device helpers: the reference's f64 epilogue, operation for operation ----
 // Compiled with -ffp-contract=off: the only fused operation is the explicit fma.

@@ -19,10 +19,6 @@
 
 namespace focr {
 
-int sort_pairs_u64_f32(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, DevArray<float> &vals, DevArray<float> &vals_alt, size_t n,
-                       unsigned end_bit);
-int reserve_hits(focr_ctx *c, size_t want);
-
 typedef int v4i_c __attribute__((ext_vector_type(4), aligned(1)));
 typedef int v2i_c __attribute__((ext_vector_type(2), aligned(1)));
 

@@ -18,8 +18,6 @@ static std::mutex g_est_mu;
 static std::unordered_map<uint64_t, SizeEstimate> g_est;
 static hipEvent_t g_base_event[64] = {};  // per device: the origin of focr_debug_phase_stamps (guarded by g_est_mu)
 
-void row_segments(const focr_ctx *c, uint32_t *seg_shift, uint32_t *n_seg);  // rows.hip
-
 // bounds for the next scan of the same setup: this scan's counts + a margin that follows how much the counts have been moving (20 %
 // after the first scan of a setup; 4 % once consecutive batches agree to ~1 %): every element of margin is sorted, scanned and stepped
 // over by all the later phases

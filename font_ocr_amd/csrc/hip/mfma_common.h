@@ -1,4 +1,4 @@
-// mfma_common.h — declarations shared by the MFMA prefilter kernels (scan_mfma.hip, scan_mfma2.hip): threshold planes,
+// mfma_common.h — declarations shared by the MFMA prefilter kernels (stats.hip, scan_mfma2.hip) and their host side: threshold planes,
 // item queues, K layouts.
 #pragma once
 #include "common.h"
@@ -38,7 +38,7 @@ __device__ __forceinline__ void flush_wave_candidates(uint64_t *wbuf, uint32_t c
 //
 //     L(w) = kappa * norm_p(w)  -  c * rho_max * dnorm(w)            candidate  <=>  G(w, t) > L(w)
 //
-// kappa = c*thr - e_max - margins (scan_mfma.hip header).  The second term exists for classes whose LAST COLUMN the MFMA
+// kappa = c*thr - e_max - margins (bank_mfma.hip header).  The second term exists for classes whose LAST COLUMN the MFMA
 // does not multiply ("column drop": a 9-wide template costs 3 K-steps of 64 bytes for 135 taps; its first 8 columns fit 2):
 // with m = mean of the window over the kept columns, beta = the unit mean-centred template, sigma = sum of beta over the
 // dropped column, and beta'_k = beta_k + sigma / n_keep on the kept columns (so that sum beta' = 0),
@@ -428,8 +428,9 @@ struct PlaneArgs {
     uint32_t seg_dead_from[MAX_SEGS];  // per segment: first N-tile (chunk-local) that holds dead / padding slots — a class's live templates come first
 };
 
-// scan_mfma.hip (host)
+// bank_mfma.hip (host)
 PlaneParams plane_params(const focr_ctx *c, size_t k, double thr_d);
+// scan_mfma.hip (host)
 int plan_passes(focr_ctx *c, size_t plane, size_t &tiles_total, size_t &plane_vals, bool &need_L);
 // scan_mfma2.hip
 uint32_t mfma2_chunk_tiles(uint32_t ksteps);

@@ -15,9 +15,6 @@
 
 namespace focr {
 
-int exclusive_scan_u64(focr_ctx *c, const uint64_t *in, uint64_t *out, size_t n);
-int finish_results(focr_ctx *c);
-
 __device__ __forceinline__ int32_t total_key(float f) {  // f32::total_cmp as a signed-int order
     int32_t b = __float_as_int(f);
     return b ^ (int32_t)(((uint32_t)(b >> 31)) >> 1);

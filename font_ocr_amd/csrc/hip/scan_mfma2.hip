@@ -1,6 +1,6 @@
 // scan_mfma2.hip — the barrier-free i8 MFMA prefilter kernels.
 //
-// The maths is in scan_mfma.hip's header, the K layouts and the item queues in mfma_common.h.  Every wave is an independent
+// The maths is in bank_mfma.hip's header, the K layouts and the item queues in mfma_common.h.  Every wave is an independent
 // worker: it takes items of MT consecutive 16-window M-tiles from its XCD's queue, reads its window fragments straight from
 // the page in HBM/L2 (byte-unaligned global loads that land in the MFMA operand registers; the page is read ~16x per class,
 // all but the first time from L2), and streams the whole quantised bank chunk past them from LDS.  The bank is staged once

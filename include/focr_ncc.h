@@ -438,7 +438,7 @@ int focr_debug_phase_stamps(focr_ctx_t *ctx, double out[9]);
 int focr_debug_set_tail_grid(focr_ctx_t *ctx, uint32_t num, uint32_t den);
 
 /* Test hooks for the window statistics: form 1 = the LDS-tiled kernel for every size class (0: the register form for classes whose
- * kept width is 8 px, scan_mfma.hip); focr_debug_planes copies the int16 threshold planes of the context's last MFMA scan to the
+ * kept width is 8 px, stats.hip); focr_debug_planes copies the int16 threshold planes of the context's last MFMA scan to the
  * host ([value][page][Lrows][Lpitch] per pass, Lpitch = (r_w + 63) / 64 * 64 + 64, Lrows = (r_h + 7) / 8 * 8 + 8; out = NULL: only
  * their number).  Both forms must write the same planes wherever the scan kernel reads them. */
 int focr_debug_set_stats_form(focr_ctx_t *ctx, int form);

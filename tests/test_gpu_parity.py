@@ -384,7 +384,7 @@ def test_c5_256_template_gemm_variant(scanner, bank_x2):
     """BASELINE configs[4]: "template-bank-as-GEMM variant, 256-glyph bank, bf16 MFMA windows x templates".  Here the
     GEMM operand type is int8 (v_mfma_i32_16x16x64_i8), not bf16: BASELINE's north_star leaves the MFMA form open
     ("MFMA only if ... that wins on rocprof"), int8 has twice bf16's rate and — unlike bf16 accumulation in fp32 of
-    products up to 255*255*135 — keeps the prefilter's bound in exact integer arithmetic (scan_mfma.hip header);
+    products up to 255*255*135 — keeps the prefilter's bound in exact integer arithmetic (bank_mfma.hip header);
     every emitted match is re-evaluated with the reference's u8*u8->u32 + f64 arithmetic (src/ncc.cpp:316-321,
     352-361).  256 templates = the 95 shift-0 glyphs (8x15) + 161 templates of shifts 1/4 and 1/2 (9x15): the GEMM
     formulation (MFMA), the v_dot4 formulation (direct) and the reference kernel must produce identical lists."""
