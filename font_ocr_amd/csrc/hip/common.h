@@ -253,7 +253,7 @@ struct focr_ctx {
     focr::DevArray<uint32_t> d_counter;  // COUNTER_BYTES: u64 [0] hits, u64 [1] candidates, u32 [8..47] live M-tile counts, then the scan kernels' item queues
     uint32_t scan_queues_used = 0;  // item queues handed out since the last reset (launch_scan_mfma)
     focr::DevArray<uint64_t> d_cand, d_cand_alt;
-    bool ordered = false;  // the scan path already produced d_matches (MFMA path); order_hits is skipped
+    bool ordered = false;  // the scan path already ran the ordering pass (MFMA path); order_hits is skipped
     focr::DevArray<int32_t> d_L;  // prefilter thresholds [class][page][r_h][pitchL]
     focr::DevArray<uint8_t> d_sort_tmp;  // rocPRIM's temporary storage
     size_t n_hits_raw = 0;    // hits before the cap
@@ -262,6 +262,14 @@ struct focr_ctx {
     focr::DevArray<uint64_t> d_seg_start;   // [n_pages*T] start in the sorted arrays
     focr::DevArray<uint64_t> d_seg_offset;  // [n_pages*T + 1] CSR offsets of the capped lists
     focr::DevArray<focr_match_t> d_matches;  // capped, ordered by (page, template, y, x); Grow::eighth
+    // order.hip's counting form writes d_matches on demand (materialise_matches): pending = nobody has read the last scan's lists yet;
+    // the rest is the geometry of the tables the ordering left in ord_v / ord_k2 (pages of the scan, unit capacity, the unit kernels' grid)
+    struct LazyMatches {
+        bool pending = false;
+        uint32_t n_pages = 0;
+        size_t max_units = 0;
+        unsigned blocks = 0;
+    } lazy;
     // views, not owners: all hits (before the cap) in process_hits order (page, y, x, t), in the hit arrays or in acc_hkeys / acc_hsims
     uint64_t *d_hkeys = nullptr;
     float *d_hsims = nullptr;
@@ -370,6 +378,7 @@ int compact_candidates(focr_ctx *c, const uint64_t *keys, const float *sims, con
                        const unsigned long long *n_cand_p, size_t ub_c);
 int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t *n_p, size_t ub, const unsigned long long *n_cand_p, size_t ub_c);
 int order_hits(focr_ctx *ctx);  // direct path: unordered hits in d_hit_keys / d_hit_sims -> everything below
+int materialise_matches(focr_ctx *c, hipStream_t s);  // d_matches of the last scan, if still to be written, on stream s (after finish_results)
 // ctx.hip
 int finish_results(focr_ctx *c);  // wait for the stream once and read the result sizes of the last scan / process_hits
 void bank_host_prepare(focr_ctx *c, const focr_template_t *templates, size_t n_templates, const uint8_t *needles,

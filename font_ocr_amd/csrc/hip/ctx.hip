@@ -660,6 +660,7 @@ static int scan_split(focr_ctx *c, Run &run) {
         if (rc) return rc;
         // append: matches, per-call counts, kept hits
         const size_t nm = c->n_matches, nh = c->n_hits;
+        if (nm && (rc = materialise_matches(c, c->stream))) return rc;  // the sub-batch's lists are read here
         if (c->acc_matches.reserve(match_total + nm + 1, Grow::half, &c->stream, match_total) ||
             c->acc_hkeys.reserve(hit_total + nm + 1, Grow::half, &c->stream, hit_total) ||
             c->acc_hsims.reserve(hit_total + nm + 1, Grow::half, &c->stream, hit_total))
@@ -699,6 +700,7 @@ static int scan_split(focr_ctx *c, Run &run) {
         FOCR_HIP(c, hipMemsetAsync(c->ord_keep, 1, hit_total + 1, c->stream));
         FOCR_HIP(c, hipStreamSynchronize(c->stream));
         std::swap(c->d_matches, c->acc_matches);  // hand the accumulated list over
+        c->lazy.pending = false;                  // ... complete: nothing is left to write on demand
         c->d_hkeys = c->acc_hkeys;
         c->d_hsims = c->acc_hsims;
         // the accumulated hit count as the device-side value process_hits reads
@@ -736,6 +738,7 @@ static int scan_now(focr_ctx *c) {
         c->sub_p0 = p0;
         c->sub_np = np;
         c->ordered = false;
+        c->lazy.pending = false;
         int r = mode == FOCR_SCAN_MFMA ? launch_scan_mfma(c, threshold) : launch_scan_direct(c, threshold, mode == FOCR_SCAN_RUST);
         if (r) return r;
         if (!c->ordered && (r = order_hits(c))) return r;
@@ -921,9 +924,11 @@ int focr_get_matches(focr_ctx_t *c, uint64_t *offsets, focr_match_t *matches) {
     if (offsets)
         FOCR_HIP(c, hipMemcpyAsync(offsets, c->d_seg_offset, (c->n_pages * c->n_templates + 1) * 8, hipMemcpyDeviceToHost,
                                    c->io_stream));
-    if (matches && c->n_matches)
+    if (matches && c->n_matches) {
+        if (int rc = materialise_matches(c, c->io_stream)) return rc;  // the first reader of this scan's lists writes them (order.hip)
         FOCR_HIP(c, hipMemcpyAsync(matches, c->d_matches, c->n_matches * sizeof(focr_match_t), hipMemcpyDeviceToHost,
                                    c->io_stream));
+    }
     FOCR_HIP(c, hipStreamSynchronize(c->io_stream));
     return FOCR_OK;
 }

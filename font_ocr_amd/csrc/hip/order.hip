@@ -188,6 +188,7 @@ static int order_sorted_hits_sort(focr_ctx *c, uint64_t *hkeys, float *hsims, co
     uint64_t *k2 = c->ord_k2.as<uint64_t>(), *k2_alt = c->ord_k2_alt.as<uint64_t>();
     float *v = c->ord_v.as<float>(), *v_alt = c->ord_v_alt.as<float>();
     uint8_t *keep = c->ord_keep;
+    c->lazy.pending = false;  // this form writes d_matches itself
     c->d_hkeys = hkeys;
     c->d_hsims = hsims;
     uint64_t *count64 = c->d_seg_start + (n_seg + 1);
@@ -230,8 +231,15 @@ static int order_sorted_hits_sort(focr_ctx *c, uint64_t *hkeys, float *hsims, co
 //   unit_prefix    one thread per (page, t): running sum over the page's units -> uhist becomes the unit's base rank;
 //                  the (page, t) total, capped, is the call's match count (src/ncc.cpp:225-227)
 //   prefix         match offsets (CSR) over the (page, t) calls
-//   unit_emit      one wave per unit, its hits 64 at a time, in order: rank = base + earlier hits of the same t in the unit
-//                  (lanes of one group with equal t are found with one ballot per bit of t) -> keep flag, match at its place
+//   unit_rank      one wave per unit, its hits 64 at a time, in order: rank = base + earlier hits of the same t in the unit
+//                  (lanes of one group with equal t are found with one ballot per bit of t) -> keep flag
+//   unit_matches   the same walk once more, ON DEMAND: a kept hit's match at seg_offset[call] + rank (materialise_matches)
+// LAZY match lists: process_hits reads the keep flags, focr_get_counts the per-call counts, the result sizes the offsets' total —
+// only focr_get_matches (Scanner.matches(), `ncc --raw`) and the split-batch append read d_matches.  A batch that is consumed as
+// lines and characters never pays for the 8-byte scattered store per hit and the similarities' load: the counting form leaves
+// focr_ctx::lazy.pending set, and the first reader runs unit_matches_kernel over what the ordering left in place (hit keys and
+// similarities, unit tables, base ranks, offsets: all of them the context's own and untouched until its next scan).  The SORTING
+// form above stays eager (emit_matches writes the flag and the match in one pass over its sorted pairs).
 // Six launches of a few microseconds each instead of ~14 (two radix passes over 2.7 M pairs with their histograms and scans,
 // binary-searched segment bounds, a library scan).  Banks with more than ORDER_T_MAX templates or batches with more than
 // 2^31 hits take the sorting form above.
@@ -383,23 +391,26 @@ __global__ __launch_bounds__(1024) void unit_prefix_kernel(uint32_t T, uint32_t 
     }
 }
 
-__global__ __launch_bounds__(256) void unit_emit_kernel(const uint64_t *__restrict__ hkeys, const float *__restrict__ hsims, KeyFmt fmt, uint32_t T,
-                                                        uint32_t page_base, const uint32_t *__restrict__ page_unit0, uint32_t n_pages,
-                                                        const uint32_t *__restrict__ unit_page, const uint32_t *__restrict__ unit_begin,
-                                                        const uint32_t *__restrict__ unit_end, const uint32_t *__restrict__ uhist, uint32_t cap,
-                                                        const uint64_t *__restrict__ seg_offset, focr_match_t *__restrict__ out, uint8_t *__restrict__ keep) {
-    extern __shared__ uint32_t cnt_lds[];  // 4 waves x T: hits of each t seen so far in the unit
+// The walk both unit kernels share.  MATCHES = false: the keep flags (what the batch's own stream needs); true: the matches of the
+// kept hits at their places in the CSR lists (on demand; the flags are there already).  Both compute the same ranks from the same
+// base ranks, so the lists are exactly what one fused pass wrote.
+template <bool MATCHES>
+__device__ __forceinline__ void unit_walk(const uint64_t *__restrict__ hkeys, const float *__restrict__ hsims, KeyFmt fmt, uint32_t T,
+                                          const uint32_t *__restrict__ page_unit0, uint32_t n_pages, const uint32_t *__restrict__ unit_page,
+                                          const uint32_t *__restrict__ unit_begin, const uint32_t *__restrict__ unit_end, const uint32_t *__restrict__ uhist,
+                                          uint32_t cap, const uint64_t *__restrict__ seg_offset, focr_match_t *__restrict__ out, uint8_t *__restrict__ keep,
+                                          uint32_t *cnt_lds) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t *cnt = cnt_lds + (size_t)wv * T;
+    uint32_t *cnt = cnt_lds + (size_t)wv * T;  // hits of each t seen so far in the unit
     const uint32_t n_units = page_unit0[n_pages], n_waves = gridDim.x * 4;
     const uint64_t lt_mask = (1ull << lane) - 1;
     for (uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wv); u < n_units; u += n_waves) {
         const uint32_t *ubase = uhist + (size_t)u * T;
         for (uint32_t i = lane; i < T; i += 64) cnt[i] = ubase[i];  // the unit's base ranks
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const uint32_t b = unit_begin[u], e = unit_end[u], p = unit_page[u];
-        uint64_t k_next = b + lane < e ? hkeys[b + lane] : 0;  // the next group's key and similarity are loaded a group ahead
-        float s_next = b + lane < e ? hsims[b + lane] : 0.f;
+        const uint32_t b = unit_begin[u], e = unit_end[u], p = MATCHES ? unit_page[u] : 0;
+        uint64_t k_next = b + lane < e ? hkeys[b + lane] : 0;  // the next group's key (and similarity) are loaded a group ahead
+        float s_next = MATCHES && b + lane < e ? hsims[b + lane] : 0.f;
         for (uint32_t i0 = b; i0 < e; i0 += 64) {
             const uint32_t i = i0 + lane;
             const bool valid = i < e;
@@ -407,7 +418,7 @@ __global__ __launch_bounds__(256) void unit_emit_kernel(const uint64_t *__restri
             const float sim = s_next;
             if (i + 64 < e) {
                 k_next = hkeys[i + 64];
-                s_next = hsims[i + 64];
+                if (MATCHES) s_next = hsims[i + 64];
             }
             const uint32_t t = valid ? fmt.t(k) : 0xffffffffu;
             // lanes of this group with the same t: one ballot per bit of t
@@ -420,8 +431,8 @@ __global__ __launch_bounds__(256) void unit_emit_kernel(const uint64_t *__restri
             if (valid) {
                 const uint32_t rank = cnt[t] + (uint32_t)__builtin_popcountll(peers & lt_mask);
                 const bool kept = rank < cap;
-                keep[i] = kept ? 1 : 0;
-                if (kept) {
+                if (!MATCHES) keep[i] = kept ? 1 : 0;
+                if (MATCHES && kept) {
                     focr_match_t m;
                     m.x = (uint16_t)fmt.x(k);
                     m.y = (uint16_t)fmt.y(k);
@@ -437,6 +448,46 @@ __global__ __launch_bounds__(256) void unit_emit_kernel(const uint64_t *__restri
     }
 }
 
+__global__ __launch_bounds__(256) void unit_rank_kernel(const uint64_t *__restrict__ hkeys, KeyFmt fmt, uint32_t T, const uint32_t *__restrict__ page_unit0,
+                                                        uint32_t n_pages, const uint32_t *__restrict__ unit_begin, const uint32_t *__restrict__ unit_end,
+                                                        const uint32_t *__restrict__ uhist, uint32_t cap, uint8_t *__restrict__ keep) {
+    extern __shared__ uint32_t cnt_lds[];  // 4 waves x T
+    unit_walk<false>(hkeys, nullptr, fmt, T, page_unit0, n_pages, nullptr, unit_begin, unit_end, uhist, cap, nullptr, nullptr, keep, cnt_lds);
+}
+
+__global__ __launch_bounds__(256) void unit_matches_kernel(const uint64_t *__restrict__ hkeys, const float *__restrict__ hsims, KeyFmt fmt, uint32_t T,
+                                                           const uint32_t *__restrict__ page_unit0, uint32_t n_pages, const uint32_t *__restrict__ unit_page,
+                                                           const uint32_t *__restrict__ unit_begin, const uint32_t *__restrict__ unit_end,
+                                                           const uint32_t *__restrict__ uhist, uint32_t cap, const uint64_t *__restrict__ seg_offset,
+                                                           focr_match_t *__restrict__ out) {
+    extern __shared__ uint32_t cnt_lds[];  // 4 waves x T
+    unit_walk<true>(hkeys, hsims, fmt, T, page_unit0, n_pages, unit_page, unit_begin, unit_end, uhist, cap, seg_offset, out, nullptr, cnt_lds);
+}
+
+// The counting form's tables in the context's scratch: page_start, page_unit0 (n_pages + 1 each), unit_page / begin / end (max_units each)
+struct UnitTables {
+    uint32_t *page_start, *page_unit0, *unit_page, *unit_begin, *unit_end, *uhist;
+    UnitTables(focr_ctx *c, uint32_t n_pages, size_t max_units) {
+        uint32_t *tab = c->ord_v.as<uint32_t>();
+        page_start = tab, page_unit0 = tab + n_pages + 1, unit_page = page_unit0 + n_pages + 1, unit_begin = unit_page + max_units, unit_end = unit_begin + max_units;
+        uhist = c->ord_k2.as<uint32_t>();
+    }
+};
+
+// The match lists of the last scan, if nobody has asked for them yet (counting form), on stream s: the caller has waited for the scan
+// (finish_results) and reads d_matches on s.  Everything the kernel reads was left in place by order_sorted_hits.
+int materialise_matches(focr_ctx *c, hipStream_t s) {
+    if (!c->lazy.pending) return FOCR_OK;
+    const uint32_t T = (uint32_t)c->n_templates;
+    const UnitTables ut(c, c->lazy.n_pages, c->lazy.max_units);
+    hipLaunchKernelGGL(unit_matches_kernel, dim3(c->lazy.blocks), dim3(256), (size_t)4 * T * 4, s, (const uint64_t *)c->d_hkeys, (const float *)c->d_hsims, c->fmt, T,
+                       (const uint32_t *)ut.page_unit0, c->lazy.n_pages, (const uint32_t *)ut.unit_page, (const uint32_t *)ut.unit_begin, (const uint32_t *)ut.unit_end,
+                       (const uint32_t *)ut.uhist, c->cap, (const uint64_t *)c->d_seg_offset, c->d_matches.p);
+    FOCR_HIP(c, hipGetLastError());
+    c->lazy.pending = false;
+    return FOCR_OK;
+}
+
 int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t *n_p, size_t ub, const unsigned long long *n_cand_p, size_t ub_c) {
     const uint32_t T = (uint32_t)c->n_templates, n_pages = (uint32_t)c->sub_np;
     const size_t n_seg = (size_t)n_pages * T;
@@ -448,9 +499,8 @@ int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t
     if (!c->scratch(c->ord_keep, ub + 1) || !c->scratch(c->ord_v, (2 * ((size_t)n_pages + 1) + 3 * max_units) * 4) || !c->scratch(c->ord_k2, max_units * T * 4))
         return fail(c, FOCR_ERR_NOMEM, "order: hipMalloc failed");
     uint8_t *keep = c->ord_keep;
-    uint32_t *tab = c->ord_v.as<uint32_t>(), *uhist = c->ord_k2.as<uint32_t>();
-    uint32_t *page_start = tab, *page_unit0 = tab + n_pages + 1, *unit_page = page_unit0 + n_pages + 1, *unit_begin = unit_page + max_units,
-             *unit_end = unit_begin + max_units;
+    const UnitTables ut(c, n_pages, max_units);
+    uint32_t *page_start = ut.page_start, *page_unit0 = ut.page_unit0, *unit_page = ut.unit_page, *unit_begin = ut.unit_begin, *unit_end = ut.unit_end, *uhist = ut.uhist;
     c->d_hkeys = hkeys;
     c->d_hsims = hsims;
     const unsigned unit_blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((max_units + 3) / 4, (size_t)c->n_cus * 4));
@@ -466,10 +516,10 @@ int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t
     hipLaunchKernelGGL(unit_prefix_kernel, dim3((n_seg_padded + 1023) / 1024), dim3(1024), 0, c->stream, T, n_pages, (const uint32_t *)page_unit0, uhist, c->cap,
                        c->d_seg_count, n_seg_padded, c->d_counter + ORDER_DONE_WORD, c->d_seg_offset);
     FOCR_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(unit_emit_kernel, dim3(unit_blocks), dim3(256), lds, c->stream, hkeys, hsims, c->fmt, T, (uint32_t)c->sub_p0, (const uint32_t *)page_unit0,
-                       n_pages, (const uint32_t *)unit_page, (const uint32_t *)unit_begin, (const uint32_t *)unit_end, (const uint32_t *)uhist, c->cap,
-                       (const uint64_t *)c->d_seg_offset, c->d_matches, keep);
+    hipLaunchKernelGGL(unit_rank_kernel, dim3(unit_blocks), dim3(256), lds, c->stream, (const uint64_t *)hkeys, c->fmt, T, (const uint32_t *)page_unit0, n_pages,
+                       (const uint32_t *)unit_begin, (const uint32_t *)unit_end, (const uint32_t *)uhist, c->cap, keep);
     FOCR_HIP(c, hipGetLastError());
+    c->lazy = {true, n_pages, max_units, unit_blocks};  // d_matches: written by whoever reads it first (materialise_matches)
     hipLaunchKernelGGL(record_scan_sizes, dim3(1), dim3(1), 0, c->stream, n_cand_p, (uint64_t)ub_c, n_p, (uint64_t)ub, c->d_seg_offset + n_seg, c->d_res);
     FOCR_HIP(c, hipGetLastError());
     FOCR_HIP(c, hipMemcpyAsync(c->h_res, c->d_res, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));

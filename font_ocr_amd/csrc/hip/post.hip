@@ -360,6 +360,7 @@ int focr_debug_process_hits(focr_ctx_t *c, const uint32_t *page, const uint32_t 
     c->sizes_pending = c->post_pending = c->estimated = false;
     c->processed = c->lines_on_host = false;
     c->scanned = c->debug_hits = true;
+    c->lazy.pending = false;  // no per-call lists stand behind these hits
     return FOCR_OK;
 }
 

@@ -181,7 +181,9 @@ int focr_scan(focr_ctx_t *ctx, float threshold, uint32_t cap, int mode);
 int focr_get_counts(focr_ctx_t *ctx, uint32_t *counts);
 size_t focr_total_matches(focr_ctx_t *ctx);
 /* All matches in (page, template, y, x) order; offsets is
- * [n_pages*n_templates + 1] (CSR), matches has focr_total_matches entries. */
+ * [n_pages*n_templates + 1] (CSR), matches has focr_total_matches entries.
+ * The device writes the lists when they are first asked for after a scan (a batch that is only read through focr_get_counts and
+ * focr_process_hits / focr_get_lines never pays for them); a later call finds them there.  Valid until the context's next scan. */
 int focr_get_matches(focr_ctx_t *ctx, uint64_t *offsets, focr_match_t *matches);
 
 /* process_hits on the device (src/ncc.rs:723-786 + partition_by 1036-1052)

@@ -10,7 +10,7 @@ for set in "SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_BUSY
 done
 python3 - <<'PY'
 import csv, glob, collections
-names = ["verify_flat", "stats_kernel", "row_sort_kernel<1024", "row_scatter", "unit_emit", "scan_mfma2s"]
+names = ["verify_flat", "stats_kernel", "row_sort_kernel<1024", "row_scatter", "unit_rank", "scan_mfma2s"]
 for f in sorted(glob.glob("gpurun_out/pmc_tail/pass*.csv")):
     by = collections.defaultdict(lambda: collections.defaultdict(list))
     for x in csv.DictReader(open(f)):
