@@ -113,6 +113,8 @@ HIP_SYMBOLS = {
     "focr_total_lines": (C.c_size_t, [C.c_void_p]),
     "focr_get_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "focr_lines_device_chars": (C.c_void_p, [C.c_void_p]),
+    "focr_verify_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "focr_last_verify_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "focr_last_timings": (C.c_int, [C.c_void_p, C.c_void_p]),
     "focr_last_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
     "focr_sync": (C.c_int, [C.c_void_p]),
@@ -188,6 +190,7 @@ HOST_SYMBOLS = {
     "focr_image_load_luma8_into": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                              C.c_char_p, C.c_size_t]),
     "focr_image_save_pgm": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_size_t]),
+    "focr_image_save_png": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "focr_synth_page": (C.c_size_t, [C.POINTER(BankStruct), C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p,
                                      C.c_void_p, C.c_size_t]),
     "focr_format_f32": (C.c_size_t, [C.c_float, C.c_char_p, C.c_size_t]),

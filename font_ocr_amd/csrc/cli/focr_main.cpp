@@ -25,7 +25,6 @@
 
 #include <sys/stat.h>
 #include <unistd.h>
-#include <zlib.h>
 
 #include "focr_decode.h"
 #include "focr_host.h"
@@ -174,45 +173,9 @@ std::string utf8_encode(uint32_t cp) {
     return s;
 }
 
-// 8-bit RGB (colour type 2) or RGBA (colour type 6) PNG, filter 0 on every row (what DynamicImage::save writes for an
-// RgbImage / RgbaImage, byte for byte in the pixels)
+// 8-bit RGB or RGBA PNG (focr_image_save_png, the host library's writer)
 bool write_png(const std::string &path, const uint8_t *px, uint32_t w, uint32_t h, bool alpha) {
-    const size_t row = (size_t)w * (alpha ? 4 : 3);
-    std::vector<uint8_t> raw((row + 1) * h);
-    for (uint32_t y = 0; y < h; y++) {
-        raw[(size_t)y * (row + 1)] = 0;
-        if (row) memcpy(&raw[(size_t)y * (row + 1) + 1], px + (size_t)y * row, row);
-    }
-    uLongf zl = compressBound((uLong)raw.size());
-    std::vector<uint8_t> z(zl);
-    if (compress2(z.data(), &zl, raw.data(), (uLong)raw.size(), 6) != Z_OK) return false;
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) return false;
-    auto be32 = [](uint8_t *p, uint32_t v) { p[0] = v >> 24, p[1] = v >> 16, p[2] = v >> 8, p[3] = v; };
-    auto chunk = [&](const char *type, const uint8_t *data, uint32_t len) {
-        uint8_t hdr[8];
-        be32(hdr, len);
-        memcpy(hdr + 4, type, 4);
-        fwrite(hdr, 1, 8, f);
-        if (len) fwrite(data, 1, len, f);
-        uLong crc = crc32(0, (const Bytef *)type, 4);
-        if (len) crc = crc32(crc, data, len);
-        uint8_t c[4];
-        be32(c, (uint32_t)crc);
-        fwrite(c, 1, 4, f);
-    };
-    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
-    fwrite(sig, 1, 8, f);
-    uint8_t ihdr[13] = {0};
-    be32(ihdr, w);
-    be32(ihdr + 4, h);
-    ihdr[8] = 8;  // bit depth
-    ihdr[9] = alpha ? 6 : 2;  // colour type: RGBA or RGB
-    chunk("IHDR", ihdr, 13);
-    chunk("IDAT", z.data(), (uint32_t)zl);
-    chunk("IEND", nullptr, 0);
-    bool ok = ferror(f) == 0;
-    return fclose(f) == 0 && ok;
+    return focr_image_save_png(path.c_str(), px, w, h, alpha ? 4 : 3) == 0;
 }
 
 struct Line {

@@ -7,7 +7,9 @@
 //     (src/ncc.rs:839-847); output order is still the order of -i;
 //   * --rust runs the exact v_dot4 device kernel with the arithmetic and skips of the reference's scalar Rust
 //     scan and without the 1024 cap (FOCR_SCAN_RUST; src/ncc.rs:320-330, 406-483);
-//   * a page without any hit prints nothing (the reference panics in partition_by, src/ncc.rs:1040).
+//   * a page without any hit prints nothing (the reference panics in partition_by, src/ncc.rs:1040);
+//   * --verify DIR (extension) writes, per input image, the device's verify image (focr_verify_images: the page in red, the
+//     decoded characters' templates in blue) as DIR/<file stem>.png and prints "<image> <mse>" on stderr, as `focr --verify` does.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -20,6 +22,7 @@
 #include <deque>
 #include <future>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -27,7 +30,6 @@
 
 #include <sys/stat.h>
 #include <unistd.h>
-#include <zlib.h>
 
 #include "focr_host.h"
 
@@ -50,6 +52,8 @@ struct Args {
     bool save_letters = false, rust = false, verbose = false, csv = false, raw = false;
     bool allow_wide = false;  // extension: templates 17..32 px wide instead of the reference's panic (src/ncc.rs:392)
     bool spaces = false;  // extension: fill gaps between characters with blanks (the reference does not, README.md:46)
+    std::string verify;   // extension: directory for the verify images (focr_verify_images), as `focr --verify`
+    bool have_verify = false;
 };
 
 [[noreturn]] void usage_error(const std::string &msg) {
@@ -79,6 +83,7 @@ void print_help() {
          "      --raw                                  \n"
          "      --spaces                               [extension] print blanks for gaps of whole advances\n"
          "      --allow-wide                           [extension] accept templates 17..32 px wide\n"
+         "      --verify <VERIFY>                      [extension] Dir for verify images. Red is the page, Blue the decoded characters\n"
          "  -h, --help                                 Print help\n"
          "  -V, --version                              Print version");
 }
@@ -148,6 +153,7 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--raw") a.raw = true;
         else if (k == "--spaces") a.spaces = true;
         else if (k == "--allow-wide") a.allow_wide = true;
+        else if (k == "--verify") a.verify = need(), a.have_verify = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -158,6 +164,11 @@ Args parse_args(int argc, char **argv) {
     }
     if (a.font.empty()) usage_error("the following required arguments were not provided:\n  --font <FONT>");
     if (!a.have_text_size) usage_error("the following required arguments were not provided:\n  --text-size <TEXT_SIZE>");
+    if (a.have_verify) {  // refused here, before the bank is rasterised or a device is touched
+        if (a.raw) usage_error("the argument '--verify <VERIFY>' cannot be used with '--raw' (no characters are decoded in that mode)");
+        struct stat st;
+        if (stat(a.verify.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) usage_error("--verify should be a dir: '" + a.verify + "'");
+    }
     return a;
 }
 
@@ -199,42 +210,11 @@ std::string f32s(float v) {  // Rust `{}` of an f32
     return buf;
 }
 
-// --save-letters: letters/{letter}-{x}_{y}.png, 8-bit grey (src/ncc.rs:642-649)
-bool write_png_gray(const std::string &path, const uint8_t *px, uint32_t w, uint32_t h) {
-    std::vector<uint8_t> raw((size_t)(w + 1) * h);
-    for (uint32_t y = 0; y < h; y++) {
-        raw[(size_t)y * (w + 1)] = 0;
-        memcpy(&raw[(size_t)y * (w + 1) + 1], px + (size_t)y * w, w);
-    }
-    uLongf zl = compressBound((uLong)raw.size());
-    std::vector<uint8_t> z(zl);
-    if (compress2(z.data(), &zl, raw.data(), (uLong)raw.size(), 6) != Z_OK) return false;
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) return false;
-    auto be32 = [](uint8_t *p, uint32_t v) { p[0] = v >> 24, p[1] = v >> 16, p[2] = v >> 8, p[3] = v; };
-    auto chunk = [&](const char *type, const uint8_t *data, uint32_t len) {
-        uint8_t hdr[8];
-        be32(hdr, len);
-        memcpy(hdr + 4, type, 4);
-        fwrite(hdr, 1, 8, f);
-        if (len) fwrite(data, 1, len, f);
-        uLong crc = crc32(0, (const Bytef *)type, 4);
-        if (len) crc = crc32(crc, data, len);
-        uint8_t c[4];
-        be32(c, (uint32_t)crc);
-        fwrite(c, 1, 4, f);
-    };
-    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
-    fwrite(sig, 1, 8, f);
-    uint8_t ihdr[13] = {0};
-    be32(ihdr, w);
-    be32(ihdr + 4, h);
-    ihdr[8] = 8;  // bit depth, colour type 0 (grey)
-    chunk("IHDR", ihdr, 13);
-    chunk("IDAT", z.data(), (uint32_t)zl);
-    chunk("IEND", nullptr, 0);
-    fclose(f);
-    return true;
+std::string verify_path(const std::string &dir, const std::string &img) {  // DIR/<file stem>.png, as `focr --verify` names it
+    std::string name = img.substr(img.find_last_of('/') == std::string::npos ? 0 : img.find_last_of('/') + 1);
+    const size_t dot = name.find_last_of('.');
+    if (dot != std::string::npos && dot != 0) name = name.substr(0, dot);
+    return dir + (dir.empty() || dir.back() == '/' ? "" : "/") + name + ".png";
 }
 
 [[noreturn]] void die(const std::string &msg) {
@@ -306,7 +286,7 @@ int main(int argc, char **argv) {
             const focr_template_t &d = bank.templates[t];
             std::string path = "letters/" + utf8_encode(d.letter) + "-" + std::to_string((size_t)(d.off_x * 1000.f)) + "_" +
                                std::to_string((size_t)(d.off_y * 1000.f)) + ".png";
-            if (!write_png_gray(path, bank.needles + d.offset, d.n_w, d.n_h)) die("cannot write " + path);
+            if (focr_image_save_png(path.c_str(), bank.needles + d.offset, d.n_w, d.n_h, 1) != 0) die("cannot write " + path);  // 8-bit grey, src/ncc.rs:642-649
         }
     }
     if (args.img.empty()) return 0;
@@ -388,14 +368,40 @@ int main(int argc, char **argv) {
     size_t n_slabs = 0;                    // set once the device count is known (guarded by mu; 0 = decoders wait)
     bool stop = false;
     std::atomic<size_t> next{0};
+    // --verify: the PNGs of a retired batch are jobs for these same threads (a worker that waits for a slab, or has no image
+    // left to decode, encodes), so that the device loop does not wait for zlib
+    struct PngJob {
+        std::string path;
+        std::shared_ptr<std::vector<uint8_t>> rgb;  // the batch's images
+        size_t off = 0, w = 0, h = 0;
+    };
+    std::deque<PngJob> png_jobs;        // guarded by mu, as the three below
+    size_t png_pending = 0;             // queued or being written
+    bool png_open = args.have_verify;   // more jobs may come
+    std::string png_failed;             // the first file that could not be written
+    auto run_png_job = [&](std::unique_lock<std::mutex> &lk) {  // mu held, a job queued
+        PngJob j = std::move(png_jobs.front());
+        png_jobs.pop_front();
+        lk.unlock();
+        const bool ok = focr_image_save_png(j.path.c_str(), j.rgb->data() + j.off, j.w, j.h, 3) == 0;
+        j.rgb.reset();
+        lk.lock();
+        if (!ok && png_failed.empty()) png_failed = j.path;
+        png_pending--;
+        cv.notify_all();
+    };
     auto decode_worker = [&]() {
         for (size_t i; (i = next.fetch_add(1)) < N;) {
             const size_t b = pages[i].batch;
             uint8_t *slab;
             {
                 std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || (n_slabs && b < retired + n_slabs); });
-                if (stop) return;
+                for (;;) {
+                    cv.wait(lk, [&] { return stop || !png_jobs.empty() || (n_slabs && b < retired + n_slabs); });
+                    if (stop) return;
+                    if (n_slabs && b < retired + n_slabs) break;  // decoding feeds the devices: it goes first
+                    run_png_job(lk);
+                }
                 slab = slabs[b % n_slabs];
             }
             const size_t bytes = batches[b].w * batches[b].h;
@@ -407,6 +413,13 @@ int main(int argc, char **argv) {
                 pages[i].err = args.img[i] + ": size changed between header and decode";
             std::lock_guard<std::mutex> lk(mu);
             if (--left[b] == 0) cv.notify_all();
+        }
+        std::unique_lock<std::mutex> lk(mu);  // nothing left to decode: encode until the queue is closed
+        for (;;) {
+            cv.wait(lk, [&] { return stop || !png_jobs.empty() || !png_open; });
+            if (stop) return;
+            if (png_jobs.empty()) return;  // closed
+            run_png_job(lk);
         }
     };
     std::vector<std::thread> pool;
@@ -509,6 +522,32 @@ int main(int argc, char **argv) {
         }
         const uint64_t *page_off = R.page_line_off, *line_off = R.line_char_off;
         const focr_hit_t *chars = R.chars;
+        if (args.have_verify) {  // the batch's images, between its wait and its release, on the device it ran on
+            focr_ctx_t *ctx = nullptr;  // (focr_fleet_host_results above completed the batch: this wait returns at once, with the context)
+            if (focr_fleet_wait(fleet, tickets[b], &ctx) != FOCR_OK) fatal(std::string("scan: ") + focr_last_error_global());
+            {  // at most two batches of images in host memory
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return png_pending <= kBatch || !png_failed.empty(); });
+                if (!png_failed.empty()) {  // a full disk: stop here, not after every batch
+                    const std::string path = png_failed;
+                    lk.unlock();
+                    fatal("cannot write " + path);
+                }
+            }
+            auto rgb = std::make_shared<std::vector<uint8_t>>(B.n * B.w * B.h * 3);
+            std::vector<uint64_t> sums(B.n, 0);
+            if (focr_verify_images(ctx, rgb->data(), 0, sums.data()) != FOCR_OK) fatal(std::string("focr_verify_images: ") + focr_last_error(ctx));
+            for (size_t k = 0; k < B.n; k++) {  // red_blue_mse's quotient and `focr --verify`'s line
+                const float mse = (float)sums[k] / (float)(uint32_t)(B.w * B.h);
+                fprintf(stderr, "%s %.6f\n", args.img[B.p0 + k].c_str(), (double)mse);
+            }
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                for (size_t k = 0; k < B.n; k++) png_jobs.push_back(PngJob{verify_path(args.verify, args.img[B.p0 + k]), rgb, k * B.w * B.h * 3, B.w, B.h});
+                png_pending += B.n;
+            }
+            cv.notify_all();
+        }
         ms_results += since(t0);
         t0 = now();
         for (size_t k = 0; k < B.n; k++) {  // output, src/ncc.rs:849-877
@@ -617,6 +656,16 @@ int main(int argc, char **argv) {
             fatal(std::string("focr_fleet_submit: ") + focr_last_error_global());
     }
     while (next_retire < n_batches) retire(next_retire++);
+    {  // --verify: every image is on disk before the pool goes
+        std::unique_lock<std::mutex> lk(mu);
+        png_open = false;
+        cv.notify_all();
+        cv.wait(lk, [&] { return png_pending == 0; });
+        if (!png_failed.empty()) {
+            lk.unlock();
+            fatal("cannot write " + png_failed);
+        }
+    }
     stop_pool();
     if (args.verbose) {
         std::vector<std::pair<uint64_t, uint32_t>> by;  // src/ncc.rs:711-718: (count, char) ascending, zero counts skipped

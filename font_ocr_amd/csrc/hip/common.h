@@ -13,6 +13,10 @@
 #include "devmem.h"
 #include "focr_ncc.h"
 
+namespace focr_dec {
+struct VerifyRec;  // decode.h
+}
+
 namespace focr {
 
 struct VerifyMeta;  // mfma_common.h
@@ -304,6 +308,14 @@ struct focr_ctx {
     size_t n_chars = 0, n_lines = 0;
     std::vector<uint64_t> h_page_line_off, h_line_char_off;
     std::vector<focr_hit_t> h_chars;
+
+    // focr_verify_images (ncc_images.hip): buffers of its own, exact growth, idle between two calls (each ends with a wait for io_stream)
+    focr::DevArray<focr_dec::VerifyRec> vimg_recs;
+    focr::DevArray<unsigned long long> vimg_sums;
+    focr::DevArray<uint8_t> vimg_rgb;  // the image on its way to host memory
+    hipEvent_t vimg_ev[2] = {};
+    float vimg_ms = 0.f;
+    uint32_t vimg_launches = 0;
 
     template <typename T>
     bool scratch(focr::DevArray<T> &a, size_t want) {  // grow-only scratch: Grow::quarter, behind the context's stream

@@ -197,6 +197,7 @@ int focr_ctx_create(int device, focr_ctx_t **out) {
             if (!b && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(b, c->stream);
         }
         for (auto &ev : c->ev) FOCR_HIP(c, hipEventCreate(&ev));
+        for (auto &ev : c->vimg_ev) FOCR_HIP(c, hipEventCreate(&ev));
         FOCR_HIP(c, c->d_counter.reserve(COUNTER_BYTES / sizeof(uint32_t), Grow::exact, nullptr));
         FOCR_HIP(c, hipMemsetAsync(c->d_counter, 0, COUNTER_BYTES, c->stream));
         FOCR_HIP(c, c->d_res.reserve(8, Grow::exact, nullptr));
@@ -223,6 +224,8 @@ void focr_ctx_destroy(focr_ctx_t *c) {
     if (c->h_res) (void)hipHostFree(c->h_res);
     if (c->h_live) (void)hipHostFree(c->h_live);
     for (auto &ev : c->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : c->vimg_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->launch_events)
         if (ev) (void)hipEventDestroy(ev);

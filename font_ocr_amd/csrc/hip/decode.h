@@ -1,6 +1,6 @@
 // decode.h — what the two halves of the `focr` decoder share (decode.hip: font and line decoder; decode_images.hip: the
-// verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels, the blank
-// test's crop, the decoder itself, and the host plumbing every entry point repeats (errors, stages, staging, refusals).
+// verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels (ncc_images.hip
+// is its third user), the blank test's crop, the decoder itself, and the host plumbing every entry point repeats (errors, stages, staging, refusals).
 #pragma once
 
 #include <algorithm>
@@ -119,16 +119,23 @@ __device__ __forceinline__ void slot_range(const Geometry &g, int r0, int r1, in
     *i_hi = hi < 0 ? -1 : std::min<int64_t>(g.n_slots - 1, hi / g.line_advance);
 }
 
-// Every wave takes glyph records of recs[0 .. n), clips them to the tile and leaves 1 + index of the last glyph over each
-// pixel in win: an LDS atomic max, so neither placement nor arrival order matters.
+// Every wave takes glyph records of recs[0 .. n), clips them to the tile and leaves base + 1 + index of the last glyph over each
+// pixel in win: an LDS atomic max, so neither placement nor arrival order matters.  INK_ONLY: a glyph counts only where its
+// bitmap byte is not zero (the NCC images, where a character's zero pixels leave an earlier character's blue standing); base:
+// recs is a piece of a longer array whose index orders the glyphs (the caller reads the word back against that array).
+template <bool INK_ONLY = false>
 __device__ __forceinline__ void mark_glyphs(uint32_t *win, const VerifyRec *__restrict__ recs, uint32_t n, const Tile &T, uint32_t lane,
-                                            uint32_t wave) {
+                                            uint32_t wave, uint32_t base = 0, const uint8_t *__restrict__ bitmaps = nullptr) {
     for (uint32_t j = wave; j < n; j += VERIFY_TILE_W / 64) {
         const VerifyRec r = recs[j];
         const int x0 = std::max(r.x0, T.c0), x1 = std::min(r.x1, T.c1), y0 = std::max(r.y0, T.r0), y1 = std::min(r.y1, T.r1);
         if (x0 >= x1 || y0 >= y1) continue;
         const int w = x1 - x0, npx = w * (y1 - y0);
-        for (int q = (int)lane; q < npx; q += 64) atomicMax(&win[(y0 + q / w - T.r0) * VERIFY_TILE_W + (x0 + q % w - T.c0)], j + 1);
+        for (int q = (int)lane; q < npx; q += 64) {
+            const int x = x0 + q % w, y = y0 + q / w;
+            if (INK_ONLY && !bitmaps[r.src + (uint32_t)(y - r.y0) * r.stride + (uint32_t)(x - r.x0)]) continue;
+            atomicMax(&win[(y - T.r0) * VERIFY_TILE_W + (x - T.c0)], base + j + 1);
+        }
     }
 }
 
@@ -136,6 +143,20 @@ __device__ __forceinline__ void mark_glyphs(uint32_t *win, const VerifyRec *__re
 __device__ __forceinline__ uint8_t glyph_value(uint32_t w, const VerifyRec *__restrict__ recs, const uint8_t *__restrict__ bitmaps, int x, int y) {
     const VerifyRec r = recs[w - 1];
     return bitmaps[r.src + (uint32_t)(y - r.y0) * r.stride + (uint32_t)(x - r.x0)];
+}
+
+// The workgroup's sum of every thread's acc (at most 2^32 in all), added to *sum with one 64-bit atomic by thread 0; `part` is
+// VERIFY_TILE_W / 64 words of LDS.  Ends with a barrier: win and part are free again.
+__device__ __forceinline__ void tile_add_sum(uint32_t acc, uint32_t *part, unsigned long long *sum, uint32_t t) {
+    for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 64);
+    if ((t & 63) == 0) part[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) {
+        unsigned long long total = 0;
+        for (uint32_t w = 0; w < VERIFY_TILE_W / 64; w++) total += part[w];
+        if (total) atomicAdd(sum, total);
+    }
+    __syncthreads();
 }
 
 struct Stage {  // the kernels of one entry point's last call: device events around them, their time and their number

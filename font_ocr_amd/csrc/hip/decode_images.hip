@@ -155,15 +155,7 @@ __global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_kernel(const uin
                 const int dd = (int)red - (int)b;
                 acc += (uint32_t)(dd * dd);  // at most 16 * 255^2 per thread, 2^28 per workgroup
             }
-        for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 64);
-        if (lane == 0) part[wave] = acc;
-        __syncthreads();
-        if (t == 0) {
-            unsigned long long sum = 0;
-            for (uint32_t w = 0; w < VERIFY_TILE_W / 64; w++) sum += part[w];
-            if (sum) atomicAdd(&sums[page], sum);
-        }
-        __syncthreads();
+        tile_add_sum(acc, part, &sums[page], t);
     }
 }
 

@@ -500,6 +500,47 @@ int focr_image_save_pgm(const char *path, const uint8_t *px, size_t w, size_t h)
     return ok ? 0 : 1;
 }
 
+int focr_image_save_png(const char *path, const uint8_t *px, size_t w, size_t h, int channels) {
+    if (!path || (channels != 1 && channels != 3 && channels != 4) || w > 0x7fffffffu || h > 0x7fffffffu || (!px && w && h)) return 1;
+    const size_t row = w * (size_t)channels;
+    std::vector<uint8_t> raw((row + 1) * h);
+    for (size_t y = 0; y < h; y++) {
+        raw[y * (row + 1)] = 0;  // filter 0
+        if (row) memcpy(&raw[y * (row + 1) + 1], px + y * row, row);
+    }
+    if (raw.size() > 0x7fffffffu) return 1;
+    uLongf zl = compressBound((uLong)raw.size());
+    std::vector<uint8_t> z(zl);
+    if (compress2(z.data(), &zl, raw.data(), (uLong)raw.size(), 6) != Z_OK) return 1;
+    FILE *f = fopen(path, "wb");
+    if (!f) return 1;
+    auto be32 = [](uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 24), p[1] = (uint8_t)(v >> 16), p[2] = (uint8_t)(v >> 8), p[3] = (uint8_t)v; };
+    auto chunk = [&](const char *type, const uint8_t *data, uint32_t len) {
+        uint8_t hdr[8];
+        be32(hdr, len);
+        memcpy(hdr + 4, type, 4);
+        fwrite(hdr, 1, 8, f);
+        if (len) fwrite(data, 1, len, f);
+        uLong crc = crc32(0, (const Bytef *)type, 4);
+        if (len) crc = crc32(crc, data, len);
+        uint8_t c[4];
+        be32(c, (uint32_t)crc);
+        fwrite(c, 1, 4, f);
+    };
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    fwrite(sig, 1, 8, f);
+    uint8_t ihdr[13] = {0};
+    be32(ihdr, (uint32_t)w);
+    be32(ihdr + 4, (uint32_t)h);
+    ihdr[8] = 8;                                           // bit depth
+    ihdr[9] = channels == 1 ? 0 : channels == 3 ? 2 : 6;  // colour type: grey, RGB, RGBA
+    chunk("IHDR", ihdr, 13);
+    chunk("IDAT", z.data(), (uint32_t)zl);
+    chunk("IEND", nullptr, 0);
+    const bool ok = ferror(f) == 0;
+    return fclose(f) == 0 && ok ? 0 : 1;
+}
+
 size_t focr_synth_page(const focr_bank_t *bank, uint64_t seed, size_t r_w, size_t r_h, uint8_t *luma_out,
                        focr_hit_t *truth, size_t truth_cap) {
     std::vector<uint8_t> ink(r_w * r_h, 0);

@@ -344,6 +344,40 @@ class Scanner:
     def total_chars(self):
         return int(self._lib.focr_total_chars(self._h))
 
+    def verify_images(self, rgb=True, out=None, sq_sums=True):
+        """focr_verify_images: the characters of the last process_hits() redrawn over their pages on the device, read like
+        `focr --verify`'s image: red = the page (255 - ink), blue = 255 - v of the decoded characters' templates where v != 0
+        (later characters win where they have ink), green = 0.  Returns (rgb, sq_sums): an (n_pages, r_h, r_w, 3) uint8 array
+        and the per-page exact uint64 sums of (R - B)^2 (verify_mse turns them into the reference's f32 quotient).
+        rgb=False / None: sums only (rgb is None); sq_sums=False / None: image only.  out: where the image goes instead of a
+        fresh array, either a C-contiguous uint8 numpy array of that shape or a device pointer (int, e.g. tensor.data_ptr() of
+        a uint8 tensor of n_pages * r_h * r_w * 3 elements on the context's device), which is then returned as it is.
+        Works the same on the Scanner that Pipeline.wait / Fleet.wait return, until the ticket's release.
+
+            sc.scan(0.8); sc.process_hits(0.95, 5)
+            rgb, sums = sc.verify_images()
+            worst = int(np.argmax(verify_mse(sums, sc.r_w, sc.r_h)))   # the page to look at first
+        """
+        shape = (self.n_pages, self.r_h, self.r_w, 3)
+        want_rgb = out is not None or (rgb is not None and rgb is not False)
+        sums = np.zeros(self.n_pages, np.uint64) if (sq_sums is not None and sq_sums is not False) else None
+        img, ptr, on_dev = None, None, 0
+        if out is not None and not isinstance(out, np.ndarray):
+            img, ptr, on_dev = out, C.c_void_p(int(out)), 1
+        elif want_rgb:
+            img = np.empty(shape, np.uint8) if out is None else out
+            if img.dtype != np.uint8 or not img.flags["C_CONTIGUOUS"] or img.shape != shape:
+                raise ValueError(f"verify_images: out must be a C-contiguous uint8 array of shape {shape}")
+            ptr = _ptr(img)
+        self._ck(self._lib.focr_verify_images(self._h, ptr, on_dev, None if sums is None else _ptr(sums)))
+        return img, sums
+
+    def last_verify_images(self):
+        """focr_last_verify_images: {'ms': device time of the last verify_images' kernels, 'launches': their number}."""
+        ms, n = C.c_float(), C.c_uint32()
+        self._ck(self._lib.focr_last_verify_images(self._h, C.byref(ms), C.byref(n)))
+        return {"ms": float(ms.value), "launches": int(n.value)}
+
     def timings(self):
         ms = (C.c_float * 6)()
         self._lib.focr_last_timings(self._h, ms)
@@ -489,6 +523,12 @@ class Pipeline:
         rc = self._lib.focr_pipe_release(self._h, int(ticket))
         if rc != 0:
             raise FocrError(f"[{rc}] focr_pipe_release: ticket is not outstanding")
+
+
+def verify_mse(sq_sums, r_w, r_h):
+    """The reference's red_blue_mse of verify_images' sums: (float)sum / (float)(uint32_t)(r_w * r_h), one f32 division per page."""
+    n = np.float32(np.uint32((int(r_w) * int(r_h)) & 0xFFFFFFFF))
+    return np.asarray(sq_sums, np.uint64).astype(np.float32) / n
 
 
 def text_of(lines, advance_px=None):

@@ -77,6 +77,11 @@ int focr_image_load_luma8_into(const char *path, uint8_t *dst, size_t cap, size_
                                size_t errlen);
 int focr_image_save_pgm(const char *path, const uint8_t *px, size_t w, size_t h);
 
+/* 8-bit PNG of w x h pixels with 1 (grey), 3 (RGB) or 4 (RGBA) channels, tight rows, filter 0 on every row, one IDAT
+ * (what image's DynamicImage::save writes for these buffers, byte for byte in the pixels): `ncc --save-letters` and
+ * `--verify`, `focr --verify` and `--test`.  Non-zero if it cannot be written. */
+int focr_image_save_png(const char *path, const uint8_t *px, size_t w, size_t h, int channels);
+
 /* Text of one output line as `ncc` prints it (src/ncc.rs:869-876): the letters
  * of the line's characters concatenated, UTF-8, no terminator written beyond a
  * NUL when it fits.  spaces != 0 is an EXTENSION (the reference does not detect

@@ -209,6 +209,33 @@ int focr_get_lines_into(focr_ctx_t *ctx, uint64_t *page_line_offsets, uint64_t *
  * device-side consumers (e.g. the RCCL gather of match lists across GPUs). */
 const focr_hit_t *focr_lines_device_chars(focr_ctx_t *ctx);
 
+/* Verify images: the characters of the last focr_process_hits redrawn over their pages on the device, read like the line
+ * decoder's --verify image (draw_verify + red_blue_mse of the reference's src/main.rs, as focr_decoder_verify restates them).
+ * For every page of the batch an RGB image of r_w x r_h, from black:
+ *   red    the page's luma where it is not 255 (255 - ink where the resident page has ink; the same whether the page was
+ *          uploaded with invert or as ink-high bytes), 0 elsewhere; characters never change it
+ *   blue   255 - v where a character's template has v != 0 at the pixel.  A character is one focr_hit_t of the output:
+ *          template template_index with its top-left corner at (x, y), w x h canvas bytes verbatim (paddings included).
+ *          Characters apply in the output's order (page, line, x: their index in chars); a later one replaces an earlier
+ *          one's blue only where its own v != 0
+ *   green  0
+ * and sq_sums[page] = the exact integer sum over the page of (R - B)^2; the reference's MSE is
+ * (float)sum / (float)(uint32_t)(r_w * r_h), the caller's to compute.  The reference's quirks are kept: uncovered paper adds
+ * 0, and so does an uncovered pixel of luma 0 (red 0, blue 0).
+ * rgb: n_pages * r_h * r_w * 3 bytes, tight, in host memory or (rgb_on_device != 0) on the context's device; NULL = sums
+ * only.  sq_sums: n_pages values in host memory; NULL = image only.  Both NULL: FOCR_ERR_INVALID.  Returns when both are
+ * written.  FOCR_ERR_STATE unless a focr_process_hits has completed on this context since its last scan.  Valid after a
+ * plain scan, a split-batch scan and focr_debug_process_hits (with pages and bank uploaded: this call reads them), and on
+ * the context focr_pipe_wait / focr_fleet_wait hand out, until that ticket's release: the batch's pages stay the context's
+ * resident set until its next batch is queued, which focr_pipe_submit does only once the slot is released.  There it waits
+ * for the batch's own event and runs on the lane's side stream, like the getters, never behind the lane's next batch.
+ * Two kernel launches per call, whatever the data.  (Python: Scanner.verify_images(rgb=True, out=None, sq_sums=True); the
+ * third argument, beyond rgb and out, is how the "sq_sums NULL" form is reached from there.) */
+int focr_verify_images(focr_ctx_t *ctx, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums);
+/* Device time (ms, HIP events around the two kernels) and number of launches of the context's last focr_verify_images
+ * (0 and 0 after one that failed); either pointer may be NULL. */
+int focr_last_verify_images(focr_ctx_t *ctx, float *ms, uint32_t *launches);
+
 /* Device time (ms, HIP events on the context's stream) of the phases of the
  * last focr_scan / focr_process_hits: [0] window statistics, [1] scan kernel
  * (MFMA prefilter or direct), [2] exact verify, [3] ordering + cap,
@@ -507,7 +534,8 @@ int focr_debug_plane_value_device(focr_ctx_t *ctx, const float *L, size_t n, uin
  * group boundaries and capped hits where focr_process_hits' line walk cuts a row into chunks of 64.  Hit i is (page[i], y[i],
  * x[i], template t[i], similarity[i]); keep[i] == 0 marks a hit cut off by its call's cap, which process_hits does not see.
  * The hits must be strictly increasing in (page, y, x, t) and lie inside the context's pages and bank (focr_pages_alloc,
- * focr_bank_upload; their contents are not read).  focr_process_hits and focr_get_lines then run unchanged;
+ * focr_bank_upload; focr_process_hits does not read their contents, focr_verify_images does: upload both before asking
+ * for images).  focr_process_hits and focr_get_lines then run unchanged;
  * focr_get_counts and focr_get_matches refuse, as no per-call lists stand behind such hits.  The next focr_scan replaces them. */
 int focr_debug_process_hits(focr_ctx_t *ctx, const uint32_t *page, const uint32_t *y, const uint32_t *x, const uint32_t *t,
                             const float *similarity, const uint8_t *keep, size_t n);
