@@ -327,6 +327,12 @@ class DecodedLine(C.Structure):
     _fields_ = [("page", C.c_uint32), ("y", C.c_uint32), ("first", C.c_uint64), ("n_chars", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class CharScore(C.Structure):
+    """focr_char_score_t (include/focr_decode.h)."""
+
+    _fields_ = [("score", C.c_int64), ("runner_score", C.c_int64), ("runner", C.c_uint16), ("pad", C.c_uint16 * 3)]
+
+
 # the declarations of include/focr_decode.h in libfocr_raster.so
 DECODE_RASTER_SYMBOLS = {
     "focr_raster_glyph": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_size_t,
@@ -356,6 +362,8 @@ DECODE_HIP_SYMBOLS = {
     "focr_decoder_get": (C.c_int, [C.c_void_p, C.POINTER(DecodedLine), C.c_void_p]),
     "focr_decoder_last_ms": (C.c_float, [C.c_void_p]),
     "focr_decoder_last_launches": (C.c_uint32, [C.c_void_p]),
+    "focr_decoder_set_scores": (C.c_int, [C.c_void_p, C.c_int]),
+    "focr_decoder_get_scores": (C.c_int, [C.c_void_p, C.POINTER(CharScore), C.c_void_p]),
     "focr_decoder_set_verify_font": (C.c_int, [C.c_void_p, C.POINTER(VerifyFontStruct)]),
     "focr_decoder_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "focr_decoder_last_verify_ms": (C.c_float, [C.c_void_p]),
@@ -370,7 +378,10 @@ DECODE_HIP_SYMBOLS = {
 
 
 def _bind(lib, symbols):
+    experiment = bool(os.environ.get("FOCR_HIP_LIB"))
     for sym, (restype, argtypes) in symbols.items():
+        if experiment and not hasattr(lib, sym):
+            continue  # as in _load: an A/B build of another commit may predate a symbol
         fn = getattr(lib, sym)  # AttributeError if the library does not export it
         fn.restype = restype
         fn.argtypes = argtypes

@@ -9,7 +9,9 @@
 //   * --test draws its two images on the device (focr_decoder_test_images) from the first -i image only, as the reference
 //     does; boxes that fall outside the page are clipped (the reference panics in get_pixel_mut), the decode font's
 //     refusals apply (kerning <= 0, a glyph that does not advance; the reference's --test decodes nothing), line_advance 0
-//     is refused, and its blend is image's Blend for Rgba<u8> restated in f32 (parity unpinned).
+//     is refused, and its blend is image's Blend for Rgba<u8> restated in f32 (parity unpinned);
+//   * --scores PATH is an extension: a CSV row per decoded character with its score, the runner-up and the margin between
+//     them (focr_decoder_get_scores); stdout and the --verify files are the same with and without it.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -36,8 +38,8 @@ const size_t BATCH_PAGES = 256;
 
 struct Args {
     std::vector<std::string> img;
-    std::string font, alphabet = DEFAULT_ALPHABET, verify, test;
-    bool hinting = false, have_verify = false, have_test = false;
+    std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores;
+    bool hinting = false, have_verify = false, have_test = false, have_scores = false;
     float text_size = 0.f, kerning = 1.f;
     uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0;
     bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
@@ -73,6 +75,7 @@ void print_help() {
            "      --line-advance <LINE_ADVANCE>    \n"
            "      --test <TEST>                    Prefix for output test images\n"
            "      --verify <VERIFY>                Dir for verify images. Red is reference, Blue is rendered\n"
+           "      --scores <SCORES>                [extension] CSV of every decoded character's score, runner-up and margin\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -129,6 +132,7 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--line-advance") a.line_advance = num_u(need()), a.have_line_advance = true;
         else if (k == "--test") a.test = need(), a.have_test = true;
         else if (k == "--verify") a.verify = need(), a.have_verify = true;
+        else if (k == "--scores") a.scores = need(), a.have_scores = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -181,6 +185,7 @@ bool write_png(const std::string &path, const uint8_t *px, uint32_t w, uint32_t 
 struct Line {
     uint32_t y;
     std::vector<uint32_t> text;  // code points
+    std::vector<focr_char_score_t> scores;  // --scores: one per code point
 };
 
 // Writes the batch's verify images (the device's draw_verify, n x H x W x 3 bytes) as PNGs on at most 16 threads, and
@@ -254,6 +259,8 @@ int main(int argc, char **argv) {
     }
     std::vector<uint32_t> alphabet = utf8_decode(args.alphabet);
     if (args.have_test) return run_test(args, alphabet);
+    FILE *csv = nullptr;
+    if (args.have_scores && !(csv = fopen(args.scores.c_str(), "w"))) usage_error("cannot write '" + args.scores + "' for '--scores'");
     if (args.img.empty()) return 0;
 
     char err[256] = {0};
@@ -283,6 +290,7 @@ int main(int argc, char **argv) {
         if (focr_decoder_set_verify_font(dec, &vfont) != 0) die(std::string("focr_decoder_set_verify_font: ") + focr_decoder_last_error(dec), 1);
         focr_verify_font_free(&vfont);
     }
+    if (csv && focr_decoder_set_scores(dec, 1) != 0) die(std::string("focr_decoder_set_scores: ") + focr_decoder_last_error(dec), 1);
 
     std::vector<std::vector<Line>> lines(n_img);
     std::vector<uint8_t> batch, rgb;
@@ -307,9 +315,13 @@ int main(int argc, char **argv) {
             std::vector<focr_decoded_line_t> dl(focr_decoder_n_lines(dec));
             std::vector<uint16_t> dc(focr_decoder_n_chars(dec));
             focr_decoder_get(dec, dl.data(), dc.data());
+            std::vector<focr_char_score_t> ds(csv ? dc.size() : 0);
+            if (csv && focr_decoder_get_scores(dec, ds.data(), nullptr) != 0)
+                die(std::string("focr_decoder_get_scores: ") + focr_decoder_last_error(dec), 1);
             for (const focr_decoded_line_t &l : dl) {
-                Line out{l.y, {}};
+                Line out{l.y, {}, {}};
                 for (uint32_t c = 0; c < l.n_chars; c++) out.text.push_back(alphabet[dc[l.first + c]]);
+                if (csv) out.scores.assign(ds.begin() + l.first, ds.begin() + l.first + l.n_chars);
                 lines[grp.second[b0 + l.page]].push_back(std::move(out));
             }
             if (args.have_verify) {  // draw_verify + red_blue_mse (src/main.rs:300-329, 518-524) on the device
@@ -338,5 +350,18 @@ int main(int argc, char **argv) {
             out += '\n';
         }
     fwrite(out.data(), 1, out.size(), stdout);
+    if (csv) {  // one row per decoded character, in the order of stdout; a one-glyph alphabet has no runner-up and no margin
+        fprintf(csv, "image_index,y,column,codepoint,score,runner_codepoint,runner_score,margin\n");
+        for (size_t i = 0; i < n_img; i++)
+            for (const Line &l : lines[i])
+                for (size_t c = 0; c < l.text.size(); c++) {
+                    const focr_char_score_t &sc = l.scores[c];
+                    fprintf(csv, "%zu,%u,%zu,%u,%lld,", i, l.y, c, l.text[c], (long long)sc.score);
+                    if (sc.runner < alphabet.size())
+                        fprintf(csv, "%u,%lld,%lld\n", alphabet[sc.runner], (long long)sc.runner_score, (long long)(sc.runner_score - sc.score));
+                    else fprintf(csv, ",%lld,\n", (long long)sc.runner_score);
+                }
+        if (fclose(csv) != 0) die("cannot write " + args.scores);
+    }
     return 0;
 }

@@ -188,9 +188,17 @@ struct focr_decoder {
     focr::DevArray<uint8_t> d_pages, d_strips;
     focr::DevArray<uint32_t> d_flags, d_work, d_nchars, d_count;
     focr::DevArray<uint16_t> d_chars;
+    // scores (focr_decoder_set_scores): per step beside d_chars, per work-list line beside d_nchars; grown by a run with scores on
+    bool scores_on = false;
+    focr::DevArray<int32_t> d_term, d_runner_term;
+    focr::DevArray<uint16_t> d_runner;
+    focr::DevArray<uint64_t> d_base;
     // results of the last run
     std::vector<focr_decoded_line_t> lines;
     std::vector<uint16_t> chars;
+    bool have_scores = false;  // the last successful run was made with scores on
+    std::vector<focr_char_score_t> char_scores;
+    std::vector<uint64_t> line_base;
     // verify: the table, what the last successful run left for it, buffers
     uint32_t n_vglyphs = 0, hmax = 0;
     focr::DevArray<focr_dec::VerifyGlyph> d_vglyphs;

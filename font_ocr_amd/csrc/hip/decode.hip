@@ -6,7 +6,8 @@
 //   2. line_compact_kernel: one workgroup turns the flags into the work list of non-blank slots, in (page, line) order;
 //   3. line_decode_kernel: one wave per work-list line runs the reference's pen loop.  The pen and the step count are
 //      uniform across the wave; each lane scores its glyphs (lane, lane + 64, ...) against the strip (LDS when it fits)
-//      from the glyph's phase tile, then a wave argmin takes the lowest (score, glyph index).
+//      from the glyph's phase tile, then a wave argmin takes the lowest (score, glyph index).  With scores on
+//      (focr_decoder_set_scores) the same launch also keeps the second lowest key and sums r^2 over the line's crop.
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
@@ -79,13 +80,33 @@ __device__ __forceinline__ uint32_t edge_mask(int base, int w) {
     return m;
 }
 
-// 3. the pen loop, one wave per work-list line
-template <bool LDS>
+// The wave's sum of every lane's v, in every lane.
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
+        v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+
+__device__ __forceinline__ int key_term(uint64_t key) { return (int)((uint32_t)(key >> 32) ^ 0x80000000u); }
+
+// What line_decode_kernel<.., true> writes beside chars: per step (the layout of chars) the footprint terms of the
+// chosen glyph and of the runner-up and the runner-up's index; per work-list line the sum of r^2 over its crop.
+struct ScoreOut {
+    int32_t *term, *runner_term;
+    uint16_t *runner;
+    uint64_t *base;
+};
+
+// 3. the pen loop, one wave per work-list line.  SCORES: also the runner-up of every step (the second lowest key;
+// keys carry the glyph index, so they are distinct and a top-2 merge is exact) and the line's sum of r^2.
+template <bool LDS, bool SCORES>
 __global__ __launch_bounds__(64) void line_decode_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
                                                          const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
                                                          const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps,
                                                          uint32_t n_glyphs, float origin_x, uint32_t *__restrict__ n_chars,
-                                                         uint16_t *__restrict__ chars) {
+                                                         uint16_t *__restrict__ chars, ScoreOut so) {
     extern __shared__ uint32_t lds_strip[];
     const uint32_t k = blockIdx.x;
     if (k >= *count) return;
@@ -103,12 +124,18 @@ __global__ __launch_bounds__(64) void line_decode_kernel(const uint8_t *__restri
     const int w = (int)g.w;
     const float fw = (float)g.w;
     uint16_t *out = chars + (size_t)k * g.cap;
+    if (SCORES) {  // the rows below h hold nothing of this line, and a row's pad bytes are zero: whole rows of the crop
+        uint64_t acc = 0;
+        for (uint32_t q = lane; q < sdw * h; q += 64) acc += __builtin_amdgcn_udot4(strip[q], strip[q], 0u, false);
+        acc = wave_sum_u64(acc);
+        if (lane == 0) so.base[k] = acc;
+    }
     float pos = 0.f;
     uint32_t n = 0;
     while (pos < fw && n < g.cap) {
         const int d = (int)((origin_x + pos) * 64.0f);  // FreeType's delta: trunc(t * 64)
         const int phase = d & 63, shift = d >> 6;
-        uint64_t best = ~0ull;
+        uint64_t best = ~0ull, second = ~0ull;  // second: SCORES only
         for (uint32_t gi = lane; gi < n_glyphs; gi += 64) {
             const DevGlyph gl = glyphs[gi];
             const int2 o = offs[gi * 64 + phase];
@@ -132,14 +159,26 @@ __global__ __launch_bounds__(64) void line_decode_kernel(const uint8_t *__restri
             }
             const int score = (int)cc - 2 * (int)cr;
             const uint64_t key = ((uint64_t)((uint32_t)score ^ 0x80000000u) << 32) | gi;  // (score, index), lowest first
+            if (SCORES) second = std::min(second, std::max(best, key));
             best = std::min(best, key);
         }
         for (int m = 32; m >= 1; m >>= 1) {
             const uint32_t lo = __shfl_xor((uint32_t)best, m, 64), hi = __shfl_xor((uint32_t)(best >> 32), m, 64);
-            best = std::min(best, ((uint64_t)hi << 32) | lo);
+            const uint64_t p1 = ((uint64_t)hi << 32) | lo;
+            if (SCORES) {
+                const uint32_t lo2 = __shfl_xor((uint32_t)second, m, 64), hi2 = __shfl_xor((uint32_t)(second >> 32), m, 64);
+                second = std::min(std::max(best, p1), std::min(second, ((uint64_t)hi2 << 32) | lo2));
+            }
+            best = std::min(best, p1);
         }
         const uint32_t gbest = (uint32_t)best;
         if (lane == 0) out[n] = (uint16_t)gbest;
+        if (SCORES && lane == 0) {  // no runner-up (one glyph): the key stays ~0, whose index reads 0xffff
+            const size_t at = (size_t)k * g.cap + n;
+            so.term[at] = key_term(best);
+            so.runner_term[at] = key_term(second);
+            so.runner[at] = (uint16_t)second;
+        }
         n++;
         pos = __fadd_rn(pos, glyphs[gbest].inc);
     }
@@ -242,6 +281,9 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     dec->run_ok = false;
     dec->lines.clear();
     dec->chars.clear();
+    dec->have_scores = false;
+    dec->char_scores.clear();
+    dec->line_base.clear();
     dec->run.ms = 0.f;
     dec->run.launches = 0;
     if (!dec->n_glyphs) return dfail(dec, "focr_decoder_run: no font (focr_decoder_set_font)");
@@ -252,9 +294,11 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     const uint8_t *d_src = nullptr;
     if (stage_in(dec, dec->d_pages, pages, on_device, page_w * page_h * n_pages, &d_src)) return 1;
     const size_t total = g.total;
+    const bool scores = dec->scores_on;
     if (total == 0) {  // nothing to decode and nothing launched; a verify still draws the pages
         DEC_CHECK(hipStreamSynchronize(dec->stream));
         remember_run(dec, g, d_src, n_pages, x_start);
+        dec->have_scores = scores;
         return 0;
     }
     g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;
@@ -276,18 +320,24 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     DEC_GROW(dec->d_nchars, total);
     DEC_GROW(dec->d_count, 1);
     DEC_GROW(dec->d_chars, (size_t)g.cap * total);
+    if (scores) {
+        DEC_GROW(dec->d_term, (size_t)g.cap * total);
+        DEC_GROW(dec->d_runner_term, (size_t)g.cap * total);
+        DEC_GROW(dec->d_runner, (size_t)g.cap * total);
+        DEC_GROW(dec->d_base, total);
+    }
+    const ScoreOut so{dec->d_term, dec->d_runner_term, dec->d_runner, dec->d_base};  // null arrays with scores off: never touched
 
     DEC_CHECK(hipEventRecord(dec->run.begin, dec->stream));
     line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
     DEC_CHECK(hipGetLastError());
     line_compact_kernel<<<1, COMPACT_THREADS, 0, dec->stream>>>(dec->d_flags, g.total, dec->d_work, dec->d_count);
     DEC_CHECK(hipGetLastError());
-    if (strip_bytes <= LDS_STRIP_MAX)
-        line_decode_kernel<true><<<g.total, 64, strip_bytes, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs,
-                                                                         dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs, dec->origin_x, dec->d_nchars, dec->d_chars);
-    else
-        line_decode_kernel<false><<<g.total, 64, 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs,
-                                                                dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs, dec->origin_x, dec->d_nchars, dec->d_chars);
+    const auto decode = strip_bytes <= LDS_STRIP_MAX ? (scores ? line_decode_kernel<true, true> : line_decode_kernel<true, false>)
+                                                     : (scores ? line_decode_kernel<false, true> : line_decode_kernel<false, false>);
+    decode<<<g.total, 64, strip_bytes <= LDS_STRIP_MAX ? strip_bytes : 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs,
+                                                                                       dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs, dec->origin_x,
+                                                                                       dec->d_nchars, dec->d_chars, so);
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->run.end, dec->stream));
 
@@ -298,6 +348,16 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     DEC_CHECK(hipMemcpyAsync(work.data(), dec->d_work, total * 4, hipMemcpyDeviceToHost, dec->stream));
     DEC_CHECK(hipMemcpyAsync(nch.data(), dec->d_nchars, total * 4, hipMemcpyDeviceToHost, dec->stream));
     DEC_CHECK(hipMemcpyAsync(all.data(), dec->d_chars, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
+    std::vector<int32_t> term, runner_term;
+    std::vector<uint16_t> runner;
+    std::vector<uint64_t> base;
+    if (scores) {
+        term.resize(all.size()), runner_term.resize(all.size()), runner.resize(all.size()), base.resize(total);
+        DEC_CHECK(hipMemcpyAsync(term.data(), dec->d_term, all.size() * 4, hipMemcpyDeviceToHost, dec->stream));
+        DEC_CHECK(hipMemcpyAsync(runner_term.data(), dec->d_runner_term, all.size() * 4, hipMemcpyDeviceToHost, dec->stream));
+        DEC_CHECK(hipMemcpyAsync(runner.data(), dec->d_runner, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
+        DEC_CHECK(hipMemcpyAsync(base.data(), dec->d_base, total * 8, hipMemcpyDeviceToHost, dec->stream));
+    }
     DEC_CHECK(hipStreamSynchronize(dec->stream));
     DEC_CHECK(hipEventElapsedTime(&dec->run.ms, dec->run.begin, dec->run.end));
     dec->run.launches = 3;
@@ -313,8 +373,31 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         l.n_chars = n;
         l.pad = 0;
         dec->chars.insert(dec->chars.end(), all.begin() + (size_t)k * g.cap, all.begin() + (size_t)k * g.cap + n);
+        if (!scores) continue;
+        dec->line_base.push_back(base[k]);
+        for (size_t at = (size_t)k * g.cap; at < (size_t)k * g.cap + n; at++) {  // the reference's score: sum r^2 plus the footprint term
+            focr_char_score_t c{(int64_t)base[k] + term[at], (int64_t)base[k] + runner_term[at], runner[at], {0, 0, 0}};
+            if (dec->n_glyphs == 1) c.runner_score = INT64_MAX, c.runner = 0xffff;
+            dec->char_scores.push_back(c);
+        }
     }
     remember_run(dec, g, d_src, n_pages, x_start);
+    dec->have_scores = scores;
+    return 0;
+}
+
+extern "C" int focr_decoder_set_scores(focr_decoder_t *dec, int on) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_scores: null decoder");
+    dec->scores_on = on != 0;
+    return 0;
+}
+
+extern "C" int focr_decoder_get_scores(const focr_decoder_t *dec, focr_char_score_t *scores, uint64_t *line_base) {
+    if (!dec) return dfail(nullptr, "focr_decoder_get_scores: null decoder");
+    if (!dec->have_scores)
+        return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_scores: no successful run with scores on (focr_decoder_set_scores)");
+    if (scores && !dec->char_scores.empty()) memcpy(scores, dec->char_scores.data(), dec->char_scores.size() * sizeof(focr_char_score_t));
+    if (line_base && !dec->line_base.empty()) memcpy(line_base, dec->line_base.data(), dec->line_base.size() * sizeof(uint64_t));
     return 0;
 }
 

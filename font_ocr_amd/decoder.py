@@ -6,11 +6,14 @@
         # [[(y, text), ...] per page]
         pages, mse, images = dec.decode(luma_pages, 45, 39, 608, 12, 15, verify="image")
         # focr --verify on the device: red = the page's ink, blue = the decoded text re-rendered; MSE per page
+        pages, scores = dec.decode(luma_pages, 45, 39, 608, 12, 15, scores=True)
+        # scores[page][line]: what the argmin knew about each character of pages[page][line] (LineScores)
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
 There is no CPU path: the decoder needs a device, and says so when it has none.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -22,6 +25,16 @@ FOCR_DEFAULT_ALPHABET = "> =ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz
 
 class DecoderError(RuntimeError):
     pass
+
+
+class LineScores(collections.namedtuple("LineScores", "base score runner runner_score")):
+    """The scores of one decoded line (decode(..., scores=True)), aligned with its text.  base: the sum of r^2 over the
+    line's crop (int), the part of a score every candidate shares.  Per character: score, the reference's score of the
+    chosen glyph (int64); runner, the alphabet index of the glyph the argmin would have taken next (uint16; 0xFFFF for
+    a one-glyph alphabet); runner_score, that glyph's score (int64; INT64_MAX without a runner).  Glyphs with
+    identical bitmaps tie: runner_score == score."""
+
+    __slots__ = ()
 
 
 def _err():
@@ -163,6 +176,7 @@ class LineDecoder:
         self.last_test_ms = 0.0
         self._vfont = None
         self._batch = None  # (n_pages, page_h, page_w) of the last run
+        self._scores = False  # the library's switch (focr_decoder_set_scores)
 
     def _check(self, rc):
         if rc != 0:
@@ -275,8 +289,12 @@ class LineDecoder:
         mse = sums.astype(np.float32) / np.float32((h * w) & 0xFFFFFFFF)  # red_blue_mse: (sum as f32) / (w * h as u32)
         return mse, imgs
 
-    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance):
+    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False):
+        """[[(y, text), ...] per page] of one batch, and with scores [[LineScores, ...] per page] beside it (else None)."""
         self._batch = None
+        if bool(scores) != self._scores:
+            self._check(self._lib.focr_decoder_set_scores(self._h, int(bool(scores))))
+            self._scores = bool(scores)
         self._check(self._lib.focr_decoder_run(self._h, ptr, int(on_device), n, w, h, x, y, width, line_height, line_advance))
         self._batch = (n, h, w)
         self.last_ms = float(self._lib.focr_decoder_last_ms(self._h))
@@ -284,19 +302,28 @@ class LineDecoder:
         lines = (N.DecodedLine * max(1, nl))()
         chars = np.zeros(max(1, nc), dtype=np.uint16)
         self._check(self._lib.focr_decoder_get(self._h, lines, chars.ctypes.data))
+        if scores:
+            cs = np.zeros(max(1, nc), dtype=np.dtype([("score", "<i8"), ("runner_score", "<i8"), ("runner", "<u2"), ("pad", "<u2", 3)]))
+            base = np.zeros(max(1, nl), dtype=np.uint64)
+            self._check(self._lib.focr_decoder_get_scores(self._h, cs.ctypes.data_as(C.POINTER(N.CharScore)), base.ctypes.data))
         alpha = self.font.alphabet
         out = [[] for _ in range(n)]
+        sc = [[] for _ in range(n)] if scores else None
         for k in range(nl):
             ln = lines[k]
             text = "".join(alpha[c] for c in chars[ln.first: ln.first + ln.n_chars])
             out[ln.page].append((int(ln.y), text))
-        return out
+            if scores:
+                c = cs[ln.first: ln.first + ln.n_chars]
+                sc[ln.page].append(LineScores(int(base[k]), c["score"].copy(), c["runner"].copy(), c["runner_score"].copy()))
+        return out, sc
 
-    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None):
+    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
         Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
         mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
-        "image" and None for "mse"; each size group is verified on the device right after its own decode."""
+        "image" and None for "mse"; each size group is verified on the device right after its own decode.  With
+        scores=True the result has one more element at its end: scores[page][line], the LineScores of lines[page][line]."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
@@ -306,6 +333,7 @@ class LineDecoder:
         else:
             pages = list(luma_pages)
         out = [None] * len(pages)
+        sc = [None] * len(pages)
         mse = np.zeros(len(pages), dtype=np.float32)
         images = [None] * len(pages) if verify == "image" else None
         by_size = {}
@@ -313,29 +341,37 @@ class LineDecoder:
             by_size.setdefault(np.asarray(p).shape, []).append(i)
         for (h, w), idx in by_size.items():
             batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
-            res = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo)
-            for i, r in zip(idx, res):
-                out[i] = r
+            res, res_sc = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores)
+            for j, i in enumerate(idx):
+                out[i] = res[j]
+                if scores:
+                    sc[i] = res_sc[j]
             if verify:
                 m, imgs = self._verified(verify, h, w)
                 mse[idx] = m
                 for j, i in enumerate(idx):
                     if images is not None:
                         images[i] = imgs[j]
-        return (out, mse, images) if verify else out
+        res = (out, mse, images) if verify else (out,)
+        if scores:
+            res += (sc,)
+        return res if len(res) > 1 else out
 
-    def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None):
+    def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
-        out = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
-                        int(line_height), int(line_advance))
-        if not verify:
-            return out
-        mse, imgs = self._verified(verify, int(page_h), int(page_w))
-        return out, mse, (list(imgs) if imgs is not None else None)
+        out, sc = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
+                            int(line_height), int(line_advance), scores=scores)
+        res = (out,)
+        if verify:
+            mse, imgs = self._verified(verify, int(page_h), int(page_w))
+            res = (out, mse, (list(imgs) if imgs is not None else None))
+        if scores:
+            res += (sc,)
+        return res if len(res) > 1 else out
 
     def close(self):
         if self._h is not None:

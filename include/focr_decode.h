@@ -141,6 +141,26 @@ float focr_decoder_last_ms(const focr_decoder_t *dec);
 /* Kernel launches of the last run (constant per batch). */
 uint32_t focr_decoder_last_launches(const focr_decoder_t *dec);
 
+/* ---- device: per-character scores of a run (an extension: the reference prints the text only) -------------------- */
+
+/* What the argmin knew about one decoded character.  score is the reference's score of the chosen glyph (score_glyph,
+ * src/main.rs:87-110: the sum over the whole line canvas of (r - c)^2); runner is the alphabet index of the glyph the
+ * argmin would have taken next, the lowest (score, index) among all the others, and runner_score its score.  Glyphs
+ * with identical bitmaps tie: runner_score == score.  A one-glyph alphabet has no runner: 0xFFFF and INT64_MAX. */
+typedef struct focr_char_score {
+    int64_t score, runner_score;
+    uint16_t runner;
+    uint16_t pad[3];
+} focr_char_score_t;
+
+/* Switch the scores of later runs on or off (off when the decoder is created; a state of the decoder, not of the
+ * font).  With scores on a run takes the same launches and returns the same lines, verify and test images. */
+int focr_decoder_set_scores(focr_decoder_t *dec, int on);
+/* The scores of the last run, in the order of focr_decoder_get: scores[n_chars], and line_base[n_lines], each line's sum
+ * of r^2 over its crop (the part of a score every candidate shares: score - line_base is the footprint term the
+ * device compares).  Either may be NULL.  Fails with a message unless the last successful run had scores on. */
+int focr_decoder_get_scores(const focr_decoder_t *dec, focr_char_score_t *scores, uint64_t *line_base);
+
 /* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
 
 /* Upload the verify table of the current decode font (the decoder keeps its own copy).  Refused unless it matches the

@@ -10,6 +10,12 @@ With --verify, also focr --verify's images of the batch on the device (focr_deco
   verify_device_ms_per_batch  median device time of the verify's kernels
   verify_launches             their launch count
   verify_wall_ms              median host time of one verify call with the images read back to the host
+With --scores, also the decode with per-character scores on (LineDecoder.decode(scores=True)), in runs that alternate with
+plain ones so that both see the same clocks:
+  scores_device_ms_per_batch  median device time of the batch's kernels with scores on (the same 3 launches)
+  scores_plain_device_ms      median device time of the plain runs in between
+  scores_over_plain           the ratio of the two
+  scores_wall_ms_per_batch    median host time of one decode(scores=True) call (more to read back and to unpack)
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -59,6 +65,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--verify", action="store_true", help="also time the device verify of the batch")
     ap.add_argument("--test-images", action="store_true", help="also time focr --test's images of the batch")
+    ap.add_argument("--scores", action="store_true", help="also time the decode with per-character scores on")
     a = ap.parse_args()
     pages = synth(a.pages, a.seed)
     geo = (45, 39, 608, 12, 15)
@@ -86,6 +93,18 @@ def main():
                 vwall.append((time.perf_counter() - t) * 1e3)
                 vdev.append(dec.last_verify_ms)
             vlaunches = int(dec._lib.focr_decoder_last_verify_launches(dec._h))
+        if a.scores:
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, scores=True)
+            sdev, swall, pdev = [], [], []
+            for _ in range(a.steps):
+                dec.decode(pages, *geo)
+                pdev.append(dec.last_ms)
+                t = time.perf_counter()
+                dec.decode(pages, *geo, scores=True)
+                swall.append((time.perf_counter() - t) * 1e3)
+                sdev.append(dec.last_ms)
+            slaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
         if a.test_images:
             for _ in range(a.warmup):
                 dec.test_images(pages, *geo)
@@ -110,6 +129,11 @@ def main():
     if a.verify:
         res.update({"verify_device_ms_per_batch": round(float(np.median(vdev)), 4), "verify_launches": vlaunches,
                     "verify_wall_ms": round(float(np.median(vwall)), 3)})
+    if a.scores:
+        sms, pms = float(np.median(sdev)), float(np.median(pdev))
+        res.update({"scores_device_ms_per_batch": round(sms, 4), "scores_device_ms_min": round(float(min(sdev)), 4),
+                    "scores_plain_device_ms": round(pms, 4), "scores_over_plain": round(sms / pms, 4), "scores_launches": slaunches,
+                    "scores_wall_ms_per_batch": round(float(np.median(swall)), 3)})
     if a.test_images:
         tms = float(np.median(tdev))
         res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
