@@ -115,6 +115,8 @@ HIP_SYMBOLS = {
     "focr_lines_device_chars": (C.c_void_p, [C.c_void_p]),
     "focr_verify_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "focr_last_verify_images": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "focr_get_runners": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "focr_last_runners": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "focr_last_timings": (C.c_int, [C.c_void_p, C.c_void_p]),
     "focr_last_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
     "focr_sync": (C.c_int, [C.c_void_p]),

@@ -9,7 +9,9 @@
 //     scan and without the 1024 cap (FOCR_SCAN_RUST; src/ncc.rs:320-330, 406-483);
 //   * a page without any hit prints nothing (the reference panics in partition_by, src/ncc.rs:1040);
 //   * --verify DIR (extension) writes, per input image, the device's verify image (focr_verify_images: the page in red, the
-//     decoded characters' templates in blue) as DIR/<file stem>.png and prints "<image> <mse>" on stderr, as `focr --verify` does.
+//     decoded characters' templates in blue) as DIR/<file stem>.png and prints "<image> <mse>" on stderr, as `focr --verify` does;
+//   * --scores PATH (extension) writes a CSV row per output character: the character, the size of its overlap group and the best
+//     hit of another letter in it (focr_get_runners), as `focr --scores` does for the line decoder.  stdout is unchanged.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -54,6 +56,8 @@ struct Args {
     bool spaces = false;  // extension: fill gaps between characters with blanks (the reference does not, README.md:46)
     std::string verify;   // extension: directory for the verify images (focr_verify_images), as `focr --verify`
     bool have_verify = false;
+    std::string scores;   // extension: CSV of per-character scores and runner-ups (focr_get_runners), as `focr --scores`
+    bool have_scores = false;
 };
 
 [[noreturn]] void usage_error(const std::string &msg) {
@@ -84,6 +88,7 @@ void print_help() {
          "      --spaces                               [extension] print blanks for gaps of whole advances\n"
          "      --allow-wide                           [extension] accept templates 17..32 px wide\n"
          "      --verify <VERIFY>                      [extension] Dir for verify images. Red is the page, Blue the decoded characters\n"
+         "      --scores <SCORES>                      [extension] CSV of every character's similarity, overlap group size and runner-up\n"
          "  -h, --help                                 Print help\n"
          "  -V, --version                              Print version");
 }
@@ -154,6 +159,7 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--spaces") a.spaces = true;
         else if (k == "--allow-wide") a.allow_wide = true;
         else if (k == "--verify") a.verify = need(), a.have_verify = true;
+        else if (k == "--scores") a.scores = need(), a.have_scores = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -168,6 +174,10 @@ Args parse_args(int argc, char **argv) {
         if (a.raw) usage_error("the argument '--verify <VERIFY>' cannot be used with '--raw' (no characters are decoded in that mode)");
         struct stat st;
         if (stat(a.verify.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) usage_error("--verify should be a dir: '" + a.verify + "'");
+    }
+    if (a.have_scores) {  // as --verify: refused before the bank is rasterised or a device is touched
+        if (a.raw) usage_error("the argument '--scores <SCORES>' cannot be used with '--raw' (no characters are decoded in that mode)");
+        if (a.scores.empty()) usage_error("a value is required for '--scores <SCORES>' but none was supplied");
     }
     return a;
 }
@@ -215,6 +225,20 @@ std::string verify_path(const std::string &dir, const std::string &img) {  // DI
     const size_t dot = name.find_last_of('.');
     if (dot != std::string::npos && dot != 0) name = name.substr(0, dot);
     return dir + (dir.empty() || dir.back() == '/' ? "" : "/") + name + ".png";
+}
+
+// --scores: one row per output character.  Floats as %.9g (a float32 reads back exactly); margin in double; no runner: four empty fields.
+const char *SCORES_HEADER = "image_index,line,column,codepoint,x,y,similarity,members,runner_codepoint,runner_x,runner_similarity,margin\n";
+void scores_row(std::string &out, size_t image, size_t line, size_t column, const focr_hit_t &c, const focr_runner_t &r) {
+    char row[256];
+    int n = snprintf(row, sizeof row, "%zu,%zu,%zu,%u,%u,%u,%.9g,%u,", image, line, column, c.letter, c.x, c.y, (double)c.similarity, r.members);
+    out.append(row, (size_t)n);
+    if (r.template_index == FOCR_NO_RUNNER) {
+        out += ",,,\n";  // runner_codepoint, runner_x, runner_similarity, margin: empty
+        return;
+    }
+    n = snprintf(row, sizeof row, "%u,%u,%.9g,%.9g\n", r.letter, r.x, (double)r.similarity, (double)c.similarity - (double)r.similarity);
+    out.append(row, (size_t)n);
 }
 
 [[noreturn]] void die(const std::string &msg) {
@@ -290,6 +314,11 @@ int main(int argc, char **argv) {
         }
     }
     if (args.img.empty()) return 0;
+    FILE *scores_file = nullptr;
+    if (args.have_scores) {
+        if (!(scores_file = fopen(args.scores.c_str(), "w"))) die("cannot write " + args.scores);
+        fputs(SCORES_HEADER, scores_file);
+    }
 
     // Pipeline (the reference's page parallelism, src/ncc.rs:839-847, on the GPU's terms):
     //   1. all host cores read the image headers, then the batch plan is fixed: consecutive pages of one size, at most
@@ -548,6 +577,18 @@ int main(int argc, char **argv) {
             }
             cv.notify_all();
         }
+        if (scores_file) {  // the batch's runner-ups, where --verify reads its images: the waited context, before the release
+            focr_ctx_t *ctx = nullptr;
+            if (focr_fleet_wait(fleet, tickets[b], &ctx) != FOCR_OK) fatal(std::string("scan: ") + focr_last_error_global());
+            std::vector<focr_runner_t> runners(R.n_chars);
+            if (focr_get_runners(ctx, runners.data()) != FOCR_OK) fatal(std::string("focr_get_runners: ") + focr_last_error(ctx));
+            std::string rows;
+            for (size_t k = 0; k < B.n; k++)  // batches retire in input order, so the file is in input order whatever the device count
+                for (uint64_t l = page_off[k]; l < page_off[k + 1]; l++)
+                    for (uint64_t q = line_off[l]; q < line_off[l + 1]; q++)
+                        scores_row(rows, B.p0 + k, (size_t)(l - page_off[k]), (size_t)(q - line_off[l]), chars[q], runners[q]);
+            if (fwrite(rows.data(), 1, rows.size(), scores_file) != rows.size()) fatal("cannot write " + args.scores);
+        }
         ms_results += since(t0);
         t0 = now();
         for (size_t k = 0; k < B.n; k++) {  // output, src/ncc.rs:849-877
@@ -667,6 +708,7 @@ int main(int argc, char **argv) {
         }
     }
     stop_pool();
+    if (scores_file && fclose(scores_file) != 0) die("cannot write " + args.scores);
     if (args.verbose) {
         std::vector<std::pair<uint64_t, uint32_t>> by;  // src/ncc.rs:711-718: (count, char) ascending, zero counts skipped
         for (size_t a = 0; a < alphabet.size(); a++)

@@ -317,6 +317,13 @@ struct focr_ctx {
     float vimg_ms = 0.f;
     uint32_t vimg_launches = 0;
 
+    // focr_get_runners (post.hip): one record per character of the last process_hits, written by the first call after it
+    focr::DevArray<focr_runner_t> post_runners;  // post_chars' bound, Grow::quarter; used on io_stream only, idle between two calls
+    bool runners_valid = false;                  // the records belong to the last focr_process_hits
+    hipEvent_t run_ev[2] = {};
+    float run_ms = 0.f;
+    uint32_t run_launches = 0;
+
     template <typename T>
     bool scratch(focr::DevArray<T> &a, size_t want) {  // grow-only scratch: Grow::quarter, behind the context's stream
         return a.reserve(want, focr::Grow::quarter, &stream) == hipSuccess;

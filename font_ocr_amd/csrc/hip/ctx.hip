@@ -198,6 +198,7 @@ int focr_ctx_create(int device, focr_ctx_t **out) {
         }
         for (auto &ev : c->ev) FOCR_HIP(c, hipEventCreate(&ev));
         for (auto &ev : c->vimg_ev) FOCR_HIP(c, hipEventCreate(&ev));
+        for (auto &ev : c->run_ev) FOCR_HIP(c, hipEventCreate(&ev));
         FOCR_HIP(c, c->d_counter.reserve(COUNTER_BYTES / sizeof(uint32_t), Grow::exact, nullptr));
         FOCR_HIP(c, hipMemsetAsync(c->d_counter, 0, COUNTER_BYTES, c->stream));
         FOCR_HIP(c, c->d_res.reserve(8, Grow::exact, nullptr));
@@ -226,6 +227,8 @@ void focr_ctx_destroy(focr_ctx_t *c) {
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->vimg_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : c->run_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->launch_events)
         if (ev) (void)hipEventDestroy(ev);

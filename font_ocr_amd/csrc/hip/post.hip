@@ -54,11 +54,59 @@ __device__ __forceinline__ uint32_t wave_umax(uint32_t v) {
 // of the lanes that reach it — the highest such lane is the LAST maximum, which is what max_by keeps (:761-764).
 // Outputs: choice[b + k] = winning element of the row's k-th group, row_groups[row] = 1<<32 | number of groups.
 constexpr uint32_t WALK_ROWS = 16;  // (page, row) entries per wave
-__global__ __launch_bounds__(256) void walk_lines(const uint64_t *__restrict__ keys, const float *__restrict__ sims,
-                                                  const uint8_t *__restrict__ keep, KeyFmt fmt, uint32_t n_rows_total,
-                                                  int32_t overlap, const uint8_t *__restrict__ keep_row,
-                                                  const uint32_t *__restrict__ line_b, const uint32_t *__restrict__ line_e,
-                                                  uint32_t *__restrict__ choice, uint64_t *__restrict__ row_groups) {
+
+// focr_get_runners' second walk (walk_runners below): what the walk carries per open group on top of the winner.  A Top is one
+// member: its total_cmp order, its element index in the row and its letter, and what its record needs (template and x: a group's
+// close then stores without loading anything); `has` says that there is one at all, because order 0 is a legal similarity (the
+// negative NaN with every payload bit set).
+struct Top {
+    uint32_t ord, idx, letter, t, x;
+    bool has;
+};
+// b takes a's place as the LAST maximum: a higher order, or the same order further on in (x, t)
+__device__ __forceinline__ bool top_beats(const Top &a, const Top &b) { return b.has && (!a.has || b.ord > a.ord || (b.ord == a.ord && b.idx > a.idx)); }
+struct RunnerArgs {  // RUNNERS only
+    const uint32_t *t_letter;  // by global template index
+    const uint64_t *scanned;   // the row scan of process_hits: low word = the row's first character
+    focr_runner_t *out;
+    uint32_t bound;            // records `out` has room for
+};
+__device__ __forceinline__ void store_runner(const RunnerArgs &ra, uint32_t slot, uint32_t members, const Top &second) {
+    if (slot >= ra.bound) return;
+    focr_runner_t r;
+    r.members = members;
+    r.letter = r.template_index = FOCR_NO_RUNNER;
+    r.similarity = -__builtin_inff();
+    r.x = r.reserved = 0;
+    if (second.has) {
+        r.letter = second.letter;
+        r.template_index = second.t;
+        // total_key is its own inverse (the sign bit selects the mask and stays): the similarity's bits as they were, so that a
+        // NaN or -inf runner is told from "none" by template_index alone
+        r.similarity = __int_as_float(total_key(__int_as_float((int32_t)(second.ord ^ 0x80000000u))));
+        r.x = (uint16_t)second.x;
+    }
+    ra.out[slot] = r;
+}
+
+// The walk of both kernels.  RUNNERS = false is walk_lines as it always was (same instruction stream: DESIGN.md 4c); RUNNERS = true
+// walks the rows again after process_hits and writes no choice / row_groups but one focr_runner_t per group, at the slot emit_chars
+// gave the group's character: the group's size and the last maximum among its members of ANOTHER letter than the winner's.
+// Per open group it carries a top-2 over distinct letters (best, second = the best member whose letter differs from best's); a
+// chunk gives (m1, m2) the same way, and the merge is exact because whatever a side left out as "same letter as its best" is
+// dominated by that best: second' = the last maximum of {loser of best / m1, second, m2} whose letter differs from best'.
+struct NoArgs {};
+__device__ __forceinline__ NoArgs runner_args() { return {}; }
+__device__ __forceinline__ const RunnerArgs &runner_args(const RunnerArgs &ra) { return ra; }
+template <bool RUNNERS, typename... Extra>  // Extra: RunnerArgs if RUNNERS, else nothing, so that walk_lines keeps its kernel arguments
+__global__ __launch_bounds__(256) void walk_kernel(const uint64_t *__restrict__ keys, const float *__restrict__ sims,
+                                                   const uint8_t *__restrict__ keep, KeyFmt fmt, uint32_t n_rows_total,
+                                                   int32_t overlap, const uint8_t *__restrict__ keep_row,
+                                                   const uint32_t *__restrict__ line_b, const uint32_t *__restrict__ line_e,
+                                                   uint32_t *__restrict__ choice, uint64_t *__restrict__ row_groups,
+                                                   const Extra... extra) {
+    static_assert(sizeof...(Extra) == (RUNNERS ? 1 : 0), "walk_runners takes one RunnerArgs, walk_lines nothing");
+    [[maybe_unused]] const auto ra = runner_args(extra...);
     // A wave looks at WALK_ROWS consecutive (page, row) entries at once and walks the anchored ones among them (one text line in
     // fifteen rows at BASELINE configs[1]): one wave per ROW meant 92 160 waves per batch of which 6 000 had work — 77 us alone and
     // 0.33 ms in flight for a few microseconds of arithmetic.
@@ -77,11 +125,19 @@ __global__ __launch_bounds__(256) void walk_lines(const uint64_t *__restrict__ k
     bool open = false;            // a group is open (carried across chunks)
     int32_t anchor = 0;           // x of the open group's first element
     uint32_t best_ord = 0, best_idx = 0;  // winner so far of the open group: total_cmp order, element index
+    Top a1{}, a2{};               // RUNNERS: the open group's best and the best of another letter
+    uint32_t members = 0, slot0 = 0;
+    if constexpr (RUNNERS) slot0 = (uint32_t)ra.scanned[wave];
     for (uint64_t base = b; base < e; base += 64) {
         const uint64_t i = base + lane;
         const bool valid = i < e && keep[i];
         const int32_t x = valid ? (int32_t)fmt.x(keys[i]) : 0x7fffffff;
         const uint32_t ord = valid ? ((uint32_t)total_key(sims[i]) ^ 0x80000000u) : 0u;  // unsigned order of total_cmp
+        uint32_t let = 0, tt = 0;
+        if constexpr (RUNNERS) {
+            tt = valid ? fmt.t(keys[i]) : 0u;
+            let = valid ? ra.t_letter[tt] : 0u;
+        }
         const uint64_t vmask = __builtin_amdgcn_ballot_w64(valid);
         uint32_t pos = 0;  // wave-uniform cursor inside the chunk
         int32_t opened_at = -1;  // lane of the element that opened the open group in this chunk; -1: the group was carried in
@@ -99,6 +155,7 @@ __global__ __launch_bounds__(256) void walk_lines(const uint64_t *__restrict__ k
                 best_ord = 0;
                 best_idx = 0;
                 open = true;
+                if constexpr (RUNNERS) a1.has = a2.has = false, members = 0;
             }
             // kept members of the open group at/after pos; the first kept non-member closes it.  With overlap < 0 nothing but
             // the opener is a member: every kept hit of an anchored row is a character of its own.
@@ -113,8 +170,35 @@ __global__ __launch_bounds__(256) void walk_lines(const uint64_t *__restrict__ k
                 best_ord = mx;
                 best_idx = (uint32_t)(base - b) + (63u - (uint32_t)__builtin_clzll(top));
             }
+            if constexpr (RUNNERS) {
+                members += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(member));
+                if (top) {  // the chunk's part of the group: m1 its last maximum, m2 the last maximum of another letter
+                    const int l1 = 63 - (int)__builtin_clzll(top);
+                    const Top m1{mx, (uint32_t)(base - b) + (uint32_t)l1, (uint32_t)__builtin_amdgcn_readlane((int)let, l1),
+                                 (uint32_t)__builtin_amdgcn_readlane((int)tt, l1), (uint32_t)__builtin_amdgcn_readlane(x, l1), true};
+                    Top m2{};
+                    const bool other = member && let != m1.letter;
+                    if (__builtin_amdgcn_ballot_w64(other)) {
+                        const uint32_t mx2 = wave_umax(other ? ord : 0u);
+                        const int l2 = 63 - (int)__builtin_clzll(__builtin_amdgcn_ballot_w64(other && ord == mx2));
+                        m2 = Top{mx2, (uint32_t)(base - b) + (uint32_t)l2, (uint32_t)__builtin_amdgcn_readlane((int)let, l2),
+                                 (uint32_t)__builtin_amdgcn_readlane((int)tt, l2), (uint32_t)__builtin_amdgcn_readlane(x, l2), true};
+                    }
+                    Top lose = m1;
+                    if (!a1.has || m1.ord >= a1.ord) lose = a1, a1 = m1;  // later elements win ties, as best_ord / best_idx
+                    Top s{};
+                    if (lose.has && lose.letter != a1.letter) s = lose;
+                    if (a2.has && a2.letter != a1.letter && top_beats(s, a2)) s = a2;
+                    if (m2.has && m2.letter != a1.letter && top_beats(s, m2)) s = m2;
+                    a2 = s;
+                }
+            }
             if (stop < 64) {  // the group closes inside this chunk
-                if (lane == 0) choice[b + groups] = (uint32_t)b + best_idx;
+                if constexpr (RUNNERS) {
+                    if (lane == 0) store_runner(ra, slot0 + groups, members, a2);
+                } else {
+                    if (lane == 0) choice[b + groups] = (uint32_t)b + best_idx;
+                }
                 groups++;
                 open = false;
             }
@@ -122,12 +206,20 @@ __global__ __launch_bounds__(256) void walk_lines(const uint64_t *__restrict__ k
         }
     }
     if (open) {  // the row ends with a group still open
-        if (lane == 0) choice[b + groups] = (uint32_t)b + best_idx;
+        if constexpr (RUNNERS) {
+            if (lane == 0) store_runner(ra, slot0 + groups, members, a2);
+        } else {
+            if (lane == 0) choice[b + groups] = (uint32_t)b + best_idx;
+        }
         groups++;
     }
-    if (lane == 0) row_groups[wave] = ((uint64_t)1 << 32) | groups;
+    if constexpr (!RUNNERS)
+        if (lane == 0) row_groups[wave] = ((uint64_t)1 << 32) | groups;
     }  // anchored rows of this wave
 }
+
+constexpr auto walk_lines = walk_kernel<false>;    // process_hits' walk
+constexpr auto walk_runners = walk_kernel<true, RunnerArgs>;   // focr_get_runners' walk over what process_hits left resident
 
 // one thread per hit slot: slot i of a row is the row's (i - line_b)-th output character if the row has that many groups
 __global__ void emit_chars(const uint64_t *__restrict__ keys, const float *__restrict__ sims, const uint64_t *__restrict__ n_p, uint64_t ub, KeyFmt fmt, uint32_t r_h,
@@ -198,6 +290,7 @@ int focr_process_hits(focr_ctx_t *c, float anchor_threshold, int32_t overlap) {
     FOCR_HIP(c, hipSetDevice(c->device));
     c->processed = false;
     c->lines_on_host = false;
+    c->runners_valid = false;
     c->post_anchor = anchor_threshold;
     c->post_overlap = overlap;
     c->n_chars = c->n_lines = 0;
@@ -312,6 +405,49 @@ const focr_hit_t *focr_lines_device_chars(focr_ctx_t *c) {
     return (c && c->processed && finish_results(c) == FOCR_OK && c->n_chars) ? (const focr_hit_t *)c->post_chars.p : nullptr;
 }
 
+// The walk once more over what focr_process_hits left in place (nothing between it and the context's next scan writes any of it:
+// the lazy match lists read the hits and write d_matches, focr_verify_images reads post_chars and writes its own buffers, the
+// getters copy): one launch on the stream finished results are read on, its counts taken from device memory.
+int focr_get_runners(focr_ctx_t *c, focr_runner_t *out) {
+    if (!c) return FOCR_ERR_INVALID;
+    c->run_ms = 0.f;
+    c->run_launches = 0;
+    if (!c->scanned || !c->processed) return fail(c, FOCR_ERR_STATE, "focr_get_runners: call focr_process_hits first (after the last scan)");
+    if (int rc = finish_results(c)) return rc;  // the batch's own event inside an executor; a redo on exact sizes runs process_hits again
+    const size_t n_chars = c->n_chars;
+    if (!n_chars) return FOCR_OK;  // process_hits may not have run a kernel at all (no hits): its tables are not read
+    if (!out) return fail(c, FOCR_ERR_INVALID, "focr_get_runners: no output buffer");
+    FOCR_HIP(c, hipSetDevice(c->device));
+    const hipStream_t s = c->io_stream;
+    if (!c->runners_valid) {
+        const size_t bound = c->ub_hits + 1, n_rows_total = c->n_pages * c->pages.r_h;  // characters <= hits, as post_chars
+        if (bound >= 0xffffffffull) return fail(c, FOCR_ERR_OVERFLOW, "focr_get_runners: more than 2^32 hits in one batch");
+        if (c->post_runners.reserve(bound, Grow::quarter, nullptr) != hipSuccess) return fail(c, FOCR_ERR_NOMEM, "focr_get_runners: hipMalloc failed");
+        FOCR_HIP(c, hipEventRecord(c->run_ev[0], s));
+        hipLaunchKernelGGL(walk_runners, dim3((unsigned)(((n_rows_total + WALK_ROWS - 1) / WALK_ROWS * 64 + 255) / 256)), dim3(256), 0, s, (const uint64_t *)c->d_hkeys,
+                           (const float *)c->d_hsims, (const uint8_t *)c->ord_keep.p, c->fmt, (uint32_t)n_rows_total, c->post_overlap, (const uint8_t *)c->post_keep.p,
+                           (const uint32_t *)c->post_line_be.p, (const uint32_t *)c->post_line_be.p + n_rows_total, (uint32_t *)nullptr, (uint64_t *)nullptr,
+                           RunnerArgs{c->bank.d_t_letter.p, c->post_scanned.p, c->post_runners.p, (uint32_t)bound});
+        FOCR_HIP(c, hipGetLastError());
+        FOCR_HIP(c, hipEventRecord(c->run_ev[1], s));
+    }
+    FOCR_HIP(c, hipMemcpyAsync(out, c->post_runners.p, n_chars * sizeof(focr_runner_t), hipMemcpyDeviceToHost, s));
+    FOCR_HIP(c, hipStreamSynchronize(s));
+    if (!c->runners_valid) {
+        FOCR_HIP(c, hipEventElapsedTime(&c->run_ms, c->run_ev[0], c->run_ev[1]));
+        c->run_launches = 1;
+        c->runners_valid = true;
+    }
+    return FOCR_OK;
+}
+
+int focr_last_runners(focr_ctx_t *c, float *ms, uint32_t *launches) {
+    if (!c) return FOCR_ERR_INVALID;
+    if (ms) *ms = c->run_ms;
+    if (launches) *launches = c->run_launches;
+    return FOCR_OK;
+}
+
 // Test hook: the caller's hits where a scan leaves them for focr_process_hits — keys packed with the batch's KeyFmt, similarities
 // and keep flags in the buffers a split scan installs (scan_split, ctx.hip), the count on the device in d_res[7].
 int focr_debug_process_hits(focr_ctx_t *c, const uint32_t *page, const uint32_t *y, const uint32_t *x, const uint32_t *t,
@@ -358,7 +494,7 @@ int focr_debug_process_hits(focr_ctx_t *c, const uint32_t *page, const uint32_t 
     c->sub_p0 = 0;
     c->sub_np = c->n_pages;
     c->sizes_pending = c->post_pending = c->estimated = false;
-    c->processed = c->lines_on_host = false;
+    c->processed = c->lines_on_host = c->runners_valid = false;
     c->scanned = c->debug_hits = true;
     c->lazy.pending = false;  // no per-call lists stand behind these hits
     return FOCR_OK;

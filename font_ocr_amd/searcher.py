@@ -16,6 +16,10 @@ from .bank import HIT_DTYPE, MATCH_DTYPE
 MAX_MATCHES = 1024  # src/ncc.rs:31
 SCAN_MFMA, SCAN_DIRECT, SCAN_RUST = 0, 1, 2
 PREFILTER_AUTO, PREFILTER_ONE_STAGE, PREFILTER_LEGACY = 0, 1, 3
+NO_RUNNER = 0xFFFFFFFF  # FOCR_NO_RUNNER
+# focr_runner_t: a character's overlap group (members) and the best hit of another letter in it (NO_RUNNER: there is none)
+RUNNER_DTYPE = np.dtype([("members", "<u4"), ("letter", "<u4"), ("template_index", "<u4"), ("similarity", "<f4"), ("x", "<u2"), ("reserved", "<u2")])
+assert RUNNER_DTYPE.itemsize == 20
 
 
 class FocrError(RuntimeError):
@@ -316,8 +320,9 @@ class Scanner:
             raise ValueError("debug_process_hits: fields of different lengths")
         self._ck(self._lib.focr_debug_process_hits(self._h, *[_ptr(a) for a in cols], _ptr(sims), _ptr(kp), n))
 
-    def lines(self):
-        """-> list over pages of list over lines of HIT_DTYPE arrays."""
+    def lines(self, runners=False):
+        """-> list over pages of list over lines of HIT_DTYPE arrays; runners=True: (lines, runners), the second nested alike
+        with RUNNER_DTYPE arrays (runners())."""
         n_lines = int(self._lib.focr_total_lines(self._h))
         n_chars = int(self._lib.focr_total_chars(self._h))
         page_off = np.zeros(self.n_pages + 1, np.uint64)
@@ -327,6 +332,10 @@ class Scanner:
         out = []
         for p in range(self.n_pages):
             out.append([chars[int(line_off[k]): int(line_off[k + 1])] for k in range(int(page_off[p]), int(page_off[p + 1]))])
+        if runners:
+            r = self.runners()
+            return out, [[r[int(line_off[k]): int(line_off[k + 1])] for k in range(int(page_off[p]), int(page_off[p + 1]))]
+                         for p in range(self.n_pages)]
         return out
 
     def lines_flat(self):
@@ -335,6 +344,29 @@ class Scanner:
         chars = np.zeros(n_chars, HIT_DTYPE)
         self._ck(self._lib.focr_get_lines(self._h, None, None, _ptr(chars)))
         return chars
+
+    def runners(self):
+        """focr_get_runners: one RUNNER_DTYPE record per character of the last process_hits(), aligned with lines_flat(): the size
+        of the character's overlap group (`members`) and the group's best hit of ANOTHER letter than the winner's (the last maximum
+        by f32::total_cmp; other shifts of the winner's glyph never count): its letter, template_index, similarity and x.  No such
+        hit: letter = template_index = NO_RUNNER, similarity = -inf, x = 0.  Computed on the device at the first call after a
+        process_hits() (one launch; later calls only copy).  Works the same on the Scanner that Pipeline.wait / Fleet.wait return,
+        until the ticket's release.
+
+            sc.scan(0.8); sc.process_hits(0.95, 5)
+            c, r = sc.lines_flat(), sc.runners()
+            has = r["template_index"] != NO_RUNNER
+            doubt = np.flatnonzero(has & (c["similarity"] - r["similarity"] < 0.01))   # characters that won narrowly
+        """
+        out = np.zeros(int(self._lib.focr_total_chars(self._h)), RUNNER_DTYPE)
+        self._ck(self._lib.focr_get_runners(self._h, _ptr(out) if len(out) else None))
+        return out
+
+    def last_runners(self):
+        """focr_last_runners: {'ms': device time of the last runners()' kernel, 'launches': 1 if it computed the records, 0 if it only copied}."""
+        ms, n = C.c_float(), C.c_uint32()
+        self._ck(self._lib.focr_last_runners(self._h, C.byref(ms), C.byref(n)))
+        return {"ms": float(ms.value), "launches": int(n.value)}
 
     def device_chars(self):
         """(device pointer, count) of the post-processed characters still resident in HBM (HIT_DTYPE records)."""

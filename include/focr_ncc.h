@@ -236,6 +236,38 @@ int focr_verify_images(focr_ctx_t *ctx, uint8_t *rgb, int rgb_on_device, uint64_
  * (0 and 0 after one that failed); either pointer may be NULL. */
 int focr_last_verify_images(focr_ctx_t *ctx, float *ms, uint32_t *launches);
 
+/* Runner-ups: for every character of the last focr_process_hits, the size of its overlap group and the best competing hit of
+ * ANOTHER letter inside it -- what says "this l beat a 1 by 0.003".  Exact definitions (everything compares with ==):
+ *   group    the kept hits of the character's anchored row that the reference's partition_by puts together: anchored on its
+ *            first element, which is always a member; hits cut off by their call's cap are neither members nor runners
+ *   members  the number of hits in the group (the winner included)
+ *   runner   what max_by(f32::total_cmp) returns over the members whose bank letter differs from the winner's: the LAST
+ *            maximum in (x, template) order.  Other shifts of the winner's own glyph are never the runner, and the runner need
+ *            not be the group's second-best hit.  letter / template_index / similarity / x are that hit's; its y is the
+ *            character's.  The similarity's bits are returned verbatim (a NaN or -inf included)
+ *   none     no member of another letter: template_index = letter = FOCR_NO_RUNNER, similarity = -inf, x = 0.  Only
+ *            template_index / letter tell "none" from a real runner whose similarity is -inf.
+ * out: focr_total_chars() records in host memory, entry i belonging to entry i of focr_get_lines' chars.  Computed on demand, on
+ * the device, from what focr_process_hits leaves resident until the context's next scan (the ordered hits and their keep flags,
+ * the anchored rows and their extents, the row scan, the bank's letters): one kernel launch at the first call after a
+ * focr_process_hits, on the stream finished results are read on and behind the batch's own event inside an executor; further
+ * calls copy the records again without a launch.  A batch that never asks pays nothing: focr_process_hits launches what it
+ * always did.  FOCR_ERR_STATE unless a focr_process_hits has completed on this context since its last scan; a new
+ * focr_process_hits replaces the records.  Valid after a plain scan, a scan on size estimates (its redo included), a split-batch
+ * scan and focr_debug_process_hits, and on the context focr_pipe_wait / focr_fleet_wait hand out, until that ticket's release.
+ * Zero characters: FOCR_OK, nothing written (out may be NULL).  (Python: Scanner.runners(), Scanner.lines(runners=True).) */
+#define FOCR_NO_RUNNER 0xffffffffu
+typedef struct focr_runner {
+    uint32_t members;
+    uint32_t letter, template_index;
+    float similarity;
+    uint16_t x, reserved; /* reserved = 0 */
+} focr_runner_t;          /* 20 bytes */
+int focr_get_runners(focr_ctx_t *ctx, focr_runner_t *out);
+/* Device time (ms, HIP events around the kernel) and number of launches of the context's last focr_get_runners: 1 launch for
+ * the call that computed the records, 0 and 0 ms for one that only copied them or had no characters; either pointer may be NULL. */
+int focr_last_runners(focr_ctx_t *ctx, float *ms, uint32_t *launches);
+
 /* Device time (ms, HIP events on the context's stream) of the phases of the
  * last focr_scan / focr_process_hits: [0] window statistics, [1] scan kernel
  * (MFMA prefilter or direct), [2] exact verify, [3] ordering + cap,
