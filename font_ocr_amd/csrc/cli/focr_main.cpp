@@ -11,7 +11,10 @@
 //     refusals apply (kerning <= 0, a glyph that does not advance; the reference's --test decodes nothing), line_advance 0
 //     is refused, and its blend is image's Blend for Rgba<u8> restated in f32 (parity unpinned);
 //   * --scores PATH is an extension: a CSV row per decoded character with its score, the runner-up and the margin between
-//     them (focr_decoder_get_scores); stdout and the --verify files are the same with and without it.
+//     them (focr_decoder_get_scores); stdout and the --verify files are the same with and without it;
+//   * --pen-search N is an extension: every step also searches the pen offsets -N ..= N (in 1/64 px, at most 64) and
+//     carries the chosen one forward (focr_decoder_set_pen_search); stdout stays text only, the --verify files and MSEs
+//     come from the searched positions, and --scores gains a trailing pen_offset column.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -41,7 +44,7 @@ struct Args {
     std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores;
     bool hinting = false, have_verify = false, have_test = false, have_scores = false;
     float text_size = 0.f, kerning = 1.f;
-    uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0;
+    uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0, pen_search = 0;
     bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
 };
 
@@ -76,6 +79,7 @@ void print_help() {
            "      --test <TEST>                    Prefix for output test images\n"
            "      --verify <VERIFY>                Dir for verify images. Red is reference, Blue is rendered\n"
            "      --scores <SCORES>                [extension] CSV of every decoded character's score, runner-up and margin\n"
+           "      --pen-search <N>                 [extension] Also search pen offsets of up to N/64 px at every step, N <= 64 [default: 0]\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -133,6 +137,11 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--test") a.test = need(), a.have_test = true;
         else if (k == "--verify") a.verify = need(), a.have_verify = true;
         else if (k == "--scores") a.scores = need(), a.have_scores = true;
+        else if (k == "--pen-search") {
+            const std::string s = need();
+            a.pen_search = num_u(s);
+            if (a.pen_search > FOCR_PEN_SEARCH_MAX) usage_error("invalid value '" + s + "' for '--pen-search': the radius is at most 64");
+        }
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -186,6 +195,7 @@ struct Line {
     uint32_t y;
     std::vector<uint32_t> text;  // code points
     std::vector<focr_char_score_t> scores;  // --scores: one per code point
+    std::vector<int8_t> offsets;            // --scores with --pen-search: one per code point
 };
 
 // Writes the batch's verify images (the device's draw_verify, n x H x W x 3 bytes) as PNGs on at most 16 threads, and
@@ -291,6 +301,8 @@ int main(int argc, char **argv) {
         focr_verify_font_free(&vfont);
     }
     if (csv && focr_decoder_set_scores(dec, 1) != 0) die(std::string("focr_decoder_set_scores: ") + focr_decoder_last_error(dec), 1);
+    if (focr_decoder_set_pen_search(dec, args.pen_search) != 0) die(std::string("focr_decoder_set_pen_search: ") + focr_decoder_last_error(dec), 1);
+    const bool csv_offsets = csv && args.pen_search > 0;
 
     std::vector<std::vector<Line>> lines(n_img);
     std::vector<uint8_t> batch, rgb;
@@ -318,10 +330,14 @@ int main(int argc, char **argv) {
             std::vector<focr_char_score_t> ds(csv ? dc.size() : 0);
             if (csv && focr_decoder_get_scores(dec, ds.data(), nullptr) != 0)
                 die(std::string("focr_decoder_get_scores: ") + focr_decoder_last_error(dec), 1);
+            std::vector<int8_t> dj(csv_offsets ? dc.size() : 0);
+            if (csv_offsets && focr_decoder_get_offsets(dec, dj.data()) != 0)
+                die(std::string("focr_decoder_get_offsets: ") + focr_decoder_last_error(dec), 1);
             for (const focr_decoded_line_t &l : dl) {
-                Line out{l.y, {}, {}};
+                Line out{l.y, {}, {}, {}};
                 for (uint32_t c = 0; c < l.n_chars; c++) out.text.push_back(alphabet[dc[l.first + c]]);
                 if (csv) out.scores.assign(ds.begin() + l.first, ds.begin() + l.first + l.n_chars);
+                if (csv_offsets) out.offsets.assign(dj.begin() + l.first, dj.begin() + l.first + l.n_chars);
                 lines[grp.second[b0 + l.page]].push_back(std::move(out));
             }
             if (args.have_verify) {  // draw_verify + red_blue_mse (src/main.rs:300-329, 518-524) on the device
@@ -351,15 +367,17 @@ int main(int argc, char **argv) {
         }
     fwrite(out.data(), 1, out.size(), stdout);
     if (csv) {  // one row per decoded character, in the order of stdout; a one-glyph alphabet has no runner-up and no margin
-        fprintf(csv, "image_index,y,column,codepoint,score,runner_codepoint,runner_score,margin\n");
+        fprintf(csv, "image_index,y,column,codepoint,score,runner_codepoint,runner_score,margin%s\n", csv_offsets ? ",pen_offset" : "");
         for (size_t i = 0; i < n_img; i++)
             for (const Line &l : lines[i])
                 for (size_t c = 0; c < l.text.size(); c++) {
                     const focr_char_score_t &sc = l.scores[c];
                     fprintf(csv, "%zu,%u,%zu,%u,%lld,", i, l.y, c, l.text[c], (long long)sc.score);
                     if (sc.runner < alphabet.size())
-                        fprintf(csv, "%u,%lld,%lld\n", alphabet[sc.runner], (long long)sc.runner_score, (long long)(sc.runner_score - sc.score));
-                    else fprintf(csv, ",%lld,\n", (long long)sc.runner_score);
+                        fprintf(csv, "%u,%lld,%lld", alphabet[sc.runner], (long long)sc.runner_score, (long long)(sc.runner_score - sc.score));
+                    else fprintf(csv, ",%lld,", (long long)sc.runner_score);
+                    if (csv_offsets) fprintf(csv, ",%d", (int)l.offsets[c]);
+                    fputc('\n', csv);
                 }
         if (fclose(csv) != 0) die("cannot write " + args.scores);
     }

@@ -193,17 +193,21 @@ struct focr_decoder {
     focr::DevArray<int32_t> d_term, d_runner_term;
     focr::DevArray<uint16_t> d_runner;
     focr::DevArray<uint64_t> d_base;
+    // pen search (focr_decoder_set_pen_search): the chosen offset of every step beside d_chars; grown by a run with a radius
+    uint32_t pen_search = 0;
+    focr::DevArray<int8_t> d_pen;
     // results of the last run
     std::vector<focr_decoded_line_t> lines;
     std::vector<uint16_t> chars;
     bool have_scores = false;  // the last successful run was made with scores on
     std::vector<focr_char_score_t> char_scores;
     std::vector<uint64_t> line_base;
+    std::vector<int8_t> offsets;  // beside chars: all zero after a run without a search
     // verify: the table, what the last successful run left for it, buffers
     uint32_t n_vglyphs = 0, hmax = 0;
     focr::DevArray<focr_dec::VerifyGlyph> d_vglyphs;
     focr::DevArray<focr_dec::VerifyPhase> d_vphases;
-    bool run_ok = false;
+    bool run_ok = false, run_searched = false;  // run_searched: the last successful run wrote d_pen
     focr_dec::Geometry run_g{};
     size_t run_pages = 0;
     uint32_t run_x_start = 0;

@@ -8,6 +8,8 @@
 //      uniform across the wave; each lane scores its glyphs (lane, lane + 64, ...) against the strip (LDS when it fits)
 //      from the glyph's phase tile, then a wave argmin takes the lowest (score, glyph index).  With scores on
 //      (focr_decoder_set_scores) the same launch also keeps the second lowest key and sums r^2 over the line's crop.
+//      With a pen search radius (focr_decoder_set_pen_search) line_search_kernel takes its place: one workgroup per line,
+//      the argmin over (glyph, pen offset), and the chosen offset of every step beside its glyph.
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
@@ -185,6 +187,148 @@ __global__ __launch_bounds__(64) void line_decode_kernel(const uint8_t *__restri
     if (lane == 0) n_chars[k] = n;
 }
 
+// ---- pen search (focr_decoder_set_pen_search; an extension, see include/focr_decode.h) ------------------------------
+
+constexpr uint32_t SEARCH_THREADS = 256;    // one workgroup of four waves per work-list line
+constexpr uint32_t SEARCH_WAVES = SEARCH_THREADS / 64;
+constexpr uint32_t SEARCH_RED_BYTES = 2 * SEARCH_WAVES * 2 * 8;  // two parities of (best, other) per wave, behind the strip
+
+// A search key: (score, rank of the offset, glyph index), lowest first.  rank(0) = 0, rank(-1) = 1, rank(+1) = 2, ...
+__device__ __forceinline__ uint32_t key_glyph(uint64_t key) { return (uint32_t)key & 0xffffu; }
+__device__ __forceinline__ int rank_offset(uint32_t rank) { return rank & 1 ? -(int)((rank + 1) >> 1) : (int)(rank >> 1); }
+
+// The minimum of two sets of keys, and the minimum of those of their keys whose glyph is not the minimum's.  Each set
+// comes as (best, other): its lowest key, and its lowest key of another glyph than best's (~0: none).  The winner's
+// other already leaves out the winner's glyph; of the loser's set, its best is the lowest of all and counts when its
+// glyph differs, else its other does, which leaves out exactly that glyph.  So the merge is exact in any order.
+__device__ __forceinline__ void merge_other_glyph(uint64_t &best, uint64_t &other, uint64_t b2, uint64_t o2) {
+    const bool keep = best <= b2;
+    const uint64_t win = keep ? best : b2, lose = keep ? b2 : best;
+    const uint64_t o_win = keep ? other : o2, o_lose = keep ? o2 : other;
+    other = std::min(o_win, key_glyph(lose) != key_glyph(win) ? lose : o_lose);  // an empty set's ~0 names no glyph
+    best = win;
+}
+
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// 3s. the pen loop with a search over (glyph, pen offset), one workgroup per work-list line.  The candidates of a step,
+// n_glyphs * (2 * radius + 1) of them, are flattened glyph-major over the 256 lanes (the offsets of one glyph share its
+// box, so neighbouring lanes run the same trip counts); every lane keeps the (best, other-glyph) pair of its own, a wave
+// merges by shuffles, and the four waves meet in LDS: one barrier per step, the pairs double-buffered by the step's
+// parity (a wave that writes step n + 2 has passed the barrier of step n + 1, which every wave reaches only after it
+// has read step n).  Pen, step count and choice are uniform across the workgroup.  radius >= 1.
+template <bool LDS, bool SCORES>
+__global__ __launch_bounds__(SEARCH_THREADS) void line_search_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
+                                                                     const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
+                                                                     const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps,
+                                                                     uint32_t n_glyphs, float origin_x, uint32_t radius, uint32_t *__restrict__ n_chars,
+                                                                     uint16_t *__restrict__ chars, int8_t *__restrict__ pen_offs, ScoreOut so) {
+    extern __shared__ uint32_t lds_search[];  // the reduction pairs, then (LDS) the strip
+    uint64_t *red = (uint64_t *)lds_search;
+    const uint32_t k = blockIdx.x;
+    if (k >= *count) return;
+    const uint32_t slot = work[k];
+    uint32_t yc, h;
+    slot_rows(g, slot % g.n_slots, &yc, &h);
+    const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
+    const uint32_t sdw = g.stride / 4;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (LDS) {
+        uint32_t *lds_strip = lds_search + SEARCH_RED_BYTES / 4;
+        for (uint32_t q = tid; q < sdw * h; q += SEARCH_THREADS) lds_strip[q] = strip[q];
+        __syncthreads();
+        strip = lds_strip;
+    }
+    const int w = (int)g.w;
+    const float fw = (float)g.w;
+    const size_t row = (size_t)k * g.cap;
+    if (SCORES) {  // as in line_decode_kernel: whole rows of the crop
+        uint64_t acc = 0;
+        for (uint32_t q = tid; q < sdw * h; q += SEARCH_THREADS) acc += __builtin_amdgcn_udot4(strip[q], strip[q], 0u, false);
+        acc = wave_sum_u64(acc);
+        if (lane == 0) red[wave] = acc;
+        __syncthreads();
+        if (tid == 0) {
+            uint64_t total = 0;
+            for (uint32_t v = 0; v < SEARCH_WAVES; v++) total += red[v];
+            so.base[k] = total;
+        }
+        __syncthreads();
+    }
+    const uint32_t n_off = 2 * radius + 1, n_cand = n_glyphs * n_off;
+    float pos = 0.f;
+    uint32_t n = 0;
+    while (pos < fw && n < g.cap) {
+        uint64_t best = ~0ull, other = ~0ull;  // other: SCORES only
+        for (uint32_t c = tid; c < n_cand; c += SEARCH_THREADS) {
+            const uint32_t gi = c / n_off, rank = c - gi * n_off;
+            const float t = __fadd_rn(origin_x, __fadd_rn(pos, (float)rank_offset(rank) * 0.015625f));
+            if (t < 0.f) continue;  // left of the line's first delta: no such rendering in the reference
+            const int d = (int)__fmul_rn(t, 64.0f);  // FreeType's delta: trunc(t * 64)
+            const int phase = d & 63, shift = d >> 6;
+            const DevGlyph gl = glyphs[gi];
+            const int2 o = offs[gi * 64 + phase];
+            const int x0 = shift + o.x, y0 = o.y;
+            const uint32_t *tile = bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h;
+            const int r_lo = std::max(0, -y0), r_hi = std::min((int)gl.box_h, (int)h - y0);
+            uint32_t cc = 0, cr = 0;
+            for (int r = r_lo; r < r_hi; r++) {
+                const uint32_t *srow = strip + (size_t)(y0 + r) * sdw;
+                const uint32_t *trow = tile + (size_t)r * gl.ndw;
+                for (uint32_t q = 0; q < gl.ndw; q++) {
+                    const int base = x0 + 4 * (int)q;
+                    if (base <= -4 || base >= w) continue;
+                    uint32_t cv = trow[q];
+                    if (base < 0 || base + 4 > w) cv &= edge_mask(base, w);
+                    const uint32_t a = (uint32_t)(base + (int)PAD);
+                    const uint32_t rv = __builtin_amdgcn_alignbyte(srow[(a >> 2) + 1], srow[a >> 2], a & 3);
+                    cr = __builtin_amdgcn_udot4(cv, rv, cr, false);
+                    cc = __builtin_amdgcn_udot4(cv, cv, cc, false);
+                }
+            }
+            const int score = (int)cc - 2 * (int)cr;
+            const uint64_t key = ((uint64_t)((uint32_t)score ^ 0x80000000u) << 32) | (rank << 16) | gi;
+            if (SCORES) merge_other_glyph(best, other, key, ~0ull);
+            else best = std::min(best, key);
+        }
+        for (int m = 32; m >= 1; m >>= 1) {
+            const uint64_t b2 = shfl_xor_u64(best, m);
+            if (SCORES) merge_other_glyph(best, other, b2, shfl_xor_u64(other, m));
+            else best = std::min(best, b2);
+        }
+        uint64_t *slot_red = red + (n & 1) * 2 * SEARCH_WAVES;
+        if (lane == 0) {
+            slot_red[2 * wave] = best;
+            if (SCORES) slot_red[2 * wave + 1] = other;
+        }
+        __syncthreads();
+        best = slot_red[0];
+        if (SCORES) other = slot_red[1];
+        for (uint32_t v = 1; v < SEARCH_WAVES; v++) {
+            if (SCORES) merge_other_glyph(best, other, slot_red[2 * v], slot_red[2 * v + 1]);
+            else best = std::min(best, slot_red[2 * v]);
+        }
+        if (best == ~0ull) break;  // every candidate dropped (a caller-built font with origin_x < 0): the line ends here; uniform
+        const uint32_t gbest = key_glyph(best);
+        const int j = rank_offset(((uint32_t)best >> 16) & 0xffu);
+        if (tid == 0) {
+            chars[row + n] = (uint16_t)gbest;
+            pen_offs[row + n] = (int8_t)j;
+            if (SCORES) {  // no other glyph (a one-glyph alphabet): the key stays ~0, and the host says so
+                so.term[row + n] = key_term(best);
+                so.runner_term[row + n] = key_term(other);
+                so.runner[row + n] = (uint16_t)key_glyph(other);
+            }
+        }
+        n++;
+        pos = __fadd_rn(__fadd_rn(pos, (float)j * 0.015625f), glyphs[gbest].inc);  // the chosen candidate's pen, then its increment
+    }
+    if (tid == 0) n_chars[k] = n;
+}
+
 }  // namespace focr_dec
 
 using namespace focr_dec;
@@ -192,7 +336,8 @@ using namespace focr_dec;
 namespace {
 
 // What focr_decoder_verify draws from: the successful run's geometry and its pages on the device.
-void remember_run(focr_decoder *dec, const Geometry &g, const uint8_t *d_src, size_t n_pages, uint32_t x_start) {
+void remember_run(focr_decoder *dec, const Geometry &g, const uint8_t *d_src, size_t n_pages, uint32_t x_start, bool searched) {
+    dec->run_searched = searched;
     dec->run_g = g;
     dec->run_pages = n_pages;
     dec->run_x_start = x_start;
@@ -284,10 +429,15 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     dec->have_scores = false;
     dec->char_scores.clear();
     dec->line_base.clear();
+    dec->offsets.clear();
     dec->run.ms = 0.f;
     dec->run.launches = 0;
     if (!dec->n_glyphs) return dfail(dec, "focr_decoder_run: no font (focr_decoder_set_font)");
     if (n_pages && !pages) return dfail(dec, "focr_decoder_run: null pages");
+    const uint32_t radius = dec->pen_search;
+    const float reach = (float)radius * 0.015625f;  // exact
+    if (reach > dec->min_inc * 0.5f)
+        return dfail(dec, "focr_decoder_run: the pen search radius is more than half the smallest pen increment (the pen could crawl)");
     Geometry g{};
     if (batch_geometry(dec, "focr_decoder_run", n_pages, page_w, page_h, x_start, y_start, width, line_height, line_advance, &g)) return 1;
     DEC_CHECK(hipSetDevice(dec->device));
@@ -297,18 +447,22 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     const bool scores = dec->scores_on;
     if (total == 0) {  // nothing to decode and nothing launched; a verify still draws the pages
         DEC_CHECK(hipStreamSynchronize(dec->stream));
-        remember_run(dec, g, d_src, n_pages, x_start);
+        remember_run(dec, g, d_src, n_pages, x_start, radius != 0);
         dec->have_scores = scores;
         return 0;
     }
     g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;
     // characters per line at most: the pen moves at least min_inc per step, and f32 rounding is monotone, so the
-    // sequence 0, min_inc, ... reaches w no earlier than any pen does
+    // sequence 0, min_inc, ... reaches w no earlier than any pen does.  With a pen search a step is two f32 adds,
+    // pen' = (pen + j / 64) + inc with j / 64 >= -reach (exact) and inc >= min_inc; an f32 add is monotone in each
+    // operand, so by induction the sequence q' = (q - reach) + min_inc from 0 stays at or below every pen and reaches w
+    // no earlier.  It does advance: reach <= min_inc / 2 (checked above), so a step gains min_inc / 2 up to rounding,
+    // and one that stalls in f32 runs into the step limit below.  (Dropped candidates only remove choices.)
     {
         float p = 0.f;
         uint32_t steps = 0;
         while (p < (float)g.w) {
-            p = p + dec->min_inc;
+            p = radius ? (p - reach) + dec->min_inc : p + dec->min_inc;
             if (++steps > (1u << 20)) return dfail(dec, "focr_decoder_run: the pen advance is too small for the line width");
         }
         g.cap = std::max<uint32_t>(steps, 1);
@@ -327,17 +481,27 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         DEC_GROW(dec->d_base, total);
     }
     const ScoreOut so{dec->d_term, dec->d_runner_term, dec->d_runner, dec->d_base};  // null arrays with scores off: never touched
+    if (radius) DEC_GROW(dec->d_pen, (size_t)g.cap * total);
 
     DEC_CHECK(hipEventRecord(dec->run.begin, dec->stream));
     line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
     DEC_CHECK(hipGetLastError());
     line_compact_kernel<<<1, COMPACT_THREADS, 0, dec->stream>>>(dec->d_flags, g.total, dec->d_work, dec->d_count);
     DEC_CHECK(hipGetLastError());
-    const auto decode = strip_bytes <= LDS_STRIP_MAX ? (scores ? line_decode_kernel<true, true> : line_decode_kernel<true, false>)
-                                                     : (scores ? line_decode_kernel<false, true> : line_decode_kernel<false, false>);
-    decode<<<g.total, 64, strip_bytes <= LDS_STRIP_MAX ? strip_bytes : 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs,
-                                                                                       dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs, dec->origin_x,
-                                                                                       dec->d_nchars, dec->d_chars, so);
+    if (radius) {  // the strip shares LDS with the reduction pairs, so it stays in LDS up to that much less
+        const bool lds = strip_bytes + SEARCH_RED_BYTES <= LDS_STRIP_MAX;
+        const auto search = lds ? (scores ? line_search_kernel<true, true> : line_search_kernel<true, false>)
+                                : (scores ? line_search_kernel<false, true> : line_search_kernel<false, false>);
+        search<<<g.total, SEARCH_THREADS, SEARCH_RED_BYTES + (lds ? strip_bytes : 0), dec->stream>>>(
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs,
+            dec->origin_x, radius, dec->d_nchars, dec->d_chars, dec->d_pen, so);
+    } else {
+        const auto decode = strip_bytes <= LDS_STRIP_MAX ? (scores ? line_decode_kernel<true, true> : line_decode_kernel<true, false>)
+                                                         : (scores ? line_decode_kernel<false, true> : line_decode_kernel<false, false>);
+        decode<<<g.total, 64, strip_bytes <= LDS_STRIP_MAX ? strip_bytes : 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs,
+                                                                                           dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs,
+                                                                                           dec->origin_x, dec->d_nchars, dec->d_chars, so);
+    }
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->run.end, dec->stream));
 
@@ -348,6 +512,8 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     DEC_CHECK(hipMemcpyAsync(work.data(), dec->d_work, total * 4, hipMemcpyDeviceToHost, dec->stream));
     DEC_CHECK(hipMemcpyAsync(nch.data(), dec->d_nchars, total * 4, hipMemcpyDeviceToHost, dec->stream));
     DEC_CHECK(hipMemcpyAsync(all.data(), dec->d_chars, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
+    std::vector<int8_t> pen(radius ? all.size() : 0);
+    if (radius) DEC_CHECK(hipMemcpyAsync(pen.data(), dec->d_pen, pen.size(), hipMemcpyDeviceToHost, dec->stream));
     std::vector<int32_t> term, runner_term;
     std::vector<uint16_t> runner;
     std::vector<uint64_t> base;
@@ -373,6 +539,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         l.n_chars = n;
         l.pad = 0;
         dec->chars.insert(dec->chars.end(), all.begin() + (size_t)k * g.cap, all.begin() + (size_t)k * g.cap + n);
+        if (radius) dec->offsets.insert(dec->offsets.end(), pen.begin() + (size_t)k * g.cap, pen.begin() + (size_t)k * g.cap + n);
         if (!scores) continue;
         dec->line_base.push_back(base[k]);
         for (size_t at = (size_t)k * g.cap; at < (size_t)k * g.cap + n; at++) {  // the reference's score: sum r^2 plus the footprint term
@@ -381,8 +548,22 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
             dec->char_scores.push_back(c);
         }
     }
-    remember_run(dec, g, d_src, n_pages, x_start);
+    if (!radius) dec->offsets.assign(dec->chars.size(), 0);
+    remember_run(dec, g, d_src, n_pages, x_start, radius != 0);
     dec->have_scores = scores;
+    return 0;
+}
+
+extern "C" int focr_decoder_set_pen_search(focr_decoder_t *dec, uint32_t n) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_pen_search: null decoder");
+    if (n > FOCR_PEN_SEARCH_MAX) return dfail(dec, "focr_decoder_set_pen_search: the radius is at most 64 (one pixel)");
+    dec->pen_search = n;
+    return 0;
+}
+
+extern "C" int focr_decoder_get_offsets(const focr_decoder_t *dec, int8_t *offsets) {
+    if (!dec) return dfail(nullptr, "focr_decoder_get_offsets: null decoder");
+    if (offsets && !dec->offsets.empty()) memcpy(offsets, dec->offsets.data(), dec->offsets.size());
     return 0;
 }
 

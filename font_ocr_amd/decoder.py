@@ -8,6 +8,8 @@
         # focr --verify on the device: red = the page's ink, blue = the decoded text re-rendered; MSE per page
         pages, scores = dec.decode(luma_pages, 45, 39, 608, 12, 15, scores=True)
         # scores[page][line]: what the argmin knew about each character of pages[page][line] (LineScores)
+        pages, offsets = dec.decode(luma_pages, 45, 39, 608, 12, 15, pen_search=8)
+        # a search of 8/64 px around the pen at every step, carried forward; offsets[page][line]: each character's offset
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -177,6 +179,7 @@ class LineDecoder:
         self._vfont = None
         self._batch = None  # (n_pages, page_h, page_w) of the last run
         self._scores = False  # the library's switch (focr_decoder_set_scores)
+        self._pen_search = 0  # the library's radius (focr_decoder_set_pen_search)
 
     def _check(self, rc):
         if rc != 0:
@@ -289,9 +292,13 @@ class LineDecoder:
         mse = sums.astype(np.float32) / np.float32((h * w) & 0xFFFFFFFF)  # red_blue_mse: (sum as f32) / (w * h as u32)
         return mse, imgs
 
-    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False):
-        """[[(y, text), ...] per page] of one batch, and with scores [[LineScores, ...] per page] beside it (else None)."""
+    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0):
+        """[[(y, text), ...] per page] of one batch; with scores [[LineScores, ...] per page] beside it (else None); with
+        a pen search [[int8 offsets, ...] per page] (else None)."""
         self._batch = None
+        if int(pen_search) != self._pen_search:
+            self._check(self._lib.focr_decoder_set_pen_search(self._h, int(pen_search)))
+            self._pen_search = int(pen_search)
         if bool(scores) != self._scores:
             self._check(self._lib.focr_decoder_set_scores(self._h, int(bool(scores))))
             self._scores = bool(scores)
@@ -306,27 +313,44 @@ class LineDecoder:
             cs = np.zeros(max(1, nc), dtype=np.dtype([("score", "<i8"), ("runner_score", "<i8"), ("runner", "<u2"), ("pad", "<u2", 3)]))
             base = np.zeros(max(1, nl), dtype=np.uint64)
             self._check(self._lib.focr_decoder_get_scores(self._h, cs.ctypes.data_as(C.POINTER(N.CharScore)), base.ctypes.data))
+        if pen_search:
+            js = np.zeros(max(1, nc), dtype=np.int8)
+            self._check(self._lib.focr_decoder_get_offsets(self._h, js.ctypes.data))
         alpha = self.font.alphabet
         out = [[] for _ in range(n)]
         sc = [[] for _ in range(n)] if scores else None
+        offs = [[] for _ in range(n)] if pen_search else None
         for k in range(nl):
             ln = lines[k]
             text = "".join(alpha[c] for c in chars[ln.first: ln.first + ln.n_chars])
             out[ln.page].append((int(ln.y), text))
+            if pen_search:
+                offs[ln.page].append(js[ln.first: ln.first + ln.n_chars].copy())
             if scores:
                 c = cs[ln.first: ln.first + ln.n_chars]
                 sc[ln.page].append(LineScores(int(base[k]), c["score"].copy(), c["runner"].copy(), c["runner_score"].copy()))
-        return out, sc
+        return out, sc, offs
 
-    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False):
+    @staticmethod
+    def _check_pen_search(pen_search):
+        if not 0 <= int(pen_search) <= 64:
+            raise ValueError(f"pen_search must be 0 .. 64 (1/64 px), not {pen_search!r}")
+        return int(pen_search)
+
+    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
         Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
         mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
         "image" and None for "mse"; each size group is verified on the device right after its own decode.  With
-        scores=True the result has one more element at its end: scores[page][line], the LineScores of lines[page][line]."""
+        scores=True the result has one more element at its end: scores[page][line], the LineScores of lines[page][line].
+        With pen_search=N > 0 (an extension, in 1/64 px up to 64; include/focr_decode.h) every step searches the pen
+        offsets -N ..= N as well as the glyphs and carries the chosen offset forward; the result gains one last element,
+        after the scores: offsets[page][line], an int8 array aligned with the line's text.  The verify then renders every
+        character where it was decoded, and a LineScores' runner is the best candidate of another glyph."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
+        pen_search = self._check_pen_search(pen_search)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
@@ -334,6 +358,7 @@ class LineDecoder:
             pages = list(luma_pages)
         out = [None] * len(pages)
         sc = [None] * len(pages)
+        offs = [None] * len(pages)
         mse = np.zeros(len(pages), dtype=np.float32)
         images = [None] * len(pages) if verify == "image" else None
         by_size = {}
@@ -341,9 +366,12 @@ class LineDecoder:
             by_size.setdefault(np.asarray(p).shape, []).append(i)
         for (h, w), idx in by_size.items():
             batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
-            res, res_sc = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores)
+            res, res_sc, res_offs = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
+                                              pen_search=pen_search)
             for j, i in enumerate(idx):
                 out[i] = res[j]
+                if pen_search:
+                    offs[i] = res_offs[j]
                 if scores:
                     sc[i] = res_sc[j]
             if verify:
@@ -355,22 +383,28 @@ class LineDecoder:
         res = (out, mse, images) if verify else (out,)
         if scores:
             res += (sc,)
+        if pen_search:
+            res += (offs,)
         return res if len(res) > 1 else out
 
-    def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False):
+    def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False,
+                      pen_search=0):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
-        out, sc = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
-                            int(line_height), int(line_advance), scores=scores)
+        pen_search = self._check_pen_search(pen_search)
+        out, sc, offs = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
+                                  int(line_height), int(line_advance), scores=scores, pen_search=pen_search)
         res = (out,)
         if verify:
             mse, imgs = self._verified(verify, int(page_h), int(page_w))
             res = (out, mse, (list(imgs) if imgs is not None else None))
         if scores:
             res += (sc,)
+        if pen_search:
+            res += (offs,)
         return res if len(res) > 1 else out
 
     def close(self):

@@ -161,6 +161,32 @@ int focr_decoder_set_scores(focr_decoder_t *dec, int on);
  * device compares).  Either may be NULL.  Fails with a message unless the last successful run had scores on. */
 int focr_decoder_get_scores(const focr_decoder_t *dec, focr_char_score_t *scores, uint64_t *line_base);
 
+/* ---- device: pen search (an extension: the reference's pen is never corrected) ------------------------------------ */
+
+/* The reference moves the pen by the chosen glyph's increment and never corrects it, so text whose advance is not
+ * quite the font's, or whose glyphs were snapped to the pixel grid, loses the line.  With a search radius N (in 1/64 px,
+ * 0 <= N <= FOCR_PEN_SEARCH_MAX) every step takes the argmin over (glyph i, offset j), j in -N ..= N, instead of over the
+ * glyphs alone.  All of it is exact:
+ *   - the candidate's pen is p_j = pos + (float)j * 0.015625f, one f32 add (pos is the f32 pen, 0 at the line's start);
+ *   - a candidate whose origin_x + p_j (an f32 add) is negative is dropped;
+ *   - otherwise its score is the reference's score_glyph with the pen at p_j: delta trunc((origin_x + p_j) * 64), phase
+ *     delta & 63, whole-pixel shift delta >> 6;
+ *   - the step takes the lowest (score, rank(j), i) with rank(0) = 0, rank(-1) = 1, rank(+1) = 2, rank(-2) = 3, ...: on
+ *     a tie the offset nearest 0 wins, negative before positive, then the first glyph in alphabet order; a blank glyph
+ *     scores the same at every offset and so takes j = 0;
+ *   - the pen becomes p_j + increment[i], one f32 add on the winning candidate's pen: the offset is carried forward.
+ * The loop still runs while pos < width.  N = 0 is the plain decoder, choice for choice and launch for launch.
+ * With scores on (focr_decoder_set_scores), score is the chosen candidate's, and runner / runner_score are the best
+ * candidate, at any offset, of another glyph: the other offsets of the chosen glyph never count. */
+enum { FOCR_PEN_SEARCH_MAX = 64 };
+/* Set the search radius of later runs (0 when the decoder is created; a state of the decoder, not of the font).  n above
+ * FOCR_PEN_SEARCH_MAX is refused.  focr_decoder_run refuses, with a message, a radius of more than half the font's
+ * smallest increment (n / 64 > min_increment / 2): the pen could crawl. */
+int focr_decoder_set_pen_search(focr_decoder_t *dec, uint32_t n);
+/* The chosen offset j of every character of the last run, in the order of focr_decoder_get: offsets[n_chars], all zero
+ * after a run with the search off. */
+int focr_decoder_get_offsets(const focr_decoder_t *dec, int8_t *offsets);
+
 /* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
 
 /* Upload the verify table of the current decode font (the decoder keeps its own copy).  Refused unless it matches the
@@ -173,9 +199,10 @@ int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_verify_font_t *
  * n_pages x page_h x page_w x 3 bytes, in host memory, or in device memory of the decoder's device when
  * rgb_on_device != 0, or nothing when NULL; sq_sums[n_pages] receives the exact sum over the page of (R - B)^2 (the
  * reference's MSE is (float)sum / (float)(uint32_t)(page_w * page_h)).  For a run from device-memory pages, the
- * caller's page buffer must still hold those pages.  Runs a fixed number of launches and returns when the results are
- * in rgb and sq_sums.  Fails with a message without a successful run since the last set_font, or without a verify
- * table. */
+ * caller's page buffer must still hold those pages.  After a run with a pen search every character is rendered at
+ * the pen the run chose for it (pen + j / 64, then the increment from there), so the image shows the line where it was
+ * decoded.  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
+ * without a successful run since the last set_font, or without a verify table. */
 int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums);
 /* Device time of the last verify's kernels in ms (events), and their launch count (constant per batch). */
 float focr_decoder_last_verify_ms(const focr_decoder_t *dec);

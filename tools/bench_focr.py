@@ -16,6 +16,13 @@ plain ones so that both see the same clocks:
   scores_plain_device_ms      median device time of the plain runs in between
   scores_over_plain           the ratio of the two
   scores_wall_ms_per_batch    median host time of one decode(scores=True) call (more to read back and to unpack)
+With --pen-search N, also the decode with a pen search of N/64 px (LineDecoder.decode(pen_search=N)), in runs that
+alternate with plain ones:
+  search_device_ms_per_batch  median device time of the batch's kernels with the search on (the same 3 launches)
+  search_plain_device_ms      median device time of the plain runs in between
+  search_over_plain           the ratio of the two, beside search_candidates = 2 N + 1 offsets per glyph
+  search_wall_ms_per_batch    median host time of one decode(pen_search=N) call, offsets read back and unpacked
+  search_lines_changed        lines of the batch the search decodes differently from the plain run
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -66,6 +73,7 @@ def main():
     ap.add_argument("--verify", action="store_true", help="also time the device verify of the batch")
     ap.add_argument("--test-images", action="store_true", help="also time focr --test's images of the batch")
     ap.add_argument("--scores", action="store_true", help="also time the decode with per-character scores on")
+    ap.add_argument("--pen-search", type=int, default=0, metavar="N", help="also time the decode with a pen search of N/64 px")
     a = ap.parse_args()
     pages = synth(a.pages, a.seed)
     geo = (45, 39, 608, 12, 15)
@@ -105,6 +113,19 @@ def main():
                 swall.append((time.perf_counter() - t) * 1e3)
                 sdev.append(dec.last_ms)
             slaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+        if a.pen_search:
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, pen_search=a.pen_search)
+            ndev, nwall, npdev = [], [], []
+            for _ in range(a.steps):
+                dec.decode(pages, *geo)
+                npdev.append(dec.last_ms)
+                t = time.perf_counter()
+                dec.decode(pages, *geo, pen_search=a.pen_search)
+                nwall.append((time.perf_counter() - t) * 1e3)
+                ndev.append(dec.last_ms)
+            found, _ = dec.decode(pages, *geo, pen_search=a.pen_search)
+            nlaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
         if a.test_images:
             for _ in range(a.warmup):
                 dec.test_images(pages, *geo)
@@ -134,6 +155,13 @@ def main():
         res.update({"scores_device_ms_per_batch": round(sms, 4), "scores_device_ms_min": round(float(min(sdev)), 4),
                     "scores_plain_device_ms": round(pms, 4), "scores_over_plain": round(sms / pms, 4), "scores_launches": slaunches,
                     "scores_wall_ms_per_batch": round(float(np.median(swall)), 3)})
+    if a.pen_search:
+        nms, npms = float(np.median(ndev)), float(np.median(npdev))
+        changed = sum(ta != tb for pa, pb in zip(out, found) for (_, ta), (_, tb) in zip(pa, pb))
+        res.update({"pen_search": a.pen_search, "search_candidates": 2 * a.pen_search + 1, "search_device_ms_per_batch": round(nms, 4),
+                    "search_device_ms_min": round(float(min(ndev)), 4), "search_plain_device_ms": round(npms, 4),
+                    "search_over_plain": round(nms / npms, 3), "search_launches": nlaunches,
+                    "search_wall_ms_per_batch": round(float(np.median(nwall)), 3), "search_lines_changed": changed})
     if a.test_images:
         tms = float(np.median(tdev))
         res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
