@@ -368,6 +368,9 @@ DECODE_HIP_SYMBOLS = {
     "focr_decoder_get_scores": (C.c_int, [C.c_void_p, C.POINTER(CharScore), C.c_void_p]),
     "focr_decoder_set_pen_search": (C.c_int, [C.c_void_p, C.c_uint32]),
     "focr_decoder_get_offsets": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "focr_decoder_set_whole_line": (C.c_int, [C.c_void_p, C.c_int]),
+    "focr_decoder_get_pens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "focr_decoder_debug_set_whole_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "focr_decoder_set_verify_font": (C.c_int, [C.c_void_p, C.POINTER(VerifyFontStruct)]),
     "focr_decoder_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "focr_decoder_last_verify_ms": (C.c_float, [C.c_void_p]),

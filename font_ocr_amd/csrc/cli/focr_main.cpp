@@ -14,7 +14,10 @@
 //     them (focr_decoder_get_scores); stdout and the --verify files are the same with and without it;
 //   * --pen-search N is an extension: every step also searches the pen offsets -N ..= N (in 1/64 px, at most 64) and
 //     carries the chosen one forward (focr_decoder_set_pen_search); stdout stays text only, the --verify files and MSEs
-//     come from the searched positions, and --scores gains a trailing pen_offset column.
+//     come from the searched positions, and --scores gains a trailing pen_offset column;
+//   * --whole-line is an extension for proportional fonts: every line is the text that minimises the whole line's squared
+//     error over pens on the 1/64 px grid (focr_decoder_set_whole_line), not the pen loop's greedy choice; stdout stays
+//     text only and --verify draws every character at its pen; with --scores or --pen-search it is a usage error.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -42,7 +45,7 @@ const size_t BATCH_PAGES = 256;
 struct Args {
     std::vector<std::string> img;
     std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores;
-    bool hinting = false, have_verify = false, have_test = false, have_scores = false;
+    bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false;
     float text_size = 0.f, kerning = 1.f;
     uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0, pen_search = 0;
     bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
@@ -80,6 +83,7 @@ void print_help() {
            "      --verify <VERIFY>                Dir for verify images. Red is reference, Blue is rendered\n"
            "      --scores <SCORES>                [extension] CSV of every decoded character's score, runner-up and margin\n"
            "      --pen-search <N>                 [extension] Also search pen offsets of up to N/64 px at every step, N <= 64 [default: 0]\n"
+           "      --whole-line                     [extension] Decode each line as a whole, for proportional fonts (not with scores or a pen search)\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -142,6 +146,7 @@ Args parse_args(int argc, char **argv) {
             a.pen_search = num_u(s);
             if (a.pen_search > FOCR_PEN_SEARCH_MAX) usage_error("invalid value '" + s + "' for '--pen-search': the radius is at most 64");
         }
+        else if (k == "--whole-line") a.whole_line = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -157,6 +162,8 @@ Args parse_args(int argc, char **argv) {
     if (!a.have_line_height) missing += "\n  --line-height <LINE_HEIGHT>";
     if (!a.have_line_advance) missing += "\n  --line-advance <LINE_ADVANCE>";
     if (!missing.empty()) usage_error("the following required arguments were not provided:" + missing);
+    if (a.whole_line && a.have_scores) usage_error("the argument '--whole-line' cannot be used with '--scores <SCORES>'");
+    if (a.whole_line && a.pen_search) usage_error("the argument '--whole-line' cannot be used with '--pen-search <N>'");
     return a;
 }
 
@@ -302,6 +309,7 @@ int main(int argc, char **argv) {
     }
     if (csv && focr_decoder_set_scores(dec, 1) != 0) die(std::string("focr_decoder_set_scores: ") + focr_decoder_last_error(dec), 1);
     if (focr_decoder_set_pen_search(dec, args.pen_search) != 0) die(std::string("focr_decoder_set_pen_search: ") + focr_decoder_last_error(dec), 1);
+    if (focr_decoder_set_whole_line(dec, args.whole_line) != 0) die(std::string("focr_decoder_set_whole_line: ") + focr_decoder_last_error(dec), 1);
     const bool csv_offsets = csv && args.pen_search > 0;
 
     std::vector<std::vector<Line>> lines(n_img);

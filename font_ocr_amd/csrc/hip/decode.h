@@ -196,6 +196,13 @@ struct focr_decoder {
     // pen search (focr_decoder_set_pen_search): the chosen offset of every step beside d_chars; grown by a run with a radius
     uint32_t pen_search = 0;
     focr::DevArray<int8_t> d_pen;
+    // whole-line decode (focr_decoder_set_whole_line): inc64 per glyph, the workgroups' backpointer scratch, and the pen of
+    // every character beside d_chars and the cost of every work-list line beside d_nchars; grown by a run with the mode on
+    bool whole_on = false;
+    uint32_t whole_grid = 0;  // focr_decoder_debug_set_whole_grid: at most this many workgroups (0: no limit of the test's)
+    focr::DevArray<uint32_t> d_inc64, d_pens;
+    focr::DevArray<uint16_t> d_back;
+    focr::DevArray<int64_t> d_cost;
     // results of the last run
     std::vector<focr_decoded_line_t> lines;
     std::vector<uint16_t> chars;
@@ -203,11 +210,14 @@ struct focr_decoder {
     std::vector<focr_char_score_t> char_scores;
     std::vector<uint64_t> line_base;
     std::vector<int8_t> offsets;  // beside chars: all zero after a run without a search
+    bool have_whole = false;      // the last successful run was a whole-line run
+    std::vector<uint32_t> pens;   // beside chars: each character's pen in 1/64 px
+    std::vector<int64_t> line_cost;
     // verify: the table, what the last successful run left for it, buffers
     uint32_t n_vglyphs = 0, hmax = 0;
     focr::DevArray<focr_dec::VerifyGlyph> d_vglyphs;
     focr::DevArray<focr_dec::VerifyPhase> d_vphases;
-    bool run_ok = false, run_searched = false;  // run_searched: the last successful run wrote d_pen
+    bool run_ok = false, run_searched = false, run_whole = false;  // the last successful run wrote d_pen / d_pens
     focr_dec::Geometry run_g{};
     size_t run_pages = 0;
     uint32_t run_x_start = 0;

@@ -10,12 +10,15 @@
 //      (focr_decoder_set_scores) the same launch also keeps the second lowest key and sums r^2 over the line's crop.
 //      With a pen search radius (focr_decoder_set_pen_search) line_search_kernel takes its place: one workgroup per line,
 //      the argmin over (glyph, pen offset), and the chosen offset of every step beside its glyph.
+//      With the whole-line decode on (focr_decoder_set_whole_line) line_whole_kernel takes its place: a dynamic programme
+//      over pens in 1/64 px that minimises the sum of the footprint terms along the line, and every character's pen.
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
 // order of the sums nor the device changes a choice.  The pen update is one f32 add of the host-computed increment.
 //
 // The verify and --test images of a batch are decode_images.hip's; decode.h holds what the two files share.
+#include <cmath>
 #include <cstring>
 
 #include "decode.h"
@@ -329,6 +332,154 @@ __global__ __launch_bounds__(SEARCH_THREADS) void line_search_kernel(const uint8
     if (tid == 0) n_chars[k] = n;
 }
 
+// ---- whole-line decode (focr_decoder_set_whole_line; an extension, see include/focr_decode.h) ------------------------
+
+constexpr uint32_t WHOLE_THREADS = 256;     // one workgroup of four waves per work-list line at a time
+constexpr uint32_t WHOLE_BATCH_MAX = 512;   // states per batch at most (and at most the smallest inc64)
+constexpr uint32_t WHOLE_MISC_BYTES = 64 + 2 * WHOLE_BATCH_MAX;  // the waves' end keys, the live count; the batch's live states
+constexpr uint32_t WHOLE_RING_MAX = 4096;   // keys of the cost ring at most: ring and the rest stay inside LDS_STRIP_MAX
+constexpr uint64_t WHOLE_COST_BIAS = 1ull << 47;
+constexpr size_t WHOLE_SCRATCH_BUDGET = 64u << 20;  // bytes of backpointer scratch at most (a single workgroup's may exceed it)
+constexpr uint32_t WHOLE_GRID_MAX = 2048;
+
+struct WholeParams {
+    int origin_d;        // 64 * origin_x
+    uint32_t batch;      // B: states per batch, <= the smallest inc64
+    uint32_t ring_mask;  // ring length - 1; the length is a power of two >= B + max_inc
+    uint32_t max_inc;    // the largest inc64
+    uint32_t n_states;   // 64 * w + max_inc: the scratch of one workgroup
+};
+
+// The footprint term of one glyph rendering against a strip: the sum over the bitmap's pixels inside the crop (w columns,
+// h rows) of c * (c - 2 r), the inner loop of line_decode_kernel.  The two older kernels keep their own copy: calling this
+// from them changes their machine code (tools/isa_hash.py), and the plain decoder's instruction stream is what its
+// benchmark pins.
+__device__ __forceinline__ int footprint_term(const uint32_t *strip, uint32_t sdw, int w, uint32_t h, const uint32_t *__restrict__ tile,
+                                              uint32_t ndw, uint32_t box_h, int x0, int y0) {
+    const int r_lo = std::max(0, -y0), r_hi = std::min((int)box_h, (int)h - y0);
+    uint32_t cc = 0, cr = 0;
+    for (int r = r_lo; r < r_hi; r++) {
+        const uint32_t *srow = strip + (size_t)(y0 + r) * sdw;
+        const uint32_t *trow = tile + (size_t)r * ndw;
+        for (uint32_t q = 0; q < ndw; q++) {
+            const int base = x0 + 4 * (int)q;
+            if (base <= -4 || base >= w) continue;
+            uint32_t c = trow[q];
+            if (base < 0 || base + 4 > w) c &= edge_mask(base, w);
+            const uint32_t a = (uint32_t)(base + (int)PAD);
+            const uint32_t rv = __builtin_amdgcn_alignbyte(srow[(a >> 2) + 1], srow[a >> 2], a & 3);
+            cr = __builtin_amdgcn_udot4(c, rv, cr, false);
+            cc = __builtin_amdgcn_udot4(c, c, cc, false);
+        }
+    }
+    return (int)cc - 2 * (int)cr;
+}
+
+// 3w. the dynamic programme over pens in 1/64 px, one workgroup per work-list line at a time (k = blockIdx.x, then
+// += gridDim.x).  ring[s & mask] holds state s's key ((cost + 2^47) << 16 | remembered glyph; ~0: unreachable) while s is
+// within ring length of the batch.  A batch is B <= min inc64 consecutive states: no step is shorter than B, so nothing
+// scored in a batch lands in it and its keys are final when it starts.  Per batch: every reachable state's glyph goes to
+// the scratch and the state to the live list; barrier; the (live state, glyph) candidates, glyph-major over the lanes
+// (neighbouring lanes share a box), are scored and pushed with an LDS 64-bit atomic min, whose order cannot matter;
+// barrier; the batch's slots are cleared for the states one ring length on; barrier.  The targets of a batch reach at
+// most B - 1 + max_inc past its start, so they never alias a live slot.  At the end the states 64 * w .. (all still in
+// the ring) are reduced to the lowest (cost, state), thread 0 walks the scratch back, and the workgroup turns the
+// result into text order.  The scratch needs no clearing: the walk visits only states this line reached and wrote.
+template <bool LDS>
+__global__ __launch_bounds__(WHOLE_THREADS) void line_whole_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
+                                                                   const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
+                                                                   const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps,
+                                                                   const uint32_t *__restrict__ inc64, uint32_t n_glyphs, WholeParams wp,
+                                                                   uint16_t *scratch, uint32_t *__restrict__ n_chars, uint16_t *chars,
+                                                                   uint32_t *pens, int64_t *__restrict__ costs) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_whole[];  // the waves' end keys and the live count, the live list, the ring, then (LDS) the strip
+    uint64_t *red = (uint64_t *)lds_whole;                          // [4]
+    uint32_t *n_live = lds_whole + 8;                               // [1], and [1] the line's character count
+    uint16_t *live = (uint16_t *)(lds_whole + 16);                  // [WHOLE_BATCH_MAX]
+    uint64_t *ring = (uint64_t *)(lds_whole + WHOLE_MISC_BYTES / 4);
+    uint32_t *lds_strip = lds_whole + WHOLE_MISC_BYTES / 4 + 2 * (wp.ring_mask + 1);
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t sdw = g.stride / 4, mask = wp.ring_mask, B = wp.batch;
+    const int w = (int)g.w;
+    const uint32_t n_live_states = 64u * g.w;
+    uint16_t *back = scratch + (size_t)blockIdx.x * wp.n_states;
+    const uint32_t n_lines = *count;
+    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
+        const uint32_t slot = work[k];
+        uint32_t yc, h;
+        slot_rows(g, slot % g.n_slots, &yc, &h);
+        const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
+        if (LDS) {
+            for (uint32_t q = tid; q < sdw * h; q += WHOLE_THREADS) lds_strip[q] = strip[q];
+            strip = lds_strip;
+        }
+        for (uint32_t q = tid; q <= mask; q += WHOLE_THREADS) ring[q] = q ? ~0ull : (WHOLE_COST_BIAS << 16) | 0xffffu;  // cost[0] = 0, no glyph
+        if (tid == 0) n_live[0] = 0;
+        __syncthreads();
+        for (uint32_t b0 = 0; b0 < n_live_states; b0 += B) {
+            const uint32_t nb = std::min(B, n_live_states - b0);
+            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) {
+                const uint64_t key = ring[(b0 + j) & mask];
+                if (key == ~0ull) continue;
+                back[b0 + j] = (uint16_t)key;
+                live[atomicAdd(&n_live[0], 1u)] = (uint16_t)j;
+            }
+            __syncthreads();
+            const uint32_t nl = n_live[0], n_cand = nl * n_glyphs;  // nl <= 512 and n_glyphs < 65536
+            for (uint32_t c = tid; c < n_cand; c += WHOLE_THREADS) {
+                const uint32_t gi = c / nl, s = b0 + live[c - gi * nl];
+                const int d = wp.origin_d + (int)s;
+                const int phase = d & 63, shift = d >> 6;
+                const DevGlyph gl = glyphs[gi];
+                const int2 o = offs[gi * 64 + phase];
+                const int term = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
+                                                shift + o.x, o.y);
+                const uint64_t cost = (ring[s & mask] >> 16) + (uint64_t)(int64_t)term;  // biased, mod 2^64: stays in (0, 2^48)
+                atomicMin((unsigned long long *)&ring[(s + inc64[gi]) & mask], (unsigned long long)((cost << 16) | gi));
+            }
+            __syncthreads();
+            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) ring[(b0 + j) & mask] = ~0ull;
+            if (tid == 0) n_live[0] = 0;
+            __syncthreads();
+        }
+        // the end state: the lowest (cost, t) over t = 64 * w + e, e < max_inc (e < 4096 takes the glyph's place in the key)
+        uint64_t best = ~0ull;
+        for (uint32_t e = tid; e < wp.max_inc; e += WHOLE_THREADS) {
+            const uint64_t key = ring[(n_live_states + e) & mask];
+            if (key != ~0ull) best = std::min<uint64_t>(best, (key & ~(uint64_t)0xffff) | e);
+        }
+        for (int m = 32; m >= 1; m >>= 1) best = std::min(best, shfl_xor_u64(best, m));
+        if (lane == 0) red[wave] = best;
+        __syncthreads();
+        if (tid == 0) {
+            for (uint32_t v = 1; v < WHOLE_THREADS / 64; v++) best = std::min(best, red[v]);
+            // some end state is reachable (every step from a state below 64 * w lands somewhere); without one the line is empty
+            uint32_t t = best != ~0ull ? n_live_states + (uint32_t)(best & 0xffffu) : 0, n = 0;
+            uint32_t gi = (uint32_t)ring[t & mask] & 0xffffu;
+            costs[k] = best != ~0ull ? (int64_t)((best >> 16) - WHOLE_COST_BIAS) : 0;
+            while (t > 0 && n < g.cap && gi < n_glyphs && inc64[gi] <= t) {  // back to front; all but t > 0 always hold (the host's bound; a reached state's glyph) and only guard the accesses
+                t -= inc64[gi];
+                chars[(size_t)k * g.cap + n] = (uint16_t)gi;
+                pens[(size_t)k * g.cap + n] = t;
+                n++;
+                gi = back[t];
+            }
+            n_chars[k] = n;
+            n_live[1] = n;
+        }
+        __syncthreads();
+        const uint32_t n = n_live[1];
+        for (uint32_t q = tid; q < n / 2; q += WHOLE_THREADS) {  // into text order
+            const size_t a = (size_t)k * g.cap + q, b = (size_t)k * g.cap + n - 1 - q;
+            const uint16_t ca = chars[a], cb = chars[b];
+            const uint32_t pa = pens[a], pb = pens[b];
+            chars[a] = cb, chars[b] = ca;
+            pens[a] = pb, pens[b] = pa;
+        }
+        __syncthreads();  // the ring, the strip and the counts are free for the next line
+    }
+}
+
 }  // namespace focr_dec
 
 using namespace focr_dec;
@@ -336,8 +487,9 @@ using namespace focr_dec;
 namespace {
 
 // What focr_decoder_verify draws from: the successful run's geometry and its pages on the device.
-void remember_run(focr_decoder *dec, const Geometry &g, const uint8_t *d_src, size_t n_pages, uint32_t x_start, bool searched) {
+void remember_run(focr_decoder *dec, const Geometry &g, const uint8_t *d_src, size_t n_pages, uint32_t x_start, bool searched, bool whole) {
     dec->run_searched = searched;
+    dec->run_whole = dec->have_whole = whole;
     dec->run_g = g;
     dec->run_pages = n_pages;
     dec->run_x_start = x_start;
@@ -382,7 +534,7 @@ extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
 extern "C" const char *focr_decoder_last_error(const focr_decoder_t *dec) { return dec ? dec->err.c_str() : g_dec_err.c_str(); }
 
 extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font_t *font) {
-    if (dec) dec->run_ok = false, dec->n_vglyphs = 0;  // the last run and the verify table belong to the previous font
+    if (dec) dec->run_ok = false, dec->have_whole = false, dec->n_vglyphs = 0;  // the last run and the verify table belong to the previous font
     if (!dec || !font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_font: bad arguments");
     if (font->n_glyphs > 65535) return dfail(dec, "focr_decoder_set_font: more than 65535 glyphs");
     if (font->bitmaps_len % 4 || font->bitmaps_len / 4 > 0xffffffffull) return dfail(dec, "focr_decoder_set_font: bad bitmap table");
@@ -405,6 +557,7 @@ extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font
         min_inc = std::min(min_inc, s.increment);
     }
     dec->n_glyphs = 0;
+    dec->d_inc64.release();  // the previous font's; a whole-line run uploads its own
     DEC_UPLOAD(dec->d_glyphs, gl.data(), G);
     DEC_UPLOAD(dec->d_offs, offs.data(), offs.size());
     DEC_UPLOAD(dec->d_bitmaps, (const uint8_t *)font->bitmaps, font->bitmaps_len, 4);
@@ -430,6 +583,9 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     dec->char_scores.clear();
     dec->line_base.clear();
     dec->offsets.clear();
+    dec->have_whole = false;
+    dec->pens.clear();
+    dec->line_cost.clear();
     dec->run.ms = 0.f;
     dec->run.launches = 0;
     if (!dec->n_glyphs) return dfail(dec, "focr_decoder_run: no font (focr_decoder_set_font)");
@@ -444,10 +600,44 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     const uint8_t *d_src = nullptr;
     if (stage_in(dec, dec->d_pages, pages, on_device, page_w * page_h * n_pages, &d_src)) return 1;
     const size_t total = g.total;
-    const bool scores = dec->scores_on;
+    const bool scores = dec->scores_on, whole = dec->whole_on;
+    WholeParams wp{};
+    std::vector<uint32_t> inc64;
+    uint32_t whole_cap = 1;
+    if (whole) {  // the refusals of include/focr_decode.h, before anything is launched
+        if (scores) return dfail(dec, "focr_decoder_run: whole-line decode with scores on (a runner-up has no definition under the dynamic programme)");
+        if (radius) return dfail(dec, "focr_decoder_run: whole-line decode with a pen search radius (the dynamic programme does not search offsets)");
+        const float ox = dec->origin_x;
+        if (!(ox >= 0.f && ox <= 65536.f && ox == floorf(ox)))
+            return dfail(dec, "focr_decoder_run: whole-line decode needs origin_x to be a whole number >= 0 (at most 65536)");
+        uint32_t lo = ~0u, hi = 0;
+        uint64_t T = 0;  // set_font's own bound on a term's magnitude
+        inc64.resize(dec->n_glyphs);
+        for (uint32_t i = 0; i < dec->n_glyphs; i++) {
+            const float v = rintf(dec->inc[i] * 64.0f);
+            if (!(v >= 1.f)) return dfail(dec, "focr_decoder_run: whole-line decode needs every pen increment to be at least 1/64 px (an inc64 below 1)");
+            inc64[i] = v < 16777216.f ? (uint32_t)v : (1u << 24);
+            lo = std::min(lo, inc64[i]), hi = std::max(hi, inc64[i]);
+            T = std::max<uint64_t>(T, (uint64_t)dec->font_glyphs[i].stride * dec->font_glyphs[i].box_h * 2 * 255 * 255);
+        }
+        if (64ull * g.w + hi >= (1ull << 24))
+            return dfail(dec, "focr_decoder_run: whole-line decode needs 64 * width + the largest inc64 below 2^24 (pens must stay exact in f32)");
+        whole_cap = std::max<uint32_t>((64u * g.w + lo - 1) / lo, 1);  // every character advances the pen by at least lo from below 64 * w
+        if ((uint64_t)whole_cap * T >= (1ull << 47))
+            return dfail(dec, "focr_decoder_run: whole-line decode: characters per line times the font's score bound reaches 2^47 (a packed cost could overflow)");
+        wp.origin_d = 64 * (int)ox;
+        wp.batch = std::min(lo, WHOLE_BATCH_MAX);
+        wp.max_inc = hi;
+        uint32_t ring = 64;
+        while (ring < wp.batch + hi && ring <= WHOLE_RING_MAX) ring *= 2;
+        if (ring > WHOLE_RING_MAX)
+            return dfail(dec, "focr_decoder_run: whole-line decode: the widest advance is too large (the cost ring does not fit in LDS)");
+        wp.ring_mask = ring - 1;
+        wp.n_states = 64u * g.w + hi;
+    }
     if (total == 0) {  // nothing to decode and nothing launched; a verify still draws the pages
         DEC_CHECK(hipStreamSynchronize(dec->stream));
-        remember_run(dec, g, d_src, n_pages, x_start, radius != 0);
+        remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
         dec->have_scores = scores;
         return 0;
     }
@@ -465,7 +655,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
             p = radius ? (p - reach) + dec->min_inc : p + dec->min_inc;
             if (++steps > (1u << 20)) return dfail(dec, "focr_decoder_run: the pen advance is too small for the line width");
         }
-        g.cap = std::max<uint32_t>(steps, 1);
+        g.cap = whole ? whole_cap : std::max<uint32_t>(steps, 1);
     }
     const size_t strip_bytes = (size_t)g.stride * g.line_height;
     DEC_GROW(dec->d_strips, strip_bytes * total);
@@ -482,13 +672,29 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     }
     const ScoreOut so{dec->d_term, dec->d_runner_term, dec->d_runner, dec->d_base};  // null arrays with scores off: never touched
     if (radius) DEC_GROW(dec->d_pen, (size_t)g.cap * total);
+    uint32_t whole_grid = 0;
+    if (whole) {  // as many workgroups as the scratch budget allows (one always), each with 64 * w + max inc64 backpointers
+        const size_t fit = std::max<size_t>(WHOLE_SCRATCH_BUDGET / ((size_t)wp.n_states * sizeof(uint16_t)), 1);
+        whole_grid = (uint32_t)std::min<size_t>({total, fit, WHOLE_GRID_MAX});
+        if (dec->whole_grid) whole_grid = std::min(whole_grid, dec->whole_grid);
+        DEC_GROW(dec->d_back, (size_t)whole_grid * wp.n_states);
+        DEC_GROW(dec->d_pens, (size_t)g.cap * total);
+        DEC_GROW(dec->d_cost, total);
+        if (!dec->d_inc64.p) DEC_UPLOAD(dec->d_inc64, inc64.data(), inc64.size());
+    }
 
     DEC_CHECK(hipEventRecord(dec->run.begin, dec->stream));
     line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
     DEC_CHECK(hipGetLastError());
     line_compact_kernel<<<1, COMPACT_THREADS, 0, dec->stream>>>(dec->d_flags, g.total, dec->d_work, dec->d_count);
     DEC_CHECK(hipGetLastError());
-    if (radius) {  // the strip shares LDS with the reduction pairs, so it stays in LDS up to that much less
+    if (whole) {  // the strip shares LDS with the cost ring and the live list
+        const size_t ring_bytes = WHOLE_MISC_BYTES + ((size_t)wp.ring_mask + 1) * 8;
+        const bool lds = strip_bytes + ring_bytes <= LDS_STRIP_MAX;
+        (lds ? line_whole_kernel<true> : line_whole_kernel<false>)<<<whole_grid, WHOLE_THREADS, ring_bytes + (lds ? strip_bytes : 0), dec->stream>>>(
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
+            dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost);
+    } else if (radius) {  // the strip shares LDS with the reduction pairs, so it stays in LDS up to that much less
         const bool lds = strip_bytes + SEARCH_RED_BYTES <= LDS_STRIP_MAX;
         const auto search = lds ? (scores ? line_search_kernel<true, true> : line_search_kernel<true, false>)
                                 : (scores ? line_search_kernel<false, true> : line_search_kernel<false, false>);
@@ -514,6 +720,12 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     DEC_CHECK(hipMemcpyAsync(all.data(), dec->d_chars, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
     std::vector<int8_t> pen(radius ? all.size() : 0);
     if (radius) DEC_CHECK(hipMemcpyAsync(pen.data(), dec->d_pen, pen.size(), hipMemcpyDeviceToHost, dec->stream));
+    std::vector<uint32_t> wpens(whole ? all.size() : 0);
+    std::vector<int64_t> wcost(whole ? total : 0);
+    if (whole) {
+        DEC_CHECK(hipMemcpyAsync(wpens.data(), dec->d_pens, wpens.size() * 4, hipMemcpyDeviceToHost, dec->stream));
+        DEC_CHECK(hipMemcpyAsync(wcost.data(), dec->d_cost, total * 8, hipMemcpyDeviceToHost, dec->stream));
+    }
     std::vector<int32_t> term, runner_term;
     std::vector<uint16_t> runner;
     std::vector<uint64_t> base;
@@ -540,6 +752,10 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         l.pad = 0;
         dec->chars.insert(dec->chars.end(), all.begin() + (size_t)k * g.cap, all.begin() + (size_t)k * g.cap + n);
         if (radius) dec->offsets.insert(dec->offsets.end(), pen.begin() + (size_t)k * g.cap, pen.begin() + (size_t)k * g.cap + n);
+        if (whole) {
+            dec->pens.insert(dec->pens.end(), wpens.begin() + (size_t)k * g.cap, wpens.begin() + (size_t)k * g.cap + n);
+            dec->line_cost.push_back(wcost[k]);
+        }
         if (!scores) continue;
         dec->line_base.push_back(base[k]);
         for (size_t at = (size_t)k * g.cap; at < (size_t)k * g.cap + n; at++) {  // the reference's score: sum r^2 plus the footprint term
@@ -549,7 +765,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         }
     }
     if (!radius) dec->offsets.assign(dec->chars.size(), 0);
-    remember_run(dec, g, d_src, n_pages, x_start, radius != 0);
+    remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
     dec->have_scores = scores;
     return 0;
 }
@@ -564,6 +780,27 @@ extern "C" int focr_decoder_set_pen_search(focr_decoder_t *dec, uint32_t n) {
 extern "C" int focr_decoder_get_offsets(const focr_decoder_t *dec, int8_t *offsets) {
     if (!dec) return dfail(nullptr, "focr_decoder_get_offsets: null decoder");
     if (offsets && !dec->offsets.empty()) memcpy(offsets, dec->offsets.data(), dec->offsets.size());
+    return 0;
+}
+
+extern "C" int focr_decoder_set_whole_line(focr_decoder_t *dec, int on) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_whole_line: null decoder");
+    dec->whole_on = on != 0;
+    return 0;
+}
+
+extern "C" int focr_decoder_get_pens(const focr_decoder_t *dec, uint32_t *pens, int64_t *line_cost) {
+    if (!dec) return dfail(nullptr, "focr_decoder_get_pens: null decoder");
+    if (!dec->have_whole)
+        return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_pens: the last successful run was not a whole-line run (focr_decoder_set_whole_line)");
+    if (pens && !dec->pens.empty()) memcpy(pens, dec->pens.data(), dec->pens.size() * sizeof(uint32_t));
+    if (line_cost && !dec->line_cost.empty()) memcpy(line_cost, dec->line_cost.data(), dec->line_cost.size() * sizeof(int64_t));
+    return 0;
+}
+
+extern "C" int focr_decoder_debug_set_whole_grid(focr_decoder_t *dec, uint32_t grid) {
+    if (!dec) return dfail(nullptr, "focr_decoder_debug_set_whole_grid: null decoder");
+    dec->whole_grid = grid;
     return 0;
 }
 

@@ -3,7 +3,8 @@
 //
 // focr_decoder_verify draws focr --verify's image of the last run (decode.hip) in two launches, from the run's own buffers:
 //   4. verify_layout_kernel: one wave per work-list line repeats render()'s f32 arithmetic (pen, round_out bounds, the
-//      26.6 delta of every glyph; after a run with a pen search, from the pens the run chose) and writes each glyph's
+//      26.6 delta of every glyph; after a run with a pen search or a whole-line run, from the pens the run chose) and
+//      writes each glyph's
 //      true bitmap rectangle, clipped to the canvas and the page;
 //   5. verify_compose_kernel: one workgroup per (page, 16 rows, 256 columns) tile takes, line by line in order, the
 //      last glyph covering each pixel (an LDS atomic max of the glyph index, so placement and order do not matter),
@@ -28,10 +29,11 @@ namespace focr_dec {
 // and the page, written to out[0 .. n).  The line is cs[0 .. n) at (x_start, y of g's slot), or for IOTA the alphabet
 // indices 0 .. n - 1 at (x_start, 0).  Lane 0 writes the line's canvas on the page to *line, clipped (empty when none
 // of it is on the page), with k and n.  js (null: none) is the run's pen search: glyph q is placed at pen + js[q] / 64
-// and the pen advances from there, the decoder's own two f32 adds.
+// and the pen advances from there, the decoder's own two f32 adds.  ps (null: none) is a whole-line run's pens in
+// 1/64 px: glyph q is placed at ps[q] / 64 (exact), whatever the increments before it.
 template <bool IOTA>
 __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, const uint16_t *__restrict__ cs,
-                                            const int8_t *__restrict__ js, uint32_t n, uint32_t k,
+                                            const int8_t *__restrict__ js, const uint32_t *__restrict__ ps, uint32_t n, uint32_t k,
                                             uint32_t x_start, const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
                                             const VerifyPhase *__restrict__ vphases, VerifyRec *__restrict__ out, VerifyLine *__restrict__ line) {
     const uint32_t lane = threadIdx.x;
@@ -43,8 +45,8 @@ __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, co
         const uint32_t c = live ? (IOTA ? j : cs[j]) : 0;
         const float inc = live ? glyphs[c].inc : 0.f;
         const float dj = live && js ? (float)js[j] * 0.015625f : 0.f;
-        float pos = 0.f;
-        for (uint32_t q = 0; q < m; q++) {
+        float pos = live && ps ? __fmul_rn((float)ps[j], 0.015625f) : 0.f;
+        for (uint32_t q = 0; q < m && !ps; q++) {
             if (js) pen = __fadd_rn(pen, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dj), q)));
             if (lane == q) pos = pen;
             pen = __fadd_rn(pen, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), q)));
@@ -95,7 +97,8 @@ __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, co
 __global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t n_pages, uint32_t x_start, const uint32_t *__restrict__ flags,
                                                            const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
                                                            const uint32_t *__restrict__ n_chars, const uint16_t *__restrict__ chars,
-                                                           const int8_t *__restrict__ pen_offs, const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
+                                                           const int8_t *__restrict__ pen_offs, const uint32_t *__restrict__ pens,
+                                                           const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
                                                            const VerifyPhase *__restrict__ vphases, VerifyLine *__restrict__ lines,
                                                            VerifyRec *__restrict__ recs, unsigned long long *__restrict__ sums) {
     const uint32_t b = blockIdx.x, lane = threadIdx.x;
@@ -104,7 +107,8 @@ __global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t 
     if (lane == 0 && flags[b] == 0) lines[b] = VerifyLine{0, 0, 0, 0, 0, 0};  // blank slots are in no work-list entry
     if (b >= *count) return;
     const uint32_t k = b, slot = work[k], n = n_chars[k];
-    layout_line<false>(g, slot, chars + (size_t)k * g.cap, pen_offs ? pen_offs + (size_t)k * g.cap : nullptr, n, k, x_start,
+    layout_line<false>(g, slot, chars + (size_t)k * g.cap, pen_offs ? pen_offs + (size_t)k * g.cap : nullptr,
+                       pens ? pens + (size_t)k * g.cap : nullptr, n, k, x_start,
                        glyphs, vglyphs, vphases, recs + (size_t)k * g.cap, lines + slot);
 }
 
@@ -205,7 +209,7 @@ __global__ __launch_bounds__(TEST_THREADS) void test_flags_kernel(const uint8_t 
 __global__ __launch_bounds__(64) void test_layout_kernel(Geometry g, uint32_t n_glyphs, const DevGlyph *__restrict__ glyphs,
                                                          const VerifyGlyph *__restrict__ vglyphs, const VerifyPhase *__restrict__ vphases,
                                                          VerifyRec *__restrict__ recs, VerifyLine *__restrict__ line) {
-    layout_line<true>(g, 0, nullptr, nullptr, n_glyphs, 0, 0, glyphs, vglyphs, vphases, recs, line);
+    layout_line<true>(g, 0, nullptr, nullptr, nullptr, n_glyphs, 0, 0, glyphs, vglyphs, vphases, recs, line);
 }
 
 // 8. both test images, tile by tile; every thread owns one column of a 16-row, 256-column tile.  The base pixel is
@@ -348,7 +352,8 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     DEC_CHECK(hipEventRecord(dec->verify.begin, dec->stream));
     verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, dec->run_x_start, dec->d_flags, dec->d_work,
                                                                          dec->d_count, dec->d_nchars, dec->d_chars,
-                                                                         dec->run_searched ? (const int8_t *)dec->d_pen : nullptr, dec->d_glyphs,
+                                                                         dec->run_searched ? (const int8_t *)dec->d_pen : nullptr,
+                                                                         dec->run_whole ? (const uint32_t *)dec->d_pens : nullptr, dec->d_glyphs,
                                                                          dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
     DEC_CHECK(hipGetLastError());
     verify_compose_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->run_src, g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y, dec->d_vlines, dec->d_vrecs,

@@ -10,6 +10,9 @@
         # scores[page][line]: what the argmin knew about each character of pages[page][line] (LineScores)
         pages, offsets = dec.decode(luma_pages, 45, 39, 608, 12, 15, pen_search=8)
         # a search of 8/64 px around the pen at every step, carried forward; offsets[page][line]: each character's offset
+        pages, pens, costs = dec.decode(luma_pages, 45, 39, 608, 12, 15, whole_line=True)
+        # the whole line's squared error minimised over pens on the 1/64 px grid (for proportional fonts); pens[page][line]:
+        # each character's pen in 1/64 px, costs[page][line]: the line's sum of footprint terms
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -180,6 +183,7 @@ class LineDecoder:
         self._batch = None  # (n_pages, page_h, page_w) of the last run
         self._scores = False  # the library's switch (focr_decoder_set_scores)
         self._pen_search = 0  # the library's radius (focr_decoder_set_pen_search)
+        self._whole = False  # the library's switch (focr_decoder_set_whole_line)
 
     def _check(self, rc):
         if rc != 0:
@@ -292,10 +296,14 @@ class LineDecoder:
         mse = sums.astype(np.float32) / np.float32((h * w) & 0xFFFFFFFF)  # red_blue_mse: (sum as f32) / (w * h as u32)
         return mse, imgs
 
-    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0):
+    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0, whole_line=False):
         """[[(y, text), ...] per page] of one batch; with scores [[LineScores, ...] per page] beside it (else None); with
-        a pen search [[int8 offsets, ...] per page] (else None)."""
+        a pen search [[int8 offsets, ...] per page] (else None); with whole_line ([[uint32 pens, ...] per page],
+        [[cost, ...] per page]) (else None)."""
         self._batch = None
+        if bool(whole_line) != self._whole:
+            self._check(self._lib.focr_decoder_set_whole_line(self._h, int(bool(whole_line))))
+            self._whole = bool(whole_line)
         if int(pen_search) != self._pen_search:
             self._check(self._lib.focr_decoder_set_pen_search(self._h, int(pen_search)))
             self._pen_search = int(pen_search)
@@ -316,7 +324,12 @@ class LineDecoder:
         if pen_search:
             js = np.zeros(max(1, nc), dtype=np.int8)
             self._check(self._lib.focr_decoder_get_offsets(self._h, js.ctypes.data))
+        if whole_line:
+            ps = np.zeros(max(1, nc), dtype=np.uint32)
+            lc = np.zeros(max(1, nl), dtype=np.int64)
+            self._check(self._lib.focr_decoder_get_pens(self._h, ps.ctypes.data, lc.ctypes.data))
         alpha = self.font.alphabet
+        whole = ([[] for _ in range(n)], [[] for _ in range(n)]) if whole_line else None
         out = [[] for _ in range(n)]
         sc = [[] for _ in range(n)] if scores else None
         offs = [[] for _ in range(n)] if pen_search else None
@@ -326,10 +339,13 @@ class LineDecoder:
             out[ln.page].append((int(ln.y), text))
             if pen_search:
                 offs[ln.page].append(js[ln.first: ln.first + ln.n_chars].copy())
+            if whole_line:
+                whole[0][ln.page].append(ps[ln.first: ln.first + ln.n_chars].copy())
+                whole[1][ln.page].append(int(lc[k]))
             if scores:
                 c = cs[ln.first: ln.first + ln.n_chars]
                 sc[ln.page].append(LineScores(int(base[k]), c["score"].copy(), c["runner"].copy(), c["runner_score"].copy()))
-        return out, sc, offs
+        return out, sc, offs, whole
 
     @staticmethod
     def _check_pen_search(pen_search):
@@ -337,7 +353,15 @@ class LineDecoder:
             raise ValueError(f"pen_search must be 0 .. 64 (1/64 px), not {pen_search!r}")
         return int(pen_search)
 
-    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0):
+    @staticmethod
+    def _check_whole_line(whole_line, scores, pen_search):
+        if whole_line and scores:
+            raise ValueError("whole_line=True does not go with scores=True (a runner-up has no definition under the dynamic programme)")
+        if whole_line and pen_search:
+            raise ValueError("whole_line=True does not go with pen_search (the dynamic programme does not search offsets)")
+        return bool(whole_line)
+
+    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, whole_line=False):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
         Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
         mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
@@ -346,11 +370,17 @@ class LineDecoder:
         With pen_search=N > 0 (an extension, in 1/64 px up to 64; include/focr_decode.h) every step searches the pen
         offsets -N ..= N as well as the glyphs and carries the chosen offset forward; the result gains one last element,
         after the scores: offsets[page][line], an int8 array aligned with the line's text.  The verify then renders every
-        character where it was decoded, and a LineScores' runner is the best candidate of another glyph."""
+        character where it was decoded, and a LineScores' runner is the best candidate of another glyph.
+        With whole_line=True (an extension for proportional fonts; include/focr_decode.h) every line is the text that
+        minimises the whole line's squared error over pens on the 1/64 px grid, not the pen loop's greedy choice; the
+        result gains two last elements: pens[page][line], a uint32 array of each character's pen in 1/64 px, and
+        costs[page][line], the line's sum of footprint terms (int).  The verify then renders every character at its pen.
+        It goes with neither scores nor pen_search."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
         pen_search = self._check_pen_search(pen_search)
+        whole_line = self._check_whole_line(whole_line, scores, pen_search)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
@@ -359,6 +389,7 @@ class LineDecoder:
         out = [None] * len(pages)
         sc = [None] * len(pages)
         offs = [None] * len(pages)
+        wpens, wcosts = [None] * len(pages), [None] * len(pages)
         mse = np.zeros(len(pages), dtype=np.float32)
         images = [None] * len(pages) if verify == "image" else None
         by_size = {}
@@ -366,10 +397,12 @@ class LineDecoder:
             by_size.setdefault(np.asarray(p).shape, []).append(i)
         for (h, w), idx in by_size.items():
             batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
-            res, res_sc, res_offs = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
-                                              pen_search=pen_search)
+            res, res_sc, res_offs, res_whole = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
+                                                         pen_search=pen_search, whole_line=whole_line)
             for j, i in enumerate(idx):
                 out[i] = res[j]
+                if whole_line:
+                    wpens[i], wcosts[i] = res_whole[0][j], res_whole[1][j]
                 if pen_search:
                     offs[i] = res_offs[j]
                 if scores:
@@ -385,18 +418,21 @@ class LineDecoder:
             res += (sc,)
         if pen_search:
             res += (offs,)
+        if whole_line:
+            res += (wpens, wcosts)
         return res if len(res) > 1 else out
 
     def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False,
-                      pen_search=0):
+                      pen_search=0, whole_line=False):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
         pen_search = self._check_pen_search(pen_search)
-        out, sc, offs = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
-                                  int(line_height), int(line_advance), scores=scores, pen_search=pen_search)
+        whole_line = self._check_whole_line(whole_line, scores, pen_search)
+        out, sc, offs, whole = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
+                                         int(line_height), int(line_advance), scores=scores, pen_search=pen_search, whole_line=whole_line)
         res = (out,)
         if verify:
             mse, imgs = self._verified(verify, int(page_h), int(page_w))
@@ -405,6 +441,8 @@ class LineDecoder:
             res += (sc,)
         if pen_search:
             res += (offs,)
+        if whole_line:
+            res += whole
         return res if len(res) > 1 else out
 
     def close(self):

@@ -187,6 +187,48 @@ int focr_decoder_set_pen_search(focr_decoder_t *dec, uint32_t n);
  * after a run with the search off. */
 int focr_decoder_get_offsets(const focr_decoder_t *dec, int8_t *offsets);
 
+/* ---- device: whole-line decode (an extension: the reference's pen loop is greedy) ---------------------------------- */
+
+/* The reference takes, at every pen position, the glyph with the lowest score, and that score is not normalised by the
+ * glyph's area: in a proportional font a wide glyph that covers two narrow ones ("rn" -> "m", "cl" -> "d") collects more
+ * matching ink than either and wins, and the pen is lost from then on.  The objective behind the loop is the whole
+ * line's squared error, sum over the canvas of (r - render(text))^2 = sum r^2 + the sum over the characters of the
+ * footprint term the decoder already compares (exact while footprints do not overlap; the true text makes it zero).
+ * With the mode on, a run minimises that sum by a dynamic programme over pens on FreeType's own 1/64 px grid:
+ *   - inc64[i] = (int)rintf(increment[i] * 64);
+ *   - states are pens s in 1/64 px, starting at s = 0;
+ *   - the rendering at state s is the plain decoder's at pos = s / 64: delta 64 * origin_x + s, phase delta & 63, whole-
+ *     pixel shift delta >> 6;
+ *   - term(i, s) is the int32 footprint term of glyph i there: the sum over the glyph's bitmap, clipped to the crop, of
+ *     c * (c - 2 r), the plain decoder's score less the crop's sum of r^2;
+ *   - cost[0] = 0; for t > 0, cost[t] is the minimum of cost[s] + term(i, s) over glyphs i and reachable states
+ *     s = t - inc64[i] with 0 <= s < 64 * width (the reference's loop runs while pos < width);
+ *   - the glyph remembered for t is the one with the lowest (cost, i);
+ *   - the line ends in the reachable state t >= 64 * width with the lowest (cost[t], t);
+ *   - the text is read back along the remembered glyphs.
+ * A run returns, beside the lines of focr_decoder_get, each character's pen s and each line's final cost, the sum of its
+ * characters' terms: the line's squared error is line_base + cost.  Prepass and compaction are the plain run's and the
+ * launch count stays 3.  focr_decoder_run refuses, with a message:
+ *   - an origin_x that is not a whole number >= 0;
+ *   - any inc64 < 1;
+ *   - 64 * width + max inc64 >= 2^24 (pens must stay exact in f32);
+ *   - ceil(64 * width / min inc64) * T >= 2^47, T = max stride * box_h * 2 * 255^2 (set_font's own bound on a term): a
+ *     packed cost could overflow; the first factor is the exact bound on a line's characters;
+ *   - a widest advance so large that the device's cost ring does not fit in LDS (min(min inc64, 512) + max inc64 > 4096);
+ *   - scores on (a runner-up has no definition under a dynamic programme yet);
+ *   - a pen search radius (a programme over offsets as well is a later step).
+ * With the mode off a run launches and returns what it did before the mode existed. */
+/* Switch the whole-line decode of later runs on or off (off when the decoder is created; a state of the decoder, not of
+ * the font). */
+int focr_decoder_set_whole_line(focr_decoder_t *dec, int on);
+/* The pens of the last run, in the order of focr_decoder_get: pens[n_chars], each character's state s (its pen is
+ * s / 64 px), and line_cost[n_lines].  Either may be NULL.  Fails with a message unless the last successful run was a
+ * whole-line run. */
+int focr_decoder_get_pens(const focr_decoder_t *dec, uint32_t *pens, int64_t *line_cost);
+/* Debug: at most `grid` workgroups for later whole-line runs (0: the decoder's own choice), so that a test can make one
+ * workgroup take several lines. */
+int focr_decoder_debug_set_whole_grid(focr_decoder_t *dec, uint32_t grid);
+
 /* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
 
 /* Upload the verify table of the current decode font (the decoder keeps its own copy).  Refused unless it matches the
@@ -200,8 +242,8 @@ int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_verify_font_t *
  * rgb_on_device != 0, or nothing when NULL; sq_sums[n_pages] receives the exact sum over the page of (R - B)^2 (the
  * reference's MSE is (float)sum / (float)(uint32_t)(page_w * page_h)).  For a run from device-memory pages, the
  * caller's page buffer must still hold those pages.  After a run with a pen search every character is rendered at
- * the pen the run chose for it (pen + j / 64, then the increment from there), so the image shows the line where it was
- * decoded.  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
+ * the pen the run chose for it (pen + j / 64, then the increment from there), and after a whole-line run at
+ * pos = s / 64 of its returned pen s, so the image shows the line where it was decoded.  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
  * without a successful run since the last set_font, or without a verify table. */
 int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums);
 /* Device time of the last verify's kernels in ms (events), and their launch count (constant per batch). */

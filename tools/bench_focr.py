@@ -23,6 +23,14 @@ alternate with plain ones:
   search_over_plain           the ratio of the two, beside search_candidates = 2 N + 1 offsets per glyph
   search_wall_ms_per_batch    median host time of one decode(pen_search=N) call, offsets read back and unpacked
   search_lines_changed        lines of the batch the search decodes differently from the plain run
+With --whole-line, also the whole-line decode (LineDecoder.decode(whole_line=True)), in runs that alternate with plain
+ones; --font PATH sets the pages and decodes them in another font than DejaVu Sans Mono (a proportional one is what the
+mode is for: nearly every 1/64 px pen is then a state, where a monospace line has one state per character):
+  whole_device_ms_per_batch   median device time of the batch's kernels with the mode on (the same 3 launches)
+  whole_plain_device_ms       median device time of the plain runs in between
+  whole_over_plain            the ratio of the two
+  whole_wall_ms_per_batch     median host time of one decode(whole_line=True) call, pens and costs read back and unpacked
+  whole_lines_changed         lines of the batch the mode decodes differently from the plain run
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -50,14 +58,14 @@ from font_ocr_amd.decoder import render_text  # noqa: E402
 FONT = os.path.join(ROOT, "tests", "golden", "DejaVuSansMono.ttf")
 
 
-def synth(n_pages, seed, W=608, H=720, x=45, y=39, n_lines=40, advance=15, size=13.0):
+def synth(n_pages, seed, W=608, H=720, x=45, y=39, n_lines=40, advance=15, size=13.0, font=FONT):
     rng = np.random.default_rng(seed)
     ink = FOCR_DEFAULT_ALPHABET.replace(" ", "")
     pages = np.full((n_pages, H, W), 255, dtype=np.uint8)
     for p in range(n_pages):
         for i in range(n_lines):
             words = [''.join(rng.choice(list(ink), int(rng.integers(2, 10)))) for _ in range(12)]
-            c = render_text(FONT, size, " ".join(words)[:68])
+            c = render_text(font, size, " ".join(words)[:68])
             ly = y + i * advance
             hh, ww = min(c.shape[0], H - ly), min(c.shape[1], W - x)
             pages[p, ly: ly + hh, x: x + ww] = np.minimum(pages[p, ly: ly + hh, x: x + ww], 255 - c[:hh, :ww])
@@ -74,11 +82,13 @@ def main():
     ap.add_argument("--test-images", action="store_true", help="also time focr --test's images of the batch")
     ap.add_argument("--scores", action="store_true", help="also time the decode with per-character scores on")
     ap.add_argument("--pen-search", type=int, default=0, metavar="N", help="also time the decode with a pen search of N/64 px")
+    ap.add_argument("--whole-line", action="store_true", help="also time the whole-line decode")
+    ap.add_argument("--font", default=FONT, metavar="PATH", help="the font of the pages and of the decoder [DejaVu Sans Mono]")
     a = ap.parse_args()
-    pages = synth(a.pages, a.seed)
+    pages = synth(a.pages, a.seed, font=a.font)
     geo = (45, 39, 608, 12, 15)
     t0 = time.perf_counter()
-    font = DecodeFont(FONT, 13.0, FOCR_DEFAULT_ALPHABET)
+    font = DecodeFont(a.font, 13.0, FOCR_DEFAULT_ALPHABET)
     host_ms = (time.perf_counter() - t0) * 1e3
     with LineDecoder(0) as dec:
         dec.set_font(font, 13.0)
@@ -126,6 +136,18 @@ def main():
                 ndev.append(dec.last_ms)
             found, _ = dec.decode(pages, *geo, pen_search=a.pen_search)
             nlaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+        if a.whole_line:
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, whole_line=True)
+            wdev, wwall, wpdev = [], [], []
+            for _ in range(a.steps):
+                dec.decode(pages, *geo)
+                wpdev.append(dec.last_ms)
+                t = time.perf_counter()
+                whole = dec.decode(pages, *geo, whole_line=True)[0]
+                wwall.append((time.perf_counter() - t) * 1e3)
+                wdev.append(dec.last_ms)
+            wlaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
         if a.test_images:
             for _ in range(a.warmup):
                 dec.test_images(pages, *geo)
@@ -141,7 +163,7 @@ def main():
     ms = float(np.median(dev))
     res = {
         "bench": "focr_decode", "pages": a.pages, "page_w": 608, "page_h": 720, "lines": n_lines, "chars": n_chars,
-        "font": "DejaVuSansMono 13px", "alphabet_len": len(FOCR_DEFAULT_ALPHABET), "launches_per_batch": launches,
+        "font": os.path.splitext(os.path.basename(a.font))[0] + " 13px", "alphabet_len": len(FOCR_DEFAULT_ALPHABET), "launches_per_batch": launches,
         "host_table_ms": round(host_ms, 2), "device_ms_per_batch": round(ms, 4), "device_ms_min": round(float(min(dev)), 4),
         "wall_ms_per_batch": round(float(np.median(wall)), 3), "steps": a.steps, "warmup": a.warmup,
         "pages_per_s": round(a.pages / ms * 1e3, 1), "lines_per_s": round(n_lines / ms * 1e3, 1),
@@ -162,6 +184,12 @@ def main():
                     "search_device_ms_min": round(float(min(ndev)), 4), "search_plain_device_ms": round(npms, 4),
                     "search_over_plain": round(nms / npms, 3), "search_launches": nlaunches,
                     "search_wall_ms_per_batch": round(float(np.median(nwall)), 3), "search_lines_changed": changed})
+    if a.whole_line:
+        wms, wpms = float(np.median(wdev)), float(np.median(wpdev))
+        changed = sum(ta != tb for pa, pb in zip(out, whole) for (_, ta), (_, tb) in zip(pa, pb))
+        res.update({"whole_device_ms_per_batch": round(wms, 4), "whole_device_ms_min": round(float(min(wdev)), 4),
+                    "whole_plain_device_ms": round(wpms, 4), "whole_over_plain": round(wms / wpms, 3), "whole_launches": wlaunches,
+                    "whole_wall_ms_per_batch": round(float(np.median(wwall)), 3), "whole_lines_changed": changed})
     if a.test_images:
         tms = float(np.median(tdev))
         res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
