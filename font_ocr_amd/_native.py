@@ -126,6 +126,7 @@ HIP_SYMBOLS = {
     "focr_debug_device_bytes": (C.c_size_t, []),
     "focr_debug_set_tail_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "focr_debug_phase_stamps": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "focr_debug_tail_path": (C.c_int, [C.c_void_p, C.c_void_p]),
     "focr_debug_set_stats_form": (C.c_int, [C.c_void_p, C.c_int]),
     "focr_debug_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "focr_ctx_set_size_estimates": (C.c_int, [C.c_void_p, C.c_int]),

@@ -229,6 +229,11 @@ struct focr_ctx {
     bool cand_intact = false;                   // tests: d_cand still holds the last MFMA scan's candidates as the scan kernels left them (focr_debug_candidates)
     int dbg_stats_form = 0;  // tests / A-B: 1 = the LDS-tiled statistics kernel for every class (focr_debug_set_stats_form; 0: the register form where it applies)
     uint32_t dbg_grid_num = 0, dbg_grid_den = 0;  // tests: the tail's persistent kernels on num / den times their workgroups (focr_debug_set_tail_grid; 0: as designed)
+    // tests: what the last scan's tail chose (focr_debug_tail_path; host bookkeeping, written by launch_scan_mfma, row_tail, rows2_verify and
+    // the ordering pass): the values of FOCR_TAIL_* / FOCR_ORDER_* / FOCR_VERIFY_FORM_* in include/focr_ncc.h
+    struct TailPath {
+        uint32_t tail = 0, big_launch = 0, library_sort = 0, order_form = 0, seg_shift = 0, n_seg = 0, verify_form = 0, verify_chunks = 0;
+    } tail_path;
     int prefilter = 0;                          // FOCR_PREFILTER_*: auto / plane kernel / legacy kernel (focr_ctx_set_prefilter)
     focr::DevArray<uint16_t> d_planes;          // threshold planes, int16: [super-class][value][page][Lrows][Lpitch] (mfma_common.h); exact, grow-only
 

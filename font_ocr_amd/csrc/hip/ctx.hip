@@ -310,6 +310,16 @@ int focr_debug_set_tail_grid(focr_ctx_t *c, uint32_t num, uint32_t den) {
     return FOCR_OK;
 }
 
+int focr_debug_tail_path(focr_ctx_t *c, uint32_t out[8]) {
+    if (!c || !out) return fail(c, FOCR_ERR_INVALID, "focr_debug_tail_path: bad arguments");
+    if (!c->scanned) return fail(c, FOCR_ERR_STATE, "focr_debug_tail_path: no scan results");
+    if (int rc = finish_results(c)) return rc;  // (an estimated scan whose counts exceeded their bounds is redone here: the redo's path is the scan's)
+    const focr_ctx::TailPath &p = c->tail_path;
+    const uint32_t v[8] = {p.tail, p.big_launch, p.library_sort, p.order_form, p.seg_shift, p.n_seg, p.verify_form, p.verify_chunks};
+    memcpy(out, v, sizeof v);
+    return FOCR_OK;
+}
+
 int focr_debug_set_stats_form(focr_ctx_t *c, int form) {
     if (!c || form < 0 || form > 1) return FOCR_ERR_INVALID;
     c->dbg_stats_form = form;
@@ -745,6 +755,7 @@ static int scan_now(focr_ctx *c) {
         c->sub_np = np;
         c->ordered = false;
         c->lazy.pending = false;
+        c->tail_path = {};
         int r = mode == FOCR_SCAN_MFMA ? launch_scan_mfma(c, threshold) : launch_scan_direct(c, threshold, mode == FOCR_SCAN_RUST);
         if (r) return r;
         if (!c->ordered && (r = order_hits(c))) return r;

@@ -189,6 +189,7 @@ static int order_sorted_hits_sort(focr_ctx *c, uint64_t *hkeys, float *hsims, co
     float *v = c->ord_v.as<float>(), *v_alt = c->ord_v_alt.as<float>();
     uint8_t *keep = c->ord_keep;
     c->lazy.pending = false;  // this form writes d_matches itself
+    c->tail_path.order_form = FOCR_ORDER_SORTING;
     c->d_hkeys = hkeys;
     c->d_hsims = hsims;
     uint64_t *count64 = c->d_seg_start + (n_seg + 1);
@@ -519,6 +520,7 @@ int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t
     hipLaunchKernelGGL(unit_rank_kernel, dim3(unit_blocks), dim3(256), lds, c->stream, (const uint64_t *)hkeys, c->fmt, T, (const uint32_t *)page_unit0, n_pages,
                        (const uint32_t *)unit_begin, (const uint32_t *)unit_end, (const uint32_t *)uhist, c->cap, keep);
     FOCR_HIP(c, hipGetLastError());
+    c->tail_path.order_form = FOCR_ORDER_COUNTING;
     c->lazy = {true, n_pages, max_units, unit_blocks};  // d_matches: written by whoever reads it first (materialise_matches)
     hipLaunchKernelGGL(record_scan_sizes, dim3(1), dim3(1), 0, c->stream, n_cand_p, (uint64_t)ub_c, n_p, (uint64_t)ub, c->d_seg_offset + n_seg, c->d_res);
     FOCR_HIP(c, hipGetLastError());

@@ -614,6 +614,8 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
 #undef FOCR_VERIFY_CHUNKS
                 if (attr == hipSuccess) {
                     FOCR_HIP(c, hipGetLastError());
+                    c->tail_path.verify_form = FOCR_VERIFY_FORM_CHUNKS;
+                    c->tail_path.verify_chunks = ct.n;
                     goto verified;
                 }
                 (void)hipGetLastError();  // the device refuses that much LDS: the rows come from global memory instead (below)
@@ -634,6 +636,7 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
         }
 #undef FOCR_VERIFY_LIST
         FOCR_HIP(c, hipGetLastError());
+        c->tail_path.verify_form = mode == 2 ? FOCR_VERIFY_FORM_LDS12 : mode == 1 ? FOCR_VERIFY_FORM_LDS16 : FOCR_VERIFY_FORM_GLOBAL;
     }
 verified:
     FOCR_HIP(c, hipEventRecord(c->ev[3], c->stream));

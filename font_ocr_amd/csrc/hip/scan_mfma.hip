@@ -244,6 +244,10 @@ static int row_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_
     // (exact sizes only: launch_scan_mfma): library sort of the placed hits
     c->row_cap = rows_capacity_for(row_max);
     const bool big_expected = row_max > 1024, sort_rows = c->row_cap != 0;
+    c->tail_path.big_launch = sort_rows && big_expected;
+    c->tail_path.library_sort = !sort_rows && ub_h >= 2;
+    c->tail_path.seg_shift = c->row_hist.seg_shift;
+    c->tail_path.n_seg = c->row_hist.n_seg;
     if ((rc = rows2_place(c, n_cand_p, ub_c, ub_h, big_expected, sort_rows))) return rc;
     if (!sort_rows && (rc = sort_pairs_u64_f32(c, c->d_hit_keys, c->d_hit_keys_alt, c->d_hit_sims_alt, c->d_hit_sims, ub_h, c->fmt.bits()))) return rc;
     return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims_alt, c->d_res + 6, ub_h, n_cand_p, ub_c);
@@ -348,6 +352,7 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
             ub_c = (size_t)n_cand;
         }
         c->cand_intact = use_rows;  // the row tail only reads d_cand; the legacy tail sorts and compacts it in place (focr_debug_candidates)
+        c->tail_path.tail = use_rows ? FOCR_TAIL_ROWS : FOCR_TAIL_LEGACY;
         return use_rows ? row_tail(c, thr_d, n_cand_p, ub_c) : legacy_tail(c, thr_d, n_cand_p, ub_c);
     }
     return fail(c, FOCR_ERR_OVERFLOW, "scan_mfma: candidate buffer kept overflowing");

@@ -498,6 +498,31 @@ int focr_debug_phase_stamps(focr_ctx_t *ctx, double out[9]);
  * num / den times the workgroups they are designed for (0 / 0: as designed).  Results must be identical for every grid. */
 int focr_debug_set_tail_grid(focr_ctx_t *ctx, uint32_t num, uint32_t den);
 
+/* Test hook: what the tail of the context's last scan chose (host-side bookkeeping; nothing on the device changes for it), so
+ * that a test built to reach one path can tell that it did:
+ *   out[0]  FOCR_TAIL_*: the hits-first row tail, the legacy tail (sort, verify, compact), or neither (a direct / rust
+ *           scan)
+ *   out[1]  1 if the row sort's second launch ran (buckets of 1025 .. 4096 hits)
+ *   out[2]  1 if the library radix sort of the placed hits ran instead of the row sort (a bucket above 4096 hits, exact sizes)
+ *   out[3]  FOCR_ORDER_*: the form of the ordering pass: counting, or sorting (banks above 4096 templates); also set by a direct
+ *           / rust scan, whose hits take the same pass behind their radix sort
+ *   out[4], out[5]  log2 of the bucket's x-segment width and the segments per page row (row tail; else 0)
+ *   out[6]  FOCR_VERIFY_FORM_*: where the row tail's exact verify took the template rows from (global memory, 16- or 12-byte
+ *           rows staged in LDS whole, LDS in chunks of templates); out[7]: the chunk passes of the last form
+ * A batch scanned in page sub-ranges reports its last sub-range; an estimated scan that was redone reports the redo. */
+#define FOCR_TAIL_NONE 0
+#define FOCR_TAIL_ROWS 1
+#define FOCR_TAIL_LEGACY 2
+#define FOCR_ORDER_NONE 0
+#define FOCR_ORDER_COUNTING 1
+#define FOCR_ORDER_SORTING 2
+#define FOCR_VERIFY_FORM_NONE 0
+#define FOCR_VERIFY_FORM_GLOBAL 1
+#define FOCR_VERIFY_FORM_LDS16 2
+#define FOCR_VERIFY_FORM_LDS12 3
+#define FOCR_VERIFY_FORM_CHUNKS 4
+int focr_debug_tail_path(focr_ctx_t *ctx, uint32_t out[8]);
+
 /* Test hooks for the window statistics: form 1 = the LDS-tiled kernel for every size class (0: the register form for classes whose
  * kept width is 8 px, stats.hip); focr_debug_planes copies the int16 threshold planes of the context's last MFMA scan to the
  * host ([value][page][Lrows][Lpitch] per pass, Lpitch = (r_w + 63) / 64 * 64 + 64, Lrows = (r_h + 7) / 8 * 8 + 8; out = NULL: only
