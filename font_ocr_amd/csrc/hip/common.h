@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
@@ -138,7 +139,7 @@ __host__ __device__ inline uint32_t row_of_key(uint64_t key, const RowHist &h) {
     return (((line >> h.by) - h.page_base) * h.r_h + (line & ((1u << h.by) - 1u))) * h.n_seg + (x >> h.seg_shift);
 }
 
-// Size estimates of one setup (focr_ctx::est_sig: bank, device, geometry, threshold, cap, mode) for its next scan (ctx.hip: focr_scan,
+// Size estimates of one setup (focr_ctx::est_sig: bank, device, geometry, threshold, cap, mode) for its next scan (results.hip: focr_scan,
 // finish_results).  Bounds only: a count above its bound redoes the batch with exact sizes.
 struct SizeEstimate {
     size_t cand = 0, hits = 0;  // bounds of the next scan: the last counts + margin() (0: none, exact sizes)
@@ -149,8 +150,8 @@ struct SizeEstimate {
     void reset() { *this = SizeEstimate{}; }
     double margin() const { return std::min(0.2, std::max(0.04, 3.0 * var)); }  // 4 .. 20 %
     uint64_t row_bound() const { return (uint64_t)row_max + row_max / 4 + 16; }   // the next scan's largest row: the last + 25 %
-    void update(const focr_ctx *c, uint64_t n_cand, uint64_t n_hits);  // a finished batch's counts (and its largest row bucket)
-    void adopt(uint64_t sig);  // shared with the other contexts of the process that scan the same setup (ctx.hip: g_est)
+    void update(const focr_ctx *c, uint64_t n_cand, uint64_t n_hits, uint64_t largest_row);  // a finished batch's counts and its largest row bucket
+    void adopt(uint64_t sig);  // shared with the other contexts of the process that scan the same setup (results.hip: g_est)
     void publish(uint64_t sig) const;
     static void forget(uint64_t sig);
 };
@@ -161,7 +162,41 @@ struct SizeEstimate {
 // apart, all zeroed with the counters by the clear launch at the start of a scan (ClearList).
 constexpr uint32_t COUNTER_WORDS = 64, QUEUE_XCDS = 8, QUEUE_STRIDE = 32, MAX_SCAN_QUEUES = 128;
 constexpr uint32_t TAIL_DONE_WORD = 56, ORDER_DONE_WORD = 57;  // d_counter words: workgroups of the verify / of unit_prefix that have finished ("last workgroup" work)
+constexpr uint32_t LIVE_WORD0 = 8, LIVE_WORDS = 40;  // d_counter words: the live M-tile count of each super-class's pass (written by pass_stats, read by its scan launches; h_live is their pinned copy)
+static_assert(LIVE_WORD0 + LIVE_WORDS <= TAIL_DONE_WORD && ORDER_DONE_WORD < COUNTER_WORDS, "d_counter's named words overlap");
 constexpr size_t COUNTER_BYTES = (COUNTER_WORDS + (size_t)MAX_SCAN_QUEUES * QUEUE_XCDS * QUEUE_STRIDE) * sizeof(uint32_t);
+
+// ---- the result block -------------------------------------------------------
+// The sizes and flags of a scan and its process_hits: one block on the device (focr_ctx::d_res) and its pinned host copy (h_res, filled
+// by the copy behind record_scan_sizes and read by finish_results once the batch is done).  Kernels take a pointer to one field.  The
+// scan's clear launch zeroes everything in front of host_hits.
+struct ResultBlock {
+    uint64_t candidates;   // written: record_scan_sizes (order.hip; MFMA scans only).  Read: finish_results
+    uint64_t hits;         // written: record_scan_sizes.  Read: finish_results
+    uint64_t matches;      // hits that survive their call's cap.  Written: record_scan_sizes.  Read: finish_results
+    uint64_t lines_chars;  // lines << 32 | chars.  Written: focr_process_hits, into the HOST copy only (the row scan's grand total).  Read: finish_results
+    uint64_t flags;        // RES_FLAG_*.  Written: record_scan_sizes, row_sort_kernel (rows.hip), verify_candidate (mfma_common.h).  Read: finish_results
+    uint64_t row_max;      // largest row bucket.  Written: the row prefix (rows.hip: the verify's last workgroup, or row_prefix_kernel).  Read: row_tail (exact sizes), finish_results for SizeEstimate::update
+    uint64_t tail_hits;    // hits the row tail's verify counted.  Written: the same prefix.  Read: row_tail (exact sizes); as d_n_hits by every kernel behind it
+    uint64_t host_hits;    // a hit count the HOST knows (direct scan, split batch, debug hits).  Written: install_host_hits.  Read: as d_n_hits by the ordering and process_hits
+};
+// record_scan_sizes addresses the block as eight words
+enum ResSlot : uint32_t { RES_CANDIDATES, RES_HITS, RES_MATCHES, RES_LINES_CHARS, RES_FLAGS, RES_ROW_MAX, RES_TAIL_HITS, RES_HOST_HITS, RES_SLOTS };
+static_assert(sizeof(ResultBlock) == 64 && sizeof(ResultBlock) == RES_SLOTS * sizeof(uint64_t), "the result block is eight words");
+static_assert(offsetof(ResultBlock, candidates) == 8 * RES_CANDIDATES && offsetof(ResultBlock, hits) == 8 * RES_HITS && offsetof(ResultBlock, matches) == 8 * RES_MATCHES &&
+                  offsetof(ResultBlock, lines_chars) == 8 * RES_LINES_CHARS && offsetof(ResultBlock, flags) == 8 * RES_FLAGS && offsetof(ResultBlock, row_max) == 8 * RES_ROW_MAX &&
+                  offsetof(ResultBlock, tail_hits) == 8 * RES_TAIL_HITS && offsetof(ResultBlock, host_hits) == 8 * RES_HOST_HITS,
+              "the result block's layout is shared by host code and kernels");
+constexpr unsigned long long RES_FLAG_COUNT = 1;  // a count above the bound its phase ran with (estimated sizes): the batch is redone with exact sizes
+constexpr unsigned long long RES_FLAG_ROW = 2;    // a row bucket above the row kernel's capacity: redone likewise
+constexpr unsigned long long RES_FLAG_KEY = 4;    // a candidate key outside the batch reached the verify: internal error
+
+// focr_ctx::ev, ::ms and ::counters, numbered as include/focr_ncc.h documents them (focr_debug_phase_stamps [0..6], focr_last_timings,
+// focr_last_counters)
+enum PhaseEvent { EV_STATS_BEGIN, EV_STATS_END, EV_SCAN_END, EV_VERIFY_END, EV_ORDER_END, EV_POST_BEGIN, EV_POST_END, N_PHASE_EVENTS };
+enum TimingSlot { MS_STATS, MS_SCAN, MS_VERIFY, MS_ORDER, MS_POST, MS_TOTAL, N_TIMINGS };
+enum CounterSlot { CNT_CANDIDATES, CNT_HITS, CNT_ALG_MACS, CNT_ISSUED_MACS, N_COUNTERS };
+static_assert(N_PHASE_EVENTS + 2 == 9 && N_TIMINGS == 6 && N_COUNTERS == 4, "focr_debug_phase_stamps (the events + the dominant launch's two), focr_last_timings and focr_last_counters fill arrays of 9, 6 and 4");
 
 struct focr_ctx {
     int device = -1;
@@ -206,18 +241,18 @@ struct focr_ctx {
     std::vector<focr::SuperClass> supers;
     bool column_drop = true;                    // bound the last column of 9- / 13-wide classes instead of multiplying it (takes effect at the next bank upload)
     std::vector<uint32_t> mfma_slot;            // per class-ordered template: its slot inside its class's N-tiles (tile = slot / 16)
-    // ---- result sizes (ctx.hip: finish_results) ----
+    // ---- result sizes (results.hip: finish_results) ----
     // Every phase after the scan kernel takes its element count from device memory; the host only supplies upper bounds for
     // grids and buffers.  Exact mode reads the counts between the phases (as round 1 did); estimated mode (same bank,
     // geometry, threshold, cap as the previous scan) bounds them by the previous scan's counts + a margin (4 .. 20 %), launches everything
     // without waiting, and reads all sizes once at the end; a count above its bound redoes the batch in exact mode.
-    focr::DevArray<uint64_t> d_res;  // 8 values: [0] candidates [1] hits [2] matches [3] lines << 32 | chars [4] overflow flag [7] scratch count
-    uint64_t *h_res = nullptr;   // pinned copy
-    uint32_t *h_live = nullptr;  // pinned copy of the live M-tile counts (d_counter + 8 ..), 40 entries
+    focr::DevArray<ResultBlock> d_res;  // one block (above)
+    ResultBlock *h_res = nullptr;  // pinned copy
+    uint32_t *h_live = nullptr;    // pinned copy of the live M-tile counts (d_counter words LIVE_WORD0 ..), LIVE_WORDS entries
     const uint64_t *d_n_hits = nullptr;  // view, not an owner: the device-side number of hits of the last scan (in d_res, or in scan_pos)
     size_t ub_hits = 0;                  // the bound its buffers were sized for
     uint64_t n_hits_raw_u64 = 0;
-    bool sizes_pending = false, post_pending = false, estimated = false, estimates_enabled = true;
+    bool estimated = false, estimates_enabled = true;
     focr::SizeEstimate est;
     size_t ub_cand = 0;
     uint64_t est_sig = 0, bank_gen = 0, bank_hash = 0, counters_redone = 0;
@@ -225,22 +260,15 @@ struct focr_ctx {
     int scan_mode = 0;
     int32_t post_overlap = 0;
     bool force_split = false;                   // tests: take scan_split without waiting for an overflow (focr_debug_force_split)
-    bool debug_hits = false;                    // tests: the hits came from focr_debug_process_hits, no per-call lists stand behind them
-    bool cand_intact = false;                   // tests: d_cand still holds the last MFMA scan's candidates as the scan kernels left them (focr_debug_candidates)
     int dbg_stats_form = 0;  // tests / A-B: 1 = the LDS-tiled statistics kernel for every class (focr_debug_set_stats_form; 0: the register form where it applies)
     uint32_t dbg_grid_num = 0, dbg_grid_den = 0;  // tests: the tail's persistent kernels on num / den times their workgroups (focr_debug_set_tail_grid; 0: as designed)
-    // tests: what the last scan's tail chose (focr_debug_tail_path; host bookkeeping, written by launch_scan_mfma, row_tail, rows2_verify and
-    // the ordering pass): the values of FOCR_TAIL_* / FOCR_ORDER_* / FOCR_VERIFY_FORM_* in include/focr_ncc.h
-    struct TailPath {
-        uint32_t tail = 0, big_launch = 0, library_sort = 0, order_form = 0, seg_shift = 0, n_seg = 0, verify_form = 0, verify_chunks = 0;
-    } tail_path;
     int prefilter = 0;                          // FOCR_PREFILTER_*: auto / plane kernel / legacy kernel (focr_ctx_set_prefilter)
     focr::DevArray<uint16_t> d_planes;          // threshold planes, int16: [super-class][value][page][Lrows][Lpitch] (mfma_common.h); exact, grow-only
 
     // pages: the resident set the scans read, and the executor's second set (pipe.hip, focr_pipe_prefetch): the NEXT batch of a
     // lane is ingested into `alt`, on the lane's copy stream, while the lane still scans `pages`; the two change places when that
-    // batch starts (pages_alt_swap, ctx.hip)
-    struct PageSet {  // [capacity][rows_alloc][pitch] ink-high u8, zero padded (ctx.hip: page_set_alloc)
+    // batch starts (pages_alt_swap, pages.hip)
+    struct PageSet {  // [capacity][rows_alloc][pitch] ink-high u8, zero padded (pages.hip: page_set_alloc)
         focr::DevArray<uint8_t> u8;
         focr::DevArray<uint8_t> i8;  // the same pages as int8 (ink - 128, i.e. byte ^ 0x80; padding = 0x80): the MFMA prefilter's window operand,
                                      // written at ingest so that the scan kernels need no v_xor per fragment dword
@@ -255,14 +283,12 @@ struct focr_ctx {
     // scan results (every reserve waits for the context's stream first)
     size_t sub_p0 = 0, sub_np = 0;  // page range the scan pipeline is currently working on (normally the whole batch)
     focr::KeyFmt fmt{};
-    bool scanned = false;
     uint32_t cap = FOCR_MAX_MATCHES;
     focr::DevArray<uint64_t> d_hit_keys, d_hit_keys_alt;  // the four hit arrays have one length (reserve_hits, scan_direct.hip)
     focr::DevArray<float> d_hit_sims, d_hit_sims_alt;
-    focr::DevArray<uint32_t> d_counter;  // COUNTER_BYTES: u64 [0] hits, u64 [1] candidates, u32 [8..47] live M-tile counts, then the scan kernels' item queues
+    focr::DevArray<uint32_t> d_counter;  // COUNTER_BYTES: u64 [0] hits, u64 [1] candidates, u32 [LIVE_WORD0 ..] live M-tile counts, then the scan kernels' item queues
     uint32_t scan_queues_used = 0;  // item queues handed out since the last reset (launch_scan_mfma)
     focr::DevArray<uint64_t> d_cand, d_cand_alt;
-    bool ordered = false;  // the scan path already ran the ordering pass (MFMA path); order_hits is skipped
     focr::DevArray<int32_t> d_L;  // prefilter thresholds [class][page][r_h][pitchL]
     focr::DevArray<uint8_t> d_sort_tmp;  // rocPRIM's temporary storage
     size_t n_hits_raw = 0;    // hits before the cap
@@ -271,14 +297,6 @@ struct focr_ctx {
     focr::DevArray<uint64_t> d_seg_start;   // [n_pages*T] start in the sorted arrays
     focr::DevArray<uint64_t> d_seg_offset;  // [n_pages*T + 1] CSR offsets of the capped lists
     focr::DevArray<focr_match_t> d_matches;  // capped, ordered by (page, template, y, x); Grow::eighth
-    // order.hip's counting form writes d_matches on demand (materialise_matches): pending = nobody has read the last scan's lists yet;
-    // the rest is the geometry of the tables the ordering left in ord_v / ord_k2 (pages of the scan, unit capacity, the unit kernels' grid)
-    struct LazyMatches {
-        bool pending = false;
-        uint32_t n_pages = 0;
-        size_t max_units = 0;
-        unsigned blocks = 0;
-    } lazy;
     // views, not owners: all hits (before the cap) in process_hits order (page, y, x, t), in the hit arrays or in acc_hkeys / acc_hsims
     uint64_t *d_hkeys = nullptr;
     float *d_hsims = nullptr;
@@ -308,8 +326,6 @@ struct focr_ctx {
     focr::DevArray<uint8_t> post_keep;
     focr::DevArray<uint64_t> post_packed, post_scanned, post_page_off, post_line_off;
     focr::DevArray<focr_hit_t> post_chars;
-    bool lines_on_host = false;
-    bool processed = false;
     size_t n_chars = 0, n_lines = 0;
     std::vector<uint64_t> h_page_line_off, h_line_char_off;
     std::vector<focr_hit_t> h_chars;
@@ -324,10 +340,52 @@ struct focr_ctx {
 
     // focr_get_runners (post.hip): one record per character of the last process_hits, written by the first call after it
     focr::DevArray<focr_runner_t> post_runners;  // post_chars' bound, Grow::quarter; used on io_stream only, idle between two calls
-    bool runners_valid = false;                  // the records belong to the last focr_process_hits
     hipEvent_t run_ev[2] = {};
     float run_ms = 0.f;
     uint32_t run_launches = 0;
+
+    // ---- validity of the results: every flag that says what of the last scan / process_hits still stands, and the four transitions
+    // that withdraw results as a whole.  Elsewhere a flag changes only where the pipeline produces or consumes what it describes
+    // (finish_results reads the pending sizes, materialise_matches writes the pending lists, a split batch leaves d_cand incomplete).
+    bool scanned = false;        // a scan's results (or debug hits) stand: focr_scan, focr_debug_process_hits
+    bool processed = false;      // ... and a focr_process_hits of them
+    bool sizes_pending = false;  // the scan's sizes are still to be read from h_res (finish_results)
+    bool post_pending = false;   // ... and those of its process_hits
+    bool debug_hits = false;     // tests: the hits came from focr_debug_process_hits, no per-call lists stand behind them
+    bool cand_intact = false;    // tests: d_cand still holds the last MFMA scan's candidates as the scan kernels left them (focr_debug_candidates)
+    bool ordered = false;        // the scan path already ran the ordering pass (MFMA path); order_hits is skipped
+    bool lines_on_host = false;  // h_page_line_off / h_line_char_off / h_chars hold the last process_hits' lines (fetch_lines, post.hip)
+    bool runners_valid = false;  // post_runners' records belong to the last focr_process_hits
+    // order.hip's counting form writes d_matches on demand (materialise_matches): pending = nobody has read the last scan's lists yet;
+    // the rest is the geometry of the tables the ordering left in ord_v / ord_k2 (pages of the scan, unit capacity, the unit kernels' grid)
+    struct LazyMatches {
+        bool pending = false;
+        uint32_t n_pages = 0;
+        size_t max_units = 0;
+        unsigned blocks = 0;
+    } lazy;
+    // tests: what the last scan's tail chose (focr_debug_tail_path; host bookkeeping, written by launch_scan_mfma, row_tail, rows2_verify and
+    // the ordering pass): the values of FOCR_TAIL_* / FOCR_ORDER_* / FOCR_VERIFY_FORM_* in include/focr_ncc.h
+    struct TailPath {
+        uint32_t tail = 0, big_launch = 0, library_sort = 0, order_form = 0, seg_shift = 0, n_seg = 0, verify_form = 0, verify_chunks = 0;
+    } tail_path;
+    void sub_run_starts() {  // the pipeline starts on a page range (scan_now's run): what the previous range left behind is not this one's
+        ordered = lazy.pending = false;
+        tail_path = {};
+    }
+    void results_gone() {  // the bank or the pages changed, or a new scan starts: nothing stands
+        scanned = processed = sizes_pending = post_pending = debug_hits = cand_intact = lines_on_host = runners_valid = false;
+        sub_run_starts();
+    }
+    void post_starts() {  // focr_process_hits: the previous call's lines and runners are replaced
+        processed = lines_on_host = runners_valid = false;
+        n_chars = n_lines = 0;
+    }
+    void debug_hits_installed() {  // the caller's hits stand in for a scan's; the last scan's tail_path stays readable, as it always did
+        sizes_pending = post_pending = processed = lines_on_host = runners_valid = cand_intact = lazy.pending = false;
+        scanned = debug_hits = true;
+    }
+    // ---- end of validity ----
 
     template <typename T>
     bool scratch(focr::DevArray<T> &a, size_t want) {  // grow-only scratch: Grow::quarter, behind the context's stream
@@ -337,16 +395,18 @@ struct focr_ctx {
     template <typename T>
     int upload(focr::DevArray<T> &a, const T *src, size_t n, size_t at_least = 0);  // a bank array from host memory (ctx.hip: fail() on error)
 
-    hipEvent_t ev[8] = {};
-    float ms[6] = {};
-    uint64_t counters[4] = {};
+    hipEvent_t ev[N_PHASE_EVENTS] = {};  // PhaseEvent
+    float ms[N_TIMINGS] = {};            // TimingSlot
+    uint64_t counters[N_COUNTERS] = {};  // CounterSlot
 
     // per-launch timing of the scan kernels (focr_last_launches)
-    std::vector<focr_launch_info_t> launches;
-    std::vector<hipEvent_t> launch_events;  // pool, two per launch
-    void launch_begin(const char *name, uint32_t n_templates, uint64_t alg, uint64_t issued);
+    static constexpr uint32_t NO_SUPER = 0xffffffffu;
+    std::vector<focr_launch_info_t> launches;  // the public records, as focr_last_launches copies them out
+    std::vector<uint32_t> launch_super;        // beside them: the super-class whose live M-tile count scales the launch's issued_macs (NO_SUPER: none)
+    std::vector<hipEvent_t> launch_events;     // pool, two per launch
+    void launch_begin(const char *name, uint32_t n_templates, uint64_t alg, uint64_t issued, uint32_t super_index = NO_SUPER);
     void launch_end();
-    void launches_reset() { launches.clear(); }
+    void launches_reset() { launches.clear(), launch_super.clear(); }
     void launches_collect();  // after a stream sync: fill ms
 };
 
@@ -404,13 +464,17 @@ int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t
 int order_hits(focr_ctx *ctx);  // direct path: unordered hits in d_hit_keys / d_hit_sims -> everything below
 int materialise_matches(focr_ctx *c, hipStream_t s);  // d_matches of the last scan, if still to be written, on stream s (after finish_results)
 // ctx.hip
-int finish_results(focr_ctx *c);  // wait for the stream once and read the result sizes of the last scan / process_hits
 void bank_host_prepare(focr_ctx *c, const focr_template_t *templates, size_t n_templates, const uint8_t *needles,
                        std::vector<uint32_t> &direct, std::vector<uint8_t> &dense);
-int pages_alt_ingest(focr_ctx *c, const void *d_luma, size_t n_pages, size_t r_w, size_t r_h, int invert, hipStream_t s);
-int pages_alt_swap(focr_ctx *c, size_t n_pages, size_t r_w, size_t r_h);
 void ctx_share_stream(focr_ctx *c, hipStream_t lane_stream, hipStream_t io_stream);  // the context joins an executor's lane
 int wait_batch(focr_ctx *c);  // until the context's queued work is done (its batch's event inside an executor, else its stream)
+// pages.hip
+int pages_alt_ingest(focr_ctx *c, const void *d_luma, size_t n_pages, size_t r_w, size_t r_h, int invert, hipStream_t s);
+int pages_alt_swap(focr_ctx *c, size_t n_pages, size_t r_w, size_t r_h);
+// results.hip
+int finish_results(focr_ctx *c);  // wait for the stream once and read the result sizes of the last scan / process_hits
+int install_host_hits(focr_ctx *c, uint64_t n);  // n, a count the host knows, becomes the device-side hit count (d_n_hits, ub_hits): a copy queued on the context's stream
+void phase_origin_record(int device, hipStream_t s);  // the device's first context stamps the origin of focr_debug_phase_stamps
 // post.hip
 bool post_queue_chars_copy(focr_ctx *c, void *dst, size_t dst_bytes);  // the batch's characters to a device buffer, queued on the context's stream
 

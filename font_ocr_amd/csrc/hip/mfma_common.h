@@ -272,7 +272,7 @@ struct VerifyArgs {
     double thr_d;
     const struct VerifyMeta *vmeta;           // by global template index (the row tail's verify stages it in LDS)
     uint32_t n_templates, n_pages, r_w, r_h;  // bounds of a well-formed key
-    unsigned long long *flags_word;           // d_res[4]: bit 2 = a key outside those bounds was met (internal error, never a fault)
+    unsigned long long *flags_word;           // the result block's flags: RES_FLAG_KEY = a key outside those bounds was met (internal error, never a fault)
 };
 VerifyArgs verify_args(const focr_ctx *c, double thr_d);  // scan_mfma.hip
 // LDS: the whole of needles16 is staged in LDS at `lds` (rows.hip, verify_list_kernel) — a compile-time choice, so that every
@@ -281,7 +281,7 @@ template <bool LDS>
 __device__ __forceinline__ bool verify_candidate_t(uint64_t key, const VerifyArgs &va, const v4i *lds, float *sim_out) {
     const uint32_t page = va.fmt.page(key), t = va.fmt.t(key), x = va.fmt.x(key), y = va.fmt.y(key);
     if (t >= va.n_templates || page >= va.n_pages || x >= va.r_w || y >= va.r_h) {  // cannot happen; would otherwise be a wild read
-        atomicOr(va.flags_word, 4ull);
+        atomicOr(va.flags_word, RES_FLAG_KEY);
         *sim_out = 0.f;
         return false;
     }
@@ -325,7 +325,7 @@ template <bool LDS>
 __device__ __forceinline__ bool verify_candidate_meta(uint64_t key, const VerifyArgs &va, const v4i *lds, const VerifyMeta *meta, float *sim_out) {
     const uint32_t page = va.fmt.page(key), t = va.fmt.t(key), x = va.fmt.x(key), y = va.fmt.y(key);
     if (t >= va.n_templates || page >= va.n_pages || x >= va.r_w || y >= va.r_h) {  // cannot happen; would otherwise be a wild read
-        atomicOr(va.flags_word, 4ull);
+        atomicOr(va.flags_word, RES_FLAG_KEY);
         *sim_out = 0.f;
         return false;
     }
@@ -377,7 +377,7 @@ typedef v3i v3i_b1 __attribute__((aligned(1)));
 __device__ __forceinline__ bool verify_candidate_narrow(uint64_t key, const VerifyArgs &va, const uint32_t *lds_rows, const VerifyMeta *meta, float *sim_out) {
     const uint32_t page = va.fmt.page(key), t = va.fmt.t(key), x = va.fmt.x(key), y = va.fmt.y(key);
     if (t >= va.n_templates || page >= va.n_pages || x >= va.r_w || y >= va.r_h) {  // cannot happen; would otherwise be a wild read
-        atomicOr(va.flags_word, 4ull);
+        atomicOr(va.flags_word, RES_FLAG_KEY);
         *sim_out = 0.f;
         return false;
     }

@@ -157,13 +157,13 @@ __global__ void emit_matches(const uint64_t *__restrict__ k2, const float *__res
 }
 
 // result sizes of a scan -> the context's device result block (copied to pinned host memory at the end of the scan):
-// res[0] candidates, res[1] hits, res[2] matches after the cap, res[4] |= 1 if a count exceeded the bound its phase ran with
+// candidates, hits, matches after the cap, and RES_FLAG_COUNT if a count exceeded the bound its phase ran with (res: the block as words, ResSlot)
 __global__ void record_scan_sizes(const unsigned long long *__restrict__ n_cand_p, uint64_t ub_c, const uint64_t *__restrict__ n_hits_p,
                                   uint64_t ub_h, const uint64_t *__restrict__ total_p, uint64_t *__restrict__ res) {
-    if (n_cand_p) res[0] = *n_cand_p;
-    res[1] = *n_hits_p;
-    res[2] = *total_p;
-    if ((n_cand_p && *n_cand_p > ub_c) || *n_hits_p > ub_h) res[4] |= 1;
+    if (n_cand_p) res[RES_CANDIDATES] = *n_cand_p;
+    res[RES_HITS] = *n_hits_p;
+    res[RES_MATCHES] = *total_p;
+    if ((n_cand_p && *n_cand_p > ub_c) || *n_hits_p > ub_h) res[RES_FLAGS] |= RES_FLAG_COUNT;
 }
 
 // The per-call arrays for n_seg (page, template) calls and the match list for `ub` hits (matches <= hits)
@@ -213,10 +213,10 @@ static int order_sorted_hits_sort(focr_ctx *c, uint64_t *hkeys, float *hsims, co
                            c->d_seg_start, c->d_seg_offset, c->d_matches, keep);
         FOCR_HIP(c, hipGetLastError());
     }
-    hipLaunchKernelGGL(record_scan_sizes, dim3(1), dim3(1), 0, c->stream, n_cand_p, (uint64_t)ub_c, n_p, (uint64_t)ub, c->d_seg_offset + n_seg, c->d_res);
+    hipLaunchKernelGGL(record_scan_sizes, dim3(1), dim3(1), 0, c->stream, n_cand_p, (uint64_t)ub_c, n_p, (uint64_t)ub, c->d_seg_offset + n_seg, c->d_res.as<uint64_t>());
     FOCR_HIP(c, hipGetLastError());
-    FOCR_HIP(c, hipMemcpyAsync(c->h_res, c->d_res, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    FOCR_HIP(c, hipEventRecord(c->ev[4], c->stream));
+    FOCR_HIP(c, hipMemcpyAsync(c->h_res, c->d_res, sizeof(ResultBlock), hipMemcpyDeviceToHost, c->stream));
+    FOCR_HIP(c, hipEventRecord(c->ev[EV_ORDER_END], c->stream));
     c->d_n_hits = n_p;
     c->ub_hits = ub;
     c->ordered = true;
@@ -522,10 +522,10 @@ int order_sorted_hits(focr_ctx *c, uint64_t *hkeys, float *hsims, const uint64_t
     FOCR_HIP(c, hipGetLastError());
     c->tail_path.order_form = FOCR_ORDER_COUNTING;
     c->lazy = {true, n_pages, max_units, unit_blocks};  // d_matches: written by whoever reads it first (materialise_matches)
-    hipLaunchKernelGGL(record_scan_sizes, dim3(1), dim3(1), 0, c->stream, n_cand_p, (uint64_t)ub_c, n_p, (uint64_t)ub, c->d_seg_offset + n_seg, c->d_res);
+    hipLaunchKernelGGL(record_scan_sizes, dim3(1), dim3(1), 0, c->stream, n_cand_p, (uint64_t)ub_c, n_p, (uint64_t)ub, c->d_seg_offset + n_seg, c->d_res.as<uint64_t>());
     FOCR_HIP(c, hipGetLastError());
-    FOCR_HIP(c, hipMemcpyAsync(c->h_res, c->d_res, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    FOCR_HIP(c, hipEventRecord(c->ev[4], c->stream));
+    FOCR_HIP(c, hipMemcpyAsync(c->h_res, c->d_res, sizeof(ResultBlock), hipMemcpyDeviceToHost, c->stream));
+    FOCR_HIP(c, hipEventRecord(c->ev[EV_ORDER_END], c->stream));
     c->d_n_hits = n_p;
     c->ub_hits = ub;
     c->ordered = true;
@@ -553,10 +553,8 @@ int order_hits(focr_ctx *c) {
     int rc;
     if ((rc = sort_pairs_u64_f32(c, c->d_hit_keys, c->d_hit_keys_alt, c->d_hit_sims, c->d_hit_sims_alt, n, c->fmt.bits()))) return rc;
     // the count as a device-side value for the shared kernels
-    uint64_t *cnt = c->d_res + 7;
-    c->n_hits_raw_u64 = n;
-    FOCR_HIP(c, hipMemcpyAsync(cnt, &c->n_hits_raw_u64, 8, hipMemcpyHostToDevice, c->stream));
-    return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims, cnt, n, nullptr, 0);
+    if ((rc = install_host_hits(c, n))) return rc;
+    return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims, c->d_n_hits, n, nullptr, 0);
 }
 
 }  // namespace focr

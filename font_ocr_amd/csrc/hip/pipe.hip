@@ -80,7 +80,7 @@ struct PipeSlot {
     bool fetched = false;
     bool chars_queued = false;  // the copy into job.chars_out was queued behind process_hits on the lane's stream (no copy at completion)
     // focr_pipe_prefetch: the slot's NEXT batch crosses PCIe into the lane's staging buffer and is ingested into the context's
-    // ALTERNATE page set (pages_alt_ingest, ctx.hip), both on the lane's copy stream, under the batches in flight; when the
+    // ALTERNATE page set (pages_alt_ingest, pages.hip), both on the lane's copy stream, under the batches in flight; when the
     // announced batch is queued, the context's two page sets change places
     hipEvent_t ev_prefetch = nullptr;  // copy + ingest done
     const void *pf_ptr = nullptr;      // host pages announced and on their way (consumed when the batch that brings the same pointer is queued)
@@ -267,9 +267,9 @@ static int complete(focr_pipe *P, PipeSlot *S, uint64_t t, std::unique_lock<std:
         R.n_matches = focr_total_matches(c);
         R.n_lines = job.post ? focr_total_lines(c) : 0;
         R.n_chars = job.post ? focr_total_chars(c) : 0;
-        float ms[6] = {0};
+        float ms[N_TIMINGS] = {0};
         focr_last_timings(c, ms);
-        R.device_ms = ms[5] + ms[4];
+        R.device_ms = ms[MS_TOTAL] + ms[MS_POST];
         uint32_t *hc = (uint32_t *)S->h_counts.ensure(R.n_pages * R.n_templates * 4 + 16);
         uint64_t *hp = (uint64_t *)S->h_page_off.ensure((R.n_pages + 1) * 8);
         uint64_t *hl = (uint64_t *)S->h_line_off.ensure((R.n_lines + 1) * 8);

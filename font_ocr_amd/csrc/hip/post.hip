@@ -288,22 +288,19 @@ int focr_process_hits(focr_ctx_t *c, float anchor_threshold, int32_t overlap) {
     if (!c) return FOCR_ERR_INVALID;
     if (!c->scanned) return fail(c, FOCR_ERR_STATE, "focr_process_hits: no scan results");
     FOCR_HIP(c, hipSetDevice(c->device));
-    c->processed = false;
-    c->lines_on_host = false;
-    c->runners_valid = false;
+    c->post_starts();
     c->post_anchor = anchor_threshold;
     c->post_overlap = overlap;
-    c->n_chars = c->n_lines = 0;
     // all hits in (page, y, x, t) order; d_keep marks the ones that survive their call's cap.  Their number lives on the
     // device (c->d_n_hits); `ub` is what the scan sized its buffers for (the exact count unless the scan ran on estimates)
     const size_t ub = c->ub_hits, n_pages = c->n_pages;
     if (!c->sizes_pending && (c->n_hits == 0 || c->n_matches == 0)) {  // the reference panics on an empty hit list (src/ncc.rs:1040); we return zero lines
         c->processed = true;
-        c->ms[4] = 0.f;
+        c->ms[MS_POST] = 0.f;
         return FOCR_OK;
     }
     if (ub >= 0xffffffffull) return fail(c, FOCR_ERR_OVERFLOW, "focr_process_hits: more than 2^32 hits in one batch");
-    FOCR_HIP(c, hipEventRecord(c->ev[5], c->stream));
+    FOCR_HIP(c, hipEventRecord(c->ev[EV_POST_BEGIN], c->stream));
     // grow-only device scratch (no allocation in the steady state); outputs are sized by their bounds: characters <= hits,
     // lines <= page rows
     const size_t n_rows_total = n_pages * c->pages.r_h;
@@ -332,14 +329,14 @@ int focr_process_hits(focr_ctx_t *c, float anchor_threshold, int32_t overlap) {
     int rc;
     if ((rc = exclusive_scan_u64(c, packed, scanned, n_rows_total + 1))) return rc;
     // packed[n_rows_total] = 0, so the scan's last entry is the grand total (lines << 32 | characters): into the result block
-    FOCR_HIP(c, hipMemcpyAsync(c->h_res + 3, scanned + n_rows_total, 8, hipMemcpyDeviceToHost, c->stream));
+    FOCR_HIP(c, hipMemcpyAsync(&c->h_res->lines_chars, scanned + n_rows_total, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (ub)
         hipLaunchKernelGGL(emit_chars, dim3(nb), dim3(256), 0, c->stream, c->d_hkeys, c->d_hsims, c->d_n_hits, (uint64_t)ub, c->fmt, (uint32_t)c->pages.r_h,
                            keep_row, line_b, choice, packed, scanned, c->bank.d_t_w, c->bank.d_t_h, c->bank.d_t_letter, d_line_off, d_chars);
     hipLaunchKernelGGL(page_offsets, dim3((unsigned)((n_pages + 1 + 255) / 256)), dim3(256), 0, c->stream, scanned, (uint32_t)c->pages.r_h,
                        (uint32_t)n_pages, d_page_off);
     FOCR_HIP(c, hipGetLastError());
-    FOCR_HIP(c, hipEventRecord(c->ev[6], c->stream));
+    FOCR_HIP(c, hipEventRecord(c->ev[EV_POST_END], c->stream));
     c->post_pending = true;
     c->processed = true;
     if (!c->sizes_pending) return finish_results(c);  // exact sizes: complete now, as the call always did
@@ -449,7 +446,7 @@ int focr_last_runners(focr_ctx_t *c, float *ms, uint32_t *launches) {
 }
 
 // Test hook: the caller's hits where a scan leaves them for focr_process_hits — keys packed with the batch's KeyFmt, similarities
-// and keep flags in the buffers a split scan installs (scan_split, ctx.hip), the count on the device in d_res[7].
+// and keep flags in the buffers a split scan installs (scan_split, results.hip), the count on the device in the result block's host_hits.
 int focr_debug_process_hits(focr_ctx_t *c, const uint32_t *page, const uint32_t *y, const uint32_t *x, const uint32_t *t,
                             const float *similarity, const uint8_t *keep, size_t n) {
     if (!c) return FOCR_ERR_INVALID;
@@ -476,27 +473,22 @@ int focr_debug_process_hits(focr_ctx_t *c, const uint32_t *page, const uint32_t 
     uint64_t *d_keys = c->acc_hkeys;
     float *d_sims = c->acc_hsims;
     uint8_t *d_keep = c->ord_keep;
-    c->n_hits_raw_u64 = n;
     if (n) {
         FOCR_HIP(c, hipMemcpyAsync(d_keys, keys.data(), n * 8, hipMemcpyHostToDevice, c->stream));
         FOCR_HIP(c, hipMemcpyAsync(d_sims, similarity, n * 4, hipMemcpyHostToDevice, c->stream));
         FOCR_HIP(c, hipMemcpyAsync(d_keep, kept.data(), n, hipMemcpyHostToDevice, c->stream));
     }
-    FOCR_HIP(c, hipMemcpyAsync(c->d_res + 7, &c->n_hits_raw_u64, 8, hipMemcpyHostToDevice, c->stream));
+    if (int rc = install_host_hits(c, n)) return rc;
     FOCR_HIP(c, hipStreamSynchronize(c->stream));
     c->fmt = fmt;
     c->d_hkeys = d_keys;
     c->d_hsims = d_sims;
-    c->d_n_hits = c->d_res + 7;
-    c->ub_hits = n;
     c->n_hits = c->n_hits_raw = n;
     c->n_matches = n_kept;
     c->sub_p0 = 0;
     c->sub_np = c->n_pages;
-    c->sizes_pending = c->post_pending = c->estimated = false;
-    c->processed = c->lines_on_host = c->runners_valid = false;
-    c->scanned = c->debug_hits = true;
-    c->lazy.pending = false;  // no per-call lists stand behind these hits
+    c->estimated = false;
+    c->debug_hits_installed();  // no per-call lists stand behind these hits
     return FOCR_OK;
 }
 

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(WAVES * 64) void row_sort_kernel(uint32_t n_rows, c
         } else if (n > (uint32_t)CAP) {
             if (lane == 0) {
                 if (LIST || !big) {  // beyond the last capacity class, or no second launch was planned for this batch (estimated sizes): redo
-                    atomicOr(flags_word, 2ull);
+                    atomicOr(flags_word, RES_FLAG_ROW);
                 } else {
                     big[1 + atomicAdd(big, 1u)] = r;  // room for every row
                 }
@@ -479,7 +479,7 @@ __global__ __launch_bounds__(256) void hit_scatter_kernel(const uint64_t *__rest
 // the second, slower launch).  Candidates per row grow with the row's windows x templates: the first scan of a setup takes one
 // segment per <= 2^19 of them (BASELINE configs[1]: 608 x 380 -> one segment, a row or two per batch just above 1024;
 // configs[2]: 1200 x 1520 -> 5 segments of 256 px), later scans halve the segments while the largest bucket stays above 2048
-// (ctx.hip, finish_results: configs[2] settles at 128 px).  The segmentation never changes a result.
+// (results.hip, SizeEstimate::update: configs[2] settles at 128 px).  The segmentation never changes a result.
 void row_segments(const focr_ctx *c, uint32_t *seg_shift, uint32_t *n_seg) {
     uint32_t sh = c->est.seg_shift;
     if (!sh) {
@@ -544,7 +544,7 @@ static int verify_mode(const focr_ctx *c, size_t *lds, uint32_t *rows_out) {
 }
 
 // hits-first tail, phase 1 (right behind the scan kernels): exact verify of the candidate list in flush order, hit counts and
-// slots per bucket, prefix -> d_res[6] = hits, d_res[5] = the largest bucket.  Records ev[3] behind the verify.
+// slots per bucket, prefix -> the result block's tail_hits and row_max (the largest bucket).  Records EV_VERIFY_END behind the verify.
 int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c) {
     const uint32_t n_rows = (uint32_t)row_buckets(c);
     if (!c->scratch(c->scan_pos, (ub_c + 1) * 4) || !c->scratch(c->scan_flags, (ub_c + 1) * 4)) return fail(c, FOCR_ERR_NOMEM, "rows: hipMalloc failed");
@@ -552,7 +552,7 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
     uint32_t *cslots = c->scan_flags.as<uint32_t>();
     const unsigned cus = c->n_cus;
     uint32_t *hits = c->rows_hits, *hbase = c->rows_hbase;
-    const TailWork tw{c->d_counter + TAIL_DONE_WORD, n_rows, hbase, c->d_res + 6, c->d_res + 5};  // the verify's last workgroup does the prefix
+    const TailWork tw{c->d_counter + TAIL_DONE_WORD, n_rows, hbase, &c->d_res.p->tail_hits, &c->d_res.p->row_max};  // the verify's last workgroup does the prefix
     // The verify's workgroups are persistent (they walk the list with the grid's stride), so where the scan kernel is confined to
     // scan_cus CUs — several batches in flight — the verify asks for no more workgroups than fit the CUs the scan leaves free: a
     // verify launched in the gap between two scan launches would otherwise put a workgroup on every CU of the chip and hold it
@@ -639,16 +639,16 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
         c->tail_path.verify_form = mode == 2 ? FOCR_VERIFY_FORM_LDS12 : mode == 1 ? FOCR_VERIFY_FORM_LDS16 : FOCR_VERIFY_FORM_GLOBAL;
     }
 verified:
-    FOCR_HIP(c, hipEventRecord(c->ev[3], c->stream));
+    FOCR_HIP(c, hipEventRecord(c->ev[EV_VERIFY_END], c->stream));
     if (!ub_c) {  // no candidate can exist (nothing was verified): the prefix of all-zero counts, as a launch of its own
-        hipLaunchKernelGGL(row_prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t *)hits, n_rows, hbase, (uint32_t *)nullptr, c->d_res + 6, c->d_res + 5);
+        hipLaunchKernelGGL(row_prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t *)hits, n_rows, hbase, (uint32_t *)nullptr, &c->d_res.p->tail_hits, &c->d_res.p->row_max);
         FOCR_HIP(c, hipGetLastError());
     }
     return FOCR_OK;
 }
 
 // hits-first tail, phase 2: hits to their buckets, every bucket sorted with its similarities -> the dense sorted hits in
-// d_hit_keys / d_hit_sims_alt (their number: d_res[6]).  ub_h: bound on the hits (exact sizes: the count itself).
+// d_hit_keys / d_hit_sims_alt (their number: the result block's tail_hits).  ub_h: bound on the hits (exact sizes: the count itself).
 int rows2_place(focr_ctx *c, const unsigned long long *n_cand_p, size_t ub_c, size_t ub_h, bool big_expected, bool sort) {
     const uint32_t n_rows = (uint32_t)row_buckets(c);
     int rc;
@@ -662,7 +662,7 @@ int rows2_place(focr_ctx *c, const unsigned long long *n_cand_p, size_t ub_c, si
         FOCR_HIP(c, hipGetLastError());
     }
     if (!sort) return FOCR_OK;  // a bucket beyond the row sort's capacity (exact sizes know): the caller sorts the placed hits with the library sort
-    unsigned long long *flags_word = (unsigned long long *)(c->d_res + 4);
+    unsigned long long *flags_word = (unsigned long long *)&c->d_res.p->flags;
     const unsigned row_blocks = tail_grid(c, (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)n_rows + 3) / 4, (size_t)cus * 8)));
     const uint32_t seg_w = 1u << c->row_hist.seg_shift;
     uint32_t xs = 0;

@@ -216,7 +216,7 @@ int launch_scan_tall(focr_ctx *c, size_t k, double thr_d, uint64_t *keys, float 
         default: return fail(c, FOCR_ERR_INVALID, "scan_tall: unsupported size class");
     }
     FOCR_HIP(c, hipGetLastError());
-    c->counters[3] += (uint64_t)(c->pages.r_w - sc.n_w) * (c->pages.r_h - sc.n_h) * sc.ndw * 4 * sc.n_h * sc.n_templates * c->sub_np;
+    c->counters[CNT_ISSUED_MACS] += (uint64_t)(c->pages.r_w - sc.n_w) * (c->pages.r_h - sc.n_h) * sc.ndw * 4 * sc.n_h * sc.n_templates * c->sub_np;
     return FOCR_OK;
 }
 
@@ -254,8 +254,8 @@ int launch_scan_direct(focr_ctx *c, float threshold, int rust) {
     for (int attempt = 0; attempt < 3; attempt++) {
         c->launches_reset();
         FOCR_HIP(c, hipMemsetAsync(c->d_counter, 0, 64 * sizeof(uint32_t), c->stream));
-        FOCR_HIP(c, hipEventRecord(c->ev[0], c->stream));
-        FOCR_HIP(c, hipEventRecord(c->ev[1], c->stream));
+        FOCR_HIP(c, hipEventRecord(c->ev[EV_STATS_BEGIN], c->stream));
+        FOCR_HIP(c, hipEventRecord(c->ev[EV_STATS_END], c->stream));
         for (size_t k = 0; k < c->bank.classes.size(); k++) {
             const SizeClass &sc = c->bank.classes[k];
             if (sc.n_w >= c->pages.r_w || sc.n_h >= c->pages.r_h) continue;  // no window with x,y >= 1 fits
@@ -277,23 +277,23 @@ int launch_scan_direct(focr_ctx *c, float threshold, int rust) {
                 default: return fail(c, FOCR_ERR_INVALID, "scan_direct: unsupported size class");
             }
             FOCR_HIP(c, hipGetLastError());
-            c->counters[3] += (uint64_t)(c->pages.r_w - sc.n_w) * (c->pages.r_h - sc.n_h) * sc.ndw * 4 * sc.maxh * sc.n_templates * c->sub_np;
+            c->counters[CNT_ISSUED_MACS] += (uint64_t)(c->pages.r_w - sc.n_w) * (c->pages.r_h - sc.n_h) * sc.ndw * 4 * sc.maxh * sc.n_templates * c->sub_np;
         }
-        FOCR_HIP(c, hipEventRecord(c->ev[2], c->stream));
-        FOCR_HIP(c, hipEventRecord(c->ev[3], c->stream));
+        FOCR_HIP(c, hipEventRecord(c->ev[EV_SCAN_END], c->stream));
+        FOCR_HIP(c, hipEventRecord(c->ev[EV_VERIFY_END], c->stream));
         unsigned long long n = 0;
         FOCR_HIP(c, hipMemcpyAsync(&n, c->d_counter, 8, hipMemcpyDeviceToHost, c->stream));
         FOCR_HIP(c, hipStreamSynchronize(c->stream));
         c->n_hits_raw = n;
         c->n_cand = n;
         if (n <= c->d_hit_keys.cap) {
-            FOCR_HIP(c, hipEventElapsedTime(&c->ms[1], c->ev[1], c->ev[2]));
-            c->counters[0] = n;
-            c->counters[1] = n;
+            FOCR_HIP(c, hipEventElapsedTime(&c->ms[MS_SCAN], c->ev[EV_STATS_END], c->ev[EV_SCAN_END]));
+            c->counters[CNT_CANDIDATES] = n;
+            c->counters[CNT_HITS] = n;
             c->launches_collect();
             return FOCR_OK;
         }
-        c->counters[3] = 0;
+        c->counters[CNT_ISSUED_MACS] = 0;
         rc = reserve_hits(c, (size_t)n + (size_t)n / 8 + 1024);  // grow and rescan
         if (rc) return rc;
     }

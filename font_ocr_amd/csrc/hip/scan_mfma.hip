@@ -13,7 +13,7 @@
 //     the per-call ranks and the cap.  (verify_kernel below + the library radix sort = the legacy tail, kept as a fallback.)
 //
 // Sizes: every phase behind the scan kernel takes its element count from device memory; exact / estimated mode: see
-// launch_scan_mfma and ctx.hip (finish_results).
+// launch_scan_mfma and results.hip (finish_results).
 //
 // Layout: one operand = windows (fragments straight from the page's int8 copy), the other = the quantised bank staged once per
 // block in LDS in exactly the per-lane order the MFMA wants; the K layouts (how image rows map to 16-byte k-groups) are
@@ -30,7 +30,8 @@ namespace focr {
 // on the previous turn (begin) to the record of its own when it goes out of scope, error returns included; nothing in it waits on the host.
 struct TurnChain {
     std::mutex mu;
-    hipEvent_t ev[8] = {};
+    static constexpr unsigned RING = 8;
+    hipEvent_t ev[RING] = {};
     unsigned n = 0;
 };
 static TurnChain scan_turns[64], stats_turns[64];  // per device: the scan kernels', and the statistics' in front of them
@@ -44,11 +45,11 @@ struct Turn {
     int begin() {
         for (hipEvent_t &e : chain.ev)
             if (!e) FOCR_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (chain.n) FOCR_HIP(c, hipStreamWaitEvent(c->stream, chain.ev[(chain.n - 1) % 8], 0));
+        if (chain.n) FOCR_HIP(c, hipStreamWaitEvent(c->stream, chain.ev[(chain.n - 1) % TurnChain::RING], 0));
         entered = true;
         return FOCR_OK;
     }
-    ~Turn() { if (entered) (void)hipEventRecord(chain.ev[chain.n++ % 8], c->stream); }
+    ~Turn() { if (entered) (void)hipEventRecord(chain.ev[chain.n++ % TurnChain::RING], c->stream); }
 };
 
 // THE decision whether a pass takes the threshold planes: the planes it takes (the kernel is instantiated for 1 / 2 / 4 values), or
@@ -99,7 +100,7 @@ static int plan_scan(focr_ctx *c, bool nothing, size_t want_cand, ScanPlan &P) {
     };
     if (int rc = exact(c->d_cand, want_cand, "cand")) return rc;
     if (nothing) return FOCR_OK;  // no statistics, no scan
-    if (c->supers.size() > 40) return fail(c, FOCR_ERR_INVALID, "scan_mfma: too many super-classes");
+    if (c->supers.size() > LIVE_WORDS) return fail(c, FOCR_ERR_INVALID, "scan_mfma: too many super-classes");
     P.Lpitch = (uint32_t)((c->pages.r_w + 63) / 64 * 64 + 64);
     P.Lrows = (uint32_t)((c->pages.r_h + 7) / 8 * 8 + 8);
     P.L_per_class = c->n_pages * (size_t)P.Lrows * P.Lpitch;
@@ -128,7 +129,7 @@ static int stats_phase(focr_ctx *c, const ScanPlan &P, ClearList &clear, double 
     if (rc || (rc = launch_clear(c, clear))) return rc;
     for (size_t si = 0; si < c->supers.size(); si++)
         if (c->supers[si].mtx && (rc = pass_stats(c, P, si, thr_d))) return rc;
-    FOCR_HIP(c, hipEventRecord(c->ev[1], c->stream));
+    FOCR_HIP(c, hipEventRecord(c->ev[EV_STATS_END], c->stream));
     return FOCR_OK;
 }
 
@@ -157,7 +158,7 @@ static int scan_phase(focr_ctx *c, const ScanPlan &P, double thr_d) {
                 L.mtx = su.mtx;
                 L.n_rows = su.n_rows;
                 L.live_list = P.live_list + su.live_offset;
-                L.live_count = c->d_counter + 8 + si;
+                L.live_count = c->d_counter + LIVE_WORD0 + si;
                 L.super_index = (uint32_t)si;
                 const uint32_t t_limit = std::min(su.n_tiles, t0 + chunk_tiles);
                 uint32_t t1 = t0;
@@ -224,7 +225,7 @@ VerifyArgs verify_args(const focr_ctx *c, double thr_d) {
     return VerifyArgs{c->pages.u8, (uint32_t)c->pages.pitch, (uint32_t)c->pages.rows_alloc, c->fmt, c->bank.d_order_of, c->bank.d_tconst,
                       c->bank.d_needles16.as<const v4i>(), c->bank.d_needle16_row, thr_d, c->bank.d_vmeta.p,
                       (uint32_t)c->n_templates, (uint32_t)c->n_pages,
-                      (uint32_t)c->pages.r_w, (uint32_t)c->pages.r_h, (unsigned long long *)(c->d_res + 4)};
+                      (uint32_t)c->pages.r_w, (uint32_t)c->pages.r_h, (unsigned long long *)&c->d_res.p->flags};
 }
 
 // 3a. hits-first row tail: verify the candidates where they lie, then bucket + sort the hits only (rows.hip)
@@ -235,8 +236,8 @@ static int row_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_
     uint64_t row_max = c->est.row_bound();
     if (!c->estimated) {  // exact number of hits and the largest bucket
         uint64_t hits = 0;
-        FOCR_HIP(c, hipMemcpyAsync(&hits, c->d_res + 6, 8, hipMemcpyDeviceToHost, c->stream));
-        FOCR_HIP(c, hipMemcpyAsync(&row_max, c->d_res + 5, 8, hipMemcpyDeviceToHost, c->stream));
+        FOCR_HIP(c, hipMemcpyAsync(&hits, &c->d_res.p->tail_hits, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        FOCR_HIP(c, hipMemcpyAsync(&row_max, &c->d_res.p->row_max, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         FOCR_HIP(c, hipStreamSynchronize(c->stream));
         ub_h = (size_t)hits;
     }
@@ -250,7 +251,7 @@ static int row_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_
     c->tail_path.n_seg = c->row_hist.n_seg;
     if ((rc = rows2_place(c, n_cand_p, ub_c, ub_h, big_expected, sort_rows))) return rc;
     if (!sort_rows && (rc = sort_pairs_u64_f32(c, c->d_hit_keys, c->d_hit_keys_alt, c->d_hit_sims_alt, c->d_hit_sims, ub_h, c->fmt.bits()))) return rc;
-    return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims_alt, c->d_res + 6, ub_h, n_cand_p, ub_c);
+    return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims_alt, &c->d_res.p->tail_hits, ub_h, n_cand_p, ub_c);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -285,7 +286,7 @@ static int legacy_tail(focr_ctx *c, double thr_d, const unsigned long long *n_ca
     hipLaunchKernelGGL(verify_kernel, dim3((unsigned)((ub_c + 1 + 255) / 256)), dim3(256), 0, c->stream, c->d_cand, n_cand_p, (unsigned long long)ub_c,
                        verify_args(c, thr_d), c->d_hit_sims, flags);
     FOCR_HIP(c, hipGetLastError());
-    FOCR_HIP(c, hipEventRecord(c->ev[3], c->stream));
+    FOCR_HIP(c, hipEventRecord(c->ev[EV_VERIFY_END], c->stream));
     if ((rc = compact_candidates(c, c->d_cand, c->d_hit_sims, flags, pos, n_cand_p, ub_c))) return rc;
     size_t ub_h = std::min(ub_c, c->est.hits);
     if (!c->estimated) {  // exact number of hits for the ordering pass
@@ -309,15 +310,15 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
     for (int attempt = 0; attempt < 4; attempt++) {
         ScanPlan P;
         if ((rc = plan_scan(c, nothing, want_cand, P))) return rc;
-        c->counters[3] = 0;
+        c->counters[CNT_ISSUED_MACS] = 0;
         c->launches_reset();
         ClearList clear{};  // everything the scan needs zeroed: one launch (launch_clear), in front of the first kernel
-        if (!clear.add(c->d_counter, COUNTER_BYTES) || !clear.add(c->d_res, 7 * sizeof(uint64_t)))  // counters + the scan kernels' item queues, result sizes
+        if (!clear.add(c->d_counter, COUNTER_BYTES) || !clear.add(c->d_res, offsetof(ResultBlock, host_hits)))  // counters + the scan kernels' item queues, the result block up to the host's own slot
             return fail(c, FOCR_ERR_INVALID, "scan_mfma: clear list full or region too large");
         c->scan_queues_used = 0;
         // Sizes.  Exact mode: the host reads the candidate count after the scan kernels and the hit count after the
-        // verify (two waits), so every later phase runs on exact sizes.  Estimated mode (ctx.hip: same setup as the
-        // previous scan): the counts stay on the device, grids and buffers take the previous counts + a margin (4 .. 20 %, ctx.hip) as bounds,
+        // verify (two waits), so every later phase runs on exact sizes.  Estimated mode (results.hip: same setup as the
+        // previous scan): the counts stay on the device, grids and buffers take the previous counts + a margin (4 .. 20 %, results.hip) as bounds,
         // unused candidate slots hold the largest key so that the sort leaves them at the end; nothing waits.
         c->ub_cand = c->estimated ? std::min(c->est.cand, c->d_cand.cap) : c->d_cand.cap;
         // Tail: the row path (rows.hip) unless a row could exceed its capacity — exact mode finds out after the scan kernels,
@@ -328,16 +329,16 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
         if (use_rows && (rc = rows2_begin(c, clear))) return rc;  // hits-first row tail: verify in flush order, only hits are bucketed and sorted (rows.hip)
         // legacy tail, estimated sizes: unused candidate slots hold the largest key so that the radix sort leaves them at the end
         if (c->estimated && !use_rows) FOCR_HIP(c, hipMemsetAsync(c->d_cand, 0xff, c->ub_cand * 8, c->stream));
-        FOCR_HIP(c, hipEventRecord(c->ev[0], c->stream));
+        FOCR_HIP(c, hipEventRecord(c->ev[EV_STATS_BEGIN], c->stream));
         if (nothing) {
             if ((rc = launch_clear(c, clear))) return rc;
-            FOCR_HIP(c, hipEventRecord(c->ev[1], c->stream));
+            FOCR_HIP(c, hipEventRecord(c->ev[EV_STATS_END], c->stream));
             use_rows = false;
         } else if ((rc = stats_phase(c, P, clear, thr_d)) || (rc = scan_phase(c, P, thr_d))) {
             return rc;
         }
-        FOCR_HIP(c, hipEventRecord(c->ev[2], c->stream));
-        FOCR_HIP(c, hipMemcpyAsync(c->h_live, c->d_counter + 8, 40 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        FOCR_HIP(c, hipEventRecord(c->ev[EV_SCAN_END], c->stream));
+        FOCR_HIP(c, hipMemcpyAsync(c->h_live, c->d_counter + LIVE_WORD0, LIVE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         const unsigned long long *n_cand_p = c->d_counter.as<const unsigned long long>() + 1;
         size_t ub_c = c->ub_cand;
         if (!c->estimated) {

@@ -400,7 +400,7 @@ static void launch_v2s(focr_ctx *c, const MfmaLaunch &L, const PlaneArgs &A3, un
     const uint64_t issued = 16 * ksteps_issued * 16 * 64;  // per live M-tile; scaled by the live count after the scan
     char name[64];
     snprintf(name, sizeof name, "scan_mfma2s_kernel<%d,%d,%d,%d>", KSTEPS, RPG, MT, NW);
-    c->launch_begin(name, L.n_templates | (L.super_index << 24), L.alg_macs, issued);
+    c->launch_begin(name, L.n_templates, L.alg_macs, issued, L.super_index);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, c->stream, c->pages.i8 + c->sub_p0 * c->pages.rows_alloc * c->pages.pitch, (uint32_t)c->pages.pitch, (uint32_t)c->pages.rows_alloc,
                        L.live_list, L.live_count, (uint32_t)c->sub_p0, reinterpret_cast<const v4i *>(c->bank.d_qbank + L.q_offset), n_tiles16, L.segs, L.Lpitch, L.Lrows, A3,
                        c->bank.d_tglobal + L.tg_offset, c->fmt, c->d_cand, c->d_counter.as<unsigned long long>() + 1, (unsigned long long)c->ub_cand, L.queue, c->row_hist);
@@ -442,7 +442,7 @@ static void launch_v2(focr_ctx *c, const MfmaLaunch &L, unsigned n_cus) {
     const uint64_t issued = 16 * (uint64_t)n_tiles16 * 16 * KSTEPS * 64;  // per live M-tile; scaled by the live count after the scan
     char name[64];
     snprintf(name, sizeof name, "scan_mfma2_kernel<%d,%d,%d,%d>", KSTEPS, RPG, MT, NW);
-    c->launch_begin(name, L.n_templates | (L.super_index << 24), L.alg_macs, issued);
+    c->launch_begin(name, L.n_templates, L.alg_macs, issued, L.super_index);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, c->stream, c->pages.i8 + c->sub_p0 * c->pages.rows_alloc * c->pages.pitch, (uint32_t)c->pages.pitch, (uint32_t)c->pages.rows_alloc,
                        L.live_list, L.live_count, (uint32_t)c->sub_p0, qb, n_tiles16, L.segs, L.Lpitch, L.Lrows, c->bank.d_tglobal + L.tg_offset,
                        c->fmt, c->d_cand, c->d_counter.as<unsigned long long>() + 1,

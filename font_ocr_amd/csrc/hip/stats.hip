@@ -605,12 +605,12 @@ int pass_stats(focr_ctx *c, const ScanPlan &P, size_t si, double thr_d) {
         void *out = su.planes ? (void *)(c->d_planes + su.plane_off + L.v * P.plane) : (void *)(c->d_L + L.k * P.L_per_class);
         void *out_pair = L.pair < 0 ? nullptr : su.planes ? (void *)(c->d_planes + su.plane_off + L.pv * P.plane) : (void *)(c->d_L + (size_t)L.pair * P.L_per_class);
         if (int rc = launch_stats(c, su.planes, L.k, L.pair, thr_d, out, out_pair, P.Lpitch, P.Lrows, last && todo.size() == 1 ? nullptr : lv, su.mtx, su.n_rows,
-                                  last ? P.live_list + su.live_offset : nullptr, last ? c->d_counter + 8 + si : nullptr)) return rc;
+                                  last ? P.live_list + su.live_offset : nullptr, last ? c->d_counter + LIVE_WORD0 + si : nullptr)) return rc;
     }
     if (direct) return FOCR_OK;
     const uint32_t nt = (uint32_t)((uint64_t)su.mtx * su.n_rows * c->sub_np);
     hipLaunchKernelGGL(compact_live_tiles, dim3((nt + 256 * CLT_PER_THREAD - 1) / (256 * CLT_PER_THREAD)), dim3(256), 0, c->stream, lv, nt, su.mtx,
-                       su.n_rows, 1u, P.live_list + su.live_offset, c->d_counter + 8 + si);
+                       su.n_rows, 1u, P.live_list + su.live_offset, c->d_counter + LIVE_WORD0 + si);
     FOCR_HIP(c, hipGetLastError());
     return FOCR_OK;
 }

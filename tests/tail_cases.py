@@ -8,7 +8,7 @@ The construction: a page of noise bytes 1 .. 255 against a bank of T noise templ
 noise in columns [0, L_j + 1) — L non-increasing — has exactly L_y * T hits in page row y ("stairs").  Where a case needs few
 hits it plants templates on paper at a positive threshold instead.  The targets below are written out, not computed: the host test
 holds the oracle's lists against them (a case that misses its targets fails there, before any device sees it), `plan` restates the
-host's choice of path (scan_mfma.hip: launch_scan_mfma, row_tail; ctx.hip: SizeEstimate::update) from the oracle's hits, and the
+host's choice of path (scan_mfma.hip: launch_scan_mfma, row_tail; results.hip: SizeEstimate::update) from the oracle's hits, and the
 device test asserts the path the library reports (focr_debug_tail_path) against the same table.
 
 Every case has a seed of its own and hence bank content no other test uses: size estimates are shared per process, keyed by the

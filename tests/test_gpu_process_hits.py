@@ -187,7 +187,7 @@ def test_executor_and_fleet_forward_anchor_and_overlap(bank_x2):
 
 def test_size_estimate_redo_keeps_anchor_and_overlap(bank_x2):
     """A process_hits queued behind a scan that overflows its estimated sizes is re-run with the stored anchor and overlap
-    (ctx.hip: the redo): its lines equal an exact-size run's and the reference's."""
+    (results.hip: the redo): its lines equal an exact-size run's and the reference's."""
     bank = bank_x2.subset(list(range(33, 80)) + list(range(95 + 33, 95 + 80)))
     dense = synth_pages(bank_x2, 2, 608, 720, first=7100)  # ~18 000 hits a page: far above the sparse batch's bounds (+8192)
     sparse = np.full_like(dense, 255)
