@@ -17,7 +17,10 @@
 //     come from the searched positions, and --scores gains a trailing pen_offset column;
 //   * --whole-line is an extension for proportional fonts: every line is the text that minimises the whole line's squared
 //     error over pens on the 1/64 px grid (focr_decoder_set_whole_line), not the pen loop's greedy choice; stdout stays
-//     text only and --verify draws every character at its pen; with --scores or --pen-search it is a usage error.
+//     text only and --verify draws every character at its pen; with --scores or --pen-search it is a usage error;
+//   * --margins PATH is an extension of --whole-line: a CSV row per decoded character with its pen, its term, and the
+//     glyph and margin of the best whole line that reads another glyph over its middle (focr_decoder_get_margins);
+//     stdout and the --verify files are the same with and without it; without --whole-line it is a usage error.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -44,8 +47,8 @@ const size_t BATCH_PAGES = 256;
 
 struct Args {
     std::vector<std::string> img;
-    std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores;
-    bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false;
+    std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores, margins;
+    bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false, have_margins = false;
     float text_size = 0.f, kerning = 1.f;
     uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0, pen_search = 0;
     bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
@@ -84,6 +87,7 @@ void print_help() {
            "      --scores <SCORES>                [extension] CSV of every decoded character's score, runner-up and margin\n"
            "      --pen-search <N>                 [extension] Also search pen offsets of up to N/64 px at every step, N <= 64 [default: 0]\n"
            "      --whole-line                     [extension] Decode each line as a whole, for proportional fonts (not with scores or a pen search)\n"
+           "      --margins <MARGINS>              [extension] CSV of every character's pen, term, runner-up and margin (only with the whole-line decode)\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -147,6 +151,7 @@ Args parse_args(int argc, char **argv) {
             if (a.pen_search > FOCR_PEN_SEARCH_MAX) usage_error("invalid value '" + s + "' for '--pen-search': the radius is at most 64");
         }
         else if (k == "--whole-line") a.whole_line = true;
+        else if (k == "--margins") a.margins = need(), a.have_margins = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -164,6 +169,7 @@ Args parse_args(int argc, char **argv) {
     if (!missing.empty()) usage_error("the following required arguments were not provided:" + missing);
     if (a.whole_line && a.have_scores) usage_error("the argument '--whole-line' cannot be used with '--scores <SCORES>'");
     if (a.whole_line && a.pen_search) usage_error("the argument '--whole-line' cannot be used with '--pen-search <N>'");
+    if (a.have_margins && !a.whole_line) usage_error("the argument '--margins <MARGINS>' cannot be used without '--whole-line'");
     return a;
 }
 
@@ -203,6 +209,8 @@ struct Line {
     std::vector<uint32_t> text;  // code points
     std::vector<focr_char_score_t> scores;  // --scores: one per code point
     std::vector<int8_t> offsets;            // --scores with --pen-search: one per code point
+    std::vector<uint32_t> pens;             // --margins: one per code point, in 1/64 px
+    std::vector<focr_char_margin_t> margins;
 };
 
 // Writes the batch's verify images (the device's draw_verify, n x H x W x 3 bytes) as PNGs on at most 16 threads, and
@@ -278,6 +286,8 @@ int main(int argc, char **argv) {
     if (args.have_test) return run_test(args, alphabet);
     FILE *csv = nullptr;
     if (args.have_scores && !(csv = fopen(args.scores.c_str(), "w"))) usage_error("cannot write '" + args.scores + "' for '--scores'");
+    FILE *mcsv = nullptr;
+    if (args.have_margins && !(mcsv = fopen(args.margins.c_str(), "w"))) usage_error("cannot write '" + args.margins + "' for '--margins'");
     if (args.img.empty()) return 0;
 
     char err[256] = {0};
@@ -310,6 +320,7 @@ int main(int argc, char **argv) {
     if (csv && focr_decoder_set_scores(dec, 1) != 0) die(std::string("focr_decoder_set_scores: ") + focr_decoder_last_error(dec), 1);
     if (focr_decoder_set_pen_search(dec, args.pen_search) != 0) die(std::string("focr_decoder_set_pen_search: ") + focr_decoder_last_error(dec), 1);
     if (focr_decoder_set_whole_line(dec, args.whole_line) != 0) die(std::string("focr_decoder_set_whole_line: ") + focr_decoder_last_error(dec), 1);
+    if (mcsv && focr_decoder_set_whole_margins(dec, 1) != 0) die(std::string("focr_decoder_set_whole_margins: ") + focr_decoder_last_error(dec), 1);
     const bool csv_offsets = csv && args.pen_search > 0;
 
     std::vector<std::vector<Line>> lines(n_img);
@@ -341,8 +352,14 @@ int main(int argc, char **argv) {
             std::vector<int8_t> dj(csv_offsets ? dc.size() : 0);
             if (csv_offsets && focr_decoder_get_offsets(dec, dj.data()) != 0)
                 die(std::string("focr_decoder_get_offsets: ") + focr_decoder_last_error(dec), 1);
+            std::vector<uint32_t> dp(mcsv ? dc.size() : 0);
+            std::vector<focr_char_margin_t> dm(mcsv ? dc.size() : 0);
+            if (mcsv && (focr_decoder_get_pens(dec, dp.data(), nullptr) != 0 || focr_decoder_get_margins(dec, dm.data()) != 0))
+                die(std::string("focr_decoder_get_margins: ") + focr_decoder_last_error(dec), 1);
             for (const focr_decoded_line_t &l : dl) {
-                Line out{l.y, {}, {}, {}};
+                Line out{l.y, {}, {}, {}, {}, {}};
+                if (mcsv) out.pens.assign(dp.begin() + l.first, dp.begin() + l.first + l.n_chars);
+                if (mcsv) out.margins.assign(dm.begin() + l.first, dm.begin() + l.first + l.n_chars);
                 for (uint32_t c = 0; c < l.n_chars; c++) out.text.push_back(alphabet[dc[l.first + c]]);
                 if (csv) out.scores.assign(ds.begin() + l.first, ds.begin() + l.first + l.n_chars);
                 if (csv_offsets) out.offsets.assign(dj.begin() + l.first, dj.begin() + l.first + l.n_chars);
@@ -388,6 +405,18 @@ int main(int argc, char **argv) {
                     fputc('\n', csv);
                 }
         if (fclose(csv) != 0) die("cannot write " + args.scores);
+    }
+    if (mcsv) {  // one row per decoded character, in the order of stdout; a one-glyph alphabet has no runner-up and no margin
+        fprintf(mcsv, "image_index,y,column,codepoint,pen,term,runner_codepoint,margin\n");
+        for (size_t i = 0; i < n_img; i++)
+            for (const Line &l : lines[i])
+                for (size_t c = 0; c < l.text.size(); c++) {
+                    const focr_char_margin_t &m = l.margins[c];
+                    fprintf(mcsv, "%zu,%u,%zu,%u,%u,%d,", i, l.y, c, l.text[c], l.pens[c], (int)m.term);
+                    if (m.runner < alphabet.size()) fprintf(mcsv, "%u,%lld\n", alphabet[m.runner], (long long)m.margin);
+                    else fprintf(mcsv, ",\n");
+                }
+        if (fclose(mcsv) != 0) die("cannot write " + args.margins);
     }
     return 0;
 }

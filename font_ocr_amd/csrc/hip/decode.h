@@ -203,6 +203,13 @@ struct focr_decoder {
     focr::DevArray<uint32_t> d_inc64, d_pens;
     focr::DevArray<uint16_t> d_back;
     focr::DevArray<int64_t> d_cost;
+    // margins of a whole-line run (focr_decoder_set_whole_margins): the workgroups' forward keys in d_back's place, and per
+    // character beside d_chars the term, the runner and the margin; grown by a run with margins on
+    bool margins_on = false;
+    focr::DevArray<uint64_t> d_fwd;
+    focr::DevArray<int32_t> d_mterm;
+    focr::DevArray<uint16_t> d_mrunner;
+    focr::DevArray<int64_t> d_margin;
     // results of the last run
     std::vector<focr_decoded_line_t> lines;
     std::vector<uint16_t> chars;
@@ -213,6 +220,8 @@ struct focr_decoder {
     bool have_whole = false;      // the last successful run was a whole-line run
     std::vector<uint32_t> pens;   // beside chars: each character's pen in 1/64 px
     std::vector<int64_t> line_cost;
+    bool have_margins = false;    // the last successful run was a whole-line run with margins
+    std::vector<focr_char_margin_t> margins;  // beside chars
     // verify: the table, what the last successful run left for it, buffers
     uint32_t n_vglyphs = 0, hmax = 0;
     focr::DevArray<focr_dec::VerifyGlyph> d_vglyphs;

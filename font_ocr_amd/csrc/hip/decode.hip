@@ -12,6 +12,8 @@
 //      the argmin over (glyph, pen offset), and the chosen offset of every step beside its glyph.
 //      With the whole-line decode on (focr_decoder_set_whole_line) line_whole_kernel takes its place: a dynamic programme
 //      over pens in 1/64 px that minimises the sum of the footprint terms along the line, and every character's pen.
+//      With margins as well (focr_decoder_set_whole_margins) line_whole_margins_kernel takes that one's place: the same
+//      programme and a backward sweep, for every character's term, runner-up and margin.
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
@@ -340,7 +342,11 @@ constexpr uint32_t WHOLE_MISC_BYTES = 64 + 2 * WHOLE_BATCH_MAX;  // the waves' e
 constexpr uint32_t WHOLE_RING_MAX = 4096;   // keys of the cost ring at most: ring and the rest stay inside LDS_STRIP_MAX
 constexpr uint64_t WHOLE_COST_BIAS = 1ull << 47;
 constexpr size_t WHOLE_SCRATCH_BUDGET = 64u << 20;  // bytes of backpointer scratch at most (a single workgroup's may exceed it)
+constexpr size_t WHOLE_MARGINS_SCRATCH_BUDGET = 4 * WHOLE_SCRATCH_BUDGET;  // with margins: 64-bit keys in the 16-bit backpointers' place
 constexpr uint32_t WHOLE_GRID_MAX = 2048;
+
+// Dwords of a line's runner keys (64-bit) and midpoints beside the ring or in the scratch, a multiple of four.
+__host__ __device__ constexpr uint32_t whole_chars_dwords(uint32_t cap) { return (3 * cap + 3) & ~3u; }
 
 struct WholeParams {
     int origin_d;        // 64 * origin_x
@@ -480,6 +486,183 @@ __global__ __launch_bounds__(WHOLE_THREADS) void line_whole_kernel(const uint8_t
     }
 }
 
+// What line_whole_margins_kernel needs beyond the plain programme: the workgroups' scratch of 64-bit words (per
+// workgroup wp.n_states of them: every live state's forward key, then cap runner keys and cap midpoints for the lines
+// whose characters do not fit in LDS), and per character (the layout of chars) the results of include/focr_decode.h.
+struct MarginOut {
+    uint64_t *scratch;
+    int32_t *term;
+    uint16_t *runner;
+    int64_t *margin;
+};
+
+// 3m. line_whole_kernel with margins (focr_decoder_set_whole_margins; the definition is include/focr_decode.h's): the same
+// programme, whose batches also leave every state's key in the workgroup's scratch (~0: not reached, so this scratch is
+// written for every state of the line; the low 16 bits of a key are the backpointer), then, line by line, the backward
+// sweep described below.  A kernel of its own and not a switch of line_whole_kernel's: sharing the body changed that
+// kernel's machine code (tools/isa_hash.py), and a run without margins launches what it always did.
+template <bool LDS, bool CHARS_LDS>
+__global__ __launch_bounds__(WHOLE_THREADS) void line_whole_margins_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
+                                                                           const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
+                                                                           const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps,
+                                                                           const uint32_t *__restrict__ inc64, uint32_t n_glyphs, WholeParams wp,
+                                                                           uint32_t *__restrict__ n_chars, uint16_t *chars, uint32_t *pens,
+                                                                           int64_t *__restrict__ costs, MarginOut mo) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_whole[];  // the waves' end keys and the live count, the live list, the ring, then (LDS) the strip
+    uint64_t *red = (uint64_t *)lds_whole;                          // [4]
+    uint32_t *n_live = lds_whole + 8;                               // [1], and [1] the line's character count
+    uint16_t *live = (uint16_t *)(lds_whole + 16);                  // [WHOLE_BATCH_MAX]
+    uint64_t *ring = (uint64_t *)(lds_whole + WHOLE_MISC_BYTES / 4);
+    uint32_t *lds_strip = lds_whole + WHOLE_MISC_BYTES / 4 + 2 * (wp.ring_mask + 1);
+    if (CHARS_LDS) lds_strip += whole_chars_dwords(g.cap);  // the characters' runner keys and midpoints come before the strip
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t sdw = g.stride / 4, mask = wp.ring_mask, B = wp.batch;
+    const int w = (int)g.w;
+    const uint32_t n_live_states = 64u * g.w;
+    uint64_t *fwd = mo.scratch + (size_t)blockIdx.x * wp.n_states;  // the forward keys, in the backpointers' place
+    uint64_t *cost_b = (uint64_t *)(lds_whole + 10);                // the line's cost + 2^47, for every thread
+    const uint32_t n_lines = *count;
+    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
+        const uint32_t slot = work[k];
+        uint32_t yc, h;
+        slot_rows(g, slot % g.n_slots, &yc, &h);
+        const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
+        if (LDS) {
+            for (uint32_t q = tid; q < sdw * h; q += WHOLE_THREADS) lds_strip[q] = strip[q];
+            strip = lds_strip;
+        }
+        for (uint32_t q = tid; q <= mask; q += WHOLE_THREADS) ring[q] = q ? ~0ull : (WHOLE_COST_BIAS << 16) | 0xffffu;  // cost[0] = 0, no glyph
+        if (tid == 0) n_live[0] = 0;
+        __syncthreads();
+        for (uint32_t b0 = 0; b0 < n_live_states; b0 += B) {
+            const uint32_t nb = std::min(B, n_live_states - b0);
+            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) {
+                const uint64_t key = ring[(b0 + j) & mask];
+                fwd[b0 + j] = key;  // every state of the batch: ~0 marks the ones this line did not reach
+                if (key == ~0ull) continue;
+                live[atomicAdd(&n_live[0], 1u)] = (uint16_t)j;
+            }
+            __syncthreads();
+            const uint32_t nl = n_live[0], n_cand = nl * n_glyphs;  // nl <= 512 and n_glyphs < 65536
+            for (uint32_t c = tid; c < n_cand; c += WHOLE_THREADS) {
+                const uint32_t gi = c / nl, s = b0 + live[c - gi * nl];
+                const int d = wp.origin_d + (int)s;
+                const int phase = d & 63, shift = d >> 6;
+                const DevGlyph gl = glyphs[gi];
+                const int2 o = offs[gi * 64 + phase];
+                const int term = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
+                                                shift + o.x, o.y);
+                const uint64_t cost = (ring[s & mask] >> 16) + (uint64_t)(int64_t)term;  // biased, mod 2^64: stays in (0, 2^48)
+                atomicMin((unsigned long long *)&ring[(s + inc64[gi]) & mask], (unsigned long long)((cost << 16) | gi));
+            }
+            __syncthreads();
+            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) ring[(b0 + j) & mask] = ~0ull;
+            if (tid == 0) n_live[0] = 0;
+            __syncthreads();
+        }
+        // the end state: the lowest (cost, t) over t = 64 * w + e, e < max_inc (e < 4096 takes the glyph's place in the key)
+        uint64_t best = ~0ull;
+        for (uint32_t e = tid; e < wp.max_inc; e += WHOLE_THREADS) {
+            const uint64_t key = ring[(n_live_states + e) & mask];
+            if (key != ~0ull) best = std::min<uint64_t>(best, (key & ~(uint64_t)0xffff) | e);
+        }
+        for (int m = 32; m >= 1; m >>= 1) best = std::min(best, shfl_xor_u64(best, m));
+        if (lane == 0) red[wave] = best;
+        __syncthreads();
+        if (tid == 0) {
+            for (uint32_t v = 1; v < WHOLE_THREADS / 64; v++) best = std::min(best, red[v]);
+            // some end state is reachable (every step from a state below 64 * w lands somewhere); without one the line is empty
+            uint32_t t = best != ~0ull ? n_live_states + (uint32_t)(best & 0xffffu) : 0, n = 0;
+            uint32_t gi = (uint32_t)ring[t & mask] & 0xffffu;
+            costs[k] = best != ~0ull ? (int64_t)((best >> 16) - WHOLE_COST_BIAS) : 0;
+            while (t > 0 && n < g.cap && gi < n_glyphs && inc64[gi] <= t) {  // back to front; all but t > 0 always hold (the host's bound; a reached state's glyph) and only guard the accesses
+                t -= inc64[gi];
+                chars[(size_t)k * g.cap + n] = (uint16_t)gi;
+                pens[(size_t)k * g.cap + n] = t;
+                n++;
+                gi = (uint32_t)fwd[t] & 0xffffu;
+            }
+            n_chars[k] = n;
+            n_live[1] = n;
+            cost_b[0] = best >> 16;
+        }
+        __syncthreads();
+        const uint32_t n = n_live[1];
+        for (uint32_t q = tid; q < n / 2; q += WHOLE_THREADS) {  // into text order
+            const size_t a = (size_t)k * g.cap + q, b = (size_t)k * g.cap + n - 1 - q;
+            const uint16_t ca = chars[a], cb = chars[b];
+            const uint32_t pa = pens[a], pb = pens[b];
+            chars[a] = cb, chars[b] = ca;
+            pens[a] = pb, pens[b] = pa;
+        }
+        __syncthreads();  // chars and pens are in text order
+        if (n == 0) continue;  // uniform
+        // The backward sweep of include/focr_decode.h.  ring[t & mask] now holds B[t] + 2^47 while t is within ring length
+        // of the batch: every slot starts at B = 0 (the states from 64 * w on; the others are cleared before they are
+        // used), and the batches are the forward pass's, last to first.  Per batch: its slots are cleared and its reached
+        // states listed; barrier; every (state, glyph) edge takes B of its target, which lies above the batch and is
+        // final, pushes term + B into its own state's slot, and pushes its through-cost into the runner key of every
+        // character whose midpoint it covers and whose glyph is another; barrier; the count is reset; barrier.  The
+        // slots of a batch alias states one ring length on, above every target of this and of later batches.
+        const size_t row = (size_t)k * g.cap;
+        uint64_t *rkey = CHARS_LDS ? ring + mask + 1 : fwd + wp.n_states - whole_chars_dwords(g.cap) / 2;  // [cap]
+        uint32_t *mids = (uint32_t *)(rkey + g.cap);                                                      // [cap], ascending
+        for (uint32_t q = tid; q < n; q += WHOLE_THREADS) {
+            mids[q] = pens[row + q] + (inc64[chars[row + q]] >> 1);
+            rkey[q] = ~0ull;
+        }
+        for (uint32_t q = tid; q <= mask; q += WHOLE_THREADS) ring[q] = WHOLE_COST_BIAS;
+        __syncthreads();
+        const uint64_t line_cost = cost_b[0];
+        for (uint32_t b0 = (n_live_states - 1) / B * B;; b0 -= B) {  // n_live_states > 0: a line has characters
+            const uint32_t nb = std::min(B, n_live_states - b0);
+            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) {
+                ring[(b0 + j) & mask] = ~0ull;
+                if (fwd[b0 + j] != ~0ull) live[atomicAdd(&n_live[0], 1u)] = (uint16_t)j;
+            }
+            __syncthreads();
+            const uint32_t nl = n_live[0], n_cand = nl * n_glyphs;
+            for (uint32_t c = tid; c < n_cand; c += WHOLE_THREADS) {
+                const uint32_t gi = c / nl, s = b0 + live[c - gi * nl], t = s + inc64[gi];
+                const int d = wp.origin_d + (int)s;
+                const int phase = d & 63, shift = d >> 6;
+                const DevGlyph gl = glyphs[gi];
+                const int2 o = offs[gi * 64 + phase];
+                const int term = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
+                                                shift + o.x, o.y);
+                const uint64_t rest = ring[t & mask] + (uint64_t)(int64_t)term;  // term + B[t], biased: in (0, 2^48)
+                atomicMin((unsigned long long *)&ring[s & mask], (unsigned long long)rest);
+                const uint64_t through = (fwd[s] >> 16) + rest - WHOLE_COST_BIAS;  // F[s] + term + B[t], biased: a whole path's cost
+                uint32_t lo = 0, hi = n;  // the first midpoint at or after s
+                while (lo < hi) {
+                    const uint32_t m = (lo + hi) >> 1;
+                    if (mids[m] < s) lo = m + 1;
+                    else hi = m;
+                }
+                for (; lo < n && mids[lo] < t; lo++)
+                    if (chars[row + lo] != gi) atomicMin((unsigned long long *)&rkey[lo], (unsigned long long)((through << 16) | gi));
+            }
+            __syncthreads();
+            if (tid == 0) n_live[0] = 0;
+            __syncthreads();
+            if (b0 == 0) break;
+        }
+        for (uint32_t q = tid; q < n; q += WHOLE_THREADS) {
+            const uint32_t gi = chars[row + q];
+            const int d = wp.origin_d + (int)pens[row + q];
+            const int phase = d & 63, shift = d >> 6;
+            const DevGlyph gl = glyphs[gi];
+            const int2 o = offs[gi * 64 + phase];
+            mo.term[row + q] = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
+                                              shift + o.x, o.y);
+            const uint64_t key = rkey[q];  // ~0: no edge of another glyph (a one-glyph alphabet); its index reads 0xffff
+            mo.runner[row + q] = (uint16_t)key;
+            mo.margin[row + q] = key != ~0ull ? (int64_t)((key >> 16) - line_cost) : -1;
+        }
+        __syncthreads();  // the ring, the characters' keys and the strip are free for the next line
+    }
+}
+
 }  // namespace focr_dec
 
 using namespace focr_dec;
@@ -534,7 +717,7 @@ extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
 extern "C" const char *focr_decoder_last_error(const focr_decoder_t *dec) { return dec ? dec->err.c_str() : g_dec_err.c_str(); }
 
 extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font_t *font) {
-    if (dec) dec->run_ok = false, dec->have_whole = false, dec->n_vglyphs = 0;  // the last run and the verify table belong to the previous font
+    if (dec) dec->run_ok = false, dec->have_whole = false, dec->have_margins = false, dec->n_vglyphs = 0;  // the last run and the verify table belong to the previous font
     if (!dec || !font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_font: bad arguments");
     if (font->n_glyphs > 65535) return dfail(dec, "focr_decoder_set_font: more than 65535 glyphs");
     if (font->bitmaps_len % 4 || font->bitmaps_len / 4 > 0xffffffffull) return dfail(dec, "focr_decoder_set_font: bad bitmap table");
@@ -586,10 +769,14 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     dec->have_whole = false;
     dec->pens.clear();
     dec->line_cost.clear();
+    dec->have_margins = false;
+    dec->margins.clear();
     dec->run.ms = 0.f;
     dec->run.launches = 0;
     if (!dec->n_glyphs) return dfail(dec, "focr_decoder_run: no font (focr_decoder_set_font)");
     if (n_pages && !pages) return dfail(dec, "focr_decoder_run: null pages");
+    if (dec->margins_on && !dec->whole_on)
+        return dfail(dec, "focr_decoder_run: margins on with the whole-line decode off (focr_decoder_set_whole_margins needs focr_decoder_set_whole_line)");
     const uint32_t radius = dec->pen_search;
     const float reach = (float)radius * 0.015625f;  // exact
     if (reach > dec->min_inc * 0.5f)
@@ -600,7 +787,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     const uint8_t *d_src = nullptr;
     if (stage_in(dec, dec->d_pages, pages, on_device, page_w * page_h * n_pages, &d_src)) return 1;
     const size_t total = g.total;
-    const bool scores = dec->scores_on, whole = dec->whole_on;
+    const bool scores = dec->scores_on, whole = dec->whole_on, margins = dec->margins_on;
     WholeParams wp{};
     std::vector<uint32_t> inc64;
     uint32_t whole_cap = 1;
@@ -639,6 +826,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         DEC_CHECK(hipStreamSynchronize(dec->stream));
         remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
         dec->have_scores = scores;
+        dec->have_margins = margins;
         return 0;
     }
     g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;
@@ -674,10 +862,19 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     if (radius) DEC_GROW(dec->d_pen, (size_t)g.cap * total);
     uint32_t whole_grid = 0;
     if (whole) {  // as many workgroups as the scratch budget allows (one always), each with 64 * w + max inc64 backpointers
-        const size_t fit = std::max<size_t>(WHOLE_SCRATCH_BUDGET / ((size_t)wp.n_states * sizeof(uint16_t)), 1);
+        // with margins a workgroup's scratch is 64-bit words: a forward key per state, then the characters' keys and midpoints
+        if (margins) wp.n_states += whole_chars_dwords(g.cap) / 2;
+        const size_t fit = std::max<size_t>(margins ? WHOLE_MARGINS_SCRATCH_BUDGET / ((size_t)wp.n_states * sizeof(uint64_t))
+                                                    : WHOLE_SCRATCH_BUDGET / ((size_t)wp.n_states * sizeof(uint16_t)), 1);
         whole_grid = (uint32_t)std::min<size_t>({total, fit, WHOLE_GRID_MAX});
         if (dec->whole_grid) whole_grid = std::min(whole_grid, dec->whole_grid);
-        DEC_GROW(dec->d_back, (size_t)whole_grid * wp.n_states);
+        if (margins) {
+            DEC_GROW(dec->d_fwd, (size_t)whole_grid * wp.n_states);
+            DEC_GROW(dec->d_mterm, (size_t)g.cap * total);
+            DEC_GROW(dec->d_mrunner, (size_t)g.cap * total);
+            DEC_GROW(dec->d_margin, (size_t)g.cap * total);
+        } else
+            DEC_GROW(dec->d_back, (size_t)whole_grid * wp.n_states);
         DEC_GROW(dec->d_pens, (size_t)g.cap * total);
         DEC_GROW(dec->d_cost, total);
         if (!dec->d_inc64.p) DEC_UPLOAD(dec->d_inc64, inc64.data(), inc64.size());
@@ -688,7 +885,17 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     DEC_CHECK(hipGetLastError());
     line_compact_kernel<<<1, COMPACT_THREADS, 0, dec->stream>>>(dec->d_flags, g.total, dec->d_work, dec->d_count);
     DEC_CHECK(hipGetLastError());
-    if (whole) {  // the strip shares LDS with the cost ring and the live list
+    if (whole && margins) {  // the characters' keys and midpoints come first: beside the ring when they fit, then the strip when it still fits
+        const size_t ring_bytes = WHOLE_MISC_BYTES + ((size_t)wp.ring_mask + 1) * 8, chars_bytes = (size_t)whole_chars_dwords(g.cap) * 4;
+        const bool chars_lds = ring_bytes + chars_bytes <= LDS_STRIP_MAX;
+        const size_t fixed = ring_bytes + (chars_lds ? chars_bytes : 0);
+        const bool lds = strip_bytes + fixed <= LDS_STRIP_MAX;
+        const auto kernel = lds ? (chars_lds ? line_whole_margins_kernel<true, true> : line_whole_margins_kernel<true, false>)
+                                : (chars_lds ? line_whole_margins_kernel<false, true> : line_whole_margins_kernel<false, false>);
+        kernel<<<whole_grid, WHOLE_THREADS, fixed + (lds ? strip_bytes : 0), dec->stream>>>(
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
+            dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, MarginOut{dec->d_fwd, dec->d_mterm, dec->d_mrunner, dec->d_margin});
+    } else if (whole) {  // the strip shares LDS with the cost ring and the live list
         const size_t ring_bytes = WHOLE_MISC_BYTES + ((size_t)wp.ring_mask + 1) * 8;
         const bool lds = strip_bytes + ring_bytes <= LDS_STRIP_MAX;
         (lds ? line_whole_kernel<true> : line_whole_kernel<false>)<<<whole_grid, WHOLE_THREADS, ring_bytes + (lds ? strip_bytes : 0), dec->stream>>>(
@@ -726,6 +933,14 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         DEC_CHECK(hipMemcpyAsync(wpens.data(), dec->d_pens, wpens.size() * 4, hipMemcpyDeviceToHost, dec->stream));
         DEC_CHECK(hipMemcpyAsync(wcost.data(), dec->d_cost, total * 8, hipMemcpyDeviceToHost, dec->stream));
     }
+    std::vector<int32_t> mterm(margins ? all.size() : 0);
+    std::vector<uint16_t> mrunner(margins ? all.size() : 0);
+    std::vector<int64_t> mmargin(margins ? all.size() : 0);
+    if (margins) {
+        DEC_CHECK(hipMemcpyAsync(mterm.data(), dec->d_mterm, all.size() * 4, hipMemcpyDeviceToHost, dec->stream));
+        DEC_CHECK(hipMemcpyAsync(mrunner.data(), dec->d_mrunner, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
+        DEC_CHECK(hipMemcpyAsync(mmargin.data(), dec->d_margin, all.size() * 8, hipMemcpyDeviceToHost, dec->stream));
+    }
     std::vector<int32_t> term, runner_term;
     std::vector<uint16_t> runner;
     std::vector<uint64_t> base;
@@ -756,6 +971,8 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
             dec->pens.insert(dec->pens.end(), wpens.begin() + (size_t)k * g.cap, wpens.begin() + (size_t)k * g.cap + n);
             dec->line_cost.push_back(wcost[k]);
         }
+        for (size_t at = (size_t)k * g.cap; margins && at < (size_t)k * g.cap + n; at++)
+            dec->margins.push_back(focr_char_margin_t{mterm[at], mrunner[at], 0, mmargin[at]});
         if (!scores) continue;
         dec->line_base.push_back(base[k]);
         for (size_t at = (size_t)k * g.cap; at < (size_t)k * g.cap + n; at++) {  // the reference's score: sum r^2 plus the footprint term
@@ -767,6 +984,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     if (!radius) dec->offsets.assign(dec->chars.size(), 0);
     remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
     dec->have_scores = scores;
+    dec->have_margins = margins;
     return 0;
 }
 
@@ -795,6 +1013,20 @@ extern "C" int focr_decoder_get_pens(const focr_decoder_t *dec, uint32_t *pens, 
         return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_pens: the last successful run was not a whole-line run (focr_decoder_set_whole_line)");
     if (pens && !dec->pens.empty()) memcpy(pens, dec->pens.data(), dec->pens.size() * sizeof(uint32_t));
     if (line_cost && !dec->line_cost.empty()) memcpy(line_cost, dec->line_cost.data(), dec->line_cost.size() * sizeof(int64_t));
+    return 0;
+}
+
+extern "C" int focr_decoder_set_whole_margins(focr_decoder_t *dec, int on) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_whole_margins: null decoder");
+    dec->margins_on = on != 0;
+    return 0;
+}
+
+extern "C" int focr_decoder_get_margins(const focr_decoder_t *dec, focr_char_margin_t *out) {
+    if (!dec) return dfail(nullptr, "focr_decoder_get_margins: null decoder");
+    if (!dec->have_margins)
+        return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_margins: the last successful run was not a margins run (focr_decoder_set_whole_margins)");
+    if (out && !dec->margins.empty()) memcpy(out, dec->margins.data(), dec->margins.size() * sizeof(focr_char_margin_t));
     return 0;
 }
 

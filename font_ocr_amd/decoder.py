@@ -13,6 +13,9 @@
         pages, pens, costs = dec.decode(luma_pages, 45, 39, 608, 12, 15, whole_line=True)
         # the whole line's squared error minimised over pens on the 1/64 px grid (for proportional fonts); pens[page][line]:
         # each character's pen in 1/64 px, costs[page][line]: the line's sum of footprint terms
+        pages, pens, costs, margins = dec.decode(luma_pages, 45, 39, 608, 12, 15, whole_line=True, margins=True)
+        # margins[page][line]: which characters of a whole line to doubt (LineMargins): each one's term, the glyph the
+        # best other whole line reads over its middle, and how much worse that line is
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -40,6 +43,17 @@ class LineScores(collections.namedtuple("LineScores", "base score runner runner_
     identical bitmaps tie: runner_score == score."""
 
     __slots__ = ()
+
+
+class LineMargins(collections.namedtuple("LineMargins", "term runner margin")):
+    """The margins of one whole line (decode(..., whole_line=True, margins=True)), aligned with its text.  Per character:
+    term, its footprint term (int32; the terms of a line sum to its cost); runner, the glyph that the best whole line
+    reading another glyph over the character's midpoint reads there (a str, one character each; NO_RUNNER, "\\0", for a
+    one-glyph alphabet); margin, that line's cost less the decoded line's (int64; >= 0, 0 between identical glyphs, -1
+    without a runner).  include/focr_decode.h has the definition."""
+
+    __slots__ = ()
+    NO_RUNNER = "\0"
 
 
 def _err():
@@ -184,6 +198,7 @@ class LineDecoder:
         self._scores = False  # the library's switch (focr_decoder_set_scores)
         self._pen_search = 0  # the library's radius (focr_decoder_set_pen_search)
         self._whole = False  # the library's switch (focr_decoder_set_whole_line)
+        self._margins = False  # the library's switch (focr_decoder_set_whole_margins)
 
     def _check(self, rc):
         if rc != 0:
@@ -296,11 +311,15 @@ class LineDecoder:
         mse = sums.astype(np.float32) / np.float32((h * w) & 0xFFFFFFFF)  # red_blue_mse: (sum as f32) / (w * h as u32)
         return mse, imgs
 
-    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0, whole_line=False):
+    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0, whole_line=False,
+             margins=False):
         """[[(y, text), ...] per page] of one batch; with scores [[LineScores, ...] per page] beside it (else None); with
         a pen search [[int8 offsets, ...] per page] (else None); with whole_line ([[uint32 pens, ...] per page],
-        [[cost, ...] per page]) (else None)."""
+        [[cost, ...] per page]) (else None), and with margins [[LineMargins, ...] per page] as a third element of that."""
         self._batch = None
+        if bool(margins) != self._margins:
+            self._check(self._lib.focr_decoder_set_whole_margins(self._h, int(bool(margins))))
+            self._margins = bool(margins)
         if bool(whole_line) != self._whole:
             self._check(self._lib.focr_decoder_set_whole_line(self._h, int(bool(whole_line))))
             self._whole = bool(whole_line)
@@ -328,8 +347,11 @@ class LineDecoder:
             ps = np.zeros(max(1, nc), dtype=np.uint32)
             lc = np.zeros(max(1, nl), dtype=np.int64)
             self._check(self._lib.focr_decoder_get_pens(self._h, ps.ctypes.data, lc.ctypes.data))
+        if margins:
+            ms = np.zeros(max(1, nc), dtype=np.dtype([("term", "<i4"), ("runner", "<u2"), ("pad", "<u2"), ("margin", "<i8")]))
+            self._check(self._lib.focr_decoder_get_margins(self._h, ms.ctypes.data))
         alpha = self.font.alphabet
-        whole = ([[] for _ in range(n)], [[] for _ in range(n)]) if whole_line else None
+        whole = ([[] for _ in range(n)], [[] for _ in range(n)]) + (([[] for _ in range(n)],) if margins else ()) if whole_line else None
         out = [[] for _ in range(n)]
         sc = [[] for _ in range(n)] if scores else None
         offs = [[] for _ in range(n)] if pen_search else None
@@ -342,6 +364,10 @@ class LineDecoder:
             if whole_line:
                 whole[0][ln.page].append(ps[ln.first: ln.first + ln.n_chars].copy())
                 whole[1][ln.page].append(int(lc[k]))
+            if margins:
+                m = ms[ln.first: ln.first + ln.n_chars]
+                runner = "".join(LineMargins.NO_RUNNER if i == 0xFFFF else alpha[i] for i in m["runner"])
+                whole[2][ln.page].append(LineMargins(m["term"].copy(), runner, m["margin"].copy()))
             if scores:
                 c = cs[ln.first: ln.first + ln.n_chars]
                 sc[ln.page].append(LineScores(int(base[k]), c["score"].copy(), c["runner"].copy(), c["runner_score"].copy()))
@@ -361,7 +387,14 @@ class LineDecoder:
             raise ValueError("whole_line=True does not go with pen_search (the dynamic programme does not search offsets)")
         return bool(whole_line)
 
-    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, whole_line=False):
+    @staticmethod
+    def _check_margins(margins, whole_line):
+        if margins and not whole_line:
+            raise ValueError("margins=True needs whole_line=True (the margins are the whole-line decode's)")
+        return bool(margins)
+
+    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, margins=False,
+               whole_line=False):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
         Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
         mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
@@ -375,12 +408,15 @@ class LineDecoder:
         minimises the whole line's squared error over pens on the 1/64 px grid, not the pen loop's greedy choice; the
         result gains two last elements: pens[page][line], a uint32 array of each character's pen in 1/64 px, and
         costs[page][line], the line's sum of footprint terms (int).  The verify then renders every character at its pen.
-        It goes with neither scores nor pen_search."""
+        It goes with neither scores nor pen_search.  With margins=True as well the result gains one more element after
+        costs: margins[page][line], the LineMargins of lines[page][line]: which characters of the line to doubt.
+        margins=True without whole_line raises ValueError."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
         pen_search = self._check_pen_search(pen_search)
         whole_line = self._check_whole_line(whole_line, scores, pen_search)
+        margins = self._check_margins(margins, whole_line)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
@@ -389,7 +425,7 @@ class LineDecoder:
         out = [None] * len(pages)
         sc = [None] * len(pages)
         offs = [None] * len(pages)
-        wpens, wcosts = [None] * len(pages), [None] * len(pages)
+        wpens, wcosts, wmargins = [None] * len(pages), [None] * len(pages), [None] * len(pages)
         mse = np.zeros(len(pages), dtype=np.float32)
         images = [None] * len(pages) if verify == "image" else None
         by_size = {}
@@ -398,11 +434,13 @@ class LineDecoder:
         for (h, w), idx in by_size.items():
             batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
             res, res_sc, res_offs, res_whole = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
-                                                         pen_search=pen_search, whole_line=whole_line)
+                                                         pen_search=pen_search, whole_line=whole_line, margins=margins)
             for j, i in enumerate(idx):
                 out[i] = res[j]
                 if whole_line:
                     wpens[i], wcosts[i] = res_whole[0][j], res_whole[1][j]
+                if margins:
+                    wmargins[i] = res_whole[2][j]
                 if pen_search:
                     offs[i] = res_offs[j]
                 if scores:
@@ -420,10 +458,12 @@ class LineDecoder:
             res += (offs,)
         if whole_line:
             res += (wpens, wcosts)
+        if margins:
+            res += (wmargins,)
         return res if len(res) > 1 else out
 
     def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False,
-                      pen_search=0, whole_line=False):
+                      pen_search=0, margins=False, whole_line=False):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
         if self.font is None:
@@ -431,8 +471,10 @@ class LineDecoder:
         _check_verify(verify)
         pen_search = self._check_pen_search(pen_search)
         whole_line = self._check_whole_line(whole_line, scores, pen_search)
+        margins = self._check_margins(margins, whole_line)
         out, sc, offs, whole = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
-                                         int(line_height), int(line_advance), scores=scores, pen_search=pen_search, whole_line=whole_line)
+                                         int(line_height), int(line_advance), scores=scores, pen_search=pen_search, whole_line=whole_line,
+                                         margins=margins)
         res = (out,)
         if verify:
             mse, imgs = self._verified(verify, int(page_h), int(page_w))

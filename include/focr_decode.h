@@ -229,6 +229,44 @@ int focr_decoder_get_pens(const focr_decoder_t *dec, uint32_t *pens, int64_t *li
  * workgroup take several lines. */
 int focr_decoder_debug_set_whole_grid(focr_decoder_t *dec, uint32_t grid);
 
+/* ---- device: per-character margins of a whole-line run (an extension of the extension) ----------------------------- */
+
+/* Which characters of a whole line to doubt.  Scores stay refused beside the whole-line decode (the plain decoder's
+ * runner-up is the second glyph at one pen, and the programme has no one pen), but a runner-up does have an exact
+ * definition under the programme.  Take a point of the line: every complete pen path has exactly one character whose span
+ * [start pen, end pen) contains it, so the paths split by that covering character, and the best whole line that reads a
+ * different glyph over the middle of a decoded character is a minimum over covering edges.  In the names of the
+ * whole-line definition above (states s in 1/64 px, term(i, s), inc64, n_live = 64 * width):
+ *   - F[t] is the forward cost the programme already has (cost[t] above); F[0] = 0; unreachable states carry no cost;
+ *   - B[t] = 0 for every t >= n_live; for s < n_live, B[s] is the minimum over glyphs i of term(i, s) + B[s + inc64[i]];
+ *     it follows that B[0] equals the line's cost;
+ *   - a decoded character k has glyph i_k, pen s_k and midpoint m_k = s_k + (inc64[i_k] >> 1);
+ *   - an edge (s, i) covers m_k when s is reachable and s <= m_k < s + inc64[i];
+ *   - its through-cost is T(s, i) = F[s] + term(i, s) + B[s + inc64[i]], the cost of the best complete path that uses it.
+ * Per character a margins run returns:
+ *   - term   = term(i_k, s_k); the terms of a line sum to its cost;
+ *   - runner = the glyph i != i_k with the lowest (T, i) over the edges that cover m_k.  Edges of the chosen glyph at
+ *              other pens never count, as with the pen search's runner.  The runner's pen is not reported;
+ *   - margin = that T less the line's cost: >= 0, and 0 for glyphs with identical bitmaps and advances;
+ *   - runner = 0xFFFF and margin = -1 when there is no such edge (a one-glyph alphabet).
+ * |T| stays below the bound a whole-line run already checks (characters per line times T < 2^47): it is the cost of a
+ * complete path.  Forbidding glyph i_k at every state that covers m_k and decoding the line again costs exactly
+ * cost + margin.  The text, pens, costs, verify and launch count (3) of the run are the whole-line run's. */
+typedef struct focr_char_margin {
+    int32_t term;
+    uint16_t runner;
+    uint16_t pad;
+    int64_t margin;
+} focr_char_margin_t;
+
+/* Switch the margins of later whole-line runs on or off (off when the decoder is created; a state of the decoder, not
+ * of the font).  focr_decoder_run refuses, before anything is launched and with a message that names both, margins on
+ * with the whole-line decode off.  With margins off a whole-line run launches what it did before they existed. */
+int focr_decoder_set_whole_margins(focr_decoder_t *dec, int on);
+/* The margins of the last run, in the order of focr_decoder_get and focr_decoder_get_pens: out[n_chars] (may be NULL).
+ * Fails with a message unless the last successful run was a whole-line run with margins on. */
+int focr_decoder_get_margins(const focr_decoder_t *dec, focr_char_margin_t *out);
+
 /* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
 
 /* Upload the verify table of the current decode font (the decoder keeps its own copy).  Refused unless it matches the

@@ -31,6 +31,13 @@ mode is for: nearly every 1/64 px pen is then a state, where a monospace line ha
   whole_over_plain            the ratio of the two
   whole_wall_ms_per_batch     median host time of one decode(whole_line=True) call, pens and costs read back and unpacked
   whole_lines_changed         lines of the batch the mode decodes differently from the plain run
+With --whole-line --margins, also the whole-line decode with per-character margins (LineDecoder.decode(whole_line=True,
+margins=True)), in runs that alternate with whole-line runs without them:
+  margins_device_ms_per_batch median device time of the batch's kernels with margins on (the same 3 launches)
+  margins_whole_device_ms     median device time of the whole-line runs in between
+  margins_over_whole          the ratio of the two
+  margins_wall_ms_per_batch   median host time of one decode(whole_line=True, margins=True) call, margins read back and unpacked
+  margins_text_equal          the margins runs return the whole-line runs' lines, pens and costs
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -83,8 +90,11 @@ def main():
     ap.add_argument("--scores", action="store_true", help="also time the decode with per-character scores on")
     ap.add_argument("--pen-search", type=int, default=0, metavar="N", help="also time the decode with a pen search of N/64 px")
     ap.add_argument("--whole-line", action="store_true", help="also time the whole-line decode")
+    ap.add_argument("--margins", action="store_true", help="with --whole-line: also time the whole-line decode with margins")
     ap.add_argument("--font", default=FONT, metavar="PATH", help="the font of the pages and of the decoder [DejaVu Sans Mono]")
     a = ap.parse_args()
+    if a.margins and not a.whole_line:
+        ap.error("--margins needs --whole-line")
     pages = synth(a.pages, a.seed, font=a.font)
     geo = (45, 39, 608, 12, 15)
     t0 = time.perf_counter()
@@ -148,6 +158,19 @@ def main():
                 wwall.append((time.perf_counter() - t) * 1e3)
                 wdev.append(dec.last_ms)
             wlaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+        if a.margins:
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, whole_line=True, margins=True)
+            mdev, mwall, mwdev = [], [], []
+            for _ in range(a.steps):
+                ref = dec.decode(pages, *geo, whole_line=True)
+                mwdev.append(dec.last_ms)
+                t = time.perf_counter()
+                got = dec.decode(pages, *geo, whole_line=True, margins=True)
+                mwall.append((time.perf_counter() - t) * 1e3)
+                mdev.append(dec.last_ms)
+            mlaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+            mequal = got[0] == ref[0] and got[2] == ref[2] and all(np.array_equal(x, y) for pa, pb in zip(got[1], ref[1]) for x, y in zip(pa, pb))
         if a.test_images:
             for _ in range(a.warmup):
                 dec.test_images(pages, *geo)
@@ -190,6 +213,11 @@ def main():
         res.update({"whole_device_ms_per_batch": round(wms, 4), "whole_device_ms_min": round(float(min(wdev)), 4),
                     "whole_plain_device_ms": round(wpms, 4), "whole_over_plain": round(wms / wpms, 3), "whole_launches": wlaunches,
                     "whole_wall_ms_per_batch": round(float(np.median(wwall)), 3), "whole_lines_changed": changed})
+    if a.margins:
+        mms, mwms = float(np.median(mdev)), float(np.median(mwdev))
+        res.update({"margins_device_ms_per_batch": round(mms, 4), "margins_device_ms_min": round(float(min(mdev)), 4),
+                    "margins_whole_device_ms": round(mwms, 4), "margins_over_whole": round(mms / mwms, 3), "margins_launches": mlaunches,
+                    "margins_wall_ms_per_batch": round(float(np.median(mwall)), 3), "margins_text_equal": bool(mequal)})
     if a.test_images:
         tms = float(np.median(tdev))
         res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
