@@ -373,6 +373,7 @@ DECODE_HIP_SYMBOLS = {
     "focr_decoder_get_pens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "focr_decoder_debug_set_whole_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "focr_decoder_set_whole_margins": (C.c_int, [C.c_void_p, C.c_int]),
+    "focr_decoder_set_whole_slack": (C.c_int, [C.c_void_p, C.c_uint32]),
     "focr_decoder_get_margins": (C.c_int, [C.c_void_p, C.c_void_p]),
     "focr_decoder_set_verify_font": (C.c_int, [C.c_void_p, C.POINTER(VerifyFontStruct)]),
     "focr_decoder_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

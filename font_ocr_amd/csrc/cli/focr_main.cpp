@@ -20,7 +20,11 @@
 //     text only and --verify draws every character at its pen; with --scores or --pen-search it is a usage error;
 //   * --margins PATH is an extension of --whole-line: a CSV row per decoded character with its pen, its term, and the
 //     glyph and margin of the best whole line that reads another glyph over its middle (focr_decoder_get_margins);
-//     stdout and the --verify files are the same with and without it; without --whole-line it is a usage error.
+//     stdout and the --verify files are the same with and without it; without --whole-line it is a usage error;
+//   * --pen-slack N is an extension of --whole-line for text off the 1/64 px grid: every step of the whole-line decode may
+//     move the pen by an offset of -N ..= N (in 1/64 px, at most 64) before its glyph is rendered
+//     (focr_decoder_set_whole_slack); stdout stays text only and --verify draws every character where it was decoded;
+//     without --whole-line, or with --margins or --pen-search, it is a usage error.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -50,7 +54,7 @@ struct Args {
     std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores, margins;
     bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false, have_margins = false;
     float text_size = 0.f, kerning = 1.f;
-    uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0, pen_search = 0;
+    uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0, pen_search = 0, pen_slack = 0;
     bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
 };
 
@@ -88,6 +92,7 @@ void print_help() {
            "      --pen-search <N>                 [extension] Also search pen offsets of up to N/64 px at every step, N <= 64 [default: 0]\n"
            "      --whole-line                     [extension] Decode each line as a whole, for proportional fonts (not with scores or a pen search)\n"
            "      --margins <MARGINS>              [extension] CSV of every character's pen, term, runner-up and margin (only with the whole-line decode)\n"
+           "      --pen-slack <N>                  [extension] Let every step of the whole-line decode move the pen by up to N/64 px, N <= 64 (not with margins or a pen search) [default: 0]\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -150,6 +155,11 @@ Args parse_args(int argc, char **argv) {
             a.pen_search = num_u(s);
             if (a.pen_search > FOCR_PEN_SEARCH_MAX) usage_error("invalid value '" + s + "' for '--pen-search': the radius is at most 64");
         }
+        else if (k == "--pen-slack") {
+            const std::string s = need();
+            a.pen_slack = num_u(s);
+            if (a.pen_slack > FOCR_PEN_SEARCH_MAX) usage_error("invalid value '" + s + "' for '--pen-slack': the radius is at most 64");
+        }
         else if (k == "--whole-line") a.whole_line = true;
         else if (k == "--margins") a.margins = need(), a.have_margins = true;
         else if (k == "-h" || k == "--help") {
@@ -170,6 +180,9 @@ Args parse_args(int argc, char **argv) {
     if (a.whole_line && a.have_scores) usage_error("the argument '--whole-line' cannot be used with '--scores <SCORES>'");
     if (a.whole_line && a.pen_search) usage_error("the argument '--whole-line' cannot be used with '--pen-search <N>'");
     if (a.have_margins && !a.whole_line) usage_error("the argument '--margins <MARGINS>' cannot be used without '--whole-line'");
+    if (a.pen_slack && a.pen_search) usage_error("the argument '--pen-slack <N>' cannot be used with '--pen-search <N>'");
+    if (a.pen_slack && !a.whole_line) usage_error("the argument '--pen-slack <N>' cannot be used without '--whole-line'");
+    if (a.pen_slack && a.have_margins) usage_error("the argument '--pen-slack <N>' cannot be used with '--margins <MARGINS>'");
     return a;
 }
 
@@ -320,6 +333,7 @@ int main(int argc, char **argv) {
     if (csv && focr_decoder_set_scores(dec, 1) != 0) die(std::string("focr_decoder_set_scores: ") + focr_decoder_last_error(dec), 1);
     if (focr_decoder_set_pen_search(dec, args.pen_search) != 0) die(std::string("focr_decoder_set_pen_search: ") + focr_decoder_last_error(dec), 1);
     if (focr_decoder_set_whole_line(dec, args.whole_line) != 0) die(std::string("focr_decoder_set_whole_line: ") + focr_decoder_last_error(dec), 1);
+    if (focr_decoder_set_whole_slack(dec, args.pen_slack) != 0) die(std::string("focr_decoder_set_whole_slack: ") + focr_decoder_last_error(dec), 1);
     if (mcsv && focr_decoder_set_whole_margins(dec, 1) != 0) die(std::string("focr_decoder_set_whole_margins: ") + focr_decoder_last_error(dec), 1);
     const bool csv_offsets = csv && args.pen_search > 0;
 

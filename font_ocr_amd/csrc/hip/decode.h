@@ -203,6 +203,10 @@ struct focr_decoder {
     focr::DevArray<uint32_t> d_inc64, d_pens;
     focr::DevArray<uint16_t> d_back;
     focr::DevArray<int64_t> d_cost;
+    // pen slack of a whole-line run (focr_decoder_set_whole_slack): the workgroups' offset scratch beside d_back; the chosen
+    // offset of every character goes to d_pen, as a search's does; grown by a run with a slack radius
+    uint32_t whole_slack = 0;
+    focr::DevArray<int8_t> d_woff;
     // margins of a whole-line run (focr_decoder_set_whole_margins): the workgroups' forward keys in d_back's place, and per
     // character beside d_chars the term, the runner and the margin; grown by a run with margins on
     bool margins_on = false;

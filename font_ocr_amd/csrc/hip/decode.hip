@@ -14,6 +14,8 @@
 //      over pens in 1/64 px that minimises the sum of the footprint terms along the line, and every character's pen.
 //      With margins as well (focr_decoder_set_whole_margins) line_whole_margins_kernel takes that one's place: the same
 //      programme and a backward sweep, for every character's term, runner-up and margin.
+//      With a pen slack instead (focr_decoder_set_whole_slack) line_whole_slack_kernel takes line_whole_kernel's place: the
+//      programme over pen offsets as well, and every character's render pen and offset.
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
@@ -343,6 +345,7 @@ constexpr uint32_t WHOLE_RING_MAX = 4096;   // keys of the cost ring at most: ri
 constexpr uint64_t WHOLE_COST_BIAS = 1ull << 47;
 constexpr size_t WHOLE_SCRATCH_BUDGET = 64u << 20;  // bytes of backpointer scratch at most (a single workgroup's may exceed it)
 constexpr size_t WHOLE_MARGINS_SCRATCH_BUDGET = 4 * WHOLE_SCRATCH_BUDGET;  // with margins: 64-bit keys in the 16-bit backpointers' place
+constexpr size_t WHOLE_SLACK_SCRATCH_BUDGET = WHOLE_SCRATCH_BUDGET / 2 * 3;  // with slack: an 8-bit offset beside every 16-bit backpointer
 constexpr uint32_t WHOLE_GRID_MAX = 2048;
 
 // Dwords of a line's runner keys (64-bit) and midpoints beside the ring or in the scratch, a multiple of four.
@@ -663,6 +666,147 @@ __global__ __launch_bounds__(WHOLE_THREADS) void line_whole_margins_kernel(const
     }
 }
 
+// ---- whole-line decode with pen slack (focr_decoder_set_whole_slack; the definition is include/focr_decode.h's) ---------
+
+constexpr uint32_t WHOLE_SLACK_MISC_BYTES = WHOLE_MISC_BYTES + 8 * WHOLE_BATCH_MAX;  // line_whole_kernel's, then G of the batch's render pens
+
+// What line_whole_slack_kernel needs beyond the plain programme: the radius, the workgroups' scratch of one offset per
+// state beside the backpointers, and per character (the layout of chars) the chosen offset.
+struct SlackOut {
+    uint32_t radius;   // N >= 1
+    int8_t *scratch;   // per workgroup wp.n_states offsets: off[p] of every render pen the line reached
+    int8_t *offs;
+};
+
+// 3x. line_whole_kernel with pen slack: a step moves the pen by an offset j, -N <= j <= N, before the glyph is rendered.
+// The ring holds the arrival states' keys as before.  A batch is B <= min inc64 - N consecutive render pens [b, b + B):
+// their windows read the states [b - N, b + B + N), and the shortest edge from a render pen at or above b lands at or
+// above b + min inc64 >= b + B + N, so what the batch reads is final when it starts.  Per batch: every
+// arrival state of the batch that was reached leaves its glyph in the scratch, as in line_whole_kernel; every render pen
+// takes the lowest (cost, rank(j)) over its window, 2N + 1 ring reads in rank order with a strict compare, and one
+// that finds a state writes j to the offset scratch, keeps the cost in G and joins the live list; barrier; the (live
+// pen, glyph) candidates are scored at the render pen and pushed from G with the same atomic min; barrier; the states
+// [b - N, b + B - N) are cleared, N late, because the next batch's windows still read the last N states of this one;
+// barrier.  A slot's next tenant is one ring length >= B + 2N + max inc64 on, beyond every target of the batches that
+// still read the slot.  The walk back alternates the two scratches: glyph of t, render pen p = t - inc64, offset of p,
+// arrival state p - j.  A kernel of its own: a run without slack launches what it always did.
+template <bool LDS>
+__global__ __launch_bounds__(WHOLE_THREADS) void line_whole_slack_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
+                                                                         const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
+                                                                         const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps,
+                                                                         const uint32_t *__restrict__ inc64, uint32_t n_glyphs, WholeParams wp,
+                                                                         uint16_t *scratch, uint32_t *__restrict__ n_chars, uint16_t *chars,
+                                                                         uint32_t *pens, int64_t *__restrict__ costs, SlackOut so) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_whole[];  // the waves' end keys and the live count, the live list, G, the ring, then (LDS) the strip
+    uint64_t *red = (uint64_t *)lds_whole;                          // [4]
+    uint32_t *n_live = lds_whole + 8;                               // [1], and [1] the line's character count
+    uint16_t *live = (uint16_t *)(lds_whole + 16);                  // [WHOLE_BATCH_MAX]
+    uint64_t *G = (uint64_t *)(lds_whole + WHOLE_MISC_BYTES / 4);   // [WHOLE_BATCH_MAX]: cost + 2^47 at the batch's render pens
+    uint64_t *ring = (uint64_t *)(lds_whole + WHOLE_SLACK_MISC_BYTES / 4);
+    uint32_t *lds_strip = lds_whole + WHOLE_SLACK_MISC_BYTES / 4 + 2 * (wp.ring_mask + 1);
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t sdw = g.stride / 4, mask = wp.ring_mask, B = wp.batch;
+    const int w = (int)g.w;
+    const uint32_t n_live_states = 64u * g.w;
+    const int N = (int)so.radius, n_rank = 2 * N + 1;
+    uint16_t *back = scratch + (size_t)blockIdx.x * wp.n_states;
+    int8_t *off = so.scratch + (size_t)blockIdx.x * wp.n_states;
+    const uint32_t n_lines = *count;
+    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
+        const uint32_t slot = work[k];
+        uint32_t yc, h;
+        slot_rows(g, slot % g.n_slots, &yc, &h);
+        const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
+        if (LDS) {
+            for (uint32_t q = tid; q < sdw * h; q += WHOLE_THREADS) lds_strip[q] = strip[q];
+            strip = lds_strip;
+        }
+        for (uint32_t q = tid; q <= mask; q += WHOLE_THREADS) ring[q] = q ? ~0ull : (WHOLE_COST_BIAS << 16) | 0xffffu;  // cost[0] = 0, no glyph
+        if (tid == 0) n_live[0] = 0;
+        __syncthreads();
+        for (uint32_t b0 = 0; b0 < n_live_states; b0 += B) {
+            const uint32_t nb = std::min(B, n_live_states - b0);
+            for (uint32_t q = tid; q < nb; q += WHOLE_THREADS) {
+                const int p = (int)(b0 + q);
+                const uint64_t here = ring[(uint32_t)p & mask];
+                if (here != ~0ull) back[p] = (uint16_t)here;  // p as an arrival state
+                uint64_t low = ~0ull >> 16;  // what an unreached state reads: above every biased cost
+                int at = 0;
+                for (int r = 0; r < n_rank; r++) {  // p as a render pen: the lowest (cost, rank)
+                    const int j = rank_offset((uint32_t)r), s = p - j;
+                    if (s < 0 || s >= (int)n_live_states) continue;
+                    const uint64_t c = ring[(uint32_t)s & mask] >> 16;
+                    if (c < low) low = c, at = j;
+                }
+                if (low == ~0ull >> 16) continue;
+                off[p] = (int8_t)at;
+                G[q] = low;
+                live[atomicAdd(&n_live[0], 1u)] = (uint16_t)q;
+            }
+            __syncthreads();
+            const uint32_t nl = n_live[0], n_cand = nl * n_glyphs;  // nl <= 512 and n_glyphs < 65536
+            for (uint32_t c = tid; c < n_cand; c += WHOLE_THREADS) {
+                const uint32_t gi = c / nl, q = live[c - gi * nl], s = b0 + q;
+                const int d = wp.origin_d + (int)s;
+                const int phase = d & 63, shift = d >> 6;
+                const DevGlyph gl = glyphs[gi];
+                const int2 o = offs[gi * 64 + phase];
+                const int term = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
+                                                shift + o.x, o.y);
+                const uint64_t cost = G[q] + (uint64_t)(int64_t)term;  // biased, mod 2^64: stays in (0, 2^48)
+                atomicMin((unsigned long long *)&ring[(s + inc64[gi]) & mask], (unsigned long long)((cost << 16) | gi));
+            }
+            __syncthreads();
+            for (uint32_t q = tid; q < nb; q += WHOLE_THREADS)  // N late: the next batch's windows start at b0 + nb - N
+                if (b0 + q >= (uint32_t)N) ring[(b0 + q - (uint32_t)N) & mask] = ~0ull;
+            if (tid == 0) n_live[0] = 0;
+            __syncthreads();
+        }
+        // the end state: the lowest (cost, t) over t = 64 * w + e, e < max_inc (e < 4096 takes the glyph's place in the key)
+        uint64_t best = ~0ull;
+        for (uint32_t e = tid; e < wp.max_inc; e += WHOLE_THREADS) {
+            const uint64_t key = ring[(n_live_states + e) & mask];
+            if (key != ~0ull) best = std::min<uint64_t>(best, (key & ~(uint64_t)0xffff) | e);
+        }
+        for (int m = 32; m >= 1; m >>= 1) best = std::min(best, shfl_xor_u64(best, m));
+        if (lane == 0) red[wave] = best;
+        __syncthreads();
+        if (tid == 0) {
+            for (uint32_t v = 1; v < WHOLE_THREADS / 64; v++) best = std::min(best, red[v]);
+            uint32_t t = best != ~0ull ? n_live_states + (uint32_t)(best & 0xffffu) : 0, n = 0;
+            uint32_t gi = (uint32_t)ring[t & mask] & 0xffffu;
+            costs[k] = best != ~0ull ? (int64_t)((best >> 16) - WHOLE_COST_BIAS) : 0;
+            while (t > 0 && n < g.cap && gi < n_glyphs && inc64[gi] <= t) {  // back to front; all but t > 0 always hold and only guard the accesses
+                const uint32_t p = t - inc64[gi];
+                if (p >= n_live_states) break;  // never: an edge starts at a render pen below 64 * w
+                const int j = off[p];
+                if (j > (int)p) break;          // never: the window keeps p - j >= 0
+                chars[(size_t)k * g.cap + n] = (uint16_t)gi;
+                pens[(size_t)k * g.cap + n] = p;
+                so.offs[(size_t)k * g.cap + n] = (int8_t)j;
+                n++;
+                t = (uint32_t)((int)p - j);
+                if (t >= n_live_states) break;  // never: the window keeps p - j below 64 * w
+                gi = back[t];
+            }
+            n_chars[k] = n;
+            n_live[1] = n;
+        }
+        __syncthreads();
+        const uint32_t n = n_live[1];
+        for (uint32_t q = tid; q < n / 2; q += WHOLE_THREADS) {  // into text order
+            const size_t a = (size_t)k * g.cap + q, b = (size_t)k * g.cap + n - 1 - q;
+            const uint16_t ca = chars[a], cb = chars[b];
+            const uint32_t pa = pens[a], pb = pens[b];
+            const int8_t ja = so.offs[a], jb = so.offs[b];
+            chars[a] = cb, chars[b] = ca;
+            pens[a] = pb, pens[b] = pa;
+            so.offs[a] = jb, so.offs[b] = ja;
+        }
+        __syncthreads();  // the ring, the strip and the counts are free for the next line
+    }
+}
+
 }  // namespace focr_dec
 
 using namespace focr_dec;
@@ -777,6 +921,11 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     if (n_pages && !pages) return dfail(dec, "focr_decoder_run: null pages");
     if (dec->margins_on && !dec->whole_on)
         return dfail(dec, "focr_decoder_run: margins on with the whole-line decode off (focr_decoder_set_whole_margins needs focr_decoder_set_whole_line)");
+    const uint32_t slack = dec->whole_slack;
+    if (slack && !dec->whole_on)
+        return dfail(dec, "focr_decoder_run: pen slack on with the whole-line decode off (focr_decoder_set_whole_slack needs focr_decoder_set_whole_line)");
+    if (slack && dec->margins_on)
+        return dfail(dec, "focr_decoder_run: pen slack on with margins on (focr_decoder_set_whole_slack does not go with focr_decoder_set_whole_margins yet)");
     const uint32_t radius = dec->pen_search;
     const float reach = (float)radius * 0.015625f;  // exact
     if (reach > dec->min_inc * 0.5f)
@@ -809,16 +958,20 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         }
         if (64ull * g.w + hi >= (1ull << 24))
             return dfail(dec, "focr_decoder_run: whole-line decode needs 64 * width + the largest inc64 below 2^24 (pens must stay exact in f32)");
-        whole_cap = std::max<uint32_t>((64u * g.w + lo - 1) / lo, 1);  // every character advances the pen by at least lo from below 64 * w
+        if (2 * slack > lo)
+            return dfail(dec, "focr_decoder_run: whole-line decode: the pen slack is more than half the smallest inc64 (focr_decoder_set_whole_slack; the pen could crawl)");
+        const uint32_t gain = lo - slack;  // every character advances the arrival state by at least this from below 64 * w; >= 1
+        whole_cap = std::max<uint32_t>((64u * g.w + gain - 1) / gain, 1);
         if ((uint64_t)whole_cap * T >= (1ull << 47))
             return dfail(dec, "focr_decoder_run: whole-line decode: characters per line times the font's score bound reaches 2^47 (a packed cost could overflow)");
         wp.origin_d = 64 * (int)ox;
-        wp.batch = std::min(lo, WHOLE_BATCH_MAX);
+        wp.batch = std::min(gain, WHOLE_BATCH_MAX);
         wp.max_inc = hi;
         uint32_t ring = 64;
-        while (ring < wp.batch + hi && ring <= WHOLE_RING_MAX) ring *= 2;
+        while (ring < wp.batch + 2 * slack + hi && ring <= WHOLE_RING_MAX) ring *= 2;
         if (ring > WHOLE_RING_MAX)
-            return dfail(dec, "focr_decoder_run: whole-line decode: the widest advance is too large (the cost ring does not fit in LDS)");
+            return dfail(dec, slack ? "focr_decoder_run: whole-line decode with pen slack: the widest advance and the slack are too large (the cost ring does not fit in LDS)"
+                                    : "focr_decoder_run: whole-line decode: the widest advance is too large (the cost ring does not fit in LDS)");
         wp.ring_mask = ring - 1;
         wp.n_states = 64u * g.w + hi;
     }
@@ -859,12 +1012,14 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         DEC_GROW(dec->d_base, total);
     }
     const ScoreOut so{dec->d_term, dec->d_runner_term, dec->d_runner, dec->d_base};  // null arrays with scores off: never touched
-    if (radius) DEC_GROW(dec->d_pen, (size_t)g.cap * total);
+    if (radius || slack) DEC_GROW(dec->d_pen, (size_t)g.cap * total);
     uint32_t whole_grid = 0;
     if (whole) {  // as many workgroups as the scratch budget allows (one always), each with 64 * w + max inc64 backpointers
         // with margins a workgroup's scratch is 64-bit words: a forward key per state, then the characters' keys and midpoints
         if (margins) wp.n_states += whole_chars_dwords(g.cap) / 2;
+        // with slack a state has an offset (int8) beside its backpointer, and both count against that run's budget
         const size_t fit = std::max<size_t>(margins ? WHOLE_MARGINS_SCRATCH_BUDGET / ((size_t)wp.n_states * sizeof(uint64_t))
+                                            : slack ? WHOLE_SLACK_SCRATCH_BUDGET / ((size_t)wp.n_states * (sizeof(uint16_t) + sizeof(int8_t)))
                                                     : WHOLE_SCRATCH_BUDGET / ((size_t)wp.n_states * sizeof(uint16_t)), 1);
         whole_grid = (uint32_t)std::min<size_t>({total, fit, WHOLE_GRID_MAX});
         if (dec->whole_grid) whole_grid = std::min(whole_grid, dec->whole_grid);
@@ -875,6 +1030,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
             DEC_GROW(dec->d_margin, (size_t)g.cap * total);
         } else
             DEC_GROW(dec->d_back, (size_t)whole_grid * wp.n_states);
+        if (slack) DEC_GROW(dec->d_woff, (size_t)whole_grid * wp.n_states);
         DEC_GROW(dec->d_pens, (size_t)g.cap * total);
         DEC_GROW(dec->d_cost, total);
         if (!dec->d_inc64.p) DEC_UPLOAD(dec->d_inc64, inc64.data(), inc64.size());
@@ -895,6 +1051,12 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         kernel<<<whole_grid, WHOLE_THREADS, fixed + (lds ? strip_bytes : 0), dec->stream>>>(
             dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
             dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, MarginOut{dec->d_fwd, dec->d_mterm, dec->d_mrunner, dec->d_margin});
+    } else if (whole && slack) {  // the strip shares LDS with the cost ring, the live list and G
+        const size_t ring_bytes = WHOLE_SLACK_MISC_BYTES + ((size_t)wp.ring_mask + 1) * 8;
+        const bool lds = strip_bytes + ring_bytes <= LDS_STRIP_MAX;
+        (lds ? line_whole_slack_kernel<true> : line_whole_slack_kernel<false>)<<<whole_grid, WHOLE_THREADS, ring_bytes + (lds ? strip_bytes : 0), dec->stream>>>(
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
+            dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, SlackOut{slack, dec->d_woff, dec->d_pen});
     } else if (whole) {  // the strip shares LDS with the cost ring and the live list
         const size_t ring_bytes = WHOLE_MISC_BYTES + ((size_t)wp.ring_mask + 1) * 8;
         const bool lds = strip_bytes + ring_bytes <= LDS_STRIP_MAX;
@@ -925,8 +1087,9 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     DEC_CHECK(hipMemcpyAsync(work.data(), dec->d_work, total * 4, hipMemcpyDeviceToHost, dec->stream));
     DEC_CHECK(hipMemcpyAsync(nch.data(), dec->d_nchars, total * 4, hipMemcpyDeviceToHost, dec->stream));
     DEC_CHECK(hipMemcpyAsync(all.data(), dec->d_chars, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
-    std::vector<int8_t> pen(radius ? all.size() : 0);
-    if (radius) DEC_CHECK(hipMemcpyAsync(pen.data(), dec->d_pen, pen.size(), hipMemcpyDeviceToHost, dec->stream));
+    const bool offsets = radius || slack;  // d_pen holds the search's offsets, or the slack's
+    std::vector<int8_t> pen(offsets ? all.size() : 0);
+    if (offsets) DEC_CHECK(hipMemcpyAsync(pen.data(), dec->d_pen, pen.size(), hipMemcpyDeviceToHost, dec->stream));
     std::vector<uint32_t> wpens(whole ? all.size() : 0);
     std::vector<int64_t> wcost(whole ? total : 0);
     if (whole) {
@@ -966,7 +1129,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         l.n_chars = n;
         l.pad = 0;
         dec->chars.insert(dec->chars.end(), all.begin() + (size_t)k * g.cap, all.begin() + (size_t)k * g.cap + n);
-        if (radius) dec->offsets.insert(dec->offsets.end(), pen.begin() + (size_t)k * g.cap, pen.begin() + (size_t)k * g.cap + n);
+        if (offsets) dec->offsets.insert(dec->offsets.end(), pen.begin() + (size_t)k * g.cap, pen.begin() + (size_t)k * g.cap + n);
         if (whole) {
             dec->pens.insert(dec->pens.end(), wpens.begin() + (size_t)k * g.cap, wpens.begin() + (size_t)k * g.cap + n);
             dec->line_cost.push_back(wcost[k]);
@@ -981,7 +1144,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
             dec->char_scores.push_back(c);
         }
     }
-    if (!radius) dec->offsets.assign(dec->chars.size(), 0);
+    if (!offsets) dec->offsets.assign(dec->chars.size(), 0);
     remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
     dec->have_scores = scores;
     dec->have_margins = margins;
@@ -1004,6 +1167,13 @@ extern "C" int focr_decoder_get_offsets(const focr_decoder_t *dec, int8_t *offse
 extern "C" int focr_decoder_set_whole_line(focr_decoder_t *dec, int on) {
     if (!dec) return dfail(nullptr, "focr_decoder_set_whole_line: null decoder");
     dec->whole_on = on != 0;
+    return 0;
+}
+
+extern "C" int focr_decoder_set_whole_slack(focr_decoder_t *dec, uint32_t n) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_whole_slack: null decoder");
+    if (n > FOCR_PEN_SEARCH_MAX) return dfail(dec, "focr_decoder_set_whole_slack: the slack radius is at most 64 (one pixel)");
+    dec->whole_slack = n;
     return 0;
 }
 

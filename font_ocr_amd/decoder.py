@@ -16,6 +16,9 @@
         pages, pens, costs, margins = dec.decode(luma_pages, 45, 39, 608, 12, 15, whole_line=True, margins=True)
         # margins[page][line]: which characters of a whole line to doubt (LineMargins): each one's term, the glyph the
         # best other whole line reads over its middle, and how much worse that line is
+        pages, pens, costs, offsets = dec.decode(luma_pages, 45, 39, 608, 12, 15, whole_line=True, pen_slack=8)
+        # the whole-line decode for text off the 1/64 px grid: every step may move the pen by up to 8/64 px before its glyph
+        # is rendered; pens[page][line]: each character's render pen, offsets[page][line]: the offset it took
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -199,6 +202,7 @@ class LineDecoder:
         self._pen_search = 0  # the library's radius (focr_decoder_set_pen_search)
         self._whole = False  # the library's switch (focr_decoder_set_whole_line)
         self._margins = False  # the library's switch (focr_decoder_set_whole_margins)
+        self._pen_slack = 0  # the library's radius (focr_decoder_set_whole_slack)
 
     def _check(self, rc):
         if rc != 0:
@@ -312,11 +316,15 @@ class LineDecoder:
         return mse, imgs
 
     def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0, whole_line=False,
-             margins=False):
+             margins=False, pen_slack=0):
         """[[(y, text), ...] per page] of one batch; with scores [[LineScores, ...] per page] beside it (else None); with
         a pen search [[int8 offsets, ...] per page] (else None); with whole_line ([[uint32 pens, ...] per page],
-        [[cost, ...] per page]) (else None), and with margins [[LineMargins, ...] per page] as a third element of that."""
+        [[cost, ...] per page]) (else None), and with margins [[LineMargins, ...] per page], or with a pen slack
+        [[int8 offsets, ...] per page], as a third element of that."""
         self._batch = None
+        if int(pen_slack) != self._pen_slack:
+            self._check(self._lib.focr_decoder_set_whole_slack(self._h, int(pen_slack)))
+            self._pen_slack = int(pen_slack)
         if bool(margins) != self._margins:
             self._check(self._lib.focr_decoder_set_whole_margins(self._h, int(bool(margins))))
             self._margins = bool(margins)
@@ -340,7 +348,7 @@ class LineDecoder:
             cs = np.zeros(max(1, nc), dtype=np.dtype([("score", "<i8"), ("runner_score", "<i8"), ("runner", "<u2"), ("pad", "<u2", 3)]))
             base = np.zeros(max(1, nl), dtype=np.uint64)
             self._check(self._lib.focr_decoder_get_scores(self._h, cs.ctypes.data_as(C.POINTER(N.CharScore)), base.ctypes.data))
-        if pen_search:
+        if pen_search or pen_slack:
             js = np.zeros(max(1, nc), dtype=np.int8)
             self._check(self._lib.focr_decoder_get_offsets(self._h, js.ctypes.data))
         if whole_line:
@@ -351,7 +359,7 @@ class LineDecoder:
             ms = np.zeros(max(1, nc), dtype=np.dtype([("term", "<i4"), ("runner", "<u2"), ("pad", "<u2"), ("margin", "<i8")]))
             self._check(self._lib.focr_decoder_get_margins(self._h, ms.ctypes.data))
         alpha = self.font.alphabet
-        whole = ([[] for _ in range(n)], [[] for _ in range(n)]) + (([[] for _ in range(n)],) if margins else ()) if whole_line else None
+        whole = ([[] for _ in range(n)], [[] for _ in range(n)]) + (([[] for _ in range(n)],) if margins or pen_slack else ()) if whole_line else None
         out = [[] for _ in range(n)]
         sc = [[] for _ in range(n)] if scores else None
         offs = [[] for _ in range(n)] if pen_search else None
@@ -364,6 +372,8 @@ class LineDecoder:
             if whole_line:
                 whole[0][ln.page].append(ps[ln.first: ln.first + ln.n_chars].copy())
                 whole[1][ln.page].append(int(lc[k]))
+            if pen_slack:
+                whole[2][ln.page].append(js[ln.first: ln.first + ln.n_chars].copy())
             if margins:
                 m = ms[ln.first: ln.first + ln.n_chars]
                 runner = "".join(LineMargins.NO_RUNNER if i == 0xFFFF else alpha[i] for i in m["runner"])
@@ -393,8 +403,18 @@ class LineDecoder:
             raise ValueError("margins=True needs whole_line=True (the margins are the whole-line decode's)")
         return bool(margins)
 
-    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, margins=False,
-               whole_line=False):
+    @staticmethod
+    def _check_pen_slack(pen_slack, whole_line, margins):
+        if not 0 <= int(pen_slack) <= 64:
+            raise ValueError(f"pen_slack must be 0 .. 64 (1/64 px), not {pen_slack!r}")
+        if int(pen_slack) and not whole_line:
+            raise ValueError("pen_slack needs whole_line=True (the slack is the whole-line decode's; pen_search is the pen loop's)")
+        if int(pen_slack) and margins:
+            raise ValueError("pen_slack does not go with margins=True (margins under a pen slack have no definition yet)")
+        return int(pen_slack)
+
+    def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, pen_slack=0,
+               margins=False, whole_line=False):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
         Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
         mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
@@ -410,13 +430,18 @@ class LineDecoder:
         costs[page][line], the line's sum of footprint terms (int).  The verify then renders every character at its pen.
         It goes with neither scores nor pen_search.  With margins=True as well the result gains one more element after
         costs: margins[page][line], the LineMargins of lines[page][line]: which characters of the line to doubt.
-        margins=True without whole_line raises ValueError."""
+        margins=True without whole_line raises ValueError.  With pen_slack=N > 0 as well (in 1/64 px up to 64, and at
+        most half the font's smallest advance) every step of the whole-line decode may move the pen by an offset of -N ..= N
+        before its glyph is rendered, for pages whose glyphs do not sit on this FreeType's 1/64 px pens; pens then holds
+        each character's render pen and the result gains one last element after costs: offsets[page][line], an int8 array
+        of the offset each character took.  It needs whole_line=True and does not go with margins."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
         pen_search = self._check_pen_search(pen_search)
         whole_line = self._check_whole_line(whole_line, scores, pen_search)
         margins = self._check_margins(margins, whole_line)
+        pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
@@ -425,7 +450,7 @@ class LineDecoder:
         out = [None] * len(pages)
         sc = [None] * len(pages)
         offs = [None] * len(pages)
-        wpens, wcosts, wmargins = [None] * len(pages), [None] * len(pages), [None] * len(pages)
+        wpens, wcosts, wmargins, woffs = [None] * len(pages), [None] * len(pages), [None] * len(pages), [None] * len(pages)
         mse = np.zeros(len(pages), dtype=np.float32)
         images = [None] * len(pages) if verify == "image" else None
         by_size = {}
@@ -434,13 +459,16 @@ class LineDecoder:
         for (h, w), idx in by_size.items():
             batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
             res, res_sc, res_offs, res_whole = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
-                                                         pen_search=pen_search, whole_line=whole_line, margins=margins)
+                                                         pen_search=pen_search, whole_line=whole_line, margins=margins,
+                                                         pen_slack=pen_slack)
             for j, i in enumerate(idx):
                 out[i] = res[j]
                 if whole_line:
                     wpens[i], wcosts[i] = res_whole[0][j], res_whole[1][j]
                 if margins:
                     wmargins[i] = res_whole[2][j]
+                if pen_slack:
+                    woffs[i] = res_whole[2][j]
                 if pen_search:
                     offs[i] = res_offs[j]
                 if scores:
@@ -460,10 +488,12 @@ class LineDecoder:
             res += (wpens, wcosts)
         if margins:
             res += (wmargins,)
+        if pen_slack:
+            res += (woffs,)
         return res if len(res) > 1 else out
 
     def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False,
-                      pen_search=0, margins=False, whole_line=False):
+                      pen_search=0, pen_slack=0, margins=False, whole_line=False):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
         if self.font is None:
@@ -472,9 +502,10 @@ class LineDecoder:
         pen_search = self._check_pen_search(pen_search)
         whole_line = self._check_whole_line(whole_line, scores, pen_search)
         margins = self._check_margins(margins, whole_line)
+        pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
         out, sc, offs, whole = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
                                          int(line_height), int(line_advance), scores=scores, pen_search=pen_search, whole_line=whole_line,
-                                         margins=margins)
+                                         margins=margins, pen_slack=pen_slack)
         res = (out,)
         if verify:
             mse, imgs = self._verified(verify, int(page_h), int(page_w))

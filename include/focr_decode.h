@@ -184,7 +184,8 @@ enum { FOCR_PEN_SEARCH_MAX = 64 };
  * smallest increment (n / 64 > min_increment / 2): the pen could crawl. */
 int focr_decoder_set_pen_search(focr_decoder_t *dec, uint32_t n);
 /* The chosen offset j of every character of the last run, in the order of focr_decoder_get: offsets[n_chars], all zero
- * after a run with the search off. */
+ * after a run with the search off (unless it was a whole-line run with pen slack, focr_decoder_set_whole_slack, whose
+ * offsets these then are). */
 int focr_decoder_get_offsets(const focr_decoder_t *dec, int8_t *offsets);
 
 /* ---- device: whole-line decode (an extension: the reference's pen loop is greedy) ---------------------------------- */
@@ -216,7 +217,7 @@ int focr_decoder_get_offsets(const focr_decoder_t *dec, int8_t *offsets);
  *     packed cost could overflow; the first factor is the exact bound on a line's characters;
  *   - a widest advance so large that the device's cost ring does not fit in LDS (min(min inc64, 512) + max inc64 > 4096);
  *   - scores on (a runner-up has no definition under a dynamic programme yet);
- *   - a pen search radius (a programme over offsets as well is a later step).
+ *   - a pen search radius (the pen loop's search; the programme over offsets as well is focr_decoder_set_whole_slack).
  * With the mode off a run launches and returns what it did before the mode existed. */
 /* Switch the whole-line decode of later runs on or off (off when the decoder is created; a state of the decoder, not of
  * the font). */
@@ -267,6 +268,40 @@ int focr_decoder_set_whole_margins(focr_decoder_t *dec, int on);
  * Fails with a message unless the last successful run was a whole-line run with margins on. */
 int focr_decoder_get_margins(const focr_decoder_t *dec, focr_char_margin_t *out);
 
+/* ---- device: pen slack of a whole-line run (an extension of the extension) ------------------------------------------- */
+
+/* The whole-line programme only allows pens that are exact sums of inc64, so it reads pages whose glyphs sit exactly
+ * where this FreeType build puts them.  Pages snapped to the pixel grid, or set with a slightly different advance, do
+ * not.  The pen loop's remedy is the pen search; this is the programme's.  In the names of the whole-line definition
+ * (states in 1/64 px, term(i, s), inc64, n_live = 64 * width), with a slack radius N (0 <= N <= FOCR_PEN_SEARCH_MAX) a
+ * step moves the pen by an offset j, -N <= j <= N, before the glyph is rendered, and the offset is carried forward, as
+ * in the pen search:
+ *   - cost[0] = 0; every other state starts unreachable;
+ *   - for a render pen p, 0 <= p < n_live: G[p] is the lowest (cost[p - j], rank(j)) over j in -N ..= N for which
+ *     0 <= p - j < n_live and p - j is reachable; rank is the pen search's (0, -1, +1, -2, ...); off[p] is that j; a
+ *     pen p with no such j renders nothing;
+ *   - for t > 0: cost[t] is the minimum over glyphs i of G[t - inc64[i]].cost + term(i, t - inc64[i]); the glyph
+ *     remembered for t is the one with the lowest (cost, i);
+ *   - the line ends in the reachable t >= n_live with the lowest (cost[t], t);
+ *   - read-back from t: i = glyph[t], p = t - inc64[i], j = off[p]; emit character i with pen p and offset j, then
+ *     continue from t = p - j.
+ * A run returns, per character, the alphabet index, the render pen p (focr_decoder_get_pens) and j
+ * (focr_decoder_get_offsets), so focr_decoder_verify draws every character where it was decoded.  pens[0] ==
+ * offsets[0], and pens[q + 1] - offsets[q + 1] == pens[q] + inc64[idx[q]].  A line's cost is the sum of its terms: an
+ * offset costs nothing, and on a tie the offset nearest 0 wins, so a blank stretch takes none.  N = 0 is the plain
+ * whole-line run: the same text, pens, costs and launches.  With N > 0 prepass and compaction are still the plain run's
+ * and the launch count stays 3.  focr_decoder_run refuses, before anything is launched and each with its own message:
+ *   - slack on with the whole-line decode off (the message names both setters);
+ *   - slack on with margins on (margins under slack are a later step; the message names both setters);
+ *   - 2 * N > min inc64: the pen could crawl (the pen search's rule);
+ *   - a cost ring that does not fit in LDS: min(min inc64 - N, 512) + 2 * N + max inc64 > 4096;
+ *   - ceil(64 * width / (min inc64 - N)) * T >= 2^47: a step gains at least min inc64 - N, so the first factor is now the
+ *     exact bound on a line's characters, and a packed cost could overflow;
+ * and what a whole-line run refuses anyway. */
+/* Set the slack radius of later whole-line runs (0 when the decoder is created; a state of the decoder, not of the
+ * font).  n above FOCR_PEN_SEARCH_MAX is refused here. */
+int focr_decoder_set_whole_slack(focr_decoder_t *dec, uint32_t n);
+
 /* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
 
 /* Upload the verify table of the current decode font (the decoder keeps its own copy).  Refused unless it matches the
@@ -281,7 +316,7 @@ int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_verify_font_t *
  * reference's MSE is (float)sum / (float)(uint32_t)(page_w * page_h)).  For a run from device-memory pages, the
  * caller's page buffer must still hold those pages.  After a run with a pen search every character is rendered at
  * the pen the run chose for it (pen + j / 64, then the increment from there), and after a whole-line run at
- * pos = s / 64 of its returned pen s, so the image shows the line where it was decoded.  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
+ * pos = s / 64 of its returned pen s (with pen slack that is the render pen), so the image shows the line where it was decoded.  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
  * without a successful run since the last set_font, or without a verify table. */
 int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums);
 /* Device time of the last verify's kernels in ms (events), and their launch count (constant per batch). */

@@ -38,6 +38,14 @@ margins=True)), in runs that alternate with whole-line runs without them:
   margins_over_whole          the ratio of the two
   margins_wall_ms_per_batch   median host time of one decode(whole_line=True, margins=True) call, margins read back and unpacked
   margins_text_equal          the margins runs return the whole-line runs' lines, pens and costs
+With --whole-line --pen-slack N, also the whole-line decode with a pen slack of N/64 px (LineDecoder.decode(whole_line=True,
+pen_slack=N)), in runs that alternate with whole-line runs without it:
+  slack_device_ms_per_batch   median device time of the batch's kernels with the slack on (the same 3 launches)
+  slack_whole_device_ms       median device time of the whole-line runs in between
+  slack_over_whole            the ratio of the two
+  slack_wall_ms_per_batch     median host time of one decode(whole_line=True, pen_slack=N) call, offsets read back and unpacked
+  slack_lines_changed         lines of the batch the slack decodes differently from the whole-line run
+  slack_chars_offset          characters of the batch that took an offset other than 0
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -91,10 +99,13 @@ def main():
     ap.add_argument("--pen-search", type=int, default=0, metavar="N", help="also time the decode with a pen search of N/64 px")
     ap.add_argument("--whole-line", action="store_true", help="also time the whole-line decode")
     ap.add_argument("--margins", action="store_true", help="with --whole-line: also time the whole-line decode with margins")
+    ap.add_argument("--pen-slack", type=int, default=0, metavar="N", help="with --whole-line: also time the whole-line decode with a pen slack of N/64 px")
     ap.add_argument("--font", default=FONT, metavar="PATH", help="the font of the pages and of the decoder [DejaVu Sans Mono]")
     a = ap.parse_args()
     if a.margins and not a.whole_line:
         ap.error("--margins needs --whole-line")
+    if a.pen_slack and not a.whole_line:
+        ap.error("--pen-slack needs --whole-line")
     pages = synth(a.pages, a.seed, font=a.font)
     geo = (45, 39, 608, 12, 15)
     t0 = time.perf_counter()
@@ -171,6 +182,18 @@ def main():
                 mdev.append(dec.last_ms)
             mlaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
             mequal = got[0] == ref[0] and got[2] == ref[2] and all(np.array_equal(x, y) for pa, pb in zip(got[1], ref[1]) for x, y in zip(pa, pb))
+        if a.pen_slack:
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, whole_line=True, pen_slack=a.pen_slack)
+            kdev, kwall, kwdev = [], [], []
+            for _ in range(a.steps):
+                kref = dec.decode(pages, *geo, whole_line=True)
+                kwdev.append(dec.last_ms)
+                t = time.perf_counter()
+                kgot = dec.decode(pages, *geo, whole_line=True, pen_slack=a.pen_slack)
+                kwall.append((time.perf_counter() - t) * 1e3)
+                kdev.append(dec.last_ms)
+            klaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
         if a.test_images:
             for _ in range(a.warmup):
                 dec.test_images(pages, *geo)
@@ -218,6 +241,13 @@ def main():
         res.update({"margins_device_ms_per_batch": round(mms, 4), "margins_device_ms_min": round(float(min(mdev)), 4),
                     "margins_whole_device_ms": round(mwms, 4), "margins_over_whole": round(mms / mwms, 3), "margins_launches": mlaunches,
                     "margins_wall_ms_per_batch": round(float(np.median(mwall)), 3), "margins_text_equal": bool(mequal)})
+    if a.pen_slack:
+        kms, kwms = float(np.median(kdev)), float(np.median(kwdev))
+        changed = sum(ta != tb for pa, pb in zip(kref[0], kgot[0]) for (_, ta), (_, tb) in zip(pa, pb))
+        moved = sum(int(np.count_nonzero(o)) for pg in kgot[3] for o in pg)
+        res.update({"pen_slack": a.pen_slack, "slack_device_ms_per_batch": round(kms, 4), "slack_device_ms_min": round(float(min(kdev)), 4),
+                    "slack_whole_device_ms": round(kwms, 4), "slack_over_whole": round(kms / kwms, 3), "slack_launches": klaunches,
+                    "slack_wall_ms_per_batch": round(float(np.median(kwall)), 3), "slack_lines_changed": changed, "slack_chars_offset": moved})
     if a.test_images:
         tms = float(np.median(tdev))
         res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
