@@ -1,5 +1,5 @@
-// decode.h — what the two halves of the `focr` decoder share (decode.hip: font and line decoder; decode_images.hip: the
-// verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels (ncc_images.hip
+// decode.h — what the files of the `focr` decoder share (decode.hip: font and line decoder; decode_whole.hip: its whole-line
+// decode, with decode_line.h between the two; decode_images.hip: the verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels (ncc_images.hip
 // is its third user), the blank test's crop, the decoder itself, and the host plumbing every entry point repeats (errors, stages, staging, refusals).
 #pragma once
 

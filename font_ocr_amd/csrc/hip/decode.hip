@@ -10,27 +10,22 @@
 //      (focr_decoder_set_scores) the same launch also keeps the second lowest key and sums r^2 over the line's crop.
 //      With a pen search radius (focr_decoder_set_pen_search) line_search_kernel takes its place: one workgroup per line,
 //      the argmin over (glyph, pen offset), and the chosen offset of every step beside its glyph.
-//      With the whole-line decode on (focr_decoder_set_whole_line) line_whole_kernel takes its place: a dynamic programme
-//      over pens in 1/64 px that minimises the sum of the footprint terms along the line, and every character's pen.
-//      With margins as well (focr_decoder_set_whole_margins) line_whole_margins_kernel takes that one's place: the same
-//      programme and a backward sweep, for every character's term, runner-up and margin.
-//      With a pen slack instead (focr_decoder_set_whole_slack) line_whole_slack_kernel takes line_whole_kernel's place: the
-//      programme over pen offsets as well, and every character's render pen and offset.
+//      With the whole-line decode on (focr_decoder_set_whole_line) one of decode_whole.hip's kernels takes its place: a
+//      dynamic programme over pens in 1/64 px, with margins or with a pen slack when those are on.
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
 // order of the sums nor the device changes a choice.  The pen update is one f32 add of the host-computed increment.
 //
-// The verify and --test images of a batch are decode_images.hip's; decode.h holds what the two files share.
+// The verify and --test images of a batch are decode_images.hip's; decode.h holds what the decoder's files share, and
+// decode_line.h what this file shares with decode_whole.hip.
 #include <cmath>
 #include <cstring>
 
-#include "decode.h"
+#include "decode_line.h"
 
 namespace focr_dec {
 
-constexpr uint32_t PAD = 4;                 // zero bytes left of a strip row (reads up to 3 bytes left of column 0)
-constexpr uint32_t LDS_STRIP_MAX = 65536;   // the strip is staged in LDS up to this many bytes, else read from global
 constexpr uint32_t PREPASS_THREADS = 256;
 constexpr uint32_t COMPACT_THREADS = 1024;
 
@@ -80,13 +75,6 @@ __global__ __launch_bounds__(COMPACT_THREADS) void line_compact_kernel(const uin
         __syncthreads();
     }
     if (threadIdx.x == 0) *count = base;
-}
-
-__device__ __forceinline__ uint32_t edge_mask(int base, int w) {
-    uint32_t m = 0;
-    for (int b = 0; b < 4; b++)
-        if (base + b >= 0 && base + b < w) m |= 0xffu << (8 * b);
-    return m;
 }
 
 // The wave's sum of every lane's v, in every lane.
@@ -200,9 +188,8 @@ constexpr uint32_t SEARCH_THREADS = 256;    // one workgroup of four waves per w
 constexpr uint32_t SEARCH_WAVES = SEARCH_THREADS / 64;
 constexpr uint32_t SEARCH_RED_BYTES = 2 * SEARCH_WAVES * 2 * 8;  // two parities of (best, other) per wave, behind the strip
 
-// A search key: (score, rank of the offset, glyph index), lowest first.  rank(0) = 0, rank(-1) = 1, rank(+1) = 2, ...
+// A search key: (score, rank of the offset, glyph index), lowest first (rank_offset, decode_line.h).
 __device__ __forceinline__ uint32_t key_glyph(uint64_t key) { return (uint32_t)key & 0xffffu; }
-__device__ __forceinline__ int rank_offset(uint32_t rank) { return rank & 1 ? -(int)((rank + 1) >> 1) : (int)(rank >> 1); }
 
 // The minimum of two sets of keys, and the minimum of those of their keys whose glyph is not the minimum's.  Each set
 // comes as (best, other): its lowest key, and its lowest key of another glyph than best's (~0: none).  The winner's
@@ -214,11 +201,6 @@ __device__ __forceinline__ void merge_other_glyph(uint64_t &best, uint64_t &othe
     const uint64_t o_win = keep ? other : o2, o_lose = keep ? o2 : other;
     other = std::min(o_win, key_glyph(lose) != key_glyph(win) ? lose : o_lose);  // an empty set's ~0 names no glyph
     best = win;
-}
-
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
-    return ((uint64_t)hi << 32) | lo;
 }
 
 // 3s. the pen loop with a search over (glyph, pen offset), one workgroup per work-list line.  The candidates of a step,
@@ -336,477 +318,6 @@ __global__ __launch_bounds__(SEARCH_THREADS) void line_search_kernel(const uint8
     if (tid == 0) n_chars[k] = n;
 }
 
-// ---- whole-line decode (focr_decoder_set_whole_line; an extension, see include/focr_decode.h) ------------------------
-
-constexpr uint32_t WHOLE_THREADS = 256;     // one workgroup of four waves per work-list line at a time
-constexpr uint32_t WHOLE_BATCH_MAX = 512;   // states per batch at most (and at most the smallest inc64)
-constexpr uint32_t WHOLE_MISC_BYTES = 64 + 2 * WHOLE_BATCH_MAX;  // the waves' end keys, the live count; the batch's live states
-constexpr uint32_t WHOLE_RING_MAX = 4096;   // keys of the cost ring at most: ring and the rest stay inside LDS_STRIP_MAX
-constexpr uint64_t WHOLE_COST_BIAS = 1ull << 47;
-constexpr size_t WHOLE_SCRATCH_BUDGET = 64u << 20;  // bytes of backpointer scratch at most (a single workgroup's may exceed it)
-constexpr size_t WHOLE_MARGINS_SCRATCH_BUDGET = 4 * WHOLE_SCRATCH_BUDGET;  // with margins: 64-bit keys in the 16-bit backpointers' place
-constexpr size_t WHOLE_SLACK_SCRATCH_BUDGET = WHOLE_SCRATCH_BUDGET / 2 * 3;  // with slack: an 8-bit offset beside every 16-bit backpointer
-constexpr uint32_t WHOLE_GRID_MAX = 2048;
-
-// Dwords of a line's runner keys (64-bit) and midpoints beside the ring or in the scratch, a multiple of four.
-__host__ __device__ constexpr uint32_t whole_chars_dwords(uint32_t cap) { return (3 * cap + 3) & ~3u; }
-
-struct WholeParams {
-    int origin_d;        // 64 * origin_x
-    uint32_t batch;      // B: states per batch, <= the smallest inc64
-    uint32_t ring_mask;  // ring length - 1; the length is a power of two >= B + max_inc
-    uint32_t max_inc;    // the largest inc64
-    uint32_t n_states;   // 64 * w + max_inc: the scratch of one workgroup
-};
-
-// The footprint term of one glyph rendering against a strip: the sum over the bitmap's pixels inside the crop (w columns,
-// h rows) of c * (c - 2 r), the inner loop of line_decode_kernel.  The two older kernels keep their own copy: calling this
-// from them changes their machine code (tools/isa_hash.py), and the plain decoder's instruction stream is what its
-// benchmark pins.
-__device__ __forceinline__ int footprint_term(const uint32_t *strip, uint32_t sdw, int w, uint32_t h, const uint32_t *__restrict__ tile,
-                                              uint32_t ndw, uint32_t box_h, int x0, int y0) {
-    const int r_lo = std::max(0, -y0), r_hi = std::min((int)box_h, (int)h - y0);
-    uint32_t cc = 0, cr = 0;
-    for (int r = r_lo; r < r_hi; r++) {
-        const uint32_t *srow = strip + (size_t)(y0 + r) * sdw;
-        const uint32_t *trow = tile + (size_t)r * ndw;
-        for (uint32_t q = 0; q < ndw; q++) {
-            const int base = x0 + 4 * (int)q;
-            if (base <= -4 || base >= w) continue;
-            uint32_t c = trow[q];
-            if (base < 0 || base + 4 > w) c &= edge_mask(base, w);
-            const uint32_t a = (uint32_t)(base + (int)PAD);
-            const uint32_t rv = __builtin_amdgcn_alignbyte(srow[(a >> 2) + 1], srow[a >> 2], a & 3);
-            cr = __builtin_amdgcn_udot4(c, rv, cr, false);
-            cc = __builtin_amdgcn_udot4(c, c, cc, false);
-        }
-    }
-    return (int)cc - 2 * (int)cr;
-}
-
-// 3w. the dynamic programme over pens in 1/64 px, one workgroup per work-list line at a time (k = blockIdx.x, then
-// += gridDim.x).  ring[s & mask] holds state s's key ((cost + 2^47) << 16 | remembered glyph; ~0: unreachable) while s is
-// within ring length of the batch.  A batch is B <= min inc64 consecutive states: no step is shorter than B, so nothing
-// scored in a batch lands in it and its keys are final when it starts.  Per batch: every reachable state's glyph goes to
-// the scratch and the state to the live list; barrier; the (live state, glyph) candidates, glyph-major over the lanes
-// (neighbouring lanes share a box), are scored and pushed with an LDS 64-bit atomic min, whose order cannot matter;
-// barrier; the batch's slots are cleared for the states one ring length on; barrier.  The targets of a batch reach at
-// most B - 1 + max_inc past its start, so they never alias a live slot.  At the end the states 64 * w .. (all still in
-// the ring) are reduced to the lowest (cost, state), thread 0 walks the scratch back, and the workgroup turns the
-// result into text order.  The scratch needs no clearing: the walk visits only states this line reached and wrote.
-template <bool LDS>
-__global__ __launch_bounds__(WHOLE_THREADS) void line_whole_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
-                                                                   const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
-                                                                   const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps,
-                                                                   const uint32_t *__restrict__ inc64, uint32_t n_glyphs, WholeParams wp,
-                                                                   uint16_t *scratch, uint32_t *__restrict__ n_chars, uint16_t *chars,
-                                                                   uint32_t *pens, int64_t *__restrict__ costs) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_whole[];  // the waves' end keys and the live count, the live list, the ring, then (LDS) the strip
-    uint64_t *red = (uint64_t *)lds_whole;                          // [4]
-    uint32_t *n_live = lds_whole + 8;                               // [1], and [1] the line's character count
-    uint16_t *live = (uint16_t *)(lds_whole + 16);                  // [WHOLE_BATCH_MAX]
-    uint64_t *ring = (uint64_t *)(lds_whole + WHOLE_MISC_BYTES / 4);
-    uint32_t *lds_strip = lds_whole + WHOLE_MISC_BYTES / 4 + 2 * (wp.ring_mask + 1);
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t sdw = g.stride / 4, mask = wp.ring_mask, B = wp.batch;
-    const int w = (int)g.w;
-    const uint32_t n_live_states = 64u * g.w;
-    uint16_t *back = scratch + (size_t)blockIdx.x * wp.n_states;
-    const uint32_t n_lines = *count;
-    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
-        const uint32_t slot = work[k];
-        uint32_t yc, h;
-        slot_rows(g, slot % g.n_slots, &yc, &h);
-        const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
-        if (LDS) {
-            for (uint32_t q = tid; q < sdw * h; q += WHOLE_THREADS) lds_strip[q] = strip[q];
-            strip = lds_strip;
-        }
-        for (uint32_t q = tid; q <= mask; q += WHOLE_THREADS) ring[q] = q ? ~0ull : (WHOLE_COST_BIAS << 16) | 0xffffu;  // cost[0] = 0, no glyph
-        if (tid == 0) n_live[0] = 0;
-        __syncthreads();
-        for (uint32_t b0 = 0; b0 < n_live_states; b0 += B) {
-            const uint32_t nb = std::min(B, n_live_states - b0);
-            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) {
-                const uint64_t key = ring[(b0 + j) & mask];
-                if (key == ~0ull) continue;
-                back[b0 + j] = (uint16_t)key;
-                live[atomicAdd(&n_live[0], 1u)] = (uint16_t)j;
-            }
-            __syncthreads();
-            const uint32_t nl = n_live[0], n_cand = nl * n_glyphs;  // nl <= 512 and n_glyphs < 65536
-            for (uint32_t c = tid; c < n_cand; c += WHOLE_THREADS) {
-                const uint32_t gi = c / nl, s = b0 + live[c - gi * nl];
-                const int d = wp.origin_d + (int)s;
-                const int phase = d & 63, shift = d >> 6;
-                const DevGlyph gl = glyphs[gi];
-                const int2 o = offs[gi * 64 + phase];
-                const int term = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
-                                                shift + o.x, o.y);
-                const uint64_t cost = (ring[s & mask] >> 16) + (uint64_t)(int64_t)term;  // biased, mod 2^64: stays in (0, 2^48)
-                atomicMin((unsigned long long *)&ring[(s + inc64[gi]) & mask], (unsigned long long)((cost << 16) | gi));
-            }
-            __syncthreads();
-            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) ring[(b0 + j) & mask] = ~0ull;
-            if (tid == 0) n_live[0] = 0;
-            __syncthreads();
-        }
-        // the end state: the lowest (cost, t) over t = 64 * w + e, e < max_inc (e < 4096 takes the glyph's place in the key)
-        uint64_t best = ~0ull;
-        for (uint32_t e = tid; e < wp.max_inc; e += WHOLE_THREADS) {
-            const uint64_t key = ring[(n_live_states + e) & mask];
-            if (key != ~0ull) best = std::min<uint64_t>(best, (key & ~(uint64_t)0xffff) | e);
-        }
-        for (int m = 32; m >= 1; m >>= 1) best = std::min(best, shfl_xor_u64(best, m));
-        if (lane == 0) red[wave] = best;
-        __syncthreads();
-        if (tid == 0) {
-            for (uint32_t v = 1; v < WHOLE_THREADS / 64; v++) best = std::min(best, red[v]);
-            // some end state is reachable (every step from a state below 64 * w lands somewhere); without one the line is empty
-            uint32_t t = best != ~0ull ? n_live_states + (uint32_t)(best & 0xffffu) : 0, n = 0;
-            uint32_t gi = (uint32_t)ring[t & mask] & 0xffffu;
-            costs[k] = best != ~0ull ? (int64_t)((best >> 16) - WHOLE_COST_BIAS) : 0;
-            while (t > 0 && n < g.cap && gi < n_glyphs && inc64[gi] <= t) {  // back to front; all but t > 0 always hold (the host's bound; a reached state's glyph) and only guard the accesses
-                t -= inc64[gi];
-                chars[(size_t)k * g.cap + n] = (uint16_t)gi;
-                pens[(size_t)k * g.cap + n] = t;
-                n++;
-                gi = back[t];
-            }
-            n_chars[k] = n;
-            n_live[1] = n;
-        }
-        __syncthreads();
-        const uint32_t n = n_live[1];
-        for (uint32_t q = tid; q < n / 2; q += WHOLE_THREADS) {  // into text order
-            const size_t a = (size_t)k * g.cap + q, b = (size_t)k * g.cap + n - 1 - q;
-            const uint16_t ca = chars[a], cb = chars[b];
-            const uint32_t pa = pens[a], pb = pens[b];
-            chars[a] = cb, chars[b] = ca;
-            pens[a] = pb, pens[b] = pa;
-        }
-        __syncthreads();  // the ring, the strip and the counts are free for the next line
-    }
-}
-
-// What line_whole_margins_kernel needs beyond the plain programme: the workgroups' scratch of 64-bit words (per
-// workgroup wp.n_states of them: every live state's forward key, then cap runner keys and cap midpoints for the lines
-// whose characters do not fit in LDS), and per character (the layout of chars) the results of include/focr_decode.h.
-struct MarginOut {
-    uint64_t *scratch;
-    int32_t *term;
-    uint16_t *runner;
-    int64_t *margin;
-};
-
-// 3m. line_whole_kernel with margins (focr_decoder_set_whole_margins; the definition is include/focr_decode.h's): the same
-// programme, whose batches also leave every state's key in the workgroup's scratch (~0: not reached, so this scratch is
-// written for every state of the line; the low 16 bits of a key are the backpointer), then, line by line, the backward
-// sweep described below.  A kernel of its own and not a switch of line_whole_kernel's: sharing the body changed that
-// kernel's machine code (tools/isa_hash.py), and a run without margins launches what it always did.
-template <bool LDS, bool CHARS_LDS>
-__global__ __launch_bounds__(WHOLE_THREADS) void line_whole_margins_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
-                                                                           const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
-                                                                           const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps,
-                                                                           const uint32_t *__restrict__ inc64, uint32_t n_glyphs, WholeParams wp,
-                                                                           uint32_t *__restrict__ n_chars, uint16_t *chars, uint32_t *pens,
-                                                                           int64_t *__restrict__ costs, MarginOut mo) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_whole[];  // the waves' end keys and the live count, the live list, the ring, then (LDS) the strip
-    uint64_t *red = (uint64_t *)lds_whole;                          // [4]
-    uint32_t *n_live = lds_whole + 8;                               // [1], and [1] the line's character count
-    uint16_t *live = (uint16_t *)(lds_whole + 16);                  // [WHOLE_BATCH_MAX]
-    uint64_t *ring = (uint64_t *)(lds_whole + WHOLE_MISC_BYTES / 4);
-    uint32_t *lds_strip = lds_whole + WHOLE_MISC_BYTES / 4 + 2 * (wp.ring_mask + 1);
-    if (CHARS_LDS) lds_strip += whole_chars_dwords(g.cap);  // the characters' runner keys and midpoints come before the strip
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t sdw = g.stride / 4, mask = wp.ring_mask, B = wp.batch;
-    const int w = (int)g.w;
-    const uint32_t n_live_states = 64u * g.w;
-    uint64_t *fwd = mo.scratch + (size_t)blockIdx.x * wp.n_states;  // the forward keys, in the backpointers' place
-    uint64_t *cost_b = (uint64_t *)(lds_whole + 10);                // the line's cost + 2^47, for every thread
-    const uint32_t n_lines = *count;
-    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
-        const uint32_t slot = work[k];
-        uint32_t yc, h;
-        slot_rows(g, slot % g.n_slots, &yc, &h);
-        const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
-        if (LDS) {
-            for (uint32_t q = tid; q < sdw * h; q += WHOLE_THREADS) lds_strip[q] = strip[q];
-            strip = lds_strip;
-        }
-        for (uint32_t q = tid; q <= mask; q += WHOLE_THREADS) ring[q] = q ? ~0ull : (WHOLE_COST_BIAS << 16) | 0xffffu;  // cost[0] = 0, no glyph
-        if (tid == 0) n_live[0] = 0;
-        __syncthreads();
-        for (uint32_t b0 = 0; b0 < n_live_states; b0 += B) {
-            const uint32_t nb = std::min(B, n_live_states - b0);
-            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) {
-                const uint64_t key = ring[(b0 + j) & mask];
-                fwd[b0 + j] = key;  // every state of the batch: ~0 marks the ones this line did not reach
-                if (key == ~0ull) continue;
-                live[atomicAdd(&n_live[0], 1u)] = (uint16_t)j;
-            }
-            __syncthreads();
-            const uint32_t nl = n_live[0], n_cand = nl * n_glyphs;  // nl <= 512 and n_glyphs < 65536
-            for (uint32_t c = tid; c < n_cand; c += WHOLE_THREADS) {
-                const uint32_t gi = c / nl, s = b0 + live[c - gi * nl];
-                const int d = wp.origin_d + (int)s;
-                const int phase = d & 63, shift = d >> 6;
-                const DevGlyph gl = glyphs[gi];
-                const int2 o = offs[gi * 64 + phase];
-                const int term = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
-                                                shift + o.x, o.y);
-                const uint64_t cost = (ring[s & mask] >> 16) + (uint64_t)(int64_t)term;  // biased, mod 2^64: stays in (0, 2^48)
-                atomicMin((unsigned long long *)&ring[(s + inc64[gi]) & mask], (unsigned long long)((cost << 16) | gi));
-            }
-            __syncthreads();
-            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) ring[(b0 + j) & mask] = ~0ull;
-            if (tid == 0) n_live[0] = 0;
-            __syncthreads();
-        }
-        // the end state: the lowest (cost, t) over t = 64 * w + e, e < max_inc (e < 4096 takes the glyph's place in the key)
-        uint64_t best = ~0ull;
-        for (uint32_t e = tid; e < wp.max_inc; e += WHOLE_THREADS) {
-            const uint64_t key = ring[(n_live_states + e) & mask];
-            if (key != ~0ull) best = std::min<uint64_t>(best, (key & ~(uint64_t)0xffff) | e);
-        }
-        for (int m = 32; m >= 1; m >>= 1) best = std::min(best, shfl_xor_u64(best, m));
-        if (lane == 0) red[wave] = best;
-        __syncthreads();
-        if (tid == 0) {
-            for (uint32_t v = 1; v < WHOLE_THREADS / 64; v++) best = std::min(best, red[v]);
-            // some end state is reachable (every step from a state below 64 * w lands somewhere); without one the line is empty
-            uint32_t t = best != ~0ull ? n_live_states + (uint32_t)(best & 0xffffu) : 0, n = 0;
-            uint32_t gi = (uint32_t)ring[t & mask] & 0xffffu;
-            costs[k] = best != ~0ull ? (int64_t)((best >> 16) - WHOLE_COST_BIAS) : 0;
-            while (t > 0 && n < g.cap && gi < n_glyphs && inc64[gi] <= t) {  // back to front; all but t > 0 always hold (the host's bound; a reached state's glyph) and only guard the accesses
-                t -= inc64[gi];
-                chars[(size_t)k * g.cap + n] = (uint16_t)gi;
-                pens[(size_t)k * g.cap + n] = t;
-                n++;
-                gi = (uint32_t)fwd[t] & 0xffffu;
-            }
-            n_chars[k] = n;
-            n_live[1] = n;
-            cost_b[0] = best >> 16;
-        }
-        __syncthreads();
-        const uint32_t n = n_live[1];
-        for (uint32_t q = tid; q < n / 2; q += WHOLE_THREADS) {  // into text order
-            const size_t a = (size_t)k * g.cap + q, b = (size_t)k * g.cap + n - 1 - q;
-            const uint16_t ca = chars[a], cb = chars[b];
-            const uint32_t pa = pens[a], pb = pens[b];
-            chars[a] = cb, chars[b] = ca;
-            pens[a] = pb, pens[b] = pa;
-        }
-        __syncthreads();  // chars and pens are in text order
-        if (n == 0) continue;  // uniform
-        // The backward sweep of include/focr_decode.h.  ring[t & mask] now holds B[t] + 2^47 while t is within ring length
-        // of the batch: every slot starts at B = 0 (the states from 64 * w on; the others are cleared before they are
-        // used), and the batches are the forward pass's, last to first.  Per batch: its slots are cleared and its reached
-        // states listed; barrier; every (state, glyph) edge takes B of its target, which lies above the batch and is
-        // final, pushes term + B into its own state's slot, and pushes its through-cost into the runner key of every
-        // character whose midpoint it covers and whose glyph is another; barrier; the count is reset; barrier.  The
-        // slots of a batch alias states one ring length on, above every target of this and of later batches.
-        const size_t row = (size_t)k * g.cap;
-        uint64_t *rkey = CHARS_LDS ? ring + mask + 1 : fwd + wp.n_states - whole_chars_dwords(g.cap) / 2;  // [cap]
-        uint32_t *mids = (uint32_t *)(rkey + g.cap);                                                      // [cap], ascending
-        for (uint32_t q = tid; q < n; q += WHOLE_THREADS) {
-            mids[q] = pens[row + q] + (inc64[chars[row + q]] >> 1);
-            rkey[q] = ~0ull;
-        }
-        for (uint32_t q = tid; q <= mask; q += WHOLE_THREADS) ring[q] = WHOLE_COST_BIAS;
-        __syncthreads();
-        const uint64_t line_cost = cost_b[0];
-        for (uint32_t b0 = (n_live_states - 1) / B * B;; b0 -= B) {  // n_live_states > 0: a line has characters
-            const uint32_t nb = std::min(B, n_live_states - b0);
-            for (uint32_t j = tid; j < nb; j += WHOLE_THREADS) {
-                ring[(b0 + j) & mask] = ~0ull;
-                if (fwd[b0 + j] != ~0ull) live[atomicAdd(&n_live[0], 1u)] = (uint16_t)j;
-            }
-            __syncthreads();
-            const uint32_t nl = n_live[0], n_cand = nl * n_glyphs;
-            for (uint32_t c = tid; c < n_cand; c += WHOLE_THREADS) {
-                const uint32_t gi = c / nl, s = b0 + live[c - gi * nl], t = s + inc64[gi];
-                const int d = wp.origin_d + (int)s;
-                const int phase = d & 63, shift = d >> 6;
-                const DevGlyph gl = glyphs[gi];
-                const int2 o = offs[gi * 64 + phase];
-                const int term = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
-                                                shift + o.x, o.y);
-                const uint64_t rest = ring[t & mask] + (uint64_t)(int64_t)term;  // term + B[t], biased: in (0, 2^48)
-                atomicMin((unsigned long long *)&ring[s & mask], (unsigned long long)rest);
-                const uint64_t through = (fwd[s] >> 16) + rest - WHOLE_COST_BIAS;  // F[s] + term + B[t], biased: a whole path's cost
-                uint32_t lo = 0, hi = n;  // the first midpoint at or after s
-                while (lo < hi) {
-                    const uint32_t m = (lo + hi) >> 1;
-                    if (mids[m] < s) lo = m + 1;
-                    else hi = m;
-                }
-                for (; lo < n && mids[lo] < t; lo++)
-                    if (chars[row + lo] != gi) atomicMin((unsigned long long *)&rkey[lo], (unsigned long long)((through << 16) | gi));
-            }
-            __syncthreads();
-            if (tid == 0) n_live[0] = 0;
-            __syncthreads();
-            if (b0 == 0) break;
-        }
-        for (uint32_t q = tid; q < n; q += WHOLE_THREADS) {
-            const uint32_t gi = chars[row + q];
-            const int d = wp.origin_d + (int)pens[row + q];
-            const int phase = d & 63, shift = d >> 6;
-            const DevGlyph gl = glyphs[gi];
-            const int2 o = offs[gi * 64 + phase];
-            mo.term[row + q] = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
-                                              shift + o.x, o.y);
-            const uint64_t key = rkey[q];  // ~0: no edge of another glyph (a one-glyph alphabet); its index reads 0xffff
-            mo.runner[row + q] = (uint16_t)key;
-            mo.margin[row + q] = key != ~0ull ? (int64_t)((key >> 16) - line_cost) : -1;
-        }
-        __syncthreads();  // the ring, the characters' keys and the strip are free for the next line
-    }
-}
-
-// ---- whole-line decode with pen slack (focr_decoder_set_whole_slack; the definition is include/focr_decode.h's) ---------
-
-constexpr uint32_t WHOLE_SLACK_MISC_BYTES = WHOLE_MISC_BYTES + 8 * WHOLE_BATCH_MAX;  // line_whole_kernel's, then G of the batch's render pens
-
-// What line_whole_slack_kernel needs beyond the plain programme: the radius, the workgroups' scratch of one offset per
-// state beside the backpointers, and per character (the layout of chars) the chosen offset.
-struct SlackOut {
-    uint32_t radius;   // N >= 1
-    int8_t *scratch;   // per workgroup wp.n_states offsets: off[p] of every render pen the line reached
-    int8_t *offs;
-};
-
-// 3x. line_whole_kernel with pen slack: a step moves the pen by an offset j, -N <= j <= N, before the glyph is rendered.
-// The ring holds the arrival states' keys as before.  A batch is B <= min inc64 - N consecutive render pens [b, b + B):
-// their windows read the states [b - N, b + B + N), and the shortest edge from a render pen at or above b lands at or
-// above b + min inc64 >= b + B + N, so what the batch reads is final when it starts.  Per batch: every
-// arrival state of the batch that was reached leaves its glyph in the scratch, as in line_whole_kernel; every render pen
-// takes the lowest (cost, rank(j)) over its window, 2N + 1 ring reads in rank order with a strict compare, and one
-// that finds a state writes j to the offset scratch, keeps the cost in G and joins the live list; barrier; the (live
-// pen, glyph) candidates are scored at the render pen and pushed from G with the same atomic min; barrier; the states
-// [b - N, b + B - N) are cleared, N late, because the next batch's windows still read the last N states of this one;
-// barrier.  A slot's next tenant is one ring length >= B + 2N + max inc64 on, beyond every target of the batches that
-// still read the slot.  The walk back alternates the two scratches: glyph of t, render pen p = t - inc64, offset of p,
-// arrival state p - j.  A kernel of its own: a run without slack launches what it always did.
-template <bool LDS>
-__global__ __launch_bounds__(WHOLE_THREADS) void line_whole_slack_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
-                                                                         const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
-                                                                         const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps,
-                                                                         const uint32_t *__restrict__ inc64, uint32_t n_glyphs, WholeParams wp,
-                                                                         uint16_t *scratch, uint32_t *__restrict__ n_chars, uint16_t *chars,
-                                                                         uint32_t *pens, int64_t *__restrict__ costs, SlackOut so) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_whole[];  // the waves' end keys and the live count, the live list, G, the ring, then (LDS) the strip
-    uint64_t *red = (uint64_t *)lds_whole;                          // [4]
-    uint32_t *n_live = lds_whole + 8;                               // [1], and [1] the line's character count
-    uint16_t *live = (uint16_t *)(lds_whole + 16);                  // [WHOLE_BATCH_MAX]
-    uint64_t *G = (uint64_t *)(lds_whole + WHOLE_MISC_BYTES / 4);   // [WHOLE_BATCH_MAX]: cost + 2^47 at the batch's render pens
-    uint64_t *ring = (uint64_t *)(lds_whole + WHOLE_SLACK_MISC_BYTES / 4);
-    uint32_t *lds_strip = lds_whole + WHOLE_SLACK_MISC_BYTES / 4 + 2 * (wp.ring_mask + 1);
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t sdw = g.stride / 4, mask = wp.ring_mask, B = wp.batch;
-    const int w = (int)g.w;
-    const uint32_t n_live_states = 64u * g.w;
-    const int N = (int)so.radius, n_rank = 2 * N + 1;
-    uint16_t *back = scratch + (size_t)blockIdx.x * wp.n_states;
-    int8_t *off = so.scratch + (size_t)blockIdx.x * wp.n_states;
-    const uint32_t n_lines = *count;
-    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
-        const uint32_t slot = work[k];
-        uint32_t yc, h;
-        slot_rows(g, slot % g.n_slots, &yc, &h);
-        const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
-        if (LDS) {
-            for (uint32_t q = tid; q < sdw * h; q += WHOLE_THREADS) lds_strip[q] = strip[q];
-            strip = lds_strip;
-        }
-        for (uint32_t q = tid; q <= mask; q += WHOLE_THREADS) ring[q] = q ? ~0ull : (WHOLE_COST_BIAS << 16) | 0xffffu;  // cost[0] = 0, no glyph
-        if (tid == 0) n_live[0] = 0;
-        __syncthreads();
-        for (uint32_t b0 = 0; b0 < n_live_states; b0 += B) {
-            const uint32_t nb = std::min(B, n_live_states - b0);
-            for (uint32_t q = tid; q < nb; q += WHOLE_THREADS) {
-                const int p = (int)(b0 + q);
-                const uint64_t here = ring[(uint32_t)p & mask];
-                if (here != ~0ull) back[p] = (uint16_t)here;  // p as an arrival state
-                uint64_t low = ~0ull >> 16;  // what an unreached state reads: above every biased cost
-                int at = 0;
-                for (int r = 0; r < n_rank; r++) {  // p as a render pen: the lowest (cost, rank)
-                    const int j = rank_offset((uint32_t)r), s = p - j;
-                    if (s < 0 || s >= (int)n_live_states) continue;
-                    const uint64_t c = ring[(uint32_t)s & mask] >> 16;
-                    if (c < low) low = c, at = j;
-                }
-                if (low == ~0ull >> 16) continue;
-                off[p] = (int8_t)at;
-                G[q] = low;
-                live[atomicAdd(&n_live[0], 1u)] = (uint16_t)q;
-            }
-            __syncthreads();
-            const uint32_t nl = n_live[0], n_cand = nl * n_glyphs;  // nl <= 512 and n_glyphs < 65536
-            for (uint32_t c = tid; c < n_cand; c += WHOLE_THREADS) {
-                const uint32_t gi = c / nl, q = live[c - gi * nl], s = b0 + q;
-                const int d = wp.origin_d + (int)s;
-                const int phase = d & 63, shift = d >> 6;
-                const DevGlyph gl = glyphs[gi];
-                const int2 o = offs[gi * 64 + phase];
-                const int term = footprint_term(strip, sdw, w, h, bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h,
-                                                shift + o.x, o.y);
-                const uint64_t cost = G[q] + (uint64_t)(int64_t)term;  // biased, mod 2^64: stays in (0, 2^48)
-                atomicMin((unsigned long long *)&ring[(s + inc64[gi]) & mask], (unsigned long long)((cost << 16) | gi));
-            }
-            __syncthreads();
-            for (uint32_t q = tid; q < nb; q += WHOLE_THREADS)  // N late: the next batch's windows start at b0 + nb - N
-                if (b0 + q >= (uint32_t)N) ring[(b0 + q - (uint32_t)N) & mask] = ~0ull;
-            if (tid == 0) n_live[0] = 0;
-            __syncthreads();
-        }
-        // the end state: the lowest (cost, t) over t = 64 * w + e, e < max_inc (e < 4096 takes the glyph's place in the key)
-        uint64_t best = ~0ull;
-        for (uint32_t e = tid; e < wp.max_inc; e += WHOLE_THREADS) {
-            const uint64_t key = ring[(n_live_states + e) & mask];
-            if (key != ~0ull) best = std::min<uint64_t>(best, (key & ~(uint64_t)0xffff) | e);
-        }
-        for (int m = 32; m >= 1; m >>= 1) best = std::min(best, shfl_xor_u64(best, m));
-        if (lane == 0) red[wave] = best;
-        __syncthreads();
-        if (tid == 0) {
-            for (uint32_t v = 1; v < WHOLE_THREADS / 64; v++) best = std::min(best, red[v]);
-            uint32_t t = best != ~0ull ? n_live_states + (uint32_t)(best & 0xffffu) : 0, n = 0;
-            uint32_t gi = (uint32_t)ring[t & mask] & 0xffffu;
-            costs[k] = best != ~0ull ? (int64_t)((best >> 16) - WHOLE_COST_BIAS) : 0;
-            while (t > 0 && n < g.cap && gi < n_glyphs && inc64[gi] <= t) {  // back to front; all but t > 0 always hold and only guard the accesses
-                const uint32_t p = t - inc64[gi];
-                if (p >= n_live_states) break;  // never: an edge starts at a render pen below 64 * w
-                const int j = off[p];
-                if (j > (int)p) break;          // never: the window keeps p - j >= 0
-                chars[(size_t)k * g.cap + n] = (uint16_t)gi;
-                pens[(size_t)k * g.cap + n] = p;
-                so.offs[(size_t)k * g.cap + n] = (int8_t)j;
-                n++;
-                t = (uint32_t)((int)p - j);
-                if (t >= n_live_states) break;  // never: the window keeps p - j below 64 * w
-                gi = back[t];
-            }
-            n_chars[k] = n;
-            n_live[1] = n;
-        }
-        __syncthreads();
-        const uint32_t n = n_live[1];
-        for (uint32_t q = tid; q < n / 2; q += WHOLE_THREADS) {  // into text order
-            const size_t a = (size_t)k * g.cap + q, b = (size_t)k * g.cap + n - 1 - q;
-            const uint16_t ca = chars[a], cb = chars[b];
-            const uint32_t pa = pens[a], pb = pens[b];
-            const int8_t ja = so.offs[a], jb = so.offs[b];
-            chars[a] = cb, chars[b] = ca;
-            pens[a] = pb, pens[b] = pa;
-            so.offs[a] = jb, so.offs[b] = ja;
-        }
-        __syncthreads();  // the ring, the strip and the counts are free for the next line
-    }
-}
-
 }  // namespace focr_dec
 
 using namespace focr_dec;
@@ -900,23 +411,43 @@ extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font
     return 0;
 }
 
-extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int on_device, size_t n_pages, size_t page_w, size_t page_h,
-                                uint32_t x_start, uint32_t y_start, uint32_t width, uint32_t line_height, uint32_t line_advance) {
-    if (!dec) return dfail(nullptr, "focr_decoder_run: null decoder");
-    dec->run_ok = false;
+namespace {
+
+// A run starts: the results of the last one are gone, whatever becomes of this one.
+void clear_results(focr_decoder *dec) {
+    dec->run_ok = dec->have_scores = dec->have_whole = dec->have_margins = false;
     dec->lines.clear();
     dec->chars.clear();
-    dec->have_scores = false;
     dec->char_scores.clear();
     dec->line_base.clear();
     dec->offsets.clear();
-    dec->have_whole = false;
     dec->pens.clear();
     dec->line_cost.clear();
-    dec->have_margins = false;
     dec->margins.clear();
     dec->run.ms = 0.f;
     dec->run.launches = 0;
+}
+
+// The first n elements of a device array into v, queued on the decoder's stream.
+template <typename T>
+int read_back(focr_decoder *dec, std::vector<T> &v, const T *d, size_t n) {
+    v.resize(n);
+    DEC_CHECK(hipMemcpyAsync(v.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, dec->stream));
+    return 0;
+}
+
+// The n results of work-list line k, [k * cap, k * cap + n) of the device's array, behind those of the lines before it.
+template <typename T>
+void append_line(std::vector<T> &to, const std::vector<T> &all, size_t k, uint32_t cap, uint32_t n) {
+    to.insert(to.end(), all.begin() + k * cap, all.begin() + k * cap + n);
+}
+
+}  // namespace
+
+extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int on_device, size_t n_pages, size_t page_w, size_t page_h,
+                                uint32_t x_start, uint32_t y_start, uint32_t width, uint32_t line_height, uint32_t line_advance) {
+    if (!dec) return dfail(nullptr, "focr_decoder_run: null decoder");
+    clear_results(dec);
     if (!dec->n_glyphs) return dfail(dec, "focr_decoder_run: no font (focr_decoder_set_font)");
     if (n_pages && !pages) return dfail(dec, "focr_decoder_run: null pages");
     if (dec->margins_on && !dec->whole_on)
@@ -937,44 +468,8 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     if (stage_in(dec, dec->d_pages, pages, on_device, page_w * page_h * n_pages, &d_src)) return 1;
     const size_t total = g.total;
     const bool scores = dec->scores_on, whole = dec->whole_on, margins = dec->margins_on;
-    WholeParams wp{};
-    std::vector<uint32_t> inc64;
-    uint32_t whole_cap = 1;
-    if (whole) {  // the refusals of include/focr_decode.h, before anything is launched
-        if (scores) return dfail(dec, "focr_decoder_run: whole-line decode with scores on (a runner-up has no definition under the dynamic programme)");
-        if (radius) return dfail(dec, "focr_decoder_run: whole-line decode with a pen search radius (the dynamic programme does not search offsets)");
-        const float ox = dec->origin_x;
-        if (!(ox >= 0.f && ox <= 65536.f && ox == floorf(ox)))
-            return dfail(dec, "focr_decoder_run: whole-line decode needs origin_x to be a whole number >= 0 (at most 65536)");
-        uint32_t lo = ~0u, hi = 0;
-        uint64_t T = 0;  // set_font's own bound on a term's magnitude
-        inc64.resize(dec->n_glyphs);
-        for (uint32_t i = 0; i < dec->n_glyphs; i++) {
-            const float v = rintf(dec->inc[i] * 64.0f);
-            if (!(v >= 1.f)) return dfail(dec, "focr_decoder_run: whole-line decode needs every pen increment to be at least 1/64 px (an inc64 below 1)");
-            inc64[i] = v < 16777216.f ? (uint32_t)v : (1u << 24);
-            lo = std::min(lo, inc64[i]), hi = std::max(hi, inc64[i]);
-            T = std::max<uint64_t>(T, (uint64_t)dec->font_glyphs[i].stride * dec->font_glyphs[i].box_h * 2 * 255 * 255);
-        }
-        if (64ull * g.w + hi >= (1ull << 24))
-            return dfail(dec, "focr_decoder_run: whole-line decode needs 64 * width + the largest inc64 below 2^24 (pens must stay exact in f32)");
-        if (2 * slack > lo)
-            return dfail(dec, "focr_decoder_run: whole-line decode: the pen slack is more than half the smallest inc64 (focr_decoder_set_whole_slack; the pen could crawl)");
-        const uint32_t gain = lo - slack;  // every character advances the arrival state by at least this from below 64 * w; >= 1
-        whole_cap = std::max<uint32_t>((64u * g.w + gain - 1) / gain, 1);
-        if ((uint64_t)whole_cap * T >= (1ull << 47))
-            return dfail(dec, "focr_decoder_run: whole-line decode: characters per line times the font's score bound reaches 2^47 (a packed cost could overflow)");
-        wp.origin_d = 64 * (int)ox;
-        wp.batch = std::min(gain, WHOLE_BATCH_MAX);
-        wp.max_inc = hi;
-        uint32_t ring = 64;
-        while (ring < wp.batch + 2 * slack + hi && ring <= WHOLE_RING_MAX) ring *= 2;
-        if (ring > WHOLE_RING_MAX)
-            return dfail(dec, slack ? "focr_decoder_run: whole-line decode with pen slack: the widest advance and the slack are too large (the cost ring does not fit in LDS)"
-                                    : "focr_decoder_run: whole-line decode: the widest advance is too large (the cost ring does not fit in LDS)");
-        wp.ring_mask = ring - 1;
-        wp.n_states = 64u * g.w + hi;
-    }
+    WholePlan plan;
+    if (whole && whole_plan(dec, g, &plan)) return 1;  // the refusals of include/focr_decode.h, before anything is launched
     if (total == 0) {  // nothing to decode and nothing launched; a verify still draws the pages
         DEC_CHECK(hipStreamSynchronize(dec->stream));
         remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
@@ -996,73 +491,32 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
             p = radius ? (p - reach) + dec->min_inc : p + dec->min_inc;
             if (++steps > (1u << 20)) return dfail(dec, "focr_decoder_run: the pen advance is too small for the line width");
         }
-        g.cap = whole ? whole_cap : std::max<uint32_t>(steps, 1);
+        g.cap = whole ? plan.cap : std::max<uint32_t>(steps, 1);
     }
-    const size_t strip_bytes = (size_t)g.stride * g.line_height;
+    const size_t strip_bytes = (size_t)g.stride * g.line_height, n_all = (size_t)g.cap * total;
     DEC_GROW(dec->d_strips, strip_bytes * total);
     DEC_GROW(dec->d_flags, total);
     DEC_GROW(dec->d_work, total);
     DEC_GROW(dec->d_nchars, total);
     DEC_GROW(dec->d_count, 1);
-    DEC_GROW(dec->d_chars, (size_t)g.cap * total);
+    DEC_GROW(dec->d_chars, n_all);
     if (scores) {
-        DEC_GROW(dec->d_term, (size_t)g.cap * total);
-        DEC_GROW(dec->d_runner_term, (size_t)g.cap * total);
-        DEC_GROW(dec->d_runner, (size_t)g.cap * total);
+        DEC_GROW(dec->d_term, n_all);
+        DEC_GROW(dec->d_runner_term, n_all);
+        DEC_GROW(dec->d_runner, n_all);
         DEC_GROW(dec->d_base, total);
     }
     const ScoreOut so{dec->d_term, dec->d_runner_term, dec->d_runner, dec->d_base};  // null arrays with scores off: never touched
-    if (radius || slack) DEC_GROW(dec->d_pen, (size_t)g.cap * total);
-    uint32_t whole_grid = 0;
-    if (whole) {  // as many workgroups as the scratch budget allows (one always), each with 64 * w + max inc64 backpointers
-        // with margins a workgroup's scratch is 64-bit words: a forward key per state, then the characters' keys and midpoints
-        if (margins) wp.n_states += whole_chars_dwords(g.cap) / 2;
-        // with slack a state has an offset (int8) beside its backpointer, and both count against that run's budget
-        const size_t fit = std::max<size_t>(margins ? WHOLE_MARGINS_SCRATCH_BUDGET / ((size_t)wp.n_states * sizeof(uint64_t))
-                                            : slack ? WHOLE_SLACK_SCRATCH_BUDGET / ((size_t)wp.n_states * (sizeof(uint16_t) + sizeof(int8_t)))
-                                                    : WHOLE_SCRATCH_BUDGET / ((size_t)wp.n_states * sizeof(uint16_t)), 1);
-        whole_grid = (uint32_t)std::min<size_t>({total, fit, WHOLE_GRID_MAX});
-        if (dec->whole_grid) whole_grid = std::min(whole_grid, dec->whole_grid);
-        if (margins) {
-            DEC_GROW(dec->d_fwd, (size_t)whole_grid * wp.n_states);
-            DEC_GROW(dec->d_mterm, (size_t)g.cap * total);
-            DEC_GROW(dec->d_mrunner, (size_t)g.cap * total);
-            DEC_GROW(dec->d_margin, (size_t)g.cap * total);
-        } else
-            DEC_GROW(dec->d_back, (size_t)whole_grid * wp.n_states);
-        if (slack) DEC_GROW(dec->d_woff, (size_t)whole_grid * wp.n_states);
-        DEC_GROW(dec->d_pens, (size_t)g.cap * total);
-        DEC_GROW(dec->d_cost, total);
-        if (!dec->d_inc64.p) DEC_UPLOAD(dec->d_inc64, inc64.data(), inc64.size());
-    }
+    if (radius || slack) DEC_GROW(dec->d_pen, n_all);
+    if (whole && whole_reserve(dec, g, plan)) return 1;
 
     DEC_CHECK(hipEventRecord(dec->run.begin, dec->stream));
     line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
     DEC_CHECK(hipGetLastError());
     line_compact_kernel<<<1, COMPACT_THREADS, 0, dec->stream>>>(dec->d_flags, g.total, dec->d_work, dec->d_count);
     DEC_CHECK(hipGetLastError());
-    if (whole && margins) {  // the characters' keys and midpoints come first: beside the ring when they fit, then the strip when it still fits
-        const size_t ring_bytes = WHOLE_MISC_BYTES + ((size_t)wp.ring_mask + 1) * 8, chars_bytes = (size_t)whole_chars_dwords(g.cap) * 4;
-        const bool chars_lds = ring_bytes + chars_bytes <= LDS_STRIP_MAX;
-        const size_t fixed = ring_bytes + (chars_lds ? chars_bytes : 0);
-        const bool lds = strip_bytes + fixed <= LDS_STRIP_MAX;
-        const auto kernel = lds ? (chars_lds ? line_whole_margins_kernel<true, true> : line_whole_margins_kernel<true, false>)
-                                : (chars_lds ? line_whole_margins_kernel<false, true> : line_whole_margins_kernel<false, false>);
-        kernel<<<whole_grid, WHOLE_THREADS, fixed + (lds ? strip_bytes : 0), dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
-            dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, MarginOut{dec->d_fwd, dec->d_mterm, dec->d_mrunner, dec->d_margin});
-    } else if (whole && slack) {  // the strip shares LDS with the cost ring, the live list and G
-        const size_t ring_bytes = WHOLE_SLACK_MISC_BYTES + ((size_t)wp.ring_mask + 1) * 8;
-        const bool lds = strip_bytes + ring_bytes <= LDS_STRIP_MAX;
-        (lds ? line_whole_slack_kernel<true> : line_whole_slack_kernel<false>)<<<whole_grid, WHOLE_THREADS, ring_bytes + (lds ? strip_bytes : 0), dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
-            dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, SlackOut{slack, dec->d_woff, dec->d_pen});
-    } else if (whole) {  // the strip shares LDS with the cost ring and the live list
-        const size_t ring_bytes = WHOLE_MISC_BYTES + ((size_t)wp.ring_mask + 1) * 8;
-        const bool lds = strip_bytes + ring_bytes <= LDS_STRIP_MAX;
-        (lds ? line_whole_kernel<true> : line_whole_kernel<false>)<<<whole_grid, WHOLE_THREADS, ring_bytes + (lds ? strip_bytes : 0), dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
-            dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost);
+    if (whole) {
+        whole_launch(dec, g, plan, strip_bytes);
     } else if (radius) {  // the strip shares LDS with the reduction pairs, so it stays in LDS up to that much less
         const bool lds = strip_bytes + SEARCH_RED_BYTES <= LDS_STRIP_MAX;
         const auto search = lds ? (scores ? line_search_kernel<true, true> : line_search_kernel<true, false>)
@@ -1080,46 +534,29 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->run.end, dec->stream));
 
-    uint32_t count = 0;
-    std::vector<uint32_t> work(total), nch(total);
-    std::vector<uint16_t> all((size_t)g.cap * total);
-    DEC_CHECK(hipMemcpyAsync(&count, dec->d_count, 4, hipMemcpyDeviceToHost, dec->stream));
-    DEC_CHECK(hipMemcpyAsync(work.data(), dec->d_work, total * 4, hipMemcpyDeviceToHost, dec->stream));
-    DEC_CHECK(hipMemcpyAsync(nch.data(), dec->d_nchars, total * 4, hipMemcpyDeviceToHost, dec->stream));
-    DEC_CHECK(hipMemcpyAsync(all.data(), dec->d_chars, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
     const bool offsets = radius || slack;  // d_pen holds the search's offsets, or the slack's
-    std::vector<int8_t> pen(offsets ? all.size() : 0);
-    if (offsets) DEC_CHECK(hipMemcpyAsync(pen.data(), dec->d_pen, pen.size(), hipMemcpyDeviceToHost, dec->stream));
-    std::vector<uint32_t> wpens(whole ? all.size() : 0);
-    std::vector<int64_t> wcost(whole ? total : 0);
-    if (whole) {
-        DEC_CHECK(hipMemcpyAsync(wpens.data(), dec->d_pens, wpens.size() * 4, hipMemcpyDeviceToHost, dec->stream));
-        DEC_CHECK(hipMemcpyAsync(wcost.data(), dec->d_cost, total * 8, hipMemcpyDeviceToHost, dec->stream));
-    }
-    std::vector<int32_t> mterm(margins ? all.size() : 0);
-    std::vector<uint16_t> mrunner(margins ? all.size() : 0);
-    std::vector<int64_t> mmargin(margins ? all.size() : 0);
-    if (margins) {
-        DEC_CHECK(hipMemcpyAsync(mterm.data(), dec->d_mterm, all.size() * 4, hipMemcpyDeviceToHost, dec->stream));
-        DEC_CHECK(hipMemcpyAsync(mrunner.data(), dec->d_mrunner, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
-        DEC_CHECK(hipMemcpyAsync(mmargin.data(), dec->d_margin, all.size() * 8, hipMemcpyDeviceToHost, dec->stream));
-    }
-    std::vector<int32_t> term, runner_term;
-    std::vector<uint16_t> runner;
+    std::vector<uint32_t> count, work, nch, wpens;
+    std::vector<uint16_t> all, mrunner, runner;
+    std::vector<int8_t> pen;
+    std::vector<int64_t> wcost, mmargin;
+    std::vector<int32_t> mterm, term, runner_term;
     std::vector<uint64_t> base;
-    if (scores) {
-        term.resize(all.size()), runner_term.resize(all.size()), runner.resize(all.size()), base.resize(total);
-        DEC_CHECK(hipMemcpyAsync(term.data(), dec->d_term, all.size() * 4, hipMemcpyDeviceToHost, dec->stream));
-        DEC_CHECK(hipMemcpyAsync(runner_term.data(), dec->d_runner_term, all.size() * 4, hipMemcpyDeviceToHost, dec->stream));
-        DEC_CHECK(hipMemcpyAsync(runner.data(), dec->d_runner, all.size() * 2, hipMemcpyDeviceToHost, dec->stream));
-        DEC_CHECK(hipMemcpyAsync(base.data(), dec->d_base, total * 8, hipMemcpyDeviceToHost, dec->stream));
-    }
+    if (read_back(dec, count, dec->d_count.p, 1) || read_back(dec, work, dec->d_work.p, total) || read_back(dec, nch, dec->d_nchars.p, total) ||
+        read_back(dec, all, dec->d_chars.p, n_all))
+        return 1;
+    if (offsets && read_back(dec, pen, dec->d_pen.p, n_all)) return 1;
+    if (whole && (read_back(dec, wpens, dec->d_pens.p, n_all) || read_back(dec, wcost, dec->d_cost.p, total))) return 1;
+    if (margins && (read_back(dec, mterm, dec->d_mterm.p, n_all) || read_back(dec, mrunner, dec->d_mrunner.p, n_all) || read_back(dec, mmargin, dec->d_margin.p, n_all)))
+        return 1;
+    if (scores && (read_back(dec, term, dec->d_term.p, n_all) || read_back(dec, runner_term, dec->d_runner_term.p, n_all) ||
+                   read_back(dec, runner, dec->d_runner.p, n_all) || read_back(dec, base, dec->d_base.p, total)))
+        return 1;
     DEC_CHECK(hipStreamSynchronize(dec->stream));
     DEC_CHECK(hipEventElapsedTime(&dec->run.ms, dec->run.begin, dec->run.end));
     dec->run.launches = 3;
-    if (count > total) return dfail(dec, "focr_decoder_run: inconsistent line count from the device");
-    dec->lines.resize(count);
-    for (uint32_t k = 0; k < count; k++) {
+    if (count[0] > total) return dfail(dec, "focr_decoder_run: inconsistent line count from the device");
+    dec->lines.resize(count[0]);
+    for (uint32_t k = 0; k < count[0]; k++) {
         const uint32_t slot = work[k], n = nch[k];
         if (slot >= total || n > g.cap) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
         focr_decoded_line_t &l = dec->lines[k];
@@ -1128,10 +565,10 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         l.first = dec->chars.size();
         l.n_chars = n;
         l.pad = 0;
-        dec->chars.insert(dec->chars.end(), all.begin() + (size_t)k * g.cap, all.begin() + (size_t)k * g.cap + n);
-        if (offsets) dec->offsets.insert(dec->offsets.end(), pen.begin() + (size_t)k * g.cap, pen.begin() + (size_t)k * g.cap + n);
+        append_line(dec->chars, all, k, g.cap, n);
+        if (offsets) append_line(dec->offsets, pen, k, g.cap, n);
         if (whole) {
-            dec->pens.insert(dec->pens.end(), wpens.begin() + (size_t)k * g.cap, wpens.begin() + (size_t)k * g.cap + n);
+            append_line(dec->pens, wpens, k, g.cap, n);
             dec->line_cost.push_back(wcost[k]);
         }
         for (size_t at = (size_t)k * g.cap; margins && at < (size_t)k * g.cap + n; at++)

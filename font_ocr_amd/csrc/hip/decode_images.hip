@@ -3,7 +3,7 @@
 //
 // focr_decoder_verify draws focr --verify's image of the last run (decode.hip) in two launches, from the run's own buffers:
 //   4. verify_layout_kernel: one wave per work-list line repeats render()'s f32 arithmetic (pen, round_out bounds, the
-//      26.6 delta of every glyph; after a run with a pen search or a whole-line run, from the pens the run chose) and
+//      26.6 delta of every glyph; after a run with a pen search or a whole-line run (decode_whole.hip), from the pens the run chose) and
 //      writes each glyph's
 //      true bitmap rectangle, clipped to the canvas and the page;
 //   5. verify_compose_kernel: one workgroup per (page, 16 rows, 256 columns) tile takes, line by line in order, the

@@ -1,0 +1,76 @@
+// decode_line.h — what the two translation units of the `focr` line decoder share (decode.hip: prepass, compaction, the pen
+// loop and its search, and the run itself; decode_whole.hip: the whole-line decode): the strip's constants, the device
+// helpers both files' kernels call (no relocatable device code: they are inlined into each), and the whole-line decode's
+// plan, which focr_decoder_run asks for and hands back.
+#pragma once
+
+#include "decode.h"
+
+namespace focr_dec {
+
+constexpr uint32_t PAD = 4;                 // zero bytes left of a strip row (reads up to 3 bytes left of column 0)
+constexpr uint32_t LDS_STRIP_MAX = 65536;   // the strip is staged in LDS up to this many bytes, else read from global
+
+__device__ __forceinline__ uint32_t edge_mask(int base, int w) {
+    uint32_t m = 0;
+    for (int b = 0; b < 4; b++)
+        if (base + b >= 0 && base + b < w) m |= 0xffu << (8 * b);
+    return m;
+}
+
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// The pen offset of a rank, lowest rank first: rank(0) = 0, rank(-1) = 1, rank(+1) = 2, ...
+__device__ __forceinline__ int rank_offset(uint32_t rank) { return rank & 1 ? -(int)((rank + 1) >> 1) : (int)(rank >> 1); }
+
+// The footprint term of one glyph rendering against a strip: the sum over the bitmap's pixels inside the crop (w columns,
+// h rows) of c * (c - 2 r), the inner loop of line_decode_kernel.  line_decode_kernel and line_search_kernel keep their own
+// copy: calling this from them changes their machine code (tools/isa_hash.py), and the plain decoder's instruction stream
+// is what its benchmark pins.
+__device__ __forceinline__ int footprint_term(const uint32_t *strip, uint32_t sdw, int w, uint32_t h, const uint32_t *__restrict__ tile,
+                                              uint32_t ndw, uint32_t box_h, int x0, int y0) {
+    const int r_lo = std::max(0, -y0), r_hi = std::min((int)box_h, (int)h - y0);
+    uint32_t cc = 0, cr = 0;
+    for (int r = r_lo; r < r_hi; r++) {
+        const uint32_t *srow = strip + (size_t)(y0 + r) * sdw;
+        const uint32_t *trow = tile + (size_t)r * ndw;
+        for (uint32_t q = 0; q < ndw; q++) {
+            const int base = x0 + 4 * (int)q;
+            if (base <= -4 || base >= w) continue;
+            uint32_t c = trow[q];
+            if (base < 0 || base + 4 > w) c &= edge_mask(base, w);
+            const uint32_t a = (uint32_t)(base + (int)PAD);
+            const uint32_t rv = __builtin_amdgcn_alignbyte(srow[(a >> 2) + 1], srow[a >> 2], a & 3);
+            cr = __builtin_amdgcn_udot4(c, rv, cr, false);
+            cc = __builtin_amdgcn_udot4(c, c, cc, false);
+        }
+    }
+    return (int)cc - 2 * (int)cr;
+}
+
+// ---- the whole-line decode as focr_decoder_run sees it (decode_whole.hip) --------------------------------------------
+
+// The plan of a whole-line run: what whole_plan works out from the font, the modes and the geometry before anything is
+// launched, and whole_launch launches from.
+struct WholePlan {
+    std::vector<uint32_t> inc64;  // per glyph: the pen increment in 1/64 px
+    int origin_d = 0;             // 64 * origin_x
+    uint32_t batch = 0;           // B: states per batch
+    uint32_t ring = 0;            // keys of the cost ring, a power of two
+    uint32_t max_inc = 0;         // the largest inc64
+    uint32_t n_states = 0;        // words of one workgroup's scratch
+    uint32_t cap = 1;             // characters per line at most
+    uint32_t grid = 0;            // workgroups
+};
+
+// The refusals of a whole-line run (include/focr_decode.h) and its plan for the batch of geometry g (g.w and g.total).
+int whole_plan(focr_decoder *dec, const Geometry &g, WholePlan *plan);
+// The run's scratch and result buffers and the font's inc64 table; g.cap is the plan's.
+int whole_reserve(focr_decoder *dec, const Geometry &g, const WholePlan &plan);
+// The third launch of a whole-line run, on the decoder's stream; the caller checks hipGetLastError.
+void whole_launch(focr_decoder *dec, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
+
+}  // namespace focr_dec

@@ -23,9 +23,9 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 MONO = os.path.join(GOLD, "DejaVuSansMono.ttf")
 SANS = os.path.join(GOLD, "DejaVuSans.ttf")
 FOCR = os.path.join(ROOT, "font_ocr_amd", "bin", "focr")
-LDS_STRIP_MAX = 65536      # decode.hip: strip, cost ring, live list and the characters' keys share this much LDS
-WHOLE_MISC_BYTES = 1088    # decode.hip: the end keys, the counts and the live list
-WHOLE_BATCH_MAX = 512      # decode.hip: states per batch at most
+LDS_STRIP_MAX = 65536      # decode_line.h: strip, cost ring, live list and the characters' keys share this much LDS
+WHOLE_MISC_BYTES = 1088    # decode_whole.hip: the end keys, the counts and the live list
+WHOLE_BATCH_MAX = 512      # decode_whole.hip: states per batch at most
 TEXT = "burn clip ffH vvill rnrn cl"
 
 pytestmark = pytest.mark.gpu
@@ -85,7 +85,7 @@ def strip_bytes(w, line_height):
 
 
 def chars_bytes(fm, w):
-    """decode.hip's whole_chars_dwords: a 64-bit key and a midpoint per character of the bound, in whole 16 bytes."""
+    """decode_whole.hip's whole_chars_dwords: a 64-bit key and a midpoint per character of the bound, in whole 16 bytes."""
     return ((3 * W.char_bound(fm.incs, w) + 3) & ~3) * 4
 
 

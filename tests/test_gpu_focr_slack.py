@@ -23,10 +23,10 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 MONO = os.path.join(GOLD, "DejaVuSansMono.ttf")
 SANS = os.path.join(GOLD, "DejaVuSans.ttf")
 FOCR = os.path.join(ROOT, "font_ocr_amd", "bin", "focr")
-LDS_STRIP_MAX = 65536           # decode.hip: strip, cost ring, live list and G share this much LDS, else the strip is read from global
-WHOLE_SLACK_MISC_BYTES = 5184   # decode.hip: the end keys, the counts, the live list and G
-WHOLE_BATCH_MAX = 512           # decode.hip: render pens per batch at most
-WHOLE_RING_MAX = 4096           # decode.hip: keys of the cost ring at most
+LDS_STRIP_MAX = 65536           # decode_line.h: strip, cost ring, live list and G share this much LDS, else the strip is read from global
+WHOLE_SLACK_MISC_BYTES = 5184   # decode_whole.hip: the end keys, the counts, the live list and G
+WHOLE_BATCH_MAX = 512           # decode_whole.hip: render pens per batch at most
+WHOLE_RING_MAX = 4096           # decode_whole.hip: keys of the cost ring at most
 TEXT = "burn clip ffH vvill rnrn cl"
 SMALL = "burn clif"
 

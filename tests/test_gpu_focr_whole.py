@@ -21,9 +21,9 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 MONO = os.path.join(GOLD, "DejaVuSansMono.ttf")
 SANS = os.path.join(GOLD, "DejaVuSans.ttf")
 FOCR = os.path.join(ROOT, "font_ocr_amd", "bin", "focr")
-LDS_STRIP_MAX = 65536      # decode.hip: strip, cost ring and live list share this much LDS, else the strip is read from global
-WHOLE_MISC_BYTES = 1088    # decode.hip: the end keys, the counts and the live list
-WHOLE_BATCH_MAX = 512      # decode.hip: states per batch at most
+LDS_STRIP_MAX = 65536      # decode_line.h: strip, cost ring and live list share this much LDS, else the strip is read from global
+WHOLE_MISC_BYTES = 1088    # decode_whole.hip: the end keys, the counts and the live list
+WHOLE_BATCH_MAX = 512      # decode_whole.hip: states per batch at most
 TEXT = "burn clip ffH vvill rnrn cl"  # the line the greedy loop decodes as "bunY dm+Tl vvillmmY d>" in Sans 13
 
 pytestmark = pytest.mark.gpu
