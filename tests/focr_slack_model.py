@@ -66,9 +66,9 @@ def slack_line(fm, ref, n, term=W.term_from_scores):
         states += 1
         off[p] = gj
         c = term(fm, r, total, p)
-        for i in range(len(inc)):  # ascending i and a strict compare: the lowest (cost, i)
+        for i in range(len(inc)):  # the lowest (cost, i), also against a glyph of another advance pushed from a lower pen
             t = p + int(inc[i])
-            if g + int(c[i]) < cost[t]:
+            if (g + int(c[i]), i) < (int(cost[t]), int(glyph[t]) if glyph[t] >= 0 else len(inc)):
                 cost[t], glyph[t] = g + int(c[i]), i
     end = n_live + int(np.argmin(cost[n_live:]))  # the first minimum: the lowest (cost, t)
     assert cost[end] != INF

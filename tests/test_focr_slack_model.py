@@ -153,6 +153,64 @@ def test_duplicate_glyph_decodes_to_the_lower_index():
     assert s.text[:5] == "rnirr" and 3 not in s.idx.tolist() and s.idx.tolist()[:5] == [0, 1, 2, 0, 0]
 
 
+def by_definition(fm, ref, n):
+    """include/focr_decode.h's slack programme read literally, state by state: cost[t] and glyph[t] are the lowest
+    (G[t - inc64[i]].cost + term(i, t - inc64[i]), i) over the glyphs i, G[p] the lowest (cost[p - j], rank(j)).  Every state
+    G[p] looks at lies below p + N < t, so ascending t sees only final costs.  Returns (text, pens, offsets, cost)."""
+    r = 255 - ref.astype(np.int64)
+    total = int((r * r).sum())
+    inc = [int(v) for v in W.inc64(fm.incs)]
+    n_live = 64 * ref.shape[1]
+    cost, glyph, G, terms = {0: 0}, {}, {}, {}
+
+    def window(p):
+        if p not in G:
+            reach = [(cost[p - j], S.rank(j), j) for j in range(-n, n + 1) if 0 <= p - j < n_live and p - j in cost]
+            G[p] = min(reach) if reach else None
+            if reach:
+                terms[p] = W.term_from_scores(fm, r, total, p)
+        return G[p]
+
+    for t in range(1, n_live + max(inc)):
+        cand = [(window(t - v)[0] + int(terms[t - v][i]), i) for i, v in enumerate(inc) if 0 <= t - v < n_live and window(t - v)]
+        if cand:
+            cost[t], glyph[t] = min(cand)
+    end = min((cost[t], t) for t in cost if t >= n_live)[1]
+    text, pens, offs, t = [], [], [], end
+    while t > 0:
+        i = glyph[t]
+        p = t - inc[i]
+        text.append(fm.alphabet[i]), pens.append(p), offs.append(G[p][2])
+        t = p - G[p][2]
+    return "".join(text[::-1]), pens[::-1], offs[::-1], cost[end]
+
+
+@pytest.mark.parametrize("n", [0, 1, 8])
+def test_ties_between_glyphs_of_different_advances_go_to_the_lower_index(n):
+    """Sans 11.5 px hinted, "v=,-b", crops one row high (the line-height-1 case of tests/focr_fuzz_cases.py, where the
+    device and this model first differed): "," and "-" miss the row, so both cost nothing at every pen, and a state that
+    ",-" and "-," both reach is a tie between glyphs pushed from different render pens.  The definition remembers the
+    lower index; a push loop with a strict compare would keep the glyph of the lower pen, the wider one.  The model must
+    be the definition read literally, on an inked row and on a blank one."""
+    al = ",-v=b"
+    fm = FastModel(SANS, 11.5, al, True, 1.0)
+    inc = W.inc64(fm.incs)
+    assert inc[0] < inc[1]  # the lower index is the narrower glyph: pushed from the higher pen, so visited later
+    row = np.full((1, 32), 255, dtype=np.uint8)
+    raster = np.zeros((14, 32), dtype=np.uint8)
+    raster_glyph(SANS, 11.5, "b", F32(fm.font.origin[0] + F32(20.3)), fm.font.origin[1], raster, True)
+    inked = 255 - raster[3:4]
+    assert (inked != 255).any()
+    for ref in (row, inked):
+        s = K.slack_line(fm, ref, n)
+        K.check_invariants(fm, s)
+        assert (s.text, s.pens.tolist(), s.offsets.tolist(), s.cost) == by_definition(fm, ref, n)
+        if n == 0:
+            w = W.whole_line(fm, ref)
+            assert (s.text, s.pens.tolist(), s.cost) == (w.text, w.pens.tolist(), w.cost)
+    fm.close()
+
+
 def test_helpers():
     incs = np.array([3.611328, 7.8], dtype=F32)  # inc64 231 and 499
     assert K.max_slack(incs) == 64 and K.max_slack(np.array([1.0], dtype=F32)) == 32 and K.max_slack(np.array([0.02], dtype=F32)) == 0
