@@ -82,19 +82,23 @@ static uint64_t content_hash(const void *p, size_t n) {
     const uint8_t *b = (const uint8_t *)p;
     uint64_t h[8] = {0x9e3779b97f4a7c15ull, 0xbf58476d1ce4e5b9ull, 0x94d049bb133111ebull, 0x2545f4914f6cdd1dull,
                      0xd6e8feb86659fd93ull, 0xa0761d6478bd642full, 0xe7037ed1a0b428dbull, 0x8ebc6af09c88c6e3ull};
-    size_t i = 0;
-    for (; i + 64 <= n; i += 64) {
+    auto block = [&](const uint8_t *src) {
         uint64_t v[8];
-        memcpy(v, b + i, 64);
+        memcpy(v, src, 64);
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             h[k] = (h[k] ^ v[k]) * 0x9fb21c651e98df25ull;
             h[k] ^= h[k] >> 29;
         }
+    };
+    size_t i = 0;
+    for (; i + 64 <= n; i += 64) block(b + i);
+    if (i < n) {  // the last n % 64 bytes, zero-padded to a block of their own: every byte keeps its position (the length is mixed in below)
+        uint8_t last[64] = {0};
+        memcpy(last, b + i, n - i);
+        block(last);
     }
-    uint64_t tail = 0;
-    for (int sh = 0; i < n; i++, sh = (sh + 8) & 63) tail ^= (uint64_t)b[i] << sh;
-    uint64_t r = tail ^ (uint64_t)n * 0xd6e8feb86659fd93ull;
+    uint64_t r = (uint64_t)n * 0xd6e8feb86659fd93ull;
     for (int k = 0; k < 8; k++) r = (r ^ h[k]) * 0x9fb21c651e98df25ull + (uint64_t)k;
     r ^= r >> 32;
     r *= 0xd6e8feb86659fd93ull;
@@ -192,8 +196,11 @@ static size_t compat_call(uint8_t *reference, size_t r_w, size_t r_h, uint8_t *n
 
     {
         // Residency rests on a 64-bit NON-cryptographic content hash of each input: two different pages (or tables) of one
-        // geometry with equal hashes would be scanned with the stale copy — probability ~2^-64 per pair, accepted for this
-        // plumbing path (the ABI has no error channel and no generation counter to key on).
+        // geometry with equal hashes would be scanned with the stale copy — accepted for this plumbing path (the ABI has no
+        // error channel and no generation counter to key on).  Every byte enters the hash through
+        // a multiply of its own position's lane and block, the last n % 64 bytes included (a plain XOR fold of those would
+        // not see two of them swapped), so unrelated inputs collide with probability ~2^-64 per pair; an input built to
+        // collide still can.
         // FOCR_COMPAT_ALWAYS_UPLOAD=1 switches it off: every call re-uploads every input.
         static const bool always_upload = getenv("FOCR_COMPAT_ALWAYS_UPLOAD") != nullptr;
         const bool geo = always_upload || tl.res_w != r_w || tl.res_h != r_h;

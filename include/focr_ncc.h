@@ -118,7 +118,9 @@ enum {
                            * (`ncc --rust`, src/ncc.rs:406-483): num = acc - s_n*s_p/n (a division),
                            * sim = num / sqrt(norm2_n * norm2_p), windows with s_p == 0 or num < 0
                            * are skipped, templates with s_n == 0 yield nothing; that path has no
-                           * 1024 cap (pass cap = UINT32_MAX) */
+                           * 1024 cap (pass cap = UINT32_MAX).  Extension: the reference's dispatch stops
+                           * at 16 px (todo!(), src/ncc.rs:328); templates 17..32 px wide are scanned here
+                           * with the same arithmetic, search_n_u8 being generic in the width */
 };
 
 /* One raw or post-processed hit with its template, as MatchWithLetter

@@ -54,6 +54,9 @@ def lib():
         L.oracle_scan_page_rust.restype = C.c_size_t
         L.oracle_scan_page_rust.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float,
                                             C.c_size_t, C.c_void_p, C.c_void_p]
+        L.oracle_search_rust_u8.restype = C.c_size_t
+        L.oracle_search_rust_u8.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t]
         L.oracle_scan_pages_mt.restype = C.c_size_t
         L.oracle_scan_pages_mt.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_float, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int,
@@ -187,6 +190,26 @@ def scan_page_rust(page_inv, bank, threshold, cap=1 << 16):
     lib().oracle_scan_page_rust(flat.ctypes.data, r_w, r_h, needles.ctypes.data, tm.ctypes.data, len(tm), threshold, cap,
                                 counts.ctypes.data, matches.ctypes.data)
     return counts, matches
+
+
+def search_rust_u8(page_inv, needle, threshold, cap=1 << 16, tabs=None, start_end=None):
+    """Searcher::search_n_u8 (src/ncc.rs:406-483) for ONE template of any width: the scalar Rust scan is generic in n_w, only its
+    dispatch stops at 16 px (todo!(), src/ncc.rs:328), so this is also the oracle for FOCR_SCAN_RUST on templates 17..32 px wide,
+    which scan_page_rust skips.  tabs = tables(page_inv) and start_end = prepare_for_size(...)[2], where the caller has them.
+    -> (count, matches): the full number of matches and the first min(count, cap) of them."""
+    r_h, r_w = page_inv.shape
+    needle = np.ascontiguousarray(needle, np.uint8)
+    n_h, n_w = needle.shape
+    out = np.zeros(cap, MATCH_DTYPE)
+    if n_w > r_w or n_h > r_h:
+        return 0, out[:0]
+    s, s2 = tabs if tabs is not None else tables(page_inv)
+    if start_end is None:
+        start_end = prepare_for_size(page_inv, n_w, n_h, (s, s2))[2]
+    flat = padded(page_inv)
+    c = lib().oracle_search_rust_u8(flat.ctypes.data, r_w, r_h, needle.ctypes.data, n_w, n_h, s.ctypes.data, s2.ctypes.data,
+                                    start_end.ctypes.data, threshold, out.ctypes.data, cap)
+    return int(c), out[: min(int(c), cap)].copy()
 
 
 def scan_pages_mt(pages_inv, bank, threshold, cap=1024, use_ref=False, threads=1, keep_matches=False):
