@@ -347,6 +347,8 @@ DECODE_RASTER_SYMBOLS = {
     "focr_decode_font_build": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_size_t,
                                          C.POINTER(DecodeFontStruct), C.c_char_p, C.c_size_t]),
     "focr_decode_font_free": (None, [C.POINTER(DecodeFontStruct)]),
+    "focr_decode_font_build_y": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.c_uint32,
+                                           C.POINTER(DecodeFontStruct), C.c_char_p, C.c_size_t]),
     "focr_verify_font_build": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_size_t,
                                          C.POINTER(VerifyFontStruct), C.c_char_p, C.c_size_t]),
     "focr_verify_font_free": (None, [C.POINTER(VerifyFontStruct)]),
@@ -375,6 +377,10 @@ DECODE_HIP_SYMBOLS = {
     "focr_decoder_set_whole_margins": (C.c_int, [C.c_void_p, C.c_int]),
     "focr_decoder_set_whole_slack": (C.c_int, [C.c_void_p, C.c_uint32]),
     "focr_decoder_get_margins": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "focr_decoder_set_baseline_fonts": (C.c_int, [C.c_void_p, C.POINTER(DecodeFontStruct), C.c_uint32]),
+    "focr_decoder_set_baseline_search": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "focr_decoder_get_baselines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "focr_decoder_debug_set_baseline_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "focr_decoder_set_verify_font": (C.c_int, [C.c_void_p, C.POINTER(VerifyFontStruct)]),
     "focr_decoder_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "focr_decoder_last_verify_ms": (C.c_float, [C.c_void_p]),

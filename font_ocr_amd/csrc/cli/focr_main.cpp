@@ -24,7 +24,12 @@
 //   * --pen-slack N is an extension of --whole-line for text off the 1/64 px grid: every step of the whole-line decode may
 //     move the pen by an offset of -N ..= N (in 1/64 px, at most 64) before its glyph is rendered
 //     (focr_decoder_set_whole_slack); stdout stays text only and --verify draws every character where it was decoded;
-//     without --whole-line, or with --margins or --pen-search, it is a usage error.
+//     without --whole-line, or with --margins or --pen-search, it is a usage error;
+//   * --baseline-search N [--y-bits B] is an extension: every line is decoded at the vertical offsets -N ..= N (in steps of
+//     2^-B px, N <= 32, B <= 3) and the one with the lowest summed footprint term is kept (focr_decoder_set_baseline_search);
+//     stdout stays text only, --verify draws every line moved by the nearest whole row of its offset, and --baselines PATH
+//     writes a CSV row per decoded line: image_index,y,q,offset_px,cost; with --scores, --pen-search or --whole-line it is a
+//     usage error, and so are --y-bits and --baselines without it.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -51,8 +56,10 @@ const size_t BATCH_PAGES = 256;
 
 struct Args {
     std::vector<std::string> img;
-    std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores, margins;
+    std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores, margins, baselines;
     bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false, have_margins = false;
+    bool have_baselines = false, have_y_bits = false;
+    uint32_t baseline_search = 0, y_bits = 0;
     float text_size = 0.f, kerning = 1.f;
     uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0, pen_search = 0, pen_slack = 0;
     bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
@@ -93,6 +100,9 @@ void print_help() {
            "      --whole-line                     [extension] Decode each line as a whole, for proportional fonts (not with scores or a pen search)\n"
            "      --margins <MARGINS>              [extension] CSV of every character's pen, term, runner-up and margin (only with the whole-line decode)\n"
            "      --pen-slack <N>                  [extension] Let every step of the whole-line decode move the pen by up to N/64 px, N <= 64 (not with margins or a pen search) [default: 0]\n"
+           "      --baseline-search <N>            [extension] Decode every line at the vertical offsets -N ..= N, in steps of 2^-B px (--y-bits), and keep the best, N <= 32 (only with the plain pen loop) [default: 0]\n"
+           "      --y-bits <B>                     [extension] Sub-pixel bits of the baseline search's step, B <= 3 [default: 0]\n"
+           "      --baselines <BASELINES>          [extension] CSV of every line's chosen vertical offset and cost (only with a baseline search)\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -160,6 +170,17 @@ Args parse_args(int argc, char **argv) {
             a.pen_slack = num_u(s);
             if (a.pen_slack > FOCR_PEN_SEARCH_MAX) usage_error("invalid value '" + s + "' for '--pen-slack': the radius is at most 64");
         }
+        else if (k == "--baseline-search") {
+            const std::string s = need();
+            a.baseline_search = num_u(s);
+            if (a.baseline_search > FOCR_BASELINE_MAX) usage_error("invalid value '" + s + "' for '--baseline-search': the radius is at most 32");
+        }
+        else if (k == "--y-bits") {
+            const std::string s = need();
+            a.y_bits = num_u(s), a.have_y_bits = true;
+            if (a.y_bits > FOCR_BASELINE_Y_BITS_MAX) usage_error("invalid value '" + s + "' for '--y-bits': at most 3");
+        }
+        else if (k == "--baselines") a.baselines = need(), a.have_baselines = true;
         else if (k == "--whole-line") a.whole_line = true;
         else if (k == "--margins") a.margins = need(), a.have_margins = true;
         else if (k == "-h" || k == "--help") {
@@ -183,6 +204,11 @@ Args parse_args(int argc, char **argv) {
     if (a.pen_slack && a.pen_search) usage_error("the argument '--pen-slack <N>' cannot be used with '--pen-search <N>'");
     if (a.pen_slack && !a.whole_line) usage_error("the argument '--pen-slack <N>' cannot be used without '--whole-line'");
     if (a.pen_slack && a.have_margins) usage_error("the argument '--pen-slack <N>' cannot be used with '--margins <MARGINS>'");
+    if (a.baseline_search && a.have_scores) usage_error("the argument '--baseline-search <N>' cannot be used with '--scores <SCORES>'");
+    if (a.baseline_search && a.pen_search) usage_error("the argument '--baseline-search <N>' cannot be used with '--pen-search <N>'");
+    if (a.baseline_search && a.whole_line) usage_error("the argument '--baseline-search <N>' cannot be used with '--whole-line'");
+    if (a.have_y_bits && !a.baseline_search) usage_error("the argument '--y-bits <B>' cannot be used without '--baseline-search <N>'");
+    if (a.have_baselines && !a.baseline_search) usage_error("the argument '--baselines <BASELINES>' cannot be used without '--baseline-search <N>'");
     return a;
 }
 
@@ -224,6 +250,8 @@ struct Line {
     std::vector<int8_t> offsets;            // --scores with --pen-search: one per code point
     std::vector<uint32_t> pens;             // --margins: one per code point, in 1/64 px
     std::vector<focr_char_margin_t> margins;
+    int q = 0;                              // --baselines: the line's chosen vertical offset, in steps of 2^-B px
+    long long cost = 0;
 };
 
 // Writes the batch's verify images (the device's draw_verify, n x H x W x 3 bytes) as PNGs on at most 16 threads, and
@@ -301,13 +329,19 @@ int main(int argc, char **argv) {
     if (args.have_scores && !(csv = fopen(args.scores.c_str(), "w"))) usage_error("cannot write '" + args.scores + "' for '--scores'");
     FILE *mcsv = nullptr;
     if (args.have_margins && !(mcsv = fopen(args.margins.c_str(), "w"))) usage_error("cannot write '" + args.margins + "' for '--margins'");
+    FILE *bcsv = nullptr;
+    if (args.have_baselines && !(bcsv = fopen(args.baselines.c_str(), "w"))) usage_error("cannot write '" + args.baselines + "' for '--baselines'");
     if (args.img.empty()) return 0;
 
     char err[256] = {0};
-    focr_decode_font_t font{};
-    if (focr_decode_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), &font, err,
-                               sizeof err) != 0)
+    const bool y_fonts = args.baseline_search && args.y_bits;  // the y-phase fonts; fonts[0] is the plain decode font
+    std::vector<focr_decode_font_t> fonts((size_t)1 << (y_fonts ? args.y_bits : 0));
+    if ((y_fonts ? focr_decode_font_build_y(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), args.y_bits,
+                                            fonts.data(), err, sizeof err)
+                 : focr_decode_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), fonts.data(),
+                                          err, sizeof err)) != 0)
         die(std::string("decode font: ") + err);
+    focr_decode_font_t &font = fonts[0];
 
     // sizes first, so that pages of one size form one batch
     const size_t n_img = args.img.size();
@@ -335,6 +369,10 @@ int main(int argc, char **argv) {
     if (focr_decoder_set_whole_line(dec, args.whole_line) != 0) die(std::string("focr_decoder_set_whole_line: ") + focr_decoder_last_error(dec), 1);
     if (focr_decoder_set_whole_slack(dec, args.pen_slack) != 0) die(std::string("focr_decoder_set_whole_slack: ") + focr_decoder_last_error(dec), 1);
     if (mcsv && focr_decoder_set_whole_margins(dec, 1) != 0) die(std::string("focr_decoder_set_whole_margins: ") + focr_decoder_last_error(dec), 1);
+    if (y_fonts && focr_decoder_set_baseline_fonts(dec, fonts.data(), args.y_bits) != 0)
+        die(std::string("focr_decoder_set_baseline_fonts: ") + focr_decoder_last_error(dec), 1);
+    if (focr_decoder_set_baseline_search(dec, args.baseline_search ? args.y_bits : 0, args.baseline_search) != 0)
+        die(std::string("focr_decoder_set_baseline_search: ") + focr_decoder_last_error(dec), 1);
     const bool csv_offsets = csv && args.pen_search > 0;
 
     std::vector<std::vector<Line>> lines(n_img);
@@ -370,8 +408,14 @@ int main(int argc, char **argv) {
             std::vector<focr_char_margin_t> dm(mcsv ? dc.size() : 0);
             if (mcsv && (focr_decoder_get_pens(dec, dp.data(), nullptr) != 0 || focr_decoder_get_margins(dec, dm.data()) != 0))
                 die(std::string("focr_decoder_get_margins: ") + focr_decoder_last_error(dec), 1);
-            for (const focr_decoded_line_t &l : dl) {
+            std::vector<int8_t> bq(bcsv ? dl.size() : 0);
+            std::vector<int64_t> bc(bcsv ? dl.size() : 0);
+            if (bcsv && focr_decoder_get_baselines(dec, bq.data(), bc.data()) != 0)
+                die(std::string("focr_decoder_get_baselines: ") + focr_decoder_last_error(dec), 1);
+            for (size_t li = 0; li < dl.size(); li++) {
+                const focr_decoded_line_t &l = dl[li];
                 Line out{l.y, {}, {}, {}, {}, {}};
+                if (bcsv) out.q = bq[li], out.cost = (long long)bc[li];
                 if (mcsv) out.pens.assign(dp.begin() + l.first, dp.begin() + l.first + l.n_chars);
                 if (mcsv) out.margins.assign(dm.begin() + l.first, dm.begin() + l.first + l.n_chars);
                 for (uint32_t c = 0; c < l.n_chars; c++) out.text.push_back(alphabet[dc[l.first + c]]);
@@ -396,7 +440,7 @@ int main(int argc, char **argv) {
         }
     }
     focr_decoder_destroy(dec);
-    focr_decode_font_free(&font);
+    for (focr_decode_font_t &f : fonts) focr_decode_font_free(&f);
 
     std::string out;
     for (size_t i = 0; i < n_img; i++)
@@ -419,6 +463,12 @@ int main(int argc, char **argv) {
                     fputc('\n', csv);
                 }
         if (fclose(csv) != 0) die("cannot write " + args.scores);
+    }
+    if (bcsv) {  // one row per decoded line, in the order of stdout
+        fprintf(bcsv, "image_index,y,q,offset_px,cost\n");
+        for (size_t i = 0; i < n_img; i++)
+            for (const Line &l : lines[i]) fprintf(bcsv, "%zu,%u,%d,%g,%lld\n", i, l.y, l.q, (double)l.q / (double)(1u << args.y_bits), l.cost);
+        if (fclose(bcsv) != 0) die("cannot write " + args.baselines);
     }
     if (mcsv) {  // one row per decoded character, in the order of stdout; a one-glyph alphabet has no runner-up and no margin
         fprintf(mcsv, "image_index,y,column,codepoint,pen,term,runner_codepoint,margin\n");

@@ -1,5 +1,5 @@
 // decode.h — what the files of the `focr` decoder share (decode.hip: font and line decoder; decode_whole.hip: its whole-line
-// decode, with decode_line.h between the two; decode_images.hip: the verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels (ncc_images.hip
+// decode, and decode_baseline.hip: its baseline search, with decode_line.h between the three; decode_images.hip: the verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels (ncc_images.hip
 // is its third user), the blank test's crop, the decoder itself, and the host plumbing every entry point repeats (errors, stages, staging, refusals).
 #pragma once
 
@@ -214,7 +214,22 @@ struct focr_decoder {
     focr::DevArray<int32_t> d_mterm;
     focr::DevArray<uint16_t> d_mrunner;
     focr::DevArray<int64_t> d_margin;
+    // baseline search (focr_decoder_set_baseline_search): the y-phase tables v >= 1 of the font (set_baseline_fonts; glyph
+    // records and offsets v-major, one bitmap table whose dword offsets the records carry), and per work-list line beside
+    // d_nchars the chosen q and its cost; grown by a run with a radius
+    uint32_t base_bits = 0, base_n = 0;
+    uint32_t base_grid = 0;        // focr_decoder_debug_set_baseline_grid: at most this many workgroups (0: no limit of the test's)
+    bool have_base_fonts = false;  // y-phase fonts of font_bits are uploaded for the current font
+    uint32_t font_bits = 0, ybitmaps_dw = 0;  // ... and the dwords of their bitmap table
+    focr::DevArray<focr_dec::DevGlyph> d_yglyphs;
+    focr::DevArray<int2> d_yoffs;
+    focr::DevArray<uint8_t> d_ybitmaps;
+    focr::DevArray<int32_t> d_base_q;
+    focr::DevArray<int64_t> d_base_cost;
     // results of the last run
+    bool have_baselines = false;   // the last successful run searched baselines
+    std::vector<int8_t> base_q;    // beside lines
+    std::vector<int64_t> base_cost;
     std::vector<focr_decoded_line_t> lines;
     std::vector<uint16_t> chars;
     bool have_scores = false;  // the last successful run was made with scores on
@@ -231,6 +246,8 @@ struct focr_decoder {
     focr::DevArray<focr_dec::VerifyGlyph> d_vglyphs;
     focr::DevArray<focr_dec::VerifyPhase> d_vphases;
     bool run_ok = false, run_searched = false, run_whole = false;  // the last successful run wrote d_pen / d_pens
+    bool run_base = false;  // ... or d_base_q, in steps of 2^-run_bits px
+    uint32_t run_bits = 0;
     focr_dec::Geometry run_g{};
     size_t run_pages = 0;
     uint32_t run_x_start = 0;
@@ -249,6 +266,9 @@ struct focr_decoder {
 namespace focr_dec {
 
 inline thread_local std::string g_dec_err;
+
+// The second launch of a verify after a baseline run (decode_baseline.hip), on the decoder's stream; the caller checks hipGetLastError.
+void verify_compose_moved_launch(focr_decoder *dec, const TileGrid &tg, size_t n_pages, uint8_t *d_rgb);
 
 inline int dfail(focr_decoder *dec, const std::string &msg) {
     if (dec) dec->err = msg;

@@ -12,6 +12,8 @@
 //      the argmin over (glyph, pen offset), and the chosen offset of every step beside its glyph.
 //      With the whole-line decode on (focr_decoder_set_whole_line) one of decode_whole.hip's kernels takes its place: a
 //      dynamic programme over pens in 1/64 px, with margins or with a pen slack when those are on.
+//      With a baseline search radius (focr_decoder_set_baseline_search) decode_baseline.hip's line_baseline_kernel takes its
+//      place: the pen loop under every vertical candidate, and the candidate with the lowest summed footprint term.
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
@@ -328,6 +330,8 @@ namespace {
 void remember_run(focr_decoder *dec, const Geometry &g, const uint8_t *d_src, size_t n_pages, uint32_t x_start, bool searched, bool whole) {
     dec->run_searched = searched;
     dec->run_whole = dec->have_whole = whole;
+    dec->run_base = dec->base_n != 0;  // (a run that got here with a radius searched baselines)
+    dec->run_bits = dec->base_bits;
     dec->run_g = g;
     dec->run_pages = n_pages;
     dec->run_x_start = x_start;
@@ -373,6 +377,7 @@ extern "C" const char *focr_decoder_last_error(const focr_decoder_t *dec) { retu
 
 extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font_t *font) {
     if (dec) dec->run_ok = false, dec->have_whole = false, dec->have_margins = false, dec->n_vglyphs = 0;  // the last run and the verify table belong to the previous font
+    if (dec) dec->have_baselines = dec->have_base_fonts = false;  // and so do the y-phase fonts (released below, once the device is selected)
     if (!dec || !font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_font: bad arguments");
     if (font->n_glyphs > 65535) return dfail(dec, "focr_decoder_set_font: more than 65535 glyphs");
     if (font->bitmaps_len % 4 || font->bitmaps_len / 4 > 0xffffffffull) return dfail(dec, "focr_decoder_set_font: bad bitmap table");
@@ -396,6 +401,10 @@ extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font
     }
     dec->n_glyphs = 0;
     dec->d_inc64.release();  // the previous font's; a whole-line run uploads its own
+    dec->font_bits = dec->ybitmaps_dw = 0;
+    dec->d_yglyphs.release();
+    dec->d_yoffs.release();
+    dec->d_ybitmaps.release();
     DEC_UPLOAD(dec->d_glyphs, gl.data(), G);
     DEC_UPLOAD(dec->d_offs, offs.data(), offs.size());
     DEC_UPLOAD(dec->d_bitmaps, (const uint8_t *)font->bitmaps, font->bitmaps_len, 4);
@@ -415,7 +424,9 @@ namespace {
 
 // A run starts: the results of the last one are gone, whatever becomes of this one.
 void clear_results(focr_decoder *dec) {
-    dec->run_ok = dec->have_scores = dec->have_whole = dec->have_margins = false;
+    dec->run_ok = dec->have_scores = dec->have_whole = dec->have_margins = dec->have_baselines = false;
+    dec->base_q.clear();
+    dec->base_cost.clear();
     dec->lines.clear();
     dec->chars.clear();
     dec->char_scores.clear();
@@ -450,6 +461,8 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     clear_results(dec);
     if (!dec->n_glyphs) return dfail(dec, "focr_decoder_run: no font (focr_decoder_set_font)");
     if (n_pages && !pages) return dfail(dec, "focr_decoder_run: null pages");
+    const bool baseline = dec->base_n != 0;
+    if (baseline && baseline_plan(dec)) return 1;  // the refusals of include/focr_decode.h, before anything is launched
     if (dec->margins_on && !dec->whole_on)
         return dfail(dec, "focr_decoder_run: margins on with the whole-line decode off (focr_decoder_set_whole_margins needs focr_decoder_set_whole_line)");
     const uint32_t slack = dec->whole_slack;
@@ -475,6 +488,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
         dec->have_scores = scores;
         dec->have_margins = margins;
+        dec->have_baselines = baseline;
         return 0;
     }
     g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;
@@ -509,6 +523,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     const ScoreOut so{dec->d_term, dec->d_runner_term, dec->d_runner, dec->d_base};  // null arrays with scores off: never touched
     if (radius || slack) DEC_GROW(dec->d_pen, n_all);
     if (whole && whole_reserve(dec, g, plan)) return 1;
+    if (baseline && baseline_reserve(dec, g)) return 1;
 
     DEC_CHECK(hipEventRecord(dec->run.begin, dec->stream));
     line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
@@ -517,6 +532,8 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     DEC_CHECK(hipGetLastError());
     if (whole) {
         whole_launch(dec, g, plan, strip_bytes);
+    } else if (baseline) {
+        baseline_launch(dec, g, strip_bytes);
     } else if (radius) {  // the strip shares LDS with the reduction pairs, so it stays in LDS up to that much less
         const bool lds = strip_bytes + SEARCH_RED_BYTES <= LDS_STRIP_MAX;
         const auto search = lds ? (scores ? line_search_kernel<true, true> : line_search_kernel<true, false>)
@@ -538,13 +555,15 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     std::vector<uint32_t> count, work, nch, wpens;
     std::vector<uint16_t> all, mrunner, runner;
     std::vector<int8_t> pen;
-    std::vector<int64_t> wcost, mmargin;
+    std::vector<int64_t> wcost, mmargin, bcost;
+    std::vector<int32_t> bq;
     std::vector<int32_t> mterm, term, runner_term;
     std::vector<uint64_t> base;
     if (read_back(dec, count, dec->d_count.p, 1) || read_back(dec, work, dec->d_work.p, total) || read_back(dec, nch, dec->d_nchars.p, total) ||
         read_back(dec, all, dec->d_chars.p, n_all))
         return 1;
     if (offsets && read_back(dec, pen, dec->d_pen.p, n_all)) return 1;
+    if (baseline && (read_back(dec, bq, dec->d_base_q.p, total) || read_back(dec, bcost, dec->d_base_cost.p, total))) return 1;
     if (whole && (read_back(dec, wpens, dec->d_pens.p, n_all) || read_back(dec, wcost, dec->d_cost.p, total))) return 1;
     if (margins && (read_back(dec, mterm, dec->d_mterm.p, n_all) || read_back(dec, mrunner, dec->d_mrunner.p, n_all) || read_back(dec, mmargin, dec->d_margin.p, n_all)))
         return 1;
@@ -567,6 +586,11 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         l.pad = 0;
         append_line(dec->chars, all, k, g.cap, n);
         if (offsets) append_line(dec->offsets, pen, k, g.cap, n);
+        if (baseline) {
+            if (bq[k] < -(int)FOCR_BASELINE_MAX || bq[k] > (int)FOCR_BASELINE_MAX) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
+            dec->base_q.push_back((int8_t)bq[k]);
+            dec->base_cost.push_back(bcost[k]);
+        }
         if (whole) {
             append_line(dec->pens, wpens, k, g.cap, n);
             dec->line_cost.push_back(wcost[k]);
@@ -585,6 +609,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
     dec->have_scores = scores;
     dec->have_margins = margins;
+    dec->have_baselines = baseline;
     return 0;
 }
 

@@ -1,0 +1,370 @@
+// decode_baseline.hip — the baseline search of the `focr` line decoder (focr_decoder_set_baseline_search; an extension, see
+// include/focr_decode.h): every line is decoded once per vertical candidate q in -N ..= N, in steps of 2^-B px, and the
+// candidate with the lowest summed footprint term is the line.
+//
+// line_baseline_kernel takes line_decode_kernel's place as the third launch of a run (decode.hip).  One workgroup of four
+// waves takes a work-list line (grid-stride, so a smaller grid takes several):
+//   - the strip is staged in LDS once and shared by every candidate (when it fits; else it is read from global memory);
+//   - wave w runs the plain pen loop for the candidates of rank w, w + 4, ... and keeps only the lowest (cost, rank);
+//   - the four waves meet in LDS, and every wave works out the same winner;
+//   - one wave decodes the winner once more and writes its characters: no trial buffers, and nothing depends on which
+//     wave finished first.
+// Candidate q renders from y-phase v = q & (2^B - 1) of the font (phase 0 is the decode font itself; the others are
+// focr_decoder_set_baseline_fonts') with every box moved down by d = q >> B rows; footprint_term_wide clips a
+// box to the crop's rows on both sides, so rows that d pushes above row 0 or below the last row are never read.
+// Everything is exact integer arithmetic but the f32 pen, which is the plain loop's.
+#include <cstring>
+
+#include "decode_line.h"
+
+namespace focr_dec {
+
+constexpr uint32_t BASE_THREADS = 256;  // one workgroup of four waves per work-list line
+constexpr uint32_t BASE_WAVES = BASE_THREADS / 64;
+constexpr uint32_t BASE_RED_BYTES = BASE_WAVES * 2 * 8;  // (cost, rank) per wave, in front of the strip
+
+// The font as a candidate reads it: y-phase 0 is the decode font, the others lie v-major in tables of their own.
+struct BaseFont {
+    const DevGlyph *glyphs, *yglyphs;
+    const int2 *offs, *yoffs;
+    const uint32_t *bitmaps, *ybitmaps;
+    uint32_t n_dw, yn_dw;  // dwords of the two bitmap tables
+    uint32_t n_glyphs;
+    float origin_x;
+    int origin_y;   // a whole number >= 0
+    uint32_t bits;  // B
+};
+
+// One dword c of a tile row at canvas column `base` against the strip row srow: footprint_term's inner step.
+__device__ __forceinline__ void term_dword(uint32_t c, const uint32_t *srow, int base, int w, uint32_t &cc, uint32_t &cr) {
+    if (base <= -4 || base >= w) return;
+    if (base < 0 || base + 4 > w) c &= edge_mask(base, w);
+    const uint32_t a = (uint32_t)(base + (int)PAD);
+    const uint32_t rv = __builtin_amdgcn_alignbyte(srow[(a >> 2) + 1], srow[a >> 2], a & 3);
+    cr = __builtin_amdgcn_udot4(c, rv, cr, false);
+    cc = __builtin_amdgcn_udot4(c, c, cc, false);
+}
+
+// footprint_term (decode_line.h) with a tile row read four dwords at a time: the lanes of a wave read different glyphs, so
+// every load of theirs touches up to 64 cache lines, and the loads, not the arithmetic, are what a candidate costs.  A
+// read past a short row's end stays inside the table (the dwords of the next row; they are not used), and the table's last
+// rows, where it would not, are read dword by dword.  The sums are integer sums: the same term in any order.
+__device__ __forceinline__ int footprint_term_wide(const uint32_t *strip, uint32_t sdw, int w, uint32_t h, const uint32_t *__restrict__ tile,
+                                                   const uint32_t *__restrict__ table_end, uint32_t ndw, uint32_t box_h, int x0, int y0) {
+    const int r_lo = std::max(0, -y0), r_hi = std::min((int)box_h, (int)h - y0);
+    uint32_t cc = 0, cr = 0;
+    for (int r = r_lo; r < r_hi; r++) {
+        const uint32_t *srow = strip + (size_t)(y0 + r) * sdw;
+        const uint32_t *trow = tile + (size_t)r * ndw;
+        for (uint32_t q = 0; q < ndw; q += 4) {
+            uint32_t c0, c1 = 0, c2 = 0, c3 = 0;
+            if (trow + q + 4 <= table_end) {
+                uint4 t;
+                __builtin_memcpy(&t, trow + q, sizeof t);  // dword-aligned
+                c0 = t.x, c1 = t.y, c2 = t.z, c3 = t.w;
+            } else {
+                c0 = trow[q];
+                if (q + 1 < ndw) c1 = trow[q + 1];
+                if (q + 2 < ndw) c2 = trow[q + 2];
+                if (q + 3 < ndw) c3 = trow[q + 3];
+            }
+            const int base = x0 + 4 * (int)q;
+            term_dword(c0, srow, base, w, cc, cr);
+            if (q + 1 < ndw) term_dword(c1, srow, base + 4, w, cc, cr);
+            if (q + 2 < ndw) term_dword(c2, srow, base + 8, w, cc, cr);
+            if (q + 3 < ndw) term_dword(c3, srow, base + 12, w, cc, cr);
+        }
+    }
+    return (int)cc - 2 * (int)cr;
+}
+
+// The plain pen loop (line_decode_kernel) by one wave, with every box moved down by d rows: the line's summed footprint
+// terms, and with WRITE its characters to out and their number to *n_out (lane 0).  Uniform across the wave.
+template <bool WRITE>
+__device__ __forceinline__ int64_t pen_loop(const uint32_t *strip, uint32_t sdw, int w, uint32_t h, uint32_t cap, const DevGlyph *__restrict__ glyphs,
+                                            const int2 *__restrict__ offs, const uint32_t *__restrict__ bitmaps, uint32_t n_dw, uint32_t n_glyphs,
+                                            float origin_x, int d, uint32_t lane, uint16_t *__restrict__ out, uint32_t *__restrict__ n_out) {
+    const float fw = (float)w;
+    float pos = 0.f;
+    uint32_t n = 0;
+    int64_t cost = 0;
+    while (pos < fw && n < cap) {
+        const int dx = (int)((origin_x + pos) * 64.0f);  // FreeType's delta: trunc(t * 64)
+        const int phase = dx & 63, shift = dx >> 6;
+        uint64_t best = ~0ull;
+        for (uint32_t gi = lane; gi < n_glyphs; gi += 64) {
+            const DevGlyph gl = glyphs[gi];
+            const int2 o = offs[gi * 64 + phase];
+            const uint32_t *tile = bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h;
+            const int score = footprint_term_wide(strip, sdw, w, h, tile, bitmaps + n_dw, gl.ndw, gl.box_h, shift + o.x, o.y + d);
+            best = std::min(best, ((uint64_t)((uint32_t)score ^ 0x80000000u) << 32) | gi);  // (score, index), lowest first
+        }
+        for (int m = 32; m >= 1; m >>= 1) best = std::min(best, shfl_xor_u64(best, m));
+        const uint32_t gbest = (uint32_t)best;
+        cost += (int)((uint32_t)(best >> 32) ^ 0x80000000u);
+        if (WRITE && lane == 0) out[n] = (uint16_t)gbest;
+        n++;
+        pos = __fadd_rn(pos, glyphs[gbest].inc);
+    }
+    if (WRITE && lane == 0) *n_out = n;
+    return cost;
+}
+
+// pen_loop under candidate q of the font.
+template <bool WRITE>
+__device__ __forceinline__ int64_t candidate_loop(const uint32_t *strip, uint32_t sdw, int w, uint32_t h, uint32_t cap, const BaseFont &f, int q,
+                                                  uint32_t lane, uint16_t *__restrict__ out, uint32_t *__restrict__ n_out) {
+    const uint32_t v = (uint32_t)q & ((1u << f.bits) - 1);
+    const int d = q >> f.bits;  // floor
+    const DevGlyph *glyphs = v ? f.yglyphs + (size_t)(v - 1) * f.n_glyphs : f.glyphs;
+    const int2 *offs = v ? f.yoffs + (size_t)(v - 1) * f.n_glyphs * 64 : f.offs;
+    return pen_loop<WRITE>(strip, sdw, w, h, cap, glyphs, offs, v ? f.ybitmaps : f.bitmaps, v ? f.yn_dw : f.n_dw, f.n_glyphs, f.origin_x, d, lane, out,
+                           n_out);
+}
+
+// 3b. the pen loop under every baseline candidate, one workgroup per work-list line (grid-stride).  radius >= 1.
+template <bool LDS>
+__global__ __launch_bounds__(BASE_THREADS) void line_baseline_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
+                                                                     const uint32_t *__restrict__ count, BaseFont f, uint32_t radius,
+                                                                     uint32_t *__restrict__ n_chars, uint16_t *__restrict__ chars,
+                                                                     int32_t *__restrict__ line_q, int64_t *__restrict__ line_cost) {
+    extern __shared__ __align__(8) uint32_t lds_base[];  // the waves' (cost, rank), then (LDS) the strip
+    uint64_t *red = (uint64_t *)lds_base;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t sdw = g.stride / 4, n_cand = 2 * radius + 1, n_lines = *count;
+    // the winner's decode goes to a wave that has one candidate fewer than wave 0 (n_cand is odd: wave 1 or 3)
+    const uint32_t writer = n_cand & (BASE_WAVES - 1);
+    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
+        const uint32_t slot = work[k];
+        uint32_t yc, h;
+        slot_rows(g, slot % g.n_slots, &yc, &h);
+        const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
+        if (LDS) {
+            uint32_t *lds_strip = lds_base + BASE_RED_BYTES / 4;
+            for (uint32_t i = tid; i < sdw * h; i += BASE_THREADS) lds_strip[i] = strip[i];
+            __syncthreads();
+            strip = lds_strip;
+        }
+        int64_t best_cost = INT64_MAX;
+        uint32_t best_rank = ~0u;  // a wave without a candidate: never the winner (rank 0 is never dropped)
+        for (uint32_t rank = wave; rank < n_cand; rank += BASE_WAVES) {
+            const int q = rank_offset(rank);
+            if (f.origin_y * (1 << f.bits) + q < 0) continue;  // ty_q < 0: no such rendering
+            const int64_t cost = candidate_loop<false>(strip, sdw, (int)g.w, h, g.cap, f, q, lane, nullptr, nullptr);
+            if (cost < best_cost) best_cost = cost, best_rank = rank;  // a wave's ranks ascend: the first of equal costs stays
+        }
+        if (lane == 0) red[2 * wave] = (uint64_t)best_cost, red[2 * wave + 1] = best_rank;
+        __syncthreads();
+        best_cost = (int64_t)red[0], best_rank = (uint32_t)red[1];
+        for (uint32_t v = 1; v < BASE_WAVES; v++) {
+            const int64_t c = (int64_t)red[2 * v];
+            const uint32_t r = (uint32_t)red[2 * v + 1];
+            if (c < best_cost || (c == best_cost && r < best_rank)) best_cost = c, best_rank = r;
+        }
+        if (wave == writer) {
+            const int q = rank_offset(best_rank);
+            const int64_t cost = candidate_loop<true>(strip, sdw, (int)g.w, h, g.cap, f, q, lane, chars + (size_t)k * g.cap, n_chars + k);
+            if (lane == 0) line_q[k] = q, line_cost[k] = cost;
+        }
+        __syncthreads();  // the strip and the pairs are the next line's from here
+    }
+}
+
+// 5b. decode_images.hip's verify_compose_kernel after a baseline run: the canvases lie up to FOCR_BASELINE_MAX rows above or below their slots, so
+// a tile looks that much further for the slots that can reach it; the rest is the same.  (A kernel of its own, not a template
+// or a shared body, and in this file: each of the three changes verify_compose_kernel's machine code, tools/isa_hash.py, which
+// the plain verify's timing pins.)
+__global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_moved_kernel(const uint8_t *__restrict__ pages, Geometry g, uint32_t n_pages,
+                                                                       uint32_t hmax, uint32_t tiles_x, uint32_t tiles_y, const VerifyLine *__restrict__ lines,
+                                                                       const VerifyRec *__restrict__ recs, const uint8_t *__restrict__ bitmaps,
+                                                                       uint8_t *__restrict__ rgb, unsigned long long *__restrict__ sums) {
+    __shared__ uint32_t win[VERIFY_TILE_H * VERIFY_TILE_W];  // 1 + index of the last glyph of the current line over the pixel
+    __shared__ uint8_t blue[VERIFY_TILE_H * VERIFY_TILE_W];
+    __shared__ uint32_t part[VERIFY_TILE_W / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y * n_pages;
+    const size_t W = g.page_w, H = g.page_h;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const Tile T = tile_at(tile, tiles_x, tiles_y, g.page_w, g.page_h);
+        const auto [page, r0, c0, r1, c1] = T;
+        for (uint32_t r = 0; r < VERIFY_TILE_H; r++) {
+            win[r * VERIFY_TILE_W + t] = 0;
+            blue[r * VERIFY_TILE_W + t] = 0;
+        }
+        __syncthreads();
+        // the slots whose canvas (at most hmax rows, from the slot's y moved either way) can reach rows r0 .. r1 - 1, in line order
+        int64_t i_lo, i_hi;
+        slot_range(g, r0, r1 + (int)FOCR_BASELINE_MAX, (int64_t)hmax - 1 + FOCR_BASELINE_MAX, &i_lo, &i_hi);
+        for (int64_t i = i_lo; i <= i_hi; i++) {
+            const VerifyLine l = lines[(size_t)page * g.n_slots + i];
+            if (l.n == 0 || l.x0 >= c1 || l.x1 <= c0 || l.y0 >= r1 || l.y1 <= r0) continue;  // uniform across the workgroup
+            const VerifyRec *lr = recs + (size_t)l.k * g.cap;
+            mark_glyphs(win, lr, l.n, T, lane, wave);
+            __syncthreads();
+            const int x = c0 + (int)t;
+            for (int y = r0; y < r1 && x < c1; y++) {
+                const uint32_t idx = (uint32_t)(y - r0) * VERIFY_TILE_W + t, w = win[idx];
+                if (!w) continue;
+                win[idx] = 0;
+                const uint8_t v = glyph_value(w, lr, bitmaps, x, y);
+                if (v) blue[idx] = (uint8_t)(255 - v);  // canvas_to_lum8 then draw_verify: only v != 0 reaches the page
+            }
+            __syncthreads();
+        }
+        uint32_t acc = 0;
+        const int x = c0 + (int)t;
+        if (x < c1)
+            for (int y = r0; y < r1; y++) {
+                const size_t at = ((size_t)page * H + y) * W + x;
+                const uint8_t l = pages[at];
+                const uint8_t red = l != 255 ? l : 0, b = blue[(uint32_t)(y - r0) * VERIFY_TILE_W + t];
+                if (rgb) {
+                    rgb[at * 3] = red;
+                    rgb[at * 3 + 1] = 0;
+                    rgb[at * 3 + 2] = b;
+                }
+                const int dd = (int)red - (int)b;
+                acc += (uint32_t)(dd * dd);  // at most 16 * 255^2 per thread, 2^28 per workgroup
+            }
+        tile_add_sum(acc, part, &sums[page], t);
+    }
+}
+
+void verify_compose_moved_launch(focr_decoder *dec, const TileGrid &tg, size_t n_pages, uint8_t *d_rgb) {
+    verify_compose_moved_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->run_src, dec->run_g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y,
+                                                                            dec->d_vlines, dec->d_vrecs, (const uint8_t *)dec->d_bitmaps, d_rgb, dec->d_sums);
+}
+
+int baseline_plan(focr_decoder *dec) {
+    const char *pre = "focr_decoder_run: a baseline search (focr_decoder_set_baseline_search) does not go with ";
+    if (dec->scores_on) return dfail(dec, std::string(pre) + "scores (focr_decoder_set_scores): a runner-up has no definition across candidates yet");
+    if (dec->pen_search) return dfail(dec, std::string(pre) + "a pen search (focr_decoder_set_pen_search) yet");
+    if (dec->whole_on) return dfail(dec, std::string(pre) + "the whole-line decode (focr_decoder_set_whole_line) yet");
+    if (dec->margins_on) return dfail(dec, std::string(pre) + "margins (focr_decoder_set_whole_margins) yet");
+    if (dec->whole_slack) return dfail(dec, std::string(pre) + "a pen slack (focr_decoder_set_whole_slack) yet");
+    if (dec->base_bits && !(dec->have_base_fonts && dec->font_bits == dec->base_bits))
+        return dfail(dec, "focr_decoder_run: a baseline search with y_bits > 0 (focr_decoder_set_baseline_search) needs the y-phase fonts of that "
+                          "y_bits (focr_decoder_set_baseline_fonts)");
+    const float oy = dec->origin_y;
+    if (!(oy >= 0.f) || oy > 65536.f || oy != (float)(int)oy)
+        return dfail(dec, "focr_decoder_run: a baseline search (focr_decoder_set_baseline_search) needs an origin_y that is a whole number >= 0");
+    return 0;
+}
+
+int baseline_reserve(focr_decoder *dec, const Geometry &g) {
+    DEC_GROW(dec->d_base_q, g.total);
+    DEC_GROW(dec->d_base_cost, g.total);
+    return 0;
+}
+
+void baseline_launch(focr_decoder *dec, const Geometry &g, size_t strip_bytes) {
+    const bool lds = strip_bytes + BASE_RED_BYTES <= LDS_STRIP_MAX;  // the strip shares LDS with the waves' pairs
+    const uint32_t grid = dec->base_grid ? std::min(dec->base_grid, g.total) : g.total;
+    const BaseFont f{dec->d_glyphs, dec->d_yglyphs, dec->d_offs, dec->d_yoffs, dec->d_bitmaps.as<const uint32_t>(), dec->d_ybitmaps.as<const uint32_t>(),
+                     (uint32_t)(dec->bitmaps_len / 4), dec->ybitmaps_dw, dec->n_glyphs, dec->origin_x, (int)dec->origin_y, dec->base_bits};
+    const auto kernel = lds ? line_baseline_kernel<true> : line_baseline_kernel<false>;
+    kernel<<<grid, BASE_THREADS, BASE_RED_BYTES + (lds ? strip_bytes : 0), dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, f, dec->base_n,
+                                                                                         dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
+}
+
+}  // namespace focr_dec
+
+using namespace focr_dec;
+
+namespace {
+
+void drop_fonts(focr_decoder *dec) {
+    dec->have_base_fonts = false;
+    dec->font_bits = 0;
+    dec->ybitmaps_dw = 0;
+    dec->d_yglyphs.release();
+    dec->d_yoffs.release();
+    dec->d_ybitmaps.release();
+}
+
+}  // namespace
+
+extern "C" int focr_decoder_set_baseline_fonts(focr_decoder_t *dec, const focr_decode_font_t *fonts, uint32_t y_bits) {
+    const char *who = "focr_decoder_set_baseline_fonts: ";
+    if (!dec) return dfail(nullptr, std::string(who) + "null decoder");
+    DEC_CHECK(hipSetDevice(dec->device));
+    DEC_CHECK(hipStreamSynchronize(dec->stream));
+    drop_fonts(dec);
+    if (!fonts) return dfail(dec, std::string(who) + "bad arguments");
+    if (y_bits > FOCR_BASELINE_Y_BITS_MAX) return dfail(dec, std::string(who) + "y_bits is at most 3");
+    if (!dec->n_glyphs) return dfail(dec, std::string(who) + "no font (focr_decoder_set_font)");
+    const size_t G = dec->n_glyphs, V = (size_t)1 << y_bits;
+    std::vector<DevGlyph> gl((V - 1) * G);
+    std::vector<int2> offs((V - 1) * G * FOCR_DECODE_PHASES);
+    uint64_t total = 0;
+    for (size_t v = 0; v < V; v++) {
+        const focr_decode_font_t &f = fonts[v];
+        if (!f.glyphs || f.n_glyphs != G || f.bitmaps_len % 4 || (f.bitmaps_len && !f.bitmaps))
+            return dfail(dec, std::string(who) + "a font does not match the decode font (glyph count)");
+        if (memcmp(&f.origin_x, &dec->origin_x, 4) || memcmp(&f.origin_y, &dec->origin_y, 4) || memcmp(&f.text_size, &dec->text_size, 4) ||
+            memcmp(&f.kerning, &dec->kerning, 4) || f.hinting != dec->hinting)
+            return dfail(dec, std::string(who) + "a font does not match the decode font (origin, size, kerning or hinting)");
+        for (size_t i = 0; i < G; i++) {
+            const focr_decode_glyph_t &s = f.glyphs[i], &t = dec->font_glyphs[i];
+            if (s.codepoint != t.codepoint || memcmp(&s.increment, &t.increment, 4))
+                return dfail(dec, std::string(who) + "a font does not match the decode font (code points or increments)");
+            if (s.stride % 4 || s.stride < s.box_w || s.offset % 4 || s.offset + (uint64_t)FOCR_DECODE_PHASES * s.stride * s.box_h > f.bitmaps_len ||
+                (uint64_t)s.stride * s.box_h * 2 * 255 * 255 >= (1ull << 31))
+                return dfail(dec, std::string(who) + "inconsistent glyph table");
+            if (v == 0) {
+                if (s.box_w != t.box_w || s.box_h != t.box_h || s.stride != t.stride || s.offset != t.offset ||
+                    memcmp(s.off_x, t.off_x, sizeof s.off_x) || memcmp(s.off_y, t.off_y, sizeof s.off_y))
+                    return dfail(dec, std::string(who) + "fonts[0] is not the decode font (glyph table)");
+                continue;
+            }
+            gl[(v - 1) * G + i] = DevGlyph{(uint32_t)((total + s.offset) / 4), s.stride / 4, s.box_h, s.increment};
+            for (int p = 0; p < FOCR_DECODE_PHASES; p++) offs[((v - 1) * G + i) * FOCR_DECODE_PHASES + p] = make_int2(s.off_x[p], s.off_y[p]);
+        }
+        if (v) total += f.bitmaps_len;
+        if (total / 4 > 0xffffffffull) return dfail(dec, std::string(who) + "bitmap tables too large");
+    }
+    {  // fonts[0]'s bitmaps against the decoder's own copy
+        if (fonts[0].bitmaps_len != dec->bitmaps_len) return dfail(dec, std::string(who) + "fonts[0] is not the decode font (bitmaps)");
+        std::vector<uint8_t> mine(dec->bitmaps_len);
+        if (!mine.empty()) DEC_CHECK(hipMemcpy(mine.data(), dec->d_bitmaps, mine.size(), hipMemcpyDeviceToHost));
+        if (!mine.empty() && memcmp(mine.data(), fonts[0].bitmaps, mine.size())) return dfail(dec, std::string(who) + "fonts[0] is not the decode font (bitmaps)");
+    }
+    if (V > 1) {
+        std::vector<uint8_t> all;
+        all.reserve(total);
+        for (size_t v = 1; v < V; v++) all.insert(all.end(), fonts[v].bitmaps, fonts[v].bitmaps + fonts[v].bitmaps_len);
+        if (dec->d_yglyphs.upload(gl.data(), gl.size()) != hipSuccess || dec->d_yoffs.upload(offs.data(), offs.size()) != hipSuccess ||
+            dec->d_ybitmaps.upload(all.data(), all.size(), 4) != hipSuccess) {
+            drop_fonts(dec);
+            return dfail(dec, std::string(who) + "hipMalloc / hipMemcpy failed");
+        }
+    }
+    dec->have_base_fonts = true;
+    dec->font_bits = y_bits;
+    dec->ybitmaps_dw = (uint32_t)(total / 4);
+    return 0;
+}
+
+extern "C" int focr_decoder_set_baseline_search(focr_decoder_t *dec, uint32_t y_bits, uint32_t n) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_baseline_search: null decoder");
+    if (y_bits > FOCR_BASELINE_Y_BITS_MAX) return dfail(dec, "focr_decoder_set_baseline_search: y_bits is at most 3");
+    if (n > FOCR_BASELINE_MAX) return dfail(dec, "focr_decoder_set_baseline_search: the radius is at most 32 steps");
+    dec->base_bits = y_bits;
+    dec->base_n = n;
+    return 0;
+}
+
+extern "C" int focr_decoder_get_baselines(const focr_decoder_t *dec, int8_t *q, int64_t *cost) {
+    if (!dec) return dfail(nullptr, "focr_decoder_get_baselines: null decoder");
+    if (!dec->have_baselines)
+        return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_baselines: the last successful run did not search baselines (focr_decoder_set_baseline_search)");
+    if (q && !dec->base_q.empty()) memcpy(q, dec->base_q.data(), dec->base_q.size());
+    if (cost && !dec->base_cost.empty()) memcpy(cost, dec->base_cost.data(), dec->base_cost.size() * sizeof(int64_t));
+    return 0;
+}
+
+extern "C" int focr_decoder_debug_set_baseline_grid(focr_decoder_t *dec, uint32_t grid) {
+    if (!dec) return dfail(nullptr, "focr_decoder_debug_set_baseline_grid: null decoder");
+    dec->base_grid = grid;
+    return 0;
+}

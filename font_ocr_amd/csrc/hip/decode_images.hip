@@ -3,7 +3,8 @@
 //
 // focr_decoder_verify draws focr --verify's image of the last run (decode.hip) in two launches, from the run's own buffers:
 //   4. verify_layout_kernel: one wave per work-list line repeats render()'s f32 arithmetic (pen, round_out bounds, the
-//      26.6 delta of every glyph; after a run with a pen search or a whole-line run (decode_whole.hip), from the pens the run chose) and
+//      26.6 delta of every glyph; after a run with a pen search or a whole-line run (decode_whole.hip), from the pens the run chose;
+//      after a baseline run (decode_baseline.hip) with the canvas moved by the nearest whole row of the line's offset) and
 //      writes each glyph's
 //      true bitmap rectangle, clipped to the canvas and the page;
 //   5. verify_compose_kernel: one workgroup per (page, 16 rows, 256 columns) tile takes, line by line in order, the
@@ -30,10 +31,12 @@ namespace focr_dec {
 // indices 0 .. n - 1 at (x_start, 0).  Lane 0 writes the line's canvas on the page to *line, clipped (empty when none
 // of it is on the page), with k and n.  js (null: none) is the run's pen search: glyph q is placed at pen + js[q] / 64
 // and the pen advances from there, the decoder's own two f32 adds.  ps (null: none) is a whole-line run's pens in
-// 1/64 px: glyph q is placed at ps[q] / 64 (exact), whatever the increments before it.
+// 1/64 px: glyph q is placed at ps[q] / 64 (exact), whatever the increments before it.  moved is a baseline run's whole rows
+// for this line (0: none): the canvas is drawn that many rows below the slot's y, above it when negative, and is then
+// clipped at the page's top as well.
 template <bool IOTA>
 __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, const uint16_t *__restrict__ cs,
-                                            const int8_t *__restrict__ js, const uint32_t *__restrict__ ps, uint32_t n, uint32_t k,
+                                            const int8_t *__restrict__ js, const uint32_t *__restrict__ ps, int moved, uint32_t n, uint32_t k,
                                             uint32_t x_start, const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
                                             const VerifyPhase *__restrict__ vphases, VerifyRec *__restrict__ out, VerifyLine *__restrict__ line) {
     const uint32_t lane = threadIdx.x;
@@ -68,14 +71,15 @@ __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, co
     }
     const int cw = lx - ox, ch = ly - oy;
     const int64_t W = g.page_w, H = g.page_h;
-    const int64_t line_y = IOTA ? 0 : (int64_t)g.y_start + (int64_t)(slot % g.n_slots) * g.line_advance;
+    const int64_t line_y = IOTA ? 0 : (int64_t)g.y_start + (int64_t)(slot % g.n_slots) * g.line_advance + moved;
+    const int top = IOTA ? 0 : (int)std::max<int64_t>(-line_y, 0);  // the canvas rows above the page (a line moved up)
     const float neg_ox = (float)(-ox);
     for (uint32_t j = lane; j < n; j += 64) {
         const float pos = __int_as_float(out[j].x0);
         const int d = (int)__fmul_rn(__fadd_rn(neg_ox, pos), 64.0f);  // FreeType's delta: trunc((-bounds.ox + pos) * 64) >= 0
         const VerifyPhase ph = vphases[(size_t)(IOTA ? j : cs[j]) * FOCR_DECODE_PHASES + (d & 63)];
         const int gx0 = (d >> 6) + ph.x, gy0 = ph.y - oy;  // on the canvas: whole-pixel shift, vertical delta -bounds.oy
-        const int ax0 = std::max(gx0, 0), ay0 = std::max(gy0, 0);
+        const int ax0 = std::max(gx0, 0), ay0 = std::max(gy0, top);
         const int ax1 = std::min(gx0 + (int)ph.w, cw), ay1 = std::min(gy0 + (int)ph.h, ch);
         const int64_t X0 = x_start + (int64_t)ax0, Y0 = line_y + ay0;
         const int64_t X1 = std::min<int64_t>(x_start + (int64_t)ax1, W), Y1 = std::min<int64_t>(line_y + ay1, H);
@@ -88,7 +92,7 @@ __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, co
     if (lane == 0) {
         const int64_t X1 = std::min<int64_t>(x_start + (int64_t)cw, W), Y1 = std::min<int64_t>(line_y + ch, H);
         VerifyLine l{0, 0, 0, 0, k, n};
-        if ((int64_t)x_start < X1 && line_y < Y1) l = VerifyLine{(int32_t)x_start, (int32_t)line_y, (int32_t)X1, (int32_t)Y1, k, n};
+        if ((int64_t)x_start < X1 && line_y + top < Y1) l = VerifyLine{(int32_t)x_start, (int32_t)(line_y + top), (int32_t)X1, (int32_t)Y1, k, n};
         *line = l;
     }
 }
@@ -98,6 +102,7 @@ __global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t 
                                                            const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
                                                            const uint32_t *__restrict__ n_chars, const uint16_t *__restrict__ chars,
                                                            const int8_t *__restrict__ pen_offs, const uint32_t *__restrict__ pens,
+                                                           const int32_t *__restrict__ line_q, uint32_t y_bits,
                                                            const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
                                                            const VerifyPhase *__restrict__ vphases, VerifyLine *__restrict__ lines,
                                                            VerifyRec *__restrict__ recs, unsigned long long *__restrict__ sums) {
@@ -107,8 +112,10 @@ __global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t 
     if (lane == 0 && flags[b] == 0) lines[b] = VerifyLine{0, 0, 0, 0, 0, 0};  // blank slots are in no work-list entry
     if (b >= *count) return;
     const uint32_t k = b, slot = work[k], n = n_chars[k];
+    // a baseline run's line (line_q; null: none) is drawn moved by the nearest whole row of its offset q * 2^-y_bits
+    const int moved = line_q ? (line_q[k] + (int)((1u << y_bits) >> 1)) >> y_bits : 0;
     layout_line<false>(g, slot, chars + (size_t)k * g.cap, pen_offs ? pen_offs + (size_t)k * g.cap : nullptr,
-                       pens ? pens + (size_t)k * g.cap : nullptr, n, k, x_start,
+                       pens ? pens + (size_t)k * g.cap : nullptr, moved, n, k, x_start,
                        glyphs, vglyphs, vphases, recs + (size_t)k * g.cap, lines + slot);
 }
 
@@ -209,7 +216,7 @@ __global__ __launch_bounds__(TEST_THREADS) void test_flags_kernel(const uint8_t 
 __global__ __launch_bounds__(64) void test_layout_kernel(Geometry g, uint32_t n_glyphs, const DevGlyph *__restrict__ glyphs,
                                                          const VerifyGlyph *__restrict__ vglyphs, const VerifyPhase *__restrict__ vphases,
                                                          VerifyRec *__restrict__ recs, VerifyLine *__restrict__ line) {
-    layout_line<true>(g, 0, nullptr, nullptr, nullptr, n_glyphs, 0, 0, glyphs, vglyphs, vphases, recs, line);
+    layout_line<true>(g, 0, nullptr, nullptr, nullptr, 0, n_glyphs, 0, 0, glyphs, vglyphs, vphases, recs, line);
 }
 
 // 8. both test images, tile by tile; every thread owns one column of a 16-row, 256-column tile.  The base pixel is
@@ -353,11 +360,15 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, dec->run_x_start, dec->d_flags, dec->d_work,
                                                                          dec->d_count, dec->d_nchars, dec->d_chars,
                                                                          dec->run_searched ? (const int8_t *)dec->d_pen : nullptr,
-                                                                         dec->run_whole ? (const uint32_t *)dec->d_pens : nullptr, dec->d_glyphs,
+                                                                         dec->run_whole ? (const uint32_t *)dec->d_pens : nullptr,
+                                                                         dec->run_base ? (const int32_t *)dec->d_base_q : nullptr, dec->run_bits, dec->d_glyphs,
                                                                          dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
     DEC_CHECK(hipGetLastError());
-    verify_compose_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->run_src, g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y, dec->d_vlines, dec->d_vrecs,
-                                                                      (const uint8_t *)dec->d_bitmaps, d_rgb, dec->d_sums);
+    if (dec->run_base)  // the canvases of a baseline run are moved off their slots: decode_baseline.hip's compose finds them
+        verify_compose_moved_launch(dec, tg, n_pages, d_rgb);
+    else
+        verify_compose_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->run_src, g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y, dec->d_vlines, dec->d_vrecs,
+                                                                          (const uint8_t *)dec->d_bitmaps, d_rgb, dec->d_sums);
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->verify.end, dec->stream));
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit sums");

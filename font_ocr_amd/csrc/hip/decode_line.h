@@ -1,7 +1,8 @@
-// decode_line.h — what the two translation units of the `focr` line decoder share (decode.hip: prepass, compaction, the pen
-// loop and its search, and the run itself; decode_whole.hip: the whole-line decode): the strip's constants, the device
-// helpers both files' kernels call (no relocatable device code: they are inlined into each), and the whole-line decode's
-// plan, which focr_decoder_run asks for and hands back.
+// decode_line.h — what the translation units of the `focr` line decoder share (decode.hip: prepass, compaction, the pen
+// loop and its search, and the run itself; decode_whole.hip: the whole-line decode; decode_baseline.hip: the baseline
+// search): the strip's constants, the device helpers the files' kernels call (no relocatable device code: they are inlined
+// into each), the whole-line decode's plan, which focr_decoder_run asks for and hands back, and the baseline search's
+// three steps of a run.
 #pragma once
 
 #include "decode.h"
@@ -72,5 +73,14 @@ int whole_plan(focr_decoder *dec, const Geometry &g, WholePlan *plan);
 int whole_reserve(focr_decoder *dec, const Geometry &g, const WholePlan &plan);
 // The third launch of a whole-line run, on the decoder's stream; the caller checks hipGetLastError.
 void whole_launch(focr_decoder *dec, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
+
+// ---- the baseline search as focr_decoder_run sees it (decode_baseline.hip) -------------------------------------------
+
+// The refusals of a baseline run (include/focr_decode.h), before anything is launched.
+int baseline_plan(focr_decoder *dec);
+// The run's per-line result buffers.
+int baseline_reserve(focr_decoder *dec, const Geometry &g);
+// The third launch of a baseline run, on the decoder's stream; the caller checks hipGetLastError.
+void baseline_launch(focr_decoder *dec, const Geometry &g, size_t strip_bytes);
 
 }  // namespace focr_dec

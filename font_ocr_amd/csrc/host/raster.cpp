@@ -482,8 +482,10 @@ struct Phases {
     int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
 };
 
-int render_phases(Alphabet &a, size_t i, float text_size, int hinting, Phases *out, char *err, size_t errlen) {
-    const FT_Pos dy = -delta_of(a.origin_y + 0.f);  // origin + pos, pos.y = 0
+// FreeType's delta y of the line origin: origin + pos, pos.y = 0
+FT_Pos origin_dy(const Alphabet &a) { return -delta_of(a.origin_y + 0.f); }
+
+int render_phases(Alphabet &a, size_t i, float text_size, int hinting, FT_Pos dy, Phases *out, char *err, size_t errlen) {
     bool any = false;
     for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
         if (!render_delta(a.f, a.gids[i], text_size, hinting, p, dy, &out->ph[p])) return fail(err, errlen, "FT_Load_Glyph failed");
@@ -498,16 +500,9 @@ int render_phases(Alphabet &a, size_t i, float text_size, int hinting, Phases *o
     return 0;
 }
 
-}  // namespace
-
-extern "C" int focr_decode_font_build(const char *font_path, float text_size, int hinting, float kerning,
-                                      const uint32_t *alphabet, size_t n_alphabet, focr_decode_font_t *out, char *err,
-                                      size_t errlen) {
-    if (!font_path || !alphabet || !n_alphabet || !out) return fail(err, errlen, "focr_decode_font_build: bad arguments");
-    memset(out, 0, sizeof *out);
-    Alphabet a;
-    if (open_alphabet(font_path, text_size, kerning, alphabet, n_alphabet, &a, err, errlen)) return 1;
-
+// The decode font of an open alphabet with every phase rendered at FreeType's delta y = dy
+int build_decode_font(Alphabet &a, float text_size, int hinting, float kerning, const uint32_t *alphabet, size_t n_alphabet, FT_Pos dy,
+                      focr_decode_font_t *out, char *err, size_t errlen) {
     std::vector<focr_decode_glyph_t> glyphs(n_alphabet);
     std::vector<uint8_t> bitmaps;
     float min_inc = 0.f;
@@ -518,7 +513,7 @@ extern "C" int focr_decode_font_build(const char *font_path, float text_size, in
         if (glyph_increment(a, i, alphabet[i], text_size, kerning, &g.increment, err, errlen)) return 1;
         min_inc = i == 0 ? g.increment : std::fmin(min_inc, g.increment);
         Phases ph;
-        if (render_phases(a, i, text_size, hinting, &ph, err, errlen)) return 1;
+        if (render_phases(a, i, text_size, hinting, dy, &ph, err, errlen)) return 1;
         g.box_w = (uint32_t)(ph.x1 - ph.x0);
         g.box_h = (uint32_t)(ph.y1 - ph.y0);
         g.stride = (g.box_w + 3) & ~3u;
@@ -554,6 +549,37 @@ extern "C" int focr_decode_font_build(const char *font_path, float text_size, in
     return 0;
 }
 
+}  // namespace
+
+extern "C" int focr_decode_font_build(const char *font_path, float text_size, int hinting, float kerning,
+                                      const uint32_t *alphabet, size_t n_alphabet, focr_decode_font_t *out, char *err,
+                                      size_t errlen) {
+    if (!font_path || !alphabet || !n_alphabet || !out) return fail(err, errlen, "focr_decode_font_build: bad arguments");
+    memset(out, 0, sizeof *out);
+    Alphabet a;
+    if (open_alphabet(font_path, text_size, kerning, alphabet, n_alphabet, &a, err, errlen)) return 1;
+    return build_decode_font(a, text_size, hinting, kerning, alphabet, n_alphabet, origin_dy(a), out, err, errlen);
+}
+
+extern "C" int focr_decode_font_build_y(const char *font_path, float text_size, int hinting, float kerning,
+                                        const uint32_t *alphabet, size_t n_alphabet, uint32_t y_bits, focr_decode_font_t *out,
+                                        char *err, size_t errlen) {
+    if (!font_path || !alphabet || !n_alphabet || !out) return fail(err, errlen, "focr_decode_font_build_y: bad arguments");
+    if (y_bits > FOCR_BASELINE_Y_BITS_MAX) return fail(err, errlen, "focr_decode_font_build_y: y_bits is at most 3");
+    const uint32_t n_v = 1u << y_bits;
+    memset(out, 0, sizeof *out * n_v);
+    Alphabet a;
+    if (open_alphabet(font_path, text_size, kerning, alphabet, n_alphabet, &a, err, errlen)) return 1;
+    for (uint32_t v = 0; v < n_v; v++) {  // v * 2^-B and the sum are exact in f32 for a whole origin_y
+        const float ty = a.origin_y + (float)v / (float)n_v;
+        if (build_decode_font(a, text_size, hinting, kerning, alphabet, n_alphabet, -delta_of(ty), &out[v], err, errlen)) {
+            for (uint32_t u = 0; u <= v; u++) focr_decode_font_free(&out[u]);
+            return 1;
+        }
+    }
+    return 0;
+}
+
 extern "C" void focr_decode_font_free(focr_decode_font_t *font) {
     if (!font) return;
     free(font->glyphs);
@@ -578,7 +604,7 @@ extern "C" int focr_verify_font_build(const char *font_path, float text_size, in
         if (!a.f.raster_box(a.gids[i], text_size, &box)) return fail(err, errlen, "glyph load failed");
         g.box[0] = box.ox, g.box[1] = box.oy, g.box[2] = box.lx, g.box[3] = box.ly;
         Phases ph;
-        if (render_phases(a, i, text_size, hinting, &ph, err, errlen)) return 1;
+        if (render_phases(a, i, text_size, hinting, origin_dy(a), &ph, err, errlen)) return 1;
         for (int p = 0; p < FOCR_DECODE_PHASES; p++) {  // an empty bitmap is the empty rectangle at the box's corner
             const Bitmap &b = ph.ph[p];
             const bool ink = b.w && b.h;

@@ -19,6 +19,10 @@
         pages, pens, costs, offsets = dec.decode(luma_pages, 45, 39, 608, 12, 15, whole_line=True, pen_slack=8)
         # the whole-line decode for text off the 1/64 px grid: every step may move the pen by up to 8/64 px before its glyph
         # is rendered; pens[page][line]: each character's render pen, offsets[page][line]: the offset it took
+        dec.set_font("DejaVuSansMono.ttf", 13.0, y_bits=2)
+        pages, baselines, costs = dec.decode(luma_pages, 45, 39, 608, 12, 15, baseline_search=8)
+        # every line decoded at the vertical offsets -8 ..= 8 quarter pixels and the one with the lowest summed footprint
+        # term kept; baselines[page][line]: its q (the line sits q / 4 px below the crop's baseline), costs[page][line]: its sum
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -109,16 +113,27 @@ def _check_verify(verify):
 
 
 class DecodeFont:
-    """The 64-phase table of an alphabet (focr_decode_font_build).  Owns the native struct; free with close()."""
+    """The 64-phase table of an alphabet (focr_decode_font_build), and with y_bits > 0 its 1 << y_bits y-phase tables
+    (focr_decode_font_build_y; phase 0 is the plain table).  Owns the native structs; free with close()."""
 
-    def __init__(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0):
+    def __init__(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0, y_bits=0):
+        if not 0 <= int(y_bits) <= 3:
+            raise ValueError(f"y_bits must be 0 .. 3, not {y_bits!r}")
         self.font_path, self.text_size, self.alphabet = font_path, float(text_size), alphabet
-        self.hinting, self.kerning = bool(hinting), float(kerning)
-        self.s = N.DecodeFontStruct()
+        self.hinting, self.kerning, self.y_bits = bool(hinting), float(kerning), int(y_bits)
+        self.fonts = (N.DecodeFontStruct * (1 << self.y_bits))()
+        self.s = self.fonts[0]
         cps, n = _codepoints(alphabet)
         e = _err()
-        if N.decode_raster().focr_decode_font_build(font_path.encode(), self.text_size, int(hinting), self.kerning, cps, n,
-                                                    C.byref(self.s), e, len(e)) != 0:
+        lib = N.decode_raster()
+        if self.y_bits:
+            rc = lib.focr_decode_font_build_y(font_path.encode(), self.text_size, int(hinting), self.kerning, cps, n, self.y_bits,
+                                              self.fonts, e, len(e))
+        else:
+            rc = lib.focr_decode_font_build(font_path.encode(), self.text_size, int(hinting), self.kerning, cps, n,
+                                            C.byref(self.s), e, len(e))
+        if rc != 0:
+            self.s = self.fonts = None
             raise DecoderError(e.value.decode())
 
     @property
@@ -128,18 +143,20 @@ class DecodeFont:
     def increments(self):
         return np.array([self.s.glyphs[i].increment for i in range(self.s.n_glyphs)], dtype=np.float32)
 
-    def phase(self, i, p):
-        """(bitmap h x w, off_x, off_y) of glyph i's phase p."""
-        g = self.s.glyphs[i]
+    def phase(self, i, p, v=0):
+        """(bitmap h x w, off_x, off_y) of glyph i's phase p in y-phase v."""
+        f = self.fonts[v]
+        g = f.glyphs[i]
         n = g.stride * g.box_h
-        raw = np.ctypeslib.as_array(self.s.bitmaps, shape=(self.s.bitmaps_len,))
+        raw = np.ctypeslib.as_array(f.bitmaps, shape=(f.bitmaps_len,))
         bm = raw[g.offset + p * n: g.offset + (p + 1) * n].reshape(g.box_h, g.stride)[:, : g.box_w]
         return bm.copy(), int(g.off_x[p]), int(g.off_y[p])
 
     def close(self):
         if self.s is not None:
-            N.decode_raster().focr_decode_font_free(C.byref(self.s))
-            self.s = None
+            for f in self.fonts:
+                N.decode_raster().focr_decode_font_free(C.byref(f))
+            self.s = self.fonts = None
 
     def __del__(self):
         try:
@@ -203,16 +220,21 @@ class LineDecoder:
         self._whole = False  # the library's switch (focr_decoder_set_whole_line)
         self._margins = False  # the library's switch (focr_decoder_set_whole_margins)
         self._pen_slack = 0  # the library's radius (focr_decoder_set_whole_slack)
+        self._baseline = (0, 0)  # the library's y_bits and radius (focr_decoder_set_baseline_search)
 
     def _check(self, rc):
         if rc != 0:
             raise DecoderError(self._lib.focr_decoder_last_error(self._h).decode())
 
-    def set_font(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0):
-        font = font_path if isinstance(font_path, DecodeFont) else DecodeFont(font_path, text_size, alphabet, hinting, kerning)
-        self._vfont, self._batch = None, None  # the library drops its verify table and its last run here too
+    def set_font(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0, y_bits=0):
+        """Build (or take, when font_path is a DecodeFont) and upload the decode font.  y_bits > 0 also builds and uploads
+        its 1 << y_bits y-phase tables, for decode(baseline_search=N) in steps of 2^-y_bits px; a DecodeFont brings its own."""
+        font = font_path if isinstance(font_path, DecodeFont) else DecodeFont(font_path, text_size, alphabet, hinting, kerning, y_bits)
+        self._vfont, self._batch = None, None  # the library drops its verify table, its y-phase fonts and its last run here too
         self._check(self._lib.focr_decoder_set_font(self._h, C.byref(font.s)))
         self.font = font
+        if font.y_bits:
+            self._check(self._lib.focr_decoder_set_baseline_fonts(self._h, font.fonts, font.y_bits))
         return font
 
     def verify(self, images=True, rgb_device=None):
@@ -316,12 +338,17 @@ class LineDecoder:
         return mse, imgs
 
     def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0, whole_line=False,
-             margins=False, pen_slack=0):
+             margins=False, pen_slack=0, baseline_search=0):
         """[[(y, text), ...] per page] of one batch; with scores [[LineScores, ...] per page] beside it (else None); with
         a pen search [[int8 offsets, ...] per page] (else None); with whole_line ([[uint32 pens, ...] per page],
         [[cost, ...] per page]) (else None), and with margins [[LineMargins, ...] per page], or with a pen slack
-        [[int8 offsets, ...] per page], as a third element of that."""
+        [[int8 offsets, ...] per page], as a third element of that; with a baseline search ([[q, ...] per page],
+        [[cost, ...] per page]) (else None)."""
         self._batch = None
+        baseline = (self.font.y_bits if baseline_search else 0, int(baseline_search))
+        if baseline != self._baseline:
+            self._check(self._lib.focr_decoder_set_baseline_search(self._h, *baseline))
+            self._baseline = baseline
         if int(pen_slack) != self._pen_slack:
             self._check(self._lib.focr_decoder_set_whole_slack(self._h, int(pen_slack)))
             self._pen_slack = int(pen_slack)
@@ -358,6 +385,11 @@ class LineDecoder:
         if margins:
             ms = np.zeros(max(1, nc), dtype=np.dtype([("term", "<i4"), ("runner", "<u2"), ("pad", "<u2"), ("margin", "<i8")]))
             self._check(self._lib.focr_decoder_get_margins(self._h, ms.ctypes.data))
+        if baseline_search:
+            bq = np.zeros(max(1, nl), dtype=np.int8)
+            bc = np.zeros(max(1, nl), dtype=np.int64)
+            self._check(self._lib.focr_decoder_get_baselines(self._h, bq.ctypes.data, bc.ctypes.data))
+        found = ([[] for _ in range(n)], [[] for _ in range(n)]) if baseline_search else None
         alpha = self.font.alphabet
         whole = ([[] for _ in range(n)], [[] for _ in range(n)]) + (([[] for _ in range(n)],) if margins or pen_slack else ()) if whole_line else None
         out = [[] for _ in range(n)]
@@ -367,6 +399,9 @@ class LineDecoder:
             ln = lines[k]
             text = "".join(alpha[c] for c in chars[ln.first: ln.first + ln.n_chars])
             out[ln.page].append((int(ln.y), text))
+            if baseline_search:
+                found[0][ln.page].append(int(bq[k]))
+                found[1][ln.page].append(int(bc[k]))
             if pen_search:
                 offs[ln.page].append(js[ln.first: ln.first + ln.n_chars].copy())
             if whole_line:
@@ -381,7 +416,7 @@ class LineDecoder:
             if scores:
                 c = cs[ln.first: ln.first + ln.n_chars]
                 sc[ln.page].append(LineScores(int(base[k]), c["score"].copy(), c["runner"].copy(), c["runner_score"].copy()))
-        return out, sc, offs, whole
+        return out, sc, offs, whole, found
 
     @staticmethod
     def _check_pen_search(pen_search):
@@ -413,8 +448,19 @@ class LineDecoder:
             raise ValueError("pen_slack does not go with margins=True (margins under a pen slack have no definition yet)")
         return int(pen_slack)
 
+    @staticmethod
+    def _check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack):
+        n = int(baseline_search)
+        if not 0 <= n <= 32:
+            raise ValueError(f"baseline_search must be 0 .. 32 (steps of 2^-y_bits px), not {baseline_search!r}")
+        for on, what in ((scores, "scores=True"), (pen_search, "pen_search"), (whole_line, "whole_line=True"), (margins, "margins=True"),
+                         (pen_slack, "pen_slack")):
+            if n and on:
+                raise ValueError(f"baseline_search does not go with {what} (the baseline search runs the plain pen loop per candidate)")
+        return n
+
     def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, pen_slack=0,
-               margins=False, whole_line=False):
+               baseline_search=0, margins=False, whole_line=False):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
         Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
         mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
@@ -434,7 +480,13 @@ class LineDecoder:
         most half the font's smallest advance) every step of the whole-line decode may move the pen by an offset of -N ..= N
         before its glyph is rendered, for pages whose glyphs do not sit on this FreeType's 1/64 px pens; pens then holds
         each character's render pen and the result gains one last element after costs: offsets[page][line], an int8 array
-        of the offset each character took.  It needs whole_line=True and does not go with margins."""
+        of the offset each character took.  It needs whole_line=True and does not go with margins.
+        With baseline_search=N > 0 (an extension, up to 32; include/focr_decode.h) every line is decoded at the vertical
+        offsets q in -N ..= N, in steps of 2^-y_bits px of the font's y_bits (set_font(..., y_bits=B)), and the candidate
+        with the lowest summed footprint term is the line (on a tie the offset nearest 0).  The result gains two last
+        elements: baselines[page][line], the chosen q (int), and costs[page][line], its sum of footprint terms (int).  The
+        verify then draws each line moved by the nearest whole row of its offset.  It goes with none of scores, pen_search,
+        whole_line, margins and pen_slack (ValueError)."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
@@ -442,6 +494,7 @@ class LineDecoder:
         whole_line = self._check_whole_line(whole_line, scores, pen_search)
         margins = self._check_margins(margins, whole_line)
         pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
+        baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
@@ -451,6 +504,7 @@ class LineDecoder:
         sc = [None] * len(pages)
         offs = [None] * len(pages)
         wpens, wcosts, wmargins, woffs = [None] * len(pages), [None] * len(pages), [None] * len(pages), [None] * len(pages)
+        bqs, bcosts = [None] * len(pages), [None] * len(pages)
         mse = np.zeros(len(pages), dtype=np.float32)
         images = [None] * len(pages) if verify == "image" else None
         by_size = {}
@@ -458,11 +512,13 @@ class LineDecoder:
             by_size.setdefault(np.asarray(p).shape, []).append(i)
         for (h, w), idx in by_size.items():
             batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
-            res, res_sc, res_offs, res_whole = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
-                                                         pen_search=pen_search, whole_line=whole_line, margins=margins,
-                                                         pen_slack=pen_slack)
+            res, res_sc, res_offs, res_whole, res_base = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
+                                                                   pen_search=pen_search, whole_line=whole_line, margins=margins,
+                                                                   pen_slack=pen_slack, baseline_search=baseline_search)
             for j, i in enumerate(idx):
                 out[i] = res[j]
+                if baseline_search:
+                    bqs[i], bcosts[i] = res_base[0][j], res_base[1][j]
                 if whole_line:
                     wpens[i], wcosts[i] = res_whole[0][j], res_whole[1][j]
                 if margins:
@@ -490,10 +546,12 @@ class LineDecoder:
             res += (wmargins,)
         if pen_slack:
             res += (woffs,)
+        if baseline_search:
+            res += (bqs, bcosts)
         return res if len(res) > 1 else out
 
     def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False,
-                      pen_search=0, pen_slack=0, margins=False, whole_line=False):
+                      pen_search=0, pen_slack=0, baseline_search=0, margins=False, whole_line=False):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
         if self.font is None:
@@ -503,9 +561,10 @@ class LineDecoder:
         whole_line = self._check_whole_line(whole_line, scores, pen_search)
         margins = self._check_margins(margins, whole_line)
         pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
-        out, sc, offs, whole = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
-                                         int(line_height), int(line_advance), scores=scores, pen_search=pen_search, whole_line=whole_line,
-                                         margins=margins, pen_slack=pen_slack)
+        baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
+        out, sc, offs, whole, base = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
+                                               int(line_height), int(line_advance), scores=scores, pen_search=pen_search,
+                                               whole_line=whole_line, margins=margins, pen_slack=pen_slack, baseline_search=baseline_search)
         res = (out,)
         if verify:
             mse, imgs = self._verified(verify, int(page_h), int(page_w))
@@ -516,6 +575,8 @@ class LineDecoder:
             res += (offs,)
         if whole_line:
             res += whole
+        if baseline_search:
+            res += base
         return res if len(res) > 1 else out
 
     def close(self):

@@ -8,7 +8,7 @@
  * the decode font below holds those 64 phases per glyph, built once on the host, and the device does an exact integer
  * argmin with them.
  *
- * libfocr_raster.so : focr_raster_glyph, focr_glyph_metrics, focr_render_text, focr_decode_font_build/free,
+ * libfocr_raster.so : focr_raster_glyph, focr_glyph_metrics, focr_render_text, focr_decode_font_build/build_y/free,
  *                     focr_verify_font_build/free (FreeType)
  * libfocr_hip.so    : focr_decoder_* (gfx950), including the device verify of a run (--verify) and the test images
  *                     (--test)
@@ -302,6 +302,60 @@ int focr_decoder_get_margins(const focr_decoder_t *dec, focr_char_margin_t *out)
  * font).  n above FOCR_PEN_SEARCH_MAX is refused here. */
 int focr_decoder_set_whole_slack(focr_decoder_t *dec, uint32_t n);
 
+/* ---- baseline search (an extension: the reference renders every glyph at one vertical position) ------------------- */
+
+/* The reference renders every glyph at the crop's top plus origin_y, and the crop's y is a whole pixel: a line whose
+ * baseline sits elsewhere (a y that is a pixel off, lines a renderer snapped one by one, a leading that is not a whole
+ * number of pixels) loses its text.  The pen search corrects the pen in x; this is its counterpart in y, per line.  With
+ * y_bits B (0 <= B <= FOCR_BASELINE_Y_BITS_MAX) and a radius N (0 <= N <= FOCR_BASELINE_MAX, in steps of 2^-B px) a run
+ * decodes every line once per candidate q in -N ..= N and keeps one of them.  All of it is exact:
+ *   - candidate q renders every glyph at the vertical translation ty_q = origin_y + q * 2^-B (exact in f32): FreeType
+ *     receives delta y = -trunc(ty_q * 64);
+ *   - a candidate with ty_q < 0 is dropped (q = 0 never is);
+ *   - origin_y must be a whole number >= 0 (the font builder's always is; the run refuses otherwise), so that rendering
+ *     is y-phase v = q & (2^B - 1) of the font (focr_decode_font_build_y) moved down by d = q >> B rows (floor; up for
+ *     d < 0);
+ *   - under candidate q the line is decoded by the plain pen loop, unchanged: the f32 pen, delta x =
+ *     trunc((origin_x + pos) * 64), the first minimum over the glyphs, while pos < width;
+ *   - bitmaps are clipped to the crop on all four sides: rows that d pushes above row 0 or below the crop's last row do
+ *     not count;
+ *   - cost_q is the int64 sum of the chosen glyphs' int32 footprint terms (score less line_base); line_base + cost_q is
+ *     the line's squared error while footprints do not overlap;
+ *   - the line is the candidate with the lowest (cost_q, rank(q)), rank as in the pen search (0, -1, +1, -2, ...): on a
+ *     tie the offset nearest 0 wins, so a line no glyph reaches takes q = 0.
+ * A run returns that candidate's text, and per line its q and its cost (focr_decoder_get_baselines); q * 2^-B px is how
+ * far below the crop's own baseline the line sits.  N = 0 is the plain decoder, choice for choice and launch for launch,
+ * whatever fonts are uploaded.  With N > 0 prepass and compaction are the plain run's and the launch count stays 3.
+ * focr_decoder_run refuses, before anything is launched and each with a message that names both setters, N > 0 with
+ * scores, a pen search, the whole-line decode, margins or a pen slack; it also refuses N > 0 with B > 0 unless y-phase
+ * fonts of that B are uploaded (focr_decoder_set_baseline_fonts), and an origin_y that is not a whole number >= 0.
+ * What it does not cure: a leading that drifts past the radius down a page (every line searches around the same crop
+ * grid; the offset is not carried from line to line). */
+enum { FOCR_BASELINE_MAX = 32, FOCR_BASELINE_Y_BITS_MAX = 3 };
+
+/* host (libfocr_raster.so): the 1 << y_bits y-phase fonts of an alphabet.  out[v] is what focr_decode_font_build
+ * produces with the vertical translation origin_y + v * 2^-y_bits in origin_y's place: all fonts share glyph order,
+ * increments (bitwise), origin (origin_y stays the line's), size, kerning and hinting; out[0] equals the plain build
+ * byte for byte; box sizes may differ between v; each font passes the build's own int32 bound.  Same refusals as
+ * focr_decode_font_build, and y_bits > FOCR_BASELINE_Y_BITS_MAX.  Free each font with focr_decode_font_free. */
+int focr_decode_font_build_y(const char *font_path, float text_size, int hinting, float kerning, const uint32_t *alphabet,
+                             size_t n_alphabet, uint32_t y_bits, focr_decode_font_t *out, char *err, size_t errlen);
+
+/* Upload the y-phase fonts fonts[0 .. 1 << y_bits) of the current decode font (the decoder keeps its own copy of the
+ * phases v >= 1).  Refused unless every one matches the decode font: glyph count, code points, increments (bitwise),
+ * origin, size, kerning and hinting, and fonts[0]'s glyph table and bitmaps byte for byte.  focr_decoder_set_font drops
+ * them, and so does a failed upload. */
+int focr_decoder_set_baseline_fonts(focr_decoder_t *dec, const focr_decode_font_t *fonts, uint32_t y_bits);
+/* Set y_bits and the radius of later runs (0, 0 when the decoder is created; a state of the decoder, not of the font).
+ * y_bits above FOCR_BASELINE_Y_BITS_MAX and n above FOCR_BASELINE_MAX are refused here. */
+int focr_decoder_set_baseline_search(focr_decoder_t *dec, uint32_t y_bits, uint32_t n);
+/* The chosen q and cost of every line of the last run, in the order of focr_decoder_get: q[n_lines], cost[n_lines].
+ * Either may be NULL.  Fails with a message unless the last successful run searched (n > 0). */
+int focr_decoder_get_baselines(const focr_decoder_t *dec, int8_t *q, int64_t *cost);
+/* Debug: at most `grid` workgroups for later baseline runs (0: one per line slot), so that a test can make one workgroup
+ * take several lines. */
+int focr_decoder_debug_set_baseline_grid(focr_decoder_t *dec, uint32_t grid);
+
 /* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
 
 /* Upload the verify table of the current decode font (the decoder keeps its own copy).  Refused unless it matches the
@@ -316,7 +370,10 @@ int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_verify_font_t *
  * reference's MSE is (float)sum / (float)(uint32_t)(page_w * page_h)).  For a run from device-memory pages, the
  * caller's page buffer must still hold those pages.  After a run with a pen search every character is rendered at
  * the pen the run chose for it (pen + j / 64, then the increment from there), and after a whole-line run at
- * pos = s / 64 of its returned pen s (with pen slack that is the render pen), so the image shows the line where it was decoded.  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
+ * pos = s / 64 of its returned pen s (with pen slack that is the render pen), so the image shows the line where it was decoded.
+ * After a run with a baseline search every line's canvas is drawn moved by the nearest whole row of its offset,
+ * (q + (1 << B >> 1)) >> B rows down (up when negative), and clipped at the page's top as well as its bottom; the
+ * sub-pixel part of the offset is not drawn (the verify table has one vertical phase).  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
  * without a successful run since the last set_font, or without a verify table. */
 int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums);
 /* Device time of the last verify's kernels in ms (events), and their launch count (constant per batch). */

@@ -46,6 +46,15 @@ pen_slack=N)), in runs that alternate with whole-line runs without it:
   slack_wall_ms_per_batch     median host time of one decode(whole_line=True, pen_slack=N) call, offsets read back and unpacked
   slack_lines_changed         lines of the batch the slack decodes differently from the whole-line run
   slack_chars_offset          characters of the batch that took an offset other than 0
+With --baseline-search N [--y-bits B], also the decode with a baseline search of N steps of 2^-B px either way
+(LineDecoder.decode(baseline_search=N) with the font's y-phase tables of B), in runs that alternate with plain ones:
+  base_device_ms_per_batch    median device time of the batch's kernels with the search on (the same 3 launches)
+  base_plain_device_ms        median device time of the plain runs in between
+  base_over_plain             the ratio of the two, beside base_candidates = 2 N + 1 decodes per line and base_ceiling =
+                              2 N + 2, what one plain run per candidate and one more for the winner would cost
+  base_wall_ms_per_batch      median host time of one decode(baseline_search=N) call, offsets and costs read back
+  base_lines_changed          lines of the batch the search decodes differently from the plain run
+  base_lines_offset           lines of the batch that took an offset other than 0
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -100,16 +109,20 @@ def main():
     ap.add_argument("--whole-line", action="store_true", help="also time the whole-line decode")
     ap.add_argument("--margins", action="store_true", help="with --whole-line: also time the whole-line decode with margins")
     ap.add_argument("--pen-slack", type=int, default=0, metavar="N", help="with --whole-line: also time the whole-line decode with a pen slack of N/64 px")
+    ap.add_argument("--baseline-search", type=int, default=0, metavar="N", help="also time the decode with a baseline search of N steps either way")
+    ap.add_argument("--y-bits", type=int, default=0, metavar="B", help="with --baseline-search: steps of 2^-B px")
     ap.add_argument("--font", default=FONT, metavar="PATH", help="the font of the pages and of the decoder [DejaVu Sans Mono]")
     a = ap.parse_args()
     if a.margins and not a.whole_line:
         ap.error("--margins needs --whole-line")
     if a.pen_slack and not a.whole_line:
         ap.error("--pen-slack needs --whole-line")
+    if a.y_bits and not a.baseline_search:
+        ap.error("--y-bits needs --baseline-search")
     pages = synth(a.pages, a.seed, font=a.font)
     geo = (45, 39, 608, 12, 15)
     t0 = time.perf_counter()
-    font = DecodeFont(a.font, 13.0, FOCR_DEFAULT_ALPHABET)
+    font = DecodeFont(a.font, 13.0, FOCR_DEFAULT_ALPHABET, y_bits=a.y_bits)
     host_ms = (time.perf_counter() - t0) * 1e3
     with LineDecoder(0) as dec:
         dec.set_font(font, 13.0)
@@ -194,6 +207,18 @@ def main():
                 kwall.append((time.perf_counter() - t) * 1e3)
                 kdev.append(dec.last_ms)
             klaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+        if a.baseline_search:
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, baseline_search=a.baseline_search)
+            bdev, bwall, bpdev = [], [], []
+            for _ in range(a.steps):
+                dec.decode(pages, *geo)
+                bpdev.append(dec.last_ms)
+                t = time.perf_counter()
+                bgot = dec.decode(pages, *geo, baseline_search=a.baseline_search)
+                bwall.append((time.perf_counter() - t) * 1e3)
+                bdev.append(dec.last_ms)
+            blaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
         if a.test_images:
             for _ in range(a.warmup):
                 dec.test_images(pages, *geo)
@@ -248,6 +273,15 @@ def main():
         res.update({"pen_slack": a.pen_slack, "slack_device_ms_per_batch": round(kms, 4), "slack_device_ms_min": round(float(min(kdev)), 4),
                     "slack_whole_device_ms": round(kwms, 4), "slack_over_whole": round(kms / kwms, 3), "slack_launches": klaunches,
                     "slack_wall_ms_per_batch": round(float(np.median(kwall)), 3), "slack_lines_changed": changed, "slack_chars_offset": moved})
+    if a.baseline_search:
+        bms, bpms = float(np.median(bdev)), float(np.median(bpdev))
+        changed = sum(ta != tb for pa, pb in zip(out, bgot[0]) for (_, ta), (_, tb) in zip(pa, pb))
+        moved = sum(q != 0 for pg in bgot[1] for q in pg)
+        res.update({"baseline_search": a.baseline_search, "y_bits": a.y_bits, "base_candidates": 2 * a.baseline_search + 1,
+                    "base_ceiling": 2 * a.baseline_search + 2, "base_device_ms_per_batch": round(bms, 4),
+                    "base_device_ms_min": round(float(min(bdev)), 4), "base_plain_device_ms": round(bpms, 4),
+                    "base_over_plain": round(bms / bpms, 3), "base_launches": blaunches,
+                    "base_wall_ms_per_batch": round(float(np.median(bwall)), 3), "base_lines_changed": changed, "base_lines_offset": moved})
     if a.test_images:
         tms = float(np.median(tdev))
         res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
