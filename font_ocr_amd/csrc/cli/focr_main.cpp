@@ -29,7 +29,12 @@
 //     2^-B px, N <= 32, B <= 3) and the one with the lowest summed footprint term is kept (focr_decoder_set_baseline_search);
 //     stdout stays text only, --verify draws every line moved by the nearest whole row of its offset, and --baselines PATH
 //     writes a CSV row per decoded line: image_index,y,q,offset_px,cost; with --scores, --pen-search or --whole-line it is a
-//     usage error, and so are --y-bits and --baselines without it.
+//     usage error, and so are --y-bits and --baselines without it (or without --whole-baseline);
+//   * --whole-line --whole-baseline N [--y-bits B] is an extension of --whole-line: the whole-line decode under every vertical
+//     offset -N ..= N (in steps of 2^-B px), the candidate whose whole line costs least kept (focr_decoder_set_whole_baseline):
+//     proportional text whose baseline is off the crop grid; stdout stays text only, --verify draws every character at its
+//     pen on a canvas moved by the nearest whole row of the offset, and --baselines PATH writes its CSV; without --whole-line,
+//     or with --margins or --pen-slack, it is a usage error.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -59,7 +64,7 @@ struct Args {
     std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores, margins, baselines;
     bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false, have_margins = false;
     bool have_baselines = false, have_y_bits = false;
-    uint32_t baseline_search = 0, y_bits = 0;
+    uint32_t baseline_search = 0, y_bits = 0, whole_baseline = 0;
     float text_size = 0.f, kerning = 1.f;
     uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0, pen_search = 0, pen_slack = 0;
     bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
@@ -101,6 +106,7 @@ void print_help() {
            "      --margins <MARGINS>              [extension] CSV of every character's pen, term, runner-up and margin (only with the whole-line decode)\n"
            "      --pen-slack <N>                  [extension] Let every step of the whole-line decode move the pen by up to N/64 px, N <= 64 (not with margins or a pen search) [default: 0]\n"
            "      --baseline-search <N>            [extension] Decode every line at the vertical offsets -N ..= N, in steps of 2^-B px (--y-bits), and keep the best, N <= 32 (only with the plain pen loop) [default: 0]\n"
+           "      --whole-baseline <N>             [extension] Run the whole-line decode under the vertical offsets -N ..= N, in steps of 2^-B px, and keep the line that costs least, N <= 32 (only with the whole-line decode; not with margins or a pen slack) [default: 0]\n"
            "      --y-bits <B>                     [extension] Sub-pixel bits of the baseline search's step, B <= 3 [default: 0]\n"
            "      --baselines <BASELINES>          [extension] CSV of every line's chosen vertical offset and cost (only with a baseline search)\n"
            "  -h, --help                           Print help\n"
@@ -175,6 +181,11 @@ Args parse_args(int argc, char **argv) {
             a.baseline_search = num_u(s);
             if (a.baseline_search > FOCR_BASELINE_MAX) usage_error("invalid value '" + s + "' for '--baseline-search': the radius is at most 32");
         }
+        else if (k == "--whole-baseline") {
+            const std::string s = need();
+            a.whole_baseline = num_u(s);
+            if (a.whole_baseline > FOCR_BASELINE_MAX) usage_error("invalid value '" + s + "' for '--whole-baseline': the radius is at most 32");
+        }
         else if (k == "--y-bits") {
             const std::string s = need();
             a.y_bits = num_u(s), a.have_y_bits = true;
@@ -207,8 +218,11 @@ Args parse_args(int argc, char **argv) {
     if (a.baseline_search && a.have_scores) usage_error("the argument '--baseline-search <N>' cannot be used with '--scores <SCORES>'");
     if (a.baseline_search && a.pen_search) usage_error("the argument '--baseline-search <N>' cannot be used with '--pen-search <N>'");
     if (a.baseline_search && a.whole_line) usage_error("the argument '--baseline-search <N>' cannot be used with '--whole-line'");
-    if (a.have_y_bits && !a.baseline_search) usage_error("the argument '--y-bits <B>' cannot be used without '--baseline-search <N>'");
-    if (a.have_baselines && !a.baseline_search) usage_error("the argument '--baselines <BASELINES>' cannot be used without '--baseline-search <N>'");
+    if (a.whole_baseline && !a.whole_line) usage_error("the argument '--whole-baseline <N>' cannot be used without '--whole-line'");
+    if (a.whole_baseline && a.have_margins) usage_error("the argument '--whole-baseline <N>' cannot be used with '--margins <MARGINS>'");
+    if (a.whole_baseline && a.pen_slack) usage_error("the argument '--whole-baseline <N>' cannot be used with '--pen-slack <N>'");
+    if (a.have_y_bits && !a.baseline_search && !a.whole_baseline) usage_error("the argument '--y-bits <B>' cannot be used without '--baseline-search <N>'");
+    if (a.have_baselines && !a.baseline_search && !a.whole_baseline) usage_error("the argument '--baselines <BASELINES>' cannot be used without '--baseline-search <N>'");
     return a;
 }
 
@@ -334,7 +348,7 @@ int main(int argc, char **argv) {
     if (args.img.empty()) return 0;
 
     char err[256] = {0};
-    const bool y_fonts = args.baseline_search && args.y_bits;  // the y-phase fonts; fonts[0] is the plain decode font
+    const bool y_fonts = (args.baseline_search || args.whole_baseline) && args.y_bits;  // the y-phase fonts; fonts[0] is the plain decode font
     std::vector<focr_decode_font_t> fonts((size_t)1 << (y_fonts ? args.y_bits : 0));
     if ((y_fonts ? focr_decode_font_build_y(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), args.y_bits,
                                             fonts.data(), err, sizeof err)
@@ -373,6 +387,8 @@ int main(int argc, char **argv) {
         die(std::string("focr_decoder_set_baseline_fonts: ") + focr_decoder_last_error(dec), 1);
     if (focr_decoder_set_baseline_search(dec, args.baseline_search ? args.y_bits : 0, args.baseline_search) != 0)
         die(std::string("focr_decoder_set_baseline_search: ") + focr_decoder_last_error(dec), 1);
+    if (focr_decoder_set_whole_baseline(dec, args.whole_baseline ? args.y_bits : 0, args.whole_baseline) != 0)
+        die(std::string("focr_decoder_set_whole_baseline: ") + focr_decoder_last_error(dec), 1);
     const bool csv_offsets = csv && args.pen_search > 0;
 
     std::vector<std::vector<Line>> lines(n_img);

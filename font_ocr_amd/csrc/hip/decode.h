@@ -1,5 +1,5 @@
 // decode.h — what the files of the `focr` decoder share (decode.hip: font and line decoder; decode_whole.hip: its whole-line
-// decode, and decode_baseline.hip: its baseline search, with decode_line.h between the three; decode_images.hip: the verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels (ncc_images.hip
+// decode, decode_baseline.hip: its baseline search, and decode_whole_baseline.hip: the two together, with decode_line.h between the four; decode_images.hip: the verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels (ncc_images.hip
 // is its third user), the blank test's crop, the decoder itself, and the host plumbing every entry point repeats (errors, stages, staging, refusals).
 #pragma once
 
@@ -226,6 +226,10 @@ struct focr_decoder {
     focr::DevArray<uint8_t> d_ybitmaps;
     focr::DevArray<int32_t> d_base_q;
     focr::DevArray<int64_t> d_base_cost;
+    // baseline candidates of a whole-line run (focr_decoder_set_whole_baseline): the programme under every candidate reads
+    // the same y-phase tables and writes the line's q to d_base_q; its cost is the whole-line run's d_cost
+    uint32_t wbase_bits = 0, wbase_n = 0;
+    uint64_t yterm_bound = 0;      // the largest stride * box_h * 2 * 255^2 of the uploaded y-phase fonts v >= 1 (a term's bound)
     // results of the last run
     bool have_baselines = false;   // the last successful run searched baselines
     std::vector<int8_t> base_q;    // beside lines

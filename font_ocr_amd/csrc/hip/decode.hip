@@ -14,6 +14,8 @@
 //      dynamic programme over pens in 1/64 px, with margins or with a pen slack when those are on.
 //      With a baseline search radius (focr_decoder_set_baseline_search) decode_baseline.hip's line_baseline_kernel takes its
 //      place: the pen loop under every vertical candidate, and the candidate with the lowest summed footprint term.
+//      With the whole-line decode on and a radius of its own (focr_decoder_set_whole_baseline)
+//      decode_whole_baseline.hip's line_whole_baseline_kernel takes its place: the programme under every candidate.
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
@@ -330,8 +332,8 @@ namespace {
 void remember_run(focr_decoder *dec, const Geometry &g, const uint8_t *d_src, size_t n_pages, uint32_t x_start, bool searched, bool whole) {
     dec->run_searched = searched;
     dec->run_whole = dec->have_whole = whole;
-    dec->run_base = dec->base_n != 0;  // (a run that got here with a radius searched baselines)
-    dec->run_bits = dec->base_bits;
+    dec->run_base = dec->base_n != 0 || dec->wbase_n != 0;  // (a run that got here with a radius searched baselines)
+    dec->run_bits = dec->wbase_n ? dec->wbase_bits : dec->base_bits;  // (never both: a baseline search refuses the whole-line decode)
     dec->run_g = g;
     dec->run_pages = n_pages;
     dec->run_x_start = x_start;
@@ -402,6 +404,7 @@ extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font
     dec->n_glyphs = 0;
     dec->d_inc64.release();  // the previous font's; a whole-line run uploads its own
     dec->font_bits = dec->ybitmaps_dw = 0;
+    dec->yterm_bound = 0;
     dec->d_yglyphs.release();
     dec->d_yoffs.release();
     dec->d_ybitmaps.release();
@@ -463,6 +466,8 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     if (n_pages && !pages) return dfail(dec, "focr_decoder_run: null pages");
     const bool baseline = dec->base_n != 0;
     if (baseline && baseline_plan(dec)) return 1;  // the refusals of include/focr_decode.h, before anything is launched
+    const bool candidates = dec->wbase_n != 0;     // a whole-line run under every baseline candidate
+    if (candidates && whole_baseline_plan(dec)) return 1;
     if (dec->margins_on && !dec->whole_on)
         return dfail(dec, "focr_decoder_run: margins on with the whole-line decode off (focr_decoder_set_whole_margins needs focr_decoder_set_whole_line)");
     const uint32_t slack = dec->whole_slack;
@@ -488,7 +493,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
         dec->have_scores = scores;
         dec->have_margins = margins;
-        dec->have_baselines = baseline;
+        dec->have_baselines = baseline || candidates;
         return 0;
     }
     g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;
@@ -564,6 +569,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         return 1;
     if (offsets && read_back(dec, pen, dec->d_pen.p, n_all)) return 1;
     if (baseline && (read_back(dec, bq, dec->d_base_q.p, total) || read_back(dec, bcost, dec->d_base_cost.p, total))) return 1;
+    if (candidates && read_back(dec, bq, dec->d_base_q.p, total)) return 1;  // the cost is the whole-line run's
     if (whole && (read_back(dec, wpens, dec->d_pens.p, n_all) || read_back(dec, wcost, dec->d_cost.p, total))) return 1;
     if (margins && (read_back(dec, mterm, dec->d_mterm.p, n_all) || read_back(dec, mrunner, dec->d_mrunner.p, n_all) || read_back(dec, mmargin, dec->d_margin.p, n_all)))
         return 1;
@@ -586,10 +592,10 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         l.pad = 0;
         append_line(dec->chars, all, k, g.cap, n);
         if (offsets) append_line(dec->offsets, pen, k, g.cap, n);
-        if (baseline) {
+        if (baseline || candidates) {
             if (bq[k] < -(int)FOCR_BASELINE_MAX || bq[k] > (int)FOCR_BASELINE_MAX) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
             dec->base_q.push_back((int8_t)bq[k]);
-            dec->base_cost.push_back(bcost[k]);
+            dec->base_cost.push_back(baseline ? bcost[k] : wcost[k]);
         }
         if (whole) {
             append_line(dec->pens, wpens, k, g.cap, n);
@@ -609,7 +615,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
     dec->have_scores = scores;
     dec->have_margins = margins;
-    dec->have_baselines = baseline;
+    dec->have_baselines = baseline || candidates;
     return 0;
 }
 

@@ -277,6 +277,7 @@ void drop_fonts(focr_decoder *dec) {
     dec->have_base_fonts = false;
     dec->font_bits = 0;
     dec->ybitmaps_dw = 0;
+    dec->yterm_bound = 0;
     dec->d_yglyphs.release();
     dec->d_yoffs.release();
     dec->d_ybitmaps.release();
@@ -296,7 +297,7 @@ extern "C" int focr_decoder_set_baseline_fonts(focr_decoder_t *dec, const focr_d
     const size_t G = dec->n_glyphs, V = (size_t)1 << y_bits;
     std::vector<DevGlyph> gl((V - 1) * G);
     std::vector<int2> offs((V - 1) * G * FOCR_DECODE_PHASES);
-    uint64_t total = 0;
+    uint64_t total = 0, bound = 0;
     for (size_t v = 0; v < V; v++) {
         const focr_decode_font_t &f = fonts[v];
         if (!f.glyphs || f.n_glyphs != G || f.bitmaps_len % 4 || (f.bitmaps_len && !f.bitmaps))
@@ -317,6 +318,7 @@ extern "C" int focr_decoder_set_baseline_fonts(focr_decoder_t *dec, const focr_d
                     return dfail(dec, std::string(who) + "fonts[0] is not the decode font (glyph table)");
                 continue;
             }
+            bound = std::max<uint64_t>(bound, (uint64_t)s.stride * s.box_h * 2 * 255 * 255);
             gl[(v - 1) * G + i] = DevGlyph{(uint32_t)((total + s.offset) / 4), s.stride / 4, s.box_h, s.increment};
             for (int p = 0; p < FOCR_DECODE_PHASES; p++) offs[((v - 1) * G + i) * FOCR_DECODE_PHASES + p] = make_int2(s.off_x[p], s.off_y[p]);
         }
@@ -342,6 +344,7 @@ extern "C" int focr_decoder_set_baseline_fonts(focr_decoder_t *dec, const focr_d
     dec->have_base_fonts = true;
     dec->font_bits = y_bits;
     dec->ybitmaps_dw = (uint32_t)(total / 4);
+    dec->yterm_bound = bound;
     return 0;
 }
 
@@ -357,7 +360,7 @@ extern "C" int focr_decoder_set_baseline_search(focr_decoder_t *dec, uint32_t y_
 extern "C" int focr_decoder_get_baselines(const focr_decoder_t *dec, int8_t *q, int64_t *cost) {
     if (!dec) return dfail(nullptr, "focr_decoder_get_baselines: null decoder");
     if (!dec->have_baselines)
-        return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_baselines: the last successful run did not search baselines (focr_decoder_set_baseline_search)");
+        return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_baselines: the last successful run did not search baselines (focr_decoder_set_baseline_search, or focr_decoder_set_whole_baseline beside the whole-line decode)");
     if (q && !dec->base_q.empty()) memcpy(q, dec->base_q.data(), dec->base_q.size());
     if (cost && !dec->base_cost.empty()) memcpy(cost, dec->base_cost.data(), dec->base_cost.size() * sizeof(int64_t));
     return 0;

@@ -1,6 +1,6 @@
 // decode_line.h — what the translation units of the `focr` line decoder share (decode.hip: prepass, compaction, the pen
 // loop and its search, and the run itself; decode_whole.hip: the whole-line decode; decode_baseline.hip: the baseline
-// search): the strip's constants, the device helpers the files' kernels call (no relocatable device code: they are inlined
+// search; decode_whole_baseline.hip: the whole-line decode under every baseline candidate): the strip's constants, the device helpers the files' kernels call (no relocatable device code: they are inlined
 // into each), the whole-line decode's plan, which focr_decoder_run asks for and hands back, and the baseline search's
 // three steps of a run.
 #pragma once
@@ -73,6 +73,13 @@ int whole_plan(focr_decoder *dec, const Geometry &g, WholePlan *plan);
 int whole_reserve(focr_decoder *dec, const Geometry &g, const WholePlan &plan);
 // The third launch of a whole-line run, on the decoder's stream; the caller checks hipGetLastError.
 void whole_launch(focr_decoder *dec, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
+
+// ---- a whole-line run under every baseline candidate (decode_whole_baseline.hip) -------------------------------------
+
+// The refusals of focr_decoder_set_whole_baseline with a radius (include/focr_decode.h), before anything is launched.
+int whole_baseline_plan(focr_decoder *dec);
+// whole_launch with a radius: line_whole_baseline_kernel in line_whole_kernel's place.
+void whole_baseline_launch(focr_decoder *dec, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
 
 // ---- the baseline search as focr_decoder_run sees it (decode_baseline.hip) -------------------------------------------
 

@@ -23,6 +23,9 @@
         pages, baselines, costs = dec.decode(luma_pages, 45, 39, 608, 12, 15, baseline_search=8)
         # every line decoded at the vertical offsets -8 ..= 8 quarter pixels and the one with the lowest summed footprint
         # term kept; baselines[page][line]: its q (the line sits q / 4 px below the crop's baseline), costs[page][line]: its sum
+        pages, pens, costs, baselines = dec.decode(luma_pages, 45, 39, 608, 12, 15, whole_line=True, whole_baseline=2)
+        # the whole-line decode under every vertical offset -2 ..= 2 quarter pixels, the candidate whose whole line costs
+        # least kept: proportional text whose baseline is off the crop grid; baselines[page][line]: its q
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -221,6 +224,7 @@ class LineDecoder:
         self._margins = False  # the library's switch (focr_decoder_set_whole_margins)
         self._pen_slack = 0  # the library's radius (focr_decoder_set_whole_slack)
         self._baseline = (0, 0)  # the library's y_bits and radius (focr_decoder_set_baseline_search)
+        self._whole_baseline = (0, 0)  # the library's y_bits and radius (focr_decoder_set_whole_baseline)
 
     def _check(self, rc):
         if rc != 0:
@@ -228,7 +232,8 @@ class LineDecoder:
 
     def set_font(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0, y_bits=0):
         """Build (or take, when font_path is a DecodeFont) and upload the decode font.  y_bits > 0 also builds and uploads
-        its 1 << y_bits y-phase tables, for decode(baseline_search=N) in steps of 2^-y_bits px; a DecodeFont brings its own."""
+        its 1 << y_bits y-phase tables, for decode(baseline_search=N) and decode(whole_line=True, whole_baseline=N) in steps
+        of 2^-y_bits px; a DecodeFont brings its own."""
         font = font_path if isinstance(font_path, DecodeFont) else DecodeFont(font_path, text_size, alphabet, hinting, kerning, y_bits)
         self._vfont, self._batch = None, None  # the library drops its verify table, its y-phase fonts and its last run here too
         self._check(self._lib.focr_decoder_set_font(self._h, C.byref(font.s)))
@@ -338,17 +343,21 @@ class LineDecoder:
         return mse, imgs
 
     def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0, whole_line=False,
-             margins=False, pen_slack=0, baseline_search=0):
+             margins=False, pen_slack=0, baseline_search=0, whole_baseline=0):
         """[[(y, text), ...] per page] of one batch; with scores [[LineScores, ...] per page] beside it (else None); with
         a pen search [[int8 offsets, ...] per page] (else None); with whole_line ([[uint32 pens, ...] per page],
         [[cost, ...] per page]) (else None), and with margins [[LineMargins, ...] per page], or with a pen slack
-        [[int8 offsets, ...] per page], as a third element of that; with a baseline search ([[q, ...] per page],
+        [[int8 offsets, ...] per page], or with whole_baseline [[q, ...] per page], as a third element of that; with a baseline search ([[q, ...] per page],
         [[cost, ...] per page]) (else None)."""
         self._batch = None
         baseline = (self.font.y_bits if baseline_search else 0, int(baseline_search))
         if baseline != self._baseline:
             self._check(self._lib.focr_decoder_set_baseline_search(self._h, *baseline))
             self._baseline = baseline
+        whole_base = (self.font.y_bits if whole_baseline else 0, int(whole_baseline))
+        if whole_base != self._whole_baseline:
+            self._check(self._lib.focr_decoder_set_whole_baseline(self._h, *whole_base))
+            self._whole_baseline = whole_base
         if int(pen_slack) != self._pen_slack:
             self._check(self._lib.focr_decoder_set_whole_slack(self._h, int(pen_slack)))
             self._pen_slack = int(pen_slack)
@@ -385,13 +394,13 @@ class LineDecoder:
         if margins:
             ms = np.zeros(max(1, nc), dtype=np.dtype([("term", "<i4"), ("runner", "<u2"), ("pad", "<u2"), ("margin", "<i8")]))
             self._check(self._lib.focr_decoder_get_margins(self._h, ms.ctypes.data))
-        if baseline_search:
+        if baseline_search or whole_baseline:
             bq = np.zeros(max(1, nl), dtype=np.int8)
             bc = np.zeros(max(1, nl), dtype=np.int64)
             self._check(self._lib.focr_decoder_get_baselines(self._h, bq.ctypes.data, bc.ctypes.data))
         found = ([[] for _ in range(n)], [[] for _ in range(n)]) if baseline_search else None
         alpha = self.font.alphabet
-        whole = ([[] for _ in range(n)], [[] for _ in range(n)]) + (([[] for _ in range(n)],) if margins or pen_slack else ()) if whole_line else None
+        whole = ([[] for _ in range(n)], [[] for _ in range(n)]) + (([[] for _ in range(n)],) if margins or pen_slack or whole_baseline else ()) if whole_line else None
         out = [[] for _ in range(n)]
         sc = [[] for _ in range(n)] if scores else None
         offs = [[] for _ in range(n)] if pen_search else None
@@ -409,6 +418,8 @@ class LineDecoder:
                 whole[1][ln.page].append(int(lc[k]))
             if pen_slack:
                 whole[2][ln.page].append(js[ln.first: ln.first + ln.n_chars].copy())
+            if whole_baseline:
+                whole[2][ln.page].append(int(bq[k]))
             if margins:
                 m = ms[ln.first: ln.first + ln.n_chars]
                 runner = "".join(LineMargins.NO_RUNNER if i == 0xFFFF else alpha[i] for i in m["runner"])
@@ -459,8 +470,20 @@ class LineDecoder:
                 raise ValueError(f"baseline_search does not go with {what} (the baseline search runs the plain pen loop per candidate)")
         return n
 
+    @staticmethod
+    def _check_whole_baseline(whole_baseline, whole_line, margins, pen_slack):
+        n = int(whole_baseline)
+        if not 0 <= n <= 32:
+            raise ValueError(f"whole_baseline must be 0 .. 32 (steps of 2^-y_bits px), not {whole_baseline!r}")
+        if n and not whole_line:
+            raise ValueError("whole_baseline needs whole_line=True (the pen loop's search is baseline_search)")
+        for on, what in ((margins, "margins=True"), (pen_slack, "pen_slack")):
+            if n and on:
+                raise ValueError(f"whole_baseline does not go with {what} (neither has a definition across candidates yet)")
+        return n
+
     def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, pen_slack=0,
-               baseline_search=0, margins=False, whole_line=False):
+               baseline_search=0, whole_baseline=0, margins=False, whole_line=False):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
         Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
         mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
@@ -486,7 +509,13 @@ class LineDecoder:
         with the lowest summed footprint term is the line (on a tie the offset nearest 0).  The result gains two last
         elements: baselines[page][line], the chosen q (int), and costs[page][line], its sum of footprint terms (int).  The
         verify then draws each line moved by the nearest whole row of its offset.  It goes with none of scores, pen_search,
-        whole_line, margins and pen_slack (ValueError)."""
+        whole_line, margins and pen_slack (ValueError).
+        With whole_line=True and whole_baseline=N > 0 (up to 32) every line is decoded by the whole-line programme at the
+        vertical offsets q in -N ..= N, in steps of 2^-y_bits px of the font's y_bits, and the candidate whose whole line
+        costs least is the line (on a tie the offset nearest 0): proportional text whose baseline is off the crop grid.
+        The result gains one last element after costs: baselines[page][line], the chosen q (int); pens and costs are that
+        candidate's.  The verify renders every character at its pen on a canvas moved by the nearest whole row of the
+        offset.  It needs whole_line=True and goes with neither margins nor pen_slack (ValueError)."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
@@ -495,6 +524,7 @@ class LineDecoder:
         margins = self._check_margins(margins, whole_line)
         pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
         baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
+        whole_baseline = self._check_whole_baseline(whole_baseline, whole_line, margins, pen_slack)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
@@ -504,6 +534,7 @@ class LineDecoder:
         sc = [None] * len(pages)
         offs = [None] * len(pages)
         wpens, wcosts, wmargins, woffs = [None] * len(pages), [None] * len(pages), [None] * len(pages), [None] * len(pages)
+        wqs = [None] * len(pages)
         bqs, bcosts = [None] * len(pages), [None] * len(pages)
         mse = np.zeros(len(pages), dtype=np.float32)
         images = [None] * len(pages) if verify == "image" else None
@@ -514,7 +545,8 @@ class LineDecoder:
             batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
             res, res_sc, res_offs, res_whole, res_base = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
                                                                    pen_search=pen_search, whole_line=whole_line, margins=margins,
-                                                                   pen_slack=pen_slack, baseline_search=baseline_search)
+                                                                   pen_slack=pen_slack, baseline_search=baseline_search,
+                                                                   whole_baseline=whole_baseline)
             for j, i in enumerate(idx):
                 out[i] = res[j]
                 if baseline_search:
@@ -525,6 +557,8 @@ class LineDecoder:
                     wmargins[i] = res_whole[2][j]
                 if pen_slack:
                     woffs[i] = res_whole[2][j]
+                if whole_baseline:
+                    wqs[i] = res_whole[2][j]
                 if pen_search:
                     offs[i] = res_offs[j]
                 if scores:
@@ -546,12 +580,14 @@ class LineDecoder:
             res += (wmargins,)
         if pen_slack:
             res += (woffs,)
+        if whole_baseline:
+            res += (wqs,)
         if baseline_search:
             res += (bqs, bcosts)
         return res if len(res) > 1 else out
 
     def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False,
-                      pen_search=0, pen_slack=0, baseline_search=0, margins=False, whole_line=False):
+                      pen_search=0, pen_slack=0, baseline_search=0, whole_baseline=0, margins=False, whole_line=False):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
         if self.font is None:
@@ -562,9 +598,11 @@ class LineDecoder:
         margins = self._check_margins(margins, whole_line)
         pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
         baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
+        whole_baseline = self._check_whole_baseline(whole_baseline, whole_line, margins, pen_slack)
         out, sc, offs, whole, base = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
                                                int(line_height), int(line_advance), scores=scores, pen_search=pen_search,
-                                               whole_line=whole_line, margins=margins, pen_slack=pen_slack, baseline_search=baseline_search)
+                                               whole_line=whole_line, margins=margins, pen_slack=pen_slack, baseline_search=baseline_search,
+                                               whole_baseline=whole_baseline)
         res = (out,)
         if verify:
             mse, imgs = self._verified(verify, int(page_h), int(page_w))

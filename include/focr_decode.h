@@ -350,11 +350,51 @@ int focr_decoder_set_baseline_fonts(focr_decoder_t *dec, const focr_decode_font_
  * y_bits above FOCR_BASELINE_Y_BITS_MAX and n above FOCR_BASELINE_MAX are refused here. */
 int focr_decoder_set_baseline_search(focr_decoder_t *dec, uint32_t y_bits, uint32_t n);
 /* The chosen q and cost of every line of the last run, in the order of focr_decoder_get: q[n_lines], cost[n_lines].
- * Either may be NULL.  Fails with a message unless the last successful run searched (n > 0). */
+ * Either may be NULL.  Fails with a message unless the last successful run searched (n > 0), as a baseline search or as
+ * a whole-line run under baseline candidates (focr_decoder_set_whole_baseline). */
 int focr_decoder_get_baselines(const focr_decoder_t *dec, int8_t *q, int64_t *cost);
 /* Debug: at most `grid` workgroups for later baseline runs (0: one per line slot), so that a test can make one workgroup
  * take several lines. */
 int focr_decoder_debug_set_baseline_grid(focr_decoder_t *dec, uint32_t grid);
+
+/* ---- device: baseline candidates of a whole-line run (the two extensions together) ---------------------------------- */
+
+/* The baseline search runs the greedy pen loop under every candidate, so it finds the offset of a proportional line and
+ * still loses its text, and on such lines the loop's own cost often picks a wrong offset as well; the whole-line decode
+ * reads proportional text but renders at the crop's top plus origin_y only.  With y_bits B and a radius N (the baseline
+ * search's limits) a whole-line run decodes every line by the dynamic programme once per vertical candidate and keeps the
+ * candidate whose whole line costs least.  Candidates, y-phases, the row shift d, the four-sided clipping, dropped
+ * candidates and rank are the baseline search's; states, inc64, cost, the end state and the read-back are the whole-line
+ * decode's:
+ *   - candidate q in -N ..= N renders every glyph at ty_q = origin_y + q * 2^-B: y-phase v = q & (2^B - 1) of the fonts
+ *     of focr_decoder_set_baseline_fonts, every glyph moved down by d = q >> B rows (floor), bitmaps clipped to the crop
+ *     on all four sides;
+ *   - a candidate with ty_q < 0 is dropped (q = 0 never is);
+ *   - term_q(i, s) is the int32 footprint term of glyph i of y-phase v at state s under that move; inc64 is the same for
+ *     every candidate (the fonts share increments bitwise);
+ *   - under candidate q the line is decoded by the whole-line programme exactly as defined above, with term_q in term's
+ *     place; cost_q is its end state's cost;
+ *   - the line is the candidate with the lowest (cost_q, rank(q)), rank 0, -1, +1, -2, ...: on a tie the offset nearest 0
+ *     wins.
+ * A run returns that candidate's text, pens and cost: focr_decoder_get_pens returns the pens and the line's cost, and
+ * focr_decoder_get_baselines its q and the same cost.  N = 0 is the plain whole-line run: the same text, pens, costs and
+ * launches (and focr_decoder_get_baselines fails after it).  With N > 0 prepass and compaction are unchanged and the
+ * launch count stays 3.  focr_decoder_run refuses N > 0, before anything is launched and each with its own message that
+ * names the setters involved:
+ *   - with the whole-line decode off;
+ *   - with margins on;
+ *   - with a pen slack;
+ *   - with B > 0 unless y-phase fonts of that B are uploaded (focr_decoder_set_baseline_fonts);
+ *   - with an origin_y that is not a whole number >= 0;
+ * and whatever a whole-line run refuses anyway; focr_decoder_set_baseline_search with n > 0 stays refused beside the
+ * whole-line decode.  The whole-line bound ceil(64 * width / min inc64) * T < 2^47 takes T over the glyph boxes of every
+ * uploaded y-phase as well, because box sizes differ between v.  focr_decoder_verify then combines its two rules: every
+ * character at pos = s / 64 of its returned pen, the line's canvas moved by (q + (1 << B >> 1)) >> B rows and clipped at
+ * the page's top and bottom.  What it does not cure: a leading that drifts past the radius, and lines that are off the
+ * 1/64 px grid in x as well (those need the pen slack under every candidate, a later step). */
+/* Set y_bits and the radius of later whole-line runs (0, 0 when the decoder is created; a state of the decoder, not of
+ * the font).  y_bits above FOCR_BASELINE_Y_BITS_MAX and n above FOCR_BASELINE_MAX are refused here. */
+int focr_decoder_set_whole_baseline(focr_decoder_t *dec, uint32_t y_bits, uint32_t n);
 
 /* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
 
@@ -373,7 +413,9 @@ int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_verify_font_t *
  * pos = s / 64 of its returned pen s (with pen slack that is the render pen), so the image shows the line where it was decoded.
  * After a run with a baseline search every line's canvas is drawn moved by the nearest whole row of its offset,
  * (q + (1 << B >> 1)) >> B rows down (up when negative), and clipped at the page's top as well as its bottom; the
- * sub-pixel part of the offset is not drawn (the verify table has one vertical phase).  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
+ * sub-pixel part of the offset is not drawn (the verify table has one vertical phase).  After a whole-line run under
+ * baseline candidates (focr_decoder_set_whole_baseline) both rules hold: every character at pos = s / 64 of its returned
+ * pen, on a canvas moved and clipped in that way.  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
  * without a successful run since the last set_font, or without a verify table. */
 int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums);
 /* Device time of the last verify's kernels in ms (events), and their launch count (constant per batch). */

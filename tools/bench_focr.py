@@ -55,6 +55,15 @@ With --baseline-search N [--y-bits B], also the decode with a baseline search of
   base_wall_ms_per_batch      median host time of one decode(baseline_search=N) call, offsets and costs read back
   base_lines_changed          lines of the batch the search decodes differently from the plain run
   base_lines_offset           lines of the batch that took an offset other than 0
+With --whole-line --whole-baseline N [--y-bits B], also the whole-line decode under the 2 N + 1 baseline candidates
+(LineDecoder.decode(whole_line=True, whole_baseline=N)), in runs that alternate with whole-line runs without it:
+  wbase_device_ms_per_batch   median device time of the batch's kernels with the candidates on (the same 3 launches)
+  wbase_whole_device_ms       median device time of the whole-line runs in between
+  wbase_over_whole            the ratio of the two, beside wbase_candidates = wbase_ceiling = 2 N + 1: one whole-line run
+                              per candidate (the winner is not decoded again)
+  wbase_wall_ms_per_batch     median host time of one such decode call, pens, costs and offsets read back
+  wbase_lines_changed         lines of the batch the mode decodes differently from the whole-line run
+  wbase_lines_offset          lines of the batch that took an offset other than 0
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -110,15 +119,19 @@ def main():
     ap.add_argument("--margins", action="store_true", help="with --whole-line: also time the whole-line decode with margins")
     ap.add_argument("--pen-slack", type=int, default=0, metavar="N", help="with --whole-line: also time the whole-line decode with a pen slack of N/64 px")
     ap.add_argument("--baseline-search", type=int, default=0, metavar="N", help="also time the decode with a baseline search of N steps either way")
-    ap.add_argument("--y-bits", type=int, default=0, metavar="B", help="with --baseline-search: steps of 2^-B px")
+    ap.add_argument("--whole-baseline", type=int, default=0, metavar="N",
+                    help="with --whole-line: also time the whole-line decode under the baseline candidates of N steps either way")
+    ap.add_argument("--y-bits", type=int, default=0, metavar="B", help="with --baseline-search or --whole-baseline: steps of 2^-B px")
     ap.add_argument("--font", default=FONT, metavar="PATH", help="the font of the pages and of the decoder [DejaVu Sans Mono]")
     a = ap.parse_args()
     if a.margins and not a.whole_line:
         ap.error("--margins needs --whole-line")
     if a.pen_slack and not a.whole_line:
         ap.error("--pen-slack needs --whole-line")
-    if a.y_bits and not a.baseline_search:
-        ap.error("--y-bits needs --baseline-search")
+    if a.whole_baseline and not a.whole_line:
+        ap.error("--whole-baseline needs --whole-line")
+    if a.y_bits and not (a.baseline_search or a.whole_baseline):
+        ap.error("--y-bits needs --baseline-search or --whole-baseline")
     pages = synth(a.pages, a.seed, font=a.font)
     geo = (45, 39, 608, 12, 15)
     t0 = time.perf_counter()
@@ -219,6 +232,18 @@ def main():
                 bwall.append((time.perf_counter() - t) * 1e3)
                 bdev.append(dec.last_ms)
             blaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+        if a.whole_baseline:
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, whole_line=True, whole_baseline=a.whole_baseline)
+            cdev, cwall, cwdev = [], [], []
+            for _ in range(a.steps):
+                cref = dec.decode(pages, *geo, whole_line=True)
+                cwdev.append(dec.last_ms)
+                t = time.perf_counter()
+                cgot = dec.decode(pages, *geo, whole_line=True, whole_baseline=a.whole_baseline)
+                cwall.append((time.perf_counter() - t) * 1e3)
+                cdev.append(dec.last_ms)
+            claunches = int(dec._lib.focr_decoder_last_launches(dec._h))
         if a.test_images:
             for _ in range(a.warmup):
                 dec.test_images(pages, *geo)
@@ -282,6 +307,15 @@ def main():
                     "base_device_ms_min": round(float(min(bdev)), 4), "base_plain_device_ms": round(bpms, 4),
                     "base_over_plain": round(bms / bpms, 3), "base_launches": blaunches,
                     "base_wall_ms_per_batch": round(float(np.median(bwall)), 3), "base_lines_changed": changed, "base_lines_offset": moved})
+    if a.whole_baseline:
+        cms, cwms = float(np.median(cdev)), float(np.median(cwdev))
+        changed = sum(ta != tb for pa, pb in zip(cref[0], cgot[0]) for (_, ta), (_, tb) in zip(pa, pb))
+        moved = sum(q != 0 for pg in cgot[3] for q in pg)
+        res.update({"whole_baseline": a.whole_baseline, "y_bits": a.y_bits, "wbase_candidates": 2 * a.whole_baseline + 1,
+                    "wbase_ceiling": 2 * a.whole_baseline + 1, "wbase_device_ms_per_batch": round(cms, 4),
+                    "wbase_device_ms_min": round(float(min(cdev)), 4), "wbase_whole_device_ms": round(cwms, 4),
+                    "wbase_over_whole": round(cms / cwms, 3), "wbase_launches": claunches,
+                    "wbase_wall_ms_per_batch": round(float(np.median(cwall)), 3), "wbase_lines_changed": changed, "wbase_lines_offset": moved})
     if a.test_images:
         tms = float(np.median(tdev))
         res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
