@@ -34,7 +34,12 @@
 //     offset -N ..= N (in steps of 2^-B px), the candidate whose whole line costs least kept (focr_decoder_set_whole_baseline):
 //     proportional text whose baseline is off the crop grid; stdout stays text only, --verify draws every character at its
 //     pen on a canvas moved by the nearest whole row of the offset, and --baselines PATH writes its CSV; without --whole-line,
-//     or with --margins or --pen-slack, it is a usage error.
+//     or with --margins or --pen-slack, it is a usage error;
+//   * --y-frac N --line-advance-frac N (each in 1/64 px, N <= 63) are an extension of those two: the sub-pixel parts of --y
+//     and --line-advance (focr_decoder_set_line_frac), for a leading that is not a whole number of pixels; every line is
+//     cropped at the whole row of its own top and searched around its own sub-pixel part; stdout, --verify and --baselines
+//     keep their formats (y is the line's crop row, q the absolute offset); without --baseline-search or --whole-baseline,
+//     or with --test, they are usage errors.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -65,6 +70,8 @@ struct Args {
     bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false, have_margins = false;
     bool have_baselines = false, have_y_bits = false;
     uint32_t baseline_search = 0, y_bits = 0, whole_baseline = 0;
+    uint32_t y_frac = 0, line_advance_frac = 0;
+    bool have_y_frac = false, have_line_advance_frac = false;
     float text_size = 0.f, kerning = 1.f;
     uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0, pen_search = 0, pen_slack = 0;
     bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
@@ -109,6 +116,8 @@ void print_help() {
            "      --whole-baseline <N>             [extension] Run the whole-line decode under the vertical offsets -N ..= N, in steps of 2^-B px, and keep the line that costs least, N <= 32 (only with the whole-line decode; not with margins or a pen slack) [default: 0]\n"
            "      --y-bits <B>                     [extension] Sub-pixel bits of the baseline search's step, B <= 3 [default: 0]\n"
            "      --baselines <BASELINES>          [extension] CSV of every line's chosen vertical offset and cost (only with a baseline search)\n"
+           "      --y-frac <N>                     [extension] Sub-pixel part of --y in 1/64 px, N <= 63 (only with a baseline search or --whole-baseline) [default: 0]\n"
+           "      --line-advance-frac <N>          [extension] Sub-pixel part of --line-advance in 1/64 px, N <= 63 (only with a baseline search or --whole-baseline) [default: 0]\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -191,6 +200,16 @@ Args parse_args(int argc, char **argv) {
             a.y_bits = num_u(s), a.have_y_bits = true;
             if (a.y_bits > FOCR_BASELINE_Y_BITS_MAX) usage_error("invalid value '" + s + "' for '--y-bits': at most 3");
         }
+        else if (k == "--y-frac") {
+            const std::string s = need();
+            a.y_frac = num_u(s), a.have_y_frac = true;
+            if (a.y_frac > 63) usage_error("invalid value '" + s + "' for '--y-frac': at most 63");
+        }
+        else if (k == "--line-advance-frac") {
+            const std::string s = need();
+            a.line_advance_frac = num_u(s), a.have_line_advance_frac = true;
+            if (a.line_advance_frac > 63) usage_error("invalid value '" + s + "' for '--line-advance-frac': at most 63");
+        }
         else if (k == "--baselines") a.baselines = need(), a.have_baselines = true;
         else if (k == "--whole-line") a.whole_line = true;
         else if (k == "--margins") a.margins = need(), a.have_margins = true;
@@ -223,6 +242,11 @@ Args parse_args(int argc, char **argv) {
     if (a.whole_baseline && a.pen_slack) usage_error("the argument '--whole-baseline <N>' cannot be used with '--pen-slack <N>'");
     if (a.have_y_bits && !a.baseline_search && !a.whole_baseline) usage_error("the argument '--y-bits <B>' cannot be used without '--baseline-search <N>'");
     if (a.have_baselines && !a.baseline_search && !a.whole_baseline) usage_error("the argument '--baselines <BASELINES>' cannot be used without '--baseline-search <N>'");
+    for (const auto &[have, name] : {std::pair<bool, const char *>{a.have_y_frac, "--y-frac <N>"}, {a.have_line_advance_frac, "--line-advance-frac <N>"}}) {
+        if (have && !a.baseline_search && !a.whole_baseline)
+            usage_error(std::string("the argument '") + name + "' cannot be used without '--baseline-search <N>' or '--whole-baseline <N>'");
+        if (have && a.have_test) usage_error(std::string("the argument '") + name + "' cannot be used with '--test <TEST>'");
+    }
     return a;
 }
 
@@ -389,6 +413,8 @@ int main(int argc, char **argv) {
         die(std::string("focr_decoder_set_baseline_search: ") + focr_decoder_last_error(dec), 1);
     if (focr_decoder_set_whole_baseline(dec, args.whole_baseline ? args.y_bits : 0, args.whole_baseline) != 0)
         die(std::string("focr_decoder_set_whole_baseline: ") + focr_decoder_last_error(dec), 1);
+    if (focr_decoder_set_line_frac(dec, args.y_frac, args.line_advance_frac) != 0)
+        die(std::string("focr_decoder_set_line_frac: ") + focr_decoder_last_error(dec), 1);
     const bool csv_offsets = csv && args.pen_search > 0;
 
     std::vector<std::vector<Line>> lines(n_img);

@@ -1,5 +1,5 @@
 // decode.h — what the files of the `focr` decoder share (decode.hip: font and line decoder; decode_whole.hip: its whole-line
-// decode, decode_baseline.hip: its baseline search, and decode_whole_baseline.hip: the two together, with decode_line.h between the four; decode_images.hip: the verify and --test images): the batch geometry, the device tables, the tile frame of the compose kernels (ncc_images.hip
+// decode, decode_baseline.hip: its baseline search, and decode_whole_baseline.hip: the two together, with decode_line.h between the four; decode_images.hip: the verify and --test images; decode_line_frac.hip: the fractional line grid's setter and compose kernel): the batch geometry, both line grids, the device tables, the tile frame of the compose kernels (ncc_images.hip
 // is its third user), the blank test's crop, the decoder itself, and the host plumbing every entry point repeats (errors, stages, staging, refusals).
 #pragma once
 
@@ -43,6 +43,51 @@ __device__ __forceinline__ const uint8_t *slot_crop(const uint8_t *__restrict__ 
     slot_rows(g, slot % g.n_slots, &yc, h);
     return pages + (size_t)(slot / g.n_slots) * g.page_w * g.page_h + (size_t)yc * g.page_w + g.x;
 }
+
+// ---- the fractional line grid (focr_decoder_set_line_frac; include/focr_decode.h): slot i's top is at
+// Y_i = 64 * y_start + y_frac + i * (64 * line_advance + advance_frac) in 1/64 px.  The kernels that read it are kernels of
+// their own (*_frac_kernel) beside the ones they restate, which keep their arguments and instruction streams
+// (tools/isa_hash.py).  The device helpers both forms share (the prepass of a slot, whole_stage, layout_line) take the grid as
+// a policy: PixelGrid is the whole-pixel grid of slot_rows, an empty type; FracGrid the fractional one ----
+
+struct LineFrac {
+    uint32_t y_frac, advance_frac;  // each 0 ..= 63; (0, 0) is off
+    __host__ __device__ bool on() const { return (y_frac | advance_frac) != 0; }
+    __host__ __device__ uint64_t top(const Geometry &g) const { return 64ull * g.y_start + y_frac; }              // Y_0
+    __host__ __device__ uint64_t step(const Geometry &g) const { return 64ull * g.line_advance + advance_frac; }  // L
+};
+
+// slot_rows on the fractional grid: the crop row yc_i = Y_i >> 6 (clamped), its rows, and f_i = Y_i & 63, the part of a pixel
+// the line sits below its crop's top.  i <= n_slots, so i * L stays below 64 * page_h + L.
+__device__ __forceinline__ void slot_rows_frac(const Geometry &g, const LineFrac &fr, uint32_t i, uint32_t *yc, uint32_t *h, uint32_t *f) {
+    const uint64_t y = fr.top(g) + (uint64_t)i * fr.step(g);
+    *yc = (uint32_t)std::min<uint64_t>(y >> 6, g.page_h);
+    *h = std::min(g.line_height, g.page_h - *yc);
+    *f = (uint32_t)y & 63;
+}
+
+// The centre of a line's baseline candidates, in steps of 2^-bits px, halves up: 0 <= c <= 2^bits.
+__device__ __forceinline__ int frac_centre(uint32_t f, uint32_t bits) { return (int)(((f << bits) + 32) >> 6); }
+
+// rows: slot i's crop row and rows, and the centre of its baseline candidates for y_bits `bits` (per line, and uniform across
+// the workgroup: a handful of scalar integer operations).  row: the slot's y as the verify draws from it.
+struct PixelGrid {
+    __device__ __forceinline__ void rows(const Geometry &g, uint32_t i, uint32_t bits, uint32_t *yc, uint32_t *h, int *centre) const {
+        slot_rows(g, i, yc, h);
+        *centre = 0;
+    }
+    __device__ __forceinline__ int64_t row(const Geometry &g, uint32_t i) const { return (int64_t)g.y_start + (int64_t)i * g.line_advance; }
+};
+
+struct FracGrid {
+    LineFrac fr;
+    __device__ __forceinline__ void rows(const Geometry &g, uint32_t i, uint32_t bits, uint32_t *yc, uint32_t *h, int *centre) const {
+        uint32_t f;
+        slot_rows_frac(g, fr, i, yc, h, &f);
+        *centre = frac_centre(f, bits);
+    }
+    __device__ __forceinline__ int64_t row(const Geometry &g, uint32_t i) const { return (int64_t)((fr.top(g) + (uint64_t)i * fr.step(g)) >> 6); }
+};
 
 constexpr uint32_t TEST_THREADS = 256;
 
@@ -117,6 +162,18 @@ __device__ __forceinline__ void slot_range(const Geometry &g, int r0, int r1, in
     const int64_t lo = (int64_t)r0 - reach - g.y_start, hi = (int64_t)r1 - 1 - g.y_start;
     *i_lo = lo <= 0 ? 0 : (lo + g.line_advance - 1) / g.line_advance;
     *i_hi = hi < 0 ? -1 : std::min<int64_t>(g.n_slots - 1, hi / g.line_advance);
+}
+
+// slot_range on the fractional grid, exactly: the slots i with yc_i <= r1 - 1 and yc_i + reach >= r0, where
+// yc_i = (Y_0 + i * L) >> 6: yc_i <= r is Y_0 + i * L < 64 * (r + 1), and yc_i >= r is Y_0 + i * L >= 64 * r.  L >= 64 when
+// there are slots (line_advance 0 is refused).
+__device__ __forceinline__ void slot_range_frac(const Geometry &g, const LineFrac &fr, int r0, int r1, int64_t reach, int64_t *i_lo, int64_t *i_hi) {
+    *i_lo = 0, *i_hi = -1;
+    if (!g.n_slots) return;
+    const int64_t Y0 = (int64_t)fr.top(g), L = (int64_t)fr.step(g);
+    const int64_t lo = 64 * ((int64_t)r0 - reach) - Y0, hi = 64 * (int64_t)r1 - 1 - Y0;
+    *i_lo = lo <= 0 ? 0 : (lo + L - 1) / L;
+    *i_hi = hi < 0 ? -1 : std::min<int64_t>(g.n_slots - 1, hi / L);
 }
 
 // Every wave takes glyph records of recs[0 .. n), clips them to the tile and leaves base + 1 + index of the last glyph over each
@@ -230,6 +287,8 @@ struct focr_decoder {
     // the same y-phase tables and writes the line's q to d_base_q; its cost is the whole-line run's d_cost
     uint32_t wbase_bits = 0, wbase_n = 0;
     uint64_t yterm_bound = 0;      // the largest stride * box_h * 2 * 255^2 of the uploaded y-phase fonts v >= 1 (a term's bound)
+    // the fractional line grid of the two baseline modes (focr_decoder_set_line_frac): (0, 0) is off
+    focr_dec::LineFrac line_frac{0, 0};
     // results of the last run
     bool have_baselines = false;   // the last successful run searched baselines
     std::vector<int8_t> base_q;    // beside lines
@@ -253,6 +312,7 @@ struct focr_decoder {
     bool run_base = false;  // ... or d_base_q, in steps of 2^-run_bits px
     uint32_t run_bits = 0;
     focr_dec::Geometry run_g{};
+    focr_dec::LineFrac run_frac{0, 0};  // the grid the run used: the verify draws on it
     size_t run_pages = 0;
     uint32_t run_x_start = 0;
     const uint8_t *run_src = nullptr;
@@ -273,6 +333,8 @@ inline thread_local std::string g_dec_err;
 
 // The second launch of a verify after a baseline run (decode_baseline.hip), on the decoder's stream; the caller checks hipGetLastError.
 void verify_compose_moved_launch(focr_decoder *dec, const TileGrid &tg, size_t n_pages, uint8_t *d_rgb);
+// ... and after a baseline run on the fractional line grid (decode_line_frac.hip).
+void verify_compose_frac_launch(focr_decoder *dec, const TileGrid &tg, size_t n_pages, uint8_t *d_rgb);
 
 inline int dfail(focr_decoder *dec, const std::string &msg) {
     if (dec) dec->err = msg;
@@ -329,9 +391,10 @@ int fetch_out(focr_decoder *dec, void *dst, int on_device, const T *d, size_t n)
 
 // The geometry of a batch for the entry point `who`, or its refusal: the page-size limit; the line slots as the
 // reference's loop visits them, with image::crop_imm's clamping of every crop (line_advance 0 with a non-empty first
-// crop never ends there); the limit on the slots of one batch.  stride and cap are the line decoder's to fill.
+// crop never ends there), or on the fractional grid fr of a run; the limit on the slots of one batch.  stride and cap are
+// the line decoder's to fill.
 inline int batch_geometry(focr_decoder *dec, const char *who, size_t n_pages, size_t page_w, size_t page_h, uint32_t x_start, uint32_t y_start,
-                          uint32_t width, uint32_t line_height, uint32_t line_advance, Geometry *out) {
+                          uint32_t width, uint32_t line_height, uint32_t line_advance, Geometry *out, const LineFrac &fr = LineFrac{0, 0}) {
     const std::string pre = std::string(who) + ": ";
     if (page_w > 0xffffu * 16 || page_h > 0xffffu * 16) return dfail(dec, pre + "page too large");
     Geometry g{};
@@ -344,7 +407,7 @@ inline int batch_geometry(focr_decoder *dec, const char *who, size_t n_pages, si
     g.line_advance = line_advance;
     if (line_height == 0 || y_start >= g.page_h) g.n_slots = 0;  // the first crop is empty: the loop ends at once
     else if (line_advance == 0) return dfail(dec, pre + "line_advance 0 (the reference never ends)");
-    else g.n_slots = (uint32_t)(((uint64_t)g.page_h - y_start + line_advance - 1) / line_advance);
+    else g.n_slots = (uint32_t)((64ull * g.page_h - fr.top(g) + fr.step(g) - 1) / fr.step(g));  // the slots with Y_i >> 6 < page_h; whole pixels off the grid
     const uint64_t total = (uint64_t)n_pages * g.n_slots;
     if (total > (1u << 30)) return dfail(dec, pre + "too many lines in one batch");
     g.total = (uint32_t)total;

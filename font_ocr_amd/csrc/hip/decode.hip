@@ -16,6 +16,8 @@
 //      place: the pen loop under every vertical candidate, and the candidate with the lowest summed footprint term.
 //      With the whole-line decode on and a radius of its own (focr_decoder_set_whole_baseline)
 //      decode_whole_baseline.hip's line_whole_baseline_kernel takes its place: the programme under every candidate.
+//      On a fractional line grid (focr_decoder_set_line_frac; the two baseline modes only) launch 1 is
+//      line_prepass_frac_kernel and launch 3 the baseline kernel's *_frac_kernel form: the slot grid in 1/64 px (decode.h).
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
@@ -33,12 +35,15 @@ namespace focr_dec {
 constexpr uint32_t PREPASS_THREADS = 256;
 constexpr uint32_t COMPACT_THREADS = 1024;
 
-// 1. crop + invert + blank flag, one workgroup per slot
-__global__ __launch_bounds__(PREPASS_THREADS) void line_prepass_kernel(const uint8_t *__restrict__ pages, Geometry g,
-                                                                       uint8_t *__restrict__ strips, uint32_t *__restrict__ flags) {
+// The prepass of one slot on a line grid (decode.h: the whole-pixel one, or the fractional one of focr_decoder_set_line_frac).
+template <class Grid>
+__device__ __forceinline__ void prepass_slot(const uint8_t *__restrict__ pages, const Geometry &g, const Grid &grid, uint8_t *__restrict__ strips,
+                                             uint32_t *__restrict__ flags) {
     const uint32_t slot = blockIdx.x;
-    uint32_t h;
-    const uint8_t *src = slot_crop(pages, g, slot, &h);
+    uint32_t yc, h;
+    int centre;
+    grid.rows(g, slot % g.n_slots, 0, &yc, &h, &centre);
+    const uint8_t *src = pages + (size_t)(slot / g.n_slots) * g.page_w * g.page_h + (size_t)yc * g.page_w + g.x;  // slot_crop
     uint8_t *dst = strips + (size_t)slot * g.stride * g.line_height;
     int ink = 0;
     const uint32_t n = g.stride * h;
@@ -55,6 +60,19 @@ __global__ __launch_bounds__(PREPASS_THREADS) void line_prepass_kernel(const uin
     }
     ink = __syncthreads_or(ink);
     if (threadIdx.x == 0) flags[slot] = ink ? 1u : 0u;
+}
+
+// 1. crop + invert + blank flag, one workgroup per slot
+__global__ __launch_bounds__(PREPASS_THREADS) void line_prepass_kernel(const uint8_t *__restrict__ pages, Geometry g,
+                                                                       uint8_t *__restrict__ strips, uint32_t *__restrict__ flags) {
+    prepass_slot(pages, g, PixelGrid{}, strips, flags);
+}
+
+// 1f. ... on the fractional line grid: a kernel of its own, so that the plain prepass keeps its arguments and its
+// instruction stream (tools/isa_hash.py)
+__global__ __launch_bounds__(PREPASS_THREADS) void line_prepass_frac_kernel(const uint8_t *__restrict__ pages, Geometry g, LineFrac fr,
+                                                                            uint8_t *__restrict__ strips, uint32_t *__restrict__ flags) {
+    prepass_slot(pages, g, FracGrid{fr}, strips, flags);
 }
 
 // 2. order-preserving compaction of the non-blank slots, one workgroup
@@ -335,6 +353,7 @@ void remember_run(focr_decoder *dec, const Geometry &g, const uint8_t *d_src, si
     dec->run_base = dec->base_n != 0 || dec->wbase_n != 0;  // (a run that got here with a radius searched baselines)
     dec->run_bits = dec->wbase_n ? dec->wbase_bits : dec->base_bits;  // (never both: a baseline search refuses the whole-line decode)
     dec->run_g = g;
+    dec->run_frac = dec->line_frac;  // (a run that got here with fractions searched baselines)
     dec->run_pages = n_pages;
     dec->run_x_start = x_start;
     dec->run_src = d_src;
@@ -479,8 +498,13 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     const float reach = (float)radius * 0.015625f;  // exact
     if (reach > dec->min_inc * 0.5f)
         return dfail(dec, "focr_decoder_run: the pen search radius is more than half the smallest pen increment (the pen could crawl)");
+    const LineFrac fr = dec->line_frac;
+    if (fr.on() && !baseline && !candidates)
+        return dfail(dec, "focr_decoder_run: a fractional line grid (focr_decoder_set_line_frac) needs a baseline search (focr_decoder_set_baseline_search) or "
+                          "baseline candidates of a whole-line run (focr_decoder_set_whole_baseline) with a radius >= 1: no other mode renders at a "
+                          "sub-pixel row yet");
     Geometry g{};
-    if (batch_geometry(dec, "focr_decoder_run", n_pages, page_w, page_h, x_start, y_start, width, line_height, line_advance, &g)) return 1;
+    if (batch_geometry(dec, "focr_decoder_run", n_pages, page_w, page_h, x_start, y_start, width, line_height, line_advance, &g, fr)) return 1;
     DEC_CHECK(hipSetDevice(dec->device));
     const uint8_t *d_src = nullptr;
     if (stage_in(dec, dec->d_pages, pages, on_device, page_w * page_h * n_pages, &d_src)) return 1;
@@ -531,7 +555,8 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     if (baseline && baseline_reserve(dec, g)) return 1;
 
     DEC_CHECK(hipEventRecord(dec->run.begin, dec->stream));
-    line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
+    if (fr.on()) line_prepass_frac_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, fr, dec->d_strips, dec->d_flags);
+    else line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
     DEC_CHECK(hipGetLastError());
     line_compact_kernel<<<1, COMPACT_THREADS, 0, dec->stream>>>(dec->d_flags, g.total, dec->d_work, dec->d_count);
     DEC_CHECK(hipGetLastError());
@@ -586,14 +611,16 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
         if (slot >= total || n > g.cap) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
         focr_decoded_line_t &l = dec->lines[k];
         l.page = slot / g.n_slots;
-        l.y = y_start + (slot % g.n_slots) * line_advance;
+        l.y = (uint32_t)((fr.top(g) + (uint64_t)(slot % g.n_slots) * fr.step(g)) >> 6);  // yc_i; y_start + i * line_advance off the fractional grid
         l.first = dec->chars.size();
         l.n_chars = n;
         l.pad = 0;
         append_line(dec->chars, all, k, g.cap, n);
         if (offsets) append_line(dec->offsets, pen, k, g.cap, n);
         if (baseline || candidates) {
-            if (bq[k] < -(int)FOCR_BASELINE_MAX || bq[k] > (int)FOCR_BASELINE_MAX) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
+            // q = c_i + offset, 0 <= c_i <= 2^B on the fractional grid and 0 off it
+            const int q_hi = (int)FOCR_BASELINE_MAX + (fr.on() ? 1 << (baseline ? dec->base_bits : dec->wbase_bits) : 0);
+            if (bq[k] < -(int)FOCR_BASELINE_MAX || bq[k] > q_hi) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
             dec->base_q.push_back((int8_t)bq[k]);
             dec->base_cost.push_back(baseline ? bcost[k] : wcost[k]);
         }

@@ -123,6 +123,7 @@ __device__ __forceinline__ int64_t candidate_loop(const uint32_t *strip, uint32_
 }
 
 // 3b. the pen loop under every baseline candidate, one workgroup per work-list line (grid-stride).  radius >= 1.
+// (line_baseline_frac_kernel below restates this body on the fractional line grid: a fix here is a fix there.)
 template <bool LDS>
 __global__ __launch_bounds__(BASE_THREADS) void line_baseline_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
                                                                      const uint32_t *__restrict__ count, BaseFont f, uint32_t radius,
@@ -170,10 +171,63 @@ __global__ __launch_bounds__(BASE_THREADS) void line_baseline_kernel(const uint8
     }
 }
 
+// 3bf. line_baseline_kernel on the fractional line grid (focr_decoder_set_line_frac; decode.h): the crop's rows are that
+// grid's, and the candidates of a line are q = c + rank_offset(rank) around the line's own centre c, worked out again for
+// every line a workgroup takes (a handful of scalar integer operations, uniform across the workgroup).  The rest is
+// line_baseline_kernel's, restated: with one body behind both kernels (the grid as a policy argument, by reference or by
+// value, with or without __restrict__) both instantiations of line_baseline_kernel changed their machine code
+// (tools/isa_hash.py), which the mode-off timing pins.
+template <bool LDS>
+__global__ __launch_bounds__(BASE_THREADS) void line_baseline_frac_kernel(const uint8_t *__restrict__ strips, Geometry g, LineFrac fr,
+                                                                          const uint32_t *__restrict__ work, const uint32_t *__restrict__ count, BaseFont f,
+                                                                          uint32_t radius, uint32_t *__restrict__ n_chars, uint16_t *__restrict__ chars,
+                                                                          int32_t *__restrict__ line_q, int64_t *__restrict__ line_cost) {
+    extern __shared__ __align__(8) uint32_t lds_base[];  // the waves' (cost, rank), then (LDS) the strip
+    uint64_t *red = (uint64_t *)lds_base;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t sdw = g.stride / 4, n_cand = 2 * radius + 1, n_lines = *count;
+    const uint32_t writer = n_cand & (BASE_WAVES - 1);
+    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
+        const uint32_t slot = work[k];
+        uint32_t yc, h, fi;
+        slot_rows_frac(g, fr, slot % g.n_slots, &yc, &h, &fi);
+        const int c = frac_centre(fi, f.bits);  // this line's
+        const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
+        if (LDS) {
+            uint32_t *lds_strip = lds_base + BASE_RED_BYTES / 4;
+            for (uint32_t i = tid; i < sdw * h; i += BASE_THREADS) lds_strip[i] = strip[i];
+            __syncthreads();
+            strip = lds_strip;
+        }
+        int64_t best_cost = INT64_MAX;
+        uint32_t best_rank = ~0u;  // a wave without a candidate: never the winner (rank 0 is never dropped: c >= 0)
+        for (uint32_t rank = wave; rank < n_cand; rank += BASE_WAVES) {
+            const int q = c + rank_offset(rank);
+            if (f.origin_y * (1 << f.bits) + q < 0) continue;  // ty_q < 0: no such rendering
+            const int64_t cost = candidate_loop<false>(strip, sdw, (int)g.w, h, g.cap, f, q, lane, nullptr, nullptr);
+            if (cost < best_cost) best_cost = cost, best_rank = rank;  // a wave's ranks ascend: the first of equal costs stays
+        }
+        if (lane == 0) red[2 * wave] = (uint64_t)best_cost, red[2 * wave + 1] = best_rank;
+        __syncthreads();
+        best_cost = (int64_t)red[0], best_rank = (uint32_t)red[1];
+        for (uint32_t v = 1; v < BASE_WAVES; v++) {
+            const int64_t cv = (int64_t)red[2 * v];
+            const uint32_t r = (uint32_t)red[2 * v + 1];
+            if (cv < best_cost || (cv == best_cost && r < best_rank)) best_cost = cv, best_rank = r;
+        }
+        if (wave == writer) {
+            const int q = c + rank_offset(best_rank);  // the absolute q: y + q * 2^-B is the line's top
+            const int64_t cost = candidate_loop<true>(strip, sdw, (int)g.w, h, g.cap, f, q, lane, chars + (size_t)k * g.cap, n_chars + k);
+            if (lane == 0) line_q[k] = q, line_cost[k] = cost;
+        }
+        __syncthreads();  // the strip and the pairs are the next line's from here
+    }
+}
+
 // 5b. decode_images.hip's verify_compose_kernel after a baseline run: the canvases lie up to FOCR_BASELINE_MAX rows above or below their slots, so
 // a tile looks that much further for the slots that can reach it; the rest is the same.  (A kernel of its own, not a template
 // or a shared body, and in this file: each of the three changes verify_compose_kernel's machine code, tools/isa_hash.py, which
-// the plain verify's timing pins.)
+// the plain verify's timing pins.  decode_line_frac.hip's verify_compose_moved_frac_kernel restates this body in turn: a fix here is a fix there.)
 __global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_moved_kernel(const uint8_t *__restrict__ pages, Geometry g, uint32_t n_pages,
                                                                        uint32_t hmax, uint32_t tiles_x, uint32_t tiles_y, const VerifyLine *__restrict__ lines,
                                                                        const VerifyRec *__restrict__ recs, const uint8_t *__restrict__ bitmaps,
@@ -262,6 +316,11 @@ void baseline_launch(focr_decoder *dec, const Geometry &g, size_t strip_bytes) {
     const uint32_t grid = dec->base_grid ? std::min(dec->base_grid, g.total) : g.total;
     const BaseFont f{dec->d_glyphs, dec->d_yglyphs, dec->d_offs, dec->d_yoffs, dec->d_bitmaps.as<const uint32_t>(), dec->d_ybitmaps.as<const uint32_t>(),
                      (uint32_t)(dec->bitmaps_len / 4), dec->ybitmaps_dw, dec->n_glyphs, dec->origin_x, (int)dec->origin_y, dec->base_bits};
+    if (dec->line_frac.on()) {
+        (lds ? line_baseline_frac_kernel<true> : line_baseline_frac_kernel<false>)<<<grid, BASE_THREADS, BASE_RED_BYTES + (lds ? strip_bytes : 0), dec->stream>>>(
+            dec->d_strips, g, dec->line_frac, dec->d_work, dec->d_count, f, dec->base_n, dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
+        return;
+    }
     const auto kernel = lds ? line_baseline_kernel<true> : line_baseline_kernel<false>;
     kernel<<<grid, BASE_THREADS, BASE_RED_BYTES + (lds ? strip_bytes : 0), dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, f, dec->base_n,
                                                                                          dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);

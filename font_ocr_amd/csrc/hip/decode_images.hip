@@ -33,12 +33,14 @@ namespace focr_dec {
 // and the pen advances from there, the decoder's own two f32 adds.  ps (null: none) is a whole-line run's pens in
 // 1/64 px: glyph q is placed at ps[q] / 64 (exact), whatever the increments before it.  moved is a baseline run's whole rows
 // for this line (0: none): the canvas is drawn that many rows below the slot's y, above it when negative, and is then
-// clipped at the page's top as well.
-template <bool IOTA>
+// clipped at the page's top as well.  grid is the line grid the slot's y is read from (decode.h): the whole-pixel one
+// unless the run was made on the fractional one.
+template <bool IOTA, class Grid = PixelGrid>
 __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, const uint16_t *__restrict__ cs,
                                             const int8_t *__restrict__ js, const uint32_t *__restrict__ ps, int moved, uint32_t n, uint32_t k,
                                             uint32_t x_start, const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
-                                            const VerifyPhase *__restrict__ vphases, VerifyRec *__restrict__ out, VerifyLine *__restrict__ line) {
+                                            const VerifyPhase *__restrict__ vphases, VerifyRec *__restrict__ out, VerifyLine *__restrict__ line,
+                                            const Grid &grid = Grid{}) {
     const uint32_t lane = threadIdx.x;
     float pen = 0.f;
     int ox = 0, oy = 0, lx = 0, ly = 0;
@@ -71,7 +73,7 @@ __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, co
     }
     const int cw = lx - ox, ch = ly - oy;
     const int64_t W = g.page_w, H = g.page_h;
-    const int64_t line_y = IOTA ? 0 : (int64_t)g.y_start + (int64_t)(slot % g.n_slots) * g.line_advance + moved;
+    const int64_t line_y = IOTA ? 0 : grid.row(g, slot % g.n_slots) + moved;
     const int top = IOTA ? 0 : (int)std::max<int64_t>(-line_y, 0);  // the canvas rows above the page (a line moved up)
     const float neg_ox = (float)(-ox);
     for (uint32_t j = lane; j < n; j += 64) {
@@ -98,6 +100,7 @@ __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, co
 }
 
 // 4. render()'s layout of every decoded line, one wave per work-list line; blocks below n_pages also zero the sums
+// (verify_layout_frac_kernel below restates this body on the fractional line grid: a fix here is a fix there)
 __global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t n_pages, uint32_t x_start, const uint32_t *__restrict__ flags,
                                                            const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
                                                            const uint32_t *__restrict__ n_chars, const uint16_t *__restrict__ chars,
@@ -117,6 +120,29 @@ __global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t 
     layout_line<false>(g, slot, chars + (size_t)k * g.cap, pen_offs ? pen_offs + (size_t)k * g.cap : nullptr,
                        pens ? pens + (size_t)k * g.cap : nullptr, moved, n, k, x_start,
                        glyphs, vglyphs, vphases, recs + (size_t)k * g.cap, lines + slot);
+}
+
+// 4f. verify_layout_kernel after a run on the fractional line grid (focr_decoder_set_line_frac): every line's y is its crop
+// row Y_i >> 6.  A kernel of its own, so that verify_layout_kernel keeps its arguments and its instruction stream
+// (tools/isa_hash.py).
+__global__ __launch_bounds__(64) void verify_layout_frac_kernel(Geometry g, LineFrac fr, uint32_t n_pages, uint32_t x_start, const uint32_t *__restrict__ flags,
+                                                                const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
+                                                                const uint32_t *__restrict__ n_chars, const uint16_t *__restrict__ chars,
+                                                                const int8_t *__restrict__ pen_offs, const uint32_t *__restrict__ pens,
+                                                                const int32_t *__restrict__ line_q, uint32_t y_bits,
+                                                                const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
+                                                                const VerifyPhase *__restrict__ vphases, VerifyLine *__restrict__ lines,
+                                                                VerifyRec *__restrict__ recs, unsigned long long *__restrict__ sums) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (b < n_pages && lane == 0) sums[b] = 0;
+    if (b >= g.total) return;
+    if (lane == 0 && flags[b] == 0) lines[b] = VerifyLine{0, 0, 0, 0, 0, 0};
+    if (b >= *count) return;
+    const uint32_t k = b, slot = work[k], n = n_chars[k];
+    const int moved = line_q ? (line_q[k] + (int)((1u << y_bits) >> 1)) >> y_bits : 0;  // q is the absolute one: from the crop row
+    layout_line<false>(g, slot, chars + (size_t)k * g.cap, pen_offs ? pen_offs + (size_t)k * g.cap : nullptr,
+                       pens ? pens + (size_t)k * g.cap : nullptr, moved, n, k, x_start,
+                       glyphs, vglyphs, vphases, recs + (size_t)k * g.cap, lines + slot, FracGrid{fr});
 }
 
 // 5. compose the verify image tile by tile; every thread owns one column of a 16-row, 256-column tile
@@ -357,14 +383,22 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     uint8_t *d_rgb = nullptr;
     if (stage_out(dec, dec->d_rgb, rgb, rgb_on_device, px * 3, &d_rgb)) return 1;
     DEC_CHECK(hipEventRecord(dec->verify.begin, dec->stream));
-    verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, dec->run_x_start, dec->d_flags, dec->d_work,
-                                                                         dec->d_count, dec->d_nchars, dec->d_chars,
-                                                                         dec->run_searched ? (const int8_t *)dec->d_pen : nullptr,
-                                                                         dec->run_whole ? (const uint32_t *)dec->d_pens : nullptr,
-                                                                         dec->run_base ? (const int32_t *)dec->d_base_q : nullptr, dec->run_bits, dec->d_glyphs,
-                                                                         dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
+    const int8_t *pen_offs = dec->run_searched ? (const int8_t *)dec->d_pen : nullptr;
+    const uint32_t *pens = dec->run_whole ? (const uint32_t *)dec->d_pens : nullptr;
+    const int32_t *line_q = dec->run_base ? (const int32_t *)dec->d_base_q : nullptr;
+    if (dec->run_frac.on())  // (only a baseline run is made on the fractional grid: run_base holds)
+        verify_layout_frac_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, dec->run_frac, (uint32_t)n_pages, dec->run_x_start, dec->d_flags, dec->d_work,
+                                                                                  dec->d_count, dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, dec->run_bits,
+                                                                                  dec->d_glyphs, dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs,
+                                                                                  dec->d_sums);
+    else
+        verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, dec->run_x_start, dec->d_flags, dec->d_work, dec->d_count,
+                                                                             dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, dec->run_bits, dec->d_glyphs,
+                                                                             dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
     DEC_CHECK(hipGetLastError());
-    if (dec->run_base)  // the canvases of a baseline run are moved off their slots: decode_baseline.hip's compose finds them
+    if (dec->run_frac.on())  // ... and on the fractional grid the slots that reach a tile come from that grid's inverse
+        verify_compose_frac_launch(dec, tg, n_pages, d_rgb);
+    else if (dec->run_base)  // the canvases of a baseline run are moved off their slots: decode_baseline.hip's compose finds them
         verify_compose_moved_launch(dec, tg, n_pages, d_rgb);
     else
         verify_compose_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->run_src, g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y, dec->d_vlines, dec->d_vrecs,

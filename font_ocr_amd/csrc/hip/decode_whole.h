@@ -107,17 +107,21 @@ __device__ __forceinline__ int glyph_term_at(const TermIn &T, uint32_t gi, int d
     return footprint_term(T.strip, T.sdw, T.w, T.h, T.bitmaps + gl.off_dw + (uint32_t)phase * gl.ndw * gl.box_h, gl.ndw, gl.box_h, shift + o.x, o.y + T.d);
 }
 
-// A line's rows and its strip, staged in LDS when it fits.  No barrier: whole_reset's follows.
-template <bool LDS>
-__device__ __forceinline__ void whole_stage(const WholeLds &L, const uint8_t *__restrict__ strips, const Geometry &g, uint32_t slot, TermIn *T) {
+// A line's rows and its strip, staged in LDS when it fits, on a line grid (decode.h); the centre of the line's baseline
+// candidates for y_bits `bits` is returned (0 on the whole-pixel grid).  No barrier: whole_reset's follows.
+template <bool LDS, class Grid = PixelGrid>
+__device__ __forceinline__ int whole_stage(const WholeLds &L, const uint8_t *__restrict__ strips, const Geometry &g, uint32_t slot, TermIn *T,
+                                           const Grid &grid = Grid{}, uint32_t bits = 0) {
     const uint32_t tid = threadIdx.x;
     uint32_t yc;
-    slot_rows(g, slot % g.n_slots, &yc, &T->h);
+    int centre;
+    grid.rows(g, slot % g.n_slots, bits, &yc, &T->h, &centre);
     T->strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
     if (LDS) {
         for (uint32_t q = tid; q < T->sdw * T->h; q += WHOLE_THREADS) L.strip[q] = T->strip[q];
         T->strip = L.strip;
     }
+    return centre;
 }
 
 // A programme begins: the ring with cost[0] = 0 and every other state unreachable, no live state.  ring[s & mask] holds

@@ -32,7 +32,8 @@ struct WholeBase {
 };
 
 // 3wb. line_whole_kernel under every baseline candidate.  scratch holds two halves of wp.n_states backpointers per
-// workgroup.
+// workgroup.  (line_whole_baseline_frac_kernel below restates this body on the fractional line grid: a fix here is a fix
+// there.)
 template <bool LDS>
 __global__ __launch_bounds__(WHOLE_THREADS) void line_whole_baseline_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
                                                                             const uint32_t *__restrict__ count, const DevGlyph *__restrict__ glyphs,
@@ -97,6 +98,73 @@ __global__ __launch_bounds__(WHOLE_THREADS) void line_whole_baseline_kernel(cons
     }
 }
 
+// 3wbf. line_whole_baseline_kernel on the fractional line grid (focr_decoder_set_line_frac; decode.h): whole_stage reads the
+// crop's rows from that grid and returns the line's own centre c, and the candidates are q = c + rank_offset(rank), for every
+// line a workgroup takes.  The rest is line_whole_baseline_kernel's, restated: with one body behind both kernels both
+// instantiations of line_whole_baseline_kernel changed their machine code (tools/isa_hash.py), which the mode-off timing pins.
+template <bool LDS>
+__global__ __launch_bounds__(WHOLE_THREADS) void line_whole_baseline_frac_kernel(const uint8_t *__restrict__ strips, Geometry g, LineFrac fr,
+                                                                                 const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
+                                                                                 const DevGlyph *__restrict__ glyphs, const int2 *__restrict__ offs,
+                                                                                 const uint32_t *__restrict__ bitmaps, const uint32_t *__restrict__ inc64,
+                                                                                 uint32_t n_glyphs, WholeParams wp, uint16_t *scratch, uint32_t *__restrict__ n_chars,
+                                                                                 uint16_t *chars, uint32_t *pens, int64_t *__restrict__ costs, WholeBase wb) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_whole[];
+    const WholeLds L = whole_carve(lds_whole, false, wp.ring_mask + 1, 0);
+    const uint32_t tid = threadIdx.x, mask = wp.ring_mask, n_live_states = 64u * g.w;
+    const uint32_t n_cand = 2 * wb.radius + 1;
+    TermIn T{nullptr, g.stride / 4, 0, (int)g.w, glyphs, offs, bitmaps, 0};
+    uint16_t *halves = scratch + (size_t)blockIdx.x * 2 * wp.n_states;
+    const uint32_t n_lines = *count;
+    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
+        const size_t row = (size_t)k * g.cap;
+        const int c = whole_stage<LDS>(L, strips, g, work[k], &T, FracGrid{fr}, wb.bits);  // this line's
+        if (tid == 0) *L.half = 0;
+        int64_t best_cost = INT64_MAX;
+        int best_q = 0;
+        uint32_t best_t = 0, best_gi = 0xffffu, best_half = 0;
+        for (uint32_t rank = 0; rank < n_cand; rank++) {
+            const int q = c + rank_offset(rank);  // the absolute q: y + q * 2^-B is the line's top
+            if (wb.origin_y * (1 << wb.bits) + q < 0) continue;  // ty_q < 0: no such rendering (uniform; never rank 0: c >= 0)
+            const uint32_t v = (uint32_t)q & ((1u << wb.bits) - 1);
+            T.glyphs = v ? wb.yglyphs + (size_t)(v - 1) * n_glyphs : glyphs;
+            T.offs = v ? wb.yoffs + (size_t)(v - 1) * n_glyphs * 64 : offs;
+            T.bitmaps = v ? wb.ybitmaps : bitmaps;
+            T.d = q >> wb.bits;  // floor
+            whole_reset(L, mask);
+            const uint32_t half = *L.half;
+            uint16_t *back = halves + (size_t)half * wp.n_states;
+            whole_forward(
+                L, T, wp, inc64, n_glyphs, n_live_states, 0u,
+                [&](uint32_t b0, uint32_t j) {
+                    const uint64_t key = L.ring[(b0 + j) & mask];
+                    if (key == ~0ull) return;
+                    back[b0 + j] = (uint16_t)key;
+                    whole_list(L, j);
+                },
+                [&](uint32_t, uint32_t s) { return L.ring[s & mask] >> 16; });
+            const uint64_t best = whole_end_state(L, wp, n_live_states);
+            if (tid == 0) {
+                int64_t cost;
+                uint32_t t;
+                const uint32_t gi = whole_walk_start(L, wp, best, n_live_states, &cost, &t);
+                if (cost < best_cost) {  // ranks ascend: the first of equal costs stays
+                    best_cost = cost, best_q = q, best_t = t, best_gi = gi, best_half = half;
+                    *L.half = half ^ 1;
+                }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const uint16_t *won = halves + (size_t)best_half * wp.n_states;
+            costs[k] = best_cost;
+            wb.line_q[k] = best_q;
+            whole_walk_from(L, best_t, best_gi, inc64, n_glyphs, g.cap, row, chars, pens, &n_chars[k], [&](uint32_t t) { return (uint32_t)won[t]; });
+        }
+        whole_reverse<false>(L, row, chars, pens, nullptr);
+    }
+}
+
 // ---- the host's side (decode_line.h) ---------------------------------------------------------------------------------
 
 int whole_baseline_plan(focr_decoder *dec) {
@@ -118,6 +186,12 @@ void whole_baseline_launch(focr_decoder *dec, const Geometry &g, const WholePlan
     const size_t fixed = whole_fixed_bytes(false, plan.ring, 0);
     const bool lds = strip_bytes + fixed <= LDS_STRIP_MAX;
     const WholeBase wb{dec->d_yglyphs, dec->d_yoffs, dec->d_ybitmaps.as<const uint32_t>(), (int)dec->origin_y, dec->wbase_bits, dec->wbase_n, dec->d_base_q};
+    if (dec->line_frac.on()) {
+        (lds ? line_whole_baseline_frac_kernel<true> : line_whole_baseline_frac_kernel<false>)<<<plan.grid, WHOLE_THREADS, fixed + (lds ? strip_bytes : 0), dec->stream>>>(
+            dec->d_strips, g, dec->line_frac, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64,
+            dec->n_glyphs, wp, dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, wb);
+        return;
+    }
     (lds ? line_whole_baseline_kernel<true> : line_whole_baseline_kernel<false>)<<<plan.grid, WHOLE_THREADS, fixed + (lds ? strip_bytes : 0), dec->stream>>>(
         dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
         dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, wb);

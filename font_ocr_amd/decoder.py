@@ -26,6 +26,9 @@
         pages, pens, costs, baselines = dec.decode(luma_pages, 45, 39, 608, 12, 15, whole_line=True, whole_baseline=2)
         # the whole-line decode under every vertical offset -2 ..= 2 quarter pixels, the candidate whose whole line costs
         # least kept: proportional text whose baseline is off the crop grid; baselines[page][line]: its q
+        pages, baselines, costs = dec.decode(luma_pages, 45, 39, 608, 12, 15, baseline_search=1, y_frac=20, line_advance_frac=38)
+        # a fractional line grid for the two baseline modes: the first line's top at 39 + 20/64 px and a leading of
+        # 15 + 38/64 px; every line is cropped at the whole row of its own top and searched around its own sub-pixel part
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -225,6 +228,7 @@ class LineDecoder:
         self._pen_slack = 0  # the library's radius (focr_decoder_set_whole_slack)
         self._baseline = (0, 0)  # the library's y_bits and radius (focr_decoder_set_baseline_search)
         self._whole_baseline = (0, 0)  # the library's y_bits and radius (focr_decoder_set_whole_baseline)
+        self._line_frac = (0, 0)  # the library's sub-pixel parts of y and line_advance (focr_decoder_set_line_frac)
 
     def _check(self, rc):
         if rc != 0:
@@ -343,7 +347,7 @@ class LineDecoder:
         return mse, imgs
 
     def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0, whole_line=False,
-             margins=False, pen_slack=0, baseline_search=0, whole_baseline=0):
+             margins=False, pen_slack=0, baseline_search=0, whole_baseline=0, line_frac=(0, 0)):
         """[[(y, text), ...] per page] of one batch; with scores [[LineScores, ...] per page] beside it (else None); with
         a pen search [[int8 offsets, ...] per page] (else None); with whole_line ([[uint32 pens, ...] per page],
         [[cost, ...] per page]) (else None), and with margins [[LineMargins, ...] per page], or with a pen slack
@@ -358,6 +362,9 @@ class LineDecoder:
         if whole_base != self._whole_baseline:
             self._check(self._lib.focr_decoder_set_whole_baseline(self._h, *whole_base))
             self._whole_baseline = whole_base
+        if tuple(line_frac) != self._line_frac:
+            self._check(self._lib.focr_decoder_set_line_frac(self._h, *line_frac))
+            self._line_frac = tuple(line_frac)
         if int(pen_slack) != self._pen_slack:
             self._check(self._lib.focr_decoder_set_whole_slack(self._h, int(pen_slack)))
             self._pen_slack = int(pen_slack)
@@ -482,8 +489,18 @@ class LineDecoder:
                 raise ValueError(f"whole_baseline does not go with {what} (neither has a definition across candidates yet)")
         return n
 
+    @staticmethod
+    def _check_line_frac(y_frac, line_advance_frac, baseline_search, whole_baseline):
+        fr = (int(y_frac), int(line_advance_frac))
+        for v, name in zip(fr, ("y_frac", "line_advance_frac")):
+            if not 0 <= v <= 63:
+                raise ValueError(f"{name} must be 0 .. 63 (1/64 px), not {v!r}")
+        if fr != (0, 0) and not baseline_search and not whole_baseline:
+            raise ValueError("y_frac and line_advance_frac need baseline_search or whole_baseline (no other mode renders at a sub-pixel row yet)")
+        return fr
+
     def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, pen_slack=0,
-               baseline_search=0, whole_baseline=0, margins=False, whole_line=False):
+               baseline_search=0, whole_baseline=0, y_frac=0, line_advance_frac=0, margins=False, whole_line=False):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
         Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
         mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
@@ -515,7 +532,12 @@ class LineDecoder:
         costs least is the line (on a tie the offset nearest 0): proportional text whose baseline is off the crop grid.
         The result gains one last element after costs: baselines[page][line], the chosen q (int); pens and costs are that
         candidate's.  The verify renders every character at its pen on a canvas moved by the nearest whole row of the
-        offset.  It needs whole_line=True and goes with neither margins nor pen_slack (ValueError)."""
+        offset.  It needs whole_line=True and goes with neither margins nor pen_slack (ValueError).
+        With y_frac and line_advance_frac (each 0 .. 63, in 1/64 px; include/focr_decode.h) beside baseline_search or
+        whole_baseline, the lines lie on a fractional grid: line i's top is at y + y_frac / 64 + i * (line_advance +
+        line_advance_frac / 64) px, its crop starts at the whole row of that (the y of the result's line), and its candidates
+        are searched around its own sub-pixel part; the returned q is the absolute one, so y + q * 2^-y_bits px stays the
+        line's top.  For pages whose leading is not a whole number of pixels.  Without either search: ValueError."""
         if self.font is None:
             raise DecoderError("set_font() first")
         _check_verify(verify)
@@ -525,6 +547,7 @@ class LineDecoder:
         pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
         baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
         whole_baseline = self._check_whole_baseline(whole_baseline, whole_line, margins, pen_slack)
+        line_frac = self._check_line_frac(y_frac, line_advance_frac, baseline_search, whole_baseline)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
@@ -546,7 +569,7 @@ class LineDecoder:
             res, res_sc, res_offs, res_whole, res_base = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
                                                                    pen_search=pen_search, whole_line=whole_line, margins=margins,
                                                                    pen_slack=pen_slack, baseline_search=baseline_search,
-                                                                   whole_baseline=whole_baseline)
+                                                                   whole_baseline=whole_baseline, line_frac=line_frac)
             for j, i in enumerate(idx):
                 out[i] = res[j]
                 if baseline_search:
@@ -587,7 +610,8 @@ class LineDecoder:
         return res if len(res) > 1 else out
 
     def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False,
-                      pen_search=0, pen_slack=0, baseline_search=0, whole_baseline=0, margins=False, whole_line=False):
+                      pen_search=0, pen_slack=0, baseline_search=0, whole_baseline=0, y_frac=0, line_advance_frac=0, margins=False,
+                      whole_line=False):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
         if self.font is None:
@@ -599,10 +623,11 @@ class LineDecoder:
         pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
         baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
         whole_baseline = self._check_whole_baseline(whole_baseline, whole_line, margins, pen_slack)
+        line_frac = self._check_line_frac(y_frac, line_advance_frac, baseline_search, whole_baseline)
         out, sc, offs, whole, base = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
                                                int(line_height), int(line_advance), scores=scores, pen_search=pen_search,
                                                whole_line=whole_line, margins=margins, pen_slack=pen_slack, baseline_search=baseline_search,
-                                               whole_baseline=whole_baseline)
+                                               whole_baseline=whole_baseline, line_frac=line_frac)
         res = (out,)
         if verify:
             mse, imgs = self._verified(verify, int(page_h), int(page_w))

@@ -330,7 +330,7 @@ int focr_decoder_set_whole_slack(focr_decoder_t *dec, uint32_t n);
  * scores, a pen search, the whole-line decode, margins or a pen slack; it also refuses N > 0 with B > 0 unless y-phase
  * fonts of that B are uploaded (focr_decoder_set_baseline_fonts), and an origin_y that is not a whole number >= 0.
  * What it does not cure: a leading that drifts past the radius down a page (every line searches around the same crop
- * grid; the offset is not carried from line to line). */
+ * grid; the offset is not carried from line to line): a leading that is known goes into focr_decoder_set_line_frac. */
 enum { FOCR_BASELINE_MAX = 32, FOCR_BASELINE_Y_BITS_MAX = 3 };
 
 /* host (libfocr_raster.so): the 1 << y_bits y-phase fonts of an alphabet.  out[v] is what focr_decode_font_build
@@ -395,6 +395,42 @@ int focr_decoder_debug_set_baseline_grid(focr_decoder_t *dec, uint32_t grid);
 /* Set y_bits and the radius of later whole-line runs (0, 0 when the decoder is created; a state of the decoder, not of
  * the font).  y_bits above FOCR_BASELINE_Y_BITS_MAX and n above FOCR_BASELINE_MAX are refused here. */
 int focr_decoder_set_whole_baseline(focr_decoder_t *dec, uint32_t y_bits, uint32_t n);
+
+/* ---- device: a fractional line grid for the two baseline modes (an extension of the extensions) ---------------------- */
+
+/* line_advance is a whole number of pixels, in the reference and here, but the leading of a rendered page seldom is (13 px
+ * text at 1.2 line spacing: 15.6 px), so down such a page the lines drift off the crop grid by the leading's fraction per
+ * line and past any radius after a few.  The two baseline modes (focr_decoder_set_baseline_search and
+ * focr_decoder_set_whole_baseline) are the modes with sub-pixel vertical phases; with a fractional grid they search around
+ * where each line is, not around the whole-pixel grid.  y_frac and advance_frac are the sub-pixel parts of y_start and
+ * line_advance in 1/64 px, the unit of pens and of FreeType.  All of it is exact integer arithmetic:
+ *   - L = 64 * line_advance + advance_frac; slot i of a page has its top at Y_i = 64 * y_start + y_frac + i * L (64 bits);
+ *   - its crop starts at row yc_i = Y_i >> 6, clamped as image::crop_imm clamps it, and has
+ *     h_i = min(line_height, page_h - yc_i) rows; f_i = Y_i & 63 is the part of a pixel the line sits below its crop's top;
+ *   - a page has the slots i with yc_i < page_h: n_slots = ceil((64 * page_h - Y_0) / L) when y_start < page_h and
+ *     line_height > 0, else 0; the blank test, the compaction, the (page, line) order and focr_decoded_line_t::y = yc_i
+ *     follow that grid;
+ *   - the line's centre is c_i = ((f_i << B) + 32) >> 6, in steps of 2^-B px, halves up: 0 <= c_i <= 2^B (a centre of 2^B is
+ *     one whole row, which q >> B handles);
+ *   - the candidates of line i are q = c_i + rank_offset(rank), rank in 0 ..= 2 N, in rank order (offsets 0, -1, +1, -2, ...);
+ *     everything else is the mode's own: y-phase q & (2^B - 1), every box moved down by q >> B rows, the four-sided clipping,
+ *     and a candidate with ty_q = origin_y + q * 2^-B < 0 dropped (rank 0 never is: c_i >= 0 and origin_y >= 0);
+ *   - the line is the candidate with the lowest (cost_q, rank): on a tie the offset nearest the centre wins;
+ *   - the returned q is the absolute one, -FOCR_BASELINE_MAX ..= 2^B + FOCR_BASELINE_MAX (at most 40: it fits the int8_t):
+ *     focr_decoder_get_baselines keeps its format, and y + q * 2^-B px stays the line's true top.
+ * focr_decoder_verify keeps its two rules with yc_i as the line's y: the canvas moved by (q + (1 << B >> 1)) >> B rows, which
+ * may now be up to FOCR_BASELINE_MAX + 1 rows below its slot, clipped at the page's top and bottom, and after a whole-line
+ * run every character at its returned pen.  The launch count stays 3 (2 for the verify).  focr_decoder_run refuses, before
+ * anything is launched and with a message that names the setters, a fractional grid without a baseline search or baseline
+ * candidates of a whole-line run at a radius >= 1: the plain loop, scores, the pen search, the whole-line decode without
+ * candidates, margins and the pen slack have no sub-pixel row to render at (giving them the grid is a later step).  Whatever
+ * the mode in force refuses is still refused, and so is line_advance == 0, whatever advance_frac.  focr_decoder_test_images
+ * takes its own geometry and knows no grid.  With (0, 0) every run launches and returns what it did before the grid existed.
+ * What it does not cure: an unknown leading still has to be read off the returned q of the first lines (y + q * 2^-B), and
+ * the other modes stay on the whole-pixel grid. */
+/* Set the sub-pixel parts of y_start and line_advance of later runs, each 0 ..= 63 in 1/64 px ((0, 0), off, when the decoder
+ * is created; a state of the decoder, not of the font).  A value above 63 is refused here. */
+int focr_decoder_set_line_frac(focr_decoder_t *dec, uint32_t y_frac, uint32_t advance_frac);
 
 /* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
 

@@ -1,0 +1,130 @@
+"""The pages and geometries that tests/test_gpu_focr_line_frac.py runs on the device and that
+tests/test_focr_line_frac_model.py proves, on the CPU model, to reach the cases their names promise.  Small on purpose:
+pages of about 100 x 130 px, lines of 12 to 16 rows, alphabets of 4 to 12 glyphs (the whole-line programme on the CPU costs
+0.3 s per candidate of a 100 px line of 11 glyphs), except where the case itself is a size (the strip past LDS).
+"""
+import collections
+import functools
+import os
+
+import numpy as np
+
+import focr_baseline_model as B
+import focr_line_frac_model as LF
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MONO = os.path.join(GOLD, "DejaVuSansMono.ttf")
+SANS = os.path.join(GOLD, "DejaVuSans.ttf")
+MONO_AL = " ABab01+"      # the baseline search's: 8 glyphs, with a space, so that the blank rest of a line costs nothing
+SANS_AL = " burnclip"     # the whole-line candidates': 9 glyphs of `burn clip`
+
+# name, whole (the whole-line decode under candidates, else the baseline search), font, size, alphabet, B, N, pages,
+# (x, y, width, line_height, line_advance), (y_frac, advance_frac)
+Case = collections.namedtuple("Case", "name whole font size alphabet y_bits n pages geo frac")
+
+
+@functools.lru_cache(maxsize=None)
+def model(font, size, alphabet, y_bits):
+    return B.BaselineModel(font, size, alphabet, y_bits=y_bits)
+
+
+def _texts(alphabet, n_lines, n_chars, seed, blank=()):
+    rng = np.random.default_rng(seed)
+    ink = [c for c in alphabet if not c.isspace()]
+    return [None if i in blank else "".join(rng.choice(ink, n_chars)) for i in range(n_lines)]
+
+
+def grid_page(font, size, alphabet, H, W, texts, x, y, frac, line_advance, shift=None):
+    """A white page with texts[i] on slot i of the grid; shift[i] px (a float, default 0) moves line i off its slot."""
+    page = np.full((H, W), 255, dtype=np.uint8)
+    for i, text in enumerate(texts):
+        Y = 64 * y + frac[0] + i * LF.step(line_advance, frac[1])
+        if text and (Y >> 6) < H:
+            B.draw_offset(page, font, size, alphabet, text, x, Y >> 6, (Y & 63) / 64.0 + (shift[i] if shift else 0.0))
+    return page
+
+
+# The standard grid: y = 3 + 60/64 px and a leading of 15 + 38/64 px on a page of 136 rows.  Nine slots at rows 3, 19, 35,
+# 50, 66, 81, 97, 113 and 128 (the whole-pixel grid's are 3, 18, 33, ...), with f = 60, 34, 8, 46, 20, 58, 32, 6, 44: slot 0
+# has the centre 2^B at every B, slot 3 is left blank between inked ones, and the page cuts slot 8 to 8 rows.
+STD_GEO, STD_FRAC, STD_H = (2, 3, 96, 14, 15), (60, 38), 136
+
+
+def std_pages(whole, seed, n_pages=1):
+    if whole:  # three lines of 58 columns: slots 0 and 2 inked, slot 1 blank, and nothing below
+        return [grid_page(SANS, 13.0, SANS_AL, 60, 62, _texts(SANS_AL, 3, 7, seed + p, blank=(1,)), 2, 3, STD_FRAC, 15) for p in range(n_pages)]
+    return [grid_page(MONO, 13.0, MONO_AL, STD_H, 100, _texts(MONO_AL, 9, 11, seed + p, blank=(3,)), 2, 3, STD_FRAC, 15) for p in range(n_pages)]
+
+
+def std_case(whole, y_bits, n):
+    if whole:
+        return Case(f"std-whole-B{y_bits}-N{n}", True, SANS, 13.0, SANS_AL, y_bits, n, std_pages(True, 7 + y_bits + n), (2, 3, 58, 14, 15), STD_FRAC)
+    return Case(f"std-base-B{y_bits}-N{n}", False, MONO, 13.0, MONO_AL, y_bits, n, std_pages(False, 7 + y_bits + n, 2), STD_GEO, STD_FRAC)
+
+
+def dropped_case(whole):
+    """A 6 px font's origin_y is 5: at B = 0 and N = 8 the candidates q < -5 are dropped, beside centres of 0 and 1; the middle line sits 3 px above its slot."""
+    al = " ABab"
+    geo, frac = (0, 0, 40, 12, 12), (20, 24)  # f = 20, 44, 4: centres 0, 1, 0
+    page = grid_page(MONO, 6.0, al, 40, 44, ["AbBa", "baAB", "ABab"], 0, 0, frac, 12, shift=[0.0, -3.0, 0.0])
+    return Case("dropped-" + ("whole" if whole else "base"), whole, MONO, 6.0, al, 0, 8, [page], geo, frac)
+
+
+def advance_one_case():
+    """line_advance 1 with a fraction under a line_height of 12: a slot every 1 + 21/64 rows, about twelve per tile row of
+    the moved compose, two text lines among them."""
+    frac = (5, 21)
+    page = np.full((44, 100), 255, dtype=np.uint8)
+    B.draw_offset(page, MONO, 13.0, MONO_AL, "Ab01+aB", 2, 4, 0.25)
+    B.draw_offset(page, MONO, 13.0, MONO_AL, "+10bA", 2, 24, 0.75)
+    return Case("advance-one", False, MONO, 13.0, MONO_AL, 2, 1, [page], (2, 0, 96, 12, 1), frac)
+
+
+def moved_off_page_case(whole):
+    """The first line sits 3 px above its slot at row 0 and the last one 3 px below a slot the page cuts: at B = 0, N = 4
+    the verify moves the first canvas above row 0 and the last one past the page's last row."""
+    al, font = (SANS_AL, SANS) if whole else (MONO_AL, MONO)
+    frac, W = (0, 38), 62 if whole else 100
+    texts = _texts(al, 3, 6 if whole else 11, 3)
+    page = grid_page(font, 13.0, al, 42, W, texts, 2, 0, frac, 15, shift=[-3.0, 0.0, 3.0])
+    return Case("moved-off-page-" + ("whole" if whole else "base"), whole, font, 13.0, al, 0, 4, [page], (2, 0, W - 4, 14, 15), frac)
+
+
+def far_below_case(y):
+    """The far end of the verify's lower reach: B = 0, N = 32, a slot of 48 rows at row y with f = 40, so the centre is 2^B = 1,
+    and a line drawn 33 rows below the slot's top: q = 1 + 32 = 33, the largest q there is, and the canvas is moved 33 rows
+    down.  Over y = 0 .. 15 the moved canvas's last row is the first row of a compose tile once."""
+    page = np.full((y + 64, 60), 255, dtype=np.uint8)
+    B.draw_offset(page, MONO, 13.0, MONO_AL, "Ab01+a", 2, y, 33.0)
+    return Case(f"far-below-y{y}", False, MONO, 13.0, MONO_AL, 0, 32, [page], (2, y, 56, 48, 60), (40, 0))
+
+
+def wide_case(whole):
+    """One wide page whose strip does not fit in LDS: stride * line_height > 65536."""
+    if whole:  # 128 rows of 512 columns, two glyphs: 32768 states per candidate on the CPU
+        al, geo, frac = " l", (0, 2, 512, 128, 100), (50, 30)
+        page = np.full((140, 512), 255, dtype=np.uint8)
+        B.draw_offset(page, SANS, 13.0, al, "l ll l", 0, 2, 50 / 64.0)
+        return Case("wide-whole", True, SANS, 13.0, al, 2, 1, [page], geo, frac)
+    geo, frac = (0, 1, 4200, 16, 15), (40, 38)
+    page = grid_page(MONO, 13.0, MONO_AL, 34, 4200, _texts(MONO_AL, 2, 60, 5), 0, 1, frac, 15)
+    return Case("wide-base", False, MONO, 13.0, MONO_AL, 2, 1, [page], geo, frac)
+
+
+def two_sizes_case(whole):
+    """A batch of two page sizes through decode(): the second page is narrower and shorter, so its grid has fewer slots."""
+    a, = std_pages(whole, 21)
+    b = std_pages(whole, 22)[0][: (44 if whole else 90), : (50 if whole else 80)].copy()
+    c = std_case(whole, 2, 1)
+    return c._replace(name="two-sizes-" + ("whole" if whole else "base"), pages=[a, b, a.copy()])
+
+
+def strip_bytes(page_w, x, width, line_height):
+    w = min(width, page_w - min(x, page_w))
+    return ((w + 7) // 4 + 2) * 4 * line_height
+
+
+def expected(case):
+    """The model's [[(yc_i, Baseline or WholeBaseline)] per page] of a case."""
+    m = model(case.font, case.size, case.alphabet, case.y_bits)
+    return [LF.search_image(m, p, *case.geo, case.n, *case.frac, whole=case.whole) for p in case.pages]

@@ -64,6 +64,16 @@ With --whole-line --whole-baseline N [--y-bits B], also the whole-line decode un
   wbase_wall_ms_per_batch     median host time of one such decode call, pens, costs and offsets read back
   wbase_lines_changed         lines of the batch the mode decodes differently from the whole-line run
   wbase_lines_offset          lines of the batch that took an offset other than 0
+With --line-frac Y,A beside --baseline-search or --whole-line --whole-baseline, the pages are drawn on the fractional line
+grid y + Y/64 + i * (line_advance + A/64) px (every glyph rasterised at its line's sub-pixel row), every section above runs
+on those pages, and the mode in force is also timed with the grid on (LineDecoder.decode(..., y_frac=Y,
+line_advance_frac=A)), in runs that alternate with the same mode at the same radius on the whole-pixel grid:
+  frac_device_ms_per_batch    median device time of the batch's kernels with the grid on (the same 3 launches)
+  frac_off_device_ms          median device time of the whole-pixel runs in between
+  frac_over_off               the ratio of the two (the candidate count is the same)
+  frac_wall_ms_per_batch      median host time of one decode call with the grid on
+  frac_lines, frac_off_lines  non-blank lines found on either grid
+  frac_lines_changed          lines of the batch whose text differs between the two grids (by position in the page)
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -86,7 +96,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from font_ocr_amd import FOCR_DEFAULT_ALPHABET, DecodeFont, LineDecoder  # noqa: E402
-from font_ocr_amd.decoder import render_text  # noqa: E402
+from font_ocr_amd.decoder import raster_glyph, render_text  # noqa: E402
 
 FONT = os.path.join(ROOT, "tests", "golden", "DejaVuSansMono.ttf")
 
@@ -102,6 +112,35 @@ def synth(n_pages, seed, W=608, H=720, x=45, y=39, n_lines=40, advance=15, size=
             ly = y + i * advance
             hh, ww = min(c.shape[0], H - ly), min(c.shape[1], W - x)
             pages[p, ly: ly + hh, x: x + ww] = np.minimum(pages[p, ly: ly + hh, x: x + ww], 255 - c[:hh, :ww])
+    return pages
+
+
+def synth_frac(n_pages, seed, frac, W=608, H=720, x=45, y=39, n_lines=40, advance=15, size=13.0, font=FONT):
+    """synth()'s pages on the fractional grid frac = (y_frac, advance_frac): line i's top at
+    Y_i = 64 * y + y_frac + i * (64 * advance + advance_frac) in 1/64 px, every glyph rasterised by FreeType on the decoder's
+    own line canvas at the row Y_i >> 6 with the vertical translation origin_y + (Y_i & 63) / 64."""
+    rng = np.random.default_rng(seed)
+    ink = FOCR_DEFAULT_ALPHABET.replace(" ", "")
+    f = DecodeFont(font, size, FOCR_DEFAULT_ALPHABET)
+    inc, (ox, oy) = f.increments(), f.origin
+    f.close()
+    pages = np.full((n_pages, H, W), 255, dtype=np.uint8)
+    g = np.zeros((int(size) + 8, 2 * int(size) + 8), dtype=np.uint8)
+    for p in range(n_pages):
+        for i in range(n_lines):
+            words = [''.join(rng.choice(list(ink), int(rng.integers(2, 10)))) for _ in range(12)]
+            Y = 64 * y + frac[0] + i * (64 * advance + frac[1])
+            ly, pen = Y >> 6, np.float32(0)
+            for ch in " ".join(words)[:68]:
+                col = int(pen)
+                if ch != " ":
+                    g[:] = 0
+                    raster_glyph(font, size, ch, np.float32(ox + np.float32(4) + (pen - np.float32(col))), np.float32(oy + np.float32((Y & 63) / 64.0)), g)
+                    x0 = x + col - 4
+                    hh, ww = min(g.shape[0], H - ly), min(g.shape[1], W - x0)
+                    if hh > 0 and ww > 0 and x0 >= 0:
+                        pages[p, ly: ly + hh, x0: x0 + ww] = np.minimum(pages[p, ly: ly + hh, x0: x0 + ww], 255 - g[:hh, :ww])
+                pen = np.float32(pen + inc[FOCR_DEFAULT_ALPHABET.index(ch)])
     return pages
 
 
@@ -122,6 +161,8 @@ def main():
     ap.add_argument("--whole-baseline", type=int, default=0, metavar="N",
                     help="with --whole-line: also time the whole-line decode under the baseline candidates of N steps either way")
     ap.add_argument("--y-bits", type=int, default=0, metavar="B", help="with --baseline-search or --whole-baseline: steps of 2^-B px")
+    ap.add_argument("--line-frac", default=None, metavar="Y,A",
+                    help="with --baseline-search or --whole-baseline: draw the pages on the fractional line grid and also time the mode with the grid on")
     ap.add_argument("--font", default=FONT, metavar="PATH", help="the font of the pages and of the decoder [DejaVu Sans Mono]")
     a = ap.parse_args()
     if a.margins and not a.whole_line:
@@ -132,7 +173,17 @@ def main():
         ap.error("--whole-baseline needs --whole-line")
     if a.y_bits and not (a.baseline_search or a.whole_baseline):
         ap.error("--y-bits needs --baseline-search or --whole-baseline")
-    pages = synth(a.pages, a.seed, font=a.font)
+    frac = None
+    if a.line_frac is not None:
+        try:
+            frac = tuple(int(v) for v in a.line_frac.split(","))
+        except ValueError:
+            frac = ()
+        if len(frac) != 2 or not all(0 <= v <= 63 for v in frac):
+            ap.error("--line-frac takes Y,A, each 0 .. 63 (1/64 px)")
+        if not (a.baseline_search or a.whole_baseline):
+            ap.error("--line-frac needs --baseline-search or --whole-baseline")
+    pages = synth_frac(a.pages, a.seed, frac, font=a.font) if frac else synth(a.pages, a.seed, font=a.font)
     geo = (45, 39, 608, 12, 15)
     t0 = time.perf_counter()
     font = DecodeFont(a.font, 13.0, FOCR_DEFAULT_ALPHABET, y_bits=a.y_bits)
@@ -244,6 +295,20 @@ def main():
                 cwall.append((time.perf_counter() - t) * 1e3)
                 cdev.append(dec.last_ms)
             claunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+        if frac:
+            mode = dict(whole_line=True, whole_baseline=a.whole_baseline) if a.whole_baseline else dict(baseline_search=a.baseline_search)
+            on = dict(mode, y_frac=frac[0], line_advance_frac=frac[1])
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, **on)
+            fdev, fwall, fodev = [], [], []
+            for _ in range(a.steps):
+                foff = dec.decode(pages, *geo, **mode)
+                fodev.append(dec.last_ms)
+                t = time.perf_counter()
+                fgot = dec.decode(pages, *geo, **on)
+                fwall.append((time.perf_counter() - t) * 1e3)
+                fdev.append(dec.last_ms)
+            flaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
         if a.test_images:
             for _ in range(a.warmup):
                 dec.test_images(pages, *geo)
@@ -316,6 +381,14 @@ def main():
                     "wbase_device_ms_min": round(float(min(cdev)), 4), "wbase_whole_device_ms": round(cwms, 4),
                     "wbase_over_whole": round(cms / cwms, 3), "wbase_launches": claunches,
                     "wbase_wall_ms_per_batch": round(float(np.median(cwall)), 3), "wbase_lines_changed": changed, "wbase_lines_offset": moved})
+    if frac:
+        fms, foms = float(np.median(fdev)), float(np.median(fodev))
+        changed = sum(ta != tb for pa, pb in zip(foff[0], fgot[0]) for (_, ta), (_, tb) in zip(pa, pb))
+        res.update({"line_frac": list(frac), "frac_mode": "whole_baseline" if a.whole_baseline else "baseline_search",
+                    "frac_radius": a.whole_baseline or a.baseline_search, "y_bits": a.y_bits, "frac_device_ms_per_batch": round(fms, 4),
+                    "frac_device_ms_min": round(float(min(fdev)), 4), "frac_off_device_ms": round(foms, 4), "frac_over_off": round(fms / foms, 4),
+                    "frac_launches": flaunches, "frac_wall_ms_per_batch": round(float(np.median(fwall)), 3),
+                    "frac_lines": sum(len(pg) for pg in fgot[0]), "frac_off_lines": sum(len(pg) for pg in foff[0]), "frac_lines_changed": changed})
     if a.test_images:
         tms = float(np.median(tdev))
         res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
