@@ -393,28 +393,26 @@ int main(int argc, char **argv) {
 
     focr_decoder_t *dec = nullptr;
     if (focr_decoder_create(0, &dec) != 0) die(std::string("no usable GPU: ") + focr_decoder_last_error(nullptr), 1);
-    if (focr_decoder_set_font(dec, &font) != 0) die(std::string("focr_decoder_set_font: ") + focr_decoder_last_error(dec), 1);
+    // a setter that refuses ends the program: "<setter>: <the library's message>", exit code 1
+    const auto set = [&](const char *setter, int rc) { if (rc != 0) die(std::string(setter) + ": " + focr_decoder_last_error(dec), 1); };
+    set("focr_decoder_set_font", focr_decoder_set_font(dec, &font));
     if (args.have_verify) {
         focr_verify_font_t vfont{};
         if (focr_verify_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), &vfont, err,
                                    sizeof err) != 0)
             die(std::string("verify font: ") + err);
-        if (focr_decoder_set_verify_font(dec, &vfont) != 0) die(std::string("focr_decoder_set_verify_font: ") + focr_decoder_last_error(dec), 1);
+        set("focr_decoder_set_verify_font", focr_decoder_set_verify_font(dec, &vfont));
         focr_verify_font_free(&vfont);
     }
-    if (csv && focr_decoder_set_scores(dec, 1) != 0) die(std::string("focr_decoder_set_scores: ") + focr_decoder_last_error(dec), 1);
-    if (focr_decoder_set_pen_search(dec, args.pen_search) != 0) die(std::string("focr_decoder_set_pen_search: ") + focr_decoder_last_error(dec), 1);
-    if (focr_decoder_set_whole_line(dec, args.whole_line) != 0) die(std::string("focr_decoder_set_whole_line: ") + focr_decoder_last_error(dec), 1);
-    if (focr_decoder_set_whole_slack(dec, args.pen_slack) != 0) die(std::string("focr_decoder_set_whole_slack: ") + focr_decoder_last_error(dec), 1);
-    if (mcsv && focr_decoder_set_whole_margins(dec, 1) != 0) die(std::string("focr_decoder_set_whole_margins: ") + focr_decoder_last_error(dec), 1);
-    if (y_fonts && focr_decoder_set_baseline_fonts(dec, fonts.data(), args.y_bits) != 0)
-        die(std::string("focr_decoder_set_baseline_fonts: ") + focr_decoder_last_error(dec), 1);
-    if (focr_decoder_set_baseline_search(dec, args.baseline_search ? args.y_bits : 0, args.baseline_search) != 0)
-        die(std::string("focr_decoder_set_baseline_search: ") + focr_decoder_last_error(dec), 1);
-    if (focr_decoder_set_whole_baseline(dec, args.whole_baseline ? args.y_bits : 0, args.whole_baseline) != 0)
-        die(std::string("focr_decoder_set_whole_baseline: ") + focr_decoder_last_error(dec), 1);
-    if (focr_decoder_set_line_frac(dec, args.y_frac, args.line_advance_frac) != 0)
-        die(std::string("focr_decoder_set_line_frac: ") + focr_decoder_last_error(dec), 1);
+    if (csv) set("focr_decoder_set_scores", focr_decoder_set_scores(dec, 1));
+    set("focr_decoder_set_pen_search", focr_decoder_set_pen_search(dec, args.pen_search));
+    set("focr_decoder_set_whole_line", focr_decoder_set_whole_line(dec, args.whole_line));
+    set("focr_decoder_set_whole_slack", focr_decoder_set_whole_slack(dec, args.pen_slack));
+    if (mcsv) set("focr_decoder_set_whole_margins", focr_decoder_set_whole_margins(dec, 1));
+    if (y_fonts) set("focr_decoder_set_baseline_fonts", focr_decoder_set_baseline_fonts(dec, fonts.data(), args.y_bits));
+    set("focr_decoder_set_baseline_search", focr_decoder_set_baseline_search(dec, args.baseline_search ? args.y_bits : 0, args.baseline_search));
+    set("focr_decoder_set_whole_baseline", focr_decoder_set_whole_baseline(dec, args.whole_baseline ? args.y_bits : 0, args.whole_baseline));
+    set("focr_decoder_set_line_frac", focr_decoder_set_line_frac(dec, args.y_frac, args.line_advance_frac));
     const bool csv_offsets = csv && args.pen_search > 0;
 
     std::vector<std::vector<Line>> lines(n_img);

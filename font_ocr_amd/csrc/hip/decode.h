@@ -1,6 +1,15 @@
-// decode.h — what the files of the `focr` decoder share (decode.hip: font and line decoder; decode_whole.hip: its whole-line
-// decode, decode_baseline.hip: its baseline search, and decode_whole_baseline.hip: the two together, with decode_line.h between the four; decode_images.hip: the verify and --test images; decode_line_frac.hip: the fractional line grid's setter and compose kernel): the batch geometry, both line grids, the device tables, the tile frame of the compose kernels (ncc_images.hip
-// is its third user), the blank test's crop, the decoder itself, and the host plumbing every entry point repeats (errors, stages, staging, refusals).
+// decode.h — what the files of the `focr` decoder share:
+//   decode.hip                 the font, the settings' resolution into one RunMode, the run in its steps, prepass, compaction,
+//                              the pen loop and its search
+//   decode_whole.hip           the whole-line decode, with margins or a pen slack
+//   decode_baseline.hip        the baseline search, its y-phase fonts and the verify's compose after a baseline run
+//   decode_whole_baseline.hip  the whole-line decode under every baseline candidate
+//   decode_line_frac.hip       the fractional line grid's setter and the verify's compose on that grid
+//   decode_images.hip          the verify and --test images
+// (decode_line.h lies between the first four.)  Here: the batch geometry, both line grids, the device tables, the tile frame of
+// the compose kernels (ncc_images.hip is its third user), the blank test's crop, the settings (Modes), what a run resolves
+// them to (RunMode), what the last run left (LastRun), the decoder itself, and the host plumbing every entry point repeats
+// (errors, stages, staging, refusals).
 #pragma once
 
 #include <algorithm>
@@ -216,6 +225,51 @@ __device__ __forceinline__ void tile_add_sum(uint32_t acc, uint32_t *part, unsig
     __syncthreads();
 }
 
+// ---- settings, the mode they resolve to, and the last run ------------------------------------------------------------
+
+struct BaseSearch {
+    uint32_t bits = 0, n = 0;  // y_bits and radius; n == 0 is off
+};
+
+// What the setters write, as they were given; nothing reads them but resolve_modes (decode.hip), once per run.
+struct Modes {
+    bool scores = false;      // focr_decoder_set_scores
+    uint32_t pen_search = 0;  // focr_decoder_set_pen_search
+    bool whole = false;       // focr_decoder_set_whole_line
+    bool margins = false;     // focr_decoder_set_whole_margins
+    uint32_t slack = 0;       // focr_decoder_set_whole_slack
+    BaseSearch base, wbase;   // focr_decoder_set_baseline_search, focr_decoder_set_whole_baseline
+    LineFrac frac{0, 0};      // focr_decoder_set_line_frac: (0, 0) is off
+    uint32_t whole_grid = 0, base_grid = 0;  // focr_decoder_debug_set_*_grid: at most this many workgroups (0: no limit of the test's)
+};
+
+// The third launch of a run (DESIGN.md has the table: kernel, buffers written, getters that answer).
+enum class Kind { pen_loop, pen_search, whole, whole_margins, whole_slack, whole_baseline, baseline };
+
+// The settings of one run, resolved: every step of the run, and the verify after it, asks this and nothing else.
+struct RunMode {
+    Kind kind = Kind::pen_loop;
+    bool scores = false;  // d_term, d_runner_term, d_runner and d_base are written (pen_loop and pen_search only)
+    uint32_t radius = 0;  // what the kind's kernel takes: the pen search's, the pen slack's or the baseline candidates' radius
+    uint32_t bits = 0;    // the baseline kinds: d_base_q is in steps of 2^-bits px
+    LineFrac frac{0, 0};  // the line grid in force ((0, 0) except under the baseline kinds)
+    uint32_t grid = 0;    // the debug limit on the kind's workgroups (the whole and baseline kinds)
+    bool whole() const { return kind == Kind::whole || kind == Kind::whole_margins || kind == Kind::whole_slack || kind == Kind::whole_baseline; }  // d_pens, d_cost
+    bool margins() const { return kind == Kind::whole_margins; }                                 // d_mterm, d_mrunner, d_margin
+    bool offsets() const { return kind == Kind::pen_search || kind == Kind::whole_slack; }       // d_pen holds offsets
+    bool base_q() const { return kind == Kind::baseline || kind == Kind::whole_baseline; }       // d_base_q (and d_base_cost: baseline)
+};
+
+// What the last successful run left for the getters and the verify.
+struct LastRun {
+    bool ok = false;  // a run succeeded since the font was set
+    RunMode mode;
+    Geometry g{};
+    size_t n_pages = 0;
+    uint32_t x_start = 0;
+    const uint8_t *src = nullptr;  // its pages on the device
+};
+
 struct Stage {  // the kernels of one entry point's last call: device events around them, their time and their number
     hipEvent_t begin = nullptr, end = nullptr;
     float ms = 0.f;
@@ -241,81 +295,60 @@ struct focr_decoder {
     focr::DevArray<focr_dec::DevGlyph> d_glyphs;
     focr::DevArray<int2> d_offs;
     focr::DevArray<uint8_t> d_bitmaps;  // dwords (read as uint32_t by the decode kernel, as bytes by the compose kernels)
+    // the settings as the setters wrote them; a run resolves them once (resolve_modes) and reads nothing else of them
+    focr_dec::Modes modes;
     // batch buffers (grown on demand)
     focr::DevArray<uint8_t> d_pages, d_strips;
     focr::DevArray<uint32_t> d_flags, d_work, d_nchars, d_count;
     focr::DevArray<uint16_t> d_chars;
-    // scores (focr_decoder_set_scores): per step beside d_chars, per work-list line beside d_nchars; grown by a run with scores on
-    bool scores_on = false;
+    // scores: per step beside d_chars, per work-list line beside d_nchars; grown by a run with scores on
     focr::DevArray<int32_t> d_term, d_runner_term;
     focr::DevArray<uint16_t> d_runner;
     focr::DevArray<uint64_t> d_base;
-    // pen search (focr_decoder_set_pen_search): the chosen offset of every step beside d_chars; grown by a run with a radius
-    uint32_t pen_search = 0;
+    // pen search: the chosen offset of every step beside d_chars; grown by a run with a radius
     focr::DevArray<int8_t> d_pen;
-    // whole-line decode (focr_decoder_set_whole_line): inc64 per glyph, the workgroups' backpointer scratch, and the pen of
-    // every character beside d_chars and the cost of every work-list line beside d_nchars; grown by a run with the mode on
-    bool whole_on = false;
-    uint32_t whole_grid = 0;  // focr_decoder_debug_set_whole_grid: at most this many workgroups (0: no limit of the test's)
+    // whole-line decode: inc64 per glyph, the workgroups' backpointer scratch, and the pen of every character beside d_chars
+    // and the cost of every work-list line beside d_nchars; grown by a whole-line run
     focr::DevArray<uint32_t> d_inc64, d_pens;
     focr::DevArray<uint16_t> d_back;
     focr::DevArray<int64_t> d_cost;
-    // pen slack of a whole-line run (focr_decoder_set_whole_slack): the workgroups' offset scratch beside d_back; the chosen
-    // offset of every character goes to d_pen, as a search's does; grown by a run with a slack radius
-    uint32_t whole_slack = 0;
+    // pen slack of a whole-line run: the workgroups' offset scratch beside d_back; the chosen offset of every character goes
+    // to d_pen, as a search's does; grown by a run with a slack radius
     focr::DevArray<int8_t> d_woff;
-    // margins of a whole-line run (focr_decoder_set_whole_margins): the workgroups' forward keys in d_back's place, and per
-    // character beside d_chars the term, the runner and the margin; grown by a run with margins on
-    bool margins_on = false;
+    // margins of a whole-line run: the workgroups' forward keys in d_back's place, and per character beside d_chars the term,
+    // the runner and the margin; grown by a run with margins on
     focr::DevArray<uint64_t> d_fwd;
     focr::DevArray<int32_t> d_mterm;
     focr::DevArray<uint16_t> d_mrunner;
     focr::DevArray<int64_t> d_margin;
-    // baseline search (focr_decoder_set_baseline_search): the y-phase tables v >= 1 of the font (set_baseline_fonts; glyph
-    // records and offsets v-major, one bitmap table whose dword offsets the records carry), and per work-list line beside
-    // d_nchars the chosen q and its cost; grown by a run with a radius
-    uint32_t base_bits = 0, base_n = 0;
-    uint32_t base_grid = 0;        // focr_decoder_debug_set_baseline_grid: at most this many workgroups (0: no limit of the test's)
+    // baseline search: the y-phase tables v >= 1 of the font (set_baseline_fonts; glyph records and offsets v-major, one
+    // bitmap table whose dword offsets the records carry), and per work-list line beside d_nchars the chosen q and its cost;
+    // grown by a run with a radius.  The baseline candidates of a whole-line run read the same tables and write the line's q
+    // to d_base_q; their cost is the whole-line run's d_cost
     bool have_base_fonts = false;  // y-phase fonts of font_bits are uploaded for the current font
     uint32_t font_bits = 0, ybitmaps_dw = 0;  // ... and the dwords of their bitmap table
+    uint64_t yterm_bound = 0;      // the largest stride * box_h * 2 * 255^2 of the uploaded y-phase fonts v >= 1 (a term's bound)
     focr::DevArray<focr_dec::DevGlyph> d_yglyphs;
     focr::DevArray<int2> d_yoffs;
     focr::DevArray<uint8_t> d_ybitmaps;
     focr::DevArray<int32_t> d_base_q;
     focr::DevArray<int64_t> d_base_cost;
-    // baseline candidates of a whole-line run (focr_decoder_set_whole_baseline): the programme under every candidate reads
-    // the same y-phase tables and writes the line's q to d_base_q; its cost is the whole-line run's d_cost
-    uint32_t wbase_bits = 0, wbase_n = 0;
-    uint64_t yterm_bound = 0;      // the largest stride * box_h * 2 * 255^2 of the uploaded y-phase fonts v >= 1 (a term's bound)
-    // the fractional line grid of the two baseline modes (focr_decoder_set_line_frac): (0, 0) is off
-    focr_dec::LineFrac line_frac{0, 0};
-    // results of the last run
-    bool have_baselines = false;   // the last successful run searched baselines
-    std::vector<int8_t> base_q;    // beside lines
-    std::vector<int64_t> base_cost;
+    // the last run: what it was (for the getters' refusals and the verify) and its results on the host
+    focr_dec::LastRun last;
     std::vector<focr_decoded_line_t> lines;
     std::vector<uint16_t> chars;
-    bool have_scores = false;  // the last successful run was made with scores on
-    std::vector<focr_char_score_t> char_scores;
-    std::vector<uint64_t> line_base;
     std::vector<int8_t> offsets;  // beside chars: all zero after a run without a search
-    bool have_whole = false;      // the last successful run was a whole-line run
-    std::vector<uint32_t> pens;   // beside chars: each character's pen in 1/64 px
+    std::vector<focr_char_score_t> char_scores;  // beside chars (a scores run)
+    std::vector<uint64_t> line_base;             // beside lines
+    std::vector<uint32_t> pens;   // beside chars: each character's pen in 1/64 px (a whole-line run)
     std::vector<int64_t> line_cost;
-    bool have_margins = false;    // the last successful run was a whole-line run with margins
-    std::vector<focr_char_margin_t> margins;  // beside chars
-    // verify: the table, what the last successful run left for it, buffers
+    std::vector<focr_char_margin_t> margins;  // beside chars (a margins run)
+    std::vector<int8_t> base_q;    // beside lines (a baseline run)
+    std::vector<int64_t> base_cost;
+    // verify: the table, buffers
     uint32_t n_vglyphs = 0, hmax = 0;
     focr::DevArray<focr_dec::VerifyGlyph> d_vglyphs;
     focr::DevArray<focr_dec::VerifyPhase> d_vphases;
-    bool run_ok = false, run_searched = false, run_whole = false;  // the last successful run wrote d_pen / d_pens
-    bool run_base = false;  // ... or d_base_q, in steps of 2^-run_bits px
-    uint32_t run_bits = 0;
-    focr_dec::Geometry run_g{};
-    focr_dec::LineFrac run_frac{0, 0};  // the grid the run used: the verify draws on it
-    size_t run_pages = 0;
-    uint32_t run_x_start = 0;
-    const uint8_t *run_src = nullptr;
     focr::DevArray<focr_dec::VerifyLine> d_vlines;
     focr::DevArray<focr_dec::VerifyRec> d_vrecs;
     focr::DevArray<unsigned long long> d_sums;

@@ -23,8 +23,11 @@
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the
 // order of the sums nor the device changes a choice.  The pen update is one f32 add of the host-computed increment.
 //
+// Which of these a run launches is decided once, by resolve_modes below: the settings become one RunMode (decode.h), with
+// every refusal of a combination, and the run's steps (line_cap, reserve, launch, collect) read that and nothing else.
+//
 // The verify and --test images of a batch are decode_images.hip's; decode.h holds what the decoder's files share, and
-// decode_line.h what this file shares with decode_whole.hip.
+// decode_line.h what this file shares with decode_whole.hip, decode_baseline.hip and decode_whole_baseline.hip.
 #include <cmath>
 #include <cstring>
 
@@ -344,24 +347,6 @@ __global__ __launch_bounds__(SEARCH_THREADS) void line_search_kernel(const uint8
 
 using namespace focr_dec;
 
-namespace {
-
-// What focr_decoder_verify draws from: the successful run's geometry and its pages on the device.
-void remember_run(focr_decoder *dec, const Geometry &g, const uint8_t *d_src, size_t n_pages, uint32_t x_start, bool searched, bool whole) {
-    dec->run_searched = searched;
-    dec->run_whole = dec->have_whole = whole;
-    dec->run_base = dec->base_n != 0 || dec->wbase_n != 0;  // (a run that got here with a radius searched baselines)
-    dec->run_bits = dec->wbase_n ? dec->wbase_bits : dec->base_bits;  // (never both: a baseline search refuses the whole-line decode)
-    dec->run_g = g;
-    dec->run_frac = dec->line_frac;  // (a run that got here with fractions searched baselines)
-    dec->run_pages = n_pages;
-    dec->run_x_start = x_start;
-    dec->run_src = d_src;
-    dec->run_ok = true;
-}
-
-}  // namespace
-
 extern "C" int focr_decoder_create(int device, focr_decoder_t **out) {
     focr_decoder *dec = nullptr;
     if (!out) return dfail(nullptr, "focr_decoder_create: null out");
@@ -397,8 +382,13 @@ extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
 extern "C" const char *focr_decoder_last_error(const focr_decoder_t *dec) { return dec ? dec->err.c_str() : g_dec_err.c_str(); }
 
 extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font_t *font) {
-    if (dec) dec->run_ok = false, dec->have_whole = false, dec->have_margins = false, dec->n_vglyphs = 0;  // the last run and the verify table belong to the previous font
-    if (dec) dec->have_baselines = dec->have_base_fonts = false;  // and so do the y-phase fonts (released below, once the device is selected)
+    if (dec) {  // the last run, the verify table and the y-phase fonts (released below, once the device is selected) belong to the previous font
+        const bool scores = dec->last.mode.scores;  // ... but focr_decoder_get_scores has always gone on answering after a set_font: kept as it was
+        dec->last = LastRun{};
+        dec->last.mode.scores = scores;
+        dec->n_vglyphs = 0;
+        dec->have_base_fonts = false;
+    }
     if (!dec || !font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_font: bad arguments");
     if (font->n_glyphs > 65535) return dfail(dec, "focr_decoder_set_font: more than 65535 glyphs");
     if (font->bitmaps_len % 4 || font->bitmaps_len / 4 > 0xffffffffull) return dfail(dec, "focr_decoder_set_font: bad bitmap table");
@@ -442,11 +432,13 @@ extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font
     return 0;
 }
 
+// ---- a run in its steps: resolve the settings, geometry and cap, reserve, the third launch, collect ------------------
+
 namespace {
 
 // A run starts: the results of the last one are gone, whatever becomes of this one.
 void clear_results(focr_decoder *dec) {
-    dec->run_ok = dec->have_scores = dec->have_whole = dec->have_margins = dec->have_baselines = false;
+    dec->last = LastRun{};
     dec->base_q.clear();
     dec->base_cost.clear();
     dec->lines.clear();
@@ -459,6 +451,151 @@ void clear_results(focr_decoder *dec) {
     dec->margins.clear();
     dec->run.ms = 0.f;
     dec->run.launches = 0;
+}
+
+// What both baseline kinds need of the font, each refused in the kind's own words: the y-phase fonts of its y_bits, and an
+// origin_y that is a whole number.
+int baseline_font(focr_decoder *dec, uint32_t bits, const std::string &no_fonts, const std::string &bent_origin) {
+    if (bits && !(dec->have_base_fonts && dec->font_bits == bits)) return dfail(dec, no_fonts);
+    const float oy = dec->origin_y;
+    if (!(oy >= 0.f) || oy > 65536.f || oy != (float)(int)oy) return dfail(dec, bent_origin);
+    return 0;
+}
+
+// The settings as one RunMode, or the refusal of their combination (include/focr_decode.h): every refusal that depends on
+// the settings, the font and the y-phase fonts alone, before anything is launched, in the order a caller has come to see
+// them.  What depends on the batch's geometry follows in the run (batch_geometry, whole_plan).
+int resolve_modes(focr_decoder *dec, RunMode *out) {
+    const Modes &m = dec->modes;
+    const bool baseline = m.base.n != 0, candidates = m.wbase.n != 0;
+    if (baseline) {
+        const std::string pre = "focr_decoder_run: a baseline search (focr_decoder_set_baseline_search) does not go with ";
+        if (m.scores) return dfail(dec, pre + "scores (focr_decoder_set_scores): a runner-up has no definition across candidates yet");
+        if (m.pen_search) return dfail(dec, pre + "a pen search (focr_decoder_set_pen_search) yet");
+        if (m.whole) return dfail(dec, pre + "the whole-line decode (focr_decoder_set_whole_line) yet");
+        if (m.margins) return dfail(dec, pre + "margins (focr_decoder_set_whole_margins) yet");
+        if (m.slack) return dfail(dec, pre + "a pen slack (focr_decoder_set_whole_slack) yet");
+        if (baseline_font(dec, m.base.bits,
+                          "focr_decoder_run: a baseline search with y_bits > 0 (focr_decoder_set_baseline_search) needs the y-phase fonts of that "
+                          "y_bits (focr_decoder_set_baseline_fonts)",
+                          "focr_decoder_run: a baseline search (focr_decoder_set_baseline_search) needs an origin_y that is a whole number >= 0"))
+            return 1;
+    }
+    if (candidates) {  // a whole-line run under every baseline candidate
+        const std::string pre = "focr_decoder_run: baseline candidates of a whole-line run (focr_decoder_set_whole_baseline) ";
+        if (!m.whole)
+            return dfail(dec, pre + "with the whole-line decode off (focr_decoder_set_whole_line; the pen loop's search is focr_decoder_set_baseline_search)");
+        if (m.margins) return dfail(dec, pre + "do not go with margins (focr_decoder_set_whole_margins) yet");
+        if (m.slack) return dfail(dec, pre + "do not go with a pen slack (focr_decoder_set_whole_slack) yet");
+        if (baseline_font(dec, m.wbase.bits, pre + "with y_bits > 0 need the y-phase fonts of that y_bits (focr_decoder_set_baseline_fonts)",
+                          pre + "need an origin_y that is a whole number >= 0"))
+            return 1;
+    }
+    if (m.margins && !m.whole)
+        return dfail(dec, "focr_decoder_run: margins on with the whole-line decode off (focr_decoder_set_whole_margins needs focr_decoder_set_whole_line)");
+    if (m.slack && !m.whole)
+        return dfail(dec, "focr_decoder_run: pen slack on with the whole-line decode off (focr_decoder_set_whole_slack needs focr_decoder_set_whole_line)");
+    if (m.slack && m.margins)
+        return dfail(dec, "focr_decoder_run: pen slack on with margins on (focr_decoder_set_whole_slack does not go with focr_decoder_set_whole_margins yet)");
+    if ((float)m.pen_search * 0.015625f > dec->min_inc * 0.5f)
+        return dfail(dec, "focr_decoder_run: the pen search radius is more than half the smallest pen increment (the pen could crawl)");
+    if (m.frac.on() && !baseline && !candidates)
+        return dfail(dec, "focr_decoder_run: a fractional line grid (focr_decoder_set_line_frac) needs a baseline search (focr_decoder_set_baseline_search) or "
+                          "baseline candidates of a whole-line run (focr_decoder_set_whole_baseline) with a radius >= 1: no other mode renders at a "
+                          "sub-pixel row yet");
+    if (m.whole && m.scores) return dfail(dec, "focr_decoder_run: whole-line decode with scores on (a runner-up has no definition under the dynamic programme)");
+    if (m.whole && m.pen_search) return dfail(dec, "focr_decoder_run: whole-line decode with a pen search radius (the dynamic programme does not search offsets)");
+    RunMode r;
+    r.frac = m.frac;
+    if (baseline) r.kind = Kind::baseline, r.radius = m.base.n, r.bits = m.base.bits, r.grid = m.base_grid;
+    else if (candidates) r.kind = Kind::whole_baseline, r.radius = m.wbase.n, r.bits = m.wbase.bits, r.grid = m.whole_grid;
+    else if (m.whole) r.kind = m.margins ? Kind::whole_margins : m.slack ? Kind::whole_slack : Kind::whole, r.radius = m.slack, r.grid = m.whole_grid;
+    else r.kind = m.pen_search ? Kind::pen_search : Kind::pen_loop, r.radius = m.pen_search, r.scores = m.scores;
+    *out = r;
+    return 0;
+}
+
+// The strip's stride and the characters per line at most, into g.
+int line_cap(focr_decoder *dec, const RunMode &mode, const WholePlan &plan, Geometry *g) {
+    g->stride = ((g->w + PAD + 3) / 4 + 2) * 4;
+    // characters per line at most: the pen moves at least min_inc per step, and f32 rounding is monotone, so the
+    // sequence 0, min_inc, ... reaches w no earlier than any pen does.  With a pen search a step is two f32 adds,
+    // pen' = (pen + j / 64) + inc with j / 64 >= -reach (exact) and inc >= min_inc; an f32 add is monotone in each
+    // operand, so by induction the sequence q' = (q - reach) + min_inc from 0 stays at or below every pen and reaches w
+    // no earlier.  It does advance: reach <= min_inc / 2 (resolve_modes), so a step gains min_inc / 2 up to rounding,
+    // and one that stalls in f32 runs into the step limit below.  (Dropped candidates only remove choices.)
+    const bool search = mode.kind == Kind::pen_search;
+    const float reach = search ? (float)mode.radius * 0.015625f : 0.f;  // exact
+    float p = 0.f;
+    uint32_t steps = 0;
+    while (p < (float)g->w) {
+        p = search ? (p - reach) + dec->min_inc : p + dec->min_inc;
+        if (++steps > (1u << 20)) return dfail(dec, "focr_decoder_run: the pen advance is too small for the line width");
+    }
+    g->cap = mode.whole() ? plan.cap : std::max<uint32_t>(steps, 1);
+    return 0;
+}
+
+int reserve(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan) {
+    const size_t total = g.total, n_all = (size_t)g.cap * total;
+    DEC_GROW(dec->d_strips, (size_t)g.stride * g.line_height * total);
+    DEC_GROW(dec->d_flags, total);
+    DEC_GROW(dec->d_work, total);
+    DEC_GROW(dec->d_nchars, total);
+    DEC_GROW(dec->d_count, 1);
+    DEC_GROW(dec->d_chars, n_all);
+    if (mode.scores) {
+        DEC_GROW(dec->d_term, n_all);
+        DEC_GROW(dec->d_runner_term, n_all);
+        DEC_GROW(dec->d_runner, n_all);
+        DEC_GROW(dec->d_base, total);
+    }
+    if (mode.offsets()) DEC_GROW(dec->d_pen, n_all);
+    if (mode.whole()) return whole_reserve(dec, mode, g, plan);
+    return mode.kind == Kind::baseline ? baseline_reserve(dec, g) : 0;
+}
+
+// The pen loop or its search as the third launch.
+void pen_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, size_t strip_bytes) {
+    const bool scores = mode.scores;
+    const ScoreOut so{dec->d_term, dec->d_runner_term, dec->d_runner, dec->d_base};  // null arrays with scores off: never touched
+    if (mode.kind == Kind::pen_search) {  // the strip shares LDS with the reduction pairs, so it stays in LDS up to that much less
+        const bool lds = strip_bytes + SEARCH_RED_BYTES <= LDS_STRIP_MAX;
+        const auto search = lds ? (scores ? line_search_kernel<true, true> : line_search_kernel<true, false>)
+                                : (scores ? line_search_kernel<false, true> : line_search_kernel<false, false>);
+        search<<<g.total, SEARCH_THREADS, SEARCH_RED_BYTES + (lds ? strip_bytes : 0), dec->stream>>>(
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs,
+            dec->origin_x, mode.radius, dec->d_nchars, dec->d_chars, dec->d_pen, so);
+    } else {
+        const auto decode = strip_bytes <= LDS_STRIP_MAX ? (scores ? line_decode_kernel<true, true> : line_decode_kernel<true, false>)
+                                                         : (scores ? line_decode_kernel<false, true> : line_decode_kernel<false, false>);
+        decode<<<g.total, 64, strip_bytes <= LDS_STRIP_MAX ? strip_bytes : 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs,
+                                                                                           dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs,
+                                                                                           dec->origin_x, dec->d_nchars, dec->d_chars, so);
+    }
+}
+
+// The run's three launches between its two events.
+int launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan, const uint8_t *d_src) {
+    const size_t strip_bytes = (size_t)g.stride * g.line_height;
+    DEC_CHECK(hipEventRecord(dec->run.begin, dec->stream));
+    if (mode.frac.on()) line_prepass_frac_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, mode.frac, dec->d_strips, dec->d_flags);
+    else line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
+    DEC_CHECK(hipGetLastError());
+    line_compact_kernel<<<1, COMPACT_THREADS, 0, dec->stream>>>(dec->d_flags, g.total, dec->d_work, dec->d_count);
+    DEC_CHECK(hipGetLastError());
+    switch (mode.kind) {
+    case Kind::pen_loop:
+    case Kind::pen_search: pen_launch(dec, mode, g, strip_bytes); break;
+    case Kind::whole:
+    case Kind::whole_margins:
+    case Kind::whole_slack: whole_launch(dec, mode, g, plan, strip_bytes); break;
+    case Kind::whole_baseline: whole_baseline_launch(dec, mode, g, plan, strip_bytes); break;
+    case Kind::baseline: baseline_launch(dec, mode, g, strip_bytes); break;
+    }
+    DEC_CHECK(hipGetLastError());
+    DEC_CHECK(hipEventRecord(dec->run.end, dec->stream));
+    return 0;
 }
 
 // The first n elements of a device array into v, queued on the decoder's stream.
@@ -475,6 +612,69 @@ void append_line(std::vector<T> &to, const std::vector<T> &all, size_t k, uint32
     to.insert(to.end(), all.begin() + k * cap, all.begin() + k * cap + n);
 }
 
+// What the kernels wrote, read back and laid out line by line in the decoder's result vectors.
+int collect(focr_decoder *dec, const RunMode &mode, const Geometry &g) {
+    const size_t total = g.total, n_all = (size_t)g.cap * total;
+    const bool baseline = mode.kind == Kind::baseline;
+    std::vector<uint32_t> count, work, nch, wpens;
+    std::vector<uint16_t> all, mrunner, runner;
+    std::vector<int8_t> pen;
+    std::vector<int64_t> wcost, mmargin, bcost;
+    std::vector<int32_t> bq, mterm, term, runner_term;
+    std::vector<uint64_t> base;
+    if (read_back(dec, count, dec->d_count.p, 1) || read_back(dec, work, dec->d_work.p, total) || read_back(dec, nch, dec->d_nchars.p, total) ||
+        read_back(dec, all, dec->d_chars.p, n_all))
+        return 1;
+    if (mode.offsets() && read_back(dec, pen, dec->d_pen.p, n_all)) return 1;
+    if (mode.base_q() && read_back(dec, bq, dec->d_base_q.p, total)) return 1;
+    if (baseline && read_back(dec, bcost, dec->d_base_cost.p, total)) return 1;  // under the whole-line decode the cost is that run's
+    if (mode.whole() && (read_back(dec, wpens, dec->d_pens.p, n_all) || read_back(dec, wcost, dec->d_cost.p, total))) return 1;
+    if (mode.margins() && (read_back(dec, mterm, dec->d_mterm.p, n_all) || read_back(dec, mrunner, dec->d_mrunner.p, n_all) || read_back(dec, mmargin, dec->d_margin.p, n_all)))
+        return 1;
+    if (mode.scores && (read_back(dec, term, dec->d_term.p, n_all) || read_back(dec, runner_term, dec->d_runner_term.p, n_all) ||
+                        read_back(dec, runner, dec->d_runner.p, n_all) || read_back(dec, base, dec->d_base.p, total)))
+        return 1;
+    DEC_CHECK(hipStreamSynchronize(dec->stream));
+    DEC_CHECK(hipEventElapsedTime(&dec->run.ms, dec->run.begin, dec->run.end));
+    dec->run.launches = 3;
+    if (count[0] > total) return dfail(dec, "focr_decoder_run: inconsistent line count from the device");
+    // q = c_i + offset, 0 <= c_i <= 2^B on the fractional grid and 0 off it
+    const int q_hi = (int)FOCR_BASELINE_MAX + (mode.frac.on() ? 1 << mode.bits : 0);
+    dec->lines.resize(count[0]);
+    for (uint32_t k = 0; k < count[0]; k++) {
+        const uint32_t slot = work[k], n = nch[k];
+        if (slot >= total || n > g.cap) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
+        focr_decoded_line_t &l = dec->lines[k];
+        l.page = slot / g.n_slots;
+        l.y = (uint32_t)((mode.frac.top(g) + (uint64_t)(slot % g.n_slots) * mode.frac.step(g)) >> 6);  // yc_i; y_start + i * line_advance off the fractional grid
+        l.first = dec->chars.size();
+        l.n_chars = n;
+        l.pad = 0;
+        append_line(dec->chars, all, k, g.cap, n);
+        if (mode.offsets()) append_line(dec->offsets, pen, k, g.cap, n);
+        if (mode.base_q()) {
+            if (bq[k] < -(int)FOCR_BASELINE_MAX || bq[k] > q_hi) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
+            dec->base_q.push_back((int8_t)bq[k]);
+            dec->base_cost.push_back(baseline ? bcost[k] : wcost[k]);
+        }
+        if (mode.whole()) {
+            append_line(dec->pens, wpens, k, g.cap, n);
+            dec->line_cost.push_back(wcost[k]);
+        }
+        for (size_t at = (size_t)k * g.cap; mode.margins() && at < (size_t)k * g.cap + n; at++)
+            dec->margins.push_back(focr_char_margin_t{mterm[at], mrunner[at], 0, mmargin[at]});
+        if (!mode.scores) continue;
+        dec->line_base.push_back(base[k]);
+        for (size_t at = (size_t)k * g.cap; at < (size_t)k * g.cap + n; at++) {  // the reference's score: sum r^2 plus the footprint term
+            focr_char_score_t c{(int64_t)base[k] + term[at], (int64_t)base[k] + runner_term[at], runner[at], {0, 0, 0}};
+            if (dec->n_glyphs == 1) c.runner_score = INT64_MAX, c.runner = 0xffff;
+            dec->char_scores.push_back(c);
+        }
+    }
+    if (!mode.offsets()) dec->offsets.assign(dec->chars.size(), 0);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int on_device, size_t n_pages, size_t page_w, size_t page_h,
@@ -483,173 +683,61 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     clear_results(dec);
     if (!dec->n_glyphs) return dfail(dec, "focr_decoder_run: no font (focr_decoder_set_font)");
     if (n_pages && !pages) return dfail(dec, "focr_decoder_run: null pages");
-    const bool baseline = dec->base_n != 0;
-    if (baseline && baseline_plan(dec)) return 1;  // the refusals of include/focr_decode.h, before anything is launched
-    const bool candidates = dec->wbase_n != 0;     // a whole-line run under every baseline candidate
-    if (candidates && whole_baseline_plan(dec)) return 1;
-    if (dec->margins_on && !dec->whole_on)
-        return dfail(dec, "focr_decoder_run: margins on with the whole-line decode off (focr_decoder_set_whole_margins needs focr_decoder_set_whole_line)");
-    const uint32_t slack = dec->whole_slack;
-    if (slack && !dec->whole_on)
-        return dfail(dec, "focr_decoder_run: pen slack on with the whole-line decode off (focr_decoder_set_whole_slack needs focr_decoder_set_whole_line)");
-    if (slack && dec->margins_on)
-        return dfail(dec, "focr_decoder_run: pen slack on with margins on (focr_decoder_set_whole_slack does not go with focr_decoder_set_whole_margins yet)");
-    const uint32_t radius = dec->pen_search;
-    const float reach = (float)radius * 0.015625f;  // exact
-    if (reach > dec->min_inc * 0.5f)
-        return dfail(dec, "focr_decoder_run: the pen search radius is more than half the smallest pen increment (the pen could crawl)");
-    const LineFrac fr = dec->line_frac;
-    if (fr.on() && !baseline && !candidates)
-        return dfail(dec, "focr_decoder_run: a fractional line grid (focr_decoder_set_line_frac) needs a baseline search (focr_decoder_set_baseline_search) or "
-                          "baseline candidates of a whole-line run (focr_decoder_set_whole_baseline) with a radius >= 1: no other mode renders at a "
-                          "sub-pixel row yet");
+    RunMode mode;
+    if (resolve_modes(dec, &mode)) return 1;
     Geometry g{};
-    if (batch_geometry(dec, "focr_decoder_run", n_pages, page_w, page_h, x_start, y_start, width, line_height, line_advance, &g, fr)) return 1;
+    if (batch_geometry(dec, "focr_decoder_run", n_pages, page_w, page_h, x_start, y_start, width, line_height, line_advance, &g, mode.frac)) return 1;
     DEC_CHECK(hipSetDevice(dec->device));
     const uint8_t *d_src = nullptr;
     if (stage_in(dec, dec->d_pages, pages, on_device, page_w * page_h * n_pages, &d_src)) return 1;
-    const size_t total = g.total;
-    const bool scores = dec->scores_on, whole = dec->whole_on, margins = dec->margins_on;
     WholePlan plan;
-    if (whole && whole_plan(dec, g, &plan)) return 1;  // the refusals of include/focr_decode.h, before anything is launched
-    if (total == 0) {  // nothing to decode and nothing launched; a verify still draws the pages
+    if (mode.whole() && whole_plan(dec, mode, g, &plan)) return 1;  // the font and width refusals of include/focr_decode.h, before anything is launched
+    if (g.total == 0) {  // nothing to decode and nothing launched; a verify still draws the pages
         DEC_CHECK(hipStreamSynchronize(dec->stream));
-        remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
-        dec->have_scores = scores;
-        dec->have_margins = margins;
-        dec->have_baselines = baseline || candidates;
-        return 0;
+    } else if (line_cap(dec, mode, plan, &g) || reserve(dec, mode, g, plan) || launch(dec, mode, g, plan, d_src) || collect(dec, mode, g)) {
+        return 1;
     }
-    g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;
-    // characters per line at most: the pen moves at least min_inc per step, and f32 rounding is monotone, so the
-    // sequence 0, min_inc, ... reaches w no earlier than any pen does.  With a pen search a step is two f32 adds,
-    // pen' = (pen + j / 64) + inc with j / 64 >= -reach (exact) and inc >= min_inc; an f32 add is monotone in each
-    // operand, so by induction the sequence q' = (q - reach) + min_inc from 0 stays at or below every pen and reaches w
-    // no earlier.  It does advance: reach <= min_inc / 2 (checked above), so a step gains min_inc / 2 up to rounding,
-    // and one that stalls in f32 runs into the step limit below.  (Dropped candidates only remove choices.)
-    {
-        float p = 0.f;
-        uint32_t steps = 0;
-        while (p < (float)g.w) {
-            p = radius ? (p - reach) + dec->min_inc : p + dec->min_inc;
-            if (++steps > (1u << 20)) return dfail(dec, "focr_decoder_run: the pen advance is too small for the line width");
-        }
-        g.cap = whole ? plan.cap : std::max<uint32_t>(steps, 1);
-    }
-    const size_t strip_bytes = (size_t)g.stride * g.line_height, n_all = (size_t)g.cap * total;
-    DEC_GROW(dec->d_strips, strip_bytes * total);
-    DEC_GROW(dec->d_flags, total);
-    DEC_GROW(dec->d_work, total);
-    DEC_GROW(dec->d_nchars, total);
-    DEC_GROW(dec->d_count, 1);
-    DEC_GROW(dec->d_chars, n_all);
-    if (scores) {
-        DEC_GROW(dec->d_term, n_all);
-        DEC_GROW(dec->d_runner_term, n_all);
-        DEC_GROW(dec->d_runner, n_all);
-        DEC_GROW(dec->d_base, total);
-    }
-    const ScoreOut so{dec->d_term, dec->d_runner_term, dec->d_runner, dec->d_base};  // null arrays with scores off: never touched
-    if (radius || slack) DEC_GROW(dec->d_pen, n_all);
-    if (whole && whole_reserve(dec, g, plan)) return 1;
-    if (baseline && baseline_reserve(dec, g)) return 1;
+    dec->last = LastRun{true, mode, g, n_pages, x_start, d_src};  // what the getters answer from and focr_decoder_verify draws
+    return 0;
+}
 
-    DEC_CHECK(hipEventRecord(dec->run.begin, dec->stream));
-    if (fr.on()) line_prepass_frac_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, fr, dec->d_strips, dec->d_flags);
-    else line_prepass_kernel<<<g.total, PREPASS_THREADS, 0, dec->stream>>>(d_src, g, dec->d_strips, dec->d_flags);
-    DEC_CHECK(hipGetLastError());
-    line_compact_kernel<<<1, COMPACT_THREADS, 0, dec->stream>>>(dec->d_flags, g.total, dec->d_work, dec->d_count);
-    DEC_CHECK(hipGetLastError());
-    if (whole) {
-        whole_launch(dec, g, plan, strip_bytes);
-    } else if (baseline) {
-        baseline_launch(dec, g, strip_bytes);
-    } else if (radius) {  // the strip shares LDS with the reduction pairs, so it stays in LDS up to that much less
-        const bool lds = strip_bytes + SEARCH_RED_BYTES <= LDS_STRIP_MAX;
-        const auto search = lds ? (scores ? line_search_kernel<true, true> : line_search_kernel<true, false>)
-                                : (scores ? line_search_kernel<false, true> : line_search_kernel<false, false>);
-        search<<<g.total, SEARCH_THREADS, SEARCH_RED_BYTES + (lds ? strip_bytes : 0), dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs,
-            dec->origin_x, radius, dec->d_nchars, dec->d_chars, dec->d_pen, so);
-    } else {
-        const auto decode = strip_bytes <= LDS_STRIP_MAX ? (scores ? line_decode_kernel<true, true> : line_decode_kernel<true, false>)
-                                                         : (scores ? line_decode_kernel<false, true> : line_decode_kernel<false, false>);
-        decode<<<g.total, 64, strip_bytes <= LDS_STRIP_MAX ? strip_bytes : 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs,
-                                                                                           dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs,
-                                                                                           dec->origin_x, dec->d_nchars, dec->d_chars, so);
-    }
-    DEC_CHECK(hipGetLastError());
-    DEC_CHECK(hipEventRecord(dec->run.end, dec->stream));
+// ---- the setters (each writes its field of Modes) and the getters (each answers from the last run) -------------------
 
-    const bool offsets = radius || slack;  // d_pen holds the search's offsets, or the slack's
-    std::vector<uint32_t> count, work, nch, wpens;
-    std::vector<uint16_t> all, mrunner, runner;
-    std::vector<int8_t> pen;
-    std::vector<int64_t> wcost, mmargin, bcost;
-    std::vector<int32_t> bq;
-    std::vector<int32_t> mterm, term, runner_term;
-    std::vector<uint64_t> base;
-    if (read_back(dec, count, dec->d_count.p, 1) || read_back(dec, work, dec->d_work.p, total) || read_back(dec, nch, dec->d_nchars.p, total) ||
-        read_back(dec, all, dec->d_chars.p, n_all))
-        return 1;
-    if (offsets && read_back(dec, pen, dec->d_pen.p, n_all)) return 1;
-    if (baseline && (read_back(dec, bq, dec->d_base_q.p, total) || read_back(dec, bcost, dec->d_base_cost.p, total))) return 1;
-    if (candidates && read_back(dec, bq, dec->d_base_q.p, total)) return 1;  // the cost is the whole-line run's
-    if (whole && (read_back(dec, wpens, dec->d_pens.p, n_all) || read_back(dec, wcost, dec->d_cost.p, total))) return 1;
-    if (margins && (read_back(dec, mterm, dec->d_mterm.p, n_all) || read_back(dec, mrunner, dec->d_mrunner.p, n_all) || read_back(dec, mmargin, dec->d_margin.p, n_all)))
-        return 1;
-    if (scores && (read_back(dec, term, dec->d_term.p, n_all) || read_back(dec, runner_term, dec->d_runner_term.p, n_all) ||
-                   read_back(dec, runner, dec->d_runner.p, n_all) || read_back(dec, base, dec->d_base.p, total)))
-        return 1;
-    DEC_CHECK(hipStreamSynchronize(dec->stream));
-    DEC_CHECK(hipEventElapsedTime(&dec->run.ms, dec->run.begin, dec->run.end));
-    dec->run.launches = 3;
-    if (count[0] > total) return dfail(dec, "focr_decoder_run: inconsistent line count from the device");
-    dec->lines.resize(count[0]);
-    for (uint32_t k = 0; k < count[0]; k++) {
-        const uint32_t slot = work[k], n = nch[k];
-        if (slot >= total || n > g.cap) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
-        focr_decoded_line_t &l = dec->lines[k];
-        l.page = slot / g.n_slots;
-        l.y = (uint32_t)((fr.top(g) + (uint64_t)(slot % g.n_slots) * fr.step(g)) >> 6);  // yc_i; y_start + i * line_advance off the fractional grid
-        l.first = dec->chars.size();
-        l.n_chars = n;
-        l.pad = 0;
-        append_line(dec->chars, all, k, g.cap, n);
-        if (offsets) append_line(dec->offsets, pen, k, g.cap, n);
-        if (baseline || candidates) {
-            // q = c_i + offset, 0 <= c_i <= 2^B on the fractional grid and 0 off it
-            const int q_hi = (int)FOCR_BASELINE_MAX + (fr.on() ? 1 << (baseline ? dec->base_bits : dec->wbase_bits) : 0);
-            if (bq[k] < -(int)FOCR_BASELINE_MAX || bq[k] > q_hi) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
-            dec->base_q.push_back((int8_t)bq[k]);
-            dec->base_cost.push_back(baseline ? bcost[k] : wcost[k]);
-        }
-        if (whole) {
-            append_line(dec->pens, wpens, k, g.cap, n);
-            dec->line_cost.push_back(wcost[k]);
-        }
-        for (size_t at = (size_t)k * g.cap; margins && at < (size_t)k * g.cap + n; at++)
-            dec->margins.push_back(focr_char_margin_t{mterm[at], mrunner[at], 0, mmargin[at]});
-        if (!scores) continue;
-        dec->line_base.push_back(base[k]);
-        for (size_t at = (size_t)k * g.cap; at < (size_t)k * g.cap + n; at++) {  // the reference's score: sum r^2 plus the footprint term
-            focr_char_score_t c{(int64_t)base[k] + term[at], (int64_t)base[k] + runner_term[at], runner[at], {0, 0, 0}};
-            if (dec->n_glyphs == 1) c.runner_score = INT64_MAX, c.runner = 0xffff;
-            dec->char_scores.push_back(c);
-        }
-    }
-    if (!offsets) dec->offsets.assign(dec->chars.size(), 0);
-    remember_run(dec, g, d_src, n_pages, x_start, radius != 0, whole);
-    dec->have_scores = scores;
-    dec->have_margins = margins;
-    dec->have_baselines = baseline || candidates;
+extern "C" int focr_decoder_set_scores(focr_decoder_t *dec, int on) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_scores: null decoder");
+    dec->modes.scores = on != 0;
     return 0;
 }
 
 extern "C" int focr_decoder_set_pen_search(focr_decoder_t *dec, uint32_t n) {
     if (!dec) return dfail(nullptr, "focr_decoder_set_pen_search: null decoder");
     if (n > FOCR_PEN_SEARCH_MAX) return dfail(dec, "focr_decoder_set_pen_search: the radius is at most 64 (one pixel)");
-    dec->pen_search = n;
+    dec->modes.pen_search = n;
+    return 0;
+}
+
+extern "C" int focr_decoder_set_whole_line(focr_decoder_t *dec, int on) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_whole_line: null decoder");
+    dec->modes.whole = on != 0;
+    return 0;
+}
+
+extern "C" int focr_decoder_set_whole_slack(focr_decoder_t *dec, uint32_t n) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_whole_slack: null decoder");
+    if (n > FOCR_PEN_SEARCH_MAX) return dfail(dec, "focr_decoder_set_whole_slack: the slack radius is at most 64 (one pixel)");
+    dec->modes.slack = n;
+    return 0;
+}
+
+extern "C" int focr_decoder_set_whole_margins(focr_decoder_t *dec, int on) {
+    if (!dec) return dfail(nullptr, "focr_decoder_set_whole_margins: null decoder");
+    dec->modes.margins = on != 0;
+    return 0;
+}
+
+extern "C" int focr_decoder_debug_set_whole_grid(focr_decoder_t *dec, uint32_t grid) {
+    if (!dec) return dfail(nullptr, "focr_decoder_debug_set_whole_grid: null decoder");
+    dec->modes.whole_grid = grid;
     return 0;
 }
 
@@ -659,57 +747,26 @@ extern "C" int focr_decoder_get_offsets(const focr_decoder_t *dec, int8_t *offse
     return 0;
 }
 
-extern "C" int focr_decoder_set_whole_line(focr_decoder_t *dec, int on) {
-    if (!dec) return dfail(nullptr, "focr_decoder_set_whole_line: null decoder");
-    dec->whole_on = on != 0;
-    return 0;
-}
-
-extern "C" int focr_decoder_set_whole_slack(focr_decoder_t *dec, uint32_t n) {
-    if (!dec) return dfail(nullptr, "focr_decoder_set_whole_slack: null decoder");
-    if (n > FOCR_PEN_SEARCH_MAX) return dfail(dec, "focr_decoder_set_whole_slack: the slack radius is at most 64 (one pixel)");
-    dec->whole_slack = n;
-    return 0;
-}
-
 extern "C" int focr_decoder_get_pens(const focr_decoder_t *dec, uint32_t *pens, int64_t *line_cost) {
     if (!dec) return dfail(nullptr, "focr_decoder_get_pens: null decoder");
-    if (!dec->have_whole)
+    if (!(dec->last.ok && dec->last.mode.whole()))
         return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_pens: the last successful run was not a whole-line run (focr_decoder_set_whole_line)");
     if (pens && !dec->pens.empty()) memcpy(pens, dec->pens.data(), dec->pens.size() * sizeof(uint32_t));
     if (line_cost && !dec->line_cost.empty()) memcpy(line_cost, dec->line_cost.data(), dec->line_cost.size() * sizeof(int64_t));
     return 0;
 }
 
-extern "C" int focr_decoder_set_whole_margins(focr_decoder_t *dec, int on) {
-    if (!dec) return dfail(nullptr, "focr_decoder_set_whole_margins: null decoder");
-    dec->margins_on = on != 0;
-    return 0;
-}
-
 extern "C" int focr_decoder_get_margins(const focr_decoder_t *dec, focr_char_margin_t *out) {
     if (!dec) return dfail(nullptr, "focr_decoder_get_margins: null decoder");
-    if (!dec->have_margins)
+    if (!(dec->last.ok && dec->last.mode.margins()))
         return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_margins: the last successful run was not a margins run (focr_decoder_set_whole_margins)");
     if (out && !dec->margins.empty()) memcpy(out, dec->margins.data(), dec->margins.size() * sizeof(focr_char_margin_t));
     return 0;
 }
 
-extern "C" int focr_decoder_debug_set_whole_grid(focr_decoder_t *dec, uint32_t grid) {
-    if (!dec) return dfail(nullptr, "focr_decoder_debug_set_whole_grid: null decoder");
-    dec->whole_grid = grid;
-    return 0;
-}
-
-extern "C" int focr_decoder_set_scores(focr_decoder_t *dec, int on) {
-    if (!dec) return dfail(nullptr, "focr_decoder_set_scores: null decoder");
-    dec->scores_on = on != 0;
-    return 0;
-}
-
 extern "C" int focr_decoder_get_scores(const focr_decoder_t *dec, focr_char_score_t *scores, uint64_t *line_base) {
     if (!dec) return dfail(nullptr, "focr_decoder_get_scores: null decoder");
-    if (!dec->have_scores)
+    if (!dec->last.mode.scores)  // (not last.ok: see focr_decoder_set_font)
         return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_scores: no successful run with scores on (focr_decoder_set_scores)");
     if (scores && !dec->char_scores.empty()) memcpy(scores, dec->char_scores.data(), dec->char_scores.size() * sizeof(focr_char_score_t));
     if (line_base && !dec->line_base.empty()) memcpy(line_base, dec->line_base.data(), dec->line_base.size() * sizeof(uint64_t));

@@ -285,24 +285,8 @@ __global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_moved_kernel(con
 }
 
 void verify_compose_moved_launch(focr_decoder *dec, const TileGrid &tg, size_t n_pages, uint8_t *d_rgb) {
-    verify_compose_moved_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->run_src, dec->run_g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y,
+    verify_compose_moved_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->last.src, dec->last.g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y,
                                                                             dec->d_vlines, dec->d_vrecs, (const uint8_t *)dec->d_bitmaps, d_rgb, dec->d_sums);
-}
-
-int baseline_plan(focr_decoder *dec) {
-    const char *pre = "focr_decoder_run: a baseline search (focr_decoder_set_baseline_search) does not go with ";
-    if (dec->scores_on) return dfail(dec, std::string(pre) + "scores (focr_decoder_set_scores): a runner-up has no definition across candidates yet");
-    if (dec->pen_search) return dfail(dec, std::string(pre) + "a pen search (focr_decoder_set_pen_search) yet");
-    if (dec->whole_on) return dfail(dec, std::string(pre) + "the whole-line decode (focr_decoder_set_whole_line) yet");
-    if (dec->margins_on) return dfail(dec, std::string(pre) + "margins (focr_decoder_set_whole_margins) yet");
-    if (dec->whole_slack) return dfail(dec, std::string(pre) + "a pen slack (focr_decoder_set_whole_slack) yet");
-    if (dec->base_bits && !(dec->have_base_fonts && dec->font_bits == dec->base_bits))
-        return dfail(dec, "focr_decoder_run: a baseline search with y_bits > 0 (focr_decoder_set_baseline_search) needs the y-phase fonts of that "
-                          "y_bits (focr_decoder_set_baseline_fonts)");
-    const float oy = dec->origin_y;
-    if (!(oy >= 0.f) || oy > 65536.f || oy != (float)(int)oy)
-        return dfail(dec, "focr_decoder_run: a baseline search (focr_decoder_set_baseline_search) needs an origin_y that is a whole number >= 0");
-    return 0;
 }
 
 int baseline_reserve(focr_decoder *dec, const Geometry &g) {
@@ -311,19 +295,18 @@ int baseline_reserve(focr_decoder *dec, const Geometry &g) {
     return 0;
 }
 
-void baseline_launch(focr_decoder *dec, const Geometry &g, size_t strip_bytes) {
+void baseline_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, size_t strip_bytes) {
     const bool lds = strip_bytes + BASE_RED_BYTES <= LDS_STRIP_MAX;  // the strip shares LDS with the waves' pairs
-    const uint32_t grid = dec->base_grid ? std::min(dec->base_grid, g.total) : g.total;
+    const size_t lds_bytes = BASE_RED_BYTES + (lds ? strip_bytes : 0);
+    const uint32_t grid = mode.grid ? std::min(mode.grid, g.total) : g.total;
     const BaseFont f{dec->d_glyphs, dec->d_yglyphs, dec->d_offs, dec->d_yoffs, dec->d_bitmaps.as<const uint32_t>(), dec->d_ybitmaps.as<const uint32_t>(),
-                     (uint32_t)(dec->bitmaps_len / 4), dec->ybitmaps_dw, dec->n_glyphs, dec->origin_x, (int)dec->origin_y, dec->base_bits};
-    if (dec->line_frac.on()) {
-        (lds ? line_baseline_frac_kernel<true> : line_baseline_frac_kernel<false>)<<<grid, BASE_THREADS, BASE_RED_BYTES + (lds ? strip_bytes : 0), dec->stream>>>(
-            dec->d_strips, g, dec->line_frac, dec->d_work, dec->d_count, f, dec->base_n, dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
-        return;
-    }
-    const auto kernel = lds ? line_baseline_kernel<true> : line_baseline_kernel<false>;
-    kernel<<<grid, BASE_THREADS, BASE_RED_BYTES + (lds ? strip_bytes : 0), dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, f, dec->base_n,
-                                                                                         dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
+                     (uint32_t)(dec->bitmaps_len / 4), dec->ybitmaps_dw, dec->n_glyphs, dec->origin_x, (int)dec->origin_y, mode.bits};
+    if (mode.frac.on())  // the kernel's form on the fractional grid: a kernel of its own beside the one it restates
+        (lds ? line_baseline_frac_kernel<true> : line_baseline_frac_kernel<false>)<<<grid, BASE_THREADS, lds_bytes, dec->stream>>>(
+            dec->d_strips, g, mode.frac, dec->d_work, dec->d_count, f, mode.radius, dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
+    else
+        (lds ? line_baseline_kernel<true> : line_baseline_kernel<false>)<<<grid, BASE_THREADS, lds_bytes, dec->stream>>>(
+            dec->d_strips, g, dec->d_work, dec->d_count, f, mode.radius, dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
 }
 
 }  // namespace focr_dec
@@ -411,14 +394,13 @@ extern "C" int focr_decoder_set_baseline_search(focr_decoder_t *dec, uint32_t y_
     if (!dec) return dfail(nullptr, "focr_decoder_set_baseline_search: null decoder");
     if (y_bits > FOCR_BASELINE_Y_BITS_MAX) return dfail(dec, "focr_decoder_set_baseline_search: y_bits is at most 3");
     if (n > FOCR_BASELINE_MAX) return dfail(dec, "focr_decoder_set_baseline_search: the radius is at most 32 steps");
-    dec->base_bits = y_bits;
-    dec->base_n = n;
+    dec->modes.base = BaseSearch{y_bits, n};
     return 0;
 }
 
 extern "C" int focr_decoder_get_baselines(const focr_decoder_t *dec, int8_t *q, int64_t *cost) {
     if (!dec) return dfail(nullptr, "focr_decoder_get_baselines: null decoder");
-    if (!dec->have_baselines)
+    if (!(dec->last.ok && dec->last.mode.base_q()))
         return dfail(const_cast<focr_decoder *>(dec), "focr_decoder_get_baselines: the last successful run did not search baselines (focr_decoder_set_baseline_search, or focr_decoder_set_whole_baseline beside the whole-line decode)");
     if (q && !dec->base_q.empty()) memcpy(q, dec->base_q.data(), dec->base_q.size());
     if (cost && !dec->base_cost.empty()) memcpy(cost, dec->base_cost.data(), dec->base_cost.size() * sizeof(int64_t));
@@ -427,6 +409,6 @@ extern "C" int focr_decoder_get_baselines(const focr_decoder_t *dec, int8_t *q, 
 
 extern "C" int focr_decoder_debug_set_baseline_grid(focr_decoder_t *dec, uint32_t grid) {
     if (!dec) return dfail(nullptr, "focr_decoder_debug_set_baseline_grid: null decoder");
-    dec->base_grid = grid;
+    dec->modes.base_grid = grid;
     return 0;
 }

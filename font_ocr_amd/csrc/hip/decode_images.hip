@@ -366,11 +366,13 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     if (!dec) return dfail(nullptr, "focr_decoder_verify: null decoder");
     dec->verify.ms = 0.f;
     dec->verify.launches = 0;
-    if (!dec->run_ok) return dfail(dec, "focr_decoder_verify: no successful focr_decoder_run since the font was set");
+    if (!dec->last.ok) return dfail(dec, "focr_decoder_verify: no successful focr_decoder_run since the font was set");
     if (!dec->n_vglyphs) return dfail(dec, "focr_decoder_verify: no verify table (focr_decoder_set_verify_font)");
     if (!sq_sums) return dfail(dec, "focr_decoder_verify: null sq_sums");
-    const Geometry &g = dec->run_g;
-    const size_t n_pages = dec->run_pages;
+    const LastRun &run = dec->last;
+    const RunMode &mode = run.mode;
+    const Geometry &g = run.g;
+    const size_t n_pages = run.n_pages;
     if (n_pages == 0) return 0;
     const size_t W = g.page_w, H = g.page_h, px = n_pages * W * H;
     const TileGrid tg = tile_grid(n_pages, W, H);
@@ -383,25 +385,26 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     uint8_t *d_rgb = nullptr;
     if (stage_out(dec, dec->d_rgb, rgb, rgb_on_device, px * 3, &d_rgb)) return 1;
     DEC_CHECK(hipEventRecord(dec->verify.begin, dec->stream));
-    const int8_t *pen_offs = dec->run_searched ? (const int8_t *)dec->d_pen : nullptr;
-    const uint32_t *pens = dec->run_whole ? (const uint32_t *)dec->d_pens : nullptr;
-    const int32_t *line_q = dec->run_base ? (const int32_t *)dec->d_base_q : nullptr;
-    if (dec->run_frac.on())  // (only a baseline run is made on the fractional grid: run_base holds)
-        verify_layout_frac_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, dec->run_frac, (uint32_t)n_pages, dec->run_x_start, dec->d_flags, dec->d_work,
-                                                                                  dec->d_count, dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, dec->run_bits,
+    // what the run wrote: a pen search's offsets (a slack's are in the pens already), a whole-line run's pens, a baseline run's q
+    const int8_t *pen_offs = mode.kind == Kind::pen_search ? (const int8_t *)dec->d_pen : nullptr;
+    const uint32_t *pens = mode.whole() ? (const uint32_t *)dec->d_pens : nullptr;
+    const int32_t *line_q = mode.base_q() ? (const int32_t *)dec->d_base_q : nullptr;
+    if (mode.frac.on())  // (only a baseline kind runs on the fractional grid)
+        verify_layout_frac_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, mode.frac, (uint32_t)n_pages, run.x_start, dec->d_flags, dec->d_work,
+                                                                                  dec->d_count, dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, mode.bits,
                                                                                   dec->d_glyphs, dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs,
                                                                                   dec->d_sums);
     else
-        verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, dec->run_x_start, dec->d_flags, dec->d_work, dec->d_count,
-                                                                             dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, dec->run_bits, dec->d_glyphs,
+        verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, run.x_start, dec->d_flags, dec->d_work, dec->d_count,
+                                                                             dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, mode.bits, dec->d_glyphs,
                                                                              dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
     DEC_CHECK(hipGetLastError());
-    if (dec->run_frac.on())  // ... and on the fractional grid the slots that reach a tile come from that grid's inverse
+    if (mode.frac.on())  // ... and on the fractional grid the slots that reach a tile come from that grid's inverse
         verify_compose_frac_launch(dec, tg, n_pages, d_rgb);
-    else if (dec->run_base)  // the canvases of a baseline run are moved off their slots: decode_baseline.hip's compose finds them
+    else if (mode.base_q())  // the canvases of a baseline run are moved off their slots: decode_baseline.hip's compose finds them
         verify_compose_moved_launch(dec, tg, n_pages, d_rgb);
     else
-        verify_compose_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->run_src, g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y, dec->d_vlines, dec->d_vrecs,
+        verify_compose_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(run.src, g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y, dec->d_vlines, dec->d_vrecs,
                                                                           (const uint8_t *)dec->d_bitmaps, d_rgb, dec->d_sums);
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->verify.end, dec->stream));

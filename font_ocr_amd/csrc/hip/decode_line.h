@@ -1,8 +1,9 @@
 // decode_line.h — what the translation units of the `focr` line decoder share (decode.hip: prepass, compaction, the pen
 // loop and its search, and the run itself; decode_whole.hip: the whole-line decode; decode_baseline.hip: the baseline
-// search; decode_whole_baseline.hip: the whole-line decode under every baseline candidate): the strip's constants, the device helpers the files' kernels call (no relocatable device code: they are inlined
-// into each), the whole-line decode's plan, which focr_decoder_run asks for and hands back, and the baseline search's
-// three steps of a run.
+// search; decode_whole_baseline.hip: the whole-line decode under every baseline candidate): the strip's constants, the
+// device helpers the files' kernels call (no relocatable device code: they are inlined into each), and the steps of a run
+// that live beside their kernels: the whole-line decode's plan, buffers and launch, and the baseline search's buffers and
+// launch.  Each takes the run's RunMode (decode.h) and reads no setting.
 #pragma once
 
 #include "decode.h"
@@ -54,8 +55,8 @@ __device__ __forceinline__ int footprint_term(const uint32_t *strip, uint32_t sd
 
 // ---- the whole-line decode as focr_decoder_run sees it (decode_whole.hip) --------------------------------------------
 
-// The plan of a whole-line run: what whole_plan works out from the font, the modes and the geometry before anything is
-// launched, and whole_launch launches from.
+// The plan of a whole-line run: what whole_plan works out from the font, the mode and the geometry before anything is
+// launched, and the launch launches from.
 struct WholePlan {
     std::vector<uint32_t> inc64;  // per glyph: the pen increment in 1/64 px
     int origin_d = 0;             // 64 * origin_x
@@ -67,27 +68,22 @@ struct WholePlan {
     uint32_t grid = 0;            // workgroups
 };
 
-// The refusals of a whole-line run (include/focr_decode.h) and its plan for the batch of geometry g (g.w and g.total).
-int whole_plan(focr_decoder *dec, const Geometry &g, WholePlan *plan);
+// The font and width refusals of a whole-line run of any kind (include/focr_decode.h) and its plan for the batch of
+// geometry g (g.w and g.total).
+int whole_plan(focr_decoder *dec, const RunMode &mode, const Geometry &g, WholePlan *plan);
 // The run's scratch and result buffers and the font's inc64 table; g.cap is the plan's.
-int whole_reserve(focr_decoder *dec, const Geometry &g, const WholePlan &plan);
-// The third launch of a whole-line run, on the decoder's stream; the caller checks hipGetLastError.
-void whole_launch(focr_decoder *dec, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
-
-// ---- a whole-line run under every baseline candidate (decode_whole_baseline.hip) -------------------------------------
-
-// The refusals of focr_decoder_set_whole_baseline with a radius (include/focr_decode.h), before anything is launched.
-int whole_baseline_plan(focr_decoder *dec);
-// whole_launch with a radius: line_whole_baseline_kernel in line_whole_kernel's place.
-void whole_baseline_launch(focr_decoder *dec, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
+int whole_reserve(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan);
+// The third launch of a whole, whole_margins or whole_slack run, on the decoder's stream; the caller checks hipGetLastError.
+void whole_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
+// ... and of a whole_baseline run (decode_whole_baseline.hip): line_whole_baseline_kernel, or its form on the fractional grid.
+void whole_baseline_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
 
 // ---- the baseline search as focr_decoder_run sees it (decode_baseline.hip) -------------------------------------------
 
-// The refusals of a baseline run (include/focr_decode.h), before anything is launched.
-int baseline_plan(focr_decoder *dec);
 // The run's per-line result buffers.
 int baseline_reserve(focr_decoder *dec, const Geometry &g);
-// The third launch of a baseline run, on the decoder's stream; the caller checks hipGetLastError.
-void baseline_launch(focr_decoder *dec, const Geometry &g, size_t strip_bytes);
+// The third launch of a baseline run, on the decoder's stream: line_baseline_kernel, or its form on the fractional grid;
+// the caller checks hipGetLastError.
+void baseline_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, size_t strip_bytes);
 
 }  // namespace focr_dec

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_moved_frac_kerne
 }
 
 void verify_compose_frac_launch(focr_decoder *dec, const TileGrid &tg, size_t n_pages, uint8_t *d_rgb) {
-    verify_compose_moved_frac_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->run_src, dec->run_g, dec->run_frac, (uint32_t)n_pages, dec->hmax, tg.tiles_x,
+    verify_compose_moved_frac_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->last.src, dec->last.g, dec->last.mode.frac, (uint32_t)n_pages, dec->hmax, tg.tiles_x,
                                                                                  tg.tiles_y, dec->d_vlines, dec->d_vrecs, (const uint8_t *)dec->d_bitmaps, d_rgb,
                                                                                  dec->d_sums);
 }
@@ -82,6 +82,6 @@ using namespace focr_dec;
 extern "C" int focr_decoder_set_line_frac(focr_decoder_t *dec, uint32_t y_frac, uint32_t advance_frac) {
     if (!dec) return dfail(nullptr, "focr_decoder_set_line_frac: null decoder");
     if (y_frac > 63 || advance_frac > 63) return dfail(dec, "focr_decoder_set_line_frac: y_frac and advance_frac are at most 63 (in 1/64 px)");
-    dec->line_frac = LineFrac{y_frac, advance_frac};
+    dec->modes.frac = LineFrac{y_frac, advance_frac};
     return 0;
 }

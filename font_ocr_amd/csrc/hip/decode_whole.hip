@@ -242,11 +242,9 @@ constexpr WholeScratch WHOLE_SCRATCH_MARGINS{sizeof(uint64_t), 4 * WHOLE_SCRATCH
 constexpr WholeScratch WHOLE_SCRATCH_SLACK{sizeof(uint16_t) + sizeof(int8_t), WHOLE_SCRATCH_BUDGET / 2 * 3};
 constexpr WholeScratch WHOLE_SCRATCH_BASELINE{2 * sizeof(uint16_t), 2 * WHOLE_SCRATCH_BUDGET};
 
-int whole_plan(focr_decoder *dec, const Geometry &g, WholePlan *plan) {
-    const uint32_t slack = dec->whole_slack;
-    const bool margins = dec->margins_on, candidates = dec->wbase_n != 0;
-    if (dec->scores_on) return dfail(dec, "focr_decoder_run: whole-line decode with scores on (a runner-up has no definition under the dynamic programme)");
-    if (dec->pen_search) return dfail(dec, "focr_decoder_run: whole-line decode with a pen search radius (the dynamic programme does not search offsets)");
+int whole_plan(focr_decoder *dec, const RunMode &mode, const Geometry &g, WholePlan *plan) {
+    const uint32_t slack = mode.kind == Kind::whole_slack ? mode.radius : 0;
+    const bool margins = mode.margins(), candidates = mode.kind == Kind::whole_baseline;
     const float ox = dec->origin_x;
     if (!(ox >= 0.f && ox <= 65536.f && ox == floorf(ox)))
         return dfail(dec, "focr_decoder_run: whole-line decode needs origin_x to be a whole number >= 0 (at most 65536)");
@@ -285,21 +283,21 @@ int whole_plan(focr_decoder *dec, const Geometry &g, WholePlan *plan) {
     const WholeScratch sc = margins ? WHOLE_SCRATCH_MARGINS : slack ? WHOLE_SCRATCH_SLACK : candidates ? WHOLE_SCRATCH_BASELINE : WHOLE_SCRATCH_PLAIN;
     const size_t fit = std::max<size_t>(sc.budget / ((size_t)plan->n_states * sc.state_bytes), 1);
     plan->grid = (uint32_t)std::min<size_t>({g.total, fit, WHOLE_GRID_MAX});
-    if (dec->whole_grid) plan->grid = std::min(plan->grid, dec->whole_grid);
+    if (mode.grid) plan->grid = std::min(plan->grid, mode.grid);
     return 0;
 }
 
-int whole_reserve(focr_decoder *dec, const Geometry &g, const WholePlan &plan) {
+int whole_reserve(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan) {
     const size_t chars = (size_t)g.cap * g.total, scratch = (size_t)plan.grid * plan.n_states;
-    if (dec->margins_on) {
+    if (mode.margins()) {
         DEC_GROW(dec->d_fwd, scratch);
         DEC_GROW(dec->d_mterm, chars);
         DEC_GROW(dec->d_mrunner, chars);
         DEC_GROW(dec->d_margin, chars);
     } else
-        DEC_GROW(dec->d_back, dec->wbase_n ? 2 * scratch : scratch);  // baseline candidates: two halves per workgroup
-    if (dec->wbase_n) DEC_GROW(dec->d_base_q, g.total);
-    if (dec->whole_slack) DEC_GROW(dec->d_woff, scratch);
+        DEC_GROW(dec->d_back, mode.base_q() ? 2 * scratch : scratch);  // baseline candidates: two halves per workgroup
+    if (mode.base_q()) DEC_GROW(dec->d_base_q, g.total);
+    if (mode.kind == Kind::whole_slack) DEC_GROW(dec->d_woff, scratch);
     DEC_GROW(dec->d_pens, chars);
     DEC_GROW(dec->d_cost, g.total);
     if (!dec->d_inc64.p) DEC_UPLOAD(dec->d_inc64, plan.inc64.data(), plan.inc64.size());
@@ -308,15 +306,15 @@ int whole_reserve(focr_decoder *dec, const Geometry &g, const WholePlan &plan) {
 
 // The strip shares LDS with what whole_layout puts before it; with margins the characters' keys and midpoints come first:
 // beside the ring when they fit, then the strip when it still fits.
-void whole_launch(focr_decoder *dec, const Geometry &g, const WholePlan &plan, size_t strip_bytes) {
-    if (dec->wbase_n) return whole_baseline_launch(dec, g, plan, strip_bytes);  // decode_whole_baseline.hip's kernel
+void whole_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan, size_t strip_bytes) {
     const WholeParams wp{plan.origin_d, plan.batch, plan.ring - 1, plan.max_inc, plan.n_states};
-    const uint32_t slack = dec->whole_slack, chars_dwords = whole_chars_dwords(g.cap);
-    const bool chars_lds = dec->margins_on && whole_fixed_bytes(false, plan.ring, chars_dwords) <= LDS_STRIP_MAX;
-    const size_t fixed = whole_fixed_bytes(slack != 0, plan.ring, chars_lds ? chars_dwords : 0);
+    const bool margins = mode.margins(), slack = mode.kind == Kind::whole_slack;
+    const uint32_t chars_dwords = whole_chars_dwords(g.cap);
+    const bool chars_lds = margins && whole_fixed_bytes(false, plan.ring, chars_dwords) <= LDS_STRIP_MAX;
+    const size_t fixed = whole_fixed_bytes(slack, plan.ring, chars_lds ? chars_dwords : 0);
     const bool lds = strip_bytes + fixed <= LDS_STRIP_MAX;
     const size_t lds_bytes = fixed + (lds ? strip_bytes : 0);
-    if (dec->margins_on) {
+    if (margins) {
         const auto kernel = lds ? (chars_lds ? line_whole_margins_kernel<true, true> : line_whole_margins_kernel<true, false>)
                                 : (chars_lds ? line_whole_margins_kernel<false, true> : line_whole_margins_kernel<false, false>);
         kernel<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
@@ -325,7 +323,7 @@ void whole_launch(focr_decoder *dec, const Geometry &g, const WholePlan &plan, s
     } else if (slack) {
         (lds ? line_whole_slack_kernel<true> : line_whole_slack_kernel<false>)<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
             dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
-            dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, SlackOut{slack, dec->d_woff, dec->d_pen});
+            dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, SlackOut{mode.radius, dec->d_woff, dec->d_pen});
     } else {
         (lds ? line_whole_kernel<true> : line_whole_kernel<false>)<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
             dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,

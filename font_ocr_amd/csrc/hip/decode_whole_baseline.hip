@@ -167,34 +167,21 @@ __global__ __launch_bounds__(WHOLE_THREADS) void line_whole_baseline_frac_kernel
 
 // ---- the host's side (decode_line.h) ---------------------------------------------------------------------------------
 
-int whole_baseline_plan(focr_decoder *dec) {
-    const char *pre = "focr_decoder_run: baseline candidates of a whole-line run (focr_decoder_set_whole_baseline) ";
-    if (!dec->whole_on)
-        return dfail(dec, std::string(pre) + "with the whole-line decode off (focr_decoder_set_whole_line; the pen loop's search is focr_decoder_set_baseline_search)");
-    if (dec->margins_on) return dfail(dec, std::string(pre) + "do not go with margins (focr_decoder_set_whole_margins) yet");
-    if (dec->whole_slack) return dfail(dec, std::string(pre) + "do not go with a pen slack (focr_decoder_set_whole_slack) yet");
-    if (dec->wbase_bits && !(dec->have_base_fonts && dec->font_bits == dec->wbase_bits))
-        return dfail(dec, std::string(pre) + "with y_bits > 0 need the y-phase fonts of that y_bits (focr_decoder_set_baseline_fonts)");
-    const float oy = dec->origin_y;
-    if (!(oy >= 0.f) || oy > 65536.f || oy != (float)(int)oy) return dfail(dec, std::string(pre) + "need an origin_y that is a whole number >= 0");
-    return 0;
-}
-
 // The LDS is the plain whole-line run's: the head, the live list and the ring, then the strip when it fits.
-void whole_baseline_launch(focr_decoder *dec, const Geometry &g, const WholePlan &plan, size_t strip_bytes) {
+void whole_baseline_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan, size_t strip_bytes) {
     const WholeParams wp{plan.origin_d, plan.batch, plan.ring - 1, plan.max_inc, plan.n_states};
     const size_t fixed = whole_fixed_bytes(false, plan.ring, 0);
     const bool lds = strip_bytes + fixed <= LDS_STRIP_MAX;
-    const WholeBase wb{dec->d_yglyphs, dec->d_yoffs, dec->d_ybitmaps.as<const uint32_t>(), (int)dec->origin_y, dec->wbase_bits, dec->wbase_n, dec->d_base_q};
-    if (dec->line_frac.on()) {
-        (lds ? line_whole_baseline_frac_kernel<true> : line_whole_baseline_frac_kernel<false>)<<<plan.grid, WHOLE_THREADS, fixed + (lds ? strip_bytes : 0), dec->stream>>>(
-            dec->d_strips, g, dec->line_frac, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64,
+    const size_t lds_bytes = fixed + (lds ? strip_bytes : 0);
+    const WholeBase wb{dec->d_yglyphs, dec->d_yoffs, dec->d_ybitmaps.as<const uint32_t>(), (int)dec->origin_y, mode.bits, mode.radius, dec->d_base_q};
+    if (mode.frac.on())  // the kernel's form on the fractional grid: a kernel of its own beside the one it restates
+        (lds ? line_whole_baseline_frac_kernel<true> : line_whole_baseline_frac_kernel<false>)<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
+            dec->d_strips, g, mode.frac, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64,
             dec->n_glyphs, wp, dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, wb);
-        return;
-    }
-    (lds ? line_whole_baseline_kernel<true> : line_whole_baseline_kernel<false>)<<<plan.grid, WHOLE_THREADS, fixed + (lds ? strip_bytes : 0), dec->stream>>>(
-        dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
-        dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, wb);
+    else
+        (lds ? line_whole_baseline_kernel<true> : line_whole_baseline_kernel<false>)<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
+            dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, wb);
 }
 
 }  // namespace focr_dec
@@ -205,7 +192,6 @@ extern "C" int focr_decoder_set_whole_baseline(focr_decoder_t *dec, uint32_t y_b
     if (!dec) return dfail(nullptr, "focr_decoder_set_whole_baseline: null decoder");
     if (y_bits > FOCR_BASELINE_Y_BITS_MAX) return dfail(dec, "focr_decoder_set_whole_baseline: y_bits is at most 3");
     if (n > FOCR_BASELINE_MAX) return dfail(dec, "focr_decoder_set_whole_baseline: the radius is at most 32 steps");
-    dec->wbase_bits = y_bits;
-    dec->wbase_n = n;
+    dec->modes.wbase = BaseSearch{y_bits, n};
     return 0;
 }

@@ -69,6 +69,27 @@ class LineMargins(collections.namedtuple("LineMargins", "term runner margin")):
     NO_RUNNER = "\0"
 
 
+# The modes of one decode()/decode_device() call, checked (LineDecoder._modes).
+_Modes = collections.namedtuple("_Modes", "scores pen_search whole_line margins pen_slack baseline_search whole_baseline line_frac")
+
+# The results of one call as per-page lists, in the order of the public tuple; None where the modes write no such result.
+_Run = collections.namedtuple("_Run", "text scores offsets pens costs margins slack_offsets whole_qs baselines baseline_costs")
+
+
+def _record(m, make):
+    """A _Run with make() in the fields the modes m fill, and None in the others."""
+    on = (True, m.scores, m.pen_search, m.whole_line, m.whole_line, m.margins, m.pen_slack, m.whole_baseline, m.baseline_search, m.baseline_search)
+    return _Run(*(make() if o else None for o in on))
+
+
+# The library's settings in the order _run issues them: the attribute that caches what the library was last given (its
+# switch, its radius, or its (y_bits, radius) / (y_frac, advance_frac) pair), the setter, and the library's own default.
+_SETTINGS = (("_baseline", "focr_decoder_set_baseline_search", (0, 0)), ("_whole_baseline", "focr_decoder_set_whole_baseline", (0, 0)),
+             ("_line_frac", "focr_decoder_set_line_frac", (0, 0)), ("_pen_slack", "focr_decoder_set_whole_slack", 0),
+             ("_margins", "focr_decoder_set_whole_margins", False), ("_whole", "focr_decoder_set_whole_line", False),
+             ("_pen_search", "focr_decoder_set_pen_search", 0), ("_scores", "focr_decoder_set_scores", False))
+
+
 def _err():
     return C.create_string_buffer(512)
 
@@ -221,14 +242,8 @@ class LineDecoder:
         self.last_test_ms = 0.0
         self._vfont = None
         self._batch = None  # (n_pages, page_h, page_w) of the last run
-        self._scores = False  # the library's switch (focr_decoder_set_scores)
-        self._pen_search = 0  # the library's radius (focr_decoder_set_pen_search)
-        self._whole = False  # the library's switch (focr_decoder_set_whole_line)
-        self._margins = False  # the library's switch (focr_decoder_set_whole_margins)
-        self._pen_slack = 0  # the library's radius (focr_decoder_set_whole_slack)
-        self._baseline = (0, 0)  # the library's y_bits and radius (focr_decoder_set_baseline_search)
-        self._whole_baseline = (0, 0)  # the library's y_bits and radius (focr_decoder_set_whole_baseline)
-        self._line_frac = (0, 0)  # the library's sub-pixel parts of y and line_advance (focr_decoder_set_line_frac)
+        for attr, _, default in _SETTINGS:
+            setattr(self, attr, default)
 
     def _check(self, rc):
         if rc != 0:
@@ -346,40 +361,16 @@ class LineDecoder:
         mse = sums.astype(np.float32) / np.float32((h * w) & 0xFFFFFFFF)  # red_blue_mse: (sum as f32) / (w * h as u32)
         return mse, imgs
 
-    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, scores=False, pen_search=0, whole_line=False,
-             margins=False, pen_slack=0, baseline_search=0, whole_baseline=0, line_frac=(0, 0)):
-        """[[(y, text), ...] per page] of one batch; with scores [[LineScores, ...] per page] beside it (else None); with
-        a pen search [[int8 offsets, ...] per page] (else None); with whole_line ([[uint32 pens, ...] per page],
-        [[cost, ...] per page]) (else None), and with margins [[LineMargins, ...] per page], or with a pen slack
-        [[int8 offsets, ...] per page], or with whole_baseline [[q, ...] per page], as a third element of that; with a baseline search ([[q, ...] per page],
-        [[cost, ...] per page]) (else None)."""
+    def _run(self, ptr, on_device, n, h, w, x, y, width, line_height, line_advance, m):
+        """One batch under the modes m: the _Run of its per-page lists."""
         self._batch = None
-        baseline = (self.font.y_bits if baseline_search else 0, int(baseline_search))
-        if baseline != self._baseline:
-            self._check(self._lib.focr_decoder_set_baseline_search(self._h, *baseline))
-            self._baseline = baseline
-        whole_base = (self.font.y_bits if whole_baseline else 0, int(whole_baseline))
-        if whole_base != self._whole_baseline:
-            self._check(self._lib.focr_decoder_set_whole_baseline(self._h, *whole_base))
-            self._whole_baseline = whole_base
-        if tuple(line_frac) != self._line_frac:
-            self._check(self._lib.focr_decoder_set_line_frac(self._h, *line_frac))
-            self._line_frac = tuple(line_frac)
-        if int(pen_slack) != self._pen_slack:
-            self._check(self._lib.focr_decoder_set_whole_slack(self._h, int(pen_slack)))
-            self._pen_slack = int(pen_slack)
-        if bool(margins) != self._margins:
-            self._check(self._lib.focr_decoder_set_whole_margins(self._h, int(bool(margins))))
-            self._margins = bool(margins)
-        if bool(whole_line) != self._whole:
-            self._check(self._lib.focr_decoder_set_whole_line(self._h, int(bool(whole_line))))
-            self._whole = bool(whole_line)
-        if int(pen_search) != self._pen_search:
-            self._check(self._lib.focr_decoder_set_pen_search(self._h, int(pen_search)))
-            self._pen_search = int(pen_search)
-        if bool(scores) != self._scores:
-            self._check(self._lib.focr_decoder_set_scores(self._h, int(bool(scores))))
-            self._scores = bool(scores)
+        y_bits = self.font.y_bits
+        values = ((y_bits if m.baseline_search else 0, m.baseline_search), (y_bits if m.whole_baseline else 0, m.whole_baseline), m.line_frac,
+                  m.pen_slack, m.margins, m.whole_line, m.pen_search, m.scores)
+        for (attr, setter, _), value in zip(_SETTINGS, values):
+            if value != getattr(self, attr):
+                self._check(getattr(self._lib, setter)(self._h, *(value if isinstance(value, tuple) else (int(value),))))
+                setattr(self, attr, value)
         self._check(self._lib.focr_decoder_run(self._h, ptr, int(on_device), n, w, h, x, y, width, line_height, line_advance))
         self._batch = (n, h, w)
         self.last_ms = float(self._lib.focr_decoder_last_ms(self._h))
@@ -387,54 +378,60 @@ class LineDecoder:
         lines = (N.DecodedLine * max(1, nl))()
         chars = np.zeros(max(1, nc), dtype=np.uint16)
         self._check(self._lib.focr_decoder_get(self._h, lines, chars.ctypes.data))
-        if scores:
+        if m.scores:
             cs = np.zeros(max(1, nc), dtype=np.dtype([("score", "<i8"), ("runner_score", "<i8"), ("runner", "<u2"), ("pad", "<u2", 3)]))
             base = np.zeros(max(1, nl), dtype=np.uint64)
             self._check(self._lib.focr_decoder_get_scores(self._h, cs.ctypes.data_as(C.POINTER(N.CharScore)), base.ctypes.data))
-        if pen_search or pen_slack:
+        if m.pen_search or m.pen_slack:
             js = np.zeros(max(1, nc), dtype=np.int8)
             self._check(self._lib.focr_decoder_get_offsets(self._h, js.ctypes.data))
-        if whole_line:
+        if m.whole_line:
             ps = np.zeros(max(1, nc), dtype=np.uint32)
             lc = np.zeros(max(1, nl), dtype=np.int64)
             self._check(self._lib.focr_decoder_get_pens(self._h, ps.ctypes.data, lc.ctypes.data))
-        if margins:
+        if m.margins:
             ms = np.zeros(max(1, nc), dtype=np.dtype([("term", "<i4"), ("runner", "<u2"), ("pad", "<u2"), ("margin", "<i8")]))
             self._check(self._lib.focr_decoder_get_margins(self._h, ms.ctypes.data))
-        if baseline_search or whole_baseline:
+        if m.baseline_search or m.whole_baseline:
             bq = np.zeros(max(1, nl), dtype=np.int8)
             bc = np.zeros(max(1, nl), dtype=np.int64)
             self._check(self._lib.focr_decoder_get_baselines(self._h, bq.ctypes.data, bc.ctypes.data))
-        found = ([[] for _ in range(n)], [[] for _ in range(n)]) if baseline_search else None
         alpha = self.font.alphabet
-        whole = ([[] for _ in range(n)], [[] for _ in range(n)]) + (([[] for _ in range(n)],) if margins or pen_slack or whole_baseline else ()) if whole_line else None
-        out = [[] for _ in range(n)]
-        sc = [[] for _ in range(n)] if scores else None
-        offs = [[] for _ in range(n)] if pen_search else None
+        r = _record(m, lambda: [[] for _ in range(n)])
+        text, sc, offs, pens, costs, mar, slack_offs, whole_qs, bqs, bcosts = r  # locals, like the modes: the loop runs once per line
+        scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, _ = m
         for k in range(nl):
             ln = lines[k]
-            text = "".join(alpha[c] for c in chars[ln.first: ln.first + ln.n_chars])
-            out[ln.page].append((int(ln.y), text))
-            if baseline_search:
-                found[0][ln.page].append(int(bq[k]))
-                found[1][ln.page].append(int(bc[k]))
-            if pen_search:
-                offs[ln.page].append(js[ln.first: ln.first + ln.n_chars].copy())
-            if whole_line:
-                whole[0][ln.page].append(ps[ln.first: ln.first + ln.n_chars].copy())
-                whole[1][ln.page].append(int(lc[k]))
-            if pen_slack:
-                whole[2][ln.page].append(js[ln.first: ln.first + ln.n_chars].copy())
-            if whole_baseline:
-                whole[2][ln.page].append(int(bq[k]))
-            if margins:
-                m = ms[ln.first: ln.first + ln.n_chars]
-                runner = "".join(LineMargins.NO_RUNNER if i == 0xFFFF else alpha[i] for i in m["runner"])
-                whole[2][ln.page].append(LineMargins(m["term"].copy(), runner, m["margin"].copy()))
+            page, at = ln.page, slice(ln.first, ln.first + ln.n_chars)
+            text[page].append((int(ln.y), "".join(alpha[c] for c in chars[at])))
             if scores:
-                c = cs[ln.first: ln.first + ln.n_chars]
-                sc[ln.page].append(LineScores(int(base[k]), c["score"].copy(), c["runner"].copy(), c["runner_score"].copy()))
-        return out, sc, offs, whole, found
+                c = cs[at]
+                sc[page].append(LineScores(int(base[k]), c["score"].copy(), c["runner"].copy(), c["runner_score"].copy()))
+            if pen_search:
+                offs[page].append(js[at].copy())
+            if whole_line:
+                pens[page].append(ps[at].copy())
+                costs[page].append(int(lc[k]))
+            if margins:
+                c = ms[at]
+                runner = "".join(LineMargins.NO_RUNNER if i == 0xFFFF else alpha[i] for i in c["runner"])
+                mar[page].append(LineMargins(c["term"].copy(), runner, c["margin"].copy()))
+            if pen_slack:
+                slack_offs[page].append(js[at].copy())
+            if whole_baseline:
+                whole_qs[page].append(int(bq[k]))
+            if baseline_search:
+                bqs[page].append(int(bq[k]))
+                bcosts[page].append(int(bc[k]))
+        return r
+
+    @staticmethod
+    def _assemble(verified, r):
+        """The public result of decode() and decode_device(): (lines[, mse, images][, scores][, offsets][, pens, costs][, margins]
+        [, slack offsets][, whole-baseline qs][, baselines, costs]), or the bare lines when nothing else was asked for.
+        verified: () or (mse, images)."""
+        res = (r.text,) + verified + tuple(v for v in r[1:] if v is not None)
+        return res if len(res) > 1 else r.text
 
     @staticmethod
     def _check_pen_search(pen_search):
@@ -499,6 +496,20 @@ class LineDecoder:
             raise ValueError("y_frac and line_advance_frac need baseline_search or whole_baseline (no other mode renders at a sub-pixel row yet)")
         return fr
 
+    def _modes(self, verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac):
+        """The checks of decode() and decode_device() in their order, and the modes as one record."""
+        if self.font is None:
+            raise DecoderError("set_font() first")
+        _check_verify(verify)
+        pen_search = self._check_pen_search(pen_search)
+        whole_line = self._check_whole_line(whole_line, scores, pen_search)
+        margins = self._check_margins(margins, whole_line)
+        pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
+        baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
+        whole_baseline = self._check_whole_baseline(whole_baseline, whole_line, margins, pen_slack)
+        line_frac = self._check_line_frac(y_frac, line_advance_frac, baseline_search, whole_baseline)
+        return _Modes(bool(scores), pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, line_frac)
+
     def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, pen_slack=0,
                baseline_search=0, whole_baseline=0, y_frac=0, line_advance_frac=0, margins=False, whole_line=False):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
@@ -538,27 +549,13 @@ class LineDecoder:
         line_advance_frac / 64) px, its crop starts at the whole row of that (the y of the result's line), and its candidates
         are searched around its own sub-pixel part; the returned q is the absolute one, so y + q * 2^-y_bits px stays the
         line's top.  For pages whose leading is not a whole number of pixels.  Without either search: ValueError."""
-        if self.font is None:
-            raise DecoderError("set_font() first")
-        _check_verify(verify)
-        pen_search = self._check_pen_search(pen_search)
-        whole_line = self._check_whole_line(whole_line, scores, pen_search)
-        margins = self._check_margins(margins, whole_line)
-        pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
-        baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
-        whole_baseline = self._check_whole_baseline(whole_baseline, whole_line, margins, pen_slack)
-        line_frac = self._check_line_frac(y_frac, line_advance_frac, baseline_search, whole_baseline)
+        m = self._modes(verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
         else:
             pages = list(luma_pages)
-        out = [None] * len(pages)
-        sc = [None] * len(pages)
-        offs = [None] * len(pages)
-        wpens, wcosts, wmargins, woffs = [None] * len(pages), [None] * len(pages), [None] * len(pages), [None] * len(pages)
-        wqs = [None] * len(pages)
-        bqs, bcosts = [None] * len(pages), [None] * len(pages)
+        out = _record(m, lambda: [None] * len(pages))
         mse = np.zeros(len(pages), dtype=np.float32)
         images = [None] * len(pages) if verify == "image" else None
         by_size = {}
@@ -566,81 +563,28 @@ class LineDecoder:
             by_size.setdefault(np.asarray(p).shape, []).append(i)
         for (h, w), idx in by_size.items():
             batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
-            res, res_sc, res_offs, res_whole, res_base = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, scores=scores,
-                                                                   pen_search=pen_search, whole_line=whole_line, margins=margins,
-                                                                   pen_slack=pen_slack, baseline_search=baseline_search,
-                                                                   whole_baseline=whole_baseline, line_frac=line_frac)
-            for j, i in enumerate(idx):
-                out[i] = res[j]
-                if baseline_search:
-                    bqs[i], bcosts[i] = res_base[0][j], res_base[1][j]
-                if whole_line:
-                    wpens[i], wcosts[i] = res_whole[0][j], res_whole[1][j]
-                if margins:
-                    wmargins[i] = res_whole[2][j]
-                if pen_slack:
-                    woffs[i] = res_whole[2][j]
-                if whole_baseline:
-                    wqs[i] = res_whole[2][j]
-                if pen_search:
-                    offs[i] = res_offs[j]
-                if scores:
-                    sc[i] = res_sc[j]
+            r = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, m)
+            for all_pages, these in zip(out, r):
+                for j, i in enumerate(idx if these is not None else ()):
+                    all_pages[i] = these[j]
             if verify:
-                m, imgs = self._verified(verify, h, w)
-                mse[idx] = m
-                for j, i in enumerate(idx):
-                    if images is not None:
-                        images[i] = imgs[j]
-        res = (out, mse, images) if verify else (out,)
-        if scores:
-            res += (sc,)
-        if pen_search:
-            res += (offs,)
-        if whole_line:
-            res += (wpens, wcosts)
-        if margins:
-            res += (wmargins,)
-        if pen_slack:
-            res += (woffs,)
-        if whole_baseline:
-            res += (wqs,)
-        if baseline_search:
-            res += (bqs, bcosts)
-        return res if len(res) > 1 else out
+                mse[idx], imgs = self._verified(verify, h, w)
+                for j, i in enumerate(idx if images is not None else ()):
+                    images[i] = imgs[j]
+        return self._assemble((mse, images) if verify else (), out)
 
     def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False,
                       pen_search=0, pen_slack=0, baseline_search=0, whole_baseline=0, y_frac=0, line_advance_frac=0, margins=False,
                       whole_line=False):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
-        if self.font is None:
-            raise DecoderError("set_font() first")
-        _check_verify(verify)
-        pen_search = self._check_pen_search(pen_search)
-        whole_line = self._check_whole_line(whole_line, scores, pen_search)
-        margins = self._check_margins(margins, whole_line)
-        pen_slack = self._check_pen_slack(pen_slack, whole_line, margins)
-        baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
-        whole_baseline = self._check_whole_baseline(whole_baseline, whole_line, margins, pen_slack)
-        line_frac = self._check_line_frac(y_frac, line_advance_frac, baseline_search, whole_baseline)
-        out, sc, offs, whole, base = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width),
-                                               int(line_height), int(line_advance), scores=scores, pen_search=pen_search,
-                                               whole_line=whole_line, margins=margins, pen_slack=pen_slack, baseline_search=baseline_search,
-                                               whole_baseline=whole_baseline, line_frac=line_frac)
-        res = (out,)
-        if verify:
-            mse, imgs = self._verified(verify, int(page_h), int(page_w))
-            res = (out, mse, (list(imgs) if imgs is not None else None))
-        if scores:
-            res += (sc,)
-        if pen_search:
-            res += (offs,)
-        if whole_line:
-            res += whole
-        if baseline_search:
-            res += base
-        return res if len(res) > 1 else out
+        m = self._modes(verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac)
+        r = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width), int(line_height),
+                      int(line_advance), m)
+        if not verify:
+            return self._assemble((), r)
+        mse, imgs = self._verified(verify, int(page_h), int(page_w))
+        return self._assemble((mse, list(imgs) if imgs is not None else None), r)
 
     def close(self):
         if self._h is not None:
