@@ -56,10 +56,15 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "cli_common.h"
 #include "focr_decode.h"
 #include "focr_host.h"
 
 namespace {
+
+using cli::utf8_decode;
+using cli::utf8_encode;
+using cli::verify_path;
 
 const char *DEFAULT_ALPHABET = "> =ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";  // src/main.rs:13-14
 const size_t BATCH_PAGES = 256;
@@ -80,17 +85,8 @@ struct Args {
 const char *USAGE =
     "Usage: focr [OPTIONS] --font <FONT> --text-size <TEXT_SIZE> --width <WIDTH> --line-height <LINE_HEIGHT> --line-advance <LINE_ADVANCE>";
 
-[[noreturn]] void usage_error(const std::string &msg) {
-    fprintf(stderr, "error: %s\n\n%s\n\nFor more information, try '--help'.\n", msg.c_str(), USAGE);
-    exit(2);  // clap's usage-error exit code
-}
-
-[[noreturn]] void die(const std::string &msg, int code = 101) {  // 101: a Rust panic's exit status
-    fprintf(stderr, "focr: %s\n", msg.c_str());
-    fflush(stdout);
-    fflush(stderr);
-    _exit(code);
-}
+[[noreturn]] void usage_error(const std::string &msg) { cli::usage_error(USAGE, msg); }
+[[noreturn]] void die(const std::string &msg, int code = 101) { cli::die("focr", msg, code); }  // 101: a Rust panic's exit status
 
 void print_help() {
     printf("%s\n\nOptions:\n"
@@ -125,101 +121,39 @@ void print_help() {
 
 Args parse_args(int argc, char **argv) {
     Args a;
-    std::vector<std::string> v(argv + 1, argv + argc);
-    auto is_opt = [](const std::string &s) { return s.size() > 1 && s[0] == '-' && !(isdigit((unsigned char)s[1]) || s[1] == '.'); };
-    for (size_t i = 0; i < v.size(); i++) {
-        std::string k = v[i], val;
-        bool has_val = false;
-        if (k.rfind("--", 0) == 0) {
-            size_t eq = k.find('=');
-            if (eq != std::string::npos) {
-                val = k.substr(eq + 1);
-                k = k.substr(0, eq);
-                has_val = true;
-            }
-        } else if (k.size() > 2 && k[0] == '-' && k[1] != '-') {  // -t13, -ipage.pgm
-            val = k.substr(k[2] == '=' ? 3 : 2);
-            k = k.substr(0, 2);
-            has_val = true;
-        }
-        auto need = [&]() -> std::string {
-            if (has_val) return val;
-            if (i + 1 >= v.size()) usage_error("a value is required for '" + k + "' but none was supplied");
-            return v[++i];
-        };
-        auto num_u = [&](const std::string &s) -> uint32_t {
-            char *e = nullptr;
-            unsigned long long r = strtoull(s.c_str(), &e, 10);
-            if (!e || *e || s.empty() || s[0] == '-' || s[0] == '+' || r > 0xffffffffull) usage_error("invalid value '" + s + "' for '" + k + "'");
-            return (uint32_t)r;
-        };
-        auto num_f = [&](const std::string &s) -> float {
-            char *e = nullptr;
-            float r = strtof(s.c_str(), &e);
-            if (!e || *e || s.empty()) usage_error("invalid value '" + s + "' for '" + k + "'");
-            return r;
-        };
-        if (k == "-i" || k == "--img") {
-            a.img.push_back(need());
-            while (i + 1 < v.size() && !is_opt(v[i + 1])) a.img.push_back(v[++i]);  // num_args = 1..
-        } else if (k == "-f" || k == "--font") a.font = need();
-        else if (k == "-a" || k == "--alphabet") a.alphabet = need();
+    for (cli::ArgCursor c(argc, argv, USAGE); c.next();) {
+        const std::string &k = c.key;
+        if (k == "-i" || k == "--img") c.need_all(a.img);
+        else if (k == "-f" || k == "--font") a.font = c.need();
+        else if (k == "-a" || k == "--alphabet") a.alphabet = c.need();
         else if (k == "--hinting") a.hinting = true;
-        else if (k == "-t" || k == "--text-size") a.text_size = num_f(need()), a.have_text_size = true;
-        else if (k == "-k" || k == "--kerning") a.kerning = num_f(need());
-        else if (k == "-x" || k == "--x") a.x = num_u(need());
-        else if (k == "-y" || k == "--y") a.y = num_u(need());
-        else if (k == "-w" || k == "--width") a.width = num_u(need()), a.have_width = true;
-        else if (k == "--line-height") a.line_height = num_u(need()), a.have_line_height = true;
-        else if (k == "--line-advance") a.line_advance = num_u(need()), a.have_line_advance = true;
-        else if (k == "--test") a.test = need(), a.have_test = true;
-        else if (k == "--verify") a.verify = need(), a.have_verify = true;
-        else if (k == "--scores") a.scores = need(), a.have_scores = true;
-        else if (k == "--pen-search") {
-            const std::string s = need();
-            a.pen_search = num_u(s);
-            if (a.pen_search > FOCR_PEN_SEARCH_MAX) usage_error("invalid value '" + s + "' for '--pen-search': the radius is at most 64");
-        }
-        else if (k == "--pen-slack") {
-            const std::string s = need();
-            a.pen_slack = num_u(s);
-            if (a.pen_slack > FOCR_PEN_SEARCH_MAX) usage_error("invalid value '" + s + "' for '--pen-slack': the radius is at most 64");
-        }
-        else if (k == "--baseline-search") {
-            const std::string s = need();
-            a.baseline_search = num_u(s);
-            if (a.baseline_search > FOCR_BASELINE_MAX) usage_error("invalid value '" + s + "' for '--baseline-search': the radius is at most 32");
-        }
-        else if (k == "--whole-baseline") {
-            const std::string s = need();
-            a.whole_baseline = num_u(s);
-            if (a.whole_baseline > FOCR_BASELINE_MAX) usage_error("invalid value '" + s + "' for '--whole-baseline': the radius is at most 32");
-        }
-        else if (k == "--y-bits") {
-            const std::string s = need();
-            a.y_bits = num_u(s), a.have_y_bits = true;
-            if (a.y_bits > FOCR_BASELINE_Y_BITS_MAX) usage_error("invalid value '" + s + "' for '--y-bits': at most 3");
-        }
-        else if (k == "--y-frac") {
-            const std::string s = need();
-            a.y_frac = num_u(s), a.have_y_frac = true;
-            if (a.y_frac > 63) usage_error("invalid value '" + s + "' for '--y-frac': at most 63");
-        }
-        else if (k == "--line-advance-frac") {
-            const std::string s = need();
-            a.line_advance_frac = num_u(s), a.have_line_advance_frac = true;
-            if (a.line_advance_frac > 63) usage_error("invalid value '" + s + "' for '--line-advance-frac': at most 63");
-        }
-        else if (k == "--baselines") a.baselines = need(), a.have_baselines = true;
+        else if (k == "-t" || k == "--text-size") a.text_size = c.f32(), a.have_text_size = true;
+        else if (k == "-k" || k == "--kerning") a.kerning = c.f32();
+        else if (k == "-x" || k == "--x") a.x = c.u32();
+        else if (k == "-y" || k == "--y") a.y = c.u32();
+        else if (k == "-w" || k == "--width") a.width = c.u32(), a.have_width = true;
+        else if (k == "--line-height") a.line_height = c.u32(), a.have_line_height = true;
+        else if (k == "--line-advance") a.line_advance = c.u32(), a.have_line_advance = true;
+        else if (k == "--test") a.test = c.need(), a.have_test = true;
+        else if (k == "--verify") a.verify = c.need(), a.have_verify = true;
+        else if (k == "--scores") a.scores = c.need(), a.have_scores = true;
+        else if (k == "--pen-search") a.pen_search = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64");
+        else if (k == "--pen-slack") a.pen_slack = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64");
+        else if (k == "--baseline-search") a.baseline_search = c.u32_at_most(FOCR_BASELINE_MAX, "the radius is at most 32");
+        else if (k == "--whole-baseline") a.whole_baseline = c.u32_at_most(FOCR_BASELINE_MAX, "the radius is at most 32");
+        else if (k == "--y-bits") a.y_bits = c.u32_at_most(FOCR_BASELINE_Y_BITS_MAX, "at most 3"), a.have_y_bits = true;
+        else if (k == "--y-frac") a.y_frac = c.u32_at_most(63, "at most 63"), a.have_y_frac = true;
+        else if (k == "--line-advance-frac") a.line_advance_frac = c.u32_at_most(63, "at most 63"), a.have_line_advance_frac = true;
+        else if (k == "--baselines") a.baselines = c.need(), a.have_baselines = true;
         else if (k == "--whole-line") a.whole_line = true;
-        else if (k == "--margins") a.margins = need(), a.have_margins = true;
+        else if (k == "--margins") a.margins = c.need(), a.have_margins = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
         } else if (k == "-V" || k == "--version") {
             puts("font-ocr 0.1.0");
             exit(0);
-        } else usage_error("unexpected argument '" + v[i] + "' found");
+        } else c.unexpected();
     }
     std::string missing;
     if (a.font.empty()) missing += "\n  --font <FONT>";
@@ -248,32 +182,6 @@ Args parse_args(int argc, char **argv) {
         if (have && a.have_test) usage_error(std::string("the argument '") + name + "' cannot be used with '--test <TEST>'");
     }
     return a;
-}
-
-std::vector<uint32_t> utf8_decode(const std::string &s) {
-    std::vector<uint32_t> out;
-    for (size_t i = 0; i < s.size();) {
-        unsigned char c = (unsigned char)s[i];
-        uint32_t cp;
-        int n;
-        if (c < 0x80) cp = c, n = 1;
-        else if ((c >> 5) == 6) cp = c & 0x1f, n = 2;
-        else if ((c >> 4) == 14) cp = c & 0x0f, n = 3;
-        else cp = c & 0x07, n = 4;
-        for (int k = 1; k < n && i + k < s.size(); k++) cp = (cp << 6) | ((unsigned char)s[i + k] & 0x3f);
-        out.push_back(cp);
-        i += n;
-    }
-    return out;
-}
-
-std::string utf8_encode(uint32_t cp) {
-    std::string s;
-    if (cp < 0x80) s += (char)cp;
-    else if (cp < 0x800) s += (char)(0xc0 | (cp >> 6)), s += (char)(0x80 | (cp & 0x3f));
-    else if (cp < 0x10000) s += (char)(0xe0 | (cp >> 12)), s += (char)(0x80 | ((cp >> 6) & 0x3f)), s += (char)(0x80 | (cp & 0x3f));
-    else s += (char)(0xf0 | (cp >> 18)), s += (char)(0x80 | ((cp >> 12) & 0x3f)), s += (char)(0x80 | ((cp >> 6) & 0x3f)), s += (char)(0x80 | (cp & 0x3f));
-    return s;
 }
 
 // 8-bit RGB or RGBA PNG (focr_image_save_png, the host library's writer)
@@ -306,13 +214,6 @@ std::vector<char> write_verify_pngs(const std::vector<std::string> &paths, const
     work();
     for (std::thread &t : pool) t.join();
     return ok;
-}
-
-std::string verify_path(const std::string &dir, const std::string &img) {  // Path::new(img).with_extension("png").file_name()
-    std::string name = img.substr(img.find_last_of('/') == std::string::npos ? 0 : img.find_last_of('/') + 1);
-    const size_t dot = name.find_last_of('.');
-    if (dot != std::string::npos && dot != 0) name = name.substr(0, dot);
-    return dir + (dir.empty() || dir.back() == '/' ? "" : "/") + name + ".png";
 }
 
 // --test PREFIX (src/main.rs:416-425): PREFIX-rect.png (the box of every non-blank line slot) and PREFIX-text.png (the

@@ -45,6 +45,13 @@ def test_cli_flags_and_errors(ncc_bin):
     assert r.returncode == 2
     r = subprocess.run([ncc_bin, "-f", "/nonexistent.ttf", "-t", "13"], capture_output=True, text=True)
     assert r.returncode == 101  # Font::from_path(..).unwrap() panics, src/ncc.rs:561
+    # the u32 flags follow Rust's u32::from_str: what does not fit is refused, not wrapped; a leading '+' is taken
+    base = [ncc_bin, "-f", "/nonexistent.ttf", "-t", "13"]
+    for form, flag, v in ((["--x-bits", "4294967296"], "--x-bits", "4294967296"),
+                          (["--x-padding=99999999999999999999"], "--x-padding", "99999999999999999999")):
+        r = subprocess.run(base + form, capture_output=True, text=True)
+        assert r.returncode == 2 and f"invalid value '{v}' for '{flag}'" in r.stderr, r.stderr
+    assert subprocess.run(base + ["--x-bits", "+1"], capture_output=True, text=True).returncode == 101
 
 
 def test_cli_overlap_is_an_i32(ncc_bin):

@@ -107,5 +107,11 @@ def test_cli_usage_errors_and_test_refused(focr_bin):
         r = subprocess.run([focr_bin] + argv, capture_output=True, text=True)
         assert r.returncode == 2, (argv, r.returncode, r.stderr)
         assert "error:" in r.stderr and "Usage: focr" in r.stderr
+    # the u32 flags follow Rust's u32::from_str: a leading '+' is taken, blanks and trailing characters are not
+    r = subprocess.run([focr_bin] + base + ["-x", "+3", "--bogus"], capture_output=True, text=True)
+    assert r.returncode == 2 and "unexpected argument '--bogus'" in r.stderr, r.stderr
+    for v in (" 3", "3x"):
+        r = subprocess.run([focr_bin] + base + ["-x", v], capture_output=True, text=True)
+        assert r.returncode == 2 and f"invalid value '{v}' for '-x'" in r.stderr, r.stderr
     r = subprocess.run([focr_bin] + base + ["--test", "out", "-i", "x.png"], capture_output=True, text=True)
     assert r.returncode != 0 and "--test" in r.stderr

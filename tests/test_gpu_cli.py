@@ -71,10 +71,8 @@ def test_cli_text_csv_raw(tmp_path):
     assert r.returncode == 101  # assert!(args.img.len() == 1), src/ncc.rs:834
 
 
-@pytest.mark.skipif(not os.path.exists(FONT), reason="DejaVu Sans Mono not installed")
-def test_cli_batched_pipeline_is_order_preserving(tmp_path):
-    """The decode/scan pipeline (batches, mixed page sizes, decode-ahead back-pressure) prints the same bytes
-    whatever the batch size; a missing image panics (exit 101) like image::open(..).unwrap(), src/ncc.rs:575."""
+def nine_pages(tmp_path):
+    """Nine pages, each of another size than the one before it: nine one-page batches whatever the batch size."""
     alphabet = ASCII95[1:40]
     bank = Bank.rasterize(FONT, 13, 0, 0, alphabet=alphabet)
     paths = []
@@ -82,6 +80,14 @@ def test_cli_batched_pipeline_is_order_preserving(tmp_path):
         pg = synth_page(bank, SYNTH_SEED_BASE + 900 + p, 280 + 24 * (p % 3), 120 + 15 * (p % 2))
         paths.append(str(tmp_path / f"q{p}.pgm"))
         save_pgm(paths[-1], pg)
+    return alphabet, paths
+
+
+@pytest.mark.skipif(not os.path.exists(FONT), reason="DejaVu Sans Mono not installed")
+def test_cli_batched_pipeline_is_order_preserving(tmp_path):
+    """The decode/scan pipeline (batches, mixed page sizes, decode-ahead back-pressure) prints the same bytes
+    whatever the batch size; a missing image panics (exit 101) like image::open(..).unwrap(), src/ncc.rs:575."""
+    alphabet, paths = nine_pages(tmp_path)
     cmd = [NCC, "-f", FONT, "-t", "13", "-a", alphabet, "--csv", "-i"] + paths
     outs = []
     for batch, contexts, devices in (("256", "1", "1"), ("1", "1", "1"), ("2", "1", "99"), ("4", "1", "1"), ("2", "2", "99"), ("1", "3", "1"), ("3", "3", "99")):
@@ -104,6 +110,30 @@ def test_cli_batched_pipeline_is_order_preserving(tmp_path):
     # ... preceded by the reference's font-metrics preamble (src/ncc.rs:791-802)
     for line in ("metrics Metrics { units_per_em: 2048, ascent: 1901.0, descent: -483.0,", "ascent  ", "descent -", "font_bbox size <", "line_space 2384 "):
         assert line in r.stderr, (line, r.stderr[:600])
+
+
+@pytest.mark.skipif(not os.path.exists(FONT), reason="DejaVu Sans Mono not installed")
+def test_cli_verify_and_scores_while_the_ring_wraps(tmp_path):
+    """--verify and --scores give the same bytes when the PNG jobs compete with decoding on two threads while the slab
+    ring wraps (9 one-page batches on 6 slabs) as when every slab is there from the start."""
+    alphabet, paths = nine_pages(tmp_path)
+    runs = []
+    for name, env in (("wide", dict(FOCR_CLI_BATCH="256")), ("tight", dict(FOCR_CLI_BATCH="1", FOCR_CLI_CONTEXTS="1", FOCR_CLI_THREADS="2"))):
+        png_dir, scores = tmp_path / name, tmp_path / (name + ".csv")
+        png_dir.mkdir()
+        r = subprocess.run([NCC, "-f", FONT, "-t", "13", "-a", alphabet, "--verify", str(png_dir), "--scores", str(scores), "-i"] + paths,
+                           capture_output=True, env=dict(os.environ, **env))
+        assert r.returncode == 0, r.stderr
+        mse_lines = [l for l in r.stderr.decode().splitlines() if len(l.split(" ")) == 2 and l.split(" ")[0] in paths]
+        runs.append((r.stdout, scores.read_bytes(), {f: (png_dir / f).read_bytes() for f in sorted(os.listdir(png_dir))}, mse_lines))
+    wide, tight = runs
+    assert len(wide[0]) > 200 and wide[1].count(b"\n") > 200
+    assert tight[0] == wide[0]  # stdout
+    assert tight[1] == wide[1]  # the scores file
+    assert list(wide[2]) == [f"q{p}.png" for p in range(9)] and all(len(v) > 100 for v in wide[2].values())
+    assert tight[2] == wide[2]  # the nine PNGs
+    assert [l.split(" ")[0] for l in wide[3]] == paths  # "<image> <mse>", in input order
+    assert tight[3] == wide[3]
 
 
 @pytest.mark.skipif(not os.path.exists(FONT), reason="DejaVu Sans Mono not installed")
