@@ -383,6 +383,10 @@ DECODE_HIP_SYMBOLS = {
     "focr_decoder_debug_set_baseline_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "focr_decoder_set_whole_baseline": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "focr_decoder_set_line_frac": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "focr_decoder_set_font_candidates": (C.c_int, [C.c_void_p, C.POINTER(DecodeFontStruct), C.c_uint32]),
+    "focr_decoder_set_font_search": (C.c_int, [C.c_void_p, C.c_int]),
+    "focr_decoder_get_fonts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "focr_decoder_debug_set_fonts_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "focr_decoder_set_verify_font": (C.c_int, [C.c_void_p, C.POINTER(VerifyFontStruct)]),
     "focr_decoder_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "focr_decoder_last_verify_ms": (C.c_float, [C.c_void_p]),

@@ -39,7 +39,15 @@
 //     and --line-advance (focr_decoder_set_line_frac), for a leading that is not a whole number of pixels; every line is
 //     cropped at the whole row of its own top and searched around its own sub-pixel part; stdout, --verify and --baselines
 //     keep their formats (y is the line's crop row, q the absolute offset); without --baseline-search or --whole-baseline,
-//     or with --test, they are usage errors.
+//     or with --test, they are usage errors;
+//   * --font-candidate SPEC (repeatable, at most 15 times) is an extension: every line is decoded in the font of -f, -t,
+//     --kerning and --hinting (candidate 0) and in every candidate, and the cheapest reading is kept
+//     (focr_decoder_set_font_candidates, focr_decoder_set_font_search), by the pen loop or, with --whole-line, by the
+//     whole-line decode.  SPEC is a comma-separated list of f=PATH, t=SIZE, k=KERNING and h=0|1; omitted keys take the
+//     values of -f, -t, --kerning and --hinting; a path may not contain a comma.  stdout stays text only, and --fonts PATH
+//     writes a CSV row per decoded line: image_index,y,font,cost (font is the candidate's index).  With --scores,
+//     --pen-search, --pen-slack, --margins, --baseline-search, --whole-baseline or --verify it is a usage error, and so is
+//     --fonts without it.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -69,8 +77,17 @@ using cli::verify_path;
 const char *DEFAULT_ALPHABET = "> =ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";  // src/main.rs:13-14
 const size_t BATCH_PAGES = 256;
 
+struct FontSpec {  // one --font-candidate
+    std::string font;
+    float text_size, kerning;
+    bool hinting;
+};
+
 struct Args {
-    std::vector<std::string> img;
+    std::vector<std::string> img, candidate_specs;
+    std::vector<FontSpec> candidates;
+    std::string fonts;
+    bool have_fonts = false;
     std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores, margins, baselines;
     bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false, have_margins = false;
     bool have_baselines = false, have_y_bits = false;
@@ -114,9 +131,35 @@ void print_help() {
            "      --baselines <BASELINES>          [extension] CSV of every line's chosen vertical offset and cost (only with a baseline search)\n"
            "      --y-frac <N>                     [extension] Sub-pixel part of --y in 1/64 px, N <= 63 (only with a baseline search or --whole-baseline) [default: 0]\n"
            "      --line-advance-frac <N>          [extension] Sub-pixel part of --line-advance in 1/64 px, N <= 63 (only with a baseline search or --whole-baseline) [default: 0]\n"
+           "      --font-candidate <SPEC>...       [extension] Also decode every line in this font and keep the cheapest reading; SPEC is f=PATH,t=SIZE,k=KERNING,h=0|1, omitted keys as -f, -t, --kerning, --hinting; at most 15 (only with the plain pen loop or the plain whole-line decode; not with --verify)\n"
+           "      --fonts <FONTS>                  [extension] CSV of every line's winning font candidate and cost (only with --font-candidate)\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
+}
+
+// One --font-candidate SPEC: key=value pairs separated by commas over the defaults of a; an unknown, empty or repeated key,
+// or a value that does not parse, is a usage error.
+FontSpec parse_font_spec(const std::string &spec, const Args &a) {
+    const auto bad = [&](const std::string &why) { usage_error("invalid value '" + spec + "' for '--font-candidate <SPEC>': " + why); };
+    FontSpec out{a.font, a.text_size, a.kerning, a.hinting};
+    std::string seen;
+    for (size_t at = 0; at <= spec.size();) {
+        const size_t end = std::min(spec.find(',', at), spec.size());
+        const std::string item = spec.substr(at, end - at);
+        at = end + 1;
+        if (item.size() < 2 || item[1] != '=' || !strchr("ftkh", item[0])) bad("'" + item + "' is not one of f=PATH, t=SIZE, k=KERNING, h=0|1");
+        const std::string val = item.substr(2);
+        if (val.empty()) bad(std::string("the key '") + item[0] + "' has no value");
+        if (seen.find(item[0]) != std::string::npos) bad(std::string("the key '") + item[0] + "' is given twice");
+        seen += item[0];
+        if (item[0] == 'f') out.font = val;
+        else if (item[0] == 'h' && (val == "0" || val == "1")) out.hinting = val == "1";
+        else if (item[0] == 't' && cli::parse_f32(val, &out.text_size)) continue;
+        else if (item[0] == 'k' && cli::parse_f32(val, &out.kerning)) continue;
+        else bad("'" + val + "' is not a value for the key '" + item[0] + "'");
+    }
+    return out;
 }
 
 Args parse_args(int argc, char **argv) {
@@ -147,6 +190,8 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--baselines") a.baselines = c.need(), a.have_baselines = true;
         else if (k == "--whole-line") a.whole_line = true;
         else if (k == "--margins") a.margins = c.need(), a.have_margins = true;
+        else if (k == "--font-candidate") a.candidate_specs.push_back(c.need());
+        else if (k == "--fonts") a.fonts = c.need(), a.have_fonts = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -181,6 +226,14 @@ Args parse_args(int argc, char **argv) {
             usage_error(std::string("the argument '") + name + "' cannot be used without '--baseline-search <N>' or '--whole-baseline <N>'");
         if (have && a.have_test) usage_error(std::string("the argument '") + name + "' cannot be used with '--test <TEST>'");
     }
+    if (a.candidate_specs.size() > FOCR_FONT_CANDIDATES_MAX - 1) usage_error("the argument '--font-candidate <SPEC>' cannot be used more than 15 times");
+    for (const std::string &spec : a.candidate_specs) a.candidates.push_back(parse_font_spec(spec, a));
+    if (a.have_fonts && a.candidates.empty()) usage_error("the argument '--fonts <FONTS>' cannot be used without '--font-candidate <SPEC>'");
+    for (const auto &[with, name] : {std::pair<bool, const char *>{a.have_scores, "--scores <SCORES>"}, {a.pen_search != 0, "--pen-search <N>"},
+                                     {a.pen_slack != 0, "--pen-slack <N>"}, {a.have_margins, "--margins <MARGINS>"},
+                                     {a.baseline_search != 0, "--baseline-search <N>"}, {a.whole_baseline != 0, "--whole-baseline <N>"},
+                                     {a.have_verify, "--verify <VERIFY>"}})
+        if (with && !a.candidates.empty()) usage_error(std::string("the argument '--font-candidate <SPEC>' cannot be used with '") + name + "'");
     return a;
 }
 
@@ -198,6 +251,8 @@ struct Line {
     std::vector<focr_char_margin_t> margins;
     int q = 0;                              // --baselines: the line's chosen vertical offset, in steps of 2^-B px
     long long cost = 0;
+    int font = 0;                           // --fonts: the line's winning candidate, and its cost
+    long long font_cost = 0;
 };
 
 // Writes the batch's verify images (the device's draw_verify, n x H x W x 3 bytes) as PNGs on at most 16 threads, and
@@ -270,6 +325,8 @@ int main(int argc, char **argv) {
     if (args.have_margins && !(mcsv = fopen(args.margins.c_str(), "w"))) usage_error("cannot write '" + args.margins + "' for '--margins'");
     FILE *bcsv = nullptr;
     if (args.have_baselines && !(bcsv = fopen(args.baselines.c_str(), "w"))) usage_error("cannot write '" + args.baselines + "' for '--baselines'");
+    FILE *fcsv = nullptr;
+    if (args.have_fonts && !(fcsv = fopen(args.fonts.c_str(), "w"))) usage_error("cannot write '" + args.fonts + "' for '--fonts'");
     if (args.img.empty()) return 0;
 
     char err[256] = {0};
@@ -314,6 +371,17 @@ int main(int argc, char **argv) {
     set("focr_decoder_set_baseline_search", focr_decoder_set_baseline_search(dec, args.baseline_search ? args.y_bits : 0, args.baseline_search));
     set("focr_decoder_set_whole_baseline", focr_decoder_set_whole_baseline(dec, args.whole_baseline ? args.y_bits : 0, args.whole_baseline));
     set("focr_decoder_set_line_frac", focr_decoder_set_line_frac(dec, args.y_frac, args.line_advance_frac));
+    if (!args.candidates.empty()) {  // built over the decode font's alphabet; the decoder keeps its own copy
+        std::vector<focr_decode_font_t> cands(args.candidates.size());
+        for (size_t k = 0; k < cands.size(); k++) {
+            const FontSpec &c = args.candidates[k];
+            if (focr_decode_font_build(c.font.c_str(), c.text_size, c.hinting, c.kerning, alphabet.data(), alphabet.size(), &cands[k], err, sizeof err) != 0)
+                die("font candidate " + std::to_string(k + 1) + ": decode font: " + err);
+        }
+        set("focr_decoder_set_font_candidates", focr_decoder_set_font_candidates(dec, cands.data(), (uint32_t)cands.size()));
+        set("focr_decoder_set_font_search", focr_decoder_set_font_search(dec, 1));
+        for (focr_decode_font_t &f : cands) focr_decode_font_free(&f);
+    }
     const bool csv_offsets = csv && args.pen_search > 0;
 
     std::vector<std::vector<Line>> lines(n_img);
@@ -353,10 +421,15 @@ int main(int argc, char **argv) {
             std::vector<int64_t> bc(bcsv ? dl.size() : 0);
             if (bcsv && focr_decoder_get_baselines(dec, bq.data(), bc.data()) != 0)
                 die(std::string("focr_decoder_get_baselines: ") + focr_decoder_last_error(dec), 1);
+            std::vector<uint8_t> fk(fcsv ? dl.size() : 0);
+            std::vector<int64_t> fc(fcsv ? dl.size() : 0);
+            if (fcsv && focr_decoder_get_fonts(dec, fk.data(), fc.data()) != 0)
+                die(std::string("focr_decoder_get_fonts: ") + focr_decoder_last_error(dec), 1);
             for (size_t li = 0; li < dl.size(); li++) {
                 const focr_decoded_line_t &l = dl[li];
                 Line out{l.y, {}, {}, {}, {}, {}};
                 if (bcsv) out.q = bq[li], out.cost = (long long)bc[li];
+                if (fcsv) out.font = fk[li], out.font_cost = (long long)fc[li];
                 if (mcsv) out.pens.assign(dp.begin() + l.first, dp.begin() + l.first + l.n_chars);
                 if (mcsv) out.margins.assign(dm.begin() + l.first, dm.begin() + l.first + l.n_chars);
                 for (uint32_t c = 0; c < l.n_chars; c++) out.text.push_back(alphabet[dc[l.first + c]]);
@@ -410,6 +483,12 @@ int main(int argc, char **argv) {
         for (size_t i = 0; i < n_img; i++)
             for (const Line &l : lines[i]) fprintf(bcsv, "%zu,%u,%d,%g,%lld\n", i, l.y, l.q, (double)l.q / (double)(1u << args.y_bits), l.cost);
         if (fclose(bcsv) != 0) die("cannot write " + args.baselines);
+    }
+    if (fcsv) {  // one row per decoded line, in the order of stdout
+        fprintf(fcsv, "image_index,y,font,cost\n");
+        for (size_t i = 0; i < n_img; i++)
+            for (const Line &l : lines[i]) fprintf(fcsv, "%zu,%u,%d,%lld\n", i, l.y, l.font, l.font_cost);
+        if (fclose(fcsv) != 0) die("cannot write " + args.fonts);
     }
     if (mcsv) {  // one row per decoded character, in the order of stdout; a one-glyph alphabet has no runner-up and no margin
         fprintf(mcsv, "image_index,y,column,codepoint,pen,term,runner_codepoint,margin\n");

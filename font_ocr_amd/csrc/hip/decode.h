@@ -5,8 +5,10 @@
 //   decode_baseline.hip        the baseline search, its y-phase fonts and the verify's compose after a baseline run
 //   decode_whole_baseline.hip  the whole-line decode under every baseline candidate
 //   decode_line_frac.hip       the fractional line grid's setter and the verify's compose on that grid
+//   decode_fonts.hip           the font search: the pen loop under every candidate font, the candidates' upload, the getter
+//   decode_whole_fonts.hip     the whole-line decode under every candidate font
 //   decode_images.hip          the verify and --test images
-// (decode_line.h lies between the first four.)  Here: the batch geometry, both line grids, the device tables, the tile frame of
+// (decode_line.h lies between the first four and the last two.)  Here: the batch geometry, both line grids, the device tables, the tile frame of
 // the compose kernels (ncc_images.hip is its third user), the blank test's crop, the settings (Modes), what a run resolves
 // them to (RunMode), what the last run left (LastRun), the decoder itself, and the host plumbing every entry point repeats
 // (errors, stages, staging, refusals).
@@ -240,11 +242,12 @@ struct Modes {
     uint32_t slack = 0;       // focr_decoder_set_whole_slack
     BaseSearch base, wbase;   // focr_decoder_set_baseline_search, focr_decoder_set_whole_baseline
     LineFrac frac{0, 0};      // focr_decoder_set_line_frac: (0, 0) is off
-    uint32_t whole_grid = 0, base_grid = 0;  // focr_decoder_debug_set_*_grid: at most this many workgroups (0: no limit of the test's)
+    bool font_search = false;  // focr_decoder_set_font_search
+    uint32_t whole_grid = 0, base_grid = 0, fonts_grid = 0;  // focr_decoder_debug_set_*_grid: at most this many workgroups (0: no limit of the test's)
 };
 
 // The third launch of a run (DESIGN.md has the table: kernel, buffers written, getters that answer).
-enum class Kind { pen_loop, pen_search, whole, whole_margins, whole_slack, whole_baseline, baseline };
+enum class Kind { pen_loop, pen_search, whole, whole_margins, whole_slack, whole_baseline, baseline, fonts, whole_fonts };
 
 // The settings of one run, resolved: every step of the run, and the verify after it, asks this and nothing else.
 struct RunMode {
@@ -254,10 +257,14 @@ struct RunMode {
     uint32_t bits = 0;    // the baseline kinds: d_base_q is in steps of 2^-bits px
     LineFrac frac{0, 0};  // the line grid in force ((0, 0) except under the baseline kinds)
     uint32_t grid = 0;    // the debug limit on the kind's workgroups (the whole and baseline kinds)
-    bool whole() const { return kind == Kind::whole || kind == Kind::whole_margins || kind == Kind::whole_slack || kind == Kind::whole_baseline; }  // d_pens, d_cost
+    bool whole() const {  // d_pens, d_cost
+        return kind == Kind::whole || kind == Kind::whole_margins || kind == Kind::whole_slack || kind == Kind::whole_baseline || kind == Kind::whole_fonts;
+    }
     bool margins() const { return kind == Kind::whole_margins; }                                 // d_mterm, d_mrunner, d_margin
     bool offsets() const { return kind == Kind::pen_search || kind == Kind::whole_slack; }       // d_pen holds offsets
     bool base_q() const { return kind == Kind::baseline || kind == Kind::whole_baseline; }       // d_base_q (and d_base_cost: baseline)
+    bool fonts() const { return kind == Kind::fonts || kind == Kind::whole_fonts; }              // d_line_font (and d_font_cost: fonts)
+    bool halves() const { return kind == Kind::whole_baseline || kind == Kind::whole_fonts; }    // d_back holds two halves per workgroup
 };
 
 // What the last successful run left for the getters and the verify.
@@ -268,6 +275,24 @@ struct LastRun {
     size_t n_pages = 0;
     uint32_t x_start = 0;
     const uint8_t *src = nullptr;  // its pages on the device
+};
+
+// One uploaded candidate of the font search (focr_decoder_set_font_candidates) as the host keeps it; its tables are on the device.
+struct FontCandidate {
+    float origin_x = 0.f, min_inc = 0.f;
+    std::vector<float> inc;
+    uint64_t term_bound = 0;  // the largest stride * box_h * 2 * 255^2 of its glyphs (a term's bound)
+    uint32_t end_dw = 0;      // the end of its bitmaps in the candidates' bitmap table, in dwords
+};
+
+// One candidate of a font search as the device reads it (decode_fonts.hip, decode_whole_fonts.hip); [0] is the decode font.
+struct FontDesc {
+    uint32_t glyph_base;  // its first glyph in the candidates' k-major glyph records (and, times 64, phase offsets)
+    uint32_t end_dw;      // the end of its bitmaps in the bitmap table it reads, in dwords (footprint_term_wide's guard)
+    float origin_x;
+    // the whole-line form only: 64 * origin_x, its batch, its largest inc64 and where its inc64 start in the candidates' table
+    int origin_d;
+    uint32_t batch, max_inc, inc_base;
 };
 
 struct Stage {  // the kernels of one entry point's last call: device events around them, their time and their number
@@ -333,6 +358,16 @@ struct focr_decoder {
     focr::DevArray<uint8_t> d_ybitmaps;
     focr::DevArray<int32_t> d_base_q;
     focr::DevArray<int64_t> d_base_cost;
+    // font search: the uploaded candidates 1 ..= K (set_font_candidates; glyph records and offsets k-major, one bitmap table
+    // whose dword offsets the records carry), a run's descriptors of the candidates 0 ..= K and, under the whole-line decode,
+    // their inc64, and per work-list line beside d_nchars the winner and (pen loop) its cost; grown by a run with the search on
+    std::vector<focr_dec::FontCandidate> cands;
+    focr::DevArray<focr_dec::DevGlyph> d_fglyphs;
+    focr::DevArray<int2> d_foffs;
+    focr::DevArray<uint8_t> d_fbitmaps;
+    focr::DevArray<focr_dec::FontDesc> d_fdesc;
+    focr::DevArray<uint32_t> d_finc64, d_line_font;
+    focr::DevArray<int64_t> d_font_cost;
     // the last run: what it was (for the getters' refusals and the verify) and its results on the host
     focr_dec::LastRun last;
     std::vector<focr_decoded_line_t> lines;
@@ -345,6 +380,8 @@ struct focr_decoder {
     std::vector<focr_char_margin_t> margins;  // beside chars (a margins run)
     std::vector<int8_t> base_q;    // beside lines (a baseline run)
     std::vector<int64_t> base_cost;
+    std::vector<uint8_t> line_font;  // beside lines (a font search)
+    std::vector<int64_t> font_cost;
     // verify: the table, buffers
     uint32_t n_vglyphs = 0, hmax = 0;
     focr::DevArray<focr_dec::VerifyGlyph> d_vglyphs;

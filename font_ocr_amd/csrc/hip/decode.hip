@@ -16,6 +16,9 @@
 //      place: the pen loop under every vertical candidate, and the candidate with the lowest summed footprint term.
 //      With the whole-line decode on and a radius of its own (focr_decoder_set_whole_baseline)
 //      decode_whole_baseline.hip's line_whole_baseline_kernel takes its place: the programme under every candidate.
+//      With the font search on (focr_decoder_set_font_search, over the candidates of focr_decoder_set_font_candidates)
+//      decode_fonts.hip's line_fonts_kernel takes its place, or beside the whole-line decode decode_whole_fonts.hip's
+//      line_whole_fonts_kernel: the pen loop, or the programme, under every candidate font, and the cheapest line kept.
 //      On a fractional line grid (focr_decoder_set_line_frac; the two baseline modes only) launch 1 is
 //      line_prepass_frac_kernel and launch 3 the baseline kernel's *_frac_kernel form: the slot grid in 1/64 px (decode.h).
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
@@ -388,6 +391,7 @@ extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font
         dec->last.mode.scores = scores;
         dec->n_vglyphs = 0;
         dec->have_base_fonts = false;
+        dec->cands.clear();  // the candidates of a font search share the previous font's alphabet (their tables are released below)
     }
     if (!dec || !font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_font: bad arguments");
     if (font->n_glyphs > 65535) return dfail(dec, "focr_decoder_set_font: more than 65535 glyphs");
@@ -417,6 +421,7 @@ extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font
     dec->d_yglyphs.release();
     dec->d_yoffs.release();
     dec->d_ybitmaps.release();
+    drop_font_candidates(dec);
     DEC_UPLOAD(dec->d_glyphs, gl.data(), G);
     DEC_UPLOAD(dec->d_offs, offs.data(), offs.size());
     DEC_UPLOAD(dec->d_bitmaps, (const uint8_t *)font->bitmaps, font->bitmaps_len, 4);
@@ -441,6 +446,8 @@ void clear_results(focr_decoder *dec) {
     dec->last = LastRun{};
     dec->base_q.clear();
     dec->base_cost.clear();
+    dec->line_font.clear();
+    dec->font_cost.clear();
     dec->lines.clear();
     dec->chars.clear();
     dec->char_scores.clear();
@@ -505,9 +512,20 @@ int resolve_modes(focr_decoder *dec, RunMode *out) {
                           "sub-pixel row yet");
     if (m.whole && m.scores) return dfail(dec, "focr_decoder_run: whole-line decode with scores on (a runner-up has no definition under the dynamic programme)");
     if (m.whole && m.pen_search) return dfail(dec, "focr_decoder_run: whole-line decode with a pen search radius (the dynamic programme does not search offsets)");
+    if (m.font_search) {  // every line under every candidate font: the plain pen loop or the whole-line programme, and nothing else yet
+        const std::string pre = "focr_decoder_run: a font search (focr_decoder_set_font_search) ";
+        if (dec->cands.empty()) return dfail(dec, pre + "with no candidates uploaded (focr_decoder_set_font_candidates)");
+        if (m.scores) return dfail(dec, pre + "does not go with scores (focr_decoder_set_scores) yet");
+        if (m.pen_search) return dfail(dec, pre + "does not go with a pen search (focr_decoder_set_pen_search) yet");
+        if (m.margins) return dfail(dec, pre + "does not go with margins (focr_decoder_set_whole_margins) yet");
+        if (m.slack) return dfail(dec, pre + "does not go with a pen slack (focr_decoder_set_whole_slack) yet");
+        if (baseline) return dfail(dec, pre + "does not go with a baseline search (focr_decoder_set_baseline_search) yet");
+        if (candidates) return dfail(dec, pre + "does not go with baseline candidates of a whole-line run (focr_decoder_set_whole_baseline) yet");
+    }
     RunMode r;
     r.frac = m.frac;
-    if (baseline) r.kind = Kind::baseline, r.radius = m.base.n, r.bits = m.base.bits, r.grid = m.base_grid;
+    if (m.font_search) r.kind = m.whole ? Kind::whole_fonts : Kind::fonts, r.grid = m.fonts_grid;
+    else if (baseline) r.kind = Kind::baseline, r.radius = m.base.n, r.bits = m.base.bits, r.grid = m.base_grid;
     else if (candidates) r.kind = Kind::whole_baseline, r.radius = m.wbase.n, r.bits = m.wbase.bits, r.grid = m.whole_grid;
     else if (m.whole) r.kind = m.margins ? Kind::whole_margins : m.slack ? Kind::whole_slack : Kind::whole, r.radius = m.slack, r.grid = m.whole_grid;
     else r.kind = m.pen_search ? Kind::pen_search : Kind::pen_loop, r.radius = m.pen_search, r.scores = m.scores;
@@ -532,6 +550,13 @@ int line_cap(focr_decoder *dec, const RunMode &mode, const WholePlan &plan, Geom
         p = search ? (p - reach) + dec->min_inc : p + dec->min_inc;
         if (++steps > (1u << 20)) return dfail(dec, "focr_decoder_run: the pen advance is too small for the line width");
     }
+    // a font search: every candidate's loop runs with its own increments, so the cap is the largest of the candidates' own
+    for (size_t k = 0; mode.kind == Kind::fonts && k < dec->cands.size(); k++) {
+        uint32_t own = 0;
+        for (p = 0.f; p < (float)g->w; p += dec->cands[k].min_inc)
+            if (++own > (1u << 20)) return dfail(dec, "focr_decoder_run: font candidate " + std::to_string(k + 1) + ": the pen advance is too small for the line width");
+        steps = std::max(steps, own);
+    }
     g->cap = mode.whole() ? plan.cap : std::max<uint32_t>(steps, 1);
     return 0;
 }
@@ -551,6 +576,7 @@ int reserve(focr_decoder *dec, const RunMode &mode, const Geometry &g, const Who
         DEC_GROW(dec->d_base, total);
     }
     if (mode.offsets()) DEC_GROW(dec->d_pen, n_all);
+    if (mode.fonts() && fonts_reserve(dec, mode, g, plan)) return 1;
     if (mode.whole()) return whole_reserve(dec, mode, g, plan);
     return mode.kind == Kind::baseline ? baseline_reserve(dec, g) : 0;
 }
@@ -592,6 +618,8 @@ int launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, const Whol
     case Kind::whole_slack: whole_launch(dec, mode, g, plan, strip_bytes); break;
     case Kind::whole_baseline: whole_baseline_launch(dec, mode, g, plan, strip_bytes); break;
     case Kind::baseline: baseline_launch(dec, mode, g, strip_bytes); break;
+    case Kind::fonts: fonts_launch(dec, mode, g, plan, strip_bytes); break;
+    case Kind::whole_fonts: whole_fonts_launch(dec, mode, g, plan, strip_bytes); break;
     }
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->run.end, dec->stream));
@@ -616,10 +644,10 @@ void append_line(std::vector<T> &to, const std::vector<T> &all, size_t k, uint32
 int collect(focr_decoder *dec, const RunMode &mode, const Geometry &g) {
     const size_t total = g.total, n_all = (size_t)g.cap * total;
     const bool baseline = mode.kind == Kind::baseline;
-    std::vector<uint32_t> count, work, nch, wpens;
+    std::vector<uint32_t> count, work, nch, wpens, lfont;
     std::vector<uint16_t> all, mrunner, runner;
     std::vector<int8_t> pen;
-    std::vector<int64_t> wcost, mmargin, bcost;
+    std::vector<int64_t> wcost, mmargin, bcost, fcost;
     std::vector<int32_t> bq, mterm, term, runner_term;
     std::vector<uint64_t> base;
     if (read_back(dec, count, dec->d_count.p, 1) || read_back(dec, work, dec->d_work.p, total) || read_back(dec, nch, dec->d_nchars.p, total) ||
@@ -628,6 +656,8 @@ int collect(focr_decoder *dec, const RunMode &mode, const Geometry &g) {
     if (mode.offsets() && read_back(dec, pen, dec->d_pen.p, n_all)) return 1;
     if (mode.base_q() && read_back(dec, bq, dec->d_base_q.p, total)) return 1;
     if (baseline && read_back(dec, bcost, dec->d_base_cost.p, total)) return 1;  // under the whole-line decode the cost is that run's
+    if (mode.fonts() && read_back(dec, lfont, dec->d_line_font.p, total)) return 1;
+    if (mode.kind == Kind::fonts && read_back(dec, fcost, dec->d_font_cost.p, total)) return 1;  // under the whole-line decode the cost is that run's
     if (mode.whole() && (read_back(dec, wpens, dec->d_pens.p, n_all) || read_back(dec, wcost, dec->d_cost.p, total))) return 1;
     if (mode.margins() && (read_back(dec, mterm, dec->d_mterm.p, n_all) || read_back(dec, mrunner, dec->d_mrunner.p, n_all) || read_back(dec, mmargin, dec->d_margin.p, n_all)))
         return 1;
@@ -656,6 +686,11 @@ int collect(focr_decoder *dec, const RunMode &mode, const Geometry &g) {
             if (bq[k] < -(int)FOCR_BASELINE_MAX || bq[k] > q_hi) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
             dec->base_q.push_back((int8_t)bq[k]);
             dec->base_cost.push_back(baseline ? bcost[k] : wcost[k]);
+        }
+        if (mode.fonts()) {
+            if (lfont[k] > dec->cands.size()) return dfail(dec, "focr_decoder_run: inconsistent result from the device");
+            dec->line_font.push_back((uint8_t)lfont[k]);
+            dec->font_cost.push_back(mode.kind == Kind::fonts ? fcost[k] : wcost[k]);
         }
         if (mode.whole()) {
             append_line(dec->pens, wpens, k, g.cap, n);
@@ -691,6 +726,7 @@ extern "C" int focr_decoder_run(focr_decoder_t *dec, const uint8_t *pages, int o
     const uint8_t *d_src = nullptr;
     if (stage_in(dec, dec->d_pages, pages, on_device, page_w * page_h * n_pages, &d_src)) return 1;
     WholePlan plan;
+    if (mode.fonts() && fonts_plan(dec, &plan)) return 1;
     if (mode.whole() && whole_plan(dec, mode, g, &plan)) return 1;  // the font and width refusals of include/focr_decode.h, before anything is launched
     if (g.total == 0) {  // nothing to decode and nothing launched; a verify still draws the pages
         DEC_CHECK(hipStreamSynchronize(dec->stream));

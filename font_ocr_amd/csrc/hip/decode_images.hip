@@ -367,6 +367,8 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     dec->verify.ms = 0.f;
     dec->verify.launches = 0;
     if (!dec->last.ok) return dfail(dec, "focr_decoder_verify: no successful focr_decoder_run since the font was set");
+    if (dec->last.mode.fonts())
+        return dfail(dec, "focr_decoder_verify: the last run searched fonts (focr_decoder_set_font_search): drawing every line in its own font is a later step");
     if (!dec->n_vglyphs) return dfail(dec, "focr_decoder_verify: no verify table (focr_decoder_set_verify_font)");
     if (!sq_sums) return dfail(dec, "focr_decoder_verify: null sq_sums");
     const LastRun &run = dec->last;

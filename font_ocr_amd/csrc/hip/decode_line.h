@@ -1,6 +1,7 @@
 // decode_line.h — what the translation units of the `focr` line decoder share (decode.hip: prepass, compaction, the pen
 // loop and its search, and the run itself; decode_whole.hip: the whole-line decode; decode_baseline.hip: the baseline
-// search; decode_whole_baseline.hip: the whole-line decode under every baseline candidate): the strip's constants, the
+// search; decode_whole_baseline.hip: the whole-line decode under every baseline candidate; decode_fonts.hip and
+// decode_whole_fonts.hip: the pen loop and the whole-line decode under every candidate font): the strip's constants, the
 // device helpers the files' kernels call (no relocatable device code: they are inlined into each), and the steps of a run
 // that live beside their kernels: the whole-line decode's plan, buffers and launch, and the baseline search's buffers and
 // launch.  Each takes the run's RunMode (decode.h) and reads no setting.
@@ -56,8 +57,10 @@ __device__ __forceinline__ int footprint_term(const uint32_t *strip, uint32_t sd
 // ---- the whole-line decode as focr_decoder_run sees it (decode_whole.hip) --------------------------------------------
 
 // The plan of a whole-line run: what whole_plan works out from the font, the mode and the geometry before anything is
-// launched, and the launch launches from.
+// launched, and the launch launches from.  A font search (pen loop or whole-line) also plans its candidates here.
 struct WholePlan {
+    std::vector<FontDesc> fonts;        // a font search: the candidates 0 ..= K (fonts_plan; whole_plan fills the whole-line part)
+    std::vector<uint32_t> fonts_inc64;  // ... and under the whole-line form their inc64, candidate-major
     std::vector<uint32_t> inc64;  // per glyph: the pen increment in 1/64 px
     int origin_d = 0;             // 64 * origin_x
     uint32_t batch = 0;           // B: states per batch
@@ -85,5 +88,18 @@ int baseline_reserve(focr_decoder *dec, const Geometry &g);
 // The third launch of a baseline run, on the decoder's stream: line_baseline_kernel, or its form on the fractional grid;
 // the caller checks hipGetLastError.
 void baseline_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, size_t strip_bytes);
+
+// ---- the font search as focr_decoder_run sees it (decode_fonts.hip, decode_whole_fonts.hip) ----------------------------
+
+// The candidates' descriptors into plan->fonts: the decode font, then the uploaded ones.
+int fonts_plan(focr_decoder *dec, WholePlan *plan);
+// The run's per-line result buffers and the descriptors on the device.
+int fonts_reserve(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan);
+// The third launch of a fonts run, on the decoder's stream: line_fonts_kernel; the caller checks hipGetLastError.
+void fonts_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
+// ... and of a whole_fonts run (decode_whole_fonts.hip): line_whole_fonts_kernel.
+void whole_fonts_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
+// The uploaded candidates and their device tables, gone (focr_decoder_set_font).
+void drop_font_candidates(focr_decoder *dec);
 
 }  // namespace focr_dec

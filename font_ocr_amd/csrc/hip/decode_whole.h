@@ -19,6 +19,39 @@ constexpr uint32_t WHOLE_GRID_MAX = 2048;
 // Dwords of a line's runner keys (64-bit) and midpoints beside the ring or in the scratch, a multiple of four.
 __host__ __device__ constexpr uint32_t whole_chars_dwords(uint32_t cap) { return (3 * cap + 3) & ~3u; }
 
+// ---- the host's plan, as the whole-line files share it (decode_whole.hip has the definitions) ------------------------
+
+// The workgroups' scratch of a mode: bytes per state, and the bytes all workgroups together may take.  Plain: a 16-bit
+// backpointer.  Margins: a 64-bit forward key in its place (and the characters' keys and midpoints, counted as states).
+// Slack: an 8-bit offset beside every backpointer, and both count.  Baseline or font candidates: two halves of
+// backpointers, with twice the budget, so that the grid is the plain run's.
+struct WholeScratch {
+    size_t state_bytes, budget;
+};
+constexpr WholeScratch WHOLE_SCRATCH_PLAIN{sizeof(uint16_t), WHOLE_SCRATCH_BUDGET};
+constexpr WholeScratch WHOLE_SCRATCH_MARGINS{sizeof(uint64_t), 4 * WHOLE_SCRATCH_BUDGET};
+constexpr WholeScratch WHOLE_SCRATCH_SLACK{sizeof(uint16_t) + sizeof(int8_t), WHOLE_SCRATCH_BUDGET / 2 * 3};
+constexpr WholeScratch WHOLE_SCRATCH_BASELINE{2 * sizeof(uint16_t), 2 * WHOLE_SCRATCH_BUDGET};
+
+// What the whole-line checks make of one font for a crop of w columns: whole_plan's part that depends on the font alone.
+struct WholeFontPlan {
+    std::vector<uint32_t> inc64;
+    int origin_d = 0;
+    uint32_t batch = 0, ring = 0, max_inc = 0, cap = 1;
+};
+
+// set_font's own bound on a term's magnitude over a glyph table: the largest stride * box_h * 2 * 255^2.
+uint64_t whole_term_bound(const focr_decode_glyph_t *glyphs, uint32_t n);
+// The font refusals of a whole-line run (include/focr_decode.h) for one font, each message behind `pre`, and its plan.
+// T: the bound on a term's magnitude; slack: the pen slack's radius (0 without).
+int whole_font_plan(focr_decoder *dec, const std::string &pre, float ox, const float *inc, uint64_t T, uint32_t n_glyphs, uint32_t slack, uint32_t w,
+                    WholeFontPlan *fp);
+// The scratch of one workgroup (from plan->max_inc and plan->cap) and the grid the mode's budget allows.
+void whole_plan_grid(const RunMode &mode, const Geometry &g, bool margins, const WholeScratch &sc, WholePlan *plan);
+// whole_plan, whole_reserve's part and the launch of a whole_fonts run (decode_whole_fonts.hip).
+int whole_fonts_plan(focr_decoder *dec, const RunMode &mode, const Geometry &g, WholePlan *plan);
+int whole_fonts_reserve(focr_decoder *dec, const WholePlan &plan);
+
 // ---- the LDS of a workgroup ----------------------------------------------------------------------------------------
 
 // Byte offsets into the workgroup's dynamic LDS: a head of 64 bytes (the waves' end keys; the batch's live count and the

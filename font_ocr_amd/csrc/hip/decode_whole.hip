@@ -230,60 +230,65 @@ __global__ __launch_bounds__(WHOLE_THREADS) void line_whole_slack_kernel(const u
 
 // ---- the host's side: plan, buffers, launch (decode_line.h) ----------------------------------------------------------
 
-// The workgroups' scratch of a mode: bytes per state, and the bytes all workgroups together may take.  Plain: a 16-bit
-// backpointer.  Margins: a 64-bit forward key in its place (and the characters' keys and midpoints, counted as states).
-// Slack: an 8-bit offset beside every backpointer, and both count.  Baseline candidates: two halves of backpointers, with
-// twice the budget, so that the grid is the plain run's.
-struct WholeScratch {
-    size_t state_bytes, budget;
-};
-constexpr WholeScratch WHOLE_SCRATCH_PLAIN{sizeof(uint16_t), WHOLE_SCRATCH_BUDGET};
-constexpr WholeScratch WHOLE_SCRATCH_MARGINS{sizeof(uint64_t), 4 * WHOLE_SCRATCH_BUDGET};
-constexpr WholeScratch WHOLE_SCRATCH_SLACK{sizeof(uint16_t) + sizeof(int8_t), WHOLE_SCRATCH_BUDGET / 2 * 3};
-constexpr WholeScratch WHOLE_SCRATCH_BASELINE{2 * sizeof(uint16_t), 2 * WHOLE_SCRATCH_BUDGET};
+uint64_t whole_term_bound(const focr_decode_glyph_t *glyphs, uint32_t n) {
+    uint64_t T = 0;
+    for (uint32_t i = 0; i < n; i++) T = std::max<uint64_t>(T, (uint64_t)glyphs[i].stride * glyphs[i].box_h * 2 * 255 * 255);
+    return T;
+}
 
-int whole_plan(focr_decoder *dec, const RunMode &mode, const Geometry &g, WholePlan *plan) {
-    const uint32_t slack = mode.kind == Kind::whole_slack ? mode.radius : 0;
-    const bool margins = mode.margins(), candidates = mode.kind == Kind::whole_baseline;
-    const float ox = dec->origin_x;
+int whole_font_plan(focr_decoder *dec, const std::string &pre, float ox, const float *inc, uint64_t T, uint32_t n_glyphs, uint32_t slack, uint32_t w,
+                    WholeFontPlan *fp) {
     if (!(ox >= 0.f && ox <= 65536.f && ox == floorf(ox)))
-        return dfail(dec, "focr_decoder_run: whole-line decode needs origin_x to be a whole number >= 0 (at most 65536)");
+        return dfail(dec, pre + "whole-line decode needs origin_x to be a whole number >= 0 (at most 65536)");
     uint32_t lo = ~0u, hi = 0;
-    uint64_t T = 0;  // set_font's own bound on a term's magnitude
-    std::vector<uint32_t> &inc64 = plan->inc64;
-    inc64.resize(dec->n_glyphs);
-    for (uint32_t i = 0; i < dec->n_glyphs; i++) {
-        const float v = rintf(dec->inc[i] * 64.0f);
-        if (!(v >= 1.f)) return dfail(dec, "focr_decoder_run: whole-line decode needs every pen increment to be at least 1/64 px (an inc64 below 1)");
+    std::vector<uint32_t> &inc64 = fp->inc64;
+    inc64.resize(n_glyphs);
+    for (uint32_t i = 0; i < n_glyphs; i++) {
+        const float v = rintf(inc[i] * 64.0f);
+        if (!(v >= 1.f)) return dfail(dec, pre + "whole-line decode needs every pen increment to be at least 1/64 px (an inc64 below 1)");
         inc64[i] = v < 16777216.f ? (uint32_t)v : (1u << 24);
         lo = std::min(lo, inc64[i]), hi = std::max(hi, inc64[i]);
-        T = std::max<uint64_t>(T, (uint64_t)dec->font_glyphs[i].stride * dec->font_glyphs[i].box_h * 2 * 255 * 255);
     }
-    if (candidates && dec->have_base_fonts) T = std::max(T, dec->yterm_bound);  // box sizes differ between y-phases
-    if (64ull * g.w + hi >= (1ull << 24))
-        return dfail(dec, "focr_decoder_run: whole-line decode needs 64 * width + the largest inc64 below 2^24 (pens must stay exact in f32)");
+    if (64ull * w + hi >= (1ull << 24))
+        return dfail(dec, pre + "whole-line decode needs 64 * width + the largest inc64 below 2^24 (pens must stay exact in f32)");
     if (2 * slack > lo)
-        return dfail(dec, "focr_decoder_run: whole-line decode: the pen slack is more than half the smallest inc64 (focr_decoder_set_whole_slack; the pen could crawl)");
+        return dfail(dec, pre + "whole-line decode: the pen slack is more than half the smallest inc64 (focr_decoder_set_whole_slack; the pen could crawl)");
     const uint32_t gain = lo - slack;  // every character advances the arrival state by at least this from below 64 * w; >= 1
-    plan->cap = std::max<uint32_t>((64u * g.w + gain - 1) / gain, 1);
-    if ((uint64_t)plan->cap * T >= (1ull << 47))
-        return dfail(dec, "focr_decoder_run: whole-line decode: characters per line times the font's score bound reaches 2^47 (a packed cost could overflow)");
-    plan->origin_d = 64 * (int)ox;
-    plan->batch = std::min(gain, WHOLE_BATCH_MAX);
-    plan->max_inc = hi;
+    fp->cap = std::max<uint32_t>((64u * w + gain - 1) / gain, 1);
+    if ((uint64_t)fp->cap * T >= (1ull << 47))
+        return dfail(dec, pre + "whole-line decode: characters per line times the font's score bound reaches 2^47 (a packed cost could overflow)");
+    fp->origin_d = 64 * (int)ox;
+    fp->batch = std::min(gain, WHOLE_BATCH_MAX);
+    fp->max_inc = hi;
     uint32_t ring = 64;
-    while (ring < plan->batch + 2 * slack + hi && ring <= WHOLE_RING_MAX) ring *= 2;
+    while (ring < fp->batch + 2 * slack + hi && ring <= WHOLE_RING_MAX) ring *= 2;
     if (ring > WHOLE_RING_MAX)
-        return dfail(dec, slack ? "focr_decoder_run: whole-line decode with pen slack: the widest advance and the slack are too large (the cost ring does not fit in LDS)"
-                                : "focr_decoder_run: whole-line decode: the widest advance is too large (the cost ring does not fit in LDS)");
-    plan->ring = ring;
-    // a workgroup's scratch: a word per state 0 .. 64 * w + max inc64, with margins then the characters' keys and midpoints;
-    // as many workgroups as the mode's budget allows (one always)
-    plan->n_states = 64u * g.w + hi + (margins ? whole_chars_dwords(plan->cap) / 2 : 0);
-    const WholeScratch sc = margins ? WHOLE_SCRATCH_MARGINS : slack ? WHOLE_SCRATCH_SLACK : candidates ? WHOLE_SCRATCH_BASELINE : WHOLE_SCRATCH_PLAIN;
+        return dfail(dec, pre + (slack ? "whole-line decode with pen slack: the widest advance and the slack are too large (the cost ring does not fit in LDS)"
+                                       : "whole-line decode: the widest advance is too large (the cost ring does not fit in LDS)"));
+    fp->ring = ring;
+    return 0;
+}
+
+void whole_plan_grid(const RunMode &mode, const Geometry &g, bool margins, const WholeScratch &sc, WholePlan *plan) {
+    plan->n_states = 64u * g.w + plan->max_inc + (margins ? whole_chars_dwords(plan->cap) / 2 : 0);
     const size_t fit = std::max<size_t>(sc.budget / ((size_t)plan->n_states * sc.state_bytes), 1);
     plan->grid = (uint32_t)std::min<size_t>({g.total, fit, WHOLE_GRID_MAX});
     if (mode.grid) plan->grid = std::min(plan->grid, mode.grid);
+}
+
+int whole_plan(focr_decoder *dec, const RunMode &mode, const Geometry &g, WholePlan *plan) {
+    if (mode.kind == Kind::whole_fonts) return whole_fonts_plan(dec, mode, g, plan);
+    const uint32_t slack = mode.kind == Kind::whole_slack ? mode.radius : 0;
+    const bool margins = mode.margins(), candidates = mode.kind == Kind::whole_baseline;
+    uint64_t T = whole_term_bound(dec->font_glyphs.data(), dec->n_glyphs);  // set_font's own bound on a term's magnitude
+    if (candidates && dec->have_base_fonts) T = std::max(T, dec->yterm_bound);  // box sizes differ between y-phases
+    WholeFontPlan fp;
+    if (whole_font_plan(dec, "focr_decoder_run: ", dec->origin_x, dec->inc.data(), T, dec->n_glyphs, slack, g.w, &fp)) return 1;
+    plan->inc64 = std::move(fp.inc64);
+    plan->cap = fp.cap, plan->origin_d = fp.origin_d, plan->batch = fp.batch, plan->max_inc = fp.max_inc, plan->ring = fp.ring;
+    // a workgroup's scratch: a word per state 0 .. 64 * w + max inc64, with margins then the characters' keys and midpoints;
+    // as many workgroups as the mode's budget allows (one always)
+    whole_plan_grid(mode, g, margins, margins ? WHOLE_SCRATCH_MARGINS : slack ? WHOLE_SCRATCH_SLACK : candidates ? WHOLE_SCRATCH_BASELINE : WHOLE_SCRATCH_PLAIN, plan);
     return 0;
 }
 
@@ -295,13 +300,13 @@ int whole_reserve(focr_decoder *dec, const RunMode &mode, const Geometry &g, con
         DEC_GROW(dec->d_mrunner, chars);
         DEC_GROW(dec->d_margin, chars);
     } else
-        DEC_GROW(dec->d_back, mode.base_q() ? 2 * scratch : scratch);  // baseline candidates: two halves per workgroup
+        DEC_GROW(dec->d_back, mode.halves() ? 2 * scratch : scratch);  // baseline or font candidates: two halves per workgroup
     if (mode.base_q()) DEC_GROW(dec->d_base_q, g.total);
     if (mode.kind == Kind::whole_slack) DEC_GROW(dec->d_woff, scratch);
     DEC_GROW(dec->d_pens, chars);
     DEC_GROW(dec->d_cost, g.total);
     if (!dec->d_inc64.p) DEC_UPLOAD(dec->d_inc64, plan.inc64.data(), plan.inc64.size());
-    return 0;
+    return mode.kind == Kind::whole_fonts ? whole_fonts_reserve(dec, plan) : 0;
 }
 
 // The strip shares LDS with what whole_layout puts before it; with margins the characters' keys and midpoints come first:

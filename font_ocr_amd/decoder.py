@@ -29,6 +29,11 @@
         pages, baselines, costs = dec.decode(luma_pages, 45, 39, 608, 12, 15, baseline_search=1, y_frac=20, line_advance_frac=38)
         # a fractional line grid for the two baseline modes: the first line's top at 39 + 20/64 px and a leading of
         # 15 + 38/64 px; every line is cropped at the whole row of its own top and searched around its own sub-pixel part
+        dec.set_font_candidates([("DejaVuSansMono.ttf", 12.0, False, 1.0), ("DejaVuSansMono-Bold.ttf", 13.0, False, 1.0)])
+        pages, fonts, costs = dec.decode(luma_pages, 45, 39, 608, 12, 15, font_search=True)
+        # every line decoded in the decode font (0) and in each candidate (1, 2) and the cheapest reading kept: pages that
+        # mix fonts, or a font whose size, kerning or hinting is being looked for; fonts[page][line]: the winner's index,
+        # costs[page][line]: its sum of footprint terms.  With whole_line=True: pages, pens, costs, fonts
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -70,15 +75,16 @@ class LineMargins(collections.namedtuple("LineMargins", "term runner margin")):
 
 
 # The modes of one decode()/decode_device() call, checked (LineDecoder._modes).
-_Modes = collections.namedtuple("_Modes", "scores pen_search whole_line margins pen_slack baseline_search whole_baseline line_frac")
+_Modes = collections.namedtuple("_Modes", "scores pen_search whole_line margins pen_slack baseline_search whole_baseline line_frac font_search")
 
 # The results of one call as per-page lists, in the order of the public tuple; None where the modes write no such result.
-_Run = collections.namedtuple("_Run", "text scores offsets pens costs margins slack_offsets whole_qs baselines baseline_costs")
+_Run = collections.namedtuple("_Run", "text scores offsets pens costs margins slack_offsets whole_qs baselines baseline_costs fonts font_costs")
 
 
 def _record(m, make):
     """A _Run with make() in the fields the modes m fill, and None in the others."""
-    on = (True, m.scores, m.pen_search, m.whole_line, m.whole_line, m.margins, m.pen_slack, m.whole_baseline, m.baseline_search, m.baseline_search)
+    on = (True, m.scores, m.pen_search, m.whole_line, m.whole_line, m.margins, m.pen_slack, m.whole_baseline, m.baseline_search, m.baseline_search,
+          m.font_search, m.font_search and not m.whole_line)
     return _Run(*(make() if o else None for o in on))
 
 
@@ -87,7 +93,8 @@ def _record(m, make):
 _SETTINGS = (("_baseline", "focr_decoder_set_baseline_search", (0, 0)), ("_whole_baseline", "focr_decoder_set_whole_baseline", (0, 0)),
              ("_line_frac", "focr_decoder_set_line_frac", (0, 0)), ("_pen_slack", "focr_decoder_set_whole_slack", 0),
              ("_margins", "focr_decoder_set_whole_margins", False), ("_whole", "focr_decoder_set_whole_line", False),
-             ("_pen_search", "focr_decoder_set_pen_search", 0), ("_scores", "focr_decoder_set_scores", False))
+             ("_pen_search", "focr_decoder_set_pen_search", 0), ("_scores", "focr_decoder_set_scores", False),
+             ("_font_search", "focr_decoder_set_font_search", False))
 
 
 def _err():
@@ -242,6 +249,7 @@ class LineDecoder:
         self.last_test_ms = 0.0
         self._vfont = None
         self._batch = None  # (n_pages, page_h, page_w) of the last run
+        self._candidates = []  # the DecodeFonts of set_font_candidates
         for attr, _, default in _SETTINGS:
             setattr(self, attr, default)
 
@@ -255,11 +263,33 @@ class LineDecoder:
         of 2^-y_bits px; a DecodeFont brings its own."""
         font = font_path if isinstance(font_path, DecodeFont) else DecodeFont(font_path, text_size, alphabet, hinting, kerning, y_bits)
         self._vfont, self._batch = None, None  # the library drops its verify table, its y-phase fonts and its last run here too
+        self._candidates = []  # ... and the candidates of the font search
         self._check(self._lib.focr_decoder_set_font(self._h, C.byref(font.s)))
         self.font = font
         if font.y_bits:
             self._check(self._lib.focr_decoder_set_baseline_fonts(self._h, font.fonts, font.y_bits))
         return font
+
+    def set_font_candidates(self, fonts):
+        """Upload the candidates 1 ..= K of decode(font_search=True), K <= 15: a list of DecodeFonts over the decode font's
+        alphabet, or of (font_path, text_size, hinting, kerning) tuples, which are built with it.  An empty list drops them, and
+        so does set_font().  Returns the DecodeFonts."""
+        if self.font is None:
+            raise DecoderError("set_font() first")
+        fonts = list(fonts)
+        if len(fonts) > 15:
+            raise ValueError(f"at most 15 font candidates, not {len(fonts)}")
+        built = [f if isinstance(f, DecodeFont) else DecodeFont(f[0], f[1], self.font.alphabet, f[2], f[3]) for f in fonts]
+        for f in built:
+            if f.alphabet != self.font.alphabet:
+                raise ValueError("a font candidate must have the decode font's alphabet")
+        arr = (N.DecodeFontStruct * max(1, len(built)))()
+        for i, f in enumerate(built):
+            arr[i] = f.s  # the struct by value: its tables stay the DecodeFont's
+        self._candidates = []
+        self._check(self._lib.focr_decoder_set_font_candidates(self._h, arr, len(built)))
+        self._candidates = built
+        return built
 
     def verify(self, images=True, rgb_device=None):
         """focr --verify of the last decode on the device: (sums, images).  sums[p] is page p's exact sum of
@@ -268,6 +298,8 @@ class LineDecoder:
         this library uses with room for N * H * W * 3 bytes.  The verify table is built on first use."""
         if self._batch is None:
             raise DecoderError("verify: no decode since the font was set")
+        if self._font_search:
+            raise DecoderError("verify: the last decode searched fonts (drawing every line in its own font is a later step)")
         self._ensure_verify_font()
         n, h, w = self._batch
         sums = np.zeros(max(1, n), dtype=np.uint64)
@@ -366,7 +398,7 @@ class LineDecoder:
         self._batch = None
         y_bits = self.font.y_bits
         values = ((y_bits if m.baseline_search else 0, m.baseline_search), (y_bits if m.whole_baseline else 0, m.whole_baseline), m.line_frac,
-                  m.pen_slack, m.margins, m.whole_line, m.pen_search, m.scores)
+                  m.pen_slack, m.margins, m.whole_line, m.pen_search, m.scores, m.font_search)
         for (attr, setter, _), value in zip(_SETTINGS, values):
             if value != getattr(self, attr):
                 self._check(getattr(self._lib, setter)(self._h, *(value if isinstance(value, tuple) else (int(value),))))
@@ -396,10 +428,14 @@ class LineDecoder:
             bq = np.zeros(max(1, nl), dtype=np.int8)
             bc = np.zeros(max(1, nl), dtype=np.int64)
             self._check(self._lib.focr_decoder_get_baselines(self._h, bq.ctypes.data, bc.ctypes.data))
+        if m.font_search:
+            fk = np.zeros(max(1, nl), dtype=np.uint8)
+            fc = np.zeros(max(1, nl), dtype=np.int64)
+            self._check(self._lib.focr_decoder_get_fonts(self._h, fk.ctypes.data, fc.ctypes.data))
         alpha = self.font.alphabet
         r = _record(m, lambda: [[] for _ in range(n)])
-        text, sc, offs, pens, costs, mar, slack_offs, whole_qs, bqs, bcosts = r  # locals, like the modes: the loop runs once per line
-        scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, _ = m
+        text, sc, offs, pens, costs, mar, slack_offs, whole_qs, bqs, bcosts, fonts, fcosts = r  # locals, like the modes: the loop runs once per line
+        scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, _, font_search = m
         for k in range(nl):
             ln = lines[k]
             page, at = ln.page, slice(ln.first, ln.first + ln.n_chars)
@@ -423,12 +459,16 @@ class LineDecoder:
             if baseline_search:
                 bqs[page].append(int(bq[k]))
                 bcosts[page].append(int(bc[k]))
+            if font_search:
+                fonts[page].append(int(fk[k]))
+                if fcosts is not None:
+                    fcosts[page].append(int(fc[k]))
         return r
 
     @staticmethod
     def _assemble(verified, r):
         """The public result of decode() and decode_device(): (lines[, mse, images][, scores][, offsets][, pens, costs][, margins]
-        [, slack offsets][, whole-baseline qs][, baselines, costs]), or the bare lines when nothing else was asked for.
+        [, slack offsets][, whole-baseline qs][, baselines, costs][, fonts[, costs]]), or the bare lines when nothing else was asked for.
         verified: () or (mse, images)."""
         res = (r.text,) + verified + tuple(v for v in r[1:] if v is not None)
         return res if len(res) > 1 else r.text
@@ -496,7 +536,17 @@ class LineDecoder:
             raise ValueError("y_frac and line_advance_frac need baseline_search or whole_baseline (no other mode renders at a sub-pixel row yet)")
         return fr
 
-    def _modes(self, verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac):
+    def _check_font_search(self, font_search, verify, scores, pen_search, margins, pen_slack, baseline_search, whole_baseline):
+        for on, what in ((scores, "scores=True"), (pen_search, "pen_search"), (margins, "margins=True"), (pen_slack, "pen_slack"),
+                         (baseline_search, "baseline_search"), (whole_baseline, "whole_baseline"), (verify, "verify")):
+            if font_search and on:
+                raise ValueError(f"font_search=True does not go with {what} yet (the candidates run the plain pen loop or the plain whole-line decode)")
+        if font_search and not getattr(self, "_candidates", None):
+            raise ValueError("font_search=True needs candidates (set_font_candidates)")
+        return bool(font_search)
+
+    def _modes(self, verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac,
+               font_search=False):
         """The checks of decode() and decode_device() in their order, and the modes as one record."""
         if self.font is None:
             raise DecoderError("set_font() first")
@@ -508,10 +558,11 @@ class LineDecoder:
         baseline_search = self._check_baseline_search(baseline_search, scores, pen_search, whole_line, margins, pen_slack)
         whole_baseline = self._check_whole_baseline(whole_baseline, whole_line, margins, pen_slack)
         line_frac = self._check_line_frac(y_frac, line_advance_frac, baseline_search, whole_baseline)
-        return _Modes(bool(scores), pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, line_frac)
+        font_search = self._check_font_search(font_search, verify, scores, pen_search, margins, pen_slack, baseline_search, whole_baseline)
+        return _Modes(bool(scores), pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, line_frac, font_search)
 
     def decode(self, luma_pages, x, y, width, line_height, line_advance, verify=None, scores=False, pen_search=0, pen_slack=0,
-               baseline_search=0, whole_baseline=0, y_frac=0, line_advance_frac=0, margins=False, whole_line=False):
+               baseline_search=0, whole_baseline=0, y_frac=0, line_advance_frac=0, font_search=False, margins=False, whole_line=False):
         """luma_pages: one (H, W) uint8 page, an (N, H, W) batch, or a list of pages (grouped by size into batches).
         Returns [[(y, text), ...] per page] in page order.  With verify="mse" or "image", returns (lines, mse, images):
         mse is focr --verify's red/blue MSE per page (f32, page order), images the (H, W, 3) verify image per page for
@@ -548,8 +599,14 @@ class LineDecoder:
         whole_baseline, the lines lie on a fractional grid: line i's top is at y + y_frac / 64 + i * (line_advance +
         line_advance_frac / 64) px, its crop starts at the whole row of that (the y of the result's line), and its candidates
         are searched around its own sub-pixel part; the returned q is the absolute one, so y + q * 2^-y_bits px stays the
-        line's top.  For pages whose leading is not a whole number of pixels.  Without either search: ValueError."""
-        m = self._modes(verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac)
+        line's top.  For pages whose leading is not a whole number of pixels.  Without either search: ValueError.
+        With font_search=True (an extension; include/focr_decode.h) every line is decoded once in the decode font (candidate 0)
+        and once in every font of set_font_candidates() (1 ..= K), by the plain pen loop, or by the whole-line decode with
+        whole_line=True, and the candidate with the lowest summed footprint term is the line (on a tie the first).  The result
+        gains two last elements: fonts[page][line], the winner's index (int), and costs[page][line], its sum of footprint
+        terms (int); with whole_line=True it gains fonts alone, after costs, which are then the winner's.  It goes with none of
+        scores, pen_search, margins, pen_slack, baseline_search, whole_baseline and verify, and needs candidates (ValueError)."""
+        m = self._modes(verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac, font_search)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
         if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
             pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
@@ -574,11 +631,11 @@ class LineDecoder:
         return self._assemble((mse, images) if verify else (), out)
 
     def decode_device(self, ptr, n_pages, page_h, page_w, x, y, width, line_height, line_advance, verify=None, scores=False,
-                      pen_search=0, pen_slack=0, baseline_search=0, whole_baseline=0, y_frac=0, line_advance_frac=0, margins=False,
-                      whole_line=False):
+                      pen_search=0, pen_slack=0, baseline_search=0, whole_baseline=0, y_frac=0, line_advance_frac=0, font_search=False,
+                      margins=False, whole_line=False):
         """As decode(), for n_pages equal-size pages already in device memory at `ptr` (an address of the HIP runtime
         this library uses, on the decoder's device, written before the call and still valid for the verify)."""
-        m = self._modes(verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac)
+        m = self._modes(verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac, font_search)
         r = self._run(C.c_void_p(int(ptr)), True, int(n_pages), int(page_h), int(page_w), int(x), int(y), int(width), int(line_height),
                       int(line_advance), m)
         if not verify:

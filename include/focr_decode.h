@@ -432,6 +432,59 @@ int focr_decoder_set_whole_baseline(focr_decoder_t *dec, uint32_t y_bits, uint32
  * is created; a state of the decoder, not of the font).  A value above 63 is refused here. */
 int focr_decoder_set_line_frac(focr_decoder_t *dec, uint32_t y_frac, uint32_t advance_frac);
 
+/* ---- device: font candidates (an extension: the reference decodes every line in one font) --------------------------- */
+
+/* The reference, and every mode above, assumes that every line of every page is set in one font at one size, one kerning
+ * and one hinting setting.  Someone looking for those parameters runs the whole job once per guess and compares verify
+ * MSEs by eye; someone whose pages mix fonts (a bold or monospace line inside body text, a heading one size up) gets
+ * garbage for every line that is not in the decode font, and nothing says which lines those are.  The quantity that
+ * separates fonts is the one the decoder already computes: a line's summed footprint terms, its squared error less
+ * line_base.  With the font search on, a run decodes every line once per candidate font and keeps the cheapest.
+ * A candidate font is a focr_decode_font_t with the decode font's glyph count and code points, in the same order;
+ * everything else may differ: size, kerning, hinting, increments, boxes, origin_x and origin_y.  Candidate 0 is the decode
+ * font of focr_decoder_set_font; candidates 1 ..= K are the uploaded ones, K <= FOCR_FONT_CANDIDATES_MAX - 1 = 15.
+ * All of it is exact:
+ *   - plain run: every non-blank line is decoded once per candidate k by the plain pen loop, unchanged: the f32 pen,
+ *     delta x = trunc((origin_x_k + pos) * 64), the first minimum over the glyphs, while pos < width, with candidate k's
+ *     own tables, increments and origin_x; cost_k is the int64 sum of the chosen glyphs' int32 footprint terms;
+ *   - whole-line run (focr_decoder_set_whole_line): every line is decoded once per candidate by the whole-line programme
+ *     exactly as defined above, with candidate k's own inc64, origin_x, terms and end state; cost_k is the end state's cost;
+ *   - the line is the candidate with the lowest (cost_k, k): on a tie the first candidate wins, so candidate 0 beats an
+ *     identical upload;
+ *   - the run returns that candidate's text as indices into the common alphabet, and per line k and cost_k
+ *     (focr_decoder_get_fonts); a whole-line run also returns the winner's pens and the same cost (focr_decoder_get_pens);
+ *   - prepass and compaction are unchanged and the launch count stays 3;
+ *   - the characters per line at most are the largest of the candidates' own bounds: the pen loop's walk with each
+ *     candidate's smallest increment, ceil(64 * width / min inc64_k) under the whole-line form.
+ * With the search off every run launches and returns what it did before the search existed, whatever is uploaded.
+ * focr_decoder_run refuses, before anything is launched and each with a message:
+ *   - the search on with no candidates uploaded (the message names the switch and the upload call);
+ *   - the search on beside scores, a pen search, margins, a pen slack, a baseline search or baseline candidates of a
+ *     whole-line run (each message names both setters and ends in "yet"); a fractional line grid is refused by its own rule;
+ *   - under the whole-line form, any candidate that fails one of the whole-line run's own checks with its own font: an
+ *     origin_x that is not a whole number >= 0, an inc64 < 1, 64 * width + max inc64_k >= 2^24,
+ *     ceil(64 * width / min inc64_k) * T_k >= 2^47, or a cost ring that does not fit in LDS; the message names the
+ *     candidate's index.
+ * focr_decoder_verify after a font-search run is refused with a message: drawing every line in its own font is a later
+ * step.  focr_decoder_test_images knows no candidates.
+ * What it does not cure: under the pen loop it is a monospace tool, as the greedy loop itself is (a proportional line is
+ * lost under every candidate, and the cheapest wrong reading picks the font: that case needs the whole-line form);
+ * focr --verify of a mixed-font run; candidates under scores, the pen search, margins, the pen slack or the baseline modes;
+ * and candidates with different alphabets. */
+enum { FOCR_FONT_CANDIDATES_MAX = 16 };
+/* Upload candidates 1 ..= n (the decoder keeps its own copy); n == 0 or NULL drops them; focr_decoder_set_font drops them,
+ * and so does a failed upload.  Refused: n > 15, a glyph count or code point that differs from the decode font's, a glyph
+ * table that fails set_font's own consistency and int32 checks, an increment <= 0. */
+int focr_decoder_set_font_candidates(focr_decoder_t *dec, const focr_decode_font_t *fonts, uint32_t n);
+/* Switch the search of later runs on or off (off when the decoder is created; a state of the decoder, not of the font). */
+int focr_decoder_set_font_search(focr_decoder_t *dec, int on);
+/* The winner k and cost of every line of the last run, in the order of focr_decoder_get: font[n_lines], cost[n_lines].
+ * Either may be NULL.  Fails with a message unless the last successful run searched fonts. */
+int focr_decoder_get_fonts(const focr_decoder_t *dec, uint8_t *font, int64_t *cost);
+/* Debug: at most `grid` workgroups for later font-search runs (0: the decoder's own choice), so that a test can make one
+ * workgroup take several lines. */
+int focr_decoder_debug_set_fonts_grid(focr_decoder_t *dec, uint32_t grid);
+
 /* ---- device: verify images of the last run (draw_verify + red_blue_mse, src/main.rs:300-329, 518-524) ------------ */
 
 /* Upload the verify table of the current decode font (the decoder keeps its own copy).  Refused unless it matches the
@@ -452,7 +505,8 @@ int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_verify_font_t *
  * sub-pixel part of the offset is not drawn (the verify table has one vertical phase).  After a whole-line run under
  * baseline candidates (focr_decoder_set_whole_baseline) both rules hold: every character at pos = s / 64 of its returned
  * pen, on a canvas moved and clipped in that way.  Runs a fixed number of launches and returns when the results are in rgb and sq_sums.  Fails with a message
- * without a successful run since the last set_font, or without a verify table. */
+ * without a successful run since the last set_font, without a verify table, or after a run that searched fonts
+ * (focr_decoder_set_font_search): the table has one font, and drawing every line in its own is a later step. */
 int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums);
 /* Device time of the last verify's kernels in ms (events), and their launch count (constant per batch). */
 float focr_decoder_last_verify_ms(const focr_decoder_t *dec);

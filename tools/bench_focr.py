@@ -74,6 +74,18 @@ line_advance_frac=A)), in runs that alternate with the same mode at the same rad
   frac_wall_ms_per_batch      median host time of one decode call with the grid on
   frac_lines, frac_off_lines  non-blank lines found on either grid
   frac_lines_changed          lines of the batch whose text differs between the two grids (by position in the page)
+With --font-candidates SIZES (comma-separated text sizes, K of them), also the decode with the font search on
+(LineDecoder.decode(font_search=True)) over the decode font and K candidates of the same face at those sizes, in runs that
+alternate with plain ones; with --whole-line as well, the same under the whole-line decode, alternating with whole-line runs:
+  fonts_device_ms_per_batch   median device time of the batch's kernels with the search on (the same 3 launches)
+  fonts_plain_device_ms       median device time of the plain runs in between
+  fonts_over_plain            the ratio of the two, beside fonts_candidates = K + 1 decodes per line and fonts_ceiling = K + 2,
+                              what one plain run per candidate and one more for the winner would cost
+  fonts_wall_ms_per_batch     median host time of one decode(font_search=True) call, winners and costs read back
+  fonts_lines_changed         lines of the batch the search decodes differently from the plain run
+  fonts_lines_other           lines of the batch won by another candidate than the decode font
+  wfonts_*                    the same under the whole-line decode, over wfonts_whole_device_ms; wfonts_ceiling = K + 1: one
+                              whole-line run per candidate (the winner is not decoded again)
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -163,6 +175,8 @@ def main():
     ap.add_argument("--y-bits", type=int, default=0, metavar="B", help="with --baseline-search or --whole-baseline: steps of 2^-B px")
     ap.add_argument("--line-frac", default=None, metavar="Y,A",
                     help="with --baseline-search or --whole-baseline: draw the pages on the fractional line grid and also time the mode with the grid on")
+    ap.add_argument("--font-candidates", default=None, metavar="SIZES",
+                    help="also time the font search over the decode font and candidates of the same face at these sizes (comma-separated)")
     ap.add_argument("--font", default=FONT, metavar="PATH", help="the font of the pages and of the decoder [DejaVu Sans Mono]")
     a = ap.parse_args()
     if a.margins and not a.whole_line:
@@ -173,6 +187,14 @@ def main():
         ap.error("--whole-baseline needs --whole-line")
     if a.y_bits and not (a.baseline_search or a.whole_baseline):
         ap.error("--y-bits needs --baseline-search or --whole-baseline")
+    sizes = []
+    if a.font_candidates:
+        try:
+            sizes = [float(v) for v in a.font_candidates.split(",")]
+        except ValueError:
+            ap.error("--font-candidates takes comma-separated text sizes")
+        if not 1 <= len(sizes) <= 15:
+            ap.error("--font-candidates takes 1 .. 15 sizes")
     frac = None
     if a.line_frac is not None:
         try:
@@ -309,6 +331,31 @@ def main():
                 fwall.append((time.perf_counter() - t) * 1e3)
                 fdev.append(dec.last_ms)
             flaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+        if sizes:
+            dec.set_font_candidates([(a.font, t, False, 1.0) for t in sizes])
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, font_search=True)
+            gdev, gwall, gpdev = [], [], []
+            for _ in range(a.steps):
+                dec.decode(pages, *geo)
+                gpdev.append(dec.last_ms)
+                t = time.perf_counter()
+                ggot = dec.decode(pages, *geo, font_search=True)
+                gwall.append((time.perf_counter() - t) * 1e3)
+                gdev.append(dec.last_ms)
+            glaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+        if sizes and a.whole_line:
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo, whole_line=True, font_search=True)
+            hdev, hwall, hwdev = [], [], []
+            for _ in range(a.steps):
+                href = dec.decode(pages, *geo, whole_line=True)
+                hwdev.append(dec.last_ms)
+                t = time.perf_counter()
+                hgot = dec.decode(pages, *geo, whole_line=True, font_search=True)
+                hwall.append((time.perf_counter() - t) * 1e3)
+                hdev.append(dec.last_ms)
+            hlaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
         if a.test_images:
             for _ in range(a.warmup):
                 dec.test_images(pages, *geo)
@@ -389,6 +436,22 @@ def main():
                     "frac_device_ms_min": round(float(min(fdev)), 4), "frac_off_device_ms": round(foms, 4), "frac_over_off": round(fms / foms, 4),
                     "frac_launches": flaunches, "frac_wall_ms_per_batch": round(float(np.median(fwall)), 3),
                     "frac_lines": sum(len(pg) for pg in fgot[0]), "frac_off_lines": sum(len(pg) for pg in foff[0]), "frac_lines_changed": changed})
+    if sizes:
+        gms, gpms = float(np.median(gdev)), float(np.median(gpdev))
+        changed = sum(ta != tb for pa, pb in zip(out, ggot[0]) for (_, ta), (_, tb) in zip(pa, pb))
+        other = sum(k != 0 for pg in ggot[1] for k in pg)
+        res.update({"font_candidate_sizes": sizes, "fonts_candidates": len(sizes) + 1, "fonts_ceiling": len(sizes) + 2,
+                    "fonts_device_ms_per_batch": round(gms, 4), "fonts_device_ms_min": round(float(min(gdev)), 4),
+                    "fonts_plain_device_ms": round(gpms, 4), "fonts_over_plain": round(gms / gpms, 3), "fonts_launches": glaunches,
+                    "fonts_wall_ms_per_batch": round(float(np.median(gwall)), 3), "fonts_lines_changed": changed, "fonts_lines_other": other})
+    if sizes and a.whole_line:
+        hms, hwms = float(np.median(hdev)), float(np.median(hwdev))
+        changed = sum(ta != tb for pa, pb in zip(href[0], hgot[0]) for (_, ta), (_, tb) in zip(pa, pb))
+        other = sum(k != 0 for pg in hgot[3] for k in pg)
+        res.update({"wfonts_candidates": len(sizes) + 1, "wfonts_ceiling": len(sizes) + 1, "wfonts_device_ms_per_batch": round(hms, 4),
+                    "wfonts_device_ms_min": round(float(min(hdev)), 4), "wfonts_whole_device_ms": round(hwms, 4),
+                    "wfonts_over_whole": round(hms / hwms, 3), "wfonts_launches": hlaunches,
+                    "wfonts_wall_ms_per_batch": round(float(np.median(hwall)), 3), "wfonts_lines_changed": changed, "wfonts_lines_other": other})
     if a.test_images:
         tms = float(np.median(tdev))
         res.update({"test_device_ms_per_batch": round(tms, 4), "test_launches": tlaunches, "test_wall_ms": round(float(np.median(twall)), 3),
