@@ -127,6 +127,9 @@ HIP_SYMBOLS = {
     "focr_debug_set_tail_grid": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "focr_debug_phase_stamps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "focr_debug_tail_path": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "focr_debug_scan_paired": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "focr_debug_bank_images": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                         C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "focr_debug_set_stats_form": (C.c_int, [C.c_void_p, C.c_int]),
     "focr_debug_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "focr_ctx_set_size_estimates": (C.c_int, [C.c_void_p, C.c_int]),

@@ -55,11 +55,20 @@ void layout_supers(focr_ctx *c) {
         su.tile_first.push_back(su.n_tiles);
         su.n_tiles += sc.n_tiles16;
     }
+    // Row pairs: a K block covers more rows than a class is tall (BASELINE configs[1]: 15-row classes in LAYOUT_W8's 16 rows), so the
+    // fragments a wave loads for window row y also hold the whole of window row y + 1 — against templates that sit one row lower in
+    // the block.  A super-class gets that second operand image behind its first one when every class of it leaves the block's last
+    // row empty and both images fit the LDS of its one launch (scan_mfma2.hip, PAIR; whether a scan uses it: plan_passes).
+    for (SuperClass &su : c->supers) {
+        const uint32_t block_rows = su.layout == LAYOUT_W16 ? 4 * su.ksteps : su.layout == LAYOUT_W8 ? 8 * su.ksteps : 16 * (su.ksteps / 3);
+        su.pairable = 2 * su.n_tiles <= mfma2_chunk_tiles(su.ksteps);
+        for (uint32_t k : su.classes) su.pairable &= c->bank.classes[k].n_h + 1 <= block_rows;
+    }
     size_t q_bytes = 0, tg_entries = 0;
     for (SuperClass &su : c->supers) {
         su.q_offset = q_bytes;
         su.tg_offset = tg_entries;
-        q_bytes += (size_t)su.n_tiles * su.ksteps * 1024;
+        q_bytes += (size_t)su.n_tiles * su.ksteps * 1024 * (su.pairable ? 2 : 1);
         tg_entries += (size_t)su.n_tiles * 16;
         for (size_t i = 0; i < su.classes.size(); i++) {
             SizeClass &sc = c->bank.classes[su.classes[i]];
@@ -91,9 +100,11 @@ static std::vector<uint32_t> live_first_slots(const std::vector<std::vector<doub
 int quantise_bank(focr_ctx *c, const uint8_t *dense, std::vector<int8_t> &qbank, std::vector<uint32_t> &tglobal, std::vector<uint32_t> &order_of) {
     layout_supers(c);
     size_t q_bytes = 0, tg_entries = 0;
+    std::vector<size_t> image1(c->bank.classes.size(), 0);  // per class: distance of its bytes in the super-class's second image (0: none)
     for (const SuperClass &su : c->supers) {
-        q_bytes += (size_t)su.n_tiles * su.ksteps * 1024;
+        q_bytes += (size_t)su.n_tiles * su.ksteps * 1024 * (su.pairable ? 2 : 1);
         tg_entries += (size_t)su.n_tiles * 16;
+        for (uint32_t k : su.classes) image1[k] = su.pairable ? (size_t)su.n_tiles * su.ksteps * 1024 : 0;
     }
     qbank.assign(q_bytes, 0);
     tglobal.assign(tg_entries, 0xffffffffu);
@@ -187,6 +198,10 @@ int quantise_bank(focr_ctx *c, const uint8_t *dense, std::vector<int8_t> &qbank,
                     uint32_t ks, g, byte;
                     kgroup_of(sc.layout, j, x, &ks, &g, &byte);
                     qbank[sc.q_offset + ((size_t)(nt * ksteps + ks) * 64 + g * 16 + nn) * 16 + byte] = (int8_t)bq[j * kw + x];
+                    if (image1[k]) {  // the second image: the same value one row lower in the K block (its last row is free: layout_supers)
+                        kgroup_of(sc.layout, j + 1, x, &ks, &g, &byte);
+                        qbank[image1[k] + sc.q_offset + ((size_t)(nt * ksteps + ks) * 64 + g * 16 + nn) * 16 + byte] = (int8_t)bq[j * kw + x];
+                    }
                 }
         }
         c->bank.mfma_c_scale.push_back(c_scale);

@@ -52,10 +52,14 @@ struct SuperClass {
     std::vector<uint32_t> tile_first;  // first N-tile of each class inside the super-class
     uint32_t n_tiles;
     size_t q_offset, tg_offset;
+    // Row pairs (scan_mfma2.hip, PAIR): every class leaves the last row of its K block empty and twice the N-tiles fit one launch, so
+    // d_qbank holds a second operand image right behind the first, every template one row lower in its K block (layout_supers)
+    bool pairable;
     // per scan (plan_scan): window enumeration of the pass (smallest searchable template), its live-tile list, its threshold planes
     uint32_t min_w, min_h, mtx, n_rows;
     size_t live_offset, plane_off;  // plane_off: first value in d_planes, if `planes` (else the legacy path: int32 tables in d_L)
     bool planes;
+    bool paired;  // this scan's work list holds row pairs and the scan kernel takes both images (plan_passes: pairable, planes, the statistics append)
 };
 
 // What a scan of the batch launches, decided before anything is enqueued (plan_scan, scan_mfma.hip: also every buffer sized)
@@ -443,6 +447,7 @@ int launch_scan_mfma(focr_ctx *ctx, float threshold);
 // stats.hip
 int launch_clear(focr_ctx *c, const focr::ClearList &l);  // zero every region of the list in one launch
 int pass_stats(focr_ctx *c, const ScanPlan &P, size_t si, double thr_d);  // one scan pass's statistics launches and its work list, queued on the context's stream
+bool pass_appends(const focr_ctx *c, const SuperClass &su);               // a plane pass's statistics append the work list themselves (no mark bytes)
 // bank_mfma.hip (host only)
 int build_mfma_bank(focr_ctx *ctx, const uint8_t *needles);
 void layout_supers(focr_ctx *c);  // size classes -> super-classes, MFMA K layouts, bank offsets

@@ -245,6 +245,7 @@ struct MfmaLaunch {
     uint32_t mtx, n_rows;   // window enumeration of the pass: M-tiles per row, searched rows (y = 1 + row)
     const uint64_t *live_list;   // packed (page << 32 | row << 12 | col) of the M-tiles that have something to scan
     const uint32_t *live_count;  // device-side length of live_list
+    bool paired;                 // an entry is a pair of image rows (y, y + 1), row = y (even); the chunk's second operand image follows its first
     uint32_t super_index;
     uint32_t *queue;      // the launch's item queue (zeroed at the start of the scan)
     MfmaSegs segs;

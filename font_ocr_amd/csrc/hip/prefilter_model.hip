@@ -262,6 +262,37 @@ extern "C" int focr_debug_prefilter_page(const focr_template_t *templates, size_
     return FOCR_OK;
 }
 
+// The MFMA operand images of a bank as focr_bank_upload builds them (focr_debug_bank_images, include/focr_ncc.h): the raw bytes of
+// d_qbank and, per super-class, where its first image starts and whether a second one follows it (row pairs, layout_supers).
+extern "C" int focr_debug_bank_images(const focr_template_t *templates, size_t n_templates, const uint8_t *needles, size_t needles_len, int column_drop,
+                                      uint32_t *super_info, size_t super_cap, size_t *n_supers, int8_t *out, size_t capacity, size_t *n_bytes) {
+    if (!templates || !n_templates || !needles || !n_supers || !n_bytes) return FOCR_ERR_INVALID;
+    for (size_t t = 0; t < n_templates; t++)
+        if (templates[t].n_w == 0 || templates[t].n_h == 0 || templates[t].n_w > 16 || templates[t].n_h > 32 ||
+            (size_t)templates[t].offset + (size_t)templates[t].n_w * templates[t].n_h > needles_len)
+            return FOCR_ERR_INVALID;
+    focr_ctx ctx;  // host state only
+    focr_ctx *c = &ctx;
+    c->column_drop = column_drop != 0;
+    std::vector<uint32_t> direct, tglobal, order_of;
+    std::vector<uint8_t> dense;
+    std::vector<int8_t> qbank;
+    bank_host_prepare(c, templates, n_templates, needles, direct, dense);
+    if (int rc = quantise_bank(c, dense.data(), qbank, tglobal, order_of)) return rc;
+    *n_supers = c->supers.size();
+    *n_bytes = qbank.size();
+    for (size_t si = 0; si < c->supers.size() && super_info && si < super_cap; si++) {
+        const SuperClass &su = c->supers[si];
+        const uint32_t v[6] = {su.layout, su.ksteps, su.n_tiles, su.pairable ? 1u : 0u, (uint32_t)su.q_offset, mfma2_chunk_tiles(su.ksteps)};
+        memcpy(super_info + 6 * si, v, sizeof v);
+    }
+    if (out) {
+        if (capacity < qbank.size()) return FOCR_ERR_INVALID;
+        if (!qbank.empty()) memcpy(out, qbank.data(), qbank.size());
+    }
+    return FOCR_OK;
+}
+
 // the plane value of a threshold L for a unit 2^shift (mfma_common.h: plane_value), host flavour (the device's is checked against it
 // on the GPU: test_gpu_parity.py)
 extern "C" void focr_debug_plane_value(const float *L, size_t n, uint32_t shift, int16_t *out) {

@@ -328,6 +328,19 @@ int focr_debug_tail_path(focr_ctx_t *c, uint32_t out[8]) {
     return FOCR_OK;
 }
 
+int focr_debug_scan_paired(focr_ctx_t *c, uint32_t out[2]) {
+    if (!c || !out) return fail(c, FOCR_ERR_INVALID, "focr_debug_scan_paired: bad arguments");
+    if (!c->scanned) return fail(c, FOCR_ERR_STATE, "focr_debug_scan_paired: no scan results");
+    if (int rc = finish_results(c)) return rc;  // (a redone scan's launches are the scan's)
+    out[0] = out[1] = 0;
+    for (const focr_launch_info_t &li : c->launches) {  // the per-launch records: the plane kernel's launches, and those of its paired form
+        if (strncmp(li.name, "scan_mfma2s_kernel<", 19) != 0) continue;
+        out[0]++;
+        if (strstr(li.name, ",pair>")) out[1]++;
+    }
+    return FOCR_OK;
+}
+
 int focr_debug_planes(focr_ctx_t *c, uint16_t *out, size_t capacity, size_t *n_values) {
     if (!c || !n_values) return FOCR_ERR_INVALID;
     FOCR_HIP(c, hipSetDevice(c->device));

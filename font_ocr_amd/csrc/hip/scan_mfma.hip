@@ -77,7 +77,7 @@ int plan_passes(focr_ctx *c, size_t plane, size_t &tiles_total, size_t &plane_va
         }
         su.mtx = su.n_rows = 0;
         su.live_offset = tiles_total;
-        su.planes = false;
+        su.planes = su.paired = false;
         if (su.min_w == 0xffffffffu) continue;  // nothing searchable
         su.mtx = (uint32_t)((c->pages.r_w - su.min_w + 1 + 15) / 16);  // windows x in [0, r_w - min n_w]
         su.n_rows = (uint32_t)(c->pages.r_h - su.min_h);               // y in [1, r_h - min n_h]
@@ -86,6 +86,10 @@ int plan_passes(focr_ctx *c, size_t plane, size_t &tiles_total, size_t &plane_va
         tiles_total += (size_t)nt;
         const size_t n_planes = pass_planes(c, su, plane);
         su.planes = n_planes != 0;
+        // THE decision whether the pass scans two window rows per fragment load (scan_mfma2.hip, PAIR): the bank holds the second operand
+        // image (layout_supers), the pass is the plane kernel's one launch, and its work list comes from the statistics' own append — the
+        // only list made of row pairs (stats.hip; the mark bytes of compact_live_tiles stay per row)
+        su.paired = su.pairable && su.planes && pass_appends(c, su);
         su.plane_off = plane_vals;
         plane_vals += n_planes * plane;
         need_L |= !su.planes;
@@ -199,6 +203,8 @@ static int scan_phase(focr_ctx *c, const ScanPlan &P, double thr_d) {
                 const unsigned cus = c->scan_cus ? std::min(c->scan_cus, c->n_cus) : c->n_cus;
                 if (c->scan_queues_used >= MAX_SCAN_QUEUES) return fail(c, FOCR_ERR_INVALID, "scan_mfma: too many scan passes for one call (bank too large)");
                 L.queue = c->d_counter + COUNTER_WORDS + (size_t)(c->scan_queues_used++) * QUEUE_XCDS * QUEUE_STRIDE;
+                if (su.paired && (t0 != 0 || t1 != su.n_tiles)) return fail(c, FOCR_ERR_INVALID, "scan_mfma: internal: a paired pass in more than one launch");
+                L.paired = su.paired;
                 if (su.planes) {
                     A3.planes = c->d_planes + su.plane_off;
                     A3.stride = P.plane;

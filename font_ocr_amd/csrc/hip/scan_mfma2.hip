@@ -8,8 +8,9 @@
 //
 //   scan_mfma2s_kernel  the default (<= 4 K-steps, <= 4 size classes per pass): A = templates, B = windows, the C-in of a
 //                       lane is the threshold of its own window, one shift away from its int16 threshold-plane value; 16
-//                       waves x 4 M-tiles per CU, 128 VGPRs.
-//   scan_mfma2_kernel   round 1's form (A = windows, int32 negL rows re-loaded per size class), kept for 5..8 K-steps and
+//                       waves x 4 M-tiles per CU, 128 VGPRs.  Its PAIR form scans two window rows per fragment load against two
+//                       operand images of the bank, where the classes leave the last row of their K block free (below).
+//   scan_mfma2_kernel  round 1's form (A = windows, int32 negL rows re-loaded per size class), kept for 5..8 K-steps and
 //                       as a cross-check (FOCR_PREFILTER_LEGACY); 8 waves x 4..8 M-tiles for the long layouts.
 #include <algorithm>
 
@@ -194,8 +195,19 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void scan_mfma2_kernel(
 // class changes.
 // 16 waves per workgroup, one workgroup per CU, 128 VGPRs (4 waves per SIMD).  Measured and not adopted (dead ends): 12- and
 // 8-wave workgroups, 96 VGPRs (a fifth wave slot per SIMD left to other kernels).
+//
+// PAIR: two window rows per fragment load.  Where every class of the pass leaves the last row of its K block empty (BASELINE
+// configs[1]: 15-row classes in LAYOUT_W8's 16 rows), the fragments of window row y — page rows y .. y + rows - 1 — hold window row
+// y + 1 whole, and G(w(x, y + 1), t) is the same integer against a template image that sits one row lower in the block.  The bank
+// holds that second image behind the first (bank_mfma.hip: layout_supers, quantise_bank), a work-list entry is the row pair
+// (y, y + 1) with y even (stats.hip, APPEND), and an item runs the N-tile loop twice over one set of fragments: image 0 with the
+// C-in of plane row y, image 1 with that of plane row y + 1 and keys of row y + 1.  Half the items, prologues, tickets and page loads
+// for the same MFMAs; a row of a pair that is not live, not searched or outside the page holds "never" in every plane and costs its
+// MFMAs for nothing (the pair (0, 1) of every M-tile column, and single-live pairs at the edges of the ink).  The two plane values
+// of a window and class share one register (row y in the low half), so the form takes no more registers than the other.
 constexpr int V2S_NW = 16, V2S_OCC = 4;
-template <int KSTEPS, int RPG, int MT, int NW, int NV>
+typedef short v2s __attribute__((ext_vector_type(2)));
+template <int KSTEPS, int RPG, int MT, int NW, int NV, bool PAIR>
 __global__ __launch_bounds__(NW * 64, V2S_OCC) void scan_mfma2s_kernel(
     const uint8_t *__restrict__ pages, uint32_t pitch, uint32_t rows_alloc, const uint64_t *__restrict__ live_list,
     const uint32_t *__restrict__ live_count, uint32_t page_base, const v4i *__restrict__ qbank, uint32_t n_tiles16, const MfmaSegs segs, uint32_t Lpitch, uint32_t Lrows,
@@ -203,7 +215,8 @@ __global__ __launch_bounds__(NW * 64, V2S_OCC) void scan_mfma2s_kernel(
     unsigned long long *__restrict__ cand_counter, unsigned long long cand_cap, uint32_t *__restrict__ queue, const RowHist rows) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     v4i *bank = reinterpret_cast<v4i *>(smem);
-    const uint32_t bank_vec = n_tiles16 * KSTEPS * 64;
+    const uint32_t n_bank_tiles = PAIR ? 2 * n_tiles16 : n_tiles16;  // PAIR: both operand images, one behind the other (the ids are those of the first)
+    const uint32_t bank_vec = n_bank_tiles * KSTEPS * 64;
     uint32_t *tg_lds = reinterpret_cast<uint32_t *>(smem + (size_t)bank_vec * 16 + (size_t)NW * WBUF * 8);
     for (uint32_t i = threadIdx.x; i < bank_vec; i += NW * 64) bank[i] = qbank[i];
     for (uint32_t i = threadIdx.x; i < n_tiles16 * 16; i += NW * 64) tg_lds[i] = tglobal[i];
@@ -214,7 +227,7 @@ __global__ __launch_bounds__(NW * 64, V2S_OCC) void scan_mfma2s_kernel(
     uint64_t *wbuf = reinterpret_cast<uint64_t *>(smem + (size_t)bank_vec * 16) + w * WBUF;
     uint32_t wcount = 0;
 
-    const uint32_t total_mt = *live_count;
+    const uint32_t total_mt = *live_count;  // PAIR: live row pairs
     const uint32_t n_items = (total_mt + MT - 1) / MT;
     uint32_t shift_of_value[NV];  // log2 of the unit of the threshold plane per value (= per size class of the super-class)
 #pragma unroll
@@ -249,7 +262,8 @@ __global__ __launch_bounds__(NW * 64, V2S_OCC) void scan_mfma2s_kernel(
             pv[mt] = m0 + mt < total_mt;
             const uint64_t e = live_list[pv[mt] ? m0 + mt : total_mt - 1];
             px[mt] = 16 * (uint32_t)(e & 0xfff);
-            py[mt] = 1 + (uint32_t)((e >> 12) & 0xfffff);  // y = 0 is never searched (src/ncc.cpp:302)
+            // y = 0 is never searched (src/ncc.cpp:302); PAIR: the entry holds the pair's even image row itself (row 0 says "never" in every plane)
+            py[mt] = (PAIR ? 0 : 1) + (uint32_t)((e >> 12) & 0xfffff);
             pp[mt] = (uint32_t)(e >> 32);
         }
         // The lane offsets are made opaque here, once per item: left visible, "pages + lane offset" is loop-invariant and gets
@@ -262,13 +276,16 @@ __global__ __launch_bounds__(NW * 64, V2S_OCC) void scan_mfma2s_kernel(
             po[v] = plane_off[v];
             asm volatile("" : "+v"(po[v]));
         }
-        int16_t nrm[MT][NV];  // threshold-plane values of the lane's own window px + r, one per size class
+        v2s nrm[MT][NV];  // threshold-plane values of the lane's own window px + r, one per size class ([1], PAIR: the same window one row down)
 #pragma unroll
         for (int mt = 0; mt < MT; mt++) {
             const uint8_t *np = reinterpret_cast<const uint8_t *>(P.planes + ((size_t)pp[mt] * Lrows + py[mt]) * Lpitch + px[mt]);  // wave-uniform
 #pragma unroll
-            for (int v = 0; v < NV; v++)  // -floor((L - 2) / S) as int16 (a sign-extending load); -32768 = never
-                nrm[mt][v] = *reinterpret_cast<const int16_t *>(np + po[v]);
+            for (int v = 0; v < NV; v++) {  // -floor((L - 2) / S) as int16 (a sign-extending load); -32768 = never
+                nrm[mt][v][0] = *reinterpret_cast<const int16_t *>(np + po[v]);
+                // the partner row's plane row exists and is written whatever the page height: stats.hip writes whole bands (Lrows > r_h)
+                nrm[mt][v][1] = PAIR ? *reinterpret_cast<const int16_t *>(np + (size_t)Lpitch * 2 + po[v]) : (short)0;
+            }
         }
         // K-step-major issue order: the N-tile loop's first MFMAs need K-step 0 of all M-tiles.  An address is a wave-uniform
         // 64-bit base (page, row, M-tile, K-step: scalar arithmetic) plus a 32-bit lane offset that never changes (lane_off[],
@@ -298,16 +315,22 @@ __global__ __launch_bounds__(NW * 64, V2S_OCC) void scan_mfma2s_kernel(
         // C-in of the lane's own window per size class (prefilter_cin, mfma_common.h: one shift; a window the class never emits at
         // holds -32768, an unreachable threshold).  M-tiles past the end of the enumeration repeat the last live one:
         // they are dropped where candidates are emitted (rare path), not here
+        // PAIR: the two rows' values stay packed in their register; the half a run needs is taken out per segment (below)
         int cin[MT][NV];
 #pragma unroll
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int v = 0; v < NV; v++) {
-                cin[mt][v] = prefilter_cin(shift_of_value[v], nrm[mt][v]);
+                cin[mt][v] = PAIR ? __builtin_bit_cast(int, nrm[mt][v]) : prefilter_cin(shift_of_value[v], nrm[mt][v][0]);
             }
         v4i bf[KSTEPS];
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ks++) bf[ks] = bank[ks * 64 + lane];
+        // PAIR: run 0 = window row y against the first operand image, run 1 = row y + 1 against the second; the images are one
+        // sequence of N-tiles to the B-fragment re-loads, so run 1 opens with its fragments in registers like any other tile
+#pragma unroll 1
+        for (uint32_t run = 0; run < (PAIR ? 2u : 1u); run++) {
+        const uint32_t tile0 = run * n_tiles16;  // the run's first N-tile in the LDS copy
         uint32_t nt = 0;
         for (uint32_t sgi = 0; sgi < segs.n; sgi++) {  // one segment = the N-tiles of one size class
             const uint32_t seg_end = segs.s[sgi].tile_end, sv = P.seg_value[sgi];
@@ -319,12 +342,14 @@ __global__ __launch_bounds__(NW * 64, V2S_OCC) void scan_mfma2s_kernel(
                 ci[mt] = cin[mt][0];
 #pragma unroll
                 for (int v = 1; v < NV; v++) ci[mt] = sv == (uint32_t)v ? cin[mt][v] : ci[mt];
+                // the run's half, sign-extended, times the unit of the segment's class (prefilter_cin)
+                if (PAIR) ci[mt] = prefilter_cin(P.shift[sgi], (int16_t)((uint32_t)ci[mt] >> (16 * run)));
             }
             for (; nt < seg_end; nt++) {
                 v4i acc[MT];
 #pragma unroll
                 for (int mt = 0; mt < MT; mt++) acc[mt] = v4i{ci[mt], ci[mt], ci[mt], ci[mt]};
-                const uint32_t nxt = nt + 1 < n_tiles16 ? nt + 1 : nt;
+                const uint32_t nxt = tile0 + nt + 1 < n_bank_tiles ? tile0 + nt + 1 : tile0 + nt;
 #pragma unroll
                 for (int ks = 0; ks < KSTEPS; ks++) {
                     if (RPG != LAYOUT_W12 || ks + 1 < KSTEPS || full) {  // wave-uniform
@@ -359,7 +384,7 @@ __global__ __launch_bounds__(NW * 64, V2S_OCC) void scan_mfma2s_kernel(
                         if (!pv[mt]) continue;  // past the end of the enumeration (a repeat of the last live M-tile): wave-uniform
                         const int mmt = max(max(acc[mt][0], acc[mt][1]), max(acc[mt][2], acc[mt][3]));
                         if (__builtin_amdgcn_ballot_w64(mmt > 0) == 0) continue;  // wave-uniform
-                        uint32_t pg = pp[mt], yy = py[mt], xx = px[mt];
+                        uint32_t pg = pp[mt], yy = py[mt] + run, xx = px[mt];  // (run 1 of a pair: the row below)
                         asm volatile("" : "+s"(pg), "+s"(yy), "+s"(xx));  // keep the key arithmetic inside this rare block
                         const uint64_t kb = fmt.pack(page_base + pg, yy, xx, 0);  // scalar
                         const uint32_t k_hi = (uint32_t)(kb >> 32), k_lo = (uint32_t)kb | r_key;
@@ -381,25 +406,27 @@ __global__ __launch_bounds__(NW * 64, V2S_OCC) void scan_mfma2s_kernel(
                 }
             }
         }
+        }
     }
     if (wcount) flush_wave_candidates(wbuf, wcount, lane, cand, cand_counter, cand_cap, rows);
 }
 
-template <int KSTEPS, int RPG, int NV>
+template <int KSTEPS, int RPG, int NV, bool PAIR>
 static void launch_v2s(focr_ctx *c, const MfmaLaunch &L, const PlaneArgs &A3, unsigned n_cus) {
     constexpr int MT = 4, NW = V2S_NW;
     const uint32_t n_tiles16 = L.n_tiles16;
-    const size_t lds = (size_t)n_tiles16 * KSTEPS * 1024 + (size_t)NW * WBUF * 8 + (size_t)n_tiles16 * 16 * 4;
-    const uint64_t total_mt = (uint64_t)L.mtx * L.n_rows * c->sub_np;
+    const size_t lds = (size_t)n_tiles16 * KSTEPS * 1024 * (PAIR ? 2 : 1) + (size_t)NW * WBUF * 8 + (size_t)n_tiles16 * 16 * 4;
+    const uint64_t total_mt = (uint64_t)L.mtx * (PAIR ? L.n_rows / 2 + 1 : L.n_rows) * c->sub_np;  // PAIR: row pairs (0, 1) .. (n_rows or n_rows - 1, + 1)
     const uint64_t n_items = (total_mt + MT - 1) / MT;
     unsigned grid = (unsigned)std::min<uint64_t>((uint64_t)n_cus * (16 / NW), (n_items + NW - 1) / NW);  // 16 waves per CU: one workgroup, or two of 8 waves (experiment builds)
-    auto kern = scan_mfma2s_kernel<KSTEPS, RPG, MT, NW, NV>;
+    auto kern = scan_mfma2s_kernel<KSTEPS, RPG, MT, NW, NV, PAIR>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     uint64_t ksteps_issued = 0;  // K-steps per live M-tile: the last one is skipped for classes that are all zero there
     for (uint32_t i = 0, t = 0; i < L.segs.n; t = L.segs.s[i].tile_end, i++) ksteps_issued += (uint64_t)(L.segs.s[i].tile_end - t) * (KSTEPS - (A3.seg_full[i] ? 0 : 1));
-    const uint64_t issued = 16 * ksteps_issued * 16 * 64;  // per live M-tile; scaled by the live count after the scan
+    // per live M-tile — PAIR: per live row pair, both rows' MFMAs, whether or not both rows are live —; scaled by the live count after the scan
+    const uint64_t issued = 16 * ksteps_issued * 16 * 64 * (PAIR ? 2 : 1);
     char name[64];
-    snprintf(name, sizeof name, "scan_mfma2s_kernel<%d,%d,%d,%d>", KSTEPS, RPG, MT, NW);
+    snprintf(name, sizeof name, PAIR ? "scan_mfma2s_kernel<%d,%d,%d,%d,pair>" : "scan_mfma2s_kernel<%d,%d,%d,%d>", KSTEPS, RPG, MT, NW);
     c->launch_begin(name, L.n_templates, L.alg_macs, issued, L.super_index);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, c->stream, c->pages.i8 + c->sub_p0 * c->pages.rows_alloc * c->pages.pitch, (uint32_t)c->pages.pitch, (uint32_t)c->pages.rows_alloc,
                        L.live_list, L.live_count, (uint32_t)c->sub_p0, reinterpret_cast<const v4i *>(c->bank.d_qbank + L.q_offset), n_tiles16, L.segs, L.Lpitch, L.Lrows, A3,
@@ -412,11 +439,17 @@ int dispatch_mfma_v2s(focr_ctx *c, const MfmaLaunch &L, const PlaneArgs &A3, uns
     // the kernel forms a key's low word from disjoint bit fields (x and template id); banks hold <= 65535 templates, pages <= 65535 px
     if (c->fmt.bt + c->fmt.bx > 32) return fail(c, FOCR_ERR_INVALID, "scan_mfma2s: key format too wide");
     const uint32_t nvp = A3.nv <= 1 ? 1 : (A3.nv <= 2 ? 2 : 4);
+    // the paired form's LDS: both operand images beside the staging buffers and the ids (layout_supers promises it; never a launch that cannot start)
+    if (L.paired && (size_t)L.n_tiles16 * L.ksteps * 2048 + (size_t)V2S_NW * WBUF * 8 + (size_t)L.n_tiles16 * 64 > ((size_t)160 << 10))
+        return fail(c, FOCR_ERR_INVALID, "scan_mfma2s: internal: the paired bank does not fit the LDS");
+#define CASE2S_NV(K, R, PR)                                          \
+    if (nvp == 1) launch_v2s<K, R, 1, PR>(c, L, A3, n_cus);          \
+    else if (nvp == 2) launch_v2s<K, R, 2, PR>(c, L, A3, n_cus);     \
+    else launch_v2s<K, R, 4, PR>(c, L, A3, n_cus);
 #define CASE2S(K, R)                                            \
     case (K) * 10 + (R):                                        \
-        if (nvp == 1) launch_v2s<K, R, 1>(c, L, A3, n_cus);     \
-        else if (nvp == 2) launch_v2s<K, R, 2>(c, L, A3, n_cus); \
-        else launch_v2s<K, R, 4>(c, L, A3, n_cus);              \
+        if (L.paired) { CASE2S_NV(K, R, true) }                 \
+        else { CASE2S_NV(K, R, false) }                         \
         break;
     switch (L.ksteps * 10 + L.layout) {
         CASE2S(1, 1) CASE2S(2, 1) CASE2S(3, 1) CASE2S(4, 1)
@@ -425,6 +458,7 @@ int dispatch_mfma_v2s(focr_ctx *c, const MfmaLaunch &L, const PlaneArgs &A3, uns
         default: return fail(c, FOCR_ERR_INVALID, "scan_mfma2s: unsupported size class");
     }
 #undef CASE2S
+#undef CASE2S_NV
     FOCR_HIP(c, hipGetLastError());
     return FOCR_OK;
 }

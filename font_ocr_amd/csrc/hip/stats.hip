@@ -233,7 +233,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
                                                       uint32_t n_w, uint32_t n_h, const StatsOut A, const StatsOut B, uint32_t Lpitch, uint32_t Lrows,
                                                       uint8_t *__restrict__ live, uint32_t mtx, uint32_t n_rows, uint32_t strips_x, uint32_t bands_y,
                                                       uint32_t GS, uint32_t GB, uint32_t sgroups, uint32_t bgroups, uint64_t *__restrict__ list,
-                                                      uint32_t *__restrict__ list_count) {
+                                                      uint32_t *__restrict__ list_count, uint32_t pair_rows) {
     __shared__ uint32_t wg_cnt[16][S8_ROWS], wg_off[16][S8_ROWS];  // [wave][window row]: live M-tiles, and where they go inside the workgroup's block
     __shared__ uint32_t wg_wsum[4];
     __shared__ uint32_t wg_base;
@@ -374,8 +374,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     if (k < k_end) window_row(k);
     }  // a strip and a band of the page
     if (APPEND) {
+        // pair_rows: an entry stands for the image rows (y, y + 1), y even — live if either row is; a band starts at a multiple of 16, so
+        // a pair never leaves its wave.  The pair's bit sits at its even row: the odd rows count nothing and append nothing.
+        const uint32_t kstep = pair_rows ? 2u : 1u;
+        if (pair_rows) mymask = (mymask | (mymask >> 1)) & 0x5555u;
         uint32_t mycnt = 0;  // lane k < 16: this wave's live M-tiles in window row k
-        for (uint32_t k = 0; k < S8_ROWS; k++) {
+        for (uint32_t k = 0; k < S8_ROWS; k += kstep) {
             const uint32_t cnt = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64((mymask >> k) & 1u));
             if (lane == k) mycnt = cnt;
         }
@@ -415,14 +419,15 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         __syncthreads();
         const uint32_t base = wg_base;
         const uint32_t myoff = lane < S8_ROWS ? wg_off[wv][lane] : 0u;
-        for (uint32_t k = 0; k < S8_ROWS; k++) {
+        for (uint32_t k = 0; k < S8_ROWS; k += kstep) {
             const bool mine = (mymask >> k) & 1u;
             const uint64_t m = __builtin_amdgcn_ballot_w64(mine);
             if (m == 0) continue;  // wave-uniform
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             const uint32_t row_at = base + (uint32_t)__builtin_amdgcn_readlane((int)myoff, (int)k);
-            // the scan kernel's entry: page << 32 | tile row (image row y - 1) << 12 | M-tile column (compact_live_tiles)
-            if (mine) list[row_at + rank] = ((uint64_t)page << 32) | ((uint64_t)(y0 + k - 1) << 12) | (xl >> 4);
+            // the scan kernel's entry: page << 32 | tile row (image row y - 1) << 12 | M-tile column (compact_live_tiles);
+            // pair_rows: the pair's even image row y itself (the pair (0, 1) has no row "- 1")
+            if (mine) list[row_at + rank] = ((uint64_t)page << 32) | ((uint64_t)(pair_rows ? y0 + k : y0 + k - 1) << 12) | (xl >> 4);
         }
     }
 }
@@ -483,6 +488,14 @@ static bool stats_register_form(const focr_ctx *c, const SizeClass &sc) {
     return sc.keep_w % 4 == 0 && sc.keep_w >= 4 && sc.keep_w <= 16 && c->dbg_stats_form == 0;
 }
 
+// whether the statistics of a plane pass end in a register-form launch that appends the work list itself (pass_stats: such a launch
+// goes last) — the only work list that can hold row pairs (plan_passes)
+bool pass_appends(const focr_ctx *c, const SuperClass &su) {
+    for (uint32_t k : su.classes)
+        if (stats_register_form(c, c->bank.classes[k])) return true;
+    return false;
+}
+
 // bands per workgroup of stats8_kernel, at most: 1 .. 5 measured 34.15 / 34.60 / 33.89 / 34.23 / 33.70 Gpx/s
 constexpr uint32_t S8_BANDS_MAX = 2;
 
@@ -514,7 +527,7 @@ static bool with_1_to_4(uint32_t v, F f) {
 // planes, else the int32 tables; append_list / append_count: the launch is the pass's only one and appends its live M-tiles to the work
 // list itself (stats8_kernel, APPEND)
 static int launch_stats(focr_ctx *c, bool planes, size_t k, int pair, double thr_d, void *out, void *out_pair, uint32_t Lpitch, uint32_t Lrows, uint8_t *live,
-                        uint32_t mtx, uint32_t n_rows, uint64_t *append_list, uint32_t *append_count) {
+                        uint32_t mtx, uint32_t n_rows, uint64_t *append_list, uint32_t *append_count, bool pair_rows) {
     const SizeClass &sc = c->bank.classes[k];
     // only what the scan kernels read: the windows of the pass's M-tiles (x < 16 * mtx) in the searched rows (y <= n_rows)
     dim3 grid(std::min<unsigned>(Lpitch / STX, (16 * mtx + STX - 1) / STX), std::min<unsigned>((Lrows + STY - 1) / STY, (n_rows + 1 + STY - 1) / STY),
@@ -523,6 +536,7 @@ static int launch_stats(focr_ctx *c, bool planes, size_t k, int pair, double thr
     if (pair >= 0) B = StatsOut{plane_params(c, (size_t)pair, thr_d), out_pair};
     const bool drop = sc.keep_w != sc.n_w, small = sc.n_w * sc.n_h <= 256, reg = planes && stats_register_form(c, sc);
     if (append_list && !reg) return fail(c, FOCR_ERR_INVALID, "scan_mfma: internal: direct append without the register form");
+    if (pair_rows && !append_list) return fail(c, FOCR_ERR_INVALID, "scan_mfma: internal: row pairs without the direct append");
     if (reg) {  // kept width 4, 8, 12, 16: the register form (stats8_kernel)
         const uint32_t cols = std::min<uint32_t>(Lpitch, 16 * mtx), rows_n = std::min<uint32_t>(Lrows, n_rows + 1);
         const uint32_t strips_x = (cols + S8_COLS - 1) / S8_COLS, bands_y = (rows_n + S8_ROWS - 1) / S8_ROWS;
@@ -534,7 +548,7 @@ static int launch_stats(focr_ctx *c, bool planes, size_t k, int pair, double thr
         auto launch8 = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3((unsigned)n_wgs), dim3(GS * GB * 64), 0, c->stream, c->pages.u8 + c->sub_p0 * c->pages.rows_alloc * c->pages.pitch, (uint32_t)c->pages.pitch,
                                (uint32_t)c->pages.rows_alloc, (uint32_t)c->pages.r_w, (uint32_t)c->pages.r_h, sc.n_w, sc.n_h, A, B, Lpitch, Lrows, live, mtx, n_rows, strips_x, bands_y,
-                               GS, GB, sgroups, bgroups, append_list, append_count);
+                               GS, GB, sgroups, bgroups, append_list, append_count, pair_rows ? 1u : 0u);
         };
         with_1_to_4(sc.keep_w / 4, [&](auto kq) {  // KQ = kept width / 4
             constexpr int KQ = decltype(kq)::value;
@@ -605,8 +619,9 @@ int pass_stats(focr_ctx *c, const ScanPlan &P, size_t si, double thr_d) {
         void *out = su.planes ? (void *)(c->d_planes + su.plane_off + L.v * P.plane) : (void *)(c->d_L + L.k * P.L_per_class);
         void *out_pair = L.pair < 0 ? nullptr : su.planes ? (void *)(c->d_planes + su.plane_off + L.pv * P.plane) : (void *)(c->d_L + (size_t)L.pair * P.L_per_class);
         if (int rc = launch_stats(c, su.planes, L.k, L.pair, thr_d, out, out_pair, P.Lpitch, P.Lrows, last && todo.size() == 1 ? nullptr : lv, su.mtx, su.n_rows,
-                                  last ? P.live_list + su.live_offset : nullptr, last ? c->d_counter + LIVE_WORD0 + si : nullptr)) return rc;
+                                  last ? P.live_list + su.live_offset : nullptr, last ? c->d_counter + LIVE_WORD0 + si : nullptr, last && su.paired)) return rc;
     }
+    if (su.paired && !direct) return fail(c, FOCR_ERR_INVALID, "scan_mfma: internal: row pairs planned for a pass whose statistics do not append");
     if (direct) return FOCR_OK;
     const uint32_t nt = (uint32_t)((uint64_t)su.mtx * su.n_rows * c->sub_np);
     hipLaunchKernelGGL(compact_live_tiles, dim3((nt + 256 * CLT_PER_THREAD - 1) / (256 * CLT_PER_THREAD)), dim3(256), 0, c->stream, lv, nt, su.mtx,

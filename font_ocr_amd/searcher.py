@@ -81,6 +81,27 @@ def prefilter_page_model(bank, page_ink, threshold, column_drop=True, prefilter=
     return out
 
 
+SUPER_INFO_FIELDS = ("layout", "ksteps", "n_tiles", "pairable", "q_offset", "chunk_tiles")
+
+
+def bank_images(bank, column_drop=True):
+    """The MFMA operand images of a bank as the upload lays them out (focr_debug_bank_images; no device): (list of per-super-class dicts,
+    SUPER_INFO_FIELDS, in pass order; the raw int8 bytes)."""
+    lib = N.hip()
+    T = len(bank.templates)
+    n_su, n_b = C.c_size_t(0), C.c_size_t(0)
+    args = (_ptr(bank.templates), T, _ptr(bank.needles), bank.needles.size, int(bool(column_drop)))
+    rc = lib.focr_debug_bank_images(*args, None, 0, C.byref(n_su), None, 0, C.byref(n_b))
+    if rc != 0:
+        raise FocrError(f"[{rc}] focr_debug_bank_images")
+    info = np.zeros((max(n_su.value, 1), 6), np.uint32)
+    q = np.zeros(max(n_b.value, 1), np.int8)
+    rc = lib.focr_debug_bank_images(*args, _ptr(info), n_su.value, C.byref(n_su), _ptr(q), q.size, C.byref(n_b))
+    if rc != 0:
+        raise FocrError(f"[{rc}] focr_debug_bank_images")
+    return [dict(zip(SUPER_INFO_FIELDS, (int(v) for v in info[i]))) for i in range(n_su.value)], q[: n_b.value]
+
+
 class PinnedPages:
     """(n, r_h, r_w) uint8 array in page-locked host memory (focr_host_alloc): `.array` is a numpy view.
     Scanner.upload_pages from it is an asynchronous DMA (see include/focr_ncc.h)."""
@@ -268,6 +289,12 @@ class Scanner:
         return {"tail": ("none", "rows", "legacy")[out[0]], "big_launch": bool(out[1]), "library_sort": bool(out[2]),
                 "order": ("none", "counting", "sorting")[out[3]], "seg_shift": int(out[4]), "n_seg": int(out[5]),
                 "verify": ("none", "global", "lds16", "lds12", "chunks")[out[6]], "verify_chunks": int(out[7])}
+
+    def scan_paired(self):
+        """Test hook (focr_debug_scan_paired): (launches of the plane prefilter kernel in the last scan, those in the paired form)."""
+        out = (C.c_uint32 * 2)()
+        self._ck(self._lib.focr_debug_scan_paired(self._h, out))
+        return int(out[0]), int(out[1])
 
     def set_stats_form(self, form):
         """Test hook (focr_debug_set_stats_form): 1 = the LDS-tiled statistics kernel for every class, 0 = the register form where it applies."""

@@ -525,6 +525,22 @@ int focr_debug_set_tail_grid(focr_ctx_t *ctx, uint32_t num, uint32_t den);
 #define FOCR_VERIFY_FORM_CHUNKS 4
 int focr_debug_tail_path(focr_ctx_t *ctx, uint32_t out[8]);
 
+/* Test hook: how the context's last scan launched the plane prefilter kernel (read from the per-launch records of
+ * focr_last_launches; nothing on the device changes for it): out[0] = its launches, out[1] = those in the paired form, which scans two
+ * window rows per fragment load against two operand images of the bank (a pass takes it when every size class of it leaves the last
+ * row of its K block empty, both images fit the LDS of one launch and the statistics append the work list themselves).  Both forms
+ * must give the same candidate set. */
+int focr_debug_scan_paired(focr_ctx_t *ctx, uint32_t out[2]);
+
+/* Host only (no device): the MFMA operand images of a bank, byte for byte as focr_bank_upload lays them out ([N-tile][K-step][lane
+ * group][slot][16 bytes] per super-class), and per super-class (in pass order, as "super" of focr_debug_prefilter_page's class
+ * records) six values: K layout, K-steps, N-tiles, 1 if a second image — every template one row lower in its K block — follows the
+ * first at + N-tiles * K-steps * 1024 bytes, the byte offset of the first image, and the N-tiles one launch can stage.
+ * out = NULL: only *n_supers and *n_bytes. */
+int focr_debug_bank_images(const focr_template_t *templates, size_t n_templates, const uint8_t *needles, size_t needles_len,
+                           int column_drop, uint32_t *super_info, size_t super_cap, size_t *n_supers, int8_t *out, size_t capacity,
+                           size_t *n_bytes);
+
 /* Test hooks for the window statistics: form 1 = the LDS-tiled kernel for every size class (0: the register form for classes whose
  * kept width is 8 px, stats.hip); focr_debug_planes copies the int16 threshold planes of the context's last MFMA scan to the
  * host ([value][page][Lrows][Lpitch] per pass, Lpitch = (r_w + 63) / 64 * 64 + 64, Lrows = (r_h + 7) / 8 * 8 + 8; out = NULL: only
