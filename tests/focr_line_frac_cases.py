@@ -2,6 +2,7 @@
 tests/test_focr_line_frac_model.py proves, on the CPU model, to reach the cases their names promise.  Small on purpose:
 pages of about 100 x 130 px, lines of 12 to 16 rows, alphabets of 4 to 12 glyphs (the whole-line programme on the CPU costs
 0.3 s per candidate of a 100 px line of 11 glyphs), except where the case itself is a size (the strip past LDS).
+Behind the hand-built cases: the seeded cases of the two baseline fuzzes on a seeded fraction (fuzz_frac, fuzz_case).
 """
 import collections
 import functools
@@ -117,6 +118,79 @@ def two_sizes_case(whole):
     b = std_pages(whole, 22)[0][: (44 if whole else 90), : (50 if whole else 80)].copy()
     c = std_case(whole, 2, 1)
     return c._replace(name="two-sizes-" + ("whole" if whole else "base"), pages=[a, b, a.copy()])
+
+
+# ---- the seeded cases of the two baseline fuzzes on a seeded fraction -------------------------------------------------------
+
+FUZZ_SEED = 0x1F4C
+N_FUZZ = 12  # of each form
+
+# as Case, with the hinting and kerning the seeded cases bring
+Fuzz = collections.namedtuple("Fuzz", "name whole font size hinting kerning alphabet y_bits n pages geo frac")
+
+
+def fuzz_frac(whole, i):
+    """(y_frac, advance_frac) of seeded case i of a form, a function of FUZZ_SEED, the form and i alone: each in 0 .. 63 and
+    not both 0; y_frac is 63 in about one draw of four (the centre ((f << B) + 32) >> 6 then reaches 2^B at every B), and
+    advance_frac is 0 in about one of four (every slot keeps slot 0's sub-pixel part)."""
+    rng = np.random.default_rng([FUZZ_SEED, int(whole), i])
+    while True:
+        y_frac = 63 if rng.random() < 0.25 else int(rng.integers(0, 64))
+        advance_frac = 0 if rng.random() < 0.25 else int(rng.integers(0, 64))
+        if y_frac or advance_frac:
+            return y_frac, advance_frac
+
+
+FUZZ_IDS = tuple(range(N_FUZZ)) + ("low",)
+
+
+def _low_case(whole):
+    """The seeded cases' fonts have an origin_y of 5 px or more and their radius reaches 1.5 px at most, so none of them can
+    drop a candidate.  This one can: the alphabet `.,_` has an origin_y of 1 px, and the radius reaches 2 px (N = 8 at B = 2,
+    N = 4 at B = 1), so that q below -2^B is dropped around a low centre; the middle line sits 1 px above its slot.
+    Hinted Serif at kerning 0.85 for the baseline search, Sans (origin_x 1) at kerning 1.07 for the whole-line candidates."""
+    font, hinting, kerning, y_bits, n = (SANS, False, 1.07, 1, 4) if whole else (os.path.join(GOLD, "DejaVuSerif.ttf"), True, 0.85, 2, 8)
+    al, size, geo, frac = ".,_", 7.15, (1, 2, 30, 6, 7), fuzz_frac(whole, N_FUZZ)
+    texts = _texts(al, 3, 9, 17 + whole)
+    page = np.full((2 + 2 * 7 + 12, 33), 255, dtype=np.uint8)
+    for i, (text, shift) in enumerate(zip(texts, (0.0, -1.0, 0.25))):
+        Y = 64 * geo[1] + frac[0] + i * LF.step(geo[4], frac[1])
+        B.draw_offset(page, font, size, al, text, geo[0], Y >> 6, (Y & 63) / 64.0 + shift, hinting, kerning)
+    H = ((64 * geo[1] + frac[0] + 2 * LF.step(geo[4], frac[1])) >> 6) + 4  # the page cuts the third slot to four rows
+    return Fuzz("whole-low" if whole else "base-low", whole, font, size, hinting, kerning, al, y_bits, n, [page[:H].copy()], geo, frac)
+
+
+def fuzz_case(whole, i):
+    """Case i of tests/focr_fuzz_cases.py at B = 2, N = 4 (the baseline search), or of tests/focr_whole_baseline_fuzz.py at
+    its own y_bits and n (the whole-line decode under candidates), on the grid of fuzz_frac(whole, i); "low" is _low_case."""
+    if i == "low":
+        return _low_case(whole)
+    if whole:
+        import focr_whole_baseline_fuzz as WF
+        c = WF.case(i)
+        return Fuzz(f"whole-{i}", True, c.font, c.size, c.hinting, c.kerning, c.alphabet, c.y_bits, c.n, [c.page], c.geo, fuzz_frac(True, i))
+    import focr_fuzz_cases as FC
+    c = FC.case(i)
+    return Fuzz(f"base-{i}", False, c.font, c.size, c.hinting, c.kerning, c.alphabet, 2, 4, c.pages, c.geo, fuzz_frac(False, i))
+
+
+@functools.lru_cache(maxsize=None)
+def _fuzz_model(font, size, alphabet, hinting, kerning, y_bits):
+    return B.BaselineModel(font, size, alphabet, hinting, kerning, y_bits)
+
+
+def fuzz_model(c):
+    return _fuzz_model(c.font, c.size, c.alphabet, c.hinting, c.kerning, c.y_bits)
+
+
+_fuzz_expected = {}
+
+
+def fuzz_expected(c):
+    """expected() of a Fuzz case, with the model of its hinting and kerning; computed once."""
+    if c.name not in _fuzz_expected:
+        _fuzz_expected[c.name] = [LF.search_image(fuzz_model(c), p, *c.geo, c.n, *c.frac, whole=c.whole) for p in c.pages]
+    return _fuzz_expected[c.name]
 
 
 def strip_bytes(page_w, x, width, line_height):

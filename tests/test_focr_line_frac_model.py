@@ -226,3 +226,69 @@ def test_verify_model_takes_the_crop_row_and_the_absolute_q():
     flat, sq0 = B.verify_image(c.pages[0], [(y, b.text, 0) for y, b in found], m.font, vf, c.geo[0], 2)
     assert sq < sq0 and not np.array_equal(img, flat)
     vf.close()
+
+
+def test_the_seeded_fractions_are_what_they_promise():
+    """fuzz_frac is a function of its arguments, stays in 0 .. 63, is never (0, 0), and over many indices draws y_frac = 63
+    and advance_frac = 0 about one time in four each."""
+    draws = [K.fuzz_frac(w, i) for w in (False, True) for i in range(400)]
+    assert draws == [K.fuzz_frac(w, i) for w in (False, True) for i in range(400)]
+    assert all(0 <= a <= 63 and 0 <= b <= 63 and (a, b) != (0, 0) for a, b in draws)
+    assert 0.2 < sum(a == 63 for a, _ in draws) / 800 < 0.32 and 0.2 < sum(b == 0 for _, b in draws) / 800 < 0.32
+    assert all(LF.centre(63, y_bits) == 1 << y_bits for y_bits in range(4))
+
+
+def test_fuzz_cases_reach_their_edges():
+    """What the seeded cases of tests/test_gpu_focr_line_frac.py::test_fuzz_cases reach on their seeded fractions, each
+    property asserted by name.  The fractional grid lies between two whole-pixel grids: (y_start, line_advance), whose rows
+    it never passes, so that a page has at most as many slots as on that one, and the next one down, (y_start + 1 where
+    y_frac > 0, line_advance + 1 where advance_frac > 0), on which a page has at most as many slots as on the fractional
+    one.  "Fewer" is against the first and "more" against the second."""
+    reach = {}
+
+    def note(name, who, hit):
+        reach.setdefault(name, [])
+        if hit:
+            reach[name].append(who)
+
+    for whole in (False, True):
+        for i in K.FUZZ_IDS:
+            c = K.fuzz_case(whole, i)
+            m, top = K.fuzz_model(c), 1 << c.y_bits
+            x, y, width, lh, adv = c.geo
+            for page, found in zip(c.pages, K.fuzz_expected(c)):
+                H = page.shape[0]
+                slots = _slots(c, page)
+                by_row = {s.yc: s for s in slots}
+                assert len(by_row) == len(slots) or adv == 1
+                below = LF.slots(H, y, 0, lh, adv, 0)
+                above = LF.slots(H, y + (c.frac[0] > 0), 0, lh, adv + (c.frac[1] > 0), 0)
+                assert len(above) <= len(slots) <= len(below), c.name
+                note("a page with fewer slots than the whole-pixel grid above it", c.name, len(slots) < len(below))
+                note("a page with more slots than the whole-pixel grid below it", c.name, len(slots) > len(above))
+                for yc, r in found:
+                    s = by_row[yc]
+                    ci = LF.centre(s.f, c.y_bits)
+                    assert 0 <= ci <= top and not m.dropped(r.q) and abs(r.q - ci) <= c.n, (c.name, yc)
+                    note("a crop row off the whole-pixel grid", c.name, yc != y + s.i * adv)
+                    note("a centre of 0", c.name, ci == 0)
+                    note("a centre of 2^B", c.name, ci == top)
+                    note("a centre strictly between", c.name, 0 < ci < top)
+                    note("a centre that only the half rounds up", c.name, ((s.f << c.y_bits) & 63) == 32)
+                    note("a winning q below its centre", c.name, r.q < ci)
+                    note("a winning q at its centre", c.name, r.q == ci)
+                    note("a winning q above its centre", c.name, r.q > ci)
+                    note("a dropped candidate beside a kept winner", c.name, any(m.dropped(q) for q in LF.candidates(ci, c.n)))
+                    note("a cut last slot with ink", c.name, s is slots[-1] and s.h < lh)
+            note("hinting on", c.name, c.hinting)
+            note("kerning off 1", c.name, c.kerning != 1.0)
+            note("y_frac 63", c.name, c.frac[0] == 63)
+            note("advance_frac 0", c.name, c.frac[1] == 0)
+    print({k: len(v) for k, v in reach.items()})
+    for name, hits in reach.items():
+        assert hits, "no case reaches: " + name
+    for form in ("base", "whole"):  # the centres and the winners in both forms (the slot count is the shared prepass's)
+        for name, hits in reach.items():
+            assert "page with" in name or [h for h in hits if h.startswith(form)], (form, name)
+    # the seeded cases cannot drop a candidate (an origin_y of 5 px or more, a radius of 1.5 px at most): the low-origin case does
+    assert reach["a dropped candidate beside a kept winner"] == ["base-low", "base-low", "whole-low", "whole-low"]

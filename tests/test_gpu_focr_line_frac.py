@@ -3,7 +3,12 @@ line_whole_baseline_frac_kernel, verify_layout_frac_kernel, verify_compose_moved
 LineDecoder.decode(y_frac=, line_advance_frac=); focr --y-frac --line-advance-frac) against tests/focr_line_frac_model.py,
 the definition of include/focr_decode.h restated in plain integers on the two baseline models.  Every quantity is an exact
 integer, so every comparison is ==.  The cases are tests/focr_line_frac_cases.py's; tests/test_focr_line_frac_model.py proves
-on the CPU that each reaches the case its name promises."""
+on the CPU that each reaches the case its name promises.
+
+Teeth of test_fuzz_cases, as measured on an MI355X with one-line mutations of the DEVICE code only (decode.h; neither touches
+an index, a bound, a size or a stride), each built once and run once against test_fuzz_cases: frac_centre with `+ 31` for
+`+ 32` fails base-2, base-5 and whole-3, the cases with an inked slot whose centre only the half rounds up, and slot_rows_frac
+with slot 0's f for every slot fails eight cases of both forms; in each the first assertion to fail is the texts' ==."""
 import ctypes as C
 import os
 import subprocess
@@ -39,9 +44,10 @@ def _check(dec, c, verify=True):
     """Decode a case on its grid: line order, y, text, q, cost (and pens) equal to the model's, and with verify the image,
     the MSE, and from a verify without images of each page size the exact sums.  Returns the model's [[(yc_i, result)] per
     page]."""
-    m = K.model(c.font, c.size, c.alphabet, c.y_bits)
+    fuzz = isinstance(c, K.Fuzz)  # a seeded case brings its hinting and kerning
+    m = K.fuzz_model(c) if fuzz else K.model(c.font, c.size, c.alphabet, c.y_bits)
     dec.set_font(m.font, c.size)
-    want = K.expected(c)
+    want = K.fuzz_expected(c) if fuzz else K.expected(c)
     got = _decode(dec, c, verify="image" if verify else None)
     lines, rest = got[0], got[3:] if verify else got[1:]
     assert lines == [[(y, r.text) for y, r in pg] for pg in want]
@@ -54,7 +60,7 @@ def _check(dec, c, verify=True):
     assert costs == [[r.cost for _, r in pg] for pg in want]
     assert dec._lib.focr_decoder_last_launches(dec._h) == 3
     if verify:
-        vf = VerifyFont(c.font, c.size, c.alphabet)
+        vf = VerifyFont(c.font, c.size, c.alphabet, c.hinting, c.kerning) if fuzz else VerifyFont(c.font, c.size, c.alphabet)
         sqs = []
         for page, found, mse, img in zip(c.pages, want, got[1], got[2]):
             wimg, sq = LF.verify_image(page, found, m.font, vf, c.geo[0], c.y_bits, whole=c.whole)
@@ -164,6 +170,20 @@ def test_off_after_on_is_a_fresh_decoder(dec, whole):
     assert repr(got[0]) == repr(want[0]) and repr(got[3:]) == repr(want[3:]) and got[1].tobytes() == want[1].tobytes()
     assert all(np.array_equal(a, b) for a, b in zip(got[2], want[2]))
     assert repr(on[0]) != repr(got[0])
+
+
+@pytest.mark.parametrize("whole,i", [(w, i) for w in (False, True) for i in K.FUZZ_IDS], ids=[f"{w}-{i}" for w in ("base", "whole") for i in K.FUZZ_IDS])
+def test_fuzz_cases(dec, whole, i):
+    """The first dozen seeded cases of tests/focr_fuzz_cases.py at B = 2, N = 4 and the dozen of
+    tests/focr_whole_baseline_fuzz.py at their own B and N (Sans, Serif and Mono, hinting on and off, kernings off 1, clipped
+    widths, cut last slots, pages of two sizes), each on its seeded fraction of focr_line_frac_cases.fuzz_frac, and the
+    low-origin case that drops candidates: crop rows, texts, the absolute q, costs and pens equal to the model's, and for
+    every third case the verify image, the per-page sums and the MSE as well.  tests/test_focr_line_frac_model.py proves
+    what the fractions reach."""
+    c = K.fuzz_case(whole, i)
+    assert c.frac != (0, 0) and all(0 <= f <= 63 for f in c.frac)
+    want = _check(dec, c, verify=i == "low" or i % 3 == 0)
+    assert sum(len(pg) for pg in want) > 0
 
 
 def _raw_run(dec, page, x, y, width, line_height, line_advance):
