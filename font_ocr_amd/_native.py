@@ -333,6 +333,12 @@ class DecodedLine(C.Structure):
     _fields_ = [("page", C.c_uint32), ("y", C.c_uint32), ("first", C.c_uint64), ("n_chars", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class TextLine(C.Structure):
+    """focr_text_line_t (include/focr_decode.h)."""
+
+    _fields_ = [("page", C.c_uint32), ("y", C.c_uint32), ("first", C.c_uint64), ("n_chars", C.c_uint32), ("font", C.c_uint32)]
+
+
 class CharScore(C.Structure):
     """focr_char_score_t (include/focr_decode.h)."""
 
@@ -394,6 +400,11 @@ DECODE_HIP_SYMBOLS = {
     "focr_decoder_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "focr_decoder_last_verify_ms": (C.c_float, [C.c_void_p]),
     "focr_decoder_last_verify_launches": (C.c_uint32, [C.c_void_p]),
+    "focr_decoder_set_verify_font_candidates": (C.c_int, [C.c_void_p, C.POINTER(VerifyFontStruct), C.c_uint32]),
+    "focr_decoder_verify_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "focr_decoder_last_verify_text_ms": (C.c_float, [C.c_void_p]),
+    "focr_decoder_last_verify_text_launches": (C.c_uint32, [C.c_void_p]),
     "focr_decoder_test_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_int]),

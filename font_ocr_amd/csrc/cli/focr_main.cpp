@@ -47,7 +47,9 @@
 //     values of -f, -t, --kerning and --hinting; a path may not contain a comma.  stdout stays text only, and --fonts PATH
 //     writes a CSV row per decoded line: image_index,y,font,cost (font is the candidate's index).  With --scores,
 //     --pen-search, --pen-slack, --margins, --baseline-search, --whole-baseline or --verify it is a usage error, and so is
-//     --fonts without it.
+//     --fonts without it.  --verify-fonts DIR is --verify's picture of such a run (focr_decoder_verify_text): DIR/<stem>.png and
+//     "<image> <mse>" on stderr exactly as --verify writes them, with every line drawn in its winning font and, under
+//     --whole-line, every character at its pen; without --font-candidate it is a usage error, and --verify stays one beside it.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -86,8 +88,8 @@ struct FontSpec {  // one --font-candidate
 struct Args {
     std::vector<std::string> img, candidate_specs;
     std::vector<FontSpec> candidates;
-    std::string fonts;
-    bool have_fonts = false;
+    std::string fonts, verify_fonts;
+    bool have_fonts = false, have_verify_fonts = false;
     std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores, margins, baselines;
     bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false, have_margins = false;
     bool have_baselines = false, have_y_bits = false;
@@ -133,6 +135,7 @@ void print_help() {
            "      --line-advance-frac <N>          [extension] Sub-pixel part of --line-advance in 1/64 px, N <= 63 (only with a baseline search or --whole-baseline) [default: 0]\n"
            "      --font-candidate <SPEC>...       [extension] Also decode every line in this font and keep the cheapest reading; SPEC is f=PATH,t=SIZE,k=KERNING,h=0|1, omitted keys as -f, -t, --kerning, --hinting; at most 15 (only with the plain pen loop or the plain whole-line decode; not with --verify)\n"
            "      --fonts <FONTS>                  [extension] CSV of every line's winning font candidate and cost (only with --font-candidate)\n"
+           "      --verify-fonts <DIR>             [extension] Dir for verify images of a --font-candidate run: every line drawn in its winning font (only with --font-candidate)\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -192,6 +195,7 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--margins") a.margins = c.need(), a.have_margins = true;
         else if (k == "--font-candidate") a.candidate_specs.push_back(c.need());
         else if (k == "--fonts") a.fonts = c.need(), a.have_fonts = true;
+        else if (k == "--verify-fonts") a.verify_fonts = c.need(), a.have_verify_fonts = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -229,6 +233,8 @@ Args parse_args(int argc, char **argv) {
     if (a.candidate_specs.size() > FOCR_FONT_CANDIDATES_MAX - 1) usage_error("the argument '--font-candidate <SPEC>' cannot be used more than 15 times");
     for (const std::string &spec : a.candidate_specs) a.candidates.push_back(parse_font_spec(spec, a));
     if (a.have_fonts && a.candidates.empty()) usage_error("the argument '--fonts <FONTS>' cannot be used without '--font-candidate <SPEC>'");
+    if (a.have_verify_fonts && a.candidates.empty())
+        usage_error("the argument '--verify-fonts <DIR>' cannot be used without '--font-candidate <SPEC>'");
     for (const auto &[with, name] : {std::pair<bool, const char *>{a.have_scores, "--scores <SCORES>"}, {a.pen_search != 0, "--pen-search <N>"},
                                      {a.pen_slack != 0, "--pen-slack <N>"}, {a.have_margins, "--margins <MARGINS>"},
                                      {a.baseline_search != 0, "--baseline-search <N>"}, {a.whole_baseline != 0, "--whole-baseline <N>"},
@@ -317,6 +323,10 @@ int main(int argc, char **argv) {
         struct stat st;
         if (stat(args.verify.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) die("--verify should be a dir");  // src/main.rs:389-391
     }
+    if (args.have_verify_fonts) {
+        struct stat st;
+        if (stat(args.verify_fonts.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) die("--verify-fonts should be a dir");
+    }
     std::vector<uint32_t> alphabet = utf8_decode(args.alphabet);
     if (args.have_test) return run_test(args, alphabet);
     FILE *csv = nullptr;
@@ -354,7 +364,7 @@ int main(int argc, char **argv) {
     // a setter that refuses ends the program: "<setter>: <the library's message>", exit code 1
     const auto set = [&](const char *setter, int rc) { if (rc != 0) die(std::string(setter) + ": " + focr_decoder_last_error(dec), 1); };
     set("focr_decoder_set_font", focr_decoder_set_font(dec, &font));
-    if (args.have_verify) {
+    if (args.have_verify || args.have_verify_fonts) {
         focr_verify_font_t vfont{};
         if (focr_verify_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), &vfont, err,
                                    sizeof err) != 0)
@@ -380,6 +390,16 @@ int main(int argc, char **argv) {
         }
         set("focr_decoder_set_font_candidates", focr_decoder_set_font_candidates(dec, cands.data(), (uint32_t)cands.size()));
         set("focr_decoder_set_font_search", focr_decoder_set_font_search(dec, 1));
+        if (args.have_verify_fonts) {  // every candidate's verify table, for focr_decoder_verify_text
+            std::vector<focr_verify_font_t> vcands(cands.size());
+            for (size_t k = 0; k < vcands.size(); k++) {
+                const FontSpec &c = args.candidates[k];
+                if (focr_verify_font_build(c.font.c_str(), c.text_size, c.hinting, c.kerning, alphabet.data(), alphabet.size(), &vcands[k], err, sizeof err) != 0)
+                    die("font candidate " + std::to_string(k + 1) + ": verify font: " + err);
+            }
+            set("focr_decoder_set_verify_font_candidates", focr_decoder_set_verify_font_candidates(dec, vcands.data(), (uint32_t)vcands.size()));
+            for (focr_verify_font_t &f : vcands) focr_verify_font_free(&f);
+        }
         for (focr_decode_font_t &f : cands) focr_decode_font_free(&f);
     }
     const bool csv_offsets = csv && args.pen_search > 0;
@@ -421,9 +441,10 @@ int main(int argc, char **argv) {
             std::vector<int64_t> bc(bcsv ? dl.size() : 0);
             if (bcsv && focr_decoder_get_baselines(dec, bq.data(), bc.data()) != 0)
                 die(std::string("focr_decoder_get_baselines: ") + focr_decoder_last_error(dec), 1);
-            std::vector<uint8_t> fk(fcsv ? dl.size() : 0);
-            std::vector<int64_t> fc(fcsv ? dl.size() : 0);
-            if (fcsv && focr_decoder_get_fonts(dec, fk.data(), fc.data()) != 0)
+            const bool want_fonts = fcsv || args.have_verify_fonts;
+            std::vector<uint8_t> fk(want_fonts ? dl.size() : 0);
+            std::vector<int64_t> fc(want_fonts ? dl.size() : 0);
+            if (want_fonts && focr_decoder_get_fonts(dec, fk.data(), fc.data()) != 0)
                 die(std::string("focr_decoder_get_fonts: ") + focr_decoder_last_error(dec), 1);
             for (size_t li = 0; li < dl.size(); li++) {
                 const focr_decoded_line_t &l = dl[li];
@@ -436,6 +457,26 @@ int main(int argc, char **argv) {
                 if (csv) out.scores.assign(ds.begin() + l.first, ds.begin() + l.first + l.n_chars);
                 if (csv_offsets) out.offsets.assign(dj.begin() + l.first, dj.begin() + l.first + l.n_chars);
                 lines[grp.second[b0 + l.page]].push_back(std::move(out));
+            }
+            if (args.have_verify_fonts) {  // the same picture of a font search: every line in its winner's font, at its pens under --whole-line
+                std::vector<focr_text_line_t> tl(dl.size());
+                for (size_t li = 0; li < dl.size(); li++) tl[li] = focr_text_line_t{dl[li].page, dl[li].y, dl[li].first, dl[li].n_chars, fk[li]};
+                std::vector<uint32_t> tp(args.whole_line ? dc.size() : 0);
+                if (args.whole_line && focr_decoder_get_pens(dec, tp.data(), nullptr) != 0)
+                    die(std::string("focr_decoder_get_pens: ") + focr_decoder_last_error(dec), 1);
+                rgb.resize(nb * W * H * 3);
+                sums.assign(nb, 0);
+                if (focr_decoder_verify_text(dec, batch.data(), 0, nb, W, H, args.x, tl.data(), tl.size(), dc.data(), args.whole_line ? tp.data() : nullptr,
+                                             nullptr, dc.size(), rgb.data(), 0, sums.data()) != 0)
+                    die(std::string("focr_decoder_verify_text: ") + focr_decoder_last_error(dec), 1);
+                std::vector<std::string> paths(nb);
+                for (size_t j = 0; j < nb; j++) paths[j] = verify_path(args.verify_fonts, args.img[grp.second[b0 + j]]);
+                const std::vector<char> ok = write_verify_pngs(paths, rgb.data(), (uint32_t)W, (uint32_t)H);
+                for (size_t j = 0; j < nb; j++) {
+                    if (!ok[j]) die("cannot write " + paths[j]);
+                    const float mse = (float)sums[j] / (float)(uint32_t)(W * H);
+                    fprintf(stderr, "%s %.6f\n", args.img[grp.second[b0 + j]].c_str(), (double)mse);
+                }
             }
             if (args.have_verify) {  // draw_verify + red_blue_mse (src/main.rs:300-329, 518-524) on the device
                 rgb.resize(nb * W * H * 3);

@@ -133,6 +133,9 @@ void drop_font_candidates(focr_decoder *dec) {
     dec->d_fbitmaps.release();
     dec->d_fdesc.release();
     dec->d_finc64.release();
+    dec->n_fvfonts = 0;  // their verify tables (focr_decoder_set_verify_font_candidates) go with them
+    dec->d_fvglyphs.release();
+    dec->d_fvphases.release();
 }
 
 }  // namespace focr_dec
@@ -160,6 +163,9 @@ extern "C" int focr_decoder_set_font_candidates(focr_decoder_t *dec, const focr_
         if (f.bitmaps_len % 4 || (f.bitmaps_len && !f.bitmaps)) return dfail(dec, pre + "bad bitmap table");
         FontCandidate &c = cands[k];
         c.origin_x = f.origin_x;
+        c.glyphs.assign(f.glyphs, f.glyphs + G);
+        c.base = total;
+        c.origin_y = f.origin_y, c.text_size = f.text_size, c.kerning = f.kerning, c.hinting = f.hinting;
         c.inc.resize(G);
         c.min_inc = f.glyphs[0].increment;
         for (size_t i = 0; i < G; i++) {

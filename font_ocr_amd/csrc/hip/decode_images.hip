@@ -25,79 +25,7 @@
 
 namespace focr_dec {
 
-// render()'s layout of one line of n glyphs on a page of g, by one wave: the pen (f32 adds in text order), the union
-// of round_out boxes folded from the empty rect at (0, 0), and each glyph's true bitmap rectangle clipped to the canvas
-// and the page, written to out[0 .. n).  The line is cs[0 .. n) at (x_start, y of g's slot), or for IOTA the alphabet
-// indices 0 .. n - 1 at (x_start, 0).  Lane 0 writes the line's canvas on the page to *line, clipped (empty when none
-// of it is on the page), with k and n.  js (null: none) is the run's pen search: glyph q is placed at pen + js[q] / 64
-// and the pen advances from there, the decoder's own two f32 adds.  ps (null: none) is a whole-line run's pens in
-// 1/64 px: glyph q is placed at ps[q] / 64 (exact), whatever the increments before it.  moved is a baseline run's whole rows
-// for this line (0: none): the canvas is drawn that many rows below the slot's y, above it when negative, and is then
-// clipped at the page's top as well.  grid is the line grid the slot's y is read from (decode.h): the whole-pixel one
-// unless the run was made on the fractional one.
-template <bool IOTA, class Grid = PixelGrid>
-__device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, const uint16_t *__restrict__ cs,
-                                            const int8_t *__restrict__ js, const uint32_t *__restrict__ ps, int moved, uint32_t n, uint32_t k,
-                                            uint32_t x_start, const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
-                                            const VerifyPhase *__restrict__ vphases, VerifyRec *__restrict__ out, VerifyLine *__restrict__ line,
-                                            const Grid &grid = Grid{}) {
-    const uint32_t lane = threadIdx.x;
-    float pen = 0.f;
-    int ox = 0, oy = 0, lx = 0, ly = 0;
-    for (uint32_t base = 0; base < n; base += 64) {
-        const uint32_t j = base + lane, m = std::min(64u, n - base);
-        const bool live = j < n;
-        const uint32_t c = live ? (IOTA ? j : cs[j]) : 0;
-        const float inc = live ? glyphs[c].inc : 0.f;
-        const float dj = live && js ? (float)js[j] * 0.015625f : 0.f;
-        float pos = live && ps ? __fmul_rn((float)ps[j], 0.015625f) : 0.f;
-        for (uint32_t q = 0; q < m && !ps; q++) {
-            if (js) pen = __fadd_rn(pen, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dj), q)));
-            if (lane == q) pos = pen;
-            pen = __fadd_rn(pen, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), q)));
-        }
-        if (live) {
-            const VerifyGlyph v = vglyphs[c];
-            ox = std::min(ox, (int)floorf(__fadd_rn(v.box[0], pos)));
-            oy = std::min(oy, (int)floorf(__fadd_rn(v.box[1], 0.f)));
-            lx = std::max(lx, (int)ceilf(__fadd_rn(v.box[2], pos)));
-            ly = std::max(ly, (int)ceilf(__fadd_rn(v.box[3], 0.f)));
-            out[j].x0 = __float_as_int(pos);  // kept for the second pass of this same lane
-        }
-    }
-    for (int s = 32; s >= 1; s >>= 1) {
-        ox = std::min(ox, __shfl_xor(ox, s, 64));
-        oy = std::min(oy, __shfl_xor(oy, s, 64));
-        lx = std::max(lx, __shfl_xor(lx, s, 64));
-        ly = std::max(ly, __shfl_xor(ly, s, 64));
-    }
-    const int cw = lx - ox, ch = ly - oy;
-    const int64_t W = g.page_w, H = g.page_h;
-    const int64_t line_y = IOTA ? 0 : grid.row(g, slot % g.n_slots) + moved;
-    const int top = IOTA ? 0 : (int)std::max<int64_t>(-line_y, 0);  // the canvas rows above the page (a line moved up)
-    const float neg_ox = (float)(-ox);
-    for (uint32_t j = lane; j < n; j += 64) {
-        const float pos = __int_as_float(out[j].x0);
-        const int d = (int)__fmul_rn(__fadd_rn(neg_ox, pos), 64.0f);  // FreeType's delta: trunc((-bounds.ox + pos) * 64) >= 0
-        const VerifyPhase ph = vphases[(size_t)(IOTA ? j : cs[j]) * FOCR_DECODE_PHASES + (d & 63)];
-        const int gx0 = (d >> 6) + ph.x, gy0 = ph.y - oy;  // on the canvas: whole-pixel shift, vertical delta -bounds.oy
-        const int ax0 = std::max(gx0, 0), ay0 = std::max(gy0, top);
-        const int ax1 = std::min(gx0 + (int)ph.w, cw), ay1 = std::min(gy0 + (int)ph.h, ch);
-        const int64_t X0 = x_start + (int64_t)ax0, Y0 = line_y + ay0;
-        const int64_t X1 = std::min<int64_t>(x_start + (int64_t)ax1, W), Y1 = std::min<int64_t>(line_y + ay1, H);
-        VerifyRec r{0, 0, 0, 0, 0, 0};
-        if (ax0 < ax1 && ay0 < ay1 && X0 < X1 && Y0 < Y1)
-            r = VerifyRec{(int32_t)X0, (int32_t)Y0, (int32_t)X1, (int32_t)Y1, ph.src + (uint32_t)(ay0 - gy0) * ph.stride + (uint32_t)(ax0 - gx0),
-                          ph.stride};
-        out[j] = r;
-    }
-    if (lane == 0) {
-        const int64_t X1 = std::min<int64_t>(x_start + (int64_t)cw, W), Y1 = std::min<int64_t>(line_y + ch, H);
-        VerifyLine l{0, 0, 0, 0, k, n};
-        if ((int64_t)x_start < X1 && line_y + top < Y1) l = VerifyLine{(int32_t)x_start, (int32_t)(line_y + top), (int32_t)X1, (int32_t)Y1, k, n};
-        *line = l;
-    }
-}
+// (layout_line, render()'s layout of one line by one wave, is decode.h's: decode_text.hip lays out a caller's lines with it.)
 
 // 4. render()'s layout of every decoded line, one wave per work-list line; blocks below n_pages also zero the sums
 // (verify_layout_frac_kernel below restates this body on the fractional line grid: a fix here is a fix there)

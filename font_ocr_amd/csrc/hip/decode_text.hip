@@ -1,0 +1,252 @@
+// decode_text.hip — focr_decoder_verify_text (include/focr_decode.h): the verify image and squared error of pages under a
+// list of lines the caller supplies, each line in any font the decoder has uploaded: the decode font (0) or a candidate of
+// the font search (1 ..= K).  What a font search decoded, or a reading somebody corrected, is drawn with it; focr_decoder_verify
+// (decode_images.hip) draws only what the last run itself decoded, in the decode font.
+//
+// Two launches, over the tile frame of decode.h and in buffers of the call's own:
+//   1. verify_layout_text_kernel: one wave per listed line runs layout_line (decode.h) with the line's own y and the glyph,
+//      box and phase tables of the line's font (the candidates' lie k-major behind a per-font base, as d_fglyphs does), and
+//      writes the line's glyph records and its clipped canvas, which carries the font; blocks below n_pages also zero the sums;
+//   2. verify_compose_text_kernel: one workgroup per (page, 16 rows, 256 columns) tile walks that page's lines
+//      [page_first[p], page_first[p + 1]) in list order.  The lines lie on no grid (any y, in any order, repeated,
+//      overlapping, in fonts of different heights), so there is no slot grid to invert: the list itself is walked, and each
+//      line's canvas is tested against the tile, uniformly across the workgroup.  A page has tens of lines.  A line that
+//      reaches the tile is marked and read as verify_compose_kernel does it (mark_glyphs, glyph_value), from the bitmap table
+//      of its font, chosen once per line; the sums are tile_add_sum's.
+// Here as well: the upload of the candidates' verify tables (focr_decoder_set_verify_font_candidates).
+#include <cmath>
+#include <cstring>
+
+#include "decode.h"
+
+namespace focr_dec {
+
+// The line grid of a caller's line: its own y, whatever the slot.
+struct OwnRow {
+    int64_t y;
+    __device__ __forceinline__ int64_t row(const Geometry &, uint32_t) const { return y; }
+};
+
+// The tables of the fonts 0 ..= K as layout_line reads them: font 0 is the decode font's, the others lie k-major.
+struct TextFonts {
+    const DevGlyph *glyphs, *fglyphs;
+    const VerifyGlyph *vglyphs, *fvglyphs;
+    const VerifyPhase *vphases, *fvphases;
+    uint32_t n_glyphs;
+};
+
+// 1. render()'s layout of every listed line, one wave per line; blocks below n_pages also zero the sums.  g carries the
+// page's size and one slot (layout_line reads the line's row from the grid policy).
+__global__ __launch_bounds__(64) void verify_layout_text_kernel(Geometry g, uint32_t n_pages, uint32_t n_lines, uint32_t x_start,
+                                                                const TextLine *__restrict__ in, const uint16_t *__restrict__ chars,
+                                                                const int8_t *__restrict__ offs, const uint32_t *__restrict__ pens, TextFonts f,
+                                                                VerifyLine *__restrict__ lines, VerifyRec *__restrict__ recs,
+                                                                unsigned long long *__restrict__ sums) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (b < n_pages && lane == 0) sums[b] = 0;
+    if (b >= n_lines) return;
+    const TextLine l = in[b];
+    const size_t at = l.font ? (size_t)(l.font - 1) * f.n_glyphs : 0;  // uniform: the per-font base of the k-major tables
+    layout_line<false>(g, 0, chars + l.first, offs ? offs + l.first : nullptr, pens ? pens + l.first : nullptr, 0, l.n, l.font, x_start,
+                       l.font ? f.fglyphs + at : f.glyphs, l.font ? f.fvglyphs + at : f.vglyphs,
+                       l.font ? f.fvphases + at * FOCR_DECODE_PHASES : f.vphases, recs + l.rec, lines + b, OwnRow{(int64_t)l.y});
+}
+
+// 2. compose the image tile by tile; every thread owns one column of a 16-row, 256-column tile
+__global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_text_kernel(const uint8_t *__restrict__ pages, uint32_t page_w, uint32_t page_h,
+                                                                            uint32_t n_pages, uint32_t tiles_x, uint32_t tiles_y,
+                                                                            const uint32_t *__restrict__ page_first, const TextLine *__restrict__ in,
+                                                                            const VerifyLine *__restrict__ lines, const VerifyRec *__restrict__ recs,
+                                                                            const uint8_t *__restrict__ bitmaps, const uint8_t *__restrict__ fbitmaps,
+                                                                            uint8_t *__restrict__ rgb, unsigned long long *__restrict__ sums) {
+    __shared__ uint32_t win[VERIFY_TILE_H * VERIFY_TILE_W];  // 1 + index of the last glyph of the current line over the pixel
+    __shared__ uint8_t blue[VERIFY_TILE_H * VERIFY_TILE_W];
+    __shared__ uint32_t part[VERIFY_TILE_W / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y * n_pages;
+    const size_t W = page_w, H = page_h;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const Tile T = tile_at(tile, tiles_x, tiles_y, page_w, page_h);
+        const auto [page, r0, c0, r1, c1] = T;
+        for (uint32_t r = 0; r < VERIFY_TILE_H; r++) {
+            win[r * VERIFY_TILE_W + t] = 0;
+            blue[r * VERIFY_TILE_W + t] = 0;
+        }
+        __syncthreads();
+        // the page's lines in list order: a later line's ink replaces an earlier line's
+        const uint32_t i_lo = page_first[page], i_hi = page_first[page + 1];
+        for (uint32_t i = i_lo; i < i_hi; i++) {
+            const VerifyLine l = lines[i];
+            if (l.n == 0 || l.x0 >= c1 || l.x1 <= c0 || l.y0 >= r1 || l.y1 <= r0) continue;  // uniform across the workgroup
+            const VerifyRec *lr = recs + in[i].rec;
+            const uint8_t *bm = l.k ? fbitmaps : bitmaps;  // per line (l.k is its font), not per pixel
+            mark_glyphs(win, lr, l.n, T, lane, wave);
+            __syncthreads();
+            const int x = c0 + (int)t;
+            for (int y = r0; y < r1 && x < c1; y++) {
+                const uint32_t idx = (uint32_t)(y - r0) * VERIFY_TILE_W + t, w = win[idx];
+                if (!w) continue;
+                win[idx] = 0;
+                const uint8_t v = glyph_value(w, lr, bm, x, y);
+                if (v) blue[idx] = (uint8_t)(255 - v);  // canvas_to_lum8 then draw_verify: only v != 0 reaches the page
+            }
+            __syncthreads();
+        }
+        uint32_t acc = 0;
+        const int x = c0 + (int)t;
+        if (x < c1)
+            for (int y = r0; y < r1; y++) {
+                const size_t at = ((size_t)page * H + y) * W + x;
+                const uint8_t l = pages[at];
+                const uint8_t red = l != 255 ? l : 0, b = blue[(uint32_t)(y - r0) * VERIFY_TILE_W + t];
+                if (rgb) {
+                    rgb[at * 3] = red;
+                    rgb[at * 3 + 1] = 0;
+                    rgb[at * 3 + 2] = b;
+                }
+                const int dd = (int)red - (int)b;
+                acc += (uint32_t)(dd * dd);  // at most 16 * 255^2 per thread, 2^28 per workgroup
+            }
+        tile_add_sum(acc, part, &sums[page], t);
+    }
+}
+
+}  // namespace focr_dec
+
+using namespace focr_dec;
+
+extern "C" int focr_decoder_set_verify_font_candidates(focr_decoder_t *dec, const focr_verify_font_t *fonts, uint32_t n) {
+    const std::string who = "focr_decoder_set_verify_font_candidates: ";
+    if (!dec) return dfail(nullptr, who + "null decoder");
+    DEC_CHECK(hipSetDevice(dec->device));
+    dec->n_fvfonts = 0;
+    dec->d_fvglyphs.release();  // (every call that reads them ends with a stream wait)
+    dec->d_fvphases.release();
+    if (!fonts || !n) return dfail(dec, who + "bad arguments");
+    if (!dec->n_glyphs) return dfail(dec, who + "no decode font (focr_decoder_set_font)");
+    if (dec->cands.empty()) return dfail(dec, who + "no font candidates (focr_decoder_set_font_candidates)");
+    if (n != dec->cands.size()) return dfail(dec, who + "one table per uploaded candidate: " + std::to_string(dec->cands.size()) + " of them");
+    const size_t G = dec->n_glyphs, K = n;
+    std::vector<VerifyGlyph> vg(K * G);
+    std::vector<VerifyPhase> vp(K * G * FOCR_DECODE_PHASES);
+    for (size_t k = 0; k < K; k++) {
+        const focr_verify_font_t &font = fonts[k];
+        const FontCandidate &c = dec->cands[k];
+        const std::string pre = who + "candidate " + std::to_string(k + 1) + ": ";
+        if (!font.glyphs || font.n_glyphs != G || font.text_size != c.text_size || font.kerning != c.kerning || (font.hinting != 0) != (c.hinting != 0) ||
+            font.origin_y != c.origin_y)
+            return dfail(dec, pre + "the table does not match the candidate (glyph count, size, kerning, hinting or origin)");
+        if ((uint64_t)c.end_dw * 4 > 0xffffffffull) return dfail(dec, pre + "the candidates' bitmaps pass 4 GiB");
+        for (size_t i = 0; i < G; i++) {
+            const focr_verify_glyph_t &v = font.glyphs[i];
+            const focr_decode_glyph_t &d = c.glyphs[i];
+            if (v.codepoint != d.codepoint || memcmp(&v.increment, &d.increment, sizeof(float)) != 0)
+                return dfail(dec, pre + "the table does not match the candidate (code points or increments)");
+            for (float b : v.box)
+                if (!std::isfinite(b) || std::fabs(b) > (float)(1 << 20)) return dfail(dec, pre + "bad glyph box");
+            memcpy(vg[k * G + i].box, v.box, sizeof v.box);
+            for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
+                if ((uint64_t)v.rect_x[p] + v.rect_w[p] > d.box_w || (uint64_t)v.rect_y[p] + v.rect_h[p] > d.box_h)
+                    return dfail(dec, pre + "a phase rectangle leaves the candidate's box");
+                vp[(k * G + i) * FOCR_DECODE_PHASES + p] = VerifyPhase{
+                    d.off_x[p] + (int32_t)v.rect_x[p], d.off_y[p] + (int32_t)v.rect_y[p] - (int32_t)font.origin_y, v.rect_w[p], v.rect_h[p],
+                    (uint32_t)(c.base + d.offset + (uint64_t)p * d.stride * d.box_h + (uint64_t)v.rect_y[p] * d.stride + v.rect_x[p]), d.stride};
+            }
+        }
+    }
+    if (dec->d_fvglyphs.upload(vg.data(), vg.size()) != hipSuccess || dec->d_fvphases.upload(vp.data(), vp.size()) != hipSuccess) {
+        dec->d_fvglyphs.release();
+        dec->d_fvphases.release();
+        return dfail(dec, who + "hipMalloc / hipMemcpy failed");
+    }
+    dec->n_fvfonts = (uint32_t)K;
+    return 0;
+}
+
+extern "C" int focr_decoder_verify_text(focr_decoder_t *dec, const uint8_t *pages, int pages_on_device, size_t n_pages, size_t page_w, size_t page_h,
+                                        uint32_t x_start, const focr_text_line_t *lines, size_t n_lines, const uint16_t *chars, const uint32_t *pens,
+                                        const int8_t *offsets, size_t n_chars, uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums) {
+    const std::string who = "focr_decoder_verify_text: ";
+    if (!dec) return dfail(nullptr, who + "null decoder");
+    dec->vtext.ms = 0.f;
+    dec->vtext.launches = 0;
+    if (n_pages && !pages) return dfail(dec, who + "null pages");
+    if (n_lines && !lines) return dfail(dec, who + "null lines");
+    if (n_chars && !chars) return dfail(dec, who + "null chars");
+    if (n_pages && !sq_sums) return dfail(dec, who + "null sq_sums");
+    if (pens && offsets) return dfail(dec, who + "pens and offsets together (a character is placed by its pen or by its offset)");
+    if (!dec->n_glyphs) return dfail(dec, who + "no decode font (focr_decoder_set_font)");
+    Geometry g{};
+    if (batch_geometry(dec, "focr_decoder_verify_text", n_pages, page_w, page_h, x_start, 0, 0, 0, 1, &g)) return 1;
+    if (n_lines > 0x7fffffffu || n_pages > 0x7fffffffu) return dfail(dec, who + "too many lines or pages in one call");
+    const size_t K = dec->cands.size();
+    std::vector<TextLine> in(n_lines);
+    std::vector<uint32_t> page_first(n_pages + 1, 0);
+    uint64_t n_recs = 0;
+    bool decode_font = false, candidates = false;
+    for (size_t l = 0; l < n_lines; l++) {
+        const focr_text_line_t &s = lines[l];
+        const std::string pre = who + "line " + std::to_string(l) + ": ";
+        if (s.font > K) return dfail(dec, pre + "font " + std::to_string(s.font) + " with " + std::to_string(K) + " candidates uploaded (focr_decoder_set_font_candidates)");
+        if (s.page >= n_pages) return dfail(dec, pre + "page " + std::to_string(s.page) + " of " + std::to_string(n_pages));
+        if (l && s.page < lines[l - 1].page) return dfail(dec, pre + "its page lies before the previous line's (lines come in page order)");
+        if (s.first > n_chars || s.n_chars > n_chars - s.first) return dfail(dec, pre + "its characters end past n_chars");
+        (s.font ? candidates : decode_font) = true;
+        in[l] = TextLine{s.y, s.n_chars, s.font, 0, s.first, n_recs};
+        n_recs += s.n_chars;
+        page_first[s.page + 1] = (uint32_t)(l + 1);
+    }
+    for (size_t p = 1; p <= n_pages; p++) page_first[p] = std::max(page_first[p], page_first[p - 1]);  // a page without lines: an empty range
+    if (n_recs > 0xffffffffull) return dfail(dec, who + "too many characters in one call");
+    if (decode_font && !dec->n_vglyphs) return dfail(dec, who + "a line in font 0 and no verify table of the decode font (focr_decoder_set_verify_font)");
+    if (candidates && dec->n_fvfonts != K)
+        return dfail(dec, who + "a line in a candidate font and no verify tables of the candidates (focr_decoder_set_verify_font_candidates)");
+    for (size_t i = 0; i < n_chars; i++)
+        if (chars[i] >= dec->n_glyphs) return dfail(dec, who + "character " + std::to_string(i) + " is not an index into the alphabet");
+    for (size_t i = 0; pens && i < n_chars; i++)
+        if (pens[i] >= (1u << 24)) return dfail(dec, who + "pen " + std::to_string(i) + " is 2^24 or more (pens must stay exact in f32)");
+    if (n_pages == 0) return 0;
+    g.n_slots = 1;  // layout_line's slot 0; the line's row is its own y
+    const size_t px = n_pages * page_w * page_h;
+    const TileGrid tg = tile_grid(n_pages, page_w, page_h);
+    const size_t layout_blocks = std::max(n_lines, n_pages);
+    DEC_CHECK(hipSetDevice(dec->device));
+    const uint8_t *d_src = nullptr;
+    uint8_t *d_rgb = nullptr;
+    if (stage_in(dec, dec->d_xpages, pages, pages_on_device, px, &d_src) || stage_out(dec, dec->d_xrgb, rgb, rgb_on_device, px * 3, &d_rgb)) return 1;
+    DEC_GROW(dec->d_xlines, std::max<size_t>(n_lines, 1));
+    DEC_GROW(dec->d_xfirst, n_pages + 1);
+    DEC_GROW(dec->d_xchars, std::max<size_t>(n_chars, 1));
+    if (pens) DEC_GROW(dec->d_xpens, std::max<size_t>(n_chars, 1));
+    if (offsets) DEC_GROW(dec->d_xoffs, std::max<size_t>(n_chars, 1));
+    DEC_GROW(dec->d_xvlines, std::max<size_t>(n_lines, 1));
+    DEC_GROW(dec->d_xrecs, std::max<size_t>(n_recs, 1));
+    DEC_GROW(dec->d_xsums, n_pages);
+    if (n_lines) DEC_CHECK(hipMemcpyAsync(dec->d_xlines, in.data(), n_lines * sizeof(TextLine), hipMemcpyHostToDevice, dec->stream));
+    DEC_CHECK(hipMemcpyAsync(dec->d_xfirst, page_first.data(), (n_pages + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
+    if (n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_xchars, chars, n_chars * sizeof(uint16_t), hipMemcpyHostToDevice, dec->stream));
+    if (pens && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_xpens, pens, n_chars * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
+    if (offsets && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_xoffs, offsets, n_chars, hipMemcpyHostToDevice, dec->stream));
+    const TextFonts f{dec->d_glyphs, dec->d_fglyphs, dec->d_vglyphs, dec->d_fvglyphs, dec->d_vphases, dec->d_fvphases, dec->n_glyphs};
+    DEC_CHECK(hipEventRecord(dec->vtext.begin, dec->stream));
+    verify_layout_text_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, (uint32_t)n_lines, x_start, dec->d_xlines, dec->d_xchars,
+                                                                              offsets ? (const int8_t *)dec->d_xoffs : nullptr,
+                                                                              pens ? (const uint32_t *)dec->d_xpens : nullptr, f, dec->d_xvlines,
+                                                                              dec->d_xrecs, dec->d_xsums);
+    DEC_CHECK(hipGetLastError());
+    verify_compose_text_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(d_src, g.page_w, g.page_h, (uint32_t)n_pages, tg.tiles_x, tg.tiles_y, dec->d_xfirst,
+                                                                           dec->d_xlines, dec->d_xvlines, dec->d_xrecs, (const uint8_t *)dec->d_bitmaps,
+                                                                           (const uint8_t *)dec->d_fbitmaps, d_rgb, dec->d_xsums);
+    DEC_CHECK(hipGetLastError());
+    DEC_CHECK(hipEventRecord(dec->vtext.end, dec->stream));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit sums");
+    DEC_CHECK(hipMemcpyAsync(sq_sums, dec->d_xsums, n_pages * sizeof(uint64_t), hipMemcpyDeviceToHost, dec->stream));
+    if (fetch_out(dec, rgb, rgb_on_device, d_rgb, px * 3)) return 1;
+    DEC_CHECK(hipStreamSynchronize(dec->stream));
+    DEC_CHECK(hipEventElapsedTime(&dec->vtext.ms, dec->vtext.begin, dec->vtext.end));
+    dec->vtext.launches = 2;
+    return 0;
+}
+
+extern "C" float focr_decoder_last_verify_text_ms(const focr_decoder_t *dec) { return dec ? dec->vtext.ms : 0.f; }
+extern "C" uint32_t focr_decoder_last_verify_text_launches(const focr_decoder_t *dec) { return dec ? dec->vtext.launches : 0; }

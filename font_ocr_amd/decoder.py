@@ -34,6 +34,8 @@
         # every line decoded in the decode font (0) and in each candidate (1, 2) and the cheapest reading kept: pages that
         # mix fonts, or a font whose size, kerning or hinting is being looked for; fonts[page][line]: the winner's index,
         # costs[page][line]: its sum of footprint terms.  With whole_line=True: pages, pens, costs, fonts
+        sums, images = dec.verify_text(luma_pages, pages, 45, fonts=fonts)
+        # focr --verify of a reading the caller supplies, each line in its own font: a font search's result, or edited text
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -250,6 +252,8 @@ class LineDecoder:
         self._vfont = None
         self._batch = None  # (n_pages, page_h, page_w) of the last run
         self._candidates = []  # the DecodeFonts of set_font_candidates
+        self._vcands = None  # ... and their VerifyFonts, once verify_text() has built them
+        self.last_verify_text_ms = 0.0
         for attr, _, default in _SETTINGS:
             setattr(self, attr, default)
 
@@ -263,7 +267,7 @@ class LineDecoder:
         of 2^-y_bits px; a DecodeFont brings its own."""
         font = font_path if isinstance(font_path, DecodeFont) else DecodeFont(font_path, text_size, alphabet, hinting, kerning, y_bits)
         self._vfont, self._batch = None, None  # the library drops its verify table, its y-phase fonts and its last run here too
-        self._candidates = []  # ... and the candidates of the font search
+        self._candidates, self._vcands = [], None  # ... and the candidates of the font search, with their verify tables
         self._check(self._lib.focr_decoder_set_font(self._h, C.byref(font.s)))
         self.font = font
         if font.y_bits:
@@ -286,7 +290,7 @@ class LineDecoder:
         arr = (N.DecodeFontStruct * max(1, len(built)))()
         for i, f in enumerate(built):
             arr[i] = f.s  # the struct by value: its tables stay the DecodeFont's
-        self._candidates = []
+        self._candidates, self._vcands = [], None  # the library drops the candidates' verify tables here too
         self._check(self._lib.focr_decoder_set_font_candidates(self._h, arr, len(built)))
         self._candidates = built
         return built
@@ -318,6 +322,89 @@ class LineDecoder:
             vf = VerifyFont(f.font_path, f.text_size, f.alphabet, f.hinting, f.kerning)
             self._check(self._lib.focr_decoder_set_verify_font(self._h, C.byref(vf.s)))
             self._vfont = vf
+
+    def _ensure_verify_candidates(self):
+        if self._vcands is None:
+            built = [VerifyFont(f.font_path, f.text_size, f.alphabet, f.hinting, f.kerning) for f in self._candidates]
+            arr = (N.VerifyFontStruct * max(1, len(built)))()
+            for i, vf in enumerate(built):
+                arr[i] = vf.s  # the struct by value: its tables stay the VerifyFont's
+            self._check(self._lib.focr_decoder_set_verify_font_candidates(self._h, arr, len(built)))
+            self._vcands = built
+
+    def verify_text(self, luma_pages, lines, x, fonts=None, pens=None, offsets=None, images=True):
+        """focr --verify of a reading the caller supplies (focr_decoder_verify_text): (sums, images), as verify() returns them,
+        for luma_pages (as for decode(); pages are grouped by size) under lines, [[(y, text), ...] per page]: every line rendered
+        at (x, y) as render() renders a string, in list order (a later line's ink replaces an earlier line's blue).
+        fonts, [[k, ...] per page], draws line by line in the decode font (0) or in candidate k of set_font_candidates();
+        None is the decode font throughout.  pens (per page and line a sequence of 1/64 px, one per character) places every
+        character at its pen, as the verify does after decode(whole_line=True); offsets (likewise) moves the pen by
+        offsets / 64 px before each character and advances from there, as after decode(pen_search=N); giving both raises.
+        The inputs have the shapes decode() returns, so a font search's picture is
+            res = dec.decode(pages, x, y, w, lh, la, font_search=True); dec.verify_text(pages, res[0], x, fonts=res[1])
+        and an edited reading is drawn by editing res[0].  A character outside the alphabet raises ValueError.  sums is a
+        uint64 array in page order; images a per-page list of (H, W, 3) uint8 arrays, or None when images is false.  The verify
+        tables are built on first use.  The last decode and its verify() are left as they were."""
+        if self.font is None:
+            raise DecoderError("set_font() first")
+        if pens is not None and offsets is not None:
+            raise ValueError("verify_text takes pens or offsets, not both")
+        if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
+            pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
+        else:
+            pages = list(luma_pages)
+        lines = [list(pg) for pg in lines]
+        if len(lines) != len(pages):
+            raise ValueError(f"lines must hold one list per page: {len(lines)} for {len(pages)} pages")
+        for name, per in (("fonts", fonts), ("pens", pens), ("offsets", offsets)):
+            if per is not None and (len(per) != len(pages) or any(len(a) != len(b) for a, b in zip(per, lines))):
+                raise ValueError(f"{name} must hold one entry per line of lines")
+        index = {c: i for i, c in reversed(list(enumerate(self.font.alphabet)))}  # the first of equal characters
+        used = {int(k) for pg in fonts for k in pg} if fonts is not None else {0}
+        if not lines or not any(lines):
+            used = set()
+        if any(k < 0 or k > len(self._candidates) for k in used):
+            raise ValueError(f"fonts must be 0 .. {len(self._candidates)} (the decode font and the candidates of set_font_candidates)")
+        if 0 in used:
+            self._ensure_verify_font()
+        if used - {0}:
+            self._ensure_verify_candidates()
+        sums = np.zeros(len(pages), dtype=np.uint64)
+        out = [None] * len(pages) if images else None
+        by_size = {}
+        for i, p in enumerate(pages):
+            by_size.setdefault(np.asarray(p).shape, []).append(i)
+        for (h, w), idx in by_size.items():
+            batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
+            recs, chars, along = [], [], []
+            for j, i in enumerate(idx):
+                for q, (ly, text) in enumerate(lines[i]):
+                    try:
+                        cs = [index[c] for c in text]
+                    except KeyError as e:
+                        raise ValueError(f"verify_text: {e.args[0]!r} (page {i}, line {q}) is not in the alphabet") from None
+                    recs.append((j, int(ly), len(chars), len(cs), int(fonts[i][q]) if fonts is not None else 0))
+                    chars.extend(cs)
+                    per = pens if pens is not None else offsets
+                    if per is not None:
+                        if len(per[i][q]) != len(cs):
+                            raise ValueError(f"verify_text: page {i}, line {q}: {len(per[i][q])} pens or offsets for {len(cs)} characters")
+                        along.extend(int(v) for v in per[i][q])
+            larr = (N.TextLine * max(1, len(recs)))(*recs)
+            carr = np.array(chars, dtype=np.uint16) if chars else np.zeros(1, dtype=np.uint16)
+            parr = np.array(along, dtype=np.uint32) if pens is not None and along else None
+            oarr = np.array(along, dtype=np.int8) if offsets is not None and along else None
+            got = np.zeros(len(idx), dtype=np.uint64)
+            rgb = np.empty((len(idx), h, w, 3), dtype=np.uint8) if images else None
+            ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None  # noqa: E731
+            self._check(self._lib.focr_decoder_verify_text(self._h, ptr(batch), 0, len(idx), w, h, int(x), larr, len(recs), ptr(carr), ptr(parr),
+                                                           ptr(oarr), len(chars), ptr(rgb), 0, got.ctypes.data))
+            self.last_verify_text_ms = float(self._lib.focr_decoder_last_verify_text_ms(self._h))
+            for j, i in enumerate(idx):
+                sums[i] = got[j]
+                if images:
+                    out[i] = rgb[j]
+        return sums, out
 
     def test_images(self, luma_pages, x, y, width, line_height, line_advance, rgba=None, rect=True, text=True):
         """focr --test on the device: (rect_images, text_images), each a per-page list of (H, W, 4) uint8 RGBA images,

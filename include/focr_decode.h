@@ -466,11 +466,13 @@ int focr_decoder_set_line_frac(focr_decoder_t *dec, uint32_t y_frac, uint32_t ad
  *     ceil(64 * width / min inc64_k) * T_k >= 2^47, or a cost ring that does not fit in LDS; the message names the
  *     candidate's index.
  * focr_decoder_verify after a font-search run is refused with a message: drawing every line in its own font is a later
- * step.  focr_decoder_test_images knows no candidates.
+ * step.  That step is focr_decoder_verify_text (below), which takes the run's lines and their winners and draws each line in
+ * its own font.  focr_decoder_test_images knows no candidates.
  * What it does not cure: under the pen loop it is a monospace tool, as the greedy loop itself is (a proportional line is
  * lost under every candidate, and the cheapest wrong reading picks the font: that case needs the whole-line form);
  * focr --verify of a mixed-font run; candidates under scores, the pen search, margins, the pen slack or the baseline modes;
- * and candidates with different alphabets. */
+ * and candidates with different alphabets.  (The picture of a mixed-font run is focr --verify-fonts, over
+ * focr_decoder_verify_text; --verify itself stays refused beside --font-candidate.) */
 enum { FOCR_FONT_CANDIDATES_MAX = 16 };
 /* Upload candidates 1 ..= n (the decoder keeps its own copy); n == 0 or NULL drops them; focr_decoder_set_font drops them,
  * and so does a failed upload.  Refused: n > 15, a glyph count or code point that differs from the decode font's, a glyph
@@ -511,6 +513,61 @@ int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on_device, ui
 /* Device time of the last verify's kernels in ms (events), and their launch count (constant per batch). */
 float focr_decoder_last_verify_ms(const focr_decoder_t *dec);
 uint32_t focr_decoder_last_verify_launches(const focr_decoder_t *dec);
+
+/* ---- device: verify images of a caller's text (an extension: the verify above draws only what the last run decoded) ---- */
+
+/* focr_decoder_verify draws the last run's own lines in the decode font, so two readings of a page have no picture: what a
+ * font search decoded (every line in its winner's font), and a reading that somebody corrected after looking at scores,
+ * margins or a checksum.  focr_decoder_verify_text draws the same image and the same sums for a list of lines the caller
+ * supplies, each line in any font the decoder has uploaded.  All of it is exact:
+ *   - line l is drawn in font lines[l].font: 0 is the decode font of focr_decoder_set_font with the verify table of
+ *     focr_decoder_set_verify_font; 1 ..= K are the candidates of focr_decoder_set_font_candidates with the verify tables of
+ *     focr_decoder_set_verify_font_candidates;
+ *   - its text is chars[first .. first + n_chars), alphabet indices, rendered as render() renders a string: the f32 pen, the
+ *     union of the glyphs' round_out boxes, FreeType's delta trunc((-bounds.ox + pos) * 64) per glyph, all with that font's
+ *     increments, boxes, phase rectangles and origin_y;
+ *   - the canvas's top-left goes at (x_start, y) on page `page` and is clipped at the page's right and bottom edges; a line
+ *     with n_chars == 0 or y >= page_h draws nothing;
+ *   - pens and offsets both NULL: the pen of a glyph is the f32 sum of the increments before it, in text order;
+ *   - pens (1/64 px, beside chars, each below 2^24): glyph q of a line is placed at pens[first + q] / 64, whatever the
+ *     increments, as focr_decoder_verify places it after a whole-line run;
+ *   - offsets (1/64 px, beside chars): glyph q is placed at pen + offsets[first + q] / 64 and the pen advances from there by
+ *     its increment, as focr_decoder_verify does after a run with a pen search; pens and offsets together are refused;
+ *   - lines come in non-decreasing page order; within a page the list order is the drawing order: a later line's non-zero
+ *     pixels replace an earlier line's blue; y may come in any order and repeat, and lines may overlap and share characters;
+ *   - the image and the sums are focr_decoder_verify's: red = the page's luma where it is not 255, blue = 255 - v where the
+ *     last line over the pixel has v != 0, green = 0; rgb (n_pages x page_h x page_w x 3 bytes) in host memory, in device
+ *     memory of the decoder's device when rgb_on_device != 0, or NULL; sq_sums[n_pages] the exact sum of (R - B)^2; a page
+ *     without a line still gets its image and its sum.  pages as for focr_decoder_run.
+ * Refused, each with its own message and before anything is launched: NULL pages, lines, chars or sq_sums where there are
+ * pages, lines or characters; no decode font; a font above K (the message names the line's index); a font whose verify table
+ * is not uploaded (the message names the setter to call); a page index that decreases or is >= n_pages; first + n_chars past
+ * the n_chars of the call; a character index >= the alphabet's size; a pen >= 2^24 (all n_chars entries of chars and pens are
+ * checked); a page too large for focr_decoder_run.
+ * The call runs two launches in buffers of its own, as focr_decoder_test_images does: the last run, its getters, its timing
+ * and its focr_decoder_verify answer as they did before, and it needs no run at all.  Returns when rgb and sq_sums are
+ * written.  What it does not do: a per-line x, lines at sub-pixel rows, per-line sums. */
+/* focr_decoded_line_t with the font in pad's place: a caller can pass focr_decoder_get's lines unchanged (font 0). */
+typedef struct focr_text_line {
+    uint32_t page, y;
+    uint64_t first;
+    uint32_t n_chars;
+    uint32_t font;
+} focr_text_line_t;
+
+/* Upload the verify tables of the candidates 1 ..= n (the decoder keeps its own copy), fonts[k - 1] for candidate k.  Refused
+ * unless n is the number of uploaded candidates and every table matches its candidate: glyph count, code points, increments
+ * (bitwise), origin_y, size, kerning and hinting, and no phase rectangle leaves the candidate's box.
+ * focr_decoder_set_font, focr_decoder_set_font_candidates and a failed upload drop the tables. */
+int focr_decoder_set_verify_font_candidates(focr_decoder_t *dec, const focr_verify_font_t *fonts, uint32_t n);
+int focr_decoder_verify_text(focr_decoder_t *dec, const uint8_t *pages, int pages_on_device, size_t n_pages,
+                             size_t page_w, size_t page_h, uint32_t x_start,
+                             const focr_text_line_t *lines, size_t n_lines,
+                             const uint16_t *chars, const uint32_t *pens, const int8_t *offsets, size_t n_chars,
+                             uint8_t *rgb, int rgb_on_device, uint64_t *sq_sums);
+/* Device time of the last verify_text's kernels in ms (events), and their launch count (constant: 2; 0 after a refusal). */
+float focr_decoder_last_verify_text_ms(const focr_decoder_t *dec);
+uint32_t focr_decoder_last_verify_text_launches(const focr_decoder_t *dec);
 
 /* ---- device: test images (focr --test: draw_test_rectangles, draw_test_text, src/main.rs:241-298) ---------------- */
 

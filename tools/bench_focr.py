@@ -86,6 +86,15 @@ alternate with plain ones; with --whole-line as well, the same under the whole-l
   fonts_lines_other           lines of the batch won by another candidate than the decode font
   wfonts_*                    the same under the whole-line decode, over wfonts_whole_device_ms; wfonts_ceiling = K + 1: one
                               whole-line run per candidate (the winner is not decoded again)
+With --verify-text, also focr_decoder_verify_text (LineDecoder.verify_text) over the plain run's decoded lines, in calls that
+alternate with focr_decoder_verify of the same run, both with the images read back:
+  vtext_device_ms_per_batch   median device time of verify_text's two kernels
+  vtext_verify_device_ms      median device time of the verify's two kernels in between
+  vtext_over_verify           the ratio of the two
+  vtext_wall_ms               median host time of one verify_text call (the lines packed in Python, uploads, images read back)
+  vtext_equal                 verify_text's images and sums equal the verify's
+and with --font-candidates SIZES as well, one mixed-font call over the same lines, line q of a page drawn in font q mod (K + 1):
+  vtext_mixed_device_ms       median device time of its two kernels, beside vtext_mixed_fonts = K + 1
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -164,6 +173,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--verify", action="store_true", help="also time the device verify of the batch")
     ap.add_argument("--test-images", action="store_true", help="also time focr --test's images of the batch")
+    ap.add_argument("--verify-text", action="store_true", help="also time verify_text over the decoded lines against the verify of the same run")
     ap.add_argument("--scores", action="store_true", help="also time the decode with per-character scores on")
     ap.add_argument("--pen-search", type=int, default=0, metavar="N", help="also time the decode with a pen search of N/64 px")
     ap.add_argument("--whole-line", action="store_true", help="also time the whole-line decode")
@@ -231,6 +241,20 @@ def main():
                 vwall.append((time.perf_counter() - t) * 1e3)
                 vdev.append(dec.last_verify_ms)
             vlaunches = int(dec._lib.focr_decoder_last_verify_launches(dec._h))
+        if a.verify_text:
+            for _ in range(a.warmup):
+                want = dec.verify()
+                xgot = dec.verify_text(pages, out, geo[0])
+            xequal = np.array_equal(want[0], xgot[0]) and all(np.array_equal(p, q) for p, q in zip(want[1], xgot[1]))
+            xdev, xwall, xvdev = [], [], []
+            for _ in range(a.steps):
+                dec.verify()
+                xvdev.append(dec.last_verify_ms)
+                t = time.perf_counter()
+                dec.verify_text(pages, out, geo[0])
+                xwall.append((time.perf_counter() - t) * 1e3)
+                xdev.append(dec.last_verify_text_ms)
+            xlaunches = int(dec._lib.focr_decoder_last_verify_text_launches(dec._h))
         if a.scores:
             for _ in range(a.warmup):
                 dec.decode(pages, *geo, scores=True)
@@ -344,6 +368,13 @@ def main():
                 gwall.append((time.perf_counter() - t) * 1e3)
                 gdev.append(dec.last_ms)
             glaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+            if a.verify_text:  # the same lines, line q of a page in font q mod (K + 1)
+                mixed = [[q % (len(sizes) + 1) for q in range(len(pg))] for pg in out]
+                ydev = []
+                for _ in range(a.warmup + a.steps):
+                    dec.verify_text(pages, out, geo[0], fonts=mixed)
+                    ydev.append(dec.last_verify_text_ms)
+                ydev = ydev[a.warmup:]
         if sizes and a.whole_line:
             for _ in range(a.warmup):
                 dec.decode(pages, *geo, whole_line=True, font_search=True)
@@ -380,6 +411,14 @@ def main():
     if a.verify:
         res.update({"verify_device_ms_per_batch": round(float(np.median(vdev)), 4), "verify_launches": vlaunches,
                     "verify_wall_ms": round(float(np.median(vwall)), 3)})
+    if a.verify_text:
+        xms, xvms = float(np.median(xdev)), float(np.median(xvdev))
+        res.update({"vtext_device_ms_per_batch": round(xms, 4), "vtext_device_ms_min": round(float(min(xdev)), 4),
+                    "vtext_verify_device_ms": round(xvms, 4), "vtext_over_verify": round(xms / xvms, 3), "vtext_launches": xlaunches,
+                    "vtext_wall_ms": round(float(np.median(xwall)), 3), "vtext_equal": bool(xequal)})
+        if sizes:
+            res.update({"vtext_mixed_fonts": len(sizes) + 1, "vtext_mixed_device_ms": round(float(np.median(ydev)), 4),
+                        "vtext_mixed_device_ms_min": round(float(min(ydev)), 4)})
     if a.scores:
         sms, pms = float(np.median(sdev)), float(np.median(pdev))
         res.update({"scores_device_ms_per_batch": round(sms, 4), "scores_device_ms_min": round(float(min(sdev)), 4),
