@@ -339,6 +339,12 @@ class TextLine(C.Structure):
     _fields_ = [("page", C.c_uint32), ("y", C.c_uint32), ("first", C.c_uint64), ("n_chars", C.c_uint32), ("font", C.c_uint32)]
 
 
+class TextScoreStruct(C.Structure):
+    """focr_text_score_t (include/focr_decode.h)."""
+
+    _fields_ = [("line_base", C.c_uint64), ("cost", C.c_int64), ("shift", C.c_int32), ("pad", C.c_uint32)]
+
+
 class CharScore(C.Structure):
     """focr_char_score_t (include/focr_decode.h)."""
 
@@ -405,6 +411,11 @@ DECODE_HIP_SYMBOLS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     "focr_decoder_last_verify_text_ms": (C.c_float, [C.c_void_p]),
     "focr_decoder_last_verify_text_launches": (C.c_uint32, [C.c_void_p]),
+    "focr_decoder_score_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32,
+                                          C.c_void_p, C.c_void_p]),
+    "focr_decoder_last_score_text_ms": (C.c_float, [C.c_void_p]),
+    "focr_decoder_last_score_text_launches": (C.c_uint32, [C.c_void_p]),
     "focr_decoder_test_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_int]),

@@ -50,6 +50,12 @@
 //     --fonts without it.  --verify-fonts DIR is --verify's picture of such a run (focr_decoder_verify_text): DIR/<stem>.png and
 //     "<image> <mse>" on stderr exactly as --verify writes them, with every line drawn in its winning font and, under
 //     --whole-line, every character at its pen; without --font-candidate it is a usage error, and --verify stays one beside it.
+//   * --rank-text TEXT [--rank-shift N] is an extension that decodes nothing: TEXT, a line somebody read off the page, is
+//     scored at the first line slot (-x, -y, --width, --line-height) of the first -i image under the font of -f, -t, --kerning
+//     and --hinting (font 0) and under every --font-candidate (focr_decoder_score_text), each at the rigid shifts -N ..= N in
+//     1/64 px (N <= 64, default 0).  stdout is a CSV: the header font,shift,cost,line_base,error and one row per font, error =
+//     line_base + cost; the row with the lowest cost is the font (and its shift what to add to -x).  A character of TEXT
+//     outside the alphabet is a usage error, and so is --rank-shift without --rank-text.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -88,8 +94,9 @@ struct FontSpec {  // one --font-candidate
 struct Args {
     std::vector<std::string> img, candidate_specs;
     std::vector<FontSpec> candidates;
-    std::string fonts, verify_fonts;
-    bool have_fonts = false, have_verify_fonts = false;
+    std::string fonts, verify_fonts, rank_text;
+    bool have_fonts = false, have_verify_fonts = false, have_rank_text = false, have_rank_shift = false;
+    uint32_t rank_shift = 0;
     std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores, margins, baselines;
     bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false, have_margins = false;
     bool have_baselines = false, have_y_bits = false;
@@ -136,6 +143,8 @@ void print_help() {
            "      --font-candidate <SPEC>...       [extension] Also decode every line in this font and keep the cheapest reading; SPEC is f=PATH,t=SIZE,k=KERNING,h=0|1, omitted keys as -f, -t, --kerning, --hinting; at most 15 (only with the plain pen loop or the plain whole-line decode; not with --verify)\n"
            "      --fonts <FONTS>                  [extension] CSV of every line's winning font candidate and cost (only with --font-candidate)\n"
            "      --verify-fonts <DIR>             [extension] Dir for verify images of a --font-candidate run: every line drawn in its winning font (only with --font-candidate)\n"
+           "      --rank-text <TEXT>               [extension] Decode nothing: score TEXT at the first line slot of the first image under -f and every --font-candidate, a CSV row per font on stdout\n"
+           "      --rank-shift <N>                 [extension] Score TEXT at the rigid shifts -N ..= N in 1/64 px and keep the best, N <= 64 (only with --rank-text) [default: 0]\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -196,6 +205,8 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--font-candidate") a.candidate_specs.push_back(c.need());
         else if (k == "--fonts") a.fonts = c.need(), a.have_fonts = true;
         else if (k == "--verify-fonts") a.verify_fonts = c.need(), a.have_verify_fonts = true;
+        else if (k == "--rank-text") a.rank_text = c.need(), a.have_rank_text = true;
+        else if (k == "--rank-shift") a.rank_shift = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64"), a.have_rank_shift = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -235,6 +246,7 @@ Args parse_args(int argc, char **argv) {
     if (a.have_fonts && a.candidates.empty()) usage_error("the argument '--fonts <FONTS>' cannot be used without '--font-candidate <SPEC>'");
     if (a.have_verify_fonts && a.candidates.empty())
         usage_error("the argument '--verify-fonts <DIR>' cannot be used without '--font-candidate <SPEC>'");
+    if (a.have_rank_shift && !a.have_rank_text) usage_error("the argument '--rank-shift <N>' cannot be used without '--rank-text <TEXT>'");
     for (const auto &[with, name] : {std::pair<bool, const char *>{a.have_scores, "--scores <SCORES>"}, {a.pen_search != 0, "--pen-search <N>"},
                                      {a.pen_slack != 0, "--pen-slack <N>"}, {a.have_margins, "--margins <MARGINS>"},
                                      {a.baseline_search != 0, "--baseline-search <N>"}, {a.whole_baseline != 0, "--whole-baseline <N>"},
@@ -315,6 +327,43 @@ int run_test(const Args &args, const std::vector<uint32_t> &alphabet) {
     return 0;
 }
 
+// --rank-text TEXT: TEXT at the first line slot of the first -i image under font 0 and every --font-candidate, the same line
+// listed K + 1 times in one focr_decoder_score_text call; a CSV row per font on stdout.  Nothing is decoded.
+int run_rank(const Args &args, const std::vector<uint32_t> &alphabet, const std::vector<uint16_t> &text) {
+    if (args.img.empty()) die("--rank-text: no -i image to score against");
+    const std::string &img = args.img[0];
+    char err[256] = {0};
+    uint8_t *luma = nullptr;
+    size_t W = 0, H = 0;
+    if (focr_image_load_luma8(img.c_str(), &luma, &W, &H, err, sizeof err) != 0)
+        die("--rank-text: called `Result::unwrap()` on an `Err` value: " + std::string(err) + " (" + img + ")");
+    std::vector<focr_decode_font_t> fonts(1 + args.candidates.size());
+    for (size_t k = 0; k < fonts.size(); k++) {
+        const FontSpec c = k ? args.candidates[k - 1] : FontSpec{args.font, args.text_size, args.kerning, args.hinting};
+        if (focr_decode_font_build(c.font.c_str(), c.text_size, c.hinting, c.kerning, alphabet.data(), alphabet.size(), &fonts[k], err, sizeof err) != 0)
+            die((k ? "--rank-text: font candidate " + std::to_string(k) : std::string("--rank-text")) + ": decode font: " + err);
+    }
+    focr_decoder_t *dec = nullptr;
+    if (focr_decoder_create(0, &dec) != 0) die(std::string("--rank-text: no usable GPU: ") + focr_decoder_last_error(nullptr), 1);
+    if (focr_decoder_set_font(dec, &fonts[0]) != 0 ||
+        (fonts.size() > 1 && focr_decoder_set_font_candidates(dec, fonts.data() + 1, (uint32_t)fonts.size() - 1) != 0))
+        die(std::string("--rank-text: ") + focr_decoder_last_error(dec), 1);
+    std::vector<focr_text_line_t> lines(fonts.size());
+    for (size_t k = 0; k < lines.size(); k++) lines[k] = focr_text_line_t{0, args.y, 0, (uint32_t)text.size(), (uint32_t)k};
+    std::vector<focr_text_score_t> got(lines.size());
+    if (focr_decoder_score_text(dec, luma, 0, 1, W, H, args.x, args.width, args.line_height, lines.data(), lines.size(), text.data(), nullptr, nullptr,
+                                text.size(), nullptr, 0, args.rank_shift, nullptr, got.data()) != 0)
+        die(std::string("--rank-text: focr_decoder_score_text: ") + focr_decoder_last_error(dec), 1);
+    focr_decoder_destroy(dec);
+    for (focr_decode_font_t &f : fonts) focr_decode_font_free(&f);
+    free(luma);
+    printf("font,shift,cost,line_base,error\n");
+    for (size_t k = 0; k < got.size(); k++)
+        printf("%zu,%d,%lld,%llu,%lld\n", k, (int)got[k].shift, (long long)got[k].cost, (unsigned long long)got[k].line_base,
+               (long long)got[k].line_base + (long long)got[k].cost);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -328,7 +377,14 @@ int main(int argc, char **argv) {
         if (stat(args.verify_fonts.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) die("--verify-fonts should be a dir");
     }
     std::vector<uint32_t> alphabet = utf8_decode(args.alphabet);
+    std::vector<uint16_t> rank_text;  // --rank-text as alphabet indices (the first of equal characters)
+    for (uint32_t cp : utf8_decode(args.rank_text)) {
+        const auto at = std::find(alphabet.begin(), alphabet.end(), cp);
+        if (at == alphabet.end()) usage_error("invalid value '" + args.rank_text + "' for '--rank-text <TEXT>': '" + utf8_encode(cp) + "' is not in the alphabet");
+        rank_text.push_back((uint16_t)(at - alphabet.begin()));
+    }
     if (args.have_test) return run_test(args, alphabet);
+    if (args.have_rank_text) return run_rank(args, alphabet, rank_text);
     FILE *csv = nullptr;
     if (args.have_scores && !(csv = fopen(args.scores.c_str(), "w"))) usage_error("cannot write '" + args.scores + "' for '--scores'");
     FILE *mcsv = nullptr;

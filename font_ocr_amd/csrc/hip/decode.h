@@ -9,6 +9,7 @@
 //   decode_whole_fonts.hip     the whole-line decode under every candidate font
 //   decode_images.hip          the verify and --test images
 //   decode_text.hip            verify_text: a caller's lines drawn over their pages, each in any uploaded font
+//   decode_score.hip           score_text: the decoder's cost of a caller's lines, each in any uploaded font (over decode_pen.h)
 // (decode_line.h lies between decode.h and the files of a run; decode_line_frac.hip, decode_images.hip and decode_text.hip include decode.h alone.)  Here: the batch geometry, both line grids, the device tables, the tile frame of
 // the compose kernels (ncc_images.hip is its third user), the blank test's crop, the settings (Modes), what a run resolves
 // them to (RunMode), what the last run left (LastRun), the decoder itself, and the host plumbing every entry point repeats
@@ -385,6 +386,15 @@ struct TextLine {
     uint64_t first, rec;
 };
 
+// One line of focr_decoder_score_text as the device reads it: the caller's line, where its terms start (a running sum of n
+// over the list: lines may share characters) and its baseline candidate q (0 without line_q).
+struct ScoreLine {
+    uint32_t page, y, n, font;
+    uint64_t first, out;
+    int32_t q;
+    uint32_t pad;
+};
+
 struct Stage {  // the kernels of one entry point's last call: device events around them, their time and their number
     hipEvent_t begin = nullptr, end = nullptr;
     float ms = 0.f;
@@ -396,7 +406,7 @@ struct Stage {  // the kernels of one entry point's last call: device events aro
 struct focr_decoder {
     int device = 0;
     hipStream_t stream = nullptr;
-    focr_dec::Stage run, verify, test, vtext;
+    focr_dec::Stage run, verify, test, vtext, stext;
     std::string err;
     // font
     uint32_t n_glyphs = 0;
@@ -498,6 +508,15 @@ struct focr_decoder {
     focr::DevArray<focr_dec::VerifyLine> d_xvlines;
     focr::DevArray<focr_dec::VerifyRec> d_xrecs;
     focr::DevArray<unsigned long long> d_xsums;
+    // score_text (decode_score.hip): buffers of its own as well; d_sstrips only when a line's strip does not fit in LDS
+    focr::DevArray<uint8_t> d_spages, d_sstrips;
+    focr::DevArray<focr_dec::ScoreLine> d_slines;
+    focr::DevArray<focr_text_score_t> d_sout;
+    focr::DevArray<uint16_t> d_schars;
+    focr::DevArray<uint32_t> d_spens;
+    focr::DevArray<int8_t> d_soffs;
+    focr::DevArray<focr_dec::FontDesc> d_sdesc;
+    focr::DevArray<int32_t> d_sterms;
 };
 
 namespace focr_dec {

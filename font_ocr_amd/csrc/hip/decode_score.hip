@@ -1,0 +1,321 @@
+// decode_score.hip — focr_decoder_score_text (include/focr_decode.h): the decoder's own cost of lines the caller supplies,
+// each line in any font the decoder has uploaded: the decode font (0) or a candidate of the font search (1 ..= K).  Per line
+// the sum of r^2 over its crop (line_base), every character's footprint term, and their sum: the number every mode of the
+// decoder minimises, for a reading that was decoded, corrected, or typed in.  There is nothing to decode: one glyph per
+// character, no alphabet per step and no dynamic programme.  With a shift radius N the whole line is scored 2N + 1 times,
+// moved rigidly by j / 64 px, and the lowest (cost, rank of j) is the line.
+//
+// score_text_kernel, one workgroup of four waves per listed line:
+//   - the line's crop is inverted into a PAD-padded strip (what line_prepass_kernel builds) in LDS, and line_base is summed
+//     on the way; a strip that does not fit LDS_STRIP_MAX is built in global memory by score_strip_kernel first (a launch
+//     of its own, in front) and read from there;
+//   - wave w takes the shift candidates of rank w, w + 4, ...; within a candidate the lanes take the characters, 64 at a
+//     time: the f32 pen walk is sequential (one readlane and one or two adds per character, as layout_line does it), the
+//     terms are the work and come from footprint_term_wide (decode_pen.h), with the row move d it already takes;
+//   - a wave keeps its lowest (cost, rank); the four waves meet in LDS, and every wave works out the same winner;
+//   - the winner's terms are computed once more by all four waves, 64 characters a wave, and written once; with one
+//     candidate (N = 0) that pass is the only one.
+// Fonts are read as the font search reads them (a FontDesc per font 0 ..= K), y-phases as the baseline search does (the
+// tables of focr_decoder_set_baseline_fonts, v-major).  Everything is exact integer arithmetic but the f32 pen.
+#include <cmath>
+#include <cstring>
+
+#include "decode_pen.h"
+
+namespace focr_dec {
+
+constexpr uint32_t SCORE_THREADS = 256;  // one workgroup of four waves per listed line
+constexpr uint32_t SCORE_WAVES = SCORE_THREADS / 64;
+// per wave: (cost, rank) of the search, the winner's partial cost, the partial line_base; in front of the strip
+constexpr uint32_t SCORE_RED_BYTES = SCORE_WAVES * 4 * 8;
+
+// The fonts 0 ..= K and the y-phases v >= 1 of font 0 as a line reads them.
+struct ScoreFonts {
+    const DevGlyph *glyphs, *fglyphs, *yglyphs;
+    const int2 *offs, *foffs, *yoffs;
+    const uint32_t *bitmaps, *fbitmaps, *ybitmaps;
+    const FontDesc *desc;  // [K + 1]: glyph_base, end_dw, origin_x and origin_d (64 * origin_x where it is whole)
+    uint32_t n_glyphs, yn_dw;
+    uint32_t bits;         // B of line_q
+};
+
+// The tables one line renders from, chosen once per workgroup.
+struct ScoreFont {
+    const DevGlyph *glyphs;
+    const int2 *offs;
+    const uint32_t *bitmaps, *end;
+    float origin_x;
+    int origin_d;
+};
+
+struct ScoreText {  // the line's text and how it is placed
+    const uint16_t *chars;
+    const uint32_t *pens;  // null: the pen walk
+    const int8_t *offs;    // null: no per-character offsets
+    uint32_t n;
+};
+
+// The wave's sum of every lane's v (mod 2^64, so a signed sum as well), in every lane.
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+    for (int m = 32; m >= 1; m >>= 1) v += shfl_xor_u64(v, m);
+    return v;
+}
+
+// The inverted strip of a crop (w columns by h rows at src, PAD zero bytes in front of every row, sdw dwords a row), by a
+// workgroup of SCORE_THREADS; this thread's share of the sum of r^2.
+__device__ __forceinline__ uint64_t score_stage(uint32_t *dst, const uint8_t *__restrict__ src, uint32_t page_w, uint32_t w, uint32_t h, uint32_t sdw) {
+    uint64_t acc = 0;
+    for (uint32_t i = threadIdx.x; i < sdw * h; i += SCORE_THREADS) {
+        const uint32_t row = i / sdw;
+        const int col = 4 * (int)(i % sdw) - (int)PAD;
+        uint32_t v = 0;
+        for (int b = 0; b < 4; b++)
+            if (col + b >= 0 && (uint32_t)(col + b) < w) v |= (uint32_t)(uint8_t)(255 - src[(size_t)row * page_w + col + b]) << (8 * b);
+        dst[i] = v;
+        acc += __builtin_amdgcn_udot4(v, v, 0u, false);
+    }
+    return acc;
+}
+
+// A line's crop as image::crop_imm clamps it: its first pixel and its rows (0 when the crop is empty either way).
+__device__ __forceinline__ const uint8_t *score_crop(const uint8_t *__restrict__ pages, const Geometry &g, const ScoreLine &l, uint32_t *h) {
+    const uint32_t yc = std::min(l.y, g.page_h);
+    *h = g.w ? std::min(g.line_height, g.page_h - yc) : 0;
+    return pages + (size_t)l.page * g.page_w * g.page_h + (size_t)yc * g.page_w + g.x;
+}
+
+// 1. (only when the strip does not fit in LDS) every listed line's strip into global memory, one workgroup per line
+__global__ __launch_bounds__(SCORE_THREADS) void score_strip_kernel(const uint8_t *__restrict__ pages, Geometry g, const ScoreLine *__restrict__ in,
+                                                                    uint8_t *__restrict__ strips) {
+    const ScoreLine l = in[blockIdx.x];
+    uint32_t h;
+    const uint8_t *src = score_crop(pages, g, l, &h);
+    (void)score_stage((uint32_t *)(strips + (size_t)blockIdx.x * g.stride * g.line_height), src, g.page_w, g.w, h, g.stride / 4);
+}
+
+// The line's summed terms with the whole line moved by j / 64 px, over the 64-character batches wv, wv + nw, ... of the
+// line (every wave walks the whole pen); with WRITE the terms go to `terms` (null: nowhere).  The wave's sum, in every lane.
+template <bool WRITE>
+__device__ __forceinline__ int64_t score_line(const uint32_t *strip, uint32_t sdw, int w, uint32_t h, const ScoreFont &f, const ScoreText &t, int d, int j,
+                                              uint32_t wv, uint32_t nw, uint32_t lane, int32_t *__restrict__ terms) {
+    int64_t cost = 0;
+    float pen = 0.f;
+    for (uint32_t base = 0, batch = 0; base < t.n; base += 64, batch++) {
+        const uint32_t i = base + lane, m = std::min(64u, t.n - base);
+        const bool live = i < t.n, mine = batch % nw == wv;  // mine: uniform
+        if (t.pens && !mine) continue;
+        const uint32_t c = live ? t.chars[i] : 0;
+        int delta;
+        if (t.pens) {  // the whole-line programme's: 64 * origin_x + s_g, all integers
+            delta = f.origin_d + (live ? (int)t.pens[i] : 0) + j;
+        } else {  // the pen loop's one add, or the pen search's two; the rigid shift joins the first character's offset
+            const float inc = live ? f.glyphs[c].inc : 0.f;
+            const float dj = (float)((live && t.offs ? (int)t.offs[i] : 0) + (i == 0 ? j : 0)) * 0.015625f;
+            float pos = 0.f;
+            for (uint32_t q = 0; q < m; q++) {
+                pen = __fadd_rn(pen, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dj), q)));
+                if (lane == q) pos = pen;
+                pen = __fadd_rn(pen, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), q)));
+            }
+            if (!mine) continue;
+            delta = (int)__fmul_rn(__fadd_rn(f.origin_x, pos), 64.0f);  // FreeType's delta: trunc(t * 64), negative ones included
+        }
+        int term = 0;
+        if (live) {
+            const uint32_t phase = (uint32_t)delta & 63u;
+            const int shift = delta >> 6;
+            const DevGlyph gl = f.glyphs[c];
+            const int2 o = f.offs[c * 64 + phase];
+            const uint32_t *tile = f.bitmaps + gl.off_dw + phase * gl.ndw * gl.box_h;
+            term = footprint_term_wide(strip, sdw, w, h, tile, f.end, gl.ndw, gl.box_h, shift + o.x, o.y + d);
+            if (WRITE && terms) terms[i] = term;
+        }
+        cost += term;
+    }
+    return (int64_t)wave_sum((uint64_t)cost);
+}
+
+// 2. the lines' costs, one workgroup per listed line
+template <bool LDS>
+__global__ __launch_bounds__(SCORE_THREADS) void score_text_kernel(const uint8_t *__restrict__ pages, Geometry g, const ScoreLine *__restrict__ in,
+                                                                   const uint16_t *__restrict__ chars, const uint32_t *__restrict__ pens,
+                                                                   const int8_t *__restrict__ offs, ScoreFonts fonts, uint32_t radius,
+                                                                   const uint8_t *__restrict__ strips, int32_t *__restrict__ terms,
+                                                                   focr_text_score_t *__restrict__ out) {
+    extern __shared__ __align__(8) uint32_t lds_score[];  // the waves' pairs and partial sums, then (LDS) the strip
+    uint64_t *red = (uint64_t *)lds_score;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));  // uniform, and the compiler knows it
+    const ScoreLine l = in[blockIdx.x];
+    const uint32_t sdw = g.stride / 4;
+    uint32_t h;
+    const uint8_t *src = score_crop(pages, g, l, &h);
+    const uint32_t *strip;
+    uint64_t acc = 0;
+    if (LDS) {
+        uint32_t *lds_strip = lds_score + SCORE_RED_BYTES / 4;
+        acc = score_stage(lds_strip, src, g.page_w, g.w, h, sdw);
+        strip = lds_strip;
+    } else {  // score_strip_kernel's: the rows below h hold nothing of this line, and a row's pad bytes are zero
+        strip = (const uint32_t *)(strips + (size_t)blockIdx.x * g.stride * g.line_height);
+        for (uint32_t i = tid; i < sdw * h; i += SCORE_THREADS) acc += __builtin_amdgcn_udot4(strip[i], strip[i], 0u, false);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) red[3 * SCORE_WAVES + wave] = acc;
+    __syncthreads();  // the strip is staged
+    // the line's font, its y-phase and its rows' move: uniform across the workgroup
+    const FontDesc fd = fonts.desc[l.font];
+    const uint32_t v = (uint32_t)l.q & ((1u << fonts.bits) - 1);  // 0 for every font but 0 (refused on the host)
+    const int d = l.q >> fonts.bits;                              // floor
+    ScoreFont f;
+    if (l.font) {
+        f = ScoreFont{fonts.fglyphs + fd.glyph_base, fonts.foffs + (size_t)fd.glyph_base * 64, fonts.fbitmaps, fonts.fbitmaps + fd.end_dw, fd.origin_x, fd.origin_d};
+    } else if (v) {
+        const size_t at = (size_t)(v - 1) * fonts.n_glyphs;
+        f = ScoreFont{fonts.yglyphs + at, fonts.yoffs + at * 64, fonts.ybitmaps, fonts.ybitmaps + fonts.yn_dw, fd.origin_x, fd.origin_d};
+    } else {
+        f = ScoreFont{fonts.glyphs, fonts.offs, fonts.bitmaps, fonts.bitmaps + fd.end_dw, fd.origin_x, fd.origin_d};
+    }
+    const ScoreText t{chars + l.first, pens ? pens + l.first : nullptr, offs ? offs + l.first : nullptr, l.n};
+    const int w = (int)g.w;
+    uint32_t best_rank = 0;
+    const uint32_t n_cand = 2 * radius + 1;
+    if (n_cand > 1) {
+        int64_t best_cost = INT64_MAX;
+        best_rank = ~0u;  // a wave without a candidate: never the winner (wave 0 always has rank 0)
+        for (uint32_t rank = wave; rank < n_cand; rank += SCORE_WAVES) {
+            const int64_t cost = score_line<false>(strip, sdw, w, h, f, t, d, rank_offset(rank), 0, 1, lane, nullptr);
+            if (cost < best_cost) best_cost = cost, best_rank = rank;  // a wave's ranks ascend: the first of equal costs stays
+        }
+        if (lane == 0) red[2 * wave] = (uint64_t)best_cost, red[2 * wave + 1] = best_rank;
+        __syncthreads();
+        best_cost = (int64_t)red[0], best_rank = (uint32_t)red[1];
+        for (uint32_t u = 1; u < SCORE_WAVES; u++) {
+            const int64_t c = (int64_t)red[2 * u];
+            const uint32_t r = (uint32_t)red[2 * u + 1];
+            if (c < best_cost || (c == best_cost && r < best_rank)) best_cost = c, best_rank = r;
+        }
+        best_rank = (uint32_t)__builtin_amdgcn_readfirstlane((int)best_rank);
+    }
+    const int j = rank_offset(best_rank);
+    const int64_t part = score_line<true>(strip, sdw, w, h, f, t, d, j, wave, SCORE_WAVES, lane, terms ? terms + l.out : nullptr);
+    if (lane == 0) red[2 * SCORE_WAVES + wave] = (uint64_t)part;
+    __syncthreads();
+    if (tid == 0) {
+        uint64_t base = 0;
+        int64_t cost = 0;
+        for (uint32_t u = 0; u < SCORE_WAVES; u++) base += red[3 * SCORE_WAVES + u], cost += (int64_t)red[2 * SCORE_WAVES + u];
+        out[blockIdx.x] = focr_text_score_t{base, cost, j, 0};
+    }
+}
+
+}  // namespace focr_dec
+
+using namespace focr_dec;
+
+namespace {
+
+bool whole_origin(float o) { return o >= 0.f && o <= 65536.f && o == floorf(o); }
+
+}  // namespace
+
+extern "C" int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages, int pages_on_device, size_t n_pages, size_t page_w, size_t page_h,
+                                       uint32_t x_start, uint32_t width, uint32_t line_height, const focr_text_line_t *lines, size_t n_lines,
+                                       const uint16_t *chars, const uint32_t *pens, const int8_t *offsets, size_t n_chars, const int8_t *line_q,
+                                       uint32_t y_bits, uint32_t shift_radius, int32_t *terms, focr_text_score_t *out) {
+    const std::string who = "focr_decoder_score_text: ";
+    if (!dec) return dfail(nullptr, who + "null decoder");
+    dec->stext.ms = 0.f;
+    dec->stext.launches = 0;
+    if (n_pages && !pages) return dfail(dec, who + "null pages");
+    if (n_lines && !lines) return dfail(dec, who + "null lines");
+    if (n_chars && !chars) return dfail(dec, who + "null chars");
+    if (n_lines && !out) return dfail(dec, who + "null out");
+    if (pens && offsets) return dfail(dec, who + "pens and offsets together (a character is placed by its pen or by its offset)");
+    if (!dec->n_glyphs) return dfail(dec, who + "no decode font (focr_decoder_set_font)");
+    if (width == 0) return dfail(dec, who + "width 0");
+    if (line_height == 0) return dfail(dec, who + "line_height 0");
+    if (shift_radius > FOCR_PEN_SEARCH_MAX) return dfail(dec, who + "the shift radius is at most 64 (one pixel)");
+    if (y_bits > FOCR_BASELINE_Y_BITS_MAX) return dfail(dec, who + "y_bits is at most 3");
+    Geometry g{};
+    if (batch_geometry(dec, "focr_decoder_score_text", n_pages, page_w, page_h, x_start, 0, width, 0, 1, &g)) return 1;
+    if (n_lines > 0x7fffffffu || n_pages > 0x7fffffffu) return dfail(dec, who + "too many lines or pages in one call");
+    if (line_q && y_bits && !(dec->have_base_fonts && dec->font_bits == y_bits))
+        return dfail(dec, who + "line_q with y_bits > 0 needs the y-phase fonts of that y_bits (focr_decoder_set_baseline_fonts)");
+    const size_t K = dec->cands.size();
+    const auto font_origin_x = [&](uint32_t k) { return k ? dec->cands[k - 1].origin_x : dec->origin_x; };
+    const auto font_origin_y = [&](uint32_t k) { return k ? dec->cands[k - 1].origin_y : dec->origin_y; };
+    std::vector<ScoreLine> in(n_lines);
+    uint64_t n_terms = 0;
+    for (size_t l = 0; l < n_lines; l++) {
+        const focr_text_line_t &s = lines[l];
+        const std::string pre = who + "line " + std::to_string(l) + ": ";
+        if (s.font > K) return dfail(dec, pre + "font " + std::to_string(s.font) + " with " + std::to_string(K) + " candidates uploaded (focr_decoder_set_font_candidates)");
+        if (s.page >= n_pages) return dfail(dec, pre + "page " + std::to_string(s.page) + " of " + std::to_string(n_pages));
+        if (s.first > n_chars || s.n_chars > n_chars - s.first) return dfail(dec, pre + "its characters end past n_chars");
+        if (pens && !whole_origin(font_origin_x(s.font)))
+            return dfail(dec, pre + "pens need its font's origin_x to be a whole number >= 0 (at most 65536)");
+        const int q = line_q ? line_q[l] : 0;
+        if (line_q && s.font && (q & ((1 << y_bits) - 1)))
+            return dfail(dec, pre + "a fractional-phase q in a candidate font (the candidates have one vertical phase)");
+        if (line_q && !whole_origin(font_origin_y(s.font))) return dfail(dec, pre + "line_q needs its font's origin_y to be a whole number >= 0");
+        in[l] = ScoreLine{s.page, s.y, s.n_chars, s.font, s.first, n_terms, q, 0};
+        n_terms += s.n_chars;
+    }
+    if (n_terms > 0xffffffffull) return dfail(dec, who + "too many characters in one call");
+    for (size_t i = 0; i < n_chars; i++)
+        if (chars[i] >= dec->n_glyphs) return dfail(dec, who + "character " + std::to_string(i) + " is not an index into the alphabet");
+    for (size_t i = 0; pens && i < n_chars; i++)
+        if (pens[i] >= (1u << 24)) return dfail(dec, who + "pen " + std::to_string(i) + " is 2^24 or more (pens must stay exact in f32)");
+    if (n_lines == 0) return 0;
+    g.line_height = line_height;
+    g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;  // line_cap's
+    const size_t strip_bytes = (size_t)g.stride * line_height;
+    const bool lds = strip_bytes + SCORE_RED_BYTES <= LDS_STRIP_MAX;  // the strip shares LDS with the waves' pairs and sums
+    WholePlan plan;
+    if (fonts_plan(dec, &plan)) return 1;  // the descriptors of the fonts 0 ..= K
+    for (size_t k = 0; k < plan.fonts.size(); k++) plan.fonts[k].origin_d = whole_origin(plan.fonts[k].origin_x) ? 64 * (int)plan.fonts[k].origin_x : 0;
+    DEC_CHECK(hipSetDevice(dec->device));
+    const uint8_t *d_src = nullptr;
+    if (stage_in(dec, dec->d_spages, pages, pages_on_device, n_pages * page_w * page_h, &d_src)) return 1;
+    DEC_GROW(dec->d_slines, n_lines);
+    DEC_GROW(dec->d_schars, std::max<size_t>(n_chars, 1));
+    if (pens) DEC_GROW(dec->d_spens, std::max<size_t>(n_chars, 1));
+    if (offsets) DEC_GROW(dec->d_soffs, std::max<size_t>(n_chars, 1));
+    DEC_GROW(dec->d_sdesc, plan.fonts.size());
+    if (terms) DEC_GROW(dec->d_sterms, std::max<size_t>(n_terms, 1));
+    DEC_GROW(dec->d_sout, n_lines);
+    if (!lds) DEC_GROW(dec->d_sstrips, strip_bytes * n_lines);
+    DEC_CHECK(hipMemcpyAsync(dec->d_slines, in.data(), n_lines * sizeof(ScoreLine), hipMemcpyHostToDevice, dec->stream));
+    if (n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_schars, chars, n_chars * sizeof(uint16_t), hipMemcpyHostToDevice, dec->stream));
+    if (pens && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_spens, pens, n_chars * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
+    if (offsets && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_soffs, offsets, n_chars, hipMemcpyHostToDevice, dec->stream));
+    DEC_CHECK(hipMemcpyAsync(dec->d_sdesc, plan.fonts.data(), plan.fonts.size() * sizeof(FontDesc), hipMemcpyHostToDevice, dec->stream));
+    const ScoreFonts f{dec->d_glyphs, dec->d_fglyphs, dec->d_yglyphs, dec->d_offs, dec->d_foffs, dec->d_yoffs, dec->d_bitmaps.as<const uint32_t>(),
+                       dec->d_fbitmaps.as<const uint32_t>(), dec->d_ybitmaps.as<const uint32_t>(), dec->d_sdesc, dec->n_glyphs, dec->ybitmaps_dw,
+                       line_q ? y_bits : 0};
+    const uint32_t *d_pens = pens ? (const uint32_t *)dec->d_spens : nullptr;
+    const int8_t *d_offs = offsets ? (const int8_t *)dec->d_soffs : nullptr;
+    int32_t *d_terms = terms ? (int32_t *)dec->d_sterms : nullptr;
+    DEC_CHECK(hipEventRecord(dec->stext.begin, dec->stream));
+    if (lds) {
+        score_text_kernel<true><<<(uint32_t)n_lines, SCORE_THREADS, SCORE_RED_BYTES + strip_bytes, dec->stream>>>(
+            d_src, g, dec->d_slines, dec->d_schars, d_pens, d_offs, f, shift_radius, nullptr, d_terms, dec->d_sout);
+    } else {
+        score_strip_kernel<<<(uint32_t)n_lines, SCORE_THREADS, 0, dec->stream>>>(d_src, g, dec->d_slines, dec->d_sstrips);
+        DEC_CHECK(hipGetLastError());
+        score_text_kernel<false><<<(uint32_t)n_lines, SCORE_THREADS, SCORE_RED_BYTES, dec->stream>>>(
+            d_src, g, dec->d_slines, dec->d_schars, d_pens, d_offs, f, shift_radius, dec->d_sstrips, d_terms, dec->d_sout);
+    }
+    DEC_CHECK(hipGetLastError());
+    DEC_CHECK(hipEventRecord(dec->stext.end, dec->stream));
+    DEC_CHECK(hipMemcpyAsync(out, dec->d_sout, n_lines * sizeof(focr_text_score_t), hipMemcpyDeviceToHost, dec->stream));
+    if (terms && n_terms) DEC_CHECK(hipMemcpyAsync(terms, dec->d_sterms, n_terms * sizeof(int32_t), hipMemcpyDeviceToHost, dec->stream));
+    DEC_CHECK(hipStreamSynchronize(dec->stream));
+    DEC_CHECK(hipEventElapsedTime(&dec->stext.ms, dec->stext.begin, dec->stext.end));
+    dec->stext.launches = lds ? 1 : 2;
+    return 0;
+}
+
+extern "C" float focr_decoder_last_score_text_ms(const focr_decoder_t *dec) { return dec ? dec->stext.ms : 0.f; }
+extern "C" uint32_t focr_decoder_last_score_text_launches(const focr_decoder_t *dec) { return dec ? dec->stext.launches : 0; }

@@ -36,6 +36,10 @@
         # costs[page][line]: its sum of footprint terms.  With whole_line=True: pages, pens, costs, fonts
         sums, images = dec.verify_text(luma_pages, pages, 45, fonts=fonts)
         # focr --verify of a reading the caller supplies, each line in its own font: a font search's result, or edited text
+        scores = dec.score_text(luma_pages, pages, 45, 608, 12, fonts=fonts)
+        # the decoder's own cost of such a reading: scores[page][line] is a TextScore(base, cost, shift, terms)
+        base, cost, shift = dec.rank_text(luma_pages[0], 39, "the first line as a person reads it", 45, 608, 12, shift=8)
+        # a known string under the decode font and every candidate: the argmin of cost is the font, no decoding
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -74,6 +78,16 @@ class LineMargins(collections.namedtuple("LineMargins", "term runner margin")):
 
     __slots__ = ()
     NO_RUNNER = "\0"
+
+
+class TextScore(collections.namedtuple("TextScore", "base cost shift terms")):
+    """The decoder's cost of one line the caller supplied (LineDecoder.score_text).  base: the sum of r^2 over the line's
+    crop (int); cost: the sum of its characters' footprint terms at the winning rigid shift (int), what decode() returns as
+    a line's cost; shift: that shift in 1/64 px (0 without a shift search); terms: each character's footprint term (an
+    int32 array aligned with the text; None when not asked for).  base + cost is the squared error of the rendering
+    against the crop where footprints do not overlap."""
+
+    __slots__ = ()
 
 
 # The modes of one decode()/decode_device() call, checked (LineDecoder._modes).
@@ -254,6 +268,7 @@ class LineDecoder:
         self._candidates = []  # the DecodeFonts of set_font_candidates
         self._vcands = None  # ... and their VerifyFonts, once verify_text() has built them
         self.last_verify_text_ms = 0.0
+        self.last_score_text_ms = 0.0
         for attr, _, default in _SETTINGS:
             setattr(self, attr, default)
 
@@ -405,6 +420,107 @@ class LineDecoder:
                 if images:
                     out[i] = rgb[j]
         return sums, out
+
+    def score_text(self, luma_pages, lines, x, width, line_height, fonts=None, pens=None, offsets=None, baselines=None, y_bits=0, shift=0,
+                   terms=True):
+        """The decoder's cost of a reading the caller supplies (focr_decoder_score_text): per [page][line] a
+        TextScore(base, cost, shift, terms).  luma_pages and lines, [[(y, text), ...] per page], are decode()'s and
+        verify_text()'s; every line is cropped as decode() crops it (x, width, line_height at its y) and its text scored in
+        the decode font (0) or candidate fonts[page][line] of set_font_candidates(): base is the crop's sum of r^2, terms
+        each character's footprint term (an int32 array; None when terms is false) and cost their sum, the number every
+        mode of decode() minimises and returns.  Without pens and offsets the characters are placed as the pen loop places
+        them; offsets (per page and line one per character, 1/64 px) as after decode(pen_search=N); pens (likewise) as after
+        decode(whole_line=True); giving both raises.  baselines[page][line] is each line's q in steps of 2^-y_bits px, as
+        decode(baseline_search=N) returns it.  shift=N scores every line at the rigid shifts -N ..= N in 1/64 px and keeps the
+        lowest (cost, rank of the shift); TextScore.shift is the winner.  A character outside the alphabet raises ValueError.
+        The last decode, its results and its verify() are left as they were."""
+        if self.font is None:
+            raise DecoderError("set_font() first")
+        if pens is not None and offsets is not None:
+            raise ValueError("score_text takes pens or offsets, not both")
+        if not 0 <= int(shift) <= 64:
+            raise ValueError(f"shift must be 0 .. 64 (1/64 px), not {shift!r}")
+        if not 0 <= int(y_bits) <= 3:
+            raise ValueError(f"y_bits must be 0 .. 3, not {y_bits!r}")
+        if int(width) <= 0 or int(line_height) <= 0:
+            raise ValueError("score_text: width and line_height must be positive")
+        if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
+            pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
+        else:
+            pages = list(luma_pages)
+        lines = [list(pg) for pg in lines]
+        if len(lines) != len(pages):
+            raise ValueError(f"lines must hold one list per page: {len(lines)} for {len(pages)} pages")
+        for name, per in (("fonts", fonts), ("pens", pens), ("offsets", offsets), ("baselines", baselines)):
+            if per is not None and (len(per) != len(pages) or any(len(a) != len(b) for a, b in zip(per, lines))):
+                raise ValueError(f"{name} must hold one entry per line of lines")
+        used = {int(k) for pg in fonts for k in pg} if fonts is not None else set()
+        if any(k < 0 or k > len(self._candidates) for k in used):
+            raise ValueError(f"fonts must be 0 .. {len(self._candidates)} (the decode font and the candidates of set_font_candidates)")
+        index = {c: i for i, c in reversed(list(enumerate(self.font.alphabet)))}  # the first of equal characters
+        out = [[None] * len(pg) for pg in lines]
+        by_size = {}
+        for i, p in enumerate(pages):
+            by_size.setdefault(np.asarray(p).shape, []).append(i)
+        for (h, w), idx in by_size.items():
+            batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
+            recs, chars, along, qs, where = [], [], [], [], []
+            for j, i in enumerate(idx):
+                for q, (ly, text) in enumerate(lines[i]):
+                    try:
+                        cs = [index[c] for c in text]
+                    except KeyError as e:
+                        raise ValueError(f"score_text: {e.args[0]!r} (page {i}, line {q}) is not in the alphabet") from None
+                    recs.append((j, int(ly), len(chars), len(cs), int(fonts[i][q]) if fonts is not None else 0))
+                    where.append((i, q))
+                    chars.extend(cs)
+                    if baselines is not None:
+                        qs.append(int(baselines[i][q]))
+                    per = pens if pens is not None else offsets
+                    if per is not None:
+                        if len(per[i][q]) != len(cs):
+                            raise ValueError(f"score_text: page {i}, line {q}: {len(per[i][q])} pens or offsets for {len(cs)} characters")
+                        along.extend(int(v) for v in per[i][q])
+            got = self._score_text(batch, recs, chars, along if pens is not None else None, along if offsets is not None else None,
+                                   qs if baselines is not None else None, x, width, line_height, y_bits, shift, terms)
+            for (i, q), score in zip(where, got):
+                out[i][q] = score
+        return out
+
+    def _score_text(self, batch, recs, chars, pens, offsets, qs, x, width, line_height, y_bits, shift, terms):
+        """One focr_decoder_score_text call over an (N, H, W) uint8 batch: recs are (page, y, first, n_chars, font) into chars
+        (alphabet indices), pens / offsets lie beside chars and qs beside recs (None: not given).  A TextScore per record."""
+        n, h, w = batch.shape
+        larr = (N.TextLine * max(1, len(recs)))(*recs)
+        carr = np.array(chars, dtype=np.uint16) if chars else np.zeros(1, dtype=np.uint16)
+        parr = np.array(pens, dtype=np.uint32) if pens else None
+        oarr = np.array(offsets, dtype=np.int8) if offsets else None
+        qarr = np.array(qs, dtype=np.int8) if qs else None
+        n_terms = sum(r[3] for r in recs)
+        tarr = np.zeros(max(1, n_terms), dtype=np.int32) if terms else None
+        sarr = (N.TextScoreStruct * max(1, len(recs)))()
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None  # noqa: E731
+        self._check(self._lib.focr_decoder_score_text(self._h, ptr(batch), 0, n, w, h, int(x), int(width), int(line_height), larr, len(recs), ptr(carr),
+                                                      ptr(parr), ptr(oarr), len(chars), ptr(qarr), int(y_bits), int(shift), ptr(tarr), sarr))
+        self.last_score_text_ms = float(self._lib.focr_decoder_last_score_text_ms(self._h))
+        out, at = [], 0
+        for r, s in zip(recs, sarr):
+            out.append(TextScore(int(s.line_base), int(s.cost), int(s.shift), tarr[at: at + r[3]].copy() if terms else None))
+            at += r[3]
+        return out
+
+    def rank_text(self, page, y, text, x, width, line_height, shift=0):
+        """Which uploaded font renders a known string closest to the page: text scored at line slot (x, y) of one luma page
+        under the decode font and every candidate of set_font_candidates() in one call, the same line listed K + 1 times.
+        Returns (base, cost[K + 1], shift[K + 1]): the crop's sum of r^2, and per font its cost (int64) and its winning rigid
+        shift in 1/64 px (shift=N searches -N ..= N).  The argmin over (cost, k) is the font; base + cost[k] is its squared
+        error (footprints that overlap counted once each).  Nothing is decoded."""
+        page = np.asarray(page)
+        if page.ndim != 2:
+            raise ValueError("rank_text takes one luma page (H, W)")
+        k1 = len(self._candidates) + 1
+        got = self.score_text([page], [[(y, text)] * k1], x, width, line_height, fonts=[list(range(k1))], shift=shift, terms=False)[0]
+        return got[0].base, np.array([s.cost for s in got], dtype=np.int64), np.array([s.shift for s in got], dtype=np.int32)
 
     def test_images(self, luma_pages, x, y, width, line_height, line_advance, rgba=None, rect=True, text=True):
         """focr --test on the device: (rect_images, text_images), each a per-page list of (H, W, 4) uint8 RGBA images,

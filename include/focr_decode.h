@@ -546,7 +546,8 @@ uint32_t focr_decoder_last_verify_launches(const focr_decoder_t *dec);
  * checked); a page too large for focr_decoder_run.
  * The call runs two launches in buffers of its own, as focr_decoder_test_images does: the last run, its getters, its timing
  * and its focr_decoder_verify answer as they did before, and it needs no run at all.  Returns when rgb and sq_sums are
- * written.  What it does not do: a per-line x, lines at sub-pixel rows, per-line sums. */
+ * written.  What it does not do: a per-line x, lines at sub-pixel rows, per-line sums (the decoder's
+ * per-line cost is focr_decoder_score_text, below). */
 /* focr_decoded_line_t with the font in pad's place: a caller can pass focr_decoder_get's lines unchanged (font 0). */
 typedef struct focr_text_line {
     uint32_t page, y;
@@ -568,6 +569,75 @@ int focr_decoder_verify_text(focr_decoder_t *dec, const uint8_t *pages, int page
 /* Device time of the last verify_text's kernels in ms (events), and their launch count (constant: 2; 0 after a refusal). */
 float focr_decoder_last_verify_text_ms(const focr_decoder_t *dec);
 uint32_t focr_decoder_last_verify_text_launches(const focr_decoder_t *dec);
+
+/* ---- device: the cost of a caller's text (an extension: verify_text above gives a picture and one sum per page) ---- */
+
+/* Every mode of the decoder minimises a sum of footprint terms and returns it: scores, whole-line costs, the margins'
+ * terms, baseline costs, font costs.  focr_decoder_score_text computes that sum for lines the caller supplies, each in any
+ * font the decoder has uploaded: of a reading that was decoded (it then equals what the run returned), of one somebody
+ * corrected (is the edited line better or worse than the decoded one?), or of a string somebody typed in, under every
+ * candidate font (the font that renders a known first line closest to the page is the font: no decoding, exact for
+ * proportional fonts too).  There is one glyph per character to evaluate, not one alphabet per step, and no dynamic
+ * programme.  All of it is exact integer and f32 arithmetic:
+ *   - lines are focr_text_line_t, as for focr_decoder_verify_text, so focr_decoder_get's lines go in unchanged; unlike there
+ *     they may come in any page order; they may repeat and share characters;
+ *   - line l's crop is the decoder's: rows y .. y + min(line_height, page_h - y), columns x_start .. x_start + min(width,
+ *     page_w - x_start), clamped as image::crop_imm clamps; out[l].line_base is its sum of r^2, r = 255 - luma; an empty
+ *     crop has line_base 0 and every term 0;
+ *   - font k = lines[l].font: 0 is the decode font, 1 ..= K the candidates of focr_decoder_set_font_candidates, each with its
+ *     own glyph tables, increments and origin_x; no verify table is needed;
+ *   - pens and offsets both NULL: the pen loop's placement: pos starts at 0, glyph g is rendered at FreeType's delta
+ *     trunc((origin_x_k + pos) * 64) in f32, then pos = pos + increment, one f32 add;
+ *   - offsets (1/64 px, beside chars): the pen search's placement: p = pos + (float)offsets[g] * 0.015625f, the delta comes
+ *     from p, and pos = p + increment;
+ *   - pens (1/64 px, beside chars, each below 2^24): the whole-line programme's placement: delta = 64 * origin_x_k + pens[g],
+ *     which needs an origin_x_k that is a whole number >= 0; pens and offsets together are refused;
+ *   - the phase is delta & 63 and the whole-pixel shift delta >> 6 (an arithmetic shift), so a negative delta is what
+ *     FreeType would receive and nothing is dropped; the line does not end at pos >= width: a glyph wholly outside the crop
+ *     has term 0;
+ *   - line_q (NULL: none; else one per line): the line is rendered as the baseline modes render candidate q = line_q[l], in
+ *     steps of 2^-B px, B = y_bits <= FOCR_BASELINE_Y_BITS_MAX: from y-phase v = q & (2^B - 1) of the fonts of
+ *     focr_decoder_set_baseline_fonts, every box moved down q >> B rows (floor); bitmaps are clipped to the crop on all four
+ *     sides; on a fractional line grid pass the lines' y = yc_i and the run's absolute q;
+ *   - a character's term is the int32 footprint term the decoder compares: the sum of c * (c - 2 r) over the clipped bitmap;
+ *     out[l].cost is their sum over the line; terms (NULL: not wanted) takes one entry per listed character in list order,
+ *     line l's at the running sum of n_chars over the lines before it;
+ *   - shift_radius N, 0 <= N <= FOCR_PEN_SEARCH_MAX: every line is scored once per j in -N ..= N with the whole line moved
+ *     by j / 64 px: the pen-loop and offsets placements start from p_0 = (float)(offsets[0] + j) * 0.015625f (offsets[0] = 0
+ *     without offsets), the pens placement uses pens[g] + j for every glyph; the line's result is the lowest
+ *     (cost_j, rank(j)) with the pen search's rank (0, -1, +1, -2, ...); out[l].shift is that j, and cost and terms are its.
+ *     N = 0 scores once.
+ * Refused, each with its own message and before anything is launched: NULL pages, lines, chars or out where there are
+ * pages, lines or characters; pens and offsets together; no decode font; width 0 or line_height 0; a shift_radius or
+ * y_bits above its maximum; a page too large for focr_decoder_run; line_q with y_bits > 0 and no y-phase fonts of that
+ * y_bits; and per line (the message names its index) a font above K, a page index >= n_pages, first + n_chars past the
+ * n_chars of the call, pens with a font whose origin_x is fractional or negative, line_q with a fractional-phase q on a
+ * font other than 0 (the candidates have one vertical phase), line_q with a font whose origin_y is not a whole number
+ * >= 0; a character index >= the alphabet's size; a pen >= 2^24 (all n_chars entries of chars and pens are checked).
+ * The call runs one launch, or two when a line's strip does not fit in LDS (the strips are then built in global memory
+ * first), whatever the lines, the placement and the radius, in buffers of its own: the last run, its getters, its verify and
+ * their timings answer as they did before, and it needs no run at all.  pages as for focr_decoder_run.  Returns when out
+ * and terms are written; with n_lines == 0 nothing is launched.
+ * What it does not do: a per-line x; a vertical search (list the line at several (y, q)); a forced alignment that fits
+ * each character's offset to a known text; the true composed error where footprints overlap (line_base + cost counts an
+ * overlap once per glyph; the composed error stays focr_decoder_verify_text's page sum); any change to focr_decoder_run. */
+typedef struct focr_text_score {
+    uint64_t line_base;   /* sum of r^2 over the line's crop, r = 255 - luma */
+    int64_t  cost;        /* sum of the line's footprint terms at the winning shift */
+    int32_t  shift;       /* the winning rigid shift j in 1/64 px (0 when shift_radius == 0) */
+    uint32_t pad;
+} focr_text_score_t;
+
+int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages, int pages_on_device, size_t n_pages,
+                            size_t page_w, size_t page_h, uint32_t x_start, uint32_t width, uint32_t line_height,
+                            const focr_text_line_t *lines, size_t n_lines,
+                            const uint16_t *chars, const uint32_t *pens, const int8_t *offsets, size_t n_chars,
+                            const int8_t *line_q, uint32_t y_bits, uint32_t shift_radius,
+                            int32_t *terms, focr_text_score_t *out);
+/* Device time of the last score_text's kernels in ms (events), and their launch count (1, or 2 with global strips; 0 after a
+ * refusal or a call without lines). */
+float    focr_decoder_last_score_text_ms(const focr_decoder_t *dec);
+uint32_t focr_decoder_last_score_text_launches(const focr_decoder_t *dec);
 
 /* ---- device: test images (focr --test: draw_test_rectangles, draw_test_text, src/main.rs:241-298) ---------------- */
 

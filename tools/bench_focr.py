@@ -95,6 +95,15 @@ alternate with focr_decoder_verify of the same run, both with the images read ba
   vtext_equal                 verify_text's images and sums equal the verify's
 and with --font-candidates SIZES as well, one mixed-font call over the same lines, line q of a page drawn in font q mod (K + 1):
   vtext_mixed_device_ms       median device time of its two kernels, beside vtext_mixed_fonts = K + 1
+With --score-text, also focr_decoder_score_text (LineDecoder.score_text) over the plain run's decoded lines at the shift radii
+0, 8 and 64, in calls that alternate with the plain decode of the same batch:
+  stext_device_ms             median device time of score_text's launch per radius: {"0": .., "8": .., "64": ..}
+  stext_device_ms_min         ... and the lowest
+  stext_plain_device_ms       median device time of the plain decodes in between
+  stext_over_plain            stext_device_ms["0"] over it: one glyph per character against the alphabet per step
+  stext_over_radius0          per radius N the ratio to radius 0, beside stext_ceiling = 2N + 1
+  stext_wall_ms               median host time of one radius-0 call (the lines packed in Python, uploads, results read back)
+  stext_equal                 at radius 0 every line's terms and line_base equal the scores run's (decode(scores=True))
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -174,6 +183,7 @@ def main():
     ap.add_argument("--verify", action="store_true", help="also time the device verify of the batch")
     ap.add_argument("--test-images", action="store_true", help="also time focr --test's images of the batch")
     ap.add_argument("--verify-text", action="store_true", help="also time verify_text over the decoded lines against the verify of the same run")
+    ap.add_argument("--score-text", action="store_true", help="also time score_text over the decoded lines at shift radii 0, 8 and 64 against the plain decode")
     ap.add_argument("--scores", action="store_true", help="also time the decode with per-character scores on")
     ap.add_argument("--pen-search", type=int, default=0, metavar="N", help="also time the decode with a pen search of N/64 px")
     ap.add_argument("--whole-line", action="store_true", help="also time the whole-line decode")
@@ -255,6 +265,27 @@ def main():
                 xwall.append((time.perf_counter() - t) * 1e3)
                 xdev.append(dec.last_verify_text_ms)
             xlaunches = int(dec._lib.focr_decoder_last_verify_text_launches(dec._h))
+        if a.score_text:
+            crop = (geo[0], geo[2], geo[3])
+            _, want = dec.decode(pages, *geo, scores=True)
+            zgot = dec.score_text(pages, out, *crop)
+            zequal = all(g.base == w.base and np.array_equal(g.terms, w.score - w.base) for pg, pw in zip(zgot, want) for g, w in zip(pg, pw))
+            radii = (0, 8, 64)
+            for _ in range(a.warmup):
+                dec.decode(pages, *geo)
+                for n in radii:
+                    dec.score_text(pages, out, *crop, shift=n, terms=False)
+            zdev, zpdev, zwall = {n: [] for n in radii}, [], []
+            for _ in range(a.steps):
+                for n in radii:
+                    dec.decode(pages, *geo)
+                    zpdev.append(dec.last_ms)
+                    t = time.perf_counter()
+                    dec.score_text(pages, out, *crop, shift=n, terms=False)
+                    if n == 0:
+                        zwall.append((time.perf_counter() - t) * 1e3)
+                    zdev[n].append(dec.last_score_text_ms)
+            zlaunches = int(dec._lib.focr_decoder_last_score_text_launches(dec._h))
         if a.scores:
             for _ in range(a.warmup):
                 dec.decode(pages, *geo, scores=True)
@@ -419,6 +450,12 @@ def main():
         if sizes:
             res.update({"vtext_mixed_fonts": len(sizes) + 1, "vtext_mixed_device_ms": round(float(np.median(ydev)), 4),
                         "vtext_mixed_device_ms_min": round(float(min(ydev)), 4)})
+    if a.score_text:
+        zms, zpms = {n: float(np.median(v)) for n, v in zdev.items()}, float(np.median(zpdev))
+        res.update({"stext_device_ms": {str(n): round(v, 4) for n, v in zms.items()}, "stext_device_ms_min": {str(n): round(float(min(v)), 4) for n, v in zdev.items()},
+                    "stext_plain_device_ms": round(zpms, 4), "stext_over_plain": round(zms[0] / zpms, 3),
+                    "stext_over_radius0": {str(n): round(zms[n] / zms[0], 2) for n in zms}, "stext_ceiling": {str(n): 2 * n + 1 for n in zms},
+                    "stext_launches": zlaunches, "stext_wall_ms": round(float(np.median(zwall)), 3), "stext_equal": bool(zequal)})
     if a.scores:
         sms, pms = float(np.median(sdev)), float(np.median(pdev))
         res.update({"scores_device_ms_per_batch": round(sms, 4), "scores_device_ms_min": round(float(min(sdev)), 4),
