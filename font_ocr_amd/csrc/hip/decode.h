@@ -10,7 +10,9 @@
 //   decode_images.hip          the verify and --test images
 //   decode_text.hip            verify_text: a caller's lines drawn over their pages, each in any uploaded font
 //   decode_score.hip           score_text: the decoder's cost of a caller's lines, each in any uploaded font (over decode_pen.h)
-// (decode_line.h lies between decode.h and the files of a run; decode_line_frac.hip, decode_images.hip and decode_text.hip include decode.h alone.)  Here: the batch geometry, both line grids, the device tables, the tile frame of
+// (decode_line.h lies between decode.h and the files of a run; decode_line_frac.hip, decode_images.hip and decode_text.hip include decode.h alone.)
+// Below decode.h lies decode_font.h, host code alone: the record of an uploaded font (HostFont), the glyph and verify records the kernels
+// read, and the five font uploaders' checks and packing.  Here: the batch geometry, both line grids, the owners of the fonts' device tables, the tile frame of
 // the compose kernels (ncc_images.hip is its third user), the blank test's crop, the settings (Modes), what a run resolves
 // them to (RunMode), what the last run left (LastRun), the decoder itself, and the host plumbing every entry point repeats
 // (errors, stages, staging, refusals).
@@ -22,17 +24,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include "decode_font.h"
 #include "devmem.h"
 #include "focr_decode.h"
 
 namespace focr_dec {
-
-struct DevGlyph {
-    uint32_t off_dw;  // dword offset of phase 0 in the bitmap table
-    uint32_t ndw;     // dwords per bitmap row
-    uint32_t box_h;
-    float inc;
-};
 
 struct Geometry {
     uint32_t page_w, page_h;
@@ -114,17 +110,6 @@ __device__ __forceinline__ int slot_has_ink(const uint8_t *__restrict__ pages, c
     for (uint64_t k = threadIdx.x; k < n; k += TEST_THREADS) ink |= src[(k / g.w) * g.page_w + k % g.w] != 255;
     return ink;
 }
-
-struct VerifyGlyph {
-    float box[4];      // raster_bounds at the identity before round_out (focr_verify_glyph_t::box)
-};
-
-struct VerifyPhase {
-    int32_t x, y;      // top-left of the true bitmap on a line canvas at whole-pixel shift 0 and vertical translation 0
-    uint32_t w, h;
-    uint32_t src;      // byte offset of that top-left pixel in the bitmap table
-    uint32_t stride;
-};
 
 struct VerifyLine {    // one line slot: its canvas on the page, clipped (empty for a blank slot), and its glyph records
     int32_t x0, y0, x1, y1;
@@ -356,17 +341,46 @@ struct LastRun {
     const uint8_t *src = nullptr;  // its pages on the device
 };
 
-// One uploaded candidate of the font search (focr_decoder_set_font_candidates) as the host keeps it; its tables are on the device.
-struct FontCandidate {
-    float origin_x = 0.f, min_inc = 0.f;
-    std::vector<float> inc;
-    uint64_t term_bound = 0;  // the largest stride * box_h * 2 * 255^2 of its glyphs (a term's bound)
-    uint32_t end_dw = 0;      // the end of its bitmaps in the candidates' bitmap table, in dwords
-    // what set_verify_font_candidates checks and places the candidate's verify table against (decode_text.hip)
-    std::vector<focr_decode_glyph_t> glyphs;
-    uint64_t base = 0;        // where its bitmaps start in the candidates' bitmap table, in bytes
-    float origin_y = 0.f, text_size = 0.f, kerning = 0.f;
-    int hinting = 0;
+// One set of glyph tables on the device, all three arrays or none: glyph records and phase offsets font-major (PackedGlyphs), and one bitmap
+// table whose dword offsets the records carry (read as uint32_t by the decode kernels, as bytes by the compose kernels).
+struct GlyphTables {
+    focr::DevArray<DevGlyph> glyphs;
+    focr::DevArray<int2> offs;
+    focr::DevArray<uint8_t> bitmaps;
+    uint32_t n_dw = 0;  // dwords of the bitmap table
+    void release() { *this = GlyphTables{}; }
+    hipError_t upload(const PackedGlyphs &g, const uint8_t *bytes) {  // g.bytes of them
+        hipError_t e = glyphs.upload(g.glyphs.data(), g.glyphs.size());
+        if (e == hipSuccess) e = offs.upload(g.offs.data(), g.offs.size());
+        if (e == hipSuccess) e = bitmaps.upload(bytes, g.bytes, 4);
+        n_dw = (uint32_t)(g.bytes / 4);
+        if (e != hipSuccess) release();
+        return e;
+    }
+};
+
+// The verify tables beside a set of glyph tables (the decode font's, the candidates'): boxes and phase rectangles.
+struct VerifyTables {
+    focr::DevArray<VerifyGlyph> glyphs;
+    focr::DevArray<VerifyPhase> phases;
+    bool ok = false;    // uploaded for the fonts now beside them
+    uint32_t hmax = 0;  // the rows render() gives any line of them at most
+    void release() { *this = VerifyTables{}; }
+    hipError_t upload(const PackedVerify &v) {
+        hipError_t e = glyphs.upload(v.glyphs.data(), v.glyphs.size());
+        if (e == hipSuccess) e = phases.upload(v.phases.data(), v.phases.size());
+        hmax = (uint32_t)(v.y_hi - v.y_lo);
+        if (!(ok = e == hipSuccess)) release();
+        return e;
+    }
+};
+
+// The y-phase fonts v >= 1 of the decode font (focr_decoder_set_baseline_fonts), v-major.
+struct BaseFonts {
+    GlyphTables tables;
+    bool ok = false;          // uploaded for the current decode font, for y_bits `bits`
+    uint32_t bits = 0;
+    uint64_t term_bound = 0;  // the largest glyph_term_bound among them (box sizes differ between y-phases)
 };
 
 // One candidate of a font search as the device reads it (decode_fonts.hip, decode_whole_fonts.hip); [0] is the decode font.
@@ -408,18 +422,16 @@ struct focr_decoder {
     hipStream_t stream = nullptr;
     focr_dec::Stage run, verify, test, vtext, stext;
     std::string err;
-    // font
+    // the fonts (decode_font.h): font k of 0 ..= K is font_at(k).  n_glyphs is the alphabet's size and "a decode font is set": `font` and
+    // `tables` are that font's, and a set_font that succeeds replaces all three together
     uint32_t n_glyphs = 0;
-    float origin_x = 0.f, min_inc = 0.f;
-    std::vector<float> inc;
-    std::vector<focr_decode_glyph_t> font_glyphs;  // what set_verify_font checks and places the verify table against
-    float origin_y = 0.f, text_size = 0.f, kerning = 0.f;
-    int hinting = 0;
-    size_t bitmaps_len = 0;
+    focr_dec::HostFont font;
+    std::vector<focr_dec::HostFont> cands;  // the candidates 1 ..= K of the font search (focr_decoder_set_font_candidates)
+    const focr_dec::HostFont &font_at(size_t k) const { return k ? cands[k - 1] : font; }
     // every device array: exact growth, no stream wait (each call ends with one, so the buffers are idle when the next call grows them)
-    focr::DevArray<focr_dec::DevGlyph> d_glyphs;
-    focr::DevArray<int2> d_offs;
-    focr::DevArray<uint8_t> d_bitmaps;  // dwords (read as uint32_t by the decode kernel, as bytes by the compose kernels)
+    focr_dec::GlyphTables tables, ftables;  // the decode font's, and the candidates' k-major
+    focr_dec::VerifyTables vtables, fvtables;  // their verify tables (focr_decoder_set_verify_font, _set_verify_font_candidates)
+    focr_dec::BaseFonts yfonts;
     // the settings as the setters wrote them; a run resolves them once (resolve_modes) and reads nothing else of them
     focr_dec::Modes modes;
     // batch buffers (grown on demand)
@@ -446,25 +458,13 @@ struct focr_decoder {
     focr::DevArray<int32_t> d_mterm;
     focr::DevArray<uint16_t> d_mrunner;
     focr::DevArray<int64_t> d_margin;
-    // baseline search: the y-phase tables v >= 1 of the font (set_baseline_fonts; glyph records and offsets v-major, one
-    // bitmap table whose dword offsets the records carry), and per work-list line beside d_nchars the chosen q and its cost;
-    // grown by a run with a radius.  The baseline candidates of a whole-line run read the same tables and write the line's q
-    // to d_base_q; their cost is the whole-line run's d_cost
-    bool have_base_fonts = false;  // y-phase fonts of font_bits are uploaded for the current font
-    uint32_t font_bits = 0, ybitmaps_dw = 0;  // ... and the dwords of their bitmap table
-    uint64_t yterm_bound = 0;      // the largest stride * box_h * 2 * 255^2 of the uploaded y-phase fonts v >= 1 (a term's bound)
-    focr::DevArray<focr_dec::DevGlyph> d_yglyphs;
-    focr::DevArray<int2> d_yoffs;
-    focr::DevArray<uint8_t> d_ybitmaps;
+    // baseline search: per work-list line beside d_nchars the chosen q and its cost; grown by a run with a radius.  The
+    // baseline candidates of a whole-line run read the same y-phase tables (yfonts) and write the line's q to d_base_q; their
+    // cost is the whole-line run's d_cost
     focr::DevArray<int32_t> d_base_q;
     focr::DevArray<int64_t> d_base_cost;
-    // font search: the uploaded candidates 1 ..= K (set_font_candidates; glyph records and offsets k-major, one bitmap table
-    // whose dword offsets the records carry), a run's descriptors of the candidates 0 ..= K and, under the whole-line decode,
-    // their inc64, and per work-list line beside d_nchars the winner and (pen loop) its cost; grown by a run with the search on
-    std::vector<focr_dec::FontCandidate> cands;
-    focr::DevArray<focr_dec::DevGlyph> d_fglyphs;
-    focr::DevArray<int2> d_foffs;
-    focr::DevArray<uint8_t> d_fbitmaps;
+    // font search: a run's descriptors of the candidates 0 ..= K and, under the whole-line decode, their inc64, and per
+    // work-list line beside d_nchars the winner and (pen loop) its cost; grown by a run with the search on
     focr::DevArray<focr_dec::FontDesc> d_fdesc;
     focr::DevArray<uint32_t> d_finc64, d_line_font;
     focr::DevArray<int64_t> d_font_cost;
@@ -482,10 +482,7 @@ struct focr_decoder {
     std::vector<int64_t> base_cost;
     std::vector<uint8_t> line_font;  // beside lines (a font search)
     std::vector<int64_t> font_cost;
-    // verify: the table, buffers
-    uint32_t n_vglyphs = 0, hmax = 0;
-    focr::DevArray<focr_dec::VerifyGlyph> d_vglyphs;
-    focr::DevArray<focr_dec::VerifyPhase> d_vphases;
+    // verify: buffers
     focr::DevArray<focr_dec::VerifyLine> d_vlines;
     focr::DevArray<focr_dec::VerifyRec> d_vrecs;
     focr::DevArray<unsigned long long> d_sums;
@@ -495,11 +492,7 @@ struct focr_decoder {
     focr::DevArray<uint32_t> d_tbase, d_trect, d_ttext, d_tflags;
     focr::DevArray<focr_dec::VerifyRec> d_trecs;
     focr::DevArray<focr_dec::VerifyLine> d_tline;
-    // verify_text (decode_text.hip): the candidates' verify tables, k-major beside d_fglyphs (n_fvfonts == cands.size() once
-    // uploaded, else 0), and buffers of its own, so that a call leaves the last run and its verify as they were
-    uint32_t n_fvfonts = 0;
-    focr::DevArray<focr_dec::VerifyGlyph> d_fvglyphs;
-    focr::DevArray<focr_dec::VerifyPhase> d_fvphases;
+    // verify_text (decode_text.hip): buffers of its own, so that a call leaves the last run and its verify as they were
     focr::DevArray<uint8_t> d_xpages, d_xrgb;
     focr::DevArray<focr_dec::TextLine> d_xlines;
     focr::DevArray<uint32_t> d_xfirst, d_xpens;

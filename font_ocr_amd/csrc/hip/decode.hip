@@ -385,55 +385,27 @@ extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
 extern "C" const char *focr_decoder_last_error(const focr_decoder_t *dec) { return dec ? dec->err.c_str() : g_dec_err.c_str(); }
 
 extern "C" int focr_decoder_set_font(focr_decoder_t *dec, const focr_decode_font_t *font) {
-    if (dec) {  // the last run, the verify table and the y-phase fonts (released below, once the device is selected) belong to the previous font
+    if (dec) {  // the last run, the verify table, the y-phase fonts and the candidates belong to the previous font, whatever becomes of this one
+        DEC_CHECK(hipSetDevice(dec->device));
         const bool scores = dec->last.mode.scores;  // ... but focr_decoder_get_scores has always gone on answering after a set_font: kept as it was
         dec->last = LastRun{};
         dec->last.mode.scores = scores;
-        dec->n_vglyphs = 0;
-        dec->have_base_fonts = false;
-        dec->cands.clear();  // the candidates of a font search share the previous font's alphabet (their tables are released below)
+        dec->vtables.ok = false;
+        drop_baseline_fonts(dec);
+        drop_font_candidates(dec);  // they share the previous font's alphabet
     }
     if (!dec || !font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_font: bad arguments");
-    if (font->n_glyphs > 65535) return dfail(dec, "focr_decoder_set_font: more than 65535 glyphs");
-    if (font->bitmaps_len % 4 || font->bitmaps_len / 4 > 0xffffffffull) return dfail(dec, "focr_decoder_set_font: bad bitmap table");
-    DEC_CHECK(hipSetDevice(dec->device));
-    const size_t G = font->n_glyphs;
-    std::vector<DevGlyph> gl(G);
-    std::vector<int2> offs(G * FOCR_DECODE_PHASES);
-    dec->inc.assign(G, 0.f);
-    float min_inc = font->glyphs[0].increment;
-    for (size_t i = 0; i < G; i++) {
-        const focr_decode_glyph_t &s = font->glyphs[i];
-        if (!(s.increment > 0.f)) return dfail(dec, "focr_decoder_set_font: a glyph does not advance the pen");
-        if (s.stride % 4 || s.stride < s.box_w || s.offset % 4 ||
-            s.offset + (uint64_t)FOCR_DECODE_PHASES * s.stride * s.box_h > font->bitmaps_len ||
-            (uint64_t)s.stride * s.box_h * 2 * 255 * 255 >= (1ull << 31))
-            return dfail(dec, "focr_decoder_set_font: inconsistent glyph table");
-        gl[i] = DevGlyph{(uint32_t)(s.offset / 4), s.stride / 4, s.box_h, s.increment};
-        for (int p = 0; p < FOCR_DECODE_PHASES; p++) offs[i * FOCR_DECODE_PHASES + p] = make_int2(s.off_x[p], s.off_y[p]);
-        dec->inc[i] = s.increment;
-        min_inc = std::min(min_inc, s.increment);
-    }
-    dec->n_glyphs = 0;
+    // the font in locals: a refusal leaves the previous decode font as it was, its record, its tables and n_glyphs
+    HostFont h;
+    PackedGlyphs packed;
+    GlyphTables tables;
+    const std::string no = pack_font(*font, nullptr, &h, &packed);
+    if (!no.empty()) return dfail(dec, "focr_decoder_set_font: " + no);
+    if (tables.upload(packed, font->bitmaps) != hipSuccess) return dfail(dec, "focr_decoder_set_font: hipMalloc / hipMemcpy failed");
+    dec->font = std::move(h);
+    dec->tables = std::move(tables);
+    dec->n_glyphs = (uint32_t)font->n_glyphs;
     dec->d_inc64.release();  // the previous font's; a whole-line run uploads its own
-    dec->font_bits = dec->ybitmaps_dw = 0;
-    dec->yterm_bound = 0;
-    dec->d_yglyphs.release();
-    dec->d_yoffs.release();
-    dec->d_ybitmaps.release();
-    drop_font_candidates(dec);
-    DEC_UPLOAD(dec->d_glyphs, gl.data(), G);
-    DEC_UPLOAD(dec->d_offs, offs.data(), offs.size());
-    DEC_UPLOAD(dec->d_bitmaps, (const uint8_t *)font->bitmaps, font->bitmaps_len, 4);
-    dec->n_glyphs = (uint32_t)G;
-    dec->origin_x = font->origin_x;
-    dec->min_inc = min_inc;
-    dec->font_glyphs.assign(font->glyphs, font->glyphs + G);
-    dec->origin_y = font->origin_y;
-    dec->text_size = font->text_size;
-    dec->kerning = font->kerning;
-    dec->hinting = font->hinting;
-    dec->bitmaps_len = font->bitmaps_len;
     return 0;
 }
 
@@ -463,10 +435,8 @@ void clear_results(focr_decoder *dec) {
 // What both baseline kinds need of the font, each refused in the kind's own words: the y-phase fonts of its y_bits, and an
 // origin_y that is a whole number.
 int baseline_font(focr_decoder *dec, uint32_t bits, const std::string &no_fonts, const std::string &bent_origin) {
-    if (bits && !(dec->have_base_fonts && dec->font_bits == bits)) return dfail(dec, no_fonts);
-    const float oy = dec->origin_y;
-    if (!(oy >= 0.f) || oy > 65536.f || oy != (float)(int)oy) return dfail(dec, bent_origin);
-    return 0;
+    if (bits && !(dec->yfonts.ok && dec->yfonts.bits == bits)) return dfail(dec, no_fonts);
+    return whole_origin(dec->font.origin_y) ? 0 : dfail(dec, bent_origin);
 }
 
 // The settings as one RunMode, or the refusal of their combination (include/focr_decode.h): every refusal that depends on
@@ -504,7 +474,7 @@ int resolve_modes(focr_decoder *dec, RunMode *out) {
         return dfail(dec, "focr_decoder_run: pen slack on with the whole-line decode off (focr_decoder_set_whole_slack needs focr_decoder_set_whole_line)");
     if (m.slack && m.margins)
         return dfail(dec, "focr_decoder_run: pen slack on with margins on (focr_decoder_set_whole_slack does not go with focr_decoder_set_whole_margins yet)");
-    if ((float)m.pen_search * 0.015625f > dec->min_inc * 0.5f)
+    if ((float)m.pen_search * 0.015625f > dec->font.min_inc * 0.5f)
         return dfail(dec, "focr_decoder_run: the pen search radius is more than half the smallest pen increment (the pen could crawl)");
     if (m.frac.on() && !baseline && !candidates)
         return dfail(dec, "focr_decoder_run: a fractional line grid (focr_decoder_set_line_frac) needs a baseline search (focr_decoder_set_baseline_search) or "
@@ -544,17 +514,14 @@ int line_cap(focr_decoder *dec, const RunMode &mode, const WholePlan &plan, Geom
     // and one that stalls in f32 runs into the step limit below.  (Dropped candidates only remove choices.)
     const bool search = mode.kind == Kind::pen_search;
     const float reach = search ? (float)mode.radius * 0.015625f : 0.f;  // exact
-    float p = 0.f;
+    // a font search: every candidate's loop runs with its own increments, so the cap is the largest of the fonts' own
     uint32_t steps = 0;
-    while (p < (float)g->w) {
-        p = search ? (p - reach) + dec->min_inc : p + dec->min_inc;
-        if (++steps > (1u << 20)) return dfail(dec, "focr_decoder_run: the pen advance is too small for the line width");
-    }
-    // a font search: every candidate's loop runs with its own increments, so the cap is the largest of the candidates' own
-    for (size_t k = 0; mode.kind == Kind::fonts && k < dec->cands.size(); k++) {
+    for (size_t k = 0; k <= (mode.kind == Kind::fonts ? dec->cands.size() : 0); k++) {
+        const float min_inc = dec->font_at(k).min_inc;
         uint32_t own = 0;
-        for (p = 0.f; p < (float)g->w; p += dec->cands[k].min_inc)
-            if (++own > (1u << 20)) return dfail(dec, "focr_decoder_run: font candidate " + std::to_string(k + 1) + ": the pen advance is too small for the line width");
+        for (float p = 0.f; p < (float)g->w; p = search ? (p - reach) + min_inc : p + min_inc)
+            if (++own > (1u << 20))
+                return dfail(dec, "focr_decoder_run: " + (k ? "font candidate " + std::to_string(k) + ": " : std::string()) + "the pen advance is too small for the line width");
         steps = std::max(steps, own);
     }
     g->cap = mode.whole() ? plan.cap : std::max<uint32_t>(steps, 1);
@@ -590,14 +557,14 @@ void pen_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, size_
         const auto search = lds ? (scores ? line_search_kernel<true, true> : line_search_kernel<true, false>)
                                 : (scores ? line_search_kernel<false, true> : line_search_kernel<false, false>);
         search<<<g.total, SEARCH_THREADS, SEARCH_RED_BYTES + (lds ? strip_bytes : 0), dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs,
-            dec->origin_x, mode.radius, dec->d_nchars, dec->d_chars, dec->d_pen, so);
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->tables.glyphs, dec->tables.offs, dec->tables.bitmaps.as<const uint32_t>(), dec->n_glyphs,
+            dec->font.origin_x, mode.radius, dec->d_nchars, dec->d_chars, dec->d_pen, so);
     } else {
         const auto decode = strip_bytes <= LDS_STRIP_MAX ? (scores ? line_decode_kernel<true, true> : line_decode_kernel<true, false>)
                                                          : (scores ? line_decode_kernel<false, true> : line_decode_kernel<false, false>);
-        decode<<<g.total, 64, strip_bytes <= LDS_STRIP_MAX ? strip_bytes : 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs,
-                                                                                           dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs,
-                                                                                           dec->origin_x, dec->d_nchars, dec->d_chars, so);
+        decode<<<g.total, 64, strip_bytes <= LDS_STRIP_MAX ? strip_bytes : 0, dec->stream>>>(dec->d_strips, g, dec->d_work, dec->d_count, dec->tables.glyphs,
+                                                                                           dec->tables.offs, dec->tables.bitmaps.as<const uint32_t>(), dec->n_glyphs,
+                                                                                           dec->font.origin_x, dec->d_nchars, dec->d_chars, so);
     }
 }
 

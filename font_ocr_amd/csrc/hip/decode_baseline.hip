@@ -210,8 +210,8 @@ __global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_moved_kernel(con
 }
 
 void verify_compose_moved_launch(focr_decoder *dec, const TileGrid &tg, size_t n_pages, uint8_t *d_rgb) {
-    verify_compose_moved_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->last.src, dec->last.g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y,
-                                                                            dec->d_vlines, dec->d_vrecs, (const uint8_t *)dec->d_bitmaps, d_rgb, dec->d_sums);
+    verify_compose_moved_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->last.src, dec->last.g, (uint32_t)n_pages, dec->vtables.hmax, tg.tiles_x, tg.tiles_y,
+                                                                            dec->d_vlines, dec->d_vrecs, (const uint8_t *)dec->tables.bitmaps, d_rgb, dec->d_sums);
 }
 
 int baseline_reserve(focr_decoder *dec, const Geometry &g) {
@@ -224,8 +224,9 @@ void baseline_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, 
     const bool lds = strip_bytes + BASE_RED_BYTES <= LDS_STRIP_MAX;  // the strip shares LDS with the waves' pairs
     const size_t lds_bytes = BASE_RED_BYTES + (lds ? strip_bytes : 0);
     const uint32_t grid = mode.grid ? std::min(mode.grid, g.total) : g.total;
-    const BaseFont f{dec->d_glyphs, dec->d_yglyphs, dec->d_offs, dec->d_yoffs, dec->d_bitmaps.as<const uint32_t>(), dec->d_ybitmaps.as<const uint32_t>(),
-                     (uint32_t)(dec->bitmaps_len / 4), dec->ybitmaps_dw, dec->n_glyphs, dec->origin_x, (int)dec->origin_y, mode.bits};
+    const GlyphTables &t = dec->tables, &y = dec->yfonts.tables;
+    const BaseFont f{t.glyphs, y.glyphs, t.offs, y.offs, t.bitmaps.as<const uint32_t>(), y.bitmaps.as<const uint32_t>(), t.n_dw, y.n_dw, dec->n_glyphs,
+                     dec->font.origin_x, (int)dec->font.origin_y, mode.bits};
     if (mode.frac.on())  // the kernel's form on the fractional grid: a kernel of its own beside the one it restates
         (lds ? line_baseline_frac_kernel<true> : line_baseline_frac_kernel<false>)<<<grid, BASE_THREADS, lds_bytes, dec->stream>>>(
             dec->d_strips, g, mode.frac, dec->d_work, dec->d_count, f, mode.radius, dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
@@ -234,84 +235,40 @@ void baseline_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, 
             dec->d_strips, g, dec->d_work, dec->d_count, f, mode.radius, dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
 }
 
+void drop_baseline_fonts(focr_decoder *dec) { dec->yfonts = BaseFonts{}; }
+
 }  // namespace focr_dec
 
 using namespace focr_dec;
 
-namespace {
-
-void drop_fonts(focr_decoder *dec) {
-    dec->have_base_fonts = false;
-    dec->font_bits = 0;
-    dec->ybitmaps_dw = 0;
-    dec->yterm_bound = 0;
-    dec->d_yglyphs.release();
-    dec->d_yoffs.release();
-    dec->d_ybitmaps.release();
-}
-
-}  // namespace
-
 extern "C" int focr_decoder_set_baseline_fonts(focr_decoder_t *dec, const focr_decode_font_t *fonts, uint32_t y_bits) {
-    const char *who = "focr_decoder_set_baseline_fonts: ";
-    if (!dec) return dfail(nullptr, std::string(who) + "null decoder");
+    const std::string who = "focr_decoder_set_baseline_fonts: ";
+    if (!dec) return dfail(nullptr, who + "null decoder");
     DEC_CHECK(hipSetDevice(dec->device));
     DEC_CHECK(hipStreamSynchronize(dec->stream));
-    drop_fonts(dec);
-    if (!fonts) return dfail(dec, std::string(who) + "bad arguments");
-    if (y_bits > FOCR_BASELINE_Y_BITS_MAX) return dfail(dec, std::string(who) + "y_bits is at most 3");
-    if (!dec->n_glyphs) return dfail(dec, std::string(who) + "no font (focr_decoder_set_font)");
-    const size_t G = dec->n_glyphs, V = (size_t)1 << y_bits;
-    std::vector<DevGlyph> gl((V - 1) * G);
-    std::vector<int2> offs((V - 1) * G * FOCR_DECODE_PHASES);
-    uint64_t total = 0, bound = 0;
-    for (size_t v = 0; v < V; v++) {
-        const focr_decode_font_t &f = fonts[v];
-        if (!f.glyphs || f.n_glyphs != G || f.bitmaps_len % 4 || (f.bitmaps_len && !f.bitmaps))
-            return dfail(dec, std::string(who) + "a font does not match the decode font (glyph count)");
-        if (memcmp(&f.origin_x, &dec->origin_x, 4) || memcmp(&f.origin_y, &dec->origin_y, 4) || memcmp(&f.text_size, &dec->text_size, 4) ||
-            memcmp(&f.kerning, &dec->kerning, 4) || f.hinting != dec->hinting)
-            return dfail(dec, std::string(who) + "a font does not match the decode font (origin, size, kerning or hinting)");
-        for (size_t i = 0; i < G; i++) {
-            const focr_decode_glyph_t &s = f.glyphs[i], &t = dec->font_glyphs[i];
-            if (s.codepoint != t.codepoint || memcmp(&s.increment, &t.increment, 4))
-                return dfail(dec, std::string(who) + "a font does not match the decode font (code points or increments)");
-            if (s.stride % 4 || s.stride < s.box_w || s.offset % 4 || s.offset + (uint64_t)FOCR_DECODE_PHASES * s.stride * s.box_h > f.bitmaps_len ||
-                (uint64_t)s.stride * s.box_h * 2 * 255 * 255 >= (1ull << 31))
-                return dfail(dec, std::string(who) + "inconsistent glyph table");
-            if (v == 0) {
-                if (s.box_w != t.box_w || s.box_h != t.box_h || s.stride != t.stride || s.offset != t.offset ||
-                    memcmp(s.off_x, t.off_x, sizeof s.off_x) || memcmp(s.off_y, t.off_y, sizeof s.off_y))
-                    return dfail(dec, std::string(who) + "fonts[0] is not the decode font (glyph table)");
-                continue;
-            }
-            bound = std::max<uint64_t>(bound, (uint64_t)s.stride * s.box_h * 2 * 255 * 255);
-            gl[(v - 1) * G + i] = DevGlyph{(uint32_t)((total + s.offset) / 4), s.stride / 4, s.box_h, s.increment};
-            for (int p = 0; p < FOCR_DECODE_PHASES; p++) offs[((v - 1) * G + i) * FOCR_DECODE_PHASES + p] = make_int2(s.off_x[p], s.off_y[p]);
-        }
-        if (v) total += f.bitmaps_len;
-        if (total / 4 > 0xffffffffull) return dfail(dec, std::string(who) + "bitmap tables too large");
-    }
+    drop_baseline_fonts(dec);
+    if (!fonts) return dfail(dec, who + "bad arguments");
+    if (y_bits > FOCR_BASELINE_Y_BITS_MAX) return dfail(dec, who + "y_bits is at most 3");
+    if (!dec->n_glyphs) return dfail(dec, who + "no font (focr_decoder_set_font)");
+    const size_t V = (size_t)1 << y_bits;
+    BaseFonts y;
+    PackedGlyphs packed;
+    const std::string no = pack_baseline_fonts(fonts, V, dec->font, &y.term_bound, &packed);
+    if (!no.empty()) return dfail(dec, who + no);
     {  // fonts[0]'s bitmaps against the decoder's own copy
-        if (fonts[0].bitmaps_len != dec->bitmaps_len) return dfail(dec, std::string(who) + "fonts[0] is not the decode font (bitmaps)");
-        std::vector<uint8_t> mine(dec->bitmaps_len);
-        if (!mine.empty()) DEC_CHECK(hipMemcpy(mine.data(), dec->d_bitmaps, mine.size(), hipMemcpyDeviceToHost));
-        if (!mine.empty() && memcmp(mine.data(), fonts[0].bitmaps, mine.size())) return dfail(dec, std::string(who) + "fonts[0] is not the decode font (bitmaps)");
+        if (fonts[0].bitmaps_len != dec->font.bitmaps_len) return dfail(dec, who + "fonts[0] is not the decode font (bitmaps)");
+        std::vector<uint8_t> mine(dec->font.bitmaps_len);
+        if (!mine.empty()) DEC_CHECK(hipMemcpy(mine.data(), dec->tables.bitmaps, mine.size(), hipMemcpyDeviceToHost));
+        if (!mine.empty() && memcmp(mine.data(), fonts[0].bitmaps, mine.size())) return dfail(dec, who + "fonts[0] is not the decode font (bitmaps)");
     }
     if (V > 1) {
         std::vector<uint8_t> all;
-        all.reserve(total);
+        all.reserve(packed.bytes);
         for (size_t v = 1; v < V; v++) all.insert(all.end(), fonts[v].bitmaps, fonts[v].bitmaps + fonts[v].bitmaps_len);
-        if (dec->d_yglyphs.upload(gl.data(), gl.size()) != hipSuccess || dec->d_yoffs.upload(offs.data(), offs.size()) != hipSuccess ||
-            dec->d_ybitmaps.upload(all.data(), all.size(), 4) != hipSuccess) {
-            drop_fonts(dec);
-            return dfail(dec, std::string(who) + "hipMalloc / hipMemcpy failed");
-        }
+        if (y.tables.upload(packed, all.data()) != hipSuccess) return dfail(dec, who + "hipMalloc / hipMemcpy failed");
     }
-    dec->have_base_fonts = true;
-    dec->font_bits = y_bits;
-    dec->ybitmaps_dw = (uint32_t)(total / 4);
-    dec->yterm_bound = bound;
+    y.ok = true, y.bits = y_bits;
+    dec->yfonts = std::move(y);
     return 0;
 }
 

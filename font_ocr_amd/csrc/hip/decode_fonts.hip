@@ -100,11 +100,8 @@ __global__ __launch_bounds__(FONTS_THREADS) void line_fonts_kernel(const uint8_t
 int fonts_plan(focr_decoder *dec, WholePlan *plan) {
     const uint32_t G = dec->n_glyphs;
     plan->fonts.assign(1 + dec->cands.size(), FontDesc{});
-    plan->fonts[0] = FontDesc{0, (uint32_t)(dec->bitmaps_len / 4), dec->origin_x, 0, 0, 0, 0};
-    for (size_t k = 1; k < plan->fonts.size(); k++) {
-        const FontCandidate &c = dec->cands[k - 1];
-        plan->fonts[k] = FontDesc{(uint32_t)((k - 1) * G), c.end_dw, c.origin_x, 0, 0, 0, 0};
-    }
+    for (size_t k = 0; k < plan->fonts.size(); k++)  // (glyph_base is in the candidates' tables: font 0 has its own)
+        plan->fonts[k] = FontDesc{k ? (uint32_t)((k - 1) * G) : 0, dec->font_at(k).end_dw, dec->font_at(k).origin_x, 0, 0, 0, 0};
     return 0;
 }
 
@@ -120,22 +117,19 @@ void fonts_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, con
     const bool lds = strip_bytes + FONTS_RED_BYTES <= LDS_STRIP_MAX;  // the strip shares LDS with the waves' pairs
     const size_t lds_bytes = FONTS_RED_BYTES + (lds ? strip_bytes : 0);
     const uint32_t grid = mode.grid ? std::min(mode.grid, g.total) : g.total;
-    const FontTables f{dec->d_glyphs, dec->d_fglyphs, dec->d_offs, dec->d_foffs, dec->d_bitmaps.as<const uint32_t>(), dec->d_fbitmaps.as<const uint32_t>(),
-                       dec->d_fdesc, dec->n_glyphs, (uint32_t)plan.fonts.size()};
+    const GlyphTables &t = dec->tables, &c = dec->ftables;
+    const FontTables f{t.glyphs, c.glyphs, t.offs, c.offs, t.bitmaps.as<const uint32_t>(), c.bitmaps.as<const uint32_t>(), dec->d_fdesc, dec->n_glyphs,
+                       (uint32_t)plan.fonts.size()};
     (lds ? line_fonts_kernel<true> : line_fonts_kernel<false>)<<<grid, FONTS_THREADS, lds_bytes, dec->stream>>>(
         dec->d_strips, g, dec->d_work, dec->d_count, f, dec->d_nchars, dec->d_chars, dec->d_line_font, dec->d_font_cost);
 }
 
 void drop_font_candidates(focr_decoder *dec) {
     dec->cands.clear();
-    dec->d_fglyphs.release();
-    dec->d_foffs.release();
-    dec->d_fbitmaps.release();
+    dec->ftables.release();
     dec->d_fdesc.release();
     dec->d_finc64.release();
-    dec->n_fvfonts = 0;  // their verify tables (focr_decoder_set_verify_font_candidates) go with them
-    dec->d_fvglyphs.release();
-    dec->d_fvphases.release();
+    dec->fvtables.release();  // their verify tables (focr_decoder_set_verify_font_candidates) go with them
 }
 
 }  // namespace focr_dec
@@ -151,49 +145,17 @@ extern "C" int focr_decoder_set_font_candidates(focr_decoder_t *dec, const focr_
     if (!fonts || !n) return 0;
     if (n > FOCR_FONT_CANDIDATES_MAX - 1) return dfail(dec, who + "at most 15 candidates (FOCR_FONT_CANDIDATES_MAX - 1)");
     if (!dec->n_glyphs) return dfail(dec, who + "no font (focr_decoder_set_font)");
-    const size_t G = dec->n_glyphs;
-    std::vector<DevGlyph> gl(n * G);
-    std::vector<int2> offs(n * G * FOCR_DECODE_PHASES);
-    std::vector<FontCandidate> cands(n);
-    uint64_t total = 0;
-    for (size_t k = 0; k < n; k++) {
-        const focr_decode_font_t &f = fonts[k];
-        const std::string pre = who + "candidate " + std::to_string(k + 1) + ": ";
-        if (!f.glyphs || f.n_glyphs != G) return dfail(dec, pre + "the glyph count differs from the decode font's");
-        if (f.bitmaps_len % 4 || (f.bitmaps_len && !f.bitmaps)) return dfail(dec, pre + "bad bitmap table");
-        FontCandidate &c = cands[k];
-        c.origin_x = f.origin_x;
-        c.glyphs.assign(f.glyphs, f.glyphs + G);
-        c.base = total;
-        c.origin_y = f.origin_y, c.text_size = f.text_size, c.kerning = f.kerning, c.hinting = f.hinting;
-        c.inc.resize(G);
-        c.min_inc = f.glyphs[0].increment;
-        for (size_t i = 0; i < G; i++) {
-            const focr_decode_glyph_t &s = f.glyphs[i];
-            if (s.codepoint != dec->font_glyphs[i].codepoint) return dfail(dec, pre + "a code point differs from the decode font's");
-            if (!(s.increment > 0.f)) return dfail(dec, pre + "a glyph does not advance the pen");
-            if (s.stride % 4 || s.stride < s.box_w || s.offset % 4 || s.offset + (uint64_t)FOCR_DECODE_PHASES * s.stride * s.box_h > f.bitmaps_len ||
-                (uint64_t)s.stride * s.box_h * 2 * 255 * 255 >= (1ull << 31))
-                return dfail(dec, pre + "inconsistent glyph table");
-            gl[k * G + i] = DevGlyph{(uint32_t)((total + s.offset) / 4), s.stride / 4, s.box_h, s.increment};
-            for (int p = 0; p < FOCR_DECODE_PHASES; p++) offs[(k * G + i) * FOCR_DECODE_PHASES + p] = make_int2(s.off_x[p], s.off_y[p]);
-            c.inc[i] = s.increment;
-            c.min_inc = std::min(c.min_inc, s.increment);
-            c.term_bound = std::max<uint64_t>(c.term_bound, (uint64_t)s.stride * s.box_h * 2 * 255 * 255);
-        }
-        total += f.bitmaps_len;
-        if (total / 4 > 0xffffffffull) return dfail(dec, who + "bitmap tables too large");
-        c.end_dw = (uint32_t)(total / 4);
-    }
+    std::vector<HostFont> cands;
+    PackedGlyphs packed;
+    GlyphTables tables;
+    const std::string no = pack_candidate_fonts(fonts, n, dec->font, &cands, &packed);
+    if (!no.empty()) return dfail(dec, who + no);
     std::vector<uint8_t> all;
-    all.reserve(total);
+    all.reserve(packed.bytes);
     for (size_t k = 0; k < n; k++) all.insert(all.end(), fonts[k].bitmaps, fonts[k].bitmaps + fonts[k].bitmaps_len);
-    if (dec->d_fglyphs.upload(gl.data(), gl.size()) != hipSuccess || dec->d_foffs.upload(offs.data(), offs.size()) != hipSuccess ||
-        dec->d_fbitmaps.upload(all.data(), all.size(), 4) != hipSuccess) {
-        drop_font_candidates(dec);
-        return dfail(dec, who + "hipMalloc / hipMemcpy failed");
-    }
+    if (tables.upload(packed, all.data()) != hipSuccess) return dfail(dec, who + "hipMalloc / hipMemcpy failed");
     dec->cands = std::move(cands);
+    dec->ftables = std::move(tables);
     return 0;
 }
 

@@ -18,9 +18,6 @@
 //   8. test_compose_kernel: one workgroup per tile counts, per row, the non-blank boxes with an edge on it and blends each
 //      pixel once per edge through it (the rect image), and blends the last alphabet glyph over each pixel (the text
 //      image), both from the base RGBA pixel with image's Blend for Rgba<u8> restated in f32 (blend_rgba).
-#include <cmath>
-#include <cstring>
-
 #include "decode.h"
 
 namespace focr_dec {
@@ -252,41 +249,16 @@ __global__ __launch_bounds__(VERIFY_TILE_W) void test_compose_kernel(const uint8
 using namespace focr_dec;
 
 extern "C" int focr_decoder_set_verify_font(focr_decoder_t *dec, const focr_verify_font_t *font) {
-    if (!dec) return dfail(nullptr, "focr_decoder_set_verify_font: null decoder");
-    dec->n_vglyphs = 0;
-    if (!font || !font->glyphs || !font->n_glyphs) return dfail(dec, "focr_decoder_set_verify_font: bad arguments");
-    if (!dec->n_glyphs) return dfail(dec, "focr_decoder_set_verify_font: no decode font (focr_decoder_set_font)");
-    const size_t G = font->n_glyphs;
-    if (G != dec->n_glyphs || font->text_size != dec->text_size || font->kerning != dec->kerning ||
-        (font->hinting != 0) != (dec->hinting != 0) || font->origin_y != dec->origin_y)
-        return dfail(dec, "focr_decoder_set_verify_font: the table does not match the decode font (glyph count, size, kerning, hinting or origin)");
-    if (dec->bitmaps_len > 0xffffffffull) return dfail(dec, "focr_decoder_set_verify_font: decode font bitmaps over 4 GiB");
-    std::vector<VerifyGlyph> vg(G);
-    std::vector<VerifyPhase> vp(G * FOCR_DECODE_PHASES);
-    int y_lo = 0, y_hi = 0;
-    for (size_t i = 0; i < G; i++) {
-        const focr_verify_glyph_t &v = font->glyphs[i];
-        const focr_decode_glyph_t &d = dec->font_glyphs[i];
-        if (v.codepoint != d.codepoint || memcmp(&v.increment, &d.increment, sizeof(float)) != 0)
-            return dfail(dec, "focr_decoder_set_verify_font: the table does not match the decode font (code points or increments)");
-        for (float b : v.box)
-            if (!std::isfinite(b) || std::fabs(b) > (float)(1 << 20)) return dfail(dec, "focr_decoder_set_verify_font: bad glyph box");
-        memcpy(vg[i].box, v.box, sizeof v.box);
-        y_lo = std::min(y_lo, (int)std::floor(v.box[1] + 0.f));  // the rows render() gives any line: at most hmax
-        y_hi = std::max(y_hi, (int)std::ceil(v.box[3] + 0.f));
-        for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
-            if ((uint64_t)v.rect_x[p] + v.rect_w[p] > d.box_w || (uint64_t)v.rect_y[p] + v.rect_h[p] > d.box_h)
-                return dfail(dec, "focr_decoder_set_verify_font: a phase rectangle leaves the decode font's box");
-            vp[i * FOCR_DECODE_PHASES + p] = VerifyPhase{
-                d.off_x[p] + (int32_t)v.rect_x[p], d.off_y[p] + (int32_t)v.rect_y[p] - (int32_t)font->origin_y, v.rect_w[p], v.rect_h[p],
-                (uint32_t)(d.offset + (uint64_t)p * d.stride * d.box_h + (uint64_t)v.rect_y[p] * d.stride + v.rect_x[p]), d.stride};
-        }
-    }
+    const std::string who = "focr_decoder_set_verify_font: ";
+    if (!dec) return dfail(nullptr, who + "null decoder");
+    dec->vtables.ok = false;
+    if (!font || !font->glyphs || !font->n_glyphs) return dfail(dec, who + "bad arguments");
+    if (!dec->n_glyphs) return dfail(dec, who + "no decode font (focr_decoder_set_font)");
+    PackedVerify packed;
+    const std::string no = pack_verify_font(*font, dec->font, false, &packed);
+    if (!no.empty()) return dfail(dec, who + no);
     DEC_CHECK(hipSetDevice(dec->device));
-    DEC_UPLOAD(dec->d_vglyphs, vg.data(), G);
-    DEC_UPLOAD(dec->d_vphases, vp.data(), vp.size());
-    dec->hmax = (uint32_t)(y_hi - y_lo);
-    dec->n_vglyphs = (uint32_t)G;
+    if (dec->vtables.upload(packed) != hipSuccess) return dfail(dec, who + "hipMalloc / hipMemcpy failed");
     return 0;
 }
 
@@ -297,7 +269,7 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     if (!dec->last.ok) return dfail(dec, "focr_decoder_verify: no successful focr_decoder_run since the font was set");
     if (dec->last.mode.fonts())
         return dfail(dec, "focr_decoder_verify: the last run searched fonts (focr_decoder_set_font_search): drawing every line in its own font is a later step");
-    if (!dec->n_vglyphs) return dfail(dec, "focr_decoder_verify: no verify table (focr_decoder_set_verify_font)");
+    if (!dec->vtables.ok) return dfail(dec, "focr_decoder_verify: no verify table (focr_decoder_set_verify_font)");
     if (!sq_sums) return dfail(dec, "focr_decoder_verify: null sq_sums");
     const LastRun &run = dec->last;
     const RunMode &mode = run.mode;
@@ -322,20 +294,20 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     if (mode.frac.on())  // (only a baseline kind runs on the fractional grid)
         verify_layout_frac_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, mode.frac, (uint32_t)n_pages, run.x_start, dec->d_flags, dec->d_work,
                                                                                   dec->d_count, dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, mode.bits,
-                                                                                  dec->d_glyphs, dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs,
+                                                                                  dec->tables.glyphs, dec->vtables.glyphs, dec->vtables.phases, dec->d_vlines, dec->d_vrecs,
                                                                                   dec->d_sums);
     else
         verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, run.x_start, dec->d_flags, dec->d_work, dec->d_count,
-                                                                             dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, mode.bits, dec->d_glyphs,
-                                                                             dec->d_vglyphs, dec->d_vphases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
+                                                                             dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, mode.bits, dec->tables.glyphs,
+                                                                             dec->vtables.glyphs, dec->vtables.phases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
     DEC_CHECK(hipGetLastError());
     if (mode.frac.on())  // ... and on the fractional grid the slots that reach a tile come from that grid's inverse
         verify_compose_frac_launch(dec, tg, n_pages, d_rgb);
     else if (mode.base_q())  // the canvases of a baseline run are moved off their slots: decode_baseline.hip's compose finds them
         verify_compose_moved_launch(dec, tg, n_pages, d_rgb);
     else
-        verify_compose_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(run.src, g, (uint32_t)n_pages, dec->hmax, tg.tiles_x, tg.tiles_y, dec->d_vlines, dec->d_vrecs,
-                                                                          (const uint8_t *)dec->d_bitmaps, d_rgb, dec->d_sums);
+        verify_compose_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(run.src, g, (uint32_t)n_pages, dec->vtables.hmax, tg.tiles_x, tg.tiles_y, dec->d_vlines, dec->d_vrecs,
+                                                                          (const uint8_t *)dec->tables.bitmaps, d_rgb, dec->d_sums);
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->verify.end, dec->stream));
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit sums");
@@ -356,7 +328,7 @@ extern "C" int focr_decoder_test_images(focr_decoder_t *dec, const uint8_t *page
     dec->test.launches = 0;
     if (n_pages && !pages) return dfail(dec, "focr_decoder_test_images: null pages");
     if (text_rgba && !dec->n_glyphs) return dfail(dec, "focr_decoder_test_images: the text image needs a decode font (focr_decoder_set_font)");
-    if (text_rgba && !dec->n_vglyphs)
+    if (text_rgba && !dec->vtables.ok)
         return dfail(dec, "focr_decoder_test_images: the text image needs a verify table (focr_decoder_set_verify_font)");
     Geometry g{};
     if (batch_geometry(dec, "focr_decoder_test_images", n_pages, page_w, page_h, x_start, y_start, width, line_height, line_advance, &g)) return 1;
@@ -386,12 +358,12 @@ extern "C" int focr_decoder_test_images(focr_decoder_t *dec, const uint8_t *page
         launches++;
     }
     if (text_rgba) {
-        test_layout_kernel<<<1, 64, 0, dec->stream>>>(g, dec->n_glyphs, dec->d_glyphs, dec->d_vglyphs, dec->d_vphases, dec->d_trecs, dec->d_tline);
+        test_layout_kernel<<<1, 64, 0, dec->stream>>>(g, dec->n_glyphs, dec->tables.glyphs, dec->vtables.glyphs, dec->vtables.phases, dec->d_trecs, dec->d_tline);
         DEC_CHECK(hipGetLastError());
         launches++;
     }
     test_compose_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(d_src, d_base, g, (uint32_t)n_pages, x_start, width, tg.tiles_x, tg.tiles_y, dec->d_tflags, dec->d_tline, dec->d_trecs,
-                                                                    (const uint8_t *)dec->d_bitmaps, d_rect, d_text);
+                                                                    (const uint8_t *)dec->tables.bitmaps, d_rect, d_text);
     DEC_CHECK(hipGetLastError());
     launches++;
     DEC_CHECK(hipEventRecord(dec->test.end, dec->stream));

@@ -101,5 +101,7 @@ void fonts_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, con
 void whole_fonts_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, const WholePlan &plan, size_t strip_bytes);
 // The uploaded candidates and their device tables, gone (focr_decoder_set_font).
 void drop_font_candidates(focr_decoder *dec);
+// ... and the y-phase fonts (decode_baseline.hip).
+void drop_baseline_fonts(focr_decoder *dec);
 
 }  // namespace focr_dec

@@ -70,8 +70,8 @@ __global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_moved_frac_kerne
 }
 
 void verify_compose_frac_launch(focr_decoder *dec, const TileGrid &tg, size_t n_pages, uint8_t *d_rgb) {
-    verify_compose_moved_frac_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->last.src, dec->last.g, dec->last.mode.frac, (uint32_t)n_pages, dec->hmax, tg.tiles_x,
-                                                                                 tg.tiles_y, dec->d_vlines, dec->d_vrecs, (const uint8_t *)dec->d_bitmaps, d_rgb,
+    verify_compose_moved_frac_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(dec->last.src, dec->last.g, dec->last.mode.frac, (uint32_t)n_pages, dec->vtables.hmax, tg.tiles_x,
+                                                                                 tg.tiles_y, dec->d_vlines, dec->d_vrecs, (const uint8_t *)dec->tables.bitmaps, d_rgb,
                                                                                  dec->d_sums);
 }
 

@@ -17,9 +17,6 @@
 //     candidate (N = 0) that pass is the only one.
 // Fonts are read as the font search reads them (a FontDesc per font 0 ..= K), y-phases as the baseline search does (the
 // tables of focr_decoder_set_baseline_fonts, v-major).  Everything is exact integer arithmetic but the f32 pen.
-#include <cmath>
-#include <cstring>
-
 #include "decode_pen.h"
 
 namespace focr_dec {
@@ -213,12 +210,6 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_text_kernel(const uint8_t
 
 using namespace focr_dec;
 
-namespace {
-
-bool whole_origin(float o) { return o >= 0.f && o <= 65536.f && o == floorf(o); }
-
-}  // namespace
-
 extern "C" int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages, int pages_on_device, size_t n_pages, size_t page_w, size_t page_h,
                                        uint32_t x_start, uint32_t width, uint32_t line_height, const focr_text_line_t *lines, size_t n_lines,
                                        const uint16_t *chars, const uint32_t *pens, const int8_t *offsets, size_t n_chars, const int8_t *line_q,
@@ -240,11 +231,9 @@ extern "C" int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages
     Geometry g{};
     if (batch_geometry(dec, "focr_decoder_score_text", n_pages, page_w, page_h, x_start, 0, width, 0, 1, &g)) return 1;
     if (n_lines > 0x7fffffffu || n_pages > 0x7fffffffu) return dfail(dec, who + "too many lines or pages in one call");
-    if (line_q && y_bits && !(dec->have_base_fonts && dec->font_bits == y_bits))
+    if (line_q && y_bits && !(dec->yfonts.ok && dec->yfonts.bits == y_bits))
         return dfail(dec, who + "line_q with y_bits > 0 needs the y-phase fonts of that y_bits (focr_decoder_set_baseline_fonts)");
     const size_t K = dec->cands.size();
-    const auto font_origin_x = [&](uint32_t k) { return k ? dec->cands[k - 1].origin_x : dec->origin_x; };
-    const auto font_origin_y = [&](uint32_t k) { return k ? dec->cands[k - 1].origin_y : dec->origin_y; };
     std::vector<ScoreLine> in(n_lines);
     uint64_t n_terms = 0;
     for (size_t l = 0; l < n_lines; l++) {
@@ -253,12 +242,12 @@ extern "C" int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages
         if (s.font > K) return dfail(dec, pre + "font " + std::to_string(s.font) + " with " + std::to_string(K) + " candidates uploaded (focr_decoder_set_font_candidates)");
         if (s.page >= n_pages) return dfail(dec, pre + "page " + std::to_string(s.page) + " of " + std::to_string(n_pages));
         if (s.first > n_chars || s.n_chars > n_chars - s.first) return dfail(dec, pre + "its characters end past n_chars");
-        if (pens && !whole_origin(font_origin_x(s.font)))
+        if (pens && !whole_origin(dec->font_at(s.font).origin_x))
             return dfail(dec, pre + "pens need its font's origin_x to be a whole number >= 0 (at most 65536)");
         const int q = line_q ? line_q[l] : 0;
         if (line_q && s.font && (q & ((1 << y_bits) - 1)))
             return dfail(dec, pre + "a fractional-phase q in a candidate font (the candidates have one vertical phase)");
-        if (line_q && !whole_origin(font_origin_y(s.font))) return dfail(dec, pre + "line_q needs its font's origin_y to be a whole number >= 0");
+        if (line_q && !whole_origin(dec->font_at(s.font).origin_y)) return dfail(dec, pre + "line_q needs its font's origin_y to be a whole number >= 0");
         in[l] = ScoreLine{s.page, s.y, s.n_chars, s.font, s.first, n_terms, q, 0};
         n_terms += s.n_chars;
     }
@@ -291,9 +280,9 @@ extern "C" int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages
     if (pens && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_spens, pens, n_chars * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
     if (offsets && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_soffs, offsets, n_chars, hipMemcpyHostToDevice, dec->stream));
     DEC_CHECK(hipMemcpyAsync(dec->d_sdesc, plan.fonts.data(), plan.fonts.size() * sizeof(FontDesc), hipMemcpyHostToDevice, dec->stream));
-    const ScoreFonts f{dec->d_glyphs, dec->d_fglyphs, dec->d_yglyphs, dec->d_offs, dec->d_foffs, dec->d_yoffs, dec->d_bitmaps.as<const uint32_t>(),
-                       dec->d_fbitmaps.as<const uint32_t>(), dec->d_ybitmaps.as<const uint32_t>(), dec->d_sdesc, dec->n_glyphs, dec->ybitmaps_dw,
-                       line_q ? y_bits : 0};
+    const GlyphTables &t = dec->tables, &c = dec->ftables, &y = dec->yfonts.tables;
+    const ScoreFonts f{t.glyphs, c.glyphs, y.glyphs, t.offs, c.offs, y.offs, t.bitmaps.as<const uint32_t>(), c.bitmaps.as<const uint32_t>(),
+                       y.bitmaps.as<const uint32_t>(), dec->d_sdesc, dec->n_glyphs, y.n_dw, line_q ? y_bits : 0};
     const uint32_t *d_pens = pens ? (const uint32_t *)dec->d_spens : nullptr;
     const int8_t *d_offs = offsets ? (const int8_t *)dec->d_soffs : nullptr;
     int32_t *d_terms = terms ? (int32_t *)dec->d_sterms : nullptr;

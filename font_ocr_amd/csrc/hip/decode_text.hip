@@ -5,7 +5,7 @@
 //
 // Two launches, over the tile frame of decode.h and in buffers of the call's own:
 //   1. verify_layout_text_kernel: one wave per listed line runs layout_line (decode.h) with the line's own y and the glyph,
-//      box and phase tables of the line's font (the candidates' lie k-major behind a per-font base, as d_fglyphs does), and
+//      box and phase tables of the line's font (the candidates' lie k-major behind a per-font base, as their glyph records do), and
 //      writes the line's glyph records and its clipped canvas, which carries the font; blocks below n_pages also zero the sums;
 //   2. verify_compose_text_kernel: one workgroup per (page, 16 rows, 256 columns) tile walks that page's lines
 //      [page_first[p], page_first[p + 1]) in list order.  The lines lie on no grid (any y, in any order, repeated,
@@ -14,9 +14,6 @@
 //      reaches the tile is marked and read as verify_compose_kernel does it (mark_glyphs, glyph_value), from the bitmap table
 //      of its font, chosen once per line; the sums are tile_add_sum's.
 // Here as well: the upload of the candidates' verify tables (focr_decoder_set_verify_font_candidates).
-#include <cmath>
-#include <cstring>
-
 #include "decode.h"
 
 namespace focr_dec {
@@ -119,47 +116,15 @@ extern "C" int focr_decoder_set_verify_font_candidates(focr_decoder_t *dec, cons
     const std::string who = "focr_decoder_set_verify_font_candidates: ";
     if (!dec) return dfail(nullptr, who + "null decoder");
     DEC_CHECK(hipSetDevice(dec->device));
-    dec->n_fvfonts = 0;
-    dec->d_fvglyphs.release();  // (every call that reads them ends with a stream wait)
-    dec->d_fvphases.release();
+    dec->fvtables.release();  // (every call that reads them ends with a stream wait)
     if (!fonts || !n) return dfail(dec, who + "bad arguments");
     if (!dec->n_glyphs) return dfail(dec, who + "no decode font (focr_decoder_set_font)");
     if (dec->cands.empty()) return dfail(dec, who + "no font candidates (focr_decoder_set_font_candidates)");
     if (n != dec->cands.size()) return dfail(dec, who + "one table per uploaded candidate: " + std::to_string(dec->cands.size()) + " of them");
-    const size_t G = dec->n_glyphs, K = n;
-    std::vector<VerifyGlyph> vg(K * G);
-    std::vector<VerifyPhase> vp(K * G * FOCR_DECODE_PHASES);
-    for (size_t k = 0; k < K; k++) {
-        const focr_verify_font_t &font = fonts[k];
-        const FontCandidate &c = dec->cands[k];
-        const std::string pre = who + "candidate " + std::to_string(k + 1) + ": ";
-        if (!font.glyphs || font.n_glyphs != G || font.text_size != c.text_size || font.kerning != c.kerning || (font.hinting != 0) != (c.hinting != 0) ||
-            font.origin_y != c.origin_y)
-            return dfail(dec, pre + "the table does not match the candidate (glyph count, size, kerning, hinting or origin)");
-        if ((uint64_t)c.end_dw * 4 > 0xffffffffull) return dfail(dec, pre + "the candidates' bitmaps pass 4 GiB");
-        for (size_t i = 0; i < G; i++) {
-            const focr_verify_glyph_t &v = font.glyphs[i];
-            const focr_decode_glyph_t &d = c.glyphs[i];
-            if (v.codepoint != d.codepoint || memcmp(&v.increment, &d.increment, sizeof(float)) != 0)
-                return dfail(dec, pre + "the table does not match the candidate (code points or increments)");
-            for (float b : v.box)
-                if (!std::isfinite(b) || std::fabs(b) > (float)(1 << 20)) return dfail(dec, pre + "bad glyph box");
-            memcpy(vg[k * G + i].box, v.box, sizeof v.box);
-            for (int p = 0; p < FOCR_DECODE_PHASES; p++) {
-                if ((uint64_t)v.rect_x[p] + v.rect_w[p] > d.box_w || (uint64_t)v.rect_y[p] + v.rect_h[p] > d.box_h)
-                    return dfail(dec, pre + "a phase rectangle leaves the candidate's box");
-                vp[(k * G + i) * FOCR_DECODE_PHASES + p] = VerifyPhase{
-                    d.off_x[p] + (int32_t)v.rect_x[p], d.off_y[p] + (int32_t)v.rect_y[p] - (int32_t)font.origin_y, v.rect_w[p], v.rect_h[p],
-                    (uint32_t)(c.base + d.offset + (uint64_t)p * d.stride * d.box_h + (uint64_t)v.rect_y[p] * d.stride + v.rect_x[p]), d.stride};
-            }
-        }
-    }
-    if (dec->d_fvglyphs.upload(vg.data(), vg.size()) != hipSuccess || dec->d_fvphases.upload(vp.data(), vp.size()) != hipSuccess) {
-        dec->d_fvglyphs.release();
-        dec->d_fvphases.release();
-        return dfail(dec, who + "hipMalloc / hipMemcpy failed");
-    }
-    dec->n_fvfonts = (uint32_t)K;
+    PackedVerify packed;
+    const std::string no = pack_verify_fonts(fonts, dec->cands, &packed);
+    if (!no.empty()) return dfail(dec, who + no);
+    if (dec->fvtables.upload(packed) != hipSuccess) return dfail(dec, who + "hipMalloc / hipMemcpy failed");
     return 0;
 }
 
@@ -198,8 +163,8 @@ extern "C" int focr_decoder_verify_text(focr_decoder_t *dec, const uint8_t *page
     }
     for (size_t p = 1; p <= n_pages; p++) page_first[p] = std::max(page_first[p], page_first[p - 1]);  // a page without lines: an empty range
     if (n_recs > 0xffffffffull) return dfail(dec, who + "too many characters in one call");
-    if (decode_font && !dec->n_vglyphs) return dfail(dec, who + "a line in font 0 and no verify table of the decode font (focr_decoder_set_verify_font)");
-    if (candidates && dec->n_fvfonts != K)
+    if (decode_font && !dec->vtables.ok) return dfail(dec, who + "a line in font 0 and no verify table of the decode font (focr_decoder_set_verify_font)");
+    if (candidates && !dec->fvtables.ok)
         return dfail(dec, who + "a line in a candidate font and no verify tables of the candidates (focr_decoder_set_verify_font_candidates)");
     for (size_t i = 0; i < n_chars; i++)
         if (chars[i] >= dec->n_glyphs) return dfail(dec, who + "character " + std::to_string(i) + " is not an index into the alphabet");
@@ -227,7 +192,7 @@ extern "C" int focr_decoder_verify_text(focr_decoder_t *dec, const uint8_t *page
     if (n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_xchars, chars, n_chars * sizeof(uint16_t), hipMemcpyHostToDevice, dec->stream));
     if (pens && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_xpens, pens, n_chars * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
     if (offsets && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_xoffs, offsets, n_chars, hipMemcpyHostToDevice, dec->stream));
-    const TextFonts f{dec->d_glyphs, dec->d_fglyphs, dec->d_vglyphs, dec->d_fvglyphs, dec->d_vphases, dec->d_fvphases, dec->n_glyphs};
+    const TextFonts f{dec->tables.glyphs, dec->ftables.glyphs, dec->vtables.glyphs, dec->fvtables.glyphs, dec->vtables.phases, dec->fvtables.phases, dec->n_glyphs};
     DEC_CHECK(hipEventRecord(dec->vtext.begin, dec->stream));
     verify_layout_text_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, (uint32_t)n_lines, x_start, dec->d_xlines, dec->d_xchars,
                                                                               offsets ? (const int8_t *)dec->d_xoffs : nullptr,
@@ -235,8 +200,8 @@ extern "C" int focr_decoder_verify_text(focr_decoder_t *dec, const uint8_t *page
                                                                               dec->d_xrecs, dec->d_xsums);
     DEC_CHECK(hipGetLastError());
     verify_compose_text_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(d_src, g.page_w, g.page_h, (uint32_t)n_pages, tg.tiles_x, tg.tiles_y, dec->d_xfirst,
-                                                                           dec->d_xlines, dec->d_xvlines, dec->d_xrecs, (const uint8_t *)dec->d_bitmaps,
-                                                                           (const uint8_t *)dec->d_fbitmaps, d_rgb, dec->d_xsums);
+                                                                           dec->d_xlines, dec->d_xvlines, dec->d_xrecs, (const uint8_t *)dec->tables.bitmaps,
+                                                                           (const uint8_t *)dec->ftables.bitmaps, d_rgb, dec->d_xsums);
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->vtext.end, dec->stream));
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit sums");

@@ -40,12 +40,9 @@ struct WholeFontPlan {
     uint32_t batch = 0, ring = 0, max_inc = 0, cap = 1;
 };
 
-// set_font's own bound on a term's magnitude over a glyph table: the largest stride * box_h * 2 * 255^2.
-uint64_t whole_term_bound(const focr_decode_glyph_t *glyphs, uint32_t n);
 // The font refusals of a whole-line run (include/focr_decode.h) for one font, each message behind `pre`, and its plan.
 // T: the bound on a term's magnitude; slack: the pen slack's radius (0 without).
-int whole_font_plan(focr_decoder *dec, const std::string &pre, float ox, const float *inc, uint64_t T, uint32_t n_glyphs, uint32_t slack, uint32_t w,
-                    WholeFontPlan *fp);
+int whole_font_plan(focr_decoder *dec, const std::string &pre, const HostFont &f, uint64_t T, uint32_t slack, uint32_t w, WholeFontPlan *fp);
 // The scratch of one workgroup (from plan->max_inc and plan->cap) and the grid the mode's budget allows.
 void whole_plan_grid(const RunMode &mode, const Geometry &g, bool margins, const WholeScratch &sc, WholePlan *plan);
 // whole_plan, whole_reserve's part and the launch of a whole_fonts run (decode_whole_fonts.hip).

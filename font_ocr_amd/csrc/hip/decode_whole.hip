@@ -230,21 +230,13 @@ __global__ __launch_bounds__(WHOLE_THREADS) void line_whole_slack_kernel(const u
 
 // ---- the host's side: plan, buffers, launch (decode_line.h) ----------------------------------------------------------
 
-uint64_t whole_term_bound(const focr_decode_glyph_t *glyphs, uint32_t n) {
-    uint64_t T = 0;
-    for (uint32_t i = 0; i < n; i++) T = std::max<uint64_t>(T, (uint64_t)glyphs[i].stride * glyphs[i].box_h * 2 * 255 * 255);
-    return T;
-}
-
-int whole_font_plan(focr_decoder *dec, const std::string &pre, float ox, const float *inc, uint64_t T, uint32_t n_glyphs, uint32_t slack, uint32_t w,
-                    WholeFontPlan *fp) {
-    if (!(ox >= 0.f && ox <= 65536.f && ox == floorf(ox)))
-        return dfail(dec, pre + "whole-line decode needs origin_x to be a whole number >= 0 (at most 65536)");
+int whole_font_plan(focr_decoder *dec, const std::string &pre, const HostFont &f, uint64_t T, uint32_t slack, uint32_t w, WholeFontPlan *fp) {
+    if (!whole_origin(f.origin_x)) return dfail(dec, pre + "whole-line decode needs origin_x to be a whole number >= 0 (at most 65536)");
     uint32_t lo = ~0u, hi = 0;
     std::vector<uint32_t> &inc64 = fp->inc64;
-    inc64.resize(n_glyphs);
-    for (uint32_t i = 0; i < n_glyphs; i++) {
-        const float v = rintf(inc[i] * 64.0f);
+    inc64.resize(f.inc.size());
+    for (size_t i = 0; i < f.inc.size(); i++) {
+        const float v = rintf(f.inc[i] * 64.0f);
         if (!(v >= 1.f)) return dfail(dec, pre + "whole-line decode needs every pen increment to be at least 1/64 px (an inc64 below 1)");
         inc64[i] = v < 16777216.f ? (uint32_t)v : (1u << 24);
         lo = std::min(lo, inc64[i]), hi = std::max(hi, inc64[i]);
@@ -257,7 +249,7 @@ int whole_font_plan(focr_decoder *dec, const std::string &pre, float ox, const f
     fp->cap = std::max<uint32_t>((64u * w + gain - 1) / gain, 1);
     if ((uint64_t)fp->cap * T >= (1ull << 47))
         return dfail(dec, pre + "whole-line decode: characters per line times the font's score bound reaches 2^47 (a packed cost could overflow)");
-    fp->origin_d = 64 * (int)ox;
+    fp->origin_d = 64 * (int)f.origin_x;
     fp->batch = std::min(gain, WHOLE_BATCH_MAX);
     fp->max_inc = hi;
     uint32_t ring = 64;
@@ -280,10 +272,10 @@ int whole_plan(focr_decoder *dec, const RunMode &mode, const Geometry &g, WholeP
     if (mode.kind == Kind::whole_fonts) return whole_fonts_plan(dec, mode, g, plan);
     const uint32_t slack = mode.kind == Kind::whole_slack ? mode.radius : 0;
     const bool margins = mode.margins(), candidates = mode.kind == Kind::whole_baseline;
-    uint64_t T = whole_term_bound(dec->font_glyphs.data(), dec->n_glyphs);  // set_font's own bound on a term's magnitude
-    if (candidates && dec->have_base_fonts) T = std::max(T, dec->yterm_bound);  // box sizes differ between y-phases
+    uint64_t T = dec->font.term_bound;  // set_font's own bound on a term's magnitude
+    if (candidates && dec->yfonts.ok) T = std::max(T, dec->yfonts.term_bound);  // box sizes differ between y-phases
     WholeFontPlan fp;
-    if (whole_font_plan(dec, "focr_decoder_run: ", dec->origin_x, dec->inc.data(), T, dec->n_glyphs, slack, g.w, &fp)) return 1;
+    if (whole_font_plan(dec, "focr_decoder_run: ", dec->font, T, slack, g.w, &fp)) return 1;
     plan->inc64 = std::move(fp.inc64);
     plan->cap = fp.cap, plan->origin_d = fp.origin_d, plan->batch = fp.batch, plan->max_inc = fp.max_inc, plan->ring = fp.ring;
     // a workgroup's scratch: a word per state 0 .. 64 * w + max inc64, with margins then the characters' keys and midpoints;
@@ -323,15 +315,15 @@ void whole_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, con
         const auto kernel = lds ? (chars_lds ? line_whole_margins_kernel<true, true> : line_whole_margins_kernel<true, false>)
                                 : (chars_lds ? line_whole_margins_kernel<false, true> : line_whole_margins_kernel<false, false>);
         kernel<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->tables.glyphs, dec->tables.offs, dec->tables.bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
             dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, MarginOut{dec->d_fwd, dec->d_mterm, dec->d_mrunner, dec->d_margin});
     } else if (slack) {
         (lds ? line_whole_slack_kernel<true> : line_whole_slack_kernel<false>)<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->tables.glyphs, dec->tables.offs, dec->tables.bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
             dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, SlackOut{mode.radius, dec->d_woff, dec->d_pen});
     } else {
         (lds ? line_whole_kernel<true> : line_whole_kernel<false>)<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->tables.glyphs, dec->tables.offs, dec->tables.bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
             dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost);
     }
 }

@@ -173,14 +173,14 @@ void whole_baseline_launch(focr_decoder *dec, const RunMode &mode, const Geometr
     const size_t fixed = whole_fixed_bytes(false, plan.ring, 0);
     const bool lds = strip_bytes + fixed <= LDS_STRIP_MAX;
     const size_t lds_bytes = fixed + (lds ? strip_bytes : 0);
-    const WholeBase wb{dec->d_yglyphs, dec->d_yoffs, dec->d_ybitmaps.as<const uint32_t>(), (int)dec->origin_y, mode.bits, mode.radius, dec->d_base_q};
+    const WholeBase wb{dec->yfonts.tables.glyphs, dec->yfonts.tables.offs, dec->yfonts.tables.bitmaps.as<const uint32_t>(), (int)dec->font.origin_y, mode.bits, mode.radius, dec->d_base_q};
     if (mode.frac.on())  // the kernel's form on the fractional grid: a kernel of its own beside the one it restates
         (lds ? line_whole_baseline_frac_kernel<true> : line_whole_baseline_frac_kernel<false>)<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
-            dec->d_strips, g, mode.frac, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64,
+            dec->d_strips, g, mode.frac, dec->d_work, dec->d_count, dec->tables.glyphs, dec->tables.offs, dec->tables.bitmaps.as<const uint32_t>(), dec->d_inc64,
             dec->n_glyphs, wp, dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, wb);
     else
         (lds ? line_whole_baseline_kernel<true> : line_whole_baseline_kernel<false>)<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
+            dec->d_strips, g, dec->d_work, dec->d_count, dec->tables.glyphs, dec->tables.offs, dec->tables.bitmaps.as<const uint32_t>(), dec->d_inc64, dec->n_glyphs, wp,
             dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, wb);
 }
 

@@ -109,9 +109,7 @@ int whole_fonts_plan(focr_decoder *dec, const RunMode &mode, const Geometry &g, 
     for (size_t k = 0; k < plan->fonts.size(); k++) {
         WholeFontPlan fp;
         const std::string pre = k ? "focr_decoder_run: font candidate " + std::to_string(k) + ": " : std::string("focr_decoder_run: ");
-        if (k == 0 ? whole_font_plan(dec, pre, dec->origin_x, dec->inc.data(), whole_term_bound(dec->font_glyphs.data(), G), G, 0, g.w, &fp)
-                   : whole_font_plan(dec, pre, dec->cands[k - 1].origin_x, dec->cands[k - 1].inc.data(), dec->cands[k - 1].term_bound, G, 0, g.w, &fp))
-            return 1;
+        if (whole_font_plan(dec, pre, dec->font_at(k), dec->font_at(k).term_bound, 0, g.w, &fp)) return 1;
         FontDesc &d = plan->fonts[k];
         d.origin_d = fp.origin_d, d.batch = fp.batch, d.max_inc = fp.max_inc, d.inc_base = (uint32_t)(k * G);
         plan->fonts_inc64.insert(plan->fonts_inc64.end(), fp.inc64.begin(), fp.inc64.end());
@@ -133,9 +131,9 @@ void whole_fonts_launch(focr_decoder *dec, const RunMode &mode, const Geometry &
     const size_t fixed = whole_fixed_bytes(false, plan.ring, 0);
     const bool lds = strip_bytes + fixed <= LDS_STRIP_MAX;
     const size_t lds_bytes = fixed + (lds ? strip_bytes : 0);
-    const WholeFonts wf{dec->d_fglyphs, dec->d_foffs, dec->d_fbitmaps.as<const uint32_t>(), dec->d_fdesc, dec->d_finc64, (uint32_t)plan.fonts.size(), dec->d_line_font};
+    const WholeFonts wf{dec->ftables.glyphs, dec->ftables.offs, dec->ftables.bitmaps.as<const uint32_t>(), dec->d_fdesc, dec->d_finc64, (uint32_t)plan.fonts.size(), dec->d_line_font};
     (lds ? line_whole_fonts_kernel<true> : line_whole_fonts_kernel<false>)<<<plan.grid, WHOLE_THREADS, lds_bytes, dec->stream>>>(
-        dec->d_strips, g, dec->d_work, dec->d_count, dec->d_glyphs, dec->d_offs, dec->d_bitmaps.as<const uint32_t>(), dec->n_glyphs, plan.ring - 1,
+        dec->d_strips, g, dec->d_work, dec->d_count, dec->tables.glyphs, dec->tables.offs, dec->tables.bitmaps.as<const uint32_t>(), dec->n_glyphs, plan.ring - 1,
         plan.n_states, dec->d_back, dec->d_nchars, dec->d_chars, dec->d_pens, dec->d_cost, wf);
 }
 
