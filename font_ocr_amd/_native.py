@@ -131,6 +131,7 @@ HIP_SYMBOLS = {
     "focr_debug_bank_images": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                          C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "focr_debug_set_stats_form": (C.c_int, [C.c_void_p, C.c_int]),
+    "focr_debug_set_verify_form": (C.c_int, [C.c_void_p, C.c_int]),
     "focr_debug_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "focr_ctx_set_size_estimates": (C.c_int, [C.c_void_p, C.c_int]),
     "focr_size_estimate_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),

@@ -181,6 +181,12 @@ int focr_debug_set_stats_form(focr_ctx_t *c, int form) {
     return FOCR_OK;
 }
 
+int focr_debug_set_verify_form(focr_ctx_t *c, int form) {
+    if (!c || form < 0 || form > 1) return FOCR_ERR_INVALID;
+    c->dbg_verify_form = form;
+    return FOCR_OK;
+}
+
 int focr_sync(focr_ctx_t *c) {
     if (!c) return FOCR_ERR_INVALID;
     FOCR_HIP(c, hipSetDevice(c->device));

@@ -413,6 +413,77 @@ __device__ __forceinline__ bool verify_candidate_narrow(uint64_t key, const Veri
     *sim_out = (float)sim;
     return ncc_emits(sim, va.thr_d);
 }
+// The same for banks of 8- and 9-wide templates of ONE height n_h <= 16 (BASELINE configs[1]: 95 templates of 8 x 15, 285 of 9 x 15),
+// where the 12-byte form spends a third of its dot products on a dword that holds one byte or none: the window's first two dwords
+// lie inside it whatever its width — no mask — and meet template rows of 8 bytes (`rows8`, indexed like needles16); the ninth
+// column is gathered from the third dwords of the loaded page rows, four rows to a dword, and meets the template's ninth column
+// packed the same way (`col9`: 16 bytes per template, by global index; zero for an 8-wide template and for rows past n_h).  The
+// width never becomes a branch — a wave's 64 candidates mix both — it is folded into the byte selectors of the gather: an 8-wide
+// template's lane selects the constant 0 for every byte, and so does every lane for a row at or past n_h, so that s_p and s2_p sum the
+// window's own bytes only.  n_h is the bank's, hence wave-uniform: the row loop has a scalar trip count and no per-lane guard.
+// acc, s_p, s2_p are sums of the same products as the other forms' — u32 without overflow (n_w * n_h * 255^2 < 2^32: rows.hip,
+// verify_mode), so their order does not matter — and the f64 epilogue is the same code: bit-identical results.
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ bool verify_candidate_w89(uint64_t key, const VerifyArgs &va, const v2u *rows8, const v4i *col9, const VerifyMeta *meta, float *sim_out) {
+    const uint32_t page = va.fmt.page(key), t = va.fmt.t(key), x = va.fmt.x(key), y = va.fmt.y(key);
+    if (t >= va.n_templates || page >= va.n_pages || x >= va.r_w || y >= va.r_h) {  // cannot happen; would otherwise be a wild read
+        atomicOr(va.flags_word, RES_FLAG_KEY);
+        *sim_out = 0.f;
+        return false;
+    }
+    // the record's doubles are read behind the rows (they would only hold registers until then); its n_h is the bank's: made a scalar HERE,
+    // so that every row's "j < n_h" is a scalar compare where it is used (as a kernel argument the sixteen compares are hoisted out of the
+    // kernel's loop as sixteen lane masks, more scalar registers than there are)
+    const uint32_t n_w = meta[t].n_w, n_h = __builtin_amdgcn_readfirstlane((uint32_t)meta[t].n_h), row0 = meta[t].row0;
+    const uint8_t *pg = va.pages + ((size_t)page * va.rows_alloc + y) * va.pitch + x;  // rows have >= 64 readable bytes past r_w
+    const v2u *nd = rows8 + row0;
+    const uint32_t *b9 = reinterpret_cast<const uint32_t *>(col9 + t);
+    const bool wide = n_w > 8;
+    uint32_t acc = 0, s_p = 0, s2_p = 0;
+#pragma unroll
+    for (int g = 0; g < 2; g++) {
+        const uint32_t j0 = 8 * g;
+        if (j0 < n_h) {  // wave-uniform; rows past n_h are read (every page has 48 readable rows below it) but not accumulated
+            v3i a[8];
+#pragma unroll
+            for (int jj = 0; jj < 8; jj++) a[jj] = *reinterpret_cast<const v3i_b1 *>(pg + (size_t)(j0 + jj) * va.pitch);
+#pragma unroll
+            for (int jj = 0; jj < 8; jj++) {
+                if (j0 + jj < n_h) {  // wave-uniform
+                    const v2u b = nd[j0 + jj];
+#pragma unroll
+                    for (int k = 0; k < 2; k++) {
+                        const uint32_t aw = (uint32_t)a[jj][k];
+                        acc = __builtin_amdgcn_udot4(aw, b[k], acc, false);          // src/ncc.cpp:316-321
+                        s_p = __builtin_amdgcn_udot4(aw, 0x01010101u, s_p, false);   // patch_sum, src/ncc.rs:307
+                        s2_p = __builtin_amdgcn_udot4(aw, aw, s2_p, false);          // sum of squares, src/ncc.rs:308
+                    }
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                // byte 8 of rows j .. j + 3 -> one dword, three v_perm_b32 (selector 0 .. 3 = that byte of the second operand, 4 = byte 0 of
+                // the first, 12 = the constant 0).  The last one's selector takes out the rows at or past n_h (scalar) and, per lane, the
+                // whole dword for an 8-wide template.
+                const uint32_t j = j0 + 4 * h;
+                const uint32_t live = (j < n_h ? 0x00u : 0x0cu) | (j + 1 < n_h ? 0x0100u : 0x0c00u) | (j + 2 < n_h ? 0x020000u : 0x0c0000u) |
+                                      (j + 3 < n_h ? 0x04000000u : 0x0c000000u);
+                uint32_t p = __builtin_amdgcn_perm((uint32_t)a[4 * h + 1][2], (uint32_t)a[4 * h][2], 0x0c0c0400u);
+                p = __builtin_amdgcn_perm((uint32_t)a[4 * h + 2][2], p, 0x0c040100u);
+                p = __builtin_amdgcn_perm((uint32_t)a[4 * h + 3][2], p, wide ? live : 0x0c0c0c0cu);
+                const uint32_t b = b9[2 * g + h];
+                acc = __builtin_amdgcn_udot4(p, b, acc, false);
+                s_p = __builtin_amdgcn_udot4(p, 0x01010101u, s_p, false);
+                s2_p = __builtin_amdgcn_udot4(p, p, s2_p, false);
+            }
+        }
+    }
+    const VerifyMeta c = meta[t];
+    const double rnorm_p = window_rnorm(s_p, (uint64_t)s2_p, (double)((uint32_t)c.n_w * c.n_h));
+    const double sim = ncc_similarity(acc, s_p, c.s_n, c.n_recip, c.rnorm_n, rnorm_p);
+    *sim_out = (float)sim;
+    return ncc_emits(sim, va.thr_d);
+}
 __device__ __forceinline__ bool verify_candidate(uint64_t key, const VerifyArgs &va, float *sim_out) {
     return verify_candidate_t<false>(key, va, nullptr, sim_out);
 }

@@ -273,18 +273,21 @@ __global__ __launch_bounds__(WAVES * 64) void row_sort_kernel(uint32_t n_rows, c
 // MODE 0: template rows from global memory · 1: the bank's verify operand staged in LDS once per workgroup, 16 bytes per row (all
 // of it fits 144 KiB) · 2: 12 bytes per row (every template at most 12 px wide and the whole operand within half a CU's LDS): 64
 // VGPRs, two workgroups per CU — the kernel waits on memory four fifths of its time, and in flight it has only the CUs the scan
-// leaves free, so waves per CU are what it runs on.
+// leaves free, so waves per CU are what it runs on · 3: banks of 8- and 9-wide templates of one height n_h (verify_candidate_w89,
+// mfma_common.h): 8 bytes per row and the ninth columns packed, 16 bytes per template; two workgroups per CU like MODE 2.
 template <int MODE>
-__global__ __launch_bounds__(VERIFY_THREADS, MODE == 2 ? 8 : 1) void verify_list_kernel(
-    const uint64_t *__restrict__ cand, const unsigned long long *__restrict__ n_cand_p, unsigned long long cap, const VerifyArgs va, uint32_t lds_rows, const RowHist rows,
-    float *__restrict__ sims, uint32_t *__restrict__ slots, uint32_t *__restrict__ row_hits, const TailWork tw) {
+__global__ __launch_bounds__(VERIFY_THREADS, MODE >= 2 ? 8 : 1) void verify_list_kernel(
+    const uint64_t *__restrict__ cand, const unsigned long long *__restrict__ n_cand_p, unsigned long long cap, const VerifyArgs va, uint32_t lds_rows, uint32_t n_h,
+    const RowHist rows, float *__restrict__ sims, uint32_t *__restrict__ slots, uint32_t *__restrict__ row_hits, const TailWork tw) {
     // LDS: [template records: n_templates x 32 B][template rows, 16 B (MODE 1) or 12 B (MODE 2) each]
+    //      MODE 3: [template records][ninth columns: n_templates x 16 B][template rows, 8 B each]
     extern __shared__ __attribute__((aligned(16))) v4i verify_lds[];
     __shared__ uint32_t wave_sum[16], wave_max[16];
     constexpr bool LDS = MODE == 1;
     VerifyMeta *meta = reinterpret_cast<VerifyMeta *>(verify_lds);
     v4i *needle_lds = verify_lds + 2 * va.n_templates;
     uint32_t *needle12 = reinterpret_cast<uint32_t *>(needle_lds);
+    v2u *needle8 = reinterpret_cast<v2u *>(needle_lds + va.n_templates);
     for (uint32_t i = threadIdx.x; i < 2 * va.n_templates; i += blockDim.x) verify_lds[i] = reinterpret_cast<const v4i *>(va.vmeta)[i];
     if (MODE == 1)
         for (uint32_t i = threadIdx.x; i < lds_rows; i += blockDim.x) needle_lds[i] = va.needles16[i];
@@ -293,6 +296,21 @@ __global__ __launch_bounds__(VERIFY_THREADS, MODE == 2 ? 8 : 1) void verify_list
             const v4i r = va.needles16[i];
             needle12[3 * i] = (uint32_t)r[0], needle12[3 * i + 1] = (uint32_t)r[1], needle12[3 * i + 2] = (uint32_t)r[2];
         }
+    if (MODE == 3) {
+        for (uint32_t i = threadIdx.x; i < lds_rows; i += blockDim.x) {
+            const v4i r = va.needles16[i];
+            needle8[i] = v2u{(uint32_t)r[0], (uint32_t)r[1]};
+        }
+        // byte 8 of the template's rows 4q .. 4q + 3 -> dword q of its ninth column (rows at or past n_h: zero)
+        for (uint32_t i = threadIdx.x; i < 4 * va.n_templates; i += blockDim.x) {
+            const uint32_t t = i >> 2, q = i & 3, row0 = va.vmeta[t].row0;
+            uint32_t d = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++)
+                if (4 * q + k < n_h) d |= ((uint32_t)va.needles16[row0 + 4 * q + k][2] & 0xffu) << (8 * k);
+            reinterpret_cast<uint32_t *>(needle_lds)[i] = d;
+        }
+    }
     __syncthreads();
     const unsigned long long n = min(*n_cand_p, cap);
     const int lane = threadIdx.x & 63;
@@ -305,7 +323,9 @@ __global__ __launch_bounds__(VERIFY_THREADS, MODE == 2 ? 8 : 1) void verify_list
         const uint64_t key = key_next;
         if (i + stride < n) key_next = cand[i + stride];
         float sim = 0.f;
-        const bool emit = valid && (MODE == 2 ? verify_candidate_narrow(key, va, needle12, meta, &sim) : verify_candidate_meta<LDS>(key, va, needle_lds, meta, &sim));
+        const bool emit = valid && (MODE == 3   ? verify_candidate_w89(key, va, needle8, needle_lds, meta, &sim)
+                                    : MODE == 2 ? verify_candidate_narrow(key, va, needle12, meta, &sim)
+                                                : verify_candidate_meta<LDS>(key, va, needle_lds, meta, &sim));
         // a hit's slot inside its bucket: the wave's 64 candidates come from a handful of page rows
         const uint32_t r = emit ? row_of_key(key, rows) : 0xffffffffu;
         uint32_t slot = 0xffffffffu;
@@ -527,20 +547,31 @@ static unsigned tail_grid(const focr_ctx *c, unsigned blocks) {
     return (unsigned)std::max<uint64_t>(1, (uint64_t)blocks * c->dbg_grid_num / c->dbg_grid_den);
 }
 
-// The verify operand's place for this bank: 2 = 12-byte rows in LDS, two workgroups per CU; 1 = 16-byte rows in LDS; 0 = global memory
-static int verify_mode(const focr_ctx *c, size_t *lds, uint32_t *rows_out) {
+// The verify operand's place for this bank: 3 = 8-byte rows and packed ninth columns in LDS (*n_h_out: the bank's one height) · 2 = 12-byte
+// rows in LDS · both with two workgroups per CU · 1 = 16-byte rows in LDS · 0 = global memory
+static int verify_mode(const focr_ctx *c, size_t *lds, uint32_t *rows_out, uint32_t *n_h_out) {
     size_t all_rows = 0;
-    uint32_t max_w = 0;
+    uint32_t max_w = 0, min_w = ~0u, h_lo = ~0u, h_hi = 0;
     for (const TemplateConst &tc : c->bank.h_tconst) {
         all_rows += (size_t)tc.n_h * (tc.n_w > 16 ? 2u : 1u);
         max_w = std::max<uint32_t>(max_w, tc.n_w);
+        min_w = std::min<uint32_t>(min_w, tc.n_w);
+        h_lo = std::min<uint32_t>(h_lo, tc.n_h);
+        h_hi = std::max<uint32_t>(h_hi, tc.n_h);
     }
     const size_t meta_bytes = c->n_templates * sizeof(VerifyMeta);  // <= 4096 templates here: 128 KiB at most
-    const bool narrow = max_w <= 12 && meta_bytes + all_rows * 12 <= ((size_t)80 << 10) - 256;
+    const size_t half_cu = ((size_t)80 << 10) - 256;
+    // verify_candidate_w89: every template 8 or 9 px wide — with a ninth column somewhere: a bank of 8-wide templates alone wants 8-byte
+    // page loads and no ninth-column stage, a form of its own (not built) — and of one height of at most 16 rows (two groups of eight page
+    // rows).  Its sums are u32 like the other forms': 9 * 16 * 255^2 < 2^24.  focr_debug_set_verify_form(1): the 12-byte form for such a bank too.
+    const bool w89 = min_w >= 8 && max_w == 9 && h_lo == h_hi && h_hi <= 16 && (uint64_t)max_w * h_hi * 255 * 255 <= 0xffffffffull &&
+                     meta_bytes + c->n_templates * 16 + all_rows * 8 <= half_cu && c->dbg_verify_form == 0;
+    const bool narrow = max_w <= 12 && meta_bytes + all_rows * 12 <= half_cu;
     const bool in_lds = meta_bytes + all_rows * 16 <= ((size_t)144 << 10);
-    *lds = meta_bytes + (narrow ? all_rows * 12 : in_lds ? all_rows * 16 : 0);
+    *lds = meta_bytes + (w89 ? c->n_templates * 16 + all_rows * 8 : narrow ? all_rows * 12 : in_lds ? all_rows * 16 : 0);
     *rows_out = (uint32_t)all_rows;
-    return narrow ? 2 : in_lds ? 1 : 0;
+    *n_h_out = w89 ? h_hi : 0;
+    return w89 ? 3 : narrow ? 2 : in_lds ? 1 : 0;
 }
 
 // hits-first tail, phase 1 (right behind the scan kernels): exact verify of the candidate list in flush order, hit counts and
@@ -566,8 +597,8 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
     if (ub_c) {
         const VerifyArgs va = verify_args(c, thr_d);
         size_t lds;
-        uint32_t all_rows;
-        const int mode = verify_mode(c, &lds, &all_rows);
+        uint32_t all_rows, n_h;
+        const int mode = verify_mode(c, &lds, &all_rows, &n_h);
         if (mode == 0 && c->bank.vrow_bytes) {
             // the operand does not fit the LDS whole: chunks of consecutive templates that do (verify_chunks_kernel)
             const bool narrow = c->bank.vrow_bytes == 12;
@@ -621,13 +652,15 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
                 (void)hipGetLastError();  // the device refuses that much LDS: the rows come from global memory instead (below)
             }
         }
-        const unsigned per_cu = mode == 2 ? 2u : (mode == 0 && c->n_templates * sizeof(VerifyMeta) <= ((size_t)64 << 10) ? 2u : 1u);
+        const unsigned per_cu = mode >= 2 ? 2u : (mode == 0 && c->n_templates * sizeof(VerifyMeta) <= ((size_t)64 << 10) ? 2u : 1u);
         const unsigned nb = tail_grid(c, (unsigned)std::max<size_t>(1, std::min<size_t>((ub_c + VERIFY_THREADS - 1) / VERIFY_THREADS, (size_t)vcus * per_cu)));
 #define FOCR_VERIFY_LIST(M)                                                                                                                                      \
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(verify_list_kernel<M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
     hipLaunchKernelGGL(verify_list_kernel<M>, dim3(nb), dim3(VERIFY_THREADS), lds, c->stream, (const uint64_t *)c->d_cand, n_cand_p, (unsigned long long)ub_c, va, \
-                       M == 0 ? 0u : all_rows, c->row_hist, csims, cslots, hits, tw)
-        if (mode == 2) {
+                       M == 0 ? 0u : all_rows, n_h, c->row_hist, csims, cslots, hits, tw)
+        if (mode == 3) {
+            FOCR_VERIFY_LIST(3);
+        } else if (mode == 2) {
             FOCR_VERIFY_LIST(2);
         } else if (mode == 1) {
             FOCR_VERIFY_LIST(1);
@@ -636,7 +669,7 @@ int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, 
         }
 #undef FOCR_VERIFY_LIST
         FOCR_HIP(c, hipGetLastError());
-        c->tail_path.verify_form = mode == 2 ? FOCR_VERIFY_FORM_LDS12 : mode == 1 ? FOCR_VERIFY_FORM_LDS16 : FOCR_VERIFY_FORM_GLOBAL;
+        c->tail_path.verify_form = mode == 3 ? FOCR_VERIFY_FORM_LDS8 : mode == 2 ? FOCR_VERIFY_FORM_LDS12 : mode == 1 ? FOCR_VERIFY_FORM_LDS16 : FOCR_VERIFY_FORM_GLOBAL;
     }
 verified:
     FOCR_HIP(c, hipEventRecord(c->ev[EV_VERIFY_END], c->stream));

@@ -283,12 +283,12 @@ class Scanner:
     def tail_path(self):
         """Test hook (focr_debug_tail_path): what the last scan's tail chose: {'tail': 'rows' / 'legacy' / 'none', 'big_launch': the row
         sort's second launch ran, 'library_sort': the placed hits went through the library sort, 'order': 'counting' / 'sorting' / 'none',
-        'seg_shift', 'n_seg': the row buckets' x-segments, 'verify': 'global' / 'lds16' / 'lds12' / 'chunks' / 'none', 'verify_chunks'}."""
+        'seg_shift', 'n_seg': the row buckets' x-segments, 'verify': 'global' / 'lds16' / 'lds12' / 'chunks' / 'lds8' / 'none', 'verify_chunks'}."""
         out = (C.c_uint32 * 8)()
         self._ck(self._lib.focr_debug_tail_path(self._h, out))
         return {"tail": ("none", "rows", "legacy")[out[0]], "big_launch": bool(out[1]), "library_sort": bool(out[2]),
                 "order": ("none", "counting", "sorting")[out[3]], "seg_shift": int(out[4]), "n_seg": int(out[5]),
-                "verify": ("none", "global", "lds16", "lds12", "chunks")[out[6]], "verify_chunks": int(out[7])}
+                "verify": ("none", "global", "lds16", "lds12", "chunks", "lds8")[out[6]], "verify_chunks": int(out[7])}
 
     def scan_paired(self):
         """Test hook (focr_debug_scan_paired): (launches of the plane prefilter kernel in the last scan, those in the paired form)."""
@@ -299,6 +299,10 @@ class Scanner:
     def set_stats_form(self, form):
         """Test hook (focr_debug_set_stats_form): 1 = the LDS-tiled statistics kernel for every class, 0 = the register form where it applies."""
         self._ck(self._lib.focr_debug_set_stats_form(self._h, int(form)))
+
+    def set_verify_form(self, form):
+        """Test hook (focr_debug_set_verify_form): 1 = the 12-byte verify form also for a bank that would take the 8-byte one, 0 = as designed."""
+        self._ck(self._lib.focr_debug_set_verify_form(self._h, int(form)))
 
     def planes(self):
         """Test hook (focr_debug_planes): the int16 threshold planes of the last MFMA scan, flat."""

@@ -510,7 +510,8 @@ int focr_debug_set_tail_grid(focr_ctx_t *ctx, uint32_t num, uint32_t den);
  *           / rust scan, whose hits take the same pass behind their radix sort
  *   out[4], out[5]  log2 of the bucket's x-segment width and the segments per page row (row tail; else 0)
  *   out[6]  FOCR_VERIFY_FORM_*: where the row tail's exact verify took the template rows from (global memory, 16- or 12-byte
- *           rows staged in LDS whole, LDS in chunks of templates); out[7]: the chunk passes of the last form
+ *           rows staged in LDS whole, LDS in chunks of templates, 8-byte rows and packed ninth columns in LDS: banks of 8- and
+ *           9-wide templates of one height); out[7]: the chunk passes of the chunked form
  * A batch scanned in page sub-ranges reports its last sub-range; an estimated scan that was redone reports the redo. */
 #define FOCR_TAIL_NONE 0
 #define FOCR_TAIL_ROWS 1
@@ -523,7 +524,12 @@ int focr_debug_set_tail_grid(focr_ctx_t *ctx, uint32_t num, uint32_t den);
 #define FOCR_VERIFY_FORM_LDS16 2
 #define FOCR_VERIFY_FORM_LDS12 3
 #define FOCR_VERIFY_FORM_CHUNKS 4
+#define FOCR_VERIFY_FORM_LDS8 5
 int focr_debug_tail_path(focr_ctx_t *ctx, uint32_t out[8]);
+
+/* Test hook: form 1 = the row tail's exact verify takes the 12-byte form (FOCR_VERIFY_FORM_LDS12) also for a bank that would take the
+ * 8-byte one (0: as designed).  Both forms must give the same hits, similarities and slots, bit for bit. */
+int focr_debug_set_verify_form(focr_ctx_t *ctx, int form);
 
 /* Test hook: how the context's last scan launched the plane prefilter kernel (read from the per-launch records of
  * focr_last_launches; nothing on the device changes for it): out[0] = its launches, out[1] = those in the paired form, which scans two
