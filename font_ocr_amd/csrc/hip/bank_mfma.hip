@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "mfma_common.h"
+#include "verify.h"
 
 namespace focr {
 
@@ -238,7 +239,7 @@ int build_mfma_bank(focr_ctx *c, const uint8_t *dense) {
         if (int rc = c->upload(c->bank.d_vmeta, vm.data(), vm.size())) return rc;
     }
     {  // the same operand by GLOBAL template index, as rows of 12 bytes (every template at most 12 px wide) or 16: chunks of consecutive
-       // templates are contiguous there (verify_chunks_kernel, rows.hip: banks whose operand does not fit the LDS whole)
+       // templates are contiguous there (verify_chunks_kernel, verify.hip: banks whose operand does not fit the LDS whole)
         uint32_t max_w = 0;
         for (const TemplateConst &tc : c->bank.h_tconst) max_w = std::max<uint32_t>(max_w, tc.n_w);
         c->bank.vrow_bytes = max_w <= 12 ? 12u : max_w <= 16 ? 16u : 0u;

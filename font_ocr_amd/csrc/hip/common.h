@@ -20,7 +20,7 @@ struct VerifyRec;  // decode.h
 
 namespace focr {
 
-struct VerifyMeta;  // mfma_common.h
+struct VerifyMeta;  // verify.h
 
 // ---- geometry of one size class -------------------------------------------
 // A size class is the set of templates that share (n_w, n_h); window statistics
@@ -179,8 +179,8 @@ struct ResultBlock {
     uint64_t hits;         // written: record_scan_sizes.  Read: finish_results
     uint64_t matches;      // hits that survive their call's cap.  Written: record_scan_sizes.  Read: finish_results
     uint64_t lines_chars;  // lines << 32 | chars.  Written: focr_process_hits, into the HOST copy only (the row scan's grand total).  Read: finish_results
-    uint64_t flags;        // RES_FLAG_*.  Written: record_scan_sizes, row_sort_kernel (rows.hip), verify_candidate (mfma_common.h).  Read: finish_results
-    uint64_t row_max;      // largest row bucket.  Written: the row prefix (rows.hip: the verify's last workgroup, or row_prefix_kernel).  Read: row_tail (exact sizes), finish_results for SizeEstimate::update
+    uint64_t flags;        // RES_FLAG_*.  Written: record_scan_sizes, row_sort_kernel (rows.hip), verify_reject (verify.h).  Read: finish_results
+    uint64_t row_max;      // largest row bucket.  Written: the row prefix (verify.hip: the verify's last workgroup, or row_prefix_kernel).  Read: row_tail (exact sizes), finish_results for SizeEstimate::update
     uint64_t tail_hits;    // hits the row tail's verify counted.  Written: the same prefix.  Read: row_tail (exact sizes); as d_n_hits by every kernel behind it
     uint64_t host_hits;    // a hit count the HOST knows (direct scan, split batch, debug hits).  Written: install_host_hits.  Read: as d_n_hits by the ordering and process_hits
 };
@@ -232,9 +232,9 @@ struct focr_ctx {
         focr::DevArray<uint32_t> d_needle_off;
         focr::DevArray<uint8_t> d_needles16;               // class-ordered, n_h rows of 16 bytes each (verify operand)
         focr::DevArray<uint32_t> d_needle16_row;           // class-ordered first row index into d_needles16
-        focr::DevArray<focr::VerifyMeta> d_vmeta;          // by GLOBAL template index (mfma_common.h): what the verify needs about a template, 32 B
+        focr::DevArray<focr::VerifyMeta> d_vmeta;          // by GLOBAL template index (verify.h): what the verify needs about a template, 32 B
         // the verify operand once more, ordered by GLOBAL template index, for banks that do not fit the LDS whole: a chunk of
-        // consecutive templates is then one contiguous piece (verify_chunks_kernel, rows.hip)
+        // consecutive templates is then one contiguous piece (verify_chunks_kernel, verify.hip)
         focr::DevArray<uint8_t> d_vrows_t;                 // rows of vrow_bytes each (12 when every template is at most 12 px wide, else 16), by global index
         focr::DevArray<focr::VerifyMeta> d_vmeta_t;        // VerifyMeta by global index whose row0 counts rows of d_vrows_t
         std::vector<uint32_t> h_vrow0_t;                   // [n_templates + 1] first row of every template in d_vrows_t
@@ -264,7 +264,7 @@ struct focr_ctx {
     int scan_mode = 0;
     int32_t post_overlap = 0;
     bool force_split = false;                   // tests: take scan_split without waiting for an overflow (focr_debug_force_split)
-    int dbg_verify_form = 0;  // tests / A-B: 1 = the 12-byte verify form also for a bank that would take the 8-byte one (focr_debug_set_verify_form; rows.hip, verify_mode)
+    int dbg_verify_form = 0;  // tests / A-B: 1 = the 12-byte verify form also for a bank that would take the 8-byte one (focr_debug_set_verify_form; verify_plan.h)
     int dbg_stats_form = 0;  // tests / A-B: 1 = the LDS-tiled statistics kernel for every class (focr_debug_set_stats_form; 0: the register form where it applies)
     uint32_t dbg_grid_num = 0, dbg_grid_den = 0;  // tests: the tail's persistent kernels on num / den times their workgroups (focr_debug_set_tail_grid; 0: as designed)
     int prefilter = 0;                          // FOCR_PREFILTER_*: auto / plane kernel / legacy kernel (focr_ctx_set_prefilter)
@@ -309,7 +309,7 @@ struct focr_ctx {
     size_t n_matches = 0;
 
     // grow-only scratch (Grow::quarter at every reserve).  scan_flags / scan_pos and ord_k2 / ord_v are bytes: their readers disagree
-    // about the type (u64 flags and positions in scan_split and the legacy tail, u32 slots / f32 similarities in rows.hip; u64 keys /
+    // about the type (u64 flags and positions in scan_split and the legacy tail, u32 slots / f32 similarities in verify.hip and rows.hip; u64 keys /
     // f32 values in order.hip's sorting form, u32 tables in its counting form)
     focr::DevArray<uint8_t> scan_flags, scan_pos, scan_live;
     focr::DevArray<uint64_t> scan_live_list;
@@ -457,9 +457,13 @@ int quantise_bank(focr_ctx *c, const uint8_t *dense, std::vector<int8_t> &qbank,
 bool rows_applicable(const focr_ctx *c);
 uint32_t rows_capacity_for(uint64_t row_max);
 void row_segments(const focr_ctx *c, uint32_t *seg_shift, uint32_t *n_seg);
+size_t row_buckets(const focr_ctx *c);
+unsigned tail_grid(const focr_ctx *c, unsigned blocks);  // a persistent tail kernel's grid under the test hook focr_debug_set_tail_grid
 int rows2_begin(focr_ctx *c, ClearList &clear);  // the hits-first tail: verify in flush order, then only hits are placed and sorted
-int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c);
 int rows2_place(focr_ctx *c, const unsigned long long *n_cand_p, size_t ub_c, size_t ub_h, bool big_expected, bool sort);
+// verify.hip: the exact verify of the candidate list
+int rows2_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c);  // the hits-first tail's: slots per bucket, their prefix
+int legacy_verify(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c, float *sims, uint64_t *flags);  // the legacy tail's: flags in place
 // order.hip
 int sort_keys_u64(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, size_t n, unsigned end_bit);
 int sort_pairs_u64_f32(focr_ctx *c, DevArray<uint64_t> &keys, DevArray<uint64_t> &keys_alt, DevArray<float> &vals, DevArray<float> &vals_alt, size_t n, unsigned end_bit);

@@ -8,9 +8,9 @@
 //     (mfma_common.h; int32 tables on the legacy path), and the work list of the 16-window M-tiles that have a live window.
 //  2. MFMA prefilter (scan_mfma2.hip) against the quantised bank (bank_mfma.hip: the bound, and why it has no false negatives).
 //     Survivors go to a candidate list.
-//  3. the hits-first row tail (rows.hip): candidates verified exactly where they lie — the reference formula, operation for
-//     operation (verify_candidate, mfma_common.h / common.h) — hits bucketed by page row and sorted per bucket; order.hip derives
-//     the per-call ranks and the cap.  (verify_kernel below + the library radix sort = the legacy tail, kept as a fallback.)
+//  3. the hits-first row tail: candidates verified exactly where they lie (verify.hip) — the reference formula, operation for
+//     operation (verify.h / common.h) — hits bucketed by page row and sorted per bucket (rows.hip); order.hip derives
+//     the per-call ranks and the cap.  (verify_kernel, verify.hip, + the library radix sort = the legacy tail, kept as a fallback.)
 //
 // Sizes: every phase behind the scan kernel takes its element count from device memory; exact / estimated mode: see
 // launch_scan_mfma and results.hip (finish_results).
@@ -227,14 +227,7 @@ static int scan_phase(focr_ctx *c, const ScanPlan &P, double thr_d) {
     return FOCR_OK;
 }
 
-VerifyArgs verify_args(const focr_ctx *c, double thr_d) {
-    return VerifyArgs{c->pages.u8, (uint32_t)c->pages.pitch, (uint32_t)c->pages.rows_alloc, c->fmt, c->bank.d_order_of, c->bank.d_tconst,
-                      c->bank.d_needles16.as<const v4i>(), c->bank.d_needle16_row, thr_d, c->bank.d_vmeta.p,
-                      (uint32_t)c->n_templates, (uint32_t)c->n_pages,
-                      (uint32_t)c->pages.r_w, (uint32_t)c->pages.r_h, (unsigned long long *)&c->d_res.p->flags};
-}
-
-// 3a. hits-first row tail: verify the candidates where they lie, then bucket + sort the hits only (rows.hip)
+// 3a. hits-first row tail: verify the candidates where they lie (verify.hip), then bucket + sort the hits only (rows.hip)
 static int row_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c) {
     int rc = rows2_verify(c, thr_d, n_cand_p, ub_c);
     if (rc) return rc;
@@ -260,27 +253,7 @@ static int row_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_
     return order_sorted_hits(c, c->d_hit_keys, c->d_hit_sims_alt, &c->d_res.p->tail_hits, ub_h, n_cand_p, ub_c);
 }
 
-// ---------------------------------------------------------------------------------------------
-// 3. exact verify: the reference arithmetic on every candidate (verify_candidate, mfma_common.h)
-//
-// Legacy tail (fallback of the row path, rows.hip): candidates arrive radix-sorted by the packed key (page, y, x, t):
-// neighbouring lanes verify the same or neighbouring windows (cache-friendly), and the survivors stay in process_hits order,
-// so no atomics: flag[i] / sim[i] are written in place and order.hip compacts them and derives the per-call lists.
-__global__ __launch_bounds__(256) void verify_kernel(const uint64_t *__restrict__ cand, const unsigned long long *__restrict__ n_cand_p, unsigned long long ub,
-                                                     const VerifyArgs va, float *__restrict__ sims, uint64_t *__restrict__ flags) {
-    unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > ub) return;  // grid and buffers are sized for `ub` candidates (+ the sentinel at ub)
-    if (i >= min(*n_cand_p, ub)) {  // past the device-side count (and the sentinel: the exclusive scan of flags also yields the total)
-        flags[i] = 0;
-        return;
-    }
-    float sim;
-    const bool emit = verify_candidate(cand[i], va, &sim);
-    sims[i] = sim;
-    flags[i] = emit ? 1 : 0;
-}
-
-// 3b. legacy tail: sort the candidates into emission order, verify them exactly in place, compact + cap (order.hip)
+// 3b. legacy tail: sort the candidates into emission order, verify them exactly in place (verify.hip), compact + cap (order.hip)
 static int legacy_tail(focr_ctx *c, double thr_d, const unsigned long long *n_cand_p, size_t ub_c) {
     c->row_cap = 0;
     int rc = reserve_hits(c, ub_c + 1);
@@ -289,9 +262,7 @@ static int legacy_tail(focr_ctx *c, double thr_d, const unsigned long long *n_ca
     uint64_t *flags = c->scan_flags.as<uint64_t>(), *pos = c->scan_pos.as<uint64_t>();
     if (c->d_cand_alt.reserve(c->d_cand.cap, Grow::exact, &c->stream)) return fail(c, FOCR_ERR_NOMEM, "scan_mfma: hipMalloc(cand_alt) failed");
     if ((rc = sort_keys_u64(c, c->d_cand, c->d_cand_alt, ub_c, c->fmt.bits()))) return rc;
-    hipLaunchKernelGGL(verify_kernel, dim3((unsigned)((ub_c + 1 + 255) / 256)), dim3(256), 0, c->stream, c->d_cand, n_cand_p, (unsigned long long)ub_c,
-                       verify_args(c, thr_d), c->d_hit_sims, flags);
-    FOCR_HIP(c, hipGetLastError());
+    if ((rc = legacy_verify(c, thr_d, n_cand_p, ub_c, c->d_hit_sims, flags))) return rc;
     FOCR_HIP(c, hipEventRecord(c->ev[EV_VERIFY_END], c->stream));
     if ((rc = compact_candidates(c, c->d_cand, c->d_hit_sims, flags, pos, n_cand_p, ub_c))) return rc;
     size_t ub_h = std::min(ub_c, c->est.hits);
@@ -332,7 +303,7 @@ int launch_scan_mfma(focr_ctx *c, float threshold) {
         bool use_rows = rows_applicable(c);
         if (use_rows && c->estimated) use_rows = c->est.row_max != 0 && rows_capacity_for(c->est.row_bound()) != 0;
         c->row_hist = RowHist{};
-        if (use_rows && (rc = rows2_begin(c, clear))) return rc;  // hits-first row tail: verify in flush order, only hits are bucketed and sorted (rows.hip)
+        if (use_rows && (rc = rows2_begin(c, clear))) return rc;  // hits-first row tail: verify in flush order (verify.hip), only hits are bucketed and sorted (rows.hip)
         // legacy tail, estimated sizes: unused candidate slots hold the largest key so that the radix sort leaves them at the end
         if (c->estimated && !use_rows) FOCR_HIP(c, hipMemsetAsync(c->d_cand, 0xff, c->ub_cand * 8, c->stream));
         FOCR_HIP(c, hipEventRecord(c->ev[EV_STATS_BEGIN], c->stream));

@@ -308,7 +308,7 @@ int focr_ctx_set_prefilter(focr_ctx_t *ctx, int mode);
  * the next focr_bank_upload. */
 int focr_ctx_set_column_drop(focr_ctx_t *ctx, int on);
 
-/* Tail of the MFMA scan (rows.hip).  1 (default) = the hits-first row path: the candidates are verified where the scan kernels
+/* Tail of the MFMA scan (verify.hip, rows.hip).  1 (default) = the hits-first row path: the candidates are verified where the scan kernels
  * left them (flush order: neighbouring lanes, neighbouring windows), then only the HITS are bucketed by page row and sorted
  * per bucket with their similarities.  0 = the legacy tail (library radix sort of all candidates, verify, flag scan, compaction), which
  * also serves batches the row path does not cover (banks with templates taller than 32 px or more than 4096 templates).
@@ -511,7 +511,7 @@ int focr_debug_set_tail_grid(focr_ctx_t *ctx, uint32_t num, uint32_t den);
  *   out[4], out[5]  log2 of the bucket's x-segment width and the segments per page row (row tail; else 0)
  *   out[6]  FOCR_VERIFY_FORM_*: where the row tail's exact verify took the template rows from (global memory, 16- or 12-byte
  *           rows staged in LDS whole, LDS in chunks of templates, 8-byte rows and packed ninth columns in LDS: banks of 8- and
- *           9-wide templates of one height); out[7]: the chunk passes of the chunked form
+ *           9-wide templates of one height); out[7]: the chunk passes of the chunked form (the host's plan: csrc/hip/verify_plan.h)
  * A batch scanned in page sub-ranges reports its last sub-range; an estimated scan that was redone reports the redo. */
 #define FOCR_TAIL_NONE 0
 #define FOCR_TAIL_ROWS 1

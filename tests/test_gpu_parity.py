@@ -466,7 +466,7 @@ def test_random_banks_all_layouts(scanner, mode, shapes):
 @pytest.mark.parametrize("shapes,per_shape", [([(16, 24), (14, 20)], 220), ([(9, 16), (8, 15), (12, 12)], 700)], ids=["rows16", "rows12"])
 def test_banks_above_the_lds_verify_in_chunks(scanner, shapes, per_shape):
     """Round 4: a bank whose verify operand does not fit the LDS whole (here 180 KB of 16-byte rows / 330 KB of 12-byte rows) is
-    verified in chunk passes (verify_chunks_kernel, rows.hip: chunk rows in LDS, a wave-private queue per chunk); same lists as
+    verified in chunk passes (verify_chunks_kernel, verify.hip: chunk rows in LDS, a wave-private queue per chunk); same lists as
     the reference kernel, also through the legacy tail (template rows gathered from global memory)."""
     import zlib
 

@@ -1,5 +1,5 @@
-"""The exact verify's form for banks of 8- and 9-wide templates of one height (verify_candidate_w89, mfma_common.h; verify_list_kernel<3>,
-rows.hip: template rows of 8 bytes, the ninth column packed four rows to a dword) on the device.  The form computes the same integers as
+"""The exact verify's form for banks of 8- and 9-wide templates of one height (verify_candidate_w89, verify.h; verify_list_kernel<3>,
+verify.hip: template rows of 8 bytes, the ninth column packed four rows to a dword) on the device.  The form computes the same integers as
 the 12-byte form and shares its f64 epilogue, so everything a scan returns must be the same bit for bit: per context, the 8-byte form (as
 designed) and the 12-byte form (focr_debug_set_verify_form(1)) give the same offsets, match lists (x, y, f32 bits, order), counts and
 candidate sets, with exact and with estimated sizes, and both equal the exact scan (SCAN_DIRECT) on the same pages; the library reports the
@@ -16,11 +16,10 @@ import pytest
 import prefilter_cases as PC
 from font_ocr_amd import synth_page
 from font_ocr_amd.bank import SYNTH_SEED_BASE, Bank
-from font_ocr_amd.searcher import SCAN_DIRECT, SCAN_MFMA, Scanner
+from font_ocr_amd.searcher import SCAN_MFMA, Scanner
+from verify_cases import CAP, noise_bank as _noise_bank, noise_pages as _noise_pages, scan_all
 
 pytestmark = pytest.mark.gpu
-
-CAP = 1024
 
 
 @pytest.fixture(scope="module")
@@ -33,61 +32,9 @@ def bank32():
     return bank
 
 
-def _noise_bank(classes, seed):
-    """[(n_w, n_h, templates)] -> a bank of noise templates, the classes interleaved."""
-    rng = np.random.default_rng(seed)
-    needles = []
-    for n_w, n_h, count in classes:
-        for _ in range(count):
-            nd = rng.integers(0, 256, (n_h, n_w), dtype=np.uint8)
-            nd[0, 0], nd[-1, -1] = 255, 0  # never constant
-            needles.append(nd)
-    return PC.bank_of([needles[i] for i in rng.permutation(len(needles))])
-
-
-def _noise_pages(bank, shape, seed, plants):
-    """Half-empty noise with the bank's templates planted at (t, page, y, x)."""
-    rng = np.random.default_rng(seed)
-    ink = rng.integers(0, 256, shape, dtype=np.uint8)
-    ink[rng.random(shape) < 0.5] = 0
-    for t, p, y, x in plants:
-        nd = bank.needle(t)
-        ink[p, y:y + nd.shape[0], x:x + nd.shape[1]] = nd
-    return ink
-
-
-def _result(sc):
-    offsets, m = sc.matches()
-    return offsets.tobytes(), m.tobytes(), sc.counts().tobytes()
-
-
-def _cand_set(sc):
-    cand = sc.candidates()
-    assert len(cand) == sc.counters()["candidates"]
-    keys = set(map(tuple, cand.tolist()))
-    assert len(keys) == len(cand), "duplicates in the candidate list"
-    return keys
-
-
 def _scan_all(sc, thr, form_designed, what):
-    """Both verify forms of one context (exact sizes, then estimated), then the exact scan: all results equal.  Returns (the direct scan's
-    matches, the candidate set)."""
-    results, cands = [], []
-    for form, name in ((0, form_designed), (1, "lds12")):
-        sc.set_verify_form(form)
-        for which in ("exact sizes", "estimated sizes"):
-            sc.scan(thr, CAP, SCAN_MFMA)
-            tp = sc.tail_path()
-            assert tp["tail"] == "rows" and tp["verify"] == name, (what, form, which, tp)
-            results.append(_result(sc))
-            cands.append(_cand_set(sc))
-    sc.set_verify_form(0)
-    sc.scan(thr, CAP, SCAN_DIRECT)
-    direct = _result(sc)
-    for i, r in enumerate(results):
-        assert r == direct, f"{what}: scan {i} (verify form {i // 2}, {'estimated' if i % 2 else 'exact'} sizes) differs from the exact scan"
-    assert cands[0] == cands[1] == cands[2] == cands[3], (what, [len(c) for c in cands])
-    return sc.matches()[1], cands[0]
+    """Both verify forms of one context, then the exact scan: all results equal (verify_cases.scan_all)."""
+    return scan_all(sc, thr, ((0, form_designed), (1, "lds12")), what)
 
 
 @pytest.mark.parametrize("thr", [0.8, 0.3])
