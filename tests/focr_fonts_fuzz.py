@@ -22,7 +22,7 @@ import numpy as np
 
 import focr_fonts_model as FM
 import focr_whole_model as W
-from focr_fuzz_cases import FONTS, KERNINGS, MONO, SANS, SERIF, SIZES, WHOLE_BATCH_MAX, WHOLE_RING_MAX, _alphabet, _ink_line, crops, fast
+from focr_fuzz_cases import FONTS, KERNINGS, MONO, SANS, SERIF, SIZES, WHOLE_BATCH_MAX, WHOLE_RING_MAX, _alphabet, _ink_line, crops, fast, last_batch
 
 SEED = 0xF0F7
 N_RANDOM = 24
@@ -173,3 +173,34 @@ def want(c, form):
         _want[key] = [FM.search_image(ms, p, *c.geo, whole=form == "whole") for p in c.pages]
     return _want[key]
 
+
+# ---- a case on a LineDecoder (the device tests') ---------------------------------------------------------------------------
+
+def get_fonts(d):
+    n = d._lib.focr_decoder_n_lines(d._h)
+    k, cost = np.full(max(n, 1), 99, dtype=np.uint8), np.zeros(max(n, 1), dtype=np.int64)
+    return d._lib.focr_decoder_get_fonts(d._h, k.ctypes.data, cost.ctypes.data), [int(v) for v in k[:n]], [int(v) for v in cost[:n]]
+
+
+def searched(d, c, form):
+    """set_font, set_font_candidates and a searched decode() of a case in a form, its result named; every second odd case
+    runs several lines through one workgroup, or through two."""
+    who = (c.name, form)
+    ms = models(c)
+    d.set_font(ms[0].font, c.size)
+    d.set_font_candidates([m.font for m in ms[1:]])
+    grid = 1 + (c.index // 4) % 2 if c.index % 4 == 1 else 0
+    assert d._lib.focr_decoder_debug_set_fonts_grid(d._h, grid) == 0, who
+    try:
+        res = d.decode(c.pages, *c.geo, font_search=True, whole_line=form == "whole")
+    finally:
+        assert d._lib.focr_decoder_debug_set_fonts_grid(d._h, 0) == 0, who
+    names = ("lines", "pens", "costs", "fonts") if form == "whole" else ("lines", "fonts", "costs")
+    assert len(res) == len(names), who
+    got = dict(zip(names, res))
+    launches = d._lib.focr_decoder_last_launches(d._h)
+    idx, has_slots = last_batch(c)
+    assert launches == (3 if has_slots else 0), who + (launches,)
+    rc, ks, costs = get_fonts(d)  # of the size group that ran last
+    assert rc == 0 and ks == [k for i in idx for k in got["fonts"][i]] and costs == [v for i in idx for v in got["costs"][i]], who + ("focr_decoder_get_fonts",)
+    return got

@@ -203,3 +203,40 @@ def want(c, mode):
             out = [[(y, line(ref)) for y, ref in crops(c, p) if not np.all(ref == 255)] for p in c.pages]
         _want[key] = out
     return _want[key]
+
+
+# ---- a case on a LineDecoder (the device tests') ---------------------------------------------------------------------------
+
+SWITCHES = {"plain": {}, "scores": dict(scores=True), "search": dict(pen_search=True), "search_scores": dict(pen_search=True, scores=True),
+            "whole": dict(whole_line=True), "margins": dict(whole_line=True, margins=True), "slack": dict(whole_line=True, pen_slack=True)}
+
+
+def run(dec, c, mode, verify=None):
+    """decode() of a case in a mode, its result named: lines, (mse, images,) scores, offsets, pens, costs, margins."""
+    kw = dict(SWITCHES[mode])
+    if "pen_search" in kw:
+        kw["pen_search"] = c.radius
+    if "pen_slack" in kw:
+        kw["pen_slack"] = c.slack
+    fm = model(c)
+    if dec.font is not fm.font:
+        dec.set_font(fm.font, c.size)
+    grid = 1 + (c.index // 2) % 2 if c.index % 2 and mode in WHOLE_MODES else 0  # several lines through one workgroup
+    assert dec._lib.focr_decoder_debug_set_whole_grid(dec._h, grid) == 0, (c.name, mode)
+    try:
+        res = dec.decode(c.pages, *c.geo, verify=verify, **kw)
+    finally:
+        assert dec._lib.focr_decoder_debug_set_whole_grid(dec._h, 0) == 0, (c.name, mode)
+    res = res if isinstance(res, tuple) else (res,)
+    names = ["lines"] + (["mse", "images"] if verify else []) + [n for n, on in (
+        ("scores", "scores" in kw), ("offsets", "pen_search" in kw), ("pens", "whole_line" in kw), ("costs", "whole_line" in kw),
+        ("margins", "margins" in kw), ("offsets", "pen_slack" in kw)) if on]
+    assert len(res) == len(names), (c.name, mode)
+    return dict(zip(names, res))
+
+
+def last_batch(c):
+    """The pages of the size group that decode() runs last, and whether that run has any line slot."""
+    shapes = list(dict.fromkeys(p.shape for p in c.pages))
+    idx = [i for i, p in enumerate(c.pages) if p.shape == shapes[-1]]
+    return idx, c.geo[3] > 0 and c.geo[1] < shapes[-1][0]

@@ -7,6 +7,8 @@ translation ty = origin_y + q * 2^-B of the line's baseline candidate q; its ter
 (raster_glyph clips to the canvas on all four sides); the line's cost is the sum of its terms, and with a shift radius N the
 lowest (cost_j, rank(j)) over the rigid shifts j in -N ..= N.  A font is a DecodeFont, of which only the numbers are read
 (path, size, hinting, alphabet, increments, origin): nothing comes from the phase table, and nothing from the device path.
+FreeType refuses a translation near 2^15 px (a pen near 2^21); such a glyph lies wholly right of any crop of the tests and
+its term is 0 by the definition, which terms() checks before it takes the 0.
 """
 import collections
 
@@ -14,7 +16,7 @@ import numpy as np
 
 from focr_fast_model import crop
 from focr_search_model import rank
-from font_ocr_amd.decoder import raster_glyph
+from font_ocr_amd.decoder import DecoderError, raster_glyph
 
 F32 = np.float32
 STEP = F32(0.015625)
@@ -52,7 +54,11 @@ def terms(font, ref, idx, ds, q=0, y_bits=0):
     canvas = np.zeros(ref.shape, dtype=np.uint8)
     for g, (i, d) in enumerate(zip(idx, ds)):
         canvas[:] = 0
-        raster_glyph(font.font_path, font.text_size, font.alphabet[i], F32(d) / F32(64), ty, canvas, font.hinting)
+        try:
+            raster_glyph(font.font_path, font.text_size, font.alphabet[i], F32(d) / F32(64), ty, canvas, font.hinting)
+        except DecoderError:  # FreeType refuses a translation near 2^15 px: such a glyph lies wholly right of the crop, term 0
+            assert d >= 1 << 20 and (d >> 6) - 2 * int(np.ceil(font.text_size)) - 2 >= ref.shape[1], (d, ref.shape)
+            continue
         c = canvas.astype(np.int64)
         out[g] = int((c * (c - 2 * r)).sum())
     return out

@@ -22,6 +22,7 @@ import pytest
 
 import focr_fonts_fuzz as FZ
 import focr_whole_model as W
+from focr_fonts_fuzz import get_fonts, searched
 from font_ocr_amd import LineDecoder
 from font_ocr_amd import _native as N
 
@@ -37,43 +38,6 @@ def dec():
     _module["bytes"] = N.hip().focr_debug_device_bytes()
     with LineDecoder(0) as d:
         yield d
-
-
-def last_batch(c):
-    """The pages of the size group that decode() runs last, and whether that run has any line slot."""
-    shapes = list(dict.fromkeys(p.shape for p in c.pages))
-    idx = [i for i, p in enumerate(c.pages) if p.shape == shapes[-1]]
-    return idx, c.geo[3] > 0 and c.geo[1] < shapes[-1][0]
-
-
-def get_fonts(d):
-    n = d._lib.focr_decoder_n_lines(d._h)
-    k, cost = np.full(max(n, 1), 99, dtype=np.uint8), np.zeros(max(n, 1), dtype=np.int64)
-    return d._lib.focr_decoder_get_fonts(d._h, k.ctypes.data, cost.ctypes.data), [int(v) for v in k[:n]], [int(v) for v in cost[:n]]
-
-
-def searched(d, c, form):
-    """set_font, set_font_candidates and a searched decode() of a case in a form, its result named; every second odd case
-    runs several lines through one workgroup, or through two."""
-    who = (c.name, form)
-    ms = FZ.models(c)
-    d.set_font(ms[0].font, c.size)
-    d.set_font_candidates([m.font for m in ms[1:]])
-    grid = 1 + (c.index // 4) % 2 if c.index % 4 == 1 else 0
-    assert d._lib.focr_decoder_debug_set_fonts_grid(d._h, grid) == 0, who
-    try:
-        res = d.decode(c.pages, *c.geo, font_search=True, whole_line=form == "whole")
-    finally:
-        assert d._lib.focr_decoder_debug_set_fonts_grid(d._h, 0) == 0, who
-    names = ("lines", "pens", "costs", "fonts") if form == "whole" else ("lines", "fonts", "costs")
-    assert len(res) == len(names), who
-    got = dict(zip(names, res))
-    launches = d._lib.focr_decoder_last_launches(d._h)
-    idx, has_slots = last_batch(c)
-    assert launches == (3 if has_slots else 0), who + (launches,)
-    rc, ks, costs = get_fonts(d)  # of the size group that ran last
-    assert rc == 0 and ks == [k for i in idx for k in got["fonts"][i]] and costs == [v for i in idx for v in got["costs"][i]], who + ("focr_decoder_get_fonts",)
-    return got
 
 
 def same(got, c, form):

@@ -14,6 +14,7 @@ import focr_margins_model as MM
 import focr_search_model as S
 import focr_slack_model as K
 import focr_whole_model as W
+from focr_fuzz_cases import last_batch, run
 from font_ocr_amd import LineDecoder, LineMargins, LineScores, VerifyFont
 from font_ocr_amd import _native as N
 
@@ -21,8 +22,6 @@ pytestmark = pytest.mark.gpu
 
 GROUP = 6
 GROUPS = [list(range(a, min(a + GROUP, FC.N_CASES))) for a in range(0, FC.N_CASES, GROUP)]
-SWITCHES = {"plain": {}, "scores": dict(scores=True), "search": dict(pen_search=True), "search_scores": dict(pen_search=True, scores=True),
-            "whole": dict(whole_line=True), "margins": dict(whole_line=True, margins=True), "slack": dict(whole_line=True, pen_slack=True)}
 _module = {}
 
 
@@ -40,37 +39,6 @@ def verify_font(c):
     if c.index not in _vfonts:
         _vfonts[c.index] = VerifyFont(c.font, c.size, c.alphabet, c.hinting, c.kerning)
     return _vfonts[c.index]
-
-
-def run(dec, c, mode, verify=None):
-    """decode() of a case in a mode, its result named: lines, (mse, images,) scores, offsets, pens, costs, margins."""
-    kw = dict(SWITCHES[mode])
-    if "pen_search" in kw:
-        kw["pen_search"] = c.radius
-    if "pen_slack" in kw:
-        kw["pen_slack"] = c.slack
-    fm = FC.model(c)
-    if dec.font is not fm.font:
-        dec.set_font(fm.font, c.size)
-    grid = 1 + (c.index // 2) % 2 if c.index % 2 and mode in FC.WHOLE_MODES else 0  # several lines through one workgroup
-    assert dec._lib.focr_decoder_debug_set_whole_grid(dec._h, grid) == 0, (c.name, mode)
-    try:
-        res = dec.decode(c.pages, *c.geo, verify=verify, **kw)
-    finally:
-        assert dec._lib.focr_decoder_debug_set_whole_grid(dec._h, 0) == 0, (c.name, mode)
-    res = res if isinstance(res, tuple) else (res,)
-    names = ["lines"] + (["mse", "images"] if verify else []) + [n for n, on in (
-        ("scores", "scores" in kw), ("offsets", "pen_search" in kw), ("pens", "whole_line" in kw), ("costs", "whole_line" in kw),
-        ("margins", "margins" in kw), ("offsets", "pen_slack" in kw)) if on]
-    assert len(res) == len(names), (c.name, mode)
-    return dict(zip(names, res))
-
-
-def last_batch(c):
-    """The pages of the size group that decode() runs last, and whether that run has any line slot."""
-    shapes = list(dict.fromkeys(p.shape for p in c.pages))
-    idx = [i for i, p in enumerate(c.pages) if p.shape == shapes[-1]]
-    return idx, c.geo[3] > 0 and c.geo[1] < shapes[-1][0]
 
 
 def same(got, c, mode):
