@@ -11,7 +11,8 @@
 //   decode_text.hip            verify_text: a caller's lines drawn over their pages, each in any uploaded font
 //   decode_score.hip           score_text: the decoder's cost of a caller's lines, each in any uploaded font (over decode_pen.h)
 // (decode_line.h lies between decode.h and the files of a run; decode_line_frac.hip, decode_images.hip and decode_text.hip include decode.h alone.)
-// Below decode.h lies decode_font.h, host code alone: the record of an uploaded font (HostFont), the glyph and verify records the kernels
+// Below decode.h lie text_plan.h, host code alone (the input rules of a caller's reading and the record the device reads of a line), and
+// decode_font.h, host code alone: the record of an uploaded font (HostFont), the glyph and verify records the kernels
 // read, and the five font uploaders' checks and packing.  Here: the batch geometry, both line grids, the owners of the fonts' device tables, the tile frame of
 // the compose kernels (ncc_images.hip is its third user), the blank test's crop, the settings (Modes), what a run resolves
 // them to (RunMode), what the last run left (LastRun), the decoder itself, and the host plumbing every entry point repeats
@@ -27,6 +28,7 @@
 #include "decode_font.h"
 #include "devmem.h"
 #include "focr_decode.h"
+#include "text_plan.h"
 
 namespace focr_dec {
 
@@ -393,20 +395,25 @@ struct FontDesc {
     uint32_t batch, max_inc, inc_base;
 };
 
-// One line of focr_decoder_verify_text as the device reads it: the caller's line, and where its glyph records start (lines may
-// share characters, so the records are per line: a running sum of n over the list).
-struct TextLine {
-    uint32_t y, n, font, pad;
-    uint64_t first, rec;
+// The staged reading of a verify_text or score_text call (text_plan.h has its rules): its pages when they come from host memory, its
+// records, characters and pens or offsets.  One set serves both entry points: each call ends with a stream wait and keeps nothing
+// here between calls, so the arrays are idle when the next call, of either kind, grows and fills them.  They are apart from the
+// run's buffers (d_pages, d_chars, ...): a call leaves the last run, its getters and its verify as they were.
+struct TextStage {
+    focr::DevArray<uint8_t> pages;
+    focr::DevArray<TextRec> recs;
+    focr::DevArray<uint16_t> chars;
+    focr::DevArray<uint32_t> pens;
+    focr::DevArray<int8_t> offs;
 };
 
-// One line of focr_decoder_score_text as the device reads it: the caller's line, where its terms start (a running sum of n
-// over the list: lines may share characters) and its baseline candidate q (0 without line_q).
-struct ScoreLine {
-    uint32_t page, y, n, font;
-    uint64_t first, out;
-    int32_t q;
-    uint32_t pad;
+// ... and where one call's kernels read it (stage_text, below): pens and offs are null where the call gave none.
+struct StagedText {
+    const uint8_t *pages;
+    const TextRec *recs;
+    const uint16_t *chars;
+    const uint32_t *pens;
+    const int8_t *offs;
 };
 
 struct Stage {  // the kernels of one entry point's last call: device events around them, their time and their number
@@ -492,22 +499,15 @@ struct focr_decoder {
     focr::DevArray<uint32_t> d_tbase, d_trect, d_ttext, d_tflags;
     focr::DevArray<focr_dec::VerifyRec> d_trecs;
     focr::DevArray<focr_dec::VerifyLine> d_tline;
-    // verify_text (decode_text.hip): buffers of its own, so that a call leaves the last run and its verify as they were
-    focr::DevArray<uint8_t> d_xpages, d_xrgb;
-    focr::DevArray<focr_dec::TextLine> d_xlines;
-    focr::DevArray<uint32_t> d_xfirst, d_xpens;
-    focr::DevArray<uint16_t> d_xchars;
-    focr::DevArray<int8_t> d_xoffs;
+    // verify_text (decode_text.hip) and score_text (decode_score.hip): the staged reading both share, and buffers of each one's
+    // own beside it (d_sstrips only when a line's strip does not fit in LDS), so that a call leaves the last run and its verify as they were
+    focr_dec::TextStage text;
+    focr::DevArray<uint8_t> d_xrgb, d_sstrips;
+    focr::DevArray<uint32_t> d_xfirst;
     focr::DevArray<focr_dec::VerifyLine> d_xvlines;
     focr::DevArray<focr_dec::VerifyRec> d_xrecs;
     focr::DevArray<unsigned long long> d_xsums;
-    // score_text (decode_score.hip): buffers of its own as well; d_sstrips only when a line's strip does not fit in LDS
-    focr::DevArray<uint8_t> d_spages, d_sstrips;
-    focr::DevArray<focr_dec::ScoreLine> d_slines;
     focr::DevArray<focr_text_score_t> d_sout;
-    focr::DevArray<uint16_t> d_schars;
-    focr::DevArray<uint32_t> d_spens;
-    focr::DevArray<int8_t> d_soffs;
     focr::DevArray<focr_dec::FontDesc> d_sdesc;
     focr::DevArray<int32_t> d_sterms;
 };
@@ -571,6 +571,30 @@ int stage_out(focr_decoder *dec, focr::DevArray<T> &a, void *dst, int on_device,
 template <typename T>
 int fetch_out(focr_decoder *dec, void *dst, int on_device, const T *d, size_t n) {
     if (dst && !on_device) DEC_CHECK(hipMemcpyAsync(dst, d, n * sizeof(T), hipMemcpyDeviceToHost, dec->stream));
+    return 0;
+}
+
+// A call's reading where its kernels read it: n_px page bytes through stage_in, the plan's records and the caller's characters,
+// pens and offsets into dec->text, the copies queued on the decoder's stream.  What the call did not give is null in *out, whatever
+// an earlier call left in the arrays.
+inline int stage_text(focr_decoder *dec, const TextInput &in, const std::vector<TextRec> &recs, const uint8_t *pages, int pages_on_device, size_t n_px,
+                      StagedText *out) {
+    TextStage &t = dec->text;
+    *out = StagedText{nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (stage_in(dec, t.pages, pages, pages_on_device, n_px, &out->pages)) return 1;
+    const size_t n_chars = std::max<size_t>(in.n_chars, 1);
+    DEC_GROW(t.recs, std::max<size_t>(recs.size(), 1));
+    DEC_GROW(t.chars, n_chars);
+    if (in.pens) DEC_GROW(t.pens, n_chars);
+    if (in.offsets) DEC_GROW(t.offs, n_chars);
+    if (!recs.empty()) DEC_CHECK(hipMemcpyAsync(t.recs, recs.data(), recs.size() * sizeof(TextRec), hipMemcpyHostToDevice, dec->stream));
+    if (in.n_chars) DEC_CHECK(hipMemcpyAsync(t.chars, in.chars, in.n_chars * sizeof(uint16_t), hipMemcpyHostToDevice, dec->stream));
+    if (in.pens && in.n_chars) DEC_CHECK(hipMemcpyAsync(t.pens, in.pens, in.n_chars * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
+    if (in.offsets && in.n_chars) DEC_CHECK(hipMemcpyAsync(t.offs, in.offsets, in.n_chars, hipMemcpyHostToDevice, dec->stream));
+    out->recs = t.recs;
+    out->chars = t.chars;
+    if (in.pens) out->pens = t.pens;
+    if (in.offsets) out->offs = t.offs;
     return 0;
 }
 

@@ -16,7 +16,8 @@
 //   - the winner's terms are computed once more by all four waves, 64 characters a wave, and written once; with one
 //     candidate (N = 0) that pass is the only one.
 // Fonts are read as the font search reads them (a FontDesc per font 0 ..= K), y-phases as the baseline search does (the
-// tables of focr_decoder_set_baseline_fonts, v-major).  Everything is exact integer arithmetic but the f32 pen.
+// tables of focr_decoder_set_baseline_fonts, v-major).  Everything is exact integer arithmetic but the f32 pen.  The reading is
+// checked by text_plan.h and staged by stage_text (decode.h), as focr_decoder_verify_text's is.
 #include "decode_pen.h"
 
 namespace focr_dec {
@@ -75,16 +76,16 @@ __device__ __forceinline__ uint64_t score_stage(uint32_t *dst, const uint8_t *__
 }
 
 // A line's crop as image::crop_imm clamps it: its first pixel and its rows (0 when the crop is empty either way).
-__device__ __forceinline__ const uint8_t *score_crop(const uint8_t *__restrict__ pages, const Geometry &g, const ScoreLine &l, uint32_t *h) {
+__device__ __forceinline__ const uint8_t *score_crop(const uint8_t *__restrict__ pages, const Geometry &g, const TextRec &l, uint32_t *h) {
     const uint32_t yc = std::min(l.y, g.page_h);
     *h = g.w ? std::min(g.line_height, g.page_h - yc) : 0;
     return pages + (size_t)l.page * g.page_w * g.page_h + (size_t)yc * g.page_w + g.x;
 }
 
 // 1. (only when the strip does not fit in LDS) every listed line's strip into global memory, one workgroup per line
-__global__ __launch_bounds__(SCORE_THREADS) void score_strip_kernel(const uint8_t *__restrict__ pages, Geometry g, const ScoreLine *__restrict__ in,
+__global__ __launch_bounds__(SCORE_THREADS) void score_strip_kernel(const uint8_t *__restrict__ pages, Geometry g, const TextRec *__restrict__ in,
                                                                     uint8_t *__restrict__ strips) {
-    const ScoreLine l = in[blockIdx.x];
+    const TextRec l = in[blockIdx.x];
     uint32_t h;
     const uint8_t *src = score_crop(pages, g, l, &h);
     (void)score_stage((uint32_t *)(strips + (size_t)blockIdx.x * g.stride * g.line_height), src, g.page_w, g.w, h, g.stride / 4);
@@ -134,7 +135,7 @@ __device__ __forceinline__ int64_t score_line(const uint32_t *strip, uint32_t sd
 
 // 2. the lines' costs, one workgroup per listed line
 template <bool LDS>
-__global__ __launch_bounds__(SCORE_THREADS) void score_text_kernel(const uint8_t *__restrict__ pages, Geometry g, const ScoreLine *__restrict__ in,
+__global__ __launch_bounds__(SCORE_THREADS) void score_text_kernel(const uint8_t *__restrict__ pages, Geometry g, const TextRec *__restrict__ in,
                                                                    const uint16_t *__restrict__ chars, const uint32_t *__restrict__ pens,
                                                                    const int8_t *__restrict__ offs, ScoreFonts fonts, uint32_t radius,
                                                                    const uint8_t *__restrict__ strips, int32_t *__restrict__ terms,
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_text_kernel(const uint8_t
     uint64_t *red = (uint64_t *)lds_score;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));  // uniform, and the compiler knows it
-    const ScoreLine l = in[blockIdx.x];
+    const TextRec l = in[blockIdx.x];
     const uint32_t sdw = g.stride / 4;
     uint32_t h;
     const uint8_t *src = score_crop(pages, g, l, &h);
@@ -218,11 +219,9 @@ extern "C" int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages
     if (!dec) return dfail(nullptr, who + "null decoder");
     dec->stext.ms = 0.f;
     dec->stext.launches = 0;
-    if (n_pages && !pages) return dfail(dec, who + "null pages");
-    if (n_lines && !lines) return dfail(dec, who + "null lines");
-    if (n_chars && !chars) return dfail(dec, who + "null chars");
-    if (n_lines && !out) return dfail(dec, who + "null out");
-    if (pens && offsets) return dfail(dec, who + "pens and offsets together (a character is placed by its pen or by its offset)");
+    const TextInput in{lines, n_lines, chars, pens, offsets, n_chars, n_pages};
+    std::string no = text_guards(in, pages, n_lines && !out ? "out" : nullptr);
+    if (!no.empty()) return dfail(dec, who + no);
     if (!dec->n_glyphs) return dfail(dec, who + "no decode font (focr_decoder_set_font)");
     if (width == 0) return dfail(dec, who + "width 0");
     if (line_height == 0) return dfail(dec, who + "line_height 0");
@@ -233,29 +232,13 @@ extern "C" int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages
     if (n_lines > 0x7fffffffu || n_pages > 0x7fffffffu) return dfail(dec, who + "too many lines or pages in one call");
     if (line_q && y_bits && !(dec->yfonts.ok && dec->yfonts.bits == y_bits))
         return dfail(dec, who + "line_q with y_bits > 0 needs the y-phase fonts of that y_bits (focr_decoder_set_baseline_fonts)");
-    const size_t K = dec->cands.size();
-    std::vector<ScoreLine> in(n_lines);
-    uint64_t n_terms = 0;
-    for (size_t l = 0; l < n_lines; l++) {
-        const focr_text_line_t &s = lines[l];
-        const std::string pre = who + "line " + std::to_string(l) + ": ";
-        if (s.font > K) return dfail(dec, pre + "font " + std::to_string(s.font) + " with " + std::to_string(K) + " candidates uploaded (focr_decoder_set_font_candidates)");
-        if (s.page >= n_pages) return dfail(dec, pre + "page " + std::to_string(s.page) + " of " + std::to_string(n_pages));
-        if (s.first > n_chars || s.n_chars > n_chars - s.first) return dfail(dec, pre + "its characters end past n_chars");
-        if (pens && !whole_origin(dec->font_at(s.font).origin_x))
-            return dfail(dec, pre + "pens need its font's origin_x to be a whole number >= 0 (at most 65536)");
-        const int q = line_q ? line_q[l] : 0;
-        if (line_q && s.font && (q & ((1 << y_bits) - 1)))
-            return dfail(dec, pre + "a fractional-phase q in a candidate font (the candidates have one vertical phase)");
-        if (line_q && !whole_origin(dec->font_at(s.font).origin_y)) return dfail(dec, pre + "line_q needs its font's origin_y to be a whole number >= 0");
-        in[l] = ScoreLine{s.page, s.y, s.n_chars, s.font, s.first, n_terms, q, 0};
-        n_terms += s.n_chars;
-    }
-    if (n_terms > 0xffffffffull) return dfail(dec, who + "too many characters in one call");
-    for (size_t i = 0; i < n_chars; i++)
-        if (chars[i] >= dec->n_glyphs) return dfail(dec, who + "character " + std::to_string(i) + " is not an index into the alphabet");
-    for (size_t i = 0; pens && i < n_chars; i++)
-        if (pens[i] >= (1u << 24)) return dfail(dec, who + "pen " + std::to_string(i) + " is 2^24 or more (pens must stay exact in f32)");
+    TextAsk ask;
+    ask.line_q = line_q;
+    ask.y_bits = y_bits;
+    ask.pen_origin = true;
+    TextPlan text;
+    if (!(no = plan_text_lines(in, dec->font, dec->cands, ask, &text)).empty() || !(no = plan_text_chars(in, dec->n_glyphs)).empty()) return dfail(dec, who + no);
+    const uint64_t n_terms = text.n_out;
     if (n_lines == 0) return 0;
     g.line_height = line_height;
     g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;  // line_cap's
@@ -265,36 +248,26 @@ extern "C" int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages
     if (fonts_plan(dec, &plan)) return 1;  // the descriptors of the fonts 0 ..= K
     for (size_t k = 0; k < plan.fonts.size(); k++) plan.fonts[k].origin_d = whole_origin(plan.fonts[k].origin_x) ? 64 * (int)plan.fonts[k].origin_x : 0;
     DEC_CHECK(hipSetDevice(dec->device));
-    const uint8_t *d_src = nullptr;
-    if (stage_in(dec, dec->d_spages, pages, pages_on_device, n_pages * page_w * page_h, &d_src)) return 1;
-    DEC_GROW(dec->d_slines, n_lines);
-    DEC_GROW(dec->d_schars, std::max<size_t>(n_chars, 1));
-    if (pens) DEC_GROW(dec->d_spens, std::max<size_t>(n_chars, 1));
-    if (offsets) DEC_GROW(dec->d_soffs, std::max<size_t>(n_chars, 1));
+    StagedText st;
+    if (stage_text(dec, in, text.recs, pages, pages_on_device, n_pages * page_w * page_h, &st)) return 1;
     DEC_GROW(dec->d_sdesc, plan.fonts.size());
     if (terms) DEC_GROW(dec->d_sterms, std::max<size_t>(n_terms, 1));
     DEC_GROW(dec->d_sout, n_lines);
     if (!lds) DEC_GROW(dec->d_sstrips, strip_bytes * n_lines);
-    DEC_CHECK(hipMemcpyAsync(dec->d_slines, in.data(), n_lines * sizeof(ScoreLine), hipMemcpyHostToDevice, dec->stream));
-    if (n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_schars, chars, n_chars * sizeof(uint16_t), hipMemcpyHostToDevice, dec->stream));
-    if (pens && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_spens, pens, n_chars * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
-    if (offsets && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_soffs, offsets, n_chars, hipMemcpyHostToDevice, dec->stream));
     DEC_CHECK(hipMemcpyAsync(dec->d_sdesc, plan.fonts.data(), plan.fonts.size() * sizeof(FontDesc), hipMemcpyHostToDevice, dec->stream));
     const GlyphTables &t = dec->tables, &c = dec->ftables, &y = dec->yfonts.tables;
     const ScoreFonts f{t.glyphs, c.glyphs, y.glyphs, t.offs, c.offs, y.offs, t.bitmaps.as<const uint32_t>(), c.bitmaps.as<const uint32_t>(),
                        y.bitmaps.as<const uint32_t>(), dec->d_sdesc, dec->n_glyphs, y.n_dw, line_q ? y_bits : 0};
-    const uint32_t *d_pens = pens ? (const uint32_t *)dec->d_spens : nullptr;
-    const int8_t *d_offs = offsets ? (const int8_t *)dec->d_soffs : nullptr;
     int32_t *d_terms = terms ? (int32_t *)dec->d_sterms : nullptr;
     DEC_CHECK(hipEventRecord(dec->stext.begin, dec->stream));
     if (lds) {
         score_text_kernel<true><<<(uint32_t)n_lines, SCORE_THREADS, SCORE_RED_BYTES + strip_bytes, dec->stream>>>(
-            d_src, g, dec->d_slines, dec->d_schars, d_pens, d_offs, f, shift_radius, nullptr, d_terms, dec->d_sout);
+            st.pages, g, st.recs, st.chars, st.pens, st.offs, f, shift_radius, nullptr, d_terms, dec->d_sout);
     } else {
-        score_strip_kernel<<<(uint32_t)n_lines, SCORE_THREADS, 0, dec->stream>>>(d_src, g, dec->d_slines, dec->d_sstrips);
+        score_strip_kernel<<<(uint32_t)n_lines, SCORE_THREADS, 0, dec->stream>>>(st.pages, g, st.recs, dec->d_sstrips);
         DEC_CHECK(hipGetLastError());
         score_text_kernel<false><<<(uint32_t)n_lines, SCORE_THREADS, SCORE_RED_BYTES, dec->stream>>>(
-            d_src, g, dec->d_slines, dec->d_schars, d_pens, d_offs, f, shift_radius, dec->d_sstrips, d_terms, dec->d_sout);
+            st.pages, g, st.recs, st.chars, st.pens, st.offs, f, shift_radius, dec->d_sstrips, d_terms, dec->d_sout);
     }
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->stext.end, dec->stream));

@@ -3,7 +3,8 @@
 // the font search (1 ..= K).  What a font search decoded, or a reading somebody corrected, is drawn with it; focr_decoder_verify
 // (decode_images.hip) draws only what the last run itself decoded, in the decode font.
 //
-// Two launches, over the tile frame of decode.h and in buffers of the call's own:
+// The reading is checked by text_plan.h and staged by stage_text (decode.h), both shared with focr_decoder_score_text.  Two launches, over
+// the tile frame of decode.h and in buffers apart from the run's:
 //   1. verify_layout_text_kernel: one wave per listed line runs layout_line (decode.h) with the line's own y and the glyph,
 //      box and phase tables of the line's font (the candidates' lie k-major behind a per-font base, as their glyph records do), and
 //      writes the line's glyph records and its clipped canvas, which carries the font; blocks below n_pages also zero the sums;
@@ -35,24 +36,24 @@ struct TextFonts {
 // 1. render()'s layout of every listed line, one wave per line; blocks below n_pages also zero the sums.  g carries the
 // page's size and one slot (layout_line reads the line's row from the grid policy).
 __global__ __launch_bounds__(64) void verify_layout_text_kernel(Geometry g, uint32_t n_pages, uint32_t n_lines, uint32_t x_start,
-                                                                const TextLine *__restrict__ in, const uint16_t *__restrict__ chars,
+                                                                const TextRec *__restrict__ in, const uint16_t *__restrict__ chars,
                                                                 const int8_t *__restrict__ offs, const uint32_t *__restrict__ pens, TextFonts f,
                                                                 VerifyLine *__restrict__ lines, VerifyRec *__restrict__ recs,
                                                                 unsigned long long *__restrict__ sums) {
     const uint32_t b = blockIdx.x, lane = threadIdx.x;
     if (b < n_pages && lane == 0) sums[b] = 0;
     if (b >= n_lines) return;
-    const TextLine l = in[b];
+    const TextRec l = in[b];
     const size_t at = l.font ? (size_t)(l.font - 1) * f.n_glyphs : 0;  // uniform: the per-font base of the k-major tables
     layout_line<false>(g, 0, chars + l.first, offs ? offs + l.first : nullptr, pens ? pens + l.first : nullptr, 0, l.n, l.font, x_start,
                        l.font ? f.fglyphs + at : f.glyphs, l.font ? f.fvglyphs + at : f.vglyphs,
-                       l.font ? f.fvphases + at * FOCR_DECODE_PHASES : f.vphases, recs + l.rec, lines + b, OwnRow{(int64_t)l.y});
+                       l.font ? f.fvphases + at * FOCR_DECODE_PHASES : f.vphases, recs + l.out, lines + b, OwnRow{(int64_t)l.y});
 }
 
 // 2. compose the image tile by tile; every thread owns one column of a 16-row, 256-column tile
 __global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_text_kernel(const uint8_t *__restrict__ pages, uint32_t page_w, uint32_t page_h,
                                                                             uint32_t n_pages, uint32_t tiles_x, uint32_t tiles_y,
-                                                                            const uint32_t *__restrict__ page_first, const TextLine *__restrict__ in,
+                                                                            const uint32_t *__restrict__ page_first, const TextRec *__restrict__ in,
                                                                             const VerifyLine *__restrict__ lines, const VerifyRec *__restrict__ recs,
                                                                             const uint8_t *__restrict__ bitmaps, const uint8_t *__restrict__ fbitmaps,
                                                                             uint8_t *__restrict__ rgb, unsigned long long *__restrict__ sums) {
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(VERIFY_TILE_W) void verify_compose_text_kernel(cons
         for (uint32_t i = i_lo; i < i_hi; i++) {
             const VerifyLine l = lines[i];
             if (l.n == 0 || l.x0 >= c1 || l.x1 <= c0 || l.y0 >= r1 || l.y1 <= r0) continue;  // uniform across the workgroup
-            const VerifyRec *lr = recs + in[i].rec;
+            const VerifyRec *lr = recs + in[i].out;
             const uint8_t *bm = l.k ? fbitmaps : bitmaps;  // per line (l.k is its font), not per pixel
             mark_glyphs(win, lr, l.n, T, lane, wave);
             __syncthreads();
@@ -135,72 +136,42 @@ extern "C" int focr_decoder_verify_text(focr_decoder_t *dec, const uint8_t *page
     if (!dec) return dfail(nullptr, who + "null decoder");
     dec->vtext.ms = 0.f;
     dec->vtext.launches = 0;
-    if (n_pages && !pages) return dfail(dec, who + "null pages");
-    if (n_lines && !lines) return dfail(dec, who + "null lines");
-    if (n_chars && !chars) return dfail(dec, who + "null chars");
-    if (n_pages && !sq_sums) return dfail(dec, who + "null sq_sums");
-    if (pens && offsets) return dfail(dec, who + "pens and offsets together (a character is placed by its pen or by its offset)");
+    const TextInput in{lines, n_lines, chars, pens, offsets, n_chars, n_pages};
+    std::string no = text_guards(in, pages, n_pages && !sq_sums ? "sq_sums" : nullptr);
+    if (!no.empty()) return dfail(dec, who + no);
     if (!dec->n_glyphs) return dfail(dec, who + "no decode font (focr_decoder_set_font)");
     Geometry g{};
     if (batch_geometry(dec, "focr_decoder_verify_text", n_pages, page_w, page_h, x_start, 0, 0, 0, 1, &g)) return 1;
     if (n_lines > 0x7fffffffu || n_pages > 0x7fffffffu) return dfail(dec, who + "too many lines or pages in one call");
-    const size_t K = dec->cands.size();
-    std::vector<TextLine> in(n_lines);
-    std::vector<uint32_t> page_first(n_pages + 1, 0);
-    uint64_t n_recs = 0;
-    bool decode_font = false, candidates = false;
-    for (size_t l = 0; l < n_lines; l++) {
-        const focr_text_line_t &s = lines[l];
-        const std::string pre = who + "line " + std::to_string(l) + ": ";
-        if (s.font > K) return dfail(dec, pre + "font " + std::to_string(s.font) + " with " + std::to_string(K) + " candidates uploaded (focr_decoder_set_font_candidates)");
-        if (s.page >= n_pages) return dfail(dec, pre + "page " + std::to_string(s.page) + " of " + std::to_string(n_pages));
-        if (l && s.page < lines[l - 1].page) return dfail(dec, pre + "its page lies before the previous line's (lines come in page order)");
-        if (s.first > n_chars || s.n_chars > n_chars - s.first) return dfail(dec, pre + "its characters end past n_chars");
-        (s.font ? candidates : decode_font) = true;
-        in[l] = TextLine{s.y, s.n_chars, s.font, 0, s.first, n_recs};
-        n_recs += s.n_chars;
-        page_first[s.page + 1] = (uint32_t)(l + 1);
-    }
-    for (size_t p = 1; p <= n_pages; p++) page_first[p] = std::max(page_first[p], page_first[p - 1]);  // a page without lines: an empty range
-    if (n_recs > 0xffffffffull) return dfail(dec, who + "too many characters in one call");
-    if (decode_font && !dec->vtables.ok) return dfail(dec, who + "a line in font 0 and no verify table of the decode font (focr_decoder_set_verify_font)");
-    if (candidates && !dec->fvtables.ok)
+    TextAsk ask;
+    ask.page_order = true;
+    TextPlan plan;
+    if (!(no = plan_text_lines(in, dec->font, dec->cands, ask, &plan)).empty()) return dfail(dec, who + no);
+    if (plan.decode_font && !dec->vtables.ok) return dfail(dec, who + "a line in font 0 and no verify table of the decode font (focr_decoder_set_verify_font)");
+    if (plan.candidates && !dec->fvtables.ok)
         return dfail(dec, who + "a line in a candidate font and no verify tables of the candidates (focr_decoder_set_verify_font_candidates)");
-    for (size_t i = 0; i < n_chars; i++)
-        if (chars[i] >= dec->n_glyphs) return dfail(dec, who + "character " + std::to_string(i) + " is not an index into the alphabet");
-    for (size_t i = 0; pens && i < n_chars; i++)
-        if (pens[i] >= (1u << 24)) return dfail(dec, who + "pen " + std::to_string(i) + " is 2^24 or more (pens must stay exact in f32)");
+    if (!(no = plan_text_chars(in, dec->n_glyphs)).empty()) return dfail(dec, who + no);
     if (n_pages == 0) return 0;
     g.n_slots = 1;  // layout_line's slot 0; the line's row is its own y
     const size_t px = n_pages * page_w * page_h;
     const TileGrid tg = tile_grid(n_pages, page_w, page_h);
     const size_t layout_blocks = std::max(n_lines, n_pages);
     DEC_CHECK(hipSetDevice(dec->device));
-    const uint8_t *d_src = nullptr;
+    StagedText t;
     uint8_t *d_rgb = nullptr;
-    if (stage_in(dec, dec->d_xpages, pages, pages_on_device, px, &d_src) || stage_out(dec, dec->d_xrgb, rgb, rgb_on_device, px * 3, &d_rgb)) return 1;
-    DEC_GROW(dec->d_xlines, std::max<size_t>(n_lines, 1));
+    if (stage_text(dec, in, plan.recs, pages, pages_on_device, px, &t) || stage_out(dec, dec->d_xrgb, rgb, rgb_on_device, px * 3, &d_rgb)) return 1;
     DEC_GROW(dec->d_xfirst, n_pages + 1);
-    DEC_GROW(dec->d_xchars, std::max<size_t>(n_chars, 1));
-    if (pens) DEC_GROW(dec->d_xpens, std::max<size_t>(n_chars, 1));
-    if (offsets) DEC_GROW(dec->d_xoffs, std::max<size_t>(n_chars, 1));
     DEC_GROW(dec->d_xvlines, std::max<size_t>(n_lines, 1));
-    DEC_GROW(dec->d_xrecs, std::max<size_t>(n_recs, 1));
+    DEC_GROW(dec->d_xrecs, std::max<size_t>(plan.n_out, 1));
     DEC_GROW(dec->d_xsums, n_pages);
-    if (n_lines) DEC_CHECK(hipMemcpyAsync(dec->d_xlines, in.data(), n_lines * sizeof(TextLine), hipMemcpyHostToDevice, dec->stream));
-    DEC_CHECK(hipMemcpyAsync(dec->d_xfirst, page_first.data(), (n_pages + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
-    if (n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_xchars, chars, n_chars * sizeof(uint16_t), hipMemcpyHostToDevice, dec->stream));
-    if (pens && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_xpens, pens, n_chars * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
-    if (offsets && n_chars) DEC_CHECK(hipMemcpyAsync(dec->d_xoffs, offsets, n_chars, hipMemcpyHostToDevice, dec->stream));
+    DEC_CHECK(hipMemcpyAsync(dec->d_xfirst, plan.page_first.data(), (n_pages + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, dec->stream));
     const TextFonts f{dec->tables.glyphs, dec->ftables.glyphs, dec->vtables.glyphs, dec->fvtables.glyphs, dec->vtables.phases, dec->fvtables.phases, dec->n_glyphs};
     DEC_CHECK(hipEventRecord(dec->vtext.begin, dec->stream));
-    verify_layout_text_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, (uint32_t)n_lines, x_start, dec->d_xlines, dec->d_xchars,
-                                                                              offsets ? (const int8_t *)dec->d_xoffs : nullptr,
-                                                                              pens ? (const uint32_t *)dec->d_xpens : nullptr, f, dec->d_xvlines,
-                                                                              dec->d_xrecs, dec->d_xsums);
+    verify_layout_text_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, (uint32_t)n_lines, x_start, t.recs, t.chars, t.offs, t.pens, f,
+                                                                              dec->d_xvlines, dec->d_xrecs, dec->d_xsums);
     DEC_CHECK(hipGetLastError());
-    verify_compose_text_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(d_src, g.page_w, g.page_h, (uint32_t)n_pages, tg.tiles_x, tg.tiles_y, dec->d_xfirst,
-                                                                           dec->d_xlines, dec->d_xvlines, dec->d_xrecs, (const uint8_t *)dec->tables.bitmaps,
+    verify_compose_text_kernel<<<tg.grid, VERIFY_TILE_W, 0, dec->stream>>>(t.pages, g.page_w, g.page_h, (uint32_t)n_pages, tg.tiles_x, tg.tiles_y, dec->d_xfirst, t.recs,
+                                                                           dec->d_xvlines, dec->d_xrecs, (const uint8_t *)dec->tables.bitmaps,
                                                                            (const uint8_t *)dec->ftables.bitmaps, d_rgb, dec->d_xsums);
     DEC_CHECK(hipGetLastError());
     DEC_CHECK(hipEventRecord(dec->vtext.end, dec->stream));

@@ -157,6 +157,28 @@ def render_text(font_path, text_size, text, kerning=1.0, hinting=False):
     return out[: w.value * h.value].reshape(h.value, w.value)
 
 
+def _page_list(luma_pages):
+    """One (H, W) page, an (N, H, W) batch or a sequence of pages, as a list of pages."""
+    if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
+        return [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
+    return list(luma_pages)
+
+
+def _size_groups(pages):
+    """The pages grouped by size, in the order each size first appears: ((h, w), idx, batch) with the pages idx stacked into one
+    contiguous batch."""
+    by_size = {}
+    for i, p in enumerate(pages):
+        by_size.setdefault(np.asarray(p).shape, []).append(i)
+    for shape, idx in by_size.items():
+        yield shape, idx, np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
+
+
+def _ptr(a, empty=False):
+    """The address of an array for the library; None for no array and, unless `empty`, for an array without elements."""
+    return C.c_void_p(a.ctypes.data) if a is not None and (empty or a.size) else None
+
+
 def _check_verify(verify):
     if verify not in (None, "mse", "image"):
         raise ValueError(f"verify must be None, 'mse' or 'image', not {verify!r}")
@@ -364,62 +386,36 @@ class LineDecoder:
             raise DecoderError("set_font() first")
         if pens is not None and offsets is not None:
             raise ValueError("verify_text takes pens or offsets, not both")
-        if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
-            pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
-        else:
-            pages = list(luma_pages)
-        lines = [list(pg) for pg in lines]
-        if len(lines) != len(pages):
-            raise ValueError(f"lines must hold one list per page: {len(lines)} for {len(pages)} pages")
-        for name, per in (("fonts", fonts), ("pens", pens), ("offsets", offsets)):
-            if per is not None and (len(per) != len(pages) or any(len(a) != len(b) for a, b in zip(per, lines))):
-                raise ValueError(f"{name} must hold one entry per line of lines")
-        index = {c: i for i, c in reversed(list(enumerate(self.font.alphabet)))}  # the first of equal characters
-        used = {int(k) for pg in fonts for k in pg} if fonts is not None else {0}
-        if not lines or not any(lines):
-            used = set()
-        if any(k < 0 or k > len(self._candidates) for k in used):
-            raise ValueError(f"fonts must be 0 .. {len(self._candidates)} (the decode font and the candidates of set_font_candidates)")
+        pages, lines, used, groups = self._pack_text("verify_text", luma_pages, lines, fonts, pens, offsets)
+        if fonts is None and any(lines):
+            used = {0}
         if 0 in used:
             self._ensure_verify_font()
         if used - {0}:
             self._ensure_verify_candidates()
         sums = np.zeros(len(pages), dtype=np.uint64)
         out = [None] * len(pages) if images else None
-        by_size = {}
-        for i, p in enumerate(pages):
-            by_size.setdefault(np.asarray(p).shape, []).append(i)
-        for (h, w), idx in by_size.items():
-            batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
-            recs, chars, along = [], [], []
-            for j, i in enumerate(idx):
-                for q, (ly, text) in enumerate(lines[i]):
-                    try:
-                        cs = [index[c] for c in text]
-                    except KeyError as e:
-                        raise ValueError(f"verify_text: {e.args[0]!r} (page {i}, line {q}) is not in the alphabet") from None
-                    recs.append((j, int(ly), len(chars), len(cs), int(fonts[i][q]) if fonts is not None else 0))
-                    chars.extend(cs)
-                    per = pens if pens is not None else offsets
-                    if per is not None:
-                        if len(per[i][q]) != len(cs):
-                            raise ValueError(f"verify_text: page {i}, line {q}: {len(per[i][q])} pens or offsets for {len(cs)} characters")
-                        along.extend(int(v) for v in per[i][q])
-            larr = (N.TextLine * max(1, len(recs)))(*recs)
-            carr = np.array(chars, dtype=np.uint16) if chars else np.zeros(1, dtype=np.uint16)
-            parr = np.array(along, dtype=np.uint32) if pens is not None and along else None
-            oarr = np.array(along, dtype=np.int8) if offsets is not None and along else None
-            got = np.zeros(len(idx), dtype=np.uint64)
-            rgb = np.empty((len(idx), h, w, 3), dtype=np.uint8) if images else None
-            ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None  # noqa: E731
-            self._check(self._lib.focr_decoder_verify_text(self._h, ptr(batch), 0, len(idx), w, h, int(x), larr, len(recs), ptr(carr), ptr(parr),
-                                                           ptr(oarr), len(chars), ptr(rgb), 0, got.ctypes.data))
-            self.last_verify_text_ms = float(self._lib.focr_decoder_last_verify_text_ms(self._h))
+        for idx, batch, recs, chars, along, _, _ in groups:
+            got, rgb = self._verify_text(batch, recs, chars, along if pens is not None else None, along if offsets is not None else None, x, images)
             for j, i in enumerate(idx):
                 sums[i] = got[j]
                 if images:
                     out[i] = rgb[j]
         return sums, out
+
+    def _verify_text(self, batch, recs, chars, pens, offsets, x, images):
+        """One focr_decoder_verify_text call over an (N, H, W) uint8 batch, its arguments as _score_text's: (sums, images or None)."""
+        n, h, w = batch.shape
+        larr = (N.TextLine * max(1, len(recs)))(*recs)
+        carr = np.array(chars, dtype=np.uint16) if chars else np.zeros(1, dtype=np.uint16)
+        parr = np.array(pens, dtype=np.uint32) if pens else None
+        oarr = np.array(offsets, dtype=np.int8) if offsets else None
+        got = np.zeros(n, dtype=np.uint64)
+        rgb = np.empty((n, h, w, 3), dtype=np.uint8) if images else None
+        self._check(self._lib.focr_decoder_verify_text(self._h, _ptr(batch), 0, n, w, h, int(x), larr, len(recs), _ptr(carr), _ptr(parr), _ptr(oarr),
+                                                       len(chars), _ptr(rgb), 0, got.ctypes.data))
+        self.last_verify_text_ms = float(self._lib.focr_decoder_last_verify_text_ms(self._h))
+        return got, rgb
 
     def score_text(self, luma_pages, lines, x, width, line_height, fonts=None, pens=None, offsets=None, baselines=None, y_bits=0, shift=0,
                    terms=True):
@@ -444,43 +440,9 @@ class LineDecoder:
             raise ValueError(f"y_bits must be 0 .. 3, not {y_bits!r}")
         if int(width) <= 0 or int(line_height) <= 0:
             raise ValueError("score_text: width and line_height must be positive")
-        if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
-            pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
-        else:
-            pages = list(luma_pages)
-        lines = [list(pg) for pg in lines]
-        if len(lines) != len(pages):
-            raise ValueError(f"lines must hold one list per page: {len(lines)} for {len(pages)} pages")
-        for name, per in (("fonts", fonts), ("pens", pens), ("offsets", offsets), ("baselines", baselines)):
-            if per is not None and (len(per) != len(pages) or any(len(a) != len(b) for a, b in zip(per, lines))):
-                raise ValueError(f"{name} must hold one entry per line of lines")
-        used = {int(k) for pg in fonts for k in pg} if fonts is not None else set()
-        if any(k < 0 or k > len(self._candidates) for k in used):
-            raise ValueError(f"fonts must be 0 .. {len(self._candidates)} (the decode font and the candidates of set_font_candidates)")
-        index = {c: i for i, c in reversed(list(enumerate(self.font.alphabet)))}  # the first of equal characters
+        _, lines, _, groups = self._pack_text("score_text", luma_pages, lines, fonts, pens, offsets, baselines)
         out = [[None] * len(pg) for pg in lines]
-        by_size = {}
-        for i, p in enumerate(pages):
-            by_size.setdefault(np.asarray(p).shape, []).append(i)
-        for (h, w), idx in by_size.items():
-            batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
-            recs, chars, along, qs, where = [], [], [], [], []
-            for j, i in enumerate(idx):
-                for q, (ly, text) in enumerate(lines[i]):
-                    try:
-                        cs = [index[c] for c in text]
-                    except KeyError as e:
-                        raise ValueError(f"score_text: {e.args[0]!r} (page {i}, line {q}) is not in the alphabet") from None
-                    recs.append((j, int(ly), len(chars), len(cs), int(fonts[i][q]) if fonts is not None else 0))
-                    where.append((i, q))
-                    chars.extend(cs)
-                    if baselines is not None:
-                        qs.append(int(baselines[i][q]))
-                    per = pens if pens is not None else offsets
-                    if per is not None:
-                        if len(per[i][q]) != len(cs):
-                            raise ValueError(f"score_text: page {i}, line {q}: {len(per[i][q])} pens or offsets for {len(cs)} characters")
-                        along.extend(int(v) for v in per[i][q])
+        for _, batch, recs, chars, along, qs, where in groups:
             got = self._score_text(batch, recs, chars, along if pens is not None else None, along if offsets is not None else None,
                                    qs if baselines is not None else None, x, width, line_height, y_bits, shift, terms)
             for (i, q), score in zip(where, got):
@@ -499,15 +461,54 @@ class LineDecoder:
         n_terms = sum(r[3] for r in recs)
         tarr = np.zeros(max(1, n_terms), dtype=np.int32) if terms else None
         sarr = (N.TextScoreStruct * max(1, len(recs)))()
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None  # noqa: E731
-        self._check(self._lib.focr_decoder_score_text(self._h, ptr(batch), 0, n, w, h, int(x), int(width), int(line_height), larr, len(recs), ptr(carr),
-                                                      ptr(parr), ptr(oarr), len(chars), ptr(qarr), int(y_bits), int(shift), ptr(tarr), sarr))
+        self._check(self._lib.focr_decoder_score_text(self._h, _ptr(batch), 0, n, w, h, int(x), int(width), int(line_height), larr, len(recs), _ptr(carr),
+                                                      _ptr(parr), _ptr(oarr), len(chars), _ptr(qarr), int(y_bits), int(shift), _ptr(tarr), sarr))
         self.last_score_text_ms = float(self._lib.focr_decoder_last_score_text_ms(self._h))
         out, at = [], 0
         for r, s in zip(recs, sarr):
             out.append(TextScore(int(s.line_base), int(s.cost), int(s.shift), tarr[at: at + r[3]].copy() if terms else None))
             at += r[3]
         return out
+
+    def _pack_text(self, who, luma_pages, lines, fonts, pens, offsets, baselines=None):
+        """The reading of verify_text / score_text (`who`, for the messages), checked: (pages, lines, used, groups).  pages and lines
+        as lists, used the set of fonts named, groups a generator of one (idx, batch, recs, chars, along, qs, where) per page size:
+        the pages idx as one uint8 batch, recs (page in batch, y, first, n_chars, font) into chars (alphabet indices), along the
+        pens or offsets beside chars, qs the baselines beside recs, where each record's (page, line)."""
+        pages = _page_list(luma_pages)
+        lines = [list(pg) for pg in lines]
+        if len(lines) != len(pages):
+            raise ValueError(f"lines must hold one list per page: {len(lines)} for {len(pages)} pages")
+        for name, per in (("fonts", fonts), ("pens", pens), ("offsets", offsets), ("baselines", baselines)):
+            if per is not None and (len(per) != len(pages) or any(len(a) != len(b) for a, b in zip(per, lines))):
+                raise ValueError(f"{name} must hold one entry per line of lines")
+        used = {int(k) for pg in fonts for k in pg} if fonts is not None else set()
+        if any(k < 0 or k > len(self._candidates) for k in used):
+            raise ValueError(f"fonts must be 0 .. {len(self._candidates)} (the decode font and the candidates of set_font_candidates)")
+        index = {c: i for i, c in reversed(list(enumerate(self.font.alphabet)))}  # the first of equal characters
+        per = pens if pens is not None else offsets
+
+        def groups():
+            for _, idx, batch in _size_groups(pages):
+                recs, chars, along, qs, where = [], [], [], [], []
+                for j, i in enumerate(idx):
+                    for q, (ly, text) in enumerate(lines[i]):
+                        try:
+                            cs = [index[c] for c in text]
+                        except KeyError as e:
+                            raise ValueError(f"{who}: {e.args[0]!r} (page {i}, line {q}) is not in the alphabet") from None
+                        recs.append((j, int(ly), len(chars), len(cs), int(fonts[i][q]) if fonts is not None else 0))
+                        where.append((i, q))
+                        chars.extend(cs)
+                        if baselines is not None:
+                            qs.append(int(baselines[i][q]))
+                        if per is not None:
+                            if len(per[i][q]) != len(cs):
+                                raise ValueError(f"{who}: page {i}, line {q}: {len(per[i][q])} pens or offsets for {len(cs)} characters")
+                            along.extend(int(v) for v in per[i][q])
+                yield idx, batch, recs, chars, along, qs, where
+
+        return pages, lines, used, groups()
 
     def rank_text(self, page, y, text, x, width, line_height, shift=0):
         """Which uploaded font renders a known string closest to the page: text scored at line slot (x, y) of one luma page
@@ -532,10 +533,7 @@ class LineDecoder:
         if text and self.font is None:
             raise DecoderError("set_font() first")
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
-        if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
-            pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
-        else:
-            pages = list(luma_pages)
+        pages = _page_list(luma_pages)
         if rgba is not None:
             if isinstance(rgba, np.ndarray) and rgba.ndim == 3:
                 rgba = [rgba]
@@ -546,17 +544,12 @@ class LineDecoder:
             self._ensure_verify_font()
         rects = [None] * len(pages) if rect else None
         texts = [None] * len(pages) if text else None
-        by_size = {}
-        for i, p in enumerate(pages):
-            by_size.setdefault(np.asarray(p).shape, []).append(i)
-        for (h, w), idx in by_size.items():
-            batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
+        for (h, w), idx, batch in _size_groups(pages):
             base = None if rgba is None else np.ascontiguousarray(np.stack([np.asarray(rgba[i], dtype=np.uint8) for i in idx]))
             r_out = np.empty((len(idx), h, w, 4), dtype=np.uint8) if rect else None
             t_out = np.empty((len(idx), h, w, 4), dtype=np.uint8) if text else None
-            ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
-            self._check(self._lib.focr_decoder_test_images(self._h, ptr(batch), ptr(base), 0, len(idx), w, h, *geo, ptr(r_out),
-                                                           ptr(t_out), 0))
+            self._check(self._lib.focr_decoder_test_images(self._h, _ptr(batch, True), _ptr(base, True), 0, len(idx), w, h, *geo, _ptr(r_out, True),
+                                                           _ptr(t_out, True), 0))
             self.last_test_ms = float(self._lib.focr_decoder_last_test_ms(self._h))
             for j, i in enumerate(idx):
                 if rect:
@@ -811,18 +804,11 @@ class LineDecoder:
         scores, pen_search, margins, pen_slack, baseline_search, whole_baseline and verify, and needs candidates (ValueError)."""
         m = self._modes(verify, scores, pen_search, whole_line, margins, pen_slack, baseline_search, whole_baseline, y_frac, line_advance_frac, font_search)
         geo = (int(x), int(y), int(width), int(line_height), int(line_advance))
-        if isinstance(luma_pages, np.ndarray) and luma_pages.ndim in (2, 3):
-            pages = [luma_pages] if luma_pages.ndim == 2 else list(luma_pages)
-        else:
-            pages = list(luma_pages)
+        pages = _page_list(luma_pages)
         out = _record(m, lambda: [None] * len(pages))
         mse = np.zeros(len(pages), dtype=np.float32)
         images = [None] * len(pages) if verify == "image" else None
-        by_size = {}
-        for i, p in enumerate(pages):
-            by_size.setdefault(np.asarray(p).shape, []).append(i)
-        for (h, w), idx in by_size.items():
-            batch = np.ascontiguousarray(np.stack([np.asarray(pages[i], dtype=np.uint8) for i in idx]))
+        for (h, w), idx, batch in _size_groups(pages):
             r = self._run(C.c_void_p(batch.ctypes.data), False, len(idx), h, w, *geo, m)
             for all_pages, these in zip(out, r):
                 for j, i in enumerate(idx if these is not None else ()):

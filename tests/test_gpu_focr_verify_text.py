@@ -256,6 +256,43 @@ def test_no_lines_null_rgb_and_device_buffers(dec):
         hip.hipFree(src)
 
 
+# ---- the staging verify_text shares with score_text ------------------------------------------------------------------------
+
+def test_shared_staging_keeps_nothing_between_calls(dec):
+    """verify_text and score_text stage their reading in one set of device arrays.  One handle draws with pens, costs the same
+    lines with neither pens nor offsets, draws with offsets, costs a longer list (eight lines that share characters) and draws
+    the first again: every answer (sums, image bytes, TextScores with their terms) is what a fresh decoder gives to that
+    call alone, so no call reads an earlier call's pens or offsets, or arrays of an earlier call's size."""
+    setup(dec, [MONO13, SANS20])
+    pages = [noisy(80, 20, 31), noisy(80, 20, 32)]
+    batch = np.ascontiguousarray(np.stack(pages))
+    lines, fonts = [[(2, "ahoi")], [(2, "ahoi")]], [[0], [1]]
+    pens, offs = [[[0, 500, 1000, 1500]]] * 2, [[[3, -5, 0, 64]], [[-64, 0, 7, 1]]]
+    chars = [AL.index(c) for c in "Hinein im ohr ab"]
+    recs = [(0, 0, 0, 16, 0), (0, 2, 0, 16, 1), (0, 4, 3, 9, 0), (1, 1, 3, 9, 1), (1, 1, 8, 8, 0), (1, 3, 15, 1, 1), (1, 5, 16, 0, 0), (1, 6, 0, 6, 1)]
+
+    def drawn(got):
+        return got[0].tobytes(), [img.tobytes() for img in got[1]]
+
+    def costs(got):
+        return [(s.base, s.cost, s.shift, s.terms.tobytes()) for s in got]
+
+    calls = [lambda d: drawn(d.verify_text(pages, lines, 1, fonts=fonts, pens=pens)),
+             lambda d: costs(sum(d.score_text(pages, lines, 1, 70, LH, fonts=fonts, shift=2), [])),
+             lambda d: drawn(d.verify_text(pages, lines, 1, fonts=fonts, offsets=offs)),
+             lambda d: costs(d._score_text(batch, recs, chars, None, None, None, 1, 70, LH, 0, 2, True))]
+    calls.append(calls[0])
+    want = []
+    for call in calls[:4]:
+        with LineDecoder(0) as fresh:
+            fresh.set_font(dec.font, None)
+            fresh.set_font_candidates(dec._candidates)
+            want.append(call(fresh))
+    want.append(want[0])
+    assert len({repr(w) for w in want}) == 4  # pens, offsets and the longer list each change the answer
+    assert [call(dec) for call in calls] == want
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------------
 
 def test_refusals(dec):
