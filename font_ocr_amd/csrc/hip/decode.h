@@ -2,8 +2,8 @@
 //   decode.hip                 the font, the settings' resolution into one RunMode, the run in its steps, prepass, compaction,
 //                              the pen loop and its search
 //   decode_whole.hip           the whole-line decode, with margins or a pen slack
-//   decode_baseline.hip        the baseline search, its y-phase fonts and the verify's compose after a baseline run
-//   decode_whole_baseline.hip  the whole-line decode under every baseline candidate
+//   decode_baseline.hip        the baseline search on either line grid, its y-phase fonts and the verify's compose after a baseline run
+//   decode_whole_baseline.hip  the whole-line decode under every baseline candidate, on either line grid
 //   decode_line_frac.hip       the fractional line grid's setter and the verify's compose on that grid
 //   decode_fonts.hip           the font search: the pen loop under every candidate font, the candidates' upload, the getter
 //   decode_whole_fonts.hip     the whole-line decode under every candidate font
@@ -56,10 +56,14 @@ __device__ __forceinline__ const uint8_t *slot_crop(const uint8_t *__restrict__ 
 }
 
 // ---- the fractional line grid (focr_decoder_set_line_frac; include/focr_decode.h): slot i's top is at
-// Y_i = 64 * y_start + y_frac + i * (64 * line_advance + advance_frac) in 1/64 px.  The kernels that read it are kernels of
-// their own (*_frac_kernel) beside the ones they restate, which keep their arguments and instruction streams
-// (tools/isa_hash.py).  The device helpers both forms share (the prepass of a slot, whole_stage, layout_line) take the grid as
-// a policy: PixelGrid is the whole-pixel grid of slot_rows, an empty type; FracGrid the fractional one ----
+// Y_i = 64 * y_start + y_frac + i * (64 * line_advance + advance_frac) in 1/64 px.  At (0, 0) it is the whole-pixel grid, integer
+// for integer, so a kernel that takes a LineFrac serves both grids: line_baseline_kernel (decode_baseline.hip) and
+// verify_layout_kernel (decode_images.hip) do.  Three kernels still have a form of their own on this grid beside the one it
+// restates, which keeps its arguments and its instruction stream (tools/isa_hash.py): line_prepass_frac_kernel (the plain decode's
+// first launch stays untouched), line_whole_baseline_frac_kernel and verify_compose_moved_frac_kernel (as the only kernel of their
+// kind each was measurably slower with the grid off).  The device helpers the forms share (the prepass of a slot,
+// whole_stage, layout_line) take the grid as a policy: PixelGrid is the whole-pixel grid of slot_rows, an empty type; FracGrid the
+// fractional one ----
 
 struct LineFrac {
     uint32_t y_frac, advance_frac;  // each 0 ..= 63; (0, 0) is off
@@ -227,8 +231,9 @@ __device__ __forceinline__ void tile_add_sum(uint32_t acc, uint32_t *part, unsig
 // and the pen advances from there, the decoder's own two f32 adds.  ps (null: none) is a whole-line run's pens in
 // 1/64 px: glyph q is placed at ps[q] / 64 (exact), whatever the increments before it.  moved is a baseline run's whole rows
 // for this line (0: none): the canvas is drawn that many rows below the slot's y, above it when negative, and is then
-// clipped at the page's top as well.  grid is the line grid the slot's y is read from: the whole-pixel one unless the run
-// was made on the fractional one (or the line brings its own y: decode_text.hip).
+// clipped at the page's top as well.  grid is the line grid the slot's y is read from: FracGrid with the run's
+// fractions for a run's lines ((0, 0) unless the run was made on the fractional grid), and the default where no slot's y is read
+// (the alphabet) or the line brings its own (decode_text.hip).
 template <bool IOTA, class Grid = PixelGrid>
 __device__ __forceinline__ void layout_line(const Geometry &g, uint32_t slot, const uint16_t *__restrict__ cs,
                                             const int8_t *__restrict__ js, const uint32_t *__restrict__ ps, int moved, uint32_t n, uint32_t k,

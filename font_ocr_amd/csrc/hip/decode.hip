@@ -20,7 +20,9 @@
 //      decode_fonts.hip's line_fonts_kernel takes its place, or beside the whole-line decode decode_whole_fonts.hip's
 //      line_whole_fonts_kernel: the pen loop, or the programme, under every candidate font, and the cheapest line kept.
 //      On a fractional line grid (focr_decoder_set_line_frac; the two baseline modes only) launch 1 is
-//      line_prepass_frac_kernel and launch 3 the baseline kernel's *_frac_kernel form: the slot grid in 1/64 px (decode.h).
+//      line_prepass_frac_kernel: the slot grid in 1/64 px (decode.h).  Launch 3 of a baseline search is the same
+//      line_baseline_kernel on either grid (it takes the grid as an argument, (0, 0) when it is off); the whole-line decode
+//      under candidates launches line_whole_baseline_frac_kernel on the fractional grid.
 // The reference scores sum over the canvas of (r - c)^2; that is sum r^2 + sum over the clipped glyph footprint of
 // c * (c - 2r), and sum r^2 is the same for every candidate, so the footprint term alone decides the argmin, ties
 // included.  It is exact integer arithmetic (v_dot4_u32_u8; the font builder bounds it below 2^31), so neither the

@@ -13,6 +13,11 @@
 // focr_decoder_set_baseline_fonts') with every box moved down by d = q >> B rows; footprint_term_wide clips a
 // box to the crop's rows on both sides, so rows that d pushes above row 0 or below the last row are never read.
 // Everything is exact integer arithmetic but the f32 pen, which is the plain loop's.
+// The kernel takes the line grid (decode.h's LineFrac) and serves both: on the fractional grid of focr_decoder_set_line_frac a
+// line's candidates lie around its own centre, and at (0, 0), the whole-pixel grid, every centre is 0 and every crop row is
+// y_start + i * line_advance.  (verify_compose_moved_kernel, the compose of a verify after a run of either baseline kind, is the
+// whole-pixel grid's alone: its restated twin on the fractional grid is decode_line_frac.hip's, and DESIGN.md 4b-7 has the
+// measurement that kept the two apart.)
 #include <cstring>
 
 #include "decode_pen.h"
@@ -47,70 +52,20 @@ __device__ __forceinline__ int64_t candidate_loop(const uint32_t *strip, uint32_
                            n_out);
 }
 
-// 3b. the pen loop under every baseline candidate, one workgroup per work-list line (grid-stride).  radius >= 1.
-// (line_baseline_frac_kernel below restates this body on the fractional line grid: a fix here is a fix there.)
+// 3b. the pen loop under every baseline candidate, one workgroup per work-list line (grid-stride).  radius >= 1.  The crop's
+// rows are the line grid's (decode.h: fr is (0, 0) on the whole-pixel grid), and the candidates of a line are
+// q = c + rank_offset(rank) around the line's own centre c, worked out again for every line a workgroup takes (a handful of
+// scalar integer operations, uniform across the workgroup); c is 0 on the whole-pixel grid.
 template <bool LDS>
-__global__ __launch_bounds__(BASE_THREADS) void line_baseline_kernel(const uint8_t *__restrict__ strips, Geometry g, const uint32_t *__restrict__ work,
-                                                                     const uint32_t *__restrict__ count, BaseFont f, uint32_t radius,
-                                                                     uint32_t *__restrict__ n_chars, uint16_t *__restrict__ chars,
+__global__ __launch_bounds__(BASE_THREADS) void line_baseline_kernel(const uint8_t *__restrict__ strips, Geometry g, LineFrac fr,
+                                                                     const uint32_t *__restrict__ work, const uint32_t *__restrict__ count, BaseFont f,
+                                                                     uint32_t radius, uint32_t *__restrict__ n_chars, uint16_t *__restrict__ chars,
                                                                      int32_t *__restrict__ line_q, int64_t *__restrict__ line_cost) {
     extern __shared__ __align__(8) uint32_t lds_base[];  // the waves' (cost, rank), then (LDS) the strip
     uint64_t *red = (uint64_t *)lds_base;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t sdw = g.stride / 4, n_cand = 2 * radius + 1, n_lines = *count;
     // the winner's decode goes to a wave that has one candidate fewer than wave 0 (n_cand is odd: wave 1 or 3)
-    const uint32_t writer = n_cand & (BASE_WAVES - 1);
-    for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
-        const uint32_t slot = work[k];
-        uint32_t yc, h;
-        slot_rows(g, slot % g.n_slots, &yc, &h);
-        const uint32_t *strip = (const uint32_t *)(strips + (size_t)slot * g.stride * g.line_height);
-        if (LDS) {
-            uint32_t *lds_strip = lds_base + BASE_RED_BYTES / 4;
-            for (uint32_t i = tid; i < sdw * h; i += BASE_THREADS) lds_strip[i] = strip[i];
-            __syncthreads();
-            strip = lds_strip;
-        }
-        int64_t best_cost = INT64_MAX;
-        uint32_t best_rank = ~0u;  // a wave without a candidate: never the winner (rank 0 is never dropped)
-        for (uint32_t rank = wave; rank < n_cand; rank += BASE_WAVES) {
-            const int q = rank_offset(rank);
-            if (f.origin_y * (1 << f.bits) + q < 0) continue;  // ty_q < 0: no such rendering
-            const int64_t cost = candidate_loop<false>(strip, sdw, (int)g.w, h, g.cap, f, q, lane, nullptr, nullptr);
-            if (cost < best_cost) best_cost = cost, best_rank = rank;  // a wave's ranks ascend: the first of equal costs stays
-        }
-        if (lane == 0) red[2 * wave] = (uint64_t)best_cost, red[2 * wave + 1] = best_rank;
-        __syncthreads();
-        best_cost = (int64_t)red[0], best_rank = (uint32_t)red[1];
-        for (uint32_t v = 1; v < BASE_WAVES; v++) {
-            const int64_t c = (int64_t)red[2 * v];
-            const uint32_t r = (uint32_t)red[2 * v + 1];
-            if (c < best_cost || (c == best_cost && r < best_rank)) best_cost = c, best_rank = r;
-        }
-        if (wave == writer) {
-            const int q = rank_offset(best_rank);
-            const int64_t cost = candidate_loop<true>(strip, sdw, (int)g.w, h, g.cap, f, q, lane, chars + (size_t)k * g.cap, n_chars + k);
-            if (lane == 0) line_q[k] = q, line_cost[k] = cost;
-        }
-        __syncthreads();  // the strip and the pairs are the next line's from here
-    }
-}
-
-// 3bf. line_baseline_kernel on the fractional line grid (focr_decoder_set_line_frac; decode.h): the crop's rows are that
-// grid's, and the candidates of a line are q = c + rank_offset(rank) around the line's own centre c, worked out again for
-// every line a workgroup takes (a handful of scalar integer operations, uniform across the workgroup).  The rest is
-// line_baseline_kernel's, restated: with one body behind both kernels (the grid as a policy argument, by reference or by
-// value, with or without __restrict__) both instantiations of line_baseline_kernel changed their machine code
-// (tools/isa_hash.py), which the mode-off timing pins.
-template <bool LDS>
-__global__ __launch_bounds__(BASE_THREADS) void line_baseline_frac_kernel(const uint8_t *__restrict__ strips, Geometry g, LineFrac fr,
-                                                                          const uint32_t *__restrict__ work, const uint32_t *__restrict__ count, BaseFont f,
-                                                                          uint32_t radius, uint32_t *__restrict__ n_chars, uint16_t *__restrict__ chars,
-                                                                          int32_t *__restrict__ line_q, int64_t *__restrict__ line_cost) {
-    extern __shared__ __align__(8) uint32_t lds_base[];  // the waves' (cost, rank), then (LDS) the strip
-    uint64_t *red = (uint64_t *)lds_base;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t sdw = g.stride / 4, n_cand = 2 * radius + 1, n_lines = *count;
     const uint32_t writer = n_cand & (BASE_WAVES - 1);
     for (uint32_t k = blockIdx.x; k < n_lines; k += gridDim.x) {
         const uint32_t slot = work[k];
@@ -227,12 +182,8 @@ void baseline_launch(focr_decoder *dec, const RunMode &mode, const Geometry &g, 
     const GlyphTables &t = dec->tables, &y = dec->yfonts.tables;
     const BaseFont f{t.glyphs, y.glyphs, t.offs, y.offs, t.bitmaps.as<const uint32_t>(), y.bitmaps.as<const uint32_t>(), t.n_dw, y.n_dw, dec->n_glyphs,
                      dec->font.origin_x, (int)dec->font.origin_y, mode.bits};
-    if (mode.frac.on())  // the kernel's form on the fractional grid: a kernel of its own beside the one it restates
-        (lds ? line_baseline_frac_kernel<true> : line_baseline_frac_kernel<false>)<<<grid, BASE_THREADS, lds_bytes, dec->stream>>>(
-            dec->d_strips, g, mode.frac, dec->d_work, dec->d_count, f, mode.radius, dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
-    else
-        (lds ? line_baseline_kernel<true> : line_baseline_kernel<false>)<<<grid, BASE_THREADS, lds_bytes, dec->stream>>>(
-            dec->d_strips, g, dec->d_work, dec->d_count, f, mode.radius, dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
+    (lds ? line_baseline_kernel<true> : line_baseline_kernel<false>)<<<grid, BASE_THREADS, lds_bytes, dec->stream>>>(
+        dec->d_strips, g, mode.frac, dec->d_work, dec->d_count, f, mode.radius, dec->d_nchars, dec->d_chars, dec->d_base_q, dec->d_base_cost);
 }
 
 void drop_baseline_fonts(focr_decoder *dec) { dec->yfonts = BaseFonts{}; }

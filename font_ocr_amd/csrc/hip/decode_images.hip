@@ -6,7 +6,8 @@
 //      26.6 delta of every glyph; after a run with a pen search or a whole-line run (decode_whole.hip), from the pens the run chose;
 //      after a baseline run (decode_baseline.hip) with the canvas moved by the nearest whole row of the line's offset) and
 //      writes each glyph's
-//      true bitmap rectangle, clipped to the canvas and the page;
+//      true bitmap rectangle, clipped to the canvas and the page; it takes the run's line grid (decode.h's LineFrac), which
+//      is (0, 0), the whole-pixel grid, after every run but a baseline kind's on the fractional grid;
 //   5. verify_compose_kernel: one workgroup per (page, 16 rows, 256 columns) tile takes, line by line in order, the
 //      last glyph covering each pixel (an LDS atomic max of the glyph index, so placement and order do not matter),
 //      lets a non-zero value replace the blue of earlier lines, writes RGB and adds the exact sum of (R - B)^2 to the
@@ -24,9 +25,10 @@ namespace focr_dec {
 
 // (layout_line, render()'s layout of one line by one wave, is decode.h's: decode_text.hip lays out a caller's lines with it.)
 
-// 4. render()'s layout of every decoded line, one wave per work-list line; blocks below n_pages also zero the sums
-// (verify_layout_frac_kernel below restates this body on the fractional line grid: a fix here is a fix there)
-__global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t n_pages, uint32_t x_start, const uint32_t *__restrict__ flags,
+// 4. render()'s layout of every decoded line, one wave per work-list line; blocks below n_pages also zero the sums.  Every
+// line's y is its slot's crop row on the run's line grid, Y_i >> 6 (decode.h: fr is (0, 0) on the whole-pixel grid, where that is
+// y_start + i * line_advance).
+__global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, LineFrac fr, uint32_t n_pages, uint32_t x_start, const uint32_t *__restrict__ flags,
                                                            const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
                                                            const uint32_t *__restrict__ n_chars, const uint16_t *__restrict__ chars,
                                                            const int8_t *__restrict__ pen_offs, const uint32_t *__restrict__ pens,
@@ -40,31 +42,9 @@ __global__ __launch_bounds__(64) void verify_layout_kernel(Geometry g, uint32_t 
     if (lane == 0 && flags[b] == 0) lines[b] = VerifyLine{0, 0, 0, 0, 0, 0};  // blank slots are in no work-list entry
     if (b >= *count) return;
     const uint32_t k = b, slot = work[k], n = n_chars[k];
-    // a baseline run's line (line_q; null: none) is drawn moved by the nearest whole row of its offset q * 2^-y_bits
+    // a baseline run's line (line_q; null: none) is drawn moved by the nearest whole row of its offset q * 2^-y_bits, the
+    // absolute one: from the crop row
     const int moved = line_q ? (line_q[k] + (int)((1u << y_bits) >> 1)) >> y_bits : 0;
-    layout_line<false>(g, slot, chars + (size_t)k * g.cap, pen_offs ? pen_offs + (size_t)k * g.cap : nullptr,
-                       pens ? pens + (size_t)k * g.cap : nullptr, moved, n, k, x_start,
-                       glyphs, vglyphs, vphases, recs + (size_t)k * g.cap, lines + slot);
-}
-
-// 4f. verify_layout_kernel after a run on the fractional line grid (focr_decoder_set_line_frac): every line's y is its crop
-// row Y_i >> 6.  A kernel of its own, so that verify_layout_kernel keeps its arguments and its instruction stream
-// (tools/isa_hash.py).
-__global__ __launch_bounds__(64) void verify_layout_frac_kernel(Geometry g, LineFrac fr, uint32_t n_pages, uint32_t x_start, const uint32_t *__restrict__ flags,
-                                                                const uint32_t *__restrict__ work, const uint32_t *__restrict__ count,
-                                                                const uint32_t *__restrict__ n_chars, const uint16_t *__restrict__ chars,
-                                                                const int8_t *__restrict__ pen_offs, const uint32_t *__restrict__ pens,
-                                                                const int32_t *__restrict__ line_q, uint32_t y_bits,
-                                                                const DevGlyph *__restrict__ glyphs, const VerifyGlyph *__restrict__ vglyphs,
-                                                                const VerifyPhase *__restrict__ vphases, VerifyLine *__restrict__ lines,
-                                                                VerifyRec *__restrict__ recs, unsigned long long *__restrict__ sums) {
-    const uint32_t b = blockIdx.x, lane = threadIdx.x;
-    if (b < n_pages && lane == 0) sums[b] = 0;
-    if (b >= g.total) return;
-    if (lane == 0 && flags[b] == 0) lines[b] = VerifyLine{0, 0, 0, 0, 0, 0};
-    if (b >= *count) return;
-    const uint32_t k = b, slot = work[k], n = n_chars[k];
-    const int moved = line_q ? (line_q[k] + (int)((1u << y_bits) >> 1)) >> y_bits : 0;  // q is the absolute one: from the crop row
     layout_line<false>(g, slot, chars + (size_t)k * g.cap, pen_offs ? pen_offs + (size_t)k * g.cap : nullptr,
                        pens ? pens + (size_t)k * g.cap : nullptr, moved, n, k, x_start,
                        glyphs, vglyphs, vphases, recs + (size_t)k * g.cap, lines + slot, FracGrid{fr});
@@ -291,15 +271,10 @@ extern "C" int focr_decoder_verify(focr_decoder_t *dec, uint8_t *rgb, int rgb_on
     const int8_t *pen_offs = mode.kind == Kind::pen_search ? (const int8_t *)dec->d_pen : nullptr;
     const uint32_t *pens = mode.whole() ? (const uint32_t *)dec->d_pens : nullptr;
     const int32_t *line_q = mode.base_q() ? (const int32_t *)dec->d_base_q : nullptr;
-    if (mode.frac.on())  // (only a baseline kind runs on the fractional grid)
-        verify_layout_frac_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, mode.frac, (uint32_t)n_pages, run.x_start, dec->d_flags, dec->d_work,
-                                                                                  dec->d_count, dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, mode.bits,
-                                                                                  dec->tables.glyphs, dec->vtables.glyphs, dec->vtables.phases, dec->d_vlines, dec->d_vrecs,
-                                                                                  dec->d_sums);
-    else
-        verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, (uint32_t)n_pages, run.x_start, dec->d_flags, dec->d_work, dec->d_count,
-                                                                             dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, mode.bits, dec->tables.glyphs,
-                                                                             dec->vtables.glyphs, dec->vtables.phases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
+    // mode.frac is the run's line grid: (0, 0), the whole-pixel one, except after a baseline kind on the fractional grid
+    verify_layout_kernel<<<(uint32_t)layout_blocks, 64, 0, dec->stream>>>(g, mode.frac, (uint32_t)n_pages, run.x_start, dec->d_flags, dec->d_work, dec->d_count,
+                                                                         dec->d_nchars, dec->d_chars, pen_offs, pens, line_q, mode.bits, dec->tables.glyphs,
+                                                                         dec->vtables.glyphs, dec->vtables.phases, dec->d_vlines, dec->d_vrecs, dec->d_sums);
     DEC_CHECK(hipGetLastError());
     if (mode.frac.on())  // ... and on the fractional grid the slots that reach a tile come from that grid's inverse
         verify_compose_frac_launch(dec, tg, n_pages, d_rgb);

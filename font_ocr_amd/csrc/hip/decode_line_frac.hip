@@ -1,9 +1,9 @@
 // decode_line_frac.hip — the fractional line grid of the `focr` line decoder's two baseline modes (focr_decoder_set_line_frac;
 // an extension, see include/focr_decode.h): its setter, and the compose kernel of a verify after a run on that grid.  The
-// grid itself is stated once in decode.h (LineFrac, slot_rows_frac, frac_centre, slot_range_frac); the other four kernels that
-// read it stand beside the kernels they restate: line_prepass_frac_kernel (decode.hip), line_baseline_frac_kernel
-// (decode_baseline.hip), line_whole_baseline_frac_kernel (decode_whole_baseline.hip) and verify_layout_frac_kernel
-// (decode_images.hip).
+// grid itself is stated once in decode.h (LineFrac, slot_rows_frac, frac_centre, slot_range_frac).  Of the other kernels that
+// read it, line_prepass_frac_kernel (decode.hip) and line_whole_baseline_frac_kernel (decode_whole_baseline.hip) stand beside
+// the kernels they restate, and line_baseline_kernel (decode_baseline.hip) and verify_layout_kernel (decode_images.hip) take the
+// grid as an argument and serve the whole-pixel grid as well, at (0, 0).
 #include "decode.h"
 
 namespace focr_dec {

@@ -12,6 +12,7 @@ import numpy as np
 
 import focr_baseline_model as B
 import focr_line_frac_model as LF
+import focr_whole_baseline_model as WB
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MONO = os.path.join(GOLD, "DejaVuSansMono.ttf")
@@ -198,7 +199,19 @@ def strip_bytes(page_w, x, width, line_height):
     return ((w + 7) // 4 + 2) * 4 * line_height
 
 
+def off(case):
+    """The case at the fraction (0, 0), the whole-pixel grid, on the same pages: the baseline search's kernel and the
+    verify's layout kernel are the same ones on both grids, so the edges the hand-built cases aim at are run on each.  The
+    lines were drawn for the fractional grid, so they sit off these slots and the searches answer with q != 0."""
+    return case._replace(name=case.name + "-off", frac=(0, 0))
+
+
 def expected(case):
-    """The model's [[(yc_i, Baseline or WholeBaseline)] per page] of a case."""
+    """The model's [[(yc_i, Baseline or WholeBaseline)] per page] of a case: the fractional grid's model, or at (0, 0) the two
+    whole-pixel baseline models' own walk of the page."""
     m = model(case.font, case.size, case.alphabet, case.y_bits)
+    if tuple(case.frac) == (0, 0):
+        if case.whole:
+            return [WB.search_image(m, p, *case.geo, case.n) for p in case.pages]
+        return [m.search_image(p, *case.geo, case.n) for p in case.pages]
     return [LF.search_image(m, p, *case.geo, case.n, *case.frac, whole=case.whole) for p in case.pages]

@@ -213,6 +213,46 @@ def test_far_below_reaches_the_largest_q():
     vf.close()
 
 
+def test_cases_at_zero_fraction_reach_their_edges():
+    """K.off(case), the hand-built cases at (0, 0) on their own pages, which tests/test_gpu_focr_line_frac.py's
+    *_at_zero_fraction tests run: the expectation is the two whole-pixel models' (not the fractional model at (0, 0), which is
+    compared with it here), every case has a non-blank line and a line whose winning q is not 0, and each edge is still reached."""
+    from font_ocr_amd import VerifyFont
+
+    def held(c):
+        want = K.expected(c)
+        m = K.model(c.font, c.size, c.alphabet, c.y_bits)
+        frac = [LF.search_image(m, p, *c.geo, c.n, 0, 0, whole=c.whole) for p in c.pages]
+        assert c.frac == (0, 0) and [[(y, r.text, r.q, r.cost) for y, r in pg] for pg in want] == [[(y, r.text, r.q, r.cost) for y, r in pg] for pg in frac]
+        assert all((y - c.geo[1]) % c.geo[4] == 0 for pg in want for y, _ in pg)  # the rows y_start + i * line_advance
+        assert sum(len(pg) for pg in want) >= 1 and any(r.q != 0 for pg in want for _, r in pg), c.name
+        return want
+
+    c = K.off(K.advance_one_case())
+    found = held(c)[0]
+    assert len(found) > 20 and sum(y < 16 for y, _ in found) >= 10  # many slots per tile row
+    for whole in (False, True):
+        c = K.off(K.moved_off_page_case(whole))
+        found = held(c)[0]
+        y, last = found[-1]
+        assert (found[0][0], found[0][1].q, last.q) == (0, -3, 4) and y + 4 + 13 > c.pages[0].shape[0]
+        c = K.off(K.wide_case(whole))
+        assert K.strip_bytes(c.pages[0].shape[1], c.geo[0], c.geo[2], c.geo[3]) > 65536 and held(c)
+        c = K.std_case(whole, 2, 1)
+        want = held(K.off(c._replace(pages=K.std_pages(whole, 31, 2))))
+        assert len(want) == 2 and all(len(pg) >= 2 for pg in want) and {r.q for pg in want for _, r in pg} <= {-1, 0, 1}
+    vf = VerifyFont(K.MONO, 13.0, K.MONO_AL)
+    last = []
+    for y in range(16):  # the largest q of the whole-pixel grid, FOCR_BASELINE_MAX = 32, and a canvas whose last row opens a tile once
+        c = K.off(K.far_below_case(y))
+        (yc, b), = held(c)[0]
+        assert (yc, b.q, B.row_shift(b.q, 0)) == (y, 32, 32)
+        img, _ = LF.verify_image(c.pages[0], [(yc, b)], K.model(c.font, c.size, c.alphabet, 0).font, vf, c.geo[0], 0)
+        last.append(int(np.nonzero(img[..., 2].any(axis=1))[0].max()))
+    assert sum(r % 16 == 0 for r in last) == 1
+    vf.close()
+
+
 def test_verify_model_takes_the_crop_row_and_the_absolute_q():
     """The verify of a fractional run is the baseline run's with (yc_i, text, q): with the centre 2^B of slot 0 the canvas is
     drawn one row below the crop row, where the line's top (f = 60) is nearest."""

@@ -1,9 +1,11 @@
-"""The focr decoder's fractional line grid (focr_decoder_set_line_frac; line_prepass_frac_kernel, line_baseline_frac_kernel,
-line_whole_baseline_frac_kernel, verify_layout_frac_kernel, verify_compose_moved_frac_kernel;
+"""The focr decoder's fractional line grid (focr_decoder_set_line_frac; line_prepass_frac_kernel,
+line_whole_baseline_frac_kernel, verify_compose_moved_frac_kernel, and the two kernels that take the grid as an argument and
+serve the whole-pixel grid at (0, 0) as well: line_baseline_kernel, verify_layout_kernel;
 LineDecoder.decode(y_frac=, line_advance_frac=); focr --y-frac --line-advance-frac) against tests/focr_line_frac_model.py,
 the definition of include/focr_decode.h restated in plain integers on the two baseline models.  Every quantity is an exact
 integer, so every comparison is ==.  The cases are tests/focr_line_frac_cases.py's; tests/test_focr_line_frac_model.py proves
-on the CPU that each reaches the case its name promises.
+on the CPU that each reaches the case its name promises.  The edge cases run at (0, 0) too (the *_at_zero_fraction tests),
+against the two whole-pixel models: there the grid-taking kernels must give what the whole-pixel kernels they replaced gave.
 
 Teeth of test_fuzz_cases, as measured on an MI355X with one-line mutations of the DEVICE code only (decode.h; neither touches
 an index, a bound, a size or a stride), each built once and run once against test_fuzz_cases: frac_centre with `+ 31` for
@@ -134,14 +136,7 @@ def test_two_page_sizes_through_decode(dec, whole):
     assert [y for y, _ in want[0]] == [y for y, _ in want[2]] and all(len(pg) >= 2 for pg in want)
 
 
-@pytest.mark.parametrize("whole", [False, True], ids=["base", "whole"])
-def test_one_workgroup_takes_several_lines(dec, whole):
-    """With the debug grid at 1 and 2 one workgroup takes every line, or every other one: the centre is worked out again for
-    each, so the result is the free run's, which is the model's."""
-    c = K.std_case(whole, 2, 1)
-    c = c._replace(pages=K.std_pages(whole, 31, 2))
-    want = _check(dec, c, verify=False)
-    assert len({r.q for pg in want for _, r in pg}) >= (2 if whole else 4)  # several centres
+def _same_under_debug_grids(dec, c, whole):
     free = _decode(dec, c)
     setter = dec._lib.focr_decoder_debug_set_whole_grid if whole else dec._lib.focr_decoder_debug_set_baseline_grid
     try:
@@ -153,9 +148,68 @@ def test_one_workgroup_takes_several_lines(dec, whole):
 
 
 @pytest.mark.parametrize("whole", [False, True], ids=["base", "whole"])
+def test_one_workgroup_takes_several_lines(dec, whole):
+    """With the debug grid at 1 and 2 one workgroup takes every line, or every other one: the centre is worked out again for
+    each, so the result is the free run's, which is the model's."""
+    c = K.std_case(whole, 2, 1)
+    c = c._replace(pages=K.std_pages(whole, 31, 2))
+    want = _check(dec, c, verify=False)
+    assert len({r.q for pg in want for _, r in pg}) >= (2 if whole else 4)  # several centres
+    _same_under_debug_grids(dec, c, whole)
+
+
+# ---- the same edges at the fraction (0, 0): the baseline search's kernel and the verify's layout kernel are the same ones on
+# both grids, and at (0, 0) the fractional grid is the whole-pixel one, so K.off(case) is held to the two whole-pixel models
+# (focr_baseline_model, focr_whole_baseline_model; K.expected).  The pages are the cases' own: their lines were drawn for the
+# fractional grid and sit off these slots, so the searches move them (tests/test_focr_line_frac_model.py proves each q) ----
+
+
+def _moved(want):
+    return any(r.q != 0 for pg in want for _, r in pg)
+
+
+def test_line_advance_one_at_zero_fraction(dec):
+    want = _check(dec, K.off(K.advance_one_case()))[0]
+    assert len(want) > 20 and _moved([want])
+
+
+@pytest.mark.parametrize("whole", [False, True], ids=["base", "whole"])
+def test_canvas_moved_off_the_page_at_zero_fraction(dec, whole):
+    """The last line, drawn for a leading of 15 + 38/64 px, lies four rows below its whole-pixel slot."""
+    want = _check(dec, K.off(K.moved_off_page_case(whole)))[0]
+    assert want[0][1].q == -3 and want[-1][1].q == 4
+
+
+def test_canvas_at_the_far_lower_reach_at_zero_fraction(dec):
+    """The centre is 0, so the largest q is 32 = FOCR_BASELINE_MAX: the same sweep with the canvas 32 rows below its slot."""
+    for y in range(16):
+        (_, b), = _check(dec, K.off(K.far_below_case(y)))[0]
+        assert b.q == 32
+
+
+@pytest.mark.parametrize("whole", [False, True], ids=["base", "whole"])
+def test_strip_too_large_for_lds_at_zero_fraction(dec, whole):
+    c = K.off(K.wide_case(whole))
+    assert K.strip_bytes(c.pages[0].shape[1], c.geo[0], c.geo[2], c.geo[3]) > 65536
+    assert _moved(_check(dec, c))
+
+
+@pytest.mark.parametrize("whole", [False, True], ids=["base", "whole"])
+def test_one_workgroup_takes_several_lines_at_zero_fraction(dec, whole):
+    """Every centre is 0, and the lines drift off their slots until the radius of one step saturates either way."""
+    c = K.std_case(whole, 2, 1)
+    c = K.off(c._replace(pages=K.std_pages(whole, 31, 2)))
+    want = _check(dec, c, verify=False)
+    assert _moved(want) and {r.q for pg in want for _, r in pg} <= {-1, 0, 1}
+    _same_under_debug_grids(dec, c, whole)
+
+
+@pytest.mark.parametrize("whole", [False, True], ids=["base", "whole"])
 def test_off_after_on_is_a_fresh_decoder(dec, whole):
     """(0, 0) after a fractional run returns exactly what a decoder that never had a grid returns: lines, q, costs, verify
-    images and MSE, in three launches; and the device's q on the whole-pixel grid differs from the fractional one's."""
+    images and MSE, in three launches; and the device's q on the whole-pixel grid differs from the fractional one's.  The
+    baseline search and the verify's layout launch the same kernel in both runs: (0, 0) after (60, 38) differs in its
+    arguments alone."""
     c = K.std_case(whole, 2, 1)
     m = K.model(c.font, c.size, c.alphabet, c.y_bits)
     off = c._replace(frac=(0, 0))

@@ -64,6 +64,9 @@ With --whole-line --whole-baseline N [--y-bits B], also the whole-line decode un
   wbase_wall_ms_per_batch     median host time of one such decode call, pens, costs and offsets read back
   wbase_lines_changed         lines of the batch the mode decodes differently from the whole-line run
   wbase_lines_offset          lines of the batch that took an offset other than 0
+With --verify beside --baseline-search or --whole-baseline, also the verify of that baseline run (its moved compose):
+  base_verify_device_ms, wbase_verify_device_ms            median device time of the verify's two kernels, the images drawn
+  base_verify_sums_device_ms, wbase_verify_sums_device_ms  ... and of the verify that draws no image, in alternating calls
 With --line-frac Y,A beside --baseline-search or --whole-line --whole-baseline, the pages are drawn on the fractional line
 grid y + Y/64 + i * (line_advance + A/64) px (every glyph rasterised at its line's sub-pixel row), every section above runs
 on those pages, and the mode in force is also timed with the grid on (LineDecoder.decode(..., y_frac=Y,
@@ -172,6 +175,17 @@ def synth_frac(n_pages, seed, frac, W=608, H=720, x=45, y=39, n_lines=40, advanc
                         pages[p, ly: ly + hh, x0: x0 + ww] = np.minimum(pages[p, ly: ly + hh, x0: x0 + ww], 255 - g[:hh, :ww])
                 pen = np.float32(pen + inc[FOCR_DEFAULT_ALPHABET.index(ch)])
     return pages
+
+
+def moved_verify(dec, a):
+    """Device ms of the verify of the decoder's last run, a baseline one, with the images and without, in alternating calls."""
+    with_images, without = [], []
+    for i in range(a.warmup + a.steps):
+        dec.verify()
+        with_images.append(dec.last_verify_ms)
+        dec.verify(images=False)
+        without.append(dec.last_verify_ms)
+    return with_images[a.warmup:], without[a.warmup:]
 
 
 def main():
@@ -360,6 +374,8 @@ def main():
                 bwall.append((time.perf_counter() - t) * 1e3)
                 bdev.append(dec.last_ms)
             blaunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+            if a.verify:
+                bvdev, bvndev = moved_verify(dec, a)
         if a.whole_baseline:
             for _ in range(a.warmup):
                 dec.decode(pages, *geo, whole_line=True, whole_baseline=a.whole_baseline)
@@ -372,6 +388,8 @@ def main():
                 cwall.append((time.perf_counter() - t) * 1e3)
                 cdev.append(dec.last_ms)
             claunches = int(dec._lib.focr_decoder_last_launches(dec._h))
+            if a.verify:
+                cvdev, cvndev = moved_verify(dec, a)
         if frac:
             mode = dict(whole_line=True, whole_baseline=a.whole_baseline) if a.whole_baseline else dict(baseline_search=a.baseline_search)
             on = dict(mode, y_frac=frac[0], line_advance_frac=frac[1])
@@ -495,6 +513,8 @@ def main():
                     "base_device_ms_min": round(float(min(bdev)), 4), "base_plain_device_ms": round(bpms, 4),
                     "base_over_plain": round(bms / bpms, 3), "base_launches": blaunches,
                     "base_wall_ms_per_batch": round(float(np.median(bwall)), 3), "base_lines_changed": changed, "base_lines_offset": moved})
+        if a.verify:
+            res.update({"base_verify_device_ms": round(float(np.median(bvdev)), 4), "base_verify_sums_device_ms": round(float(np.median(bvndev)), 4)})
     if a.whole_baseline:
         cms, cwms = float(np.median(cdev)), float(np.median(cwdev))
         changed = sum(ta != tb for pa, pb in zip(cref[0], cgot[0]) for (_, ta), (_, tb) in zip(pa, pb))
@@ -504,6 +524,8 @@ def main():
                     "wbase_device_ms_min": round(float(min(cdev)), 4), "wbase_whole_device_ms": round(cwms, 4),
                     "wbase_over_whole": round(cms / cwms, 3), "wbase_launches": claunches,
                     "wbase_wall_ms_per_batch": round(float(np.median(cwall)), 3), "wbase_lines_changed": changed, "wbase_lines_offset": moved})
+        if a.verify:
+            res.update({"wbase_verify_device_ms": round(float(np.median(cvdev)), 4), "wbase_verify_sums_device_ms": round(float(np.median(cvndev)), 4)})
     if frac:
         fms, foms = float(np.median(fdev)), float(np.median(fodev))
         changed = sum(ta != tb for pa, pb in zip(foff[0], fgot[0]) for (_, ta), (_, tb) in zip(pa, pb))
