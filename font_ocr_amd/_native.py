@@ -82,6 +82,14 @@ class TicketTimes(C.Structure):
                 ("done_us", C.c_double), ("device_gap_ms", C.c_float)]
 
 
+class HostResults(C.Structure):
+    """focr_host_results_t (include/focr_ncc.h): pointers into a context's page-locked result buffers, valid until the ticket's release."""
+
+    _fields_ = [("counts", C.c_void_p), ("page_line_off", C.c_void_p), ("line_char_off", C.c_void_p), ("chars", C.c_void_p),
+                ("n_pages", C.c_size_t), ("n_templates", C.c_size_t), ("n_matches", C.c_size_t), ("n_lines", C.c_size_t),
+                ("n_chars", C.c_size_t), ("device_ms", C.c_float)]
+
+
 _NCC_ARGS = [
     C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
     C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t,
@@ -161,7 +169,7 @@ HIP_SYMBOLS = {
     "focr_pipe_prefetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]),
     "focr_pipe_end_of_stream": (C.c_int, [C.c_void_p]),
     "focr_pipe_set_fetch": (C.c_int, [C.c_void_p, C.c_int]),
-    "focr_pipe_host_results": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "focr_pipe_host_results": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(HostResults)]),
     "focr_get_lines_into": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "focr_pipe_wait": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "focr_pipe_release": (C.c_int, [C.c_void_p, C.c_uint64]),
@@ -179,7 +187,7 @@ HIP_SYMBOLS = {
     "focr_fleet_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_uint32,
                                     C.c_int, C.c_int, C.c_float, C.c_int32, C.POINTER(C.c_uint64)]),
     "focr_fleet_wait": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
-    "focr_fleet_host_results": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "focr_fleet_host_results": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(HostResults)]),
     "focr_fleet_release": (C.c_int, [C.c_void_p, C.c_uint64]),
     "focr_last_launches": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "focr_debug_rnorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

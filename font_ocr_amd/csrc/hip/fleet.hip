@@ -3,6 +3,7 @@
 // k % n_devices.  A device's pipe sees every n_devices-th batch in order, so the pipe's own ticket of fleet ticket T is
 // (T - 1) / n_devices + 1 and nothing has to be looked up.
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -16,7 +17,10 @@ struct focr_fleet {
     unsigned lanes = 0, slots_per_pipe = 0;  // contexts per device's executor: batches it can hold unreleased
     std::mutex mu;  // serialises submit: tickets are handed out in submission order
     uint64_t next_ticket = 1;
-    std::atomic<uint64_t> released{0};  // tickets given back with focr_fleet_release
+    // per context of the fleet (ticket T -> (T - 1) % focr_fleet_slots: T and T + slots share a device, an executor and its context):
+    // the fleet ticket it holds unreleased, 0 = none.  Set by submit, cleared by focr_fleet_release (which may run on another thread)
+    std::unique_ptr<std::atomic<uint64_t>[]> held;
+    size_t n_slots = 0;
 };
 
 using focr::fail;
@@ -62,6 +66,9 @@ int focr_fleet_create(const int *devices, unsigned n_devices, unsigned lanes_per
             return fail(nullptr, rc, msg);
         }
     f->slots_per_pipe = focr_pipe_contexts(f->pipes[0]);
+    f->n_slots = f->pipes.size() * f->slots_per_pipe;
+    f->held.reset(new std::atomic<uint64_t>[f->n_slots]);
+    for (size_t i = 0; i < f->n_slots; i++) f->held[i].store(0);
     *out = f;
     return FOCR_OK;
 }
@@ -75,7 +82,7 @@ void focr_fleet_destroy(focr_fleet_t *f) {
 
 unsigned focr_fleet_devices(const focr_fleet_t *f) { return f ? (unsigned)f->pipes.size() : 0; }
 unsigned focr_fleet_lanes(const focr_fleet_t *f) { return f ? f->lanes : 0; }
-unsigned focr_fleet_slots(const focr_fleet_t *f) { return f ? (unsigned)(f->pipes.size() * f->slots_per_pipe) : 0; }
+unsigned focr_fleet_slots(const focr_fleet_t *f) { return f ? (unsigned)f->n_slots : 0; }
 focr_pipe_t *focr_fleet_pipe(focr_fleet_t *f, unsigned index) { return f && index < f->pipes.size() ? f->pipes[index] : nullptr; }
 
 int focr_fleet_device_of(const focr_fleet_t *f, uint64_t ticket) {
@@ -124,10 +131,12 @@ int focr_fleet_submit(focr_fleet_t *f, const void *pages, int pages_on_device, s
     if (!f || !ticket) return fail(nullptr, FOCR_ERR_INVALID, "focr_fleet_submit: bad arguments");
     std::lock_guard<std::mutex> lk(f->mu);  // submissions are ordered by definition
     const uint64_t t = f->next_ticket;
-    // Every context holding an unreleased batch: the context this batch maps to is the one with the OLDEST ticket, and waiting for it
-    // here would be waiting for the caller's own focr_fleet_release — a consumer that submits and retires on one thread would
-    // hang with no diagnostic.  Refuse instead (a consumer that releases from a second thread simply submits again).
-    if (t - 1 - f->released.load() >= (uint64_t)f->pipes.size() * f->slots_per_pipe)
+    // The context this batch maps to still holds an unreleased batch (ticket t - slots: with every context taken, the OLDEST one):
+    // waiting for it here would be waiting for the caller's own focr_fleet_release — a consumer that submits and retires on one
+    // thread would hang with no diagnostic.  Refuse instead (a consumer that releases from a second thread simply submits again).
+    // The question is this context's own ticket, not how many tickets were released: after releases out of order the count can
+    // be below the number of contexts while ticket t - slots is still out.
+    if (f->held[(t - 1) % f->n_slots].load() != 0)
         return fail(nullptr, FOCR_ERR_STATE, "focr_fleet_submit: every context holds an unreleased batch; release the oldest ticket first");
     uint64_t pt = 0;
     const int rc = focr_pipe_submit(pipe_of(f, t), pages, pages_on_device, n_pages, r_w, r_h, invert, threshold, cap, mode, process_hits, anchor_threshold,
@@ -139,6 +148,7 @@ int focr_fleet_submit(focr_fleet_t *f, const void *pages, int pages_on_device, s
         (void)focr_pipe_release(pipe_of(f, t), pt);
         return fail(nullptr, FOCR_ERR_STATE, "focr_fleet_submit: a pipe of the fleet was submitted to directly");
     }
+    f->held[(t - 1) % f->n_slots].store(t);
     f->next_ticket++;
     *ticket = t;
     return FOCR_OK;
@@ -157,7 +167,10 @@ int focr_fleet_host_results(focr_fleet_t *f, uint64_t ticket, focr_host_results_
 int focr_fleet_release(focr_fleet_t *f, uint64_t ticket) {
     if (!f || !ticket) return fail(nullptr, FOCR_ERR_INVALID, "focr_fleet_release: bad arguments");
     const int rc = focr_pipe_release(pipe_of(f, ticket), pipe_ticket(f, ticket));
-    if (rc == FOCR_OK) f->released.fetch_add(1);
+    if (rc == FOCR_OK) {
+        uint64_t mine = ticket;
+        f->held[(ticket - 1) % f->n_slots].compare_exchange_strong(mine, 0);  // (a stale ticket number never frees a later batch's mark)
+    }
     return rc;
 }
 

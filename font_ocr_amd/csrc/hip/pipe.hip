@@ -47,12 +47,14 @@ struct PinBuf {  // grow-only page-locked host buffer
     size_t bytes = 0;
     void *ensure(size_t want) {
         if (want <= bytes && p) return p;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
+        // the larger buffer first, then the old one goes: a grown buffer never comes back at the old address, so a stale pointer into
+        // the old one cannot happen to look valid (and the tests can tell growth from the address)
+        void *q = nullptr;
         const size_t grow = want + want / 4 + 4096;
-        if (hipHostMalloc(&p, grow, hipHostMallocDefault) != hipSuccess) return p = nullptr;
-        bytes = grow;
+        const bool ok = hipHostMalloc(&q, grow, hipHostMallocDefault) == hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = ok ? q : nullptr;
+        bytes = ok ? grow : 0;
         return p;
     }
     void release() {

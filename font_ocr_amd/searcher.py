@@ -128,6 +128,81 @@ class PinnedPages:
             pass
 
 
+class RegisteredPages:
+    """Context manager that page-locks an existing C-contiguous numpy array for as long as the `with` block lasts
+    (focr_host_register on entry, focr_host_unregister on exit): uploads, Pipeline.prefetch and Pipeline.submit from `.array` are then
+    asynchronous DMAs, as from PinnedPages memory.  The C call takes a page-aligned start, so the whole pages the array lies in are
+    locked (two arrays that share a page cannot both be registered).  Leave the block only after the wait() / host_results() of every batch that reads the array has returned."""
+
+    PAGE = 4096
+
+    def __init__(self, array):
+        if not isinstance(array, np.ndarray) or not array.flags["C_CONTIGUOUS"] or array.nbytes == 0:
+            raise ValueError("RegisteredPages: a non-empty C-contiguous numpy array")
+        self._lib = N.hip()
+        self.array = array
+        self._base = array.ctypes.data // self.PAGE * self.PAGE
+        self._bytes = (array.ctypes.data + array.nbytes + self.PAGE - 1) // self.PAGE * self.PAGE - self._base
+        self._on = False
+
+    def __enter__(self):
+        rc = self._lib.focr_host_register(C.c_void_p(self._base), self._bytes)
+        if rc != 0:
+            raise FocrError(f"[{rc}] {self._lib.focr_last_error_global().decode()}")
+        self._on = True
+        return self
+
+    def __exit__(self, *a):
+        if self._on:
+            self._lib.focr_host_unregister(C.c_void_p(self._base))
+            self._on = False
+
+
+class HostResults:
+    """One batch's results in the page-locked buffers of its context (focr_host_results_t; Pipeline.host_results,
+    Fleet.host_results).  n_pages, n_templates, n_matches, n_lines, n_chars, device_ms are plain numbers.  counts ((n_pages,
+    n_templates) uint32), page_line_off ((n_pages + 1,) uint64), line_char_off ((n_lines + 1,) uint64) and chars ((n_chars,)
+    HIT_DTYPE) are numpy VIEWS of the executor's own memory, None where the C field is NULL (the three line fields of a batch
+    submitted with process_hits=False); `addresses` holds the four raw pointers (0 = NULL).  The views die at the ticket's
+    release: the context's next batch overwrites or frees the buffers.  copy() gives a record that owns its arrays."""
+
+    FIELDS = ("counts", "page_line_off", "line_char_off", "chars")
+
+    def __init__(self, n_pages, n_templates, n_matches, n_lines, n_chars, device_ms, arrays, addresses):
+        self.n_pages, self.n_templates, self.n_matches, self.n_lines, self.n_chars = n_pages, n_templates, n_matches, n_lines, n_chars
+        self.device_ms = device_ms
+        self.counts, self.page_line_off, self.line_char_off, self.chars = arrays
+        self.addresses = dict(addresses)
+
+    @staticmethod
+    def _view(addr, dtype, n):
+        if not addr:
+            return None
+        dtype = np.dtype(dtype)
+        if n == 0:
+            return np.zeros(0, dtype)
+        return np.frombuffer((C.c_uint8 * (n * dtype.itemsize)).from_address(addr), dtype)
+
+    @classmethod
+    def _from_struct(cls, r):
+        arrays = (cls._view(r.counts, np.uint32, r.n_pages * r.n_templates), cls._view(r.page_line_off, np.uint64, r.n_pages + 1),
+                  cls._view(r.line_char_off, np.uint64, r.n_lines + 1), cls._view(r.chars, HIT_DTYPE, r.n_chars))
+        if arrays[0] is not None:
+            arrays = (arrays[0].reshape(r.n_pages, r.n_templates),) + arrays[1:]
+        return cls(int(r.n_pages), int(r.n_templates), int(r.n_matches), int(r.n_lines), int(r.n_chars), float(r.device_ms), arrays,
+                   {k: int(getattr(r, k) or 0) for k in cls.FIELDS})
+
+    def copy(self):
+        """The same record detached from the executor's buffers (it outlives the ticket's release; `addresses` stay what they were)."""
+        return HostResults(self.n_pages, self.n_templates, self.n_matches, self.n_lines, self.n_chars, self.device_ms,
+                           tuple(None if a is None else a.copy() for a in (self.counts, self.page_line_off, self.line_char_off, self.chars)),
+                           self.addresses)
+
+    def lines_flat_bytes(self):
+        """The batch's characters in the layout of Scanner.lines_flat().tobytes() (b"" without process_hits)."""
+        return b"" if self.chars is None else self.chars.tobytes()
+
+
 class Searcher:
     """Per-page state of the reference (src/ncc.rs:128-141, 231-261) for the drop-in FFI symbols.
 
@@ -386,6 +461,18 @@ class Scanner:
         self._ck(self._lib.focr_get_lines(self._h, None, None, _ptr(chars)))
         return chars
 
+    def lines_into(self):
+        """focr_get_lines_into: the lines of the last process_hits() copied from the device straight into freshly allocated numpy
+        buffers -> (page_line_off[n_pages + 1], line_char_off[total_lines + 1], chars[total_chars]) (uint64, uint64, HIT_DTYPE)."""
+        n_lines = int(self._lib.focr_total_lines(self._h))
+        n_chars = int(self._lib.focr_total_chars(self._h))
+        # (every entry is the call's to write: a pattern, not zeros, so that one it leaves out cannot pass for an offset)
+        page_off = np.full(self.n_pages + 1, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        line_off = np.full(n_lines + 1, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        chars = np.zeros(max(n_chars, 1), HIT_DTYPE)  # (the C call wants all three pointers, also for zero characters)
+        self._ck(self._lib.focr_get_lines_into(self._h, _ptr(page_off), _ptr(line_off), _ptr(chars)))
+        return page_off, line_off, chars[:n_chars]
+
     def runners(self):
         """focr_get_runners: one RUNNER_DTYPE record per character of the last process_hits(), aligned with lines_flat(): the size
         of the character's overlap group (`members`) and the group's best hit of ANOTHER letter than the winner's (the last maximum
@@ -573,6 +660,25 @@ class Pipeline:
         batch yet (say it before the last submit with announce_last)."""
         self._lib.focr_pipe_end_of_stream(self._h)
 
+    def set_fetch(self, on=True):
+        """focr_pipe_set_fetch: completing a batch also copies its counts and lines into page-locked host memory of its context
+        (host_results).  Read when a batch is completed: set it before submitting."""
+        rc = self._lib.focr_pipe_set_fetch(self._h, int(bool(on)))
+        if rc != 0:
+            raise FocrError(f"[{rc}] {self._lib.focr_last_error_global().decode()}")
+
+    def host_results(self, ticket):
+        """focr_pipe_host_results: blocks until the batch is done, like wait(); returns its HostResults, whose arrays are views of
+        the context's page-locked buffers — valid until release(ticket), copy() what has to live longer.  Raises the batch's own
+        error if it failed, and FocrError unless fetch was on when the batch was completed (set_fetch)."""
+        r = N.HostResults()
+        rc = self._lib.focr_pipe_host_results(self._h, int(ticket), C.byref(r))
+        self._keep.pop(ticket, None)
+        if rc != 0:
+            sc = self.scanners[(ticket - 1) % len(self.scanners)]
+            raise FocrError(f"[{rc}] " + self._lib.focr_last_error(sc._h).decode())
+        return HostResults._from_struct(r)
+
     def ticket_times(self, ticket):
         """focr_pipe_ticket_times (after wait, before release): dict of host stamps (us since the executor was created) and the
         device-side interval to the previous ticket's completion (ms; < 0: not available)."""
@@ -675,6 +781,41 @@ class Fleet:
             raise FocrError(f"[{rc}] {self._lib.focr_last_error_global().decode()}")
         self._keep[t.value] = luma
         return t.value
+
+    def set_fetch(self, on=True):
+        """focr_fleet_set_fetch: Pipeline.set_fetch on every device's executor (before the first submit)."""
+        rc = self._lib.focr_fleet_set_fetch(self._h, int(bool(on)))
+        if rc != 0:
+            raise FocrError(f"[{rc}] {self._lib.focr_last_error_global().decode()}")
+
+    def host_results(self, ticket):
+        """focr_fleet_host_results: Pipeline.host_results for a fleet ticket; the views die at release(ticket)."""
+        r = N.HostResults()
+        rc = self._lib.focr_fleet_host_results(self._h, int(ticket), C.byref(r))
+        self._keep.pop(ticket, None)
+        if rc != 0:
+            raise FocrError(f"[{rc}] {self._lib.focr_last_error_global().decode()}")
+        return HostResults._from_struct(r)
+
+    def announce_last(self):
+        """focr_fleet_announce_last: the next n_devices batches end their devices' streams (call before submitting them)."""
+        rc = self._lib.focr_fleet_announce_last(self._h)
+        if rc != 0:
+            raise FocrError(f"[{rc}] {self._lib.focr_last_error_global().decode()}")
+
+    def end_of_stream(self):
+        """focr_fleet_end_of_stream: Pipeline.end_of_stream on every device's executor (right after the last submit)."""
+        rc = self._lib.focr_fleet_end_of_stream(self._h)
+        if rc != 0:
+            raise FocrError(f"[{rc}] {self._lib.focr_last_error_global().decode()}")
+
+    def pipe(self, index):
+        """focr_fleet_pipe: the raw handle (an int) of the index-th device's executor, for the focr_pipe_* getters (it belongs to
+        the fleet: submit to it only through the fleet)."""
+        h = self._lib.focr_fleet_pipe(self._h, int(index))
+        if not h:
+            raise IndexError(f"Fleet.pipe: no executor {index} (the fleet has {self.n_devices})")
+        return int(h)
 
     def wait(self, ticket):
         """Blocks until the batch is done; returns a Scanner view of the context holding its results."""

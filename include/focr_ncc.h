@@ -438,8 +438,9 @@ int focr_pipe_release(focr_pipe_t *pipe, uint64_t ticket);
  * them in that order and the output order is the submission order whatever the device count.  No collective: results
  * converge on the host that consumes them (a device-resident consumer uses focr_rccl.h).  `devices` == NULL or
  * n_devices == 0: all visible devices.  At most focr_fleet_slots() = n_devices * lanes_per_device * DEPTH batches are
- * outstanding: with every context holding an unreleased batch focr_fleet_submit returns FOCR_ERR_STATE ("release the oldest
- * ticket first") instead of waiting for a release that a single-threaded consumer could never make; with
+ * outstanding: ticket T takes the context of ticket T - focr_fleet_slots(), and while that one is unreleased (whatever other
+ * tickets have been released meanwhile) focr_fleet_submit returns FOCR_ERR_STATE ("release the oldest ticket first") and
+ * takes no ticket, instead of waiting for a release that a single-threaded consumer could never make; with
  * pages_on_device != 0 the pointer must belong to focr_fleet_device_of(ticket it will get) — host pages are the normal case.
  * The `ncc` binary is this loop. */
 typedef struct focr_fleet focr_fleet_t;
