@@ -56,6 +56,13 @@
 //     1/64 px (N <= 64, default 0).  stdout is a CSV: the header font,shift,cost,line_base,error and one row per font, error =
 //     line_base + cost; the row with the lowest cost is the font (and its shift what to add to -x).  A character of TEXT
 //     outside the alphabet is a usage error, and so is --rank-shift without --rank-text.
+//   * --rank-text TEXT --rank-drift W [--rank-step N] fits every character's pen under each font instead
+//     (focr_decoder_align_text from start 0: offsets of up to W / 64 px from the font's own pens, W <= 1024, consecutive
+//     characters' offsets at most N / 64 px apart, N <= 64, default 2), for a page whose kerning or x is not the font's.  The CSV
+//     is font,first,last,cost,line_base,error,scale,x64: the first and the last character's offset, and the least-squares line
+//     of the fitted pens on the font's own (include/focr_decode.h has the sums): scale (%.6f) is the page's kerning relative to
+//     the font's, x64 (%.2f) what to add to -x in 1/64 px; both are empty without two inked characters.  --rank-drift without
+//     --rank-text or beside --rank-shift is a usage error, and so is --rank-step without --rank-drift.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -95,8 +102,8 @@ struct Args {
     std::vector<std::string> img, candidate_specs;
     std::vector<FontSpec> candidates;
     std::string fonts, verify_fonts, rank_text;
-    bool have_fonts = false, have_verify_fonts = false, have_rank_text = false, have_rank_shift = false;
-    uint32_t rank_shift = 0;
+    bool have_fonts = false, have_verify_fonts = false, have_rank_text = false, have_rank_shift = false, have_rank_drift = false, have_rank_step = false;
+    uint32_t rank_shift = 0, rank_drift = 0, rank_step = 2;
     std::string font, alphabet = DEFAULT_ALPHABET, verify, test, scores, margins, baselines;
     bool hinting = false, have_verify = false, have_test = false, have_scores = false, whole_line = false, have_margins = false;
     bool have_baselines = false, have_y_bits = false;
@@ -145,6 +152,8 @@ void print_help() {
            "      --verify-fonts <DIR>             [extension] Dir for verify images of a --font-candidate run: every line drawn in its winning font (only with --font-candidate)\n"
            "      --rank-text <TEXT>               [extension] Decode nothing: score TEXT at the first line slot of the first image under -f and every --font-candidate, a CSV row per font on stdout\n"
            "      --rank-shift <N>                 [extension] Score TEXT at the rigid shifts -N ..= N in 1/64 px and keep the best, N <= 64 (only with --rank-text) [default: 0]\n"
+           "      --rank-drift <W>                 [extension] Fit every character's pen of TEXT instead: offsets of up to W/64 px from the font's own pens, W <= 1024; the CSV gains first,last,scale,x64 (only with --rank-text, not with --rank-shift)\n"
+           "      --rank-step <N>                  [extension] Consecutive characters' offsets differ by at most N/64 px, N <= 64 (only with --rank-drift) [default: 2]\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -207,6 +216,8 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--verify-fonts") a.verify_fonts = c.need(), a.have_verify_fonts = true;
         else if (k == "--rank-text") a.rank_text = c.need(), a.have_rank_text = true;
         else if (k == "--rank-shift") a.rank_shift = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64"), a.have_rank_shift = true;
+        else if (k == "--rank-drift") a.rank_drift = c.u32_at_most(FOCR_ALIGN_DRIFT_MAX, "the radius is at most 1024"), a.have_rank_drift = true;
+        else if (k == "--rank-step") a.rank_step = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64"), a.have_rank_step = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -247,6 +258,9 @@ Args parse_args(int argc, char **argv) {
     if (a.have_verify_fonts && a.candidates.empty())
         usage_error("the argument '--verify-fonts <DIR>' cannot be used without '--font-candidate <SPEC>'");
     if (a.have_rank_shift && !a.have_rank_text) usage_error("the argument '--rank-shift <N>' cannot be used without '--rank-text <TEXT>'");
+    if (a.have_rank_drift && !a.have_rank_text) usage_error("the argument '--rank-drift <W>' cannot be used without '--rank-text <TEXT>'");
+    if (a.have_rank_drift && a.have_rank_shift) usage_error("the argument '--rank-drift <W>' cannot be used with '--rank-shift <N>'");
+    if (a.have_rank_step && !a.have_rank_drift) usage_error("the argument '--rank-step <N>' cannot be used without '--rank-drift <W>'");
     for (const auto &[with, name] : {std::pair<bool, const char *>{a.have_scores, "--scores <SCORES>"}, {a.pen_search != 0, "--pen-search <N>"},
                                      {a.pen_slack != 0, "--pen-slack <N>"}, {a.have_margins, "--margins <MARGINS>"},
                                      {a.baseline_search != 0, "--baseline-search <N>"}, {a.whole_baseline != 0, "--whole-baseline <N>"},
@@ -350,6 +364,39 @@ int run_rank(const Args &args, const std::vector<uint32_t> &alphabet, const std:
         die(std::string("--rank-text: ") + focr_decoder_last_error(dec), 1);
     std::vector<focr_text_line_t> lines(fonts.size());
     for (size_t k = 0; k < lines.size(); k++) lines[k] = focr_text_line_t{0, args.y, 0, (uint32_t)text.size(), (uint32_t)k};
+    if (args.have_rank_drift) {  // the pens fitted under every font, and the line through them
+        std::vector<focr_text_align_t> fit(lines.size());
+        std::vector<uint32_t> pens(std::max<size_t>(lines.size() * text.size(), 1));
+        std::vector<int32_t> terms(pens.size());
+        if (focr_decoder_align_text(dec, luma, 0, 1, W, H, args.x, args.width, args.line_height, lines.data(), lines.size(), text.data(), text.size(), nullptr, 0,
+                                    0, args.rank_drift, args.rank_step, pens.data(), terms.data(), fit.data()) != 0)
+            die(std::string("--rank-text: focr_decoder_align_text: ") + focr_decoder_last_error(dec), 1);
+        focr_decoder_destroy(dec);
+        printf("font,first,last,cost,line_base,error,scale,x64\n");
+        for (size_t k = 0; k < fit.size(); k++) {
+            // include/focr_decode.h's sums, in list order: u the nominal pen (start 0), p the fitted one, over the inked characters
+            double n = 0, su = 0, sp = 0, suu = 0, sup = 0;
+            uint64_t nominal = 0;
+            for (size_t g = 0; g < text.size(); g++) {
+                if (terms[k * text.size() + g] != 0) {
+                    const double u = (double)nominal, p = (double)pens[k * text.size() + g];
+                    n += 1, su += u, sp += p, suu += u * u, sup += u * p;
+                }
+                nominal += (uint64_t)(int)rintf(fonts[k].glyphs[text[g]].increment * 64.0f);  // below 2^24: the call accepted the line
+            }
+            const double d = n * suu - su * su;
+            printf("%zu,%d,%d,%lld,%llu,%lld,", k, (int)fit[k].first, (int)fit[k].last, (long long)fit[k].cost, (unsigned long long)fit[k].line_base,
+                   (long long)fit[k].line_base + (long long)fit[k].cost);
+            if (n < 2 || d == 0) printf(",\n");
+            else {
+                const double scale = (n * sup - su * sp) / d;
+                printf("%.6f,%.2f\n", scale, (sp - scale * su) / n);
+            }
+        }
+        for (focr_decode_font_t &f : fonts) focr_decode_font_free(&f);
+        free(luma);
+        return 0;
+    }
     std::vector<focr_text_score_t> got(lines.size());
     if (focr_decoder_score_text(dec, luma, 0, 1, W, H, args.x, args.width, args.line_height, lines.data(), lines.size(), text.data(), nullptr, nullptr,
                                 text.size(), nullptr, 0, args.rank_shift, nullptr, got.data()) != 0)

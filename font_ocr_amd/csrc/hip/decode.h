@@ -10,8 +10,10 @@
 //   decode_images.hip          the verify and --test images
 //   decode_text.hip            verify_text: a caller's lines drawn over their pages, each in any uploaded font
 //   decode_score.hip           score_text: the decoder's cost of a caller's lines, each in any uploaded font (over decode_pen.h)
+//   decode_align.hip           align_text: a caller's lines with every character's pen fitted to the page (over decode_score.h, align_plan.h)
 // (decode_line.h lies between decode.h and the files of a run; decode_line_frac.hip, decode_images.hip and decode_text.hip include decode.h alone.)
-// Below decode.h lie text_plan.h, host code alone (the input rules of a caller's reading and the record the device reads of a line), and
+// Below decode.h lie text_plan.h, host code alone (the input rules of a caller's reading and the record the device reads of a line),
+// align_plan.h on top of it (the host plan of align_text: nominal pens, the 2^24 rule, the backpointers' budget), and
 // decode_font.h, host code alone: the record of an uploaded font (HostFont), the glyph and verify records the kernels
 // read, and the five font uploaders' checks and packing.  Here: the batch geometry, both line grids, the owners of the fonts' device tables, the tile frame of
 // the compose kernels (ncc_images.hip is its third user), the blank test's crop, the settings (Modes), what a run resolves
@@ -27,6 +29,7 @@
 
 #include "decode_font.h"
 #include "devmem.h"
+#include "align_plan.h"
 #include "focr_decode.h"
 #include "text_plan.h"
 
@@ -432,7 +435,7 @@ struct Stage {  // the kernels of one entry point's last call: device events aro
 struct focr_decoder {
     int device = 0;
     hipStream_t stream = nullptr;
-    focr_dec::Stage run, verify, test, vtext, stext;
+    focr_dec::Stage run, verify, test, vtext, stext, atext;
     std::string err;
     // the fonts (decode_font.h): font k of 0 ..= K is font_at(k).  n_glyphs is the alphabet's size and "a decode font is set": `font` and
     // `tables` are that font's, and a set_font that succeeds replaces all three together
@@ -515,6 +518,16 @@ struct focr_decoder {
     focr::DevArray<focr_text_score_t> d_sout;
     focr::DevArray<focr_dec::FontDesc> d_sdesc;
     focr::DevArray<int32_t> d_sterms;
+    // align_text (decode_align.hip): the staged reading is the one above; everything else is its own: the plan's records and nominal
+    // pens, the backpointers (one byte per character and state), the fitted pens, the terms, the results, the fonts' descriptors and
+    // (only when a line's strip and the programme's rows do not fit in LDS together) the strips
+    focr::DevArray<focr_dec::AlignRec> d_arecs;
+    focr::DevArray<uint32_t> d_anominal, d_apens;
+    focr::DevArray<int8_t> d_aback;
+    focr::DevArray<int32_t> d_aterms;
+    focr::DevArray<focr_text_align_t> d_aout;
+    focr::DevArray<focr_dec::FontDesc> d_adesc;
+    focr::DevArray<uint8_t> d_astrips;
 };
 
 namespace focr_dec {

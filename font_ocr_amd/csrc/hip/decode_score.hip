@@ -17,34 +17,14 @@
 //     candidate (N = 0) that pass is the only one.
 // Fonts are read as the font search reads them (a FontDesc per font 0 ..= K), y-phases as the baseline search does (the
 // tables of focr_decoder_set_baseline_fonts, v-major).  Everything is exact integer arithmetic but the f32 pen.  The reading is
-// checked by text_plan.h and staged by stage_text (decode.h), as focr_decoder_verify_text's is.
-#include "decode_pen.h"
+// checked by text_plan.h and staged by stage_text (decode.h), as focr_decoder_verify_text's is.  The strip staging, the fonts'
+// record and the wave's sum are decode_score.h's, shared with focr_decoder_align_text (decode_align.hip).
+#include "decode_score.h"
 
 namespace focr_dec {
 
-constexpr uint32_t SCORE_THREADS = 256;  // one workgroup of four waves per listed line
-constexpr uint32_t SCORE_WAVES = SCORE_THREADS / 64;
 // per wave: (cost, rank) of the search, the winner's partial cost, the partial line_base; in front of the strip
 constexpr uint32_t SCORE_RED_BYTES = SCORE_WAVES * 4 * 8;
-
-// The fonts 0 ..= K and the y-phases v >= 1 of font 0 as a line reads them.
-struct ScoreFonts {
-    const DevGlyph *glyphs, *fglyphs, *yglyphs;
-    const int2 *offs, *foffs, *yoffs;
-    const uint32_t *bitmaps, *fbitmaps, *ybitmaps;
-    const FontDesc *desc;  // [K + 1]: glyph_base, end_dw, origin_x and origin_d (64 * origin_x where it is whole)
-    uint32_t n_glyphs, yn_dw;
-    uint32_t bits;         // B of line_q
-};
-
-// The tables one line renders from, chosen once per workgroup.
-struct ScoreFont {
-    const DevGlyph *glyphs;
-    const int2 *offs;
-    const uint32_t *bitmaps, *end;
-    float origin_x;
-    int origin_d;
-};
 
 struct ScoreText {  // the line's text and how it is placed
     const uint16_t *chars;
@@ -52,35 +32,6 @@ struct ScoreText {  // the line's text and how it is placed
     const int8_t *offs;    // null: no per-character offsets
     uint32_t n;
 };
-
-// The wave's sum of every lane's v (mod 2^64, so a signed sum as well), in every lane.
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-    for (int m = 32; m >= 1; m >>= 1) v += shfl_xor_u64(v, m);
-    return v;
-}
-
-// The inverted strip of a crop (w columns by h rows at src, PAD zero bytes in front of every row, sdw dwords a row), by a
-// workgroup of SCORE_THREADS; this thread's share of the sum of r^2.
-__device__ __forceinline__ uint64_t score_stage(uint32_t *dst, const uint8_t *__restrict__ src, uint32_t page_w, uint32_t w, uint32_t h, uint32_t sdw) {
-    uint64_t acc = 0;
-    for (uint32_t i = threadIdx.x; i < sdw * h; i += SCORE_THREADS) {
-        const uint32_t row = i / sdw;
-        const int col = 4 * (int)(i % sdw) - (int)PAD;
-        uint32_t v = 0;
-        for (int b = 0; b < 4; b++)
-            if (col + b >= 0 && (uint32_t)(col + b) < w) v |= (uint32_t)(uint8_t)(255 - src[(size_t)row * page_w + col + b]) << (8 * b);
-        dst[i] = v;
-        acc += __builtin_amdgcn_udot4(v, v, 0u, false);
-    }
-    return acc;
-}
-
-// A line's crop as image::crop_imm clamps it: its first pixel and its rows (0 when the crop is empty either way).
-__device__ __forceinline__ const uint8_t *score_crop(const uint8_t *__restrict__ pages, const Geometry &g, const TextRec &l, uint32_t *h) {
-    const uint32_t yc = std::min(l.y, g.page_h);
-    *h = g.w ? std::min(g.line_height, g.page_h - yc) : 0;
-    return pages + (size_t)l.page * g.page_w * g.page_h + (size_t)yc * g.page_w + g.x;
-}
 
 // 1. (only when the strip does not fit in LDS) every listed line's strip into global memory, one workgroup per line
 __global__ __launch_bounds__(SCORE_THREADS) void score_strip_kernel(const uint8_t *__restrict__ pages, Geometry g, const TextRec *__restrict__ in,
@@ -161,19 +112,8 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_text_kernel(const uint8_t
     acc = wave_sum(acc);
     if (lane == 0) red[3 * SCORE_WAVES + wave] = acc;
     __syncthreads();  // the strip is staged
-    // the line's font, its y-phase and its rows' move: uniform across the workgroup
-    const FontDesc fd = fonts.desc[l.font];
-    const uint32_t v = (uint32_t)l.q & ((1u << fonts.bits) - 1);  // 0 for every font but 0 (refused on the host)
-    const int d = l.q >> fonts.bits;                              // floor
-    ScoreFont f;
-    if (l.font) {
-        f = ScoreFont{fonts.fglyphs + fd.glyph_base, fonts.foffs + (size_t)fd.glyph_base * 64, fonts.fbitmaps, fonts.fbitmaps + fd.end_dw, fd.origin_x, fd.origin_d};
-    } else if (v) {
-        const size_t at = (size_t)(v - 1) * fonts.n_glyphs;
-        f = ScoreFont{fonts.yglyphs + at, fonts.yoffs + at * 64, fonts.ybitmaps, fonts.ybitmaps + fonts.yn_dw, fd.origin_x, fd.origin_d};
-    } else {
-        f = ScoreFont{fonts.glyphs, fonts.offs, fonts.bitmaps, fonts.bitmaps + fd.end_dw, fd.origin_x, fd.origin_d};
-    }
+    int d;
+    const ScoreFont f = score_font(fonts, l, &d);
     const ScoreText t{chars + l.first, pens ? pens + l.first : nullptr, offs ? offs + l.first : nullptr, l.n};
     const int w = (int)g.w;
     uint32_t best_rank = 0;
@@ -244,20 +184,15 @@ extern "C" int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages
     g.stride = ((g.w + PAD + 3) / 4 + 2) * 4;  // line_cap's
     const size_t strip_bytes = (size_t)g.stride * line_height;
     const bool lds = strip_bytes + SCORE_RED_BYTES <= LDS_STRIP_MAX;  // the strip shares LDS with the waves' pairs and sums
-    WholePlan plan;
-    if (fonts_plan(dec, &plan)) return 1;  // the descriptors of the fonts 0 ..= K
-    for (size_t k = 0; k < plan.fonts.size(); k++) plan.fonts[k].origin_d = whole_origin(plan.fonts[k].origin_x) ? 64 * (int)plan.fonts[k].origin_x : 0;
     DEC_CHECK(hipSetDevice(dec->device));
+    WholePlan plan;
+    ScoreFonts f;
+    if (score_fonts(dec, &plan, dec->d_sdesc, line_q ? y_bits : 0, &f)) return 1;
     StagedText st;
     if (stage_text(dec, in, text.recs, pages, pages_on_device, n_pages * page_w * page_h, &st)) return 1;
-    DEC_GROW(dec->d_sdesc, plan.fonts.size());
     if (terms) DEC_GROW(dec->d_sterms, std::max<size_t>(n_terms, 1));
     DEC_GROW(dec->d_sout, n_lines);
     if (!lds) DEC_GROW(dec->d_sstrips, strip_bytes * n_lines);
-    DEC_CHECK(hipMemcpyAsync(dec->d_sdesc, plan.fonts.data(), plan.fonts.size() * sizeof(FontDesc), hipMemcpyHostToDevice, dec->stream));
-    const GlyphTables &t = dec->tables, &c = dec->ftables, &y = dec->yfonts.tables;
-    const ScoreFonts f{t.glyphs, c.glyphs, y.glyphs, t.offs, c.offs, y.offs, t.bitmaps.as<const uint32_t>(), c.bitmaps.as<const uint32_t>(),
-                       y.bitmaps.as<const uint32_t>(), dec->d_sdesc, dec->n_glyphs, y.n_dw, line_q ? y_bits : 0};
     int32_t *d_terms = terms ? (int32_t *)dec->d_sterms : nullptr;
     DEC_CHECK(hipEventRecord(dec->stext.begin, dec->stream));
     if (lds) {

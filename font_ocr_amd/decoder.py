@@ -40,6 +40,11 @@
         # the decoder's own cost of such a reading: scores[page][line] is a TextScore(base, cost, shift, terms)
         base, cost, shift = dec.rank_text(luma_pages[0], 39, "the first line as a person reads it", 45, 608, 12, shift=8)
         # a known string under the decode font and every candidate: the argmin of cost is the font, no decoding
+        aligned = dec.align_text(luma_pages, pages, 45, 608, 12, start=64, drift=128, step=4)
+        # every character's pen fitted to the page: aligned[page][line] is a TextAlign(base, cost, first, last, pens, terms)
+        base, cost, first, last, fit = dec.rank_text_aligned(luma_pages[0], 39, "the first line as a person reads it", 45, 608, 12, drift=128, step=4)
+        # the same ranking with the pens fitted under each font; fit[k] = (scale, x64): the page's kerning relative to font k's
+        # and where its text starts, in 1/64 px
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -88,6 +93,50 @@ class TextScore(collections.namedtuple("TextScore", "base cost shift terms")):
     against the crop where footprints do not overlap."""
 
     __slots__ = ()
+
+
+class TextAlign(collections.namedtuple("TextAlign", "base cost first last pens terms")):
+    """The forced alignment of one line the caller supplied (LineDecoder.align_text).  base: the sum of r^2 over the line's
+    crop (int); cost: the sum of its characters' footprint terms at the fitted pens (int); first, last: the first and the
+    last character's offset from its nominal pen in 1/64 px; pens: each character's fitted pen in 1/64 px (a uint32 array
+    aligned with the text), which score_text(pens=) and verify_text(pens=) take as they are; terms: each character's footprint
+    term there (an int32 array; None when not asked for)."""
+
+    __slots__ = ()
+
+
+def nominal_pens(font, text, start=0):
+    """The pens the whole-line programme gives `text` in the DecodeFont `font`: start + the running sum of
+    inc64 = rint(increment * 64) in f32, in 1/64 px: what align_text measures its offsets from."""
+    inc = font.increments()
+    index = {c: i for i, c in reversed(list(enumerate(font.alphabet)))}
+    inc64 = [int(np.rint(np.float32(inc[index[c]]) * np.float32(64))) for c in text]
+    return np.array([int(start) + sum(inc64[:g]) for g in range(len(text))], dtype=np.int64)
+
+
+def fit_pens(nominal, pens, terms, start=None):
+    """The least-squares line of pen on nominal - start over the characters whose term is not 0 (a space never has one):
+    (scale, x64), the page's kerning relative to the font's and the pen of a character at nominal `start` in 1/64 px, or
+    (None, None) with fewer than two such characters or when they share one nominal pen.  start defaults to nominal[0].
+    The sums are include/focr_decode.h's, in list order and in double arithmetic, so every implementation agrees to the bit."""
+    nominal = [int(v) for v in nominal]
+    if start is None:
+        start = nominal[0] if nominal else 0
+    k, su, sp, suu, sup = 0, 0.0, 0.0, 0.0, 0.0
+    for m, p, t in zip(nominal, pens, terms):
+        if int(t) == 0:
+            continue
+        u, q = float(m - int(start)), float(int(p))
+        k += 1
+        su += u
+        sp += q
+        suu += u * u
+        sup += u * q
+    d = k * suu - su * su
+    if k < 2 or d == 0.0:
+        return None, None
+    scale = (k * sup - su * sp) / d
+    return scale, (sp - scale * su) / k
 
 
 # The modes of one decode()/decode_device() call, checked (LineDecoder._modes).
@@ -291,6 +340,7 @@ class LineDecoder:
         self._vcands = None  # ... and their VerifyFonts, once verify_text() has built them
         self.last_verify_text_ms = 0.0
         self.last_score_text_ms = 0.0
+        self.last_align_text_ms = 0.0
         for attr, _, default in _SETTINGS:
             setattr(self, attr, default)
 
@@ -510,18 +560,82 @@ class LineDecoder:
 
         return pages, lines, used, groups()
 
+    def align_text(self, luma_pages, lines, x, width, line_height, fonts=None, baselines=None, y_bits=0, start=0, drift=64, step=2, terms=True):
+        """A forced alignment of a reading the caller supplies (focr_decoder_align_text): per [page][line] a
+        TextAlign(base, cost, first, last, pens, terms).  luma_pages, lines, fonts, baselines and y_bits are score_text()'s.
+        Every character g of a line starts from its nominal pen (nominal_pens(font, text, start): `start` in 1/64 px plus the
+        font's own advances) and may sit e_g / 64 px from it, -drift <= e_g <= drift, with consecutive characters' offsets at
+        most step / 64 px apart; the call returns the pens with the lowest summed footprint term (ties: the pen search's rank,
+        0, -1, +1, ...).  step=0 is a rigid search of radius drift.  fit_pens() turns a result into the page's kerning and x.
+        A character outside the alphabet raises ValueError.  The last decode, its results and its verify() are left as they were."""
+        if self.font is None:
+            raise DecoderError("set_font() first")
+        if not 0 <= int(drift) <= 1024:
+            raise ValueError(f"drift must be 0 .. 1024 (1/64 px), not {drift!r}")
+        if not 0 <= int(step) <= 64:
+            raise ValueError(f"step must be 0 .. 64 (1/64 px), not {step!r}")
+        if not 0 <= int(start) < 1 << 24:
+            raise ValueError(f"start must be 0 .. 2^24 - 1 (1/64 px), not {start!r}")
+        if not 0 <= int(y_bits) <= 3:
+            raise ValueError(f"y_bits must be 0 .. 3, not {y_bits!r}")
+        if int(width) <= 0 or int(line_height) <= 0:
+            raise ValueError("align_text: width and line_height must be positive")
+        _, lines, _, groups = self._pack_text("align_text", luma_pages, lines, fonts, None, None, baselines)
+        out = [[None] * len(pg) for pg in lines]
+        for _, batch, recs, chars, _, qs, where in groups:
+            got = self._align_text(batch, recs, chars, qs if baselines is not None else None, x, width, line_height, y_bits, start, drift, step, terms)
+            for (i, q), a in zip(where, got):
+                out[i][q] = a
+        return out
+
+    def _align_text(self, batch, recs, chars, qs, x, width, line_height, y_bits, start, drift, step, terms):
+        """One focr_decoder_align_text call over an (N, H, W) uint8 batch, its arguments as _score_text's.  A TextAlign per record."""
+        n, h, w = batch.shape
+        larr = (N.TextLine * max(1, len(recs)))(*recs)
+        carr = np.array(chars, dtype=np.uint16) if chars else np.zeros(1, dtype=np.uint16)
+        qarr = np.array(qs, dtype=np.int8) if qs else None
+        n_out = sum(r[3] for r in recs)
+        parr = np.zeros(max(1, n_out), dtype=np.uint32)
+        tarr = np.zeros(max(1, n_out), dtype=np.int32) if terms else None
+        aarr = (N.TextAlignStruct * max(1, len(recs)))()
+        self._check(self._lib.focr_decoder_align_text(self._h, _ptr(batch), 0, n, w, h, int(x), int(width), int(line_height), larr, len(recs), _ptr(carr),
+                                                      len(chars), _ptr(qarr), int(y_bits), int(start), int(drift), int(step), _ptr(parr), _ptr(tarr), aarr))
+        self.last_align_text_ms = float(self._lib.focr_decoder_last_align_text_ms(self._h))
+        out, at = [], 0
+        for r, a in zip(recs, aarr):
+            out.append(TextAlign(int(a.line_base), int(a.cost), int(a.first), int(a.last), parr[at: at + r[3]].copy(),
+                                 tarr[at: at + r[3]].copy() if terms else None))
+            at += r[3]
+        return out
+
     def rank_text(self, page, y, text, x, width, line_height, shift=0):
         """Which uploaded font renders a known string closest to the page: text scored at line slot (x, y) of one luma page
         under the decode font and every candidate of set_font_candidates() in one call, the same line listed K + 1 times.
         Returns (base, cost[K + 1], shift[K + 1]): the crop's sum of r^2, and per font its cost (int64) and its winning rigid
         shift in 1/64 px (shift=N searches -N ..= N).  The argmin over (cost, k) is the font; base + cost[k] is its squared
-        error (footprints that overlap counted once each).  Nothing is decoded."""
+        error (footprints that overlap counted once each).  Nothing is decoded.  rank_text_aligned() fits the pens instead."""
         page = np.asarray(page)
         if page.ndim != 2:
             raise ValueError("rank_text takes one luma page (H, W)")
         k1 = len(self._candidates) + 1
         got = self.score_text([page], [[(y, text)] * k1], x, width, line_height, fonts=[list(range(k1))], shift=shift, terms=False)[0]
         return got[0].base, np.array([s.cost for s in got], dtype=np.int64), np.array([s.shift for s in got], dtype=np.int32)
+
+    def rank_text_aligned(self, page, y, text, x, width, line_height, drift=64, step=2, start=0):
+        """rank_text() with the pens fitted under every font (align_text(start=start, drift=drift, step=step), the same line
+        listed K + 1 times), for a page whose kerning or x is not the font's, where a rigid shift loses the page's own font.
+        Returns (base, cost[K + 1], first[K + 1], last[K + 1], fit[K + 1]): the crop's sum of r^2 and per font its cost (int64),
+        its first and last character's offset in 1/64 px (int32) and fit_pens()'s (scale, x64), (None, None) without a fit.  It is
+        a method of its own, so that rank_text() stays exactly what it was: a rigid shift and a drift do not combine."""
+        page = np.asarray(page)
+        if page.ndim != 2:
+            raise ValueError("rank_text_aligned takes one luma page (H, W)")
+        k1 = len(self._candidates) + 1
+        got = self.align_text([page], [[(y, text)] * k1], x, width, line_height, fonts=[list(range(k1))], start=start, drift=drift, step=step)[0]
+        fonts = [self.font] + list(self._candidates)
+        fits = [fit_pens(nominal_pens(f, text, start), a.pens, a.terms, start) for f, a in zip(fonts, got)]
+        return (got[0].base, np.array([a.cost for a in got], dtype=np.int64), np.array([a.first for a in got], dtype=np.int32),
+                np.array([a.last for a in got], dtype=np.int32), fits)
 
     def test_images(self, luma_pages, x, y, width, line_height, line_advance, rgba=None, rect=True, text=True):
         """focr --test on the device: (rect_images, text_images), each a per-page list of (H, W, 4) uint8 RGBA images,

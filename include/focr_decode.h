@@ -619,7 +619,7 @@ uint32_t focr_decoder_last_verify_text_launches(const focr_decoder_t *dec);
  * their timings answer as they did before, and it needs no run at all.  pages as for focr_decoder_run.  Returns when out
  * and terms are written; with n_lines == 0 nothing is launched.
  * What it does not do: a per-line x; a vertical search (list the line at several (y, q)); a forced alignment that fits
- * each character's offset to a known text; the true composed error where footprints overlap (line_base + cost counts an
+ * each character's offset to a known text (that is focr_decoder_align_text, below); the true composed error where footprints overlap (line_base + cost counts an
  * overlap once per glyph; the composed error stays focr_decoder_verify_text's page sum); any change to focr_decoder_run. */
 typedef struct focr_text_score {
     uint64_t line_base;   /* sum of r^2 over the line's crop, r = 255 - luma */
@@ -638,6 +638,66 @@ int focr_decoder_score_text(focr_decoder_t *dec, const uint8_t *pages, int pages
  * refusal or a call without lines). */
 float    focr_decoder_last_score_text_ms(const focr_decoder_t *dec);
 uint32_t focr_decoder_last_score_text_launches(const focr_decoder_t *dec);
+
+/* ---- device: a forced alignment (an extension: the fit score_text above leaves out) ------------------------------- */
+
+/* focr_decoder_score_text costs a known line at pens it is given, or at the font's own advances moved rigidly by at most one
+ * pixel.  A page set at another kerning, moved by a fraction of a pixel or snapped to the pixel grid loses its own font
+ * there.  focr_decoder_align_text fits every character's pen to the page instead: a banded dynamic programme over offsets
+ * from the font's own pens, one line per listed line, exact integer arithmetic throughout.
+ *   - lines, chars, line_q / y_bits, the crop (x_start, width, line_height at the line's y) and line_base are
+ *     focr_decoder_score_text's; the listed line l has characters c_0 .. c_{n-1} in font k = lines[l].font;
+ *   - inc64[i] = (int)rintf(increment[i] * 64) of font k, the whole-line programme's; the nominal pen of character g is
+ *     m_g = start + sum over h < g of inc64[c_h], in 1/64 px;
+ *   - a state is (g, e) with -W <= e <= W, W = drift <= FOCR_ALIGN_DRIFT_MAX; it is live when m_g + e >= 0;
+ *   - its placement is focr_decoder_score_text's pens placement at the pen m_g + e: delta = 64 * origin_x_k + m_g + e, phase
+ *     delta & 63, whole-pixel shift delta >> 6; the line's q applies as there (y-phase q & (2^B - 1), rows moved q >> B);
+ *     the bitmap is clipped to the crop on all four sides; T(g, e) is the int32 footprint term there;
+ *   - F(0, e) = T(0, e) for live e; for g > 0, F(g, e) = T(g, e) + the lowest (F(g - 1, e - d), rank(d)) over d in -N ..= N,
+ *     N = step <= FOCR_PEN_SEARCH_MAX, with (g - 1, e - d) inside the band, live and reachable; rank is the pen search's
+ *     (0, -1, +1, -2, ...); back(g, e) is that d, and a state without such a d is unreachable;
+ *   - the line ends in the reachable e with the lowest (F(n - 1, e), rank(e)); the walk back is e_{g-1} = e_g - back(g, e_g);
+ *   - out[l] = { line_base, cost = F(n - 1, e_{n-1}), first = e_0, last = e_{n-1} }; per listed character, line l's at the
+ *     running sum of n_chars over the lines before it (as score_text's terms): pens_out takes the pen m_g + e_g, terms
+ *     (NULL: not wanted) the term T(g, e_g); the terms of a line sum to its cost, and focr_decoder_score_text and
+ *     focr_decoder_verify_text take the pens as they are;
+ *   - n == 0 gives cost 0 and first = last = 0; an empty crop has every term 0, so the ranks give e_g = 0 throughout (e = 0
+ *     is live whatever start is); an offset costs nothing; N = 0 is a rigid
+ *     search of radius W (with start >= W and W <= 64 it is score_text's shift search over the nominal pens).
+ * The fit of the pens (what the kerning and x of the page were): over the characters g of a line whose term is not 0 (a space
+ * never has one), in list order and in double arithmetic, with u_g = (double)(m_g - start) and p_g = (double)pen_g and k their
+ * number: Su = sum u_g, Sp = sum p_g, Suu = sum u_g * u_g, Sup = sum u_g * p_g, D = k * Suu - Su * Su;
+ * scale = (k * Sup - Su * Sp) / D and x64 = (Sp - scale * Su) / k, each product and sum rounded once, left to right as written;
+ * there is no fit when k < 2 or D == 0.  scale is the page's kerning relative to the font's, x64 the pen of a character at
+ * nominal `start`, in 1/64 px.
+ * Refused, each with its own message and before anything is launched: what focr_decoder_score_text refuses of the same
+ * arguments; NULL pens_out where there are lines; drift or step above its maximum; per line (the message names its index) a
+ * font whose origin_x is fractional or negative, and start + the sum of its inc64 + drift >= 2^24; the backpointers of the
+ * call (one byte per listed character and state of the band, n_out * (2 * drift + 1)) above 256 MiB: the message says to list
+ * fewer lines or ask for less drift.
+ * The call runs one launch, or two when a line's strip and the programme's two cost rows do not fit in LDS together (the strips
+ * are then built in global memory first), in buffers of its own: the last run, its getters, its verify, and score_text's and
+ * verify_text's last timings answer as they did before, and it needs no run at all.  pages as for focr_decoder_run.  Returns
+ * when out, pens_out and terms are written; with n_lines == 0 nothing is launched.
+ * What it does not do: a per-line start; a vertical fit (list the line at several q); alignment inside focr_decoder_run; a
+ * penalty on offsets. */
+enum { FOCR_ALIGN_DRIFT_MAX = 1024 };
+typedef struct focr_text_align {
+    uint64_t line_base;   /* sum of r^2 over the line's crop, r = 255 - luma */
+    int64_t  cost;        /* F(n - 1, e_{n-1}): the sum of the line's footprint terms at the fitted pens */
+    int32_t  first, last; /* e_0 and e_{n-1} in 1/64 px */
+} focr_text_align_t;
+
+int focr_decoder_align_text(focr_decoder_t *dec, const uint8_t *pages, int pages_on_device, size_t n_pages,
+                            size_t page_w, size_t page_h, uint32_t x_start, uint32_t width, uint32_t line_height,
+                            const focr_text_line_t *lines, size_t n_lines,
+                            const uint16_t *chars, size_t n_chars,
+                            const int8_t *line_q, uint32_t y_bits, uint32_t start, uint32_t drift, uint32_t step,
+                            uint32_t *pens_out, int32_t *terms, focr_text_align_t *out);
+/* Device time of the last align_text's kernels in ms (events), and their launch count (1, or 2 with global strips; 0 after a
+ * refusal or a call without lines). */
+float    focr_decoder_last_align_text_ms(const focr_decoder_t *dec);
+uint32_t focr_decoder_last_align_text_launches(const focr_decoder_t *dec);
 
 /* ---- device: test images (focr --test: draw_test_rectangles, draw_test_text, src/main.rs:241-298) ---------------- */
 

@@ -107,6 +107,16 @@ With --score-text, also focr_decoder_score_text (LineDecoder.score_text) over th
   stext_over_radius0          per radius N the ratio to radius 0, beside stext_ceiling = 2N + 1
   stext_wall_ms               median host time of one radius-0 call (the lines packed in Python, uploads, results read back)
   stext_equal                 at radius 0 every line's terms and line_base equal the scores run's (decode(scores=True))
+With --align-text, also focr_decoder_align_text (LineDecoder.align_text) over the plain run's decoded lines at the (drift, step)
+pairs (0, 0), (16, 2) and (128, 8) from start 128 (every state of every band live), in calls that alternate with score_text at radius 0
+on the same lines; the result also goes to profiles/focr_align_text_bench.json:
+  atext_device_ms             median device time of align_text's launch per pair: {"0,0": .., "16,2": .., "128,8": ..}
+  atext_device_ms_min         ... and the lowest
+  atext_score_device_ms       median device time of the score_text calls in between (one term per character)
+  atext_states                per pair the states of the band, 2 * drift + 1: the yardstick is that many score_text calls
+  atext_over_yardstick        per pair atext_device_ms over atext_states x atext_score_device_ms
+  atext_wall_ms               median host time of one (16, 2) call (the lines packed in Python, uploads, results read back)
+  atext_equal                 at (0, 0) every line's cost and terms equal score_text's at the nominal pens
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -129,7 +139,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from font_ocr_amd import FOCR_DEFAULT_ALPHABET, DecodeFont, LineDecoder  # noqa: E402
-from font_ocr_amd.decoder import raster_glyph, render_text  # noqa: E402
+from font_ocr_amd.decoder import nominal_pens, raster_glyph, render_text  # noqa: E402
 
 FONT = os.path.join(ROOT, "tests", "golden", "DejaVuSansMono.ttf")
 
@@ -198,6 +208,7 @@ def main():
     ap.add_argument("--test-images", action="store_true", help="also time focr --test's images of the batch")
     ap.add_argument("--verify-text", action="store_true", help="also time verify_text over the decoded lines against the verify of the same run")
     ap.add_argument("--score-text", action="store_true", help="also time score_text over the decoded lines at shift radii 0, 8 and 64 against the plain decode")
+    ap.add_argument("--align-text", action="store_true", help="also time align_text over the decoded lines at (drift, step) (0, 0), (16, 2) and (128, 8) against score_text")
     ap.add_argument("--scores", action="store_true", help="also time the decode with per-character scores on")
     ap.add_argument("--pen-search", type=int, default=0, metavar="N", help="also time the decode with a pen search of N/64 px")
     ap.add_argument("--whole-line", action="store_true", help="also time the whole-line decode")
@@ -300,6 +311,28 @@ def main():
                         zwall.append((time.perf_counter() - t) * 1e3)
                     zdev[n].append(dec.last_score_text_ms)
             zlaunches = int(dec._lib.focr_decoder_last_score_text_launches(dec._h))
+        if a.align_text:
+            crop = (geo[0], geo[2], geo[3])
+            pairs, a_start = ((0, 0), (16, 2), (128, 8)), 128
+            noms = [[nominal_pens(font, t, a_start) for _, t in pg] for pg in out]
+            agot = dec.align_text(pages, out, *crop, start=a_start, drift=0, step=0)
+            awant = dec.score_text(pages, out, *crop, pens=noms)
+            aequal = all(g.base == w.base and g.cost == w.cost and np.array_equal(g.terms, w.terms) for pg, pw in zip(agot, awant) for g, w in zip(pg, pw))
+            for _ in range(a.warmup):
+                for w, n in pairs:
+                    dec.score_text(pages, out, *crop, terms=False)
+                    dec.align_text(pages, out, *crop, start=a_start, drift=w, step=n, terms=False)
+            adev, asdev, awall = {pr: [] for pr in pairs}, [], []
+            for _ in range(a.steps):
+                for w, n in pairs:
+                    dec.score_text(pages, out, *crop, terms=False)
+                    asdev.append(dec.last_score_text_ms)
+                    t = time.perf_counter()
+                    dec.align_text(pages, out, *crop, start=a_start, drift=w, step=n, terms=False)
+                    if (w, n) == pairs[1]:
+                        awall.append((time.perf_counter() - t) * 1e3)
+                    adev[(w, n)].append(dec.last_align_text_ms)
+            alaunches = int(dec._lib.focr_decoder_last_align_text_launches(dec._h))
         if a.scores:
             for _ in range(a.warmup):
                 dec.decode(pages, *geo, scores=True)
@@ -474,6 +507,17 @@ def main():
                     "stext_plain_device_ms": round(zpms, 4), "stext_over_plain": round(zms[0] / zpms, 3),
                     "stext_over_radius0": {str(n): round(zms[n] / zms[0], 2) for n in zms}, "stext_ceiling": {str(n): 2 * n + 1 for n in zms},
                     "stext_launches": zlaunches, "stext_wall_ms": round(float(np.median(zwall)), 3), "stext_equal": bool(zequal)})
+    if a.align_text:
+        ams, asms = {pr: float(np.median(v)) for pr, v in adev.items()}, float(np.median(asdev))
+        name = lambda pr: "%d,%d" % pr  # noqa: E731
+        res.update({"atext_device_ms": {name(pr): round(v, 4) for pr, v in ams.items()},
+                    "atext_device_ms_min": {name(pr): round(float(min(v)), 4) for pr, v in adev.items()},
+                    "atext_score_device_ms": round(asms, 4), "atext_states": {name(pr): 2 * pr[0] + 1 for pr in ams},
+                    "atext_over_yardstick": {name(pr): round(v / ((2 * pr[0] + 1) * asms), 3) for pr, v in ams.items()},
+                    "atext_start": a_start, "atext_launches": alaunches, "atext_wall_ms": round(float(np.median(awall)), 3), "atext_equal": bool(aequal)})
+        with open(os.path.join(ROOT, "profiles", "focr_align_text_bench.json"), "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
     if a.scores:
         sms, pms = float(np.median(sdev)), float(np.median(pdev))
         res.update({"scores_device_ms_per_batch": round(sms, 4), "scores_device_ms_min": round(float(min(sdev)), 4),
