@@ -382,6 +382,8 @@ DECODE_RASTER_SYMBOLS = {
     "focr_verify_font_build": (C.c_int, [C.c_char_p, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_size_t,
                                          C.POINTER(VerifyFontStruct), C.c_char_p, C.c_size_t]),
     "focr_verify_font_free": (None, [C.POINTER(VerifyFontStruct)]),
+    "focr_decode_font_learn": (C.c_int, [C.POINTER(DecodeFontStruct), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DecodeFontStruct),
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
 }
 
 # the declarations of include/focr_decode.h in libfocr_hip.so
@@ -436,6 +438,11 @@ DECODE_HIP_SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "focr_decoder_last_align_text_ms": (C.c_float, [C.c_void_p]),
     "focr_decoder_last_align_text_launches": (C.c_uint32, [C.c_void_p]),
+    "focr_decoder_learn_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "focr_decoder_last_learn_text_ms": (C.c_float, [C.c_void_p]),
+    "focr_decoder_last_learn_text_launches": (C.c_uint32, [C.c_void_p]),
     "focr_decoder_test_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_int]),

@@ -63,6 +63,17 @@
 //     of the fitted pens on the font's own (include/focr_decode.h has the sums): scale (%.6f) is the page's kerning relative to
 //     the font's, x64 (%.2f) what to add to -x in 1/64 px; both are empty without two inked characters.  --rank-drift without
 //     --rank-text or beside --rank-shift is a usage error, and so is --rank-step without --rank-drift.
+//   * --learn FILE [--learn-min-count M] [--learn-grow G] is an extension for pages another renderer or another cut of the font
+//     drew: FILE is a reading somebody TRUSTS (a few corrected pages, or a text that is known) in focr's own stdout format, one
+//     line per non-blank line slot in -i order; it may stop early, and an empty line skips its slot.  The run finds the slots
+//     with a plain run, learns font 0's glyph tables from the paired lines at the pen loop's placements
+//     (focr_decoder_learn_text, focr_decode_font_learn: a cell with at least M samples, default 1, takes the mean of the page
+//     under it inside its own ink's bounding rectangle grown by G pixels, default 0), sets the learned font, and then decodes and
+//     prints everything as usual.  stderr gets one line: the characters used and skipped and the cells learned out of those with
+//     ink.  Tables learned from the decoder's own reading reproduce its errors: FILE has to be right.  Plain pen loop only: with
+//     --pen-search, --whole-line, --baseline-search, --whole-baseline, --font-candidate, --test or --rank-text it is a usage
+//     error, and so are --learn-min-count and --learn-grow without it and a character of FILE outside the alphabet (the message
+//     names the line).
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -113,6 +124,9 @@ struct Args {
     float text_size = 0.f, kerning = 1.f;
     uint32_t x = 0, y = 0, width = 0, line_height = 0, line_advance = 0, pen_search = 0, pen_slack = 0;
     bool have_text_size = false, have_width = false, have_line_height = false, have_line_advance = false;
+    std::string learn;
+    bool have_learn = false, have_learn_min_count = false, have_learn_grow = false;
+    uint32_t learn_min_count = 1, learn_grow = 0;
 };
 
 const char *USAGE =
@@ -154,6 +168,9 @@ void print_help() {
            "      --rank-shift <N>                 [extension] Score TEXT at the rigid shifts -N ..= N in 1/64 px and keep the best, N <= 64 (only with --rank-text) [default: 0]\n"
            "      --rank-drift <W>                 [extension] Fit every character's pen of TEXT instead: offsets of up to W/64 px from the font's own pens, W <= 1024; the CSV gains first,last,scale,x64 (only with --rank-text, not with --rank-shift)\n"
            "      --rank-step <N>                  [extension] Consecutive characters' offsets differ by at most N/64 px, N <= 64 (only with --rank-drift) [default: 2]\n"
+           "      --learn <FILE>                   [extension] Learn the glyph tables from FILE, a reading you trust in focr's own output format (one line per non-blank line slot in -i order; it may stop early, an empty line skips its slot), then decode with them; learning from the decoder's own reading reproduces its errors (only with the plain pen loop)\n"
+           "      --learn-min-count <M>            [extension] Learn a (glyph, phase) cell from at least M samples, M >= 1 (only with --learn) [default: 1]\n"
+           "      --learn-grow <G>                 [extension] Grow every learned cell's support by G pixels a side; above 0 neighbours overlap and costs drop below the objective's limit (only with --learn) [default: 0]\n"
            "  -h, --help                           Print help\n"
            "  -V, --version                        Print version\n",
            USAGE, DEFAULT_ALPHABET);
@@ -218,6 +235,9 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--rank-shift") a.rank_shift = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64"), a.have_rank_shift = true;
         else if (k == "--rank-drift") a.rank_drift = c.u32_at_most(FOCR_ALIGN_DRIFT_MAX, "the radius is at most 1024"), a.have_rank_drift = true;
         else if (k == "--rank-step") a.rank_step = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64"), a.have_rank_step = true;
+        else if (k == "--learn") a.learn = c.need(), a.have_learn = true;
+        else if (k == "--learn-min-count") a.learn_min_count = c.u32(), a.have_learn_min_count = true;
+        else if (k == "--learn-grow") a.learn_grow = c.u32(), a.have_learn_grow = true;
         else if (k == "-h" || k == "--help") {
             print_help();
             exit(0);
@@ -266,6 +286,14 @@ Args parse_args(int argc, char **argv) {
                                      {a.baseline_search != 0, "--baseline-search <N>"}, {a.whole_baseline != 0, "--whole-baseline <N>"},
                                      {a.have_verify, "--verify <VERIFY>"}})
         if (with && !a.candidates.empty()) usage_error(std::string("the argument '--font-candidate <SPEC>' cannot be used with '") + name + "'");
+    for (const auto &[with, name] : {std::pair<bool, const char *>{a.pen_search != 0, "--pen-search <N>"}, {a.whole_line, "--whole-line"},
+                                     {a.baseline_search != 0, "--baseline-search <N>"}, {a.whole_baseline != 0, "--whole-baseline <N>"},
+                                     {!a.candidates.empty(), "--font-candidate <SPEC>"}, {a.have_test, "--test <TEST>"},
+                                     {a.have_rank_text, "--rank-text <TEXT>"}})
+        if (with && a.have_learn) usage_error(std::string("the argument '--learn <FILE>' cannot be used with '") + name + "'");
+    if (a.have_learn_min_count && !a.have_learn) usage_error("the argument '--learn-min-count <M>' cannot be used without '--learn <FILE>'");
+    if (a.have_learn_grow && !a.have_learn) usage_error("the argument '--learn-grow <G>' cannot be used without '--learn <FILE>'");
+    if (a.have_learn_min_count && a.learn_min_count < 1) usage_error("invalid value '0' for '--learn-min-count <M>': at least 1");
     return a;
 }
 
@@ -411,6 +439,30 @@ int run_rank(const Args &args, const std::vector<uint32_t> &alphabet, const std:
     return 0;
 }
 
+// --learn FILE as alphabet indices (the first of equal characters), one entry per line of FILE; an empty line is an empty entry.
+std::vector<std::vector<uint16_t>> read_reading(const std::string &path, const std::vector<uint32_t> &alphabet) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) usage_error("cannot read '" + path + "' for '--learn'");
+    std::string all;
+    char buf[4096];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) all.append(buf, n);
+    fclose(f);
+    std::vector<std::vector<uint16_t>> out;
+    for (size_t at = 0; at < all.size();) {
+        const size_t end = std::min(all.find('\n', at), all.size());
+        std::vector<uint16_t> line;
+        for (uint32_t cp : utf8_decode(all.substr(at, end - at))) {
+            const auto hit = std::find(alphabet.begin(), alphabet.end(), cp);
+            if (hit == alphabet.end())
+                usage_error("invalid value '" + path + "' for '--learn <FILE>': line " + std::to_string(out.size() + 1) + ": '" + utf8_encode(cp) + "' is not in the alphabet");
+            line.push_back((uint16_t)(hit - alphabet.begin()));
+        }
+        out.push_back(std::move(line));
+        at = end + 1;
+    }
+    return out;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -430,6 +482,8 @@ int main(int argc, char **argv) {
         if (at == alphabet.end()) usage_error("invalid value '" + args.rank_text + "' for '--rank-text <TEXT>': '" + utf8_encode(cp) + "' is not in the alphabet");
         rank_text.push_back((uint16_t)(at - alphabet.begin()));
     }
+    std::vector<std::vector<uint16_t>> reading;
+    if (args.have_learn) reading = read_reading(args.learn, alphabet);
     if (args.have_test) return run_test(args, alphabet);
     if (args.have_rank_text) return run_rank(args, alphabet, rank_text);
     FILE *csv = nullptr;
@@ -467,14 +521,15 @@ int main(int argc, char **argv) {
     // a setter that refuses ends the program: "<setter>: <the library's message>", exit code 1
     const auto set = [&](const char *setter, int rc) { if (rc != 0) die(std::string(setter) + ": " + focr_decoder_last_error(dec), 1); };
     set("focr_decoder_set_font", focr_decoder_set_font(dec, &font));
-    if (args.have_verify || args.have_verify_fonts) {
+    const auto set_verify_font = [&]() {  // font 0's verify table (a learned font keeps the boxes and rectangles of the font it came from)
         focr_verify_font_t vfont{};
         if (focr_verify_font_build(args.font.c_str(), args.text_size, args.hinting, args.kerning, alphabet.data(), alphabet.size(), &vfont, err,
                                    sizeof err) != 0)
             die(std::string("verify font: ") + err);
         set("focr_decoder_set_verify_font", focr_decoder_set_verify_font(dec, &vfont));
         focr_verify_font_free(&vfont);
-    }
+    };
+    if (args.have_verify || args.have_verify_fonts) set_verify_font();
     if (csv) set("focr_decoder_set_scores", focr_decoder_set_scores(dec, 1));
     set("focr_decoder_set_pen_search", focr_decoder_set_pen_search(dec, args.pen_search));
     set("focr_decoder_set_whole_line", focr_decoder_set_whole_line(dec, args.whole_line));
@@ -510,21 +565,80 @@ int main(int argc, char **argv) {
     std::vector<std::vector<Line>> lines(n_img);
     std::vector<uint8_t> batch, rgb;
     std::vector<uint64_t> sums;
+    const auto load_batch = [&](const std::vector<size_t> &idx, size_t b0, size_t nb, size_t W, size_t H) {  // the images idx[b0 .. b0 + nb) into `batch`
+        batch.assign(nb * W * H, 255);
+        for (size_t j = 0; j < nb; j++) {
+            const size_t i = idx[b0 + j];
+            uint8_t *px = nullptr;
+            size_t w = 0, h = 0;
+            if (focr_image_load_luma8(args.img[i].c_str(), &px, &w, &h, err, sizeof err) != 0)
+                die("called `Result::unwrap()` on an `Err` value: " + std::string(err) + " (" + args.img[i] + ")");
+            if (w != W || h != H) die("image size changed while reading " + args.img[i]);
+            memcpy(batch.data() + j * W * H, px, W * H);
+            free(px);
+        }
+    };
+    if (args.have_learn) {
+        // 1. the slots: a plain run of every batch, the rows of its non-blank line slots kept per image
+        std::vector<std::vector<uint32_t>> slots(n_img);
+        for (const auto &grp : groups)
+            for (size_t b0 = 0; b0 < grp.second.size(); b0 += BATCH_PAGES) {
+                const size_t nb = std::min(BATCH_PAGES, grp.second.size() - b0), W = grp.first.first, H = grp.first.second;
+                load_batch(grp.second, b0, nb, W, H);
+                if (focr_decoder_run(dec, batch.data(), 0, nb, W, H, args.x, args.y, args.width, args.line_height, args.line_advance) != 0)
+                    die(std::string("--learn: focr_decoder_run: ") + focr_decoder_last_error(dec), 1);
+                std::vector<focr_decoded_line_t> dl(focr_decoder_n_lines(dec));
+                std::vector<uint16_t> dc(focr_decoder_n_chars(dec));
+                focr_decoder_get(dec, dl.data(), dc.data());
+                for (const focr_decoded_line_t &l : dl) slots[grp.second[b0 + l.page]].push_back(l.y);
+            }
+        // 2. slot k in -i order reads line k of FILE; the paired lines are learned batch by batch and added up
+        std::vector<size_t> first_slot(n_img + 1, 0);
+        for (size_t i = 0; i < n_img; i++) first_slot[i + 1] = first_slot[i] + slots[i].size();
+        std::vector<uint64_t> lsums(font.bitmaps_len, 0), lcounts(font.n_glyphs * FOCR_DECODE_PHASES, 0);
+        std::vector<uint32_t> s32(std::max<size_t>(lsums.size(), 1)), c32(std::max<size_t>(lcounts.size(), 1));
+        size_t n_used = 0, n_listed = 0;
+        for (const auto &grp : groups)
+            for (size_t b0 = 0; b0 < grp.second.size(); b0 += BATCH_PAGES) {
+                const size_t nb = std::min(BATCH_PAGES, grp.second.size() - b0), W = grp.first.first, H = grp.first.second;
+                std::vector<focr_text_line_t> tl;
+                std::vector<uint16_t> tc;
+                for (size_t j = 0; j < nb; j++) {
+                    const size_t i = grp.second[b0 + j];
+                    for (size_t q = 0; q < slots[i].size(); q++) {
+                        const size_t k = first_slot[i] + q;
+                        if (k >= reading.size() || reading[k].empty()) continue;
+                        tl.push_back(focr_text_line_t{(uint32_t)j, slots[i][q], tc.size(), (uint32_t)reading[k].size(), 0});
+                        tc.insert(tc.end(), reading[k].begin(), reading[k].end());
+                    }
+                }
+                if (tl.empty()) continue;
+                load_batch(grp.second, b0, nb, W, H);
+                std::vector<uint8_t> used(tc.size());
+                if (focr_decoder_learn_text(dec, batch.data(), 0, nb, W, H, args.x, args.width, args.line_height, tl.data(), tl.size(), tc.data(), nullptr, nullptr,
+                                            nullptr, tc.size(), 0, s32.data(), c32.data(), used.data()) != 0)
+                    die(std::string("--learn: focr_decoder_learn_text: ") + focr_decoder_last_error(dec), 1);
+                for (size_t e = 0; e < lsums.size(); e++) lsums[e] += s32[e];
+                for (size_t e = 0; e < lcounts.size(); e++) lcounts[e] += c32[e];
+                n_listed += used.size();
+                n_used += (size_t)std::count(used.begin(), used.end(), 1);
+            }
+        // 3. the learned font replaces font 0: everything below decodes with it
+        focr_decode_font_t learned{};
+        size_t n_learned = 0, n_inked = 0;
+        if (focr_decode_font_learn(&font, lsums.data(), lcounts.data(), args.learn_min_count, args.learn_grow, &learned, &n_learned, &n_inked, err, sizeof err) != 0)
+            die(std::string("--learn: ") + err);
+        fprintf(stderr, "learn: %zu characters used, %zu skipped, %zu of %zu cells with ink learned\n", n_used, n_listed - n_used, n_learned, n_inked);
+        focr_decode_font_free(&font);
+        font = learned;
+        set("focr_decoder_set_font", focr_decoder_set_font(dec, &font));
+        if (args.have_verify) set_verify_font();  // set_font drops the table with the previous font
+    }
     for (const auto &grp : groups) {
         const size_t W = grp.first.first, H = grp.first.second;
         for (size_t b0 = 0; b0 < grp.second.size(); b0 += BATCH_PAGES) {
             const size_t nb = std::min(BATCH_PAGES, grp.second.size() - b0);
-            batch.assign(nb * W * H, 255);
-            for (size_t j = 0; j < nb; j++) {
-                const size_t i = grp.second[b0 + j];
-                uint8_t *px = nullptr;
-                size_t w = 0, h = 0;
-                if (focr_image_load_luma8(args.img[i].c_str(), &px, &w, &h, err, sizeof err) != 0)
-                    die("called `Result::unwrap()` on an `Err` value: " + std::string(err) + " (" + args.img[i] + ")");
-                if (w != W || h != H) die("image size changed while reading " + args.img[i]);
-                memcpy(batch.data() + j * W * H, px, W * H);
-                free(px);
-            }
+            load_batch(grp.second, b0, nb, W, H);
             if (focr_decoder_run(dec, batch.data(), 0, nb, W, H, args.x, args.y, args.width, args.line_height, args.line_advance) != 0)
                 die(std::string("focr_decoder_run: ") + focr_decoder_last_error(dec), 1);
             std::vector<focr_decoded_line_t> dl(focr_decoder_n_lines(dec));

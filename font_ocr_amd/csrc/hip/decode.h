@@ -11,6 +11,7 @@
 //   decode_text.hip            verify_text: a caller's lines drawn over their pages, each in any uploaded font
 //   decode_score.hip           score_text: the decoder's cost of a caller's lines, each in any uploaded font (over decode_pen.h)
 //   decode_align.hip           align_text: a caller's lines with every character's pen fitted to the page (over decode_score.h, align_plan.h)
+//   decode_learn.hip           learn_text: the page's luma summed under every (glyph, phase) cell of a caller's lines (over decode_score.h)
 // (decode_line.h lies between decode.h and the files of a run; decode_line_frac.hip, decode_images.hip and decode_text.hip include decode.h alone.)
 // Below decode.h lie text_plan.h, host code alone (the input rules of a caller's reading and the record the device reads of a line),
 // align_plan.h on top of it (the host plan of align_text: nominal pens, the 2^24 rule, the backpointers' budget), and
@@ -435,7 +436,7 @@ struct Stage {  // the kernels of one entry point's last call: device events aro
 struct focr_decoder {
     int device = 0;
     hipStream_t stream = nullptr;
-    focr_dec::Stage run, verify, test, vtext, stext, atext;
+    focr_dec::Stage run, verify, test, vtext, stext, atext, ltext;
     std::string err;
     // the fonts (decode_font.h): font k of 0 ..= K is font_at(k).  n_glyphs is the alphabet's size and "a decode font is set": `font` and
     // `tables` are that font's, and a set_font that succeeds replaces all three together
@@ -528,6 +529,13 @@ struct focr_decoder {
     focr::DevArray<focr_text_align_t> d_aout;
     focr::DevArray<focr_dec::FontDesc> d_adesc;
     focr::DevArray<uint8_t> d_astrips;
+    // learn_text (decode_learn.hip): the staged reading is the one above; everything else is its own: the learned font's box records,
+    // the sums (one uint32 per byte of that font's bitmaps), the counts per (glyph, phase), the `use` mask and the `used` flags, the
+    // fonts' descriptors and (only when a line's strip does not fit in LDS) the strips
+    focr::DevArray<focr_dec::LearnGlyph> d_lboxes;
+    focr::DevArray<uint32_t> d_lsums, d_lcounts;
+    focr::DevArray<uint8_t> d_luse, d_lused, d_lstrips;
+    focr::DevArray<focr_dec::FontDesc> d_ldesc;
 };
 
 namespace focr_dec {

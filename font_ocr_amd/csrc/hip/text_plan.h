@@ -1,5 +1,6 @@
 // text_plan.h — the input rules of a reading the caller supplies, stated once for the two entry points that take one:
-// focr_decoder_verify_text (decode_text.hip) draws it, focr_decoder_score_text (decode_score.hip) costs it.  Both take
+// focr_decoder_verify_text (decode_text.hip) draws it, focr_decoder_score_text (decode_score.hip) costs it (and so do
+// focr_decoder_align_text and focr_decoder_learn_text, whose own rules, align_plan.h's and plan_learn below, come on top).  Both take
 // focr_text_line_t lines into one `chars` array, optional pens or offsets beside the characters, and any uploaded font per line.
 // Here: the one record the device reads of a line (TextRec), the guards, the per-line checks with the running sum, and the
 // per-character checks, as pure functions that return the refusal's text behind the entry point's prefix (empty: accepted), in the
@@ -96,6 +97,27 @@ inline std::string plan_text_chars(const TextInput &in, uint32_t n_glyphs) {
         if (in.chars[i] >= n_glyphs) return "character " + std::to_string(i) + " is not an index into the alphabet";
     for (size_t i = 0; in.pens && i < in.n_chars; i++)
         if (in.pens[i] >= (1u << 24)) return "pen " + std::to_string(i) + " is 2^24 or more (pens must stay exact in f32)";
+    return {};
+}
+
+// One glyph of the font focr_decoder_learn_text learns, as its kernel reads it beside the glyph record: the box's columns (a
+// DevGlyph has only the row's dwords) and where the glyph's phase 0 lies in the font's own `bitmaps`, which `sums` mirrors.
+struct LearnGlyph {
+    uint64_t at;
+    uint32_t box_w, pad;
+};
+
+inline std::vector<LearnGlyph> learn_boxes(const HostFont &f) {
+    std::vector<LearnGlyph> out;
+    for (const focr_decode_glyph_t &s : f.glyphs) out.push_back(LearnGlyph{s.offset, s.box_w, 0});
+    return out;
+}
+
+// focr_decoder_learn_text's two rules beyond the reading's own: the font to learn is one of 0 ..= K, and a sum of n_out samples
+// of at most 255 each stays inside a uint32 (n_out is plan_text_lines' running sum: every listed character).
+inline std::string plan_learn(uint32_t font, size_t K, uint64_t n_out) {
+    if (font > K) return "font " + std::to_string(font) + " to learn with " + std::to_string(K) + " candidates uploaded (focr_decoder_set_font_candidates)";
+    if (n_out >= (1ull << 24)) return "2^24 or more listed characters (a cell's sums are 32 bits wide: list fewer lines and add the calls up)";
     return {};
 }
 

@@ -28,6 +28,7 @@
 
 #include "focr_decode.h"
 #include "focr_host.h"
+#include "../hip/learn_font.h"
 
 namespace {
 
@@ -585,6 +586,28 @@ extern "C" void focr_decode_font_free(focr_decode_font_t *font) {
     free(font->glyphs);
     free(font->bitmaps);
     memset(font, 0, sizeof *font);
+}
+
+// The learned font (../hip/learn_font.h has the rule): base's records and the learned bitmaps, in tables of its own.
+extern "C" int focr_decode_font_learn(const focr_decode_font_t *base, const uint64_t *sums, const uint64_t *counts, uint32_t min_count, uint32_t grow,
+                                      focr_decode_font_t *out, size_t *learned, size_t *inked, char *err, size_t errlen) {
+    if (!base || !out) return fail(err, errlen, "focr_decode_font_learn: bad arguments");
+    std::vector<uint8_t> bitmaps;
+    focr_dec::LearnStats stats;
+    const std::string no = focr_dec::learn_font_bitmaps(*base, sums, counts, min_count, grow, &bitmaps, &stats);
+    if (!no.empty()) return fail(err, errlen, ("focr_decode_font_learn: " + no).c_str());
+    *out = *base;
+    out->glyphs = (focr_decode_glyph_t *)malloc(sizeof(focr_decode_glyph_t) * (base->n_glyphs ? base->n_glyphs : 1));
+    out->bitmaps = (uint8_t *)malloc(bitmaps.size() ? bitmaps.size() : 1);
+    if (!out->glyphs || !out->bitmaps) {
+        focr_decode_font_free(out);
+        return fail(err, errlen, "out of memory");
+    }
+    if (base->n_glyphs) memcpy(out->glyphs, base->glyphs, sizeof(focr_decode_glyph_t) * base->n_glyphs);
+    if (!bitmaps.empty()) memcpy(out->bitmaps, bitmaps.data(), bitmaps.size());
+    if (learned) *learned = stats.learned;
+    if (inked) *inked = stats.inked;
+    return 0;
 }
 
 extern "C" int focr_verify_font_build(const char *font_path, float text_size, int hinting, float kerning,

@@ -45,6 +45,10 @@
         base, cost, first, last, fit = dec.rank_text_aligned(luma_pages[0], 39, "the first line as a person reads it", 45, 608, 12, drift=128, step=4)
         # the same ranking with the pens fitted under each font; fit[k] = (scale, x64): the page's kerning relative to font k's
         # and where its text starts, in 1/64 px
+        glyphs = dec.learn_text(luma_pages[:2], corrected_pages, 45, 608, 12)
+        dec.set_font(dec.font.learned(glyphs))
+        # glyph tables averaged from a reading somebody trusts (a LearnedGlyphs(sums, counts, used)): the rest of the pages are
+        # then decoded with the page's own glyph shapes instead of this FreeType build's
         rects, texts = dec.test_images(luma_pages, 45, 39, 608, 12, 15)
         # focr --test on the device: the line boxes, and the alphabet at the top-left corner, over each page
 
@@ -103,6 +107,23 @@ class TextAlign(collections.namedtuple("TextAlign", "base cost first last pens t
     term there (an int32 array; None when not asked for)."""
 
     __slots__ = ()
+
+
+class LearnedGlyphs(collections.namedtuple("LearnedGlyphs", "sums counts used")):
+    """What a trusted reading showed of a font's glyphs (LineDecoder.learn_text).  sums: the page's inverted luma summed under
+    every byte of the font's bitmaps (a uint64 array in the font's own `bitmaps` layout); counts: the samples of every cell, a
+    uint64 array at [glyph * 64 + phase]; used[page][line]: a uint8 array aligned with the text, 1 where the character
+    contributed (in use, its box wholly inside the crop, its line in the font that was learned).  a + b adds two: the sums and
+    the counts, b's pages listed behind a's.  DecodeFont.learned() turns one into a font."""
+
+    __slots__ = ()
+
+    def __add__(self, other):
+        if not isinstance(other, LearnedGlyphs):
+            return NotImplemented
+        if self.sums.shape != other.sums.shape or self.counts.shape != other.counts.shape:
+            raise ValueError("LearnedGlyphs of different fonts do not add")
+        return LearnedGlyphs(self.sums + other.sums, self.counts + other.counts, list(self.used) + list(other.used))
 
 
 def nominal_pens(font, text, start=0):
@@ -273,6 +294,34 @@ class DecodeFont:
         bm = raw[g.offset + p * n: g.offset + (p + 1) * n].reshape(g.box_h, g.stride)[:, : g.box_w]
         return bm.copy(), int(g.off_x[p]), int(g.off_y[p])
 
+    def learned(self, glyphs, min_count=1, grow=0):
+        """This font with the cells a trusted reading showed replaced by their means (focr_decode_font_learn): glyphs is the
+        LearnedGlyphs of LineDecoder.learn_text for this font, calls added up.  A cell (glyph, phase) is learned when it has at
+        least min_count samples and its phase has ink here; inside the bounding rectangle of that ink, grown by `grow` pixels a
+        side and clipped to the box, each byte becomes the mean rounded half up; everything else, every increment, box, offset
+        and the origin are this font's.  With grow=1 supports of neighbours overlap and a page's cost drops below -line_base
+        (the objective counts an overlap once per glyph), hence the default 0.  Returns a DecodeFont (y_bits 0) that set_font()
+        and set_font_candidates() take as they are; n_learned and n_inked on it count the learned cells and the cells with ink."""
+        if int(min_count) < 1 or int(grow) < 0:
+            raise ValueError("learned: min_count must be at least 1 and grow at least 0")
+        sums = np.ascontiguousarray(glyphs.sums, dtype=np.uint64)
+        counts = np.ascontiguousarray(glyphs.counts, dtype=np.uint64)
+        if sums.shape != (self.s.bitmaps_len,) or counts.shape != (self.s.n_glyphs * 64,):
+            raise ValueError("learned: the sums and counts are not this font's")
+        new = DecodeFont.__new__(DecodeFont)
+        new.font_path, new.text_size, new.alphabet = self.font_path, self.text_size, self.alphabet
+        new.hinting, new.kerning, new.y_bits = self.hinting, self.kerning, 0
+        new.fonts = (N.DecodeFontStruct * 1)()
+        new.s = new.fonts[0]
+        n_learned, n_inked = C.c_size_t(), C.c_size_t()
+        e = _err()
+        if N.decode_raster().focr_decode_font_learn(C.byref(self.s), _ptr(sums, True), _ptr(counts, True), int(min_count), int(grow), C.byref(new.s),
+                                                    C.byref(n_learned), C.byref(n_inked), e, len(e)) != 0:
+            new.s = new.fonts = None
+            raise DecoderError(e.value.decode())
+        new.n_learned, new.n_inked = int(n_learned.value), int(n_inked.value)
+        return new
+
     def close(self):
         if self.s is not None:
             for f in self.fonts:
@@ -341,6 +390,7 @@ class LineDecoder:
         self.last_verify_text_ms = 0.0
         self.last_score_text_ms = 0.0
         self.last_align_text_ms = 0.0
+        self.last_learn_text_ms = 0.0
         for attr, _, default in _SETTINGS:
             setattr(self, attr, default)
 
@@ -348,10 +398,12 @@ class LineDecoder:
         if rc != 0:
             raise DecoderError(self._lib.focr_decoder_last_error(self._h).decode())
 
-    def set_font(self, font_path, text_size, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0, y_bits=0):
+    def set_font(self, font_path, text_size=None, alphabet=FOCR_DEFAULT_ALPHABET, hinting=False, kerning=1.0, y_bits=0):
         """Build (or take, when font_path is a DecodeFont) and upload the decode font.  y_bits > 0 also builds and uploads
         its 1 << y_bits y-phase tables, for decode(baseline_search=N) and decode(whole_line=True, whole_baseline=N) in steps
-        of 2^-y_bits px; a DecodeFont brings its own."""
+        of 2^-y_bits px; a DecodeFont (a learned one too: DecodeFont.learned) brings its own, and needs no text_size."""
+        if text_size is None and not isinstance(font_path, DecodeFont):
+            raise TypeError("set_font() needs a text_size to build a font from a path")
         font = font_path if isinstance(font_path, DecodeFont) else DecodeFont(font_path, text_size, alphabet, hinting, kerning, y_bits)
         self._vfont, self._batch = None, None  # the library drops its verify table, its y-phase fonts and its last run here too
         self._candidates, self._vcands = [], None  # ... and the candidates of the font search, with their verify tables
@@ -607,6 +659,65 @@ class LineDecoder:
                                  tarr[at: at + r[3]].copy() if terms else None))
             at += r[3]
         return out
+
+    def learn_text(self, luma_pages, lines, x, width, line_height, fonts=None, pens=None, offsets=None, use=None, font=0):
+        """What a reading the caller TRUSTS shows of font `font`'s glyphs (focr_decoder_learn_text): a LearnedGlyphs(sums, counts,
+        used).  luma_pages, lines, fonts, pens and offsets are score_text()'s, placed as there at shift 0; font is 0 for the decode
+        font or k for a candidate of set_font_candidates(), and only the lines in that font contribute.  Every character in use
+        whose glyph box lies wholly inside its line's crop adds the page's inverted luma under the box to its cell (glyph, phase)
+        and 1 to the cell's count; use[page][line] holds one truth value per character (None: all), and a character left out
+        still moves the pen.  Page sizes and batches are added up in uint64; add further calls with +.  DecodeFont.learned()
+        makes the font.  The reading must be right: tables learned from the decoder's own reading reproduce its errors.
+        A character outside the alphabet raises ValueError.  The last decode, its results and its verify() are left as they were."""
+        if self.font is None:
+            raise DecoderError("set_font() first")
+        if pens is not None and offsets is not None:
+            raise ValueError("learn_text takes pens or offsets, not both")
+        if not 0 <= int(font) <= len(self._candidates):
+            raise ValueError(f"font must be 0 .. {len(self._candidates)} (the decode font and the candidates of set_font_candidates)")
+        if int(width) <= 0 or int(line_height) <= 0:
+            raise ValueError("learn_text: width and line_height must be positive")
+        _, lines, _, groups = self._pack_text("learn_text", luma_pages, lines, fonts, pens, offsets)
+        if use is not None and (len(use) != len(lines) or any(len(a) != len(b) for a, b in zip(use, lines))):
+            raise ValueError("use must hold one entry per line of lines")
+        target = self._candidates[int(font) - 1] if int(font) else self.font
+        sums = np.zeros(target.s.bitmaps_len, dtype=np.uint64)
+        counts = np.zeros(target.s.n_glyphs * 64, dtype=np.uint64)
+        used = [[None] * len(pg) for pg in lines]
+        for _, batch, recs, chars, along, _, where in groups:
+            mask = None
+            if use is not None:
+                mask = []
+                for (i, q), r in zip(where, recs):
+                    if len(use[i][q]) != r[3]:
+                        raise ValueError(f"learn_text: page {i}, line {q}: {len(use[i][q])} use flags for {r[3]} characters")
+                    mask.extend(1 if v else 0 for v in use[i][q])
+            s, c, u = self._learn_text(batch, recs, chars, along if pens is not None else None, along if offsets is not None else None, mask, x, width,
+                                       line_height, int(font), len(sums), len(counts))
+            sums += s
+            counts += c
+            at = 0
+            for (i, q), r in zip(where, recs):
+                used[i][q] = u[at: at + r[3]].copy()
+                at += r[3]
+        return LearnedGlyphs(sums, counts, used)
+
+    def _learn_text(self, batch, recs, chars, pens, offsets, use, x, width, line_height, font, n_sums, n_counts):
+        """One focr_decoder_learn_text call over an (N, H, W) uint8 batch, its reading as _score_text's and use beside chars
+        (None: all).  (sums uint32, counts uint32, used uint8 per listed character)."""
+        n, h, w = batch.shape
+        larr = (N.TextLine * max(1, len(recs)))(*recs)
+        carr = np.array(chars, dtype=np.uint16) if chars else np.zeros(1, dtype=np.uint16)
+        parr = np.array(pens, dtype=np.uint32) if pens else None
+        oarr = np.array(offsets, dtype=np.int8) if offsets else None
+        uarr = np.array(use, dtype=np.uint8) if use else None
+        sarr = np.zeros(max(1, n_sums), dtype=np.uint32)
+        karr = np.zeros(max(1, n_counts), dtype=np.uint32)
+        darr = np.zeros(max(1, sum(r[3] for r in recs)), dtype=np.uint8)
+        self._check(self._lib.focr_decoder_learn_text(self._h, _ptr(batch), 0, n, w, h, int(x), int(width), int(line_height), larr, len(recs), _ptr(carr),
+                                                      _ptr(parr), _ptr(oarr), _ptr(uarr), len(chars), int(font), _ptr(sarr), _ptr(karr), _ptr(darr)))
+        self.last_learn_text_ms = float(self._lib.focr_decoder_last_learn_text_ms(self._h))
+        return sarr[:n_sums], karr[:n_counts], darr
 
     def rank_text(self, page, y, text, x, width, line_height, shift=0):
         """Which uploaded font renders a known string closest to the page: text scored at line slot (x, y) of one luma page

@@ -699,6 +699,68 @@ int focr_decoder_align_text(focr_decoder_t *dec, const uint8_t *pages, int pages
 float    focr_decoder_last_align_text_ms(const focr_decoder_t *dec);
 uint32_t focr_decoder_last_align_text_launches(const focr_decoder_t *dec);
 
+/* ---- device: glyph tables from a trusted reading (an extension: the tables are what score_text and align_text leave wrong) ---- */
+
+/* Every mode compares the page with what this FreeType build draws; a page from another renderer or another cut of the font is
+ * "very close but not identical".  Once font, size, kerning and x are right (focr_decoder_score_text, focr_decoder_align_text), the
+ * glyph tables are what is still wrong.  The least-squares template of a cell (glyph i, phase p) is the mean of the page's
+ * inverted luma under every occurrence of that cell.  focr_decoder_learn_text computes the sums and the counts of those means from
+ * a reading the caller TRUSTS (a few corrected pages, or a text that is known); focr_decode_font_learn (below) turns them into a
+ * focr_decode_font_t, and the remaining pages are decoded with it.  All of it is exact integer arithmetic but the f32 pen:
+ *   - lines, chars, pens, offsets, the crop (x_start, width, line_height at the line's y, clamped) and the three placements are
+ *     focr_decoder_score_text's at shift 0; there is no line_q: a line moved by whole rows is a line at another y, and the
+ *     y-phase tables are not learned;
+ *   - font k, 0 <= k <= K, is the font to learn: 0 the decode font, 1 ..= K a candidate.  Only the listed lines with
+ *     lines[l].font == k contribute; the others are accepted (and checked) and contribute nothing;
+ *   - use (NULL: every character) has one byte per entry of chars; 0 leaves that character out, and it still moves the pen;
+ *   - character g of a contributing line, glyph i of font k, has its delta as score_text computes it, phase p = delta & 63 and
+ *     whole-pixel shift delta >> 6; its box is box_w x box_h at crop column shift + off_x[p] and crop row off_y[p];
+ *   - it contributes iff it is in use and that box lies wholly inside the crop (there are no partial boxes); an empty crop holds
+ *     no box, not even a blank glyph's box without pixels;
+ *   - a contributing character adds 1 to counts[i * 64 + p], and for row < box_h and col < box_w the value r = 255 - luma of the
+ *     crop pixel under it to sums[offset_i + (p * box_h + row) * stride + col]: font k's own `bitmaps` layout, one uint32 per
+ *     byte, so sums has bitmaps_len entries and counts 64 * n_glyphs; the padding columns col >= box_w stay 0;
+ *   - used (NULL: not wanted) takes 1 or 0 per listed character, line l's at the running sum of n_chars over the lines before
+ *     it (as score_text's terms), 0 throughout a line of another font;
+ *   - repeated lines and shared characters count once per listing;
+ *   - sums, counts and used are this call's alone: they are zeroed first, and the caller adds calls up (in 64 bits).
+ * Refused, each with its own message and before anything is launched: what focr_decoder_score_text refuses of the same
+ * arguments (NULL pages, lines or chars; pens and offsets together; no decode font; width 0 or line_height 0; a page too
+ * large; per line a font above K, a page index >= n_pages, characters past n_chars, pens with a fractional or negative
+ * origin_x; a character index >= the alphabet's size; a pen >= 2^24); NULL sums or NULL counts, whatever n_lines; a font to learn
+ * above K; 2^24 or more listed characters in one call (255 * 2^24 is the bound of a uint32 sum).
+ * The call runs one launch, or two when a line's strip does not fit in LDS (the strips are then built in global memory first;
+ * the zeroing of its outputs lies inside the measured time and is no launch of the count), in buffers of its own: the last
+ * run, its getters, its verify, and the other text calls' last timings answer as they did before, and it needs no run at all.
+ * pages as for focr_decoder_run.  Returns when sums, counts and used are written; with n_lines == 0 nothing is launched and sums
+ * and counts are zeros.
+ * What it does not do: y-phase tables; pooling of neighbouring phases; weights; an NCC bank from the result; and learning from
+ * an untrusted reading: measured on 8 px hinted pages, tables learned from the decoder's own reading of those pages reproduce that
+ * reading's errors (no fewer wrong characters after than before), and gating the samples by score margin does not help. */
+int focr_decoder_learn_text(focr_decoder_t *dec, const uint8_t *pages, int pages_on_device, size_t n_pages,
+                            size_t page_w, size_t page_h, uint32_t x_start, uint32_t width, uint32_t line_height,
+                            const focr_text_line_t *lines, size_t n_lines,
+                            const uint16_t *chars, const uint32_t *pens, const int8_t *offsets, const uint8_t *use, size_t n_chars,
+                            uint32_t font, uint32_t *sums, uint32_t *counts, uint8_t *used);
+/* Device time of the last learn_text's kernels and of the zeroing in front of them in ms (events), and the kernels' launch
+ * count (1, or 2 with global strips; 0 after a refusal or a call without lines). */
+float    focr_decoder_last_learn_text_ms(const focr_decoder_t *dec);
+uint32_t focr_decoder_last_learn_text_launches(const focr_decoder_t *dec);
+
+/* The learned font (host, libfocr_raster.so): `base` with the cells that were seen replaced by their means.  sums and counts are
+ * focr_decoder_learn_text's of `base`, calls added up in 64 bits (sums: base->bitmaps_len entries, counts: 64 * n_glyphs).
+ *   - cell (i, p) is learned when counts[i * 64 + p] >= min_count (min_count >= 1) and phase p of glyph i has ink in base;
+ *   - its support is the bounding rectangle of the base phase's non-zero pixels, grown by `grow` pixels on each side and clipped
+ *     to the box; inside it the byte is (2 * sum + n) / (2 * n), n the cell's count: the mean rounded half up, at most 255;
+ *   - an unlearned cell, everything outside a support and every other field are base's: increments, boxes, offsets, origin,
+ *     size, kerning, hinting.  A blank glyph stays blank, and base's verify table still matches.
+ * With grow = 0 a glyph never claims ink outside its own extent.  With grow = 1 the measured cost of a page drops below
+ * -line_base: neighbouring supports overlap more, and the objective counts an overlap once per glyph (its known limit), so 0 is
+ * the default of every caller (where the boxes themselves overlap, as at 8 px, a cost slightly below -line_base is met at 0 too).  *learned (NULL: not wanted) takes the number of learned cells, *inked the number of cells with ink.
+ * out owns its tables: free with focr_decode_font_free.  Fails with a message on a NULL argument, min_count 0 or no memory. */
+int focr_decode_font_learn(const focr_decode_font_t *base, const uint64_t *sums, const uint64_t *counts, uint32_t min_count,
+                           uint32_t grow, focr_decode_font_t *out, size_t *learned, size_t *inked, char *err, size_t errlen);
+
 /* ---- device: test images (focr --test: draw_test_rectangles, draw_test_text, src/main.rs:241-298) ---------------- */
 
 /* focr --test's two images of each page of a batch of n_pages equal-size pages, drawn on the decoder's stream.  Both

@@ -117,6 +117,17 @@ on the same lines; the result also goes to profiles/focr_align_text_bench.json:
   atext_over_yardstick        per pair atext_device_ms over atext_states x atext_score_device_ms
   atext_wall_ms               median host time of one (16, 2) call (the lines packed in Python, uploads, results read back)
   atext_equal                 at (0, 0) every line's cost and terms equal score_text's at the nominal pens
+With --learn-text, also focr_decoder_learn_text (LineDecoder.learn_text) of font 0 over the plain run's decoded lines (its own reading:
+what is timed is the work, not what the tables are worth), in calls that alternate with score_text at radius 0 on the same lines, at the
+--steps and --warmup of the align_text run; the result also goes to profiles/focr_learn_text_bench.json:
+  ltext_device_ms             median device time of learn_text's launch and the zeroing of its sums and counts in front of it
+  ltext_device_ms_min         ... and the lowest
+  ltext_score_device_ms       median device time of the score_text calls in between: the same strip and the same walk, without the adds
+  ltext_over_score            ltext_device_ms over ltext_score_device_ms
+  ltext_form                  how the sums are accumulated ("atomic": no-return 32-bit integer atomic adds straight to the cell)
+  ltext_characters            the listed characters, ltext_used those whose box lay inside their crop, ltext_cells the cells seen
+  ltext_wall_ms               median host time of one call (the lines packed in Python, uploads, sums and counts read back and added in uint64)
+  ltext_equal                 a second call gives the same sums and counts, and the counts add up to the used characters
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -209,6 +220,7 @@ def main():
     ap.add_argument("--verify-text", action="store_true", help="also time verify_text over the decoded lines against the verify of the same run")
     ap.add_argument("--score-text", action="store_true", help="also time score_text over the decoded lines at shift radii 0, 8 and 64 against the plain decode")
     ap.add_argument("--align-text", action="store_true", help="also time align_text over the decoded lines at (drift, step) (0, 0), (16, 2) and (128, 8) against score_text")
+    ap.add_argument("--learn-text", action="store_true", help="also time learn_text over the decoded lines against score_text")
     ap.add_argument("--scores", action="store_true", help="also time the decode with per-character scores on")
     ap.add_argument("--pen-search", type=int, default=0, metavar="N", help="also time the decode with a pen search of N/64 px")
     ap.add_argument("--whole-line", action="store_true", help="also time the whole-line decode")
@@ -333,6 +345,24 @@ def main():
                         awall.append((time.perf_counter() - t) * 1e3)
                     adev[(w, n)].append(dec.last_align_text_ms)
             alaunches = int(dec._lib.focr_decoder_last_align_text_launches(dec._h))
+        if a.learn_text:
+            crop = (geo[0], geo[2], geo[3])
+            lgot = dec.learn_text(pages, out, *crop)
+            lagain = dec.learn_text(pages, out, *crop)
+            n_used = int(sum(int(u.sum()) for pg in lgot.used for u in pg))
+            lequal = np.array_equal(lgot.sums, lagain.sums) and np.array_equal(lgot.counts, lagain.counts) and int(lgot.counts.sum()) == n_used
+            for _ in range(a.warmup):
+                dec.score_text(pages, out, *crop, terms=False)
+                dec.learn_text(pages, out, *crop)
+            ldev, lsdev, lwall = [], [], []
+            for _ in range(a.steps):
+                dec.score_text(pages, out, *crop, terms=False)
+                lsdev.append(dec.last_score_text_ms)
+                t = time.perf_counter()
+                dec.learn_text(pages, out, *crop)
+                lwall.append((time.perf_counter() - t) * 1e3)
+                ldev.append(dec.last_learn_text_ms)
+            llaunches = int(dec._lib.focr_decoder_last_learn_text_launches(dec._h))
         if a.scores:
             for _ in range(a.warmup):
                 dec.decode(pages, *geo, scores=True)
@@ -516,6 +546,15 @@ def main():
                     "atext_over_yardstick": {name(pr): round(v / ((2 * pr[0] + 1) * asms), 3) for pr, v in ams.items()},
                     "atext_start": a_start, "atext_launches": alaunches, "atext_wall_ms": round(float(np.median(awall)), 3), "atext_equal": bool(aequal)})
         with open(os.path.join(ROOT, "profiles", "focr_align_text_bench.json"), "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+    if a.learn_text:
+        lms, lsms = float(np.median(ldev)), float(np.median(lsdev))
+        res.update({"ltext_device_ms": round(lms, 4), "ltext_device_ms_min": round(float(min(ldev)), 4), "ltext_score_device_ms": round(lsms, 4),
+                    "ltext_over_score": round(lms / lsms, 2), "ltext_form": "atomic", "ltext_launches": llaunches,
+                    "ltext_characters": int(sum(len(t) for pg in out for _, t in pg)), "ltext_used": n_used,
+                    "ltext_cells": int((lgot.counts > 0).sum()), "ltext_wall_ms": round(float(np.median(lwall)), 3), "ltext_equal": bool(lequal)})
+        with open(os.path.join(ROOT, "profiles", "focr_learn_text_bench.json"), "w") as f:
             json.dump(res, f, indent=1, sort_keys=True)
             f.write("\n")
     if a.scores:
