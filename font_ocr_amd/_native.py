@@ -354,6 +354,12 @@ class TextScoreStruct(C.Structure):
     _fields_ = [("line_base", C.c_uint64), ("cost", C.c_int64), ("shift", C.c_int32), ("pad", C.c_uint32)]
 
 
+class TextRefineStruct(C.Structure):
+    """focr_text_refine_t (include/focr_decode.h)."""
+
+    _fields_ = [("line_base", C.c_uint64), ("cost_in", C.c_int64), ("cost", C.c_int64), ("sweeps_run", C.c_uint32), ("changed", C.c_uint32)]
+
+
 class TextAlignStruct(C.Structure):
     """focr_text_align_t (include/focr_decode.h)."""
 
@@ -443,6 +449,11 @@ DECODE_HIP_SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "focr_decoder_last_learn_text_ms": (C.c_float, [C.c_void_p]),
     "focr_decoder_last_learn_text_launches": (C.c_uint32, [C.c_void_p]),
+    "focr_decoder_refine_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "focr_decoder_last_refine_text_ms": (C.c_float, [C.c_void_p]),
+    "focr_decoder_last_refine_text_launches": (C.c_uint32, [C.c_void_p]),
     "focr_decoder_test_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t,
                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_int]),

@@ -74,6 +74,13 @@
 //     --pen-search, --whole-line, --baseline-search, --whole-baseline, --font-candidate, --test or --rank-text it is a usage
 //     error, and so are --learn-min-count and --learn-grow without it and a character of FILE outside the alphabet (the message
 //     names the line).
+//   * --refine S [--refine-radius N] is an extension for tight proportional text, where glyph footprints overlap and the sum of
+//     per-glyph terms every mode minimises is no longer the page's error: after the run (the plain pen loop, --pen-search,
+//     --whole-line or --pen-slack) every line's reading goes through focr_decoder_refine_text at the run's own pens: the line is
+//     drawn with all its glyphs together, and in at most S <= 8 sweeps each character takes the glyph and the offset within N/64 px
+//     (N <= 64, default 4) that lower the composed error the most.  stdout carries the repaired text; stderr gets one line: how
+//     many characters in how many of the lines changed; --verify and every CSV stay the run's.  With --font-candidate,
+//     --baseline-search, --whole-baseline, --test or --rank-text it is a usage error, and so is --refine-radius without it.
 // There is no CPU fallback: without a device it exits non-zero with the error.
 #include <algorithm>
 #include <atomic>
@@ -127,6 +134,8 @@ struct Args {
     std::string learn;
     bool have_learn = false, have_learn_min_count = false, have_learn_grow = false;
     uint32_t learn_min_count = 1, learn_grow = 0;
+    bool have_refine = false, have_refine_radius = false;
+    uint32_t refine = 0, refine_radius = 4;
 };
 
 const char *USAGE =
@@ -168,6 +177,8 @@ void print_help() {
            "      --rank-shift <N>                 [extension] Score TEXT at the rigid shifts -N ..= N in 1/64 px and keep the best, N <= 64 (only with --rank-text) [default: 0]\n"
            "      --rank-drift <W>                 [extension] Fit every character's pen of TEXT instead: offsets of up to W/64 px from the font's own pens, W <= 1024; the CSV gains first,last,scale,x64 (only with --rank-text, not with --rank-shift)\n"
            "      --rank-step <N>                  [extension] Consecutive characters' offsets differ by at most N/64 px, N <= 64 (only with --rank-drift) [default: 2]\n"
+           "      --refine <S>                     [extension] Repair the reading against the line with all its glyphs drawn together, one character at a time, in at most S <= 8 sweeps; stdout carries the repaired text (after the plain pen loop, a pen search, the whole-line decode or a pen slack)\n"
+           "      --refine-radius <N>              [extension] Let a repaired character move by up to N/64 px, N <= 64 (only with --refine) [default: 4]\n"
            "      --learn <FILE>                   [extension] Learn the glyph tables from FILE, a reading you trust in focr's own output format (one line per non-blank line slot in -i order; it may stop early, an empty line skips its slot), then decode with them; learning from the decoder's own reading reproduces its errors (only with the plain pen loop)\n"
            "      --learn-min-count <M>            [extension] Learn a (glyph, phase) cell from at least M samples, M >= 1 (only with --learn) [default: 1]\n"
            "      --learn-grow <G>                 [extension] Grow every learned cell's support by G pixels a side; above 0 neighbours overlap and costs drop below the objective's limit (only with --learn) [default: 0]\n"
@@ -235,6 +246,8 @@ Args parse_args(int argc, char **argv) {
         else if (k == "--rank-shift") a.rank_shift = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64"), a.have_rank_shift = true;
         else if (k == "--rank-drift") a.rank_drift = c.u32_at_most(FOCR_ALIGN_DRIFT_MAX, "the radius is at most 1024"), a.have_rank_drift = true;
         else if (k == "--rank-step") a.rank_step = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64"), a.have_rank_step = true;
+        else if (k == "--refine") a.refine = c.u32_at_most(FOCR_REFINE_SWEEPS_MAX, "at most 8 sweeps"), a.have_refine = true;
+        else if (k == "--refine-radius") a.refine_radius = c.u32_at_most(FOCR_PEN_SEARCH_MAX, "the radius is at most 64"), a.have_refine_radius = true;
         else if (k == "--learn") a.learn = c.need(), a.have_learn = true;
         else if (k == "--learn-min-count") a.learn_min_count = c.u32(), a.have_learn_min_count = true;
         else if (k == "--learn-grow") a.learn_grow = c.u32(), a.have_learn_grow = true;
@@ -291,6 +304,10 @@ Args parse_args(int argc, char **argv) {
                                      {!a.candidates.empty(), "--font-candidate <SPEC>"}, {a.have_test, "--test <TEST>"},
                                      {a.have_rank_text, "--rank-text <TEXT>"}})
         if (with && a.have_learn) usage_error(std::string("the argument '--learn <FILE>' cannot be used with '") + name + "'");
+    for (const auto &[with, name] : {std::pair<bool, const char *>{!a.candidates.empty(), "--font-candidate <SPEC>"}, {a.baseline_search != 0, "--baseline-search <N>"},
+                                     {a.whole_baseline != 0, "--whole-baseline <N>"}, {a.have_test, "--test <TEST>"}, {a.have_rank_text, "--rank-text <TEXT>"}})
+        if (with && a.have_refine) usage_error(std::string("the argument '--refine <S>' cannot be used with '") + name + "'");
+    if (a.have_refine_radius && !a.have_refine) usage_error("the argument '--refine-radius <N>' cannot be used without '--refine <S>'");
     if (a.have_learn_min_count && !a.have_learn) usage_error("the argument '--learn-min-count <M>' cannot be used without '--learn <FILE>'");
     if (a.have_learn_grow && !a.have_learn) usage_error("the argument '--learn-grow <G>' cannot be used without '--learn <FILE>'");
     if (a.have_learn_min_count && a.learn_min_count < 1) usage_error("invalid value '0' for '--learn-min-count <M>': at least 1");
@@ -313,6 +330,8 @@ struct Line {
     long long cost = 0;
     int font = 0;                           // --fonts: the line's winning candidate, and its cost
     long long font_cost = 0;
+    bool refined = false;                   // --refine: stdout carries `repaired` in the text's place
+    std::vector<uint32_t> repaired{};
 };
 
 // Writes the batch's verify images (the device's draw_verify, n x H x W x 3 bytes) as PNGs on at most 16 threads, and
@@ -561,6 +580,7 @@ int main(int argc, char **argv) {
         for (focr_decode_font_t &f : cands) focr_decode_font_free(&f);
     }
     const bool csv_offsets = csv && args.pen_search > 0;
+    size_t refine_chars = 0, refine_lines = 0, refine_listed = 0;
 
     std::vector<std::vector<Line>> lines(n_img);
     std::vector<uint8_t> batch, rgb;
@@ -663,9 +683,42 @@ int main(int argc, char **argv) {
             std::vector<int64_t> fc(want_fonts ? dl.size() : 0);
             if (want_fonts && focr_decoder_get_fonts(dec, fk.data(), fc.data()) != 0)
                 die(std::string("focr_decoder_get_fonts: ") + focr_decoder_last_error(dec), 1);
+            std::vector<uint16_t> rc(args.have_refine ? dc.size() : 0);  // --refine: the repaired characters, line li's at the running sum of n_chars
+            std::vector<focr_text_refine_t> rr(args.have_refine ? dl.size() : 0);
+            if (args.have_refine && !dl.empty()) {  // the reading repaired against the composed line error; the run's own results stay what they were
+                std::vector<uint32_t> tp(dc.size()), rp(dc.size());
+                if (args.whole_line) {
+                    if (focr_decoder_get_pens(dec, tp.data(), nullptr) != 0) die(std::string("focr_decoder_get_pens: ") + focr_decoder_last_error(dec), 1);
+                } else {  // the pen loop's f32 walk, with the pen search's offsets: delta - 64 * origin_x
+                    std::vector<int8_t> tj(dc.size(), 0);
+                    if (args.pen_search && focr_decoder_get_offsets(dec, tj.data()) != 0)
+                        die(std::string("focr_decoder_get_offsets: ") + focr_decoder_last_error(dec), 1);
+                    for (const focr_decoded_line_t &l : dl) {
+                        float pos = 0.f;
+                        for (uint32_t c = 0; c < l.n_chars; c++) {
+                            const float at = pos + (float)tj[l.first + c] * 0.015625f;
+                            tp[l.first + c] = (uint32_t)((int)((font.origin_x + at) * 64.0f) - 64 * (int)font.origin_x);
+                            pos = at + font.glyphs[dc[l.first + c]].increment;
+                        }
+                    }
+                }
+                std::vector<focr_text_line_t> tl(dl.size());
+                for (size_t li = 0; li < dl.size(); li++) tl[li] = focr_text_line_t{dl[li].page, dl[li].y, dl[li].first, dl[li].n_chars, 0};
+                if (focr_decoder_refine_text(dec, batch.data(), 0, nb, W, H, args.x, args.width, args.line_height, tl.data(), tl.size(), dc.data(), tp.data(), dc.size(),
+                                             args.refine_radius, args.refine, 1, rc.data(), rp.data(), rr.data()) != 0)
+                    die(std::string("--refine: focr_decoder_refine_text: ") + focr_decoder_last_error(dec), 1);
+                refine_listed += dl.size();
+            }
+            size_t rat = 0;
             for (size_t li = 0; li < dl.size(); li++) {
                 const focr_decoded_line_t &l = dl[li];
                 Line out{l.y, {}, {}, {}, {}, {}};
+                if (args.have_refine) {
+                    out.refined = true;
+                    for (uint32_t c = 0; c < l.n_chars; c++) out.repaired.push_back(alphabet[rc[rat + c]]);
+                    rat += l.n_chars;
+                    refine_chars += rr[li].changed, refine_lines += rr[li].changed != 0;
+                }
                 if (bcsv) out.q = bq[li], out.cost = (long long)bc[li];
                 if (fcsv) out.font = fk[li], out.font_cost = (long long)fc[li];
                 if (mcsv) out.pens.assign(dp.begin() + l.first, dp.begin() + l.first + l.n_chars);
@@ -713,11 +766,12 @@ int main(int argc, char **argv) {
     }
     focr_decoder_destroy(dec);
     for (focr_decode_font_t &f : fonts) focr_decode_font_free(&f);
+    if (args.have_refine) fprintf(stderr, "refine: %zu characters in %zu of %zu lines changed\n", refine_chars, refine_lines, refine_listed);
 
     std::string out;
     for (size_t i = 0; i < n_img; i++)
         for (const Line &l : lines[i]) {
-            for (uint32_t cp : l.text) out += utf8_encode(cp);
+            for (uint32_t cp : l.refined ? l.repaired : l.text) out += utf8_encode(cp);
             out += '\n';
         }
     fwrite(out.data(), 1, out.size(), stdout);

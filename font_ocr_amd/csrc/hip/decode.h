@@ -12,9 +12,11 @@
 //   decode_score.hip           score_text: the decoder's cost of a caller's lines, each in any uploaded font (over decode_pen.h)
 //   decode_align.hip           align_text: a caller's lines with every character's pen fitted to the page (over decode_score.h, align_plan.h)
 //   decode_learn.hip           learn_text: the page's luma summed under every (glyph, phase) cell of a caller's lines (over decode_score.h)
+//   decode_refine.hip          refine_text: a caller's lines repaired against the composed line error (over decode_score.h, refine_plan.h)
 // (decode_line.h lies between decode.h and the files of a run; decode_line_frac.hip, decode_images.hip and decode_text.hip include decode.h alone.)
 // Below decode.h lie text_plan.h, host code alone (the input rules of a caller's reading and the record the device reads of a line),
-// align_plan.h on top of it (the host plan of align_text: nominal pens, the 2^24 rule, the backpointers' budget), and
+// align_plan.h and refine_plan.h on top of it (the host plans of align_text: nominal pens, the 2^24 rule, the backpointers' budget;
+// and of refine_text: the monotone pens, the fonts' extents, a step's window), and
 // decode_font.h, host code alone: the record of an uploaded font (HostFont), the glyph and verify records the kernels
 // read, and the five font uploaders' checks and packing.  Here: the batch geometry, both line grids, the owners of the fonts' device tables, the tile frame of
 // the compose kernels (ncc_images.hip is its third user), the blank test's crop, the settings (Modes), what a run resolves
@@ -32,6 +34,7 @@
 #include "devmem.h"
 #include "align_plan.h"
 #include "focr_decode.h"
+#include "refine_plan.h"
 #include "text_plan.h"
 
 namespace focr_dec {
@@ -436,7 +439,7 @@ struct Stage {  // the kernels of one entry point's last call: device events aro
 struct focr_decoder {
     int device = 0;
     hipStream_t stream = nullptr;
-    focr_dec::Stage run, verify, test, vtext, stext, atext, ltext;
+    focr_dec::Stage run, verify, test, vtext, stext, atext, ltext, rtext;
     std::string err;
     // the fonts (decode_font.h): font k of 0 ..= K is font_at(k).  n_glyphs is the alphabet's size and "a decode font is set": `font` and
     // `tables` are that font's, and a set_font that succeeds replaces all three together
@@ -536,6 +539,15 @@ struct focr_decoder {
     focr::DevArray<uint32_t> d_lsums, d_lcounts;
     focr::DevArray<uint8_t> d_luse, d_lused, d_lstrips;
     focr::DevArray<focr_dec::FontDesc> d_ldesc;
+    // refine_text (decode_refine.hip): the staged reading is the one above; everything else is its own: the fonts' extents, the
+    // characters and pens as the sweeps leave them, the results, the fonts' descriptors and (only when a line's strip and a step's
+    // window do not fit in LDS together) the strips
+    focr::DevArray<focr_dec::RefineFont> d_rfonts;
+    focr::DevArray<uint16_t> d_rchars;
+    focr::DevArray<uint32_t> d_rpens;
+    focr::DevArray<focr_text_refine_t> d_rout;
+    focr::DevArray<focr_dec::FontDesc> d_rdesc;
+    focr::DevArray<uint8_t> d_rstrips;
 };
 
 namespace focr_dec {

@@ -364,7 +364,7 @@ extern "C" int focr_decoder_create(int device, focr_decoder_t **out) {
     dec = new focr_decoder;
     dec->device = device;
     bool ok = hipStreamCreateWithFlags(&dec->stream, hipStreamNonBlocking) == hipSuccess;
-    for (Stage *s : {&dec->run, &dec->verify, &dec->test, &dec->vtext, &dec->stext, &dec->atext, &dec->ltext}) ok = ok && hipEventCreate(&s->begin) == hipSuccess && hipEventCreate(&s->end) == hipSuccess;
+    for (Stage *s : {&dec->run, &dec->verify, &dec->test, &dec->vtext, &dec->stext, &dec->atext, &dec->ltext, &dec->rtext}) ok = ok && hipEventCreate(&s->begin) == hipSuccess && hipEventCreate(&s->end) == hipSuccess;
     if (!ok) {
         focr_decoder_destroy(dec);
         return dfail(nullptr, "focr_decoder_create: stream / event creation failed");
@@ -377,7 +377,7 @@ extern "C" void focr_decoder_destroy(focr_decoder_t *dec) {
     if (!dec) return;
     (void)hipSetDevice(dec->device);
     if (dec->stream) (void)hipStreamSynchronize(dec->stream);
-    for (const Stage &s : {dec->run, dec->verify, dec->test, dec->vtext, dec->stext, dec->atext, dec->ltext})
+    for (const Stage &s : {dec->run, dec->verify, dec->test, dec->vtext, dec->stext, dec->atext, dec->ltext, dec->rtext})
         for (hipEvent_t e : {s.begin, s.end})
             if (e) (void)hipEventDestroy(e);
     if (dec->stream) (void)hipStreamDestroy(dec->stream);

@@ -109,6 +109,16 @@ class TextAlign(collections.namedtuple("TextAlign", "base cost first last pens t
     __slots__ = ()
 
 
+class TextRefine(collections.namedtuple("TextRefine", "base cost_in cost sweeps changed text pens")):
+    """One line the caller supplied, repaired against the composed line error (LineDecoder.refine_text).  base: the sum of r^2
+    over the line's crop (int); cost_in, cost: the composed cost of the input and of the output (int; base + cost is the squared
+    error of the line with all its glyphs drawn together, the max of their ink); sweeps: the sweeps made; changed: the
+    characters whose glyph or pen differs from the input; text: the repaired text; pens: each character's pen in 1/64 px (a
+    uint32 array aligned with the text), which score_text(pens=), verify_text(pens=) and learn_text(pens=) take as they are."""
+
+    __slots__ = ()
+
+
 class LearnedGlyphs(collections.namedtuple("LearnedGlyphs", "sums counts used")):
     """What a trusted reading showed of a font's glyphs (LineDecoder.learn_text).  sums: the page's inverted luma summed under
     every byte of the font's bitmaps (a uint64 array in the font's own `bitmaps` layout); counts: the samples of every cell, a
@@ -133,6 +143,27 @@ def nominal_pens(font, text, start=0):
     index = {c: i for i, c in reversed(list(enumerate(font.alphabet)))}
     inc64 = [int(np.rint(np.float32(inc[index[c]]) * np.float32(64))) for c in text]
     return np.array([int(start) + sum(inc64[:g]) for g in range(len(text))], dtype=np.int64)
+
+
+def placed_pens(font, text, offsets=None):
+    """The pens at which the pen loop (offsets None) or the pen search (its offsets, 1/64 px per character) places `text` in the
+    DecodeFont `font`: the f32 walk of both (pos = pos + offset / 64, then pos + increment) and FreeType's delta
+    trunc((origin_x + pos) * 64), less 64 * origin_x, in 1/64 px: what refine_text(pens=), score_text(pens=) and verify_text(pens=)
+    take for a plain or pen_search reading.  origin_x must be a whole number >= 0, as for every pens placement."""
+    ox = font.origin[0]
+    if float(ox) != int(ox) or ox < 0:
+        raise ValueError("placed_pens needs a font whose origin_x is a whole number >= 0")
+    if offsets is not None and len(offsets) != len(text):
+        raise ValueError(f"{len(offsets)} offsets for {len(text)} characters")
+    inc = font.increments()
+    index = {c: i for i, c in reversed(list(enumerate(font.alphabet)))}
+    f32 = np.float32
+    out, pos = [], f32(0)
+    for g, c in enumerate(text):
+        p = f32(pos + f32(int(offsets[g]) if offsets is not None else 0) * f32(0.015625))
+        out.append(int(f32(f32(ox + p) * f32(64))) - 64 * int(ox))
+        pos = f32(p + inc[index[c]])
+    return np.array(out, dtype=np.int64)
 
 
 def fit_pens(nominal, pens, terms, start=None):
@@ -391,6 +422,7 @@ class LineDecoder:
         self.last_score_text_ms = 0.0
         self.last_align_text_ms = 0.0
         self.last_learn_text_ms = 0.0
+        self.last_refine_text_ms = 0.0
         for attr, _, default in _SETTINGS:
             setattr(self, attr, default)
 
@@ -657,6 +689,53 @@ class LineDecoder:
         for r, a in zip(recs, aarr):
             out.append(TextAlign(int(a.line_base), int(a.cost), int(a.first), int(a.last), parr[at: at + r[3]].copy(),
                                  tarr[at: at + r[3]].copy() if terms else None))
+            at += r[3]
+        return out
+
+    def refine_text(self, luma_pages, lines, x, width, line_height, pens, fonts=None, radius=4, sweeps=4, glyphs=True):
+        """A reading the caller supplies, repaired against the composed line error (focr_decoder_refine_text): per [page][line] a
+        TextRefine(base, cost_in, cost, sweeps, changed, text, pens).  luma_pages, lines and fonts are score_text()'s; pens (per
+        page and line one per character, 1/64 px, not decreasing within a line) are required: a whole-line run's, align_text's,
+        or placed_pens() of a plain or pen_search reading.  The line is drawn with all its glyphs together (the max of their
+        ink); a sweep visits the characters in order, and each takes the (glyph, pen offset j, -radius <= j <= radius) that lowers
+        the composed cost the most, if any does (glyphs=False: its own glyph only); at most `sweeps` sweeps, 0 only evaluates.
+        No other pen moves when a glyph with another advance is chosen.  A character outside the alphabet raises ValueError.  The
+        last decode, its results and its verify() are left as they were."""
+        if self.font is None:
+            raise DecoderError("set_font() first")
+        if pens is None:
+            raise ValueError("refine_text needs pens (placed_pens() gives a plain or pen_search reading's)")
+        if not 0 <= int(radius) <= 64:
+            raise ValueError(f"radius must be 0 .. 64 (1/64 px), not {radius!r}")
+        if not 0 <= int(sweeps) <= 8:
+            raise ValueError(f"sweeps must be 0 .. 8, not {sweeps!r}")
+        if int(width) <= 0 or int(line_height) <= 0:
+            raise ValueError("refine_text: width and line_height must be positive")
+        _, lines, _, groups = self._pack_text("refine_text", luma_pages, lines, fonts, pens, None)
+        out = [[None] * len(pg) for pg in lines]
+        for _, batch, recs, chars, along, _, where in groups:
+            got = self._refine_text(batch, recs, chars, along, x, width, line_height, radius, sweeps, glyphs)
+            for (i, q), r in zip(where, got):
+                out[i][q] = r
+        return out
+
+    def _refine_text(self, batch, recs, chars, pens, x, width, line_height, radius, sweeps, glyphs):
+        """One focr_decoder_refine_text call over an (N, H, W) uint8 batch, its arguments as _score_text's.  A TextRefine per record."""
+        n, h, w = batch.shape
+        larr = (N.TextLine * max(1, len(recs)))(*recs)
+        carr = np.array(chars, dtype=np.uint16) if chars else np.zeros(1, dtype=np.uint16)
+        parr = np.array(pens, dtype=np.uint32) if pens else np.zeros(1, dtype=np.uint32)
+        n_out = sum(r[3] for r in recs)
+        cout = np.zeros(max(1, n_out), dtype=np.uint16)
+        pout = np.zeros(max(1, n_out), dtype=np.uint32)
+        rarr = (N.TextRefineStruct * max(1, len(recs)))()
+        self._check(self._lib.focr_decoder_refine_text(self._h, _ptr(batch), 0, n, w, h, int(x), int(width), int(line_height), larr, len(recs), _ptr(carr),
+                                                       _ptr(parr), len(chars), int(radius), int(sweeps), int(bool(glyphs)), _ptr(cout), _ptr(pout), rarr))
+        self.last_refine_text_ms = float(self._lib.focr_decoder_last_refine_text_ms(self._h))
+        out, at = [], 0
+        for r, a in zip(recs, rarr):
+            text = "".join(self.font.alphabet[i] for i in cout[at: at + r[3]])
+            out.append(TextRefine(int(a.line_base), int(a.cost_in), int(a.cost), int(a.sweeps_run), int(a.changed), text, pout[at: at + r[3]].copy()))
             at += r[3]
         return out
 

@@ -761,6 +761,69 @@ uint32_t focr_decoder_last_learn_text_launches(const focr_decoder_t *dec);
 int focr_decode_font_learn(const focr_decode_font_t *base, const uint64_t *sums, const uint64_t *counts, uint32_t min_count,
                            uint32_t grow, focr_decode_font_t *out, size_t *learned, size_t *inked, char *err, size_t errlen);
 
+/* ---- device: a reading repaired against the composed line error (an extension: the step score_text above leaves out) ---- */
+
+/* Every mode minimises a sum of per-glyph footprint terms, which is the page's squared error only while footprints do not
+ * overlap: where they do, an overlap is counted once per glyph, and tight proportional text is misread (`born` for `burn`,
+ * `cIIp` for `clip`).  focr_decoder_refine_text takes a reading a run produced, holds it against the line with all its glyphs
+ * drawn together, and repairs one character at a time.  Exact integer arithmetic throughout:
+ *   - lines and chars are focr_decoder_score_text's, in any page order; the crop (x_start, width, line_height at the line's y,
+ *     clamped) and line_base are its; font k = lines[l].font is 0 or a candidate, with its own tables; pens (1/64 px, beside
+ *     chars, each below 2^24) are required, and the placement is score_text's pens placement: delta = 64 * origin_x_k + s_g,
+ *     phase delta & 63, whole-pixel shift delta >> 6, the phase bitmap clipped to the crop on all four sides: c_g(p);
+ *   - the composed canvas is v(p) = max over the line's characters of c_g(p), 0 where none reaches (the max of ink: what
+ *     np.minimum of luma draws), and with r = 255 - luma the composed cost is C = sum over p of v(p) * (v(p) - 2 r(p)), so
+ *     line_base + C = sum of (r - v)^2 >= 0; where no two glyphs put ink on one pixel C is score_text's cost;
+ *   - one step, for character g with glyph a_g at pen s_g: o(p) is the max over all characters but g as they stand now, and
+ *     with f(v) = v * (v - 2 r), D(a, j) = sum over the clipped box of glyph a at pen s_g + j of f(max(c, o)) - f(o): what the
+ *     composed cost gains when (a, j) is drawn over the others.  The candidates are every glyph a of the font (only a_g when
+ *     glyphs == 0) times j in -N ..= N, N = radius <= FOCR_PEN_SEARCH_MAX, with 0 <= s_g + j < 2^24; the incumbent is (a_g, 0).
+ *     If some candidate has D strictly below the incumbent's, character g becomes the lowest (D, rank(j), a) among the
+ *     candidates, rank the pen search's (0, -1, +1, -2, ...); otherwise it stays;
+ *   - a sweep takes g = 0 .. n - 1 in order, each step seeing the earlier steps' results; a line stops after a sweep that
+ *     changed nothing or after `sweeps` <= FOCR_REFINE_SWEEPS_MAX sweeps; sweeps == 0 only evaluates;
+ *   - a pixel's f(max(c, o)) - f(o) = (m - o) * (m + o - 2 r), m = max(c, o), is at most 2 * 255^2 in magnitude, and every font
+ *     upload refuses a glyph whose box area times 2 * 255^2 reaches 2^31: D fits an int32 and is kept in one; C, summed over the
+ *     crop, is kept in 64 bits;
+ *   - out[l] = { line_base, cost_in (C of the input), cost (C of the output), sweeps_run (the sweeps made, the one that changed
+ *     nothing included), changed (the characters whose glyph or pen differs from the input) }; chars_out and pens_out take the
+ *     output per listed character, line l's at the running sum of n_chars over the lines before it (as align_text's pens_out).
+ *     No other pen moves when a glyph with another advance is chosen.  focr_decoder_score_text, focr_decoder_verify_text and
+ *     focr_decoder_learn_text take chars_out and pens_out as they are; cost <= cost_in always.
+ * Refused, each with its own message and before anything is launched: what focr_decoder_score_text refuses of the same
+ * arguments; NULL pens, and NULL chars_out, pens_out or out where there are lines; radius or sweeps above its maximum; per line
+ * (the message names its index) a font whose origin_x is fractional or negative, pens that decrease within the line (the
+ * message names the character), a font with a glyph box more than 2^20 px from its pen; and fonts whose boxes span so many
+ * columns and rows that the window of one step does not fit a workgroup's memory.  Non-decreasing pens are what every run
+ * produces; the rule lets the kernel bound which characters can reach a step's window, since no pen moves more than
+ * sweeps * radius from a sorted input.
+ * The call runs one launch, or two when a line's strip and a step's window do not fit in LDS together (the strips are then built
+ * in global memory first), in buffers of its own: the last run, its getters, its verify and the other text calls' last timings
+ * answer as they did before, and it needs no run at all.  pages as for focr_decoder_run.  Returns when out, chars_out and
+ * pens_out are written; with n_lines == 0 nothing is launched.
+ * What it does not do: insertions and deletions (`rn` against `m` stays the whole-line decode's job); baseline candidates or
+ * line_q; a per-line x; any change to focr_decoder_run; render()'s copy rule, under which a later glyph's blank margin erases an
+ * earlier glyph's ink (that picture stays focr_decoder_verify_text's). */
+enum { FOCR_REFINE_SWEEPS_MAX = 8 };
+typedef struct focr_text_refine {
+    uint64_t line_base;   /* sum of r^2 over the line's crop, r = 255 - luma */
+    int64_t  cost_in;     /* the composed cost C of the input */
+    int64_t  cost;        /* ... and of the output */
+    uint32_t sweeps_run;  /* sweeps made */
+    uint32_t changed;     /* characters whose glyph or pen differs from the input */
+} focr_text_refine_t;
+
+int focr_decoder_refine_text(focr_decoder_t *dec, const uint8_t *pages, int pages_on_device, size_t n_pages,
+                             size_t page_w, size_t page_h, uint32_t x_start, uint32_t width, uint32_t line_height,
+                             const focr_text_line_t *lines, size_t n_lines,
+                             const uint16_t *chars, const uint32_t *pens, size_t n_chars,
+                             uint32_t radius, uint32_t sweeps, int glyphs,
+                             uint16_t *chars_out, uint32_t *pens_out, focr_text_refine_t *out);
+/* Device time of the last refine_text's kernels in ms (events), and their launch count (1, or 2 with global strips; 0 after a
+ * refusal or a call without lines). */
+float    focr_decoder_last_refine_text_ms(const focr_decoder_t *dec);
+uint32_t focr_decoder_last_refine_text_launches(const focr_decoder_t *dec);
+
 /* ---- device: test images (focr --test: draw_test_rectangles, draw_test_text, src/main.rs:241-298) ---------------- */
 
 /* focr --test's two images of each page of a batch of n_pages equal-size pages, drawn on the decoder's stream.  Both

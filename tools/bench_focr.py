@@ -128,6 +128,18 @@ what is timed is the work, not what the tables are worth), in calls that alterna
   ltext_characters            the listed characters, ltext_used those whose box lay inside their crop, ltext_cells the cells seen
   ltext_wall_ms               median host time of one call (the lines packed in Python, uploads, sums and counts read back and added in uint64)
   ltext_equal                 a second call gives the same sums and counts, and the counts add up to the used characters
+With --refine-text, also focr_decoder_refine_text (LineDecoder.refine_text) over the plain run's decoded lines at placed_pens(), at the
+(radius, sweeps) pairs (0, 0), (4, 1) and (8, 1), in calls that alternate with decode(pen_search=radius) on the same pages: one sweep
+evaluates the n * A * (2N + 1) candidates one pen-search run evaluates, so that run is the yardstick; the result also goes to
+profiles/focr_refine_text_bench.json:
+  rtext_device_ms             median device time of refine_text's launch per pair: {"0,0": .., "4,1": .., "8,1": ..}
+  rtext_device_ms_min         ... and the lowest
+  rtext_search_device_ms      median device time of the decode(pen_search=radius) runs in between (radius 0: the plain run)
+  rtext_over_search           per pair rtext_device_ms over it
+  rtext_candidates_per_character   A * (2N + 1)
+  rtext_lines_cost_in_is_score_text   the lines whose composed cost equals score_text's at the same pens (no two footprints meet)
+  rtext_characters_changed, rtext_lines_text_changed, rtext_cost_drop   per pair what the call changed, and the summed cost_in - cost
+  rtext_wall_ms               median host time of one (4, 1) call (the lines packed in Python, uploads, results read back)
 With --test-images, also focr --test's two RGBA images of the batch on the device (focr_decoder_test_images, over the
 grey pages):
   test_device_ms_per_batch    median device time of its kernels (2 x pages x 608 x 720 x 4 bytes written)
@@ -150,7 +162,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from font_ocr_amd import FOCR_DEFAULT_ALPHABET, DecodeFont, LineDecoder  # noqa: E402
-from font_ocr_amd.decoder import nominal_pens, raster_glyph, render_text  # noqa: E402
+from font_ocr_amd.decoder import nominal_pens, placed_pens, raster_glyph, render_text  # noqa: E402
 
 FONT = os.path.join(ROOT, "tests", "golden", "DejaVuSansMono.ttf")
 
@@ -221,6 +233,8 @@ def main():
     ap.add_argument("--score-text", action="store_true", help="also time score_text over the decoded lines at shift radii 0, 8 and 64 against the plain decode")
     ap.add_argument("--align-text", action="store_true", help="also time align_text over the decoded lines at (drift, step) (0, 0), (16, 2) and (128, 8) against score_text")
     ap.add_argument("--learn-text", action="store_true", help="also time learn_text over the decoded lines against score_text")
+    ap.add_argument("--refine-text", action="store_true",
+                    help="also time refine_text over the decoded lines at (radius, sweeps) (0, 0), (4, 1) and (8, 1) against decode(pen_search=radius)")
     ap.add_argument("--scores", action="store_true", help="also time the decode with per-character scores on")
     ap.add_argument("--pen-search", type=int, default=0, metavar="N", help="also time the decode with a pen search of N/64 px")
     ap.add_argument("--whole-line", action="store_true", help="also time the whole-line decode")
@@ -363,6 +377,29 @@ def main():
                 lwall.append((time.perf_counter() - t) * 1e3)
                 ldev.append(dec.last_learn_text_ms)
             llaunches = int(dec._lib.focr_decoder_last_learn_text_launches(dec._h))
+        if a.refine_text:
+            crop = (geo[0], geo[2], geo[3])
+            rpairs = ((0, 0), (4, 1), (8, 1))
+            placed = [[placed_pens(font, t) for _, t in pg] for pg in out]
+            rgot = {pr: dec.refine_text(pages, out, *crop, placed, radius=pr[0], sweeps=pr[1]) for pr in rpairs}
+            rwant = dec.score_text(pages, out, *crop, pens=placed, terms=False)
+            rsame = sum(g.cost_in == w.cost for pg, pw in zip(rgot[rpairs[0]], rwant) for g, w in zip(pg, pw))
+            for _ in range(a.warmup):
+                for n, sw in rpairs:
+                    dec.decode(pages, *geo, pen_search=n)
+                    dec.refine_text(pages, out, *crop, placed, radius=n, sweeps=sw)
+            rdev, rsdev, rwall = {pr: [] for pr in rpairs}, {pr: [] for pr in rpairs}, []
+            for _ in range(a.steps):
+                for n, sw in rpairs:
+                    dec.decode(pages, *geo, pen_search=n)
+                    rsdev[(n, sw)].append(dec.last_ms)
+                    t = time.perf_counter()
+                    dec.refine_text(pages, out, *crop, placed, radius=n, sweeps=sw)
+                    if (n, sw) == rpairs[1]:
+                        rwall.append((time.perf_counter() - t) * 1e3)
+                    rdev[(n, sw)].append(dec.last_refine_text_ms)
+            rlaunches = int(dec._lib.focr_decoder_last_refine_text_launches(dec._h))
+            dec.decode(pages, *geo)  # the plain run is the last run again
         if a.scores:
             for _ in range(a.warmup):
                 dec.decode(pages, *geo, scores=True)
@@ -555,6 +592,24 @@ def main():
                     "ltext_characters": int(sum(len(t) for pg in out for _, t in pg)), "ltext_used": n_used,
                     "ltext_cells": int((lgot.counts > 0).sum()), "ltext_wall_ms": round(float(np.median(lwall)), 3), "ltext_equal": bool(lequal)})
         with open(os.path.join(ROOT, "profiles", "focr_learn_text_bench.json"), "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+    if a.refine_text:
+        rms, rsms = {pr: float(np.median(v)) for pr, v in rdev.items()}, {pr: float(np.median(v)) for pr, v in rsdev.items()}
+        name = lambda pr: "%d,%d" % pr  # noqa: E731
+        flat = lambda got: [g for pg in got for g in pg]  # noqa: E731
+        res.update({"rtext_device_ms": {name(pr): round(v, 4) for pr, v in rms.items()},
+                    "rtext_device_ms_min": {name(pr): round(float(min(v)), 4) for pr, v in rdev.items()},
+                    "rtext_search_device_ms": {name(pr): round(v, 4) for pr, v in rsms.items()},
+                    "rtext_over_search": {name(pr): round(rms[pr] / rsms[pr], 3) for pr in rms},
+                    "rtext_candidates_per_character": {name(pr): len(FOCR_DEFAULT_ALPHABET) * (2 * pr[0] + 1) for pr in rms},
+                    "rtext_lines": len(flat(rgot[(0, 0)])), "rtext_characters": int(sum(len(g.text) for g in flat(rgot[(0, 0)]))),
+                    "rtext_lines_cost_in_is_score_text": int(rsame),
+                    "rtext_characters_changed": {name(pr): int(sum(g.changed for g in flat(got))) for pr, got in rgot.items()},
+                    "rtext_lines_text_changed": {name(pr): int(sum(g.text != t for pg, po in zip(got, out) for g, (_, t) in zip(pg, po))) for pr, got in rgot.items()},
+                    "rtext_cost_drop": {name(pr): int(sum(g.cost_in - g.cost for g in flat(got))) for pr, got in rgot.items()},
+                    "rtext_launches": rlaunches, "rtext_wall_ms": round(float(np.median(rwall)), 3)})
+        with open(os.path.join(ROOT, "profiles", "focr_refine_text_bench.json"), "w") as f:
             json.dump(res, f, indent=1, sort_keys=True)
             f.write("\n")
     if a.scores:
