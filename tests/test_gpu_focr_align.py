@@ -83,6 +83,15 @@ def test_the_widest_band(dec):
     check(dec, [noisy(70, 20, 9)], [[(1, "Hi ab")]], 2, 60, LH, start=1100, drift=1024, step=3)
 
 
+def test_wide_tiles(dec):
+    """Sans 30 px over "il.W@m": tiles of 2, 7 and 8 dwords a row (every font above is 13 px, at most 4 dwords) under a band of five
+    states, the last W cut by the crop's right edge and the tall glyphs by its bottom."""
+    font = dec.set_font(SANS, 30.0, "il.W@m")
+    dec.set_font_candidates([])
+    assert {font.s.glyphs[i].stride // 4 for i in range(6)} == {2, 7, 8}
+    check(dec, [noisy(130, 40, 17)], [[(2, "W@mil."), (9, "lmWW")]], 3, 96, 26, start=40, drift=2, step=1)
+
+
 def test_line_lengths(dec):
     """Lines of 0, 1, 64, 65 and 300 characters: the walk back and the terms' second pass over one thread, a full wave, a wave and
     a thread, the workgroup and 44.  The longest runs far past the crop: its last glyphs lie wholly right of it and cost 0, so

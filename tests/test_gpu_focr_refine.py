@@ -2,7 +2,8 @@
 against the composed line error.  Device == tests/focr_refine_model.py (the definition step by step over the phase tables the
 decoder itself was given) at the shapes the kernel branches on: the alphabet and the candidates against the workgroup's 256 lanes,
 the radius, the sweeps, the line's length against the waves, pens that lie on one another, pens at 0, crops cut on every side,
-empty and one-column crops, a candidate font, the strip in LDS and in global memory; then score_text on the device at the output
+empty and one-column crops, a candidate font, the strip in LDS and in global memory, tiles of up to 11 dwords a row (24 to 44 px),
+the table's last tile, a hinted font; then score_text on the device at the output
 pens, the page the feature is for, every refusal, the last run's getters and device memory.  Every comparison is ==."""
 import ctypes as C
 import os
@@ -189,6 +190,88 @@ def test_strip_in_lds_and_in_global_memory(dec, width, n_launches):
     fms = setup(dec, MONO, 13.0, AL)
     pens = [[[0, 300, 64 * 1500 + 7, 64 * 1500 + 300, 64 * (width - 9)], [64 * (width - 20), 64 * (width - 20) + 200]]]
     check(dec, fms, [noisy(4100, 17, 101)], [[(0, "Hmabe"), (1, "oh")]], 0, width, 16, pens, radius=2, sweeps=1, n_launches=n_launches)
+
+
+def ndws(fm):
+    """The dwords per tile row (DevGlyph.ndw, stride / 4) of every glyph of a FastModel, as the upload lays its tiles out."""
+    out = []
+    for i in range(len(fm.alphabet)):
+        g = fm.font.s.glyphs[i]
+        assert g.stride % 4 == 0 and g.stride >= fm.font.phase(i, 0)[0].shape[1] > g.stride - 4
+        out.append(g.stride // 4)
+    return out
+
+
+WIDE = {24.0: {1, 2, 6}, 30.0: {2, 7, 8}, 36.0: {2, 8, 9}, 44.0: {2, 10, 11}}
+
+
+@pytest.mark.parametrize("size", sorted(WIDE), ids=["24", "30", "36", "44"])
+def test_wide_tiles(dec, size):
+    """Tiles of more than four dwords a row: refine_term's second and third trip through a row and their partial tails (ndw 6 ..= 11;
+    every font setup above stays within 4).  Sans over "il.W@m" on noise, the pens so close that the wide glyphs lie on one another;
+    the crop cuts a W at its right edge and every tall glyph at its bottom; then the same with boxes that start 5 columns left of
+    the pen (a W at pen 0 is cut at the crop's left edge), and once with glyphs=False."""
+    al = "il.W@m"
+    fms = setup(dec, SANS, size, al)
+    assert set(ndws(fms[0])) == WIDE[size]
+    g = fms[0].font.s.glyphs
+    assert max(g[i].stride * g[i].box_h for i in range(len(al))) * 2 * 255 * 255 < 1 << 31  # the upload's box-area rule: set_font took it
+    px = int(size)
+    lh, w = px - 4, 3 * px
+    pages = [noisy(w + 9, px + 12, int(size))]
+    pens = [0, 16 * px, 40 * px, 64 * px, 64 * (w - px // 2), 64 * (w - px // 2) + 90]
+    lines, ps = [[(3, "W@mi.W"), (9, "ml@W")]], [[pens, pens[1:5]]]
+    check(dec, fms, pages, lines, 4, w, lh, ps, radius=2, sweeps=2)
+    check(dec, fms, pages, lines, 4, w, lh, ps, radius=2, sweeps=2, glyphs=False)
+    bent = FastModel(SANS, size, al)
+    for i in range(len(al)):
+        for p in range(64):
+            bent.font.s.glyphs[i].off_x[p] -= 5
+    dec.set_font(bent.font)
+    assert int(bent.font.origin[0]) + bent.font.phase(al.index("W"), 0)[1] < 0
+    check(dec, [bent], pages, lines, 4, w, lh, ps, radius=2, sweeps=2)
+    dec.set_font(fms[0].font)
+    bent.close()
+
+
+@pytest.mark.parametrize("size,al,ndw", [(13.0, "Wi", 1), (8.0, "iH", 2), (13.0, "im", 3), (17.0, "iW", 5), (20.0, "iW", 6)], ids=["1", "2", "3", "5", "6"])
+def test_last_glyph_of_the_table(dec, size, al, ndw):
+    """The table's last tile (the last glyph's phase 63) is read dword by dword where four dwords would pass the table's end: the
+    last glyph drawn at a pen of phase 63 and read as the other one, so the step's winner is that tile; narrow and wide rows."""
+    fms = setup(dec, SANS, size, al)
+    assert ndws(fms[0])[-1] == ndw and int(fms[0].font.origin[0]) == 0
+    last, other = al[1], al[0]
+    text, pens = other + last + other, [64, 64 * 30 + 63, 64 * 60]
+    page = K.draw_at(SANS, size, al, text, pens, 100, 30)
+    got = check(dec, fms, [page], [[(0, other * 3)]], 0, 100, 30, [[pens]], radius=1, sweeps=2)[0][0]
+    assert got.text == text and got.pens.tolist() == pens and got.cost == -got.base
+    check(dec, fms, [noisy(100, 30, ndw)], [[(0, other * 3), (2, last * 2)]], 0, 100, 30, [[pens, pens[1:]]], radius=1, sweeps=2)
+
+
+def test_the_neighbour_scan_allows_for_every_sweep(dec):
+    """The line of tests/test_focr_refine_fuzz_host.py on which the scan for the others that reach a step's window must allow a
+    pen radius * sweeps of movement: two `m` that come 8 px closer to each other in eight sweeps of radius 64.  With a slack of
+    one radius the right one ends at 1107 (the host test pins both results); no seeded line tells the two apart."""
+    from test_focr_refine_fuzz_host import ramp_line
+    fm, page, idx, pens = ramp_line()
+    dec.set_font(fm.font)
+    dec.set_font_candidates([])
+    got = check(dec, [fm], [page], [[(0, "mm")]], 0, page.shape[1], page.shape[0], [[pens]], radius=64, sweeps=8, glyphs=False)[0][0]
+    assert got.pens.tolist() == [596, 1279] and got.sweeps == 8 and idx == [0, 0]
+    setup(dec, SANS, 13.0, AL)
+    fm.close()
+
+
+def test_a_hinted_font_beside_a_candidate(dec):
+    """Mono 8 px hinted (learn_text's pinned setup: its phases differ from the unhinted font's in their boxes) with the unhinted
+    font as a candidate beside it, lines in both."""
+    fms = [fm_of(MONO, 8.0, AL, True), fm_of(MONO, 8.0, AL)]
+    assert fms[0].font.hinting and not fms[1].font.hinting
+    dec.set_font(fms[0].font)
+    dec.set_font_candidates([fms[1].font])
+    pages = [noisy(70, 26, 61)]
+    lines, pens = [[(2, "Hinein"), (2, "Hinein"), (11, "mohr ab")]], [[spaced(6, 290, 3), spaced(6, 290, 3), spaced(7, 250)]]
+    check(dec, fms, pages, lines, 3, 60, 12, pens, fonts=[[0, 1, 0]], radius=3, sweeps=3)
 
 
 # ---- on the device alone ------------------------------------------------------------------------------------------------------
